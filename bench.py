@@ -12,17 +12,31 @@ A "step" decodes every stripe of the rank once: compressed stream bytes are alre
 ABI before the timed region), Arrow buffers are left in HBM.
 
     python bench.py --gpus N --steps K --warmup W [--workload lineitem|c2|c2-direct|c2-delta|c2-arange|c2-adv|c2-rowgroup|c3|c5]
+                    [--full] [--dump-outputs DIR]
     N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the ranks
     are there: WORLD_SIZE = N), or plainly as `python bench.py --gpus N`: bench.py then starts N rank processes itself
     (fresh children, before anything touches the GPU) and relays rank 0's line.
 
-Prints ONE JSON line (rank 0).  `value` = whole-job decoded GB/s (Arrow bytes out of all ranks / time of the slowest
-rank).  `roofline` prices the dominant phase of the pipeline (HIP events on the decoder's own stream, per phase:
-orcgpu_last_phase_ms) against the HBM peak with the ALGORITHMIC bytes of SURVEY 8(d): staged stream bytes in + Arrow
-bytes out.  `cpu_baseline` = the CPU oracle (a C port of the reference's algorithm; the Rust reference cannot be
-built here) on a bounded sample of the same stripes on this box's host cores, 1 thread and all cores.
+A plain run does what its headline needs and no more: it generates and stages the stripes, decodes them once (status words
+checked), runs the W warm-up steps and the K timed steps, writes the outputs (--dump-outputs) and prints the line.
+`--full` adds everything else, as it always ran: the checks before timing, the CPU baseline, the staging / copy-back
+rates and the pipelined end-to-end measurement behind the timed region (demo12: the parity check against PyArrow, the
+CPU baselines, the read with read-ahead).  `--no-cpu`, `--skip-check` and `--no-e2e` leave parts of `--full` out.
 
-Checks before timing (lineitem): the first stripe of the rank is compared buffer by buffer with what the generator implies
+`--dump-outputs DIR`: after the timed steps, what the last step left in the result buffers -- the Arrow arrays a caller
+receives -- as DIR/<column>[.offsets|.bytes|.validity].npy (float64; string bytes and validity float32) + DIR/batches.npy
+(which batches: rank-local stripe, batch, rows).  A fixed, seeded sample of whole batches, all columns of each, the
+first and the last batch always among them, 64 MB in all at most.  The inputs are seeded: the same arguments give the same
+inputs in every run, so that two builds can be compared output for output.
+
+Prints ONE JSON line (rank 0).  `value` = whole-job decoded GB/s (Arrow bytes out of all ranks / time of the slowest
+rank); `ms_per_step` = milliseconds of one timed step (of the slowest rank).  `roofline` prices the dominant phase of the
+pipeline (HIP events on the decoder's own stream, per phase: orcgpu_last_phase_ms, read in the timed steps themselves)
+against the HBM peak with the ALGORITHMIC bytes of SURVEY 8(d): staged stream bytes in + Arrow bytes out.
+`cpu_baseline` (--full) = the CPU oracle (a C port of the reference's algorithm; the Rust reference cannot be built
+here) on a bounded sample of the same stripes on this box's host cores, 1 thread and all cores.
+
+Checks before timing (--full; lineitem): the first stripe of the rank is compared buffer by buffer with what the generator implies
 (workloads.check_result); EVERY stripe is compared through weighted word sums of its whole Arrow buffers (values, offsets;
 null counts must be zero): the worker process that generated a stripe reduces the expected buffers, torch reduces the
 decoded ones on the device (workloads.buffer_sum / device_sum below) -- nothing of the product is used by the checker.
@@ -109,12 +123,22 @@ def lineitem_total_rows(args, world):
     return per if args.scaling == "strong" else per * world
 
 
+def _lineitem_streams_task(task):
+    """workloads.lineitem_unit_task without the expected side (a run without the checks): (n_rows, columns, streams, {}, None)."""
+    from orc_rust_amd.gen import workloads as W
+    segment, rows, compression, column_ids, seed, _ = task
+    seg = W.lineitem_segment(segment, rows, seed, names=[W.LINEITEM[c - 1][0] for c in column_ids])
+    return W.lineitem_stripe(seg, 0, rows, compression, column_ids=column_ids, want_expect=False) + (None,)
+
+
 def build_workload(args, rank, world):
     """Returns (stripes, compression, label, shard description, plan).  stripes: [(n_rows, cols, streams, expect, sums)] of THIS rank
-    (expect: the generator's Arrow buffers, kept for the first stripe only at lineitem scale; sums: their reductions)."""
+    (expect: the generator's Arrow buffers, kept for the first stripe only at lineitem scale; sums: their reductions -- both
+    with --full only, else {} / None)."""
     from orc_rust_amd import shard
     from orc_rust_amd.gen import workloads as W
     wl = args.workload
+    check = args.full
     if wl == "lineitem":
         import multiprocessing as mp
         from orc_rust_amd import gen
@@ -132,6 +156,7 @@ def build_workload(args, rank, world):
             by_stripe.setdefault(s_, []).append(c_ + 1)
         order = sorted(by_stripe)
         tasks = [(s_, stripe_rows[s_], comp, sorted(by_stripe[s_]), 7, k == 0) for k, s_ in enumerate(order)]
+        task_fn = W.lineitem_unit_task if check else _lineitem_streams_task
         # every stripe is generated, encoded and compressed by a worker process of its own (this rank's share of the host cores)
         nproc = min(len(tasks), host_workers(world))
         if any(16 in t[3] for t in tasks):
@@ -142,12 +167,12 @@ def build_workload(args, rank, world):
             # and the run with it)
             pool = mp.get_context("fork").Pool(nproc)
             try:
-                stripes = pool.map(W.lineitem_unit_task, tasks, chunksize=1)
+                stripes = pool.map(task_fn, tasks, chunksize=1)
             finally:
                 pool.close()
                 pool.join()
         else:
-            stripes = [W.lineitem_unit_task(t) for t in tasks]
+            stripes = [task_fn(t) for t in tasks]
         gen_s = time.perf_counter() - t0
         label = ("C4: TPC-H-shaped lineitem stripes, scale factor %.4g (%d rows, 16 columns: 3 Int64, Int32, 4 Decimal128(15,2), 3 Date32, "
                  "4 dictionary Utf8, 1 direct Utf8), %s, %d-row stripes%s" % (
@@ -179,18 +204,18 @@ def build_workload(args, rank, world):
     elif wl == "c3":
         comp = args.compression or "snappy"
         for s in mine:
-            stripes.append(W.c3_stripe(min(C2_STRIPE_ROWS, rows - s * C2_STRIPE_ROWS), s, comp, index=args.row_index))
+            stripes.append(W.c3_stripe(min(C2_STRIPE_ROWS, rows - s * C2_STRIPE_ROWS), s, comp, want_expect=check, index=args.row_index))
         label = "C3: dictionary Utf8 (7 entries) + PRESENT (10 %% nulls), %d rows, %s, %d stripes" % (rows, comp, n_stripes)
         if args.row_index:
             label += ", the ROW_INDEX positions of the PRESENT and DATA streams (one per 10 000 rows) given as verified run starts"
     elif wl == "c5":
         comp = args.compression or "lz4"
         for s in mine:
-            stripes.append(W.c5_stripe(min(C2_STRIPE_ROWS, rows - s * C2_STRIPE_ROWS), s, comp)[:4])
+            stripes.append(W.c5_stripe(min(C2_STRIPE_ROWS, rows - s * C2_STRIPE_ROWS), s, comp, want_expect=check)[:4])
         label = "C5: Timestamp(ns), PATCHED_BASE seconds + DIRECT nanoseconds, %d rows, %s, %d stripes" % (rows, comp, n_stripes)
     else:
         raise SystemExit("unknown workload " + wl)
-    stripes = [tuple(st) + (None,) for st in stripes]
+    stripes = [tuple(st[:3]) + (st[3] if check else {}, None) for st in stripes]
     return stripes, comp, label, desc, {"units": [(s_, 0) for s_ in mine], "n_stripes": n_stripes, "n_columns": 1, "rows": rows,
                                         "load_estimate": [len(shard.stripe_shard(n_stripes, r, world)) for r in range(world)],
                                         "gen_s": time.perf_counter() - t0, "gen_procs": 1}
@@ -378,6 +403,87 @@ def check_sums(torch, res, cols, sums, what):
             n_entries = (nb - 1) * (stride // 4) + views[-1].length + 1
             got = device_sum(torch, views[0].offsets, 4 * n_entries)
             assert got == tuple(e["offsets"]), (what, c.get("name"), "offsets differ", got, e["offsets"])
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all the files of a run together, .npy headers included
+DUMP_SEED = 20241016
+
+
+def _column_arrays(c, p):
+    """One column-batch as a caller receives it (Result.batch: values, offsets, validity) -> {file suffix: array}: values as
+    float64 (Decimal128 from its two 64-bit halves; values under a null zeroed -- Arrow leaves them undefined), string offsets
+    float64 and their value bytes float32, validity float32 (None: no nulls in the batch)."""
+    from orc_rust_amd.gen import workloads as W
+    n = p["length"]
+    raw = np.frombuffer(p["values"], dtype=np.uint8)
+    valid = None if p["validity"] is None else np.unpackbits(np.frombuffer(p["validity"], dtype=np.uint8), bitorder="little")[:n]
+    out = {"validity": valid}
+    if p["offsets"] is not None:
+        out["offsets"] = p["offsets"][:n + 1].astype(np.float64)
+        out["bytes"] = raw.astype(np.float32)
+        return out
+    if c["orc_type"] == W.BOOLEAN:
+        v = np.unpackbits(raw, bitorder="little")[:n].astype(np.float64)
+    elif n == 0:
+        v = np.zeros(0, dtype=np.float64)
+    else:
+        width = raw.size // n
+        if c["orc_type"] in (W.FLOAT, W.DOUBLE) and width in (4, 8):
+            v = raw[:n * width].view(np.float32 if width == 4 else np.float64).astype(np.float64)
+        elif width == 16:
+            lo, hi = raw[:16 * n].view(np.int64)[0::2], raw[:16 * n].view(np.int64)[1::2]
+            v = np.where(hi == lo >> 63, lo.astype(np.float64), hi.astype(np.float64) * 18446744073709551616.0 + lo.view(np.uint64).astype(np.float64))
+        else:
+            v = raw[:n * width].view({1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}[width]).astype(np.float64)
+    if valid is not None:
+        v = np.where(valid.astype(bool), v, 0.0)
+    out["values"] = v
+    return out
+
+
+def dump_outputs(path, stripes, results, rank=0, world=1, budget=DUMP_BYTES):
+    """--dump-outputs: what the results hold after the last timed step, as .npy files under `path`.  Whole batches (every column
+    of the stripe) are taken in a fixed order -- the rank's first and last batch, then the others shuffled by DUMP_SEED -- for as
+    long as the files stay within `budget` (N ranks: budget / N each, file names prefixed rank<r>.).  batches.npy lists the batches
+    taken: (stripe of the rank, batch, rows)."""
+    os.makedirs(path, exist_ok=True)
+    budget = budget // max(1, world) - 64 * 1024  # (room for the .npy headers)
+    pairs = [(k, b) for k, r in enumerate(results) for b in range(r.n_batches)]
+    if not pairs:
+        return
+    order = [0] + ([len(pairs) - 1] if len(pairs) > 1 else [])
+    rest = np.random.default_rng(DUMP_SEED).permutation(np.arange(1, len(pairs) - 1)) if len(pairs) > 2 else []
+    order += [int(i) for i in rest]
+    parts, taken, used = {}, [], 0
+    for i in order:
+        k, b = pairs[i]
+        cols = stripes[k][1]
+        got = [_column_arrays(c, results[k].batch(b, ci)) for ci, c in enumerate(cols)]
+        n = results[k].view(b, 0).length if cols else 0
+        size = 24 + sum(a.nbytes for g in got for a in g.values() if a is not None) + 4 * n * len(cols)  # (+ validity, if a batch has none)
+        if used + size > budget:
+            break
+        used += size
+        taken.append((k, b, n))
+        for c, g in zip(cols, got):
+            name = c.get("name") or "c%d" % c["column_id"]
+            col = parts.setdefault(name, {"values": [], "offsets": [], "bytes": [], "validity": [], "rows": []})
+            for key in ("values", "offsets", "bytes"):
+                if key in g:
+                    col[key].append(g[key])
+            col["validity"].append(g["validity"])
+            col["rows"].append(len(g["offsets"]) - 1 if "offsets" in g else len(g["values"]))
+    prefix = os.path.join(path, "rank%d." % rank if world > 1 else "")
+    np.save(prefix + "batches.npy", np.array(taken, dtype=np.float64).reshape(-1, 3))
+    for name, col in parts.items():
+        if col["values"]:
+            np.save(prefix + name + ".npy", np.concatenate(col["values"]))
+        else:
+            np.save(prefix + name + ".offsets.npy", np.concatenate(col["offsets"]))
+            np.save(prefix + name + ".bytes.npy", np.concatenate(col["bytes"]))
+        if any(v is not None for v in col["validity"]):
+            np.save(prefix + name + ".validity.npy", np.concatenate(
+                [np.ones(r, dtype=np.float32) if v is None else v.astype(np.float32) for v, r in zip(col["validity"], col["rows"])]))
 
 
 def pipelined_end_to_end(ctx, stripes, comp, group=4, passes=3):
@@ -582,7 +688,7 @@ def bench_demo12(args):
     table = orc.ORCFile(path).read()
     rows, arrow_bytes, file_bytes = table.num_rows, table.nbytes, os.path.getsize(path)
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         best_pa = min(_timed(lambda: orc.ORCFile(path).read()) for _ in range(5))
         import orcfile
         import oracle_lib as O
@@ -608,14 +714,15 @@ def bench_demo12(args):
     from orc_rust_amd import ArrowReaderBuilder, capi
     ctx = capi.Context(0)
     L = ctx.L
-    # parity first: the reader's batches are the PyArrow table
-    batches = list(ArrowReaderBuilder.try_new(path, ctx).build())
-    got = pa.Table.from_batches(batches)
-    assert got.num_rows == rows
-    for name in table.schema.names:
-        g, w = got.column(name), table.column(name)
-        assert g.equals(w.cast(g.type) if g.type != w.type else w), name
-    del batches, got
+    if args.full:
+        # parity first: the reader's batches are the PyArrow table
+        batches = list(ArrowReaderBuilder.try_new(path, ctx).build())
+        got = pa.Table.from_batches(batches)
+        assert got.num_rows == rows
+        for name in table.schema.names:
+            g, w = got.column(name), table.column(name)
+            assert g.equals(w.cast(g.type) if g.type != w.type else w), name
+        del batches, got
 
     class ArrowArray(C.Structure):
         _fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offset", C.c_int64), ("n_buffers", C.c_int64), ("n_children", C.c_int64),
@@ -645,7 +752,7 @@ def bench_demo12(args):
         assert n == rows
         return dt
     modes = {}
-    for prefetch in (0, 2):
+    for prefetch in ((0, 2) if args.full else (0,)):
         for _ in range(max(1, args.warmup)):
             read_once(prefetch)
         torch.cuda.synchronize()
@@ -661,9 +768,10 @@ def bench_demo12(args):
                                   "through orcgpu_reader_* (file -> Arrow C Data batches in pinned host memory: PCIe both ways INCLUDED)" % rows,
                       "rows": rows, "stripes": 1, "batch_size": 8192, "compression": "zlib", "parallelism": "one reader, serial (prefetch 0)"},
            "mrows_per_s": round(rows / dt / 1e6, 1), "file_bytes": file_bytes, "arrow_bytes_out": arrow_bytes,
-           "ms_per_read_with_read_ahead": round(modes[2] * 1e3, 4),
            "roofline": {"bound": "hbm", "kernel": None, "achieved": round(algo / dt / 1e9, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(algo / dt / 1e9 / HBM_PEAK_GBPS, 6),
                         "traffic": None, "note": "a whole-file read, host to host: latency of one stripe's launch chain and its DEFLATE chains, not a throughput figure"}}
+    if 2 in modes:
+        out["ms_per_read_with_read_ahead"] = round(modes[2] * 1e3, 4)
     if cpu is not None:
         out["cpu_baseline"] = cpu
     print(json.dumps(out))
@@ -693,14 +801,23 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every GPU gets a one-GPU share, the table grows with N (N = 8: C4's SF100); strong: one fixed table sharded over the ranks")
     ap.add_argument("--columns", default="", help="lineitem, profiling runs: decode only these columns (1-based positions, e.g. 1,4,16) of every stripe")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--skip-check", action="store_true", help="profiling runs: skip the checks before timing")
-    ap.add_argument("--no-e2e", action="store_true", help="profiling runs: skip the pipelined host-to-host measurement behind the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the checks before timing, the CPU baseline, staging / copy-back rates, the pipelined end-to-end "
+                         "measurement (demo12: the PyArrow parity check, the CPU baselines, the read with read-ahead)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of what the last timed step computed (whole batches, all columns) as DIR/*.npy, 64 MB at most")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--skip-check", action="store_true", help="--full without the checks before timing (profiling runs)")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the pipelined host-to-host measurement behind the timed region (profiling runs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.workload == "demo12":
         if args.gpus != 1:
             raise SystemExit("--workload demo12 is a one-file, one-stripe read: one GPU")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the stripe decode workloads only (demo12's reader releases every batch it times)")
         return bench_demo12(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
@@ -716,7 +833,7 @@ def main():
     stripes, comp, label, shard_desc, plan = build_workload(args, rank, world)
     cpu = None
     cpu_helper = None
-    if rank == 0 and not args.no_cpu and stripes:
+    if rank == 0 and args.full and not args.no_cpu and stripes:
         # rank 0 only, on ITS share of the workload; timed behind the GPU work (CpuBaselineHelper: forked now, before the GPU is touched)
         cpu_helper = CpuBaselineHelper(stripes, comp)
     if world > 1:
@@ -745,12 +862,13 @@ def main():
     from orc_rust_amd import capi, shard
     from orc_rust_amd.gen import workloads as W
     ctx = capi.Context(local_rank)
-    # host buffers -> HBM (not part of `value`).  Staged twice: the first pass also pays for the pinned pieces, the copy
+    # host buffers -> HBM (not part of `value`).  --full stages twice: the first pass also pays for the pinned pieces, the copy
     # threads and the arenas (hipHostMalloc / hipMalloc); the second one, timed, finds them in the context's pools -- the
     # state a reader is in from its second stripe on.
-    for s_ in [ctx.stage(n, streams, cols, compression=comp) for n, cols, streams, _, _ in stripes]:
-        s_.free()
-    torch.cuda.synchronize()
+    if args.full:
+        for s_ in [ctx.stage(n, streams, cols, compression=comp) for n, cols, streams, _, _ in stripes]:
+            s_.free()
+        torch.cuda.synchronize()
     t_stage = time.perf_counter()
     staged = [ctx.stage(n, streams, cols, compression=comp) for n, cols, streams, _, _ in stripes]
     torch.cuda.synchronize()
@@ -770,7 +888,7 @@ def main():
         st = res.status()
         err_word |= st[0]
         assert st[0] == 0, st
-        if args.skip_check:
+        if not args.full or args.skip_check:
             continue
         if expect:
             # buffer by buffer: every decoded Arrow buffer equals what the generated values imply
@@ -817,19 +935,22 @@ def main():
     my_dt = time.perf_counter() - t0
     barrier()
     dt = time.perf_counter() - t0
-    # the way back (outside the timed region, like staging): ONE pinned device-to-host copy per result arena; timed on
-    # the second round, when the pinned host copies exist (the first one allocates them).  At table scale a sample of the
-    # stripes is fetched (pinned host memory for every result of a 13 GB table is not what a reader holds either).
-    fetch_n = min(len(results), 4)
-    for r in results[:fetch_n]:
-        r.fetch()
-    if staged:
-        ctx.decode(staged[:fetch_n], results[:fetch_n])
-    t_fetch = time.perf_counter()
-    for r in results[:fetch_n]:
-        r.fetch()
-    t_fetch = time.perf_counter() - t_fetch
-    fetch_bytes = sum(r.arrow_bytes for r in results[:fetch_n])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stripes, results, rank, world)
+    if args.full:
+        # the way back (outside the timed region, like staging): ONE pinned device-to-host copy per result arena; timed on
+        # the second round, when the pinned host copies exist (the first one allocates them).  At table scale a sample of the
+        # stripes is fetched (pinned host memory for every result of a 13 GB table is not what a reader holds either).
+        fetch_n = min(len(results), 4)
+        for r in results[:fetch_n]:
+            r.fetch()
+        if staged:
+            ctx.decode(staged[:fetch_n], results[:fetch_n])
+        t_fetch = time.perf_counter()
+        for r in results[:fetch_n]:
+            r.fetch()
+        t_fetch = time.perf_counter() - t_fetch
+        fetch_bytes = sum(r.arrow_bytes for r in results[:fetch_n])
     string_bytes = sum(sum((len(e["values"]) if "values" in e else 0) for cid, e in expect.items() if "lengths" in e) for _, _, _, expect, _ in stripes)
     unit_rows = sum(n * len(cols) for n, cols, _, _, _ in stripes)  # rows x columns this rank decoded
     my_ms = my_dt / args.steps * 1e3
@@ -846,7 +967,7 @@ def main():
         assert sum(c[0] for c in allc) == plan["rows"] * plan["n_columns"], "decoded rows do not add up: %s" % allc
         total_rows = plan["rows"]
         tot_load = float(sum(plan["load_estimate"])) or 1.0
-        per_rank = [{"rows_x_columns": c[0], "string_bytes": c[1], "arrow_bytes": c[2], "stream_bytes": c[3], "units": c[4],
+        per_rank = [{"rows_x_columns": c[0], "string_bytes": c[1] if args.full else None, "arrow_bytes": c[2], "stream_bytes": c[3], "units": c[4],
                      "ms_per_step": c[6] / 1e3, "load_estimate_frac": round(plan["load_estimate"][r] / tot_load, 4)} for r, c in enumerate(allc)]
     else:
         total_rows, total_arrow, total_stream = rows, arrow_bytes, stream_bytes
@@ -855,10 +976,8 @@ def main():
     value = total_arrow / (dt / args.steps) / 1e9
     phase = {k: v / args.steps for k, v in phase.items()}
     roof = roofline_of(lane_acc, comp, args.workload, stream_bytes + arrow_bytes)
-    e2e_dt, e2e_bytes = pipelined_end_to_end(ctx, stripes, comp) if len(stripes) >= 2 and not args.no_e2e else (0.0, 0)
-    h2d = stream_bytes / t_stage / 1e9 if t_stage > 0 else None
-    d2h = fetch_bytes / t_fetch / 1e9 if t_fetch > 0 and fetch_bytes else None
-    serial_s = (t_stage + dt / args.steps + (arrow_bytes / (d2h * 1e9) if d2h else 0.0))
+    if args.full:
+        e2e_dt, e2e_bytes = pipelined_end_to_end(ctx, stripes, comp) if len(stripes) >= 2 and not args.no_e2e else (0.0, 0)
     out = {
         "metric": "decoded GB/s + Mrows/s into Arrow, TPC-H lineitem stripe" if args.workload == "lineitem" else "decoded GB/s + Mrows/s into Arrow",
         "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -871,23 +990,30 @@ def main():
         "stream_bytes_in": total_stream, "arrow_bytes_out": total_arrow,
         "device_ms_per_step": round(tot_ms / args.steps, 4),
         "phase_ms": {k: round(v, 4) for k, v in phase.items()},
-        # staging the host stream buffers is outside the timed region; the PCIe-inclusive rates are reported for DESIGN.md only
-        "h2d_stage_ms": round(t_stage * 1e3, 3), "h2d_GBps": round(h2d, 2) if h2d else None,
-        "d2h_fetch_sample": "%d of %d stripes" % (fetch_n, len(results)), "d2h_GBps": round(d2h, 2) if d2h else None,
-        "pcie_inclusive_GBps": round(arrow_bytes / (t_stage + dt / args.steps) / 1e9, 2),
-        "end_to_end_serial_GBps": round(arrow_bytes / serial_s / 1e9, 2),
-        # host stream buffers in, pinned host Arrow buffers out: a staging thread, four stripes per decode call, copies back on
-        # their own stream (stage k + 1 / decode k / copy back k - 1 overlap): measured, see pipelined_end_to_end
-        "end_to_end_GBps": round(e2e_bytes / e2e_dt / 1e9, 2) if e2e_dt > 0 else None,
-        "end_to_end_ms_per_stripe": round(e2e_dt / len(stripes) * 1e3, 3) if e2e_dt > 0 else None,
-        "setup": {"generate_s": round(plan["gen_s"], 2), "generate_procs": plan["gen_procs"], "check_s": round(t_check, 2),
-                  "checked": "skipped" if args.skip_check else ("first stripe buffer by buffer + every stripe by whole-buffer sums" if args.workload == "lineitem" else "every stripe buffer by buffer")},
+        "setup": {"generate_s": round(plan["gen_s"], 2), "generate_procs": plan["gen_procs"], "checked": "status words only (--full: the checks)"},
         # device memory in use at the end of the run (staged streams, workspace, results, pinned mirrors do not count): what decides
         # which table sizes fit one GPU's 288 GB
         "hbm_bytes_in_use": (lambda fr_to: int(fr_to[1] - fr_to[0]))(torch.cuda.mem_get_info()),
         "roofline": dict(roof, whole_step_frac=round((stream_bytes + arrow_bytes) / (my_dt / args.steps) / 1e9 / HBM_PEAK_GBPS, 4)),
         "lanes": lanes_of(lane_acc),
     }
+    if args.full:
+        h2d = stream_bytes / t_stage / 1e9 if t_stage > 0 else None
+        d2h = fetch_bytes / t_fetch / 1e9 if t_fetch > 0 and fetch_bytes else None
+        serial_s = (t_stage + dt / args.steps + (arrow_bytes / (d2h * 1e9) if d2h else 0.0))
+        out.update({
+            # staging the host stream buffers is outside the timed region; the PCIe-inclusive rates are reported for DESIGN.md only
+            "h2d_stage_ms": round(t_stage * 1e3, 3), "h2d_GBps": round(h2d, 2) if h2d else None,
+            "d2h_fetch_sample": "%d of %d stripes" % (fetch_n, len(results)), "d2h_GBps": round(d2h, 2) if d2h else None,
+            "pcie_inclusive_GBps": round(arrow_bytes / (t_stage + dt / args.steps) / 1e9, 2),
+            "end_to_end_serial_GBps": round(arrow_bytes / serial_s / 1e9, 2),
+            # host stream buffers in, pinned host Arrow buffers out: a staging thread, four stripes per decode call, copies back on
+            # their own stream (stage k + 1 / decode k / copy back k - 1 overlap): measured, see pipelined_end_to_end
+            "end_to_end_GBps": round(e2e_bytes / e2e_dt / 1e9, 2) if e2e_dt > 0 else None,
+            "end_to_end_ms_per_stripe": round(e2e_dt / len(stripes) * 1e3, 3) if e2e_dt > 0 else None,
+        })
+        out["setup"].update({"check_s": round(t_check, 2),
+                             "checked": "skipped" if args.skip_check else ("first stripe buffer by buffer + every stripe by whole-buffer sums" if args.workload == "lineitem" else "every stripe buffer by buffer")})
     if per_rank is not None:
         out["per_rank"] = per_rank
     if rank == 0:

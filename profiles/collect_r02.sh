@@ -6,13 +6,13 @@ O=$R/gpurun_out/r02
 rm -rf $O; mkdir -p $O
 cd $R
 # 1. the driver's line: default workload (lineitem SF1, Zstandard), CPU baseline included
-python bench.py > $O/bench_line.json 2> $O/bench_line.err
+python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 # 2. one bench line + one kernel table per workload / codec
 cd /tmp && export TMPDIR=/tmp
 run() {  # tag, bench args...
   tag=$1; shift
-  ( cd $R && python bench.py "$@" --steps 10 --warmup 3 --no-cpu 2> $O/$tag.err | tail -1 > $O/line_$tag.json )
-  ( cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$tag -- python3 bench.py "$@" --steps 5 --warmup 2 --no-cpu --skip-check > /dev/null 2> $O/prof_$tag.err )
+  ( cd $R && python bench.py --full "$@" --steps 10 --warmup 3 --no-cpu 2> $O/$tag.err | tail -1 > $O/line_$tag.json )
+  ( cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$tag -- python3 bench.py --full "$@" --steps 5 --warmup 2 --no-cpu --skip-check > /dev/null 2> $O/prof_$tag.err )
   f=$(find $O/raw_$tag -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/kernel_stats_$tag.csv
   rm -rf $O/raw_$tag
@@ -26,7 +26,7 @@ run c5_lz4 --workload c5 --compression lz4
 # 3. HBM traffic of the headline and of C3 / C2: FETCH_SIZE and WRITE_SIZE in passes of their own (no trace domains beside --kernel-trace)
 pmc() {  # tag, counter, bench args...
   tag=$1; cnt=$2; shift; shift
-  ( cd $R && rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $O/raw_pmc -- python3 bench.py "$@" --steps 2 --warmup 1 --no-cpu --skip-check > /dev/null 2> $O/pmc_${tag}_$cnt.err )
+  ( cd $R && rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $O/raw_pmc -- python3 bench.py --full "$@" --steps 2 --warmup 1 --no-cpu --skip-check > /dev/null 2> $O/pmc_${tag}_$cnt.err )
   f=$(find $O/raw_pmc -name '*counter_collection.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/pmc_${tag}_$cnt.csv
   rm -rf $O/raw_pmc

@@ -8,17 +8,17 @@ O=$R/gpurun_out/r04c
 rm -rf $O; mkdir -p $O
 cd $R
 # 1. the driver's line: default workload (lineitem, one GPU's share of SF100 = SF 12.5, Zstandard), CPU baseline included
-timeout 900 python bench.py > $O/bench_line.json 2> $O/bench_line.err
+timeout 900 python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 # 2. where GB/s saturates: scale factors 1 .. 50 of the same table
 for sf in 1 2 4 8 12.5 25 50; do
-  timeout 900 python bench.py --sf $sf --steps 5 --warmup 2 --no-cpu --no-e2e 2> $O/sf_$sf.err | tail -1 > $O/sf_$sf.json
+  timeout 900 python bench.py --full --sf $sf --steps 5 --warmup 2 --no-cpu --no-e2e 2> $O/sf_$sf.err | tail -1 > $O/sf_$sf.json
 done
 # 3. one bench line + one kernel table per workload / codec
 cd /tmp && export TMPDIR=/tmp
 run() {  # tag, bench args...
   tag=$1; shift
-  ( cd $R && timeout 600 python bench.py "$@" --steps 10 --warmup 3 --no-cpu 2> $O/$tag.err | tail -1 > $O/line_$tag.json )
-  ( cd $R && timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$tag -- python3 bench.py "$@" --steps 5 --warmup 2 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/prof_$tag.err )
+  ( cd $R && timeout 600 python bench.py --full "$@" --steps 10 --warmup 3 --no-cpu 2> $O/$tag.err | tail -1 > $O/line_$tag.json )
+  ( cd $R && timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$tag -- python3 bench.py --full "$@" --steps 5 --warmup 2 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/prof_$tag.err )
   f=$(find $O/raw_$tag -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/kernel_stats_$tag.csv
   rm -rf $O/raw_$tag
@@ -34,7 +34,7 @@ for c in none snappy zstd lz4 zlib; do run c3_$c --workload c3 --compression $c;
 for c in none snappy; do run c3_${c}_index --workload c3 --compression $c --row-index; done
 run c5_lz4 --workload c5 --compression lz4
 # 3b. the timeline of one headline step (kernel, queue, start, end): what runs beside what
-( cd $R && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/raw_trace -- python3 bench.py --steps 4 --warmup 3 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/prof_trace.err )
+( cd $R && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/raw_trace -- python3 bench.py --full --steps 4 --warmup 3 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/prof_trace.err )
 f=$(find $O/raw_trace -name '*kernel_trace.csv' | head -1)
 [ -n "$f" ] && python3 - "$f" > $O/timeline_lineitem_zstd.txt <<'PY'
 import csv, sys
@@ -56,7 +56,7 @@ rm -rf $O/raw_trace
 #    their own (no trace domain beside --kernel-trace), each bounded
 pmc() {  # tag, counter, bench args...
   tag=$1; cnt=$2; shift; shift
-  ( cd $R && timeout 420 rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $O/raw_pmc -- python3 bench.py "$@" --steps 2 --warmup 1 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/pmc_${tag}_$cnt.err )
+  ( cd $R && timeout 420 rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $O/raw_pmc -- python3 bench.py --full "$@" --steps 2 --warmup 1 --no-cpu --skip-check --no-e2e > /dev/null 2> $O/pmc_${tag}_$cnt.err )
   f=$(find $O/raw_pmc -name '*counter_collection.csv' | head -1)
   [ -n "$f" ] && cp "$f" $O/pmc_${tag}_$cnt.csv
   rm -rf $O/raw_pmc
@@ -66,7 +66,7 @@ for cnt in FETCH_SIZE WRITE_SIZE; do
   pmc c3_none $cnt --workload c3 --compression none
   pmc c2 $cnt --workload c2
 done
-( cd $R && timeout 300 python bench.py --workload lineitem --compression zstd --sf 4 --steps 5 --warmup 2 --no-cpu --no-e2e 2> /dev/null | tail -1 > $O/line_lineitem_zstd_sf4.json )
+( cd $R && timeout 300 python bench.py --full --workload lineitem --compression zstd --sf 4 --steps 5 --warmup 2 --no-cpu --no-e2e 2> /dev/null | tail -1 > $O/line_lineitem_zstd_sf4.json )
 # the counter files are large (one row per dispatch): keep per-kernel averages only
 python3 - $O <<'PY'
 import csv, sys, glob, json, collections, os

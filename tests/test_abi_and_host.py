@@ -123,7 +123,7 @@ from orc_rust_amd import shard
 rank = int(os.environ["RANK"]); world = int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
 # the multi-rank path of bench.py up to the point where a GPU is needed: this rank's units, their stripes, the all-gather
-args = types.SimpleNamespace(workload="lineitem", rows=30000, sf=0.0, scaling="weak", compression="none")
+args = types.SimpleNamespace(workload="lineitem", rows=30000, sf=0.0, scaling="weak", compression="none", full=True)
 stripes, comp, label, desc, plan = bench.build_workload(args, rank, world)
 assert plan["rows"] == 30000 * world and plan["n_columns"] == 16
 unit_rows = sum(n * len(cols) for n, cols, _, _, _ in stripes)
