@@ -435,6 +435,40 @@ typedef struct orcgpu_enc_stream {
 int orcgpu_encode_column(orcgpu_ctx* ctx, const orcgpu_enc_column* col, orcgpu_enc_stream streams[3], uint32_t* n_streams);
 int orcgpu_encode_fetch(orcgpu_ctx* ctx, const orcgpu_enc_stream* stream, uint8_t* out);
 
+/* ---- ArrowWriterBuilder / ArrowWriter (src/arrow_writer.rs:34-156) ----------------------------------------------------------
+ * Arrow record batches -> an ORC file, byte for byte the reference writer's: a flat schema of Boolean, Int8..Int64, Float32/64,
+ * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no compression, index or statistics.  Every stream is
+ * encoded on the device (the encoders above); a stripe is cut where the reference's would be (after a slice of batch_size rows
+ * whose summed encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.
+ * schema: an Arrow struct ("+s") of the fields.  Another type than those: ORCGPU_UNSUPPORTED at open (the reference panics).
+ * write: the batch as an Arrow struct array with the schema it was exported with; a schema that differs from the writer's (names,
+ * types, nullability, metadata): ORCGPU_UNEXPECTED.  ORCGPU_ENC_ON_DEVICE: the buffers are device memory of ctx's device (the
+ * GPU reader's batches, orcgpu_result_batch_view).  What the writer needs is copied before it returns.
+ * close: the open stripe (if it holds rows) and the tail; any call on the writer but take_bytes / stats / free after it:
+ * ORCGPU_INVALID_ARGUMENT.  take_bytes (memory sink): out = NULL reports how many bytes wait; then drains them. */
+typedef struct orcgpu_writer orcgpu_writer;
+typedef struct orcgpu_writer_opts {
+  uint32_t batch_size;        /* 0: 1024 */
+  uint32_t pad;
+  uint64_t stripe_byte_size;  /* 0: 64 MiB */
+} orcgpu_writer_opts;
+typedef struct orcgpu_writer_counts {
+  uint64_t stripes, rows;     /* written so far */
+  uint64_t bytes;             /* of the file so far */
+  uint64_t round_trips;       /* host waits for the device of the writer so far: synchronisations, and the growth of its device
+                                 buffers (a free waits for the device) */
+  uint64_t stripe_round_trips;/* ... of them, those of the stripes' encoding and copy (two a stripe once the buffers have grown) */
+} orcgpu_writer_counts;
+int orcgpu_writer_open_file(orcgpu_ctx* ctx, const char* path, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out);
+int orcgpu_writer_open_bytes(orcgpu_ctx* ctx, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out);
+int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* schema, const struct ArrowArray* batch, uint32_t flags);
+int orcgpu_writer_flush_stripe(orcgpu_writer* w);
+int orcgpu_writer_close(orcgpu_writer* w);
+int orcgpu_writer_take_bytes(orcgpu_writer* w, uint8_t* out, uint64_t cap, uint64_t* len);
+int orcgpu_writer_stats(const orcgpu_writer* w, orcgpu_writer_counts* out);
+uint64_t orcgpu_writer_stripe_rows(const orcgpu_writer* w, uint64_t stripe);  /* rows of a written stripe (0 past the last) */
+void orcgpu_writer_free(orcgpu_writer* w);
+
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) ---------------------- */
 /* Milliseconds the device spent in the last orcgpu_decode_staged call, whole call and the RLE
  * expansion kernels alone (the dominant kernel), measured with hipEvents on the ctx stream. */

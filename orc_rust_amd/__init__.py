@@ -4,5 +4,6 @@ csrc/, reached through the C ABI of include/orcgpu.h; this package is the thin P
 used by the tests and the benchmark."""
 from . import capi  # noqa: F401
 from .arrow_reader import ArrowReader, ArrowReaderBuilder  # noqa: F401
+from .arrow_writer import ArrowWriter, ArrowWriterBuilder  # noqa: F401
 
-__all__ = ["capi", "ArrowReader", "ArrowReaderBuilder"]
+__all__ = ["capi", "ArrowReader", "ArrowReaderBuilder", "ArrowWriter", "ArrowWriterBuilder"]

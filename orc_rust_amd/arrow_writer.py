@@ -1,0 +1,144 @@
+"""ArrowWriterBuilder / ArrowWriter: the reference's writer API (src/arrow_writer.rs:34-156) over the C ABI
+(`orcgpu_writer_*`).  Pure plumbing: batches go over through the Arrow C Data Interface, every stream is encoded on the GPU.
+
+    w = ArrowWriterBuilder("out.orc", schema).with_batch_size(1024).with_stripe_byte_size(64 << 20).try_build()
+    w.write(batch)          # pyarrow.RecordBatch
+    w.flush_stripe()
+    w.close()
+
+`sink` is a path, or a binary file object: that is fed from the library's memory sink after every write, flush and at close.
+"""
+import ctypes as C
+
+from . import capi
+
+DEFAULT_BATCH_SIZE = 1024            # arrow_writer.rs:49
+DEFAULT_STRIPE_BYTE_SIZE = 64 << 20  # arrow_writer.rs:51
+
+_SCHEMA_BYTES, _ARRAY_BYTES, _RELEASE_AT = 72, 80, {72: 56, 80: 64}  # struct ArrowSchema / ArrowArray, offset of `release`
+
+
+class _Exported:
+    """A pyarrow object exported to a C struct, released on exit."""
+
+    def __init__(self, size):
+        self.buf = (C.c_uint8 * size)()
+        self.size = size
+
+    @property
+    def addr(self):
+        return C.addressof(self.buf)
+
+    def release(self):
+        release = C.cast(self.addr + _RELEASE_AT[self.size], C.POINTER(C.CFUNCTYPE(None, C.c_void_p)))[0]
+        if release:
+            release(self.addr)
+
+
+def _export_schema(schema):
+    s = _Exported(_SCHEMA_BYTES)
+    schema._export_to_c(s.addr)
+    return s
+
+
+class ArrowWriterBuilder:
+    def __init__(self, sink, schema, ctx=None):
+        self._sink, self._schema, self._ctx = sink, schema, ctx
+        self._batch_size, self._stripe_byte_size = DEFAULT_BATCH_SIZE, DEFAULT_STRIPE_BYTE_SIZE
+
+    def with_batch_size(self, n):
+        self._batch_size = int(n)
+        return self
+
+    def with_stripe_byte_size(self, n):
+        self._stripe_byte_size = int(n)
+        return self
+
+    def try_build(self):
+        if self._batch_size <= 0 or self._batch_size >= 1 << 32:
+            raise ValueError("batch_size must be in 1 .. 2^32 - 1")
+        if self._stripe_byte_size <= 0:  # (the C ABI reads 0 as the default)
+            raise ValueError("stripe_byte_size must be positive")
+        ctx = self._ctx or capi.Context(0)
+        opts = capi.WriterOpts(self._batch_size, 0, self._stripe_byte_size)
+        s = _export_schema(self._schema)
+        out = C.c_void_p()
+        try:
+            if isinstance(self._sink, (str, bytes)) or hasattr(self._sink, "__fspath__"):
+                import os
+                path = os.fsencode(self._sink)
+                ctx._check(ctx.L.orcgpu_writer_open_file(ctx.h, path, s.addr, C.byref(opts), C.byref(out)))
+                fobj = None
+            else:
+                ctx._check(ctx.L.orcgpu_writer_open_bytes(ctx.h, s.addr, C.byref(opts), C.byref(out)))
+                fobj = self._sink
+        finally:
+            s.release()
+        w = ArrowWriter(ctx, out.value, self._schema, fobj)
+        w._drain()
+        return w
+
+
+class ArrowWriter:
+    def __init__(self, ctx, handle, schema, fobj):
+        self._ctx, self._h, self.schema, self._fobj = ctx, handle, schema, fobj
+
+    def _check(self, rc):
+        self._ctx._check(rc)
+
+    def _drain(self):
+        if self._fobj is None or not self._h:
+            return
+        n = C.c_uint64()
+        self._check(self._ctx.L.orcgpu_writer_take_bytes(self._h, None, 0, C.byref(n)))
+        if n.value:
+            buf = (C.c_uint8 * n.value)()
+            self._check(self._ctx.L.orcgpu_writer_take_bytes(self._h, buf, n.value, C.byref(n)))
+            self._fobj.write(bytes(buf))
+
+    def write(self, batch):
+        """ArrowWriter::write: a pyarrow.RecordBatch (its schema must equal the writer's)."""
+        s = _export_schema(batch.schema)
+        a = _Exported(_ARRAY_BYTES)
+        try:
+            batch._export_to_c(a.addr)
+            try:
+                self.write_c(s.addr, a.addr, 0)
+            finally:
+                a.release()
+        finally:
+            s.release()
+
+    def write_c(self, schema_addr, array_addr, flags=0):
+        """The C ABI call: an exported ArrowSchema / ArrowArray (flags capi.ENC_ON_DEVICE: device buffers)."""
+        self._check(self._ctx.L.orcgpu_writer_write(self._h, schema_addr, array_addr, flags))
+        self._drain()
+
+    def flush_stripe(self):
+        self._check(self._ctx.L.orcgpu_writer_flush_stripe(self._h))
+        self._drain()
+
+    def close(self):
+        """Writes the open stripe (if it holds rows) and the file's tail.  stats() stay readable until free()."""
+        self._check(self._ctx.L.orcgpu_writer_close(self._h))
+        self._drain()
+
+    def stats(self):
+        c = capi.WriterCounts()
+        self._check(self._ctx.L.orcgpu_writer_stats(self._h, C.byref(c)))
+        return {k: getattr(c, k) for k, _ in capi.WriterCounts._fields_}
+
+    def stripe_rows(self):
+        n = self.stats()["stripes"]
+        return [self._ctx.L.orcgpu_writer_stripe_rows(self._h, i) for i in range(n)]
+
+    def free(self):
+        if self._h:
+            self._ctx.L.orcgpu_writer_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -27,6 +27,8 @@ EXPORTS = [
     "orcgpu_predicate_row_groups",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
+    "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
+    "orcgpu_writer_take_bytes", "orcgpu_writer_stats", "orcgpu_writer_stripe_rows", "orcgpu_writer_free",
 ]
 
 
@@ -105,6 +107,15 @@ def timezone_offsets(name, instants):
 class EncColumn(C.Structure):
     _fields_ = [("arrow_type", C.c_int32), ("flags", C.c_uint32), ("n_rows", C.c_uint64), ("validity", C.c_void_p), ("values", C.c_void_p),
                 ("offsets", C.c_void_p)]
+
+
+class WriterOpts(C.Structure):
+    _fields_ = [("batch_size", C.c_uint32), ("pad", C.c_uint32), ("stripe_byte_size", C.c_uint64)]
+
+
+class WriterCounts(C.Structure):
+    _fields_ = [("stripes", C.c_uint64), ("rows", C.c_uint64), ("bytes", C.c_uint64), ("round_trips", C.c_uint64),
+                ("stripe_round_trips", C.c_uint64)]
 
 
 class EncStream(C.Structure):
@@ -215,6 +226,16 @@ def load():
     L.orcgpu_reader_column_name.restype = C.c_char_p
     L.orcgpu_reader_column_name.argtypes = [C.c_void_p, C.c_uint32]
     L.orcgpu_reader_next_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orcgpu_writer_open_file.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(WriterOpts), C.POINTER(C.c_void_p)]
+    L.orcgpu_writer_open_bytes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(WriterOpts), C.POINTER(C.c_void_p)]
+    L.orcgpu_writer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.orcgpu_writer_flush_stripe.argtypes = [C.c_void_p]
+    L.orcgpu_writer_close.argtypes = [C.c_void_p]
+    L.orcgpu_writer_take_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.orcgpu_writer_stats.argtypes = [C.c_void_p, C.POINTER(WriterCounts)]
+    L.orcgpu_writer_stripe_rows.restype = C.c_uint64
+    L.orcgpu_writer_stripe_rows.argtypes = [C.c_void_p, C.c_uint64]
+    L.orcgpu_writer_free.argtypes = [C.c_void_p]
     _lib = L
     return L
 

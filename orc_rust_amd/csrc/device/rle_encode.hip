@@ -513,7 +513,9 @@ __device__ __forceinline__ void enc2_plan_coop(const void* values, int int_bytes
 }
 
 extern "C" __global__ void __launch_bounds__(256) enc2_plan_kernel(const void* values, int int_bytes, int is_signed, const uint16_t* next16, const uint32_t* runs,
-                                                                   uint32_t n_runs, EncRun* recs, uint32_t* run_bytes, uint32_t rpw) {
+                                                                   uint32_t n_runs, EncRun* recs, uint32_t* run_bytes, uint32_t rpw,
+                                                                   const uint64_t* d_n_runs) {
+  if (d_n_runs) n_runs = (uint32_t)*d_n_runs;  // (the grid covers the most runs there can be)
   __shared__ uint32_t lds[4][96];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   uint32_t* hist = lds[wave];
@@ -692,7 +694,8 @@ __device__ __forceinline__ void enc2_emit_coop(const void* values, int int_bytes
 }
 
 extern "C" __global__ void __launch_bounds__(256) enc2_emit_kernel(const void* values, int int_bytes, int is_signed, const EncRun* recs, const uint64_t* offsets,
-                                                                   uint32_t n_runs, uint8_t* out, uint32_t rpw) {
+                                                                   uint32_t n_runs, uint8_t* out, uint32_t rpw, const uint64_t* d_n_runs) {
+  if (d_n_runs) n_runs = (uint32_t)*d_n_runs;
   __shared__ uint32_t lds32[4][64];
   __shared__ uint64_t lds64[4][32];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -739,7 +742,8 @@ extern "C" __global__ void __launch_bounds__(256) enc2_emit_kernel(const void* v
 // ---------------------------------------------------------------------------------------------------------------------------
 // byte RLE: write_run / write_literals (byte.rs:176-197); a wavefront per 64 runs, literals copied by the wavefront
 extern "C" __global__ void __launch_bounds__(256) enc1_emit_kernel(const uint8_t* values, const uint16_t* next16, const uint32_t* runs, const uint64_t* offsets,
-                                                                   uint32_t n_runs, uint8_t* out) {
+                                                                   uint32_t n_runs, uint8_t* out, const uint64_t* d_n_runs) {
+  if (d_n_runs) n_runs = (uint32_t)*d_n_runs;
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t r = blockIdx.x * 256 + threadIdx.x;
   uint32_t start = 0, e16 = 0;
@@ -850,4 +854,118 @@ extern "C" __global__ void __launch_bounds__(256) enc_copy_strings_kernel(const 
   const int64_t hi = offset_bytes == 4 ? ((const int32_t*)offsets)[row + 1] : ((const int64_t*)offsets)[row + 1];
   const uint64_t d = row_dst[row];
   for (int64_t i = lane; i < hi - lo; i += 64) out[d + i] = data[lo + i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the stripe writer (orcgpu_writer.inc): Arrow arrays brought to the form the encoders take, and ArrowWriter::write's stripe cut
+// (arrow_writer.rs:103-124) from the run tables of enc_plan.
+
+// n bits from bit `bit_off` of src, to dst from bit 0 (the last byte's spare bits zero); src == nullptr: all set
+extern "C" __global__ void __launch_bounds__(256) wr_bits_kernel(const uint8_t* src, uint64_t bit_off, uint64_t n_bits, uint8_t* dst) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t nb = (n_bits + 7) / 8;
+  if (i >= nb) return;
+  uint32_t x = 0xff;
+  if (src) {
+    const uint64_t b = bit_off + i * 8;
+    const uint32_t sh = (uint32_t)(b & 7);
+    const uint64_t byte = b >> 3;
+    x = src[byte] >> sh;
+    // (the next byte only when bits of it are wanted: never read past the last bit's byte)
+    if (sh && bit_off + n_bits > (byte + 1) * 8) x |= (uint32_t)src[byte + 1] << (8 - sh);
+  }
+  if (i == nb - 1 && (n_bits & 7)) x &= (1u << (n_bits & 7)) - 1;
+  dst[i] = (uint8_t)x;
+}
+
+// a bitmap (bit 0 first) -> one 0 / 1 byte per bit
+extern "C" __global__ void __launch_bounds__(256) wr_bits_to_bytes_kernel(const uint8_t* bits, uint64_t n, uint8_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = (bits[i >> 3] >> (i & 7)) & 1;
+}
+
+// per slice of batch_size rows: the valid rows and (strings) their value bytes from the batch's first row to the slice's end.
+// word_off: exclusive scan of the bitmap's 64-row popcounts; row_dst / vlen: exclusive scan of the valid rows' lengths, lengths
+extern "C" __global__ void __launch_bounds__(256) wr_slice_counts_kernel(const uint8_t* validity, const uint64_t* word_off, const uint64_t* row_dst,
+                                                                         const uint32_t* vlen, uint64_t n_rows, uint64_t batch_size, uint64_t n_slices,
+                                                                         uint64_t* cum_valid, uint64_t* cum_bytes) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_slices) return;
+  const uint64_t end = (j + 1) * batch_size < n_rows ? (j + 1) * batch_size : n_rows;  // >= 1
+  const uint64_t last = end - 1, wi = last >> 6;
+  uint64_t word = 0;
+  const uint64_t nb = (n_rows + 7) / 8;
+  for (uint32_t k = 0; k < 8; k++) word |= wi * 8 + k < nb ? (uint64_t)validity[wi * 8 + k] << (8 * k) : 0;
+  const uint32_t keep = (uint32_t)(last & 63) + 1;
+  if (keep < 64) word &= (1ull << keep) - 1;
+  cum_valid[j] = word_off[wi] + (uint64_t)__builtin_popcountll(word);
+  cum_bytes[j] = row_dst ? row_dst[last] + vlen[last] : 0;
+}
+
+// The value at which the greedy encoder writes each run out (rle_v2/mod.rs:284-360, byte.rs:47-114).  Behind every run the
+// encoder's state is a fresh one's at the run's end, so with [s, e) a run of the orbit (enc_runs_kernel):
+//   repeats (three equal values at s):  e - 1 when it reached its longest (512 / 130), else e (the value that breaks it);
+//   literals:                           e - 1 when they reached their longest (512 / 128), else e + 2 (the third of the equal values
+//                                       that end them);
+//   the last run, unless it reached its longest, only by finish(): never (~0).
+template <int KIND>
+__global__ void __launch_bounds__(256) wr_triggers_kernel(const void* values, int int_bytes, const uint32_t* runs, const uint64_t* d_n_runs, uint64_t n,
+                                                          uint64_t* trig) {
+  const uint32_t n_runs = (uint32_t)*d_n_runs;
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_runs) return;
+  const uint64_t s = runs[i], e = i + 1 < n_runs ? runs[i + 1] : n, len = e - s;
+  const bool last = i + 1 == n_runs;
+  bool rep = false;
+  if (s + 2 < n) {
+    if (KIND == 0) {
+      const int64_t a = enc_ld(values, s, int_bytes);
+      rep = a == enc_ld(values, s + 1, int_bytes) && a == enc_ld(values, s + 2, int_bytes);
+    } else {
+      const uint8_t* v = (const uint8_t*)values;
+      rep = v[s] == v[s + 1] && v[s] == v[s + 2];
+    }
+  }
+  const uint64_t longest = rep ? (KIND == 0 ? 512u : 130u) : (KIND == 0 ? 512u : 128u);
+  uint64_t t;
+  if (len == longest) t = e - 1;
+  else if (last) t = ~0ull;
+  else t = rep ? e : e + 2;
+  trig[i] = t;
+}
+
+// EstimateMemory of the encoder after `counts[j] + adjust` values, added to est[j]: the bytes of the runs written out by then
+// (RleV2Encoder: data.len(), rle_v2/mod.rs:398), and for byte RLE the values it holds besides (num_literals, byte.rs:150).
+// trig is non-decreasing (a run of literals cut short is followed by a run of three repeats or more).
+extern "C" __global__ void __launch_bounds__(256) wr_estimate_kernel(const uint64_t* trig, const uint32_t* runs, const uint32_t* run_bytes, const uint64_t* offsets,
+                                                                     const uint64_t* d_n_runs, int byte_rle, const uint64_t* counts, int64_t adjust,
+                                                                     uint64_t n_slices, uint64_t* est) {
+  const uint32_t n_runs = (uint32_t)*d_n_runs;
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_slices) return;
+  const uint64_t c = (uint64_t)((int64_t)counts[j] + adjust);
+  uint32_t lo = 0, hi = n_runs;  // k = how many runs have trig < c
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (trig[mid] < c) lo = mid + 1;
+    else hi = mid;
+  }
+  uint64_t b = lo ? offsets[lo - 1] + run_bytes[lo - 1] : 0;
+  if (byte_rle && lo < n_runs) b += c - runs[lo];
+  est[j] += b;
+}
+
+// the valid rows' bytes one behind the other, as enc_copy_strings_kernel, but never at or past `cap`: the offsets are the caller's,
+// checked (enc_lengths_kernel's `bad`) only when the write's counts come back
+extern "C" __global__ void __launch_bounds__(256) wr_copy_strings_kernel(const uint8_t* validity, const void* offsets, int offset_bytes, uint64_t n_rows,
+                                                                         const uint64_t* row_dst, const uint8_t* data, uint8_t* out, uint64_t cap) {
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (row >= n_rows) return;
+  if (!((validity[row >> 3] >> (row & 7)) & 1)) return;
+  const int64_t lo = offset_bytes == 4 ? ((const int32_t*)offsets)[row] : ((const int64_t*)offsets)[row];
+  const int64_t hi = offset_bytes == 4 ? ((const int32_t*)offsets)[row + 1] : ((const int64_t*)offsets)[row + 1];
+  const uint64_t d = row_dst[row];
+  for (int64_t i = lane; i < hi - lo && d + (uint64_t)i < cap; i += 64) out[d + i] = data[lo + i];
 }

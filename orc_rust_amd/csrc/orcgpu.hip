@@ -1228,3 +1228,4 @@ struct SummaryLayout {
 #include "orcgpu_select.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_encode.inc"
+#include "orcgpu_writer.inc"

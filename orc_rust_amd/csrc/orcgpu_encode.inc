@@ -15,6 +15,11 @@ struct EncJob {          // one stream through the pipeline: planned (sizes know
   uint32_t* run_bytes = nullptr;
   EncRun* recs = nullptr;
   uint64_t* offsets = nullptr;
+  // deferred (the stripe writer): no host waits -- tables sized for n runs, the run count and the size stay on the device
+  bool deferred = false;
+  const uint64_t* d_n_runs = nullptr;
+  const uint64_t* d_total = nullptr;
+  uint64_t* syncs = nullptr;  // counts the host waits of the plan (and the growth of its tables, which waits too)
 };
 
 #define ENC_TRY(expr)                                                                                   \
@@ -59,6 +64,7 @@ int enc_plan(orcgpu_ctx* ctx, EncJob& J) {
   }
   const uint64_t o_tile_runs = A.take((uint64_t)cnt[0] * 4), o_tile_off = A.take((uint64_t)cnt[0] * 8);
   const uint64_t o_sums = A.take(((uint64_t)cnt[0] / 2048 + 2) * 8), o_total = A.take(16);
+  if (J.syncs && A.off + kAlign > ctx->enc_a.cap) ++*J.syncs;
   if (!ctx->enc_a.ensure(A.off + kAlign)) {
     set_err(ctx, "encode: out of device memory (%llu bytes of chain tables)", (unsigned long long)A.off);
     return ORCGPU_HIP_ERROR;
@@ -90,9 +96,12 @@ int enc_plan(orcgpu_ctx* ctx, EncJob& J) {
                    (uint32_t*)nullptr, (uint32_t*)nullptr));
   int rc = enc_scan(ctx, st, d_tile_runs, cnt[0], d_sums, d_total, d_tile_off);
   if (rc) return rc;
-  uint64_t n_runs = 0;
-  ENC_TRY(hipMemcpyAsync(&n_runs, d_total, 8, hipMemcpyDeviceToHost, st));
-  ENC_TRY(hipStreamSynchronize(st));
+  uint64_t n_runs = J.n;  // deferred: as many as there can be
+  if (!J.deferred) {
+    ENC_TRY(hipMemcpyAsync(&n_runs, d_total, 8, hipMemcpyDeviceToHost, st));
+    ENC_TRY(hipStreamSynchronize(st));
+    if (J.syncs) ++*J.syncs;
+  }
   if (!n_runs || n_runs > J.n) {
     set_err(ctx, "encode: %llu runs for %llu values", (unsigned long long)n_runs, (unsigned long long)J.n);
     return ORCGPU_UNEXPECTED;
@@ -101,6 +110,7 @@ int enc_plan(orcgpu_ctx* ctx, EncJob& J) {
   Bump B;
   const uint64_t o_runs = B.take(n_runs * 4), o_bytes = B.take(n_runs * 4), o_recs = B.take(J.kind == 0 ? n_runs * sizeof(EncRun) : 8);
   const uint64_t o_offs = B.take(n_runs * 8), o_sums2 = B.take((n_runs / 2048 + 2) * 8), o_total2 = B.take(16);
+  if (J.syncs && B.off + kAlign > ctx->enc_b.cap) ++*J.syncs;
   if (!ctx->enc_b.ensure(B.off + kAlign)) {
     set_err(ctx, "encode: out of device memory (%llu bytes of run tables)", (unsigned long long)B.off);
     return ORCGPU_HIP_ERROR;
@@ -110,22 +120,27 @@ int enc_plan(orcgpu_ctx* ctx, EncJob& J) {
   J.run_bytes = (uint32_t*)(b + o_bytes);
   J.recs = (EncRun*)(b + o_recs);
   J.offsets = (uint64_t*)(b + o_offs);
+  J.d_n_runs = J.deferred ? d_total : nullptr;
+  if (J.deferred) ENC_TRY(hipMemsetAsync(J.run_bytes, 0, n_runs * 4, st));  // (the runs past the count add nothing to the scan)
   if (J.kind == 0) {
     ENC_TRY(launch(enc_runs_kernel<0>, tile_wgs, true, 256, st, (const uint16_t*)J.next16, J.n, (const uint16_t*)ent(0), cnt[0], d_tile_runs, (const uint64_t*)d_tile_off,
                    J.runs, J.run_bytes));
     // runs per wavefront: short runs are settled by a lane each (64 of them), long literals one after the other by the wavefront (4)
-    J.rpw = J.n / n_runs >= 128 ? 4u : (J.n / n_runs >= 32 ? 16u : 64u);
+    J.rpw = J.deferred ? 64u : (J.n / n_runs >= 128 ? 4u : (J.n / n_runs >= 32 ? 16u : 64u));
     const uint64_t wgs = (n_runs + 4ull * J.rpw - 1) / (4ull * J.rpw);
     ENC_TRY(launch(enc2_plan_kernel, wgs, true, 256, st, J.values, J.int_bytes, J.is_signed, (const uint16_t*)J.next16, (const uint32_t*)J.runs, J.n_runs, J.recs,
-                   J.run_bytes, J.rpw));
+                   J.run_bytes, J.rpw, J.d_n_runs));
   } else {
     ENC_TRY(launch(enc_runs_kernel<1>, tile_wgs, true, 256, st, (const uint16_t*)J.next16, J.n, (const uint16_t*)ent(0), cnt[0], d_tile_runs, (const uint64_t*)d_tile_off,
                    J.runs, J.run_bytes));
   }
   rc = enc_scan(ctx, st, J.run_bytes, n_runs, (uint64_t*)(b + o_sums2), (uint64_t*)(b + o_total2), J.offsets);
   if (rc) return rc;
+  J.d_total = (const uint64_t*)(b + o_total2);
+  if (J.deferred) return ORCGPU_OK;  // (J.total unknown: the caller's room is its bound)
   ENC_TRY(hipMemcpyAsync(&J.total, b + o_total2, 8, hipMemcpyDeviceToHost, st));
   ENC_TRY(hipStreamSynchronize(st));
+  if (J.syncs) ++*J.syncs;
   return ORCGPU_OK;
 }
 
@@ -135,10 +150,11 @@ int enc_emit(orcgpu_ctx* ctx, const EncJob& J, uint8_t* d_out) {
   hipStream_t st = ctx->stream;
   if (J.kind == 0) {
     const uint64_t wgs = ((uint64_t)J.n_runs + 4ull * J.rpw - 1) / (4ull * J.rpw);
-    ENC_TRY(launch(enc2_emit_kernel, wgs, true, 256, st, J.values, J.int_bytes, J.is_signed, (const EncRun*)J.recs, (const uint64_t*)J.offsets, J.n_runs, d_out, J.rpw));
+    ENC_TRY(launch(enc2_emit_kernel, wgs, true, 256, st, J.values, J.int_bytes, J.is_signed, (const EncRun*)J.recs, (const uint64_t*)J.offsets, J.n_runs, d_out, J.rpw,
+                   J.d_n_runs));
   } else {
     ENC_TRY(launch(enc1_emit_kernel, ((uint64_t)J.n_runs + 255) / 256, true, 256, st, (const uint8_t*)J.values, (const uint16_t*)J.next16, (const uint32_t*)J.runs,
-                   (const uint64_t*)J.offsets, J.n_runs, d_out));
+                   (const uint64_t*)J.offsets, J.n_runs, d_out, J.d_n_runs));
   }
   return ORCGPU_OK;
 }

@@ -1,0 +1,902 @@
+// orcgpu_writer.inc -- ArrowWriterBuilder / ArrowWriter (src/arrow_writer.rs:34-156) over the device encoders of orcgpu_encode.inc:
+// Arrow record batches (C Data Interface, host or device buffers) -> ORC files, byte for byte the reference's.
+//
+// What the writer holds on the device between calls, per column of the open stripe: the rows' presence (a byte each), the valid
+// rows' values in the width the column's encoder takes them (Boolean: a byte each; strings: their lengths) and the strings' bytes.
+// A stripe is encoded when it is flushed: every stream of every column through enc_plan / enc_emit, back to back in the stripe's
+// stream order (writer/stripe.rs:128-150) in one device buffer, and brought to the host in one copy.
+//
+// The stripe cut (arrow_writer.rs:103-124: after every slice of batch_size rows, flush when the summed estimate exceeds
+// stripe_byte_size) is computed, not replayed: the columns' estimates at every slice end follow from counts of valid values and
+// bytes (wr_slice_counts_kernel) and, for the run-length encoded columns, from the run table of the stripe's values so far
+// (wr_triggers_kernel: when each run is written out; wr_estimate_kernel: the bytes written out by each slice end).  Slices whose
+// estimate cannot exceed the limit by an upper bound of the encoders' output are taken without that analysis; past them the
+// analysed window grows geometrically.
+namespace {
+
+// the buffer keeps its contents when it grows (stream-ordered copy)
+struct DevVec {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  bool reserve(size_t n, size_t used, hipStream_t st) {
+    if (n <= cap) return true;
+    size_t want = std::max<size_t>(n + n / 2, 1u << 16);
+    uint8_t* q = nullptr;
+    if (hipMalloc((void**)&q, want) != hipSuccess) return false;
+    if (used && hipMemcpyAsync(q, p, used, hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+    if (p) {
+      (void)hipStreamSynchronize(st);
+      (void)hipFree(p);
+    }
+    p = q;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// a protobuf message being written: the fields in the order they are added (prost writes them in declaration order)
+struct PbOut {
+  std::vector<uint8_t> b;
+  void varint(uint64_t v) {
+    while (v >= 0x80) {
+      b.push_back((uint8_t)(v | 0x80));
+      v >>= 7;
+    }
+    b.push_back((uint8_t)v);
+  }
+  void key(uint32_t field, uint32_t wire) { varint(((uint64_t)field << 3) | wire); }
+  void u64(uint32_t field, uint64_t v) {
+    key(field, 0);
+    varint(v);
+  }
+  void bytes(uint32_t field, const void* p, size_t n) {
+    key(field, 2);
+    varint(n);
+    b.insert(b.end(), (const uint8_t*)p, (const uint8_t*)p + n);
+  }
+  void msg(uint32_t field, const PbOut& m) { bytes(field, m.b.data(), m.b.size()); }
+  void packed(uint32_t field, const std::vector<uint64_t>& v) {  // [packed = true]: nothing at all when empty
+    if (v.empty()) return;
+    PbOut m;
+    for (uint64_t x : v) m.varint(x);
+    bytes(field, m.b.data(), m.b.size());
+  }
+};
+
+struct WrStripe {
+  uint64_t offset, data_length, footer_length, rows;
+};
+
+struct WrCol {
+  int elem = 0;        // bytes of a value as the column's value encoder takes it (Boolean: a byte; strings: the offset width)
+  bool is_string = false;
+  int stream_kind = 0; // 0 Integer RLE v2 (signed), 1 byte RLE, 2 raw floats, 3 Boolean, 4 strings (bytes + unsigned RLE v2 lengths)
+  int orc_kind = 0;    // Type.Kind
+  int encoding = 0;    // ColumnEncoding.Kind
+  std::string name;
+  bool present = false;  // sticky once an array with a validity bitmap arrived (writer/column.rs:103-139)
+  uint64_t rows = 0, n_valid = 0, n_bytes = 0;  // of the open stripe
+  uint64_t base_valid = 0;                       // values of the stripe when orcgpu_writer::base_rle was found
+  DevVec pres, vals, data;
+  // this write call's batch, in the same form
+  DevBuf b_bits, b_pres, b_vals, b_data, b_tmp;
+};
+
+struct WrField {  // what ArrowWriter::write compares (batch.schema() == self.schema)
+  std::string format, name, metadata;
+  int64_t flags;
+};
+
+}  // namespace
+
+struct orcgpu_writer {
+  orcgpu_ctx* ctx = nullptr;
+  FILE* f = nullptr;
+  bool to_memory = false;
+  std::vector<uint8_t> mem;  // the memory sink's bytes not drained yet
+  bool closed = false, failed = false;
+  uint64_t batch_size = 1024, stripe_byte_size = 64ull << 20;
+  std::vector<WrCol> cols;
+  std::vector<WrField> fields;
+  std::string root_metadata;
+  int64_t root_flags = 0;
+  uint64_t written = 3;  // bytes in the file so far ("ORC")
+  uint64_t rows = 0;     // of the open stripe (StripeWriter::row_count)
+  std::vector<WrStripe> stripes;
+  uint64_t round_trips = 0, stripe_round_trips = 0, window_hint = 16;
+  DevBuf slice_counts, est, trig, lens, bits;
+  uint64_t bits_at = 0;
+  DevVec out, slots;
+  // what the size analysis knows exactly: the run-length encoded columns' summed estimate when each column had base_valid values
+  uint64_t base_rle = 0;
+  uint8_t* pinned = nullptr;
+  size_t pinned_cap = 0;
+};
+
+namespace {
+
+#define WR_TRY(expr)                                                                                    \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) {                                                                             \
+      set_err(ctx, "writer: %s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return ORCGPU_HIP_ERROR;                                                                          \
+    }                                                                                                   \
+  } while (0)
+
+int wr_sync(orcgpu_writer* w) {
+  orcgpu_ctx* ctx = w->ctx;
+  w->round_trips++;
+  WR_TRY(hipStreamSynchronize(ctx->stream));
+  return ORCGPU_OK;
+}
+
+int wr_sink(orcgpu_writer* w, const uint8_t* p, size_t n) {
+  if (!n) return ORCGPU_OK;
+  if (w->to_memory) {
+    w->mem.insert(w->mem.end(), p, p + n);
+  } else if (fwrite(p, 1, n, w->f) != n) {
+    set_err(w->ctx, "writer: cannot write %zu bytes", n);
+    return ORCGPU_IO_ERROR;
+  }
+  w->written += n;
+  return ORCGPU_OK;
+}
+
+// Arrow C schema metadata: int32 count, then (int32 length, bytes) twice per pair -> its bytes
+std::string wr_metadata(const char* m) {
+  if (!m) return std::string();
+  int32_t n;
+  memcpy(&n, m, 4);
+  size_t off = 4;
+  for (int32_t i = 0; i < 2 * n; i++) {
+    int32_t len;
+    memcpy(&len, m + off, 4);
+    off += 4 + (size_t)len;
+  }
+  return std::string(m, off);
+}
+
+// the column writer of an Arrow type (writer/stripe.rs:173-187, arrow_writer.rs:158-222); false: the reference's unimplemented!()
+bool wr_column_of(const char* fmt, WrCol& c) {
+  if (!fmt || !fmt[0] || fmt[1]) return false;
+  switch (fmt[0]) {
+    case 'b': c.elem = 1; c.stream_kind = 3; c.orc_kind = 0; c.encoding = 0; return true;
+    case 'c': c.elem = 1; c.stream_kind = 1; c.orc_kind = 1; c.encoding = 0; return true;
+    case 's': c.elem = 2; c.stream_kind = 0; c.orc_kind = 2; c.encoding = 2; return true;
+    case 'i': c.elem = 4; c.stream_kind = 0; c.orc_kind = 3; c.encoding = 2; return true;
+    case 'l': c.elem = 8; c.stream_kind = 0; c.orc_kind = 4; c.encoding = 2; return true;
+    case 'f': c.elem = 4; c.stream_kind = 2; c.orc_kind = 5; c.encoding = 0; return true;
+    case 'g': c.elem = 8; c.stream_kind = 2; c.orc_kind = 6; c.encoding = 0; return true;
+    case 'u': c.elem = 4; c.stream_kind = 4; c.orc_kind = 7; c.encoding = 2; c.is_string = true; return true;
+    case 'U': c.elem = 8; c.stream_kind = 4; c.orc_kind = 7; c.encoding = 2; c.is_string = true; return true;
+    case 'z': c.elem = 4; c.stream_kind = 4; c.orc_kind = 8; c.encoding = 2; c.is_string = true; return true;
+    case 'Z': c.elem = 8; c.stream_kind = 4; c.orc_kind = 8; c.encoding = 2; c.is_string = true; return true;
+    default: return false;
+  }
+}
+
+int wr_read_schema(orcgpu_ctx* ctx, const ArrowSchema* s, std::vector<WrField>& fields, std::string& md, int64_t& flags) {
+  if (!s || !s->format || strcmp(s->format, "+s") != 0 || s->n_children < 0 || (s->n_children && !s->children)) {
+    set_err(ctx, "writer: the schema must be an Arrow struct (format \"+s\") of its fields");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  fields.clear();
+  for (int64_t i = 0; i < s->n_children; i++) {
+    const ArrowSchema* c = s->children[i];
+    if (!c || !c->format) return ORCGPU_INVALID_ARGUMENT;
+    fields.push_back(WrField{c->format, c->name ? c->name : "", wr_metadata(c->metadata), c->flags});
+    if (c->n_children || c->dictionary) fields.back().format += "#nested";  // (nested / dictionary types: never a writer's)
+  }
+  md = wr_metadata(s->metadata);
+  flags = s->flags;
+  return ORCGPU_OK;
+}
+
+// the schema's columns and the options (the sink is the caller's)
+int wr_prepare(orcgpu_ctx* ctx, const ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer* w) {
+  w->ctx = ctx;
+  int rc = wr_read_schema(ctx, schema, w->fields, w->root_metadata, w->root_flags);
+  if (rc) return rc;
+  for (auto& fd : w->fields) {
+    WrCol c;
+    if (!wr_column_of(fd.format.c_str(), c)) {
+      set_err(ctx, "writer: unsupported Arrow type '%s' of field '%s' (the reference: unimplemented!(\"unsupported datatype\"), writer/stripe.rs:186)",
+              fd.format.c_str(), fd.name.c_str());
+      return ORCGPU_UNSUPPORTED;
+    }
+    c.name = fd.name;
+    w->cols.push_back(std::move(c));
+  }
+  if (opts && opts->batch_size) w->batch_size = opts->batch_size;
+  if (opts && opts->stripe_byte_size) w->stripe_byte_size = opts->stripe_byte_size;
+  return ORCGPU_OK;
+}
+
+// ArrowWriterBuilder::try_build: the magic "ORC" first (arrow_writer.rs:73-75)
+int wr_start(std::unique_ptr<orcgpu_writer>& w, orcgpu_writer** out) {
+  static const uint8_t magic[3] = {'O', 'R', 'C'};
+  w->written = 0;
+  int rc = wr_sink(w.get(), magic, 3);
+  if (rc) return rc;
+  *out = w.release();
+  return ORCGPU_OK;
+}
+
+// an upper bound of an encoded stream of n values (RLE v2: a run of one value is 2 header bytes + the value, a DELTA of three
+// values a header, two varints of up to 10 bytes and the packed delta, PATCHED_BASE adds its patch list; byte RLE: a header byte
+// per value and the value)
+inline uint64_t wr_stream_bound(int kind, int int_bytes, uint64_t n) { return kind == 1 ? 2 * n + 2 : (uint64_t)(3 * int_bytes + 12) * n + 64; }
+
+// DevBuf::ensure waits for the device when it grows (hipFree): counted
+bool wr_ensure(orcgpu_writer* w, DevBuf& b, uint64_t n) {
+  if (n > b.cap) w->round_trips++;
+  return b.ensure(n);
+}
+bool wr_reserve(orcgpu_writer* w, DevVec& v, uint64_t n, uint64_t used) {
+  if (n > v.cap && v.p) w->round_trips++;
+  return v.reserve(n, used, w->ctx->stream);
+}
+
+// one stream of the stripe, enqueued: values (device) through the encoder into the slot at *at of w->slots (room: its bound);
+// its length lands in d_lens[li] on the device
+int wr_rle_stream(orcgpu_writer* w, int kind, const void* d_values, uint64_t n, int int_bytes, int is_signed, uint64_t* at, uint64_t li) {
+  orcgpu_ctx* ctx = w->ctx;
+  uint64_t* d_lens = (uint64_t*)w->lens.p;
+  if (!n) {
+    WR_TRY(hipMemsetAsync(d_lens + li, 0, 8, ctx->stream));
+    return ORCGPU_OK;
+  }
+  EncJob J;
+  J.kind = kind;
+  J.int_bytes = int_bytes;
+  J.is_signed = is_signed;
+  J.n = n;
+  J.values = d_values;
+  J.deferred = true;
+  J.syncs = &w->round_trips;
+  int rc = enc_plan(ctx, J);
+  if (rc) return rc;
+  const uint64_t room = wr_stream_bound(kind, int_bytes, n);
+  if (!wr_reserve(w, w->slots, *at + room + kAlign, *at)) {
+    set_err(ctx, "writer: out of device memory (%llu bytes of stripe)", (unsigned long long)(*at + room));
+    return ORCGPU_HIP_ERROR;
+  }
+  rc = enc_emit(ctx, J, w->slots.p + *at);
+  if (rc) return rc;
+  WR_TRY(hipMemcpyAsync(d_lens + li, J.d_total, 8, hipMemcpyDeviceToDevice, ctx->stream));
+  *at += align_up(room);
+  return ORCGPU_OK;
+}
+
+// a bitmap of n bits given as 0 / 1 bytes through BooleanEncoder (boolean.rs:157-169)
+int wr_bool_stream(orcgpu_writer* w, const uint8_t* d_bytes, uint64_t n, uint64_t* at, uint64_t li) {
+  orcgpu_ctx* ctx = w->ctx;
+  const uint64_t nb = (n + 7) / 8;
+  // (the bitmaps of every Boolean / PRESENT stream of the stripe stay until it is written: one region each, at *at of `bits`)
+  const uint64_t o = w->bits_at;
+  w->bits_at += align_up(2 * nb + 16);
+  if (w->bits_at > w->bits.cap) return ORCGPU_UNEXPECTED;
+  uint8_t* bits = w->bits.p + o;
+  uint8_t* rev = bits + align_up(nb + 8);
+  WR_TRY(launch(enc_bytes_to_bits_kernel, nb, false, 256, ctx->stream, d_bytes, n, bits));
+  WR_TRY(launch(enc_bool_bytes_kernel, nb, false, 256, ctx->stream, (const uint8_t*)bits, n, rev));
+  return wr_rle_stream(w, 1, rev, nb, 1, 0, at, li);
+}
+
+// DATA of floats and strings: the bytes themselves (the length is known on the host)
+int wr_copy_stream(orcgpu_writer* w, const uint8_t* d_src, uint64_t n, uint64_t* at, uint64_t li, std::vector<uint64_t>& known) {
+  orcgpu_ctx* ctx = w->ctx;
+  if (!wr_reserve(w, w->slots, *at + n + kAlign, *at)) return ORCGPU_HIP_ERROR;
+  if (n) WR_TRY(hipMemcpyAsync(w->slots.p + *at, d_src, n, hipMemcpyDeviceToDevice, ctx->stream));
+  known[li] = n;
+  *at += align_up(n);
+  return ORCGPU_OK;
+}
+
+// StripeWriter::finish_stripe (writer/stripe.rs:109-165) + ArrowWriter::flush_stripe.  Every stream of every column is enqueued
+// without a host wait, each into a slot of its bound; then two waits, whatever the column count: the streams' lengths come back,
+// and the streams, moved back to back on the device, reach the host in one copy.
+int wr_flush(orcgpu_writer* w) {
+  orcgpu_ctx* ctx = w->ctx;
+  const uint64_t trips0 = w->round_trips;
+  struct St {
+    int kind;
+    uint32_t column;
+    uint64_t slot;
+  };
+  std::vector<St> streams;
+  // room: the lengths, the bitmaps of the Boolean / PRESENT streams
+  uint64_t n_streams = 0, bits_room = 0;
+  for (auto& c : w->cols) {
+    n_streams += 1 + (c.stream_kind == 4) + c.present;
+    if (c.stream_kind == 3) bits_room += align_up(2 * ((c.n_valid + 7) / 8) + 16);
+    if (c.present) bits_room += align_up(2 * ((c.rows + 7) / 8) + 16);
+  }
+  if (!wr_ensure(w, w->lens, n_streams * 8 + kAlign) || !wr_ensure(w, w->bits, bits_room + kAlign)) return ORCGPU_HIP_ERROR;
+  w->bits_at = 0;
+  std::vector<uint64_t> known(n_streams, ~0ull);
+  uint64_t at = 0;
+  int rc = ORCGPU_OK;
+  for (size_t ci = 0; ci < w->cols.size(); ci++) {
+    WrCol& c = w->cols[ci];
+    const uint32_t column = (uint32_t)ci + 1;
+    uint64_t li = streams.size();
+    streams.push_back(St{1, column, at});
+    switch (c.stream_kind) {
+      case 0: rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 1, &at, li); break;
+      case 1: rc = wr_rle_stream(w, 1, c.vals.p, c.n_valid, 1, 0, &at, li); break;
+      case 2: rc = wr_copy_stream(w, c.vals.p, c.n_valid * (uint64_t)c.elem, &at, li, known); break;
+      case 3: rc = wr_bool_stream(w, c.vals.p, c.n_valid, &at, li); break;
+      default: rc = wr_copy_stream(w, c.data.p, c.n_bytes, &at, li, known); break;
+    }
+    if (rc) return rc;
+    if (c.stream_kind == 4) {
+      li = streams.size();
+      streams.push_back(St{2, column, at});
+      rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li);
+      if (rc) return rc;
+    }
+    if (c.present) {
+      li = streams.size();
+      streams.push_back(St{0, column, at});
+      rc = wr_bool_stream(w, c.pres.p, c.rows, &at, li);
+      if (rc) return rc;
+    }
+  }
+  std::vector<uint64_t> lens(n_streams, 0);
+  if (n_streams) WR_TRY(hipMemcpyAsync(lens.data(), w->lens.p, n_streams * 8, hipMemcpyDeviceToHost, ctx->stream));
+  rc = wr_sync(w);
+  if (rc) return rc;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < n_streams; i++) {
+    if (known[i] != ~0ull) lens[i] = known[i];
+    total += lens[i];
+  }
+  // back to back in the stripe's stream order, then one copy to pinned memory
+  if (!wr_reserve(w, w->out, total + kAlign, 0)) return ORCGPU_HIP_ERROR;
+  uint64_t pos = 0;
+  for (uint64_t i = 0; i < n_streams; i++) {
+    if (lens[i]) WR_TRY(hipMemcpyAsync(w->out.p + pos, w->slots.p + streams[i].slot, lens[i], hipMemcpyDeviceToDevice, ctx->stream));
+    pos += lens[i];
+  }
+  if (total > w->pinned_cap) {
+    if (w->pinned) (void)hipHostFree(w->pinned);
+    w->pinned = nullptr;
+    w->pinned_cap = 0;
+    w->round_trips++;  // (hipHostMalloc / hipHostFree wait for the device)
+    WR_TRY(hipHostMalloc((void**)&w->pinned, total + total / 2, 0));
+    w->pinned_cap = total + total / 2;
+  }
+  if (total) WR_TRY(hipMemcpyAsync(w->pinned, w->out.p, total, hipMemcpyDeviceToHost, ctx->stream));
+  rc = wr_sync(w);
+  if (rc) return rc;
+  PbOut footer;
+  for (uint64_t i = 0; i < n_streams; i++) {
+    PbOut m;
+    m.u64(1, (uint64_t)streams[i].kind);
+    m.u64(2, streams[i].column);
+    m.u64(3, lens[i]);
+    footer.msg(1, m);
+  }
+  for (size_t ci = 0; ci <= w->cols.size(); ci++) {
+    PbOut m;
+    m.u64(1, ci ? (uint64_t)w->cols[ci - 1].encoding : 0u);
+    footer.msg(2, m);
+  }
+  const uint64_t start = w->written;
+  rc = wr_sink(w, w->pinned, total);
+  if (rc) return rc;
+  rc = wr_sink(w, footer.b.data(), footer.b.size());
+  if (rc) return rc;
+  w->stripes.push_back(WrStripe{start, total, footer.b.size(), w->rows});
+  w->rows = 0;
+  for (auto& c : w->cols) c.rows = c.n_valid = c.n_bytes = 0;
+  w->base_rle = 0;
+  for (auto& c : w->cols) c.base_valid = 0;
+  w->stripe_round_trips += w->round_trips - trips0;
+  return ORCGPU_OK;
+}
+
+// the tail: Footer, PostScript, the PostScript's length (arrow_writer.rs:130-156, :224-262)
+int wr_close(orcgpu_writer* w) {
+  PbOut types_root;
+  types_root.u64(1, 12);  // STRUCT
+  std::vector<uint64_t> sub;
+  for (size_t i = 0; i < w->cols.size(); i++) sub.push_back(i + 1);
+  types_root.packed(2, sub);
+  for (auto& c : w->cols) types_root.bytes(3, c.name.data(), c.name.size());
+  PbOut footer;
+  uint64_t body = 0, rows = 0;
+  for (auto& s : w->stripes) {
+    body += s.data_length + s.footer_length;
+    rows += s.rows;
+  }
+  footer.u64(1, 3);
+  footer.u64(2, body + 3);
+  for (auto& s : w->stripes) {
+    PbOut m;
+    m.u64(1, s.offset);
+    m.u64(2, 0);
+    m.u64(3, s.data_length);
+    m.u64(4, s.footer_length);
+    m.u64(5, s.rows);
+    footer.msg(3, m);
+  }
+  footer.msg(4, types_root);
+  for (auto& c : w->cols) {
+    PbOut t;
+    t.u64(1, (uint64_t)c.orc_kind);
+    footer.msg(4, t);
+  }
+  footer.u64(6, rows);
+  footer.u64(9, 0xffffffffull);
+  PbOut ps;
+  ps.u64(1, footer.b.size());
+  ps.u64(2, 0);  // CompressionKind::None
+  ps.packed(4, {0, 12});
+  ps.u64(5, 0);
+  ps.u64(6, 0xffffffffull);
+  ps.bytes(8000, "ORC", 3);
+  int rc = wr_sink(w, footer.b.data(), footer.b.size());
+  if (rc) return rc;
+  rc = wr_sink(w, ps.b.data(), ps.b.size());
+  if (rc) return rc;
+  const uint8_t len = (uint8_t)ps.b.size();
+  return wr_sink(w, &len, 1);
+}
+
+// an upper bound of what a column's value encoder can count for n values (written out or pending)
+inline uint64_t wr_bound(const WrCol& c, uint64_t n) { return wr_stream_bound(c.stream_kind == 1 ? 1 : 0, c.elem, n); }
+
+}  // namespace
+
+extern "C" int orcgpu_writer_open_file(orcgpu_ctx* ctx, const char* path, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out) {
+  if (!ctx || !path || !schema || !out) return ORCGPU_INVALID_ARGUMENT;
+  *out = nullptr;
+  auto w = std::make_unique<orcgpu_writer>();
+  int rc = wr_prepare(ctx, schema, opts, w.get());
+  if (rc) return rc;
+  w->f = fopen(path, "wb");
+  if (!w->f) {
+    set_err(ctx, "writer: cannot create '%s'", path);
+    return ORCGPU_IO_ERROR;
+  }
+  rc = wr_start(w, out);
+  if (rc) fclose(w->f);
+  return rc;
+}
+
+extern "C" int orcgpu_writer_open_bytes(orcgpu_ctx* ctx, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out) {
+  if (!ctx || !schema || !out) return ORCGPU_INVALID_ARGUMENT;
+  *out = nullptr;
+  auto w = std::make_unique<orcgpu_writer>();
+  w->to_memory = true;
+  int rc = wr_prepare(ctx, schema, opts, w.get());
+  return rc ? rc : wr_start(w, out);
+}
+
+// ArrowWriter::write after orcgpu_writer_write's checks; dev_ends: the device string columns' first and last offsets
+int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, const std::vector<int64_t>& dev_ends) {
+  orcgpu_ctx* ctx = w->ctx;
+  const uint64_t R = batch->length < 0 ? 0 : (uint64_t)batch->length;
+  if (batch->n_children != (int64_t)w->cols.size() || (w->cols.size() && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
+  if (R == 0) return ORCGPU_OK;  // (no slice: step_by over an empty range)
+  if (R >= 0xffffffffull - 1024) {
+    set_err(ctx, "writer: %llu rows in one batch (fewer than 2^32 - 1024 per write)", (unsigned long long)R);
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const bool on_device = flags & ORCGPU_ENC_ON_DEVICE;
+  const uint64_t bs = w->batch_size, n_slices = (R + bs - 1) / bs;
+  const size_t nc = w->cols.size();
+  if (!wr_ensure(w, w->slice_counts, nc * n_slices * 16 + 16 * nc + kAlign)) return ORCGPU_HIP_ERROR;
+  uint64_t* d_cv = (uint64_t*)w->slice_counts.p;  // [col][slice] valid, then [col][slice] bytes, then the columns' "bad offsets" words
+  uint64_t* d_cb = d_cv + nc * n_slices;
+  uint32_t* d_bad = (uint32_t*)(d_cb + nc * n_slices);
+  if (nc) WR_TRY(hipMemsetAsync(d_bad, 0, nc * 4, st));
+  const int64_t row0 = batch->offset;
+  // 1. every column of the batch -> presence bytes, the valid rows' values, the strings' bytes; counts per slice
+  for (size_t ci = 0; ci < nc; ci++) {
+    WrCol& c = w->cols[ci];
+    const ArrowArray* a = batch->children[ci];
+    if (!a || a->length < row0 + (int64_t)R || a->n_buffers < (c.is_string ? 3 : 2) || !a->buffers) return ORCGPU_INVALID_ARGUMENT;
+    const uint64_t off = (uint64_t)(row0 + a->offset);
+    const uint8_t* validity = (const uint8_t*)a->buffers[0];
+    const uint8_t* values = (const uint8_t*)a->buffers[1];
+    const uint8_t* strdata = c.is_string ? (const uint8_t*)a->buffers[2] : nullptr;
+    if (!values || (c.is_string && !strdata && R)) return ORCGPU_INVALID_ARGUMENT;
+    if (validity) c.present = true;
+    const uint64_t vb = (R + 7) / 8;
+    // the input on the device: bits from `off`, values from `off`
+    const uint8_t* d_valsrc = nullptr;  // validity bits, starting at bit d_valbit
+    uint64_t d_valbit = 0;
+    const uint8_t* d_values = nullptr;  // fixed width: values from row `off`; Boolean: bits (d_vbit); strings: offsets from row `off`
+    uint64_t d_vbit = 0;
+    const uint8_t* d_strbase = nullptr;  // strings: the byte the offsets count from
+    uint64_t str_hi = 0;                 // strings: bytes addressed below offsets[off + R] (a bound of the valid rows' bytes)
+    if (on_device) {
+      d_valsrc = validity;
+      d_valbit = off;
+      if (c.stream_kind == 3) {
+        d_values = values;
+        d_vbit = off;
+      } else {
+        d_values = values + off * (uint64_t)c.elem;
+      }
+      if (c.is_string) {  // (read and checked by orcgpu_writer_write before anything changed)
+        d_strbase = strdata;
+        str_hi = (uint64_t)(dev_ends[2 * ci + 1] - dev_ends[2 * ci]);
+      }
+    } else {
+      // the bytes the batch's rows occupy, brought over: [validity bytes][values / bits / offsets][string bytes]
+      const uint64_t vlo = off / 8, vhi = (off + R + 7) / 8;
+      uint64_t val_lo = 0, val_n = 0;
+      int64_t s_lo = 0, s_hi = 0;
+      if (c.stream_kind == 3) {
+        val_lo = vlo;
+        val_n = vhi - vlo;
+      } else {
+        val_lo = off * (uint64_t)c.elem;
+        val_n = (R + (c.is_string ? 1 : 0)) * (uint64_t)c.elem;
+      }
+      if (c.is_string) {
+        if (c.elem == 4) {
+          s_lo = ((const int32_t*)values)[off];
+          s_hi = ((const int32_t*)values)[off + R];
+        } else {
+          s_lo = ((const int64_t*)values)[off];
+          s_hi = ((const int64_t*)values)[off + R];
+        }
+        str_hi = (uint64_t)(s_hi - s_lo);
+      }
+      Bump I;
+      const uint64_t o_v = I.take(validity ? vhi - vlo : 0), o_x = I.take(val_n), o_s = I.take(str_hi);
+      if (!wr_ensure(w, c.b_tmp, I.off + kAlign)) return ORCGPU_HIP_ERROR;
+      if (validity) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_v, validity + vlo, vhi - vlo, hipMemcpyHostToDevice, st));
+      if (val_n) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_x, values + val_lo, val_n, hipMemcpyHostToDevice, st));
+      if (str_hi) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_s, strdata + s_lo, str_hi, hipMemcpyHostToDevice, st));
+      d_valsrc = validity ? c.b_tmp.p + o_v : nullptr;
+      d_valbit = off & 7;
+      d_values = c.b_tmp.p + o_x;
+      d_vbit = off & 7;
+      d_strbase = c.b_tmp.p + o_s - s_lo;  // (addressed at offsets >= s_lo only)
+    }
+    // presence: a bitmap from bit 0 (all set without a validity buffer) and its bytes
+    Bump T;
+    const uint64_t n_words = (R + 63) / 64;
+    const uint64_t o_bits = T.take(n_words * 8 + 8), o_vbits = T.take(c.stream_kind == 3 ? n_words * 8 + 8 : 0), o_wcnt = T.take(n_words * 4),
+                   o_woff = T.take(n_words * 8), o_sums = T.take((n_words / 2048 + 2) * 8), o_tot = T.take(16),
+                   o_len = T.take(c.is_string ? R * (uint64_t)c.elem : 0), o_vlen = T.take(c.is_string ? R * 4 : 0),
+                   o_dst = T.take(c.is_string ? R * 8 : 0), o_sums2 = T.take((R / 2048 + 2) * 8), o_tot2 = T.take(16);
+    if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, R + kAlign) || !wr_ensure(w, c.b_vals, R * (uint64_t)c.elem + kAlign) ||
+        !wr_ensure(w, c.b_data, str_hi + kAlign))
+      return ORCGPU_HIP_ERROR;
+    uint8_t* t = c.b_bits.p;
+    uint8_t* bits = t + o_bits;
+    uint64_t* woff = (uint64_t*)(t + o_woff);
+    WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, d_valsrc, d_valbit, R, bits));
+    WR_TRY(launch(wr_bits_to_bytes_kernel, R, false, 256, st, (const uint8_t*)bits, R, c.b_pres.p));
+    WR_TRY(launch(enc_valid_counts_kernel, n_words, false, 256, st, (const uint8_t*)bits, R, (uint32_t*)(t + o_wcnt)));
+    int rc = enc_scan(ctx, st, (const uint32_t*)(t + o_wcnt), n_words, (uint64_t*)(t + o_sums), (uint64_t*)(t + o_tot), woff);
+    if (rc) return rc;
+    const uint64_t* row_dst = nullptr;
+    const uint32_t* vlen = nullptr;
+    if (c.stream_kind == 3) {  // the valid rows' Boolean values as 0 / 1 bytes
+      WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, (const uint8_t*)d_values, d_vbit, R, t + o_vbits));
+      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)(t + o_vbits), 0, (void*)c.b_vals.p));
+    } else if (!c.is_string) {
+      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)d_values, c.elem, (void*)c.b_vals.p));
+    } else {
+      WR_TRY(launch(enc_lengths_kernel, R, false, 256, st, (const void*)d_values, c.elem, (const uint8_t*)bits, R, (void*)(t + o_len), (uint32_t*)(t + o_vlen),
+                    d_bad + ci));
+      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), R, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
+      if (rc) return rc;
+      // (bounded by str_hi: the offsets are checked when the counts come back, `bad`)
+      WR_TRY(launch(wr_copy_strings_kernel, (R + 3) / 4, true, 256, st, (const uint8_t*)bits, (const void*)d_values, c.elem, R, (const uint64_t*)(t + o_dst),
+                    d_strbase, c.b_data.p, str_hi));
+      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)(t + o_len), c.elem, (void*)c.b_vals.p));
+      row_dst = (const uint64_t*)(t + o_dst);
+      vlen = (const uint32_t*)(t + o_vlen);
+    }
+    WR_TRY(launch(wr_slice_counts_kernel, n_slices, false, 256, st, (const uint8_t*)bits, (const uint64_t*)woff, row_dst, vlen, R, bs, n_slices, d_cv + ci * n_slices,
+                  d_cb + ci * n_slices));
+  }
+  std::vector<uint64_t> cv(nc * n_slices), cb(nc * n_slices);
+  std::vector<uint32_t> bad(nc);
+  if (nc) {
+    WR_TRY(hipMemcpyAsync(cv.data(), d_cv, nc * n_slices * 8, hipMemcpyDeviceToHost, st));
+    WR_TRY(hipMemcpyAsync(cb.data(), d_cb, nc * n_slices * 8, hipMemcpyDeviceToHost, st));
+    WR_TRY(hipMemcpyAsync(bad.data(), d_bad, nc * 4, hipMemcpyDeviceToHost, st));
+  }
+  int rc = wr_sync(w);
+  if (rc) return rc;
+  for (size_t ci = 0; ci < nc; ci++)
+    if (bad[ci]) {
+      set_err(ctx, "writer: the offsets of column %zu are not ascending (or a value is 4 GiB or longer)", ci);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+  auto V = [&](size_t ci, uint64_t j) -> uint64_t { return j ? cv[ci * n_slices + j - 1] : 0; };  // valid rows before slice j
+  auto B = [&](size_t ci, uint64_t j) -> uint64_t { return j ? cb[ci * n_slices + j - 1] : 0; };
+  auto rows_to = [&](uint64_t j) -> uint64_t { return std::min<uint64_t>(j * bs, R); };        // rows before slice j
+  // the stripe's buffers extended by the batch's slices [j0, j1) (the counters move only with `commit`)
+  auto extend = [&](uint64_t j0, uint64_t j1, bool commit) -> int {
+    for (size_t ci = 0; ci < nc; ci++) {
+      WrCol& c = w->cols[ci];
+      const uint64_t dv = V(ci, j1) - V(ci, j0), dr = rows_to(j1) - rows_to(j0), db = B(ci, j1) - B(ci, j0);
+      const uint64_t nv = c.n_valid * c.elem, add = dv * c.elem;
+      if (!wr_reserve(w, c.vals, nv + add + kAlign, nv)) return ORCGPU_HIP_ERROR;
+      if (add) WR_TRY(hipMemcpyAsync(c.vals.p + nv, c.b_vals.p + V(ci, j0) * c.elem, add, hipMemcpyDeviceToDevice, st));
+      if (commit) {
+        if (!wr_reserve(w, c.pres, c.rows + dr + kAlign, c.rows)) return ORCGPU_HIP_ERROR;
+        if (dr) WR_TRY(hipMemcpyAsync(c.pres.p + c.rows, c.b_pres.p + rows_to(j0), dr, hipMemcpyDeviceToDevice, st));
+        if (c.is_string) {
+          if (!wr_reserve(w, c.data, c.n_bytes + db + kAlign, c.n_bytes)) return ORCGPU_HIP_ERROR;
+          if (db) WR_TRY(hipMemcpyAsync(c.data.p + c.n_bytes, c.b_data.p + B(ci, j0), db, hipMemcpyDeviceToDevice, st));
+        }
+        c.rows += dr;
+        c.n_valid += dv;
+        c.n_bytes += db;
+      }
+    }
+    if (commit) w->rows += rows_to(j1) - rows_to(j0);
+    return ORCGPU_OK;
+  };
+  // the summed estimate after slice j (j0 <= j) of the terms that are counts: floats, Booleans, string bytes, PRESENT
+  auto counted = [&](uint64_t j0, uint64_t j, uint64_t* rle_bound) -> uint64_t {
+    uint64_t e = 0, bound = 0;
+    for (size_t ci = 0; ci < nc; ci++) {
+      const WrCol& c = w->cols[ci];
+      const uint64_t nv = c.n_valid + V(ci, j + 1) - V(ci, j0);
+      if (c.present) e += (c.rows + rows_to(j + 1) - rows_to(j0)) / 8;
+      switch (c.stream_kind) {
+        case 2: e += nv * (uint64_t)c.elem; break;
+        case 3: e += nv / 8; break;
+        // (the run-length encoded terms: exactly base_rle when the columns had base_valid values; each run written out since
+        // covers values from then on, or from the run open then -- at most 512 values before)
+        case 4: e += c.n_bytes + B(ci, j + 1) - B(ci, j0); bound += wr_bound(c, nv - c.base_valid + 512); break;
+        default: bound += wr_bound(c, nv - c.base_valid + 512); break;
+      }
+    }
+    if (rle_bound) *rle_bound = w->base_rle + bound;
+    return e;
+  };
+  // the first slice in [j0, j1) after which the estimate exceeds the limit, or j1
+  std::vector<uint64_t> est;  // the run-length encoded terms after the analysed slices
+  auto analyse = [&](uint64_t j0, uint64_t j1) -> int64_t {
+    const uint64_t win = j1 - j0;
+    if (!wr_ensure(w, w->est, win * 8 + kAlign)) return -1;
+    uint64_t* d_est = (uint64_t*)w->est.p;
+    if (hipMemsetAsync(d_est, 0, win * 8, st) != hipSuccess) return -1;
+    if (extend(j0, j1, false)) return -1;
+    for (size_t ci = 0; ci < nc; ci++) {
+      WrCol& c = w->cols[ci];
+      if (c.stream_kind == 2 || c.stream_kind == 3) continue;
+      EncJob J;
+      J.kind = c.stream_kind == 1 ? 1 : 0;
+      J.int_bytes = c.elem;
+      J.is_signed = c.stream_kind == 0;
+      J.n = c.n_valid + V(ci, j1) - V(ci, j0);
+      J.values = c.vals.p;
+      J.deferred = true;  // (no host wait: the run count stays on the device, the grids cover n runs)
+      J.syncs = &w->round_trips;
+      if (!J.n) continue;
+      if (!wr_ensure(w, w->trig, J.n * 8 + kAlign)) return -1;  // (before the plan: growing waits, and the tables are the plan's)
+      if (enc_plan(ctx, J)) return -1;
+      uint64_t* d_trig = (uint64_t*)w->trig.p;
+      hipError_t e = J.kind == 0 ? launch(wr_triggers_kernel<0>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, J.int_bytes, (const uint32_t*)J.runs,
+                                          J.d_n_runs, J.n, d_trig)
+                                 : launch(wr_triggers_kernel<1>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, 1, (const uint32_t*)J.runs, J.d_n_runs,
+                                          J.n, d_trig);
+      if (e != hipSuccess) return -1;
+      // values after slice j: c.n_valid + cv[j] - V(j0)
+      e = launch(wr_estimate_kernel, win, false, 256, st, (const uint64_t*)d_trig, (const uint32_t*)J.runs, (const uint32_t*)J.run_bytes, (const uint64_t*)J.offsets,
+                 J.d_n_runs, J.kind, (const uint64_t*)(d_cv + ci * n_slices + j0), (int64_t)c.n_valid - (int64_t)V(ci, j0), win, d_est);
+      if (e != hipSuccess) return -1;
+    }
+    est.assign(win, 0);
+    if (hipMemcpyAsync(est.data(), d_est, win * 8, hipMemcpyDeviceToHost, st) != hipSuccess || wr_sync(w)) return -1;
+    for (uint64_t j = j0; j < j1; j++)
+      if (est[j - j0] + counted(j0, j, nullptr) > w->stripe_byte_size) return (int64_t)j;
+    return (int64_t)j1;
+  };
+  uint64_t j0 = 0;
+  while (j0 < n_slices) {
+    // slices that cannot reach the limit by the bound: taken as they are
+    uint64_t js = j0;
+    while (js < n_slices) {
+      uint64_t bound;
+      const uint64_t e = counted(j0, js, &bound);
+      if (e + bound > w->stripe_byte_size) break;
+      js++;
+    }
+    if (js == n_slices) {
+      rc = extend(j0, n_slices, true);
+      if (rc) return rc;
+      break;
+    }
+    // the rest: windows of the run analysis, growing
+    uint64_t win = std::max<uint64_t>(w->window_hint, js - j0 + 1);
+    int64_t cut;
+    for (;;) {
+      const uint64_t j1 = std::min<uint64_t>(n_slices, j0 + win);
+      cut = analyse(j0, j1);
+      if (cut < 0) {
+        if (ctx->err.empty()) set_err(ctx, "writer: the stripe analysis failed");
+        return ORCGPU_HIP_ERROR;
+      }
+      if ((uint64_t)cut < j1 || j1 == n_slices) break;
+      win *= 2;
+    }
+    if ((uint64_t)cut == n_slices) {
+      rc = extend(j0, n_slices, true);
+      if (rc) return rc;
+      w->base_rle = est.back();  // (exact at the end of this write: later bounds start from it)
+      for (auto& c : w->cols) c.base_valid = c.n_valid;
+      break;
+    }
+    rc = extend(j0, (uint64_t)cut + 1, true);
+    if (rc) return rc;
+    rc = wr_flush(w);
+    if (rc) return rc;
+    w->window_hint = std::max<uint64_t>(1, (uint64_t)cut + 1 - j0);
+    j0 = (uint64_t)cut + 1;
+  }
+  return wr_sync(w);  // (the caller may release the batch now)
+}
+
+// everything that can reject the batch is checked before the writer changes; a failure after that leaves it failed
+extern "C" int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* schema, const struct ArrowArray* batch, uint32_t flags) {
+  if (!w || !schema || !batch || w->closed) return ORCGPU_INVALID_ARGUMENT;
+  if (w->failed) return ORCGPU_UNEXPECTED;
+  orcgpu_ctx* ctx = w->ctx;
+  {  // ensure!(batch.schema() == self.schema, Unexpected)
+    std::vector<WrField> fields;
+    std::string md;
+    int64_t fl;
+    int rc = wr_read_schema(ctx, schema, fields, md, fl);
+    bool same = rc == ORCGPU_OK && md == w->root_metadata && fields.size() == w->fields.size();
+    for (size_t i = 0; same && i < fields.size(); i++)
+      same = fields[i].format == w->fields[i].format && fields[i].name == w->fields[i].name && fields[i].metadata == w->fields[i].metadata &&
+             (fields[i].flags & 2) == (w->fields[i].flags & 2);
+    if (!same) {
+      set_err(ctx, "writer: RecordBatch doesn't match expected schema");
+      return ORCGPU_UNEXPECTED;
+    }
+  }
+  const int64_t R = batch->length;
+  const size_t nc = w->cols.size();
+  if (R < 0 || batch->n_children != (int64_t)nc || (nc && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
+  std::vector<int64_t> dev_ends(2 * nc, 0);
+  if (R > 0 && batch->n_children == (int64_t)nc && (nc == 0 || batch->children)) {
+    const bool on_device = flags & ORCGPU_ENC_ON_DEVICE;
+    bool any_device_strings = false;
+    for (size_t ci = 0; ci < nc; ci++) {
+      const WrCol& c = w->cols[ci];
+      const ArrowArray* a = batch->children[ci];
+      if (!a || a->offset < 0 || batch->offset < 0 || a->length < batch->offset + R || a->n_buffers < (c.is_string ? 3 : 2) || !a->buffers ||
+          !a->buffers[1] || (c.is_string && !a->buffers[2])) {
+        set_err(ctx, "writer: column %zu of the batch is not an Arrow array of its type", ci);
+        return ORCGPU_INVALID_ARGUMENT;
+      }
+      if (!c.is_string) continue;
+      const uint64_t off = (uint64_t)(batch->offset + a->offset);
+      const uint8_t* o = (const uint8_t*)a->buffers[1];
+      if (on_device) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        WR_TRY(hipMemcpyAsync(&dev_ends[2 * ci], o + off * c.elem, c.elem, hipMemcpyDeviceToHost, ctx->stream));
+        WR_TRY(hipMemcpyAsync(&dev_ends[2 * ci + 1], o + (off + R) * c.elem, c.elem, hipMemcpyDeviceToHost, ctx->stream));
+        any_device_strings = true;
+        continue;
+      }
+      // host offsets: ascending (they bound the bytes the copy writes)
+      bool ascending = (c.elem == 4 ? (int64_t)((const int32_t*)o)[off] : ((const int64_t*)o)[off]) >= 0;
+      for (uint64_t r = off; ascending && r < off + (uint64_t)R; r++)
+        ascending = c.elem == 4 ? ((const int32_t*)o)[r] <= ((const int32_t*)o)[r + 1] : ((const int64_t*)o)[r] <= ((const int64_t*)o)[r + 1];
+      if (!ascending) {
+        set_err(ctx, "writer: the offsets of column %zu are not ascending", ci);
+        return ORCGPU_INVALID_ARGUMENT;
+      }
+    }
+    if (any_device_strings) {  // one wait for every string column's first and last offset
+      int rc = wr_sync(w);
+      if (rc) return rc;
+      for (size_t ci = 0; ci < nc; ci++) {
+        if (!w->cols[ci].is_string) continue;
+        if (w->cols[ci].elem == 4) {
+          dev_ends[2 * ci] = (int32_t)dev_ends[2 * ci];
+          dev_ends[2 * ci + 1] = (int32_t)dev_ends[2 * ci + 1];
+        }
+        if (dev_ends[2 * ci] < 0 || dev_ends[2 * ci + 1] < dev_ends[2 * ci]) {
+          set_err(ctx, "writer: the offsets of column %zu are not ascending", ci);
+          return ORCGPU_INVALID_ARGUMENT;
+        }
+      }
+    }
+  }
+  int rc = wr_write(w, batch, flags, dev_ends);
+  if (rc) w->failed = true;
+  return rc;
+}
+
+extern "C" int orcgpu_writer_flush_stripe(orcgpu_writer* w) {
+  if (!w || w->closed) return ORCGPU_INVALID_ARGUMENT;
+  if (w->failed) return ORCGPU_UNEXPECTED;
+  HIP_TRY(w->ctx, hipSetDevice(w->ctx->device));
+  int rc = wr_flush(w);
+  if (rc) w->failed = true;
+  return rc;
+}
+
+extern "C" int orcgpu_writer_close(orcgpu_writer* w) {
+  if (!w || w->closed) return ORCGPU_INVALID_ARGUMENT;
+  if (w->failed) return ORCGPU_UNEXPECTED;
+  HIP_TRY(w->ctx, hipSetDevice(w->ctx->device));
+  int rc = ORCGPU_OK;
+  if (w->rows > 0) rc = wr_flush(w);
+  if (!rc) rc = wr_close(w);
+  w->closed = true;
+  if (w->f) {
+    if (fclose(w->f) != 0 && !rc) rc = ORCGPU_IO_ERROR;
+    w->f = nullptr;
+  }
+  return rc;
+}
+
+extern "C" int orcgpu_writer_take_bytes(orcgpu_writer* w, uint8_t* out, uint64_t cap, uint64_t* len) {
+  if (!w || !len || !w->to_memory) return ORCGPU_INVALID_ARGUMENT;
+  *len = w->mem.size();
+  if (!out) return ORCGPU_OK;
+  if (cap < w->mem.size()) return ORCGPU_INVALID_ARGUMENT;
+  if (!w->mem.empty()) memcpy(out, w->mem.data(), w->mem.size());
+  w->mem.clear();
+  return ORCGPU_OK;
+}
+
+extern "C" int orcgpu_writer_stats(const orcgpu_writer* w, orcgpu_writer_counts* out) {
+  if (!w || !out) return ORCGPU_INVALID_ARGUMENT;
+  out->stripes = w->stripes.size();
+  uint64_t rows = 0;
+  for (auto& s : w->stripes) rows += s.rows;
+  out->rows = rows;
+  out->bytes = w->written;
+  out->round_trips = w->round_trips;
+  out->stripe_round_trips = w->stripe_round_trips;
+  return ORCGPU_OK;
+}
+
+extern "C" uint64_t orcgpu_writer_stripe_rows(const orcgpu_writer* w, uint64_t stripe) {
+  return w && stripe < w->stripes.size() ? w->stripes[stripe].rows : 0;
+}
+
+extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
+  if (!w) return;
+  if (w->f) fclose(w->f);
+  if (w->ctx) (void)hipSetDevice(w->ctx->device);
+  if (w->ctx) (void)hipStreamSynchronize(w->ctx->stream);
+  for (auto& c : w->cols) {
+    c.pres.release();
+    c.vals.release();
+    c.data.release();
+    c.b_bits.release();
+    c.b_pres.release();
+    c.b_vals.release();
+    c.b_data.release();
+    c.b_tmp.release();
+  }
+  w->slice_counts.release();
+  w->est.release();
+  w->trig.release();
+  w->lens.release();
+  w->bits.release();
+  w->out.release();
+  w->slots.release();
+  if (w->pinned) (void)hipHostFree(w->pinned);
+  delete w;
+}

@@ -1,0 +1,159 @@
+"""Rate of the GPU writer (orcgpu_writer_*, ArrowWriterBuilder): a 16-column lineitem-shaped table (numpy-generated) written to a
+memory sink from host batches and from device-resident batches (the same columns in device memory, ORCGPU_ENC_ON_DEVICE), at the
+default stripe size and at 4 MiB; beside it pyarrow.orc.write_table(..., compression="uncompressed") on the same table on the same
+host (Apache ORC C++, the CPU baseline).  GB/s = Arrow bytes of the table in / wall seconds of the whole write (open .. close).
+Usage: python profiles/writer_rate.py [rows]  -> one JSON object on stdout."""
+import ctypes as C
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pyarrow as pa
+import pyarrow.orc as po
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from orc_rust_amd import ArrowWriterBuilder, capi  # noqa: E402
+
+
+class _ArrowArray(C.Structure):
+    pass
+
+
+_ArrowArray._fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offset", C.c_int64), ("n_buffers", C.c_int64),
+                        ("n_children", C.c_int64), ("buffers", C.POINTER(C.c_void_p)), ("children", C.POINTER(C.POINTER(_ArrowArray))),
+                        ("dictionary", C.c_void_p), ("release", C.c_void_p), ("private_data", C.c_void_p)]
+
+
+def lineitem(n, rng):
+    def one(a):
+        return a.combine_chunks() if isinstance(a, pa.ChunkedArray) else a
+    cols = {
+        "l_orderkey": np.repeat(np.arange(n // 4 + 1, dtype=np.int64) * 4, 4)[:n],
+        "l_partkey": rng.integers(1, 200000, n).astype(np.int64),
+        "l_suppkey": rng.integers(1, 10000, n).astype(np.int64),
+        "l_linenumber": (np.arange(n) % 7 + 1).astype(np.int32),
+        "l_quantity": rng.integers(1, 51, n).astype(np.float64),
+        "l_extendedprice": np.round(rng.random(n) * 100000, 2),
+        "l_discount": rng.integers(0, 11, n) / 100.0,
+        "l_tax": rng.integers(0, 9, n) / 100.0,
+        "l_returnflag": np.array(["A", "N", "R"])[rng.integers(0, 3, n)],
+        "l_linestatus": np.array(["O", "F"])[rng.integers(0, 2, n)],
+        "l_shipdate": rng.integers(8000, 10600, n).astype(np.int32),
+        "l_commitdate": rng.integers(8000, 10600, n).astype(np.int32),
+        "l_receiptdate": rng.integers(8000, 10600, n).astype(np.int32),
+        "l_shipinstruct": np.array(["DELIVER IN PERSON", "COLLECT COD", "NONE", "TAKE BACK RETURN"])[rng.integers(0, 4, n)],
+        "l_shipmode": np.array(["AIR", "MAIL", "SHIP", "TRUCK", "RAIL", "FOB", "REG AIR"])[rng.integers(0, 7, n)],
+        "l_comment": np.char.add("c", rng.integers(0, 1 << 40, n).astype("U16")),
+    }
+    return pa.RecordBatch.from_pydict({k: one(pa.array(v)) for k, v in cols.items()})
+
+
+class DeviceBatch:
+    """The batch's buffers copied to device memory (hipMalloc through the HIP runtime the library uses) as an ArrowArray."""
+
+    def __init__(self, batch):
+        hip = C.CDLL("libamdhip64.so")
+        self.hip, self.ptrs = hip, []
+        kids = []
+        self.keep = []
+        for col in batch.columns:
+            bufs = []
+            for b in col.buffers():
+                if b is None:
+                    bufs.append(None)
+                    continue
+                p = C.c_void_p()
+                assert hip.hipMalloc(C.byref(p), C.c_size_t(max(1, b.size))) == 0
+                assert hip.hipMemcpy(p, C.c_void_p(b.address), C.c_size_t(b.size), 1) == 0  # hipMemcpyHostToDevice
+                self.ptrs.append(p)
+                bufs.append(p.value)
+            arr = _ArrowArray()
+            cb = (C.c_void_p * len(bufs))(*bufs)
+            arr.length, arr.null_count, arr.offset, arr.n_buffers, arr.n_children, arr.buffers = len(col), col.null_count, col.offset, len(bufs), 0, cb
+            self.keep += [arr, cb]
+            kids.append(C.pointer(arr))
+        self.kids = (C.POINTER(_ArrowArray) * len(kids))(*kids)
+        self.rbufs = (C.c_void_p * 1)(None)
+        self.root = _ArrowArray()
+        r = self.root
+        r.length, r.null_count, r.offset, r.n_buffers, r.n_children, r.buffers, r.children = batch.num_rows, 0, 0, 1, len(kids), self.rbufs, self.kids
+
+    def free(self):
+        for p in self.ptrs:
+            self.hip.hipFree(p)
+        self.ptrs = []
+
+
+def gpu_write(ctx, batches, schema, sbs, device=None):
+    out = io.BytesIO()
+    t0 = time.perf_counter()
+    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).try_build()
+    if device is None:
+        for b in batches:
+            w.write(b)
+    else:
+        sbuf = (C.c_uint8 * 72)()
+        schema._export_to_c(C.addressof(sbuf))
+        for d in device:
+            w.write_c(C.addressof(sbuf), C.addressof(d.root), capi.ENC_ON_DEVICE)
+        C.cast(C.addressof(sbuf) + 56, C.POINTER(C.CFUNCTYPE(None, C.c_void_p)))[0](C.addressof(sbuf))
+    w.close()
+    dt = time.perf_counter() - t0
+    st = w.stats()
+    w.free()
+    return dt, st, out.getbuffer().nbytes
+
+
+def main():
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 8_000_000
+    per_batch = 1_000_000
+    rng = np.random.default_rng(1)
+    batches = [lineitem(per_batch, rng) for _ in range(max(1, n // per_batch))]  # (each its own buffers: the device copies hold no more)
+    table = batches[0]
+    n = per_batch * len(batches)
+    arrow_bytes = sum(b.nbytes for b in batches)
+    ctx = capi.Context()
+    out = {"rows": n, "columns": table.num_columns, "arrow_bytes": arrow_bytes, "unit": "GB/s of Arrow input (open .. close)", "runs": {}}
+    gpu_write(ctx, batches[:1], table.schema, 64 << 20)  # warm-up (kernels loaded, buffers grown)
+    device = [DeviceBatch(b) for b in batches]
+    for sbs_name, sbs in [("default 64 MiB", 64 << 20), ("4 MiB", 4 << 20)]:
+        for src in ["host", "device"]:
+            best = None
+            for _ in range(3):
+                dt, st, size = gpu_write(ctx, batches, table.schema, sbs, device if src == "device" else None)
+                if best is None or dt < best[0]:
+                    best = (dt, st, size)
+            dt, st, size = best
+            out["runs"]["%s, %s batches" % (sbs_name, src)] = {
+                "seconds": round(dt, 4), "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                "round_trips": st["round_trips"], "round_trips_per_stripe": round(st["round_trips"] / max(1, st["stripes"]), 1),
+                "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    for d in device:
+        d.free()
+    # the reference's usual pattern: many small writes into one stripe (the size analysis runs only near the stripe's limit)
+    for rows_per_write in [8192, 1024]:
+        small = [b.slice(i, rows_per_write) for b in batches for i in range(0, b.num_rows, rows_per_write)]
+        dt, st, size = gpu_write(ctx, small, table.schema, 64 << 20)
+        out["runs"]["default 64 MiB, host batches of %d rows" % rows_per_write] = {
+            "seconds": round(dt, 4), "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"], "writes": len(small),
+            "round_trips": st["round_trips"], "round_trips_per_write": round(st["round_trips"] / len(small), 2),
+            "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    tt = pa.Table.from_batches(batches)
+    best = None
+    for _ in range(3):
+        buf = io.BytesIO()
+        t0 = time.perf_counter()
+        po.write_table(tt, buf, compression="uncompressed")
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    out["cpu_baseline"] = {"what": "pyarrow.orc.write_table(compression='uncompressed'), same host", "seconds": round(best, 4),
+                           "GB/s": round(arrow_bytes / best / 1e9, 3), "file_bytes": buf.getbuffer().nbytes}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
