@@ -437,9 +437,10 @@ int orcgpu_encode_fetch(orcgpu_ctx* ctx, const orcgpu_enc_stream* stream, uint8_
 
 /* ---- ArrowWriterBuilder / ArrowWriter (src/arrow_writer.rs:34-156) ----------------------------------------------------------
  * Arrow record batches -> an ORC file, byte for byte the reference writer's: a flat schema of Boolean, Int8..Int64, Float32/64,
- * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no compression, index or statistics.  Every stream is
- * encoded on the device (the encoders above); a stripe is cut where the reference's would be (after a slice of batch_size rows
- * whose summed encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.
+ * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no index or statistics.  Every stream is encoded on the
+ * device (the encoders above); a stripe is cut where the reference's would be (after a slice of batch_size rows whose summed
+ * encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.  Uncompressed by default (the reference writes
+ * CompressionKind::None only); orcgpu_writer_set_compression selects Snappy or LZ4, compressed on the device (below).
  * schema: an Arrow struct ("+s") of the fields.  Another type than those: ORCGPU_UNSUPPORTED at open (the reference panics).
  * write: the batch as an Arrow struct array with the schema it was exported with; a schema that differs from the writer's (names,
  * types, nullability, metadata): ORCGPU_UNEXPECTED.  ORCGPU_ENC_ON_DEVICE: the buffers are device memory of ctx's device (the
@@ -468,6 +469,22 @@ int orcgpu_writer_take_bytes(orcgpu_writer* w, uint8_t* out, uint64_t cap, uint6
 int orcgpu_writer_stats(const orcgpu_writer* w, orcgpu_writer_counts* out);
 uint64_t orcgpu_writer_stripe_rows(const orcgpu_writer* w, uint64_t stripe);  /* rows of a written stripe (0 past the last) */
 void orcgpu_writer_free(orcgpu_writer* w);
+
+/* ---- Stream compression on the device: Snappy and LZ4 (the inverse of src/compression.rs:113-195) -----------------------------
+ * A stream is cut into chunks of at most block_size bytes (0: 262144, compression.rs:31; at most 2^23 - 1, the chunk header's
+ * limit: ORCGPU_INVALID_ARGUMENT above it).  A chunk is a 3-byte little-endian header, len * 2 + is_original, and a raw Snappy
+ * block or a raw LZ4 block (no frame) -- or the chunk's own bytes (an ORIGINAL chunk) when compressing did not make it smaller.
+ * The output is the same for the same input on every run.
+ *
+ * set_compression: ORCGPU_COMP_NONE (the default), ORCGPU_COMP_SNAPPY or ORCGPU_COMP_LZ4; ZLIB, LZO and ZSTD:
+ * ORCGPU_UNSUPPORTED.  Legal only before the first write, flush_stripe or close (ORCGPU_INVALID_ARGUMENT after).  A compressed
+ * file has the stripes, rows and (decompressed) streams of the uncompressed one; its stripe footers and file footer are written
+ * as original chunks.
+ * compress_stream: one stream, in and out host memory, or device memory with ORCGPU_ENC_ON_DEVICE.  out = NULL reports a bound
+ * in *out_len (n + 3 per chunk); out_cap must hold it. */
+int orcgpu_writer_set_compression(orcgpu_writer* w, int kind, uint64_t block_size);
+int orcgpu_compress_stream(orcgpu_ctx* ctx, int kind, uint64_t block_size, const void* in, uint64_t n, uint32_t flags, uint8_t* out, uint64_t out_cap,
+                           uint64_t* out_len);
 
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) ---------------------- */
 /* Milliseconds the device spent in the last orcgpu_decode_staged call, whole call and the RLE

@@ -2,6 +2,7 @@
 (`orcgpu_writer_*`).  Pure plumbing: batches go over through the Arrow C Data Interface, every stream is encoded on the GPU.
 
     w = ArrowWriterBuilder("out.orc", schema).with_batch_size(1024).with_stripe_byte_size(64 << 20).try_build()
+    w = ArrowWriterBuilder("out.orc", schema).with_compression("snappy").try_build()   # or "lz4"; compressed on the GPU
     w.write(batch)          # pyarrow.RecordBatch
     w.flush_stripe()
     w.close()
@@ -14,6 +15,9 @@ from . import capi
 
 DEFAULT_BATCH_SIZE = 1024            # arrow_writer.rs:49
 DEFAULT_STRIPE_BYTE_SIZE = 64 << 20  # arrow_writer.rs:51
+DEFAULT_COMPRESSION_BLOCK_SIZE = 262144  # compression.rs:31
+MAX_COMPRESSION_BLOCK_SIZE = (1 << 23) - 1  # a chunk header holds len * 2 + 1 in 24 bits
+COMPRESSIONS = {None: 0, "none": 0, "snappy": 2, "lz4": 4}  # the codecs the writer compresses with (capi.COMP)
 
 _SCHEMA_BYTES, _ARRAY_BYTES, _RELEASE_AT = 72, 80, {72: 56, 80: 64}  # struct ArrowSchema / ArrowArray, offset of `release`
 
@@ -45,6 +49,7 @@ class ArrowWriterBuilder:
     def __init__(self, sink, schema, ctx=None):
         self._sink, self._schema, self._ctx = sink, schema, ctx
         self._batch_size, self._stripe_byte_size = DEFAULT_BATCH_SIZE, DEFAULT_STRIPE_BYTE_SIZE
+        self._compression, self._block_size = 0, DEFAULT_COMPRESSION_BLOCK_SIZE
 
     def with_batch_size(self, n):
         self._batch_size = int(n)
@@ -52,6 +57,17 @@ class ArrowWriterBuilder:
 
     def with_stripe_byte_size(self, n):
         self._stripe_byte_size = int(n)
+        return self
+
+    def with_compression(self, codec, block_size=DEFAULT_COMPRESSION_BLOCK_SIZE):
+        """codec: None / "none" (the default: the reference's uncompressed file), "snappy" or "lz4" -- every stream compressed on the
+        GPU in chunks of at most block_size bytes"""
+        if codec not in COMPRESSIONS:
+            raise ValueError("compression must be one of None, 'none', 'snappy', 'lz4', not %r" % (codec,))
+        block_size = int(block_size)
+        if block_size <= 0 or block_size > MAX_COMPRESSION_BLOCK_SIZE:
+            raise ValueError("block_size must be in 1 .. 2^23 - 1")
+        self._compression, self._block_size = COMPRESSIONS[codec], block_size
         return self
 
     def try_build(self):
@@ -75,6 +91,12 @@ class ArrowWriterBuilder:
         finally:
             s.release()
         w = ArrowWriter(ctx, out.value, self._schema, fobj)
+        if self._compression:
+            try:
+                ctx._check(ctx.L.orcgpu_writer_set_compression(out.value, self._compression, self._block_size))
+            except Exception:
+                w.free()
+                raise
         w._drain()
         return w
 

@@ -29,6 +29,7 @@ EXPORTS = [
     "orcgpu_reader_next_batch",
     "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
     "orcgpu_writer_take_bytes", "orcgpu_writer_stats", "orcgpu_writer_stripe_rows", "orcgpu_writer_free",
+    "orcgpu_writer_set_compression", "orcgpu_compress_stream",
 ]
 
 
@@ -236,6 +237,9 @@ def load():
     L.orcgpu_writer_stripe_rows.restype = C.c_uint64
     L.orcgpu_writer_stripe_rows.argtypes = [C.c_void_p, C.c_uint64]
     L.orcgpu_writer_free.argtypes = [C.c_void_p]
+    L.orcgpu_writer_set_compression.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    L.orcgpu_compress_stream.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                         C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -335,6 +339,25 @@ class Context:
         v = np.ascontiguousarray(bits_lsb, dtype=np.uint8)
         assert v.size * 8 >= n_bits
         return self._encode(self.L.orcgpu_encode_boolean, v.ctypes.data, n_bits, 0)
+
+    def compress_stream(self, data, codec, block_size=262144):
+        """ORC compression chunks of host bytes, compressed on the device (orcgpu_compress_stream): codec "snappy" or "lz4" """
+        kind = COMP[codec] if isinstance(codec, str) else codec
+        v = np.frombuffer(bytes(data), dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+        n = len(data)
+        bound = C.c_uint64(0)
+        self._check(self.L.orcgpu_compress_stream(self.h, kind, block_size, v.ctypes.data, n, 0, None, 0, C.byref(bound)))
+        out = np.zeros(max(1, bound.value), dtype=np.uint8)
+        m = C.c_uint64(0)
+        self._check(self.L.orcgpu_compress_stream(self.h, kind, block_size, v.ctypes.data, n, 0, out.ctypes.data, out.size, C.byref(m)))
+        return out[:m.value].tobytes()
+
+    def compress_stream_device(self, d_in, n, codec, d_out, out_cap, block_size=262144):
+        """The same from device memory to device memory (ORCGPU_ENC_ON_DEVICE): the compressed length"""
+        kind = COMP[codec] if isinstance(codec, str) else codec
+        m = C.c_uint64(0)
+        self._check(self.L.orcgpu_compress_stream(self.h, kind, block_size, d_in, n, ENC_ON_DEVICE, d_out, out_cap, C.byref(m)))
+        return m.value
 
     def encode_column(self, arrow_type, n_rows, values, validity=None, offsets=None):
         """ColumnStripeEncoder::{encode_array, finish} (writer/column.rs): [(ORC stream kind, bytes)] in finish()'s order"""

@@ -43,6 +43,7 @@
 #include "device/decompress_kernels.hip"
 #include "device/select_kernels.hip"
 #include "device/rle_encode.hip"
+#include "device/lz_compress.hip"
 
 // Arrow C Data Interface structs (public, stable ABI)
 extern "C" {
@@ -248,6 +249,7 @@ struct orcgpu_ctx {
   std::string err;
   DevBuf scratch;
   DevBuf enc_a, enc_b, enc_in, enc_tmp, enc_out[3];  // the encoder's own (orcgpu_encode.inc): chain tables, run tables, inputs brought to the device, gathered values, streams
+  DevBuf lzc_tab, lzc_stage, lzc_io;  // the stream compressor's (orcgpu_compress.inc): job / segment / chunk tables, segment bodies, a single stream's input and output
   uint8_t* pinned = nullptr;
   size_t pinned_cap = 0;
   uint8_t* fin_pinned = nullptr;       // staging of the finishers' job table
@@ -817,6 +819,9 @@ void orcgpu_close(orcgpu_ctx* c) {
   c->enc_in.release();
   c->enc_tmp.release();
   for (auto& b : c->enc_out) b.release();
+  c->lzc_tab.release();
+  c->lzc_stage.release();
+  c->lzc_io.release();
   delete c->copiers;
   for (int k = 0; k < 2; k++) {
     if (c->piece[k]) (void)hipHostFree(c->piece[k]);
@@ -1228,4 +1233,5 @@ struct SummaryLayout {
 #include "orcgpu_select.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_encode.inc"
+#include "orcgpu_compress.inc"
 #include "orcgpu_writer.inc"

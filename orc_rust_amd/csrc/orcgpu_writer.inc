@@ -12,6 +12,11 @@
 // (wr_triggers_kernel: when each run is written out; wr_estimate_kernel: the bytes written out by each slice end).  Slices whose
 // estimate cannot exceed the limit by an upper bound of the encoders' output are taken without that analysis; past them the
 // analysed window grows geometrically.
+//
+// Compression (orcgpu_writer_set_compression; the reference writes CompressionKind::None only): after the last stream of a stripe
+// is enqueued, every stream goes through the device compressor (orcgpu_compress.inc) from its slot into a slot of zout, in one
+// launch set, before the first wait; the lengths that wait brings back are the compressed ones.  Stripe footers and the file
+// Footer are written as original chunks.  The cut is unchanged: it is computed over the uncompressed encoders' estimates.
 namespace {
 
 // the buffer keeps its contents when it grows (stream-ordered copy)
@@ -116,6 +121,11 @@ struct orcgpu_writer {
   uint64_t base_rle = 0;
   uint8_t* pinned = nullptr;
   size_t pinned_cap = 0;
+  // compression (orcgpu_writer_set_compression): the streams' chunks in zout, a slot each; `started` once write / flush / close ran
+  int comp = ORCGPU_COMP_NONE;
+  uint64_t comp_block = kLzcDefaultBlock;
+  bool started = false;
+  DevVec zout;
 };
 
 namespace {
@@ -349,20 +359,41 @@ int wr_flush(orcgpu_writer* w) {
       if (rc) return rc;
     }
   }
+  // compression: every stream from its slot into its slot of zout, in one launch set; the lengths in w->lens become the chunks'
+  const bool comp = w->comp != ORCGPU_COMP_NONE;
+  std::vector<uint64_t> zslot(n_streams, 0);
+  if (comp && n_streams) {
+    std::vector<LzcStream> jobs(n_streams);
+    std::vector<uint64_t> rooms(n_streams);
+    uint64_t zat = 0;
+    for (uint64_t i = 0; i < n_streams; i++) {
+      rooms[i] = (i + 1 < n_streams ? streams[i + 1].slot : at) - streams[i].slot;
+      zslot[i] = zat;
+      jobs[i] = LzcStream{streams[i].slot, zat, known[i]};
+      zat += align_up(lzc_room(rooms[i], w->comp_block));
+    }
+    if (!wr_reserve(w, w->zout, zat + kAlign, 0)) {
+      set_err(ctx, "writer: out of device memory (%llu bytes of compressed stripe)", (unsigned long long)zat);
+      return ORCGPU_HIP_ERROR;
+    }
+    rc = lzc_enqueue(ctx, lzc_codec(w->comp), w->comp_block, w->slots.p, w->zout.p, jobs, rooms, (uint64_t*)w->lens.p, &w->round_trips);
+    if (rc) return rc;
+  }
   std::vector<uint64_t> lens(n_streams, 0);
   if (n_streams) WR_TRY(hipMemcpyAsync(lens.data(), w->lens.p, n_streams * 8, hipMemcpyDeviceToHost, ctx->stream));
   rc = wr_sync(w);
   if (rc) return rc;
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_streams; i++) {
-    if (known[i] != ~0ull) lens[i] = known[i];
+    if (known[i] != ~0ull && !comp) lens[i] = known[i];
     total += lens[i];
   }
   // back to back in the stripe's stream order, then one copy to pinned memory
   if (!wr_reserve(w, w->out, total + kAlign, 0)) return ORCGPU_HIP_ERROR;
   uint64_t pos = 0;
   for (uint64_t i = 0; i < n_streams; i++) {
-    if (lens[i]) WR_TRY(hipMemcpyAsync(w->out.p + pos, w->slots.p + streams[i].slot, lens[i], hipMemcpyDeviceToDevice, ctx->stream));
+    const uint8_t* src = comp ? w->zout.p + zslot[i] : w->slots.p + streams[i].slot;
+    if (lens[i]) WR_TRY(hipMemcpyAsync(w->out.p + pos, src, lens[i], hipMemcpyDeviceToDevice, ctx->stream));
     pos += lens[i];
   }
   if (total > w->pinned_cap) {
@@ -389,6 +420,7 @@ int wr_flush(orcgpu_writer* w) {
     m.u64(1, ci ? (uint64_t)w->cols[ci - 1].encoding : 0u);
     footer.msg(2, m);
   }
+  if (comp) footer.b = lzc_original_chunks(footer.b, w->comp_block);
   const uint64_t start = w->written;
   rc = wr_sink(w, w->pinned, total);
   if (rc) return rc;
@@ -436,9 +468,12 @@ int wr_close(orcgpu_writer* w) {
   }
   footer.u64(6, rows);
   footer.u64(9, 0xffffffffull);
+  const bool comp = w->comp != ORCGPU_COMP_NONE;
+  if (comp) footer.b = lzc_original_chunks(footer.b, w->comp_block);
   PbOut ps;
   ps.u64(1, footer.b.size());
-  ps.u64(2, 0);  // CompressionKind::None
+  ps.u64(2, (uint64_t)w->comp);  // CompressionKind (the reference: None)
+  if (comp) ps.u64(3, w->comp_block);
   ps.packed(4, {0, 12});
   ps.u64(5, 0);
   ps.u64(6, 0xffffffffull);
@@ -755,6 +790,7 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
 extern "C" int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* schema, const struct ArrowArray* batch, uint32_t flags) {
   if (!w || !schema || !batch || w->closed) return ORCGPU_INVALID_ARGUMENT;
   if (w->failed) return ORCGPU_UNEXPECTED;
+  w->started = true;
   orcgpu_ctx* ctx = w->ctx;
   {  // ensure!(batch.schema() == self.schema, Unexpected)
     std::vector<WrField> fields;
@@ -828,15 +864,34 @@ extern "C" int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* s
 extern "C" int orcgpu_writer_flush_stripe(orcgpu_writer* w) {
   if (!w || w->closed) return ORCGPU_INVALID_ARGUMENT;
   if (w->failed) return ORCGPU_UNEXPECTED;
+  w->started = true;
   HIP_TRY(w->ctx, hipSetDevice(w->ctx->device));
   int rc = wr_flush(w);
   if (rc) w->failed = true;
   return rc;
 }
 
+extern "C" int orcgpu_writer_set_compression(orcgpu_writer* w, int kind, uint64_t block_size) {
+  if (!w) return ORCGPU_INVALID_ARGUMENT;
+  if (kind == ORCGPU_COMP_ZLIB || kind == ORCGPU_COMP_LZO || kind == ORCGPU_COMP_ZSTD) {
+    set_err(w->ctx, "writer: only Snappy and LZ4 files are written compressed");
+    return ORCGPU_UNSUPPORTED;
+  }
+  const uint64_t B = block_size ? block_size : kLzcDefaultBlock;
+  if ((kind != ORCGPU_COMP_NONE && lzc_codec(kind) < 0) || B > kLzcMaxBlock) return ORCGPU_INVALID_ARGUMENT;
+  if (w->started || w->closed) {
+    set_err(w->ctx, "writer: the compression is set before the first write, flush_stripe or close");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  w->comp = kind;
+  w->comp_block = B;
+  return ORCGPU_OK;
+}
+
 extern "C" int orcgpu_writer_close(orcgpu_writer* w) {
   if (!w || w->closed) return ORCGPU_INVALID_ARGUMENT;
   if (w->failed) return ORCGPU_UNEXPECTED;
+  w->started = true;
   HIP_TRY(w->ctx, hipSetDevice(w->ctx->device));
   int rc = ORCGPU_OK;
   if (w->rows > 0) rc = wr_flush(w);
@@ -897,6 +952,7 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
   w->bits.release();
   w->out.release();
   w->slots.release();
+  w->zout.release();
   if (w->pinned) (void)hipHostFree(w->pinned);
   delete w;
 }

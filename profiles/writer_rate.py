@@ -2,7 +2,14 @@
 memory sink from host batches and from device-resident batches (the same columns in device memory, ORCGPU_ENC_ON_DEVICE), at the
 default stripe size and at 4 MiB; beside it pyarrow.orc.write_table(..., compression="uncompressed") on the same table on the same
 host (Apache ORC C++, the CPU baseline).  GB/s = Arrow bytes of the table in / wall seconds of the whole write (open .. close).
-Usage: python profiles/writer_rate.py [rows]  -> one JSON object on stdout."""
+Usage: python profiles/writer_rate.py [rows]  -> one JSON object on stdout.
+
+--compression snappy|lz4: the writer compresses every stream on the device (ArrowWriterBuilder.with_compression), at the default
+64 MiB stripes; the file sizes are set against the uncompressed file and against pyarrow.orc.write_table(..., compression=...).
+--kernel-stats FILE: folds in the kernel_stats.csv of a `rocprofv3 --kernel-trace --stats` run of the same command (the compression
+kernels, lzc_*, against the writer's other device work)."""
+import argparse
+import csv
 import ctypes as C
 import io
 import json
@@ -88,10 +95,10 @@ class DeviceBatch:
         self.ptrs = []
 
 
-def gpu_write(ctx, batches, schema, sbs, device=None):
+def gpu_write(ctx, batches, schema, sbs, device=None, compression=None):
     out = io.BytesIO()
     t0 = time.perf_counter()
-    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).try_build()
+    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).try_build()
     if device is None:
         for b in batches:
             w.write(b)
@@ -108,8 +115,71 @@ def gpu_write(ctx, batches, schema, sbs, device=None):
     return dt, st, out.getbuffer().nbytes
 
 
+def kernel_stats(path):
+    """rocprofv3's kernel_stats.csv -> the compression kernels' time against the rest of the device work"""
+    rows = list(csv.DictReader(open(path)))
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    lzc = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows if r["Name"].startswith("lzc_")}
+    top = max(rows, key=lambda r: float(r["TotalDurationNs"]))
+    return {"what": "rocprofv3 --kernel-trace --stats of this command, all runs", "all_kernels_ms": round(total / 1e6, 3),
+            "compression_kernels_ms": lzc, "compression_share": round(sum(lzc.values()) * 1e6 / total, 4),
+            "largest_kernel": {"name": top["Name"].split("(")[0], "ms": round(float(top["TotalDurationNs"]) / 1e6, 3)}}
+
+
+def main_compressed(args):
+    n, per_batch = args.rows, 1_000_000
+    rng = np.random.default_rng(1)
+    batches = [lineitem(per_batch, rng) for _ in range(max(1, n // per_batch))]
+    table = batches[0]
+    n = per_batch * len(batches)
+    arrow_bytes = sum(b.nbytes for b in batches)
+    ctx = capi.Context()
+    out = {"rows": n, "columns": table.num_columns, "arrow_bytes": arrow_bytes, "compression": args.compression,
+           "unit": "GB/s of Arrow input (open .. close)", "runs": {}}
+    gpu_write(ctx, batches[:1], table.schema, 64 << 20, compression=args.compression)  # warm-up
+    device = [DeviceBatch(b) for b in batches]
+    for comp in [args.compression, None]:
+        for src in ["host", "device"]:
+            best = None
+            for _ in range(3):
+                r = gpu_write(ctx, batches, table.schema, 64 << 20, device if src == "device" else None, compression=comp)
+                if best is None or r[0] < best[0]:
+                    best = r
+            dt, st, size = best
+            out["runs"]["default 64 MiB, %s batches, %s" % (src, comp or "uncompressed")] = {
+                "seconds": round(dt, 4), "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    for d in device:
+        d.free()
+    runs = out["runs"]
+    key = "default 64 MiB, host batches, %s" % args.compression
+    out["rate_vs_uncompressed"] = round(runs[key]["GB/s"] / runs["default 64 MiB, host batches, uncompressed"]["GB/s"], 3)
+    tt = pa.Table.from_batches(batches)
+    buf = io.BytesIO()
+    t0 = time.perf_counter()
+    po.write_table(tt, buf, compression=args.compression)
+    dt = time.perf_counter() - t0
+    size = runs[key]["file_bytes"]
+    out["file_size"] = {"this": size, "uncompressed": runs["default 64 MiB, host batches, uncompressed"]["file_bytes"],
+                        "pyarrow": buf.getbuffer().nbytes,
+                        "smaller_than_uncompressed": round(runs["default 64 MiB, host batches, uncompressed"]["file_bytes"] / size, 3),
+                        "vs_pyarrow": round(size / buf.getbuffer().nbytes, 3)}
+    out["cpu_baseline"] = {"what": "pyarrow.orc.write_table(compression=%r), same host" % args.compression, "seconds": round(dt, 4),
+                           "GB/s": round(arrow_bytes / dt / 1e9, 3)}
+    if args.kernel_stats:
+        out["kernels"] = kernel_stats(args.kernel_stats)
+    print(json.dumps(out))
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 8_000_000
+    ap = argparse.ArgumentParser()
+    ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
+    ap.add_argument("--compression", choices=["snappy", "lz4"])
+    ap.add_argument("--kernel-stats")
+    args = ap.parse_args()
+    if args.compression:
+        return main_compressed(args)
+    n = args.rows
     per_batch = 1_000_000
     rng = np.random.default_rng(1)
     batches = [lineitem(per_batch, rng) for _ in range(max(1, n // per_batch))]  # (each its own buffers: the device copies hold no more)
