@@ -437,7 +437,8 @@ int orcgpu_encode_fetch(orcgpu_ctx* ctx, const orcgpu_enc_stream* stream, uint8_
 
 /* ---- ArrowWriterBuilder / ArrowWriter (src/arrow_writer.rs:34-156) ----------------------------------------------------------
  * Arrow record batches -> an ORC file, byte for byte the reference writer's: a flat schema of Boolean, Int8..Int64, Float32/64,
- * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no index or statistics.  Every stream is encoded on the
+ * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no index or statistics unless
+ * orcgpu_writer_set_row_index asks for them (below).  Every stream is encoded on the
  * device (the encoders above); a stripe is cut where the reference's would be (after a slice of batch_size rows whose summed
  * encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.  Uncompressed by default (the reference writes
  * CompressionKind::None only); orcgpu_writer_set_compression selects Snappy or LZ4, compressed on the device (below).
@@ -485,6 +486,20 @@ void orcgpu_writer_free(orcgpu_writer* w);
 int orcgpu_writer_set_compression(orcgpu_writer* w, int kind, uint64_t block_size);
 int orcgpu_compress_stream(orcgpu_ctx* ctx, int kind, uint64_t block_size, const void* in, uint64_t n, uint32_t flags, uint8_t* out, uint64_t out_cap,
                            uint64_t* out_len);
+
+/* ---- Row index and statistics of the writer ---------------------------------------------------------------------------------
+ * set_row_index: ROW_INDEX streams and statistics (the reference writes neither).  stride 0 = none (the default: the file is
+ * what it was without the call), else 1 .. 2^31 - 1 rows per row group (ORCGPU_INVALID_ARGUMENT otherwise); legal only before
+ * the first write, flush_stripe or close, like set_compression.  Each stripe is cut into groups of `stride` rows from its first
+ * row; every column, the root struct (0) included, gets a ROW_INDEX stream ahead of its data streams, with a RowIndexEntry per
+ * group: the positions orcgpu_index_entry reads (PRESENT, DATA, LENGTH) and the group's ColumnStatistics.  The stripes'
+ * statistics go in the Metadata section, the file's in Footer.statistics, and Footer.row_index_stride is set.  Compressed
+ * files write the index and Metadata as original chunks.  Statistics: number_of_values (valid values; the root: rows), has_null,
+ * and for integers min / max / sum (the sum left out when the exact sum lies outside i64), for floats min / max / sum as f64
+ * (none at all when a value is NaN), for Utf8 min / max by bytes (over 1024 bytes: lower_bound / upper_bound) and the bytes,
+ * for binaries the bytes, for Booleans the true count.  The stripes, rows and data streams are those of the same writes without
+ * an index (index bytes do not count toward the stripe cut), and a stripe still costs two host waits. */
+int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride);
 
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) ---------------------- */
 /* Milliseconds the device spent in the last orcgpu_decode_staged call, whole call and the RLE

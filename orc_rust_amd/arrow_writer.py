@@ -3,6 +3,7 @@
 
     w = ArrowWriterBuilder("out.orc", schema).with_batch_size(1024).with_stripe_byte_size(64 << 20).try_build()
     w = ArrowWriterBuilder("out.orc", schema).with_compression("snappy").try_build()   # or "lz4"; compressed on the GPU
+    w = ArrowWriterBuilder("out.orc", schema).with_row_index_stride(10000).try_build()  # row index + statistics, on the GPU
     w.write(batch)          # pyarrow.RecordBatch
     w.flush_stripe()
     w.close()
@@ -17,6 +18,7 @@ DEFAULT_BATCH_SIZE = 1024            # arrow_writer.rs:49
 DEFAULT_STRIPE_BYTE_SIZE = 64 << 20  # arrow_writer.rs:51
 DEFAULT_COMPRESSION_BLOCK_SIZE = 262144  # compression.rs:31
 MAX_COMPRESSION_BLOCK_SIZE = (1 << 23) - 1  # a chunk header holds len * 2 + 1 in 24 bits
+MAX_ROW_INDEX_STRIDE = (1 << 31) - 1
 COMPRESSIONS = {None: 0, "none": 0, "snappy": 2, "lz4": 4}  # the codecs the writer compresses with (capi.COMP)
 
 _SCHEMA_BYTES, _ARRAY_BYTES, _RELEASE_AT = 72, 80, {72: 56, 80: 64}  # struct ArrowSchema / ArrowArray, offset of `release`
@@ -50,6 +52,7 @@ class ArrowWriterBuilder:
         self._sink, self._schema, self._ctx = sink, schema, ctx
         self._batch_size, self._stripe_byte_size = DEFAULT_BATCH_SIZE, DEFAULT_STRIPE_BYTE_SIZE
         self._compression, self._block_size = 0, DEFAULT_COMPRESSION_BLOCK_SIZE
+        self._row_index_stride = 0
 
     def with_batch_size(self, n):
         self._batch_size = int(n)
@@ -68,6 +71,17 @@ class ArrowWriterBuilder:
         if block_size <= 0 or block_size > MAX_COMPRESSION_BLOCK_SIZE:
             raise ValueError("block_size must be in 1 .. 2^23 - 1")
         self._compression, self._block_size = COMPRESSIONS[codec], block_size
+        return self
+
+    def with_row_index_stride(self, stride):
+        """Rows per row group of the ROW_INDEX streams and statistics (0, the default: none, the reference's file; Apache ORC's
+        writers use 10000).  The row groups' statistics and positions are computed on the GPU."""
+        if isinstance(stride, bool) or not isinstance(stride, int) and not hasattr(stride, "__index__"):
+            raise ValueError("row_index_stride must be an integer, not %r" % (stride,))
+        stride = int(stride.__index__())
+        if stride < 0 or stride > MAX_ROW_INDEX_STRIDE:
+            raise ValueError("row_index_stride must be 0 (none) or in 1 .. 2^31 - 1")
+        self._row_index_stride = stride
         return self
 
     def try_build(self):
@@ -91,12 +105,14 @@ class ArrowWriterBuilder:
         finally:
             s.release()
         w = ArrowWriter(ctx, out.value, self._schema, fobj)
-        if self._compression:
-            try:
+        try:
+            if self._compression:
                 ctx._check(ctx.L.orcgpu_writer_set_compression(out.value, self._compression, self._block_size))
-            except Exception:
-                w.free()
-                raise
+            if self._row_index_stride:
+                ctx._check(ctx.L.orcgpu_writer_set_row_index(out.value, self._row_index_stride))
+        except Exception:
+            w.free()
+            raise
         w._drain()
         return w
 

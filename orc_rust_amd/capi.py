@@ -29,7 +29,7 @@ EXPORTS = [
     "orcgpu_reader_next_batch",
     "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
     "orcgpu_writer_take_bytes", "orcgpu_writer_stats", "orcgpu_writer_stripe_rows", "orcgpu_writer_free",
-    "orcgpu_writer_set_compression", "orcgpu_compress_stream",
+    "orcgpu_writer_set_compression", "orcgpu_compress_stream", "orcgpu_writer_set_row_index",
 ]
 
 
@@ -238,6 +238,7 @@ def load():
     L.orcgpu_writer_stripe_rows.argtypes = [C.c_void_p, C.c_uint64]
     L.orcgpu_writer_free.argtypes = [C.c_void_p]
     L.orcgpu_writer_set_compression.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    L.orcgpu_writer_set_row_index.argtypes = [C.c_void_p, C.c_uint64]
     L.orcgpu_compress_stream.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64)]
     _lib = L

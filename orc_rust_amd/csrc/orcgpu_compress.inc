@@ -24,9 +24,11 @@ inline uint64_t lzc_room(uint64_t raw, uint64_t B) { return raw + 3 * ((raw + B 
 // Compresses streams i = 0 .. n-1: the raw bytes at d_in + jobs[i].in_off (at most rooms[i] of them), the chunks to
 // d_out + jobs[i].out_off (room: lzc_room(rooms[i], B)).  Their lengths are jobs[i].known, or d_lens[i] on the device when the
 // launches run; after them d_lens[i] holds the compressed lengths.  Enqueued on ctx->stream without a host wait (growing the
-// tables waits: counted in *syncs).
+// tables waits: counted in *syncs).  d_plan / d_chunk_off (optional): where the chunk table is left (the streams' first chunks,
+// n + 1 of them, and the compressed chunks' offsets): valid until the next call.
 int lzc_enqueue(orcgpu_ctx* ctx, int codec, uint64_t B, const uint8_t* d_in, uint8_t* d_out, const std::vector<LzcStream>& jobs,
-                const std::vector<uint64_t>& rooms, uint64_t* d_lens, uint64_t* syncs) {
+                const std::vector<uint64_t>& rooms, uint64_t* d_lens, uint64_t* syncs, const LzcPlan** d_plan_out = nullptr,
+                const uint64_t** d_chunk_off_out = nullptr) {
   const uint32_t n = (uint32_t)jobs.size();
   if (!n) return ORCGPU_OK;
   hipStream_t st = ctx->stream;
@@ -73,6 +75,8 @@ int lzc_enqueue(orcgpu_ctx* ctx, int codec, uint64_t B, const uint8_t* d_in, uin
   if (rc) return rc;
   LZC_TRY(launch(lzc_compose_kernel, max_chunks, true, 256, st, codec, d_in, (const LzcStream*)d_jobs, (const LzcPlan*)d_plan, n, B, S, stride,
                  (const LzcSeg*)d_meta, (const uint8_t*)ctx->lzc_stage.p, (const uint64_t*)d_off, d_out, d_lens));
+  if (d_plan_out) *d_plan_out = d_plan;
+  if (d_chunk_off_out) *d_chunk_off_out = d_off;
   return ORCGPU_OK;
 }
 

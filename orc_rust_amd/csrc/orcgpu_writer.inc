@@ -17,6 +17,14 @@
 // is enqueued, every stream goes through the device compressor (orcgpu_compress.inc) from its slot into a slot of zout, in one
 // launch set, before the first wait; the lengths that wait brings back are the compressed ones.  Stripe footers and the file
 // Footer are written as original chunks.  The cut is unchanged: it is computed over the uncompressed encoders' estimates.
+//
+// Row index (orcgpu_writer_set_row_index; the reference writes none): each stripe is cut into row groups of `stride` rows.  The
+// groups' ColumnStatistics come from one launch set over (column, group) jobs (device/col_stats.hip), enqueued before the
+// stripe's streams; each stream's entry positions are searched in its encoder's run table right after its plan, while the table
+// is alive; compressed files map them to chunk positions after the compressor.  Records, positions and the string minima /
+// maxima come back with the stream lengths, in the same wait.  The host writes a ROW_INDEX stream per column (the root
+// included) ahead of the data, the stripes' statistics as the Metadata section and the file's in the Footer.  Index bytes do
+// not count toward the stripe cut.
 namespace {
 
 // the buffer keeps its contents when it grows (stream-ordered copy)
@@ -65,6 +73,13 @@ struct PbOut {
     b.insert(b.end(), (const uint8_t*)p, (const uint8_t*)p + n);
   }
   void msg(uint32_t field, const PbOut& m) { bytes(field, m.b.data(), m.b.size()); }
+  void sint(uint32_t field, int64_t v) { u64(field, ((uint64_t)v << 1) ^ (uint64_t)(v >> 63)); }
+  void f64(uint32_t field, double v) {
+    key(field, 1);
+    uint8_t x[8];
+    memcpy(x, &v, 8);
+    b.insert(b.end(), x, x + 8);
+  }
   void packed(uint32_t field, const std::vector<uint64_t>& v) {  // [packed = true]: nothing at all when empty
     if (v.empty()) return;
     PbOut m;
@@ -74,7 +89,18 @@ struct PbOut {
 };
 
 struct WrStripe {
-  uint64_t offset, data_length, footer_length, rows;
+  uint64_t offset, data_length, footer_length, rows, index_length;
+};
+
+// ColumnStatistics of a range of rows of one column, as the device's records and the host's merges hold them
+struct WrStat {
+  uint64_t count = 0, bytes = 0, trues = 0;
+  bool has_null = false, has_nan = false;
+  int64_t imin = 0, imax = 0;
+  __int128 isum = 0;  // exact: written when it fits in i64
+  double dmin = 0, dmax = 0, dsum = 0, dsum_lo = 0;
+  std::string smin, smax;          // their first IX_STR_KEEP bytes at most
+  uint64_t smin_len = 0, smax_len = 0;  // and their whole lengths
 };
 
 struct WrCol {
@@ -126,6 +152,12 @@ struct orcgpu_writer {
   uint64_t comp_block = kLzcDefaultBlock;
   bool started = false;
   DevVec zout;
+  // row index (orcgpu_writer_set_row_index): 0 = none; the device tables of a stripe's index and the records' copy on the host
+  uint64_t stride = 0;
+  DevVec ix;
+  uint8_t* ix_pinned = nullptr;
+  size_t ix_pinned_cap = 0;
+  std::vector<std::vector<WrStat>> stripe_stats;  // [stripe][column], column 0 the root
 };
 
 namespace {
@@ -253,13 +285,32 @@ bool wr_reserve(orcgpu_writer* w, DevVec& v, uint64_t n, uint64_t used) {
   return v.reserve(n, used, w->ctx->stream);
 }
 
+// a stream's row index positions (ix_pos_kernel): where group g starts, into pos[g * 4 ..]
+struct WrIxPos {
+  int mode;                    // ix_pos_kernel's
+  uint64_t G, S, n;            // groups, stride, values of the stream (bit streams: bits)
+  const uint64_t* vscan;       // the column's first values per group
+  const uint64_t* bscan;       // ... first string bytes
+  int elem;
+  uint64_t* pos;
+};
+hipError_t wr_ix_pos(orcgpu_ctx* ctx, const WrIxPos* ip, const EncJob* J) {
+  if (!ip || !ip->G) return hipSuccess;
+  const bool runs = J && J->n_runs;
+  return launch(ix_pos_kernel, ip->G, false, 256, ctx->stream, ip->mode, ip->G, ip->S, ip->vscan, ip->bscan, runs ? ip->n : (uint64_t)0, ip->elem,
+                runs ? (const uint32_t*)J->runs : (const uint32_t*)nullptr, runs ? (const uint64_t*)J->offsets : (const uint64_t*)nullptr,
+                runs ? J->d_n_runs : (const uint64_t*)nullptr, runs ? J->d_total : (const uint64_t*)nullptr, ip->pos);
+}
+
 // one stream of the stripe, enqueued: values (device) through the encoder into the slot at *at of w->slots (room: its bound);
-// its length lands in d_lens[li] on the device
-int wr_rle_stream(orcgpu_writer* w, int kind, const void* d_values, uint64_t n, int int_bytes, int is_signed, uint64_t* at, uint64_t li) {
+// its length lands in d_lens[li] on the device.  ip: its row index positions, searched while the run table is the stream's
+int wr_rle_stream(orcgpu_writer* w, int kind, const void* d_values, uint64_t n, int int_bytes, int is_signed, uint64_t* at, uint64_t li,
+                  const WrIxPos* ip = nullptr) {
   orcgpu_ctx* ctx = w->ctx;
   uint64_t* d_lens = (uint64_t*)w->lens.p;
   if (!n) {
     WR_TRY(hipMemsetAsync(d_lens + li, 0, 8, ctx->stream));
+    WR_TRY(wr_ix_pos(ctx, ip, nullptr));
     return ORCGPU_OK;
   }
   EncJob J;
@@ -280,12 +331,13 @@ int wr_rle_stream(orcgpu_writer* w, int kind, const void* d_values, uint64_t n, 
   rc = enc_emit(ctx, J, w->slots.p + *at);
   if (rc) return rc;
   WR_TRY(hipMemcpyAsync(d_lens + li, J.d_total, 8, hipMemcpyDeviceToDevice, ctx->stream));
+  WR_TRY(wr_ix_pos(ctx, ip, &J));
   *at += align_up(room);
   return ORCGPU_OK;
 }
 
 // a bitmap of n bits given as 0 / 1 bytes through BooleanEncoder (boolean.rs:157-169)
-int wr_bool_stream(orcgpu_writer* w, const uint8_t* d_bytes, uint64_t n, uint64_t* at, uint64_t li) {
+int wr_bool_stream(orcgpu_writer* w, const uint8_t* d_bytes, uint64_t n, uint64_t* at, uint64_t li, const WrIxPos* ip = nullptr) {
   orcgpu_ctx* ctx = w->ctx;
   const uint64_t nb = (n + 7) / 8;
   // (the bitmaps of every Boolean / PRESENT stream of the stripe stay until it is written: one region each, at *at of `bits`)
@@ -296,7 +348,7 @@ int wr_bool_stream(orcgpu_writer* w, const uint8_t* d_bytes, uint64_t n, uint64_
   uint8_t* rev = bits + align_up(nb + 8);
   WR_TRY(launch(enc_bytes_to_bits_kernel, nb, false, 256, ctx->stream, d_bytes, n, bits));
   WR_TRY(launch(enc_bool_bytes_kernel, nb, false, 256, ctx->stream, (const uint8_t*)bits, n, rev));
-  return wr_rle_stream(w, 1, rev, nb, 1, 0, at, li);
+  return wr_rle_stream(w, 1, rev, nb, 1, 0, at, li, ip);
 }
 
 // DATA of floats and strings: the bytes themselves (the length is known on the host)
@@ -307,6 +359,173 @@ int wr_copy_stream(orcgpu_writer* w, const uint8_t* d_src, uint64_t n, uint64_t*
   known[li] = n;
   *at += align_up(n);
   return ORCGPU_OK;
+}
+
+
+// ---- row index: statistics on the host ------------------------------------------------------------------------------------
+// a group's record as the device wrote it; side: the string copies
+WrStat wr_stat_of(const WrCol& c, const IxRec& r, const uint8_t* side) {
+  WrStat s;
+  s.count = r.count;
+  s.has_null = r.has_null != 0;
+  if (!r.count) return s;
+  switch (c.stream_kind) {
+    case 0: case 1:
+      s.imin = r.imin;
+      s.imax = r.imax;
+      s.isum = (__int128)(((unsigned __int128)(uint64_t)r.sum_hi << 64) | r.sum_lo);
+      break;
+    case 2: s.dmin = r.dmin; s.dmax = r.dmax; s.dsum = r.dsum; s.dsum_lo = r.dsum_lo; s.has_nan = r.has_nan != 0; break;
+    case 3: s.trues = r.trues; break;
+    default:
+      s.bytes = r.bytes;
+      if (c.orc_kind == 7) {
+        const uint32_t a = std::min(r.smin_len, IX_STR_KEEP), b = std::min(r.smax_len, IX_STR_KEEP);
+        s.smin.assign((const char*)side + r.side, a);
+        s.smax.assign((const char*)side + r.side + a, b);
+        s.smin_len = r.smin_len;
+        s.smax_len = r.smax_len;
+      }
+      break;
+  }
+  return s;
+}
+
+// byte order of two strings known by their first IX_STR_KEEP bytes (two cut ones with equal prefixes have the same bound)
+int wr_str_cmp(const std::string& a, uint64_t la, const std::string& b, uint64_t lb) {
+  const int c = memcmp(a.data(), b.data(), std::min(a.size(), b.size()));
+  if (c) return c;
+  if (a.size() == b.size()) return a.size() == la && b.size() == lb ? (la < lb ? -1 : (la > lb ? 1 : 0)) : 0;
+  return a.size() < b.size() ? -1 : 1;
+}
+
+void wr_dd_merge(double& hi, double& lo, double h2, double l2) {
+#pragma clang fp contract(off)
+  if (!std::isfinite(hi) || !std::isfinite(h2)) {
+    hi += h2;
+    lo = 0;
+    return;
+  }
+  const double s = hi + h2, bb = s - hi;
+  double e = (hi - (s - bb)) + (h2 - bb);
+  e += lo + l2;
+  hi = s + e;
+  lo = e - (hi - s);
+}
+
+// b's rows follow a's (minimum / maximum: the first of equal values stays)
+void wr_stat_merge(WrStat& a, const WrStat& b) {
+  a.has_null |= b.has_null;
+  a.has_nan |= b.has_nan;
+  if (b.count) {
+    const bool first = a.count == 0;
+    if (first || b.imin < a.imin) a.imin = b.imin;
+    if (first || b.imax > a.imax) a.imax = b.imax;
+    if (first || b.dmin < a.dmin) a.dmin = b.dmin;
+    if (first || b.dmax > a.dmax) a.dmax = b.dmax;
+    if (first || wr_str_cmp(b.smin, b.smin_len, a.smin, a.smin_len) < 0) a.smin = b.smin, a.smin_len = b.smin_len;
+    if (first || wr_str_cmp(b.smax, b.smax_len, a.smax, a.smax_len) > 0) a.smax = b.smax, a.smax_len = b.smax_len;
+    a.isum += b.isum;
+    if (first) a.dsum = b.dsum, a.dsum_lo = b.dsum_lo;
+    else wr_dd_merge(a.dsum, a.dsum_lo, b.dsum, b.dsum_lo);
+    a.bytes += b.bytes;
+    a.trues += b.trues;
+  }
+  a.count += b.count;
+}
+
+// StringStatisticsImpl's bounds of a value longer than 1024 bytes: the longest prefix of at most 1024 bytes that ends at a
+// character boundary; for the upper bound its last character's code point incremented
+std::string wr_lower_bound(const std::string& s) {
+  size_t cut = 1024;
+  while (cut > 0 && ((uint8_t)s[cut] & 0xc0) == 0x80) cut--;
+  return s.substr(0, cut);
+}
+// (trailing U+10FFFF have no successor: they are dropped first; false when nothing is left, and no bound is an upper bound)
+bool wr_upper_bound(const std::string& s, std::string& out) {
+  std::string p = wr_lower_bound(s);
+  uint32_t cp = 0;
+  size_t k = 0;
+  for (;;) {
+    if (p.empty()) return false;
+    k = p.size() - 1;
+    while (k > 0 && ((uint8_t)p[k] & 0xc0) == 0x80) k--;
+    const uint8_t h = (uint8_t)p[k];
+    const size_t n = p.size() - k;
+    cp = n == 1 ? h : (h & (0xffu >> (n + 1)));
+    for (size_t i = 1; i < n; i++) cp = (cp << 6) | ((uint8_t)p[k + i] & 0x3f);
+    if (cp < 0x10ffff) break;
+    p.resize(k);
+  }
+  cp++;
+  if (cp >= 0xd800 && cp < 0xe000) cp = 0xe000;
+  std::string e;
+  if (cp < 0x80) e += (char)cp;
+  else if (cp < 0x800) e += (char)(0xc0 | (cp >> 6)), e += (char)(0x80 | (cp & 0x3f));
+  else if (cp < 0x10000) e += (char)(0xe0 | (cp >> 12)), e += (char)(0x80 | ((cp >> 6) & 0x3f)), e += (char)(0x80 | (cp & 0x3f));
+  else
+    e += (char)(0xf0 | (cp >> 18)), e += (char)(0x80 | ((cp >> 12) & 0x3f)), e += (char)(0x80 | ((cp >> 6) & 0x3f)), e += (char)(0x80 | (cp & 0x3f));
+  out = p.substr(0, k) + e;
+  return true;
+}
+
+// ColumnStatistics (c: nullptr for the root struct, whose values are its rows)
+PbOut wr_stat_msg(const WrCol* c, const WrStat& s) {
+  PbOut m;
+  m.u64(1, s.count);
+  if (c && s.count) {
+    PbOut t;
+    switch (c->stream_kind) {
+      case 0: case 1:
+        t.sint(1, s.imin);
+        t.sint(2, s.imax);
+        if (s.isum >= (__int128)INT64_MIN && s.isum <= (__int128)INT64_MAX) t.sint(3, (int64_t)s.isum);
+        m.msg(2, t);
+        break;
+      case 2:
+        if (s.has_nan) break;  // (no DoubleStatistics: a reader would take an absent bound for 0)
+        t.f64(1, s.dmin);
+        t.f64(2, s.dmax);
+        t.f64(3, std::isfinite(s.dsum) ? s.dsum + s.dsum_lo : s.dsum);
+        m.msg(3, t);
+        break;
+      case 3:
+        t.packed(1, {s.trues});
+        m.msg(5, t);
+        break;
+      default:
+        if (c->orc_kind == 8) {
+          t.sint(1, (int64_t)s.bytes);
+          m.msg(8, t);
+          break;
+        }
+        std::string ub;
+        if (s.smax_len > 1024 && !wr_upper_bound(s.smax, ub)) break;  // (no upper bound: no StringStatistics, nothing is pruned)
+        if (s.smin_len <= 1024) t.bytes(1, s.smin.data(), s.smin.size());
+        if (s.smax_len <= 1024) t.bytes(2, s.smax.data(), s.smax.size());
+        t.sint(3, (int64_t)s.bytes);
+        if (s.smin_len > 1024) {
+          const std::string lb = wr_lower_bound(s.smin);
+          t.bytes(4, lb.data(), lb.size());
+        }
+        if (s.smax_len > 1024) t.bytes(5, ub.data(), ub.size());
+        m.msg(4, t);
+        break;
+    }
+  }
+  m.u64(10, s.has_null ? 1 : 0);
+  return m;
+}
+
+// the positions of a column's streams for one group, PRESENT, DATA, LENGTH (form: 1 bytes, 2 run-length, 3 bits over byte runs)
+void wr_positions(const uint64_t* pos, uint64_t G, uint64_t g, bool comp, const std::vector<std::pair<uint64_t, int>>& streams, std::vector<uint64_t>& out) {
+  for (auto& st : streams) {
+    const uint64_t* p = pos + (st.first * G + g) * 4;
+    out.push_back(p[0]);
+    if (comp) out.push_back(p[1]);
+    if (st.second >= 2) out.push_back(p[2]);
+    if (st.second == 3) out.push_back(p[3]);
+  }
 }
 
 // StripeWriter::finish_stripe (writer/stripe.rs:109-165) + ArrowWriter::flush_stripe.  Every stream of every column is enqueued
@@ -333,29 +552,119 @@ int wr_flush(orcgpu_writer* w) {
   std::vector<uint64_t> known(n_streams, ~0ull);
   uint64_t at = 0;
   int rc = ORCGPU_OK;
+  // row index: the groups' statistics, enqueued ahead of the streams (jobs: column * G + group)
+  const size_t nc = w->cols.size();
+  const bool indexed = w->stride > 0;
+  const uint64_t S = w->stride, G = indexed ? (w->rows + S - 1) / S : 0, NJ = nc * G;
+  uint64_t o_cols = 0, o_cnt = 0, o_vscan = 0, o_blen = 0, o_bscan = 0, o_slen = 0, o_soff = 0, o_recs = 0, o_pos = 0, o_side = 0, ix_span = 0;
+  std::vector<std::vector<std::pair<uint64_t, int>>> ix_streams(nc);  // a column's streams (index, position form), PRESENT, DATA, LENGTH
+  if (NJ) {
+    if (NJ >= 0x7fffffffull) {
+      set_err(ctx, "writer: %llu row groups in one stripe (fewer than 2^31)", (unsigned long long)NJ);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    uint64_t side_bound = 0;
+    for (auto& c : w->cols)
+      if (c.orc_kind == 7) side_bound += std::min<uint64_t>(2ull * IX_STR_KEEP * G, 2 * c.n_bytes);
+    Bump X;
+    o_cols = X.take(nc * sizeof(IxCol));
+    o_cnt = X.take(NJ * 8);
+    o_vscan = X.take((NJ + 1) * 8);
+    o_blen = X.take(NJ * 8);
+    o_bscan = X.take((NJ + 1) * 8);
+    o_slen = X.take(NJ * 8);
+    o_soff = X.take((NJ + 1) * 8);
+    o_recs = X.take(NJ * sizeof(IxRec));  // (from here on: brought back)
+    o_pos = X.take(n_streams * G * 32);
+    o_side = X.take(side_bound);
+    ix_span = X.off - o_recs;
+    if (!wr_reserve(w, w->ix, X.off + kAlign, 0)) {
+      set_err(ctx, "writer: out of device memory (%llu bytes of row index)", (unsigned long long)X.off);
+      return ORCGPU_HIP_ERROR;
+    }
+    if (ix_span > w->ix_pinned_cap) {
+      if (w->ix_pinned) {
+        (void)hipHostFree(w->ix_pinned);
+        w->round_trips++;  // (hipHostFree waits for the device)
+      }
+      w->ix_pinned = nullptr;
+      w->ix_pinned_cap = 0;
+      WR_TRY(hipHostMalloc((void**)&w->ix_pinned, ix_span + ix_span / 2, 0));
+      w->ix_pinned_cap = ix_span + ix_span / 2;
+    }
+    uint8_t* x = w->ix.p;
+    IxCol* d_cols = (IxCol*)(x + o_cols);
+    for (uint32_t i0 = 0; i0 < nc; i0 += IX_COLS_PER_ARG) {
+      IxColArgs a{};
+      a.at = i0;
+      a.n = std::min<uint32_t>(IX_COLS_PER_ARG, (uint32_t)nc - i0);
+      for (uint32_t i = 0; i < a.n; i++) {
+        const WrCol& c = w->cols[i0 + i];
+        a.c[i] = IxCol{c.pres.p, c.vals.p, c.data.p, c.stream_kind, c.elem, c.orc_kind == 7, 0};
+      }
+      WR_TRY(launch(ix_put_cols_kernel, (uint64_t)1, true, 64, ctx->stream, a, d_cols));
+    }
+    uint64_t *d_cnt = (uint64_t*)(x + o_cnt), *d_vscan = (uint64_t*)(x + o_vscan), *d_blen = (uint64_t*)(x + o_blen), *d_bscan = (uint64_t*)(x + o_bscan),
+             *d_slen = (uint64_t*)(x + o_slen), *d_soff = (uint64_t*)(x + o_soff);
+    IxRec* d_recs = (IxRec*)(x + o_recs);
+    const IxCol* cc = d_cols;
+    WR_TRY(launch(ix_count_kernel, NJ, true, 256, ctx->stream, cc, w->rows, S, G, d_cnt));
+    WR_TRY(launch(ix_scan_kernel, (uint64_t)1, true, 1024, ctx->stream, (const uint64_t*)d_cnt, NJ, d_vscan));
+    WR_TRY(launch(ix_bytes_kernel, NJ, true, 256, ctx->stream, cc, G, (const uint64_t*)d_cnt, (const uint64_t*)d_vscan, d_blen));
+    WR_TRY(launch(ix_scan_kernel, (uint64_t)1, true, 1024, ctx->stream, (const uint64_t*)d_blen, NJ, d_bscan));
+    WR_TRY(launch(ix_stats_kernel, NJ, true, 256, ctx->stream, cc, w->rows, S, G, (const uint64_t*)d_cnt, (const uint64_t*)d_vscan, (const uint64_t*)d_bscan,
+                  d_recs, d_slen));
+    WR_TRY(launch(ix_scan_kernel, (uint64_t)1, true, 1024, ctx->stream, (const uint64_t*)d_slen, NJ, d_soff));
+    WR_TRY(launch(ix_side_kernel, NJ, true, 256, ctx->stream, cc, G, (const uint64_t*)d_soff, d_recs, x + o_side));
+  }
+  // a stream's positions: ix_pos_kernel's mode, the values (bits) of the stream
+  auto ixp = [&](int mode, size_t ci, uint64_t n, uint64_t li, int form) -> WrIxPos {
+    if (!NJ) return WrIxPos{mode, 0, 0, 0, nullptr, nullptr, 0, nullptr};
+    ix_streams[ci].push_back({li, form});
+    uint8_t* x = w->ix.p;
+    return WrIxPos{mode, G, S, n, (const uint64_t*)(x + o_vscan) + ci * G, (const uint64_t*)(x + o_bscan) + ci * G, w->cols[ci].elem,
+                   (uint64_t*)(x + o_pos) + li * G * 4};
+  };
   for (size_t ci = 0; ci < w->cols.size(); ci++) {
     WrCol& c = w->cols[ci];
     const uint32_t column = (uint32_t)ci + 1;
+    // (the positions list PRESENT first: its stream index is known before it is written)
+    const uint64_t li_present = streams.size() + 1 + (c.stream_kind == 4);
+    if (c.present) ixp(0, ci, c.rows, li_present, 3);
     uint64_t li = streams.size();
     streams.push_back(St{1, column, at});
+    WrIxPos ip;
     switch (c.stream_kind) {
-      case 0: rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 1, &at, li); break;
-      case 1: rc = wr_rle_stream(w, 1, c.vals.p, c.n_valid, 1, 0, &at, li); break;
-      case 2: rc = wr_copy_stream(w, c.vals.p, c.n_valid * (uint64_t)c.elem, &at, li, known); break;
-      case 3: rc = wr_bool_stream(w, c.vals.p, c.n_valid, &at, li); break;
-      default: rc = wr_copy_stream(w, c.data.p, c.n_bytes, &at, li, known); break;
+      case 0: ip = ixp(1, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 1, &at, li, &ip); break;
+      case 1: ip = ixp(2, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 1, c.vals.p, c.n_valid, 1, 0, &at, li, &ip); break;
+      case 2:
+        ip = ixp(4, ci, c.n_valid, li, 1);
+        rc = wr_copy_stream(w, c.vals.p, c.n_valid * (uint64_t)c.elem, &at, li, known);
+        if (!rc && wr_ix_pos(ctx, &ip, nullptr) != hipSuccess) rc = ORCGPU_HIP_ERROR;
+        break;
+      case 3: ip = ixp(3, ci, c.n_valid, li, 3); rc = wr_bool_stream(w, c.vals.p, c.n_valid, &at, li, &ip); break;
+      default:
+        ip = ixp(5, ci, c.n_valid, li, 1);
+        rc = wr_copy_stream(w, c.data.p, c.n_bytes, &at, li, known);
+        if (!rc && wr_ix_pos(ctx, &ip, nullptr) != hipSuccess) rc = ORCGPU_HIP_ERROR;
+        break;
     }
     if (rc) return rc;
     if (c.stream_kind == 4) {
       li = streams.size();
       streams.push_back(St{2, column, at});
-      rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li);
+      ip = ixp(1, ci, c.n_valid, li, 2);
+      rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li, &ip);
       if (rc) return rc;
     }
     if (c.present) {
       li = streams.size();
       streams.push_back(St{0, column, at});
-      rc = wr_bool_stream(w, c.pres.p, c.rows, &at, li);
+      if (NJ) {
+        uint8_t* x = w->ix.p;
+        ip = WrIxPos{0, G, S, c.rows, (const uint64_t*)(x + o_vscan) + ci * G, nullptr, 0, (uint64_t*)(x + o_pos) + li * G * 4};
+      }
+      rc = wr_bool_stream(w, c.pres.p, c.rows, &at, li, NJ ? &ip : nullptr);
       if (rc) return rc;
     }
   }
@@ -376,13 +685,55 @@ int wr_flush(orcgpu_writer* w) {
       set_err(ctx, "writer: out of device memory (%llu bytes of compressed stripe)", (unsigned long long)zat);
       return ORCGPU_HIP_ERROR;
     }
-    rc = lzc_enqueue(ctx, lzc_codec(w->comp), w->comp_block, w->slots.p, w->zout.p, jobs, rooms, (uint64_t*)w->lens.p, &w->round_trips);
+    const LzcPlan* d_plan = nullptr;
+    const uint64_t* d_chunk_off = nullptr;
+    rc = lzc_enqueue(ctx, lzc_codec(w->comp), w->comp_block, w->slots.p, w->zout.p, jobs, rooms, (uint64_t*)w->lens.p, &w->round_trips, &d_plan, &d_chunk_off);
     if (rc) return rc;
+    if (NJ)
+      WR_TRY(launch(ix_map_kernel, n_streams * G, false, 256, ctx->stream, n_streams * G, G, w->comp_block, d_plan, d_chunk_off, (uint64_t*)(w->ix.p + o_pos)));
   }
+  // the row index comes back with the lengths
+  if (NJ) WR_TRY(hipMemcpyAsync(w->ix_pinned, w->ix.p + o_recs, ix_span, hipMemcpyDeviceToHost, ctx->stream));
   std::vector<uint64_t> lens(n_streams, 0);
   if (n_streams) WR_TRY(hipMemcpyAsync(lens.data(), w->lens.p, n_streams * 8, hipMemcpyDeviceToHost, ctx->stream));
   rc = wr_sync(w);
   if (rc) return rc;
+  // ROW_INDEX streams (column 0 first) and the stripe's statistics
+  std::vector<std::vector<uint8_t>> index;
+  if (indexed) {
+    const IxRec* recs = (const IxRec*)w->ix_pinned;
+    const uint64_t* pos = (const uint64_t*)(w->ix_pinned + (o_pos - o_recs));
+    const uint8_t* side = w->ix_pinned + (o_side - o_recs);
+    std::vector<WrStat> stripe(nc + 1);
+    stripe[0].count = w->rows;
+    PbOut root;
+    for (uint64_t g = 0; g < G; g++) {
+      WrStat s;
+      s.count = std::min(S, w->rows - g * S);
+      PbOut e;
+      e.msg(2, wr_stat_msg(nullptr, s));
+      root.msg(1, e);
+    }
+    index.push_back(root.b);
+    for (size_t ci = 0; ci < nc; ci++) {
+      PbOut ri;
+      std::vector<uint64_t> p;
+      for (uint64_t g = 0; g < G; g++) {
+        const WrStat s = wr_stat_of(w->cols[ci], recs[ci * G + g], side);
+        wr_stat_merge(stripe[ci + 1], s);
+        p.clear();
+        wr_positions(pos, G, g, comp, ix_streams[ci], p);
+        PbOut e;
+        e.packed(1, p);
+        e.msg(2, wr_stat_msg(&w->cols[ci], s));
+        ri.msg(1, e);
+      }
+      index.push_back(ri.b);
+    }
+    if (comp)
+      for (auto& b : index) b = lzc_original_chunks(b, w->comp_block);
+    w->stripe_stats.push_back(std::move(stripe));
+  }
   uint64_t total = 0;
   for (uint64_t i = 0; i < n_streams; i++) {
     if (known[i] != ~0ull && !comp) lens[i] = known[i];
@@ -408,6 +759,15 @@ int wr_flush(orcgpu_writer* w) {
   rc = wr_sync(w);
   if (rc) return rc;
   PbOut footer;
+  uint64_t index_length = 0;
+  for (size_t ci = 0; ci < index.size(); ci++) {
+    PbOut m;
+    m.u64(1, 6);  // ROW_INDEX
+    m.u64(2, ci);
+    m.u64(3, index[ci].size());
+    footer.msg(1, m);
+    index_length += index[ci].size();
+  }
   for (uint64_t i = 0; i < n_streams; i++) {
     PbOut m;
     m.u64(1, (uint64_t)streams[i].kind);
@@ -422,11 +782,15 @@ int wr_flush(orcgpu_writer* w) {
   }
   if (comp) footer.b = lzc_original_chunks(footer.b, w->comp_block);
   const uint64_t start = w->written;
+  for (auto& b : index) {
+    rc = wr_sink(w, b.data(), b.size());
+    if (rc) return rc;
+  }
   rc = wr_sink(w, w->pinned, total);
   if (rc) return rc;
   rc = wr_sink(w, footer.b.data(), footer.b.size());
   if (rc) return rc;
-  w->stripes.push_back(WrStripe{start, total, footer.b.size(), w->rows});
+  w->stripes.push_back(WrStripe{start, total, footer.b.size(), w->rows, index_length});
   w->rows = 0;
   for (auto& c : w->cols) c.rows = c.n_valid = c.n_bytes = 0;
   w->base_rle = 0;
@@ -446,7 +810,7 @@ int wr_close(orcgpu_writer* w) {
   PbOut footer;
   uint64_t body = 0, rows = 0;
   for (auto& s : w->stripes) {
-    body += s.data_length + s.footer_length;
+    body += s.index_length + s.data_length + s.footer_length;
     rows += s.rows;
   }
   footer.u64(1, 3);
@@ -454,7 +818,7 @@ int wr_close(orcgpu_writer* w) {
   for (auto& s : w->stripes) {
     PbOut m;
     m.u64(1, s.offset);
-    m.u64(2, 0);
+    m.u64(2, s.index_length);
     m.u64(3, s.data_length);
     m.u64(4, s.footer_length);
     m.u64(5, s.rows);
@@ -467,18 +831,37 @@ int wr_close(orcgpu_writer* w) {
     footer.msg(4, t);
   }
   footer.u64(6, rows);
-  footer.u64(9, 0xffffffffull);
   const bool comp = w->comp != ORCGPU_COMP_NONE;
+  PbOut metadata;
+  if (w->stride) {
+    // Footer.statistics: the stripes' merged; Metadata: a StripeStatistics per stripe
+    std::vector<WrStat> file(w->cols.size() + 1);
+    for (auto& ss : w->stripe_stats) {
+      PbOut m;
+      for (size_t ci = 0; ci < ss.size(); ci++) {
+        m.msg(1, wr_stat_msg(ci ? &w->cols[ci - 1] : nullptr, ss[ci]));
+        wr_stat_merge(file[ci], ss[ci]);
+      }
+      metadata.msg(1, m);
+    }
+    file[0].has_null = false;
+    for (size_t ci = 0; ci < file.size(); ci++) footer.msg(7, wr_stat_msg(ci ? &w->cols[ci - 1] : nullptr, file[ci]));
+    footer.u64(8, w->stride);
+    if (comp) metadata.b = lzc_original_chunks(metadata.b, w->comp_block);
+  }
+  footer.u64(9, 0xffffffffull);
   if (comp) footer.b = lzc_original_chunks(footer.b, w->comp_block);
   PbOut ps;
   ps.u64(1, footer.b.size());
   ps.u64(2, (uint64_t)w->comp);  // CompressionKind (the reference: None)
   if (comp) ps.u64(3, w->comp_block);
   ps.packed(4, {0, 12});
-  ps.u64(5, 0);
+  ps.u64(5, metadata.b.size());
   ps.u64(6, 0xffffffffull);
   ps.bytes(8000, "ORC", 3);
-  int rc = wr_sink(w, footer.b.data(), footer.b.size());
+  int rc = wr_sink(w, metadata.b.data(), metadata.b.size());
+  if (rc) return rc;
+  rc = wr_sink(w, footer.b.data(), footer.b.size());
   if (rc) return rc;
   rc = wr_sink(w, ps.b.data(), ps.b.size());
   if (rc) return rc;
@@ -888,6 +1271,20 @@ extern "C" int orcgpu_writer_set_compression(orcgpu_writer* w, int kind, uint64_
   return ORCGPU_OK;
 }
 
+extern "C" int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride) {
+  if (!w) return ORCGPU_INVALID_ARGUMENT;
+  if (stride > 0x7fffffffull) {
+    set_err(w->ctx, "writer: the row index stride is 0 (none) or 1 .. 2^31 - 1");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (w->started || w->closed) {
+    set_err(w->ctx, "writer: the row index is set before the first write, flush_stripe or close");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  w->stride = stride;
+  return ORCGPU_OK;
+}
+
 extern "C" int orcgpu_writer_close(orcgpu_writer* w) {
   if (!w || w->closed) return ORCGPU_INVALID_ARGUMENT;
   if (w->failed) return ORCGPU_UNEXPECTED;
@@ -953,6 +1350,8 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
   w->out.release();
   w->slots.release();
   w->zout.release();
+  w->ix.release();
   if (w->pinned) (void)hipHostFree(w->pinned);
+  if (w->ix_pinned) (void)hipHostFree(w->ix_pinned);
   delete w;
 }

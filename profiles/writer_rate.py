@@ -7,7 +7,9 @@ Usage: python profiles/writer_rate.py [rows]  -> one JSON object on stdout.
 --compression snappy|lz4: the writer compresses every stream on the device (ArrowWriterBuilder.with_compression), at the default
 64 MiB stripes; the file sizes are set against the uncompressed file and against pyarrow.orc.write_table(..., compression=...).
 --kernel-stats FILE: folds in the kernel_stats.csv of a `rocprofv3 --kernel-trace --stats` run of the same command (the compression
-kernels, lzc_*, against the writer's other device work)."""
+kernels, lzc_*, against the writer's other device work).
+--row-index-stride N: the writer with ROW_INDEX streams and statistics (ArrowWriterBuilder.with_row_index_stride) against the same
+writes without them, uncompressed and with Snappy; with --kernel-stats, the row index kernels' (ix_*) share of the device time."""
 import argparse
 import csv
 import ctypes as C
@@ -95,10 +97,10 @@ class DeviceBatch:
         self.ptrs = []
 
 
-def gpu_write(ctx, batches, schema, sbs, device=None, compression=None):
+def gpu_write(ctx, batches, schema, sbs, device=None, compression=None, stride=0):
     out = io.BytesIO()
     t0 = time.perf_counter()
-    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).try_build()
+    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).with_row_index_stride(stride).try_build()
     if device is None:
         for b in batches:
             w.write(b)
@@ -171,12 +173,49 @@ def main_compressed(args):
     print(json.dumps(out))
 
 
+def main_indexed(args):
+    n, per_batch = args.rows, 1_000_000
+    rng = np.random.default_rng(1)
+    batches = [lineitem(per_batch, rng) for _ in range(max(1, n // per_batch))]
+    table = batches[0]
+    n = per_batch * len(batches)
+    arrow_bytes = sum(b.nbytes for b in batches)
+    ctx = capi.Context()
+    out = {"rows": n, "columns": table.num_columns, "arrow_bytes": arrow_bytes, "row_index_stride": args.row_index_stride,
+           "unit": "GB/s of Arrow input (open .. close), host batches, 64 MiB stripes, best of 3", "runs": {}, "rate_vs_unindexed": {}}
+    gpu_write(ctx, batches[:1], table.schema, 64 << 20, stride=args.row_index_stride)  # warm-up
+    for comp in [None, "snappy"]:
+        for stride in [args.row_index_stride, 0]:
+            best = None
+            for _ in range(3):
+                r = gpu_write(ctx, batches, table.schema, 64 << 20, compression=comp, stride=stride)
+                if best is None or r[0] < best[0]:
+                    best = r
+            dt, st, size = best
+            out["runs"]["%s, %s" % (comp or "uncompressed", "stride %d" % stride if stride else "no index")] = {
+                "seconds": round(dt, 4), "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+        runs = out["runs"]
+        c = comp or "uncompressed"
+        out["rate_vs_unindexed"][c] = round(runs["%s, stride %d" % (c, args.row_index_stride)]["GB/s"] / runs["%s, no index" % c]["GB/s"], 3)
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        ix = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows if r["Name"].startswith("ix_")}
+        out["kernels"] = {"what": "rocprofv3 --kernel-trace --stats of this command, all runs", "all_kernels_ms": round(total / 1e6, 3),
+                          "row_index_kernels_ms": ix, "row_index_share": round(sum(ix.values()) * 1e6 / total, 4)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
     ap.add_argument("--compression", choices=["snappy", "lz4"])
     ap.add_argument("--kernel-stats")
+    ap.add_argument("--row-index-stride", type=int, default=0)
     args = ap.parse_args()
+    if args.row_index_stride:
+        return main_indexed(args)
     if args.compression:
         return main_compressed(args)
     n = args.rows
