@@ -31,7 +31,14 @@ struct IxColArgs {
 
 struct IxRec {  // one job's statistics, 128 bytes (the host reads them as they are)
   uint64_t count, bytes, trues;
-  int64_t imin, imax;
+  union {  // integers: the minimum; floats: the sum of the values of magnitude >= 2^960, scaled by 2^-64 (a double-double)
+    int64_t imin;
+    double dbig;
+  };
+  union {
+    int64_t imax;
+    double dbig_lo;
+  };
   uint64_t sum_lo;
   int64_t sum_hi;  // integer sum: sum_hi:sum_lo, two's complement
   double dmin, dmax, dsum, dsum_lo;
@@ -136,6 +143,13 @@ __device__ __forceinline__ void ix_dd_merge(double& hi, double& lo, double h2, d
   hi = s + e;
   lo = e - (hi - s);
 }
+// a double-double's merge where either may be infinite or NaN (then the sum is what any order gives)
+__device__ __forceinline__ void ix_dd_merge_inf(double& hi, double& lo, double h2, double l2) {
+  if (__builtin_isfinite(hi) && __builtin_isfinite(h2)) ix_dd_merge(hi, lo, h2, l2);
+  else hi = hi + h2, lo = 0;
+}
+#define IX_BIG 0x1p960         // float values at or above this magnitude are summed apart, scaled by IX_BIG_SCALE
+#define IX_BIG_SCALE 0x1p-64
 
 // strings: the first 8 bytes, big-endian, zero-padded
 __device__ __forceinline__ uint64_t ix_key(const uint8_t* p, uint32_t len) {
@@ -161,6 +175,7 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
   __shared__ uint64_t l0[256], l1[256], l2[256];
   __shared__ uint64_t m0[256], m1[256], m2[256];
   __shared__ uint32_t n0[256], n1[256];
+  __shared__ double b0[256], b1[256];
   const uint32_t t = threadIdx.x;
   const uint64_t j = blockIdx.x, c = j / G, g = j % G;
   const IxCol col = cols[c];
@@ -206,7 +221,10 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     R.sum_lo = m0[0];
     R.sum_hi = (int64_t)m1[0];
   } else if (col.kind == 2) {  // floats as f64: min / max (the first of equal values, as a sequential writer keeps it), NaN, sum
-    double mn = 0, mx = 0, hi = 0, lo = 0;
+    // The sum is two double-doubles: values below 2^960 in magnitude, and the others scaled by 2^-64 (exact for them).  Neither
+    // can overflow for fewer than 2^63 values, so the sum does not depend on the order (the host adds them: wr_stat_msg); an
+    // infinite input makes the second one infinite.
+    double mn = 0, mx = 0, hi = 0, lo = 0, bhi = 0, blo = 0;
     uint64_t imn = ~0ull, imx = ~0ull;
     uint32_t nan = 0;
     for (uint64_t i = t; i < n; i += 256) {
@@ -218,8 +236,9 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
       }
       if (imn == ~0ull || x < mn) mn = x, imn = i;
       if (imx == ~0ull || x > mx) mx = x, imx = i;
-      if (__builtin_isfinite(hi)) ix_dd_add(hi, lo, x);
-      else hi += x;
+      if (__builtin_fabs(x) < IX_BIG) ix_dd_add(hi, lo, x);
+      else if (__builtin_isfinite(bhi)) ix_dd_add(bhi, blo, x * IX_BIG_SCALE);
+      else bhi += x;
     }
     double* d0 = (double*)l0;
     double* d1 = (double*)l1;
@@ -232,6 +251,8 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     dh[t] = hi;
     dl[t] = lo;
     n0[t] = nan;
+    b0[t] = bhi;
+    b1[t] = blo;
     __syncthreads();
     for (uint32_t d = 128; d > 0; d >>= 1) {
       if (t < d) {
@@ -239,11 +260,13 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
         if (ib != ~0ull && (ia == ~0ull || d0[t + d] < d0[t] || (d0[t + d] == d0[t] && ib < ia))) d0[t] = d0[t + d], l2[t] = ib;
         const uint64_t xa = m2[t], xb = m2[t + d];
         if (xb != ~0ull && (xa == ~0ull || d1[t + d] > d1[t] || (d1[t + d] == d1[t] && xb < xa))) d1[t] = d1[t + d], m2[t] = xb;
-        double h = dh[t], l = dl[t];
-        if (__builtin_isfinite(h) && __builtin_isfinite(dh[t + d])) ix_dd_merge(h, l, dh[t + d], dl[t + d]);
-        else h = h + dh[t + d], l = 0;
+        double h = dh[t], l = dl[t], bh = b0[t], bl = b1[t];
+        ix_dd_merge(h, l, dh[t + d], dl[t + d]);
+        ix_dd_merge_inf(bh, bl, b0[t + d], b1[t + d]);
         dh[t] = h;
         dl[t] = l;
+        b0[t] = bh;
+        b1[t] = bl;
         n0[t] |= n0[t + d];
       }
       __syncthreads();
@@ -252,6 +275,8 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     R.dmax = d1[0];
     R.dsum = dh[0];
     R.dsum_lo = dl[0];
+    R.dbig = b0[0];
+    R.dbig_lo = b1[0];
     R.has_nan = n0[0];
   } else if (col.kind == 3) {  // Boolean: trues
     uint64_t tr = 0;

@@ -99,6 +99,7 @@ struct WrStat {
   int64_t imin = 0, imax = 0;
   __int128 isum = 0;  // exact: written when it fits in i64
   double dmin = 0, dmax = 0, dsum = 0, dsum_lo = 0;
+  double dbig = 0, dbig_lo = 0;  // the sum of the values of magnitude >= 2^960, scaled by 2^-64 (col_stats.hip: IX_BIG)
   std::string smin, smax;          // their first IX_STR_KEEP bytes at most
   uint64_t smin_len = 0, smax_len = 0;  // and their whole lengths
 };
@@ -375,7 +376,7 @@ WrStat wr_stat_of(const WrCol& c, const IxRec& r, const uint8_t* side) {
       s.imax = r.imax;
       s.isum = (__int128)(((unsigned __int128)(uint64_t)r.sum_hi << 64) | r.sum_lo);
       break;
-    case 2: s.dmin = r.dmin; s.dmax = r.dmax; s.dsum = r.dsum; s.dsum_lo = r.dsum_lo; s.has_nan = r.has_nan != 0; break;
+    case 2: s.dmin = r.dmin; s.dmax = r.dmax; s.dsum = r.dsum; s.dsum_lo = r.dsum_lo; s.dbig = r.dbig; s.dbig_lo = r.dbig_lo; s.has_nan = r.has_nan != 0; break;
     case 3: s.trues = r.trues; break;
     default:
       s.bytes = r.bytes;
@@ -426,8 +427,8 @@ void wr_stat_merge(WrStat& a, const WrStat& b) {
     if (first || wr_str_cmp(b.smin, b.smin_len, a.smin, a.smin_len) < 0) a.smin = b.smin, a.smin_len = b.smin_len;
     if (first || wr_str_cmp(b.smax, b.smax_len, a.smax, a.smax_len) > 0) a.smax = b.smax, a.smax_len = b.smax_len;
     a.isum += b.isum;
-    if (first) a.dsum = b.dsum, a.dsum_lo = b.dsum_lo;
-    else wr_dd_merge(a.dsum, a.dsum_lo, b.dsum, b.dsum_lo);
+    if (first) a.dsum = b.dsum, a.dsum_lo = b.dsum_lo, a.dbig = b.dbig, a.dbig_lo = b.dbig_lo;
+    else wr_dd_merge(a.dsum, a.dsum_lo, b.dsum, b.dsum_lo), wr_dd_merge(a.dbig, a.dbig_lo, b.dbig, b.dbig_lo);
     a.bytes += b.bytes;
     a.trues += b.trues;
   }
@@ -469,6 +470,17 @@ bool wr_upper_bound(const std::string& s, std::string& out) {
   return true;
 }
 
+// a float range's sum: the two double-doubles added, with the big one's scale; infinite when the exact sum is beyond f64 (an
+// infinite input: the big one is infinite or NaN, and that is the sum)
+double wr_float_sum(const WrStat& s) {
+#pragma clang fp contract(off)
+  if (!std::isfinite(s.dbig)) return s.dbig;
+  if (s.dbig == 0 && s.dbig_lo == 0) return s.dsum + s.dsum_lo;
+  double hi = s.dbig, lo = s.dbig_lo;
+  wr_dd_merge(hi, lo, std::ldexp(s.dsum, -64), std::ldexp(s.dsum_lo, -64));
+  return std::ldexp(hi + lo, 64);
+}
+
 // ColumnStatistics (c: nullptr for the root struct, whose values are its rows)
 PbOut wr_stat_msg(const WrCol* c, const WrStat& s) {
   PbOut m;
@@ -486,7 +498,7 @@ PbOut wr_stat_msg(const WrCol* c, const WrStat& s) {
         if (s.has_nan) break;  // (no DoubleStatistics: a reader would take an absent bound for 0)
         t.f64(1, s.dmin);
         t.f64(2, s.dmax);
-        t.f64(3, std::isfinite(s.dsum) ? s.dsum + s.dsum_lo : s.dsum);
+        t.f64(3, wr_float_sum(s));
         m.msg(3, t);
         break;
       case 3:

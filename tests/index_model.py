@@ -9,6 +9,7 @@ with only the typed key of the column present, and none when n is 0 (or for floa
 import bisect
 import math
 import struct
+from fractions import Fraction
 
 import numpy as np
 import pyarrow as pa
@@ -17,6 +18,55 @@ import writer_model as WM
 from orcfile import ROW_INDEX, _packed, pb_fields
 
 I64 = (-(1 << 63), (1 << 63) - 1)
+U = Fraction(1, 1 << 53)  # the unit roundoff of f64
+ULP0 = 1 << 1074  # every finite f64 is an integer multiple of 2^-1074
+
+
+def fixed(x):
+    """a finite double as an exact integer count of 2^-1074"""
+    n, d = x.as_integer_ratio()
+    return n << (1074 - (d.bit_length() - 1))
+
+
+def sum_tol(S, A, n):
+    """the bound a float sum is held to (Fractions): 2 (u |S| + gamma_n^2 sum |x|), gamma_n = n u / (1 - n u) -- twice the error
+    bound of compensated double-double summation (Ogita, Rump and Oishi, "Accurate sum and dot product", SIAM J. Sci. Comput. 26(6),
+    2005, Prop. 4.5); the factor 2 leaves room for the tree and host merges, which Sum2 does not have"""
+    g = n * U / (1 - n * U)
+    return 2 * (U * abs(S) + g * g * A)
+
+
+class FloatSum(float):
+    """a range's expected double sum R, a float: the exact sum S rounded to nearest (+-inf beyond f64).  For ranges without an
+    infinite value it also holds S and sum |x| (`exact`, `abs_sum`: integers in units of 2^-1074) and the number of values n."""
+
+    def __new__(cls, vals):
+        pos, neg = any(x == math.inf for x in vals), any(x == -math.inf for x in vals)
+        if pos or neg:  # (one sign of infinity: that infinity; both: NaN)
+            r = float("nan") if pos and neg else (math.inf if pos else -math.inf)
+            self = float.__new__(cls, r)
+            self.exact = None
+            return self
+        S = sum(fixed(x) for x in vals)
+        try:
+            r = S / ULP0  # (int / int: correctly rounded)
+        except OverflowError:
+            r = math.inf if S > 0 else -math.inf
+        self = float.__new__(cls, r)
+        self.exact, self.abs_sum, self.n = S, sum(abs(fixed(x)) for x in vals), len(vals)
+        return self
+
+    def S(self):
+        return Fraction(self.exact, ULP0)
+
+    def tol(self):
+        return sum_tol(self.S(), Fraction(self.abs_sum, ULP0), self.n)
+
+    def admits(self, got):
+        """got meets the contract: the same infinity (sign included) for an infinite R; within tol of S for a finite one"""
+        if self.exact is None or math.isinf(self):
+            return got == self or (math.isnan(got) and math.isnan(self))
+        return math.isfinite(got) and abs(Fraction(got) - self.S()) <= self.tol()
 
 
 def _zz(v):
@@ -56,11 +106,7 @@ def column_stats(arr):
     elif pa.types.is_floating(t):
         v = [float(x) for x in valid.to_numpy(zero_copy_only=False).astype(np.float64)]
         if not any(math.isnan(x) for x in v):
-            if any(math.isinf(x) for x in v):
-                s = sum(v)  # (inf, -inf or nan: what any order gives)
-            else:
-                s = math.fsum(v)
-            d["double"] = (min(v), max(v), s)  # (min / max: the first of equal values, -0.0 against 0.0)
+            d["double"] = (min(v), max(v), FloatSum(v))  # (min / max: the first of equal values, -0.0 against 0.0)
     elif t in (pa.string(), pa.large_string()):
         v = [x.encode() if isinstance(x, str) else x for x in valid.to_pylist()]
         mn, mx = min(v), max(v)
@@ -106,7 +152,7 @@ def parse_stats(b):
 
 
 def same_stats(got, want, rel=1e-9):
-    """equal, but for double sums: within rel of the model's"""
+    """equal, but for double sums: within rel of the model's, and within FloatSum.tol of the exact sum (an infinite one: equal)"""
     if set(got) != set(want):
         return False
     for k in want:
@@ -117,10 +163,15 @@ def same_stats(got, want, rel=1e-9):
             if math.isnan(b2):
                 if not math.isnan(a2):
                     return False
-            elif math.isinf(b2) or b2 == 0:
+            elif math.isinf(b2):
+                if a2 != b2:
+                    return False
+            elif b2 == 0:
                 if a2 != b2 and abs(a2 - b2) > 1e-300:
                     return False
-            elif abs(a2 - b2) > rel * abs(b2):
+            elif not abs(a2 - b2) <= rel * abs(b2):
+                return False
+            if isinstance(b2, FloatSum) and not b2.admits(a2):
                 return False
         elif got[k] != want[k]:
             return False
