@@ -257,6 +257,7 @@ struct orcgpu_ctx {
   size_t fin_pinned_cap = 0;
   hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start, before / after expansion, end, after decompression, after the walk, after the decompressors' first stage, behind the Zstandard table kernel, behind the sequences kernel (one lane per block), [9] in front of it (behind the wait for the other lanes' table kernels)
   uint32_t n_cus = 0;
+  uint32_t dbg_inflate_threads = 0, dbg_exec_threads = 0;  // what the last launch_chunk_decoders gave DEFLATE chunks: threads per chunk of the token and the execution kernel (ORCGPU_DEBUG reports them)
   hipEvent_t kev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // around rle_walk_short_kernel [0] and dict_emit_kernel [1] (orcgpu_last_lane_stats)
   bool kev_used[2] = {false, false};
   hipStream_t aux_stream = nullptr;   // the Zstandard execution kernel runs here, beside the entropy kernel on `stream`

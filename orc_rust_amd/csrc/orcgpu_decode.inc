@@ -950,6 +950,16 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       for (uint32_t k = 0; k < 2 * DP.n_zblocks; k++) pend += zs[k] == 0xffffffffu, wd += zs[k] == 0x57a7u;
       if (pend || wd) fprintf(stderr, "[orcgpu] entropy jobs: %u of %u still pending, %u watchdog\n", pend, 2 * DP.n_zblocks, wd);
     }
+    {
+      // DEFLATE: which kernels the call's chunks got (recorded where they were launched), and how many of them the token stage left to the one-wavefront decoder (that
+      // decoder does not touch `diag`: the mark is still there) or the execution kernel rejected (its own code in `diag`)
+      uint32_t n_deflate = 0, n_deferred = 0, n_exec_bad = 0;
+      for (uint32_t k = 0; k < DP.n_chunks; k++)
+        if (cc[k].kind == 1) n_deflate++, n_deferred += cc[k].diag == LZX_DEFERRED, n_exec_bad += cc[k].diag != LZX_DEFERRED && cc[k].diag != 0;
+      if (n_deflate)
+        fprintf(stderr, "[orcgpu] deflate: %u chunks of %u in the call, token stage %u threads per chunk, execution %u threads per chunk, %u deferred to the serial decoder, %u rejected by the execution kernel\n",
+                n_deflate, DP.n_chunks, ctx->dbg_inflate_threads, ctx->dbg_exec_threads, n_deferred, n_exec_bad);
+    }
     for (uint32_t k = 0; k < DP.n_chunks && shown < 16; k++)
       if (cc[k].status) fprintf(stderr, "[orcgpu] chunk %u (stream %u, kind %u, %u bytes, cap %u): rejected, diag %u\n", k, cc[k].stream, cc[k].kind, cc[k].src_len, cc[k].dst_cap, cc[k].diag), shown++;
     for (uint32_t k = 0; k < DP.n_zblocks && shown < 32; k++)

@@ -228,6 +228,7 @@ static int launch_chunk_decoders(orcgpu_ctx* ctx, hipStream_t st, ChunkDesc* d_c
       // few chunks: four wavefronts per chunk (the call lasts as long as its longest chunk's chain of windows: C3 / zlib 11.6 -> 5.3 ms);
       // chunks enough to fill the device several times over: one (lineitem SF 4, 4.7 k chunks: four were 20 % slower)
       const bool four = n_chunks <= 6u * (ctx->n_cus ? ctx->n_cus : 256u);
+      ctx->dbg_inflate_threads = four ? 256u : 64u;
       if (four) {
         HIP_TRY(ctx, launch(inflate_parse4_kernel, (uint64_t)n_chunks, true, 256, st, d_chunks, n_chunks, 0u, 0xffffffffu));
       } else {
@@ -253,6 +254,7 @@ static int launch_chunk_decoders(orcgpu_ctx* ctx, hipStream_t st, ChunkDesc* d_c
     // (... and whenever the execution kernel has nothing to wait for and thousands of chunks to go through: a DEFLATE table)
     const bool single_shot = d_ztab != nullptr || (!side && n_chunks >= 2048);
     const bool wave_groups = single_shot;
+    if (deflate) ctx->dbg_exec_threads = wave_groups ? 64u : (uint32_t)LZX_THREADS;
     if (wave_groups)
       HIP_TRY(ctx, launch(lz_exec_wave_kernel, (uint64_t)n_chunks, true, 64, xs, d_chunks, n_chunks, d_zitems, (const ZBlock*)d_zblocks, (const uint32_t*)d_zstatus,
                           (const uint32_t*)d_zprogress, n_zblocks, copy_too, d_order));

@@ -1,9 +1,12 @@
 """GPU parity, block decompressors on their own: DOUBLE columns carry arbitrary bytes (the DATA
 stream is raw IEEE-754, float.rs:53-75), so every shape of compressed block can be pushed through
 the chunk decoders and compared with the oracle byte for byte.  The blocks come from REAL encoders
-(pyarrow's Snappy / LZ4-raw / Zstandard, Python's zlib) and from a hand-rolled Snappy writer that
-forces the element forms real encoders rarely emit (4-byte offsets, 1..4 extra length bytes,
-overlapping copies of every small distance)."""
+(pyarrow's Snappy / LZ4-raw / Zstandard, Python's zlib) and from hand-rolled writers that force the
+forms real encoders rarely emit: Snappy elements (4-byte offsets, 1..4 extra length bytes,
+overlapping copies of every small distance), LZ4 sequences (long length extensions, tiny offsets,
+the forms of a block's end) and LZO1X instructions (tests/lzo_enc.py), each with a table of
+malformed blocks that must be rejected like the oracle rejects them.  DEFLATE has a file of its own:
+tests/test_gpu_deflate.py over the streams of tests/deflate_enc.py."""
 import zlib
 
 import numpy as np
