@@ -437,7 +437,11 @@ int orcgpu_encode_fetch(orcgpu_ctx* ctx, const orcgpu_enc_stream* stream, uint8_
 
 /* ---- ArrowWriterBuilder / ArrowWriter (src/arrow_writer.rs:34-156) ----------------------------------------------------------
  * Arrow record batches -> an ORC file, byte for byte the reference writer's: a flat schema of Boolean, Int8..Int64, Float32/64,
- * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0); no index or statistics unless
+ * Utf8, LargeUtf8, Binary, LargeBinary fields (a root Struct, column 0), and beyond the reference Timestamp(s/ms/us/ns, with a zone:
+ * TIMESTAMP_INSTANT) and Decimal128(p, s) with 1 <= p <= 38, 0 <= s <= p (DATA, SECONDARY, [PRESENT]; every stripe footer of a file
+ * with a Timestamp column carries writer_timezone "UTC").  A timestamp within the second before 1970-01-01 00:00:00 (but not on
+ * it), or whose second is further from 2015 than i64 holds, has no ORC encoding: write returns ORCGPU_INVALID_ARGUMENT, nothing of
+ * the batch is taken and the writer stays usable.  No index or statistics unless
  * orcgpu_writer_set_row_index asks for them (below).  Every stream is encoded on the
  * device (the encoders above); a stripe is cut where the reference's would be (after a slice of batch_size rows whose summed
  * encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.  Uncompressed by default (the reference writes

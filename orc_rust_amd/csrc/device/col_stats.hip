@@ -18,7 +18,7 @@
 struct IxCol {
   const uint8_t* pres;  // a byte per row of the stripe
   const void* vals;     // the valid values in `elem` bytes each
-  const uint8_t* data;  // strings' bytes
+  const uint8_t* data;  // strings' bytes (Timestamp: the nanosecond codes, vals the stored seconds)
   int32_t kind;         // WrCol::stream_kind
   int32_t elem;
   int32_t minmax;       // strings: 1 with a minimum / maximum (Utf8), 0 without (Binary)
@@ -46,6 +46,8 @@ struct IxRec {  // one job's statistics, 128 bytes (the host reads them as they 
   uint64_t side;              // ... and of their copies in the side buffer (minimum, then maximum)
   uint32_t smin_len, smax_len;
   uint32_t has_null, has_nan;
+  // Timestamp: imin / imax the minimum's / maximum's second, sum_lo / sum_hi their nanoseconds.
+  // Decimal128: imin:imax the minimum (low, high word), smin_at:smax_at the maximum, sum_lo:sum_hi:trues the sum in 192 bits.
 };
 static_assert(sizeof(IxRec) == 128, "IxRec is read by the host as 128 bytes");
 
@@ -111,13 +113,18 @@ extern "C" __global__ void __launch_bounds__(256) ix_bytes_kernel(const IxCol* c
   __shared__ uint64_t lds[256];
   const uint64_t j = blockIdx.x, c = j / G;
   const IxCol col = cols[c];
-  if (col.kind != 4) {
+  if (col.kind != 4 && col.kind != 6) {
     if (threadIdx.x == 0) blen[j] = 0;
     return;
   }
   const uint64_t v0 = vscan[j] - vscan[c * G], n = cnt[j];
   uint64_t b = 0;
-  for (uint64_t i = threadIdx.x; i < n; i += 256) b += ix_len(col.vals, col.elem, v0 + i);
+  if (col.kind == 6) {  // Decimal128: the varints' bytes
+    const uint64_t* q = (const uint64_t*)col.vals;
+    for (uint64_t i = threadIdx.x; i < n; i += 256) b += wr_dec_varint_len(wr_dec_zigzag(q[2 * (v0 + i)], q[2 * (v0 + i) + 1]));
+  } else {
+    for (uint64_t i = threadIdx.x; i < n; i += 256) b += ix_len(col.vals, col.elem, v0 + i);
+  }
   b = ix_block_sum(b, lds);
   if (threadIdx.x == 0) blen[j] = b;
 }
@@ -282,6 +289,77 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     uint64_t tr = 0;
     for (uint64_t i = t; i < n; i += 256) tr += ((const uint8_t*)col.vals)[v0 + i];
     R.trues = ix_block_sum(tr, l0);
+  } else if (col.kind == 5) {  // Timestamp: minimum and maximum by (second, nanosecond)
+    int64_t s0 = INT64_MAX, s1 = INT64_MIN;
+    uint32_t q0 = 0xffffffffu, q1 = 0;
+    for (uint64_t i = t; i < n; i += 256) {
+      int64_t S;
+      uint32_t N;
+      wr_timestamp_of(((const int64_t*)col.vals)[v0 + i], ((const uint64_t*)col.data)[v0 + i], S, N);
+      if (S < s0 || (S == s0 && N < q0)) s0 = S, q0 = N;
+      if (S > s1 || (S == s1 && N > q1)) s1 = S, q1 = N;
+    }
+    l0[t] = (uint64_t)s0, l1[t] = (uint64_t)s1, n0[t] = q0, n1[t] = q1;
+    __syncthreads();
+    for (uint32_t d = 128; d > 0; d >>= 1) {
+      if (t < d) {
+        const int64_t a0 = (int64_t)l0[t + d], a1 = (int64_t)l1[t + d];
+        if (a0 < (int64_t)l0[t] || (a0 == (int64_t)l0[t] && n0[t + d] < n0[t])) l0[t] = l0[t + d], n0[t] = n0[t + d];
+        if (a1 > (int64_t)l1[t] || (a1 == (int64_t)l1[t] && n1[t + d] > n1[t])) l1[t] = l1[t + d], n1[t] = n1[t + d];
+      }
+      __syncthreads();
+    }
+    R.imin = (int64_t)l0[0];
+    R.imax = (int64_t)l1[0];
+    R.sum_lo = n0[0];
+    R.sum_hi = n1[0];
+  } else if (col.kind == 6) {  // Decimal128: minimum, maximum, and the exact sum in 192 bits (fewer than 2^32 values below 2^127)
+    const uint64_t* q = (const uint64_t*)col.vals;
+    __int128 mn = 0, mx = 0;
+    uint64_t s0 = 0, s1 = 0, s2 = 0;
+    bool any = false;
+    for (uint64_t i = t; i < n; i += 256) {
+      const uint64_t lo = q[2 * (v0 + i)], hi = q[2 * (v0 + i) + 1];
+      const __int128 x = (__int128)(((unsigned __int128)hi << 64) | lo);
+      if (!any || x < mn) mn = x;
+      if (!any || x > mx) mx = x;
+      any = true;
+      const unsigned __int128 lo2 = (unsigned __int128)s0 + lo;
+      const unsigned __int128 mid = (unsigned __int128)s1 + hi + (uint64_t)(lo2 >> 64);
+      s0 = (uint64_t)lo2;
+      s1 = (uint64_t)mid;
+      s2 += (uint64_t)((int64_t)hi >> 63) + (uint64_t)(mid >> 64);
+    }
+    uint64_t* sx = (uint64_t*)b0;
+    uint64_t* ok = (uint64_t*)b1;
+    l0[t] = (uint64_t)mn, l1[t] = (uint64_t)((unsigned __int128)mn >> 64);
+    l2[t] = (uint64_t)mx, m0[t] = (uint64_t)((unsigned __int128)mx >> 64);
+    m1[t] = s0, m2[t] = s1, sx[t] = s2, ok[t] = any;
+    __syncthreads();
+    for (uint32_t d = 128; d > 0; d >>= 1) {
+      if (t < d) {
+        if (ok[t + d]) {
+          const __int128 a = (__int128)(((unsigned __int128)l1[t] << 64) | l0[t]), b = (__int128)(((unsigned __int128)l1[t + d] << 64) | l0[t + d]);
+          const __int128 e = (__int128)(((unsigned __int128)m0[t] << 64) | l2[t]), f = (__int128)(((unsigned __int128)m0[t + d] << 64) | l2[t + d]);
+          if (!ok[t] || b < a) l0[t] = l0[t + d], l1[t] = l1[t + d];
+          if (!ok[t] || f > e) l2[t] = l2[t + d], m0[t] = m0[t + d];
+          ok[t] = 1;
+        }
+        const unsigned __int128 lo2 = (unsigned __int128)m1[t] + m1[t + d];
+        const unsigned __int128 mid = (unsigned __int128)m2[t] + m2[t + d] + (uint64_t)(lo2 >> 64);
+        m1[t] = (uint64_t)lo2;
+        m2[t] = (uint64_t)mid;
+        sx[t] += sx[t + d] + (uint64_t)(mid >> 64);
+      }
+      __syncthreads();
+    }
+    R.imin = (int64_t)l0[0];
+    R.imax = (int64_t)l1[0];
+    R.smin_at = l2[0];
+    R.smax_at = m0[0];
+    R.sum_lo = m1[0];
+    R.sum_hi = (int64_t)m2[0];
+    R.trues = sx[0];
   } else {  // strings / binaries: bytes; Utf8: min and max by bytes
     const uint64_t b0 = bscan[j] - bscan[c * G];
     R.bytes = bscan[j + 1] - bscan[j];

@@ -793,22 +793,29 @@ extern "C" __global__ void __launch_bounds__(256) enc_valid_counts_kernel(const 
   if (wi == n_words - 1 && (n_rows & 63)) word &= (1ull << (n_rows & 63)) - 1;
   counts[wi] = (uint32_t)__builtin_popcountll(word);
 }
-// elem_bytes 1 / 2 / 4 / 8: fixed-width values;  0: a bitmap's bits (Boolean values) gathered into bytes_out as 0 / 1 bytes
+// the valid rows before `row` (word_off: exclusive scan of the bitmap's 64-row popcounts)
+__device__ __forceinline__ uint64_t enc_valid_before(const uint8_t* validity, uint64_t n_rows, const uint64_t* word_off, uint64_t row) {
+  const uint64_t wi = row >> 6, nb = (n_rows + 7) / 8;
+  uint64_t word = 0;
+  for (uint32_t k = 0; k < 8; k++) word |= wi * 8 + k < nb ? (uint64_t)validity[wi * 8 + k] << (8 * k) : 0;
+  return word_off[wi] + (uint64_t)__builtin_popcountll(word & ((1ull << (row & 63)) - 1));
+}
+// elem_bytes 1 / 2 / 4 / 8 / 16: fixed-width values;  0: a bitmap's bits (Boolean values) gathered into bytes_out as 0 / 1 bytes
 extern "C" __global__ void __launch_bounds__(256) enc_gather_valid_kernel(const uint8_t* validity, uint64_t n_rows, const uint64_t* word_off, const void* values,
                                                                           int elem_bytes, void* out) {
   const uint64_t row = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n_rows) return;
   if (!((validity[row >> 3] >> (row & 7)) & 1)) return;
-  const uint64_t wi = row >> 6;
-  uint64_t word = 0;
-  const uint64_t nb = (n_rows + 7) / 8;
-  for (uint32_t k = 0; k < 8; k++) word |= wi * 8 + k < nb ? (uint64_t)validity[wi * 8 + k] << (8 * k) : 0;
-  const uint64_t at = word_off[wi] + (uint64_t)__builtin_popcountll(word & ((1ull << (row & 63)) - 1));
+  const uint64_t at = enc_valid_before(validity, n_rows, word_off, row);
   switch (elem_bytes) {
     case 0: ((uint8_t*)out)[at] = (((const uint8_t*)values)[row >> 3] >> (row & 7)) & 1; break;
     case 1: ((uint8_t*)out)[at] = ((const uint8_t*)values)[row]; break;
     case 2: ((uint16_t*)out)[at] = ((const uint16_t*)values)[row]; break;
     case 4: ((uint32_t*)out)[at] = ((const uint32_t*)values)[row]; break;
+    case 16:
+      ((uint64_t*)out)[2 * at] = ((const uint64_t*)values)[2 * row];
+      ((uint64_t*)out)[2 * at + 1] = ((const uint64_t*)values)[2 * row + 1];
+      break;
     default: ((uint64_t*)out)[at] = ((const uint64_t*)values)[row]; break;
   }
 }

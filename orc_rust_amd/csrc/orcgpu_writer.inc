@@ -102,21 +102,31 @@ struct WrStat {
   double dbig = 0, dbig_lo = 0;  // the sum of the values of magnitude >= 2^960, scaled by 2^-64 (col_stats.hip: IX_BIG)
   std::string smin, smax;          // their first IX_STR_KEEP bytes at most
   uint64_t smin_len = 0, smax_len = 0;  // and their whole lengths
+  uint32_t nmin = 0, nmax = 0;     // Timestamp: the nanoseconds of the minimum / maximum (imin / imax: their seconds)
+  __int128 qmin = 0, qmax = 0;     // Decimal128
+  uint64_t qsum[4] = {0, 0, 0, 0};  // ... the exact sum, 256 bits, two's complement
 };
 
 struct WrCol {
   int elem = 0;        // bytes of a value as the column's value encoder takes it (Boolean: a byte; strings: the offset width)
   bool is_string = false;
-  int stream_kind = 0; // 0 Integer RLE v2 (signed), 1 byte RLE, 2 raw floats, 3 Boolean, 4 strings (bytes + unsigned RLE v2 lengths)
+  int stream_kind = 0; // 0 Integer RLE v2 (signed), 1 byte RLE, 2 raw floats, 3 Boolean, 4 strings (bytes + unsigned RLE v2 lengths),
+                       // 5 Timestamp (seconds + nanosecond codes, RLE v2), 6 Decimal128 (varint bytes + the scale, signed RLE v2)
   int orc_kind = 0;    // Type.Kind
   int encoding = 0;    // ColumnEncoding.Kind
   std::string name;
   bool present = false;  // sticky once an array with a validity bitmap arrived (writer/column.rs:103-139)
   uint64_t rows = 0, n_valid = 0, n_bytes = 0;  // of the open stripe
   uint64_t base_valid = 0;                       // values of the stripe when orcgpu_writer::base_rle was found
-  DevVec pres, vals, data;
+  int64_t ups = 1, npu = 1;         // Timestamp: units per second, nanoseconds per unit
+  uint32_t precision = 0, scale = 0;  // Decimal128
+  // vals2: the second value stream's values -- Timestamp: the nanosecond codes (u64; vals: the stored seconds); Decimal128: the
+  // scale once per valid value (i16; vals: the values themselves, kept only with a row index, for its statistics; data: their varints)
+  DevVec pres, vals, vals2, data;
   // this write call's batch, in the same form
-  DevBuf b_bits, b_pres, b_vals, b_data, b_tmp;
+  DevBuf b_bits, b_pres, b_vals, b_vals2, b_data, b_tmp;
+  bool has_bytes() const { return stream_kind == 4 || stream_kind == 6; }  // n_bytes / data count toward the estimate
+  int elem2() const { return stream_kind == 5 ? 8 : 2; }
 };
 
 struct WrField {  // what ArrowWriter::write compares (batch.schema() == self.schema)
@@ -207,7 +217,32 @@ std::string wr_metadata(const char* m) {
 
 // the column writer of an Arrow type (writer/stripe.rs:173-187, arrow_writer.rs:158-222); false: the reference's unimplemented!()
 bool wr_column_of(const char* fmt, WrCol& c) {
-  if (!fmt || !fmt[0] || fmt[1]) return false;
+  if (!fmt || !fmt[0] || strstr(fmt, "#nested")) return false;
+  if (fmt[0] == 't' && fmt[1] == 's' && fmt[2] && fmt[3] == ':') {  // Timestamp(unit, tz): with a zone an instant
+    switch (fmt[2]) {
+      case 's': c.ups = 1; c.npu = 1000000000; break;
+      case 'm': c.ups = 1000; c.npu = 1000000; break;
+      case 'u': c.ups = 1000000; c.npu = 1000; break;
+      case 'n': c.ups = 1000000000; c.npu = 1; break;
+      default: return false;
+    }
+    c.elem = 8; c.stream_kind = 5; c.orc_kind = fmt[4] ? 18 : 9; c.encoding = 2;
+    return true;
+  }
+  if (fmt[0] == 'd' && fmt[1] == ':') {  // Decimal128(p, s): "d:p,s" or "d:p,s,128"
+    int p = 0, sc = 0, bits = 128, used = 0;
+    const int got = sscanf(fmt + 2, "%d,%d%n", &p, &sc, &used);
+    if (got != 2) return false;
+    const char* rest = fmt + 2 + used;
+    if (*rest) {
+      int used2 = 0;
+      if (sscanf(rest, ",%d%n", &bits, &used2) != 1 || rest[used2]) return false;
+    }
+    if (bits != 128 || p < 1 || p > 38 || sc < 0 || sc > p) return false;
+    c.elem = 16; c.stream_kind = 6; c.orc_kind = 14; c.encoding = 2; c.precision = (uint32_t)p; c.scale = (uint32_t)sc;
+    return true;
+  }
+  if (fmt[1]) return false;
   switch (fmt[0]) {
     case 'b': c.elem = 1; c.stream_kind = 3; c.orc_kind = 0; c.encoding = 0; return true;
     case 'c': c.elem = 1; c.stream_kind = 1; c.orc_kind = 1; c.encoding = 0; return true;
@@ -249,7 +284,7 @@ int wr_prepare(orcgpu_ctx* ctx, const ArrowSchema* schema, const orcgpu_writer_o
   for (auto& fd : w->fields) {
     WrCol c;
     if (!wr_column_of(fd.format.c_str(), c)) {
-      set_err(ctx, "writer: unsupported Arrow type '%s' of field '%s' (the reference: unimplemented!(\"unsupported datatype\"), writer/stripe.rs:186)",
+      set_err(ctx, "writer: unsupported Arrow type '%s' of field '%s' (the reference: unimplemented!(\"unsupported datatype\"), writer/stripe.rs:186; beyond it: Timestamp, Decimal128)",
               fd.format.c_str(), fd.name.c_str());
       return ORCGPU_UNSUPPORTED;
     }
@@ -378,6 +413,12 @@ WrStat wr_stat_of(const WrCol& c, const IxRec& r, const uint8_t* side) {
       break;
     case 2: s.dmin = r.dmin; s.dmax = r.dmax; s.dsum = r.dsum; s.dsum_lo = r.dsum_lo; s.dbig = r.dbig; s.dbig_lo = r.dbig_lo; s.has_nan = r.has_nan != 0; break;
     case 3: s.trues = r.trues; break;
+    case 5: s.imin = r.imin; s.imax = r.imax; s.nmin = (uint32_t)r.sum_lo; s.nmax = (uint32_t)r.sum_hi; break;
+    case 6:
+      s.qmin = (__int128)(((unsigned __int128)(uint64_t)r.imax << 64) | (uint64_t)r.imin);
+      s.qmax = (__int128)(((unsigned __int128)r.smax_at << 64) | r.smin_at);
+      s.qsum[0] = r.sum_lo, s.qsum[1] = (uint64_t)r.sum_hi, s.qsum[2] = r.trues, s.qsum[3] = (uint64_t)((int64_t)r.trues >> 63);
+      break;
     default:
       s.bytes = r.bytes;
       if (c.orc_kind == 7) {
@@ -420,8 +461,17 @@ void wr_stat_merge(WrStat& a, const WrStat& b) {
   a.has_nan |= b.has_nan;
   if (b.count) {
     const bool first = a.count == 0;
-    if (first || b.imin < a.imin) a.imin = b.imin;
-    if (first || b.imax > a.imax) a.imax = b.imax;
+    // (Timestamp: the nanoseconds go with their seconds; every other column leaves them 0)
+    if (first || b.imin < a.imin || (b.imin == a.imin && b.nmin < a.nmin)) a.imin = b.imin, a.nmin = b.nmin;
+    if (first || b.imax > a.imax || (b.imax == a.imax && b.nmax > a.nmax)) a.imax = b.imax, a.nmax = b.nmax;
+    if (first || b.qmin < a.qmin) a.qmin = b.qmin;
+    if (first || b.qmax > a.qmax) a.qmax = b.qmax;
+    unsigned carry = 0;
+    for (int i = 0; i < 4; i++) {
+      const unsigned __int128 t = (unsigned __int128)a.qsum[i] + b.qsum[i] + carry;
+      a.qsum[i] = (uint64_t)t;
+      carry = (unsigned)(t >> 64);
+    }
     if (first || b.dmin < a.dmin) a.dmin = b.dmin;
     if (first || b.dmax > a.dmax) a.dmax = b.dmax;
     if (first || wr_str_cmp(b.smin, b.smin_len, a.smin, a.smin_len) < 0) a.smin = b.smin, a.smin_len = b.smin_len;
@@ -481,6 +531,22 @@ double wr_float_sum(const WrStat& s) {
   return std::ldexp(hi + lo, 64);
 }
 
+// a decimal at `scale` in minimal form: no exponent, trailing fractional zeros and a bare point removed, "0" for zero
+std::string wr_decimal_string(__int128 v, uint32_t scale) {
+  const bool neg = v < 0;
+  unsigned __int128 m = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+  std::string d;
+  while (m) d.insert(d.begin(), (char)('0' + (int)(m % 10))), m /= 10;
+  if (d.size() <= scale) d.insert(0, scale + 1 - d.size(), '0');
+  if (scale) {
+    d.insert(d.size() - scale, ".");
+    while (d.back() == '0') d.pop_back();
+    if (d.back() == '.') d.pop_back();
+  }
+  if (d.empty()) d = "0";
+  return neg ? "-" + d : d;
+}
+
 // ColumnStatistics (c: nullptr for the root struct, whose values are its rows)
 PbOut wr_stat_msg(const WrCol* c, const WrStat& s) {
   PbOut m;
@@ -505,6 +571,36 @@ PbOut wr_stat_msg(const WrCol* c, const WrStat& s) {
         t.packed(1, {s.trues});
         m.msg(5, t);
         break;
+      case 5: {  // TimestampStatistics: floor milliseconds (the writer's zone is UTC: the legacy fields hold the same), and the
+                 // nanoseconds within the millisecond plus one; none when a bound's milliseconds leave i64
+        const __int128 lo = (__int128)s.imin * 1000 + s.nmin / 1000000, hi = (__int128)s.imax * 1000 + s.nmax / 1000000;
+        if (lo < (__int128)INT64_MIN || hi > (__int128)INT64_MAX) break;
+        t.sint(1, (int64_t)lo);
+        t.sint(2, (int64_t)hi);
+        t.sint(3, (int64_t)lo);
+        t.sint(4, (int64_t)hi);
+        t.u64(5, s.nmin % 1000000 + 1);
+        t.u64(6, s.nmax % 1000000 + 1);
+        m.msg(9, t);
+        break;
+      }
+      case 6: {  // DecimalStatistics: the sum when |sum| < 10^38
+        const std::string a = wr_decimal_string(s.qmin, c->scale), b = wr_decimal_string(s.qmax, c->scale);
+        t.bytes(1, a.data(), a.size());
+        t.bytes(2, b.data(), b.size());
+        const uint64_t ext = (uint64_t)((int64_t)s.qsum[1] >> 63);
+        if (s.qsum[2] == ext && s.qsum[3] == ext) {
+          const __int128 sum = (__int128)(((unsigned __int128)s.qsum[1] << 64) | s.qsum[0]);
+          __int128 lim = 1;
+          for (int i = 0; i < 38; i++) lim *= 10;
+          if (sum < lim && sum > -lim) {
+            const std::string z = wr_decimal_string(sum, c->scale);
+            t.bytes(3, z.data(), z.size());
+          }
+        }
+        m.msg(6, t);
+        break;
+      }
       default:
         if (c->orc_kind == 8) {
           t.sint(1, (int64_t)s.bytes);
@@ -555,7 +651,7 @@ int wr_flush(orcgpu_writer* w) {
   // room: the lengths, the bitmaps of the Boolean / PRESENT streams
   uint64_t n_streams = 0, bits_room = 0;
   for (auto& c : w->cols) {
-    n_streams += 1 + (c.stream_kind == 4) + c.present;
+    n_streams += 1 + (c.stream_kind >= 4) + c.present;
     if (c.stream_kind == 3) bits_room += align_up(2 * ((c.n_valid + 7) / 8) + 16);
     if (c.present) bits_room += align_up(2 * ((c.rows + 7) / 8) + 16);
   }
@@ -612,7 +708,7 @@ int wr_flush(orcgpu_writer* w) {
       a.n = std::min<uint32_t>(IX_COLS_PER_ARG, (uint32_t)nc - i0);
       for (uint32_t i = 0; i < a.n; i++) {
         const WrCol& c = w->cols[i0 + i];
-        a.c[i] = IxCol{c.pres.p, c.vals.p, c.data.p, c.stream_kind, c.elem, c.orc_kind == 7, 0};
+        a.c[i] = IxCol{c.pres.p, c.vals.p, c.stream_kind == 5 ? c.vals2.p : c.data.p, c.stream_kind, c.elem, c.orc_kind == 7, 0};
       }
       WR_TRY(launch(ix_put_cols_kernel, (uint64_t)1, true, 64, ctx->stream, a, d_cols));
     }
@@ -641,7 +737,7 @@ int wr_flush(orcgpu_writer* w) {
     WrCol& c = w->cols[ci];
     const uint32_t column = (uint32_t)ci + 1;
     // (the positions list PRESENT first: its stream index is known before it is written)
-    const uint64_t li_present = streams.size() + 1 + (c.stream_kind == 4);
+    const uint64_t li_present = streams.size() + 1 + (c.stream_kind >= 4);
     if (c.present) ixp(0, ci, c.rows, li_present, 3);
     uint64_t li = streams.size();
     streams.push_back(St{1, column, at});
@@ -655,7 +751,8 @@ int wr_flush(orcgpu_writer* w) {
         if (!rc && wr_ix_pos(ctx, &ip, nullptr) != hipSuccess) rc = ORCGPU_HIP_ERROR;
         break;
       case 3: ip = ixp(3, ci, c.n_valid, li, 3); rc = wr_bool_stream(w, c.vals.p, c.n_valid, &at, li, &ip); break;
-      default:
+      case 5: ip = ixp(1, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, 8, 1, &at, li, &ip); break;
+      default:  // strings' bytes, decimals' varints
         ip = ixp(5, ci, c.n_valid, li, 1);
         rc = wr_copy_stream(w, c.data.p, c.n_bytes, &at, li, known);
         if (!rc && wr_ix_pos(ctx, &ip, nullptr) != hipSuccess) rc = ORCGPU_HIP_ERROR;
@@ -667,6 +764,12 @@ int wr_flush(orcgpu_writer* w) {
       streams.push_back(St{2, column, at});
       ip = ixp(1, ci, c.n_valid, li, 2);
       rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li, &ip);
+      if (rc) return rc;
+    } else if (c.stream_kind >= 5) {  // SECONDARY: the nanosecond codes (unsigned); the scale (signed)
+      li = streams.size();
+      streams.push_back(St{5, column, at});
+      ip = ixp(1, ci, c.n_valid, li, 2);
+      rc = wr_rle_stream(w, 0, c.vals2.p, c.n_valid, c.elem2(), c.stream_kind == 6, &at, li, &ip);
       if (rc) return rc;
     }
     if (c.present) {
@@ -792,6 +895,11 @@ int wr_flush(orcgpu_writer* w) {
     m.u64(1, ci ? (uint64_t)w->cols[ci - 1].encoding : 0u);
     footer.msg(2, m);
   }
+  for (auto& c : w->cols)
+    if (c.stream_kind == 5) {  // (without it Apache ORC reads TIMESTAMP columns in the reading host's zone)
+      footer.bytes(3, "UTC", 3);
+      break;
+    }
   if (comp) footer.b = lzc_original_chunks(footer.b, w->comp_block);
   const uint64_t start = w->written;
   for (auto& b : index) {
@@ -840,6 +948,7 @@ int wr_close(orcgpu_writer* w) {
   for (auto& c : w->cols) {
     PbOut t;
     t.u64(1, (uint64_t)c.orc_kind);
+    if (c.stream_kind == 6) t.u64(5, c.precision), t.u64(6, c.scale);
     footer.msg(4, t);
   }
   footer.u64(6, rows);
@@ -882,7 +991,11 @@ int wr_close(orcgpu_writer* w) {
 }
 
 // an upper bound of what a column's value encoder can count for n values (written out or pending)
-inline uint64_t wr_bound(const WrCol& c, uint64_t n) { return wr_stream_bound(c.stream_kind == 1 ? 1 : 0, c.elem, n); }
+inline uint64_t wr_bound(const WrCol& c, uint64_t n) {
+  if (c.stream_kind == 5) return 2 * wr_stream_bound(0, 8, n);
+  if (c.stream_kind == 6) return wr_stream_bound(0, 2, n);
+  return wr_stream_bound(c.stream_kind == 1 ? 1 : 0, c.elem, n);
+}
 
 }  // namespace
 
@@ -911,8 +1024,9 @@ extern "C" int orcgpu_writer_open_bytes(orcgpu_ctx* ctx, const struct ArrowSchem
   return rc ? rc : wr_start(w, out);
 }
 
-// ArrowWriter::write after orcgpu_writer_write's checks; dev_ends: the device string columns' first and last offsets
-int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, const std::vector<int64_t>& dev_ends) {
+// ArrowWriter::write after orcgpu_writer_write's checks; dev_ends: the device string columns' first and last offsets.
+// *rejected: the batch holds a value without an encoding (INVALID_ARGUMENT) and the writer is as it was before the call
+int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, const std::vector<int64_t>& dev_ends, bool* rejected) {
   orcgpu_ctx* ctx = w->ctx;
   const uint64_t R = batch->length < 0 ? 0 : (uint64_t)batch->length;
   if (batch->n_children != (int64_t)w->cols.size() || (w->cols.size() && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
@@ -929,9 +1043,11 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
   if (!wr_ensure(w, w->slice_counts, nc * n_slices * 16 + 16 * nc + kAlign)) return ORCGPU_HIP_ERROR;
   uint64_t* d_cv = (uint64_t*)w->slice_counts.p;  // [col][slice] valid, then [col][slice] bytes, then the columns' "bad offsets" words
   uint64_t* d_cb = d_cv + nc * n_slices;
-  uint32_t* d_bad = (uint32_t*)(d_cb + nc * n_slices);
-  if (nc) WR_TRY(hipMemsetAsync(d_bad, 0, nc * 4, st));
+  uint32_t* d_bad = (uint32_t*)(d_cb + nc * n_slices);  // (then the columns' "timestamp without an encoding" words)
+  if (nc) WR_TRY(hipMemsetAsync(d_bad, 0, nc * 8, st));
   const int64_t row0 = batch->offset;
+  std::vector<char> present0(nc);
+  for (size_t ci = 0; ci < nc; ci++) present0[ci] = w->cols[ci].present;
   // 1. every column of the batch -> presence bytes, the valid rows' values, the strings' bytes; counts per slice
   for (size_t ci = 0; ci < nc; ci++) {
     WrCol& c = w->cols[ci];
@@ -1001,12 +1117,13 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     // presence: a bitmap from bit 0 (all set without a validity buffer) and its bytes
     Bump T;
     const uint64_t n_words = (R + 63) / 64;
+    if (c.stream_kind == 6) str_hi = R * (uint64_t)WR_DEC_MAX_BYTES;  // (the varints' bytes: a bound)
     const uint64_t o_bits = T.take(n_words * 8 + 8), o_vbits = T.take(c.stream_kind == 3 ? n_words * 8 + 8 : 0), o_wcnt = T.take(n_words * 4),
                    o_woff = T.take(n_words * 8), o_sums = T.take((n_words / 2048 + 2) * 8), o_tot = T.take(16),
-                   o_len = T.take(c.is_string ? R * (uint64_t)c.elem : 0), o_vlen = T.take(c.is_string ? R * 4 : 0),
-                   o_dst = T.take(c.is_string ? R * 8 : 0), o_sums2 = T.take((R / 2048 + 2) * 8), o_tot2 = T.take(16);
-    if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, R + kAlign) || !wr_ensure(w, c.b_vals, R * (uint64_t)c.elem + kAlign) ||
-        !wr_ensure(w, c.b_data, str_hi + kAlign))
+                   o_len = T.take(c.is_string ? R * (uint64_t)c.elem : 0), o_vlen = T.take(c.has_bytes() ? R * 4 : 0),
+                   o_dst = T.take(c.has_bytes() ? R * 8 : 0), o_sums2 = T.take((R / 2048 + 2) * 8), o_tot2 = T.take(16);
+    if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, R + kAlign) || !wr_ensure(w, c.b_vals, (c.stream_kind == 6 && !w->stride ? 0 : R * (uint64_t)c.elem) + kAlign) ||
+        !wr_ensure(w, c.b_data, str_hi + kAlign) || !wr_ensure(w, c.b_vals2, (c.stream_kind == 5 ? R * 8 : 0) + kAlign))
       return ORCGPU_HIP_ERROR;
     uint8_t* t = c.b_bits.p;
     uint8_t* bits = t + o_bits;
@@ -1021,6 +1138,19 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     if (c.stream_kind == 3) {  // the valid rows' Boolean values as 0 / 1 bytes
       WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, (const uint8_t*)d_values, d_vbit, R, t + o_vbits));
       WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)(t + o_vbits), 0, (void*)c.b_vals.p));
+    } else if (c.stream_kind == 5) {  // the valid rows' seconds since 2015 and nanosecond codes
+      WR_TRY(launch(wr_timestamp_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const int64_t*)d_values, c.ups, c.npu,
+                    (int64_t*)c.b_vals.p, (uint64_t*)c.b_vals2.p, d_bad + nc + ci));
+    } else if (c.stream_kind == 6) {  // the valid rows' varints one behind the other, and the values themselves (statistics)
+      WR_TRY(launch(wr_dec_lengths_kernel, R, false, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, R, (uint32_t*)(t + o_vlen)));
+      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), R, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
+      if (rc) return rc;
+      WR_TRY(launch(wr_dec_pack_kernel, (R + 255) / 256, true, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, R, (const uint64_t*)(t + o_dst),
+                    (const uint32_t*)(t + o_vlen), c.b_data.p, str_hi));
+      if (w->stride)  // (the values themselves: only the row index statistics read them)
+        WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)d_values, 16, (void*)c.b_vals.p));
+      row_dst = (const uint64_t*)(t + o_dst);
+      vlen = (const uint32_t*)(t + o_vlen);
     } else if (!c.is_string) {
       WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)d_values, c.elem, (void*)c.b_vals.p));
     } else {
@@ -1039,17 +1169,24 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
                   d_cb + ci * n_slices));
   }
   std::vector<uint64_t> cv(nc * n_slices), cb(nc * n_slices);
-  std::vector<uint32_t> bad(nc);
+  std::vector<uint32_t> bad(2 * nc);
   if (nc) {
     WR_TRY(hipMemcpyAsync(cv.data(), d_cv, nc * n_slices * 8, hipMemcpyDeviceToHost, st));
     WR_TRY(hipMemcpyAsync(cb.data(), d_cb, nc * n_slices * 8, hipMemcpyDeviceToHost, st));
-    WR_TRY(hipMemcpyAsync(bad.data(), d_bad, nc * 4, hipMemcpyDeviceToHost, st));
+    WR_TRY(hipMemcpyAsync(bad.data(), d_bad, nc * 8, hipMemcpyDeviceToHost, st));
   }
   int rc = wr_sync(w);
   if (rc) return rc;
   for (size_t ci = 0; ci < nc; ci++)
     if (bad[ci]) {
       set_err(ctx, "writer: the offsets of column %zu are not ascending (or a value is 4 GiB or longer)", ci);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+  for (size_t ci = 0; ci < nc; ci++)
+    if (bad[nc + ci]) {  // nothing of the batch was taken: the writer stays as it was
+      for (size_t k = 0; k < nc; k++) w->cols[k].present = present0[k];
+      set_err(ctx, "writer: column %zu holds a timestamp ORC cannot encode (within the second before 1970-01-01 00:00:00 but not on it, or its second too far from 2015 for i64)", ci);
+      *rejected = true;
       return ORCGPU_INVALID_ARGUMENT;
     }
   auto V = [&](size_t ci, uint64_t j) -> uint64_t { return j ? cv[ci * n_slices + j - 1] : 0; };  // valid rows before slice j
@@ -1060,13 +1197,20 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     for (size_t ci = 0; ci < nc; ci++) {
       WrCol& c = w->cols[ci];
       const uint64_t dv = V(ci, j1) - V(ci, j0), dr = rows_to(j1) - rows_to(j0), db = B(ci, j1) - B(ci, j0);
-      const uint64_t nv = c.n_valid * c.elem, add = dv * c.elem;
-      if (!wr_reserve(w, c.vals, nv + add + kAlign, nv)) return ORCGPU_HIP_ERROR;
-      if (add) WR_TRY(hipMemcpyAsync(c.vals.p + nv, c.b_vals.p + V(ci, j0) * c.elem, add, hipMemcpyDeviceToDevice, st));
+      const uint64_t velem = c.stream_kind == 6 && !w->stride ? 0 : (uint64_t)c.elem;  // (Decimal128 values: kept for the row index only)
+      const uint64_t nv = c.n_valid * velem, add = dv * velem;
+      if (velem && !wr_reserve(w, c.vals, nv + add + kAlign, nv)) return ORCGPU_HIP_ERROR;
+      if (add) WR_TRY(hipMemcpyAsync(c.vals.p + nv, c.b_vals.p + V(ci, j0) * velem, add, hipMemcpyDeviceToDevice, st));
+      if (c.stream_kind >= 5) {
+        const uint64_t e2 = (uint64_t)c.elem2(), nv2 = c.n_valid * e2;
+        if (!wr_reserve(w, c.vals2, nv2 + dv * e2 + kAlign, nv2)) return ORCGPU_HIP_ERROR;
+        if (dv && c.stream_kind == 5) WR_TRY(hipMemcpyAsync(c.vals2.p + nv2, c.b_vals2.p + V(ci, j0) * e2, dv * e2, hipMemcpyDeviceToDevice, st));
+        if (dv && c.stream_kind == 6) WR_TRY(launch(wr_fill16_kernel, dv, false, 256, st, (uint16_t*)(c.vals2.p + nv2), dv, (uint16_t)c.scale));
+      }
       if (commit) {
         if (!wr_reserve(w, c.pres, c.rows + dr + kAlign, c.rows)) return ORCGPU_HIP_ERROR;
         if (dr) WR_TRY(hipMemcpyAsync(c.pres.p + c.rows, c.b_pres.p + rows_to(j0), dr, hipMemcpyDeviceToDevice, st));
-        if (c.is_string) {
+        if (c.has_bytes()) {
           if (!wr_reserve(w, c.data, c.n_bytes + db + kAlign, c.n_bytes)) return ORCGPU_HIP_ERROR;
           if (db) WR_TRY(hipMemcpyAsync(c.data.p + c.n_bytes, c.b_data.p + B(ci, j0), db, hipMemcpyDeviceToDevice, st));
         }
@@ -1090,7 +1234,7 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
         case 3: e += nv / 8; break;
         // (the run-length encoded terms: exactly base_rle when the columns had base_valid values; each run written out since
         // covers values from then on, or from the run open then -- at most 512 values before)
-        case 4: e += c.n_bytes + B(ci, j + 1) - B(ci, j0); bound += wr_bound(c, nv - c.base_valid + 512); break;
+        case 4: case 6: e += c.n_bytes + B(ci, j + 1) - B(ci, j0); bound += wr_bound(c, nv - c.base_valid + 512); break;
         default: bound += wr_bound(c, nv - c.base_valid + 512); break;
       }
     }
@@ -1108,27 +1252,32 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     for (size_t ci = 0; ci < nc; ci++) {
       WrCol& c = w->cols[ci];
       if (c.stream_kind == 2 || c.stream_kind == 3) continue;
-      EncJob J;
-      J.kind = c.stream_kind == 1 ? 1 : 0;
-      J.int_bytes = c.elem;
-      J.is_signed = c.stream_kind == 0;
-      J.n = c.n_valid + V(ci, j1) - V(ci, j0);
-      J.values = c.vals.p;
-      J.deferred = true;  // (no host wait: the run count stays on the device, the grids cover n runs)
-      J.syncs = &w->round_trips;
-      if (!J.n) continue;
-      if (!wr_ensure(w, w->trig, J.n * 8 + kAlign)) return -1;  // (before the plan: growing waits, and the tables are the plan's)
-      if (enc_plan(ctx, J)) return -1;
-      uint64_t* d_trig = (uint64_t*)w->trig.p;
-      hipError_t e = J.kind == 0 ? launch(wr_triggers_kernel<0>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, J.int_bytes, (const uint32_t*)J.runs,
-                                          J.d_n_runs, J.n, d_trig)
-                                 : launch(wr_triggers_kernel<1>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, 1, (const uint32_t*)J.runs, J.d_n_runs,
-                                          J.n, d_trig);
-      if (e != hipSuccess) return -1;
-      // values after slice j: c.n_valid + cv[j] - V(j0)
-      e = launch(wr_estimate_kernel, win, false, 256, st, (const uint64_t*)d_trig, (const uint32_t*)J.runs, (const uint32_t*)J.run_bytes, (const uint64_t*)J.offsets,
-                 J.d_n_runs, J.kind, (const uint64_t*)(d_cv + ci * n_slices + j0), (int64_t)c.n_valid - (int64_t)V(ci, j0), win, d_est);
-      if (e != hipSuccess) return -1;
+      // which of the column's value streams go through an encoder: Timestamp both (as two Int64 columns would count),
+      // Decimal128 the second alone (the scale; its DATA bytes are counted), every other column its one
+      const int first = c.stream_kind == 6, last = c.stream_kind >= 5;
+      for (int second = first; second <= last; second++) {
+        EncJob J;
+        J.kind = c.stream_kind == 1 ? 1 : 0;
+        J.int_bytes = second ? c.elem2() : c.elem;
+        J.is_signed = second ? c.stream_kind == 6 : (c.stream_kind == 0 || c.stream_kind == 5);
+        J.n = c.n_valid + V(ci, j1) - V(ci, j0);
+        J.values = second ? c.vals2.p : c.vals.p;
+        J.deferred = true;  // (no host wait: the run count stays on the device, the grids cover n runs)
+        J.syncs = &w->round_trips;
+        if (!J.n) continue;
+        if (!wr_ensure(w, w->trig, J.n * 8 + kAlign)) return -1;  // (before the plan: growing waits, and the tables are the plan's)
+        if (enc_plan(ctx, J)) return -1;
+        uint64_t* d_trig = (uint64_t*)w->trig.p;
+        hipError_t e = J.kind == 0 ? launch(wr_triggers_kernel<0>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, J.int_bytes, (const uint32_t*)J.runs,
+                                            J.d_n_runs, J.n, d_trig)
+                                   : launch(wr_triggers_kernel<1>, (uint64_t)J.n_runs, false, 256, st, (const void*)J.values, 1, (const uint32_t*)J.runs, J.d_n_runs,
+                                            J.n, d_trig);
+        if (e != hipSuccess) return -1;
+        // values after slice j: c.n_valid + cv[j] - V(j0)
+        e = launch(wr_estimate_kernel, win, false, 256, st, (const uint64_t*)d_trig, (const uint32_t*)J.runs, (const uint32_t*)J.run_bytes, (const uint64_t*)J.offsets,
+                   J.d_n_runs, J.kind, (const uint64_t*)(d_cv + ci * n_slices + j0), (int64_t)c.n_valid - (int64_t)V(ci, j0), win, d_est);
+        if (e != hipSuccess) return -1;
+      }
     }
     est.assign(win, 0);
     if (hipMemcpyAsync(est.data(), d_est, win * 8, hipMemcpyDeviceToHost, st) != hipSuccess || wr_sync(w)) return -1;
@@ -1251,8 +1400,9 @@ extern "C" int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* s
       }
     }
   }
-  int rc = wr_write(w, batch, flags, dev_ends);
-  if (rc) w->failed = true;
+  bool rejected = false;
+  int rc = wr_write(w, batch, flags, dev_ends, &rejected);
+  if (rc && !rejected) w->failed = true;
   return rc;
 }
 
@@ -1347,10 +1497,12 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
   for (auto& c : w->cols) {
     c.pres.release();
     c.vals.release();
+    c.vals2.release();
     c.data.release();
     c.b_bits.release();
     c.b_pres.release();
     c.b_vals.release();
+    c.b_vals2.release();
     c.b_data.release();
     c.b_tmp.release();
   }

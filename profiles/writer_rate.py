@@ -9,7 +9,11 @@ Usage: python profiles/writer_rate.py [rows]  -> one JSON object on stdout.
 --kernel-stats FILE: folds in the kernel_stats.csv of a `rocprofv3 --kernel-trace --stats` run of the same command (the compression
 kernels, lzc_*, against the writer's other device work).
 --row-index-stride N: the writer with ROW_INDEX streams and statistics (ArrowWriterBuilder.with_row_index_stride) against the same
-writes without them, uncompressed and with Snappy; with --kernel-stats, the row index kernels' (ix_*) share of the device time."""
+writes without them, uncompressed and with Snappy; with --kernel-stats, the row index kernels' (ix_*) share of the device time.
+--types: the lineitem table with Decimal128(15,2) for its four money columns and Timestamp(ns) for l_shipdate, beside the stand-in
+table of floats and integers in the same run (host batches, 64 MiB stripes, best of 3) and their ratio; with --kernel-stats, the
+share of the Timestamp / Decimal128 kernels (wr_timestamp_kernel, wr_dec_*, wr_fill16_kernel) in the device time
+(profiles/writer_rate_types.json)."""
 import argparse
 import csv
 import ctypes as C
@@ -59,6 +63,29 @@ def lineitem(n, rng):
         "l_comment": np.char.add("c", rng.integers(0, 1 << 40, n).astype("U16")),
     }
     return pa.RecordBatch.from_pydict({k: one(pa.array(v)) for k, v in cols.items()})
+
+
+MONEY = ["l_quantity", "l_extendedprice", "l_discount", "l_tax"]
+
+
+def decimal_from_cents(cents):
+    """Decimal128(15, 2) of int64 hundredths, from its buffer (16 bytes a value, little endian, sign-extended)"""
+    v = np.empty((len(cents), 2), dtype=np.int64)
+    v[:, 0] = cents
+    v[:, 1] = cents >> 63
+    return pa.Array.from_buffers(pa.decimal128(15, 2), len(cents), [None, pa.py_buffer(v.tobytes())])
+
+
+def lineitem_types(batch):
+    """the same rows with the types TPC-H gives them: the money columns Decimal128(15,2), l_shipdate a Timestamp(ns)"""
+    cols = []
+    for name, col in zip(batch.schema.names, batch.columns):
+        if name in MONEY:
+            col = decimal_from_cents(np.round(col.to_numpy() * 100).astype(np.int64))
+        elif name == "l_shipdate":
+            col = pa.array(col.to_numpy().astype(np.int64) * 86400 * 10 ** 9 + 12345, type=pa.int64()).cast(pa.timestamp("ns"))
+        cols.append(col)
+    return pa.RecordBatch.from_arrays(cols, names=batch.schema.names)
 
 
 class DeviceBatch:
@@ -207,13 +234,52 @@ def main_indexed(args):
     print(json.dumps(out))
 
 
+TYPE_KERNELS = ("wr_timestamp_kernel", "wr_dec_lengths_kernel", "wr_dec_pack_kernel", "wr_fill16_kernel")
+
+
+def main_types(args):
+    n, per_batch = args.rows, 1_000_000
+    rng = np.random.default_rng(1)
+    plain = [lineitem(per_batch, rng) for _ in range(max(1, n // per_batch))]
+    typed = [lineitem_types(b) for b in plain]
+    ctx = capi.Context()
+    out = {"rows": per_batch * len(plain), "columns": plain[0].num_columns,
+           "unit": "GB/s of Arrow input (open .. close), host batches, 64 MiB stripes, best of 3", "runs": {}}
+    for name, batches in [("floats and integers (the stand-in)", plain), ("Decimal128(15,2) x 4, Timestamp(ns)", typed)]:
+        arrow_bytes = sum(b.nbytes for b in batches)
+        gpu_write(ctx, batches[:1], batches[0].schema, 64 << 20)  # warm-up
+        best = None
+        for _ in range(3):
+            r = gpu_write(ctx, batches, batches[0].schema, 64 << 20)
+            if best is None or r[0] < best[0]:
+                best = r
+        dt, st, size = best
+        out["runs"][name] = {"seconds": round(dt, 4), "arrow_bytes": arrow_bytes, "GB/s": round(arrow_bytes / dt / 1e9, 3),
+                             "Mrows/s": round(out["rows"] / dt / 1e6, 2), "file_bytes": size, "stripes": st["stripes"],
+                             "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    a, b = out["runs"]["floats and integers (the stand-in)"], out["runs"]["Decimal128(15,2) x 4, Timestamp(ns)"]
+    out["types_vs_stand_in"] = {"GB/s": round(b["GB/s"] / a["GB/s"], 3), "Mrows/s": round(b["Mrows/s"] / a["Mrows/s"], 3)}
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        ms = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows}
+        mine = {k: v for k, v in ms.items() if k in TYPE_KERNELS}
+        top = sorted(ms.items(), key=lambda kv: -kv[1])[:6]
+        out["kernels"] = {"what": "rocprofv3 --kernel-trace --stats of this command, both tables, all runs", "all_kernels_ms": round(total / 1e6, 3),
+                          "type_kernels_ms": mine, "type_kernels_share": round(sum(mine.values()) * 1e6 / total, 4), "largest_kernels_ms": dict(top)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
     ap.add_argument("--compression", choices=["snappy", "lz4"])
     ap.add_argument("--kernel-stats")
     ap.add_argument("--row-index-stride", type=int, default=0)
+    ap.add_argument("--types", action="store_true")
     args = ap.parse_args()
+    if args.types:
+        return main_types(args)
     if args.row_index_stride:
         return main_indexed(args)
     if args.compression:
