@@ -447,6 +447,15 @@ int orcgpu_encode_fetch(orcgpu_ctx* ctx, const orcgpu_enc_stream* stream, uint8_
  * encoder estimate exceeds stripe_byte_size) and reaches the host in one copy.  Uncompressed by default (the reference writes
  * CompressionKind::None only); orcgpu_writer_set_compression selects Snappy or LZ4, compressed on the device (below).
  * schema: an Arrow struct ("+s") of the fields.  Another type than those: ORCGPU_UNSUPPORTED at open (the reference panics).
+ * Nested fields, to any depth: Struct (STRUCT: [PRESENT], DIRECT), List / LargeList (LIST: LENGTH, [PRESENT], DIRECT_V2) and
+ * Map (MAP: the same; its key and value are its two children, the Arrow entries struct gets no column) over those leaves; the
+ * columns are numbered in preorder and their streams written in that order.  A child column holds one entry per existing
+ * row of its parent, flattened on the device from the arrays' validity, offsets and slicing.  Offsets that descend or address
+ * rows beyond the child: write returns ORCGPU_INVALID_ARGUMENT, nothing of the batch is taken and the writer stays usable.
+ * The stripe cut counts every column of the tree after each slice of batch_size root rows.  Still ORCGPU_UNSUPPORTED at open,
+ * the message naming the field's path: FixedSizeList, ListView, Union, dictionary and run-end encoded types, and Decimal128
+ * below a List or Map.  With a nested schema orcgpu_writer_set_row_index (stride > 0) and ORCGPU_ENC_ON_DEVICE batches return
+ * ORCGPU_UNSUPPORTED.
  * write: the batch as an Arrow struct array with the schema it was exported with; a schema that differs from the writer's (names,
  * types, nullability, metadata): ORCGPU_UNEXPECTED.  ORCGPU_ENC_ON_DEVICE: the buffers are device memory of ctx's device (the
  * GPU reader's batches, orcgpu_result_batch_view).  What the writer needs is copied before it returns.
@@ -464,6 +473,8 @@ typedef struct orcgpu_writer_counts {
   uint64_t round_trips;       /* host waits for the device of the writer so far: synchronisations, and the growth of its device
                                  buffers (a free waits for the device) */
   uint64_t stripe_round_trips;/* ... of them, those of the stripes' encoding and copy (two a stripe once the buffers have grown) */
+  uint64_t nested_slices;     /* columns below a Struct / List / Map, summed over the writes: taken as one slice of their array ... */
+  uint64_t nested_gathers;    /* ... or, rows of a null parent lying in between, gathered through a row map */
 } orcgpu_writer_counts;
 int orcgpu_writer_open_file(orcgpu_ctx* ctx, const char* path, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out);
 int orcgpu_writer_open_bytes(orcgpu_ctx* ctx, const struct ArrowSchema* schema, const orcgpu_writer_opts* opts, orcgpu_writer** out);

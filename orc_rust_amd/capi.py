@@ -116,7 +116,7 @@ class WriterOpts(C.Structure):
 
 class WriterCounts(C.Structure):
     _fields_ = [("stripes", C.c_uint64), ("rows", C.c_uint64), ("bytes", C.c_uint64), ("round_trips", C.c_uint64),
-                ("stripe_round_trips", C.c_uint64)]
+                ("stripe_round_trips", C.c_uint64), ("nested_slices", C.c_uint64), ("nested_gathers", C.c_uint64)]
 
 
 class EncStream(C.Structure):

@@ -111,10 +111,15 @@ struct WrCol {
   int elem = 0;        // bytes of a value as the column's value encoder takes it (Boolean: a byte; strings: the offset width)
   bool is_string = false;
   int stream_kind = 0; // 0 Integer RLE v2 (signed), 1 byte RLE, 2 raw floats, 3 Boolean, 4 strings (bytes + unsigned RLE v2 lengths),
-                       // 5 Timestamp (seconds + nanosecond codes, RLE v2), 6 Decimal128 (varint bytes + the scale, signed RLE v2)
+                       // 5 Timestamp (seconds + nanosecond codes, RLE v2), 6 Decimal128 (varint bytes + the scale, signed RLE v2),
+                       // 7 Struct (PRESENT alone), 8 List / Map (vals: the valid rows' lengths, unsigned RLE v2, in the offsets' width)
   int orc_kind = 0;    // Type.Kind
   int encoding = 0;    // ColumnEncoding.Kind
-  std::string name;
+  std::string name, path;
+  // the column tree, preorder (column id = index + 1): the parent's index (-1: the root), which of the parent array's children
+  // the column's array is (a Map's: of its entries struct's), and the children's indexes
+  int parent = -1, child = 0;
+  std::vector<int> kids;
   bool present = false;  // sticky once an array with a validity bitmap arrived (writer/column.rs:103-139)
   uint64_t rows = 0, n_valid = 0, n_bytes = 0;  // of the open stripe
   uint64_t base_valid = 0;                       // values of the stripe when orcgpu_writer::base_rle was found
@@ -125,13 +130,27 @@ struct WrCol {
   DevVec pres, vals, vals2, data;
   // this write call's batch, in the same form
   DevBuf b_bits, b_pres, b_vals, b_vals2, b_data, b_tmp;
+  // nested: a Struct's / List's children's rows as a map (device/writer_nested.hip); a leaf's arrays gathered through its parent's
+  DevBuf k_map, b_gath;
+  bool is_nest() const { return stream_kind >= 7; }
+  int value_streams() const { return stream_kind == 7 ? 0 : (stream_kind == 8 || stream_kind < 4 ? 1 : 2); }
   bool has_bytes() const { return stream_kind == 4 || stream_kind == 6; }  // n_bytes / data count toward the estimate
   int elem2() const { return stream_kind == 5 ? 8 : 2; }
 };
 
-struct WrField {  // what ArrowWriter::write compares (batch.schema() == self.schema)
+struct WrField {  // what ArrowWriter::write compares (batch.schema() == self.schema), at every level of the tree
   std::string format, name, metadata;
-  int64_t flags;
+  int64_t flags = 0;
+  bool dictionary = false;
+  std::vector<WrField> kids;
+  bool same(const WrField& o) const {
+    if (format != o.format || name != o.name || metadata != o.metadata || (flags & 2) != (o.flags & 2) || dictionary != o.dictionary ||
+        kids.size() != o.kids.size())
+      return false;
+    for (size_t i = 0; i < kids.size(); i++)
+      if (!kids[i].same(o.kids[i])) return false;
+    return true;
+  }
 };
 
 }  // namespace
@@ -143,7 +162,11 @@ struct orcgpu_writer {
   std::vector<uint8_t> mem;  // the memory sink's bytes not drained yet
   bool closed = false, failed = false;
   uint64_t batch_size = 1024, stripe_byte_size = 64ull << 20;
-  std::vector<WrCol> cols;
+  std::vector<WrCol> cols;  // every column of the tree but the root, preorder
+  std::vector<int> root_kids;
+  bool nested = false;      // a Struct, List or Map column among them
+  uint64_t nested_slices = 0, nested_gathers = 0;  // columns of a write taken as a slice of their array / gathered through a map
+  DevBuf nest;              // a write's NestRows per column, `bad`, and the columns' slice ends
   std::vector<WrField> fields;
   std::string root_metadata;
   int64_t root_flags = 0;
@@ -217,7 +240,7 @@ std::string wr_metadata(const char* m) {
 
 // the column writer of an Arrow type (writer/stripe.rs:173-187, arrow_writer.rs:158-222); false: the reference's unimplemented!()
 bool wr_column_of(const char* fmt, WrCol& c) {
-  if (!fmt || !fmt[0] || strstr(fmt, "#nested")) return false;
+  if (!fmt || !fmt[0]) return false;
   if (fmt[0] == 't' && fmt[1] == 's' && fmt[2] && fmt[3] == ':') {  // Timestamp(unit, tz): with a zone an instant
     switch (fmt[2]) {
       case 's': c.ups = 1; c.npu = 1000000000; break;
@@ -259,20 +282,80 @@ bool wr_column_of(const char* fmt, WrCol& c) {
   }
 }
 
+bool wr_read_field(const ArrowSchema* c, WrField& f, int depth) {
+  if (!c || !c->format || depth > 64 || c->n_children < 0 || (c->n_children && !c->children)) return false;
+  f.format = c->format;
+  f.name = c->name ? c->name : "";
+  f.metadata = wr_metadata(c->metadata);
+  f.flags = c->flags;
+  f.dictionary = c->dictionary != nullptr;
+  f.kids.resize((size_t)c->n_children);
+  for (int64_t i = 0; i < c->n_children; i++)
+    if (!wr_read_field(c->children[i], f.kids[(size_t)i], depth + 1)) return false;
+  return true;
+}
+
 int wr_read_schema(orcgpu_ctx* ctx, const ArrowSchema* s, std::vector<WrField>& fields, std::string& md, int64_t& flags) {
   if (!s || !s->format || strcmp(s->format, "+s") != 0 || s->n_children < 0 || (s->n_children && !s->children)) {
     set_err(ctx, "writer: the schema must be an Arrow struct (format \"+s\") of its fields");
     return ORCGPU_INVALID_ARGUMENT;
   }
   fields.clear();
-  for (int64_t i = 0; i < s->n_children; i++) {
-    const ArrowSchema* c = s->children[i];
-    if (!c || !c->format) return ORCGPU_INVALID_ARGUMENT;
-    fields.push_back(WrField{c->format, c->name ? c->name : "", wr_metadata(c->metadata), c->flags});
-    if (c->n_children || c->dictionary) fields.back().format += "#nested";  // (nested / dictionary types: never a writer's)
-  }
+  fields.resize((size_t)s->n_children);
+  for (int64_t i = 0; i < s->n_children; i++)
+    if (!wr_read_field(s->children[i], fields[(size_t)i], 0)) return ORCGPU_INVALID_ARGUMENT;
   md = wr_metadata(s->metadata);
   flags = s->flags;
+  return ORCGPU_OK;
+}
+
+int wr_unsupported(orcgpu_ctx* ctx, const WrField& f, const std::string& path, const char* why) {
+  set_err(ctx, "writer: unsupported Arrow type '%s' of field '%s'%s (the reference: unimplemented!(\"unsupported datatype\"), writer/stripe.rs:186; beyond it: Timestamp, Decimal128, Struct, List, LargeList, Map)",
+          f.format.c_str(), path.c_str(), why);
+  return ORCGPU_UNSUPPORTED;
+}
+
+// a field and what is below it -> columns, preorder.  +s STRUCT, +l / +L LIST, +m MAP (its key and value: the entries struct
+// gets no column); under_list: below a List or Map, where Decimal128 is not written
+int wr_add_column(orcgpu_ctx* ctx, orcgpu_writer* w, const WrField& f, int parent, int child, const std::string& path, bool under_list) {
+  const char* fmt = f.format.c_str();
+  if (f.dictionary) return wr_unsupported(ctx, f, path, " (dictionary encoded)");
+  WrCol c;
+  const std::vector<WrField>* kids = nullptr;
+  if (!strcmp(fmt, "+s")) {
+    c.elem = 0; c.stream_kind = 7; c.orc_kind = 12; c.encoding = 0;
+    kids = &f.kids;
+  } else if (!strcmp(fmt, "+l") || !strcmp(fmt, "+L")) {
+    if (f.kids.size() != 1) return ORCGPU_INVALID_ARGUMENT;
+    c.elem = fmt[1] == 'l' ? 4 : 8; c.stream_kind = 8; c.orc_kind = 10; c.encoding = 2;
+    kids = &f.kids;
+    under_list = true;
+  } else if (!strcmp(fmt, "+m")) {
+    if (f.kids.size() != 1 || f.kids[0].format != "+s" || f.kids[0].kids.size() != 2) return ORCGPU_INVALID_ARGUMENT;
+    c.elem = 4; c.stream_kind = 8; c.orc_kind = 11; c.encoding = 2;
+    kids = &f.kids[0].kids;
+    under_list = true;
+  } else if (fmt[0] == '+') {  // FixedSizeList, ListView, Union, run-end encoded
+    return wr_unsupported(ctx, f, path, "");
+  } else {
+    if (!wr_column_of(fmt, c)) return wr_unsupported(ctx, f, path, "");
+    if (c.stream_kind == 6 && under_list) return wr_unsupported(ctx, f, path, " (Decimal128 below a List or Map)");
+  }
+  c.name = f.name;
+  c.path = path;
+  c.parent = parent;
+  c.child = child;
+  const int me = (int)w->cols.size();
+  w->cols.push_back(std::move(c));
+  if (parent >= 0) w->cols[(size_t)parent].kids.push_back(me);
+  else w->root_kids.push_back(me);
+  if (kids) {
+    w->nested = true;
+    for (size_t i = 0; i < kids->size(); i++) {
+      const int rc = wr_add_column(ctx, w, (*kids)[i], me, (int)i, path + "." + (*kids)[i].name, under_list);
+      if (rc) return rc;
+    }
+  }
   return ORCGPU_OK;
 }
 
@@ -281,15 +364,12 @@ int wr_prepare(orcgpu_ctx* ctx, const ArrowSchema* schema, const orcgpu_writer_o
   w->ctx = ctx;
   int rc = wr_read_schema(ctx, schema, w->fields, w->root_metadata, w->root_flags);
   if (rc) return rc;
-  for (auto& fd : w->fields) {
-    WrCol c;
-    if (!wr_column_of(fd.format.c_str(), c)) {
-      set_err(ctx, "writer: unsupported Arrow type '%s' of field '%s' (the reference: unimplemented!(\"unsupported datatype\"), writer/stripe.rs:186; beyond it: Timestamp, Decimal128)",
-              fd.format.c_str(), fd.name.c_str());
-      return ORCGPU_UNSUPPORTED;
+  for (size_t i = 0; i < w->fields.size(); i++) {
+    rc = wr_add_column(ctx, w, w->fields[i], -1, (int)i, w->fields[i].name, false);
+    if (rc) {
+      if (rc == ORCGPU_INVALID_ARGUMENT) set_err(ctx, "writer: field '%s' is not a well-formed Arrow type", w->fields[i].name.c_str());
+      return rc;
     }
-    c.name = fd.name;
-    w->cols.push_back(std::move(c));
   }
   if (opts && opts->batch_size) w->batch_size = opts->batch_size;
   if (opts && opts->stripe_byte_size) w->stripe_byte_size = opts->stripe_byte_size;
@@ -651,7 +731,7 @@ int wr_flush(orcgpu_writer* w) {
   // room: the lengths, the bitmaps of the Boolean / PRESENT streams
   uint64_t n_streams = 0, bits_room = 0;
   for (auto& c : w->cols) {
-    n_streams += 1 + (c.stream_kind >= 4) + c.present;
+    n_streams += c.value_streams() + c.present;
     if (c.stream_kind == 3) bits_room += align_up(2 * ((c.n_valid + 7) / 8) + 16);
     if (c.present) bits_room += align_up(2 * ((c.rows + 7) / 8) + 16);
   }
@@ -737,12 +817,14 @@ int wr_flush(orcgpu_writer* w) {
     WrCol& c = w->cols[ci];
     const uint32_t column = (uint32_t)ci + 1;
     // (the positions list PRESENT first: its stream index is known before it is written)
-    const uint64_t li_present = streams.size() + 1 + (c.stream_kind >= 4);
+    const uint64_t li_present = streams.size() + c.value_streams();
     if (c.present) ixp(0, ci, c.rows, li_present, 3);
     uint64_t li = streams.size();
-    streams.push_back(St{1, column, at});
+    if (c.value_streams()) streams.push_back(St{c.stream_kind == 8 ? 2 : 1, column, at});
     WrIxPos ip;
     switch (c.stream_kind) {
+      case 7: break;  // a Struct: PRESENT alone
+      case 8: rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li); break;  // LENGTH
       case 0: ip = ixp(1, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 1, &at, li, &ip); break;
       case 1: ip = ixp(2, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 1, c.vals.p, c.n_valid, 1, 0, &at, li, &ip); break;
       case 2:
@@ -765,7 +847,7 @@ int wr_flush(orcgpu_writer* w) {
       ip = ixp(1, ci, c.n_valid, li, 2);
       rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li, &ip);
       if (rc) return rc;
-    } else if (c.stream_kind >= 5) {  // SECONDARY: the nanosecond codes (unsigned); the scale (signed)
+    } else if (c.stream_kind == 5 || c.stream_kind == 6) {  // SECONDARY: the nanosecond codes (unsigned); the scale (signed)
       li = streams.size();
       streams.push_back(St{5, column, at});
       ip = ixp(1, ci, c.n_valid, li, 2);
@@ -921,12 +1003,13 @@ int wr_flush(orcgpu_writer* w) {
 
 // the tail: Footer, PostScript, the PostScript's length (arrow_writer.rs:130-156, :224-262)
 int wr_close(orcgpu_writer* w) {
+  // Footer.types, preorder: subtypes and field_names of the Structs (a List: its element; a Map: its key and value)
   PbOut types_root;
   types_root.u64(1, 12);  // STRUCT
   std::vector<uint64_t> sub;
-  for (size_t i = 0; i < w->cols.size(); i++) sub.push_back(i + 1);
+  for (int k : w->root_kids) sub.push_back((uint64_t)k + 1);
   types_root.packed(2, sub);
-  for (auto& c : w->cols) types_root.bytes(3, c.name.data(), c.name.size());
+  for (int k : w->root_kids) types_root.bytes(3, w->cols[(size_t)k].name.data(), w->cols[(size_t)k].name.size());
   PbOut footer;
   uint64_t body = 0, rows = 0;
   for (auto& s : w->stripes) {
@@ -948,6 +1031,11 @@ int wr_close(orcgpu_writer* w) {
   for (auto& c : w->cols) {
     PbOut t;
     t.u64(1, (uint64_t)c.orc_kind);
+    sub.clear();
+    for (int k : c.kids) sub.push_back((uint64_t)k + 1);
+    t.packed(2, sub);
+    if (c.stream_kind == 7)
+      for (int k : c.kids) t.bytes(3, w->cols[(size_t)k].name.data(), w->cols[(size_t)k].name.size());
     if (c.stream_kind == 6) t.u64(5, c.precision), t.u64(6, c.scale);
     footer.msg(4, t);
   }
@@ -1029,7 +1117,7 @@ extern "C" int orcgpu_writer_open_bytes(orcgpu_ctx* ctx, const struct ArrowSchem
 int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, const std::vector<int64_t>& dev_ends, bool* rejected) {
   orcgpu_ctx* ctx = w->ctx;
   const uint64_t R = batch->length < 0 ? 0 : (uint64_t)batch->length;
-  if (batch->n_children != (int64_t)w->cols.size() || (w->cols.size() && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
+  if (batch->n_children != (int64_t)w->root_kids.size() || (w->root_kids.size() && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
   if (R == 0) return ORCGPU_OK;  // (no slice: step_by over an empty range)
   if (R >= 0xffffffffull - 1024) {
     set_err(ctx, "writer: %llu rows in one batch (fewer than 2^32 - 1024 per write)", (unsigned long long)R);
@@ -1048,25 +1136,187 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
   const int64_t row0 = batch->offset;
   std::vector<char> present0(nc);
   for (size_t ci = 0; ci < nc; ci++) present0[ci] = w->cols[ci].present;
-  // 1. every column of the batch -> presence bytes, the valid rows' values, the strings' bytes; counts per slice
+  auto reject = [&]() {  // nothing of the batch was taken: the writer stays as it was
+    for (size_t k = 0; k < nc; k++) w->cols[k].present = present0[k];
+    *rejected = true;
+    return ORCGPU_INVALID_ARGUMENT;
+  };
+  // 0. every column's array, and the rows it can hold by the host's look at its parent's two end offsets: the parent's index q
+  // of a row lies in [qlo, qhi) and the row's place in the array's buffers is q + base.  The root is a Struct whose rows are
+  // 0 .. R; a Struct's child has its parent's q, a List's or Map's the offsets' values [klo, khi)
+  struct WrArr {
+    const ArrowArray* a = nullptr;
+    uint64_t base = 0;
+    int64_t qlo = 0, qhi = 0, klo = 0, khi = 0;
+  };
+  std::vector<WrArr> A(nc);
+  for (size_t ci = 0; ci < nc; ci++) {
+    const WrCol& c = w->cols[ci];
+    WrArr& x = A[ci];
+    int64_t shift = row0;
+    x.qlo = 0;
+    x.qhi = (int64_t)R;
+    if (c.parent < 0) {
+      x.a = batch->children[c.child];
+    } else {
+      const WrCol& pc = w->cols[(size_t)c.parent];
+      const WrArr& px = A[(size_t)c.parent];
+      const ArrowArray* pa = px.a;
+      if (pc.orc_kind == 11) {  // (the Map's entries: a Struct without nulls of the key and the value)
+        if (pa->n_children != 1 || !pa->children || !pa->children[0] || pa->children[0]->offset < 0 || pa->children[0]->length < px.khi) return reject();
+        pa = pa->children[0];
+      }
+      if (pa->n_children <= c.child || !pa->children) return reject();
+      x.a = pa->children[c.child];
+      if (pc.stream_kind == 7) shift = (int64_t)px.base, x.qlo = px.qlo, x.qhi = px.qhi;
+      else shift = pc.orc_kind == 11 ? pa->offset : 0, x.qlo = px.klo, x.qhi = px.khi;
+    }
+    const ArrowArray* a = x.a;
+    const int need = c.stream_kind == 7 ? 1 : (c.is_string ? 3 : 2);
+    if (!a || a->offset < 0 || a->n_buffers < need || !a->buffers) return reject();
+    if (a->length < x.qhi + shift) {
+      set_err(ctx, "writer: column %zu ('%s') has %lld rows, fewer than its parent's offsets address", ci, c.path.c_str(), (long long)a->length);
+      return reject();
+    }
+    x.base = (uint64_t)(shift + a->offset);
+    const uint64_t cap = (uint64_t)(x.qhi - x.qlo);
+    if (c.stream_kind != 7 && cap && (!a->buffers[1] || (c.is_string && !a->buffers[2]))) return reject();
+    if (c.stream_kind == 8 && cap) {
+      const uint8_t* o = (const uint8_t*)a->buffers[1];
+      const uint64_t p0 = (uint64_t)x.qlo + x.base, p1 = (uint64_t)x.qhi + x.base;
+      x.klo = c.elem == 4 ? (int64_t)((const int32_t*)o)[p0] : ((const int64_t*)o)[p0];
+      x.khi = c.elem == 4 ? (int64_t)((const int32_t*)o)[p1] : ((const int64_t*)o)[p1];
+      if (x.klo < 0 || x.khi < x.klo || (uint64_t)(x.khi - x.klo) >= 0xffffffffull - 1024) {
+        set_err(ctx, "writer: the offsets of column %zu ('%s') are not ascending (or address 2^32 - 1024 rows or more)", ci, c.path.c_str());
+        return reject();
+      }
+    }
+  }
+  // 1. nested schemas: the Struct / List / Map columns, parents first, without a host wait -- their presence, lengths and counts
+  // per slice, and their children's rows (device/writer_nested.hip).  What comes back in one wait: NestRows per column (0: the
+  // root's children), `bad`, and every column's slice ends
+  struct HostRows {
+    uint64_t n, start;
+    bool contiguous;
+  };
+  std::vector<HostRows> hrows(nc + 1, HostRows{R, 0, true});
+  std::vector<uint64_t> hends;  // [column + 1][slice]: rows of the column's children before each slice end
+  const uint64_t* d_kends = nullptr;
+  if (w->nested) {
+    Bump N;
+    const uint64_t o_desc = N.take((nc + 1) * sizeof(NestRows)), o_nbad = N.take(8), o_kends = N.take((nc + 1) * n_slices * 8);
+    if (!wr_ensure(w, w->nest, N.off + kAlign)) return ORCGPU_HIP_ERROR;
+    NestRows* d_desc = (NestRows*)(w->nest.p + o_desc);
+    uint32_t* d_nbad = (uint32_t*)(w->nest.p + o_nbad);
+    uint64_t* kends = (uint64_t*)(w->nest.p + o_kends);
+    d_kends = kends;
+    const NestRows root{R, 0, 1, 0};
+    WR_TRY(hipMemsetAsync(d_nbad, 0, 8, st));
+    WR_TRY(hipMemcpyAsync(d_desc, &root, sizeof root, hipMemcpyHostToDevice, st));
+    WR_TRY(launch(nest_root_ends_kernel, n_slices, false, 256, st, R, bs, n_slices, kends));
+    for (size_t ci = 0; ci < nc; ci++) {
+      WrCol& c = w->cols[ci];
+      if (!c.is_nest()) continue;
+      const WrArr& x = A[ci];
+      const ArrowArray* a = x.a;
+      const uint8_t* validity = (const uint8_t*)a->buffers[0];
+      if (validity) c.present = true;
+      const bool is_list = c.stream_kind == 8;
+      const uint64_t cap = (uint64_t)(x.qhi - x.qlo), lo = (uint64_t)x.qlo;
+      const uint64_t kid_lo = is_list ? (uint64_t)x.klo : lo, kid_cap = is_list ? (uint64_t)(x.khi - x.klo) : cap;
+      const NestRows* d_rows = d_desc + (c.parent + 1);
+      const uint32_t* d_map = c.parent < 0 ? nullptr : (const uint32_t*)w->cols[(size_t)c.parent].k_map.p;
+      const uint64_t* d_ends = kends + (uint64_t)(c.parent + 1) * n_slices;
+      // the bytes the rows can occupy, brought over: [validity bytes][offsets]
+      const uint64_t P = lo + x.base, vlo = P / 8, vhi = (P + cap + 7) / 8;
+      Bump I;
+      const uint64_t o_v = I.take(validity && cap ? vhi - vlo : 0), o_x = I.take(is_list && cap ? (cap + 1) * (uint64_t)c.elem : 0);
+      if (!wr_ensure(w, c.b_tmp, I.off + kAlign)) return ORCGPU_HIP_ERROR;
+      if (validity && cap) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_v, validity + vlo, vhi - vlo, hipMemcpyHostToDevice, st));
+      if (is_list && cap)
+        WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_x, (const uint8_t*)a->buffers[1] + P * (uint64_t)c.elem, (cap + 1) * (uint64_t)c.elem, hipMemcpyHostToDevice, st));
+      const uint8_t* d_validity = validity && cap ? c.b_tmp.p + o_v : nullptr;
+      const int64_t vbit = (int64_t)x.base - (int64_t)(8 * vlo), oadj = -(int64_t)lo;
+      const void* d_offsets = c.b_tmp.p + o_x;
+      Bump T;
+      const uint64_t n_words = (cap + 63) / 64;
+      const uint64_t o_bits = T.take(n_words * 8 + 8), o_wcnt = T.take(n_words * 4), o_woff = T.take(n_words * 8), o_sums = T.take((n_words / 2048 + 2) * 8),
+                     o_tot = T.take(16), o_kept = T.take(cap * 4), o_E = T.take(cap * 8 + 8), o_sums2 = T.take((cap / 2048 + 2) * 8), o_tot2 = T.take(16),
+                     o_len = T.take(cap * (uint64_t)c.elem);
+      if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, cap + kAlign) || !wr_ensure(w, c.b_vals, cap * (uint64_t)c.elem + kAlign) ||
+          !wr_ensure(w, c.k_map, kid_cap * 4 + kAlign))
+        return ORCGPU_HIP_ERROR;
+      uint8_t* t = c.b_bits.p;
+      uint8_t* bits = t + o_bits;
+      uint64_t* woff = (uint64_t*)(t + o_woff);
+      uint64_t* E = (uint64_t*)(t + o_E);
+      uint64_t* tot2 = (uint64_t*)(t + o_tot2);
+      const int ob = is_list ? c.elem : 0;
+      WR_TRY(launch(nest_kept_kernel, cap, false, 256, st, d_rows, d_map, lo, cap, d_validity, vbit, d_offsets, oadj, ob, x.klo, x.khi, c.b_pres.p,
+                    (uint32_t*)(t + o_kept), (void*)(t + o_len), (const uint32_t*)d_nbad, d_nbad));
+      WR_TRY(launch(enc_bytes_to_bits_kernel, (cap + 7) / 8, false, 256, st, (const uint8_t*)c.b_pres.p, cap, bits));
+      WR_TRY(launch(enc_valid_counts_kernel, n_words, false, 256, st, (const uint8_t*)bits, cap, (uint32_t*)(t + o_wcnt)));
+      int rc = enc_scan(ctx, st, (const uint32_t*)(t + o_wcnt), n_words, (uint64_t*)(t + o_sums), (uint64_t*)(t + o_tot), woff);
+      if (rc) return rc;
+      if (is_list)  // LENGTH: the valid rows' lengths
+        WR_TRY(launch(enc_gather_valid_kernel, cap, false, 256, st, (const uint8_t*)bits, cap, (const uint64_t*)woff, (const void*)(t + o_len), c.elem, (void*)c.b_vals.p));
+      WR_TRY(launch(nest_slice_counts_kernel, n_slices, false, 256, st, (const uint8_t*)bits, (const uint64_t*)woff, (const uint64_t*)nullptr, (const uint32_t*)nullptr, cap,
+                    d_ends, n_slices, d_cv + ci * n_slices, d_cb + ci * n_slices));
+      // the children's rows
+      WR_TRY(hipMemsetAsync(tot2, 0, 8, st));
+      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_kept), cap, (uint64_t*)(t + o_sums2), tot2, E);
+      if (rc) return rc;
+      WR_TRY(launch(nest_desc_kernel, (uint64_t)1, true, 64, st, d_rows, d_map, lo, d_offsets, oadj, ob, (const uint64_t*)tot2, kid_cap, d_desc + (ci + 1), d_nbad));
+      WR_TRY(launch(nest_fill_kernel, kid_cap, false, 256, st, d_rows, d_map, lo, d_offsets, oadj, ob, (const uint64_t*)E, (const NestRows*)(d_desc + (ci + 1)), kid_lo,
+                    kid_cap, (uint32_t*)c.k_map.p, (const uint32_t*)d_nbad));
+      WR_TRY(launch(nest_ends_kernel, n_slices, false, 256, st, d_ends, d_rows, (const uint64_t*)E, (const uint64_t*)tot2, n_slices, kends + (ci + 1) * n_slices,
+                    (const uint32_t*)d_nbad));
+    }
+    std::vector<uint8_t> back(N.off);
+    WR_TRY(hipMemcpyAsync(back.data(), w->nest.p, N.off, hipMemcpyDeviceToHost, st));
+    int rc = wr_sync(w);
+    if (rc) return rc;
+    uint32_t nbad;
+    memcpy(&nbad, back.data() + o_nbad, 4);
+    if (nbad) {
+      set_err(ctx, "writer: the offsets of a List or Map column are not ascending, or address rows beyond its child");
+      return reject();
+    }
+    const NestRows* hd = (const NestRows*)(back.data() + o_desc);
+    for (size_t k = 1; k <= nc; k++)
+      if (w->cols[k - 1].is_nest()) hrows[k] = HostRows{hd[k].n, hd[k].start, hd[k].contiguous != 0};
+    hends.resize((nc + 1) * n_slices);
+    memcpy(hends.data(), back.data() + o_kends, (nc + 1) * n_slices * 8);
+  }
+  // 2. every leaf column of the batch -> presence bytes, the valid rows' values, the strings' bytes; counts per slice.  Its rows
+  // are a slice of its array (below the root always; below a Struct / List when nothing was dropped), or gathered through the map
   for (size_t ci = 0; ci < nc; ci++) {
     WrCol& c = w->cols[ci];
-    const ArrowArray* a = batch->children[ci];
-    if (!a || a->length < row0 + (int64_t)R || a->n_buffers < (c.is_string ? 3 : 2) || !a->buffers) return ORCGPU_INVALID_ARGUMENT;
-    const uint64_t off = (uint64_t)(row0 + a->offset);
+    if (c.is_nest()) continue;
+    const WrArr& x = A[ci];
+    const ArrowArray* a = x.a;
+    const HostRows& hr = hrows[(size_t)(c.parent + 1)];
+    const uint64_t Rc = hr.n;  // the column's rows in this write
     const uint8_t* validity = (const uint8_t*)a->buffers[0];
     const uint8_t* values = (const uint8_t*)a->buffers[1];
     const uint8_t* strdata = c.is_string ? (const uint8_t*)a->buffers[2] : nullptr;
-    if (!values || (c.is_string && !strdata && R)) return ORCGPU_INVALID_ARGUMENT;
     if (validity) c.present = true;
-    const uint64_t vb = (R + 7) / 8;
+    if (!Rc) {
+      WR_TRY(hipMemsetAsync(d_cv + ci * n_slices, 0, n_slices * 8, st));
+      WR_TRY(hipMemsetAsync(d_cb + ci * n_slices, 0, n_slices * 8, st));
+      continue;
+    }
+    if (!values || (c.is_string && !strdata)) return ORCGPU_INVALID_ARGUMENT;
+    if (c.parent >= 0) (hr.contiguous ? w->nested_slices : w->nested_gathers)++;
+    const uint64_t off = hr.start + x.base;
+    const uint64_t vb = (Rc + 7) / 8;
     // the input on the device: bits from `off`, values from `off`
     const uint8_t* d_valsrc = nullptr;  // validity bits, starting at bit d_valbit
     uint64_t d_valbit = 0;
     const uint8_t* d_values = nullptr;  // fixed width: values from row `off`; Boolean: bits (d_vbit); strings: offsets from row `off`
     uint64_t d_vbit = 0;
     const uint8_t* d_strbase = nullptr;  // strings: the byte the offsets count from
-    uint64_t str_hi = 0;                 // strings: bytes addressed below offsets[off + R] (a bound of the valid rows' bytes)
+    uint64_t str_hi = 0;                 // strings: bytes addressed below offsets[off + Rc] (a bound of the valid rows' bytes)
     if (on_device) {
       d_valsrc = validity;
       d_valbit = off;
@@ -1081,24 +1331,30 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
         str_hi = (uint64_t)(dev_ends[2 * ci + 1] - dev_ends[2 * ci]);
       }
     } else {
-      // the bytes the batch's rows occupy, brought over: [validity bytes][values / bits / offsets][string bytes]
-      const uint64_t vlo = off / 8, vhi = (off + R + 7) / 8;
+      // the bytes the rows occupy, brought over: [validity bytes][values / bits / offsets][string bytes] -- the slice's, or
+      // for the gather every row's the map can name: [qlo, qhi)
+      const uint64_t first = hr.contiguous ? off : (uint64_t)x.qlo + x.base, count = hr.contiguous ? Rc : (uint64_t)(x.qhi - x.qlo);
+      const uint64_t vlo = first / 8, vhi = (first + count + 7) / 8;
       uint64_t val_lo = 0, val_n = 0;
       int64_t s_lo = 0, s_hi = 0;
       if (c.stream_kind == 3) {
         val_lo = vlo;
         val_n = vhi - vlo;
       } else {
-        val_lo = off * (uint64_t)c.elem;
-        val_n = (R + (c.is_string ? 1 : 0)) * (uint64_t)c.elem;
+        val_lo = first * (uint64_t)c.elem;
+        val_n = (count + (c.is_string ? 1 : 0)) * (uint64_t)c.elem;
       }
       if (c.is_string) {
         if (c.elem == 4) {
-          s_lo = ((const int32_t*)values)[off];
-          s_hi = ((const int32_t*)values)[off + R];
+          s_lo = ((const int32_t*)values)[first];
+          s_hi = ((const int32_t*)values)[first + count];
         } else {
-          s_lo = ((const int64_t*)values)[off];
-          s_hi = ((const int64_t*)values)[off + R];
+          s_lo = ((const int64_t*)values)[first];
+          s_hi = ((const int64_t*)values)[first + count];
+        }
+        if (s_lo < 0 || s_hi < s_lo) {
+          set_err(ctx, "writer: the offsets of column %zu are not ascending", ci);
+          return reject();
         }
         str_hi = (uint64_t)(s_hi - s_lo);
       }
@@ -1108,65 +1364,105 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
       if (validity) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_v, validity + vlo, vhi - vlo, hipMemcpyHostToDevice, st));
       if (val_n) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_x, values + val_lo, val_n, hipMemcpyHostToDevice, st));
       if (str_hi) WR_TRY(hipMemcpyAsync(c.b_tmp.p + o_s, strdata + s_lo, str_hi, hipMemcpyHostToDevice, st));
-      d_valsrc = validity ? c.b_tmp.p + o_v : nullptr;
-      d_valbit = off & 7;
-      d_values = c.b_tmp.p + o_x;
-      d_vbit = off & 7;
-      d_strbase = c.b_tmp.p + o_s - s_lo;  // (addressed at offsets >= s_lo only)
+      if (hr.contiguous) {
+        d_valsrc = validity ? c.b_tmp.p + o_v : nullptr;
+        d_valbit = off & 7;
+        d_values = c.b_tmp.p + o_x;
+        d_vbit = off & 7;
+        d_strbase = c.b_tmp.p + o_s - s_lo;  // (addressed at offsets >= s_lo only)
+      } else {
+        // the gather: the column's ORC rows as an array of their own -- validity, values (Boolean: bits), offsets + bytes
+        const uint32_t* d_map = (const uint32_t*)w->cols[(size_t)c.parent].k_map.p;  // q - qlo: the copies' row
+        const int64_t bit_adj = (int64_t)(first - 8 * vlo);
+        Bump Gt;
+        const uint64_t o_gv = Gt.take(vb + 16), o_gx = Gt.take(c.stream_kind == 3 ? vb + 16 : (Rc + 1) * (uint64_t)c.elem + 16), o_gs = Gt.take(str_hi),
+                       o_gl = Gt.take(c.is_string ? Rc * 4 : 0), o_gd = Gt.take(c.is_string ? Rc * 8 : 0), o_gsum = Gt.take((Rc / 2048 + 2) * 8), o_gtot = Gt.take(16);
+        if (!wr_ensure(w, c.b_gath, Gt.off + kAlign)) return ORCGPU_HIP_ERROR;
+        uint8_t* g = c.b_gath.p;
+        if (validity) WR_TRY(launch(nest_gather_bits_kernel, vb, false, 256, st, d_map, Rc, (const uint8_t*)(c.b_tmp.p + o_v), bit_adj, g + o_gv));
+        const uint8_t* src = c.b_tmp.p + o_x;
+        const uint64_t n16 = (Rc * (uint64_t)c.elem + 15) / 16;
+        if (c.stream_kind == 3) {
+          WR_TRY(launch(nest_gather_bits_kernel, vb, false, 256, st, d_map, Rc, src, bit_adj, g + o_gx));
+        } else if (c.is_string) {
+          WR_TRY(launch(nest_str_lengths_kernel, Rc, false, 256, st, d_map, Rc, (const void*)src, c.elem, (int64_t)s_lo, (int64_t)s_hi, (uint32_t*)(g + o_gl), d_bad + ci));
+          int rc = enc_scan(ctx, st, (const uint32_t*)(g + o_gl), Rc, (uint64_t*)(g + o_gsum), (uint64_t*)(g + o_gtot), (uint64_t*)(g + o_gd));
+          if (rc) return rc;
+          WR_TRY(launch(nest_str_copy_kernel, (Rc + 3) / 4, true, 256, st, d_map, Rc, (const void*)src, c.elem, (const uint64_t*)(g + o_gd), (const uint32_t*)(g + o_gl),
+                        (const uint8_t*)(c.b_tmp.p + o_s - s_lo), g + o_gs, str_hi, (void*)(g + o_gx)));
+        } else if (c.elem == 1) {
+          WR_TRY(launch(nest_gather_kernel<uint8_t>, n16, false, 256, st, d_map, Rc, (const uint8_t*)src, (Nest16*)(g + o_gx)));
+        } else if (c.elem == 2) {
+          WR_TRY(launch(nest_gather_kernel<uint16_t>, n16, false, 256, st, d_map, Rc, (const uint16_t*)src, (Nest16*)(g + o_gx)));
+        } else if (c.elem == 4) {
+          WR_TRY(launch(nest_gather_kernel<uint32_t>, n16, false, 256, st, d_map, Rc, (const uint32_t*)src, (Nest16*)(g + o_gx)));
+        } else if (c.elem == 8) {
+          WR_TRY(launch(nest_gather_kernel<uint64_t>, n16, false, 256, st, d_map, Rc, (const uint64_t*)src, (Nest16*)(g + o_gx)));
+        } else {
+          WR_TRY(launch(nest_gather_kernel<Nest16>, n16, false, 256, st, d_map, Rc, (const Nest16*)src, (Nest16*)(g + o_gx)));
+        }
+        d_valsrc = validity ? g + o_gv : nullptr;
+        d_values = g + o_gx;
+        d_strbase = g + o_gs;
+      }
     }
     // presence: a bitmap from bit 0 (all set without a validity buffer) and its bytes
     Bump T;
-    const uint64_t n_words = (R + 63) / 64;
-    if (c.stream_kind == 6) str_hi = R * (uint64_t)WR_DEC_MAX_BYTES;  // (the varints' bytes: a bound)
+    const uint64_t n_words = (Rc + 63) / 64;
+    if (c.stream_kind == 6) str_hi = Rc * (uint64_t)WR_DEC_MAX_BYTES;  // (the varints' bytes: a bound)
     const uint64_t o_bits = T.take(n_words * 8 + 8), o_vbits = T.take(c.stream_kind == 3 ? n_words * 8 + 8 : 0), o_wcnt = T.take(n_words * 4),
                    o_woff = T.take(n_words * 8), o_sums = T.take((n_words / 2048 + 2) * 8), o_tot = T.take(16),
-                   o_len = T.take(c.is_string ? R * (uint64_t)c.elem : 0), o_vlen = T.take(c.has_bytes() ? R * 4 : 0),
-                   o_dst = T.take(c.has_bytes() ? R * 8 : 0), o_sums2 = T.take((R / 2048 + 2) * 8), o_tot2 = T.take(16);
-    if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, R + kAlign) || !wr_ensure(w, c.b_vals, (c.stream_kind == 6 && !w->stride ? 0 : R * (uint64_t)c.elem) + kAlign) ||
-        !wr_ensure(w, c.b_data, str_hi + kAlign) || !wr_ensure(w, c.b_vals2, (c.stream_kind == 5 ? R * 8 : 0) + kAlign))
+                   o_len = T.take(c.is_string ? Rc * (uint64_t)c.elem : 0), o_vlen = T.take(c.has_bytes() ? Rc * 4 : 0),
+                   o_dst = T.take(c.has_bytes() ? Rc * 8 : 0), o_sums2 = T.take((Rc / 2048 + 2) * 8), o_tot2 = T.take(16);
+    if (!wr_ensure(w, c.b_bits, T.off + kAlign) || !wr_ensure(w, c.b_pres, Rc + kAlign) || !wr_ensure(w, c.b_vals, (c.stream_kind == 6 && !w->stride ? 0 : Rc * (uint64_t)c.elem) + kAlign) ||
+        !wr_ensure(w, c.b_data, str_hi + kAlign) || !wr_ensure(w, c.b_vals2, (c.stream_kind == 5 ? Rc * 8 : 0) + kAlign))
       return ORCGPU_HIP_ERROR;
     uint8_t* t = c.b_bits.p;
     uint8_t* bits = t + o_bits;
     uint64_t* woff = (uint64_t*)(t + o_woff);
-    WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, d_valsrc, d_valbit, R, bits));
-    WR_TRY(launch(wr_bits_to_bytes_kernel, R, false, 256, st, (const uint8_t*)bits, R, c.b_pres.p));
-    WR_TRY(launch(enc_valid_counts_kernel, n_words, false, 256, st, (const uint8_t*)bits, R, (uint32_t*)(t + o_wcnt)));
+    WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, d_valsrc, d_valbit, Rc, bits));
+    WR_TRY(launch(wr_bits_to_bytes_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, c.b_pres.p));
+    WR_TRY(launch(enc_valid_counts_kernel, n_words, false, 256, st, (const uint8_t*)bits, Rc, (uint32_t*)(t + o_wcnt)));
     int rc = enc_scan(ctx, st, (const uint32_t*)(t + o_wcnt), n_words, (uint64_t*)(t + o_sums), (uint64_t*)(t + o_tot), woff);
     if (rc) return rc;
     const uint64_t* row_dst = nullptr;
     const uint32_t* vlen = nullptr;
     if (c.stream_kind == 3) {  // the valid rows' Boolean values as 0 / 1 bytes
-      WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, (const uint8_t*)d_values, d_vbit, R, t + o_vbits));
-      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)(t + o_vbits), 0, (void*)c.b_vals.p));
+      WR_TRY(launch(wr_bits_kernel, vb, false, 256, st, (const uint8_t*)d_values, d_vbit, Rc, t + o_vbits));
+      WR_TRY(launch(enc_gather_valid_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, (const uint64_t*)woff, (const void*)(t + o_vbits), 0, (void*)c.b_vals.p));
     } else if (c.stream_kind == 5) {  // the valid rows' seconds since 2015 and nanosecond codes
-      WR_TRY(launch(wr_timestamp_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const int64_t*)d_values, c.ups, c.npu,
+      WR_TRY(launch(wr_timestamp_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, (const uint64_t*)woff, (const int64_t*)d_values, c.ups, c.npu,
                     (int64_t*)c.b_vals.p, (uint64_t*)c.b_vals2.p, d_bad + nc + ci));
     } else if (c.stream_kind == 6) {  // the valid rows' varints one behind the other, and the values themselves (statistics)
-      WR_TRY(launch(wr_dec_lengths_kernel, R, false, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, R, (uint32_t*)(t + o_vlen)));
-      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), R, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
+      WR_TRY(launch(wr_dec_lengths_kernel, Rc, false, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, Rc, (uint32_t*)(t + o_vlen)));
+      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), Rc, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
       if (rc) return rc;
-      WR_TRY(launch(wr_dec_pack_kernel, (R + 255) / 256, true, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, R, (const uint64_t*)(t + o_dst),
+      WR_TRY(launch(wr_dec_pack_kernel, (Rc + 255) / 256, true, 256, st, (const uint64_t*)d_values, (const uint8_t*)bits, Rc, (const uint64_t*)(t + o_dst),
                     (const uint32_t*)(t + o_vlen), c.b_data.p, str_hi));
       if (w->stride)  // (the values themselves: only the row index statistics read them)
-        WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)d_values, 16, (void*)c.b_vals.p));
+        WR_TRY(launch(enc_gather_valid_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, (const uint64_t*)woff, (const void*)d_values, 16, (void*)c.b_vals.p));
       row_dst = (const uint64_t*)(t + o_dst);
       vlen = (const uint32_t*)(t + o_vlen);
     } else if (!c.is_string) {
-      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)d_values, c.elem, (void*)c.b_vals.p));
+      WR_TRY(launch(enc_gather_valid_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, (const uint64_t*)woff, (const void*)d_values, c.elem, (void*)c.b_vals.p));
     } else {
-      WR_TRY(launch(enc_lengths_kernel, R, false, 256, st, (const void*)d_values, c.elem, (const uint8_t*)bits, R, (void*)(t + o_len), (uint32_t*)(t + o_vlen),
+      WR_TRY(launch(enc_lengths_kernel, Rc, false, 256, st, (const void*)d_values, c.elem, (const uint8_t*)bits, Rc, (void*)(t + o_len), (uint32_t*)(t + o_vlen),
                     d_bad + ci));
-      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), R, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
+      rc = enc_scan(ctx, st, (const uint32_t*)(t + o_vlen), Rc, (uint64_t*)(t + o_sums2), (uint64_t*)(t + o_tot2), (uint64_t*)(t + o_dst));
       if (rc) return rc;
       // (bounded by str_hi: the offsets are checked when the counts come back, `bad`)
-      WR_TRY(launch(wr_copy_strings_kernel, (R + 3) / 4, true, 256, st, (const uint8_t*)bits, (const void*)d_values, c.elem, R, (const uint64_t*)(t + o_dst),
+      WR_TRY(launch(wr_copy_strings_kernel, (Rc + 3) / 4, true, 256, st, (const uint8_t*)bits, (const void*)d_values, c.elem, Rc, (const uint64_t*)(t + o_dst),
                     d_strbase, c.b_data.p, str_hi));
-      WR_TRY(launch(enc_gather_valid_kernel, R, false, 256, st, (const uint8_t*)bits, R, (const uint64_t*)woff, (const void*)(t + o_len), c.elem, (void*)c.b_vals.p));
+      WR_TRY(launch(enc_gather_valid_kernel, Rc, false, 256, st, (const uint8_t*)bits, Rc, (const uint64_t*)woff, (const void*)(t + o_len), c.elem, (void*)c.b_vals.p));
       row_dst = (const uint64_t*)(t + o_dst);
       vlen = (const uint32_t*)(t + o_vlen);
     }
-    WR_TRY(launch(wr_slice_counts_kernel, n_slices, false, 256, st, (const uint8_t*)bits, (const uint64_t*)woff, row_dst, vlen, R, bs, n_slices, d_cv + ci * n_slices,
-                  d_cb + ci * n_slices));
+    if (w->nested)
+      WR_TRY(launch(nest_slice_counts_kernel, n_slices, false, 256, st, (const uint8_t*)bits, (const uint64_t*)woff, row_dst, vlen, Rc,
+                    d_kends + (uint64_t)(c.parent + 1) * n_slices, n_slices, d_cv + ci * n_slices, d_cb + ci * n_slices));
+    else
+      WR_TRY(launch(wr_slice_counts_kernel, n_slices, false, 256, st, (const uint8_t*)bits, (const uint64_t*)woff, row_dst, vlen, Rc, bs, n_slices, d_cv + ci * n_slices,
+                    d_cb + ci * n_slices));
   }
   std::vector<uint64_t> cv(nc * n_slices), cb(nc * n_slices);
   std::vector<uint32_t> bad(2 * nc);
@@ -1180,28 +1476,31 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
   for (size_t ci = 0; ci < nc; ci++)
     if (bad[ci]) {
       set_err(ctx, "writer: the offsets of column %zu are not ascending (or a value is 4 GiB or longer)", ci);
-      return ORCGPU_INVALID_ARGUMENT;
+      return w->nested ? reject() : ORCGPU_INVALID_ARGUMENT;
     }
   for (size_t ci = 0; ci < nc; ci++)
     if (bad[nc + ci]) {  // nothing of the batch was taken: the writer stays as it was
-      for (size_t k = 0; k < nc; k++) w->cols[k].present = present0[k];
       set_err(ctx, "writer: column %zu holds a timestamp ORC cannot encode (within the second before 1970-01-01 00:00:00 but not on it, or its second too far from 2015 for i64)", ci);
-      *rejected = true;
-      return ORCGPU_INVALID_ARGUMENT;
+      return reject();
     }
   auto V = [&](size_t ci, uint64_t j) -> uint64_t { return j ? cv[ci * n_slices + j - 1] : 0; };  // valid rows before slice j
   auto B = [&](size_t ci, uint64_t j) -> uint64_t { return j ? cb[ci * n_slices + j - 1] : 0; };
   auto rows_to = [&](uint64_t j) -> uint64_t { return std::min<uint64_t>(j * bs, R); };        // rows before slice j
+  // ... and a column's own rows before it: its parent's children's
+  auto RT = [&](size_t ci, uint64_t j) -> uint64_t {
+    if (!w->nested) return rows_to(j);
+    return j ? hends[(size_t)(w->cols[ci].parent + 1) * n_slices + j - 1] : 0;
+  };
   // the stripe's buffers extended by the batch's slices [j0, j1) (the counters move only with `commit`)
   auto extend = [&](uint64_t j0, uint64_t j1, bool commit) -> int {
     for (size_t ci = 0; ci < nc; ci++) {
       WrCol& c = w->cols[ci];
-      const uint64_t dv = V(ci, j1) - V(ci, j0), dr = rows_to(j1) - rows_to(j0), db = B(ci, j1) - B(ci, j0);
+      const uint64_t dv = V(ci, j1) - V(ci, j0), dr = RT(ci, j1) - RT(ci, j0), db = B(ci, j1) - B(ci, j0);
       const uint64_t velem = c.stream_kind == 6 && !w->stride ? 0 : (uint64_t)c.elem;  // (Decimal128 values: kept for the row index only)
       const uint64_t nv = c.n_valid * velem, add = dv * velem;
       if (velem && !wr_reserve(w, c.vals, nv + add + kAlign, nv)) return ORCGPU_HIP_ERROR;
       if (add) WR_TRY(hipMemcpyAsync(c.vals.p + nv, c.b_vals.p + V(ci, j0) * velem, add, hipMemcpyDeviceToDevice, st));
-      if (c.stream_kind >= 5) {
+      if (c.stream_kind == 5 || c.stream_kind == 6) {
         const uint64_t e2 = (uint64_t)c.elem2(), nv2 = c.n_valid * e2;
         if (!wr_reserve(w, c.vals2, nv2 + dv * e2 + kAlign, nv2)) return ORCGPU_HIP_ERROR;
         if (dv && c.stream_kind == 5) WR_TRY(hipMemcpyAsync(c.vals2.p + nv2, c.b_vals2.p + V(ci, j0) * e2, dv * e2, hipMemcpyDeviceToDevice, st));
@@ -1209,7 +1508,7 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
       }
       if (commit) {
         if (!wr_reserve(w, c.pres, c.rows + dr + kAlign, c.rows)) return ORCGPU_HIP_ERROR;
-        if (dr) WR_TRY(hipMemcpyAsync(c.pres.p + c.rows, c.b_pres.p + rows_to(j0), dr, hipMemcpyDeviceToDevice, st));
+        if (dr) WR_TRY(hipMemcpyAsync(c.pres.p + c.rows, c.b_pres.p + RT(ci, j0), dr, hipMemcpyDeviceToDevice, st));
         if (c.has_bytes()) {
           if (!wr_reserve(w, c.data, c.n_bytes + db + kAlign, c.n_bytes)) return ORCGPU_HIP_ERROR;
           if (db) WR_TRY(hipMemcpyAsync(c.data.p + c.n_bytes, c.b_data.p + B(ci, j0), db, hipMemcpyDeviceToDevice, st));
@@ -1228,10 +1527,11 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     for (size_t ci = 0; ci < nc; ci++) {
       const WrCol& c = w->cols[ci];
       const uint64_t nv = c.n_valid + V(ci, j + 1) - V(ci, j0);
-      if (c.present) e += (c.rows + rows_to(j + 1) - rows_to(j0)) / 8;
+      if (c.present) e += (c.rows + RT(ci, j + 1) - RT(ci, j0)) / 8;
       switch (c.stream_kind) {
         case 2: e += nv * (uint64_t)c.elem; break;
         case 3: e += nv / 8; break;
+        case 7: break;
         // (the run-length encoded terms: exactly base_rle when the columns had base_valid values; each run written out since
         // covers values from then on, or from the run open then -- at most 512 values before)
         case 4: case 6: e += c.n_bytes + B(ci, j + 1) - B(ci, j0); bound += wr_bound(c, nv - c.base_valid + 512); break;
@@ -1251,10 +1551,10 @@ int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, c
     if (extend(j0, j1, false)) return -1;
     for (size_t ci = 0; ci < nc; ci++) {
       WrCol& c = w->cols[ci];
-      if (c.stream_kind == 2 || c.stream_kind == 3) continue;
+      if (c.stream_kind == 2 || c.stream_kind == 3 || c.stream_kind == 7) continue;
       // which of the column's value streams go through an encoder: Timestamp both (as two Int64 columns would count),
       // Decimal128 the second alone (the scale; its DATA bytes are counted), every other column its one
-      const int first = c.stream_kind == 6, last = c.stream_kind >= 5;
+      const int first = c.stream_kind == 6, last = c.stream_kind == 5 || c.stream_kind == 6;
       for (int second = first; second <= last; second++) {
         EncJob J;
         J.kind = c.stream_kind == 1 ? 1 : 0;
@@ -1342,24 +1642,32 @@ extern "C" int orcgpu_writer_write(orcgpu_writer* w, const struct ArrowSchema* s
     int64_t fl;
     int rc = wr_read_schema(ctx, schema, fields, md, fl);
     bool same = rc == ORCGPU_OK && md == w->root_metadata && fields.size() == w->fields.size();
-    for (size_t i = 0; same && i < fields.size(); i++)
-      same = fields[i].format == w->fields[i].format && fields[i].name == w->fields[i].name && fields[i].metadata == w->fields[i].metadata &&
-             (fields[i].flags & 2) == (w->fields[i].flags & 2);
+    for (size_t i = 0; same && i < fields.size(); i++) same = fields[i].same(w->fields[i]);
     if (!same) {
       set_err(ctx, "writer: RecordBatch doesn't match expected schema");
       return ORCGPU_UNEXPECTED;
     }
   }
   const int64_t R = batch->length;
-  const size_t nc = w->cols.size();
-  if (R < 0 || batch->n_children != (int64_t)nc || (nc && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
+  const size_t nc = w->cols.size(), nr = w->root_kids.size();
+  if (R < 0 || batch->n_children != (int64_t)nr || (nr && !batch->children)) return ORCGPU_INVALID_ARGUMENT;
+  if (w->nested && (flags & ORCGPU_ENC_ON_DEVICE)) {
+    set_err(ctx, "writer: batches in device memory (ORCGPU_ENC_ON_DEVICE) are not taken by a writer whose schema has a Struct, List or Map column");
+    return ORCGPU_UNSUPPORTED;
+  }
   std::vector<int64_t> dev_ends(2 * nc, 0);
-  if (R > 0 && batch->n_children == (int64_t)nc && (nc == 0 || batch->children)) {
+  if (R > 0) {
     const bool on_device = flags & ORCGPU_ENC_ON_DEVICE;
     bool any_device_strings = false;
     for (size_t ci = 0; ci < nc; ci++) {
       const WrCol& c = w->cols[ci];
-      const ArrowArray* a = batch->children[ci];
+      if (c.parent >= 0) continue;  // (the columns below: checked as the write walks the tree, before anything changes)
+      const ArrowArray* a = batch->children[c.child];
+      if (c.is_nest()) {
+        if (a && a->offset >= 0 && batch->offset >= 0 && a->length >= batch->offset + R && a->n_buffers >= (c.stream_kind == 7 ? 1 : 2) && a->buffers) continue;
+        set_err(ctx, "writer: column %zu of the batch is not an Arrow array of its type", ci);
+        return ORCGPU_INVALID_ARGUMENT;
+      }
       if (!a || a->offset < 0 || batch->offset < 0 || a->length < batch->offset + R || a->n_buffers < (c.is_string ? 3 : 2) || !a->buffers ||
           !a->buffers[1] || (c.is_string && !a->buffers[2])) {
         set_err(ctx, "writer: column %zu of the batch is not an Arrow array of its type", ci);
@@ -1443,6 +1751,10 @@ extern "C" int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride) {
     set_err(w->ctx, "writer: the row index is set before the first write, flush_stripe or close");
     return ORCGPU_INVALID_ARGUMENT;
   }
+  if (stride && w->nested) {
+    set_err(w->ctx, "writer: no row index for a schema with a Struct, List or Map column (the row groups of their children are not written)");
+    return ORCGPU_UNSUPPORTED;
+  }
   w->stride = stride;
   return ORCGPU_OK;
 }
@@ -1482,6 +1794,8 @@ extern "C" int orcgpu_writer_stats(const orcgpu_writer* w, orcgpu_writer_counts*
   out->bytes = w->written;
   out->round_trips = w->round_trips;
   out->stripe_round_trips = w->stripe_round_trips;
+  out->nested_slices = w->nested_slices;
+  out->nested_gathers = w->nested_gathers;
   return ORCGPU_OK;
 }
 
@@ -1505,7 +1819,10 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
     c.b_vals2.release();
     c.b_data.release();
     c.b_tmp.release();
+    c.k_map.release();
+    c.b_gath.release();
   }
+  w->nest.release();
   w->slice_counts.release();
   w->est.release();
   w->trig.release();

@@ -13,7 +13,12 @@ writes without them, uncompressed and with Snappy; with --kernel-stats, the row 
 --types: the lineitem table with Decimal128(15,2) for its four money columns and Timestamp(ns) for l_shipdate, beside the stand-in
 table of floats and integers in the same run (host batches, 64 MiB stripes, best of 3) and their ratio; with --kernel-stats, the
 share of the Timestamp / Decimal128 kernels (wr_timestamp_kernel, wr_dec_*, wr_fill16_kernel) in the device time
-(profiles/writer_rate_types.json)."""
+(profiles/writer_rate_types.json).
+--nested: a table of list<float32> (16 a row), a struct of three lineitem columns and a map<string,int64> (2 entries a row),
+beside a flat table holding exactly the same leaf values (16 float columns, the three columns, two key and two value columns) in
+the same run: the yardstick.  Twice: without nulls (every child column is a slice of its array) and with 5 % null lists / structs /
+maps that keep their ranges (every child column is gathered through a row map).  GB/s of the leaf arrays' Arrow bytes; with
+--kernel-stats the share of the flattening kernels (nest_*) in the device time (profiles/writer_rate_nested.json)."""
 import argparse
 import csv
 import ctypes as C
@@ -270,6 +275,62 @@ def main_types(args):
     print(json.dumps(out))
 
 
+def nested_and_flat(n, rng, nulls):
+    """(nested batch, flat batch of the same leaf values, bytes of the leaf arrays)"""
+    li = lineitem(n, rng)
+    f = rng.random(n * 16).astype(np.float32)
+    keys = pa.array(np.array(["color", "size", "weight", "k"])[rng.integers(0, 4, 2 * n)])
+    vals = pa.array(rng.integers(0, 1 << 30, 2 * n).astype(np.int64))
+    three = [li.column("l_quantity"), li.column("l_linenumber"), li.column("l_returnflag")]
+
+    def validity():
+        return pa.py_buffer(np.packbits(rng.random(n) >= nulls, bitorder="little").tobytes()) if nulls else None
+    lst = pa.Array.from_buffers(pa.list_(pa.float32()), n, [validity(), pa.py_buffer((np.arange(n + 1, dtype=np.int32) * 16).tobytes())], children=[pa.array(f)])
+    st = pa.Array.from_buffers(pa.struct([("q", pa.float64()), ("n", pa.int32()), ("r", pa.string())]), n, [validity()], children=three)
+    mt = pa.map_(pa.string(), pa.int64())
+    entries = pa.StructArray.from_arrays([keys, vals], fields=[mt.key_field, mt.item_field])
+    mp = pa.Array.from_buffers(mt, n, [validity(), pa.py_buffer((np.arange(n + 1, dtype=np.int32) * 2).tobytes())], children=[entries])
+    nested = pa.RecordBatch.from_arrays([lst, st, mp], names=["emb", "item", "attrs"])
+    cols, names = [pa.array(np.ascontiguousarray(f.reshape(n, 16)[:, k])) for k in range(16)], ["f%d" % k for k in range(16)]
+    cols += three + [keys.take(pa.array(np.arange(k, 2 * n, 2))) for k in (0, 1)] + [vals.take(pa.array(np.arange(k, 2 * n, 2))) for k in (0, 1)]
+    names += ["q", "n", "r", "k0", "k1", "v0", "v1"]
+    flat = pa.RecordBatch.from_arrays(cols, names=names)
+    return nested, flat, f.nbytes + sum(c.nbytes for c in three) + keys.nbytes + vals.nbytes
+
+
+def main_nested(args):
+    per_batch = 1_000_000
+    ctx = capi.Context()
+    out = {"rows": per_batch * max(1, args.rows // per_batch), "unit": "GB/s of the leaf arrays' Arrow bytes (open .. close), host batches, 64 MiB stripes, best of 3",
+           "runs": {}, "nested_vs_flat": {}}
+    for label, nulls in [("no nulls (slices)", 0.0), ("5 % null parents (gathers)", 0.05)]:
+        rng = np.random.default_rng(1)
+        made = [nested_and_flat(per_batch, rng, nulls) for _ in range(max(1, args.rows // per_batch))]
+        leaf_bytes = sum(m[2] for m in made)
+        for name, batches in [("flat", [m[1] for m in made]), ("nested", [m[0] for m in made])]:
+            gpu_write(ctx, batches[:1], batches[0].schema, 64 << 20)  # warm-up
+            best = None
+            for _ in range(3):
+                r = gpu_write(ctx, batches, batches[0].schema, 64 << 20)
+                if best is None or r[0] < best[0]:
+                    best = r
+            dt, st, size = best
+            out["runs"]["%s, %s" % (name, label)] = {
+                "seconds": round(dt, 4), "leaf_bytes": leaf_bytes, "GB/s": round(leaf_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1),
+                "nested_slices": st["nested_slices"], "nested_gathers": st["nested_gathers"]}
+        out["nested_vs_flat"][label] = round(out["runs"]["nested, " + label]["GB/s"] / out["runs"]["flat, " + label]["GB/s"], 3)
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        ms = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows}
+        mine = {k: v for k, v in ms.items() if "nest_" in k}
+        out["kernels"] = {"what": "rocprofv3 --kernel-trace --stats of this command, all tables, all runs", "all_kernels_ms": round(total / 1e6, 3),
+                          "nested_kernels_ms": mine, "nested_kernels_share": round(sum(mine.values()) * 1e6 / total, 4),
+                          "largest_kernels_ms": dict(sorted(ms.items(), key=lambda kv: -kv[1])[:6])}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
@@ -277,7 +338,10 @@ def main():
     ap.add_argument("--kernel-stats")
     ap.add_argument("--row-index-stride", type=int, default=0)
     ap.add_argument("--types", action="store_true")
+    ap.add_argument("--nested", action="store_true")
     args = ap.parse_args()
+    if args.nested:
+        return main_nested(args)
     if args.types:
         return main_types(args)
     if args.row_index_stride:
