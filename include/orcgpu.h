@@ -375,6 +375,46 @@ int orcgpu_predicate_row_groups(const orcgpu_predicate_node* nodes, uint32_t n_n
  * whole.  The nodes (and their strings) are copied.  With a row selection as well, a row is read when both select it (the
  * reference's own combination, arrow_reader.rs:296-308, panics unless the row selection selects every row of the stripe). */
 int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes);
+/* ---- row filter: a predicate evaluated per ROW on the device, before the copy back ------------------------------------------
+ * with_predicate (above) prunes whole row groups, as the reference does; every row of a kept row group is still decoded, copied
+ * back and exported.  A row filter evaluates the predicate on every decoded row on the device and compacts the rows it keeps
+ * (device/filter_kernels.hip), so that only those cross the link.  The reference has no row-level evaluation; the semantics are
+ * fixed here:
+ *   - SQL three-valued logic; a row is kept only when the root is TRUE.
+ *   - A comparison is UNKNOWN when the row is null or the literal is None (value_is_null).  IS NULL / IS NOT NULL are never
+ *     UNKNOWN.  AND / OR are Kleene (an AND of no children is TRUE, an OR of none FALSE); NOT UNKNOWN = UNKNOWN.
+ *   - Byte / Short / Int / Long columns take any of the Int8 .. Int64 literals and compare as int64.  Date takes Int32 / Int64
+ *     literals, as days.  Float / Double take Float32 / Float64 literals and compare as double (a Float32 literal is rounded
+ *     through float first); IEEE rules: with a NaN on either side EQ / LT / LE / GT / GE are FALSE and NE is TRUE, -0.0 == 0.0.
+ *     Boolean takes Boolean, false < true.  String / Varchar / Char / Binary take Utf8 and compare the decoded value as exported
+ *     by unsigned byte, the shorter one being the smaller on a common prefix.  Any other pair: ORCGPU_MISMATCHED_SCHEMA.
+ *   - Timestamp and Decimal columns may be projected and tested with IS [NOT] NULL; a comparison on them is ORCGPU_UNSUPPORTED
+ *     (the message names the column).  A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
+ *   - A leaf naming a column that is not there, a leaf without a name, an unknown op, a node list that ends inside a node's
+ *     children or goes on behind the root, and a predicate nested deeper than ORCGPU_FILTER_MAX_DEPTH levels (a leaf alone is
+ *     one level): ORCGPU_INVALID_ARGUMENT.
+ * The nodes are those of orcgpu_reader_set_predicate (pre-order). */
+#define ORCGPU_FILTER_MAX_DEPTH 64
+/* The analogue of orcgpu_result_select for a filter: applies to a decoded result whose batches are uniform or already selected.
+ * Afterwards the result's batches are the kept rows of those batches, in order, packed into batches of at most batch_size rows
+ * (only the last may be shorter; no kept row: 0 batches); orcgpu_result_rows / _batches / _batch_view / _copy_batch / _fetch /
+ * _fetch_async / _export_batch speak of them, and a copy back moves the kept rows only.  column_names[i] names the result's
+ * column i for the leaves (n_columns = the result's columns).  *rows_kept (may be NULL) gets the kept row count.  A result whose
+ * orcgpu_result_status is not OK is left as it is, and that status is returned.  A batch of kept rows whose string bytes exceed
+ * INT32_MAX fails like a decoded one (ORCGPU_OFFSET_OVERFLOW in orcgpu_result_status).  One host wait per call. */
+int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                         const char* const* column_names, uint32_t n_columns, uint64_t* rows_kept);
+/* A builder setter (before the first next_batch; the nodes and their strings are copied): every stripe's result is filtered
+ * after decoding -- and after the row selection if there is one: a row is returned when the selection selects it and the filter
+ * keeps it --, before its copy back is started, with and without read-ahead.  The leaves name projected root columns.  Stripes
+ * are not merged: a stripe's kept rows come in batches of batch_size rows, its last one shorter; a stripe without kept rows
+ * yields no batch.  By itself the filter prunes no row groups: set the same predicate with orcgpu_reader_set_predicate for that
+ * (under a row filter the row groups read of a stripe are ONE run, from the first to the last group wanted, so that a stripe's
+ * kept rows stay together).  Errors are loud: what orcgpu_result_filter refuses, the first orcgpu_reader_next_batch returns,
+ * and the iterator ends. */
+int orcgpu_reader_set_row_filter(orcgpu_reader* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes);
+/* Rows the row filter has seen (decoded rows, those of the row selection when there is one) and kept so far. */
+int orcgpu_reader_filter_rows(const orcgpu_reader* r, uint64_t* rows_seen, uint64_t* rows_kept);
 /* Read-ahead: how many decoded stripes the reader may be ahead of the caller (default 2 -- every result set in flight costs a pinned host copy of a stripe --, at most 8; 0 = none: every stripe is
  * read, staged, decoded and copied back inside the orcgpu_reader_next_batch call that needs it).  With read-ahead two threads
  * of the reader work beside the caller: one reads and stages the stripes to come, one decodes the stripes staged so far

@@ -84,6 +84,17 @@ class ArrowReaderBuilder:
         self._ctx._check(self._ctx.L.orcgpu_reader_set_predicate(self._h, nodes, len(nodes)))
         return self
 
+    def with_row_filter(self, predicate, prune=True):
+        """A orc_rust_amd.predicate.Predicate evaluated on every decoded row on the GPU (orcgpu_reader_set_row_filter): only the
+        rows it keeps -- SQL three-valued logic, the root must be TRUE -- are copied back and handed out, a stripe's kept rows
+        packed into batches of batch_size rows.  prune=True also gives the predicate to with_predicate, so that row groups the
+        statistics rule out are not read at all."""
+        nodes, keep = predicate.flatten()
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_row_filter(self._h, nodes, len(nodes)))
+        if prune:
+            self._ctx._check(self._ctx.L.orcgpu_reader_set_predicate(self._h, nodes, len(nodes)))
+        return self
+
     def with_row_group_pruning(self, on):
         """Under a row selection, read only the row groups that hold selected rows (orcgpu_reader_set_row_group_pruning;
         default on).  The batches are the same either way."""
@@ -123,6 +134,12 @@ class ArrowReader:
         """(row groups read so far, row groups of the stripes gone through so far): orcgpu_reader_row_groups."""
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._ctx._check(self._ctx.L.orcgpu_reader_row_groups(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def filter_rows(self):
+        """(rows the row filter has seen so far, rows it has kept): orcgpu_reader_filter_rows."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._ctx._check(self._ctx.L.orcgpu_reader_filter_rows(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def column_names(self):

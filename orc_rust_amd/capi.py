@@ -25,6 +25,7 @@ EXPORTS = [
     "orcgpu_reader_set_projection", "orcgpu_reader_set_projection_roots", "orcgpu_reader_set_schema", "orcgpu_reader_set_byte_range", "orcgpu_reader_set_shard", "orcgpu_shard_columns", "orcgpu_reader_column_weight", "orcgpu_reader_set_timestamp_precision", "orcgpu_reader_set_row_selection", "orcgpu_reader_set_prefetch",
     "orcgpu_reader_set_row_group_pruning", "orcgpu_reader_row_groups", "orcgpu_index_entry", "orcgpu_reader_set_predicate",
     "orcgpu_predicate_row_groups",
+    "orcgpu_result_filter", "orcgpu_reader_set_row_filter", "orcgpu_reader_filter_rows",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
@@ -192,6 +193,10 @@ def load():
     L.orcgpu_reader_set_predicate.argtypes = [C.c_void_p, C.POINTER(PredicateNode), C.c_uint32]
     L.orcgpu_predicate_row_groups.argtypes = [C.POINTER(PredicateNode), C.c_uint32, C.POINTER(ColumnIndex), C.c_uint32, C.c_uint64, C.c_uint64,
                                               C.c_void_p, C.POINTER(C.c_uint32)]
+    L.orcgpu_result_filter.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                       C.POINTER(C.c_uint64)]
+    L.orcgpu_reader_set_row_filter.argtypes = [C.c_void_p, C.POINTER(PredicateNode), C.c_uint32]
+    L.orcgpu_reader_filter_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.orcgpu_reader_set_row_group_pruning.argtypes = [C.c_void_p, C.c_int]
     L.orcgpu_reader_row_groups.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.orcgpu_index_entry.argtypes = [C.POINTER(Column), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.c_int32, C.POINTER(StreamEntry)]
@@ -392,6 +397,15 @@ class Context:
         self._check(self.L.orcgpu_decode_staged(self.h, sarr, n, rarr))
         # (results[i] given: its buffers were decoded into again; None: a new result)
         return [results[i] if results and results[i] is not None else Result(self, rarr[i]) for i in range(n)]
+
+    def result_filter(self, result, predicate, column_names):
+        """orcgpu_result_filter: keeps the rows of a decoded (or selected) Result that satisfy `predicate` (a
+        orc_rust_amd.predicate.Predicate); column_names[i] names the result's column i.  Returns the kept row count."""
+        nodes, keep = predicate.flatten()
+        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
+        kept = C.c_uint64(0)
+        self._check(self.L.orcgpu_result_filter(self.h, result.h, nodes, len(nodes), names, len(column_names), C.byref(kept)))
+        return kept.value
 
     def timing(self):
         a, b, c = C.c_float(), C.c_float(), C.c_uint32()

@@ -42,6 +42,7 @@
 #include "device/string_kernels.hip"
 #include "device/decompress_kernels.hip"
 #include "device/select_kernels.hip"
+#include "device/filter_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -462,6 +463,8 @@ struct HostMirror {
   size_t arena_cap[kMaxLanes] = {0, 0, 0, 0}, chars_cap[kMaxLanes] = {0, 0, 0, 0};
   uint8_t* sel = nullptr;  // per-batch buffers of a row selection
   size_t sel_cap = 0;
+  uint8_t* filt = nullptr;  // the kept rows of a row filter (then the only buffer copied)
+  size_t filt_cap = 0;
   hipEvent_t done = nullptr;  // recorded behind the copies of orcgpu_result_fetch_async
   bool pending = false;       // ... and not waited for yet
   void wait() {
@@ -473,6 +476,7 @@ struct HostMirror {
       wait();
       if (done) (void)hipEventDestroy(done);
       PinnedPool::get().give(sel, sel_cap);
+      PinnedPool::get().give(filt, filt_cap);
       for (int l = 0; l < kMaxLanes; l++) {
         PinnedPool::get().give(arena[l], arena_cap[l]);
         PinnedPool::get().give(chars[l], chars_cap[l]);
@@ -499,6 +503,11 @@ struct orcgpu_result {
   uint32_t full_batches = 0;     // batches of the underlying uniform decode
   int full_status = 0;           // status of the underlying decode (before the selection re-mapped the failing batch)
   uint32_t full_err_batch = 0, full_err_col = 0;
+  // row filter: once orcgpu_result_filter has run, the batches are the kept rows, laid out like a decode's uniform batches in
+  // an arena of their own (the columns' offsets then count from filt_arena, and only that arena is copied back)
+  bool filtered = false;
+  DevBuf filt_arena, filt_tmp;  // the kept rows; the filter's tables, keep mask and row list
+  size_t filt_used = 0;
   std::vector<ColumnOut> cols;
   std::vector<std::string> field_names;  // per column: the name of a Struct's field (set by the file reader; empty: "f<position>")
   // Elements of the List / Map columns: one result each over a "stripe" whose rows are the column's elements (all of the
@@ -1235,6 +1244,7 @@ struct SummaryLayout {
 #include "orcgpu_decode.inc"
 #include "orcgpu_export.inc"
 #include "orcgpu_select.inc"
+#include "orcgpu_filter.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"

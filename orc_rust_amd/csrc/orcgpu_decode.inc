@@ -1169,6 +1169,8 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     r->mirror_valid = false;
     r->selected = false;
     r->sel.clear();
+    r->filtered = false;
+    r->filt_used = 0;
     for (int l = 0; l < kMaxLanes; l++) r->arena_used[l] = r->chars_used[l] = 0;
   }
   // ---- lanes: whole columns, balanced by their staged bytes (longest first); a column that alone is a quarter of the

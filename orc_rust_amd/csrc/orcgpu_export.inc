@@ -110,12 +110,16 @@ int orcgpu_result_fetch_async(orcgpu_ctx* ctx, orcgpu_result* r) {
     HIP_TRY(ctx, hipMemcpyAsync(host, dev.p, used, hipMemcpyDeviceToHost, ctx->d2h_stream));
     return ORCGPU_OK;
   };
-  for (int l = 0; l < kMaxLanes; l++) {
+  if (r->filtered) {  // a row filter's kept rows live in an arena of their own: nothing else crosses the link
+    int rc = pull(m->filt, m->filt_cap, r->filt_arena, r->filt_used);
+    if (rc) return rc;
+  }
+  for (int l = 0; l < kMaxLanes && !r->filtered; l++) {
     int rc = pull(m->arena[l], m->arena_cap[l], r->arena[l], r->arena_used[l]);
     if (!rc) rc = pull(m->chars[l], m->chars_cap[l], r->chars[l], r->chars_used[l]);
     if (rc) return rc;
   }
-  {
+  if (!r->filtered) {
     int rc = pull(m->sel, m->sel_cap, r->sel_arena, r->selected ? r->sel_used : 0);
     if (rc) return rc;
   }
@@ -155,6 +159,8 @@ void orcgpu_result_free(orcgpu_result* r) {
   for (auto& a : r->arena) a.release();
   for (auto& a : r->chars) a.release();
   r->sel_arena.release();
+  r->filt_arena.release();
+  r->filt_tmp.release();
   delete r;
 }
 
@@ -175,7 +181,7 @@ int orcgpu_result_batch_view(const orcgpu_result* r, uint32_t b, uint32_t c, orc
   uint64_t rows = batch_rows(r, b);
   out->length = rows;
   out->null_count = r->selected ? 0 : co.null_counts[b];
-  const uint8_t* A = r->arena[co.lane].p;
+  const uint8_t* A = r->filtered ? r->filt_arena.p : r->arena[co.lane].p;  // (a filtered result: uniform batches of the kept rows)
   if (r->selected) {
     // a selected batch: rows [start, start + len) of the stripe.  Fixed-width values and string bytes are used in place
     // (contiguous in the stripe-wide buffers); validity, Boolean bits and offsets were rebuilt by orcgpu_result_select
@@ -267,6 +273,10 @@ static int export_batch_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, uint32_
       if (A.p && d >= A.p && d < A.p + A.cap) return qm->arena[co.lane] + (d - A.p);
       if (C.p && d >= C.p && d < C.p + C.cap) return qm->chars[co.lane] + (d - C.p);
       const DevBuf& X = q->sel_arena;
+      if (q->filtered) {
+        const DevBuf& F = q->filt_arena;
+        return F.p && d >= F.p && d < F.p + F.cap ? qm->filt + (d - F.p) : nullptr;
+      }
       if (X.p && d >= X.p && d < X.p + X.cap) return qm->sel + (d - X.p);
       return nullptr;
     };

@@ -248,6 +248,7 @@ struct PredNode {
   int op = 0;
   uint32_t n_children = 0;
   std::string column;
+  bool has_column = false;  // (the row filter tells a leaf without a name from one with an empty name)
   int value_type = 0;
   bool value_is_null = false;
   int64_t i = 0;
@@ -431,6 +432,7 @@ std::vector<PredNode> copy_predicate(const orcgpu_predicate_node* nodes, uint32_
     out[k].op = nodes[k].op;
     out[k].n_children = nodes[k].n_children;
     if (nodes[k].column) out[k].column = nodes[k].column;
+    out[k].has_column = nodes[k].column != nullptr;
     out[k].value_type = nodes[k].value_type;
     out[k].value_is_null = nodes[k].value_is_null != 0;
     out[k].i = nodes[k].i;

@@ -314,6 +314,11 @@ struct orcgpu_reader {
   bool prune = true;
   std::atomic<uint64_t> groups_read{0}, groups_total{0};
   std::deque<orcgpu_result*> serial_q;        // prefetch = 0: pieces of the current stripe decoded and not handed out yet
+  // ---- row filter (orcgpu_reader_set_row_filter): the nodes as given, and -- from the first next_batch on -- their program ----
+  bool has_filter = false, filter_ready = false, filter_failed = false;
+  std::vector<orcgpu_host::PredNode> filter_nodes;
+  orcgpu_host::FilterPlan filter_plan;
+  std::atomic<uint64_t> filter_seen{0}, filter_kept{0};
 };
 
 static int arrow_code_of_format(const char* f, uint32_t* prec, uint32_t* scale);
@@ -683,6 +688,9 @@ int reader_stage_next(orcgpu_reader* rd, std::vector<orcgpu_staged*>& out) {
           if (!ranges.empty() && ranges.back().second == g) ranges.back().second = g + 1;
           else ranges.push_back({g, g + 1});
         }
+      // (a row filter packs a stripe's kept rows into batches: the stripe stays ONE result -- one run of row groups, from the
+      // first to the last one wanted; the selection's batches skip what lies between)
+      if (rd->has_filter && ranges.size() > 1) ranges = {{ranges.front().first, ranges.back().second}};
       std::vector<std::vector<StreamPiece>> pieces(ranges.size());
       bool usable = !(ranges.size() == 1 && ranges[0].first == 0 && ranges[0].second == n_groups);
       for (size_t k = 0; k < ranges.size() && usable; k++) usable = row_group_pieces(rd, sf, n_groups, ranges[k].first, ranges[k].second, pieces[k]);
@@ -759,6 +767,47 @@ void reader_read_metadata_ahead(orcgpu_reader* rd) {
   rd->footers_read = true;
 }
 
+// The row filter on one decoded (and selected) stripe.  A stripe whose decode failed is left as it is: its error arrives with
+// its failing batch.
+int reader_filter_result(orcgpu_reader* rd, orcgpu_result* res) {
+  if (res->status) return ORCGPU_OK;
+  uint64_t seen = 0, kept = 0;
+  const int rc = result_filter_plan(rd->ctx, res, rd->filter_plan, &seen, &kept);
+  rd->filter_seen += seen;
+  rd->filter_kept += kept;
+  return rc;
+}
+
+// The filter's nodes against the projected root columns -> its program, once, at the first next_batch
+int reader_compile_filter(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<int32_t> kinds;
+  for (size_t k = 0, root = 0; k < rd->col_ids.size(); k++) {
+    // (a column below a Struct / List / Map / Union: its root is refused by its kind)
+    if (rd->col_parent[k]) continue;
+    names.push_back(rd->col_names[root++].c_str());
+    kinds.push_back(rd->md.types[rd->col_ids[k]].kind);
+  }
+  std::vector<orcgpu_predicate_node> nodes(rd->filter_nodes.size());
+  for (size_t k = 0; k < nodes.size(); k++) {
+    const PredNode& p = rd->filter_nodes[k];
+    orcgpu_predicate_node& n = nodes[k];
+    memset(&n, 0, sizeof(n));
+    n.op = p.op;
+    n.n_children = p.n_children;
+    n.column = p.has_column ? p.column.c_str() : nullptr;
+    n.value_type = p.value_type;
+    n.value_is_null = p.value_is_null ? 1 : 0;
+    n.i = p.i;
+    n.f = p.f;
+    n.s = p.s.data();
+    n.s_len = p.s.size();
+  }
+  const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan);
+  if (rc) set_err(rd->ctx, "%s", rd->filter_plan.err);
+  return rc;
+}
+
 // prefetch = 0: both steps in the caller's thread (the pieces of a stripe in one decode call).  ORCGPU_END_OF_FILE = the file has no more rows to give
 int reader_advance_stripe(orcgpu_reader* rd) {
   orcgpu_ctx* ctx = rd->ctx;
@@ -791,6 +840,7 @@ int reader_advance_stripe(orcgpu_reader* rd) {
     for (size_t k = 0; k < got.size(); k++) {
       if (!rc) res[k]->field_names = rd->col_field;
       if (!rc && got[k]->has_sel) rc = result_select_batches(ctx, res[k], got[k]->sel);  // (the stripe's share of the selection)
+      if (!rc && rd->has_filter) rc = reader_filter_result(rd, res[k]);
       orcgpu_staged_free(got[k]);
     }
     if (host_prof)
@@ -899,6 +949,7 @@ void reader_decoder(orcgpu_reader* rd) {
     for (size_t k = 0; k < group.size(); k++) {
       if (!rc) results[k]->field_names = rd->col_field;
       if (!rc && group[k]->has_sel) rc = result_select_batches(ctx, results[k], group[k]->sel);  // (the stripe's share of the selection)
+      if (!rc && rd->has_filter) rc = reader_filter_result(rd, results[k]);  // (before the copy back is started: only the kept rows cross the link)
       orcgpu_staged_free(group[k]);
       if (!rc) rc = orcgpu_result_fetch_async(ctx, results[k]);
     }
@@ -994,6 +1045,18 @@ int orcgpu_reader_set_predicate(orcgpu_reader* rd, const orcgpu_predicate_node* 
   if (!rd || rd->built || !nodes || !n_nodes) return ORCGPU_INVALID_ARGUMENT;
   rd->predicate = orcgpu_host::copy_predicate(nodes, n_nodes);
   rd->has_predicate = true;
+  return ORCGPU_OK;
+}
+int orcgpu_reader_set_row_filter(orcgpu_reader* rd, const orcgpu_predicate_node* nodes, uint32_t n_nodes) {
+  if (!rd || rd->built || !nodes || !n_nodes) return ORCGPU_INVALID_ARGUMENT;
+  rd->filter_nodes = orcgpu_host::copy_predicate(nodes, n_nodes);
+  rd->has_filter = true;
+  return ORCGPU_OK;
+}
+int orcgpu_reader_filter_rows(const orcgpu_reader* rd, uint64_t* rows_seen, uint64_t* rows_kept) {
+  if (!rd) return ORCGPU_INVALID_ARGUMENT;
+  if (rows_seen) *rows_seen = rd->filter_seen.load();
+  if (rows_kept) *rows_kept = rd->filter_kept.load();
   return ORCGPU_OK;
 }
 int orcgpu_reader_set_row_group_pruning(orcgpu_reader* rd, int on) {
@@ -1159,6 +1222,16 @@ int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, st
   if (!rd || !out_array || !out_schema) return ORCGPU_INVALID_ARGUMENT;
   int rc = orcgpu_host::reader_build(rd);
   if (rc) return rc;
+  if (rd->filter_failed) return ORCGPU_END_OF_FILE;  // (the filter was refused by the call before: the iterator has ended)
+  if (rd->has_filter && !rd->filter_ready) {
+    rc = orcgpu_host::reader_compile_filter(rd);
+    if (rc) {
+      rd->filter_failed = true;
+      rd->next_stripe = rd->stripe_order.size();
+      return rc;
+    }
+    rd->filter_ready = true;
+  }
   for (;;) {
     if (rd->current) {
       uint32_t eb = 0, ec = 0;
