@@ -556,6 +556,28 @@ int orcgpu_compress_stream(orcgpu_ctx* ctx, int kind, uint64_t block_size, const
  * an index (index bytes do not count toward the stripe cut), and a stripe still costs two host waits. */
 int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride);
 
+/* ---- String dictionaries of the writer ---------------------------------------------------------------------------------------
+ * set_dictionary: key_size_threshold 0.0 = none (the default: every file, stream and count is what it is without the call); a
+ * value in (0, 1] turns dictionaries on; NaN, a negative value or one above 1: ORCGPU_INVALID_ARGUMENT.  Legal only before the
+ * first write, flush_stripe or close, like set_compression.
+ * The rule, per stripe and per Utf8 / LargeUtf8 column (ORC STRING) at any depth of the column tree, each on its own: with n the
+ * column's non-null ORC rows in the stripe and d the distinct byte strings among them, the column is written DICTIONARY_V2 in
+ * that stripe iff n > 0 and (double)d <= key_size_threshold * (double)n (Apache ORC C++'s key ratio); else its streams and
+ * encoding are the direct ones, byte for byte.  Binary / LargeBinary columns stay DIRECT_V2: ORC has no dictionary for BINARY.
+ * A dictionary column's streams, in this order: DATA (kind 1) the n rows' ids, unsigned RLE v2 through the encoder and integer
+ * width of the direct LENGTH stream; LENGTH (2) the d entries' lengths, likewise; DICTIONARY_DATA (3) the entries' bytes back to
+ * back; PRESENT (0) under the unchanged rule.  ColumnEncoding: {DICTIONARY_V2, dictionary_size d}.  Entry k is the k-th distinct
+ * value in the stripe's row order (the dictionary is not sorted); ids start at 0 in every stripe.  The dictionary is built on
+ * the device at the flush: the file does not depend on how the device schedules the work.  The stripe cut stays the one over the
+ * direct encoders' estimates, so the file has the stripes and rows of the same writes without a threshold; statistics are
+ * unchanged; a row index entry of a dictionary column holds [PRESENT's positions,] then DATA's run-length positions, nothing
+ * for LENGTH or DICTIONARY_DATA.  A stripe with such columns costs one host wait more, whatever their number.
+ * dictionary_counts: the (string column, stripe) pairs written DICTIONARY_V2 and written DIRECT_V2 so far.
+ * ORCGPU_DICT_HASH_BITS=N (1 .. 32, read when a writer is opened) keeps N bits of the strings' hash, for tests of long probe
+ * sequences on small inputs; no byte of the output depends on it. */
+int orcgpu_writer_set_dictionary(orcgpu_writer* w, double key_size_threshold);
+int orcgpu_writer_dictionary_counts(const orcgpu_writer* w, uint64_t* dictionary, uint64_t* direct);
+
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) ---------------------- */
 /* Milliseconds the device spent in the last orcgpu_decode_staged call, whole call and the RLE
  * expansion kernels alone (the dominant kernel), measured with hipEvents on the ctx stream. */

@@ -4,6 +4,7 @@
     w = ArrowWriterBuilder("out.orc", schema).with_batch_size(1024).with_stripe_byte_size(64 << 20).try_build()
     w = ArrowWriterBuilder("out.orc", schema).with_compression("snappy").try_build()   # or "lz4"; compressed on the GPU
     w = ArrowWriterBuilder("out.orc", schema).with_row_index_stride(10000).try_build()  # row index + statistics, on the GPU
+    w = ArrowWriterBuilder("out.orc", schema).with_dictionary_key_size_threshold(0.8).try_build()  # string dictionaries, on the GPU
     w.write(batch)          # pyarrow.RecordBatch
     w.flush_stripe()
     w.close()
@@ -53,6 +54,7 @@ class ArrowWriterBuilder:
         self._batch_size, self._stripe_byte_size = DEFAULT_BATCH_SIZE, DEFAULT_STRIPE_BYTE_SIZE
         self._compression, self._block_size = 0, DEFAULT_COMPRESSION_BLOCK_SIZE
         self._row_index_stride = 0
+        self._dictionary_threshold = 0.0
 
     def with_batch_size(self, n):
         self._batch_size = int(n)
@@ -84,6 +86,18 @@ class ArrowWriterBuilder:
         self._row_index_stride = stride
         return self
 
+    def with_dictionary_key_size_threshold(self, t):
+        """0 (the default): every string column DIRECT_V2, the reference's file.  t in (0, 1]: per stripe, a Utf8 / LargeUtf8 column
+        whose distinct values are at most t times its non-null values is written DICTIONARY_V2, its dictionary built on the GPU
+        in first-occurrence order (Apache ORC's dictionary_key_size_threshold)."""
+        if isinstance(t, bool) or not isinstance(t, (int, float)):
+            raise ValueError("dictionary_key_size_threshold must be a number, not %r" % (t,))
+        t = float(t)
+        if t != t or t < 0.0 or t > 1.0:
+            raise ValueError("dictionary_key_size_threshold must be in 0 .. 1")
+        self._dictionary_threshold = t
+        return self
+
     def try_build(self):
         if self._batch_size <= 0 or self._batch_size >= 1 << 32:
             raise ValueError("batch_size must be in 1 .. 2^32 - 1")
@@ -110,6 +124,8 @@ class ArrowWriterBuilder:
                 ctx._check(ctx.L.orcgpu_writer_set_compression(out.value, self._compression, self._block_size))
             if self._row_index_stride:
                 ctx._check(ctx.L.orcgpu_writer_set_row_index(out.value, self._row_index_stride))
+            if self._dictionary_threshold:
+                ctx._check(ctx.L.orcgpu_writer_set_dictionary(out.value, self._dictionary_threshold))
         except Exception:
             w.free()
             raise
@@ -165,6 +181,12 @@ class ArrowWriter:
         c = capi.WriterCounts()
         self._check(self._ctx.L.orcgpu_writer_stats(self._h, C.byref(c)))
         return {k: getattr(c, k) for k, _ in capi.WriterCounts._fields_}
+
+    def dictionary_counts(self):
+        """(string column, stripe) pairs written so far: {"dictionary": DICTIONARY_V2, "direct": DIRECT_V2}"""
+        d, r = C.c_uint64(), C.c_uint64()
+        self._check(self._ctx.L.orcgpu_writer_dictionary_counts(self._h, C.byref(d), C.byref(r)))
+        return {"dictionary": d.value, "direct": r.value}
 
     def stripe_rows(self):
         n = self.stats()["stripes"]

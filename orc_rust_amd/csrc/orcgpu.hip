@@ -46,6 +46,7 @@
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
+#include "device/writer_dict.hip"
 #include "device/writer_nested.hip"
 #include "device/col_stats.hip"
 

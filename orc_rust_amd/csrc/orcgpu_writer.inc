@@ -132,8 +132,13 @@ struct WrCol {
   DevBuf b_bits, b_pres, b_vals, b_vals2, b_data, b_tmp;
   // nested: a Struct's / List's children's rows as a map (device/writer_nested.hip); a leaf's arrays gathered through its parent's
   DevBuf k_map, b_gath;
+  // dictionary (orcgpu_writer_set_dictionary): the stripe being flushed -- whether the column is written DICTIONARY_V2, its
+  // entries and their bytes, and the tables of device/writer_dict.hip (ids, entry lengths and bytes at these offsets of b_dict)
+  bool dict = false;
+  uint64_t dict_size = 0, dict_bytes = 0, o_dict_ids = 0, o_dict_len = 0, o_dict_data = 0;
+  DevBuf b_dict;
   bool is_nest() const { return stream_kind >= 7; }
-  int value_streams() const { return stream_kind == 7 ? 0 : (stream_kind == 8 || stream_kind < 4 ? 1 : 2); }
+  int value_streams() const { return stream_kind == 7 ? 0 : (stream_kind == 8 || stream_kind < 4 ? 1 : (dict ? 3 : 2)); }
   bool has_bytes() const { return stream_kind == 4 || stream_kind == 6; }  // n_bytes / data count toward the estimate
   int elem2() const { return stream_kind == 5 ? 8 : 2; }
 };
@@ -192,6 +197,12 @@ struct orcgpu_writer {
   uint8_t* ix_pinned = nullptr;
   size_t ix_pinned_cap = 0;
   std::vector<std::vector<WrStat>> stripe_stats;  // [stripe][column], column 0 the root
+  // dictionary (orcgpu_writer_set_dictionary): the key size threshold (0: every string column DIRECT_V2), the bits of the hash
+  // that are used (ORCGPU_DICT_HASH_BITS), what a stripe's columns bring back, and the (string column, stripe) pairs so far
+  double dict_threshold = 0.0;
+  uint32_t dict_hash_mask = 0xffffffffu;
+  DevBuf dict_res;
+  uint64_t n_dictionary = 0, n_direct = 0;
 };
 
 namespace {
@@ -373,6 +384,12 @@ int wr_prepare(orcgpu_ctx* ctx, const ArrowSchema* schema, const orcgpu_writer_o
   }
   if (opts && opts->batch_size) w->batch_size = opts->batch_size;
   if (opts && opts->stripe_byte_size) w->stripe_byte_size = opts->stripe_byte_size;
+  // ORCGPU_DICT_HASH_BITS=N (1 .. 32): the bits of a string's hash the dictionary tables use -- few bits make long probe
+  // sequences of small inputs; the file's bytes do not depend on it
+  if (const char* e = getenv("ORCGPU_DICT_HASH_BITS")) {
+    const int bits = atoi(e);
+    if (bits >= 1 && bits <= 32) w->dict_hash_mask = bits == 32 ? 0xffffffffu : (1u << bits) - 1;
+  }
   return ORCGPU_OK;
 }
 
@@ -716,6 +733,89 @@ void wr_positions(const uint64_t* pos, uint64_t G, uint64_t g, bool comp, const 
   }
 }
 
+// Which string columns of the stripe being flushed are written DICTIONARY_V2 (orcgpu_writer_set_dictionary), and their
+// dictionaries.  Every such column's tables are enqueued (device/writer_dict.hip), then one wait, whatever the column count,
+// brings back each column's entries d and their bytes; a column goes DICTIONARY_V2 iff (double)d <= threshold * (double)n.
+int wr_dictionaries(orcgpu_writer* w) {
+  orcgpu_ctx* ctx = w->ctx;
+  hipStream_t st = ctx->stream;
+  std::vector<size_t> dc;
+  for (size_t ci = 0; ci < w->cols.size(); ci++) {
+    WrCol& c = w->cols[ci];
+    c.dict = false;
+    c.dict_size = c.dict_bytes = 0;
+    if (w->dict_threshold > 0 && c.orc_kind == 7 && c.n_valid) dc.push_back(ci);
+  }
+  if (dc.empty()) return ORCGPU_OK;
+  const uint64_t K = dc.size();
+  if (!wr_ensure(w, w->dict_res, (2 * K + 1) * 8 + kAlign)) return ORCGPU_HIP_ERROR;
+  uint64_t* d_res = (uint64_t*)w->dict_res.p;  // [column] entries, bytes; then `bad`
+  uint32_t* d_bad = (uint32_t*)(d_res + 2 * K);
+  WR_TRY(hipMemsetAsync(d_bad, 0, 8, st));
+  for (uint64_t k = 0; k < K; k++) {
+    WrCol& c = w->cols[dc[k]];
+    const uint64_t n = c.n_valid;
+    if (n >= 0x7fffffffull) {
+      set_err(ctx, "writer: %llu strings of column %zu in one stripe (fewer than 2^31 with a dictionary threshold)", (unsigned long long)n, dc[k]);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    uint64_t slots = 64;
+    while (slots < 2 * n) slots <<= 1;
+    Bump T;
+    const uint64_t o_len32 = T.take(n * 4), o_offs = T.take(n * 8), o_sums = T.take((n / 2048 + 2) * 8), o_tot = T.take(16), o_table = T.take(slots * 8),
+                   o_slot = T.take(n * 4), o_flag = T.take(n * 4), o_flen = T.take(n * 4), o_first = T.take(n * 8), o_foff = T.take(n * 8), o_d = T.take(16),
+                   o_D = T.take(16), o_erow = T.take(n * 4), o_eoff = T.take(n * 8);
+    c.o_dict_ids = T.take(n * (uint64_t)c.elem);
+    c.o_dict_len = T.take(n * (uint64_t)c.elem);
+    c.o_dict_data = T.take(align_up(c.n_bytes, 16) + 16);
+    if (!wr_ensure(w, c.b_dict, T.off + kAlign)) {
+      set_err(ctx, "writer: out of device memory (%llu bytes of dictionary tables)", (unsigned long long)T.off);
+      return ORCGPU_HIP_ERROR;
+    }
+    uint8_t* t = c.b_dict.p;
+    uint32_t *len32 = (uint32_t*)(t + o_len32), *rep = (uint32_t*)(t + o_table), *low = rep + slots, *slot_of = (uint32_t*)(t + o_slot),
+             *flag = (uint32_t*)(t + o_flag), *flen = (uint32_t*)(t + o_flen), *erow = (uint32_t*)(t + o_erow);
+    uint64_t *offs = (uint64_t*)(t + o_offs), *sums = (uint64_t*)(t + o_sums), *first = (uint64_t*)(t + o_first), *foff = (uint64_t*)(t + o_foff),
+             *tot_d = (uint64_t*)(t + o_d), *tot_D = (uint64_t*)(t + o_D), *eoff = (uint64_t*)(t + o_eoff);
+    WR_TRY(launch(wd_len32_kernel, n, false, 256, st, (const void*)c.vals.p, c.elem, n, len32));
+    int rc = enc_scan(ctx, st, len32, n, sums, (uint64_t*)(t + o_tot), offs);
+    if (rc) return rc;
+    WR_TRY(hipMemsetAsync(rep, 0xff, slots * 8, st));
+    WR_TRY(launch(wd_insert_kernel, n, false, 256, st, (const uint8_t*)c.data.p, (const uint64_t*)offs, (const uint32_t*)len32, (uint32_t)n, rep, low,
+                  (uint32_t)(slots - 1), w->dict_hash_mask, slot_of, d_bad));
+    WR_TRY(launch(wd_flag_kernel, n, false, 256, st, (const uint32_t*)slot_of, (const uint32_t*)low, (const uint32_t*)len32, (uint32_t)n, flag, flen));
+    rc = enc_scan(ctx, st, flag, n, sums, tot_d, first);
+    if (rc) return rc;
+    rc = enc_scan(ctx, st, flen, n, sums, tot_D, foff);
+    if (rc) return rc;
+    WR_TRY(launch(wd_ids_kernel, n, false, 256, st, (const uint32_t*)slot_of, (const uint32_t*)low, (const uint32_t*)flag, (const uint64_t*)first,
+                  (const uint64_t*)foff, (const uint32_t*)len32, (uint32_t)n, c.elem, (void*)(t + c.o_dict_ids), (void*)(t + c.o_dict_len), erow, eoff, d_bad));
+    WR_TRY(launch(wd_gather_kernel, (c.n_bytes + 15) / 16, false, 256, st, (const uint8_t*)c.data.p, (const uint64_t*)offs, (const uint32_t*)erow,
+                  (const uint64_t*)eoff, (const uint64_t*)tot_d, (const uint64_t*)tot_D, (uint4*)(t + c.o_dict_data)));
+    WR_TRY(hipMemcpyAsync(d_res + 2 * k, tot_d, 8, hipMemcpyDeviceToDevice, st));
+    WR_TRY(hipMemcpyAsync(d_res + 2 * k + 1, tot_D, 8, hipMemcpyDeviceToDevice, st));
+  }
+  std::vector<uint64_t> res(2 * K + 1, 0);
+  WR_TRY(hipMemcpyAsync(res.data(), d_res, (2 * K + 1) * 8, hipMemcpyDeviceToHost, st));
+  int rc = wr_sync(w);
+  if (rc) return rc;
+  if ((uint32_t)res[2 * K]) {
+    set_err(ctx, "writer: a string found no slot in its column's dictionary table");
+    return ORCGPU_UNEXPECTED;
+  }
+  for (uint64_t k = 0; k < K; k++) {
+    WrCol& c = w->cols[dc[k]];
+    const uint64_t d = res[2 * k];
+    if (d > c.n_valid || res[2 * k + 1] > c.n_bytes) return ORCGPU_UNEXPECTED;
+    if ((double)d <= w->dict_threshold * (double)c.n_valid) {
+      c.dict = true;
+      c.dict_size = d;
+      c.dict_bytes = res[2 * k + 1];
+    }
+  }
+  return ORCGPU_OK;
+}
+
 // StripeWriter::finish_stripe (writer/stripe.rs:109-165) + ArrowWriter::flush_stripe.  Every stream of every column is enqueued
 // without a host wait, each into a slot of its bound; then two waits, whatever the column count: the streams' lengths come back,
 // and the streams, moved back to back on the device, reach the host in one copy.
@@ -728,6 +828,8 @@ int wr_flush(orcgpu_writer* w) {
     uint64_t slot;
   };
   std::vector<St> streams;
+  int rc = wr_dictionaries(w);
+  if (rc) return rc;
   // room: the lengths, the bitmaps of the Boolean / PRESENT streams
   uint64_t n_streams = 0, bits_room = 0;
   for (auto& c : w->cols) {
@@ -739,7 +841,6 @@ int wr_flush(orcgpu_writer* w) {
   w->bits_at = 0;
   std::vector<uint64_t> known(n_streams, ~0ull);
   uint64_t at = 0;
-  int rc = ORCGPU_OK;
   // row index: the groups' statistics, enqueued ahead of the streams (jobs: column * G + group)
   const size_t nc = w->cols.size();
   const bool indexed = w->stride > 0;
@@ -822,7 +923,22 @@ int wr_flush(orcgpu_writer* w) {
     uint64_t li = streams.size();
     if (c.value_streams()) streams.push_back(St{c.stream_kind == 8 ? 2 : 1, column, at});
     WrIxPos ip;
-    switch (c.stream_kind) {
+    if (c.dict) {
+      // DICTIONARY_V2: DATA the rows' ids (positions as an integer column's), LENGTH the entries' lengths, DICTIONARY_DATA their
+      // bytes; the row index holds nothing for the last two
+      ip = ixp(1, ci, c.n_valid, li, 2);
+      rc = wr_rle_stream(w, 0, c.b_dict.p + c.o_dict_ids, c.n_valid, c.elem, 0, &at, li, &ip);
+      if (rc) return rc;
+      li = streams.size();
+      streams.push_back(St{2, column, at});
+      rc = wr_rle_stream(w, 0, c.b_dict.p + c.o_dict_len, c.dict_size, c.elem, 0, &at, li);
+      if (rc) return rc;
+      li = streams.size();
+      streams.push_back(St{3, column, at});
+      rc = wr_copy_stream(w, c.b_dict.p + c.o_dict_data, c.dict_bytes, &at, li, known);
+      if (rc) return rc;
+      if (NJ) WR_TRY(hipMemsetAsync(w->ix.p + o_pos + (li - 1) * G * 32, 0, 2 * G * 32, ctx->stream));
+    } else switch (c.stream_kind) {
       case 7: break;  // a Struct: PRESENT alone
       case 8: rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 0, &at, li); break;  // LENGTH
       case 0: ip = ixp(1, ci, c.n_valid, li, 2); rc = wr_rle_stream(w, 0, c.vals.p, c.n_valid, c.elem, 1, &at, li, &ip); break;
@@ -841,7 +957,7 @@ int wr_flush(orcgpu_writer* w) {
         break;
     }
     if (rc) return rc;
-    if (c.stream_kind == 4) {
+    if (c.stream_kind == 4 && !c.dict) {
       li = streams.size();
       streams.push_back(St{2, column, at});
       ip = ixp(1, ci, c.n_valid, li, 2);
@@ -974,7 +1090,8 @@ int wr_flush(orcgpu_writer* w) {
   }
   for (size_t ci = 0; ci <= w->cols.size(); ci++) {
     PbOut m;
-    m.u64(1, ci ? (uint64_t)w->cols[ci - 1].encoding : 0u);
+    m.u64(1, ci ? (w->cols[ci - 1].dict ? 3u : (uint64_t)w->cols[ci - 1].encoding) : 0u);
+    if (ci && w->cols[ci - 1].dict) m.u64(2, w->cols[ci - 1].dict_size);
     footer.msg(2, m);
   }
   for (auto& c : w->cols)
@@ -994,6 +1111,10 @@ int wr_flush(orcgpu_writer* w) {
   if (rc) return rc;
   w->stripes.push_back(WrStripe{start, total, footer.b.size(), w->rows, index_length});
   w->rows = 0;
+  for (auto& c : w->cols) {
+    if (c.orc_kind == 7) (c.dict ? w->n_dictionary : w->n_direct)++;
+    c.dict = false;
+  }
   for (auto& c : w->cols) c.rows = c.n_valid = c.n_bytes = 0;
   w->base_rle = 0;
   for (auto& c : w->cols) c.base_valid = 0;
@@ -1741,6 +1862,27 @@ extern "C" int orcgpu_writer_set_compression(orcgpu_writer* w, int kind, uint64_
   return ORCGPU_OK;
 }
 
+extern "C" int orcgpu_writer_set_dictionary(orcgpu_writer* w, double key_size_threshold) {
+  if (!w) return ORCGPU_INVALID_ARGUMENT;
+  if (!(key_size_threshold >= 0.0 && key_size_threshold <= 1.0)) {  // (NaN fails both)
+    set_err(w->ctx, "writer: the dictionary key size threshold is 0 (no dictionaries) or in (0, 1]");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (w->started || w->closed) {
+    set_err(w->ctx, "writer: the dictionary key size threshold is set before the first write, flush_stripe or close");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  w->dict_threshold = key_size_threshold;
+  return ORCGPU_OK;
+}
+
+extern "C" int orcgpu_writer_dictionary_counts(const orcgpu_writer* w, uint64_t* dictionary, uint64_t* direct) {
+  if (!w || !dictionary || !direct) return ORCGPU_INVALID_ARGUMENT;
+  *dictionary = w->n_dictionary;
+  *direct = w->n_direct;
+  return ORCGPU_OK;
+}
+
 extern "C" int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride) {
   if (!w) return ORCGPU_INVALID_ARGUMENT;
   if (stride > 0x7fffffffull) {
@@ -1821,6 +1963,7 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
     c.b_tmp.release();
     c.k_map.release();
     c.b_gath.release();
+    c.b_dict.release();
   }
   w->nest.release();
   w->slice_counts.release();
@@ -1832,6 +1975,7 @@ extern "C" void orcgpu_writer_free(orcgpu_writer* w) {
   w->slots.release();
   w->zout.release();
   w->ix.release();
+  w->dict_res.release();
   if (w->pinned) (void)hipHostFree(w->pinned);
   if (w->ix_pinned) (void)hipHostFree(w->ix_pinned);
   delete w;

@@ -18,7 +18,11 @@ share of the Timestamp / Decimal128 kernels (wr_timestamp_kernel, wr_dec_*, wr_f
 beside a flat table holding exactly the same leaf values (16 float columns, the three columns, two key and two value columns) in
 the same run: the yardstick.  Twice: without nulls (every child column is a slice of its array) and with 5 % null lists / structs /
 maps that keep their ranges (every child column is gathered through a row map).  GB/s of the leaf arrays' Arrow bytes; with
---kernel-stats the share of the flattening kernels (nest_*) in the device time (profiles/writer_rate_nested.json)."""
+--kernel-stats the share of the flattening kernels (nest_*) in the device time (profiles/writer_rate_nested.json).
+--dictionary T: the lineitem table written with ArrowWriterBuilder.with_dictionary_key_size_threshold(T) and, in the same run,
+with threshold 0 (the yardstick: the writer as it is without dictionaries), host batches, 64 MiB stripes, best of 3: rows per
+second, file sizes and their ratios; with --kernel-stats the share of the dictionary kernels (wd_*) in the device time
+(profiles/writer_rate_dict.json)."""
 import argparse
 import csv
 import ctypes as C
@@ -129,10 +133,11 @@ class DeviceBatch:
         self.ptrs = []
 
 
-def gpu_write(ctx, batches, schema, sbs, device=None, compression=None, stride=0):
+def gpu_write(ctx, batches, schema, sbs, device=None, compression=None, stride=0, dictionary=0.0):
     out = io.BytesIO()
     t0 = time.perf_counter()
-    w = ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).with_row_index_stride(stride).try_build()
+    w = (ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).with_row_index_stride(stride)
+         .with_dictionary_key_size_threshold(dictionary).try_build())
     if device is None:
         for b in batches:
             w.write(b)
@@ -331,6 +336,46 @@ def main_nested(args):
     print(json.dumps(out))
 
 
+def main_dictionary(args):
+    per_batch = 1_000_000
+    rng = np.random.default_rng(1)
+    batches = [lineitem(per_batch, rng) for _ in range(max(1, args.rows // per_batch))]
+    schema = batches[0].schema
+    n = per_batch * len(batches)
+    arrow_bytes = sum(b.nbytes for b in batches)
+    ctx = capi.Context()
+    out = {"rows": n, "columns": len(schema), "arrow_bytes": arrow_bytes, "threshold": args.dictionary,
+           "unit": "Mrows/s (open .. close), host batches, 64 MiB stripes, best of 3, both arms in one process", "runs": {}}
+    for t in (args.dictionary, 0.0):
+        gpu_write(ctx, batches[:1], schema, 64 << 20, dictionary=t)  # warm-up
+    times = {args.dictionary: [], 0.0: []}
+    kept = {}
+    for _ in range(3):  # (the arms take turns)
+        for t in (args.dictionary, 0.0):
+            dt, st, size = gpu_write(ctx, batches, schema, 64 << 20, dictionary=t)
+            times[t].append(dt)
+            kept[t] = (st, size)
+    for t, name in ((args.dictionary, "threshold %g" % args.dictionary), (0.0, "threshold 0 (the yardstick)")):
+        st, size = kept[t]
+        dt = min(times[t])
+        out["runs"][name] = {"seconds": round(dt, 4), "seconds_all": [round(x, 4) for x in times[t]], "Mrows/s": round(n / dt / 1e6, 2),
+                             "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                             "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    a, b = out["runs"]["threshold %g" % args.dictionary], out["runs"]["threshold 0 (the yardstick)"]
+    out["rate_vs_yardstick"] = round(a["Mrows/s"] / b["Mrows/s"], 3)
+    out["mark"] = 0.8
+    out["file_size_vs_yardstick"] = round(a["file_bytes"] / b["file_bytes"], 4)
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        ms = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows}
+        mine = {k: v for k, v in ms.items() if k.startswith("wd_")}
+        out["kernels"] = {"what": "rocprofv3 --kernel-trace --stats of this command, both arms, all runs", "all_kernels_ms": round(total / 1e6, 3),
+                          "dictionary_kernels_ms": mine, "dictionary_kernels_share": round(sum(mine.values()) * 1e6 / total, 4),
+                          "largest_kernels_ms": dict(sorted(ms.items(), key=lambda kv: -kv[1])[:6])}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
@@ -339,7 +384,10 @@ def main():
     ap.add_argument("--row-index-stride", type=int, default=0)
     ap.add_argument("--types", action="store_true")
     ap.add_argument("--nested", action="store_true")
+    ap.add_argument("--dictionary", type=float, default=0.0)
     args = ap.parse_args()
+    if args.dictionary:
+        return main_dictionary(args)
     if args.nested:
         return main_nested(args)
     if args.types:
