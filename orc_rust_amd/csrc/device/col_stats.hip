@@ -1,6 +1,6 @@
 // device/col_stats.hip -- the writer's row index (orcgpu_writer_set_row_index): the ColumnStatistics of every row group of every
 // column of a stripe, and where each group starts in each stream.  Everything works on the stripe's device-resident form
-// (orcgpu_writer.inc, WrCol): a presence byte per row, the valid values (Boolean: 0 / 1 bytes; strings: their lengths), the
+// (orcgpu_writer.inc, WrCol / WrColDev): a presence byte per row, the valid values (Boolean: 0 / 1 bytes; strings: their lengths), the
 // strings' bytes.  A job is one (column, row group): job j = column * G + group, G groups of `stride` rows in every column.
 //
 //   ix_count_kernel      valid values per job (a block per job, over the presence bytes)
@@ -12,14 +12,15 @@
 //   ix_pos_kernel        a lane per group of one stream: its entry position, by a binary search of the encoder's run table
 //   ix_map_kernel        compressed files: uncompressed offsets -> (chunk header in the compressed stream, bytes into the chunk)
 
-#define IX_STR_KEEP 1025u  // bytes of a string minimum / maximum the host receives (a bound is cut at 1024)
+#include "writer_kinds.h"  // WrKind, IX_STR_KEEP, IxRec
+
 #define IX_COLS_PER_ARG 16
 
 struct IxCol {
   const uint8_t* pres;  // a byte per row of the stripe
   const void* vals;     // the valid values in `elem` bytes each
   const uint8_t* data;  // strings' bytes (Timestamp: the nanosecond codes, vals the stored seconds)
-  int32_t kind;         // WrCol::stream_kind
+  int32_t kind;         // WrKind
   int32_t elem;
   int32_t minmax;       // strings: 1 with a minimum / maximum (Utf8), 0 without (Binary)
   int32_t pad;
@@ -28,28 +29,6 @@ struct IxColArgs {
   uint32_t at, n;
   IxCol c[IX_COLS_PER_ARG];
 };
-
-struct IxRec {  // one job's statistics, 128 bytes (the host reads them as they are)
-  uint64_t count, bytes, trues;
-  union {  // integers: the minimum; floats: the sum of the values of magnitude >= 2^960, scaled by 2^-64 (a double-double)
-    int64_t imin;
-    double dbig;
-  };
-  union {
-    int64_t imax;
-    double dbig_lo;
-  };
-  uint64_t sum_lo;
-  int64_t sum_hi;  // integer sum: sum_hi:sum_lo, two's complement
-  double dmin, dmax, dsum, dsum_lo;
-  uint64_t smin_at, smax_at;  // strings: offsets of the minimum / maximum in the column's bytes
-  uint64_t side;              // ... and of their copies in the side buffer (minimum, then maximum)
-  uint32_t smin_len, smax_len;
-  uint32_t has_null, has_nan;
-  // Timestamp: imin / imax the minimum's / maximum's second, sum_lo / sum_hi their nanoseconds.
-  // Decimal128: imin:imax the minimum (low, high word), smin_at:smax_at the maximum, sum_lo:sum_hi:trues the sum in 192 bits.
-};
-static_assert(sizeof(IxRec) == 128, "IxRec is read by the host as 128 bytes");
 
 __global__ __launch_bounds__(64) void ix_put_cols_kernel(IxColArgs a, IxCol* dst) {
   if (threadIdx.x < a.n) dst[a.at + threadIdx.x] = a.c[threadIdx.x];
@@ -113,13 +92,13 @@ extern "C" __global__ void __launch_bounds__(256) ix_bytes_kernel(const IxCol* c
   __shared__ uint64_t lds[256];
   const uint64_t j = blockIdx.x, c = j / G;
   const IxCol col = cols[c];
-  if (col.kind != 4 && col.kind != 6) {
+  if (col.kind != WR_STRING && col.kind != WR_DECIMAL) {
     if (threadIdx.x == 0) blen[j] = 0;
     return;
   }
   const uint64_t v0 = vscan[j] - vscan[c * G], n = cnt[j];
   uint64_t b = 0;
-  if (col.kind == 6) {  // Decimal128: the varints' bytes
+  if (col.kind == WR_DECIMAL) {  // Decimal128: the varints' bytes
     const uint64_t* q = (const uint64_t*)col.vals;
     for (uint64_t i = threadIdx.x; i < n; i += 256) b += wr_dec_varint_len(wr_dec_zigzag(q[2 * (v0 + i)], q[2 * (v0 + i) + 1]));
   } else {
@@ -191,7 +170,7 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
   IxRec R = {};
   R.count = n;
   R.has_null = n < r1 - r0;
-  if (col.kind == 0 || col.kind == 1) {  // integers: min, max, exact sum
+  if (col.kind == WR_INT || col.kind == WR_BYTE) {  // integers: min, max, exact sum
     int64_t mn = INT64_MAX, mx = INT64_MIN;
     __int128 sum = 0;
     for (uint64_t i = t; i < n; i += 256) {
@@ -227,7 +206,7 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     R.imax = (int64_t)l1[0];
     R.sum_lo = m0[0];
     R.sum_hi = (int64_t)m1[0];
-  } else if (col.kind == 2) {  // floats as f64: min / max (the first of equal values, as a sequential writer keeps it), NaN, sum
+  } else if (col.kind == WR_FLOAT) {  // floats as f64: min / max (the first of equal values, as a sequential writer keeps it), NaN, sum
     // The sum is two double-doubles: values below 2^960 in magnitude, and the others scaled by 2^-64 (exact for them).  Neither
     // can overflow for fewer than 2^63 values, so the sum does not depend on the order (the host adds them: wr_stat_msg); an
     // infinite input makes the second one infinite.
@@ -285,11 +264,11 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     R.dbig = b0[0];
     R.dbig_lo = b1[0];
     R.has_nan = n0[0];
-  } else if (col.kind == 3) {  // Boolean: trues
+  } else if (col.kind == WR_BOOL) {  // Boolean: trues
     uint64_t tr = 0;
     for (uint64_t i = t; i < n; i += 256) tr += ((const uint8_t*)col.vals)[v0 + i];
     R.trues = ix_block_sum(tr, l0);
-  } else if (col.kind == 5) {  // Timestamp: minimum and maximum by (second, nanosecond)
+  } else if (col.kind == WR_TIMESTAMP) {  // Timestamp: minimum and maximum by (second, nanosecond)
     int64_t s0 = INT64_MAX, s1 = INT64_MIN;
     uint32_t q0 = 0xffffffffu, q1 = 0;
     for (uint64_t i = t; i < n; i += 256) {
@@ -313,7 +292,7 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
     R.imax = (int64_t)l1[0];
     R.sum_lo = n0[0];
     R.sum_hi = n1[0];
-  } else if (col.kind == 6) {  // Decimal128: minimum, maximum, and the exact sum in 192 bits (fewer than 2^32 values below 2^127)
+  } else if (col.kind == WR_DECIMAL) {  // Decimal128: minimum, maximum, and the exact sum in 192 bits (fewer than 2^32 values below 2^127)
     const uint64_t* q = (const uint64_t*)col.vals;
     __int128 mn = 0, mx = 0;
     uint64_t s0 = 0, s1 = 0, s2 = 0;
@@ -409,14 +388,14 @@ extern "C" __global__ void __launch_bounds__(256) ix_stats_kernel(const IxCol* c
   }
   if (t == 0) {
     recs[j] = R;
-    side_len[j] = col.kind == 4 && col.minmax && n ? min(R.smin_len, IX_STR_KEEP) + min(R.smax_len, IX_STR_KEEP) : 0;
+    side_len[j] = col.kind == WR_STRING && col.minmax && n ? min(R.smin_len, IX_STR_KEEP) + min(R.smax_len, IX_STR_KEEP) : 0;
   }
 }
 
 extern "C" __global__ void __launch_bounds__(256) ix_side_kernel(const IxCol* cols, uint64_t G, const uint64_t* side_off, IxRec* recs, uint8_t* side) {
   const uint64_t j = blockIdx.x, c = j / G;
   const IxCol col = cols[c];
-  if (col.kind != 4 || !col.minmax) return;
+  if (col.kind != WR_STRING || !col.minmax) return;
   const IxRec& R = recs[j];
   if (!R.count) return;
   const uint64_t o = side_off[j];

@@ -50,35 +50,7 @@
 #include "device/writer_nested.hip"
 #include "device/col_stats.hip"
 
-// Arrow C Data Interface structs (public, stable ABI)
-extern "C" {
-#ifndef ARROW_C_DATA_INTERFACE
-#define ARROW_C_DATA_INTERFACE
-struct ArrowSchema {
-  const char* format;
-  const char* name;
-  const char* metadata;
-  int64_t flags;
-  int64_t n_children;
-  struct ArrowSchema** children;
-  struct ArrowSchema* dictionary;
-  void (*release)(struct ArrowSchema*);
-  void* private_data;
-};
-struct ArrowArray {
-  int64_t length;
-  int64_t null_count;
-  int64_t offset;
-  int64_t n_buffers;
-  int64_t n_children;
-  const void** buffers;
-  struct ArrowArray** children;
-  struct ArrowArray* dictionary;
-  void (*release)(struct ArrowArray*);
-  void* private_data;
-};
-#endif
-}
+#include "arrow_c_data.h"
 
 namespace {
 
@@ -1249,4 +1221,7 @@ struct SummaryLayout {
 #include "orcgpu_reader.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"
+#include "orcgpu_writer_host.inc"
 #include "orcgpu_writer.inc"
+#include "orcgpu_writer_flush.inc"
+#include "orcgpu_writer_write.inc"

@@ -80,21 +80,6 @@ int lzc_enqueue(orcgpu_ctx* ctx, int codec, uint64_t B, const uint8_t* d_in, uin
   return ORCGPU_OK;
 }
 
-// ORC framing of bytes stored as they are: original chunks of at most B bytes (the writer's stripe footers and file footer)
-std::vector<uint8_t> lzc_original_chunks(const std::vector<uint8_t>& b, uint64_t B) {
-  std::vector<uint8_t> out;
-  out.reserve(lzc_room(b.size(), B));
-  for (uint64_t at = 0; at < b.size(); at += B) {
-    const uint64_t len = std::min<uint64_t>(B, b.size() - at);
-    const uint64_t h = len * 2 + 1;
-    out.push_back((uint8_t)h);
-    out.push_back((uint8_t)(h >> 8));
-    out.push_back((uint8_t)(h >> 16));
-    out.insert(out.end(), b.begin() + at, b.begin() + at + len);
-  }
-  return out;
-}
-
 }  // namespace
 
 extern "C" int orcgpu_compress_stream(orcgpu_ctx* ctx, int kind, uint64_t block_size, const void* in, uint64_t n, uint32_t flags, uint8_t* out, uint64_t out_cap,

@@ -1,5 +1,5 @@
 """Columns whose statistics sit on the edges the row index kernel (device/col_stats.hip, ix_stats_kernel) and the host merges
-(orcgpu_writer.inc: wr_stat_merge) decide, shared by the CPU checks (tests/test_writer_stats_reference.py) and the GPU tests
+(orcgpu_writer_host.inc: wr_stat_merge) decide, shared by the CPU checks (tests/test_writer_stats_reference.py) and the GPU tests
 (tests/test_gpu_writer_stats.py).
 
 The kernel gives valid value i of a (column, group) job to thread i mod 256 and then merges threads t and t + d for d = 128, 64,

@@ -1,4 +1,4 @@
-"""Row index statistics at the edges the GPU decides (device/col_stats.hip: ix_stats_kernel; orcgpu_writer.inc: wr_stat_merge,
+"""Row index statistics at the edges the GPU decides (device/col_stats.hip: ix_stats_kernel; orcgpu_writer_host.inc: wr_stat_merge,
 wr_float_sum): every group's, stripe's and the file's statistics against tests/index_model.py, whose float sums are the exact sum
 rounded to nearest, held to FloatSum.tol.  The columns are tests/stats_cases.py's, each placed in one thread, in threads merged
 last and first in the tree, in threads whose first value sits in the higher thread, in two groups and in two stripes, with and
