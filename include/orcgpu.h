@@ -578,6 +578,25 @@ int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride);
 int orcgpu_writer_set_dictionary(orcgpu_writer* w, double key_size_threshold);
 int orcgpu_writer_dictionary_counts(const orcgpu_writer* w, uint64_t* dictionary, uint64_t* direct);
 
+/* ---- Bloom filters of the writer ---------------------------------------------------------------------------------------------
+ * set_bloom_filter: a BLOOM_FILTER_UTF8 stream (kind 8) for each of the n_columns named top-level fields, directly behind the
+ * column's ROW_INDEX in the stripe's index region: a BloomFilterIndex with one BloomFilter {numHashFunctions, utf8bitset} per row
+ * group, bit for bit what Apache ORC's writer builds, so that an equality predicate prunes row groups min / max cannot.
+ * n_columns 0 = none (the default: the file is what it is without the call).  Legal only before the first write, flush_stripe
+ * or close, and only after orcgpu_writer_set_row_index with a stride above 0 (which cannot be changed afterwards); fpp, the false
+ * positive probability, strictly between 0 and 1; an unknown name or one listed twice: ORCGPU_INVALID_ARGUMENT otherwise.  A
+ * Boolean, Timestamp or Decimal128 column: ORCGPU_UNSUPPORTED, the message naming it (INTEGRATION.md 8 says why).  A call
+ * replaces the list of an earlier one; a call that fails changes nothing.
+ * Size, with n the stride: numBits = (int64)(-n ln fpp / (ln 2)^2), the bitset numBits / 64 + 1 words of 64 bits, k =
+ * max(1, round(numBits / n * ln 2)) hash functions (10000, 0.01: 1498 words, k = 7); a bitset above 2^30 bytes:
+ * ORCGPU_INVALID_ARGUMENT.  Every row group of a listed column has a filter of that size, the short last one and one without
+ * a value (all zero) too.  Nulls are not hashed.  Byte .. Long: the value as i64 through Thomas Wang's hash; Float, Double: the
+ * value as a double, its bits (every NaN as 0x7ff8000000000000) through the same hash; Utf8, LargeUtf8, Binary, LargeBinary: ORC's
+ * Murmur3 hash64 (seed 104729) of the bytes, whatever encoding the stripe writes the column with.  The filters are built on the
+ * device at the flush; the bytes do not depend on how the device schedules the work.  Compressed files write the stream as
+ * original chunks, like the row index.  Nothing else of the file changes, and a stripe costs no host wait more. */
+int orcgpu_writer_set_bloom_filter(orcgpu_writer* w, const char* const* columns, uint32_t n_columns, double fpp);
+
 /* ---- timing hooks used by bench.py (HIP events on the context's own stream) ---------------------- */
 /* Milliseconds the device spent in the last orcgpu_decode_staged call, whole call and the RLE
  * expansion kernels alone (the dominant kernel), measured with hipEvents on the ctx stream. */

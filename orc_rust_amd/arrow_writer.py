@@ -5,6 +5,7 @@
     w = ArrowWriterBuilder("out.orc", schema).with_compression("snappy").try_build()   # or "lz4"; compressed on the GPU
     w = ArrowWriterBuilder("out.orc", schema).with_row_index_stride(10000).try_build()  # row index + statistics, on the GPU
     w = ArrowWriterBuilder("out.orc", schema).with_dictionary_key_size_threshold(0.8).try_build()  # string dictionaries, on the GPU
+    w = ArrowWriterBuilder("out.orc", schema).with_row_index_stride(10000).with_bloom_filter_columns(["k"], fpp=0.01).try_build()
     w.write(batch)          # pyarrow.RecordBatch
     w.flush_stripe()
     w.close()
@@ -20,6 +21,7 @@ DEFAULT_STRIPE_BYTE_SIZE = 64 << 20  # arrow_writer.rs:51
 DEFAULT_COMPRESSION_BLOCK_SIZE = 262144  # compression.rs:31
 MAX_COMPRESSION_BLOCK_SIZE = (1 << 23) - 1  # a chunk header holds len * 2 + 1 in 24 bits
 MAX_ROW_INDEX_STRIDE = (1 << 31) - 1
+DEFAULT_BLOOM_FILTER_FPP = 0.01  # (with stride 10000: 1498 words and 7 hash functions, the filters of Apache ORC's bloom_filter.orc)
 COMPRESSIONS = {None: 0, "none": 0, "snappy": 2, "lz4": 4}  # the codecs the writer compresses with (capi.COMP)
 
 _SCHEMA_BYTES, _ARRAY_BYTES, _RELEASE_AT = 72, 80, {72: 56, 80: 64}  # struct ArrowSchema / ArrowArray, offset of `release`
@@ -55,6 +57,7 @@ class ArrowWriterBuilder:
         self._compression, self._block_size = 0, DEFAULT_COMPRESSION_BLOCK_SIZE
         self._row_index_stride = 0
         self._dictionary_threshold = 0.0
+        self._bloom_columns, self._bloom_fpp = [], DEFAULT_BLOOM_FILTER_FPP
 
     def with_batch_size(self, n):
         self._batch_size = int(n)
@@ -98,7 +101,23 @@ class ArrowWriterBuilder:
         self._dictionary_threshold = t
         return self
 
+    def with_bloom_filter_columns(self, columns, fpp=DEFAULT_BLOOM_FILTER_FPP):
+        """A BLOOM_FILTER_UTF8 stream per row group for the named top-level columns (integers, floats, strings, binaries), built on
+        the GPU and sized as Apache ORC sizes it from the row index stride and fpp, the false positive probability in (0, 1).
+        Needs with_row_index_stride(n > 0) by try_build.  An empty list: none (the default)."""
+        if not isinstance(columns, list) or not all(isinstance(c, str) for c in columns):
+            raise ValueError("bloom filter columns must be a list of str, not %r" % (columns,))
+        if isinstance(fpp, bool) or not isinstance(fpp, (int, float)):
+            raise ValueError("fpp must be a number, not %r" % (fpp,))
+        fpp = float(fpp)
+        if not 0.0 < fpp < 1.0:  # (NaN fails both)
+            raise ValueError("fpp must be strictly between 0 and 1")
+        self._bloom_columns, self._bloom_fpp = list(columns), fpp
+        return self
+
     def try_build(self):
+        if self._bloom_columns and not self._row_index_stride:
+            raise ValueError("bloom filter columns need with_row_index_stride(n) with n > 0: there is a filter per row group")
         if self._batch_size <= 0 or self._batch_size >= 1 << 32:
             raise ValueError("batch_size must be in 1 .. 2^32 - 1")
         if self._stripe_byte_size <= 0:  # (the C ABI reads 0 as the default)
@@ -126,6 +145,9 @@ class ArrowWriterBuilder:
                 ctx._check(ctx.L.orcgpu_writer_set_row_index(out.value, self._row_index_stride))
             if self._dictionary_threshold:
                 ctx._check(ctx.L.orcgpu_writer_set_dictionary(out.value, self._dictionary_threshold))
+            if self._bloom_columns:
+                names = (C.c_char_p * len(self._bloom_columns))(*[c.encode() for c in self._bloom_columns])
+                ctx._check(ctx.L.orcgpu_writer_set_bloom_filter(out.value, names, len(names), self._bloom_fpp))
         except Exception:
             w.free()
             raise

@@ -32,6 +32,7 @@ EXPORTS = [
     "orcgpu_writer_take_bytes", "orcgpu_writer_stats", "orcgpu_writer_stripe_rows", "orcgpu_writer_free",
     "orcgpu_writer_set_compression", "orcgpu_compress_stream", "orcgpu_writer_set_row_index",
     "orcgpu_writer_set_dictionary", "orcgpu_writer_dictionary_counts",
+    "orcgpu_writer_set_bloom_filter",
 ]
 
 
@@ -247,6 +248,7 @@ def load():
     L.orcgpu_writer_set_row_index.argtypes = [C.c_void_p, C.c_uint64]
     L.orcgpu_writer_set_dictionary.argtypes = [C.c_void_p, C.c_double]
     L.orcgpu_writer_dictionary_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.orcgpu_writer_set_bloom_filter.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_double]
     L.orcgpu_compress_stream.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64)]
     _lib = L

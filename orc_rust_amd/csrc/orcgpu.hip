@@ -49,6 +49,7 @@
 #include "device/writer_dict.hip"
 #include "device/writer_nested.hip"
 #include "device/col_stats.hip"
+#include "device/bloom_build.hip"
 
 #include "arrow_c_data.h"
 

@@ -26,6 +26,10 @@
 // included) ahead of the data, the stripes' statistics as the Metadata section and the file's in the Footer.  Index bytes do
 // not count toward the stripe cut.
 //
+// Bloom filters (orcgpu_writer_set_bloom_filter; the reference writes none): the listed columns' bitsets, one per row group, are
+// built behind the statistics kernels from the same tables (device/bloom_build.hip) and come back in the same copy; the host
+// writes a BLOOM_FILTER_UTF8 stream behind the column's ROW_INDEX.
+//
 // The files: orcgpu_writer_host.inc -- everything that never touches the device (the column tree, the description of a column's
 // streams, statistics, the bytes of index streams, footers and the tail); this file -- the writer, its device buffers, the
 // stream emitters and the C ABI; orcgpu_writer_flush.inc -- a stripe flushed (wr_dictionaries, wr_flush);
@@ -133,6 +137,10 @@ struct orcgpu_writer {
   uint32_t dict_hash_mask = 0xffffffffu;
   DevBuf dict_res;
   uint64_t n_dictionary = 0, n_direct = 0;
+  // Bloom filters (orcgpu_writer_set_bloom_filter): the listed columns (WrCol::bloom), n_bloom of them; every filter's 64-bit
+  // words and hash functions, sized once from the stride and the false positive probability
+  uint64_t n_bloom = 0, bloom_words = 0;
+  uint32_t bloom_k = 0;
 };
 
 namespace {
@@ -300,6 +308,8 @@ int wr_copy_stream(orcgpu_writer* w, const uint8_t* d_src, uint64_t n, uint64_t*
   *at += align_up(n);
   return ORCGPU_OK;
 }
+
+constexpr uint64_t kBloomMaxWords = 1ull << 27;  // a row group's Bloom filter: at most 2^30 bytes
 
 int wr_flush(orcgpu_writer* w);
 int wr_write(orcgpu_writer* w, const struct ArrowArray* batch, uint32_t flags, const std::vector<int64_t>& dev_ends, bool* rejected);
@@ -489,7 +499,63 @@ extern "C" int orcgpu_writer_set_row_index(orcgpu_writer* w, uint64_t stride) {
     set_err(w->ctx, "writer: no row index for a schema with a Struct, List or Map column (the row groups of their children are not written)");
     return ORCGPU_UNSUPPORTED;
   }
+  if (w->n_bloom) {
+    set_err(w->ctx, "writer: the row index stride is set before the Bloom filters, which are sized from it");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   w->stride = stride;
+  return ORCGPU_OK;
+}
+
+extern "C" int orcgpu_writer_set_bloom_filter(orcgpu_writer* w, const char* const* columns, uint32_t n_columns, double fpp) {
+  if (!w || (n_columns && !columns)) return ORCGPU_INVALID_ARGUMENT;
+  orcgpu_ctx* ctx = w->ctx;
+  if (w->started || w->closed) {
+    set_err(ctx, "writer: the Bloom filters are set before the first write, flush_stripe or close");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (!w->stride) {
+    set_err(ctx, "writer: Bloom filters need a row index (orcgpu_writer_set_row_index with a stride above 0 first): there is one per row group");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (!(fpp > 0.0 && fpp < 1.0)) {  // (NaN fails both)
+    set_err(ctx, "writer: the Bloom filters' false positive probability is strictly between 0 and 1");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  std::vector<size_t> listed;
+  for (uint32_t i = 0; i < n_columns; i++) {
+    if (!columns[i]) return ORCGPU_INVALID_ARGUMENT;
+    size_t at = w->cols.size();
+    for (int k : w->root_kids)
+      if (w->cols[(size_t)k].name == columns[i]) at = (size_t)k;
+    if (at == w->cols.size()) {
+      set_err(ctx, "writer: no field '%s' for a Bloom filter (a top-level field's name)", columns[i]);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    if (std::find(listed.begin(), listed.end(), at) != listed.end()) {
+      set_err(ctx, "writer: field '%s' is listed twice for a Bloom filter", columns[i]);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    const int kind = w->cols[at].stream_kind;
+    if (kind != WR_INT && kind != WR_BYTE && kind != WR_FLOAT && kind != WR_STRING) {
+      set_err(ctx, "writer: no Bloom filter for field '%s': Boolean, Timestamp and Decimal128 columns get none (integers, floats, strings and binaries do)",
+              columns[i]);
+      return ORCGPU_UNSUPPORTED;
+    }
+    listed.push_back(at);
+  }
+  uint64_t words = 0;
+  uint32_t k = 0;
+  wr_bloom_size(w->stride, fpp, words, k);
+  if (n_columns && words > kBloomMaxWords) {
+    set_err(ctx, "writer: a Bloom filter of %llu bytes per row group (at most 2^30: a larger stride or probability)", (unsigned long long)words * 8);
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  for (auto& c : w->cols) c.bloom = false;
+  for (size_t at : listed) w->cols[at].bloom = true;
+  w->n_bloom = listed.size();
+  w->bloom_words = words;
+  w->bloom_k = k;
   return ORCGPU_OK;
 }
 

@@ -1,7 +1,8 @@
 // orcgpu_writer_flush.inc -- a stripe of the ArrowWriter (orcgpu_writer.inc) flushed: which string columns get a dictionary
 // (wr_dictionaries), then StripeWriter::finish_stripe (wr_flush) in its steps -- the row index statistics enqueued, every
 // stream of every column enqueued from its description (orcgpu_writer_host.inc: wr_streams), compression, the ROW_INDEX streams
-// assembled on the host, the streams packed and copied back, the footer written.
+// assembled on the host (and the BLOOM_FILTER_UTF8 streams around the bitsets the device built), the streams packed and copied
+// back, the footer written.
 namespace {
 
 // Which string columns of the stripe being flushed are written DICTIONARY_V2 (orcgpu_writer_set_dictionary), and their
@@ -100,8 +101,10 @@ struct WrFlush {
   // row index: groups of S rows, G of them, NJ (column, group) jobs; the tables' places in w->ix, brought back from o_recs on
   uint64_t S = 0, G = 0, NJ = 0;
   uint64_t o_vscan = 0, o_bscan = 0, o_recs = 0, o_pos = 0, o_side = 0, ix_span = 0;
+  uint64_t o_bloom = 0;  // Bloom filters: the listed columns' bitsets, [listed column][group][words], brought back with the records
   std::vector<std::vector<std::pair<uint64_t, int>>> ix_streams;  // a column's streams (index, position form), PRESENT, DATA, LENGTH
   std::vector<std::vector<uint8_t>> index;                         // the ROW_INDEX streams, column 0 first
+  std::vector<std::vector<uint8_t>> bloom;                         // the BLOOM_FILTER_UTF8 streams, [column id] (empty: none)
 };
 
 // room: the lengths, the bitmaps of the Boolean / PRESENT streams
@@ -141,6 +144,8 @@ int wr_flush_stats(orcgpu_writer* w, WrFlush& F) {
   F.o_recs = X.take(NJ * sizeof(IxRec));  // (from here on: brought back)
   F.o_pos = X.take(F.n_streams * G * 32);
   F.o_side = X.take(side_bound);
+  const uint64_t bloom_group = w->bloom_words * 8, bloom_col = G * bloom_group;  // bytes of a group's bitset, of a column's
+  F.o_bloom = X.take(w->n_bloom * bloom_col);
   F.ix_span = X.off - F.o_recs;
   if (!wr_reserve(w, w->ix, X.off + kAlign, 0)) {
     set_err(ctx, "writer: out of device memory (%llu bytes of row index)", (unsigned long long)X.off);
@@ -173,6 +178,22 @@ int wr_flush_stats(orcgpu_writer* w, WrFlush& F) {
                 d_recs, d_slen));
   WR_TRY(launch(ix_scan_kernel, (uint64_t)1, true, 1024, ctx->stream, (const uint64_t*)d_slen, NJ, d_soff));
   WR_TRY(launch(ix_side_kernel, NJ, true, 256, ctx->stream, cc, G, (const uint64_t*)d_soff, d_recs, x + F.o_side));
+  // Bloom filters: a launch per listed column, a block per row group, over the tables just made.  A bitset that fits
+  // BLOOM_LDS_BYTES is built in LDS; a larger one in its place, zeroed first
+  uint64_t nb = 0;
+  for (size_t ci = 0; ci < nc; ci++) {
+    if (!w->cols[ci].bloom) continue;
+    uint32_t* d_bits = (uint32_t*)(x + F.o_bloom + nb++ * bloom_col);
+    if (bloom_group <= BLOOM_LDS_BYTES) {
+      hipLaunchKernelGGL(bloom_lds_kernel, dim3((uint32_t)G), dim3(256), (uint32_t)bloom_group, ctx->stream, cc, (uint32_t)ci, G, (const uint64_t*)d_cnt,
+                         (const uint64_t*)d_vscan, (const uint64_t*)d_bscan, w->bloom_k, (uint32_t)w->bloom_words, d_bits);
+      WR_TRY(hipGetLastError());
+    } else {
+      WR_TRY(hipMemsetAsync(d_bits, 0, bloom_col, ctx->stream));
+      WR_TRY(launch(bloom_global_kernel, G, true, 256, ctx->stream, cc, (uint32_t)ci, G, (const uint64_t*)d_cnt, (const uint64_t*)d_vscan,
+                    (const uint64_t*)d_bscan, w->bloom_k, w->bloom_words, d_bits));
+    }
+  }
   return ORCGPU_OK;
 }
 
@@ -266,14 +287,19 @@ int wr_flush_pack(orcgpu_writer* w, WrFlush& F) {
   return wr_sync(w);
 }
 
-// the stripe into the sink: ROW_INDEX streams, data, footer; the writer's stripe state starts over
+// the stripe into the sink: the index streams (per column ROW_INDEX, then its BLOOM_FILTER_UTF8), data, footer; the writer's
+// stripe state starts over
 int wr_flush_finish(orcgpu_writer* w, WrFlush& F) {
-  const std::vector<uint8_t> footer = wr_stripe_footer(w->cols, F.index, F.streams, F.lens, F.comp, w->comp_block);
+  const std::vector<uint8_t> footer = wr_stripe_footer(w->cols, F.index, F.streams, F.lens, F.comp, w->comp_block, F.bloom);
   const uint64_t start = w->written;
   uint64_t index_length = 0;
-  for (auto& b : F.index) {
-    index_length += b.size();
-    int rc = wr_sink(w, b.data(), b.size());
+  for (size_t ci = 0; ci < F.index.size(); ci++) {
+    index_length += F.index[ci].size();
+    int rc = wr_sink(w, F.index[ci].data(), F.index[ci].size());
+    if (rc) return rc;
+    if (!ci || !w->cols[ci - 1].bloom) continue;
+    index_length += F.bloom[ci].size();
+    rc = wr_sink(w, F.bloom[ci].data(), F.bloom[ci].size());
     if (rc) return rc;
   }
   int rc = wr_sink(w, w->pinned, F.total);
@@ -324,6 +350,13 @@ int wr_flush(orcgpu_writer* w) {
     F.index = wr_row_index(w->cols, w->rows, F.S, F.G, (const IxRec*)w->ix_pinned, (const uint64_t*)(w->ix_pinned + (F.o_pos - F.o_recs)),
                            w->ix_pinned + (F.o_side - F.o_recs), F.ix_streams, F.comp, w->comp_block, stripe);
     w->stripe_stats.push_back(std::move(stripe));
+    // BLOOM_FILTER_UTF8 streams: the bitsets came back in the same copy; the framing around them is the host's
+    F.bloom.resize(nc + 1);
+    uint64_t nb = 0;
+    for (size_t ci = 0; ci < nc; ci++)
+      if (w->cols[ci].bloom)
+        F.bloom[ci + 1] = wr_bloom_stream(w->bloom_k, w->bloom_words, F.G, w->ix_pinned + (F.o_bloom - F.o_recs) + nb++ * F.G * w->bloom_words * 8, F.comp,
+                                          w->comp_block);
   }
   rc = wr_flush_pack(w, F);
   if (!rc) rc = wr_flush_finish(w, F);

@@ -11,6 +11,8 @@
 //   wr_stat_msg, wr_*_bound
 //   wr_row_index,               the bytes of a stripe's ROW_INDEX streams, its footer and the file's tail
 //   wr_stripe_footer, wr_tail
+//   wr_bloom_size,              Bloom filters (orcgpu_writer_set_bloom_filter): Apache ORC's sizing, and a column's
+//   wr_bloom_stream             BLOOM_FILTER_UTF8 stream around the bitsets the device built (device/bloom_build.hip)
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -127,6 +129,7 @@ struct WrCol {
   // entries and their bytes
   bool dict = false;
   uint64_t dict_size = 0, dict_bytes = 0;
+  bool bloom = false;  // a BLOOM_FILTER_UTF8 stream behind the column's ROW_INDEX (orcgpu_writer_set_bloom_filter)
   bool is_nest() const { return stream_kind == WR_STRUCT || stream_kind == WR_LIST; }
   bool has_bytes() const { return stream_kind == WR_STRING || stream_kind == WR_DECIMAL; }  // n_bytes / data count toward the estimate
   bool is_utf8() const { return orc_kind == ORCGPU_T_STRING; }  // a string column with a minimum / maximum, and the one a dictionary is tried for
@@ -674,9 +677,39 @@ std::vector<std::vector<uint8_t>> wr_row_index(const std::vector<WrCol>& cols, u
   return index;
 }
 
-// StripeFooter: the ROW_INDEX streams, the data streams with their lengths, the columns' encodings (column 0 the root)
+// ---- Bloom filters ------------------------------------------------------------------------------------------------------------
+// Apache ORC's sizing (BloomFilter.java: optimalNumOfBits, optimalNumOfHashFunctions) for n = the row index stride expected
+// entries and the false positive probability fpp in (0, 1): the bitset's 64-bit words, and k hash functions
+void wr_bloom_size(uint64_t n, double fpp, uint64_t& words, uint32_t& k) {
+  const double bits = std::floor(-(double)n * std::log(fpp) / (std::log(2.0) * std::log(2.0)));  // (int64) of a value >= 0
+  words = (uint64_t)(bits / 64.0) + 1;
+  const double kk = std::floor(bits / (double)n * std::log(2.0) + 0.5);  // Math.round
+  k = kk < 1.0 ? 1u : (kk > 4294967295.0 ? 4294967295u : (uint32_t)kk);
+}
+
+// a column's BLOOM_FILTER_UTF8 stream: a BloomFilterIndex of G BloomFilter {1 numHashFunctions, 3 utf8bitset}; bitsets: G times
+// `words` u64 as the device left them (word w: 8 little-endian bytes at utf8bitset[8w]).  Its length depends on (words, k, G) alone
+std::vector<uint8_t> wr_bloom_stream(uint32_t k, uint64_t words, uint64_t G, const uint8_t* bitsets, bool comp, uint64_t comp_block) {
+  PbOut head;  // what precedes a filter's bitset bytes
+  head.u64(1, k);
+  head.key(3, 2);
+  head.varint(words * 8);
+  PbOut out;
+  out.b.reserve(G * (words * 8 + head.b.size() + 8));
+  for (uint64_t g = 0; g < G; g++) {
+    out.key(1, 2);
+    out.varint(head.b.size() + words * 8);
+    out.b.insert(out.b.end(), head.b.begin(), head.b.end());
+    out.b.insert(out.b.end(), bitsets + g * words * 8, bitsets + (g + 1) * words * 8);
+  }
+  return comp ? wr_original_chunks(out.b, comp_block) : out.b;
+}
+
+// StripeFooter: the index streams -- per column its ROW_INDEX, then its BLOOM_FILTER_UTF8 (bloom[column], of the columns that
+// have one: WrCol::bloom) --, the data streams with their lengths, the columns' encodings (column 0 the root)
 std::vector<uint8_t> wr_stripe_footer(const std::vector<WrCol>& cols, const std::vector<std::vector<uint8_t>>& index, const std::vector<WrStreamOut>& streams,
-                                      const std::vector<uint64_t>& lens, bool comp, uint64_t comp_block) {
+                                      const std::vector<uint64_t>& lens, bool comp, uint64_t comp_block,
+                                      const std::vector<std::vector<uint8_t>>& bloom = std::vector<std::vector<uint8_t>>()) {
   PbOut footer;
   for (size_t ci = 0; ci < index.size(); ci++) {
     PbOut m;
@@ -684,6 +717,13 @@ std::vector<uint8_t> wr_stripe_footer(const std::vector<WrCol>& cols, const std:
     m.u64(2, ci);
     m.u64(3, index[ci].size());
     footer.msg(1, m);
+    if (ci && cols[ci - 1].bloom && ci < bloom.size()) {
+      PbOut b;
+      b.u64(1, ORCGPU_S_BLOOM_FILTER_UTF8);
+      b.u64(2, ci);
+      b.u64(3, bloom[ci].size());
+      footer.msg(1, b);
+    }
   }
   for (size_t i = 0; i < streams.size(); i++) {
     PbOut m;

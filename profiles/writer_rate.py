@@ -22,7 +22,11 @@ maps that keep their ranges (every child column is gathered through a row map). 
 --dictionary T: the lineitem table written with ArrowWriterBuilder.with_dictionary_key_size_threshold(T) and, in the same run,
 with threshold 0 (the yardstick: the writer as it is without dictionaries), host batches, 64 MiB stripes, best of 3: rows per
 second, file sizes and their ratios; with --kernel-stats the share of the dictionary kernels (wd_*) in the device time
-(profiles/writer_rate_dict.json)."""
+(profiles/writer_rate_dict.json).
+--bloom-filter COLS (comma separated): the lineitem table written with ArrowWriterBuilder.with_bloom_filter_columns(COLS, fpp=0.01)
+and, in the same run, with the row index alone (the yardstick), at --row-index-stride (10000 when not given), host batches, 64 MiB
+stripes, best of 3: rows per second both ways, the file sizes; with --kernel-stats the share of the Bloom kernels (bloom_*) in the
+device time.  Also written to profiles/writer_rate_bloom.json."""
 import argparse
 import csv
 import ctypes as C
@@ -133,11 +137,11 @@ class DeviceBatch:
         self.ptrs = []
 
 
-def gpu_write(ctx, batches, schema, sbs, device=None, compression=None, stride=0, dictionary=0.0):
+def gpu_write(ctx, batches, schema, sbs, device=None, compression=None, stride=0, dictionary=0.0, bloom=()):
     out = io.BytesIO()
     t0 = time.perf_counter()
     w = (ArrowWriterBuilder(out, schema, ctx=ctx).with_stripe_byte_size(sbs).with_compression(compression).with_row_index_stride(stride)
-         .with_dictionary_key_size_threshold(dictionary).try_build())
+         .with_dictionary_key_size_threshold(dictionary).with_bloom_filter_columns(list(bloom), fpp=0.01).try_build())
     if device is None:
         for b in batches:
             w.write(b)
@@ -376,6 +380,51 @@ def main_dictionary(args):
     print(json.dumps(out))
 
 
+def main_bloom(args):
+    per_batch = 1_000_000
+    rng = np.random.default_rng(1)
+    batches = [lineitem(per_batch, rng) for _ in range(max(1, args.rows // per_batch))]
+    schema = batches[0].schema
+    n = per_batch * len(batches)
+    arrow_bytes = sum(b.nbytes for b in batches)
+    stride = args.row_index_stride or 10000
+    cols = [c for c in args.bloom_filter.split(",") if c]
+    ctx = capi.Context()
+    out = {"rows": n, "columns": len(schema), "arrow_bytes": arrow_bytes, "row_index_stride": stride, "bloom_filter_columns": cols, "fpp": 0.01,
+           "unit": "Mrows/s (open .. close), host batches, 64 MiB stripes, best of 3, both arms in one process", "runs": {}}
+    arms = (("bloom filters", tuple(cols)), ("row index only (the yardstick)", ()))
+    for _, bloom in arms:
+        gpu_write(ctx, batches[:1], schema, 64 << 20, stride=stride, bloom=bloom)  # warm-up
+    times, kept = {name: [] for name, _ in arms}, {}
+    for _ in range(3):  # (the arms take turns)
+        for name, bloom in arms:
+            dt, st, size = gpu_write(ctx, batches, schema, 64 << 20, stride=stride, bloom=bloom)
+            times[name].append(dt)
+            kept[name] = (st, size)
+    for name, _ in arms:
+        st, size = kept[name]
+        dt = min(times[name])
+        out["runs"][name] = {"seconds": round(dt, 4), "seconds_all": [round(x, 4) for x in times[name]], "Mrows/s": round(n / dt / 1e6, 2),
+                             "GB/s": round(arrow_bytes / dt / 1e9, 3), "file_bytes": size, "stripes": st["stripes"],
+                             "stripe_round_trips_per_stripe": round(st["stripe_round_trips"] / max(1, st["stripes"]), 1)}
+    a, b = out["runs"][arms[0][0]], out["runs"][arms[1][0]]
+    out["rate_vs_yardstick"] = round(a["Mrows/s"] / b["Mrows/s"], 3)
+    out["file_size_vs_yardstick"] = round(a["file_bytes"] / b["file_bytes"], 4)
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        ms = {r["Name"].split("(")[0]: round(float(r["TotalDurationNs"]) / 1e6, 3) for r in rows}
+        mine = {k: v for k, v in ms.items() if k.startswith("bloom_")}
+        out["kernels"] = {"what": "rocprofv3 --kernel-trace --stats of this command in a run of its own, both arms, all runs",
+                          "all_kernels_ms": round(total / 1e6, 3), "bloom_kernels_ms": mine,
+                          "bloom_kernels_share": round(sum(mine.values()) * 1e6 / total, 4),
+                          "largest_kernels_ms": dict(sorted(ms.items(), key=lambda kv: -kv[1])[:6])}
+    text = json.dumps(out)
+    with open(os.path.join(ROOT, "profiles", "writer_rate_bloom.json"), "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rows", nargs="?", type=int, default=8_000_000)
@@ -385,7 +434,10 @@ def main():
     ap.add_argument("--types", action="store_true")
     ap.add_argument("--nested", action="store_true")
     ap.add_argument("--dictionary", type=float, default=0.0)
+    ap.add_argument("--bloom-filter", default="")
     args = ap.parse_args()
+    if args.bloom_filter:
+        return main_bloom(args)
     if args.dictionary:
         return main_dictionary(args)
     if args.nested:
