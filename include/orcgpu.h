@@ -168,10 +168,11 @@ void orcgpu_close(orcgpu_ctx* ctx);
 const char* orcgpu_last_error(const orcgpu_ctx* ctx);
 const char* orcgpu_version(void);
 /* The binary interface a caller was built against: bumped whenever a struct of this header changes size or layout, or an entry
- * point changes its meaning.  3 (round 6): orcgpu_lane_stats gained literals_kernel_ms; 2 (round 5): orcgpu_reader_next_batch
+ * point changes its meaning.  4: device-resident batches (struct ArrowDeviceArray and the *_device entry points) were added;
+ * 3 (round 6): orcgpu_lane_stats gained literals_kernel_ms; 2 (round 5): orcgpu_reader_next_batch
  * ends with ORCGPU_END_OF_FILE (110) instead of 1, orcgpu_stream gained skip_bits.  A binding checks orcgpu_abi_version() ==
  * ORCGPU_ABI_VERSION once, after loading the library. */
-#define ORCGPU_ABI_VERSION 3
+#define ORCGPU_ABI_VERSION 4
 int orcgpu_abi_version(void);
 
 /* ---- staging: host stream bytes -> HBM --------------------------------------------------------- */
@@ -273,6 +274,51 @@ int orcgpu_result_fetch_async(orcgpu_ctx* ctx, orcgpu_result* r);
 /* ---- Arrow C Data Interface export (https://arrow.apache.org/docs/format/CDataInterface.html) ---- */
 struct ArrowSchema;
 struct ArrowArray;
+struct ArrowDeviceArray;
+/* The three are incomplete types here: a caller brings its own definitions (Arrow's abi.h, arrow::ffi, a restatement of the
+ * specification).  A caller that wants them from this header defines ORCGPU_ARROW_STRUCTS before including it. */
+#ifdef ORCGPU_ARROW_STRUCTS
+#ifndef ARROW_C_DATA_INTERFACE
+#define ARROW_C_DATA_INTERFACE
+struct ArrowSchema {
+  const char* format;
+  const char* name;
+  const char* metadata;
+  int64_t flags;
+  int64_t n_children;
+  struct ArrowSchema** children;
+  struct ArrowSchema* dictionary;
+  void (*release)(struct ArrowSchema*);
+  void* private_data;
+};
+struct ArrowArray {
+  int64_t length;
+  int64_t null_count;
+  int64_t offset;
+  int64_t n_buffers;
+  int64_t n_children;
+  const void** buffers;
+  struct ArrowArray** children;
+  struct ArrowArray* dictionary;
+  void (*release)(struct ArrowArray*);
+  void* private_data;
+};
+#endif
+/* The Arrow C Device Data Interface (https://arrow.apache.org/docs/format/CDeviceDataInterface.html): an ArrowArray whose buffer
+ * pointers are device memory, the device they live on, and an event to wait for before reading them. */
+#ifndef ARROW_C_DEVICE_DATA_INTERFACE
+#define ARROW_C_DEVICE_DATA_INTERFACE
+#define ARROW_DEVICE_CPU 1
+#define ARROW_DEVICE_ROCM 10
+struct ArrowDeviceArray {
+  struct ArrowArray array;
+  int64_t device_id;
+  int32_t device_type;  /* ARROW_DEVICE_* */
+  void* sync_event;     /* ROCm: a hipEvent_t*, or NULL when no synchronisation is needed */
+  int64_t reserved[3];
+};
+#endif
+#endif /* ORCGPU_ARROW_STRUCTS */
 /* Exports batch `batch` as a struct array (one child per projected column) into HOST memory owned
  * by the release callbacks; a Rust caller imports it with arrow::ffi::from_ffi, Python with
  * pyarrow.RecordBatch._import_from_c.  Field names are "c<column_id>"; the caller renames. */
@@ -429,6 +475,62 @@ const char* orcgpu_reader_column_name(orcgpu_reader* r, uint32_t i);
 /* ArrowReader::next: 0 = one RecordBatch exported (struct array, host memory), ORCGPU_END_OF_FILE = no more batches,
  * anything else = the OrcError status of the failing batch (the iterator then ends). */
 int orcgpu_reader_next_batch(orcgpu_reader* r, struct ArrowArray* out_array, struct ArrowSchema* out_schema);
+
+/* ---- device-resident batches (Arrow C Device Data Interface, DLPack) --------------------------------------------------------------
+ * A decoded result lives in HBM; the entry points above copy it to pinned host memory before a consumer sees a byte.  These
+ * hand the device buffers out instead, for consumers on the same GPU (a torch model, this library's own writer with
+ * ORCGPU_ENC_ON_DEVICE): nothing crosses the link.  Flat schemas only: every root column a primitive, string, binary, decimal
+ * or timestamp column; a Struct, List, Map or Union column among them is ORCGPU_UNSUPPORTED, the message naming the column.
+ *
+ * export_batch_device: the device twin of orcgpu_result_export_batch -- the same struct array, formats, null counts and the same
+ * rule of no validity buffer when the batch has no null --, every buffer pointer being the device pointer that
+ * orcgpu_result_batch_view reports.  No byte is copied.  device_type is ARROW_DEVICE_ROCM, device_id the context's device, and
+ * sync_event points to a hipEvent_t recorded on the decode stream behind the last work that writes the result (decode, row
+ * selection, row filter): wait for it (orcgpu_device_array_wait) before reading a buffer on another stream or on the host.
+ *
+ * Ownership.  Every exported ArrowDeviceArray, and every DLPack tensor made from one, holds a reference on the result it views.
+ * A result with references outstanding is neither decoded into again nor freed: orcgpu_result_free and orcgpu_reader_close
+ * only give up the owner's claim, and the memory goes when the last reference is released (a reader that is still open then takes
+ * the result back and decodes a later stripe into it; meanwhile it allocates fresh ones).  So exported batches stay valid after
+ * orcgpu_result_free and orcgpu_reader_close -- but NOT after orcgpu_close: the context must outlive every exported batch and
+ * tensor.  Release an array exactly once through array.release; it may be released in any thread, and with work that reads its
+ * buffers still in flight on any stream of the device: before the library writes into a result that has been exported again --
+ * the reader recycling it, a caller passing it to orcgpu_decode_staged once more -- it waits for the device (freeing waits, too).
+ * While exports view it, a result is refused by orcgpu_decode_staged, orcgpu_result_select and orcgpu_result_filter
+ * (ORCGPU_INVALID_ARGUMENT). */
+int orcgpu_result_export_batch_device(orcgpu_ctx* ctx, const orcgpu_result* r, uint32_t batch, struct ArrowDeviceArray* out_array,
+                                      struct ArrowSchema* out_schema);
+/* A builder setter (before the first batch): on != 0 makes the reader hand out device batches through
+ * orcgpu_reader_next_batch_device; it then never starts a device-to-host copy of a column buffer.  Everything else -- batch
+ * size, projection, schema, byte range, shard, timestamp precision, row selection, predicate, row filter, read-ahead -- works as
+ * on the host path and yields the same batches.  orcgpu_reader_next_batch on such a reader, and orcgpu_reader_next_batch_device
+ * on a host reader, return ORCGPU_INVALID_ARGUMENT and leave the reader usable for the right call.  A nested column in the
+ * projection fails the first batch with ORCGPU_UNSUPPORTED. */
+int orcgpu_reader_set_device_output(orcgpu_reader* r, int on);
+int orcgpu_reader_next_batch_device(orcgpu_reader* r, struct ArrowDeviceArray* out_array, struct ArrowSchema* out_schema);
+/* Column-buffer bytes the reader has copied to the host so far (what orcgpu_result_fetch_async moves; the decoder's small
+ * summaries are not counted).  0 on a device-output reader. */
+int orcgpu_reader_d2h_bytes(const orcgpu_reader* r, uint64_t* bytes);
+/* Bytes of the result's column buffers in HBM, as the decode (and the selection or filter after it) laid them out: what a copy back
+ * of the result moves -- whole arenas, alignment gaps included; a filtered result: the kept rows' arena alone. */
+uint64_t orcgpu_result_buffer_bytes(const orcgpu_result* r);
+/* 1 while the reader's read-ahead threads are at work on its context (from the first batch of a reader with prefetch > 0 until its
+ * last stripe is decoded, an error or orcgpu_reader_close), else 0: the context takes no other call meanwhile. */
+int orcgpu_reader_reads_ahead(orcgpu_reader* r);
+/* Makes `hip_stream` (a hipStream_t) wait for the array's sync_event; with a NULL stream -- which is also what HIP's default
+ * stream is -- the calling thread waits instead.  An array without an event: nothing to wait for. */
+int orcgpu_device_array_wait(const struct ArrowDeviceArray* array, void* hip_stream);
+/* One buffer of one column of an array exported by this library as a DLPack tensor (include/orcgpu_dlpack.h: a DLManagedTensor*,
+ * kDLROCM, the array's device): buffer 0 the validity bitmap (uint8, ceil(n / 8)), 1 the values (fixed width: the natural type,
+ * [n]; Decimal128: int64 [n, 2], low word first; Boolean: the bitmap as uint8) or, for strings and binaries, the int32 offsets
+ * [n + 1], 2 the string bytes (uint8).  A buffer the column does not have (no validity: the batch has no null), or an empty one:
+ * ORCGPU_INVALID_ARGUMENT.  The tensor holds a reference of its own (see Ownership): it outlives the array; its deleter drops it. */
+int orcgpu_device_array_dlpack(const struct ArrowDeviceArray* array, uint32_t column, int buffer, void** out_managed_tensor);
+/* Unpacks an LSB-first bitmap of n bits in device memory, from bit 0 on, to one byte per bit (0 or 1) in device memory of the
+ * context's device, by a kernel on `hip_stream` (a hipStream_t; NULL is HIP's default stream).  The call does not wait.  Reads
+ * ceil(n / 8) bytes, writes n bytes; neither pointer needs any alignment.  The caller orders the stream behind the bitmap's
+ * producer (orcgpu_device_array_wait). */
+int orcgpu_unpack_bits(orcgpu_ctx* ctx, const void* d_bits, uint64_t n, uint8_t* d_bytes, void* hip_stream);
 
 /* ---- GPU encode: the reference's value encoders, byte for byte ------------------------------ */
 /* Replace RleV2Encoder<N, S>::{write_slice, take_inner} (src/encoding/integer/rle_v2/mod.rs:255-531), ByteRleEncoder

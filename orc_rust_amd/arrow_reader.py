@@ -4,6 +4,8 @@ C++ host layer inside liborcgpu.so.  Pure plumbing: every call forwards to the C
 
     reader = ArrowReaderBuilder.try_new("file.orc").with_batch_size(8192).with_projection(["a", "b"]).build()
     for batch in reader: ...            # pyarrow.RecordBatch, like `impl Iterator<Item = Result<RecordBatch>>`
+    reader = ArrowReaderBuilder.try_new("file.orc").with_device_output().build()
+    for batch in reader: ...            # device_batch.DeviceRecordBatch: torch tensors over the decoder's buffers, nothing copied
 """
 import ctypes as C
 
@@ -15,6 +17,7 @@ DEFAULT_BATCH_SIZE = 8192  # arrow_reader.rs:37
 class ArrowReaderBuilder:
     def __init__(self, ctx, handle, keep=None):
         self._ctx, self._h, self._keep = ctx, handle, keep
+        self._device_output = False
 
     @classmethod
     def try_new(cls, source, ctx=None):
@@ -107,6 +110,13 @@ class ArrowReaderBuilder:
         self._ctx._check(self._ctx.L.orcgpu_reader_set_prefetch(self._h, stripes))
         return self
 
+    def with_device_output(self, on=True):
+        """The reader yields device_batch.DeviceRecordBatch objects: the decoder's buffers in HBM as torch tensors, no copy to the
+        host (orcgpu_reader_set_device_output).  Flat schemas only; every other builder option works as on the host path."""
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_device_output(self._h, 1 if on else 0))
+        self._device_output = bool(on)
+        return self
+
     def total_row_count(self):
         return self._ctx.L.orcgpu_reader_total_rows(self._h)
 
@@ -114,7 +124,7 @@ class ArrowReaderBuilder:
         return self._ctx.L.orcgpu_reader_stripe_count(self._h)
 
     def build(self):
-        r = ArrowReader(self._ctx, self._h, self._keep)
+        r = ArrowReader(self._ctx, self._h, self._keep, self._device_output)
         self._h = None
         return r
 
@@ -124,8 +134,9 @@ class ArrowReaderBuilder:
 
 
 class ArrowReader:
-    def __init__(self, ctx, handle, keep=None):
+    def __init__(self, ctx, handle, keep=None, device_output=False):
         self._ctx, self._h, self._keep = ctx, handle, keep
+        self._device_output = device_output
 
     def total_row_count(self):
         return self._ctx.L.orcgpu_reader_total_rows(self._h)
@@ -142,6 +153,16 @@ class ArrowReader:
         self._ctx._check(self._ctx.L.orcgpu_reader_filter_rows(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def d2h_bytes(self):
+        """Column-buffer bytes this reader has copied to the host so far (orcgpu_reader_d2h_bytes); 0 with device output."""
+        n = C.c_uint64(0)
+        self._ctx._check(self._ctx.L.orcgpu_reader_d2h_bytes(self._h, C.byref(n)))
+        return n.value
+
+    def reads_ahead(self):
+        """Whether the reader's read-ahead threads are at work on its context right now (orcgpu_reader_reads_ahead)"""
+        return bool(self._h) and bool(self._ctx.L.orcgpu_reader_reads_ahead(self._h))
+
     def column_names(self):
         n = self._ctx.L.orcgpu_reader_column_count(self._h)
         return [self._ctx.L.orcgpu_reader_column_name(self._h, i).decode() for i in range(n)]
@@ -149,8 +170,21 @@ class ArrowReader:
     def __iter__(self):
         return self
 
+    def _next_device(self):
+        import pyarrow as pa
+        from .device_batch import ArrowDeviceArrayStruct, DeviceRecordBatch
+        a = ArrowDeviceArrayStruct()
+        s = (C.c_uint8 * 72)()
+        rc = self._ctx.L.orcgpu_reader_next_batch_device(self._h, C.addressof(a), C.addressof(s))
+        if rc == 110:  # ORCGPU_END_OF_FILE
+            raise StopIteration
+        self._ctx._check(rc)
+        return DeviceRecordBatch(self._ctx, a, pa.Schema._import_from_c(C.addressof(s)), self)
+
     def __next__(self):
         import pyarrow as pa
+        if self._device_output:
+            return self._next_device()
         a = (C.c_uint8 * 80)()
         s = (C.c_uint8 * 72)()
         rc = self._ctx.L.orcgpu_reader_next_batch(self._h, C.addressof(a), C.addressof(s))

@@ -7,6 +7,7 @@
     w = ArrowWriterBuilder("out.orc", schema).with_dictionary_key_size_threshold(0.8).try_build()  # string dictionaries, on the GPU
     w = ArrowWriterBuilder("out.orc", schema).with_row_index_stride(10000).with_bloom_filter_columns(["k"], fpp=0.01).try_build()
     w.write(batch)          # pyarrow.RecordBatch
+    w.write_device(batch)   # device_batch.DeviceRecordBatch (ArrowReaderBuilder.with_device_output()): encoded from HBM, no host copy
     w.flush_stripe()
     w.close()
 
@@ -189,6 +190,27 @@ class ArrowWriter:
         """The C ABI call: an exported ArrowSchema / ArrowArray (flags capi.ENC_ON_DEVICE: device buffers)."""
         self._check(self._ctx.L.orcgpu_writer_write(self._h, schema_addr, array_addr, flags))
         self._drain()
+
+    def write_device(self, batch):
+        """A device_batch.DeviceRecordBatch, written from its device buffers (ORCGPU_ENC_ON_DEVICE): nothing of it crosses the link.
+        The writer's context must be on the batch's device.  On the batch's own context the write runs behind the decode on the same
+        stream -- which needs a reader that does not read ahead (with_prefetch(0)), or one that has ended: a reading-ahead reader's
+        threads own their context.  On another context of the same device the host waits for the batch's event first."""
+        if batch._array is None:
+            raise ValueError("the batch has been released")
+        if self._ctx.device != batch.device_id:
+            raise ValueError("the batch lives on device %d, the writer's context on device %d" % (batch.device_id, self._ctx.device))
+        if self._ctx is batch._ctx:
+            reader = batch._reader() if batch._reader is not None else None
+            if reader is not None and reader.reads_ahead():
+                raise ValueError("the batch's reader reads ahead on this context: give the writer a context of its own, or build the reader with_prefetch(0)")
+        else:
+            self._check(self._ctx.L.orcgpu_device_array_wait(C.byref(batch._array), None))
+        s = _export_schema(batch.schema)
+        try:
+            self.write_c(s.addr, C.addressof(batch._array), capi.ENC_ON_DEVICE)
+        finally:
+            s.release()
 
     def flush_stripe(self):
         self._check(self._ctx.L.orcgpu_writer_flush_stripe(self._h))

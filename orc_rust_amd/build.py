@@ -17,6 +17,7 @@ def _sources():
             if f.endswith((".hip", ".inc", ".h")):
                 out.append(os.path.join(root, f))
     out.append(os.path.join(os.path.dirname(HERE), "include", "orcgpu.h"))
+    out.append(os.path.join(os.path.dirname(HERE), "include", "orcgpu_dlpack.h"))
     return out
 
 

@@ -28,6 +28,8 @@ EXPORTS = [
     "orcgpu_result_filter", "orcgpu_reader_set_row_filter", "orcgpu_reader_filter_rows",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
+    "orcgpu_result_export_batch_device", "orcgpu_reader_set_device_output", "orcgpu_reader_next_batch_device", "orcgpu_reader_d2h_bytes",
+    "orcgpu_device_array_wait", "orcgpu_device_array_dlpack", "orcgpu_unpack_bits", "orcgpu_result_buffer_bytes", "orcgpu_reader_reads_ahead",
     "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
     "orcgpu_writer_take_bytes", "orcgpu_writer_stats", "orcgpu_writer_stripe_rows", "orcgpu_writer_free",
     "orcgpu_writer_set_compression", "orcgpu_compress_stream", "orcgpu_writer_set_row_index",
@@ -137,7 +139,7 @@ class BatchView(C.Structure):
 
 
 _lib = None
-ABI_VERSION = 3  # include/orcgpu.h: ORCGPU_ABI_VERSION
+ABI_VERSION = 4  # include/orcgpu.h: ORCGPU_ABI_VERSION
 
 
 def lib_path():
@@ -234,6 +236,16 @@ def load():
     L.orcgpu_reader_column_name.restype = C.c_char_p
     L.orcgpu_reader_column_name.argtypes = [C.c_void_p, C.c_uint32]
     L.orcgpu_reader_next_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orcgpu_result_export_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.orcgpu_reader_set_device_output.argtypes = [C.c_void_p, C.c_int]
+    L.orcgpu_reader_next_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orcgpu_reader_d2h_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.orcgpu_device_array_wait.argtypes = [C.c_void_p, C.c_void_p]
+    L.orcgpu_device_array_dlpack.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.orcgpu_unpack_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.orcgpu_result_buffer_bytes.restype = C.c_uint64
+    L.orcgpu_result_buffer_bytes.argtypes = [C.c_void_p]
+    L.orcgpu_reader_reads_ahead.argtypes = [C.c_void_p]
     L.orcgpu_writer_open_file.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(WriterOpts), C.POINTER(C.c_void_p)]
     L.orcgpu_writer_open_bytes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(WriterOpts), C.POINTER(C.c_void_p)]
     L.orcgpu_writer_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -260,6 +272,7 @@ class Context:
 
     def __init__(self, device=0):
         self.L = load()
+        self.device = device
         self.h = self.L.orcgpu_open(device, None)
         if not self.h:
             raise OrcGpuError(100, "orcgpu_open(%d) failed: no usable HIP device (this library has no CPU path)" % device)
@@ -499,6 +512,11 @@ class Result:
     def arrow_bytes(self):
         return self.ctx.L.orcgpu_result_arrow_bytes(self.h)
 
+    @property
+    def buffer_bytes(self):
+        """Bytes of the result's column buffers in HBM: what a copy back moves (orcgpu_result_buffer_bytes)"""
+        return self.ctx.L.orcgpu_result_buffer_bytes(self.h)
+
     def view(self, batch, column):
         v = BatchView()
         self.ctx._check(self.ctx.L.orcgpu_result_batch_view(self.h, batch, column, C.byref(v)))
@@ -529,6 +547,16 @@ class Result:
     def fetch_async(self):
         """Starts that copy and returns (orcgpu_result_fetch_async); fetch() / export_batch() wait for it."""
         self.ctx._check(self.ctx.L.orcgpu_result_fetch_async(self.ctx.h, self.h))
+
+    def export_batch_device(self, batch):
+        """Arrow C Device Data Interface export -> orc_rust_amd.device_batch.DeviceRecordBatch: views of the result's own device
+        buffers (orcgpu_result_export_batch_device), valid after free()."""
+        import pyarrow as pa
+        from .device_batch import ArrowDeviceArrayStruct, DeviceRecordBatch
+        a = ArrowDeviceArrayStruct()
+        s = (C.c_uint8 * 72)()
+        self.ctx._check(self.ctx.L.orcgpu_result_export_batch_device(self.ctx.h, self.h, batch, C.addressof(a), C.addressof(s)))
+        return DeviceRecordBatch(self.ctx, a, pa.Schema._import_from_c(C.addressof(s)))
 
     def export_batch(self, batch):
         """Arrow C Data Interface export -> pyarrow.RecordBatch (zero-copy import of host buffers)."""

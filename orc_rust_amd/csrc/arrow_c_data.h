@@ -29,4 +29,17 @@ struct ArrowArray {
   void* private_data;
 };
 #endif
+// ... and the Arrow C Device Data Interface
+#ifndef ARROW_C_DEVICE_DATA_INTERFACE
+#define ARROW_C_DEVICE_DATA_INTERFACE
+#define ARROW_DEVICE_CPU 1
+#define ARROW_DEVICE_ROCM 10
+struct ArrowDeviceArray {
+  struct ArrowArray array;
+  int64_t device_id;
+  int32_t device_type;
+  void* sync_event;
+  int64_t reserved[3];
+};
+#endif
 }

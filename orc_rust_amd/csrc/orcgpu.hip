@@ -50,8 +50,11 @@
 #include "device/writer_nested.hip"
 #include "device/col_stats.hip"
 #include "device/bloom_build.hip"
+#include "device/export_kernels.hip"
 
 #include "arrow_c_data.h"
+#include "../../include/orcgpu_dlpack.h"
+#include "device_hold.h"
 
 namespace {
 
@@ -469,6 +472,13 @@ struct orcgpu_result {
   size_t arena_used[kMaxLanes] = {0, 0, 0, 0}, chars_used[kMaxLanes] = {0, 0, 0, 0};  // bytes of the last decode
   HostMirror* mirror = nullptr;  // filled by orcgpu_result_fetch
   bool mirror_valid = false;
+  uint64_t d2h_bytes = 0;        // column-buffer bytes the last orcgpu_result_fetch_async moved (sub-results included)
+  // device-resident exports (orcgpu_export_device.inc): who else holds the result (device_hold.h; null until the first export or
+  // until a device-output reader adopts it), and "its last writer is enqueued" on the decode stream
+  orcgpu_hold::Hold* hold = nullptr;
+  hipEvent_t dev_ready = nullptr;
+  bool dev_ready_recorded = false;
+  bool was_exported = false;     // batches of the current contents have been handed out: consumers' work may be in flight on any stream
   // row selection: once orcgpu_result_select has run, batch b is rows [sel[b].start, sel[b].start + sel[b].len)
   bool selected = false;
   std::vector<SelBatch> sel;
@@ -1217,6 +1227,7 @@ struct SummaryLayout {
 #include "orcgpu_ext.inc"
 #include "orcgpu_decode.inc"
 #include "orcgpu_export.inc"
+#include "orcgpu_export_device.inc"
 #include "orcgpu_select.inc"
 #include "orcgpu_filter.inc"
 #include "orcgpu_reader.inc"

@@ -1140,6 +1140,15 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     orcgpu_staged* s = stripes[si];
     if (!s || s->ctx != ctx) return ORCGPU_INVALID_ARGUMENT;
     orcgpu_result* r = results[si];
+    if (r && r->hold && orcgpu_hold::hold_exported(r->hold)) {
+      set_err(ctx, "a result that exported device batches still view cannot be decoded into again");
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    // (its exports are released -- on the host: what their consumers enqueued on streams of their own may still read the buffers)
+    if (r && r->was_exported) {
+      HIP_TRY(ctx, hipDeviceSynchronize());
+      r->was_exported = false;
+    }
     if (!r) {
       r = new orcgpu_result();
       results[si] = r;
@@ -1167,6 +1176,7 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     r->err_batch = r->err_col = 0;
     if (r->mirror) r->mirror->wait();  // (a copy of the previous contents still on its way to the host reads these buffers)
     r->mirror_valid = false;
+    r->dev_ready_recorded = false;
     r->selected = false;
     r->sel.clear();
     r->filtered = false;

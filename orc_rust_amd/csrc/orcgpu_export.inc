@@ -7,6 +7,8 @@
 
 namespace {
 
+void result_destroy(void* result);  // (orcgpu_export_device.inc)
+
 uint64_t batch_rows(const orcgpu_result* r, uint32_t b) {
   if (r->selected) return r->sel[b].len;
   return std::min<uint64_t>(r->batch, r->n_rows - (uint64_t)b * r->batch);
@@ -93,6 +95,7 @@ int orcgpu_result_fetch_async(orcgpu_ctx* ctx, orcgpu_result* r) {
   if (!m->done) HIP_TRY(ctx, hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
   HIP_TRY(ctx, hipEventRecord(ctx->d2h_gate, ctx->stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h_stream, ctx->d2h_gate, 0));
+  r->d2h_bytes = 0;
   auto pull = [&](uint8_t*& host, size_t& cap, const DevBuf& dev, size_t used) -> int {
     if (!used) return ORCGPU_OK;
     if (cap < used) {
@@ -108,6 +111,7 @@ int orcgpu_result_fetch_async(orcgpu_ctx* ctx, orcgpu_result* r) {
     // (one copy per arena: cutting it into pieces -- so that the small copies of the decode running beside it would wait less
     // behind it -- changed nothing at 32 MiB and cost throughput below 8 MiB: measured, MI355X)
     HIP_TRY(ctx, hipMemcpyAsync(host, dev.p, used, hipMemcpyDeviceToHost, ctx->d2h_stream));
+    r->d2h_bytes += used;
     return ORCGPU_OK;
   };
   if (r->filtered) {  // a row filter's kept rows live in an arena of their own: nothing else crosses the link
@@ -129,6 +133,7 @@ int orcgpu_result_fetch_async(orcgpu_ctx* ctx, orcgpu_result* r) {
   for (auto* sub : r->subs) {  // the elements of List / Map columns
     int rc = orcgpu_result_fetch_async(ctx, sub);
     if (rc) return rc;
+    r->d2h_bytes += sub->d2h_bytes;
   }
   return ORCGPU_OK;
 }
@@ -152,16 +157,11 @@ int orcgpu_result_fetch(orcgpu_ctx* ctx, orcgpu_result* r) {
   return ORCGPU_OK;
 }
 
+// (a result that device-resident batches still view only loses its owner here: the last of them frees it, device_hold.h)
 void orcgpu_result_free(orcgpu_result* r) {
   if (!r) return;
-  for (auto* sub : r->subs) orcgpu_result_free(sub);
-  if (r->mirror) r->mirror->unref();
-  for (auto& a : r->arena) a.release();
-  for (auto& a : r->chars) a.release();
-  r->sel_arena.release();
-  r->filt_arena.release();
-  r->filt_tmp.release();
-  delete r;
+  if (r->hold) orcgpu_hold::hold_owner_done(r->hold, false);
+  else result_destroy(r);
 }
 
 int orcgpu_result_status(const orcgpu_result* r, uint32_t* batch, uint32_t* column) {

@@ -14,6 +14,10 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   if (rows_seen) *rows_seen = 0;
   if (rows_kept) *rows_kept = 0;
   if (r->status) return r->status;  // a failed decode is left as it is
+  if (r->hold && orcgpu_hold::hold_exported(r->hold)) {
+    set_err(ctx, "a result that exported device batches still view cannot be filtered");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (r->filtered) {
     set_err(ctx, "a row filter has already been applied to this result");
     return ORCGPU_INVALID_ARGUMENT;
@@ -242,6 +246,7 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   r->sel.clear();
   r->filtered = true;
   r->mirror_valid = false;
+  r->dev_ready_recorded = false;
   if (status) {
     r->status = status;
     r->err_batch = err_batch;

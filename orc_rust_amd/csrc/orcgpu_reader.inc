@@ -319,6 +319,16 @@ struct orcgpu_reader {
   std::vector<orcgpu_host::PredNode> filter_nodes;
   orcgpu_host::FilterPlan filter_plan;
   std::atomic<uint64_t> filter_seen{0}, filter_kept{0};
+  // ---- device output (orcgpu_reader_set_device_output): the batches are views of the results' HBM, handed out by
+  // orcgpu_reader_next_batch_device; no copy back is started.  A result the caller is done with goes to `home` instead of `spare`
+  // -- at once, or when the last exported batch or tensor that views it is released (device_hold.h) ----
+  bool device_output = false;
+  std::shared_ptr<orcgpu_hold::Home> home;
+  uint64_t d2h_bytes = 0;                     // column-buffer bytes copied to the host so far (orcgpu_reader_d2h_bytes)
+  bool current_counted = false;               // ... those of `current` are in it
+  bool device_checked = false, device_refused = false;  // the projection has been looked at for nested columns; it has one
+  std::string device_refused_name;
+  const char* device_refused_kind = "";
 };
 
 static int arrow_code_of_format(const char* f, uint32_t* prec, uint32_t* scale);
@@ -808,6 +818,29 @@ int reader_compile_filter(orcgpu_reader* rd) {
   return rc;
 }
 
+// A result the caller is done with, to decode a later stripe into (rd->m is held by a reader that reads ahead)
+orcgpu_result* reader_take_spare(orcgpu_reader* rd) {
+  // (a result that comes home was viewed by batches and tensors whose consumers released them on the HOST: work they enqueued on
+  // streams of their own may not have run yet, and nothing orders the decode stream behind it -- so decode_staged_once waits for
+  // the device before it writes into a result that has been exported)
+  if (rd->device_output) return static_cast<orcgpu_result*>(orcgpu_hold::home_take(*rd->home));
+  if (rd->spare.empty()) return nullptr;
+  orcgpu_result* r = rd->spare.back();
+  rd->spare.pop_back();
+  return r;
+}
+void reader_give_spare(orcgpu_reader* rd, orcgpu_result* r) {
+  if (rd->device_output && r->hold) orcgpu_hold::hold_owner_done(r->hold, true);  // (now, or when its last exported batch is released)
+  else rd->spare.push_back(r);
+}
+// A decoded stripe on its way to the caller: the host path starts its copy back, the device path adopts it (its references are
+// counted from here on, its home is this reader) and marks where on the decode stream it is complete
+int reader_result_decoded(orcgpu_reader* rd, orcgpu_result* r, bool start_copy) {
+  if (!rd->device_output) return start_copy ? orcgpu_result_fetch_async(rd->ctx, r) : ORCGPU_OK;
+  if (!r->hold) r->hold = orcgpu_hold::hold_new(r, result_destroy, rd->home);
+  return result_mark_ready(rd->ctx, r);
+}
+
 // prefetch = 0: both steps in the caller's thread (the pieces of a stripe in one decode call).  ORCGPU_END_OF_FILE = the file has no more rows to give
 int reader_advance_stripe(orcgpu_reader* rd) {
   orcgpu_ctx* ctx = rd->ctx;
@@ -829,11 +862,7 @@ int reader_advance_stripe(orcgpu_reader* rd) {
       for (size_t k = before; k < got.size(); k++) staged_bytes += orcgpu_staged_bytes(got[k]);
     } while (!rc && rd->next_stripe < rd->stripe_order.size() && got.size() < 32 && staged_bytes < (64u << 20));
     std::vector<orcgpu_result*> res(got.size(), nullptr);
-    for (auto& r : res)  // (results the caller is done with are decoded into again: their arenas and pinned host copies stay)
-      if (!rd->spare.empty()) {
-        r = rd->spare.back();
-        rd->spare.pop_back();
-      }
+    for (auto& r : res) r = reader_take_spare(rd);  // (results the caller is done with are decoded into again: their arenas and pinned host copies stay)
     const double t2 = now();
     if (!rc && !got.empty()) rc = orcgpu_decode_staged(ctx, got.data(), (uint32_t)got.size(), res.data());
     const double t3 = now();
@@ -842,6 +871,7 @@ int reader_advance_stripe(orcgpu_reader* rd) {
       if (!rc && got[k]->has_sel) rc = result_select_batches(ctx, res[k], got[k]->sel);  // (the stripe's share of the selection)
       if (!rc && rd->has_filter) rc = reader_filter_result(rd, res[k]);
       orcgpu_staged_free(got[k]);
+      if (!rc) rc = reader_result_decoded(rd, res[k], false);  // (the host path copies back when the first batch is asked for)
     }
     if (host_prof)
       fprintf(stderr, "[orcgpu] reader: metadata %.2f ms, staging %zu pieces (%.1f MB) %.2f ms, decode %.2f ms, selection %.2f ms\n", t1 - t0,
@@ -853,10 +883,11 @@ int reader_advance_stripe(orcgpu_reader* rd) {
     }
     for (auto* r : res) rd->serial_q.push_back(r);
   }
-  if (rd->current) rd->spare.push_back(rd->current);
+  if (rd->current) reader_give_spare(rd, rd->current);
   rd->current = rd->serial_q.front();
   rd->serial_q.pop_front();
   rd->next_batch = 0;
+  rd->current_counted = false;
   return ORCGPU_OK;
 }
 
@@ -936,12 +967,7 @@ void reader_decoder(orcgpu_reader* rd) {
         group_bytes += orcgpu_staged_bytes(rd->staged_q.front());
         group.push_back(rd->staged_q.front());
         rd->staged_q.pop_front();
-        orcgpu_result* r = nullptr;
-        if (!rd->spare.empty()) {  // (a result the caller has given back is decoded into again: no allocations in steady state)
-          r = rd->spare.back();
-          rd->spare.pop_back();
-        }
-        results.push_back(r);
+        results.push_back(reader_take_spare(rd));  // (a result the caller has given back is decoded into again: no allocations in steady state)
       }
     }
     rd->cv_staged_room.notify_all();
@@ -951,7 +977,7 @@ void reader_decoder(orcgpu_reader* rd) {
       if (!rc && group[k]->has_sel) rc = result_select_batches(ctx, results[k], group[k]->sel);  // (the stripe's share of the selection)
       if (!rc && rd->has_filter) rc = reader_filter_result(rd, results[k]);  // (before the copy back is started: only the kept rows cross the link)
       orcgpu_staged_free(group[k]);
-      if (!rc) rc = orcgpu_result_fetch_async(ctx, results[k]);
+      if (!rc) rc = reader_result_decoded(rd, results[k], true);
     }
     if (rc) {
       err = ctx->err;
@@ -1039,6 +1065,9 @@ void orcgpu_reader_close(orcgpu_reader* rd) {
   for (auto* r : rd->serial_q) orcgpu_result_free(r);
   for (auto* r : rd->spare) orcgpu_result_free(r);
   rd->spare.clear();
+  // (results that exported device batches still view are freed by the last of them: nothing comes home from here on)
+  if (rd->home)
+    for (void* r : orcgpu_hold::home_close(*rd->home)) orcgpu_result_free(static_cast<orcgpu_result*>(r));
   delete rd;
 }
 int orcgpu_reader_set_predicate(orcgpu_reader* rd, const orcgpu_predicate_node* nodes, uint32_t n_nodes) {
@@ -1218,10 +1247,32 @@ int orcgpu_index_entry(const orcgpu_column* column, int has_present, int compres
 
 // ArrowReader::next (arrow_reader.rs:333-346): 0 = a batch was exported, ORCGPU_END_OF_FILE = no more batches, else an error code
 // (the end has a code of its own: the status of a failing batch may be any OrcError, ORCGPU_IO_ERROR = 1 included)
-int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowSchema* out_schema) {
-  if (!rd || !out_array || !out_schema) return ORCGPU_INVALID_ARGUMENT;
+// (out_array: the host path; out_device: the device path -- the reader is in one mode or the other, and the wrong call changes nothing)
+static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowDeviceArray* out_device, struct ArrowSchema* out_schema) {
+  if (!rd || (!out_array && !out_device) || !out_schema) return ORCGPU_INVALID_ARGUMENT;
+  if (rd->device_output != (out_device != nullptr)) {
+    set_err(rd->ctx, rd->device_output ? "this reader hands out device batches (orcgpu_reader_set_device_output): call orcgpu_reader_next_batch_device"
+                                       : "orcgpu_reader_next_batch_device needs orcgpu_reader_set_device_output before the first batch");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   int rc = orcgpu_host::reader_build(rd);
   if (rc) return rc;
+  if (rd->device_output && !rd->stripe_order.empty() && !rd->device_checked) {
+    // flat schemas only: a nested root column is refused before anything of the file is read (a file without stripes has no first
+    // batch to fail: it ends as on the host path).  Checked once; a refusal is final
+    rd->device_checked = true;
+    for (size_t k = 0, root = 0; k < rd->col_ids.size() && !rd->device_refused; k++) {
+      if (rd->col_parent[k]) continue;
+      const std::string& name = rd->col_names[root++];
+      const int kind = rd->md.types[rd->col_ids[k]].kind;
+      if (kind == ORCGPU_T_STRUCT || kind == ORCGPU_T_LIST || kind == ORCGPU_T_MAP || kind == ORCGPU_T_UNION) {
+        rd->device_refused = true;
+        rd->device_refused_name = name;
+        rd->device_refused_kind = kind == ORCGPU_T_STRUCT ? "Struct" : (kind == ORCGPU_T_LIST ? "List" : (kind == ORCGPU_T_MAP ? "Map" : "Union"));
+      }
+    }
+  }
+  if (rd->device_refused) return refuse_nested(rd->ctx, rd->device_refused_name, rd->device_refused_kind);
   if (rd->filter_failed) return ORCGPU_END_OF_FILE;  // (the filter was refused by the call before: the iterator has ended)
   if (rd->has_filter && !rd->filter_ready) {
     rc = orcgpu_host::reader_compile_filter(rd);
@@ -1246,12 +1297,18 @@ int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, st
       }
       if (rd->next_batch < orcgpu_result_batches(rd->current)) {
         // (the exported schema owns copies of the column names: it may outlive the reader)
-        return export_batch_named(rd->ctx, rd->current, rd->next_batch++, out_array, out_schema, &rd->col_names);
+        if (out_device) return export_batch_device_named(rd->ctx, rd->current, rd->next_batch++, out_device, out_schema, &rd->col_names);
+        rc = export_batch_named(rd->ctx, rd->current, rd->next_batch++, out_array, out_schema, &rd->col_names);
+        if (!rd->current_counted) {  // (the stripe's copy back has been started by now, by the worker or by this export)
+          rd->d2h_bytes += rd->current->d2h_bytes;
+          rd->current_counted = true;
+        }
+        return rc;
       }
       {
         // done with this stripe: a later one is decoded into its buffers (by the worker, or by this thread when there is none)
         std::lock_guard<std::mutex> g(rd->m);
-        rd->spare.push_back(rd->current);
+        orcgpu_host::reader_give_spare(rd, rd->current);
       }
       rd->current = nullptr;
     }
@@ -1287,7 +1344,33 @@ int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, st
     }
     rd->current = item.res;
     rd->next_batch = 0;
+    rd->current_counted = false;
   }
+}
+
+int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowSchema* out_schema) {
+  if (!out_array) return ORCGPU_INVALID_ARGUMENT;
+  return reader_next(rd, out_array, nullptr, out_schema);
+}
+int orcgpu_reader_next_batch_device(orcgpu_reader* rd, struct ArrowDeviceArray* out_array, struct ArrowSchema* out_schema) {
+  if (!out_array) return ORCGPU_INVALID_ARGUMENT;
+  return reader_next(rd, nullptr, out_array, out_schema);
+}
+int orcgpu_reader_set_device_output(orcgpu_reader* rd, int on) {
+  if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
+  rd->device_output = on != 0;
+  if (rd->device_output && !rd->home) rd->home = std::make_shared<orcgpu_hold::Home>();
+  return ORCGPU_OK;
+}
+int orcgpu_reader_reads_ahead(orcgpu_reader* rd) {
+  if (!rd) return 0;
+  std::lock_guard<std::mutex> g(rd->m);
+  return rd->worker_started && !rd->worker_done && !rd->stop ? 1 : 0;
+}
+int orcgpu_reader_d2h_bytes(const orcgpu_reader* rd, uint64_t* bytes) {
+  if (!rd || !bytes) return ORCGPU_INVALID_ARGUMENT;
+  *bytes = rd->d2h_bytes;
+  return ORCGPU_OK;
 }
 
 }  // extern "C"

@@ -9,6 +9,10 @@ int result_select(orcgpu_ctx* ctx, orcgpu_result* r, const std::vector<RowSel>& 
 }
 // ... with the batches given as row ranges of the result (each at most `batch` rows, inside the result's rows)
 int result_select_batches(orcgpu_ctx* ctx, orcgpu_result* r, std::vector<SelBatch> batches) {
+  if (r->hold && orcgpu_hold::hold_exported(r->hold)) {
+    set_err(ctx, "a result that exported device batches still view cannot be selected on");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (r->selected) {
     set_err(ctx, "a row selection has already been applied to this result");
     return ORCGPU_INVALID_ARGUMENT;
@@ -108,6 +112,7 @@ int result_select_batches(orcgpu_ctx* ctx, orcgpu_result* r, std::vector<SelBatc
   r->n_batches = nb;
   r->selected = true;
   r->mirror_valid = false;
+  r->dev_ready_recorded = false;
   return ORCGPU_OK;
 }
 
