@@ -178,6 +178,8 @@ int orcgpu_abi_version(void);
 /* ---- staging: host stream bytes -> HBM --------------------------------------------------------- */
 /* Copies every stream of the stripe into one HBM arena (taken from a pool) and scans the 3-byte chunk headers
  * (compression.rs:113-123, :244-267; Zstandard: also the frame / block headers) on the host while the bytes are at hand.
+ * From that scan every compressed stream gets its part of the block decompressors' tables (chunk, block and item descriptors,
+ * its blocks ordered by sequence count, the workspace it needs), relative to the stream: a decode call copies and rebases them.
  * The copy is a pipeline: 16 MiB pieces go through two pinned buffers, filled by a few host threads while the previous
  * piece is on its way (hipMemcpyAsync on a copy stream).  The call does NOT wait for the last piece: decodes wait for
  * it on the device, so staging stripe k + 1 overlaps decoding stripe k (the analogue of the reference's
@@ -743,6 +745,24 @@ typedef struct orcgpu_lane_stats {
   float literals_kernel_ms;
 } orcgpu_lane_stats;
 int orcgpu_last_lane_stats(const orcgpu_ctx* ctx, uint32_t lane, orcgpu_lane_stats* out);
+
+/* The HOST time of lane `lane` in the last orcgpu_decode_staged call on `ctx`, in microseconds of the lane's own thread, part
+ * by part in the order they run (us[0..n) receives the first n):
+ *   0 lanes     the call's entry to the lane's start: results reset, columns dealt out to the lanes
+ *   1 columns   the lane's columns planned (streams, jobs, result offsets)
+ *   2 chunks    plan_decompress: the chunk / block tables counted, ordered and given their workspace
+ *   3 layout    job layout, workspace and result buffers, the wait for the lane's previous call, the summary's host mirror
+ *               (0 .. 3 together are orcgpu_lane_stats::start_ms)
+ *   4 fill      the chunk / stream / block / item tables written to pinned memory
+ *   5 upload    the copies of the summary and of those tables to the device enqueued
+ *   6 gate      waiting for the other lanes to enqueue their Zstandard table kernels
+ *   7 decomp    the decompression launches themselves (what launch_decompress took beyond 4 .. 6)
+ *   8 enqueue   every launch behind them
+ *   9 wait      the last launch to the end of the lane's work on the device (the final synchronise)
+ *  10 summary   the summary read: errors resolved per column, null counts, what the next call needs
+ * Returns ORCGPU_INVALID_ARGUMENT for a lane the last call did not run. */
+#define ORCGPU_N_HOST_PARTS 11
+int orcgpu_last_lane_host_us(const orcgpu_ctx* ctx, uint32_t lane, float* us, uint32_t n);
 
 #ifdef __cplusplus
 }

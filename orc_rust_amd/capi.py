@@ -20,7 +20,7 @@ EXPORTS = [
     "orcgpu_open", "orcgpu_close", "orcgpu_last_error", "orcgpu_version", "orcgpu_abi_version", "orcgpu_stage_stripe", "orcgpu_staged_free",
     "orcgpu_staged_bytes", "orcgpu_decode_staged", "orcgpu_stripe_decode", "orcgpu_result_free", "orcgpu_result_status",
     "orcgpu_result_rows", "orcgpu_result_batches", "orcgpu_result_arrow_bytes", "orcgpu_result_batch_view",
-    "orcgpu_result_copy_batch", "orcgpu_result_fetch", "orcgpu_result_fetch_async", "orcgpu_result_select", "orcgpu_selection_batches", "orcgpu_timezone_offsets", "orcgpu_result_export_batch", "orcgpu_last_timing", "orcgpu_last_phase_ms", "orcgpu_last_lane_stats", "orcgpu_encode_rle2_i64", "orcgpu_encode_rle2", "orcgpu_encode_byte_rle", "orcgpu_encode_boolean", "orcgpu_encode_column", "orcgpu_encode_fetch",
+    "orcgpu_result_copy_batch", "orcgpu_result_fetch", "orcgpu_result_fetch_async", "orcgpu_result_select", "orcgpu_selection_batches", "orcgpu_timezone_offsets", "orcgpu_result_export_batch", "orcgpu_last_timing", "orcgpu_last_phase_ms", "orcgpu_last_lane_stats", "orcgpu_last_lane_host_us", "orcgpu_encode_rle2_i64", "orcgpu_encode_rle2", "orcgpu_encode_byte_rle", "orcgpu_encode_boolean", "orcgpu_encode_column", "orcgpu_encode_fetch",
     "orcgpu_reader_open_file", "orcgpu_reader_open_bytes", "orcgpu_reader_close", "orcgpu_reader_set_batch_size",
     "orcgpu_reader_set_projection", "orcgpu_reader_set_projection_roots", "orcgpu_reader_set_schema", "orcgpu_reader_set_byte_range", "orcgpu_reader_set_shard", "orcgpu_shard_columns", "orcgpu_reader_column_weight", "orcgpu_reader_set_timestamp_precision", "orcgpu_reader_set_row_selection", "orcgpu_reader_set_prefetch",
     "orcgpu_reader_set_row_group_pruning", "orcgpu_reader_row_groups", "orcgpu_index_entry", "orcgpu_reader_set_predicate",
@@ -212,6 +212,7 @@ def load():
     L.orcgpu_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     L.orcgpu_last_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]
     L.orcgpu_last_lane_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LaneStats)]
+    L.orcgpu_last_lane_host_us.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32]
     L.orcgpu_encode_rle2_i64.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.orcgpu_encode_rle2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.orcgpu_encode_byte_rle.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -458,6 +459,17 @@ class Context:
             k += 1
             if k >= st.n_lanes:
                 break
+        return out
+
+    HOST_PARTS = ("lanes", "columns", "chunks", "layout", "fill", "upload", "gate", "decomp", "enqueue", "wait", "summary")
+
+    def lane_host_us(self):
+        """Every column lane's host time in the last decode call, part by part in microseconds (orcgpu_last_lane_host_us):
+        [{lanes, columns, chunks, layout, fill, upload, gate, decomp, enqueue, wait, summary}], lane 0 first."""
+        out = []
+        a = (C.c_float * len(self.HOST_PARTS))()
+        while len(out) < 4 and self.L.orcgpu_last_lane_host_us(self.h, len(out), a, len(self.HOST_PARTS)) == OK:
+            out.append(dict(zip(self.HOST_PARTS, [float(x) for x in a])))
         return out
 
 

@@ -14,30 +14,7 @@
 #pragma once
 #include "rle_parse.h"
 
-struct ChunkDesc {
-  const uint8_t* src;   // compressed payload
-  uint8_t* dst;         // output slot
-  uint8_t* scratch;     // per-chunk scratch (zstd literals), may be null
-  uint32_t src_len;
-  uint32_t dst_cap;
-  uint32_t kind;        // 0 = original (copy), else ORCGPU_COMP_*
-  uint32_t stream;      // index into the per-stream tables
-  uint32_t out_len;     // written by the kernel
-  uint32_t status;      // 0 ok, else ORC_E_CODEC (Zstandard: preset by the host when the frame / block headers do not parse)
-  uint32_t first_item, n_items;  // Zstandard: the chunk's blocks in the ZItem table (lz_exec.h)
-  uint32_t diag;        // diagnostics: where a rejected chunk failed
-  uint32_t pad;
-};
-
-struct StreamDesc {
-  uint32_t first_chunk, n_chunks;
-  uint32_t len_idx;     // scalar receiving the plain length
-  uint32_t err_idx;     // scalar receiving a codec error flag
-  uint8_t* base;        // start of the stream's plain buffer
-  uint32_t framing_error;
-  uint32_t skip;        // a stream entered at a row group: bytes of its first chunk that belong to the rows before (the plain length
-                        // published is what lies behind them; the consumers start there)
-};
+#include "decomp_tables.h"  // ChunkDesc, StreamDesc, ZBlock, ZSeqHdr, ZItem: the tables the host fills
 
 __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 __device__ __forceinline__ void lds_order() {  // LDS accesses of one wavefront execute in order; this only pins the compiler

@@ -35,21 +35,7 @@
 #define LZX_SEQ_PACKED 0xffffffffu  // lz_exec_block's `soa`: the block's sequences are 8-byte records (zseq_pack)
 #define LZX_DEFERRED 0x57a7u  // ChunkDesc::diag of a chunk put off: the second launch (behind the entropy kernel) takes it
 
-struct ZItem {       // one block of a frame, in output order
-  uint32_t kind;     // 0 Raw_Block, 1 RLE_Block, 2 Compressed_Block
-  uint32_t flags;    // 1: first block of a frame (repeat offsets restart at 1, 4, 8; matches cannot reach before it)
-                     // 2: last block of a frame that states its content size (fcs)
-                     // 4: last block of a frame that carries a content checksum (ck_off)
-  uint32_t size;     // raw / rle: regenerated bytes
-  uint32_t src_off;  // raw: offset of the bytes in the payload; rle: the byte
-  uint32_t lit_kind; // compressed: 0 raw literals at payload[lit_off], 1 one repeated byte (lit_off), 2 decoded (ZBlock::lit_out)
-  uint32_t lit_off, litn, nseq;
-  uint32_t zblock;   // index of the ZBlock
-  uint32_t seq_packed;  // its sequences are 8-byte records (zseq_pack: one lane per block) instead of three arrays
-  uint64_t fcs;
-  uint32_t ck_off;   // flags & 4: the frame carries a content checksum; its four bytes lie here in the payload
-  uint32_t pad;
-};
+#include "decomp_tables.h"  // ZItem: one block of a frame, in output order
 
 template <int T>
 struct ExecLds {

@@ -21,26 +21,8 @@
 // the LZ77 copies executed, by lz_exec_kernel (lz_exec.h), one workgroup per chunk.
 #pragma once
 
-struct ZBlock {
-  const uint8_t* src;    // chunk payload in the staged arena
-  uint8_t* lit_out;      // decoded literals (lit_type >= 2): lit_regen bytes (+ 8 bytes of slack)
-  uint32_t* seq_out;     // three arrays of ((nseq + 3) & ~3) entries, one behind the other: offset values, match lengths, literal lengths
-  uint32_t chunk;        // index into the chunk table
-  uint32_t content_off, content_end;  // block content inside the payload
-  uint32_t lit_type, lit_streams, lit_hdr, lit_regen, lit_comp;
-  uint32_t nseq, seq_off;    // seq_off: offset of the byte behind Number_of_Sequences (the modes byte)
-  uint32_t huf_off, huf_end; // Huffman tree description: own, or (Treeless) the defining block's; end of that literals section
-  uint32_t tab_off[3];   // per table LL, OF, ML: offset of the modes byte of the block that defines it (own: seq_off)
-  uint32_t tab_end[3];   // ... and the end of that block
-  uint32_t pad[2];
-};
+#include "decomp_tables.h"  // ZBlock, ZSeqHdr
 
-struct ZSeqHdr {      // written by zstd_entropy_kernel (tables mode) per block with sequences
-  uint32_t bit_off;   // where the sequences' bit stream starts in the chunk payload
-  uint32_t logs;      // table logs: LL | OF << 8 | ML << 16
-  uint32_t status;    // nonzero: a table description is broken (the code zstd_entropy_kernel would report)
-  uint32_t pad;
-};
 // A sequence as zstd_seq_quads_kernel leaves it for the execution kernel: 8 bytes {offset value : 29, match length : 18, literal
 // length : 17}.  Match lengths end at 65 539 + 65 535, literal lengths at 65 536 + 65 535 (RFC 8878 3.1.1.3.2.1.1); an offset
 // value of 2^29 or more cannot be met by any chunk (a chunk header holds 23 bits of length, a plain chunk is bounded by the

@@ -95,18 +95,11 @@ struct Bump {
   }
 };
 
-struct ChunkInfo {
-  uint64_t src_off;  // offset of the chunk payload inside the stream
-  uint32_t len;
-  uint32_t original;
-  uint32_t plain_cap;  // bytes the chunk can expand to (exact for original and Snappy chunks, and for Zstandard frames that state their size)
-  int32_t zparse = -1; // Zstandard: index into StagedStream::zchunks
-};
-
 
 }  // namespace
 
 #include "orcgpu_zstd_host.inc"
+#include "orcgpu_decomp_plan.inc"
 #include "orcgpu_tz.inc"
 
 namespace {
@@ -117,6 +110,7 @@ struct StagedStream {
   uint64_t len;
   std::vector<ChunkInfo> chunks;  // only for compressed stripes
   std::vector<ZChunkParse> zchunks;  // Zstandard: frame / block headers of every compressed chunk
+  StreamTables tables;            // the stream's part of the decompressors' tables, built with the two above (scan_chunks): a decode call copies and rebases it
   uint32_t skip_bytes = 0, skip_values = 0, skip_bits = 0;  // entry point (orcgpu_stream): where in the plain bytes the decoder starts, values it drops, bits of a bit stream's first byte that come before
   std::vector<std::pair<uint32_t, uint32_t>> hints;  // verified run starts (orcgpu_stream::entries): (chunk index or ~0, byte in its plain bytes), the stream's start first
   bool framing_error = false;     // truncated chunk header / payload (compression.rs:253-261 panics)
@@ -250,6 +244,8 @@ struct orcgpu_ctx {
   orcgpu_lane_stats last_stats{};     // this lane's part of the last call (orcgpu_last_lane_stats)
   uint32_t last_n_lanes = 1;          // lane 0: lanes the last call ran
   double call_t0 = 0;                 // host clock (us) when the call that drives this lane was entered
+  float last_host_us[ORCGPU_N_HOST_PARTS] = {};  // this lane's host time in the last call, part by part (orcgpu_last_lane_host_us)
+  double hp_fill = 0, hp_upload = 0, hp_gate = 0;  // launch_decompress's own parts of it: table fill, uploads, the wait for the other lanes' table kernels
   // Zstandard at table scale, several lanes: a lane's sequences kernel takes every CU's LDS (three wavefronts of 52.5 KB); launched
   // before another lane's FSE table kernel (15 KB a wavefront) it keeps that one out until its own chains end -- the other lane then
   // starts 4 to 25 ms late (the "straggler" of round 4).  So every lane's table kernel first: a lane launches its sequences kernel
@@ -585,6 +581,7 @@ void scan_chunks(const uint8_t* ptr, uint64_t len_total, int compression, uint64
     p += 3 + (uint64_t)len;
   }
   st.framed_len = p;
+  build_stream_tables(st.chunks, st.zchunks, compression, st.off, ORC_E_CODEC, st.tables);
 }
 
 uint32_t type_width(int t) {

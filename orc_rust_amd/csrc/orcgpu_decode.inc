@@ -555,6 +555,8 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   ctx->kev_used[0] = ctx->kev_used[1] = false;
   ctx->lit_ev_used = false;
   HIP_TRY(ctx, hipMemcpyAsync(dsum, hs, SL.bytes, hipMemcpyHostToDevice, st));
+  const double ht_launch = hclock();  // (the waits for the stripes' bytes and the summary's copy are enqueued)
+  ctx->hp_fill = ctx->hp_upload = ctx->hp_gate = 0;
   rc = launch_decompress(ctx, P, DP, S, d_scalars, hs + SL.bytes, ctx->ev[6], ctx->ev[7], ctx->ev[4], ctx->ev[8]);
   const double ht_first = hclock();
   if (rc) return rc;
@@ -915,12 +917,13 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   if (getenv("ORCGPU_DEBUG") && DP.n_zitems) {
     fprintf(stderr, "[orcgpu] zstd plan: %u blocks, %u with sequences (%llu in all): %s\n", DP.n_zblocks, DP.n_zchains, (unsigned long long)DP.z_total_seq,
             DP.z_lanes ? "one lane per block" : "one wavefront per block");
-    // the chunks with the most sequences (what the entropy and execution stages last as long as)
+    // the chunks with the most sequences (what the entropy and execution stages last as long as), from the host's copy of the tables
+    const ChunkDesc* tc = reinterpret_cast<const ChunkDesc*>(hs + SL.bytes + DP.chunks_off);
+    const ZItem* ti = reinterpret_cast<const ZItem*>(hs + SL.bytes + DP.zitems_off);
     std::vector<std::pair<uint64_t, uint32_t>> top;
     for (uint32_t c = 0; c < DP.n_chunks; c++) {
       uint64_t ns = 0;
-      const uint32_t f = DP.chunk_first_item[c], e = c + 1 < DP.n_chunks ? DP.chunk_first_item[c + 1] : DP.n_zitems;
-      for (uint32_t k = f; k < e; k++) ns += DP.zitems[k].item->nseq;
+      for (uint32_t k = tc[c].first_item; k < tc[c].first_item + tc[c].n_items; k++) ns += ti[k].nseq;
       top.push_back({ns, c});
     }
     std::sort(top.rbegin(), top.rend());
@@ -930,9 +933,9 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       fprintf(stderr, "[orcgpu] zstd chunks: %zu; with >= 40k / 20k / 10k / 5k sequences: %zu / %zu / %zu / %zu\n", top.size(), h40, h20, h10, h5);
     }
     for (size_t k = 0; k < top.size() && k < 6; k++) {
-      const uint32_t c = top[k].second, f = DP.chunk_first_item[c], e = c + 1 < DP.n_chunks ? DP.chunk_first_item[c + 1] : DP.n_zitems;
+      const uint32_t c = top[k].second, f = tc[c].first_item, e = f + tc[c].n_items;
       uint32_t mxs = 0, lit = 0;
-      for (uint32_t q = f; q < e; q++) mxs = std::max(mxs, DP.zitems[q].item->nseq), lit += DP.zitems[q].item->lit_regen;
+      for (uint32_t q = f; q < e; q++) mxs = std::max(mxs, ti[q].nseq), lit += ti[q].litn;
       fprintf(stderr, "[orcgpu] zstd chunk %u: %u blocks, %llu sequences (largest block %u), %u literal bytes\n", c, e - f, (unsigned long long)top[k].first, mxs, lit);
     }
   }
@@ -999,15 +1002,18 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       for (auto& ds : P.decomp) {
         const int kind = ds.stripe->desc.compression;
         const uint64_t limit = std::max<uint64_t>(ds.stripe->desc.block_size, 1u << 22);
+        bool grown_here = false;
         for (auto& c : const_cast<StagedStream*>(ds.st)->chunks) {
           const bool grows = kind == ORCGPU_COMP_ZLIB || kind == ORCGPU_COMP_LZO ||
                              (kind == ORCGPU_COMP_ZSTD && c.zparse >= 0 && !ds.st->zchunks[c.zparse].size_known && !ds.st->zchunks[c.zparse].bad);
           if (!c.original && grows && hc[ci].status && c.plain_cap < limit) {
             c.plain_cap = (uint32_t)limit;
-            grown = true;
+            grown = grown_here = true;
           }
           ci++;
         }
+        // (the slots are part of the stream's tables: built again for the second run)
+        if (grown_here) build_stream_tables(ds.st->chunks, ds.st->zchunks, kind, ds.st->off, ORC_E_CODEC, const_cast<StagedStream*>(ds.st)->tables);
       }
       if (grown) return ORCGPU_RETRY_LARGER_SLOTS;
     }
@@ -1119,6 +1125,12 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
     }
   }
   if (host_prof) fprintf(stderr, "[orcgpu] lane %d host us: post %.1f  (call total %.1f)\n", ctx->lane_id, hclock() - ht_sync, hclock() - ht0);
+  {
+    // the lane's host time, part by part (orcgpu_last_lane_host_us)
+    const double parts[ORCGPU_N_HOST_PARTS] = {ctx->call_t0 > 0 ? ht0 - ctx->call_t0 : 0.0, ht_cols - ht0, ht_dp - ht_cols, ht_plan - ht_dp, ctx->hp_fill, ctx->hp_upload + (ht_launch - ht_plan),
+                                               ctx->hp_gate, (ht_first - ht_launch) - ctx->hp_fill - ctx->hp_upload - ctx->hp_gate, ht_enq - ht_first, ht_sync - ht_enq, hclock() - ht_sync};
+    for (int k = 0; k < ORCGPU_N_HOST_PARTS; k++) ctx->last_host_us[k] = (float)parts[k];
+  }
   return ORCGPU_OK;
 }
 
@@ -1202,8 +1214,7 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     for (uint32_t si = 0; si < n; si++)
       for (auto& st : stripes[si]->streams) {
         staged += st.len;
-        for (auto& zp : st.zchunks)
-          for (auto& it : zp.items) mx_all = std::max(mx_all, it.nseq);
+        mx_all = std::max(mx_all, st.tables.max_nseq);
       }
     if (staged >= (64ull << 20) && mx_all >= 16384) want_lanes = 2;
   }
@@ -1265,15 +1276,12 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
           for (; k < w.size(); k++)
             if (w[k].second == rid) break;
           if (k == w.size()) continue;
-          for (auto& zp : st.zchunks)
-            for (auto& it : zp.items) mx[k] = std::max(mx[k], it.nseq);
+          mx[k] = std::max(mx[k], st.tables.max_nseq);
           mxmax = std::max(mxmax, mx[k]);
         }
       uint64_t seq_all = 0;
       for (uint32_t si = 0; si < n; si++)
-        for (auto& st : stripes[si]->streams)
-          for (auto& zp : st.zchunks)
-            for (auto& it : zp.items) seq_all += it.nseq;
+        for (auto& st : stripes[si]->streams) seq_all += st.tables.total_seq;
       const uint64_t lanes_min = kZstdLanesMinSequences;
       // (one decision for the call: a lane whose own columns hold fewer sequences than the threshold took the other path -- SF 3: 32 against 22 ms)
       call_z = seq_all >= lanes_min ? 1 : 0;
@@ -1543,6 +1551,12 @@ extern "C" int orcgpu_last_phase_ms(const orcgpu_ctx* ctx, float* ms, uint32_t n
 extern "C" int orcgpu_last_lane_stats(const orcgpu_ctx* ctx, uint32_t lane, orcgpu_lane_stats* out) {
   if (!ctx || !out || lane >= ctx->last_n_lanes || lane >= (uint32_t)kMaxLanes || !ctx->lanes[lane]) return ORCGPU_INVALID_ARGUMENT;
   *out = ctx->lanes[lane]->last_stats;
+  return ORCGPU_OK;
+}
+
+extern "C" int orcgpu_last_lane_host_us(const orcgpu_ctx* ctx, uint32_t lane, float* us, uint32_t n) {
+  if (!ctx || !us || lane >= ctx->last_n_lanes || lane >= (uint32_t)kMaxLanes || !ctx->lanes[lane]) return ORCGPU_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n && k < ORCGPU_N_HOST_PARTS; k++) us[k] = ctx->lanes[lane]->last_host_us[k];
   return ORCGPU_OK;
 }
 

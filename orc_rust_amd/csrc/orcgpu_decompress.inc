@@ -1,35 +1,7 @@
 // orcgpu_decompress.inc -- chunk tables and launches of the block decompressors.
 namespace {
 
-struct ZBlockPlan {
-  uint32_t chunk;        // global chunk index
-  const ZItemH* item;
-  const ZChunkParse* zp;
-  uint64_t lit_off = ~0ull, seq_off = ~0ull;  // scratch offsets
-  uint32_t zblock = 0;   // index into the ZBlock table (compressed items)
-};
-
-// Indices [0, n) whose count(k) is not negative, by count descending and index ascending within a count: a counting sort (counts are
-// sequence counts of blocks / chunks: clamped to 2^18, what lies above shares the top bucket in index order)
-template <class F>
-std::vector<uint32_t> order_by_count_desc(uint32_t n, F count) {
-  constexpr uint32_t kBuckets = 1u << 18;
-  std::vector<uint32_t> key(n), at;
-  uint32_t mx = 0, live = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    const int64_t c = count(k);
-    key[k] = c < 0 ? 0xffffffffu : (uint32_t)std::min<int64_t>(c, kBuckets - 1);
-    if (c >= 0) mx = std::max(mx, key[k]), live++;
-  }
-  at.assign((size_t)mx + 2, 0);
-  for (uint32_t k = 0; k < n; k++)
-    if (key[k] != 0xffffffffu) at[mx - key[k] + 1]++;  // bucket 0 = the largest count
-  for (uint32_t b = 0; b <= mx; b++) at[b + 1] += at[b];
-  std::vector<uint32_t> out(live);
-  for (uint32_t k = 0; k < n; k++)
-    if (key[k] != 0xffffffffu) out[at[mx - key[k]]++] = k;
-  return out;
-}
+inline double host_us_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct DecompPlan {
   uint64_t table_bytes = 0;      // host/pinned bytes of the tables
@@ -46,87 +18,53 @@ struct DecompPlan {
   uint32_t n_zchains = 0;        // blocks that have sequences: ZBlocks [0, n_zchains) (most sequences first)
   uint64_t ztab_off = 0, zhdr_off = 0;  // z_lanes: 2560 bytes of table cells + a ZSeqHdr per chain
   uint64_t chunk_start_off = 0;  // per chunk: where its plain bytes start in its stream (written by the finalize kernel)
-  std::vector<ZBlockPlan> zitems;            // every block of every Zstandard chunk, chunk after chunk
-  std::vector<uint32_t> chunk_first_item;    // per chunk: first entry of zitems (n_items from the parse)
-  std::vector<uint64_t> chunk_rec_off;       // per chunk: scratch offset of its token records (Snappy / LZ4), ~0 if none
+  TableCounts counts;                    // the streams' tables added up, their orders merged (orcgpu_decomp_plan.inc)
+  std::vector<uint64_t> stream_scratch;  // per stream: scratch offset of its record / literal / sequence scratch, ~0 if it needs none
 };
 
+// The streams' tables were built when they were staged (StagedStream::tables): a call adds up their counts, merges their block
+// orders and hands out the bases; launch_decompress copies and rebases the entries.
 int plan_decompress(Plan& P, DecompPlan& DP) {
   if (P.decomp.empty()) return ORCGPU_OK;
+  const size_t ns = P.decomp.size();
   {
-    size_t n_items = 0, n_chunks = 0;
-    for (auto& ds : P.decomp) {
-      n_chunks += ds.st->chunks.size();
-      for (auto& zp : ds.st->zchunks) n_items += zp.items.size();
-    }
-    DP.zitems.reserve(n_items);
-    DP.chunk_first_item.reserve(n_chunks);
-    DP.chunk_rec_off.reserve(n_chunks);
+    std::vector<const StreamTables*> t(ns);
+    for (size_t k = 0; k < ns; k++) t[k] = &P.decomp[k].st->tables;
+    tables_count(t.data(), ns, DP.counts);
   }
-  for (auto& ds : P.decomp) {
-    int k = ds.stripe->desc.compression;
-    DP.n_streams++;
-    for (auto& c : ds.st->chunks) {
-      DP.chunk_first_item.push_back((uint32_t)DP.zitems.size());
-      // Snappy / LZ4: one 8-byte record per token (lz_parse.h).  A Snappy element takes two bytes or more; an LZ4 sequence
-      // (two records) three, but for the last one
-      uint64_t rec = ~0ull;
-      if (!c.original && k == ORCGPU_COMP_SNAPPY) rec = P.scratch.take(8ull * (c.len / 2 + 2), 16);
-      else if (!c.original && k == ORCGPU_COMP_LZ4) rec = P.scratch.take(8ull * (2 * (c.len / 3 + 1) + 2), 16);
-      // DEFLATE: literal bytes + 12-byte match records (inflate_parse.h); a match yields three bytes or more
-      else if (!c.original && k == ORCGPU_COMP_ZLIB) rec = P.scratch.take(((uint64_t)c.plain_cap + 16 + 15 & ~15ull) + 12ull * (c.plain_cap / 3 + 2) + 16, 16);
-      DP.chunk_rec_off.push_back(rec);
-      if (c.zparse >= 0) {
-        const ZChunkParse& zp = ds.st->zchunks[c.zparse];
-        for (auto& it : zp.items) {
-          ZBlockPlan bp;
-          bp.chunk = DP.n_chunks;
-          bp.item = &it;
-          bp.zp = &zp;
-          if (it.kind == 2) {
-            bp.zblock = DP.n_zblocks++;
-            if (it.lit_type >= 2) bp.lit_off = P.scratch.take((uint64_t)it.lit_regen + 16, 16);
-            if (it.nseq) bp.seq_off = P.scratch.take(12ull * ((it.nseq + 3u) & ~3u) + 16, 16);  // three arrays, each rounded up to 16 bytes
-          }
-          DP.zitems.push_back(bp);
-        }
-      }
-      DP.n_chunks++;
-    }
-  }
-  DP.n_zitems = (uint32_t)DP.zitems.size();
+  const TableCounts& C = DP.counts;
+  DP.n_streams = C.n_streams;
+  DP.n_chunks = C.n_chunks;
+  DP.n_zblocks = C.n_zblocks;
+  DP.n_zitems = C.n_zitems;
+  DP.n_zchains = C.n_zchains;
+  DP.z_total_seq = C.total_seq;
   {
     // Entropy jobs are taken in index order: the blocks with the most sequences (the longest serial chains) get the lowest
-    // indices, so they start when the kernel does and the short ones fill in around them.
-    // (keys sorted in place -- sequence count, then position --: a comparison that goes through the item pointers took 3.5 ms of
-    // the host for 20 000 blocks, in front of the first launch)
-    // (a counting sort -- sequence count descending, position ascending within a count --: std::sort over 20 000 keys was most of
-    // the millisecond the chunk tables cost the host in front of a lane's first launch)
-    std::vector<uint32_t> order = order_by_count_desc(DP.n_zitems, [&](uint32_t k) -> int64_t { return DP.zitems[k].item->kind == 2 ? (int64_t)DP.zitems[k].item->nseq : -1; });
-    for (uint32_t r = 0; r < order.size(); r++) DP.zitems[order[r]].zblock = r;
+    // indices, so they start when the kernel does and the short ones fill in around them (the streams carry their blocks in that
+    // order: the call's order is their merge, TableCounts::zb_at).
     // One lane per block instead of one wavefront (zstd_lanes.h) when the call is a throughput matter: the wavefront-per-block
     // stage takes about 0.1 ns of the whole chip per sequence, a chain on its own lane about 200 ns per sequence whatever
     // runs beside it.  ORCGPU_ZSTD_LANES=0 / 1 forces either (tests run both).
-    uint64_t total_seq = 0, longest = 0;
-    for (uint32_t r = 0; r < order.size(); r++) {
-      const uint64_t ns = DP.zitems[order[r]].item->nseq;
-      total_seq += ns;
-      longest = std::max(longest, ns);
-      if (ns) DP.n_zchains++;
-    }
     const char* force = getenv("ORCGPU_ZSTD_LANES");  // (read per call: the tests switch it between calls)
     const uint64_t min_seq = kZstdLanesMinSequences;
-    DP.z_lanes = DP.n_zchains && (force ? atoi(force) != 0 : (P.call_z_lanes >= 0 ? P.call_z_lanes != 0 : total_seq >= min_seq));
+    DP.z_lanes = DP.n_zchains && (force ? atoi(force) != 0 : (P.call_z_lanes >= 0 ? P.call_z_lanes != 0 : C.total_seq >= min_seq));
     // the literals as a kernel of their own (a third of the LDS: three times the wavefronts) in that mode.  Not with one wavefront
     // per block: the execution kernel then runs BESIDE the entropy kernel and needs a block's literals first -- behind a literals
     // kernel that fills the machine its workgroups only wait (SF 12.5: 90 -> 135 ms).
     DP.z_split_literals = DP.z_lanes;
-    DP.z_total_seq = total_seq;
-    (void)longest;
-    if (DP.z_lanes) {
-      DP.ztab_off = P.scratch.take((uint64_t)DP.n_zchains * ZL_CELLS * 2 + 16, 16);
-      DP.zhdr_off = P.scratch.take((uint64_t)DP.n_zchains * sizeof(ZSeqHdr) + 16, 16);
-    }
+  }
+  // every stream's record, literal and sequence scratch, laid out when it was staged: 8 bytes per sequence when they go one lane per
+  // block (packed records), 12 when one wavefront decodes a block (three arrays)
+  DP.stream_scratch.assign(ns, ~0ull);
+  const uint32_t seq_bytes = DP.z_lanes ? kSeqBytesPacked : kSeqBytesArrays;
+  for (size_t k = 0; k < ns; k++) {
+    const uint64_t need = P.decomp[k].st->tables.scratch_bytes(seq_bytes);
+    if (need) DP.stream_scratch[k] = P.scratch.take(need, 16);
+  }
+  if (DP.z_lanes) {
+    DP.ztab_off = P.scratch.take((uint64_t)DP.n_zchains * ZL_CELLS * 2 + 16, 16);
+    DP.zhdr_off = P.scratch.take((uint64_t)DP.n_zchains * sizeof(ZSeqHdr) + 16, 16);
   }
   if (DP.n_zblocks) DP.zdump_off = P.scratch.take(1024 * 64 * 4);
   DP.zstatus_off = P.scratch.take(8ull * DP.n_zblocks + 16);  // two jobs per block
@@ -199,12 +137,14 @@ static int launch_chunk_decoders(orcgpu_ctx* ctx, hipStream_t st, ChunkDesc* d_c
       // (the other lanes' table kernels first -- in front of this lane's sequences kernel AND its literals kernel, which fills what
       // LDS the sequences kernel leaves: see orcgpu_ctx::tables_gate.  Their host threads run beside this one: wait -- bounded --
       // until each has enqueued its kernel, then let the stream wait for it)
+      const double t_gate = host_us_now();
       for (int k = 0; k < ctx->n_gate_peers; k++) {
         orcgpu_ctx* peer = ctx->gate_peers[k];
         int g = 0;
         for (int spins = 0; spins < 100000 && !(g = peer->tables_gate.load(std::memory_order_acquire)); spins++) std::this_thread::yield();
         if (g == 1) HIP_TRY(ctx, hipStreamWaitEvent(st, peer->ev[7], 0));
       }
+      ctx->hp_gate += host_us_now() - t_gate;
       if (tables_ev) HIP_TRY(ctx, hipEventRecord(ctx->ev[9], st));  // (the sequences kernel's span starts here: behind the waits)
     }
     if (n_zblocks && lit_aside) HIP_TRY(ctx, hipEventRecord(ctx->aux_ev[0], st));  // (the status words are set, the tables built)
@@ -296,143 +236,41 @@ int launch_decompress(orcgpu_ctx* ctx, Plan& P, DecompPlan& DP, uint8_t* S, uint
     stage1 = nullptr;
   }
   hipStream_t st = ctx->stream;
+  const double t_fill = host_us_now();
   ChunkDesc* hc = reinterpret_cast<ChunkDesc*>(host_blob + DP.chunks_off);
   StreamDesc* hstr = reinterpret_cast<StreamDesc*>(host_blob + DP.streams_off);
   ZBlock* hzb = reinterpret_cast<ZBlock*>(host_blob + DP.zblocks_off);
   ZItem* hzi = reinterpret_cast<ZItem*>(host_blob + DP.zitems_off);
-  // (every stream's descriptors are independent of the others' once its first chunk index is known: at table scale -- tens of
-  // thousands of blocks, 2 ms of host time in front of the first launch -- four threads fill them)
-  auto fill_stream = [&](uint32_t si, uint32_t ci) {
-    auto& ds = P.decomp[si];
-    StreamDesc& sd = hstr[si];
-    sd.first_chunk = ci;
-    sd.n_chunks = (uint32_t)ds.st->chunks.size();
-    sd.len_idx = ds.len_idx;
-    sd.err_idx = ds.err_idx;
-    sd.base = ds.result_index >= 0 ? P.results[ds.result_index]->arena[ctx->lane_id].p + ds.result_off : S + ds.scratch_off;
-    sd.framing_error = ds.st->framing_error ? 1 : 0;
-    sd.skip = ds.st->skip_bytes;
-    uint64_t slot = 0;
-    for (auto& c : ds.st->chunks) {
-      ChunkDesc& cd = hc[ci];
-      cd.src = ds.stripe->dev + ds.st->off + c.src_off;
-      cd.dst = sd.base + slot;
-      cd.scratch = DP.chunk_rec_off[ci] != ~0ull ? S + DP.chunk_rec_off[ci] : nullptr;
-      cd.src_len = c.len;
-      cd.dst_cap = c.plain_cap;
-      cd.kind = c.original ? 0u : (uint32_t)ds.stripe->desc.compression;
-      cd.stream = si;
-      cd.out_len = 0;
-      cd.status = 0;
-      cd.first_item = DP.chunk_first_item[ci];
-      cd.n_items = 0;
-      cd.diag = 0;
-      cd.pad = 0;
-      if (c.zparse >= 0) {
-        const ZChunkParse& zp = ds.st->zchunks[c.zparse];
-        cd.n_items = (uint32_t)zp.items.size();
-        if (zp.bad) cd.status = ORC_E_CODEC;
-        // the chunk's blocks
-        for (uint32_t k = 0; k < cd.n_items; k++) {
-          const ZBlockPlan& bp = DP.zitems[cd.first_item + k];
-          const ZItemH& ih = *bp.item;
-          ZItem& zi = hzi[cd.first_item + k];
-          memset(&zi, 0, sizeof(zi));
-          zi.kind = ih.kind;
-          zi.flags = ih.flags;
-          zi.fcs = ih.fcs;
-          zi.ck_off = ih.ck_off;
-          if (ih.kind == 0) {
-            zi.size = ih.size;
-            zi.src_off = ih.off;
-          } else if (ih.kind == 1) {
-            zi.size = ih.size;
-            zi.src_off = ih.rle_byte;
-          } else {
-            zi.lit_kind = ih.lit_type == 0 ? 0u : (ih.lit_type == 1 ? 1u : 2u);
-            zi.lit_off = ih.lit_type == 1 ? (uint32_t)ih.rle_byte : ih.off + ih.lit_hdr;
-            zi.litn = ih.lit_regen;
-            zi.nseq = ih.nseq;
-            zi.zblock = bp.zblock;
-            zi.seq_packed = DP.z_lanes ? 1u : 0u;
-            ZBlock& zb = hzb[bp.zblock];
-            memset(&zb, 0, sizeof(zb));
-            zb.src = cd.src;
-            zb.lit_out = bp.lit_off != ~0ull ? S + bp.lit_off : nullptr;
-            zb.seq_out = bp.seq_off != ~0ull ? reinterpret_cast<uint32_t*>(S + bp.seq_off) : nullptr;
-            zb.chunk = ci;
-            zb.content_off = ih.off;
-            zb.content_end = ih.off + ih.size;
-            zb.lit_type = ih.lit_type;
-            zb.lit_streams = ih.lit_streams;
-            zb.lit_hdr = ih.lit_hdr;
-            zb.lit_regen = ih.lit_regen;
-            zb.lit_comp = ih.lit_comp;
-            zb.nseq = ih.nseq;
-            zb.seq_off = ih.seq_off;
-            if (ih.lit_type == 3) {
-              const ZItemH& def = zp.items[ih.huf_def];
-              zb.huf_off = def.off + def.lit_hdr;
-              zb.huf_end = zb.huf_off + def.lit_comp;
-            }
-            for (int w = 0; w < 3; w++) {
-              const ZItemH& def = ih.nseq && ih.tab_def[w] >= 0 ? zp.items[ih.tab_def[w]] : ih;
-              zb.tab_off[w] = def.seq_off;
-              zb.tab_end[w] = def.off + def.size;
-            }
-          }
-        }
-      }
-      slot += c.plain_cap;
-      ci++;
-    }
-  };
   {
-    const uint32_t ns = (uint32_t)P.decomp.size();
-    std::vector<uint32_t> first(ns + 1, 0);
-    for (uint32_t k = 0; k < ns; k++) first[k + 1] = first[k] + (uint32_t)P.decomp[k].st->chunks.size();
-    const uint32_t nthreads = DP.n_zitems >= 8192 && ns >= 8 ? 4u : 1u;
-    if (nthreads == 1) {
-      for (uint32_t k = 0; k < ns; k++) fill_stream(k, first[k]);
-    } else {
-      // streams dealt out in runs of about equal chunk counts
-      std::vector<std::thread> th;
-      uint32_t lo = 0;
-      for (uint32_t t = 0; t < nthreads; t++) {
-        uint32_t hi = lo;
-        const uint32_t want = (uint32_t)((uint64_t)first[ns] * (t + 1) / nthreads);
-        while (hi < ns && (first[hi + 1] <= want || t + 1 == nthreads)) hi++;
-        if (t + 1 == nthreads) hi = ns;
-        th.emplace_back([&, lo, hi] {
-          for (uint32_t k = lo; k < hi; k++) fill_stream(k, first[k]);
-        });
-        lo = hi;
-      }
-      for (auto& x : th) x.join();
+    // the streams' prebuilt entries, copied and rebased (tables_fill): their arenas, plain buffers and scratch, their places in the call
+    std::vector<StreamUse> use(P.decomp.size());
+    for (size_t si = 0; si < use.size(); si++) {
+      const DecompStream& ds = P.decomp[si];
+      StreamUse& u = use[si];
+      u.t = &ds.st->tables;
+      u.arena = ds.stripe->dev;
+      u.plain = ds.result_index >= 0 ? P.results[ds.result_index]->arena[ctx->lane_id].p + ds.result_off : S + ds.scratch_off;
+      u.scratch = DP.stream_scratch[si] != ~0ull ? S + DP.stream_scratch[si] : nullptr;
+      u.len_idx = ds.len_idx;
+      u.err_idx = ds.err_idx;
+      u.framing_error = ds.st->framing_error ? 1 : 0;
+      u.skip = ds.st->skip_bytes;
     }
+    tables_fill(use.data(), DP.counts, DP.z_lanes, hc, hstr, hzb, hzi, reinterpret_cast<uint32_t*>(host_blob + DP.order_off));
   }
   if (decomp_side_by_side(ctx, hc, DP.n_chunks, DP.n_zblocks, DP.z_lanes))
     // the execution kernel runs twice in that mode, beside the entropy kernel and behind it: a chunk is the second launch's
     // as long as it carries this mark (the first launch replaces it with the chunk's outcome)
     for (uint32_t c = 0; c < DP.n_chunks; c++)
       if (hc[c].kind == 5 || hc[c].kind == 0) hc[c].diag = LZX_DEFERRED;
-  {
-    // the queue of lz_exec_kernel: chunks with the most sequences first (they take longest and can start while their sequences
-    // are still being decoded)
-    uint32_t* ord = reinterpret_cast<uint32_t*>(host_blob + DP.order_off);
-    const std::vector<uint32_t> by = order_by_count_desc(DP.n_chunks, [&](uint32_t c) -> int64_t {
-      uint64_t ns = 0;
-      const uint32_t f = DP.chunk_first_item[c], e = c + 1 < DP.n_chunks ? DP.chunk_first_item[c + 1] : DP.n_zitems;
-      for (uint32_t k = f; k < e; k++) ns += DP.zitems[k].item->nseq;
-      return (int64_t)ns;
-    });
-    for (uint32_t c = 0; c < DP.n_chunks; c++) ord[c] = by[c];
-  }
   ChunkDesc* d_chunks = reinterpret_cast<ChunkDesc*>(S + DP.dev_off + DP.chunks_off);
   StreamDesc* d_streams = reinterpret_cast<StreamDesc*>(S + DP.dev_off + DP.streams_off);
   ZBlock* d_zblocks = reinterpret_cast<ZBlock*>(S + DP.dev_off + DP.zblocks_off);
   ZItem* d_zitems = reinterpret_cast<ZItem*>(S + DP.dev_off + DP.zitems_off);
+  const double t_up = host_us_now();
+  ctx->hp_fill += t_up - t_fill;
   HIP_TRY(ctx, hipMemcpyAsync(S + DP.dev_off, host_blob, DP.table_bytes, hipMemcpyHostToDevice, st));
+  ctx->hp_upload += host_us_now() - t_up;
   if (DP.n_chunks) {
     int rc = launch_chunk_decoders(ctx, st, d_chunks, hc, DP.n_chunks, d_zblocks, DP.n_zblocks, d_zitems, reinterpret_cast<uint32_t*>(S + DP.zdump_off),
                                    reinterpret_cast<uint32_t*>(S + DP.zstatus_off), reinterpret_cast<uint32_t*>(S + DP.zprogress_off), reinterpret_cast<const uint32_t*>(S + DP.dev_off + DP.order_off), stage1,
