@@ -564,20 +564,20 @@ static long fse_read_ncount(const uint8_t* p, size_t n, int16_t* norm, int* nsym
 
 typedef struct {
   int maxbits;
-  uint8_t sym[2048];
-  uint8_t nb[2048];
+  uint8_t sym[4096]; /* codes of up to 12 bits: RFC 8878 4.2.1 says 11, libzstd (the reference's decoder) takes 12 */
+  uint8_t nb[4096];
 } huf_tab;
 
 static int huf_build(huf_tab* h, const uint8_t* weights, int nw) {
   /* weights for nw symbols, last one implied */
   uint32_t sum = 0;
   for (int i = 0; i < nw; i++) {
-    if (weights[i] > 11) return -1;
+    if (weights[i] > 12) return -1;
     if (weights[i]) sum += 1u << (weights[i] - 1);
   }
   if (sum == 0) return -1;
   int maxbits = hibit(sum) + 1;
-  if (maxbits > 11) return -1;
+  if (maxbits > 12) return -1;
   uint32_t left = (1u << maxbits) - sum;
   if (left & (left - 1)) return -1;
   uint8_t w[256];
@@ -585,8 +585,8 @@ static int huf_build(huf_tab* h, const uint8_t* weights, int nw) {
   w[nw] = (uint8_t)(hibit(left) + 1);
   nw++;
   h->maxbits = maxbits;
-  uint32_t rankstart[13] = {0};
-  uint32_t cnt[13] = {0};
+  uint32_t rankstart[14] = {0};
+  uint32_t cnt[14] = {0};
   for (int i = 0; i < nw; i++) cnt[w[i]]++;
   uint32_t pos = 0;
   for (int wt = 1; wt <= maxbits; wt++) {
@@ -794,10 +794,11 @@ static long z_seq_table(fse_tab* ft, int* valid, int mode, const uint8_t* p, siz
   return *valid ? 0 : -1;
 }
 
-static long z_block(zctx* z, const uint8_t* p, size_t n, uint8_t* dst, size_t cap, size_t out) {
+static long z_block(zctx* z, const uint8_t* p, size_t n, uint8_t* dst, size_t cap, size_t out, size_t block_max) {
   uint8_t* litbuf = (uint8_t*)malloc(128 * 1024 + 16);
   if (!litbuf) return -1;
   size_t litn = 0;
+  const size_t block_start = out;
   long used = z_literals(z, p, n, litbuf, 128 * 1024, &litn);
   long ret = -1;
   if (used < 0) goto done;
@@ -890,6 +891,8 @@ static long z_block(zctx* z, const uint8_t* p, size_t n, uint8_t* dst, size_t ca
     if (out + (litn - lp) > cap) goto done;
     memcpy(dst + out, litbuf + lp, litn - lp);
     out += litn - lp;
+    /* a block regenerates Block_Maximum_Size at the most (RFC 8878 3.1.1.2.4); libzstd's streaming decoder fails a larger one */
+    if (out - block_start > block_max) goto done;
     ret = (long)out;
   }
 done:
@@ -967,9 +970,13 @@ long oo_zstd_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
     uint8_t fhd = src[pos++];
     int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, has_ck = (fhd >> 2) & 1, did_flag = fhd & 3;
     if (fhd & 0x08) return -1; /* reserved bit */
+    uint64_t window = 0;
     if (!single) {
       if (pos >= n) return -1;
-      pos++; /* window descriptor: irrelevant, whole frame is decoded into dst */
+      /* window descriptor: the whole frame is decoded into dst; the window only bounds the blocks' sizes */
+      uint8_t wd = src[pos++];
+      uint64_t wbase = (uint64_t)1 << (10 + (wd >> 3));
+      window = wbase + (wbase >> 3) * (wd & 7);
     }
     static const int DID[4] = {0, 1, 2, 4};
     if (did_flag) {
@@ -985,6 +992,10 @@ long oo_zstd_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
     for (int i = 0; i < fcs_bytes; i++) fcs |= (uint64_t)src[pos + i] << (8 * i);
     if (fcs_bytes == 2) fcs += 256;
     pos += (size_t)fcs_bytes;
+    if (single) window = fcs;
+    /* Block_Maximum_Size (RFC 8878 3.1.1.2.4): the smaller of the window and 128 KiB; libzstd's streaming decoder fails a block of any
+     * type whose Block_Size, or whose regenerated size, is above it */
+    size_t block_max = window < 128 * 1024 ? (size_t)window : 128 * 1024;
     size_t frame_start = out;
     zctx* z = (zctx*)calloc(1, sizeof(zctx));
     if (!z) return -1;
@@ -1002,6 +1013,10 @@ long oo_zstd_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
       last = bh & 1;
       int bt = (bh >> 1) & 3;
       size_t bs = bh >> 3;
+      if (bs > block_max) {
+        free(z);
+        return -1;
+      }
       if (bt == 0) {
         if (pos + bs > n || out + bs > cap) {
           free(z);
@@ -1019,12 +1034,12 @@ long oo_zstd_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
         pos += 1;
         out += bs;
       } else if (bt == 2) {
-        if (pos + bs > n || bs > 128 * 1024) {
+        if (pos + bs > n) {
           free(z);
           return -1;
         }
         /* matches may reach back to the start of this frame only */
-        long r = z_block(z, src + pos, bs, dst + frame_start, cap - frame_start, out - frame_start);
+        long r = z_block(z, src + pos, bs, dst + frame_start, cap - frame_start, out - frame_start, block_max);
         if (r < 0) {
           free(z);
           return -1;

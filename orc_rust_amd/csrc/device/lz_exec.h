@@ -813,10 +813,12 @@ __device__ __forceinline__ void lz_exec_chunk(ExecLds<T>& L, uint32_t c, ChunkDe
         else {
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
           const uint8_t* lit = it.lit_kind == 2 ? as_global((const uint8_t*)zb->lit_out) : src + it.lit_off;
+          const uint32_t block_start = out;
           // matches count from the start of the frame: positions are relative to the chunk's slot, the frame's first byte is frame_start
           st = lz_exec_block<T, 0>(L, (const uint32_t*)as_global((void*)zb->seq_out), it.nseq, lit, it.lit_kind, it.lit_off, it.litn, dst, cap, frame_start, out,
                                 R, (const uint32_t*)as_global((void*)(zprogress + it.zblock)), zst + it.zblock, tid PROF_ARG, it.seq_packed ? LZX_SEQ_PACKED : (it.nseq + 3u) & ~3u);
           if (!st && job_end(it.zblock)) st = 33;  // (a block without sequences, or a job that failed behind the last one)
+          if (!st && out - block_start > it.size) st = 36;  // more than Block_Maximum_Size regenerated (inside the slot: `cap` held)
         }
       }
       if (!st && (it.flags & 2) && (uint64_t)(out - frame_start) != it.fcs) st = 34;

@@ -184,7 +184,11 @@ __device__ __forceinline__ long fse_read_ncount_dev(const uint8_t* p, uint32_t n
 // over the weights with counters in a private array, i.e. in scratch memory, and 2048 two-byte stores: 150 us a block, a sixth of
 // the literals kernel.)  Symbols s = lane, lane + 64, ...: the sum of 2^(w - 1) by a wave reduction; per weight the symbols' count
 // and every symbol's rank among the symbols of its weight by ballots; `order` = the symbols sorted by (weight, symbol); the table
-// weight class by weight class, 64 entries a step.  scratch: 256 + 16 bytes of LDS.
+// weight class by weight class, 64 entries a step.  scratch: 256 + 16 bytes of LDS (HUF_WIDE_AT + 54 for a 12-bit tree).
+// libzstd also takes trees whose longest code has 12 bits (its own encoder stops at 11, as RFC 8878 4.2.1 says): such a tree gets NO
+// table (`tab` has 2048 cells, and the literals kernel owes its occupancy to that): *maxbits_out is 12, and what huf_decode_wide needs
+// stays in scratch -- `order`, and from byte HUF_WIDE_AT on the first cell of every weight (13 + 1 words) and its first place in `order`.
+#define HUF_WIDE_AT 272
 __device__ __forceinline__ int huf_build_dev(uint16_t* tab, int* maxbits_out, uint8_t* w, int nw, uint32_t lane, uint8_t* scratch) {
   uint8_t* order = scratch;
   // this lane's symbols (nw <= 255 of them stated; the last one, nw, implied)
@@ -195,13 +199,13 @@ __device__ __forceinline__ int huf_build_dev(uint16_t* tab, int* maxbits_out, ui
   for (int r = 0; r < 4; r++) {
     const int sidx = r * 64 + (int)lane;
     ws[r] = sidx < nw ? w[sidx] : 0;
-    if (ws[r] > 11) bad = true;
+    if (ws[r] > 12) bad = true;
     else if (ws[r]) sum += 1u << (ws[r] - 1);
   }
   for (int o = 32; o; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o);
   if (__ballot(bad) || sum == 0) return 1;
   const int maxbits = z_hibit(sum) + 1;
-  if (maxbits > 11) return 1;
+  if (maxbits > 12) return 1;
   const uint32_t left = (1u << maxbits) - sum;
   if (left & (left - 1)) return 1;
   const uint32_t wlast = (uint32_t)z_hibit(left) + 1;
@@ -241,6 +245,20 @@ __device__ __forceinline__ int huf_build_dev(uint16_t* tab, int* maxbits_out, ui
 #pragma unroll
   for (int r = 0; r < 4; r++)
     if (ws[r]) order[ord_of[r]] = (uint8_t)(r * 64 + (int)lane);
+  if (maxbits == 12) {
+    if (lane == 0) {
+      uint16_t* rs = reinterpret_cast<uint16_t*>(scratch + HUF_WIDE_AT);
+#pragma unroll
+      for (int wt = 1; wt <= 12; wt++) {
+        rs[wt] = (uint16_t)rs_w[wt];
+        rs[14 + wt] = (uint16_t)cb_w[wt];
+      }
+      rs[13] = (uint16_t)total;
+    }
+    *maxbits_out = maxbits;
+    wave_sync();
+    return 0;
+  }
   wave_sync();
   // the table: the entries of weight wt are runs of 2^(wt - 1) cells, one run per symbol of that weight in symbol order
 #pragma unroll
@@ -253,6 +271,31 @@ __device__ __forceinline__ int huf_build_dev(uint16_t* tab, int* maxbits_out, ui
   *maxbits_out = maxbits;
   wave_sync();
   return 0;
+}
+
+// One stream of a tree with 12-bit codes, by ONE lane and without a table (huf_build_dev): the 12 bits below the cursor are a cell
+// number; the cells are sorted by weight, so the weight is found by comparing with every weight's first cell, and the symbol by its
+// rank among the symbols of that weight.  Slow, and only for input no Zstandard encoder is known to write.  1: a bad stream.
+__device__ __forceinline__ int huf_decode_wide(const uint8_t* scratch, const uint8_t* sp, uint32_t sn, uint8_t* out, uint32_t outn) {
+  if (sn == 0 || sp[sn - 1] == 0) return 1;  // (rb_init)
+  const uint16_t* rs = reinterpret_cast<const uint16_t*>(scratch + HUF_WIDE_AT);
+  const uint16_t* cb = rs + 14;
+  int pos = (int)(sn - 1) * 8 + (31 - __builtin_clz((uint32_t)sp[sn - 1]));  // unread bits
+  for (uint32_t i = 0; i < outn; i++) {
+    const int lo = pos - 12, b0 = lo >> 3;  // (bits before the stream read as zero)
+    uint32_t v = 0;
+    for (int t = 0; t < 3; t++) {
+      const int bi = b0 + t;
+      if (bi >= 0 && bi < (int)sn) v |= (uint32_t)sp[bi] << (8 * t);
+    }
+    v = (v >> (lo - 8 * b0)) & 0xfffu;
+    int wt = 1;
+    while (wt < 12 && v >= rs[wt + 1]) wt++;
+    out[i] = scratch[cb[wt] + ((v - rs[wt]) >> (wt - 1))];
+    pos -= 13 - wt;
+    if (pos < 0) return 1;  // the stream ran dry
+  }
+  return pos != 0;  // every bit must be used
 }
 
 // Huffman streams decoded by MANY lanes each (16 per stream for the usual four streams, 64 for a single

@@ -609,7 +609,13 @@ __device__ __forceinline__ int zstd_literals_job(LDS& L, const ZBlock& B, const 
     }
   }
   PROF_MARK(1);
-  if (!st) {
+  if (!st && mb == 12) {
+    // codes of 12 bits: no table (huf_build_dev); the first lane of every stream decodes it alone (h.p: its stream, hw_begin).
+    // What it reads lies in L.norm, which L.chunk overlays in ZLitLds: nothing may be written to L.chunk between zhuf_tree and this
+    // call (today only hw_refill inside huf_decode_w16 writes there; hw_begin's first chunk waits in registers).
+    const int bad = sk == 0 ? huf_decode_wide(reinterpret_cast<const uint8_t*>(L.norm), h.p, sn, lit_out + sout, son) : 0;
+    if (__ballot(bad != 0)) st = 16;
+  } else if (!st) {
     const int bad = huf_decode_w16(h, L.h.huf, mb, sn, lit_out + sout, son, sk, lps, true PROF_ARG);
     if (__ballot(bad != 0)) st = 16;
   }

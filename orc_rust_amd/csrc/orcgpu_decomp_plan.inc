@@ -130,6 +130,7 @@ void build_stream_tables(const std::vector<ChunkInfo>& chunks, const std::vector
           zi.lit_kind = ih.lit_type == 0 ? 0u : (ih.lit_type == 1 ? 1u : 2u);
           zi.lit_off = ih.lit_type == 1 ? (uint32_t)ih.rle_byte : ih.off + ih.lit_hdr;
           zi.litn = ih.lit_regen;
+          zi.size = ih.block_max;
           zi.nseq = ih.nseq;
           ZBlock zb;
           memset(&zb, 0, sizeof(zb));

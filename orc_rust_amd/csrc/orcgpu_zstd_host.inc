@@ -20,6 +20,7 @@ struct ZItemH {
   int32_t huf_def = -1;      // item whose literals section holds the Huffman tree this block uses
   int32_t tab_def[3] = {-1, -1, -1};  // item whose sequences section describes the LL / OF / ML table this block uses
   uint64_t fcs = 0;
+  uint32_t block_max = 0;    // compressed: Block_Maximum_Size of its frame, the most it may regenerate
   uint32_t ck_off = 0;       // flags & 4: where the checksum's four bytes lie in the chunk payload
 };
 
@@ -49,9 +50,13 @@ void zstd_parse_chunk(const uint8_t* src, uint32_t n, ZChunkParse& out) {
     const uint32_t fhd = src[pos++];
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, has_ck = (fhd >> 2) & 1, did_flag = fhd & 3;
     if (fhd & 0x08) return fail();
+    uint64_t window = 0;
     if (!single) {
       if (pos >= n) return fail();
-      pos++;  // window descriptor: the whole frame is decoded into the chunk's slot
+      // window descriptor: the whole frame is decoded into the chunk's slot; the window only bounds the blocks' sizes
+      const uint32_t wd = src[pos++];
+      const uint64_t base = 1ull << (10 + (wd >> 3));
+      window = base + (base >> 3) * (wd & 7);
     }
     const uint32_t did_bytes = did_flag == 3 ? 4 : did_flag;
     if (did_bytes) {
@@ -67,6 +72,9 @@ void zstd_parse_chunk(const uint8_t* src, uint32_t n, ZChunkParse& out) {
     for (uint32_t i = 0; i < fcs_bytes; i++) fcs |= (uint64_t)src[pos + i] << (8 * i);
     if (fcs_bytes == 2) fcs += 256;
     pos += fcs_bytes;
+    if (single) window = fcs;
+    // Block_Maximum_Size (RFC 8878 3.1.1.2.4): the smaller of the window and 128 KiB, for what a block of any type holds and regenerates
+    const uint32_t block_max = (uint32_t)std::min<uint64_t>(window, 128 * 1024);
     if (fcs_bytes) out.plain_size += fcs;
     else out.size_known = false;
     const size_t first = out.items.size();
@@ -78,6 +86,7 @@ void zstd_parse_chunk(const uint8_t* src, uint32_t n, ZChunkParse& out) {
       pos += 3;
       last = bh & 1;
       const uint32_t bt = (bh >> 1) & 3, bs = bh >> 3;
+      if (bs > block_max) return fail();  // (Raw and RLE blocks too: their Block_Size is what they regenerate)
       ZItemH it;
       it.off = pos;
       if (bt == 0) {
@@ -92,9 +101,10 @@ void zstd_parse_chunk(const uint8_t* src, uint32_t n, ZChunkParse& out) {
         it.rle_byte = src[pos];
         pos += 1;
       } else if (bt == 2) {
-        if ((uint64_t)pos + bs > n || bs > 128 * 1024) return fail();
+        if ((uint64_t)pos + bs > n) return fail();
         it.kind = 2;
         it.size = bs;
+        it.block_max = block_max;
         const uint8_t* p = src + pos;
         if (bs < 1) return fail();
         const uint32_t type = p[0] & 3, sf = (p[0] >> 2) & 3;
