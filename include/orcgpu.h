@@ -76,6 +76,10 @@ enum {
   ORCGPU_ARROW_DECIMAL128 = 20,  /* precision / scale in arrow_precision / arrow_scale; (38, 9) is also the wide target of timestamps */
   ORCGPU_ARROW_TIMESTAMP_S_UTC = 21, ORCGPU_ARROW_TIMESTAMP_MS_UTC = 22, ORCGPU_ARROW_TIMESTAMP_US_UTC = 23, ORCGPU_ARROW_TIMESTAMP_NS_UTC = 24,
   ORCGPU_ARROW_LARGE_UTF8 = 25, ORCGPU_ARROW_LARGE_BINARY = 26,  /* (the encoder's inputs only: i64 offsets) */
+  /* Dictionary(Int32, Utf8) for a STRING / VARCHAR / CHAR column, at the root or as a Struct field: int32 keys per row and one
+   * dictionary per stripe instead of Utf8 (orcgpu_dictionary_view below).  Beyond the reference, which casts its DictionaryArray
+   * back to a StringArray (array_decoder/string.rs:216-219).  Any other ORC type with it: ORCGPU_MISMATCHED_SCHEMA */
+  ORCGPU_ARROW_DICTIONARY_UTF8 = 27,
   ORCGPU_ARROW_TIMESTAMP_S_NOTZ = 31, ORCGPU_ARROW_TIMESTAMP_MS_NOTZ = 32, ORCGPU_ARROW_TIMESTAMP_US_NOTZ = 33, ORCGPU_ARROW_TIMESTAMP_NS_NOTZ = 34,
   ORCGPU_ARROW_TIMESTAMP_OTHER_TZ = 35,  /* Timestamp(_, Some(tz)) with tz != "UTC": UnsupportedTypeVariant for TimestampInstant */
   /* nested targets (array_decoder/mod.rs:464-505): the hint of a Struct / List / Map / Union column; its children carry theirs */
@@ -225,6 +229,34 @@ int orcgpu_result_batch_view(const orcgpu_result* r, uint32_t batch, uint32_t co
 int orcgpu_result_copy_batch(orcgpu_ctx* ctx, const orcgpu_result* r, uint32_t batch, uint32_t column, void* values,
                              int32_t* offsets, void* validity);
 
+/* ---- dictionary output (ORCGPU_ARROW_DICTIONARY_UTF8) -------------------------------------------------------------------------
+ * A column decoded to that target is, batch for batch, an Int32 column: orcgpu_batch_view.values are the keys (values_bytes =
+ * 4 * length, offsets = NULL), validity and null count as on the Utf8 path, a null row's key 0.  orcgpu_result_select, the row-group
+ * entry points of orcgpu_stream and orcgpu_result_filter treat the keys as an Int32 column's values and leave the dictionary alone
+ * (a filter predicate that COMPARES such a column is ORCGPU_UNSUPPORTED, the message naming it; IS [NOT] NULL works).
+ * The stripe has ONE dictionary, shared by all its batches, in Arrow Utf8 layout:
+ *   DICTIONARY / DICTIONARY_V2 stripe   entry k is the file's entry k (the LENGTH stream's prefix sums over DICTIONARY_DATA,
+ *       dictionary_size entries, file order); the keys are the DATA stream's ids.  An id >= dictionary_size or >= 2^31 is
+ *       ORCGPU_ARROW at its row: the status names the first failing batch, the batches before it are valid -- what the Utf8 target
+ *       reports for the same stripe.  A dictionary that fails to decode, or holds an entry that is not UTF-8 (checked once per entry),
+ *       fails the column as on the Utf8 path.
+ *   DIRECT / DIRECT_V2 stripe           the identity dictionary: entry k is the k-th non-null value of the stripe (LENGTH prefix sums
+ *       over DATA, no slots for nulls), a valid row's key its rank among the valid rows.  A column so has one Arrow type whatever
+ *       each stripe's writer chose.  Values that end beyond 2^31 - 1 dictionary bytes: ORCGPU_ARROW at their row.
+ * orcgpu_result_export_batch[_device] export the column as format "i" with ArrowSchema.dictionary "u" and ArrowArray.dictionary
+ * the stripe's entries; every batch of the stripe refers to the same buffers -- on the host path they come back once, with the
+ * result's arena -- and they go when the last batch referring to them is released.  orcgpu_result_arrow_bytes counts them once. */
+typedef struct {
+  uint64_t length;         /* entries */
+  const int32_t* offsets;  /* DEVICE: length + 1, first 0 (NULL: the stripe has no rows, nothing was decoded) */
+  const void* values;      /* DEVICE: the entries' bytes */
+  uint64_t values_bytes;
+} orcgpu_dictionary_view;
+/* ORCGPU_INVALID_ARGUMENT for a column that was not decoded to ORCGPU_ARROW_DICTIONARY_UTF8. */
+int orcgpu_result_dictionary_view(const orcgpu_result* r, uint32_t column, orcgpu_dictionary_view* out);
+/* Copies the dictionary to host memory supplied by the caller (sizes from the view; either pointer may be NULL). */
+int orcgpu_result_copy_dictionary(orcgpu_ctx* ctx, const orcgpu_result* r, uint32_t column, int32_t* offsets, void* values);
+
 /* ---- row selection --------------------------------------------------------------------------------------- */
 /* One run of a RowSelection (src/row_selection.rs:32-52): row_count rows skipped or selected. */
 typedef struct {
@@ -347,6 +379,14 @@ int orcgpu_reader_set_projection_roots(orcgpu_reader* r, const uint32_t* root_in
  * for makes the first orcgpu_reader_next_batch return ORCGPU_MISMATCHED_SCHEMA.  The schema is read, not consumed. */
 int orcgpu_reader_set_schema(orcgpu_reader* r, const struct ArrowSchema* schema);
 int orcgpu_reader_set_byte_range(orcgpu_reader* r, uint64_t start, uint64_t end);                    /* with_file_byte_range */
+/* Dictionary output (opt-in; the reference has no counterpart): the named columns -- projected root columns of ORC kind STRING /
+ * VARCHAR / CHAR -- come as Dictionary(Int32, Utf8) instead of Utf8: ORCGPU_ARROW_DICTIONARY_UTF8 in every stripe, whatever its
+ * encoding there.  Before the first batch; n = 0 restores the default.  A name the file's root columns do not have, a name given
+ * twice, a column of another kind: ORCGPU_INVALID_ARGUMENT, the message naming it (a name outside the projection is met at the
+ * first batch, the same way).  With orcgpu_reader_set_schema the field of such a column must be Utf8.  Everything else --
+ * projection, shards, byte ranges, row selection, pruning, read-ahead, compression -- works as before; a row filter may not
+ * compare such a column (ORCGPU_UNSUPPORTED). */
+int orcgpu_reader_set_dictionary_columns(orcgpu_reader* r, const char* const* names, uint32_t n);
 /* `world` processes, one per GPU, read ONE file together; this reader is number `rank` of them.  The units of the
  * path are independent (stripe.rs:154-165: a stripe's columns are decoded one by one), so no data is exchanged -- each reader
  * reads, stages and decodes only what is its own; what the ranks do with their batches (an all-gather of row counts,
@@ -526,7 +566,9 @@ int orcgpu_device_array_wait(const struct ArrowDeviceArray* array, void* hip_str
  * kDLROCM, the array's device): buffer 0 the validity bitmap (uint8, ceil(n / 8)), 1 the values (fixed width: the natural type,
  * [n]; Decimal128: int64 [n, 2], low word first; Boolean: the bitmap as uint8) or, for strings and binaries, the int32 offsets
  * [n + 1], 2 the string bytes (uint8).  A buffer the column does not have (no validity: the batch has no null), or an empty one:
- * ORCGPU_INVALID_ARGUMENT.  The tensor holds a reference of its own (see Ownership): it outlives the array; its deleter drops it. */
+ * ORCGPU_INVALID_ARGUMENT.  A dictionary-output column (ORCGPU_ARROW_DICTIONARY_UTF8): 1 the int32 keys [n], 3 the dictionary's
+ * int32 offsets [entries + 1], 4 its bytes (uint8).  The tensor holds a reference of its own (see Ownership): it outlives the array;
+ * its deleter drops it. */
 int orcgpu_device_array_dlpack(const struct ArrowDeviceArray* array, uint32_t column, int buffer, void** out_managed_tensor);
 /* Unpacks an LSB-first bitmap of n bits in device memory, from bit 0 on, to one byte per bit (0 or 1) in device memory of the
  * context's device, by a kernel on `hip_stream` (a hipStream_t; NULL is HIP's default stream).  The call does not wait.  Reads

@@ -14,6 +14,23 @@ from . import capi
 DEFAULT_BATCH_SIZE = 8192  # arrow_reader.rs:37
 
 
+def check_dictionary_columns(names):
+    """The argument of with_dictionary_columns, checked before anything reaches the GPU: a list or tuple of non-empty str, none
+    of them twice.  Returns it as a list."""
+    if not isinstance(names, (list, tuple)):
+        raise ValueError("with_dictionary_columns: a list or tuple of column names, not %s" % type(names).__name__)
+    seen = set()
+    for n in names:
+        if not isinstance(n, str):
+            raise ValueError("with_dictionary_columns: a column name must be a str, not %s" % type(n).__name__)
+        if not n:
+            raise ValueError("with_dictionary_columns: an empty column name")
+        if n in seen:
+            raise ValueError("with_dictionary_columns: column %r is listed twice" % n)
+        seen.add(n)
+    return list(names)
+
+
 class ArrowReaderBuilder:
     def __init__(self, ctx, handle, keep=None):
         self._ctx, self._h, self._keep = ctx, handle, keep
@@ -72,6 +89,16 @@ class ArrowReaderBuilder:
     def with_timestamp_precision(self, unit):
         """unit: 'us' or 'ns' (TimestampPrecision, schema.rs:31-38); 's'/'ms' as with_schema overrides."""
         self._ctx._check(self._ctx.L.orcgpu_reader_set_timestamp_precision(self._h, {"s": 1, "ms": 2, "us": 3, "ns": 4}[unit]))
+        return self
+
+    def with_dictionary_columns(self, names):
+        """The named root columns (ORC STRING / VARCHAR / CHAR) arrive as dictionary(int32, string) instead of string
+        (orcgpu_reader_set_dictionary_columns): int32 keys per row and one dictionary per stripe -- the file's own where the stripe is
+        dictionary-encoded, the identity dictionary where it is not.  Host batches carry pyarrow.DictionaryArrays; with
+        with_device_output() a column has `values` (the keys), `validity` and `dictionary` (`offsets`, `data`)."""
+        names = check_dictionary_columns(names)
+        arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_dictionary_columns(self._h, arr, len(names)))
         return self
 
     def with_row_selection(self, selectors):

@@ -28,6 +28,7 @@ EXPORTS = [
     "orcgpu_result_filter", "orcgpu_reader_set_row_filter", "orcgpu_reader_filter_rows",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
+    "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
     "orcgpu_result_export_batch_device", "orcgpu_reader_set_device_output", "orcgpu_reader_next_batch_device", "orcgpu_reader_d2h_bytes",
     "orcgpu_device_array_wait", "orcgpu_device_array_dlpack", "orcgpu_unpack_bits", "orcgpu_result_buffer_bytes", "orcgpu_reader_reads_ahead",
     "orcgpu_writer_open_file", "orcgpu_writer_open_bytes", "orcgpu_writer_write", "orcgpu_writer_flush_stripe", "orcgpu_writer_close",
@@ -131,11 +132,16 @@ class EncStream(C.Structure):
 ENC_ON_DEVICE = 1
 ARROW = {"bool": 10, "int8": 11, "int16": 12, "int32": 13, "int64": 14, "float32": 15, "float64": 16, "utf8": 17, "binary": 18,
          "large_utf8": 25, "large_binary": 26}
+ARROW_DICTIONARY_UTF8 = 27  # include/orcgpu.h: ORCGPU_ARROW_DICTIONARY_UTF8 (orcgpu_column.arrow_target: int32 keys + one dictionary per stripe)
 
 
 class BatchView(C.Structure):
     _fields_ = [("length", C.c_uint64), ("null_count", C.c_uint64), ("validity", C.c_void_p), ("values", C.c_void_p),
                 ("values_bytes", C.c_uint64), ("offsets", C.c_void_p)]
+
+
+class DictionaryView(C.Structure):
+    _fields_ = [("length", C.c_uint64), ("offsets", C.c_void_p), ("values", C.c_void_p), ("values_bytes", C.c_uint64)]
 
 
 _lib = None
@@ -186,6 +192,9 @@ def load():
     L.orcgpu_result_arrow_bytes.argtypes = [C.c_void_p]
     L.orcgpu_result_batch_view.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(BatchView)]
     L.orcgpu_result_copy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orcgpu_result_dictionary_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(DictionaryView)]
+    L.orcgpu_result_copy_dictionary.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.orcgpu_reader_set_dictionary_columns.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
     L.orcgpu_result_fetch.argtypes = [C.c_void_p, C.c_void_p]
     L.orcgpu_result_fetch_async.argtypes = [C.c_void_p, C.c_void_p]
     L.orcgpu_reader_set_prefetch.argtypes = [C.c_void_p, C.c_uint32]
@@ -547,6 +556,16 @@ class Result:
             validity.ctypes.data if validity is not None else None))
         return {"status": 0, "length": n, "null_count": v.null_count, "validity": validity.tobytes() if validity is not None else None,
                 "values": values[:v.values_bytes].tobytes(), "offsets": offsets}
+
+    def dictionary(self, column):
+        """Host copy of the stripe's dictionary of a column decoded to ARROW_DICTIONARY_UTF8: (int32 offsets, bytes)
+        (orcgpu_result_dictionary_view / _copy_dictionary)."""
+        v = DictionaryView()
+        self.ctx._check(self.ctx.L.orcgpu_result_dictionary_view(self.h, column, C.byref(v)))
+        offsets = np.zeros(v.length + 1, dtype=np.int32)
+        values = np.zeros(max(1, v.values_bytes), dtype=np.uint8)
+        self.ctx._check(self.ctx.L.orcgpu_result_copy_dictionary(self.ctx.h, self.h, column, offsets.ctypes.data, values.ctypes.data))
+        return offsets, values[:v.values_bytes].tobytes()
 
     def select(self, selectors):
         """Row selection over the decoded stripe: selectors = [(row_count, skip)] (orcgpu_result_select)."""

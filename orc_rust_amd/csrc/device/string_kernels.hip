@@ -240,6 +240,94 @@ __device__ __forceinline__ void dict_rows8(const DictJob& j, uint32_t bits, uint
   }
 }
 
+// ---- dictionary output: the stripe's int32 keys, the dictionary left intact (ORCGPU_ARROW_DICTIONARY_UTF8) -------------------
+// What the four kernels below expand to Utf8 -- an offset and the entry's bytes for every row -- stays a key here: 4 bytes a row,
+// the entries once per stripe.  One launch per column, the job by value.
+struct DictKeysJob {
+  const void* dense;                // DICTIONARY stripe: the decoded ids of the non-null rows, key_bytes wide (DictJob::dense); null: a DIRECT stripe
+  const unsigned long long* vbits;  // stripe-wide validity words (null: no PRESENT stream)
+  const uint32_t* rank;             // non-null rows before each 64-row word
+  int32_t* keys;                    // out: one per row, 0 in null rows (16-byte aligned)
+  unsigned long long* err;
+  const unsigned long long* dict_err;
+  const uint64_t* scalars;
+  // a DIRECT stripe's identity dictionary: entry k is the k-th non-null value, its offset the row's place in the DATA bytes
+  const int32_t* row_offsets;       // per-batch offsets of the rows, batch b at b * (batch + 1) (batch_offsets_body)
+  const unsigned long long* charbase;  // per-batch byte base
+  int32_t* dict_off;                // out: non-null rows + 1 offsets
+  uint64_t n_rows;
+  uint32_t batch, key_bytes;
+  uint32_t dict_n_idx, nonnull_idx, total_idx;  // scalars: dictionary size / non-null rows, DATA bytes the rows consume
+};
+// Thread t takes rows 8t .. 8t+7: their ids are eight consecutive dense values (one-byte ids: a single load, 0xff meaning "no
+// key" as the expansion left it), their keys leave as two 16-byte stores.  An id that is no key (DictionaryArray::try_new: not
+// below the dictionary size read here on the device; negative or wider than the key type) fails its row with ORC_E_ARROW and
+// is written as 0, as a null row's key is.
+extern "C" __global__ void __launch_bounds__(256) dict_keys_kernel(const DictKeysJob j) {
+  const uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * DICT_PER;
+  if (i >= j.n_rows) return;
+  const uint32_t cnt = j.n_rows - i < DICT_PER ? (uint32_t)(j.n_rows - i) : DICT_PER;
+  DictJob v{};
+  v.vbits = j.vbits;
+  v.rank = j.rank;
+  uint64_t d0;
+  const uint32_t bits = dict_valid8(v, i, cnt, &d0);
+  int32_t key[8];
+  uint32_t idx = 0;
+  if (j.dense) {
+    const bool dict_ok = *j.dict_err == RLE_NO_ERR;
+    const uint64_t dict_n = dict_ok ? j.scalars[j.dict_n_idx] : 0;
+    v.dense = j.dense;
+    v.key_bytes = j.key_bytes;
+    uint64_t packed = 0;
+    if (j.key_bytes == 1 && bits) packed = ld_u64(static_cast<const uint8_t*>(j.dense) + d0);  // (the key buffer has slack behind it)
+    uint32_t bad = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++) {
+      key[r] = 0;
+      if (!((bits >> r) & 1)) continue;
+      int32_t k;
+      if (j.key_bytes == 1) {
+        const uint32_t b = (uint32_t)(packed >> (8 * idx)) & 0xffu;
+        k = b == 0xffu ? -1 : (int32_t)b;
+      } else {
+        k = dict_key(v, d0 + idx);
+      }
+      idx++;
+      if (k < 0 || (uint64_t)k >= dict_n) bad |= 1u << r;
+      else key[r] = k;
+    }
+    if (bad && dict_ok) report_err64(j.err, i + (uint32_t)__builtin_ctz(bad), ORC_E_ARROW);  // (a failed dictionary is what the column reports)
+  } else {
+    const uint64_t nonnull = j.scalars[j.nonnull_idx];
+#pragma unroll
+    for (uint32_t r = 0; r < 8; r++) {
+      key[r] = 0;
+      if (!((bits >> r) & 1)) continue;
+      const uint64_t d = d0 + idx, row = i + r, b = row / j.batch;
+      idx++;
+      if (d >= nonnull) continue;  // (cannot be: the rank counts the same bits)
+      const int32_t* o = j.row_offsets + b * ((uint64_t)j.batch + 1) + (row - b * j.batch);
+      const uint64_t at = j.charbase[b] + (uint64_t)(uint32_t)o[0], end = j.charbase[b] + (uint64_t)(uint32_t)o[1];
+      // the dictionary's offsets are int32: the first value that ends beyond them fails its row
+      if (end > 0x7fffffffull) report_err64(j.err, row, ORC_E_ARROW);
+      j.dict_off[d] = (int32_t)(at > 0x7fffffffull ? 0x7fffffffull : at);
+      key[r] = (int32_t)d;
+    }
+    if (i == 0) {
+      const uint64_t total = j.scalars[j.total_idx];
+      j.dict_off[nonnull] = (int32_t)(total > 0x7fffffffull ? 0x7fffffffull : total);
+    }
+  }
+  if (cnt == DICT_PER) {
+    int4* out = reinterpret_cast<int4*>(j.keys + i);  // (i is a multiple of 8: 32-byte aligned)
+    out[0] = make_int4(key[0], key[1], key[2], key[3]);
+    out[1] = make_int4(key[4], key[5], key[6], key[7]);
+  } else {
+    for (uint32_t r = 0; r < cnt; r++) j.keys[i + r] = key[r];
+  }
+}
+
 // Pass 1, one workgroup per (batch, column): keys bounds-checked (DictionaryArray::try_new) -> the batch's value byte total.
 // Nothing per row is written: the second pass (behind the host's sizing of the character arena) forms the offsets again
 // from the keys -- one byte each for small dictionaries -- instead of reading four bytes per row back.

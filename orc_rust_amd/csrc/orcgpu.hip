@@ -356,6 +356,13 @@ struct ColumnOut {
   uint64_t values_off = 0, values_bytes = 0;      // in the result arena (or the chars arena)
   int lane = 0;                                   // which lane's arenas hold the column
   bool values_in_chars = false;                   // dictionary strings: values live in orcgpu_result::chars
+  // ORCGPU_ARROW_DICTIONARY_UTF8: the values are int32 keys (width 4, handled like an Int32 column's everywhere); the stripe's
+  // dictionary -- int32 offsets (dict_len + 1) and the entries' bytes, Arrow Utf8 layout -- lies in the same arena and goes
+  // wherever that goes (one copy back per stripe, one reference count for all batches)
+  bool dict_out = false;
+  bool dict_decoded = false;                      // the stripe had rows: the two buffers below exist
+  uint64_t dict_offsets_off = 0, dict_values_off = 0;
+  uint64_t dict_len = 0, dict_bytes = 0;          // host copies, known behind the decode's closing synchronisation
   uint64_t offsets_off = 0;                       // strings: n_batches * (B+1) int32
   uint64_t validity_off = 0;                      // n_batches * words_per_batch u64
   std::vector<uint64_t> null_counts;              // host copy, per batch
@@ -695,6 +702,8 @@ struct ColPlan {
   uint64_t lens_off = 0;       // spaced int32 lengths per row (scratch)
   uint32_t chartot_off = 0;    // index into the summary per-batch char totals
   uint64_t dictoff_off = 0;    // dictionary offsets (scratch, int32[dict+1])
+  bool dict_out = false;       // ORCGPU_ARROW_DICTIONARY_UTF8 (ColumnOut::dict_out)
+  uint64_t rowoff_off = 0;     // ... of a DIRECT stripe: the per-batch row offsets (scratch; the result holds keys instead)
   uint32_t dictbytes_idx = 0;
 };
 

@@ -26,7 +26,8 @@ int schema_pair_status(const orcgpu_column& c) {
     case ORCGPU_T_LONG: return a == ORCGPU_ARROW_INT64 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
     case ORCGPU_T_FLOAT: return a == ORCGPU_ARROW_FLOAT32 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
     case ORCGPU_T_DOUBLE: return a == ORCGPU_ARROW_FLOAT64 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
-    case ORCGPU_T_STRING: case ORCGPU_T_VARCHAR: case ORCGPU_T_CHAR: return a == ORCGPU_ARROW_UTF8 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
+    case ORCGPU_T_STRING: case ORCGPU_T_VARCHAR: case ORCGPU_T_CHAR:
+      return a == ORCGPU_ARROW_UTF8 || a == ORCGPU_ARROW_DICTIONARY_UTF8 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
     case ORCGPU_T_BINARY: return a == ORCGPU_ARROW_BINARY ? 0 : ORCGPU_MISMATCHED_SCHEMA;
     case ORCGPU_T_DATE: return a == ORCGPU_ARROW_DATE32 ? 0 : ORCGPU_MISMATCHED_SCHEMA;
     case ORCGPU_T_DECIMAL:
@@ -63,6 +64,14 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   co.width = type_width(c.orc_type);
   co.is_string = is_string_type(c.orc_type);
   co.is_bool = c.orc_type == ORCGPU_T_BOOLEAN;
+  // int32 keys + the stripe's dictionary instead of Utf8: from here on the column's values are an Int32 column's
+  co.dict_out = cp.dict_out = co.is_string && c.arrow_target == ORCGPU_ARROW_DICTIONARY_UTF8;
+  co.dict_offsets_off = co.dict_values_off = co.dict_len = co.dict_bytes = 0;
+  co.dict_decoded = false;
+  if (co.dict_out) {
+    co.is_string = false;
+    co.width = 4;
+  }
   co.precision = c.precision;
   co.scale = c.scale;
   co.ts_unit = ts_unit_of(c);
@@ -855,6 +864,8 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   }
   const double ht_fin = hclock();
   rc = launch_dict_rows(ctx, P, S, d_scalars, d_chartot);
+  if (rc) return rc;
+  rc = launch_dict_keys(ctx, P, S, d_scalars, d_chartot);
   if (rc) return rc;
   const double ht_dict = hclock();
   rc = launch_post_ext(ctx, P, S, dsum, hs, SL, d_chartot);

@@ -20,11 +20,13 @@ struct ExportPriv {
   std::vector<const void*> bufs;   // buffers array
   std::vector<ArrowArray*> kids;
   std::vector<ArrowArray> kid_store;
+  std::vector<ArrowArray> dict_store;  // a dictionary-output column: ArrowArray::dictionary (one, or none)
 };
 struct SchemaPriv {
   std::vector<std::string> strings;
   std::vector<ArrowSchema*> kids;
   std::vector<ArrowSchema> kid_store;
+  std::vector<ArrowSchema> dict_store;  // ArrowSchema::dictionary
 };
 
 void release_array(ArrowArray* a) {
@@ -32,6 +34,8 @@ void release_array(ArrowArray* a) {
   ExportPriv* p = static_cast<ExportPriv*>(a->private_data);
   if (p) {
     for (auto& k : p->kid_store)
+      if (k.release) k.release(&k);
+    for (auto& k : p->dict_store)
       if (k.release) k.release(&k);
     for (void* q : p->owned) free(q);
     if (p->mirror) p->mirror->unref();
@@ -45,6 +49,8 @@ void release_schema(ArrowSchema* s) {
   if (p) {
     for (auto& k : p->kid_store)
       if (k.release) k.release(&k);
+    for (auto& k : p->dict_store)
+      if (k.release) k.release(&k);
     delete p;
   }
   s->release = nullptr;
@@ -52,6 +58,7 @@ void release_schema(ArrowSchema* s) {
 
 std::string arrow_format(const ColumnOut& co) {
   static const char* units = "smun";
+  if (co.dict_out) return "i";  // the keys; ArrowSchema::dictionary says "u"
   switch (co.orc_type) {
     case ORCGPU_T_BOOLEAN: return "b";
     case ORCGPU_T_BYTE: return "c";
@@ -221,6 +228,35 @@ int orcgpu_result_batch_view(const orcgpu_result* r, uint32_t b, uint32_t c, orc
     out->values = A + co.values_off + (uint64_t)b * r->batch * co.width;
     out->values_bytes = rows * co.width;
   }
+  return ORCGPU_OK;
+}
+
+// The stripe's dictionary of a dictionary-output column: where it lies now -- in the decode's arena or, behind a row filter, beside
+// the kept rows
+int orcgpu_result_dictionary_view(const orcgpu_result* r, uint32_t c, orcgpu_dictionary_view* out) {
+  if (!r || !out || c >= r->cols.size()) return ORCGPU_INVALID_ARGUMENT;
+  const ColumnOut& co = r->cols[c];
+  memset(out, 0, sizeof(*out));
+  if (!co.dict_out) return ORCGPU_INVALID_ARGUMENT;
+  const uint8_t* A = r->filtered ? r->filt_arena.p : r->arena[co.lane].p;
+  if (!co.dict_decoded) return ORCGPU_OK;  // (a stripe without rows decodes nothing: no entries, no buffers)
+  out->length = co.dict_len;
+  out->offsets = reinterpret_cast<const int32_t*>(A + co.dict_offsets_off);
+  out->values = A + co.dict_values_off;
+  out->values_bytes = co.dict_bytes;
+  return ORCGPU_OK;
+}
+
+int orcgpu_result_copy_dictionary(orcgpu_ctx* ctx, const orcgpu_result* r, uint32_t c, int32_t* offsets, void* values) {
+  orcgpu_dictionary_view v;
+  int rc = orcgpu_result_dictionary_view(r, c, &v);
+  if (rc) return rc;
+  if (!ctx) return ORCGPU_INVALID_ARGUMENT;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (offsets && !v.offsets) offsets[0] = 0;
+  if (offsets && v.offsets) HIP_TRY(ctx, hipMemcpy(offsets, v.offsets, (v.length + 1) * 4, hipMemcpyDeviceToHost));
+  if (values && v.values_bytes) HIP_TRY(ctx, hipMemcpy(values, v.values, v.values_bytes, hipMemcpyDeviceToHost));
   return ORCGPU_OK;
 }
 
@@ -402,6 +438,41 @@ static int export_batch_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, uint32_
     } else {
       kp->bufs.push_back(or_empty(v.values_bytes ? host_of(v.values) : nullptr));
     }
+    if (co.dict_out) {
+      // the stripe's dictionary as a Utf8 array: every batch of the stripe points into the same host copy, which came over with
+      // the arena, once, and goes when the last array that refers to it is released (one more reference on the mirror)
+      orcgpu_dictionary_view dv;
+      memset(&dv, 0, sizeof(dv));
+      orcgpu_result_dictionary_view(q, (uint32_t)c, &dv);
+      ExportPriv* dp = new ExportPriv();
+      if (qm) {
+        dp->mirror = qm;
+        qm->refs.fetch_add(1);
+      }
+      dp->bufs.push_back(nullptr);
+      dp->bufs.push_back(or_empty(dv.length ? host_of(dv.offsets) : nullptr));
+      dp->bufs.push_back(or_empty(dv.values_bytes ? host_of(dv.values) : nullptr));
+      kp->dict_store.emplace_back();
+      ArrowArray& da = kp->dict_store.back();
+      memset(&da, 0, sizeof(da));
+      da.length = (int64_t)dv.length;
+      da.n_buffers = 3;
+      da.buffers = dp->bufs.data();
+      da.release = release_array;
+      da.private_data = dp;
+      SchemaPriv* dsp = new SchemaPriv();
+      dsp->strings.reserve(2);
+      dsp->strings.push_back("u");
+      dsp->strings.push_back("");
+      ksp->dict_store.emplace_back();
+      ArrowSchema& ds = ksp->dict_store.back();
+      memset(&ds, 0, sizeof(ds));
+      ds.format = dsp->strings[0].c_str();
+      ds.name = dsp->strings[1].c_str();
+      ds.flags = 2;
+      ds.release = release_schema;
+      ds.private_data = dsp;
+    }
     for (auto& k : kp->kid_store) kp->kids.push_back(&k);
     for (auto& k : ksp->kid_store) ksp->kids.push_back(&k);
     memset(&ka, 0, sizeof(ka));
@@ -412,6 +483,7 @@ static int export_batch_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, uint32_
     ka.buffers = kp->bufs.data();
     ka.n_children = (int64_t)kp->kids.size();
     ka.children = kp->kids.empty() ? nullptr : kp->kids.data();
+    ka.dictionary = kp->dict_store.empty() ? nullptr : &kp->dict_store[0];
     ka.release = release_array;
     ka.private_data = kp;
 
@@ -426,6 +498,7 @@ static int export_batch_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, uint32_
     ks.flags = (v.null_count || co.parent >= 0 || sliced) ? 2 /* ARROW_FLAG_NULLABLE */ : 0;
     ks.n_children = (int64_t)ksp->kids.size();
     ks.children = ksp->kids.empty() ? nullptr : ksp->kids.data();
+    ks.dictionary = ksp->dict_store.empty() ? nullptr : &ksp->dict_store[0];
     ks.release = release_schema;
     ks.private_data = ksp;
   };

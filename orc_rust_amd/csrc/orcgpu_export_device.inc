@@ -42,13 +42,26 @@ struct DeviceColumn {
   const void* values = nullptr;   // strings: the bytes
   const void* offsets = nullptr;
   uint64_t values_bytes = 0;
+  // a dictionary-output column: the stripe's dictionary (DLPack buffers 3 and 4)
+  bool has_dict = false;
+  const void* dict_offsets = nullptr;
+  const void* dict_values = nullptr;
+  uint64_t dict_len = 0, dict_bytes = 0;
 };
 
 // private_data of a child array: it may be moved out of its parent and then lives, and is released, on its own
 struct DeviceChildPriv {
   orcgpu_hold::Hold* hold = nullptr;
   const void* bufs[3] = {nullptr, nullptr, nullptr};
+  // a dictionary-output column: ArrowArray::dictionary, a Utf8 array over the stripe's entries.  It is part of the child, goes where
+  // the child is moved and is released with it; the memory it views is the result's, which the child's own reference keeps
+  bool has_dict = false;
+  ArrowArray dict;
+  const void* dict_bufs[3] = {nullptr, nullptr, nullptr};
 };
+void release_device_dictionary(ArrowArray* a) {
+  if (a) a->release = nullptr;  // (nothing of its own: see DeviceChildPriv)
+}
 // ... and of the struct array
 struct DeviceExportPriv {
   orcgpu_hold::Hold* hold = nullptr;
@@ -65,6 +78,7 @@ void release_device_child(ArrowArray* a) {
   DeviceChildPriv* p = static_cast<DeviceChildPriv*>(a->private_data);
   a->release = nullptr;
   if (p) {
+    if (p->has_dict && p->dict.release) p->dict.release(&p->dict);
     orcgpu_hold::hold_release(p->hold);
     delete p;
   }
@@ -166,6 +180,20 @@ static int export_batch_device_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, 
     ka.release = release_device_child;
     ka.private_data = kp;
     ap->kids.push_back(&ka);
+    orcgpu_dictionary_view dv;
+    memset(&dv, 0, sizeof(dv));
+    if (co.dict_out) {
+      orcgpu_result_dictionary_view(r, (uint32_t)c, &dv);
+      kp->has_dict = true;
+      kp->dict_bufs[1] = dv.offsets;
+      kp->dict_bufs[2] = dv.values;
+      memset(&kp->dict, 0, sizeof(kp->dict));
+      kp->dict.length = (int64_t)dv.length;
+      kp->dict.n_buffers = 3;
+      kp->dict.buffers = kp->dict_bufs;
+      kp->dict.release = release_device_dictionary;
+      ka.dictionary = &kp->dict;
+    }
 
     DeviceColumn& dc = ap->cols[c];
     dc.rows = rows;
@@ -179,6 +207,11 @@ static int export_batch_device_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, 
     const bool is_float = co.orc_type == ORCGPU_T_FLOAT || co.orc_type == ORCGPU_T_DOUBLE;
     dc.code = co.is_string ? kDLInt : (co.is_bool ? kDLUInt : (is_float ? kDLFloat : kDLInt));
     dc.bits = co.is_string ? 32 : (co.is_bool ? 8 : (dc.wide ? 64 : (uint8_t)(co.width * 8)));
+    dc.has_dict = co.dict_out;
+    dc.dict_offsets = dv.offsets;
+    dc.dict_values = dv.values;
+    dc.dict_len = dv.length;
+    dc.dict_bytes = dv.values_bytes;
 
     SchemaPriv* ksp = new SchemaPriv();
     ksp->strings.reserve(2);
@@ -189,6 +222,21 @@ static int export_batch_device_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, 
     ks.format = ksp->strings[0].c_str();
     ks.name = ksp->strings[1].c_str();
     ks.flags = v.null_count ? 2 /* ARROW_FLAG_NULLABLE */ : 0;
+    if (co.dict_out) {
+      SchemaPriv* dsp = new SchemaPriv();
+      dsp->strings.reserve(2);
+      dsp->strings.push_back("u");
+      dsp->strings.push_back("");
+      ksp->dict_store.emplace_back();
+      ArrowSchema& ds = ksp->dict_store.back();
+      memset(&ds, 0, sizeof(ds));
+      ds.format = dsp->strings[0].c_str();
+      ds.name = dsp->strings[1].c_str();
+      ds.flags = 2;
+      ds.release = release_schema;
+      ds.private_data = dsp;
+      ks.dictionary = &ksp->dict_store[0];
+    }
     ks.release = release_schema;
     ks.private_data = ksp;
     sp->kids.push_back(&ks);
@@ -275,6 +323,13 @@ int orcgpu_device_array_dlpack(const struct ArrowDeviceArray* array, uint32_t co
   } else if (buffer == 2 && dc.is_string) {
     data = dc.values;
     shape[0] = (int64_t)dc.values_bytes;
+  } else if (buffer == 3 && dc.has_dict) {
+    data = dc.dict_offsets;
+    dt = DLDataType{kDLInt, 32, 1};
+    shape[0] = data ? (int64_t)dc.dict_len + 1 : 0;
+  } else if (buffer == 4 && dc.has_dict) {
+    data = dc.dict_values;
+    shape[0] = (int64_t)dc.dict_bytes;
   } else {
     return ORCGPU_INVALID_ARGUMENT;
   }

@@ -17,7 +17,16 @@ int plan_column_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_staged* s, orcgp
   Bump& RB = P.result_bump[si];
   const int t = c.orc_type;
   if (is_string_type(t)) {
-    co.offsets_off = RB.take((uint64_t)r->n_batches * ((uint64_t)r->batch + 1) * 4 + 16);
+    const bool dout = cp.dict_out;
+    // (dictionary output: the result holds one int32 key per row where the Utf8 path holds per-batch offsets)
+    if (dout) {
+      co.dict_decoded = true;
+      co.values_bytes = n * 4;
+      co.values_off = RB.take(n * 4 + 32);
+      cp.rowoff_off = P.scratch.take((uint64_t)r->n_batches * ((uint64_t)r->batch + 1) * 4 + 16);
+    } else {
+      co.offsets_off = RB.take((uint64_t)r->n_batches * ((uint64_t)r->batch + 1) * 4 + 16);
+    }
     cp.chartot_off = (uint32_t)P.n_chartot_slots;
     P.n_chartot_slots += 2ull * r->n_batches;
     cp.lens_off = P.scratch.take(n * 4 + 16);
@@ -32,6 +41,11 @@ int plan_column_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_staged* s, orcgp
       cp.dictn_idx = P.new_scalar(c.dictionary_size);
       cp.dictlens_off = P.scratch.take((uint64_t)c.dictionary_size * 8 + 16);
       cp.dictoff_off = P.scratch.take(((uint64_t)c.dictionary_size + 1) * 4 + 16);
+      if (dout) {
+        // the file's dictionary, entry for entry: its offsets are formed where they stay, its bytes are copied behind them
+        co.dict_offsets_off = RB.take(((uint64_t)c.dictionary_size + 1) * 4 + 16);
+        co.dict_values_off = RB.take(cp.dict.len_upper + ORC_PAD);
+      }
       cp.dicttotal_idx = P.new_scalar(0);
       cp.job_length = add_job(P, vcls, class_codec(vcls), false, 64, 8, cp.length, cp.dictn_idx, c.dictionary_size, si, ci, ORCGPU_S_LENGTH);
       P.jobs[cp.job_length].out_scratch_off = cp.dictlens_off;
@@ -42,14 +56,21 @@ int plan_column_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_staged* s, orcgp
       P.jobs[cp.job_data].out_scratch_off = cp.dense_off;
       cp.dense_off += (uint64_t)cp.data.skip_values * cp.key_bytes;
       cp.is_dict = true;
-      co.values_in_chars = true;
+      co.values_in_chars = !dout;
     } else {
       cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
       cp.job_length = add_job(P, vcls, class_codec(vcls), false, 64, 8, cp.length, cp.nonnull_idx, n, si, ci, ORCGPU_S_LENGTH);
       P.jobs[cp.job_length].out_scratch_off = cp.dense_off;
       cp.dense_off += 8ull * cp.length.skip_values;
-      co.values_bytes = cp.data.len_upper;
-      co.values_off = RB.take(cp.data.len_upper + ORC_PAD);
+      // (dictionary output of a DIRECT stripe: the identity dictionary -- the DATA bytes are its bytes, one entry per non-null row)
+      uint64_t bytes_off = RB.take(cp.data.len_upper + ORC_PAD);
+      if (dout) {
+        co.dict_values_off = bytes_off;
+        co.dict_offsets_off = RB.take((n + 1) * 4 + 16);
+      } else {
+        co.values_bytes = cp.data.len_upper;
+        co.values_off = bytes_off;
+      }
       cp.nonascii_idx = P.new_scalar(0);
       // a compressed DATA stream read from its first byte: decompressed where its bytes belong (lineitem's l_comment: 2 GB a step
       // that were written to the workspace, read again and written to the result)
@@ -57,7 +78,7 @@ int plan_column_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_staged* s, orcgp
         for (size_t k = P.decomp.size(); k-- > 0;)
           if (P.decomp[k].st == cp.data.src && P.decomp[k].stripe == s) {
             P.decomp[k].result_index = cp.stripe;
-            P.decomp[k].result_off = co.values_off;
+            P.decomp[k].result_off = bytes_off;
             cp.data.in_result = true;
             break;
           }
@@ -125,12 +146,13 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
   const int t = cp.c.orc_type;
   if (is_string_type(t)) {
     int32_t* lens = reinterpret_cast<int32_t*>(S + cp.lens_off);
-    int32_t* offsets = reinterpret_cast<int32_t*>(r->arena[ctx->lane_id].p + co.offsets_off);
+    uint8_t* const arena = r->arena[ctx->lane_id].p;
+    int32_t* offsets = reinterpret_cast<int32_t*>(cp.dict_out ? S + cp.rowoff_off : arena + co.offsets_off);
     unsigned long long* chartot = d_chartot + cp.chartot_off;
     unsigned long long* charbase = chartot + r->n_batches;
     const bool utf8 = t != ORCGPU_T_BINARY;
     if (cp.is_dict) {
-      int32_t* doff = reinterpret_cast<int32_t*>(S + cp.dictoff_off);
+      int32_t* doff = reinterpret_cast<int32_t*>(cp.dict_out ? arena + co.dict_offsets_off : S + cp.dictoff_off);
       const uint8_t* dbytes = plain_ptr(cp.dict, S);
       unsigned long long* derr = reinterpret_cast<unsigned long long*>(d_scalars + cp.dicterr_idx);
       fin.add<dict_offsets_body, 256>(0, 1, true, (const int64_t*)(S + cp.dictlens_off), (const uint64_t*)d_scalars, cp.dictn_idx,
@@ -141,6 +163,11 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
         fin.add<utf8_boundaries_body, 256>(2, dn, false, dbytes, (const int32_t*)doff, (const unsigned long long*)nullptr,
                                            (const unsigned long long*)nullptr, dn, (uint32_t)std::min<uint64_t>(dn, 0xffffffffu), (const uint64_t*)d_scalars,
                                            cp.dicttotal_idx, cp.dict.len_idx, derr, (const uint64_t*)nullptr);
+      }
+      if (cp.dict_out) {
+        // (the entries' bytes as they are; the keys follow behind the finishers: launch_dict_keys)
+        if (cp.dict.len_upper) fin.add<copy_bytes_body, 256>(0, (cp.dict.len_upper + 15) / 16, false, dbytes, arena + co.dict_values_off, cp.dict.len_upper);
+        return ORCGPU_OK;
       }
       // keys -> lengths -> offsets -> gather run for all dictionary columns of the call together: launch_dict_rows
       P.pending_gathers.push_back((int)(&cp - P.cols.data()));
@@ -153,7 +180,7 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
     }
     fin.add<batch_base_body, 256>(2, 1, true, (const unsigned long long*)chartot, charbase, r->n_batches, d_scalars + cp.dictbytes_idx);
     if (!cp.is_dict) {
-      uint8_t* values = r->arena[ctx->lane_id].p + co.values_off;
+      uint8_t* values = arena + (cp.dict_out ? co.dict_values_off : co.values_off);
       const uint8_t* src = cp.data.in_result ? values : plain_ptr(cp.data, S);
       fin.add<string_data_check_body, 64>(3, (uint64_t)(r->n_batches + 63) / 64, true, (const unsigned long long*)chartot,
                                           (const unsigned long long*)charbase, r->n_batches, (const uint64_t*)d_scalars, cp.data.len_idx, r->batch, err);
@@ -215,6 +242,40 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
     fin.add<decimal_finish_body, 256>(5, nr, false, (const __int128*)dense, (const int32_t*)(S + cp.dense2_off), vbits, rank,
                                       reinterpret_cast<__int128*>(r->arena[ctx->lane_id].p + co.values_off), nr, cp.c.scale);
     return ORCGPU_OK;
+  }
+  return ORCGPU_OK;
+}
+
+// Dictionary output (ORCGPU_ARROW_DICTIONARY_UTF8), behind the finishers: one launch per column writes the stripe's int32 keys.
+// A DICTIONARY stripe: the DATA ids, spaced over the rows and bounds-checked against the dictionary size on the device.  A
+// DIRECT stripe: a valid row's rank among the valid rows, and with it entry `rank` of the identity dictionary's offsets.
+// Nothing is sized on the host: keys and dictionary lie in the result's arena, at places known when the call was planned.
+int launch_dict_keys(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint64_t* d_scalars, unsigned long long* d_chartot) {
+  for (auto& cp : P.cols) {
+    if (cp.col < 0 || !cp.dict_out || !cp.n_rows) continue;
+    orcgpu_result* r = P.results[cp.stripe];
+    ColumnOut& co = r->cols[cp.col];
+    uint8_t* const arena = r->arena[ctx->lane_id].p;
+    DictKeysJob j{};
+    j.dense = cp.is_dict ? S + cp.dense_off : nullptr;
+    j.vbits = cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr;
+    j.rank = cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr;
+    j.keys = reinterpret_cast<int32_t*>(arena + co.values_off);
+    j.err = reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx);
+    j.dict_err = reinterpret_cast<const unsigned long long*>(d_scalars + cp.dicterr_idx);
+    j.scalars = d_scalars;
+    j.n_rows = cp.n_rows;
+    j.batch = r->batch;
+    j.key_bytes = cp.key_bytes;
+    j.dict_n_idx = cp.dictn_idx;
+    if (!cp.is_dict) {
+      j.row_offsets = reinterpret_cast<const int32_t*>(S + cp.rowoff_off);
+      j.charbase = d_chartot + cp.chartot_off + r->n_batches;
+      j.dict_off = reinterpret_cast<int32_t*>(arena + co.dict_offsets_off);
+      j.nonnull_idx = cp.nonnull_idx;
+      j.total_idx = cp.dictbytes_idx;
+    }
+    HIP_TRY(ctx, launch(dict_keys_kernel, (cp.n_rows + DICT_PER - 1) / DICT_PER, false, 256, ctx->stream, j));
   }
   return ORCGPU_OK;
 }
@@ -388,6 +449,12 @@ void resolve_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_result* r, const ui
   } else if (is_string_type(t) && cp.n_rows) {
     co.char_total.assign(h_chartot + cp.chartot_off, h_chartot + cp.chartot_off + r->n_batches);
     co.char_base.assign(h_chartot + cp.chartot_off + r->n_batches, h_chartot + cp.chartot_off + 2ull * r->n_batches);
+    if (cp.dict_out) {
+      uint64_t nulls = 0;
+      for (auto v : co.null_counts) nulls += v;
+      co.dict_len = cp.is_dict ? cp.c.dictionary_size : cp.n_rows - nulls;
+      co.dict_bytes = std::min<uint64_t>(h_scalars[cp.is_dict ? cp.dicttotal_idx : cp.dictbytes_idx], 0x7fffffffull);
+    }
     if (cp.is_dict) {
       unsigned long long de = h_scalars[cp.dicterr_idx];
       if (de != RLE_NO_ERR) consider((int)ORC_E_ARROW == (int)(de & 0xff) ? ORCGPU_ARROW : (int)(de & 0xff), 0u);
@@ -427,6 +494,7 @@ uint64_t result_column_bytes(const orcgpu_result* r, const ColumnOut& co) {
     b += (r->n_rows + 7) / 8;
   } else {
     b += co.values_bytes;
+    if (co.dict_out) b += (co.dict_len + 1) * 4 + co.dict_bytes;  // the stripe's dictionary, once
   }
   for (uint32_t i = 0; i < r->n_batches; i++)
     if (co.null_counts[i]) b += (std::min<uint64_t>(r->batch, r->n_rows - (uint64_t)i * r->batch) + 7) / 8;

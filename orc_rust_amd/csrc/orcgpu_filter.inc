@@ -10,7 +10,8 @@ namespace {
 
 int enc_scan(orcgpu_ctx* ctx, hipStream_t st, const uint32_t* d_in, uint64_t count, uint64_t* d_sums, uint64_t* d_total, uint64_t* d_out);
 
-int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept) {
+int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept,
+                       const char* const* column_names = nullptr, uint32_t n_names = 0) {
   if (rows_seen) *rows_seen = 0;
   if (rows_kept) *rows_kept = 0;
   if (r->status) return r->status;  // a failed decode is left as it is
@@ -108,6 +109,11 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   }
   for (auto& in : plan.prog) {  // (the plan was compiled against these columns' types; what the decode made of them must fit)
     if (in.op > FOP_CMP_STRING) continue;
+    if (in.col < nc && r->cols[in.col].dict_out) {  // (string predicates evaluated on the entries: not yet)
+      if (column_names && in.col < n_names) set_err(ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[in.col]);
+      else set_err(ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", r->cols[in.col].column_id);
+      return ORCGPU_UNSUPPORTED;
+    }
     const uint32_t want = in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : FKIND_STRING;
     if (in.col >= nc || fcols[in.col].kind != want) {
       set_err(ctx, "row filter: column %u is not decoded to the type its comparison needs", in.col < nc ? r->cols[in.col].column_id : in.col);
@@ -157,7 +163,7 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   std::vector<FilterGatherJob> jobs(nc);
   std::vector<uint64_t> obase((size_t)nc * nb_max, 0);
   struct Place {
-    uint64_t validity = 0, values = 0, offsets = 0;
+    uint64_t validity = 0, values = 0, offsets = 0, dict_offsets = 0, dict_values = 0;
     bool has_validity = false;
   };
   std::vector<Place> place(nc);
@@ -185,6 +191,10 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
       p.offsets = a.take((uint64_t)nbo * (B + 1) * 4 + 16);
       p.values = a.take(bytes + 16);
     } else p.values = a.take(kept * co.width + 16);
+    if (co.dict_out && co.dict_decoded) {  // the stripe's dictionary goes along untouched: this arena is all that is copied back
+      p.dict_offsets = a.take((co.dict_len + 1) * 4 + 16);
+      p.dict_values = a.take(co.dict_bytes + 16);
+    }
   }
   r->filt_used = kept ? a.off : 0;
   if (kept) {
@@ -203,6 +213,13 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
       j.out_chars = O + p.values;
       j.out_offsets = reinterpret_cast<int32_t*>(O + p.offsets);
       j.out_char_base = reinterpret_cast<const unsigned long long*>(X + o_obase) + (uint64_t)c * nb_max;
+    }
+    for (uint32_t c = 0; c < nc; c++) {
+      const ColumnOut& co = r->cols[c];
+      if (!co.dict_out || !co.dict_decoded) continue;
+      const uint8_t* A = r->arena[co.lane].p;
+      HIP_TRY(ctx, hipMemcpyAsync(O + place[c].dict_offsets, A + co.dict_offsets_off, (co.dict_len + 1) * 4, hipMemcpyDeviceToDevice, st));
+      if (co.dict_bytes) HIP_TRY(ctx, hipMemcpyAsync(O + place[c].dict_values, A + co.dict_values_off, co.dict_bytes, hipMemcpyDeviceToDevice, st));
     }
     std::vector<uint8_t> up2(o_obase + obase.size() * 8 - o_jobs, 0);
     memcpy(up2.data(), jobs.data(), (size_t)nc * sizeof(FilterGatherJob));
@@ -223,6 +240,15 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
     co.validity_off = p.validity;
     co.values_off = p.values;
     co.offsets_off = p.offsets;
+    if (co.dict_out) {
+      if (!kept) {  // (no batch is left to refer to it)
+        co.dict_len = co.dict_bytes = 0;
+        co.dict_decoded = false;
+      }
+      co.dict_offsets_off = kept ? p.dict_offsets : 0;
+      co.dict_values_off = kept ? p.dict_values : 0;
+      if (co.dict_decoded) r->arrow_bytes += (co.dict_len + 1) * 4 + co.dict_bytes;
+    }
     co.null_counts.assign(nbo, 0);
     co.char_base.assign(co.is_string ? nbo : 0, 0);
     co.char_total.assign(co.is_string ? nbo : 0, 0);
@@ -275,5 +301,5 @@ extern "C" int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orc
     set_err(ctx, "%s", plan.err);
     return rc;
   }
-  return result_filter_plan(ctx, r, plan, nullptr, rows_kept);
+  return result_filter_plan(ctx, r, plan, nullptr, rows_kept, column_names, n_columns);
 }

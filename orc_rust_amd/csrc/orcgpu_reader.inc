@@ -17,6 +17,7 @@
 #include <memory>
 
 #include "orcgpu_meta.inc"
+#include "orcgpu_dictionary_names.inc"
 namespace orcgpu_host {
 
 struct SectionCopy {
@@ -280,6 +281,8 @@ struct orcgpu_reader {
   int shard_mode = ORCGPU_SHARD_STRIPES;
   std::vector<int> col_target;
   std::vector<uint32_t> col_precision, col_scale;
+  std::vector<std::string> dict_names;        // orcgpu_reader_set_dictionary_columns: root columns (file names) read as Dictionary(Int32, Utf8)
+  std::vector<uint8_t> col_dict;              // ... per projected column (col_ids order)
   bool has_selection = false;                 // with_row_selection
   std::vector<RowSel> selection;              // what is left of it for the stripes to come
   // ---- read-ahead (the analogue of async_arrow_reader.rs:165-280, whose state machine fetches the next stripe while the
@@ -350,10 +353,12 @@ int reader_build(orcgpu_reader* rd) {
   rd->col_target.clear();
   rd->col_precision.clear();
   rd->col_scale.clear();
+  rd->col_dict.clear();
   if (rd->md.types.empty()) return ORCGPU_OK;
   const OrcType& root = rd->md.types[0];
   // the projected root columns, in file order; with_schema: columns and fields are zipped (array_decoder/mod.rs:577-582): columns
   // beyond the schema's fields are not decoded
+  std::vector<std::string> dict_seen;  // the dictionary columns (orcgpu_reader_set_dictionary_columns) met among the columns read
   std::vector<size_t> taken;
   for (size_t k = 0; k < root.subtypes.size(); k++) {
     const std::string nm = k < root.field_names.size() ? root.field_names[k] : std::string();
@@ -414,6 +419,9 @@ int reader_build(orcgpu_reader* rd) {
       rd->col_target.push_back(target);
       rd->col_precision.push_back(hp);
       rd->col_scale.push_back(hs);
+      const bool as_dict = depth == 0 && std::find(rd->dict_names.begin(), rd->dict_names.end(), name) != rd->dict_names.end();
+      rd->col_dict.push_back(as_dict ? 1 : 0);
+      if (as_dict) dict_seen.push_back(name);
       const uint32_t me = (uint32_t)rd->col_ids.size();
       if (nested && (!hint || target != ORCGPU_ARROW_OTHER))
         for (size_t f = 0; f < t.subtypes.size(); f++) {
@@ -427,6 +435,12 @@ int reader_build(orcgpu_reader* rd) {
     int rc = add(cid, 0, std::string(), 0, rd->has_schema ? &rd->schema_tree[root_pos] : nullptr);
     if (rc) return rc;
   }
+  // (every dictionary column must be among the columns read)
+  for (auto& dn : rd->dict_names)
+    if (std::find(dict_seen.begin(), dict_seen.end(), dn) == dict_seen.end() && rd->shard_mode != ORCGPU_SHARD_COLUMNS) {
+      set_err(rd->ctx, "dictionary column '%s' is not among the projected columns", dn.c_str());
+      return ORCGPU_INVALID_ARGUMENT;
+    }
   return ORCGPU_OK;
 }
 
@@ -472,6 +486,8 @@ int reader_stage_rows(orcgpu_reader* rd, const StripeFooter& sf, const std::vect
       c.arrow_precision = rd->col_precision[k];
       c.arrow_scale = rd->col_scale[k];
     }
+    // (dictionary output: with_schema's field for such a column is Utf8, or there is no schema; any other field stays and mismatches)
+    if (rd->col_dict[cols.size()] && (c.arrow_target == ORCGPU_ARROW_DEFAULT || c.arrow_target == ORCGPU_ARROW_UTF8)) c.arrow_target = ORCGPU_ARROW_DICTIONARY_UTF8;
     cols.push_back(c);
   }
   orcgpu_stripe_desc d{};
@@ -815,7 +831,20 @@ int reader_compile_filter(orcgpu_reader* rd) {
   }
   const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan);
   if (rc) set_err(rd->ctx, "%s", rd->filter_plan.err);
-  return rc;
+  if (rc) return rc;
+  // a comparison on a dictionary-output column would have to be evaluated on the entries: refused, by name, before anything is read
+  for (auto& in : rd->filter_plan.prog) {
+    if (in.op > FOP_CMP_STRING || in.col >= names.size()) continue;
+    size_t root = 0;
+    for (size_t k = 0; k < rd->col_ids.size(); k++) {
+      if (rd->col_parent[k]) continue;
+      if (root++ == in.col && rd->col_dict[k]) {
+        set_err(rd->ctx, "row filter: column '%s' is read as a dictionary column (orcgpu_reader_set_dictionary_columns): a comparison on it is not supported", names[in.col]);
+        return ORCGPU_UNSUPPORTED;
+      }
+    }
+  }
+  return ORCGPU_OK;
 }
 
 // A result the caller is done with, to decode a later stripe into (rd->m is held by a reader that reads ahead)
@@ -1114,6 +1143,33 @@ int orcgpu_reader_set_projection(orcgpu_reader* rd, const char* const* names, ui
   rd->project_all = false;
   rd->projected_names.clear();
   for (uint32_t i = 0; i < n; i++) rd->projected_names.emplace_back(names[i]);
+  return ORCGPU_OK;
+}
+int orcgpu_reader_set_dictionary_columns(orcgpu_reader* rd, const char* const* names, uint32_t n) {
+  if (!rd || rd->built || (n && !names)) return ORCGPU_INVALID_ARGUMENT;
+  std::vector<std::string> list;
+  int rc = ORCGPU_OK;
+  if (n) {
+    char msg[256] = "";
+    std::vector<std::string> roots;
+    std::vector<int32_t> kinds;
+    if (!rd->md.types.empty()) {
+      const orcgpu_host::OrcType& root = rd->md.types[0];
+      for (size_t k = 0; k < root.subtypes.size(); k++) {
+        roots.push_back(k < root.field_names.size() ? root.field_names[k] : std::string());
+        kinds.push_back(root.subtypes[k] < rd->md.types.size() ? rd->md.types[root.subtypes[k]].kind : -1);
+      }
+    }
+    std::vector<const char*> rp;
+    for (auto& s : roots) rp.push_back(s.c_str());
+    rc = orcgpu_host::check_dictionary_names(names, n, rp.data(), kinds.data(), (uint32_t)rp.size(), msg, sizeof(msg));
+    if (rc) {
+      set_err(rd->ctx, "%s", msg);
+      return rc;
+    }
+    for (uint32_t i = 0; i < n; i++) list.emplace_back(names[i]);
+  }
+  rd->dict_names.swap(list);
   return ORCGPU_OK;
 }
 int orcgpu_reader_set_projection_roots(orcgpu_reader* rd, const uint32_t* roots, uint32_t n) {

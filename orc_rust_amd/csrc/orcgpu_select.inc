@@ -98,6 +98,7 @@ int result_select_batches(orcgpu_ctx* ctx, orcgpu_result* r, std::vector<SelBatc
       r->arrow_bytes += co.is_string ? co.sel_char_total[k] + 4 * (rows + 1) : (co.is_list ? 4 * (rows + 1) : (co.is_bool ? (rows + 7) / 8 : rows * co.width));
       if (co.sel_nulls[k]) r->arrow_bytes += (rows + 7) / 8;
     }
+    if (co.dict_out && nb) r->arrow_bytes += (co.dict_len + 1) * 4 + co.dict_bytes;  // the stripe's dictionary, once
   }
   if (r->status) {
     // The stripe failed in uniform batch err_batch, i.e. at or behind row err_batch * batch_size: the selected batches that

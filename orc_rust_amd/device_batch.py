@@ -60,11 +60,32 @@ def _value_dtype(t):
     """torch dtype of a fixed-width column's values (what an empty batch's tensor gets; DLPack says it otherwise)"""
     import pyarrow as pa
     import torch
+    if pa.types.is_dictionary(t):  # (with_dictionary_columns: the int32 keys)
+        return torch.int32
     for test, dtype in ((pa.types.is_int8, torch.int8), (pa.types.is_int16, torch.int16), (pa.types.is_int32, torch.int32),
                         (pa.types.is_date32, torch.int32), (pa.types.is_float32, torch.float32), (pa.types.is_float64, torch.float64)):
         if test(t):
             return dtype
     return torch.int64
+
+
+class DeviceDictionary:
+    """The dictionary of a dictionary column (ArrowReaderBuilder.with_dictionary_columns), one per stripe and shared by the
+    stripe's batches: `offsets` (int32, entries + 1, from 0) and `data` (uint8) in Arrow Utf8 layout, views of the decoder's
+    buffers.  Entry k is data[offsets[k]:offsets[k + 1]]."""
+
+    def __init__(self, column):
+        import torch
+        self._column = column
+        self.offsets = column._dict_buffer(3, torch.int32)
+        self.data = column._dict_buffer(4, torch.uint8, int(self.offsets[-1]))
+        self.num_entries = int(self.offsets.shape[0]) - 1
+
+    def to_pyarrow(self):
+        """A host copy as a pyarrow.StringArray"""
+        import pyarrow as pa
+        bufs = [None, pa.py_buffer(self.offsets.cpu().numpy().tobytes()), pa.py_buffer(self.data.cpu().numpy().tobytes())]
+        return pa.Array.from_buffers(pa.string(), self.num_entries, bufs, null_count=0)
 
 
 class DeviceColumn:
@@ -103,6 +124,42 @@ class DeviceColumn:
             if _PyCapsule_IsValid(cap, _DLTENSOR):
                 C.cast(out.value + 56, C.POINTER(C.CFUNCTYPE(None, C.c_void_p)))[0](out.value)  # DLManagedTensor::deleter
             raise
+
+    def _dict_buffer(self, which, dtype, n_bytes=None):
+        """buffer 3 (offsets) or 4 (bytes, n_bytes of them by the offsets) of the column's dictionary.  The library makes no tensor
+        over nothing, so what the exported array itself says is not there is made here: one zero offset for a stripe that decoded
+        no rows (the dictionary array has no offsets buffer), no bytes for a dictionary whose last offset is 0.  Every other
+        refusal of the library is an error."""
+        import torch
+        b = self._batch
+        if b._array is None:
+            raise ValueError("the batch has been released")
+        child = b._array.array.children[self._index].contents
+        if not child.dictionary:
+            raise ValueError("column %d carries no dictionary" % self._index)
+        d = C.cast(child.dictionary, C.POINTER(ArrowArrayStruct)).contents
+        if which == 3 and not d.buffers[1]:
+            return torch.zeros(1, dtype=dtype, device=b.device)
+        if which == 4 and n_bytes == 0:
+            return torch.empty(0, dtype=dtype, device=b.device)
+        out = C.c_void_p()
+        rc = b._ctx.L.orcgpu_device_array_dlpack(C.byref(b._array), self._index, which, C.byref(out))
+        b._ctx._check(rc)
+        cap = _capsule(out.value)
+        try:
+            return torch.from_dlpack(cap)
+        except Exception:
+            if _PyCapsule_IsValid(cap, _DLTENSOR):
+                C.cast(out.value + 56, C.POINTER(C.CFUNCTYPE(None, C.c_void_p)))[0](out.value)  # DLManagedTensor::deleter
+            raise
+
+    @property
+    def dictionary(self):
+        """A dictionary column's DeviceDictionary (its `values` are the int32 keys, 0 in null rows); None for every other column"""
+        import pyarrow as pa
+        if not pa.types.is_dictionary(self.type):
+            return None
+        return self._cached("dictionary", lambda: DeviceDictionary(self))
 
     def _cached(self, key, make):
         if key not in self._cache:
@@ -166,6 +223,9 @@ class DeviceColumn:
             return pa.py_buffer(t.cpu().numpy().tobytes()) if t is not None else None
 
         bufs = [host(self.validity_bits)]
+        if pa.types.is_dictionary(self.type):
+            keys = pa.Array.from_buffers(pa.int32(), self.num_rows, bufs + [host(self.values)], null_count=self.null_count)
+            return pa.DictionaryArray.from_arrays(keys, self.dictionary.to_pyarrow())
         if self._is_var():
             bufs += [host(self.offsets), host(self.data)]
         elif pa.types.is_boolean(self.type):
