@@ -24,18 +24,36 @@
 //     match lengths, literal lengths --, so a lane's values are contiguous: four 16-byte stores) -- in that order: the wait
 //     for the fetched bytes is a wait for everything issued before them, and at the top of a visit all of it is 16 steps old.
 //     A step reads its window from the ring (one unaligned 8-byte LDS read) a step AHEAD, beside the step before.
-// LDS per wavefront: 16 x (2560 + 528) bytes + 3840 for the values on their way out + 512 of base values = 52.5 KiB: three wavefronts (48 chains) per CU.
+// LDS per wavefront: 16 x (2560 + 528) bytes + 1536 for the values on their way out = 49.75 KiB: three wavefronts (48 chains) per
+// CU, and what they leave of the CU's 160 KiB holds a workgroup of zstd_literals_kernel, the kernel that runs beside this one
+// (ZQ_LDS, below).  The base values of the length codes sit in registers.
 // Blocks are dealt out in the order of their sequence counts (the host sorts them), so the chains of a wavefront end together.
 // Status words are those of zstd_entropy_kernel; the execution kernel (lz_exec_wave_kernel) runs behind this kernel.
 #pragma once
 
 #define ZQ_BCAST(v, k) ((uint32_t)__builtin_amdgcn_update_dpp((int)(v), (int)(v), (k) * 0x55, 0xf, 0xf, false))  // lane k of the quad (every lane is written: the old value is a don't-care, naming the source saves the move that would clear it)
-#define ZQ_STEPS 16  // steps between two visits to memory (16 values = one 64-byte run of a lane's array: put_vals)
+#define ZQ_STEPS 16  // steps between two visits to memory (a multiple of 8: put_vals writes eight records a quad at a time).  8 halves the rings and was measured slower: DESIGN 5
 #define ZQ_RING (ZQ_STEPS > 8 ? 512 : 256)  // bytes of a chain's stream held in LDS: stream byte b lives at ring[b & (ZQ_RING - 1)]
 #define ZQ_RING_BYTES (ZQ_RING + 16)        // (+ the first 8 bytes again behind the end: a window may start at the last byte; 16-byte aligned)
 #define ZQ_NEED ((ZQ_STEPS * 89 + 7) / 8 + 15)  // bytes below the cursor a group of steps may take (89 bits a step at the very most) + a window
 #define ZQ_ROOM (ZQ_RING - 66)              // the next 64 bytes fit below `fill` once the cursor is within this many bytes of it
-#define ZQ_XROW 80                          // bytes of a row of the values on their way out (16 values + padding: see put_vals)
+#define ZQ_XROW 32                          // bytes of a row of the values on their way out (8 values: see put_vals)
+static_assert(ZQ_STEPS % 8 == 0 && ZQ_STEPS <= 16, "put_vals: eight records a quad at a time; ZQ_NEED bytes must fit in the ring");
+
+// The LDS budget.  This kernel and zstd_literals_kernel are launched to run beside each other, so a CU should hold both: three
+// wavefronts of this one (a fourth would need another 40 KiB of tables) and k workgroups of the other in what they leave.  A CU
+// has 160 KiB and hands it out in pieces of 1280 bytes (finer pieces only loosen what follows), so with L the bytes of a workgroup
+// here and 8192 (7 pieces) those of a literals workgroup:  3 * pieces(L) + 7 k <= 128, that is L <= 51200 for k = 1 and L <= 48640 for k = 2.  The tables (16 x 2560)
+// cannot shrink: a block of the size real files carry uses the largest logs.  Tables and 528-byte rings alone are 49408, so k = 2
+// is out of reach at ZQ_STEPS 16 whatever else goes; with the rows of put_vals L = 50944 (40 pieces) and k = 1.  The 272-byte
+// rings of ZQ_STEPS 8 give L = 46848 (37 pieces) and k = 2; k = 3 would need 35 pieces.
+#define ZQ_LDS_PIECE 1280u
+#define ZQ_LDS_PIECES(bytes) (((bytes) + ZQ_LDS_PIECE - 1u) / ZQ_LDS_PIECE)
+#define ZQ_LDS (16u * ZL_CELLS * 2u + 16u * ZQ_RING_BYTES + 48u * ZQ_XROW)  // all the kernel declares
+#define ZQ_LITS_BESIDE (ZQ_STEPS > 8 ? 1u : 2u)  // literals workgroups beside three wavefronts of this kernel (k)
+static_assert((3u * ZQ_LDS_PIECES(ZQ_LDS) + ZQ_LITS_BESIDE * ZQ_LDS_PIECES(sizeof(ZLitLds))) * ZQ_LDS_PIECE <= 160u * 1024u,
+              "three sequences wavefronts and the literals workgroups beside them no longer fit in a CU's LDS");
+static_assert(3u * ZQ_LDS + ZQ_LITS_BESIDE * 8192u <= 160u * 1024u && sizeof(ZLitLds) <= 8192u, "the same without the rounding");
 
 __device__ __forceinline__ void zstd_seq_quads_body(const ZBlock* __restrict__ blocks, uint32_t n_chains, const uint16_t* ztab_, const ZSeqHdr* zhdr_, uint32_t* status_out_,
                                                     uint16_t* tabs, uint8_t* rings, uint8_t* xpose) {
@@ -88,10 +106,10 @@ __device__ __forceinline__ void zstd_seq_quads_body(const ZBlock* __restrict__ b
   const uint32_t size = 1u << log, c0 = 31u - log;  // state bits of a cell = clz(its state number) - (31 - log)
   // base values per symbol: lane s holds symbol s (read by ds_bpermute, off the chain)
   const uint32_t cA = r == 1 ? 32u : 16u, cC = r == 1 ? 43u : 25u, cD = r == 1 ? 36u : 19u;  // (extra bits of a length code: see the loop)
-  // base values per length code: in LDS, looked up when the values leave (put_vals) -- off the chain, sixteen steps at a time
-  uint32_t* const btab = reinterpret_cast<uint32_t*>(xpose + 48 * ZQ_XROW);  // [0, 64) literal lengths, [64, 128) match lengths
-  btab[lane] = lane < 36 ? Z_LL_BASE[lane] : 0u;
-  btab[64 + lane] = lane < 53 ? Z_ML_BASE[lane] : 0u;
+  // base values per length code: lane s holds code s, looked up when the values leave (put_vals: ds_bpermute, which takes no LDS
+  // memory) -- off the chain, ZQ_STEPS steps at a time
+  const uint32_t ll_base = lane < 36 ? Z_LL_BASE[lane] : 0u, ml_base = lane < 53 ? Z_ML_BASE[lane] : 0u;
+  auto base_of = [](uint32_t bases, uint32_t code) -> uint32_t { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(code << 2), (int)bases); };  // (a code has 6 bits)
   // this lane's share of the field positions: its extra bits end behind those of the roles below it, its state bits behind
   // the extra bits of all and the state bits of the roles above it (the states follow each other LL, ML, OF)
   const uint32_t mx1 = r >= 1 ? ~0u : 0u, mx2 = r >= 2 ? ~0u : 0u, ms1 = r <= 1 ? ~0u : 0u, ms0 = r == 0 ? ~0u : 0u;
@@ -165,30 +183,33 @@ __device__ __forceinline__ void zstd_seq_quads_body(const ZBlock* __restrict__ b
   // the chain took ~150 ns a step).  The three lanes of a quad put their values side by side through LDS (rows of 80 bytes: the
   // eight rows a 16-byte LDS store serves at once lie in different banks), every lane packs four sequences, and two instructions
   // write 64 contiguous bytes per quad each.  (The same transposition WITHOUT packing -- three arrays, whole 64-byte runs -- was
-  // no faster than the scattered stores.)
+  // no faster than the scattered stores.)  The rows hold EIGHT steps, not all sixteen, and are used twice a visit: whole rows of
+  // 80 bytes (3840 in all, with 512 of base values beside them) were what kept a workgroup of the literals kernel out of a CU
+  // that holds three wavefronts of this one (ZQ_LDS).  Rows of 32 bytes without padding meet in the banks -- on two instructions
+  // a visit, off the chain; LDS accesses of a wavefront execute in order, so the second half may overwrite the first behind its reads.
   uint32_t val[ZQ_STEPS];
-  uint8_t* const xrow = xpose + (cw * 3u + (r < 3 ? r : 0u)) * ZQ_XROW;  // this lane's row (values of steps 0..15)
-  const uint8_t* const xq = xpose + cw * 3u * ZQ_XROW + r * 8u;           // the quad's rows, at this lane's two steps of each half
+  uint8_t* const xrow = xpose + (cw * 3u + (r < 3 ? r : 0u)) * ZQ_XROW;  // this lane's row (values of eight steps)
+  const uint8_t* const xq = xpose + cw * 3u * ZQ_XROW + r * 8u;           // the quad's rows, at this lane's two steps
   auto put_vals = [&](uint32_t at) {  // the values of steps [at, at + ZQ_STEPS)
-    if (r < 3) {
 #pragma unroll
-      for (int k = 0; k < ZQ_STEPS / 4; k++) *reinterpret_cast<uint4*>(xrow + 16 * k) = make_uint4(val[4 * k], val[4 * k + 1], val[4 * k + 2], val[4 * k + 3]);
-    }
-    lds_order();
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
+    for (int h = 0; h < ZQ_STEPS / 8; h++) {
+      if (r < 3) {
+        *reinterpret_cast<uint4*>(xrow) = make_uint4(val[8 * h], val[8 * h + 1], val[8 * h + 2], val[8 * h + 3]);
+        *reinterpret_cast<uint4*>(xrow + 16) = make_uint4(val[8 * h + 4], val[8 * h + 5], val[8 * h + 6], val[8 * h + 7]);
+      }
+      lds_order();
       // lane j of the quad: sequences at + 8 h + 2 j and the one behind it
-      const uint2 o2 = *reinterpret_cast<const uint2*>(xq + 32 * h);
-      const uint2 m2 = *reinterpret_cast<const uint2*>(xq + ZQ_XROW + 32 * h);
-      const uint2 l2 = *reinterpret_cast<const uint2*>(xq + 2 * ZQ_XROW + 32 * h);
-      const uint32_t ma = btab[64 + (m2.x >> 16)] + (m2.x & 0xffffu), mb = btab[64 + (m2.y >> 16)] + (m2.y & 0xffffu);
-      const uint32_t la = btab[l2.x >> 16] + (l2.x & 0xffffu), lb = btab[l2.y >> 16] + (l2.y & 0xffffu);
+      const uint2 o2 = *reinterpret_cast<const uint2*>(xq);
+      const uint2 m2 = *reinterpret_cast<const uint2*>(xq + ZQ_XROW);
+      const uint2 l2 = *reinterpret_cast<const uint2*>(xq + 2 * ZQ_XROW);
+      lds_order();
+      const uint32_t ma = base_of(ml_base, m2.x >> 16) + (m2.x & 0xffffu), mb = base_of(ml_base, m2.y >> 16) + (m2.y & 0xffffu);
+      const uint32_t la = base_of(ll_base, l2.x >> 16) + (l2.x & 0xffffu), lb = base_of(ll_base, l2.y >> 16) + (l2.y & 0xffffu);
       const uint2 a = zseq_pack(o2.x, ma, la), b = zseq_pack(o2.y, mb, lb);
       const uint32_t i = at + 8u * (uint32_t)h + 2u * r;
       // (an array is padded to an even number of records: a pair that starts inside it ends inside its padding)
       if (i < nseq) *reinterpret_cast<uint4*>(so8 + i) = make_uint4(a.x, a.y, b.x, b.y);
     }
-    lds_order();
   };
   // (a quad without a chain, or behind the end of its chain, goes on decoding whatever it finds in its ring and stores nothing)
   for (uint32_t i0 = 0; i0 < maxn; i0 += ZQ_STEPS) {
@@ -266,6 +287,7 @@ extern "C" __global__ void __launch_bounds__(64) zstd_seq_quads_kernel(const ZBl
                                                                       const ZSeqHdr* zhdr_, uint32_t* status_out_) {
   __shared__ __attribute__((aligned(16))) uint16_t tabs[16 * ZL_CELLS];
   __shared__ __attribute__((aligned(16))) uint8_t rings[16 * ZQ_RING_BYTES];
-  __shared__ __attribute__((aligned(16))) uint8_t xpose[48 * ZQ_XROW + 512];  // (+ the base values of the length codes)
+  __shared__ __attribute__((aligned(16))) uint8_t xpose[48 * ZQ_XROW];
+  static_assert(sizeof(tabs) + sizeof(rings) + sizeof(xpose) == ZQ_LDS, "the LDS budget (ZQ_LDS) counts every array declared here");
   zstd_seq_quads_body(blocks, n_chains, ztab_, zhdr_, status_out_, tabs, rings, xpose);
 }
