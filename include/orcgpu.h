@@ -427,18 +427,22 @@ int orcgpu_reader_row_groups(const orcgpu_reader* r, uint64_t* read, uint64_t* t
  * NOT: one; comparisons and null tests: none). */
 enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_LE = 3, ORCGPU_PRED_GT = 4, ORCGPU_PRED_GE = 5, /* ComparisonOp */
        ORCGPU_PRED_IS_NULL = 6, ORCGPU_PRED_IS_NOT_NULL = 7, ORCGPU_PRED_AND = 8, ORCGPU_PRED_OR = 9, ORCGPU_PRED_NOT = 10 };
-/* PredicateValue (predicate.rs:29-47) */
+/* PredicateValue (predicate.rs:29-47), and two kinds the reference does not have:
+ *   ORCGPU_PV_DECIMAL128    s -> the 16 bytes of the unscaled value, little-endian two's complement, s_len = 16; i = the literal's
+ *                           scale, 0 .. 38; |unscaled| < 10^38.  Anything else is ORCGPU_INVALID_ARGUMENT (the message names the column).
+ *   ORCGPU_PV_TIMESTAMP_NS  i = nanoseconds since 1970-01-01T00:00:00 in the sense of the exported Arrow value: naive wall clock
+ *                           for a TIMESTAMP column, UTC for TIMESTAMP_INSTANT.  The literal's range is int64's: 1677-09-21 to 2262-04-11. */
 enum { ORCGPU_PV_BOOLEAN = 0, ORCGPU_PV_INT8 = 1, ORCGPU_PV_INT16 = 2, ORCGPU_PV_INT32 = 3, ORCGPU_PV_INT64 = 4, ORCGPU_PV_FLOAT32 = 5,
-       ORCGPU_PV_FLOAT64 = 6, ORCGPU_PV_UTF8 = 7 };
+       ORCGPU_PV_FLOAT64 = 6, ORCGPU_PV_UTF8 = 7, ORCGPU_PV_DECIMAL128 = 8, ORCGPU_PV_TIMESTAMP_NS = 9 };
 typedef struct {
   int32_t op;            /* ORCGPU_PRED_*                                                                 */
   uint32_t n_children;   /* AND / OR                                                                      */
   const char* column;    /* comparisons and null tests: the name of a projected root column               */
   int32_t value_type;    /* comparisons: ORCGPU_PV_*                                                       */
   int32_t value_is_null; /* ... Some / None                                                                */
-  int64_t i;             /* Boolean (0 / 1) and the integer kinds                                          */
+  int64_t i;             /* Boolean (0 / 1) and the integer kinds; Decimal128: the scale; TimestampNs      */
   double f;              /* Float32 / Float64                                                              */
-  const char* s;         /* Utf8: bytes, not necessarily terminated                                        */
+  const char* s;         /* Utf8: bytes, not necessarily terminated; Decimal128: the 16 bytes              */
   uint64_t s_len;
 } orcgpu_predicate_node;
 /* What the reader knows about one column of one stripe: the plain (decompressed) bytes of its ROW_INDEX stream, a
@@ -476,8 +480,14 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     through float first); IEEE rules: with a NaN on either side EQ / LT / LE / GT / GE are FALSE and NE is TRUE, -0.0 == 0.0.
  *     Boolean takes Boolean, false < true.  String / Varchar / Char / Binary take Utf8 and compare the decoded value as exported
  *     by unsigned byte, the shorter one being the smaller on a common prefix.  Any other pair: ORCGPU_MISMATCHED_SCHEMA.
- *   - Timestamp and Decimal columns may be projected and tested with IS [NOT] NULL; a comparison on them is ORCGPU_UNSUPPORTED
- *     (the message names the column).  A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
+ *   - Decimal takes Decimal128 and compares in exact rational order, unscaled_c * 10^-scale_c against unscaled_l * 10^-scale_l,
+ *     whatever the two scales.  Timestamp and Timestamp-instant take TimestampNs and compare as instants: the exported int64 in
+ *     its unit (s, ms, us, ns) against the literal's nanoseconds, exactly -- a literal between two values of the unit equals no
+ *     row.  The host brings the literal to the column's scale / unit (floor, with the operator adjusted where it does not
+ *     divide; clamped where it leaves int128), the device compares integers and rescales no row.  Any other literal kind on
+ *     these columns, and a Timestamp column decoded to Decimal128(38, 9), is ORCGPU_UNSUPPORTED (the message names the column);
+ *     a Decimal128 or TimestampNs literal on any other column is ORCGPU_MISMATCHED_SCHEMA.
+ *   - A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
  *   - A leaf naming a column that is not there, a leaf without a name, an unknown op, a node list that ends inside a node's
  *     children or goes on behind the root, and a predicate nested deeper than ORCGPU_FILTER_MAX_DEPTH levels (a leaf alone is
  *     one level): ORCGPU_INVALID_ARGUMENT.

@@ -7,6 +7,8 @@
 //                         post-order program (FilterInsn); a leaf yields two ballot words for the trip's 64 rows -- the rows
 //                         where it is TRUE and the rows where it is FALSE (neither: UNKNOWN) --, inner nodes combine words on
 //                         a per-wavefront stack with wave-uniform code.  Writes keep = T_root & live and its popcount.
+//                         A Decimal leaf compares the row's 16 bytes with a literal the host has brought to the column's scale,
+//                         a Timestamp leaf is the integer leaf on a literal in the column's unit: no row is ever rescaled.
 //   (enc_scan)            exclusive scan of the popcounts: the output row of every word's first kept row.
 //   filter_place_kernel   every kept row writes its stripe row at its output row: src_rows[], the gather's index list.
 //   filter_count_kernel   per (output batch, column): null count and string bytes -- what the host needs to lay the output out
@@ -114,6 +116,14 @@ filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
             lt = v < in.i;
             eq = v == in.i;
             gt = v > in.i;
+          } else if (in.op == FOP_CMP_DEC128) {
+            // one 16-byte load (row * 16 off a 256-byte aligned arena); the high words as signed, the low words as unsigned
+            const uint4 q = reinterpret_cast<const uint4*>(c.values)[row];
+            const long long vh = (long long)(((unsigned long long)q.w << 32) | q.z);
+            const unsigned long long vl = ((unsigned long long)q.y << 32) | q.x;
+            eq = vh == in.i && vl == in.lo;
+            lt = vh < in.i || (vh == in.i && vl < in.lo);
+            gt = !lt && !eq;
           } else {  // FOP_CMP_STRING
             const int32_t* o = c.offsets + u * (B + 1) + l;
             const uint32_t a = (uint32_t)o[0], len = (uint32_t)o[1] - a;

@@ -103,18 +103,22 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
       const bool is_int = ot == ORCGPU_T_BYTE || ot == ORCGPU_T_SHORT || ot == ORCGPU_T_INT || ot == ORCGPU_T_LONG || ot == ORCGPU_T_DATE;
       const bool is_float = ot == ORCGPU_T_FLOAT || ot == ORCGPU_T_DOUBLE;
       // (a value narrower or wider than the type's own -- with_schema -- is still compared as what it is: 1 / 2 / 4 / 8 bytes)
-      f.kind = is_int && co.width <= 8 ? FKIND_INT : (is_float && (co.width == 4 || co.width == 8) ? FKIND_FLOAT : FKIND_OTHER);
+      // (a Timestamp decoded to an int64 unit is compared as the integer it is; decoded to Decimal128(38, 9) it is not compared)
+      const bool is_ts = (ot == ORCGPU_T_TIMESTAMP || ot == ORCGPU_T_TIMESTAMP_INSTANT) && co.ts_unit <= 3 && co.width == 8;
+      const bool is_dec = ot == ORCGPU_T_DECIMAL && co.width == 16;
+      f.kind = (is_int && co.width <= 8) || is_ts ? FKIND_INT
+               : (is_float && (co.width == 4 || co.width == 8) ? FKIND_FLOAT : (is_dec ? FKIND_DEC128 : FKIND_OTHER));
       f.values = A + co.values_off;
     }
   }
   for (auto& in : plan.prog) {  // (the plan was compiled against these columns' types; what the decode made of them must fit)
-    if (in.op > FOP_CMP_STRING) continue;
+    if (in.op > FOP_CMP_DEC128) continue;
     if (in.col < nc && r->cols[in.col].dict_out) {  // (string predicates evaluated on the entries: not yet)
       if (column_names && in.col < n_names) set_err(ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[in.col]);
       else set_err(ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", r->cols[in.col].column_id);
       return ORCGPU_UNSUPPORTED;
     }
-    const uint32_t want = in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : FKIND_STRING;
+    const uint32_t want = in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : in.op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
     if (in.col >= nc || fcols[in.col].kind != want) {
       set_err(ctx, "row filter: column %u is not decoded to the type its comparison needs", in.col < nc ? r->cols[in.col].column_id : in.col);
       return ORCGPU_MISMATCHED_SCHEMA;
@@ -293,10 +297,14 @@ extern "C" int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orc
     set_err(ctx, "row filter: %u column names for a result of %zu columns", n_columns, r->cols.size());
     return ORCGPU_INVALID_ARGUMENT;
   }
-  std::vector<int32_t> kinds(n_columns);
-  for (uint32_t c = 0; c < n_columns; c++) kinds[c] = r->cols[c].orc_type;
+  std::vector<int32_t> kinds(n_columns), params(n_columns, 0);
+  for (uint32_t c = 0; c < n_columns; c++) {
+    const ColumnOut& co = r->cols[c];
+    kinds[c] = co.orc_type;
+    params[c] = co.orc_type == ORCGPU_T_DECIMAL ? (int32_t)co.scale : co.ts_unit;  // what Decimal128 / TimestampNs literals are brought to
+  }
   orcgpu_host::FilterPlan plan;
-  int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan);
+  int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan, params.data());
   if (rc) {
     set_err(ctx, "%s", plan.err);
     return rc;

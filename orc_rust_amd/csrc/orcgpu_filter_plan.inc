@@ -1,13 +1,15 @@
 // orcgpu_filter_plan.inc -- the row filter's plan compiler, host only and free of HIP (tests/hostcheck/filter_plan_check.cpp
 // compiles this very text under AddressSanitizer + UBSan): a predicate as the pre-order node list of include/orcgpu.h ->
 // the post-order program filter_eval_kernel runs (device/filter_program.h).  Names become column indices, the type table
-// of orcgpu_result_filter is applied, and the depth is bounded.
+// of orcgpu_result_filter is applied, Decimal128 and TimestampNs literals are brought to the column's own scale / unit, and
+// the depth is bounded.
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "device/filter_program.h"
+#include "orcgpu_decimal.inc"
 
 namespace orcgpu_host {
 
@@ -24,6 +26,7 @@ struct FilterCompiler {
   const char* const* names;
   const int32_t* kinds;  // ORCGPU_T_* of every column
   uint32_t n_columns;
+  const int32_t* params;  // per column -- Decimal: its scale; Timestamp: the unit it is decoded to (0 s, 1 ms, 2 us, 3 ns, 4 Decimal128(38, 9))
   FilterPlan& out;
 
   int fail(int rc, const char* fmt, const char* a = "", long long b = 0) {
@@ -45,6 +48,56 @@ struct FilterCompiler {
     in.cmp = cmp;
     in.col = col;
     out.prog.push_back(in);
+  }
+  // A Decimal128 literal -> (op', literal') at the column's own scale, so that the kernel compares unscaled values and never
+  // rescales a row.  d = column scale - literal scale.  d >= 0: literal * 10^d, clamped to int128 where it leaves it -- no valid
+  // Decimal (|v| < 10^38 < 2^127) equals a clamp, so EQ is never TRUE and the order comparisons are right as they stand.
+  // d < 0: q = floor(literal / 10^-d); with a remainder no row equals the literal: EQ / NE are asked of the upper clamp (still
+  // UNKNOWN on a null row), LT / LE become LE q, GT / GE become GT q.
+  int decimal(const orcgpu_predicate_node& n, uint32_t col, FilterInsn& in) {
+    i128 lit = 0;
+    if (!dec_literal(n.s, n.s_len, n.i, lit))
+      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the Decimal128 literal for column '%s' is malformed (16 bytes, a scale of 0 .. 38, a magnitude below 10^38)", n.column);
+    const int col_scale = params ? params[col] : 0;
+    if (col_scale < 0 || col_scale > kDecMaxDigits) return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' has the scale %lld", n.column, col_scale);
+    const int d = col_scale - (int)n.i;
+    i128 L = 0;
+    if (d >= 0) {
+      if (!dec_scale_up(lit, d, L)) L = lit < 0 ? dec_i128_min() : dec_i128_max();
+    } else {
+      bool exact = false;
+      dec_floor_div(lit, -d, L, exact);
+      if (!exact) {
+        if (in.cmp == ORCGPU_PRED_EQ || in.cmp == ORCGPU_PRED_NE) L = dec_i128_max();
+        else in.cmp = in.cmp == ORCGPU_PRED_LT || in.cmp == ORCGPU_PRED_LE ? ORCGPU_PRED_LE : ORCGPU_PRED_GT;
+      }
+    }
+    in.i = (long long)(L >> 64);
+    in.lo = (unsigned long long)L;
+    return ORCGPU_OK;
+  }
+  // A TimestampNs literal -> (op', literal') in the unit the column is decoded to: q = floor(ns / unit), as above.  The literal is
+  // in the finest unit, so it is only ever divided and nothing can leave int64.  Every int64 is a value a row may hold, hence the
+  // constant cases are asked of INT64_MIN: LT is TRUE for no valid row, GE for every one, both UNKNOWN on a null row.
+  int timestamp(const orcgpu_predicate_node& n, uint32_t col, FilterInsn& in) {
+    static const int64_t per_unit[4] = {1000000000, 1000000, 1000, 1};  // seconds, milli-, micro-, nanoseconds
+    const int unit = params ? params[col] : 3;
+    if (unit < 0 || unit > 3)
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is decoded to Decimal128(38, 9), not to an int64 unit: a comparison on it is not supported", n.column);
+    const int64_t p = per_unit[unit];
+    int64_t q = n.i / p, r = n.i % p;
+    if (r < 0) {  // (C++ truncates toward zero; instants before 1970 need the floor)
+      q -= 1;
+      r += p;
+    }
+    if (r) {
+      if (in.cmp == ORCGPU_PRED_EQ || in.cmp == ORCGPU_PRED_NE) {
+        in.cmp = in.cmp == ORCGPU_PRED_EQ ? ORCGPU_PRED_LT : ORCGPU_PRED_GE;
+        q = INT64_MIN;
+      } else in.cmp = in.cmp == ORCGPU_PRED_LT || in.cmp == ORCGPU_PRED_LE ? ORCGPU_PRED_LE : ORCGPU_PRED_GT;
+    }
+    in.i = q;
+    return ORCGPU_OK;
   }
   // the node at `at` and everything below it; `at` then stands behind them
   int node(uint32_t& at, uint32_t depth) {
@@ -116,8 +169,18 @@ struct FilterCompiler {
             ok = vt == ORCGPU_PV_UTF8;
             in.op = FOP_CMP_STRING;
             break;
-          case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT: case ORCGPU_T_DECIMAL:
-            return fail(ORCGPU_UNSUPPORTED, "row filter: a comparison on the Timestamp / Decimal column '%s' is not supported (IS [NOT] NULL is)", n.column);
+          case ORCGPU_T_DECIMAL:
+            if (vt != ORCGPU_PV_DECIMAL128)
+              return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' is compared with Decimal128 literals only (value type %lld is not supported)", n.column, vt);
+            ok = true;
+            in.op = FOP_CMP_DEC128;
+            break;
+          case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT:
+            if (vt != ORCGPU_PV_TIMESTAMP_NS)
+              return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is compared with TimestampNs literals only (value type %lld is not supported)", n.column, vt);
+            ok = true;
+            in.op = FOP_CMP_INT;
+            break;
           default:
             return fail(ORCGPU_UNSUPPORTED, "row filter: column '%s' of ORC type kind %lld cannot be compared", n.column, kind);
         }
@@ -125,6 +188,11 @@ struct FilterCompiler {
         if (n.value_is_null) {
           emit(FOP_UNKNOWN);
           return ORCGPU_OK;
+        }
+        if (kind == ORCGPU_T_DECIMAL) {
+          if (const int drc = decimal(n, col, in)) return drc;
+        } else if (kind == ORCGPU_T_TIMESTAMP || kind == ORCGPU_T_TIMESTAMP_INSTANT) {
+          if (const int trc = timestamp(n, col, in)) return trc;
         }
         if (in.op == FOP_CMP_STRING) {
           if (n.s_len && !n.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", n.column);
@@ -143,13 +211,14 @@ struct FilterCompiler {
 };
 
 // ORCGPU_OK, or the status a reader with this filter ends with (out.err says why).  names[k] / kinds[k]: column k.
+// params[k]: a Decimal column's scale, the unit a Timestamp column is decoded to (FilterCompiler::params); none: scale 0, nanoseconds.
 inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, const char* const* names, const int32_t* kinds, uint32_t n_columns,
-                          FilterPlan& out) {
+                          FilterPlan& out, const int32_t* params = nullptr) {
   out.prog.clear();
   out.lits.clear();
   out.depth = 0;
   out.err[0] = 0;
-  FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, out};
+  FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, params, out};
   if (!nodes || !n_nodes) return fc.fail(ORCGPU_INVALID_ARGUMENT, "row filter: no predicate%s", "");
   for (uint32_t k = 0; k < n_columns; k++) {
     const int t = kinds[k];

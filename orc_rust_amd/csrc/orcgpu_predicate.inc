@@ -1,6 +1,7 @@
 // orcgpu_predicate.inc -- predicate pushdown onto row groups, host only: row-group statistics (statistics.rs:60-200), Bloom
 // filters (bloom_filter.rs), evaluate_predicate (row_group_filter.rs:50-620), RowSelection::from_row_group_filter
 // (row_selection.rs:348-392).  The reader (orcgpu_reader.inc) turns the outcome into the row groups it reads.
+#include "orcgpu_decimal.inc"
 namespace orcgpu_host {
 
 // ColumnStatistics of one row group (statistics.rs:115-200): TryFrom picks the first typed message present
@@ -331,9 +332,19 @@ struct PredEval {
         if (!(some && (vt == ORCGPU_PV_INT32 || vt == ORCGPU_PV_INT64))) return failed = true;
         return cmp_int(st.imin, st.imax, op, n.i);
       case GroupStats::TIMESTAMP:
+        // (a TimestampNs literal prunes nothing and fails nothing: the statistics are UTC milliseconds, and what a non-instant
+        // column exports depends on the writer's time zone, which this rule does not have)
+        if (vt == ORCGPU_PV_TIMESTAMP_NS) return true;
         if (!(some && vt == ORCGPU_PV_INT64)) return failed = true;
         return cmp_int(st.imin, st.imax, op, n.i);
-      case GroupStats::DECIMAL:  // (compared as strings, as the reference does)
+      case GroupStats::DECIMAL:
+        if (some && vt == ORCGPU_PV_DECIMAL128) {  // exact rational order (the reference has no such literal)
+          i128 v;
+          bool m = true;
+          if (!dec_literal(n.s.data(), n.s.size(), n.i, v) || !dec_stats_match(st.smin, st.smax, op, v, (int)n.i, &m)) return failed = true;
+          return m;
+        }
+        // (a Utf8 literal: compared as strings, as the reference does)
         if (!(some && vt == ORCGPU_PV_UTF8)) return failed = true;
         return cmp_string(st.smin, st.smax, op, n.s, true, true);
       case GroupStats::BUCKET: {

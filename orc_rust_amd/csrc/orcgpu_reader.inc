@@ -807,12 +807,17 @@ int reader_filter_result(orcgpu_reader* rd, orcgpu_result* res) {
 // The filter's nodes against the projected root columns -> its program, once, at the first next_batch
 int reader_compile_filter(orcgpu_reader* rd) {
   std::vector<const char*> names;
-  std::vector<int32_t> kinds;
+  std::vector<int32_t> kinds, params;
   for (size_t k = 0, root = 0; k < rd->col_ids.size(); k++) {
     // (a column below a Struct / List / Map / Union: its root is refused by its kind)
     if (rd->col_parent[k]) continue;
+    const OrcType& t = rd->md.types[rd->col_ids[k]];
     names.push_back(rd->col_names[root++].c_str());
-    kinds.push_back(rd->md.types[rd->col_ids[k]].kind);
+    kinds.push_back(t.kind);
+    // what a Decimal128 / TimestampNs literal is brought to: the column's scale (with_schema takes no other), the unit it is decoded to
+    orcgpu_column c{};
+    c.arrow_target = rd->has_schema ? rd->col_target[k] : rd->ts_arrow_target;
+    params.push_back(t.kind == ORCGPU_T_DECIMAL ? (int32_t)t.scale : ts_unit_of(c));
   }
   std::vector<orcgpu_predicate_node> nodes(rd->filter_nodes.size());
   for (size_t k = 0; k < nodes.size(); k++) {
@@ -829,12 +834,12 @@ int reader_compile_filter(orcgpu_reader* rd) {
     n.s = p.s.data();
     n.s_len = p.s.size();
   }
-  const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan);
+  const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan, params.data());
   if (rc) set_err(rd->ctx, "%s", rd->filter_plan.err);
   if (rc) return rc;
   // a comparison on a dictionary-output column would have to be evaluated on the entries: refused, by name, before anything is read
   for (auto& in : rd->filter_plan.prog) {
-    if (in.op > FOP_CMP_STRING || in.col >= names.size()) continue;
+    if (in.op > FOP_CMP_DEC128 || in.col >= names.size()) continue;
     size_t root = 0;
     for (size_t k = 0; k < rd->col_ids.size(); k++) {
       if (rd->col_parent[k]) continue;

@@ -2,9 +2,12 @@
 flattened to the pre-order node list of include/orcgpu.h (orcgpu_predicate_node) for orcgpu_reader_set_predicate and
 orcgpu_predicate_row_groups."""
 import ctypes as C
+import datetime
+import decimal
 
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL, AND, OR, NOT = range(11)
-PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8 = range(8)
+PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
+_EPOCH = datetime.datetime(1970, 1, 1)
 
 
 class PredicateNode(C.Structure):
@@ -18,7 +21,9 @@ class ColumnIndex(C.Structure):
 
 
 class PredicateValue:
-    """PredicateValue::{Boolean, Int8, ..., Utf8}(Option<_>) (predicate.rs:29-47): value None = the SQL NULL literal."""
+    """PredicateValue::{Boolean, Int8, ..., Utf8}(Option<_>) (predicate.rs:29-47): value None = the SQL NULL literal.
+    Decimal128 and TimestampNs are this library's own (include/orcgpu.h: ORCGPU_PV_DECIMAL128, ORCGPU_PV_TIMESTAMP_NS); their
+    .value is the (unscaled, scale) pair and the nanoseconds since 1970-01-01T00:00:00."""
 
     def __init__(self, kind, value):
         self.kind, self.value = kind, value
@@ -31,6 +36,47 @@ class PredicateValue:
     Float32 = classmethod(lambda cls, v: cls(PV_FLOAT32, v))
     Float64 = classmethod(lambda cls, v: cls(PV_FLOAT64, v))
     Utf8 = classmethod(lambda cls, v: cls(PV_UTF8, v))
+
+    @classmethod
+    def Decimal128(cls, v):
+        """v: a decimal.Decimal, an (unscaled, scale) pair with scale 0 .. 38 and |unscaled| < 10^38, or None."""
+        if v is None:
+            return cls(PV_DECIMAL128, None)
+        if isinstance(v, decimal.Decimal):
+            if not v.is_finite():
+                raise ValueError("Decimal128 literal: %r is not a finite number" % (v,))
+            sign, digits, exponent = v.as_tuple()
+            if exponent > 0:
+                raise ValueError("Decimal128 literal: %r has a positive exponent; quantize it to the scale that is meant" % (v,))
+            unscaled, scale = int("".join(map(str, digits)) or "0"), -exponent
+            if sign:
+                unscaled = -unscaled
+        else:
+            unscaled, scale = v
+            if isinstance(unscaled, bool) or isinstance(scale, bool) or not isinstance(unscaled, int) or not isinstance(scale, int):
+                raise TypeError("Decimal128 literal: (unscaled, scale) are integers, got %r" % (v,))
+        if not 0 <= scale <= 38 or abs(unscaled) >= 10 ** 38:
+            raise ValueError("Decimal128 literal: scale %d, unscaled %d: the scale is 0 .. 38 and the magnitude below 10^38" % (scale, unscaled))
+        return cls(PV_DECIMAL128, (unscaled, scale))
+
+    @classmethod
+    def TimestampNs(cls, v):
+        """v: integer nanoseconds since 1970-01-01T00:00:00, a datetime.datetime (naive: read as wall clock; aware: converted to
+        UTC) or None.  In the sense of the column's exported value: wall clock for TIMESTAMP, UTC for TIMESTAMP_INSTANT."""
+        if v is None:
+            return cls(PV_TIMESTAMP_NS, None)
+        if isinstance(v, datetime.datetime):
+            if v.tzinfo is not None and v.utcoffset() is not None:
+                v = (v - v.utcoffset()).replace(tzinfo=None)
+            else:
+                v = v.replace(tzinfo=None)
+            d = v - _EPOCH  # (days, seconds, microseconds): exact integers, no float on the way
+            v = ((d.days * 86400 + d.seconds) * 10 ** 6 + d.microseconds) * 1000
+        elif isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("TimestampNs literal: an int or a datetime.datetime, got %r" % (v,))
+        if not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("TimestampNs literal: %d ns is outside int64 (1677-09-21 .. 2262-04-11)" % v)
+        return cls(PV_TIMESTAMP_NS, v)
 
 
 class Predicate:
@@ -85,6 +131,11 @@ class Predicate:
                         b = v.value.encode() if isinstance(v.value, str) else bytes(v.value)
                         keep.append(b)
                         n.s, n.s_len = b, len(b)
+                    elif v.kind == PV_DECIMAL128:
+                        unscaled, scale = v.value
+                        b = int(unscaled).to_bytes(16, "little", signed=True)
+                        keep.append(b)
+                        n.s, n.s_len, n.i = b, 16, int(scale)
                     elif v.kind in (PV_FLOAT32, PV_FLOAT64):
                         n.f = float(v.value)
                     else:
