@@ -118,10 +118,10 @@ struct StagedStream {
 };
 }  // namespace
 
+#include "orcgpu_decode_host.inc"
+static_assert(kJobBlockBytes == RLE_BLK && kJobTileBlocks == RLE_TILE && kJobCodecByte == CODEC_BYTE, "orcgpu_decode_host.inc states the device's constants");
+
 constexpr int kMaxLanes = 4;
-// Zstandard: sequences of a call from which on the FSE chains go one lane per block (zstd_lanes.h) instead of one wavefront per
-// block: below it the call lasts as long as its longest chain either way (SF 3: 32 against 22 ms with the lanes forced on)
-constexpr uint64_t kZstdLanesMinSequences = 40000000ull;
 constexpr size_t kStagePiece = 16u << 20;  // bytes per pinned staging piece
 constexpr int kCopyThreads = 6;
 
@@ -608,35 +608,8 @@ uint32_t type_width(int t) {
 }
 bool is_string_type(int t) { return t == ORCGPU_T_STRING || t == ORCGPU_T_VARCHAR || t == ORCGPU_T_CHAR || t == ORCGPU_T_BINARY; }
 
-// ---- per-call plan ------------------------------------------------------------------------------
-// (JC_PRESENT1 + d - 1: PRESENT streams of the fields of Structs / arms of Unions at depth d: they are as long as their parent has non-null rows)
-// kMaxStructDepth classes of them: the reference recurses without a limit (array_decoder/mod.rs:464-505); here the depth is bounded
-// by a number no schema reaches (the type tree of a file is walked recursively on the host: kMaxTypeDepth below), and the PRESENT
-// phase loops over the depths a call really has
-constexpr int kMaxStructDepth = 256;
+// ---- per-call plan (the job types: orcgpu_decode_host.inc) ----------------------------------------
 constexpr int kMaxTypeDepth = 256;  // nesting of any kind (Struct / List / Map / Union) the file reader follows below a root column
-enum JobClass { JC_PRESENT = 0, JC_RLE2 = 1, JC_RLE1 = 2, JC_BYTE = 3, JC_PRESENT1 = 4, JC_COUNT = JC_PRESENT1 + kMaxStructDepth };
-
-struct JobPlan {
-  int cls;
-  uint8_t codec, is_signed, nbits, out_bytes;
-  const uint8_t* data;      // device pointer to the plain stream (may be assigned later)
-  uint64_t data_scratch_off = ~0ull;  // when the plain stream lives in scratch (decompressed)
-  uint64_t len_upper;       // upper bound of the plain length
-  uint32_t len_idx, needed_idx, total_idx;
-  uint64_t out_scratch_off = ~0ull;   // dense output in scratch ...
-  uint64_t out_result_off = ~0ull;    // ... or directly in the result arena
-  int result_index = 0;
-  uint64_t expect_values;   // host estimate of values (for group sizing)
-  // filled while laying out
-  uint32_t block0 = 0, nblocks = 0, group0 = 0, ngroups = 0, group_size = 64;
-  uint32_t skip_values = 0;            // of the stream's entry point: decoded in front of the output (RleJob::skip)
-  const StagedStream* hint_src = nullptr;  // verified run starts, if the stream has any
-  uint32_t chunk0 = 0;
-  uint32_t uniform_idx = 0, uniform_value = 0;  // RleJob::uniform_idx / uniform_value (a Decimal column's scales)
-  int stripe = 0, col = 0, role = 0;  // role: stream kind the job decodes
-  int final_index = -1;
-};
 
 struct PlainStream {
   const uint8_t* dev = nullptr;  // device pointer when uncompressed (inside the staged arena)
@@ -1230,8 +1203,8 @@ struct SummaryLayout {
 
 }  // namespace
 
-#include "orcgpu_ext.inc"
-#include "orcgpu_decode.inc"
+#include "orcgpu_decompress.inc"
+#include "orcgpu_decode.inc"  // (includes orcgpu_ext.inc behind LaneRun, which its helpers take)
 #include "orcgpu_export.inc"
 #include "orcgpu_export_device.inc"
 #include "orcgpu_select.inc"

@@ -2,6 +2,59 @@
 
 namespace {
 
+// A lane's host clock (us) at the ends of the parts of a decode call (orcgpu_last_lane_host_us, the ORCGPU_DEBUG report)
+struct LaneClock {
+  double t0 = 0, cols = 0, dp = 0, plan = 0, launch = 0, first = 0, walk = 0, pres = 0, exp = 0, fin = 0, dict = 0, enq = 0, sync = 0;
+};
+
+// What the steps of decode_lane share: one lane's share of a decode call, from its plan to the pointers its launches take.
+struct LaneRun {
+  orcgpu_ctx* ctx;
+  hipStream_t st;
+  orcgpu_staged* const* stripes;
+  uint32_t n;
+  orcgpu_result** results;
+  const std::vector<std::vector<uint8_t>>* mask;  // the lane's columns per stripe (null: all)
+  bool host_prof;                                 // ORCGPU_DEBUG
+  Plan P;
+  DecompPlan DP;
+  JobLayout L;
+  std::vector<RleHint> hints;  // verified run starts (orcgpu_stream::entries): one table for the call, a slice per job
+  // workspace offsets: the per-block arrays (RleBlocks), the hint table, the maps of the exact parallel walk, the summary
+  struct {
+    uint64_t entry, exit_, nvals, voff, tbase, tsum, flags, badmap, gjob, hint;
+  } blk_off{};
+  uint64_t hints_off = 0;
+  bool use_exact = false;
+  uint32_t n_xspans = 0;
+  uint64_t x_fmap = 0, x_gmap = 0, x_tile = 0, x_span = 0;
+  SummaryLayout SL;
+  uint64_t summary_off = 0;
+  // the workspace, the summary's host mirror and device copy, and what lies in them
+  uint8_t *S = nullptr, *hs = nullptr, *dsum = nullptr;
+  RleJob *hjobs = nullptr, *d_jobs = nullptr;
+  uint64_t* d_scalars = nullptr;
+  unsigned long long *d_nullc = nullptr, *d_chartot = nullptr;
+  RleBlocks blk{};
+  uint32_t* d_tsum = nullptr;
+  int njobs = 0;
+  LaneClock ht;
+
+  uint8_t* arena(const orcgpu_result* r) const { return r->arena[ctx->lane_id].p; }
+  // a column's validity words and their ranks (null: no validity)
+  const unsigned long long* vbits(const ColPlan& cp) const { return cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr; }
+  const uint32_t* rank(const ColPlan& cp) const { return cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr; }
+  const uint64_t* h_scalars() const { return reinterpret_cast<const uint64_t*>(hs + SL.scalars_off); }
+  const unsigned long long* h_nullc() const { return reinterpret_cast<const unsigned long long*>(hs + SL.nullc_off); }
+  const unsigned long long* h_chartot() const { return reinterpret_cast<const unsigned long long*>(hs + SL.chartot_off); }
+};
+
+}  // namespace
+
+#include "orcgpu_ext.inc"
+
+namespace {
+
 int ts_unit_of(const orcgpu_column& c) {
   switch (c.arrow_target) {
     case ORCGPU_ARROW_TIMESTAMP_S: case ORCGPU_ARROW_TIMESTAMP_S_UTC: case ORCGPU_ARROW_TIMESTAMP_S_NOTZ: return 0;
@@ -48,6 +101,36 @@ int schema_pair_status(const orcgpu_column& c) {
   }
 }
 
+// validity scratch of a column or of a Union's arm: words, their popcounts and ranks
+void take_validity_scratch(Plan& P, ColPlan& cp) {
+  cp.n_words = (cp.n_rows + 63) / 64;
+  cp.n_rank_tiles = (cp.n_words + 1023) / 1024;
+  cp.vbits_off = P.scratch.take(cp.n_words * 8 + 16);
+  cp.wpop_off = P.scratch.take(cp.n_words * 4);
+  cp.rank_off = P.scratch.take(cp.n_words * 4);
+  cp.rank_tiles_off = P.scratch.take(cp.n_rank_tiles * 4);
+}
+
+// Where the column's DATA job writes: dense in the workspace (`scratch_bytes`; a finisher spaces the values over the rows), or
+// straight into the result; either way behind `lead` bytes, the values of the rows before an entry point
+void place_dense(Plan& P, ColPlan& cp, ColumnOut& co, uint64_t scratch_bytes, uint64_t lead, bool in_result) {
+  JobPlan& j = P.jobs[cp.job_data];
+  if (in_result) {
+    j.out_result_off = co.values_off;
+    j.result_index = cp.stripe;
+    co.values_off += lead;
+  } else {
+    cp.dense_off = P.scratch.take(scratch_bytes);
+    j.out_scratch_off = cp.dense_off;
+    cp.dense_off += lead;
+  }
+}
+
+int plan_parent(Plan& P, ColPlan& cp, orcgpu_staged* s);
+int plan_present(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r);
+int plan_union(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r);
+int plan_values(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r);
+
 // Build the plan of one column of one stripe.  Returns an ORCGPU_* status.
 int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   const orcgpu_column& c = s->cols[ci];
@@ -57,7 +140,6 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   cp.c = c;
   cp.n_rows = s->desc.n_rows;
   const uint64_t n = cp.n_rows;
-  const uint32_t B = r->batch;
   ColumnOut& co = r->cols[ci];
   co.orc_type = c.orc_type;
   co.column_id = c.column_id;
@@ -78,7 +160,6 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   co.null_counts.assign(r->n_batches, 0);
   co.status = 0;
   co.lane = s->ctx ? P.lane_id : 0;
-  Bump& RB = P.result_bump[si];
 
   switch (c.orc_type) {
     case ORCGPU_T_BOOLEAN: case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG: case ORCGPU_T_FLOAT:
@@ -107,6 +188,20 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   co.is_struct = c.orc_type == ORCGPU_T_STRUCT;
   co.is_union = c.orc_type == ORCGPU_T_UNION;
   co.parent = c.parent ? (int32_t)c.parent - 1 : -1;
+  if (int st = plan_parent(P, cp, s)) return st;
+  if (int st = plan_present(P, cp, s, r)) return st;
+  if (co.is_struct) {
+    cp.ceil8_idx = P.new_scalar((n + 7) / 8);
+    P.cols.push_back(cp);
+    return ORCGPU_OK;
+  }
+  return co.is_union ? plan_union(P, cp, s, r) : plan_values(P, cp, s, r);
+}
+
+// The Struct, or the arm of a Union, above the column: its depth below it, and its validity if it has any
+int plan_parent(Plan& P, ColPlan& cp, orcgpu_staged* s) {
+  const orcgpu_column& c = cp.c;
+  const int si = cp.stripe, ci = cp.col;
   if (c.parent) {
     const int pt = c.parent <= (uint32_t)ci ? s->cols[c.parent - 1].orc_type : -1;
     if (pt != ORCGPU_T_STRUCT && pt != ORCGPU_T_UNION) {
@@ -134,17 +229,21 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
       return ORCGPU_UNSUPPORTED;
     }
   }
-  // PRESENT (PresentDecoder::from_stripe: get_opt -> only when the stream exists)
+  return ORCGPU_OK;
+}
+
+// PRESENT (PresentDecoder::from_stripe: get_opt -> only when the stream exists)
+int plan_present(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r) {
+  const orcgpu_column& c = cp.c;
+  const uint64_t n = cp.n_rows;
+  const int si = cp.stripe, ci = cp.col;
+  ColumnOut& co = r->cols[ci];
+  Bump& RB = P.result_bump[si];
   cp.own_present = s->find(c.column_id, ORCGPU_S_PRESENT) != nullptr;
   cp.has_present = cp.own_present || cp.parent_plan >= 0;
   co.has_present = cp.has_present;
   if (cp.has_present && n) {
-    cp.n_words = (n + 63) / 64;
-    cp.n_rank_tiles = (cp.n_words + 1023) / 1024;
-    cp.vbits_off = P.scratch.take(cp.n_words * 8 + 16);
-    cp.wpop_off = P.scratch.take(cp.n_words * 4);
-    cp.rank_off = P.scratch.take(cp.n_words * 4);
-    cp.rank_tiles_off = P.scratch.take(cp.n_rank_tiles * 4);
+    take_validity_scratch(P, cp);
     if (cp.own_present) {
       cp.present = plan_stream(P, s, c.column_id, ORCGPU_S_PRESENT);
       cp.pbytes_off = P.scratch.take(cp.n_words * 8 + ORC_PAD + cp.present.skip_values);
@@ -170,66 +269,70 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
     }
     co.validity_off = RB.take((uint64_t)r->n_batches * r->words_per_batch * 8);
   }
-  if (co.is_struct) {
-    cp.ceil8_idx = P.new_scalar((n + 7) / 8);
-    P.cols.push_back(cp);
-    return ORCGPU_OK;
+  return ORCGPU_OK;
+}
+
+int plan_union(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r) {
+  const orcgpu_column& c = cp.c;
+  const uint64_t n = cp.n_rows;
+  const int si = cp.stripe, ci = cp.col;
+  ColumnOut& co = r->cols[ci];
+  Bump& RB = P.result_bump[si];
+  // union.rs:69-136: DATA = byte-RLE tags, one per row in which the Union is present; the result's values are the type ids (0 in
+  // null rows: decode_spaced), the arms follow as plans of their own.  The tags are needed before the arms' validity can be
+  // formed: their job is expanded with the PRESENT streams of the arms' depth.
+  int n_arms = 0;
+  for (size_t q = (size_t)ci + 1; q < s->cols.size(); q++) n_arms += s->cols[q].parent == (uint32_t)ci + 1;
+  if (cp.depth + 1 > kMaxStructDepth || n_arms > 127) {
+    set_err(s->ctx, "column %u: a Union %s is not decoded on the GPU path", c.column_id, n_arms > 127 ? "of more than 127 types" : "this deep inside Structs / Unions");
+    return ORCGPU_UNSUPPORTED;
   }
-  if (co.is_union) {
-    // union.rs:69-136: DATA = byte-RLE tags, one per row in which the Union is present; the result's values are the type ids (0 in
-    // null rows: decode_spaced), the arms follow as plans of their own.  The tags are needed before the arms' validity can be
-    // formed: their job is expanded with the PRESENT streams of the arms' depth.
-    int n_arms = 0;
-    for (size_t q = (size_t)ci + 1; q < s->cols.size(); q++) n_arms += s->cols[q].parent == (uint32_t)ci + 1;
-    if (cp.depth + 1 > kMaxStructDepth || n_arms > 127) {
-      set_err(s->ctx, "column %u: a Union %s is not decoded on the GPU path", c.column_id, n_arms > 127 ? "of more than 127 types" : "this deep inside Structs / Unions");
-      return ORCGPU_UNSUPPORTED;
-    }
-    co.width = 1;
-    co.values_bytes = n;
-    co.values_off = RB.take(n + 16);
+  co.width = 1;
+  co.values_bytes = n;
+  co.values_off = RB.take(n + 16);
+  if (n) {
+    cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
+    const uint64_t lead = cp.data.skip_values;
+    cp.job_data = add_job(P, JC_PRESENT1 + cp.depth, CODEC_BYTE, false, 8, 1, cp.data, cp.nonnull_idx, n, si, ci, ORCGPU_S_DATA);
+    place_dense(P, cp, co, n + 16 + lead + ORC_PAD, lead, false);
+  }
+  cp.arm0 = (int)P.cols.size() + 1;
+  cp.n_arms = n_arms;
+  const int me = (int)P.cols.size();
+  P.cols.push_back(cp);
+  for (int a = 0; a < n_arms; a++) {
+    ColPlan arm{};
+    arm.stripe = si;
+    arm.col = -1;
+    arm.c = c;
+    arm.c.orc_type = ORCGPU_T_STRUCT;  // (towards its child it is what a Struct is towards a field)
+    arm.n_rows = n;
+    arm.has_present = true;
+    arm.parent_plan = cp.has_present ? me : -1;
+    arm.depth = cp.depth + 1;
+    arm.arm_of = me;
+    arm.arm_tag = a;
+    arm.err_idx = P.new_scalar(RLE_NO_ERR);
+    arm.nonnull_idx = P.new_scalar(n);
+    arm.ceil8_idx = P.new_scalar((n + 7) / 8);
+    arm.nullcount_off = (uint32_t)P.n_nullcount_slots;
+    P.n_nullcount_slots += r->n_batches;
     if (n) {
-      cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
-      const uint64_t lead = cp.data.skip_values;
-      cp.dense_off = P.scratch.take(n + 16 + lead + ORC_PAD);
-      cp.job_data = add_job(P, JC_PRESENT1 + cp.depth, CODEC_BYTE, false, 8, 1, cp.data, cp.nonnull_idx, n, si, ci, ORCGPU_S_DATA);
-      P.jobs[cp.job_data].out_scratch_off = cp.dense_off;
-      cp.dense_off += lead;
+      take_validity_scratch(P, arm);
+      arm.arm_validity_off = P.scratch.take((uint64_t)r->n_batches * r->words_per_batch * 8 + 16);
     }
-    cp.arm0 = (int)P.cols.size() + 1;
-    cp.n_arms = n_arms;
-    const int me = (int)P.cols.size();
-    P.cols.push_back(cp);
-    for (int a = 0; a < n_arms; a++) {
-      ColPlan arm{};
-      arm.stripe = si;
-      arm.col = -1;
-      arm.c = c;
-      arm.c.orc_type = ORCGPU_T_STRUCT;  // (towards its child it is what a Struct is towards a field)
-      arm.n_rows = n;
-      arm.has_present = true;
-      arm.parent_plan = cp.has_present ? me : -1;
-      arm.depth = cp.depth + 1;
-      arm.arm_of = me;
-      arm.arm_tag = a;
-      arm.err_idx = P.new_scalar(RLE_NO_ERR);
-      arm.nonnull_idx = P.new_scalar(n);
-      arm.ceil8_idx = P.new_scalar((n + 7) / 8);
-      arm.nullcount_off = (uint32_t)P.n_nullcount_slots;
-      P.n_nullcount_slots += r->n_batches;
-      if (n) {
-        arm.n_words = (n + 63) / 64;
-        arm.n_rank_tiles = (arm.n_words + 1023) / 1024;
-        arm.vbits_off = P.scratch.take(arm.n_words * 8 + 16);
-        arm.wpop_off = P.scratch.take(arm.n_words * 4);
-        arm.rank_off = P.scratch.take(arm.n_words * 4);
-        arm.rank_tiles_off = P.scratch.take(arm.n_rank_tiles * 4);
-        arm.arm_validity_off = P.scratch.take((uint64_t)r->n_batches * r->words_per_batch * 8 + 16);
-      }
-      P.cols.push_back(arm);
-    }
-    return ORCGPU_OK;
+    P.cols.push_back(arm);
   }
+  return ORCGPU_OK;
+}
+
+// The value streams of every other kind of column, their jobs and where those write
+int plan_values(Plan& P, ColPlan& cp, orcgpu_staged* s, orcgpu_result* r) {
+  const orcgpu_column& c = cp.c;
+  const uint64_t n = cp.n_rows;
+  const int si = cp.stripe, ci = cp.col;
+  ColumnOut& co = r->cols[ci];
+  Bump& RB = P.result_bump[si];
   // a writer time zone: values are re-labelled behind the finisher (tz_shift_kernel); only the ns unit of a zone that never
   // leaves UTC cannot produce nulls and is left alone
   if (c.orc_type == ORCGPU_T_TIMESTAMP && s->zone && n && !(s->zone->table.utc && co.ts_unit >= 3)) {
@@ -252,37 +355,14 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
     P.cols.push_back(cp);
     return ORCGPU_OK;
   }
-  if (t == ORCGPU_T_SHORT || t == ORCGPU_T_INT || t == ORCGPU_T_LONG || t == ORCGPU_T_DATE) {
+  if (t == ORCGPU_T_SHORT || t == ORCGPU_T_INT || t == ORCGPU_T_LONG || t == ORCGPU_T_DATE || t == ORCGPU_T_BYTE) {
+    const int cls = t == ORCGPU_T_BYTE ? JC_BYTE : vcls;  // (a Byte column: byte RLE whatever its encoding, unsigned)
     cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
     const uint64_t lead = (uint64_t)cp.data.skip_values * co.width;  // values of the rows before an entry point: decoded in front
     co.values_bytes = n * co.width;
     co.values_off = RB.take(co.values_bytes + 16 + (cp.has_present ? 0 : lead));
-    cp.job_data = add_job(P, vcls, class_codec(vcls), true, (uint8_t)(co.width * 8), (uint8_t)co.width, cp.data, cp.nonnull_idx, n, si, ci,
-                          ORCGPU_S_DATA);
-    if (cp.has_present) {
-      cp.dense_off = P.scratch.take(n * co.width + 16 + lead);
-      P.jobs[cp.job_data].out_scratch_off = cp.dense_off;
-      cp.dense_off += lead;
-    } else {
-      P.jobs[cp.job_data].out_result_off = co.values_off;
-      P.jobs[cp.job_data].result_index = si;
-      co.values_off += lead;
-    }
-  } else if (t == ORCGPU_T_BYTE) {
-    cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
-    const uint64_t lead = cp.data.skip_values;
-    co.values_bytes = n;
-    co.values_off = RB.take(n + 16 + (cp.has_present ? 0 : lead));
-    cp.job_data = add_job(P, JC_BYTE, CODEC_BYTE, false, 8, 1, cp.data, cp.nonnull_idx, n, si, ci, ORCGPU_S_DATA);
-    if (cp.has_present) {
-      cp.dense_off = P.scratch.take(n + 16 + lead);
-      P.jobs[cp.job_data].out_scratch_off = cp.dense_off;
-      cp.dense_off += lead;
-    } else {
-      P.jobs[cp.job_data].out_result_off = co.values_off;
-      P.jobs[cp.job_data].result_index = si;
-      co.values_off += lead;
-    }
+    cp.job_data = add_job(P, cls, class_codec(cls), t != ORCGPU_T_BYTE, (uint8_t)(co.width * 8), (uint8_t)co.width, cp.data, cp.nonnull_idx, n, si, ci, ORCGPU_S_DATA);
+    place_dense(P, cp, co, co.values_bytes + 16 + lead, lead, !cp.has_present);
   } else if (t == ORCGPU_T_BOOLEAN) {
     cp.data = plan_stream(P, s, c.column_id, ORCGPU_S_DATA);
     co.values_bytes = (uint64_t)r->n_batches * r->words_per_batch * 8;
@@ -320,105 +400,61 @@ int plan_column(Plan& P, int si, int ci, orcgpu_staged* s, orcgpu_result* r) {
   return ORCGPU_OK;
 }
 
-}  // namespace
-
-// One lane's share of a decode call: the columns `mask` selects (all when null), on the lane's own stream and workspace.
-// The results have been created / reset by orcgpu_decode_staged; this fills their selected columns.
-static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results, const std::vector<std::vector<uint8_t>>* mask) {
-  const bool host_prof = getenv("ORCGPU_DEBUG") != nullptr;
-  auto hclock = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double ht0 = hclock();
-  double ht_plan = 0, ht_enq = 0, ht_sync = 0;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  Plan P;
-  P.lane_id = ctx->lane_id;
-  P.call_z_lanes = ctx->call_z_lanes;
-  P.result_bump.resize(n);
-  // ---- plan -------------------------------------------------------------------------------------
-  for (uint32_t si = 0; si < n; si++) {
-    orcgpu_staged* s = stripes[si];
-    orcgpu_result* r = results[si];
+// ---- plan -------------------------------------------------------------------------------------
+int plan_columns(LaneRun& R) {
+  Plan& P = R.P;
+  P.lane_id = R.ctx->lane_id;
+  P.call_z_lanes = R.ctx->call_z_lanes;
+  P.result_bump.resize(R.n);
+  for (uint32_t si = 0; si < R.n; si++) {
+    orcgpu_staged* s = R.stripes[si];
+    orcgpu_result* r = R.results[si];
     P.stripes.push_back(s);
     P.results.push_back(r);
     for (size_t ci = 0; ci < s->cols.size(); ci++) {
-      if (mask && !(*mask)[si][ci]) continue;
+      if (R.mask && !(*R.mask)[si][ci]) continue;
       if (r->cols[ci].elem) continue;  // an element of a List / Map: decoded with its siblings once their count is known
       int rc = plan_column(P, (int)si, (int)ci, s, r);
       if (rc) {
-        if (ctx != s->ctx) ctx->err = s->ctx->err;  // plan_column reports to the staging context
+        if (R.ctx != s->ctx) R.ctx->err = s->ctx->err;  // plan_column reports to the staging context
         return rc;
       }
     }
   }
-  const double ht_cols = hclock();
-  // compressed streams: chunk tables
-  DecompPlan DP;
-  int rc = plan_decompress(P, DP);
-  if (rc) return rc;
-  const double ht_dp = hclock();
+  R.ht.cols = host_us_now();
+  return ORCGPU_OK;
+}
 
-  // ---- lay out jobs: class order, tile aligned block ranges, expansion groups ------------------------
-  std::vector<int> order(P.jobs.size());
-  for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return P.jobs[a].cls < P.jobs[b].cls; });
-  uint32_t cls_first[JC_COUNT + 1] = {0}, cls_groups[JC_COUNT] = {0};
-  uint64_t total_blocks = 0;
-  uint64_t call_blocks = 0;  // stream blocks of all jobs of the call (before their ranges are aligned)
-  for (const JobPlan& j : P.jobs) call_blocks += std::max<uint64_t>(1, (j.len_upper + RLE_BLK - 1) / RLE_BLK);
-  constexpr uint64_t kGroupTarget = 6144;  // (measured 3072 .. 24576: the headline 35.7 - 35.9 ms at 3072 / 6144, 36.2 - 36.4 at 12288; C2 0.55 against 0.59 - 0.60)
-  {
-    int cur = 0;
-    for (size_t k = 0; k < order.size(); k++) {
-      JobPlan& j = P.jobs[order[k]];
-      while (cur < j.cls) cls_first[++cur] = (uint32_t)k;
-      j.final_index = (int)k;
-      j.nblocks = (uint32_t)std::max<uint64_t>(1, (j.len_upper + RLE_BLK - 1) / RLE_BLK);
-      j.block0 = (uint32_t)total_blocks;
-      total_blocks += align_up(j.nblocks, RLE_TILE);
-      // group size (blocks per wavefront of the expansion): bound the bytes one wavefront writes; keep enough wavefronts in flight --
-      // over the CALL, not per stream: about kGroupTarget groups in all, and 64 or more of every stream --; a power of two, so that
-      // 64 / g runs per block and trip use every lane.  (Round 5: nblocks / 512 per stream, whatever else the call held: lineitem's
-      // dictionary-key streams -- 1500 - 2300 blocks a stripe -- got groups of 2 - 4 blocks, and the chain of run headers inside a
-      // block, walked by the block's one lane, cost 16 - 32 hops per trip for a wavefront with 2 - 4 lanes at work.)
-      double out_per_block = (double)j.expect_values * j.out_bytes / j.nblocks;
-      uint32_t g = out_per_block > 0 ? (uint32_t)std::min<double>(64.0, std::max<double>(1.0, 131072.0 / out_per_block)) : 64;
-      if (j.codec == CODEC_BYTE) {
-        // (byte RLE -- PRESENT bitmaps, Byte columns --: long runs, a block expands 8 - 60 times; more and smaller groups, as before:
-        // C3's PRESENT expansion 0.16 ms with 512 groups a stream, 0.26 with the call-wide rule)
-        g = std::min<uint32_t>(g, std::max<uint32_t>(1, j.nblocks / 512));
-      } else {
-        g = std::min<uint32_t>(g, std::max<uint32_t>(1, (uint32_t)(call_blocks / kGroupTarget)));
-        g = std::min<uint32_t>(g, std::max<uint32_t>(1, j.nblocks / 64));
-      }
-      {
-        uint32_t p2 = 1;
-        while (p2 * 2 <= g) p2 *= 2;
-        g = p2;
-      }
-      j.group_size = g;
-      j.ngroups = (j.nblocks + g - 1) / g;
-      j.group0 = cls_groups[j.cls];
-      cls_groups[j.cls] += j.ngroups;
-    }
-    while (cur < JC_COUNT) cls_first[++cur] = (uint32_t)order.size();
-  }
-  if (total_blocks >= (1ull << 32)) {
-    set_err(ctx, "stripe batch too large: %llu stream blocks", (unsigned long long)total_blocks);
-    return ORCGPU_INVALID_ARGUMENT;
-  }
-  const uint32_t n_tiles = (uint32_t)(total_blocks / RLE_TILE);
-  uint64_t blk_entry = P.scratch.take(total_blocks * 4), blk_exit = P.scratch.take(total_blocks * 4);
-  uint64_t blk_nvals = P.scratch.take(total_blocks * 4), blk_voff = P.scratch.take(total_blocks * 4);
-  uint64_t blk_tbase = P.scratch.take((uint64_t)n_tiles * 4 + 16), blk_tsum = P.scratch.take((uint64_t)n_tiles * 4 + 16);
-  uint64_t blk_flags = P.scratch.take(total_blocks + 16);
-  uint64_t blk_badmap = P.scratch.take(total_blocks / 8 + 64);
-  uint32_t cls_tab0[JC_COUNT + 1] = {0};
-  for (int c = 0; c < JC_COUNT; c++) cls_tab0[c + 1] = cls_tab0[c] + cls_groups[c];
-  uint64_t blk_gjob = P.scratch.take((uint64_t)cls_tab0[JC_COUNT] * 4 + 16);
+// compressed streams: chunk tables
+int plan_chunk_tables(LaneRun& R) {
+  int rc = plan_decompress(R.P, R.DP);
+  R.ht.dp = host_us_now();
+  return rc;
+}
+
+int lay_out_jobs(LaneRun& R) {
+  R.L = layout_jobs(R.P.jobs);
+  R.njobs = (int)R.L.order.size();
+  if (R.L.fits) return ORCGPU_OK;
+  set_err(R.ctx, "stripe batch too large: %llu stream blocks", (unsigned long long)R.L.total_blocks);
+  return ORCGPU_INVALID_ARGUMENT;
+}
+
+// The workspace of everything behind the plan -- the per-block arrays, the exact walk's maps, the hint table, the summary and
+// the job tables of the later phases --, then the memory itself: workspace, result arenas, pinned summary.
+int reserve_workspace(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  Plan& P = R.P;
+  const uint64_t total_blocks = R.L.total_blocks, n_tiles = R.L.n_tiles;
+  auto& B = R.blk_off;
+  B.entry = P.scratch.take(total_blocks * 4), B.exit_ = P.scratch.take(total_blocks * 4);
+  B.nvals = P.scratch.take(total_blocks * 4), B.voff = P.scratch.take(total_blocks * 4);
+  B.tbase = P.scratch.take(n_tiles * 4 + 16), B.tsum = P.scratch.take(n_tiles * 4 + 16);
+  B.flags = P.scratch.take(total_blocks + 16);
+  B.badmap = P.scratch.take(total_blocks / 8 + 64);
+  B.gjob = P.scratch.take((uint64_t)R.L.cls_tab0[JC_COUNT] * 4 + 16);
   // the exact parallel walk (rle_exact_*): a map of 4608 two-byte exits per span of 256 blocks and per tile, 7 % of the streams' bytes
-  constexpr bool exact_walk = true;
-  const uint32_t n_xspans = (uint32_t)((total_blocks + RLE_EXACT_SPAN - 1) / RLE_EXACT_SPAN);
+  R.n_xspans = (uint32_t)((total_blocks + RLE_EXACT_SPAN - 1) / RLE_EXACT_SPAN);
   // The exact parallel walk -- four launches, two of them of 512-thread workgroups with 51 KiB of LDS that "end at once" for
   // streams that do not need them -- is only sent when the LAST call of this lane met a stream that did (orcgpu_ctx::exact_on:
   // a job whose mending passes left RLE_EXACT_MIN blocks or more).  Ending at once is not free: beside the other column lane's
@@ -426,22 +462,23 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   // one headline step, the lane's expansion behind it (rocprof, round 6).  A stream of that kind met for the first time goes
   // through the serial repair once (exact either way; 23 instead of 3.6 ms per 24 M rows of bench.py's c2-adv), the calls behind
   // it -- the next stripes of the same file -- take the parallel walk.
-  const bool use_exact = exact_walk && total_blocks >= 2048 && ctx->exact_on;  // (smaller calls: the serial repair is quick enough)
-  const uint64_t x_fmap = use_exact ? P.scratch.take((uint64_t)n_xspans * RLE_EXACT_E * 2 + 16) : 0;
-  const uint64_t x_gmap = use_exact ? P.scratch.take((uint64_t)n_tiles * RLE_EXACT_E * 2 + 16) : 0;
-  const uint64_t x_tile = use_exact ? P.scratch.take((uint64_t)n_tiles * 4 + 16) : 0;
-  const uint64_t x_span = use_exact ? P.scratch.take((uint64_t)n_xspans * 4 + 16) : 0;
-  // verified run starts (orcgpu_stream::entries): one table for the call, a slice per job; the per-block entries they give
-  std::vector<RleHint> hints;
-  for (size_t k = 0; k < order.size(); k++) {
-    const JobPlan& j = P.jobs[order[k]];
-    if (!j.hint_src) continue;
-    for (auto& h : j.hint_src->hints) hints.push_back(RleHint{(uint32_t)k, h.first == 0xffffffffu ? 0xffffffffu : j.chunk0 + h.first, h.second, 0});
+  R.use_exact = total_blocks >= 2048 && ctx->exact_on;  // (smaller calls: the serial repair is quick enough)
+  if (R.use_exact) {
+    R.x_fmap = P.scratch.take((uint64_t)R.n_xspans * RLE_EXACT_E * 2 + 16);
+    R.x_gmap = P.scratch.take(n_tiles * RLE_EXACT_E * 2 + 16);
+    R.x_tile = P.scratch.take(n_tiles * 4 + 16);
+    R.x_span = P.scratch.take((uint64_t)R.n_xspans * 4 + 16);
   }
-  const uint64_t hints_off = hints.empty() ? 0 : P.scratch.take(hints.size() * sizeof(RleHint) + 16);
-  const uint64_t blk_hint = hints.empty() ? 0 : P.scratch.take(total_blocks * 4 + 16);
+  // verified run starts (orcgpu_stream::entries): one table for the call, a slice per job; the per-block entries they give
+  for (size_t k = 0; k < R.L.order.size(); k++) {
+    const JobPlan& j = P.jobs[R.L.order[k]];
+    if (!j.hint_src) continue;
+    for (auto& h : j.hint_src->hints) R.hints.push_back(RleHint{(uint32_t)k, h.first == 0xffffffffu ? 0xffffffffu : j.chunk0 + h.first, h.second, 0});
+  }
+  R.hints_off = R.hints.empty() ? 0 : P.scratch.take(R.hints.size() * sizeof(RleHint) + 16);
+  B.hint = R.hints.empty() ? 0 : P.scratch.take(total_blocks * 4 + 16);
 
-  SummaryLayout SL;
+  SummaryLayout& SL = R.SL;
   {
     Bump sb;
     SL.scalars_off = sb.take(P.scalars.size() * 8 + 8, 16);
@@ -450,12 +487,12 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
     SL.chartot_off = sb.take(P.n_chartot_slots * 8 + 8, 16);
     SL.bytes = align_up(sb.off, 16);
   }
-  uint64_t summary_off = P.scratch.take(SL.bytes);
+  R.summary_off = P.scratch.take(SL.bytes);
   {
     size_t ndict = 0;
     for (auto& cp : P.cols) ndict += cp.is_dict ? 1 : 0;
     P.dictjobs_off = P.scratch.take(ndict * sizeof(DictJob) + 64);
-    P.dictplaces_off = P.scratch.take(n * sizeof(DictPlace) + 64);
+    P.dictplaces_off = P.scratch.take(R.n * sizeof(DictPlace) + 64);
     size_t npres = 0;
     for (auto& cp : P.cols) npres += cp.has_present ? 1 : 0;
     P.presjobs_off = P.scratch.take(npres * sizeof(PresJob) + 64);
@@ -468,13 +505,13 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   }
 
   // ---- memory ------------------------------------------------------------------------------------------
-  (void)hipStreamSynchronize(st);  // earlier work may still use scratch / pinned memory
+  (void)hipStreamSynchronize(R.st);  // earlier work may still use scratch / pinned memory
   ctx->upload_reset();
   if (!ctx->scratch.ensure(P.scratch.off + kAlign)) {
     set_err(ctx, "hipMalloc(%llu) for the decode workspace failed", (unsigned long long)P.scratch.off);
     return ORCGPU_HIP_ERROR;
   }
-  for (uint32_t si = 0; si < n; si++) {
+  for (uint32_t si = 0; si < R.n; si++) {
     P.results[si]->arena_used[ctx->lane_id] = P.result_bump[si].off;
     P.results[si]->chars_used[ctx->lane_id] = 0;
     if (!P.results[si]->arena[ctx->lane_id].ensure(P.result_bump[si].off + kAlign)) {
@@ -482,31 +519,39 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       return ORCGPU_HIP_ERROR;
     }
   }
-  if (!ctx->ensure_pinned(SL.bytes + DP.table_bytes + 64)) {
+  if (!ctx->ensure_pinned(SL.bytes + R.DP.table_bytes + 64)) {
     set_err(ctx, "hipHostMalloc for the summary failed");
     return ORCGPU_HIP_ERROR;
   }
-  uint8_t* S = ctx->scratch.p;
+  R.S = ctx->scratch.p;
   {
     // debugging aid (tests / fuzzing): fill the workspace and the result buffers with a byte pattern so that
     // anything read before it is written shows up deterministically instead of depending on earlier decodes
     static const char* poison = getenv("ORCGPU_POISON");
     if (poison && *poison) {
       const int v = (int)strtol(poison, nullptr, 0) & 0xFF;
-      (void)hipMemsetAsync(S, v, P.scratch.off, st);
-      for (uint32_t si = 0; si < n; si++) (void)hipMemsetAsync(P.results[si]->arena[ctx->lane_id].p, v, P.result_bump[si].off, st);
+      (void)hipMemsetAsync(R.S, v, P.scratch.off, R.st);
+      for (uint32_t si = 0; si < R.n; si++) (void)hipMemsetAsync(R.arena(P.results[si]), v, P.result_bump[si].off, R.st);
     }
   }
-  // ---- host mirror of the summary -----------------------------------------------------------------------
-  uint8_t* hs = ctx->pinned;
+  return ORCGPU_OK;
+}
+
+// ---- host mirror of the summary, and where its device copy and the block arrays lie -----------------------------------------
+void fill_summary_mirror(LaneRun& R) {
+  const Plan& P = R.P;
+  const JobLayout& L = R.L;
+  const SummaryLayout& SL = R.SL;
+  uint8_t* const S = R.S;
+  uint8_t* const hs = R.hs = R.ctx->pinned;
   memset(hs, 0, SL.bytes);
   memcpy(hs + SL.scalars_off, P.scalars.data(), P.scalars.size() * 8);
-  RleJob* hjobs = reinterpret_cast<RleJob*>(hs + SL.jobs_off);
-  for (size_t k = 0; k < order.size(); k++) {
-    const JobPlan& j = P.jobs[order[k]];
+  RleJob* const hjobs = R.hjobs = reinterpret_cast<RleJob*>(hs + SL.jobs_off);
+  for (size_t k = 0; k < L.order.size(); k++) {
+    const JobPlan& j = P.jobs[L.order[k]];
     RleJob& d = hjobs[k];
     d.data = j.data_scratch_off != ~0ull ? S + j.data_scratch_off : j.data;
-    d.out = j.out_result_off != ~0ull ? (void*)(P.results[j.result_index]->arena[ctx->lane_id].p + j.out_result_off) : (void*)(S + j.out_scratch_off);
+    d.out = j.out_result_off != ~0ull ? (void*)(R.arena(P.results[j.result_index]) + j.out_result_off) : (void*)(S + j.out_scratch_off);
     d.len_idx = j.len_idx;
     d.needed_idx = j.needed_idx;
     d.total_idx = j.total_idx;
@@ -515,8 +560,8 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
     d.group0 = j.group0;
     d.ngroups = j.ngroups;
     d.group_size = j.group_size;
-    d.group_tab0 = cls_tab0[j.cls] + j.group0;
-    d.class_index = (uint32_t)j.final_index - cls_first[j.cls];
+    d.group_tab0 = L.cls_tab0[j.cls] + j.group0;
+    d.class_index = (uint32_t)j.final_index - L.cls_first[j.cls];
     d.codec = j.codec;
     d.is_signed = j.is_signed;
     d.nbits = j.nbits;
@@ -533,47 +578,65 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
     d.err = RLE_NO_ERR;
     d.err_pos = RLE_NO_ERR;
   }
-  for (size_t h = 0; h < hints.size(); h++) {
-    RleJob& d = hjobs[hints[h].job];
+  for (size_t h = 0; h < R.hints.size(); h++) {
+    RleJob& d = hjobs[R.hints[h].job];
     if (!d.n_hints) d.hint0 = (uint32_t)h;
     d.n_hints++;
   }
-  uint8_t* dsum = S + summary_off;
-  uint64_t* d_scalars = reinterpret_cast<uint64_t*>(dsum + SL.scalars_off);
-  RleJob* d_jobs = reinterpret_cast<RleJob*>(dsum + SL.jobs_off);
-  unsigned long long* d_nullc = reinterpret_cast<unsigned long long*>(dsum + SL.nullc_off);
-  unsigned long long* d_chartot = reinterpret_cast<unsigned long long*>(dsum + SL.chartot_off);
-  RleBlocks blk;
-  blk.entry = reinterpret_cast<uint32_t*>(S + blk_entry);
-  blk.exit_ = reinterpret_cast<uint32_t*>(S + blk_exit);
-  blk.nvals = reinterpret_cast<uint32_t*>(S + blk_nvals);
-  blk.voff = reinterpret_cast<uint32_t*>(S + blk_voff);
-  blk.tile_base = reinterpret_cast<uint32_t*>(S + blk_tbase);
-  blk.flags = S + blk_flags;
-  blk.badmap = reinterpret_cast<uint32_t*>(S + blk_badmap);
-  blk.group_job = reinterpret_cast<uint32_t*>(S + blk_gjob);
-  blk.hint = hints.empty() ? nullptr : reinterpret_cast<uint32_t*>(S + blk_hint);
-  uint32_t* d_tsum = reinterpret_cast<uint32_t*>(S + blk_tsum);
-  const int njobs = (int)order.size();
+  uint8_t* const dsum = R.dsum = S + R.summary_off;
+  R.d_scalars = reinterpret_cast<uint64_t*>(dsum + SL.scalars_off);
+  R.d_jobs = reinterpret_cast<RleJob*>(dsum + SL.jobs_off);
+  R.d_nullc = reinterpret_cast<unsigned long long*>(dsum + SL.nullc_off);
+  R.d_chartot = reinterpret_cast<unsigned long long*>(dsum + SL.chartot_off);
+  RleBlocks& blk = R.blk;
+  const auto& B = R.blk_off;
+  blk.entry = reinterpret_cast<uint32_t*>(S + B.entry);
+  blk.exit_ = reinterpret_cast<uint32_t*>(S + B.exit_);
+  blk.nvals = reinterpret_cast<uint32_t*>(S + B.nvals);
+  blk.voff = reinterpret_cast<uint32_t*>(S + B.voff);
+  blk.tile_base = reinterpret_cast<uint32_t*>(S + B.tbase);
+  blk.flags = S + B.flags;
+  blk.badmap = reinterpret_cast<uint32_t*>(S + B.badmap);
+  blk.group_job = reinterpret_cast<uint32_t*>(S + B.gjob);
+  blk.hint = R.hints.empty() ? nullptr : reinterpret_cast<uint32_t*>(S + B.hint);
+  R.d_tsum = reinterpret_cast<uint32_t*>(S + B.tsum);
+}
 
-  // ---- launches ------------------------------------------------------------------------------------------
-  ht_plan = hclock();
-  for (uint32_t si = 0; si < n; si++)  // the stripes' bytes may still be on their way (staging does not wait for its copies)
-    if (stripes[si]->ready) HIP_TRY(ctx, hipStreamWaitEvent(st, stripes[si]->ready, 0));
+// ---- launches ------------------------------------------------------------------------------------------
+int launch_decompression(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  hipStream_t st = R.st;
+  R.ht.plan = host_us_now();
+  for (uint32_t si = 0; si < R.n; si++)  // the stripes' bytes may still be on their way (staging does not wait for its copies)
+    if (R.stripes[si]->ready) HIP_TRY(ctx, hipStreamWaitEvent(st, R.stripes[si]->ready, 0));
   HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
   ctx->kev_used[0] = ctx->kev_used[1] = false;
   ctx->lit_ev_used = false;
-  HIP_TRY(ctx, hipMemcpyAsync(dsum, hs, SL.bytes, hipMemcpyHostToDevice, st));
-  const double ht_launch = hclock();  // (the waits for the stripes' bytes and the summary's copy are enqueued)
+  HIP_TRY(ctx, hipMemcpyAsync(R.dsum, R.hs, R.SL.bytes, hipMemcpyHostToDevice, st));
+  R.ht.launch = host_us_now();  // (the waits for the stripes' bytes and the summary's copy are enqueued)
   ctx->hp_fill = ctx->hp_upload = ctx->hp_gate = 0;
-  rc = launch_decompress(ctx, P, DP, S, d_scalars, hs + SL.bytes, ctx->ev[6], ctx->ev[7], ctx->ev[4], ctx->ev[8]);
-  const double ht_first = hclock();
-  if (rc) return rc;
+  int rc = launch_decompress(ctx, R.P, R.DP, R.S, R.d_scalars, R.hs + R.SL.bytes, ctx->ev[6], ctx->ev[7], ctx->ev[4], ctx->ev[8]);
+  R.ht.first = host_us_now();
+  return rc;
+}
+
+// The per-block entries the hints give, the block walk with its mending passes, the repair and the scans of the values per block
+int launch_walk(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  hipStream_t st = R.st;
+  uint8_t* const S = R.S;
+  RleJob* const d_jobs = R.d_jobs;
+  uint64_t* const d_scalars = R.d_scalars;
+  const RleBlocks& blk = R.blk;
+  const std::vector<RleHint>& hints = R.hints;
+  const uint64_t total_blocks = R.L.total_blocks;
+  const uint32_t n_tiles = R.L.n_tiles, n_xspans = R.n_xspans;
+  const int njobs = R.njobs;
   if (njobs && !hints.empty()) {
     HIP_TRY(ctx, hipMemsetAsync(blk.hint, 0xff, total_blocks * 4, st));
-    HIP_TRY(ctx, ctx->upload(S + hints_off, hints.data(), hints.size() * sizeof(RleHint), st));
-    HIP_TRY(ctx, launch(rle_hint_kernel, (uint64_t)hints.size(), false, 64, st, d_jobs, (const RleHint*)(S + hints_off), (uint32_t)hints.size(), blk,
-                        (const uint64_t*)d_scalars, (const uint32_t*)(DP.n_chunks ? S + DP.chunk_start_off : S)));
+    HIP_TRY(ctx, ctx->upload(S + R.hints_off, hints.data(), hints.size() * sizeof(RleHint), st));
+    HIP_TRY(ctx, launch(rle_hint_kernel, (uint64_t)hints.size(), false, 64, st, d_jobs, (const RleHint*)(S + R.hints_off), (uint32_t)hints.size(), blk,
+                        (const uint64_t*)d_scalars, (const uint32_t*)(R.DP.n_chunks ? S + R.DP.chunk_start_off : S)));
   }
   if (njobs) {
     static const int kModes[] = {0, 3, -1, 1, 1, 2};  // guess, fill, short-run spans, relax x2 (4 sweeps each), verify
@@ -594,18 +657,17 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       else
         HIP_TRY(ctx, launch(rle_walk_kernel, total_blocks, false, 64, st, d_jobs, njobs, blk, (const uint64_t*)d_scalars, (uint32_t)total_blocks, mode));
     }
-    constexpr int mend_passes = 2;
-    for (int pass = 0; pass < mend_passes; pass++) {
+    for (int pass = 0; pass < 2; pass++) {
       // damaged stretches, all at once; then the check again (both return at once for streams the first check passed)
       HIP_TRY(ctx, launch(rle_mend_kernel, total_blocks, false, 256, st, d_jobs, njobs, blk, (const uint64_t*)d_scalars, (uint32_t)total_blocks));
       HIP_TRY(ctx, launch(rle_walk_kernel, total_blocks, false, 64, st, d_jobs, njobs, blk, (const uint64_t*)d_scalars, (uint32_t)total_blocks, 5));
     }
-    if (use_exact && mend_passes > 0) {
+    if (R.use_exact) {
       // streams the mending passes could not settle: the exact walk, in parallel (four launches that end at once otherwise)
-      uint16_t* fmap = reinterpret_cast<uint16_t*>(S + x_fmap);
-      uint16_t* gmap = reinterpret_cast<uint16_t*>(S + x_gmap);
-      uint32_t* tile_e = reinterpret_cast<uint32_t*>(S + x_tile);
-      uint32_t* span_e = reinterpret_cast<uint32_t*>(S + x_span);
+      uint16_t* fmap = reinterpret_cast<uint16_t*>(S + R.x_fmap);
+      uint16_t* gmap = reinterpret_cast<uint16_t*>(S + R.x_gmap);
+      uint32_t* tile_e = reinterpret_cast<uint32_t*>(S + R.x_tile);
+      uint32_t* span_e = reinterpret_cast<uint32_t*>(S + R.x_span);
       const uint64_t cus = ctx->n_cus ? ctx->n_cus : 256;
       HIP_TRY(ctx, launch(rle_exact_map_kernel, std::min<uint64_t>(n_xspans, 2 * cus), true, RLE_EXACT_WG, st, d_jobs, njobs, (const uint64_t*)d_scalars, (uint32_t)total_blocks, fmap));
       HIP_TRY(ctx, launch(rle_exact_tile_kernel, std::min<uint64_t>(n_tiles, 4 * cus), true, RLE_EXACT_WG, st, d_jobs, njobs, (const uint64_t*)d_scalars, (uint32_t)total_blocks,
@@ -615,210 +677,218 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
                           (const uint32_t*)span_e));
     }
     HIP_TRY(ctx, launch(rle_repair_kernel, (uint64_t)njobs, true, 64, st, d_jobs, njobs, blk, (const uint64_t*)d_scalars));
-    HIP_TRY(ctx, launch(rle_tile_scan_kernel, (uint64_t)n_tiles, true, 256, st, blk, d_tsum));
-    HIP_TRY(ctx, launch(rle_job_scan_kernel, (uint64_t)njobs, true, 256, st, (const RleJob*)d_jobs, blk, (const uint32_t*)d_tsum, d_scalars));
+    HIP_TRY(ctx, launch(rle_tile_scan_kernel, (uint64_t)n_tiles, true, 256, st, blk, R.d_tsum));
+    HIP_TRY(ctx, launch(rle_job_scan_kernel, (uint64_t)njobs, true, 256, st, (const RleJob*)d_jobs, blk, (const uint32_t*)R.d_tsum, d_scalars));
   }
   HIP_TRY(ctx, hipEventRecord(ctx->ev[5], st));
-  const double ht_walk = hclock();
-  // PRESENT streams first: everything else needs the non-null counts.  By depth: the PRESENT stream of a Struct's field is as
-  // long as the Struct has non-null rows, and its bits are dealt out to them (array_decoder/mod.rs:216-252): depth d needs the
-  // words, ranks and counts of depth d - 1.
-  {
-    size_t pres_at = 0;  // presjobs of the depths done so far (the device table is filled depth after depth)
-    P.presjobs.reserve(P.cols.size());
-    PresJob* const dp_all = reinterpret_cast<PresJob*>(S + P.presjobs_off);
-    P.presjobs.clear();
-    int max_depth = 0;
-    for (auto& cp : P.cols) max_depth = std::max(max_depth, cp.depth);
-    for (int depth = 0; depth <= max_depth && depth <= kMaxStructDepth; depth++) {
-      const int cls = depth == 0 ? JC_PRESENT : JC_PRESENT1 + depth - 1;
-      if (cls_groups[cls])
-        HIP_TRY(ctx, launch(byte_expand_kernel, (uint64_t)(cls_groups[cls] + 3) / 4, true, 256, st, d_jobs + cls_first[cls],
-                            (const uint32_t*)(blk.group_job + cls_tab0[cls]), blk, (const uint64_t*)d_scalars, cls_groups[cls]));
-      // validity words, ranks, per-batch bitmaps and null counts of ALL columns of this depth: five launches
-      uint64_t max_words = 0, max_tiles = 0, max_out = 0;
-      for (auto& cp : P.cols) {
-        if (!cp.has_present || cp.depth != depth || !cp.n_rows) continue;
-        orcgpu_result* r = P.results[cp.stripe];
-        PresJob j{};
-        if (cp.arm_of >= 0) {
-          // an arm of a Union: valid where the Union is and its tag is the arm's
-          const ColPlan& un = P.cols[cp.arm_of];
-          j.tags = reinterpret_cast<const int8_t*>(S + un.dense_off);
-          j.tag = cp.arm_tag;
-          j.child_bits = cp.child_bits;  // (its child's PRESENT stream entered in mid-byte: a Union in a stripe read by row groups)
-          j.vbits = reinterpret_cast<unsigned long long*>(S + cp.vbits_off);
-          j.wpop = reinterpret_cast<uint32_t*>(S + cp.wpop_off);
-          j.rank = reinterpret_cast<uint32_t*>(S + cp.rank_off);
-          j.rtiles = reinterpret_cast<uint32_t*>(S + cp.rank_tiles_off);
-          j.validity = reinterpret_cast<unsigned long long*>(S + cp.arm_validity_off);
-          j.null_counts = d_nullc + cp.nullcount_off;
-          j.nonnull_out = d_scalars + cp.nonnull_idx;
-          j.ceil8b_out = d_scalars + cp.ceil8_idx;
-          if (un.has_present) {
-            j.parent_vbits = reinterpret_cast<const unsigned long long*>(S + un.vbits_off);
-            j.parent_rank = reinterpret_cast<const uint32_t*>(S + un.rank_off);
-          }
-          j.n_rows = cp.n_rows;
-          j.n_words = cp.n_words;
-          j.n_rank_tiles = cp.n_rank_tiles;
-          j.n_out_words = (uint64_t)r->n_batches * r->words_per_batch;
-          j.batch = r->batch;
-          j.words_per_batch = r->words_per_batch;
-          P.presjobs.push_back(j);
-          max_words = std::max<uint64_t>(max_words, j.n_words);
-          max_tiles = std::max<uint64_t>(max_tiles, j.n_rank_tiles);
-          max_out = std::max<uint64_t>(max_out, j.n_out_words);
-          continue;
-        }
-        ColumnOut& co = r->cols[cp.col];
-        j.pbytes = cp.own_present ? S + cp.pbytes_off : nullptr;
-        j.vbits = reinterpret_cast<unsigned long long*>(S + cp.vbits_off);
-        j.wpop = reinterpret_cast<uint32_t*>(S + cp.wpop_off);
-        j.rank = reinterpret_cast<uint32_t*>(S + cp.rank_off);
-        j.rtiles = reinterpret_cast<uint32_t*>(S + cp.rank_tiles_off);
-        j.validity = reinterpret_cast<unsigned long long*>(r->arena[ctx->lane_id].p + co.validity_off);
-        j.null_counts = d_nullc + cp.nullcount_off;
-        j.nonnull_out = d_scalars + cp.nonnull_idx;
-        j.ceil8_out = cp.c.orc_type == ORCGPU_T_BOOLEAN ? d_scalars + cp.dictbytes_idx : nullptr;
-        j.ceil8b_out = cp.c.orc_type == ORCGPU_T_STRUCT ? d_scalars + cp.ceil8_idx : nullptr;
-        j.bit0 = cp.own_present ? cp.present.skip_bits : 0;
-        j.data_bits = cp.c.orc_type == ORCGPU_T_BOOLEAN ? cp.data.skip_bits : 0;
-        j.child_bits = cp.child_bits;
-        j.job = cp.own_present ? d_jobs + P.jobs[cp.job_present].final_index : nullptr;
-        if (cp.parent_plan >= 0) {
-          const ColPlan& pp = P.cols[cp.parent_plan];
-          j.parent_vbits = reinterpret_cast<const unsigned long long*>(S + pp.vbits_off);
-          j.parent_rank = reinterpret_cast<const uint32_t*>(S + pp.rank_off);
-        }
-        j.n_rows = cp.n_rows;
-        j.n_words = cp.n_words;
-        j.n_rank_tiles = cp.n_rank_tiles;
-        j.n_out_words = (uint64_t)r->n_batches * r->words_per_batch;
-        j.batch = r->batch;
-        j.words_per_batch = r->words_per_batch;
-        P.presjobs.push_back(j);
-        max_words = std::max<uint64_t>(max_words, j.n_words);
-        max_tiles = std::max<uint64_t>(max_tiles, j.n_rank_tiles);
-        max_out = std::max<uint64_t>(max_out, j.n_out_words);
-      }
-      const uint32_t np = (uint32_t)(P.presjobs.size() - pres_at);
-      if (np) {
-        PresJob* dp = dp_all + pres_at;
-        HIP_TRY(ctx, ctx->upload(dp, P.presjobs.data() + pres_at, np * sizeof(PresJob), st));
-        // (grid.y is limited to 65535: more columns than that go in slices)
-        for (uint32_t o = 0; o < np; o += 65535u) {
-          const uint32_t ny = std::min<uint32_t>(65535u, np - o);
-          const PresJob* dq = dp + o;
-          auto grid = [&](uint64_t threads) { return dim3((uint32_t)std::max<uint64_t>(1, (threads + 255) / 256), ny); };
-          hipLaunchKernelGGL(pres_words_kernel, grid(max_words), dim3(256), 0, st, dq);
-          hipLaunchKernelGGL(pres_scan_tiles_kernel, dim3((uint32_t)std::max<uint64_t>(1, max_tiles), ny), dim3(256), 0, st, dq);
-          hipLaunchKernelGGL(pres_scan_sums_kernel, dim3(ny), dim3(256), 0, st, dq);
-          hipLaunchKernelGGL(pres_scan_apply_kernel, grid(max_words), dim3(256), 0, st, dq);
-          hipLaunchKernelGGL(pres_validity_kernel, grid(max_out), dim3(256), 0, st, dq);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-      }
-      pres_at = P.presjobs.size();
-    }
+  R.ht.walk = host_us_now();
+  return ORCGPU_OK;
+}
+
+// One class's expansion: a wavefront per group of blocks
+template <typename K>
+hipError_t launch_expand(LaneRun& R, K kernel, int cls, uint32_t* launches = nullptr) {
+  const JobLayout& L = R.L;
+  if (!L.cls_groups[cls]) return hipSuccess;
+  const hipError_t e = launch(kernel, (uint64_t)(L.cls_groups[cls] + 3) / 4, true, 256, R.st, R.d_jobs + L.cls_first[cls], (const uint32_t*)(R.blk.group_job + L.cls_tab0[cls]),
+                              R.blk, (const uint64_t*)R.d_scalars, L.cls_groups[cls]);
+  if (e == hipSuccess && launches) ++*launches;  // (orcgpu_last_timing counts the launches of the expansion phase)
+  return e;
+}
+
+// The PRESENT job of a column, or of a Union's arm: where its bits come from and what is formed of them
+PresJob make_pres_job(LaneRun& R, const ColPlan& cp) {
+  const Plan& P = R.P;
+  uint8_t* const S = R.S;
+  uint64_t* const d_scalars = R.d_scalars;
+  orcgpu_result* r = P.results[cp.stripe];
+  PresJob j{};
+  const ColPlan* above = nullptr;  // the Struct / Union / arm whose non-null rows this one's bits are dealt out to
+  if (cp.arm_of >= 0) {
+    // an arm of a Union: valid where the Union is and its tag is the arm's
+    const ColPlan& un = P.cols[cp.arm_of];
+    j.tags = reinterpret_cast<const int8_t*>(S + un.dense_off);
+    j.tag = cp.arm_tag;
+    j.validity = reinterpret_cast<unsigned long long*>(S + cp.arm_validity_off);
+    j.ceil8b_out = d_scalars + cp.ceil8_idx;
+    if (un.has_present) above = &un;
+  } else {
+    ColumnOut& co = r->cols[cp.col];
+    j.pbytes = cp.own_present ? S + cp.pbytes_off : nullptr;
+    j.validity = reinterpret_cast<unsigned long long*>(R.arena(r) + co.validity_off);
+    j.ceil8_out = cp.c.orc_type == ORCGPU_T_BOOLEAN ? d_scalars + cp.dictbytes_idx : nullptr;
+    j.ceil8b_out = cp.c.orc_type == ORCGPU_T_STRUCT ? d_scalars + cp.ceil8_idx : nullptr;
+    j.bit0 = cp.own_present ? cp.present.skip_bits : 0;
+    j.data_bits = cp.c.orc_type == ORCGPU_T_BOOLEAN ? cp.data.skip_bits : 0;
+    j.job = cp.own_present ? R.d_jobs + P.jobs[cp.job_present].final_index : nullptr;
+    if (cp.parent_plan >= 0) above = &P.cols[cp.parent_plan];
   }
-  rc = launch_pre_expand_ext(ctx, P, S, d_scalars);
-  if (rc) return rc;
+  j.child_bits = cp.child_bits;  // (its child's PRESENT stream entered in mid-byte: a Union in a stripe read by row groups)
+  j.vbits = reinterpret_cast<unsigned long long*>(S + cp.vbits_off);
+  j.wpop = reinterpret_cast<uint32_t*>(S + cp.wpop_off);
+  j.rank = reinterpret_cast<uint32_t*>(S + cp.rank_off);
+  j.rtiles = reinterpret_cast<uint32_t*>(S + cp.rank_tiles_off);
+  j.null_counts = R.d_nullc + cp.nullcount_off;
+  j.nonnull_out = d_scalars + cp.nonnull_idx;
+  if (above) {
+    j.parent_vbits = reinterpret_cast<const unsigned long long*>(S + above->vbits_off);
+    j.parent_rank = reinterpret_cast<const uint32_t*>(S + above->rank_off);
+  }
+  j.n_rows = cp.n_rows;
+  j.n_words = cp.n_words;
+  j.n_rank_tiles = cp.n_rank_tiles;
+  j.n_out_words = (uint64_t)r->n_batches * r->words_per_batch;
+  j.batch = r->batch;
+  j.words_per_batch = r->words_per_batch;
+  return j;
+}
+
+// PRESENT streams first: everything else needs the non-null counts.  By depth: the PRESENT stream of a Struct's field is as
+// long as the Struct has non-null rows, and its bits are dealt out to them (array_decoder/mod.rs:216-252): depth d needs the
+// words, ranks and counts of depth d - 1.
+int launch_present(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  hipStream_t st = R.st;
+  Plan& P = R.P;
+  size_t pres_at = 0;  // presjobs of the depths done so far (the device table is filled depth after depth)
+  P.presjobs.reserve(P.cols.size());
+  PresJob* const dp_all = reinterpret_cast<PresJob*>(R.S + P.presjobs_off);
+  P.presjobs.clear();
+  int max_depth = 0;
+  for (auto& cp : P.cols) max_depth = std::max(max_depth, cp.depth);
+  for (int depth = 0; depth <= max_depth && depth <= kMaxStructDepth; depth++) {
+    HIP_TRY(ctx, launch_expand(R, byte_expand_kernel, depth == 0 ? JC_PRESENT : JC_PRESENT1 + depth - 1));
+    // validity words, ranks, per-batch bitmaps and null counts of ALL columns of this depth: five launches
+    uint64_t max_words = 0, max_tiles = 0, max_out = 0;
+    for (auto& cp : P.cols) {
+      if (!cp.has_present || cp.depth != depth || !cp.n_rows) continue;
+      const PresJob j = make_pres_job(R, cp);
+      P.presjobs.push_back(j);
+      max_words = std::max<uint64_t>(max_words, j.n_words);
+      max_tiles = std::max<uint64_t>(max_tiles, j.n_rank_tiles);
+      max_out = std::max<uint64_t>(max_out, j.n_out_words);
+    }
+    const uint32_t np = (uint32_t)(P.presjobs.size() - pres_at);
+    if (np) {
+      PresJob* dp = dp_all + pres_at;
+      HIP_TRY(ctx, ctx->upload(dp, P.presjobs.data() + pres_at, np * sizeof(PresJob), st));
+      // (grid.y is limited to 65535: more columns than that go in slices)
+      for (uint32_t o = 0; o < np; o += 65535u) {
+        const uint32_t ny = std::min<uint32_t>(65535u, np - o);
+        const PresJob* dq = dp + o;
+        auto grid = [&](uint64_t threads) { return dim3((uint32_t)std::max<uint64_t>(1, (threads + 255) / 256), ny); };
+        hipLaunchKernelGGL(pres_words_kernel, grid(max_words), dim3(256), 0, st, dq);
+        hipLaunchKernelGGL(pres_scan_tiles_kernel, dim3((uint32_t)std::max<uint64_t>(1, max_tiles), ny), dim3(256), 0, st, dq);
+        hipLaunchKernelGGL(pres_scan_sums_kernel, dim3(ny), dim3(256), 0, st, dq);
+        hipLaunchKernelGGL(pres_scan_apply_kernel, grid(max_words), dim3(256), 0, st, dq);
+        hipLaunchKernelGGL(pres_validity_kernel, grid(max_out), dim3(256), 0, st, dq);
+      }
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    pres_at = P.presjobs.size();
+  }
   HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
-  const double ht_pres = hclock();
+  R.ht.pres = host_us_now();
+  return ORCGPU_OK;
+}
+
+int launch_expansion(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
   ctx->last_expand_launches = 0;
   {
     // streams expected to hold one value throughout (Decimal scales): checked in front of the expansion, which then skips them
     bool any_uniform = false;
-    for (const JobPlan& j : P.jobs) any_uniform = any_uniform || j.uniform_idx != 0;
-    if (any_uniform) HIP_TRY(ctx, launch(rle2_uniform_kernel, (uint64_t)njobs, true, 256, st, (const RleJob*)d_jobs, (uint32_t)njobs, d_scalars));
+    for (const JobPlan& j : R.P.jobs) any_uniform = any_uniform || j.uniform_idx != 0;
+    if (any_uniform) HIP_TRY(ctx, launch(rle2_uniform_kernel, (uint64_t)R.njobs, true, 256, R.st, (const RleJob*)R.d_jobs, (uint32_t)R.njobs, R.d_scalars));
   }
-  if (cls_groups[JC_RLE2]) {
-    HIP_TRY(ctx, launch(rle2_expand_kernel, (uint64_t)(cls_groups[JC_RLE2] + 3) / 4, true, 256, st, d_jobs + cls_first[JC_RLE2],
-                        (const uint32_t*)(blk.group_job + cls_tab0[JC_RLE2]), blk, (const uint64_t*)d_scalars, cls_groups[JC_RLE2]));
-    ctx->last_expand_launches++;
-  }
-  if (cls_groups[JC_RLE1]) {
-    HIP_TRY(ctx, launch(rle1_expand_kernel, (uint64_t)(cls_groups[JC_RLE1] + 3) / 4, true, 256, st, d_jobs + cls_first[JC_RLE1],
-                        (const uint32_t*)(blk.group_job + cls_tab0[JC_RLE1]), blk, (const uint64_t*)d_scalars, cls_groups[JC_RLE1]));
-    ctx->last_expand_launches++;
-  }
-  if (cls_groups[JC_BYTE]) {
-    HIP_TRY(ctx, launch(byte_expand_kernel, (uint64_t)(cls_groups[JC_BYTE] + 3) / 4, true, 256, st, d_jobs + cls_first[JC_BYTE],
-                        (const uint32_t*)(blk.group_job + cls_tab0[JC_BYTE]), blk, (const uint64_t*)d_scalars, cls_groups[JC_BYTE]));
-    ctx->last_expand_launches++;
-  }
-  HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-  const double ht_exp = hclock();
+  HIP_TRY(ctx, launch_expand(R, rle2_expand_kernel, JC_RLE2, &ctx->last_expand_launches));
+  HIP_TRY(ctx, launch_expand(R, rle1_expand_kernel, JC_RLE1, &ctx->last_expand_launches));
+  HIP_TRY(ctx, launch_expand(R, byte_expand_kernel, JC_BYTE, &ctx->last_expand_launches));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev[2], R.st));
+  R.ht.exp = host_us_now();
+  return ORCGPU_OK;
+}
 
-  // ---- finishers: null spacing and per-type assembly -------------------------------------------------------
+// ---- finishers: null spacing and per-type assembly -------------------------------------------------------
+// One column's finisher launches, filed in `fin` by stage; its null spacing in P.spacejobs; its time zone shift in `tzjobs`
+int file_finishers(LaneRun& R, FinBatch& fin, std::vector<TzJob>& tzjobs, ColPlan& cp) {
+  Plan& P = R.P;
+  uint8_t* const S = R.S;
+  uint64_t* const d_scalars = R.d_scalars;
+  if (cp.col < 0) return ORCGPU_OK;  // (an arm of a Union: no column of its own)
+  orcgpu_result* r = P.results[cp.stripe];
+  ColumnOut& co = r->cols[cp.col];
+  const uint64_t nr = cp.n_rows;
+  if (!nr) return ORCGPU_OK;
+  const unsigned long long* vbits = R.vbits(cp);
+  const uint32_t* rank = R.rank(cp);
+  uint8_t* values = R.arena(r) + co.values_off;
+  const int t = cp.c.orc_type;
+  if (t == ORCGPU_T_UNION) {
+    // the type ids: the dense tags spaced over the rows (0 where the Union is null), checked against the number of arms
+    if (cp.has_present) P.spacejobs.push_back(SpaceJob{S + cp.dense_off, vbits, rank, values, nr, 1, 0, ~0ull});
+    else fin.add<copy_bytes_body, 256>(0, (nr + 15) / 16, false, (const uint8_t*)(S + cp.dense_off), values, nr);
+    fin.add<union_tags_body, 256>(0, nr, false, (const int8_t*)(S + cp.dense_off), (const uint64_t*)(d_scalars + cp.nonnull_idx), (int32_t)cp.n_arms,
+                                  reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx));
+  } else if (t == ORCGPU_T_SHORT || t == ORCGPU_T_INT || t == ORCGPU_T_LONG || t == ORCGPU_T_DATE || t == ORCGPU_T_BYTE) {
+    if (cp.has_present) P.spacejobs.push_back(SpaceJob{S + cp.dense_off, vbits, rank, values, nr, co.width, 0, ~0ull});  // one launch for all, below
+  } else if (t == ORCGPU_T_BOOLEAN) {
+    uint64_t n_out = (uint64_t)r->n_batches * r->words_per_batch;
+    fin.add<bool_values_body, 256>(0, n_out, false, (const uint8_t*)(S + cp.dense_off), vbits, rank, nr, r->batch, r->words_per_batch,
+                                   reinterpret_cast<unsigned long long*>(values), n_out, cp.data.skip_bits);
+  } else if (t == ORCGPU_T_FLOAT || t == ORCGPU_T_DOUBLE) {
+    const uint8_t* src = cp.data.scratch_off != ~0ull ? S + cp.data.scratch_off : cp.data.dev;
+    fin.add<float_check_body, 64>(0, 1, true, (const uint64_t*)d_scalars, cp.data.len_idx, cp.nonnull_idx, co.width, d_scalars + cp.err_idx);
+    if (cp.has_present) {
+      P.spacejobs.push_back(SpaceJob{src, vbits, rank, values, nr, co.width, 0, cp.data.len_upper / co.width});
+    } else {
+      uint64_t nb = std::min<uint64_t>(nr * co.width, cp.data.len_upper);
+      fin.add<copy_bytes_body, 256>(0, (nb + 15) / 16, false, src, values, nb);
+    }
+  } else if (t == ORCGPU_T_TIMESTAMP || t == ORCGPU_T_TIMESTAMP_INSTANT) {
+    fin.add<timestamp_body, 256>(0, nr, false, (const int64_t*)(S + cp.dense_off), (const int64_t*)(S + cp.dense2_off), vbits, rank, (int64_t*)values, nr,
+                                 // TIMESTAMP_INSTANT is UTC whatever the writer's zone (timestamp.rs:88-93)
+                                 t == ORCGPU_T_TIMESTAMP_INSTANT ? (int64_t)1420070400 : (int64_t)P.stripes[cp.stripe]->desc.ts_base_seconds, co.ts_unit,
+                                 reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx));
+    if (cp.tz) {
+      const orcgpu_staged* sg = P.stripes[cp.stripe];
+      const uint32_t n_at = (uint32_t)sg->zone->table.at.size();
+      TzJob j{};
+      j.values = values;
+      j.vbits = vbits;
+      j.validity = co.ts_unit != 4 ? reinterpret_cast<unsigned long long*>(R.arena(r) + co.validity_off) : nullptr;
+      j.null_counts = R.d_nullc + cp.nullcount_off;
+      j.at = reinterpret_cast<const long long*>(sg->zone->dev);
+      j.offs = reinterpret_cast<const int*>(sg->zone->dev + (size_t)n_at * 8);
+      j.n_rows = nr;
+      j.n_at = n_at;
+      j.offs0 = sg->zone->table.offs0;
+      j.fold_at = sg->zone->table.fold_at;
+      j.unit = co.ts_unit;
+      j.batch = r->batch;
+      j.words_per_batch = r->words_per_batch;
+      if (!cp.has_present && co.ts_unit != 4) {
+        const uint64_t nw = (uint64_t)r->n_batches * r->words_per_batch;
+        fin.add<validity_ones_body, 256>(0, nw, false, j.validity, nr, r->batch, r->words_per_batch, nw);
+      }
+      tzjobs.push_back(j);  // (behind the timestamp finishers: launched after the batch below)
+    }
+  } else {
+    return launch_finish_ext(R, fin, cp, co, r);
+  }
+  return ORCGPU_OK;
+}
+
+int launch_finishers(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  hipStream_t st = R.st;
+  Plan& P = R.P;
+  uint8_t* const S = R.S;
   P.spacejobs.clear();
   FinBatch fin;                 // the per-column finisher launches, filed by stage and sent together behind the loop
   std::vector<TzJob> tzjobs;
-  for (auto& cp : P.cols) {
-    if (cp.col < 0) continue;  // (an arm of a Union: no column of its own)
-    orcgpu_result* r = P.results[cp.stripe];
-    ColumnOut& co = r->cols[cp.col];
-    const uint64_t nr = cp.n_rows;
-    if (!nr) continue;
-    const unsigned long long* vbits = cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr;
-    const uint32_t* rank = cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr;
-    uint8_t* values = r->arena[ctx->lane_id].p + co.values_off;
-    const int t = cp.c.orc_type;
-    if (t == ORCGPU_T_UNION) {
-      // the type ids: the dense tags spaced over the rows (0 where the Union is null), checked against the number of arms
-      if (cp.has_present) P.spacejobs.push_back(SpaceJob{S + cp.dense_off, vbits, rank, values, nr, 1, 0, ~0ull});
-      else fin.add<copy_bytes_body, 256>(0, (nr + 15) / 16, false, (const uint8_t*)(S + cp.dense_off), values, nr);
-      fin.add<union_tags_body, 256>(0, nr, false, (const int8_t*)(S + cp.dense_off), (const uint64_t*)(d_scalars + cp.nonnull_idx), (int32_t)cp.n_arms,
-                                    reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx));
-    } else if (t == ORCGPU_T_SHORT || t == ORCGPU_T_INT || t == ORCGPU_T_LONG || t == ORCGPU_T_DATE || t == ORCGPU_T_BYTE) {
-      if (cp.has_present) P.spacejobs.push_back(SpaceJob{S + cp.dense_off, vbits, rank, values, nr, co.width, 0, ~0ull});  // one launch for all, below
-    } else if (t == ORCGPU_T_BOOLEAN) {
-      uint64_t n_out = (uint64_t)r->n_batches * r->words_per_batch;
-      fin.add<bool_values_body, 256>(0, n_out, false, (const uint8_t*)(S + cp.dense_off), vbits, rank, nr, r->batch, r->words_per_batch,
-                                     reinterpret_cast<unsigned long long*>(values), n_out, cp.data.skip_bits);
-    } else if (t == ORCGPU_T_FLOAT || t == ORCGPU_T_DOUBLE) {
-      const uint8_t* src = cp.data.scratch_off != ~0ull ? S + cp.data.scratch_off : cp.data.dev;
-      fin.add<float_check_body, 64>(0, 1, true, (const uint64_t*)d_scalars, cp.data.len_idx, cp.nonnull_idx, co.width, d_scalars + cp.err_idx);
-      if (cp.has_present) {
-        P.spacejobs.push_back(SpaceJob{src, vbits, rank, values, nr, co.width, 0, cp.data.len_upper / co.width});
-      } else {
-        uint64_t nb = std::min<uint64_t>(nr * co.width, cp.data.len_upper);
-        fin.add<copy_bytes_body, 256>(0, (nb + 15) / 16, false, src, values, nb);
-      }
-    } else if (t == ORCGPU_T_TIMESTAMP || t == ORCGPU_T_TIMESTAMP_INSTANT) {
-      fin.add<timestamp_body, 256>(0, nr, false, (const int64_t*)(S + cp.dense_off), (const int64_t*)(S + cp.dense2_off), vbits, rank, (int64_t*)values, nr,
-                                   // TIMESTAMP_INSTANT is UTC whatever the writer's zone (timestamp.rs:88-93)
-                                   t == ORCGPU_T_TIMESTAMP_INSTANT ? (int64_t)1420070400 : (int64_t)P.stripes[cp.stripe]->desc.ts_base_seconds, co.ts_unit,
-                                   reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx));
-      if (cp.tz) {
-        const orcgpu_staged* sg = P.stripes[cp.stripe];
-        const uint32_t n_at = (uint32_t)sg->zone->table.at.size();
-        TzJob j{};
-        j.values = values;
-        j.vbits = vbits;
-        j.validity = co.ts_unit != 4 ? reinterpret_cast<unsigned long long*>(r->arena[ctx->lane_id].p + co.validity_off) : nullptr;
-        j.null_counts = d_nullc + cp.nullcount_off;
-        j.at = reinterpret_cast<const long long*>(sg->zone->dev);
-        j.offs = reinterpret_cast<const int*>(sg->zone->dev + (size_t)n_at * 8);
-        j.n_rows = nr;
-        j.n_at = n_at;
-        j.offs0 = sg->zone->table.offs0;
-        j.fold_at = sg->zone->table.fold_at;
-        j.unit = co.ts_unit;
-        j.batch = r->batch;
-        j.words_per_batch = r->words_per_batch;
-        if (!cp.has_present && co.ts_unit != 4) {
-          const uint64_t nw = (uint64_t)r->n_batches * r->words_per_batch;
-          fin.add<validity_ones_body, 256>(0, nw, false, j.validity, nr, r->batch, r->words_per_batch, nw);
-        }
-        tzjobs.push_back(j);  // (behind the timestamp finishers: launched after the batch below)
-      }
-    } else {
-      rc = launch_finish_ext(ctx, fin, P, cp, co, r, S, d_scalars, d_nullc, d_chartot);
-      if (rc) return rc;
-    }
-  }
+  for (auto& cp : P.cols)
+    if (int rc = file_finishers(R, fin, tzjobs, cp)) return rc;
   if (fin.n_jobs) {
     // one upload of all job tables (pinned staging: the copy does not wait for the host), then one launch per stage and kernel
     const size_t bytes = fin.n_jobs * sizeof(MJob);
@@ -862,70 +932,93 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
                          (const SpaceJob*)(ds + o));
     HIP_TRY(ctx, hipGetLastError());
   }
-  const double ht_fin = hclock();
-  rc = launch_dict_rows(ctx, P, S, d_scalars, d_chartot);
+  R.ht.fin = host_us_now();
+  return ORCGPU_OK;
+}
+
+// The dictionary columns' rows and keys, what is left to do behind them, and the summary's way back to the host
+int launch_dictionaries_and_post(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  int rc = launch_dict_rows(R);
   if (rc) return rc;
-  rc = launch_dict_keys(ctx, P, S, d_scalars, d_chartot);
+  rc = launch_dict_keys(R);
   if (rc) return rc;
-  const double ht_dict = hclock();
-  rc = launch_post_ext(ctx, P, S, dsum, hs, SL, d_chartot);
+  R.ht.dict = host_us_now();
+  rc = launch_post_ext(R);
   if (rc) return rc;
-  HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)(SL.bytes / 8), false, 256, st, (const unsigned long long*)dsum, (unsigned long long*)hs,
-                      (uint64_t)(SL.bytes / 8)));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st));
-  ht_enq = hclock();
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  rc = settle_dict_places(ctx, P, S, dsum, hs, SL);
-  if (rc) return rc;
-  ht_sync = hclock();
-  if (host_prof) {
-    fprintf(stderr, "[orcgpu] lane %d host us: plan %.1f (columns %.1f, chunk tables %.1f, jobs %.1f)  first launch after %.1f  enqueue %.1f  wait %.1f\n", ctx->lane_id, ht_plan - ht0, ht_cols - ht0, ht_dp - ht_cols, ht_plan - ht_dp, ht_first - ht0, ht_enq - ht_plan, ht_sync - ht_enq);
-    fprintf(stderr, "[orcgpu] lane %d enqueue us: decompress %.1f  walk %.1f  present %.1f  expand %.1f  finishers %.1f  dictionary rows %.1f  post %.1f\n", ctx->lane_id,
-            ht_first - ht_plan, ht_walk - ht_first, ht_pres - ht_walk, ht_exp - ht_pres, ht_fin - ht_exp, ht_dict - ht_fin, ht_enq - ht_dict);
-  }
+  HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)(R.SL.bytes / 8), false, 256, R.st, (const unsigned long long*)R.dsum, (unsigned long long*)R.hs,
+                      (uint64_t)(R.SL.bytes / 8)));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev[3], R.st));
+  R.ht.enq = host_us_now();
+  return ORCGPU_OK;
+}
+
+int synchronise(LaneRun& R) {
+  HIP_TRY(R.ctx, hipStreamSynchronize(R.st));
+  int rc = settle_dict_places(R);
+  R.ht.sync = host_us_now();
+  return rc;
+}
+
+// The GPU's times between the call's events; this lane's launches and the bytes they worked for (orcgpu_last_lane_stats)
+void read_timings(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  const DecompPlan& DP = R.DP;
   (void)hipEventElapsedTime(&ctx->last_total_ms, ctx->ev[0], ctx->ev[3]);
   (void)hipEventElapsedTime(&ctx->last_expand_ms, ctx->ev[1], ctx->ev[2]);
-  {
-    static const int edge[6] = {0, 4, 5, 1, 2, 3};  // event index at the start of each phase (+ the end)
-    for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ctx->last_phase_ms[k], ctx->ev[edge[k]], ctx->ev[edge[k + 1]]);
-    (void)hipEventElapsedTime(&ctx->last_phase_ms[5], ctx->ev[0], ctx->ev[6]);
-    (void)hipEventElapsedTime(&ctx->last_phase_ms[6], ctx->ev[0], ctx->ev[7]);
-    {
-      // this lane's launches and the bytes they worked for (orcgpu_last_lane_stats)
-      orcgpu_lane_stats& ls = ctx->last_stats;
-      ls = orcgpu_lane_stats{};
-      ls.lane = (uint32_t)ctx->lane_id;
-      ls.n_lanes = 1;
-      for (uint32_t si = 0; si < n; si++)
-        for (size_t ci = 0; ci < stripes[si]->cols.size(); ci++) {
-          if (mask && !(*mask)[si][ci]) continue;
-          for (auto& sst : stripes[si]->streams)
-            if (sst.column_id == stripes[si]->cols[ci].column_id) ls.stream_bytes += sst.len;
-        }
-      ls.start_ms = (float)((ht_plan - (ctx->call_t0 > 0 ? ctx->call_t0 : ht0)) * 1e-3);  // (planning done: the launches follow)
-      ls.total_ms = ctx->last_total_ms;
-      for (int k = 0; k < ORCGPU_N_PHASES; k++) ls.phase_ms[k] = ctx->last_phase_ms[k];
-      if (DP.z_lanes && DP.n_zchains && DP.n_chunks) (void)hipEventElapsedTime(&ls.seq_kernel_ms, ctx->ev[9], ctx->ev[8]);
-      ls.exec_kernel_ms = ctx->last_phase_ms[0] - ctx->last_phase_ms[5];
-      if (ctx->lit_ev_used && hipEventSynchronize(ctx->lit_ev[1]) == hipSuccess) (void)hipEventElapsedTime(&ls.literals_kernel_ms, ctx->lit_ev[0], ctx->lit_ev[1]);
-      if (ctx->kev_used[0]) (void)hipEventElapsedTime(&ls.walk_short_kernel_ms, ctx->kev[0][0], ctx->kev[0][1]);
-      if (ctx->kev_used[1] && hipEventSynchronize(ctx->kev[1][1]) == hipSuccess) (void)hipEventElapsedTime(&ls.dict_emit_kernel_ms, ctx->kev[1][0], ctx->kev[1][1]);
+  static const int edge[6] = {0, 4, 5, 1, 2, 3};  // event index at the start of each phase (+ the end)
+  for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ctx->last_phase_ms[k], ctx->ev[edge[k]], ctx->ev[edge[k + 1]]);
+  (void)hipEventElapsedTime(&ctx->last_phase_ms[5], ctx->ev[0], ctx->ev[6]);
+  (void)hipEventElapsedTime(&ctx->last_phase_ms[6], ctx->ev[0], ctx->ev[7]);
+  orcgpu_lane_stats& ls = ctx->last_stats;
+  ls = orcgpu_lane_stats{};
+  ls.lane = (uint32_t)ctx->lane_id;
+  ls.n_lanes = 1;
+  for (uint32_t si = 0; si < R.n; si++)
+    for (size_t ci = 0; ci < R.stripes[si]->cols.size(); ci++) {
+      if (R.mask && !(*R.mask)[si][ci]) continue;
+      for (auto& sst : R.stripes[si]->streams)
+        if (sst.column_id == R.stripes[si]->cols[ci].column_id) ls.stream_bytes += sst.len;
     }
-    if (host_prof)
-      fprintf(stderr, "[orcgpu] lane %d GPU ms: decompress %.3f  walk %.3f  present %.3f  expand %.3f  finish %.3f  (total %.3f)\n", ctx->lane_id, ctx->last_phase_ms[0],
-              ctx->last_phase_ms[1], ctx->last_phase_ms[2], ctx->last_phase_ms[3], ctx->last_phase_ms[4], ctx->last_total_ms);
-  }
+  ls.start_ms = (float)((R.ht.plan - (ctx->call_t0 > 0 ? ctx->call_t0 : R.ht.t0)) * 1e-3);  // (planning done: the launches follow)
+  ls.total_ms = ctx->last_total_ms;
+  for (int k = 0; k < ORCGPU_N_PHASES; k++) ls.phase_ms[k] = ctx->last_phase_ms[k];
+  if (DP.z_lanes && DP.n_zchains && DP.n_chunks) (void)hipEventElapsedTime(&ls.seq_kernel_ms, ctx->ev[9], ctx->ev[8]);
+  ls.exec_kernel_ms = ctx->last_phase_ms[0] - ctx->last_phase_ms[5];
+  if (ctx->lit_ev_used && hipEventSynchronize(ctx->lit_ev[1]) == hipSuccess) (void)hipEventElapsedTime(&ls.literals_kernel_ms, ctx->lit_ev[0], ctx->lit_ev[1]);
+  if (ctx->kev_used[0]) (void)hipEventElapsedTime(&ls.walk_short_kernel_ms, ctx->kev[0][0], ctx->kev[0][1]);
+  if (ctx->kev_used[1] && hipEventSynchronize(ctx->kev[1][1]) == hipSuccess) (void)hipEventElapsedTime(&ls.dict_emit_kernel_ms, ctx->kev[1][0], ctx->kev[1][1]);
+}
 
-  {
-    bool want = false;
-    for (int k = 0; k < njobs && !want; k++) want = hjobs[k].bad_left >= 32u;  // RLE_EXACT_MIN (device/rle_scan.hip)
-    ctx->exact_on = want;
+// the exact parallel walk for the lane's next call: when a stream of this one is left damaged by the mending passes
+void note_exact_on(LaneRun& R) {
+  bool want = false;
+  for (int k = 0; k < R.njobs && !want; k++) want = R.hjobs[k].bad_left >= 32u;  // RLE_EXACT_MIN (device/rle_scan.hip)
+  R.ctx->exact_on = want;
+}
+
+// ORCGPU_DEBUG: the lane's host and GPU times, its jobs, the Zstandard plan, rejected chunks
+void debug_report(LaneRun& R) {
+  if (!R.host_prof) return;
+  orcgpu_ctx* const ctx = R.ctx;
+  const Plan& P = R.P;
+  const DecompPlan& DP = R.DP;
+  const SummaryLayout& SL = R.SL;
+  const LaneClock& ht = R.ht;
+  uint8_t* const S = R.S;
+  uint8_t* const hs = R.hs;
+  const RleJob* const hjobs = R.hjobs;
+  fprintf(stderr, "[orcgpu] lane %d host us: plan %.1f (columns %.1f, chunk tables %.1f, jobs %.1f)  first launch after %.1f  enqueue %.1f  wait %.1f\n", ctx->lane_id, ht.plan - ht.t0, ht.cols - ht.t0, ht.dp - ht.cols, ht.plan - ht.dp, ht.first - ht.t0, ht.enq - ht.plan, ht.sync - ht.enq);
+  fprintf(stderr, "[orcgpu] lane %d enqueue us: decompress %.1f  walk %.1f  present %.1f  expand %.1f  finishers %.1f  dictionary rows %.1f  post %.1f\n", ctx->lane_id,
+          ht.first - ht.plan, ht.walk - ht.first, ht.pres - ht.walk, ht.exp - ht.pres, ht.fin - ht.exp, ht.dict - ht.fin, ht.enq - ht.dict);
+  fprintf(stderr, "[orcgpu] lane %d GPU ms: decompress %.3f  walk %.3f  present %.3f  expand %.3f  finish %.3f  (total %.3f)\n", ctx->lane_id, ctx->last_phase_ms[0],
+          ctx->last_phase_ms[1], ctx->last_phase_ms[2], ctx->last_phase_ms[3], ctx->last_phase_ms[4], ctx->last_total_ms);
+  for (int k = 0; k < R.njobs; k++) {
+    const JobPlan& j = P.jobs[R.L.order[k]];
+    fprintf(stderr, "[orcgpu] job %d (stripe %d col %d role %d block0 %u nbits %d) codec %d blocks %u group %u: bad %u (first %u) repaired %u total %llu\n", k, j.stripe, j.col, j.role, hjobs[k].block0, (int)hjobs[k].nbits, hjobs[k].codec, hjobs[k].nblocks,
+            hjobs[k].group_size, hjobs[k].stat_bad, hjobs[k].first_bad, hjobs[k].stat_repaired, (unsigned long long)R.h_scalars()[hjobs[k].total_idx]);
   }
-  if (getenv("ORCGPU_DEBUG"))
-    for (int k = 0; k < njobs; k++)
-      fprintf(stderr, "[orcgpu] job %d (stripe %d col %d role %d block0 %u nbits %d) codec %d blocks %u group %u: bad %u (first %u) repaired %u total %llu\n", k, P.jobs[order[k]].stripe, P.jobs[order[k]].col, P.jobs[order[k]].role, hjobs[k].block0, (int)hjobs[k].nbits, hjobs[k].codec, hjobs[k].nblocks,
-              hjobs[k].group_size, hjobs[k].stat_bad, hjobs[k].first_bad, hjobs[k].stat_repaired, (unsigned long long)reinterpret_cast<const uint64_t*>(hs + SL.scalars_off)[hjobs[k].total_idx]);
-  if (getenv("ORCGPU_DEBUG") && DP.n_zitems) {
+  if (DP.n_zitems) {
     fprintf(stderr, "[orcgpu] zstd plan: %u blocks, %u with sequences (%llu in all): %s\n", DP.n_zblocks, DP.n_zchains, (unsigned long long)DP.z_total_seq,
             DP.z_lanes ? "one lane per block" : "one wavefront per block");
     // the chunks with the most sequences (what the entropy and execution stages last as long as), from the host's copy of the tables
@@ -950,7 +1043,7 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       fprintf(stderr, "[orcgpu] zstd chunk %u: %u blocks, %llu sequences (largest block %u), %u literal bytes\n", c, e - f, (unsigned long long)top[k].first, mxs, lit);
     }
   }
-  if (getenv("ORCGPU_DEBUG") && DP.n_chunks) {
+  if (DP.n_chunks) {
     // diagnostics: where rejected chunks / Zstandard blocks failed
     std::vector<uint8_t> tb(DP.table_bytes);
     (void)hipMemcpy(tb.data(), S + DP.dev_off, DP.table_bytes, hipMemcpyDeviceToHost);
@@ -980,7 +1073,7 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
       if (zs[k] | zs[DP.n_zblocks + k]) fprintf(stderr, "[orcgpu] zstd block %u (chunk %u, nseq %u, lit type %u regen %u): entropy stage code %u\n", k, zz[k].chunk, zz[k].nseq, zz[k].lit_type, zz[k].lit_regen, zs[k] ? zs[k] : zs[DP.n_zblocks + k]), shown++;
   }
 #ifdef ORC_PROF
-  if (getenv("ORCGPU_DEBUG")) {
+  {
     unsigned long long hp[176];
     hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_prof), sizeof(hp));
     static const struct { int base; const char* who; } sect[] = {{0, "walk"}, {48, "decompress"}, {80, "lz_exec"}, {112, "zstd_entropy"}};
@@ -995,170 +1088,202 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
     hipMemcpyToSymbol(HIP_SYMBOL(g_prof), hp, sizeof(hp));
   }
 #endif
-  // ---- chunks that need a larger slot ---------------------------------------------------------------------------
-  // flate2, lzokay and the zstd crate grow their output as needed (compression.rs:142-159, :174-183): a chunk may expand to more
-  // than the file's compression block size -- no conforming writer emits one, so every chunk gets a slot of the block size,
-  // and a chunk of those codecs that FAILED in it (whatever the reason: the decoders do not tell an overrun from other damage)
-  // gets the head-room the oracle gives the crates, max(block size, 4 MiB), and the call is run again.  A chunk that still
-  // fails is a decoder failure for the reference too.
-  {
-    bool codec_error = false;
-    const uint64_t* hsc = reinterpret_cast<const uint64_t*>(hs + SL.scalars_off);
-    for (auto& ds : P.decomp) codec_error = codec_error || hsc[ds.err_idx] != 0;
-    if (codec_error && DP.n_chunks) {
-      std::vector<ChunkDesc> hc(DP.n_chunks);
-      HIP_TRY(ctx, hipMemcpy(hc.data(), S + DP.dev_off + DP.chunks_off, (size_t)DP.n_chunks * sizeof(ChunkDesc), hipMemcpyDeviceToHost));
-      bool grown = false;
-      uint32_t ci = 0;
-      for (auto& ds : P.decomp) {
-        const int kind = ds.stripe->desc.compression;
-        const uint64_t limit = std::max<uint64_t>(ds.stripe->desc.block_size, 1u << 22);
-        bool grown_here = false;
-        for (auto& c : const_cast<StagedStream*>(ds.st)->chunks) {
-          const bool grows = kind == ORCGPU_COMP_ZLIB || kind == ORCGPU_COMP_LZO ||
-                             (kind == ORCGPU_COMP_ZSTD && c.zparse >= 0 && !ds.st->zchunks[c.zparse].size_known && !ds.st->zchunks[c.zparse].bad);
-          if (!c.original && grows && hc[ci].status && c.plain_cap < limit) {
-            c.plain_cap = (uint32_t)limit;
-            grown = grown_here = true;
-          }
-          ci++;
-        }
-        // (the slots are part of the stream's tables: built again for the second run)
-        if (grown_here) build_stream_tables(ds.st->chunks, ds.st->zchunks, kind, ds.st->off, ORC_E_CODEC, const_cast<StagedStream*>(ds.st)->tables);
+}
+
+// ---- chunks that need a larger slot ---------------------------------------------------------------------------
+// flate2, lzokay and the zstd crate grow their output as needed (compression.rs:142-159, :174-183): a chunk may expand to more
+// than the file's compression block size -- no conforming writer emits one, so every chunk gets a slot of the block size,
+// and a chunk of those codecs that FAILED in it (whatever the reason: the decoders do not tell an overrun from other damage)
+// gets the head-room the oracle gives the crates, max(block size, 4 MiB), and the call is run again.  A chunk that still
+// fails is a decoder failure for the reference too.
+int grow_failed_slots(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  Plan& P = R.P;
+  const DecompPlan& DP = R.DP;
+  bool codec_error = false;
+  const uint64_t* hsc = R.h_scalars();
+  for (auto& ds : P.decomp) codec_error = codec_error || hsc[ds.err_idx] != 0;
+  if (!codec_error || !DP.n_chunks) return ORCGPU_OK;
+  std::vector<ChunkDesc> hc(DP.n_chunks);
+  HIP_TRY(ctx, hipMemcpy(hc.data(), R.S + DP.dev_off + DP.chunks_off, (size_t)DP.n_chunks * sizeof(ChunkDesc), hipMemcpyDeviceToHost));
+  bool grown = false;
+  uint32_t ci = 0;
+  for (auto& ds : P.decomp) {
+    const int kind = ds.stripe->desc.compression;
+    const uint64_t limit = std::max<uint64_t>(ds.stripe->desc.block_size, 1u << 22);
+    bool grown_here = false;
+    for (auto& c : const_cast<StagedStream*>(ds.st)->chunks) {
+      const bool grows = kind == ORCGPU_COMP_ZLIB || kind == ORCGPU_COMP_LZO ||
+                         (kind == ORCGPU_COMP_ZSTD && c.zparse >= 0 && !ds.st->zchunks[c.zparse].size_known && !ds.st->zchunks[c.zparse].bad);
+      if (!c.original && grows && hc[ci].status && c.plain_cap < limit) {
+        c.plain_cap = (uint32_t)limit;
+        grown = grown_here = true;
       }
-      if (grown) return ORCGPU_RETRY_LARGER_SLOTS;
+      ci++;
+    }
+    // (the slots are part of the stream's tables: built again for the second run)
+    if (grown_here) build_stream_tables(ds.st->chunks, ds.st->zchunks, kind, ds.st->off, ORC_E_CODEC, const_cast<StagedStream*>(ds.st)->tables);
+  }
+  return grown ? ORCGPU_RETRY_LARGER_SLOTS : ORCGPU_OK;
+}
+
+// ---- resolve errors per column / stripe ----------------------------------------------------------------------
+void resolve_column(LaneRun& R, ColPlan& cp) {
+  Plan& P = R.P;
+  const RleJob* const hjobs = R.hjobs;
+  const uint64_t* h_scalars = R.h_scalars();
+  const unsigned long long* h_nullc = R.h_nullc();
+  if (cp.col < 0) return;  // (an arm of a Union)
+  orcgpu_result* r = P.results[cp.stripe];
+  ColumnOut& co = r->cols[cp.col];
+  for (uint32_t b = 0; b < r->n_batches; b++) co.null_counts[b] = cp.has_present || cp.tz ? h_nullc[cp.nullcount_off + b] : 0;
+  // non-null prefix per batch -> map a dense value index to its batch
+  auto batch_of_dense = [&](uint64_t d) -> uint32_t {
+    uint64_t acc = 0;
+    for (uint32_t b = 0; b < r->n_batches; b++) {
+      uint64_t rows = std::min<uint64_t>(r->batch, r->n_rows - (uint64_t)b * r->batch);
+      acc += rows - co.null_counts[b];
+      if (d < acc) return b;
+    }
+    return r->n_batches ? r->n_batches - 1 : 0;
+  };
+  int best_status = 0;
+  uint32_t best_batch = 0xffffffffu;
+  // the stream the error under consideration stems from, and whether the winning error means "stream ran dry"
+  const PlainStream* cur_src = nullptr;
+  const PlainStream* best_src = nullptr;
+  bool best_eof = false;
+  auto consider = [&](int code, uint32_t batch) {
+    if (code && batch < best_batch) {
+      best_batch = batch;
+      best_status = code & ~(int)ORC_E_EOF;
+      best_eof = (code & (int)ORC_E_EOF) || best_status == (int)ORC_E_IO;
+      best_src = cur_src;
+    }
+  };
+  // decode order inside a batch: PRESENT, DATA, LENGTH, SECONDARY, then the finisher
+  int jl[4] = {cp.job_present, cp.job_data, cp.job_length, cp.job_secondary};
+  // Errors of the same batch: the one the reference meets first wins.  Decimals read the DATA varints
+  // before the SECONDARY scales (array_decoder/decimal.rs:131-132), and their DATA errors arrive
+  // through the column's own error word.
+  unsigned long long fe = h_scalars[cp.err_idx];
+  auto consider_fe = [&] {
+    if (fe == RLE_NO_ERR) return;
+    // Float / Double: the index counts the values the stream holds (dense, i.e. non-null rows): the batch
+    // that needs the first missing one fails.  Everything else reports a row.
+    const bool dense_index = cp.c.orc_type == ORCGPU_T_FLOAT || cp.c.orc_type == ORCGPU_T_DOUBLE || cp.c.orc_type == ORCGPU_T_UNION;
+    cur_src = &cp.data;
+    const uint32_t b = dense_index ? batch_of_dense(fe >> 8) : (uint32_t)std::min<uint64_t>(r->n_batches ? r->n_batches - 1 : 0, (fe >> 8) / r->batch);
+    consider((int)(fe & 0xff), b);
+  };
+  const PlainStream* ext_src = cp.is_dict ? &cp.dict : &cp.data;  // dictionary blob / direct values / decimal varints
+  const PlainStream* job_src[4] = {&cp.present, &cp.data, &cp.length, &cp.secondary};
+  auto consider_job = [&](int k) {
+    if (jl[k] < 0) return;
+    unsigned long long e = hjobs[P.jobs[jl[k]].final_index].err;
+    if (e == RLE_NO_ERR) return;
+    uint64_t idx = e >> 8;
+    const uint64_t lead = P.jobs[jl[k]].skip_values;  // (values in front of an entry point: a failure there is the first row's)
+    idx = idx > lead ? idx - lead : 0;
+    int code = (int)(hjobs[P.jobs[jl[k]].final_index].err_pos & 0xff);  // kind: the failure first in the stream (rle_expand.hip: report)
+    if (k == 1 && cp.c.orc_type == ORCGPU_T_BOOLEAN) idx *= 8;  // the job counts bytes, the column's dense values are bits
+    cur_src = job_src[k];
+    consider(code, resolve_job_batch(cp, k, idx, batch_of_dense));
+  };
+  auto consider_ext = [&] {
+    cur_src = ext_src;
+    resolve_ext(R, cp, co, r, consider);
+  };
+  // (k = 0, PRESENT: a decode error there is swallowed like the reference does -- present_words_kernel)
+  if (cp.c.orc_type == ORCGPU_T_DECIMAL) {
+    consider_ext();  // varint (DATA) errors
+    consider_fe();
+    for (int k = 1; k < 4; k++) consider_job(k);
+  } else if (cp.is_dict) {
+    // the dictionary is built when the column's decoder is (string.rs:65-82): its LENGTH stream, then its bytes,
+    // fail before any batch does; then per batch the keys (DATA) and their range
+    consider_job(2);
+    consider_ext();
+    consider_job(1);
+    consider_fe();
+  } else {
+    for (int k = 1; k < 4; k++) consider_job(k);
+    consider_fe();
+    consider_ext();
+  }
+  // A stream cut short by its container makes the decoder run dry: that failure is reported as the container's
+  // own error -- a chunk the block decoder rejected -> Build*Decoder (error.rs), broken chunk framing -> IoError
+  // (the reader's sticky status in the oracle; the reference panics in both cases).  Errors met before the
+  // cut keep their kind.
+  if (best_status && best_eof && best_src && best_src->exists && best_src->err_idx) {
+    const uint64_t ce = h_scalars[best_src->err_idx];
+    if (ce == ORC_E_CODEC) best_status = ORCGPU_BUILD_DECODER;
+    else if (ce == ORC_E_IO) best_status = ORCGPU_IO_ERROR;
+  }
+  co.status = best_status;
+  co.err_batch = best_status ? best_batch : 0;
+  // array_decoder/decimal.rs:96-100: every batch of a Decimal column goes through with_precision_and_scale, which is an ArrowError
+  // for a precision outside 1 ..= 38, a scale above 38 or above the precision (the reference takes the footer's numbers `as u8` /
+  // `as i8`, decimal.rs:59-60): a column of such a type fails at its first batch, behind whatever its streams fail at there.
+  if (cp.c.orc_type == ORCGPU_T_DECIMAL && cp.n_rows && r->n_batches) {
+    const uint32_t pr = cp.c.precision & 0xffu;
+    const int sc = (int8_t)cp.c.scale;
+    if ((pr == 0 || pr > 38 || sc > 38 || (sc > 0 && (uint32_t)sc > pr)) && (!co.status || co.err_batch > 0)) {
+      co.status = ORCGPU_ARROW;
+      co.err_batch = 0;
     }
   }
-  // ---- resolve errors per column / stripe ----------------------------------------------------------------------
-  const uint64_t* h_scalars = reinterpret_cast<const uint64_t*>(hs + SL.scalars_off);
-  const unsigned long long* h_nullc = reinterpret_cast<const unsigned long long*>(hs + SL.nullc_off);
-  const unsigned long long* h_chartot = reinterpret_cast<const unsigned long long*>(hs + SL.chartot_off);
-  for (auto& cp : P.cols) {
-    if (cp.col < 0) continue;  // (an arm of a Union)
-    orcgpu_result* r = P.results[cp.stripe];
-    ColumnOut& co = r->cols[cp.col];
-    for (uint32_t b = 0; b < r->n_batches; b++) co.null_counts[b] = cp.has_present || cp.tz ? h_nullc[cp.nullcount_off + b] : 0;
-    // non-null prefix per batch -> map a dense value index to its batch
-    auto batch_of_dense = [&](uint64_t d) -> uint32_t {
-      uint64_t acc = 0;
-      for (uint32_t b = 0; b < r->n_batches; b++) {
-        uint64_t rows = std::min<uint64_t>(r->batch, r->n_rows - (uint64_t)b * r->batch);
-        acc += rows - co.null_counts[b];
-        if (d < acc) return b;
-      }
-      return r->n_batches ? r->n_batches - 1 : 0;
-    };
-    int best_status = 0;
-    uint32_t best_batch = 0xffffffffu;
-    // the stream the error under consideration stems from, and whether the winning error means "stream ran dry"
-    const PlainStream* cur_src = nullptr;
-    const PlainStream* best_src = nullptr;
-    bool best_eof = false;
-    auto consider = [&](int code, uint32_t batch) {
-      if (code && batch < best_batch) {
-        best_batch = batch;
-        best_status = code & ~(int)ORC_E_EOF;
-        best_eof = (code & (int)ORC_E_EOF) || best_status == (int)ORC_E_IO;
-        best_src = cur_src;
-      }
-    };
-    // decode order inside a batch: PRESENT, DATA, LENGTH, SECONDARY, then the finisher
-    int jl[4] = {cp.job_present, cp.job_data, cp.job_length, cp.job_secondary};
-    // Errors of the same batch: the one the reference meets first wins.  Decimals read the DATA varints
-    // before the SECONDARY scales (array_decoder/decimal.rs:131-132), and their DATA errors arrive
-    // through the column's own error word.
-    unsigned long long fe = h_scalars[cp.err_idx];
-    auto consider_fe = [&] {
-      if (fe == RLE_NO_ERR) return;
-      // Float / Double: the index counts the values the stream holds (dense, i.e. non-null rows): the batch
-      // that needs the first missing one fails.  Everything else reports a row.
-      const bool dense_index = cp.c.orc_type == ORCGPU_T_FLOAT || cp.c.orc_type == ORCGPU_T_DOUBLE || cp.c.orc_type == ORCGPU_T_UNION;
-      cur_src = &cp.data;
-      const uint32_t b = dense_index ? batch_of_dense(fe >> 8) : (uint32_t)std::min<uint64_t>(r->n_batches ? r->n_batches - 1 : 0, (fe >> 8) / r->batch);
-      consider((int)(fe & 0xff), b);
-    };
-    const PlainStream* ext_src = cp.is_dict ? &cp.dict : &cp.data;  // dictionary blob / direct values / decimal varints
-    const PlainStream* job_src[4] = {&cp.present, &cp.data, &cp.length, &cp.secondary};
-    auto consider_job = [&](int k) {
-      if (jl[k] < 0) return;
-      unsigned long long e = hjobs[P.jobs[jl[k]].final_index].err;
-      if (e == RLE_NO_ERR) return;
-      uint64_t idx = e >> 8;
-      const uint64_t lead = P.jobs[jl[k]].skip_values;  // (values in front of an entry point: a failure there is the first row's)
-      idx = idx > lead ? idx - lead : 0;
-      int code = (int)(hjobs[P.jobs[jl[k]].final_index].err_pos & 0xff);  // kind: the failure first in the stream (rle_expand.hip: report)
-      if (k == 1 && cp.c.orc_type == ORCGPU_T_BOOLEAN) idx *= 8;  // the job counts bytes, the column's dense values are bits
-      cur_src = job_src[k];
-      consider(code, resolve_job_batch(P, cp, co, r, k, idx, batch_of_dense));
-    };
-    auto consider_ext = [&] {
-      cur_src = ext_src;
-      resolve_ext(P, cp, co, r, h_scalars, h_chartot, consider);
-    };
-    // (k = 0, PRESENT: a decode error there is swallowed like the reference does -- present_words_kernel)
-    if (cp.c.orc_type == ORCGPU_T_DECIMAL) {
-      consider_ext();  // varint (DATA) errors
-      consider_fe();
-      for (int k = 1; k < 4; k++) consider_job(k);
-    } else if (cp.is_dict) {
-      // the dictionary is built when the column's decoder is (string.rs:65-82): its LENGTH stream, then its bytes,
-      // fail before any batch does; then per batch the keys (DATA) and their range
-      consider_job(2);
-      consider_ext();
-      consider_job(1);
-      consider_fe();
-    } else {
-      for (int k = 1; k < 4; k++) consider_job(k);
-      consider_fe();
-      consider_ext();
-    }
-    // A stream cut short by its container makes the decoder run dry: that failure is reported as the container's
-    // own error -- a chunk the block decoder rejected -> Build*Decoder (error.rs), broken chunk framing -> IoError
-    // (the reader's sticky status in the oracle; the reference panics in both cases).  Errors met before the
-    // cut keep their kind.
-    if (best_status && best_eof && best_src && best_src->exists && best_src->err_idx) {
-      const uint64_t ce = h_scalars[best_src->err_idx];
-      if (ce == ORC_E_CODEC) best_status = ORCGPU_BUILD_DECODER;
-      else if (ce == ORC_E_IO) best_status = ORCGPU_IO_ERROR;
-    }
-    co.status = best_status;
-    co.err_batch = best_status ? best_batch : 0;
-    // array_decoder/decimal.rs:96-100: every batch of a Decimal column goes through with_precision_and_scale, which is an ArrowError
-    // for a precision outside 1 ..= 38, a scale above 38 or above the precision (the reference takes the footer's numbers `as u8` /
-    // `as i8`, decimal.rs:59-60): a column of such a type fails at its first batch, behind whatever its streams fail at there.
-    if (cp.c.orc_type == ORCGPU_T_DECIMAL && cp.n_rows && r->n_batches) {
-      const uint32_t pr = cp.c.precision & 0xffu;
-      const int sc = (int8_t)cp.c.scale;
-      if ((pr == 0 || pr > 38 || sc > 38 || (sc > 0 && (uint32_t)sc > pr)) && (!co.status || co.err_batch > 0)) {
-        co.status = ORCGPU_ARROW;
-        co.err_batch = 0;
-      }
-    }
-  }
-  if (host_prof) fprintf(stderr, "[orcgpu] lane %d host us: post %.1f  (call total %.1f)\n", ctx->lane_id, hclock() - ht_sync, hclock() - ht0);
-  {
-    // the lane's host time, part by part (orcgpu_last_lane_host_us)
-    const double parts[ORCGPU_N_HOST_PARTS] = {ctx->call_t0 > 0 ? ht0 - ctx->call_t0 : 0.0, ht_cols - ht0, ht_dp - ht_cols, ht_plan - ht_dp, ctx->hp_fill, ctx->hp_upload + (ht_launch - ht_plan),
-                                               ctx->hp_gate, (ht_first - ht_launch) - ctx->hp_fill - ctx->hp_upload - ctx->hp_gate, ht_enq - ht_first, ht_sync - ht_enq, hclock() - ht_sync};
-    for (int k = 0; k < ORCGPU_N_HOST_PARTS; k++) ctx->last_host_us[k] = (float)parts[k];
-  }
+}
+
+// the lane's host time, part by part (orcgpu_last_lane_host_us)
+void note_host_parts(LaneRun& R) {
+  orcgpu_ctx* const ctx = R.ctx;
+  const LaneClock& t = R.ht;
+  if (R.host_prof) fprintf(stderr, "[orcgpu] lane %d host us: post %.1f  (call total %.1f)\n", ctx->lane_id, host_us_now() - t.sync, host_us_now() - t.t0);
+  const double parts[ORCGPU_N_HOST_PARTS] = {ctx->call_t0 > 0 ? t.t0 - ctx->call_t0 : 0.0, t.cols - t.t0, t.dp - t.cols, t.plan - t.dp, ctx->hp_fill, ctx->hp_upload + (t.launch - t.plan),
+                                             ctx->hp_gate, (t.first - t.launch) - ctx->hp_fill - ctx->hp_upload - ctx->hp_gate, t.enq - t.first, t.sync - t.enq, host_us_now() - t.sync};
+  for (int k = 0; k < ORCGPU_N_HOST_PARTS; k++) ctx->last_host_us[k] = (float)parts[k];
+}
+
+}  // namespace
+
+// One lane's share of a decode call: the columns `mask` selects (all when null), on the lane's own stream and workspace.
+// The results have been created / reset by orcgpu_decode_staged; this fills their selected columns.
+static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results, const std::vector<std::vector<uint8_t>>* mask) {
+  LaneRun R{ctx, ctx->stream, stripes, n, results, mask, getenv("ORCGPU_DEBUG") != nullptr};
+  R.ht.t0 = host_us_now();
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ORCGPU_OK;
+  for (auto step : {plan_columns, plan_chunk_tables, lay_out_jobs, reserve_workspace})
+    if ((rc = step(R))) return rc;
+  fill_summary_mirror(R);
+  for (auto step : {launch_decompression, launch_walk, launch_present, launch_expansion, launch_finishers, launch_dictionaries_and_post, synchronise})
+    if ((rc = step(R))) return rc;
+  read_timings(R);
+  note_exact_on(R);
+  debug_report(R);
+  if ((rc = grow_failed_slots(R))) return rc;
+  for (auto& cp : R.P.cols) resolve_column(R, cp);
+  note_host_parts(R);
   return ORCGPU_OK;
 }
 
 static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results);
 
-extern "C" int orcgpu_decode_staged(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
-  if (!ctx || !stripes || !results || !n) return ORCGPU_INVALID_ARGUMENT;
-  // (a second run only when chunks turned out to need larger slots than the compression block size: see decode_lane)
+// (a second run only when chunks turned out to need larger slots than the compression block size: see grow_failed_slots)
+static int decode_staged_retrying(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
   int rc = decode_staged_once(ctx, stripes, n, results);
   if (rc == ORCGPU_RETRY_LARGER_SLOTS) rc = decode_staged_once(ctx, stripes, n, results);
   return rc == ORCGPU_RETRY_LARGER_SLOTS ? ORCGPU_UNEXPECTED : rc;
 }
 
-static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
-  const double call_t0 = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // ---- results: created or reset here, filled column by column by the lanes ------------------------------------------
+extern "C" int orcgpu_decode_staged(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
+  if (!ctx || !stripes || !results || !n) return ORCGPU_INVALID_ARGUMENT;
+  return decode_staged_retrying(ctx, stripes, n, results);
+}
+
+// ---- results: created or reset here, filled column by column by the lanes ------------------------------------------
+static int reset_results(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
   for (uint32_t si = 0; si < n; si++) {
     orcgpu_staged* s = stripes[si];
     if (!s || s->ctx != ctx) return ORCGPU_INVALID_ARGUMENT;
@@ -1206,11 +1331,16 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     r->filt_used = 0;
     for (int l = 0; l < kMaxLanes; l++) r->arena_used[l] = r->chars_used[l] = 0;
   }
-  // ---- lanes: whole columns, balanced by their staged bytes (longest first); a column that alone is a quarter of the
-  // call gets a lane to itself (its decompression is a serial chain per block: what runs beside it is free) -------------
-  // ORCGPU_LANES = 1..4 forces the count.  Unset: two lanes for calls that are big enough and whose Zstandard blocks differ enough
-  // for the heavy / light split below to pay (lineitem SF1: 10.9 -> 10.1 ms); otherwise one -- lanes with equally long
-  // decompression phases have nothing to overlap, and every extra stream slows the short kernels of the others.
+  return ORCGPU_OK;
+}
+
+// ---- lanes: whole columns, balanced by their staged bytes (longest first); a column that alone is a quarter of the
+// call gets a lane to itself (its decompression is a serial chain per block: what runs beside it is free) -------------
+// ORCGPU_LANES = 1..4 forces the count.  Unset: two lanes for calls that are big enough and whose Zstandard blocks differ enough
+// for the heavy / light split below to pay (lineitem SF1: 10.9 -> 10.1 ms); otherwise one -- lanes with equally long
+// decompression phases have nothing to overlap, and every extra stream slows the short kernels of the others.
+// Returns the number of lanes and, for more than one, the columns of each per stripe (`masks`) and the call's Zstandard path.
+static int choose_lanes(orcgpu_staged* const* stripes, uint32_t n, std::vector<std::vector<std::vector<uint8_t>>>& masks, int& call_z) {
   const int forced_lanes = [] {  // (read at every call: the tests run the same stripes through every lane count)
     const char* e = getenv("ORCGPU_LANES");
     int v = e ? atoi(e) : 0;
@@ -1230,188 +1360,104 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
     if (staged >= (64ull << 20) && mx_all >= 16384) want_lanes = 2;
   }
   int n_lanes = (int)std::min<size_t>((size_t)want_lanes, max_cols);
-  const bool auto_lanes = !forced_lanes && n_lanes > 1;
-  std::vector<std::vector<std::vector<uint8_t>>> masks;
-  int call_z = -1;  // the call's Zstandard path, decided below when the call is split over lanes
-  // (a Struct and its fields stay on one lane: the fields' validity is built from the Struct's.  Columns are keyed by the id
-  // of the root column above them.)
-  auto root_id = [&](uint32_t si, uint32_t column_id) -> uint32_t {
+  if (n_lanes <= 1) return n_lanes;
+  // the weight of a root column = staged bytes of the streams of its columns over all stripes of the call; one pass per stripe,
+  // through the stripe's columns by id (the first of that id counts, as many times as the id is given) and their roots
+  std::vector<LaneRoot> roots;
+  std::map<uint32_t, uint32_t> root_at;                   // root column id -> index in `roots`
+  std::vector<std::vector<uint32_t>> root_of(n);          // [stripe][column] -> index in `roots`
+  std::vector<std::pair<uint32_t, uint32_t>> stray;       // (column id, longest block) of streams of no column of their stripe
+  uint64_t seq_all = 0;
+  for (uint32_t si = 0; si < n; si++) {
     const auto& cols = stripes[si]->cols;
-    size_t k = 0;
-    for (; k < cols.size(); k++)
-      if (cols[k].column_id == column_id) break;
-    if (k == cols.size()) return column_id;
-    while (cols[k].parent && cols[k].parent <= k) k = cols[k].parent - 1;
-    return cols[k].column_id;
-  };
-  if (n_lanes > 1) {
-    // weight of a column id = staged bytes of its streams over all stripes of the call
-    std::vector<std::pair<uint64_t, uint32_t>> w;  // (bytes, column id)
-    uint64_t total = 0;
-    for (uint32_t si = 0; si < n; si++)
-      for (auto& c : stripes[si]->cols) {
-        uint64_t b = 0;
-        for (auto& st : stripes[si]->streams)
-          if (st.column_id == c.column_id) b += st.len;
-        const uint32_t rid = root_id(si, c.column_id);
-        size_t k = 0;
-        for (; k < w.size(); k++)
-          if (w[k].second == rid) break;
-        if (k == w.size()) w.push_back({0, rid});
-        w[k].first += b;
-        total += b;
-      }
-    std::sort(w.begin(), w.end(), [](auto& a, auto& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
-    std::vector<uint64_t> load(n_lanes, 0);
-    std::vector<int> lane_of(w.size(), 0);
-    std::vector<bool> closed(n_lanes, false);
-    for (size_t k = 0; k < w.size(); k++) {
-      int best = -1;
-      for (int l = 0; l < n_lanes; l++)
-        if (!closed[l] && (best < 0 || load[l] < load[best])) best = l;
-      if (best < 0) best = 0;
-      lane_of[k] = best;
-      load[best] += w[k].first;
-      if (k == 0 && w.size() > 1 && w[0].first * 4 >= total && n_lanes > 1) closed[best] = true;
+    std::map<uint32_t, std::pair<uint32_t, uint32_t>> by_id;  // column id -> (first column of that id, columns of that id)
+    for (size_t ci = 0; ci < cols.size(); ci++) by_id.insert({cols[ci].column_id, {(uint32_t)ci, 0u}}).first->second.second++;
+    root_of[si].resize(cols.size());
+    for (size_t ci = 0; ci < cols.size(); ci++) {
+      size_t k = by_id[cols[ci].column_id].first;
+      while (cols[k].parent && cols[k].parent <= k) k = cols[k].parent - 1;
+      const auto at = root_at.insert({cols[k].column_id, (uint32_t)roots.size()});
+      if (at.second) roots.push_back(LaneRoot{cols[k].column_id, 0, 0});
+      root_of[si][ci] = at.first->second;
     }
-    // Zstandard: the entropy stage lasts as long as its longest block (a serial FSE chain, ~150 ns per sequence).  Columns whose
-    // blocks come near the longest one of the call share lane 0; everything else -- its own entropy stage is short -- goes through
-    // its whole pipeline on the other lanes meanwhile.
-    {
-      std::vector<uint32_t> mx(w.size(), 0);
-      uint32_t mxmax = 0;
-      for (uint32_t si = 0; si < n; si++)
-        for (auto& st : stripes[si]->streams) {
-          const uint32_t rid = root_id(si, st.column_id);
-          size_t k = 0;
-          for (; k < w.size(); k++)
-            if (w[k].second == rid) break;
-          if (k == w.size()) continue;
-          mx[k] = std::max(mx[k], st.tables.max_nseq);
-          mxmax = std::max(mxmax, mx[k]);
-        }
-      uint64_t seq_all = 0;
-      for (uint32_t si = 0; si < n; si++)
-        for (auto& st : stripes[si]->streams) seq_all += st.tables.total_seq;
-      const uint64_t lanes_min = kZstdLanesMinSequences;
-      // (one decision for the call: a lane whose own columns hold fewer sequences than the threshold took the other path -- SF 3: 32 against 22 ms)
-      call_z = seq_all >= lanes_min ? 1 : 0;
-      if (mxmax >= 4096 && n_lanes == 2 && seq_all >= lanes_min) {
-        // Table scale (the sequences go one lane per block, zstd_lanes.h): that kernel lasts as long as the call's longest chains and
-        // leaves most of the machine idle meanwhile.  The columns with the longest chains share lane 0, the others are dealt out by
-        // their staged bytes (largest first) -- lane 0 starting with a handicap for the wait -- so that the other lane's execution,
-        // walk and finishing kernels run beside it and both lanes end together (SF 12.5: 69.8 -> 66.9 ms; the handicap a fifth of the staged bytes since the decimal finisher takes 4 ms instead of 7.4: 51.4 -> 48.4 ms).
-        std::vector<uint64_t> lload(n_lanes, 0);
-        // per mille of the staged bytes.  (Round 6, twice in its first half: 0 .. 600 measured, 35.1 - 36.2 ms at every setting, no trend;
-        // again at the round's last kernels -- the finishers of lane 0's Decimal columns 1.5 ms shorter --: 0 -> 33.1, 33.1; 200 -> 33.7, 33.9;
-        // 300 -> 33.3, 33.5; 500 -> 33.6, 33.6; 700 -> 33.7, 34.1 ms: no head start any more)
-        const uint64_t handicap = 0;
-        lload[0] = total * handicap / 1000;
-        for (size_t k = 0; k < w.size(); k++)
-          if (mx[k] * 5ull >= mxmax * 3ull) {
-            lane_of[k] = 0;
-            lload[0] += w[k].first;
-          }
-        for (size_t k = 0; k < w.size(); k++)
-          if (mx[k] * 5ull < mxmax * 3ull) {
-            const int best = lload[1] < lload[0] ? 1 : 0;
-            lane_of[k] = best;
-            lload[best] += w[k].first;
-          }
-      } else if (mxmax >= 4096) {
-        std::vector<uint64_t> lload(n_lanes, 0);
-        size_t heavy = 0;
-        for (size_t k = 0; k < w.size(); k++) heavy += mx[k] * 2ull >= mxmax;
-        if (heavy == w.size() && auto_lanes) n_lanes = 1;  // nothing light to run beside the heavy columns
-        if (heavy < w.size())
-          for (size_t k = 0; k < w.size(); k++) {
-            if (mx[k] * 2ull >= mxmax) {
-              lane_of[k] = 0;
-            } else {
-              int best = 1;
-              for (int l = 2; l < n_lanes; l++)
-                if (lload[l] < lload[best]) best = l;
-              lane_of[k] = best;
-              lload[best] += w[k].first;
-            }
-          }
+    for (auto& st : stripes[si]->streams) {
+      seq_all += st.tables.total_seq;
+      const auto c = by_id.find(st.column_id);
+      if (c == by_id.end()) {
+        stray.push_back({st.column_id, st.tables.max_nseq});
+        continue;
       }
-    }
-    masks.assign(n_lanes, {});
-    for (int l = 0; l < n_lanes; l++) {
-      masks[l].resize(n);
-      for (uint32_t si = 0; si < n; si++) {
-        masks[l][si].assign(stripes[si]->cols.size(), 0);
-        for (size_t ci = 0; ci < stripes[si]->cols.size(); ci++) {
-          const uint32_t rid = root_id(si, stripes[si]->cols[ci].column_id);
-          size_t k = 0;
-          for (; k < w.size(); k++)
-            if (w[k].second == rid) break;
-          masks[l][si][ci] = lane_of[k] == l;
-        }
-      }
-    }
-    // lanes that got nothing are dropped
-    for (int l = n_lanes - 1; l >= 1; l--) {
-      bool any = false;
-      for (auto& m : masks[l])
-        for (auto v : m) any |= v != 0;
-      if (!any && l == n_lanes - 1) n_lanes--;
+      LaneRoot& root = roots[root_of[si][c->second.first]];
+      root.bytes += st.len * c->second.second;
+      root.max_nseq = std::max(root.max_nseq, st.tables.max_nseq);
     }
   }
+  for (auto& s : stray) {
+    const auto at = root_at.find(s.first);
+    if (at != root_at.end()) roots[at->second].max_nseq = std::max(roots[at->second].max_nseq, s.second);
+  }
+  const LaneDeal D = deal_lanes(roots, seq_all, n_lanes, forced_lanes != 0);
+  call_z = D.call_z;
+  masks.assign(D.n_lanes, {});
+  for (int l = 0; l < D.n_lanes; l++) {
+    masks[l].resize(n);
+    for (uint32_t si = 0; si < n; si++) {
+      masks[l][si].resize(root_of[si].size());
+      for (size_t ci = 0; ci < root_of[si].size(); ci++) masks[l][si][ci] = D.lane_of[root_of[si][ci]] == l;
+    }
+  }
+  return D.n_lanes;
+}
+
+// The lanes beside the caller's own are opened when first needed; every lane decodes its columns on a thread of its own
+static int run_lanes(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results, const std::vector<std::vector<std::vector<uint8_t>>>& masks, int n_lanes) {
+  if (n_lanes <= 1) return decode_lane(ctx, stripes, n, results, nullptr);
   int rc = ORCGPU_OK;
-  ctx->call_t0 = call_t0;
-  ctx->call_z_lanes = n_lanes > 1 ? call_z : -1;
-  ctx->n_gate_peers = 0;
-  ctx->tables_gate.store(0);
-  const double t_pre = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if (n_lanes <= 1) {
-    rc = decode_lane(ctx, stripes, n, results, nullptr);
-  } else {
-    for (int l = 1; l < n_lanes; l++)
-      if (!ctx->lanes[l]) {
-        orcgpu_ctx* c = open_ctx(ctx->device, nullptr, l);
-        if (!c) {
-          set_err(ctx, "could not create lane %d", l);
-          return ORCGPU_HIP_ERROR;
-        }
-        c->lane_id = l;
-        ctx->lanes[l] = c;
+  const double call_t0 = ctx->call_t0;
+  for (int l = 1; l < n_lanes; l++)
+    if (!ctx->lanes[l]) {
+      orcgpu_ctx* c = open_ctx(ctx->device, nullptr, l);
+      if (!c) {
+        set_err(ctx, "could not create lane %d", l);
+        return ORCGPU_HIP_ERROR;
       }
-    for (int l = 1; l < n_lanes; l++) ctx->lanes[l]->call_t0 = call_t0;
-    for (int l = 1; l < n_lanes; l++) ctx->lanes[l]->call_z_lanes = ctx->call_z_lanes;
-    constexpr bool tables_first = true;
-    for (int l = 0; l < n_lanes; l++) {
-      orcgpu_ctx* c = ctx->lanes[l];
-      c->tables_gate.store(0);
-      c->n_gate_peers = 0;
-      for (int o = 0; o < n_lanes && tables_first; o++)
-        if (o != l) c->gate_peers[c->n_gate_peers++] = ctx->lanes[o];
+      c->lane_id = l;
+      ctx->lanes[l] = c;
     }
-    std::vector<int> rcs(n_lanes, 0);
-    std::vector<std::thread> th;
-    for (int l = 1; l < n_lanes; l++) th.emplace_back([&, l] { rcs[l] = decode_lane(ctx->lanes[l], stripes, n, results, &masks[l]); });
-    rcs[0] = decode_lane(ctx, stripes, n, results, &masks[0]);
-    for (auto& t : th) t.join();
-    int slow = 0;
-    for (int l = 0; l < n_lanes; l++) {
-      if (rcs[l] && !rc) {
-        rc = rcs[l];
-        if (l) ctx->err = ctx->lanes[l]->err;
-      }
-      if (ctx->lanes[l]->last_total_ms > ctx->lanes[slow]->last_total_ms) slow = l;
-    }
-    if (slow) {  // timing hooks report the lane that took longest
-      orcgpu_ctx* c = ctx->lanes[slow];
-      ctx->last_total_ms = c->last_total_ms;
-      ctx->last_expand_ms = c->last_expand_ms;
-      ctx->last_expand_launches = c->last_expand_launches;
-      for (int k = 0; k < ORCGPU_N_PHASES; k++) ctx->last_phase_ms[k] = c->last_phase_ms[k];
-    }
+  for (int l = 1; l < n_lanes; l++) ctx->lanes[l]->call_t0 = call_t0;
+  for (int l = 1; l < n_lanes; l++) ctx->lanes[l]->call_z_lanes = ctx->call_z_lanes;
+  for (int l = 0; l < n_lanes; l++) {
+    orcgpu_ctx* c = ctx->lanes[l];
+    c->tables_gate.store(0);
+    c->n_gate_peers = 0;
+    for (int o = 0; o < n_lanes; o++)
+      if (o != l) c->gate_peers[c->n_gate_peers++] = ctx->lanes[o];
   }
-  const double t_lanes = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if (getenv("ORCGPU_DEBUG")) fprintf(stderr, "[orcgpu] call host us: before the lanes %.1f, lanes %.1f\n", t_pre - call_t0, t_lanes - t_pre);
-  if (rc) return rc;
+  std::vector<int> rcs(n_lanes, 0);
+  std::vector<std::thread> th;
+  for (int l = 1; l < n_lanes; l++) th.emplace_back([&, l] { rcs[l] = decode_lane(ctx->lanes[l], stripes, n, results, &masks[l]); });
+  rcs[0] = decode_lane(ctx, stripes, n, results, &masks[0]);
+  for (auto& t : th) t.join();
+  int slow = 0;
+  for (int l = 0; l < n_lanes; l++) {
+    if (rcs[l] && !rc) {
+      rc = rcs[l];
+      if (l) ctx->err = ctx->lanes[l]->err;
+    }
+    if (ctx->lanes[l]->last_total_ms > ctx->lanes[slow]->last_total_ms) slow = l;
+  }
+  if (slow) {  // timing hooks report the lane that took longest
+    orcgpu_ctx* c = ctx->lanes[slow];
+    ctx->last_total_ms = c->last_total_ms;
+    ctx->last_expand_ms = c->last_expand_ms;
+    ctx->last_expand_launches = c->last_expand_launches;
+    for (int k = 0; k < ORCGPU_N_PHASES; k++) ctx->last_phase_ms[k] = c->last_phase_ms[k];
+  }
+  return rc;
+}
+
+// The stripes' status (the failing column of the earliest failing batch) and the Arrow bytes decoded, per result and per lane
+static void sum_up_results(orcgpu_ctx* ctx, uint32_t n, orcgpu_result** results, int n_lanes) {
   ctx->last_n_lanes = (uint32_t)std::max(1, n_lanes);
   for (int l = 0; l < std::max(1, n_lanes); l++) {
     ctx->lanes[l]->last_stats.n_lanes = ctx->last_n_lanes;
@@ -1437,103 +1483,131 @@ static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, ui
       }
     }
   }
-  // ---- the elements of List / Map columns (list.rs:63-87, map.rs:74-104: `inner.next_batch(total_length, None)`) -----------
-  // Their count is known now.  Per such column a "stripe" of its own: its rows are the column's elements, ONE batch; its root
-  // columns the element column (a Map: key and value) with everything below; its streams those of the staged stripe.  All of
-  // them go through one more decode call together, which takes care of Lists inside them the same way.
-  {
-    std::vector<std::unique_ptr<orcgpu_staged>> vst;
-    std::vector<orcgpu_staged*> vptr;
-    std::vector<orcgpu_result*> vres;
-    struct Owner {
-      uint32_t si, col;
-    };
-    std::vector<Owner> owner;
-    for (uint32_t si = 0; si < n; si++) {
-      orcgpu_staged* s = stripes[si];
-      orcgpu_result* r = results[si];
-      for (size_t ci = 0; ci < r->cols.size(); ci++) {
-        ColumnOut& co = r->cols[ci];
-        if (!co.is_list || co.elem) continue;
-        uint64_t total = 0;
-        for (auto v : co.char_total) total += v;
-        if (total >= (1ull << 31)) {
-          set_err(ctx, "column %u: %llu elements in one stripe: more than 2^31 - 1 are not supported", co.column_id, (unsigned long long)total);
-          return ORCGPU_INVALID_ARGUMENT;
-        }
-        auto v = std::make_unique<orcgpu_staged>();
-        v->ctx = s->ctx;
-        v->desc = s->desc;
-        v->desc.n_rows = total;
-        v->desc.batch_size = (uint32_t)std::max<uint64_t>(total, 1);
-        v->dev = s->dev;
-        v->dev_bytes = s->dev_bytes;
-        v->zone = s->zone;
-        v->ready = nullptr;  // (the stripe's bytes have arrived: its own decode has just run)
-        // the subtree below column ci, parents re-numbered (the direct children become root columns)
-        std::vector<uint32_t> map_new(s->cols.size(), 0);  // 1 + new index
-        std::vector<uint32_t> src;
-        for (size_t k = ci + 1; k < s->cols.size(); k++) {
-          const uint32_t par = s->cols[k].parent;
-          if (!par || par > k) continue;
-          const bool child = par - 1 == ci, below = map_new[par - 1] != 0;
-          if (!child && !below) continue;
-          orcgpu_column c = s->cols[k];
-          c.parent = child ? 0u : map_new[par - 1];
-          v->cols.push_back(c);
-          // (the column of the caller's stripe this one stands for: `s` is itself a virtual stripe when the List lies inside a List)
-          src.push_back(r->src_col.empty() ? (uint32_t)k : r->src_col[k]);
-          map_new[k] = (uint32_t)v->cols.size();
-        }
-        for (auto& st : s->streams)
-          for (auto& c : v->cols)
-            if (c.column_id == st.column_id) {
-              v->streams.push_back(st);
-              v->stream_bytes += st.len;
-              break;
-            }
-        orcgpu_result* sub = new orcgpu_result();
-        sub->src_col = src;
-        co.sub = (int32_t)r->subs.size();
-        r->subs.push_back(sub);
-        vptr.push_back(v.get());
-        vres.push_back(sub);
-        vst.push_back(std::move(v));
-        owner.push_back(Owner{si, (uint32_t)ci});
+}
+
+// The virtual stripe of the elements of List / Map column `ci`, `total` of them: its rows are the elements, ONE batch; its root
+// columns the element column (a Map: key and value) with everything below; its streams those of the staged stripe.
+static std::unique_ptr<orcgpu_staged> element_stripe(const orcgpu_staged* s, const orcgpu_result* r, size_t ci, uint64_t total, std::vector<uint32_t>& src) {
+  auto v = std::make_unique<orcgpu_staged>();
+  v->ctx = s->ctx;
+  v->desc = s->desc;
+  v->desc.n_rows = total;
+  v->desc.batch_size = (uint32_t)std::max<uint64_t>(total, 1);
+  v->dev = s->dev;
+  v->dev_bytes = s->dev_bytes;
+  v->zone = s->zone;
+  v->ready = nullptr;  // (the stripe's bytes have arrived: its own decode has just run)
+  // the subtree below column ci, parents re-numbered (the direct children become root columns)
+  std::vector<uint32_t> map_new(s->cols.size(), 0);  // 1 + new index
+  for (size_t k = ci + 1; k < s->cols.size(); k++) {
+    const uint32_t par = s->cols[k].parent;
+    if (!par || par > k) continue;
+    const bool child = par - 1 == ci, below = map_new[par - 1] != 0;
+    if (!child && !below) continue;
+    orcgpu_column c = s->cols[k];
+    c.parent = child ? 0u : map_new[par - 1];
+    v->cols.push_back(c);
+    // (the column of the caller's stripe this one stands for: `s` is itself a virtual stripe when the List lies inside a List)
+    src.push_back(r->src_col.empty() ? (uint32_t)k : r->src_col[k]);
+    map_new[k] = (uint32_t)v->cols.size();
+  }
+  for (auto& st : s->streams)
+    for (auto& c : v->cols)
+      if (c.column_id == st.column_id) {
+        v->streams.push_back(st);
+        v->stream_bytes += st.len;
+        break;
       }
+  return v;
+}
+
+// ---- the elements of List / Map columns (list.rs:63-87, map.rs:74-104: `inner.next_batch(total_length, None)`) -----------
+// Their count is known now.  Per such column a "stripe" of its own (element_stripe).  All of
+// them go through one more decode call together, which takes care of Lists inside them the same way.
+static int decode_list_elements(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
+  std::vector<std::unique_ptr<orcgpu_staged>> vst;
+  std::vector<orcgpu_staged*> vptr;
+  std::vector<orcgpu_result*> vres;
+  struct Owner {
+    uint32_t si, col;
+  };
+  std::vector<Owner> owner;
+  for (uint32_t si = 0; si < n; si++) {
+    orcgpu_staged* s = stripes[si];
+    orcgpu_result* r = results[si];
+    for (size_t ci = 0; ci < r->cols.size(); ci++) {
+      ColumnOut& co = r->cols[ci];
+      if (!co.is_list || co.elem) continue;
+      uint64_t total = 0;
+      for (auto v : co.char_total) total += v;
+      if (total >= (1ull << 31)) {
+        set_err(ctx, "column %u: %llu elements in one stripe: more than 2^31 - 1 are not supported", co.column_id, (unsigned long long)total);
+        return ORCGPU_INVALID_ARGUMENT;
+      }
+      std::vector<uint32_t> src;
+      auto v = element_stripe(s, r, ci, total, src);
+      orcgpu_result* sub = new orcgpu_result();
+      sub->src_col = src;
+      co.sub = (int32_t)r->subs.size();
+      r->subs.push_back(sub);
+      vptr.push_back(v.get());
+      vres.push_back(sub);
+      vst.push_back(std::move(v));
+      owner.push_back(Owner{si, (uint32_t)ci});
     }
-    if (!vptr.empty()) {
-      int rc2 = decode_staged_once(ctx, vptr.data(), (uint32_t)vptr.size(), vres.data());
-      if (rc2 == ORCGPU_RETRY_LARGER_SLOTS) rc2 = decode_staged_once(ctx, vptr.data(), (uint32_t)vptr.size(), vres.data());
-      for (auto& v : vst) v->dev = nullptr;  // (borrowed)
-      if (rc2) return rc2 == ORCGPU_RETRY_LARGER_SLOTS ? ORCGPU_UNEXPECTED : rc2;
-      for (size_t k = 0; k < vres.size(); k++) {
-        orcgpu_result* r = results[owner[k].si];
-        r->arrow_bytes += vres[k]->arrow_bytes;
-        // a failure among the elements: its place among the rows is not kept (the elements are one batch) -- the stripe fails in
-        // its first batch, unless an earlier column already fails there
-        if (vres[k]->status && !r->status) {
-          r->status = vres[k]->status;
-          r->err_batch = 0;
-          r->err_col = owner[k].col;
-        }
-        // map.rs:90-99: the keys and the values of a Map become a StructArray whose `keys` field is not nullable -- a key column with a
-        // null in it (a file that holds a PRESENT stream for the keys, or one whose bytes were damaged) is an ArrowError there
-        // ("Found unmasked nulls for non-nullable StructArray field"), and an array no Arrow implementation imports here (Arrow C++
-        // aborts the process on it).  Like every failure among the elements it is the stripe's first batch that fails.
-        if (!r->status && r->cols[owner[k].col].orc_type == ORCGPU_T_MAP && !vres[k]->cols.empty()) {
-          uint64_t key_nulls = 0;
-          for (uint64_t c : vres[k]->cols[0].null_counts) key_nulls += c;
-          if (key_nulls) {
-            r->status = ORCGPU_ARROW;
-            r->err_batch = 0;
-            r->err_col = owner[k].col;
-          }
-        }
+  }
+  if (vptr.empty()) return ORCGPU_OK;
+  const int rc2 = decode_staged_retrying(ctx, vptr.data(), (uint32_t)vptr.size(), vres.data());
+  for (auto& v : vst) v->dev = nullptr;  // (borrowed)
+  if (rc2) return rc2;
+  for (size_t k = 0; k < vres.size(); k++) {
+    orcgpu_result* r = results[owner[k].si];
+    r->arrow_bytes += vres[k]->arrow_bytes;
+    // a failure among the elements: its place among the rows is not kept (the elements are one batch) -- the stripe fails in
+    // its first batch, unless an earlier column already fails there
+    if (vres[k]->status && !r->status) {
+      r->status = vres[k]->status;
+      r->err_batch = 0;
+      r->err_col = owner[k].col;
+    }
+    // map.rs:90-99: the keys and the values of a Map become a StructArray whose `keys` field is not nullable -- a key column with a
+    // null in it (a file that holds a PRESENT stream for the keys, or one whose bytes were damaged) is an ArrowError there
+    // ("Found unmasked nulls for non-nullable StructArray field"), and an array no Arrow implementation imports here (Arrow C++
+    // aborts the process on it).  Like every failure among the elements it is the stripe's first batch that fails.
+    if (!r->status && r->cols[owner[k].col].orc_type == ORCGPU_T_MAP && !vres[k]->cols.empty()) {
+      uint64_t key_nulls = 0;
+      for (uint64_t c : vres[k]->cols[0].null_counts) key_nulls += c;
+      if (key_nulls) {
+        r->status = ORCGPU_ARROW;
+        r->err_batch = 0;
+        r->err_col = owner[k].col;
       }
     }
   }
-  if (getenv("ORCGPU_DEBUG")) fprintf(stderr, "[orcgpu] call host us: behind the lanes %.1f\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_lanes);
+  return ORCGPU_OK;
+}
+
+static int decode_staged_once(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t n, orcgpu_result** results) {
+  const double call_t0 = host_us_now();
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = reset_results(ctx, stripes, n, results);
+  if (rc) return rc;
+  std::vector<std::vector<std::vector<uint8_t>>> masks;
+  int call_z = -1;  // the call's Zstandard path, decided when the call is split over lanes
+  const int n_lanes = choose_lanes(stripes, n, masks, call_z);
+  ctx->call_t0 = call_t0;
+  ctx->call_z_lanes = n_lanes > 1 ? call_z : -1;
+  ctx->n_gate_peers = 0;
+  ctx->tables_gate.store(0);
+  const double t_pre = host_us_now();
+  rc = run_lanes(ctx, stripes, n, results, masks, n_lanes);
+  const double t_lanes = host_us_now();
+  if (getenv("ORCGPU_DEBUG")) fprintf(stderr, "[orcgpu] call host us: before the lanes %.1f, lanes %.1f\n", t_pre - call_t0, t_lanes - t_pre);
+  if (rc) return rc;
+  sum_up_results(ctx, n, results, n_lanes);
+  rc = decode_list_elements(ctx, stripes, n, results);
+  if (rc) return rc;
+  if (getenv("ORCGPU_DEBUG")) fprintf(stderr, "[orcgpu] call host us: behind the lanes %.1f\n", host_us_now() - t_lanes);
   return ORCGPU_OK;
 }
 

@@ -131,24 +131,23 @@ int plan_column_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_staged* s, orcgp
   return ORCGPU_UNSUPPORTED;
 }
 
-int launch_pre_expand_ext(orcgpu_ctx*, Plan&, uint8_t*, uint64_t*) { return ORCGPU_OK; }
-
 const uint8_t* plain_ptr(const PlainStream& ps, const uint8_t* S) { return ps.scratch_off != ~0ull ? S + ps.scratch_off : ps.dev; }
 
 // phase 1 of the string / decimal finishers (everything that does not need the dictionary-gather output size)
 // (nothing is launched here: the launches are filed in `fin` by pipeline stage and leave together, see FinBatch)
-int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_result* r, uint8_t* S, uint64_t* d_scalars,
-                      unsigned long long* /*d_nullc*/, unsigned long long* d_chartot) {
+int launch_finish_ext(LaneRun& R, FinBatch& fin, ColPlan& cp, ColumnOut& co, orcgpu_result* r) {
+  uint8_t* const S = R.S;
+  uint64_t* const d_scalars = R.d_scalars;
   const uint64_t nr = cp.n_rows;
-  const unsigned long long* vbits = cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr;
-  const uint32_t* rank = cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr;
+  const unsigned long long* vbits = R.vbits(cp);
+  const uint32_t* rank = R.rank(cp);
   unsigned long long* err = reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx);
   const int t = cp.c.orc_type;
   if (is_string_type(t)) {
     int32_t* lens = reinterpret_cast<int32_t*>(S + cp.lens_off);
-    uint8_t* const arena = r->arena[ctx->lane_id].p;
+    uint8_t* const arena = R.arena(r);
     int32_t* offsets = reinterpret_cast<int32_t*>(cp.dict_out ? S + cp.rowoff_off : arena + co.offsets_off);
-    unsigned long long* chartot = d_chartot + cp.chartot_off;
+    unsigned long long* chartot = R.d_chartot + cp.chartot_off;
     unsigned long long* charbase = chartot + r->n_batches;
     const bool utf8 = t != ORCGPU_T_BINARY;
     if (cp.is_dict) {
@@ -170,7 +169,7 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
         return ORCGPU_OK;
       }
       // keys -> lengths -> offsets -> gather run for all dictionary columns of the call together: launch_dict_rows
-      P.pending_gathers.push_back((int)(&cp - P.cols.data()));
+      R.P.pending_gathers.push_back((int)(&cp - R.P.cols.data()));
       return ORCGPU_OK;
     } else {
       // charbase (still zero from the summary upload) collects the out-of-range lengths until batch_base_kernel fills it
@@ -202,8 +201,8 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
   }
   if (t == ORCGPU_T_LIST || t == ORCGPU_T_MAP) {
     int32_t* lens = reinterpret_cast<int32_t*>(S + cp.lens_off);
-    int32_t* offsets = reinterpret_cast<int32_t*>(r->arena[ctx->lane_id].p + co.offsets_off);
-    unsigned long long* chartot = d_chartot + cp.chartot_off;
+    int32_t* offsets = reinterpret_cast<int32_t*>(R.arena(r) + co.offsets_off);
+    unsigned long long* chartot = R.d_chartot + cp.chartot_off;
     unsigned long long* charbase = chartot + r->n_batches;
     // (the same three steps as a direct string's lengths: spaced lengths, per-batch offsets and totals, their scan)
     fin.add<string_lens_body, 256>(0, nr, false, (const int64_t*)(S + cp.dense_off), vbits, rank, lens, nr, r->batch, charbase, err);
@@ -231,7 +230,7 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
       // a column without nulls: value k is row k -- the varint decoder brings it to the column's scale and writes the Arrow buffer
       // itself (no decimal_finish pass: 36 bytes per value that re-read what was just written)
       const bool fused = !vbits && nr;
-      __int128* const arrow = reinterpret_cast<__int128*>(r->arena[ctx->lane_id].p + co.values_off);
+      __int128* const arrow = reinterpret_cast<__int128*>(R.arena(r) + co.values_off);
       fin.add<varint_decode128_body, 256>(4, (cp.data.len_upper + 7) / 8, false, src, (const uint64_t*)d_scalars, cp.data.len_idx, cp.nonnull_idx,
                                           (const unsigned long long*)tmask, (const uint32_t*)trank, fused ? arrow : dense, cp.data.len_upper,
                                           reinterpret_cast<unsigned long long*>(d_scalars + cp.utf8err_idx),
@@ -240,7 +239,7 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
       if (fused) return ORCGPU_OK;
     }
     fin.add<decimal_finish_body, 256>(5, nr, false, (const __int128*)dense, (const int32_t*)(S + cp.dense2_off), vbits, rank,
-                                      reinterpret_cast<__int128*>(r->arena[ctx->lane_id].p + co.values_off), nr, cp.c.scale);
+                                      reinterpret_cast<__int128*>(R.arena(r) + co.values_off), nr, cp.c.scale);
     return ORCGPU_OK;
   }
   return ORCGPU_OK;
@@ -250,16 +249,18 @@ int launch_finish_ext(orcgpu_ctx* ctx, FinBatch& fin, Plan& P, ColPlan& cp, Colu
 // A DICTIONARY stripe: the DATA ids, spaced over the rows and bounds-checked against the dictionary size on the device.  A
 // DIRECT stripe: a valid row's rank among the valid rows, and with it entry `rank` of the identity dictionary's offsets.
 // Nothing is sized on the host: keys and dictionary lie in the result's arena, at places known when the call was planned.
-int launch_dict_keys(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint64_t* d_scalars, unsigned long long* d_chartot) {
-  for (auto& cp : P.cols) {
+int launch_dict_keys(LaneRun& R) {
+  uint8_t* const S = R.S;
+  uint64_t* const d_scalars = R.d_scalars;
+  for (auto& cp : R.P.cols) {
     if (cp.col < 0 || !cp.dict_out || !cp.n_rows) continue;
-    orcgpu_result* r = P.results[cp.stripe];
+    orcgpu_result* r = R.P.results[cp.stripe];
     ColumnOut& co = r->cols[cp.col];
-    uint8_t* const arena = r->arena[ctx->lane_id].p;
+    uint8_t* const arena = R.arena(r);
     DictKeysJob j{};
     j.dense = cp.is_dict ? S + cp.dense_off : nullptr;
-    j.vbits = cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr;
-    j.rank = cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr;
+    j.vbits = R.vbits(cp);
+    j.rank = R.rank(cp);
     j.keys = reinterpret_cast<int32_t*>(arena + co.values_off);
     j.err = reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx);
     j.dict_err = reinterpret_cast<const unsigned long long*>(d_scalars + cp.dicterr_idx);
@@ -270,21 +271,25 @@ int launch_dict_keys(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint64_t* d_scalars, 
     j.dict_n_idx = cp.dictn_idx;
     if (!cp.is_dict) {
       j.row_offsets = reinterpret_cast<const int32_t*>(S + cp.rowoff_off);
-      j.charbase = d_chartot + cp.chartot_off + r->n_batches;
+      j.charbase = R.d_chartot + cp.chartot_off + r->n_batches;
       j.dict_off = reinterpret_cast<int32_t*>(arena + co.dict_offsets_off);
       j.nonnull_idx = cp.nonnull_idx;
       j.total_idx = cp.dictbytes_idx;
     }
-    HIP_TRY(ctx, launch(dict_keys_kernel, (cp.n_rows + DICT_PER - 1) / DICT_PER, false, 256, ctx->stream, j));
+    HIP_TRY(R.ctx, launch(dict_keys_kernel, (cp.n_rows + DICT_PER - 1) / DICT_PER, false, 256, R.st, j));
   }
   return ORCGPU_OK;
 }
 
 // Dictionary columns, pass 1: one descriptor per column, ONE launch for the per-batch value byte totals (keys bounds-checked)
 // and one for their scan per column.
-int launch_dict_rows(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint64_t* d_scalars, unsigned long long* d_chartot) {
+int launch_dict_rows(LaneRun& R) {
+  Plan& P = R.P;
   if (P.pending_gathers.empty()) return ORCGPU_OK;
-  hipStream_t st = ctx->stream;
+  orcgpu_ctx* const ctx = R.ctx;
+  hipStream_t st = R.st;
+  uint8_t* const S = R.S;
+  uint64_t* const d_scalars = R.d_scalars;
   P.dictjobs.clear();
   uint32_t max_batches = 0;
   for (int idx : P.pending_gathers) {
@@ -293,12 +298,12 @@ int launch_dict_rows(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint64_t* d_scalars, 
     ColumnOut& co = r->cols[cp.col];
     DictJob j{};
     j.dense = S + cp.dense_off;
-    j.vbits = cp.has_present ? reinterpret_cast<const unsigned long long*>(S + cp.vbits_off) : nullptr;
-    j.rank = cp.has_present ? reinterpret_cast<const uint32_t*>(S + cp.rank_off) : nullptr;
+    j.vbits = R.vbits(cp);
+    j.rank = R.rank(cp);
     j.doff = reinterpret_cast<const int32_t*>(S + cp.dictoff_off);
     j.dbytes = plain_ptr(cp.dict, S);
-    j.offsets = reinterpret_cast<int32_t*>(r->arena[ctx->lane_id].p + co.offsets_off);
-    j.chartot = d_chartot + cp.chartot_off;
+    j.offsets = reinterpret_cast<int32_t*>(R.arena(r) + co.offsets_off);
+    j.chartot = R.d_chartot + cp.chartot_off;
     j.err = reinterpret_cast<unsigned long long*>(d_scalars + cp.err_idx);
     j.dict_err = reinterpret_cast<const unsigned long long*>(d_scalars + cp.dicterr_idx);
     j.out_chars = nullptr;
@@ -340,7 +345,9 @@ static void place_dict_columns(Plan& P, const uint64_t* h_scalars, std::vector<u
     need[cp.stripe] = co.values_off + total + ORC_PAD;
   }
 }
-static int launch_dict_emit(orcgpu_ctx* ctx, Plan& P, uint8_t* S, const uint64_t* d_scalars, bool upload) {
+static int launch_dict_emit(LaneRun& R, bool upload) {
+  Plan& P = R.P;
+  orcgpu_ctx* const ctx = R.ctx;
   uint32_t max_batches = 0;
   for (size_t k = 0; k < P.pending_gathers.size(); k++) {
     ColPlan& cp = P.cols[P.pending_gathers[k]];
@@ -350,26 +357,27 @@ static int launch_dict_emit(orcgpu_ctx* ctx, Plan& P, uint8_t* S, const uint64_t
     max_batches = std::max(max_batches, r->n_batches);  // (offsets are written for every column, value bytes or not)
   }
   if (max_batches) {
-    hipStream_t st = ctx->stream;
-    DictJob* d_jobs = reinterpret_cast<DictJob*>(S + P.dictjobs_off);
+    hipStream_t st = R.st;
+    DictJob* d_jobs = reinterpret_cast<DictJob*>(R.S + P.dictjobs_off);
     const uint32_t n = (uint32_t)P.dictjobs.size();
     if (upload) HIP_TRY(ctx, ctx->upload(d_jobs, P.dictjobs.data(), n * sizeof(DictJob), st));
     HIP_TRY(ctx, hipEventRecord(ctx->kev[1][0], st));
     for (uint32_t o = 0; o < n; o += 65535u)  // grid.y limit
-      hipLaunchKernelGGL(dict_emit_kernel, dim3(max_batches, std::min<uint32_t>(65535u, n - o)), dim3(256), 0, st, (const DictJob*)(d_jobs + o), d_scalars);
+      hipLaunchKernelGGL(dict_emit_kernel, dim3(max_batches, std::min<uint32_t>(65535u, n - o)), dim3(256), 0, st, (const DictJob*)(d_jobs + o), (const uint64_t*)R.d_scalars);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->kev[1][1], st));
     ctx->kev_used[1] = true;
   }
   return ORCGPU_OK;
 }
-int launch_post_ext(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint8_t* dsum, uint8_t* hs, const SummaryLayout& SL, unsigned long long* d_chartot) {
-  (void)d_chartot;
+int launch_post_ext(LaneRun& R) {
+  Plan& P = R.P;
+  orcgpu_ctx* const ctx = R.ctx;
+  uint8_t* const S = R.S;
   P.dictplaces.clear();
   P.dictplace_result.clear();
   if (P.pending_gathers.empty()) return ORCGPU_OK;
-  hipStream_t st = ctx->stream;
-  const uint64_t* d_scalars = reinterpret_cast<const uint64_t*>(dsum + SL.scalars_off);
+  hipStream_t st = R.st;
   // the results' arenas as they are: usable when every result has one and its columns follow one another in the job table
   constexpr bool never = false;
   bool on_device = !never;
@@ -390,15 +398,15 @@ int launch_post_ext(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint8_t* dsum, uint8_t
     HIP_TRY(ctx, ctx->upload(d_places, P.dictplaces.data(), np * sizeof(DictPlace), st));
     HIP_TRY(ctx, launch(dict_place_kernel, (uint64_t)np, false, 64, st, reinterpret_cast<DictJob*>(S + P.dictjobs_off), (const DictPlace*)d_places, np, (uint64_t)ORC_PAD,
                         (uint64_t)kAlign));
-    return launch_dict_emit(ctx, P, S, d_scalars, false);
+    return launch_dict_emit(R, false);
   }
   P.dictplaces.clear();
   P.dictplace_result.clear();
-  HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)P.scalars.size(), false, 256, st, (const unsigned long long*)(dsum + SL.scalars_off),
-                      (unsigned long long*)(hs + SL.scalars_off), (uint64_t)P.scalars.size()));
+  HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)P.scalars.size(), false, 256, st, (const unsigned long long*)(R.dsum + R.SL.scalars_off),
+                      (unsigned long long*)(R.hs + R.SL.scalars_off), (uint64_t)P.scalars.size()));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   std::vector<uint64_t> need;
-  place_dict_columns(P, reinterpret_cast<const uint64_t*>(hs + SL.scalars_off), need);
+  place_dict_columns(P, R.h_scalars(), need);
   for (size_t si = 0; si < P.results.size(); si++) {
     P.results[si]->chars_used[ctx->lane_id] = need[si];
     if (need[si] && !P.results[si]->chars[ctx->lane_id].ensure(need[si] + kAlign)) {
@@ -406,14 +414,16 @@ int launch_post_ext(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint8_t* dsum, uint8_t
       return ORCGPU_HIP_ERROR;
     }
   }
-  return launch_dict_emit(ctx, P, S, d_scalars, true);
+  return launch_dict_emit(R, true);
 }
 
 // Behind the call's closing synchronisation: where the device placed the dictionary columns' value bytes (see launch_post_ext).
-int settle_dict_places(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint8_t* dsum, uint8_t* hs, const SummaryLayout& SL) {
+int settle_dict_places(LaneRun& R) {
+  Plan& P = R.P;
+  orcgpu_ctx* const ctx = R.ctx;
   if (P.dictplaces.empty()) return ORCGPU_OK;
   std::vector<uint64_t> need;
-  place_dict_columns(P, reinterpret_cast<const uint64_t*>(hs + SL.scalars_off), need);
+  place_dict_columns(P, R.h_scalars(), need);
   bool again = false;
   for (size_t k = 0; k < P.dictplaces.size(); k++) again = again || need[P.dictplace_result[k]] + kAlign > P.dictplaces[k].cap;
   for (size_t si = 0; si < P.results.size(); si++) {
@@ -425,14 +435,14 @@ int settle_dict_places(orcgpu_ctx* ctx, Plan& P, uint8_t* S, uint8_t* dsum, uint
   }
   if (!again) return ORCGPU_OK;
   // (every column once more: the arenas that grew are new memory)
-  int rc = launch_dict_emit(ctx, P, S, reinterpret_cast<const uint64_t*>(dsum + SL.scalars_off), true);
+  int rc = launch_dict_emit(R, true);
   if (rc) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(R.st));
   return ORCGPU_OK;
 }
 
 template <typename F>
-uint32_t resolve_job_batch(Plan&, ColPlan& cp, ColumnOut&, orcgpu_result*, int k, uint64_t idx, F& batch_of_dense) {
+uint32_t resolve_job_batch(const ColPlan& cp, int k, uint64_t idx, F& batch_of_dense) {
   // the dictionary LENGTH stream is decoded when the column decoder is built: a failure there fails
   // the whole stripe (new_string_decoder, string.rs:70-72), i.e. batch 0
   if (k == 2 && cp.is_dict) return 0;
@@ -440,8 +450,9 @@ uint32_t resolve_job_batch(Plan&, ColPlan& cp, ColumnOut&, orcgpu_result*, int k
 }
 
 template <typename F>
-void resolve_ext(Plan& P, ColPlan& cp, ColumnOut& co, orcgpu_result* r, const uint64_t* h_scalars, const unsigned long long* h_chartot, F& consider) {
-  (void)P;
+void resolve_ext(LaneRun& R, ColPlan& cp, ColumnOut& co, orcgpu_result* r, F& consider) {
+  const uint64_t* h_scalars = R.h_scalars();
+  const unsigned long long* h_chartot = R.h_chartot();
   const int t = cp.c.orc_type;
   if ((t == ORCGPU_T_LIST || t == ORCGPU_T_MAP) && cp.n_rows) {
     co.char_total.assign(h_chartot + cp.chartot_off, h_chartot + cp.chartot_off + r->n_batches);
@@ -502,5 +513,3 @@ uint64_t result_column_bytes(const orcgpu_result* r, const ColumnOut& co) {
 }
 
 }  // namespace
-
-#include "orcgpu_decompress.inc"

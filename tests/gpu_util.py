@@ -40,9 +40,10 @@ def oracle_column(col, streams, compression="none", block_size=262144, ts_unit=3
 
 
 def assert_column_parity(res, ci, col, streams, n_rows, batch_size, compression="none", block_size=262144, ts_unit=3,
-                         ts_base=1420070400, what="", writer_timezone=None):
+                         ts_base=1420070400, what="", writer_timezone=None, parent_present=None):
     """The reference yields Ok batches until the first failing one (arrow_reader.rs:333-346): the
-    GPU result must agree on every Ok batch bit for bit and on the index + kind of the failure."""
+    GPU result must agree on every Ok batch bit for bit and on the index + kind of the failure.
+    parent_present: one byte per row of the stripe, 0 where the Struct or Union arm above the column is null (None: a root column)."""
     oc = oracle_column(col, streams, compression, block_size, ts_unit, ts_base, writer_timezone)
     gst, gbatch, gcol = res.status()
     left = n_rows
@@ -52,7 +53,7 @@ def assert_column_parity(res, ci, col, streams, n_rows, batch_size, compression=
         return
     while left > 0:
         n = min(batch_size, left)
-        ob = oc.next_batch(n)
+        ob = oc.next_batch(n, None if parent_present is None else parent_present[n_rows - left:n_rows - left + n])
         if ob["status"] != O.OK:
             assert gst != 0 and gcol == ci and gbatch == b, (what, "oracle fails at batch", b, ob["status"], "gpu", gst, gbatch, gcol)
             assert gst == ob["status"], (what, "error kind", gst, ob["status"])
