@@ -426,7 +426,14 @@ int orcgpu_reader_row_groups(const orcgpu_reader* r, uint64_t* read, uint64_t* t
 /* A Predicate as a list of nodes in pre-order: a node, then its children one after the other (AND / OR: n_children of them,
  * NOT: one; comparisons and null tests: none). */
 enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_LE = 3, ORCGPU_PRED_GT = 4, ORCGPU_PRED_GE = 5, /* ComparisonOp */
-       ORCGPU_PRED_IS_NULL = 6, ORCGPU_PRED_IS_NOT_NULL = 7, ORCGPU_PRED_AND = 8, ORCGPU_PRED_OR = 9, ORCGPU_PRED_NOT = 10 };
+       ORCGPU_PRED_IS_NULL = 6, ORCGPU_PRED_IS_NOT_NULL = 7, ORCGPU_PRED_AND = 8, ORCGPU_PRED_OR = 9, ORCGPU_PRED_NOT = 10,
+       /* (11 .. 15: unknown ops) */
+       ORCGPU_PRED_LIKE = 16 /* SQL LIKE, this library's own: a leaf with column, value_type = ORCGPU_PV_UTF8, s / s_len = the pattern,
+                                i = the escape byte (0: none, else 1 .. 127), value_is_null = the NULL pattern; see orcgpu_result_filter */ };
+/* What a LIKE pattern may hold after unescaping: bytes (wildcards included) and non-empty parts between its `%` signs.  The
+ * compiled pattern then fits the matcher kernel's LDS. */
+#define ORCGPU_LIKE_MAX_BYTES 1024
+#define ORCGPU_LIKE_MAX_PARTS 64
 /* PredicateValue (predicate.rs:29-47), and two kinds the reference does not have:
  *   ORCGPU_PV_DECIMAL128    s -> the 16 bytes of the unscaled value, little-endian two's complement, s_len = 16; i = the literal's
  *                           scale, 0 .. 38; |unscaled| < 10^38.  Anything else is ORCGPU_INVALID_ARGUMENT (the message names the column).
@@ -487,6 +494,18 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     divide; clamped where it leaves int128), the device compares integers and rescales no row.  Any other literal kind on
  *     these columns, and a Timestamp column decoded to Decimal128(38, 9), is ORCGPU_UNSUPPORTED (the message names the column);
  *     a Decimal128 or TimestampNs literal on any other column is ORCGPU_MISMATCHED_SCHEMA.
+ *   - ORCGPU_PRED_LIKE on a String / Varchar / Char column with a Utf8 pattern.  The pattern is matched against the WHOLE exported
+ *     value of the row (a Char value with its padding).  `%` matches any run of bytes, none included; `_` matches exactly one
+ *     UTF-8 code point of the value (a lead byte with the continuation bytes 10xxxxxx behind it; a newline is a character like
+ *     any other); the escape byte (node.i; 0: none) makes the pattern byte behind it a literal, whatever that byte is; every other
+ *     pattern byte matches itself, as an unsigned byte -- the pattern need not be valid UTF-8.  A null row and the NULL pattern
+ *     are UNKNOWN; there is no NOT LIKE: put ORCGPU_PRED_NOT above the leaf (a null row is dropped either way).  A Binary
+ *     column, any other column kind and any other value_type: ORCGPU_MISMATCHED_SCHEMA.  A pattern that ends in its escape byte
+ *     and an escape outside 0 .. 127: ORCGPU_INVALID_ARGUMENT.  A pattern of more than ORCGPU_LIKE_MAX_BYTES bytes after
+ *     unescaping or more than ORCGPU_LIKE_MAX_PARTS non-empty parts between its `%`: ORCGPU_UNSUPPORTED (the compiled pattern is
+ *     held in the matcher kernel's LDS).  A column read as a dictionary column: ORCGPU_UNSUPPORTED, as for a comparison.  Each
+ *     message names the column.  The pattern is matched by a kernel of its own (filter_like_kernel) in front of the evaluation,
+ *     on the same stream: no further host wait.
  *   - A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
  *   - A leaf naming a column that is not there, a leaf without a name, an unknown op, a node list that ends inside a node's
  *     children or goes on behind the root, and a predicate nested deeper than ORCGPU_FILTER_MAX_DEPTH levels (a leaf alone is

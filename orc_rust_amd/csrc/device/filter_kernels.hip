@@ -9,6 +9,10 @@
 //                         a per-wavefront stack with wave-uniform code.  Writes keep = T_root & live and its popcount.
 //                         A Decimal leaf compares the row's 16 bytes with a literal the host has brought to the column's scale,
 //                         a Timestamp leaf is the integer leaf on a literal in the column's unit: no row is ever rescaled.
+//   filter_like_kernel    runs in front of it when the program holds LIKE leaves: per leaf a plane of match bits, one word per
+//                         64 input rows like `keep`; the evaluation forms T = match & valid, F = ~match & valid from it.  The
+//                         compiled pattern (parts of literal bytes and `_` marks between the `%`) lies in LDS; no backtracking;
+//                         a lane per short value, the wavefront on 64 candidate starts at once for a long one.
 //   (enc_scan)            exclusive scan of the popcounts: the output row of every word's first kept row.
 //   filter_place_kernel   every kept row writes its stripe row at its output row: src_rows[], the gather's index list.
 //   filter_count_kernel   per (output batch, column): null count and string bytes -- what the host needs to lay the output out
@@ -67,10 +71,158 @@ __device__ __forceinline__ uint32_t filter_str_len(const FilterCol& c, uint64_t 
   return (uint32_t)o[1] - (uint32_t)o[0];
 }
 
+// ---- LIKE: the compiled pattern of filter_program.h, staged in LDS ----
+struct LikePat {
+  uint32_t shape, flags, n_parts, n_elems;
+  const uint32_t* parts;  // per part {first element, elements}
+  const uint8_t* bytes;   // per element: the literal byte
+  const uint8_t* ones;    // per element: 1 = `_`
+};
+constexpr uint32_t kLikeFail = 0xffffffffu;
+
+// Part [first, first + n) matched forwards from position s of the value p[0, end): where the match ends, or kLikeFail.  A `_`
+// takes the byte that stands there and the continuation bytes behind it.  Nothing at or behind `end` is loaded.
+template <bool LIT>
+__device__ __forceinline__ uint32_t like_fwd(const uint8_t* p, uint32_t s, uint32_t end, const LikePat& P, uint32_t first, uint32_t n) {
+  uint32_t q = s;
+  for (uint32_t k = 0; k < n; k++) {
+    if (q >= end) return kLikeFail;
+    if (!LIT && P.ones[first + k]) {
+      q++;
+      while (q < end && (p[q] & 0xC0) == 0x80) q++;
+    } else {
+      if (p[q] != P.bytes[first + k]) return kLikeFail;
+      q++;
+    }
+  }
+  return q;
+}
+// ... and backwards from `e`, where the match is to end, without stepping below `lo`: where the match starts, or kLikeFail
+template <bool LIT>
+__device__ __forceinline__ uint32_t like_bwd(const uint8_t* p, uint32_t lo, uint32_t e, const LikePat& P, uint32_t first, uint32_t n) {
+  uint32_t q = e;
+  for (uint32_t k = n; k-- > 0;) {
+    if (q <= lo) return kLikeFail;
+    q--;
+    if (!LIT && P.ones[first + k]) {
+      while (q > lo && (p[q] & 0xC0) == 0x80) q--;
+    } else if (p[q] != P.bytes[first + k]) return kLikeFail;
+  }
+  return q;
+}
+// The leftmost match of a part that starts in [pos, end - n]: where it ends, or kLikeFail.  One lane walks the starts one by one;
+// a wavefront (every lane with the same value) tests 64 starts at once and takes the first hit by ballot.
+template <bool WAVE, bool LIT>
+__device__ __forceinline__ uint32_t like_find(const uint8_t* p, uint32_t pos, uint32_t end, const LikePat& P, uint32_t first, uint32_t n, uint32_t lane) {
+  if (end - pos < n) return kLikeFail;
+  const uint32_t last = end - n;  // (every element takes a byte at least)
+  if (!WAVE) {
+    for (uint32_t s = pos; s <= last; s++) {
+      const uint32_t q = like_fwd<LIT>(p, s, end, P, first, n);
+      if (q != kLikeFail) return q;
+    }
+    return kLikeFail;
+  }
+  for (uint32_t base = pos; base <= last; base += 64) {
+    const uint32_t s = base + lane;
+    const uint32_t q = s <= last ? like_fwd<LIT>(p, s, end, P, first, n) : kLikeFail;
+    const unsigned long long hit = __ballot(q != kLikeFail);
+    if (hit) return (uint32_t)__shfl((int)q, (int)__builtin_ctzll(hit));
+  }
+  return kLikeFail;
+}
+// Does the value p[0, len) match?  No backtracking: the first part at the start and the last part at the end where the pattern
+// anchors them, the parts between leftmost-first, each behind the one before and in front of an anchored last part.
+template <bool WAVE, bool LIT>
+__device__ __forceinline__ bool like_match(const uint8_t* p, uint32_t len, const LikePat& P, uint32_t lane) {
+  if (len < P.n_elems) return false;
+  uint32_t pos = 0, end = len, lo = 0, hi = P.n_parts;
+  if (P.flags & LIKE_ANCHOR_START) {
+    pos = like_fwd<LIT>(p, 0, len, P, P.parts[0], P.parts[1]);
+    if (pos == kLikeFail) return false;
+    lo = 1;
+    if (hi == 1 && (P.flags & LIKE_ANCHOR_END)) return pos == len;
+  }
+  if ((P.flags & LIKE_ANCHOR_END) && hi > lo) {
+    hi--;
+    end = like_bwd<LIT>(p, pos, len, P, P.parts[2 * hi], P.parts[2 * hi + 1]);
+    if (end == kLikeFail) return false;
+  }
+  for (uint32_t k = lo; k < hi; k++) {
+    pos = like_find<WAVE, LIT>(p, pos, end, P, P.parts[2 * k], P.parts[2 * k + 1], lane);
+    if (pos == kLikeFail) return false;
+  }
+  return true;
+}
+
+// The LIKE leaves' matcher, in front of filter_eval_kernel on its stream.  blockIdx.y = a mask plane, i.e. one LIKE leaf of the
+// program (FilterInsn::i); a wavefront trip is one 64-bit word of the plane, laid out like `keep`: bit = the row's value matches
+// (null rows and rows past n_in: 0).  The compiled pattern is staged in LDS once per workgroup.  Values of up to
+// kFilterShortString bytes are matched by their own lane, longer ones one after the other by the whole wavefront.  Every load of
+// a value byte is bounded by the value's length: the chars buffer promises nothing behind its last value.
+extern "C" __global__ void __launch_bounds__(256)
+filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                   const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* masks) {
+  __shared__ uint32_t pat_s[kLikeBlobMax / 4];
+  __shared__ uint32_t insn_s;
+  if (threadIdx.x == 0) {
+    uint32_t at = n_insn;
+    for (uint32_t k = 0; k < n_insn; k++)
+      if (prog[k].op == FOP_LIKE && prog[k].cmp != LIKE_ALL && prog[k].i == (long long)blockIdx.y) at = k;
+    insn_s = at;
+  }
+  __syncthreads();
+  if (insn_s >= n_insn) return;
+  const FilterInsn in = prog[insn_s];
+  const uint32_t blob = in.lit_len < kLikeBlobMax ? in.lit_len : kLikeBlobMax;
+  for (uint32_t x = threadIdx.x; x < blob; x += 256) reinterpret_cast<uint8_t*>(pat_s)[x] = lits[in.lit_off + x];
+  __syncthreads();
+  LikePat P;
+  P.shape = pat_s[0];
+  P.flags = pat_s[1];
+  P.n_parts = pat_s[2] < kLikeMaxParts ? pat_s[2] : kLikeMaxParts;
+  P.n_elems = pat_s[3] < kLikeMaxBytes ? pat_s[3] : kLikeMaxBytes;
+  P.parts = pat_s + kLikeHeaderWords;
+  P.bytes = reinterpret_cast<const uint8_t*>(pat_s + kLikeHeaderWords + 2 * P.n_parts);
+  P.ones = P.bytes + P.n_elems;
+  const bool lit = P.shape != LIKE_GENERAL;  // one part of literal bytes: the prefix, suffix and contains shapes skip the `_` tests
+  const FilterCol c = cols[in.col];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t n_words = (n_in + 63) / 64;
+  unsigned long long* plane = masks + (uint64_t)blockIdx.y * n_words;
+  for (uint64_t w = (uint64_t)blockIdx.x * 4 + wave; w < n_words; w += (uint64_t)gridDim.x * 4) {
+    const uint64_t j = w * 64 + lane;
+    const bool live = j < n_in;
+    const uint64_t row = live ? filter_src_row(segs, seg_first, n_segs, j) : 0;
+    const uint64_t u = row / B;
+    const uint32_t l = (uint32_t)(row % B);
+    const bool valid = live && filter_valid(c, u, l, W);
+    uint32_t len = 0;
+    unsigned long long at = 0;
+    if (valid) {
+      const int32_t* o = c.offsets + u * (B + 1) + l;
+      const uint32_t a = (uint32_t)o[0];
+      len = (uint32_t)o[1] - a;
+      at = c.char_base[u] + a;
+    }
+    const bool is_long = valid && len > kFilterShortString;
+    bool m = false;
+    if (valid && !is_long) m = lit ? like_match<false, true>(c.chars + at, len, P, lane) : like_match<false, false>(c.chars + at, len, P, lane);
+    unsigned long long M = __ballot(m);
+    for (unsigned long long todo = __ballot(is_long); todo; todo &= todo - 1) {
+      const int src = __builtin_ctzll(todo);
+      const uint8_t* p = c.chars + (unsigned long long)__shfl((long long)at, src);
+      const uint32_t n = (uint32_t)__shfl((int)len, src);
+      if (lit ? like_match<true, true>(p, n, P, lane) : like_match<true, false>(p, n, P, lane)) M |= 1ull << src;
+    }
+    if (lane == 0) plane[w] = M;
+  }
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
                    const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* keep,
-                   uint32_t* cnt) {
+                   uint32_t* cnt, const unsigned long long* like_masks) {
   __shared__ unsigned long long stk_t[4][kFilterStack], stk_f[4][kFilterStack];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t n_words = (n_in + 63) / 64;
@@ -153,6 +305,12 @@ filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
         }
         T = __ballot(t);
         F = __ballot(f);
+      } else if (in.op == FOP_LIKE) {
+        // the trip's match bits are there already (filter_like_kernel); only `%`: every valid row, and no plane to load
+        const unsigned long long valid_m = __ballot(live && filter_valid(cols[in.col], u, l, W));
+        const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : like_masks[(uint64_t)in.i * n_words + w];
+        T = match & valid_m;
+        F = ~match & valid_m;
       } else if (in.op == FOP_TRUE) {
         T = live_m;
       } else if (in.op == FOP_FALSE) {

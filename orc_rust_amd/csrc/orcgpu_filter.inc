@@ -67,6 +67,10 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   const uint64_t o_sums = t.take(((n_words + 2047) / 2048) * 8 + 16);
   const uint64_t n_counters = 1 + 2ull * nc * nb_max;  // the kept row count, then null counts and string bytes [column][batch]
   const uint64_t o_counters = t.take(n_counters * 8 + 16), o_rows = t.take(n_in * 4 + 16);
+  // (the LIKE leaves' planes of match bits, laid out like `keep`: part of this workspace, which only ever grows)
+  uint32_t n_like = 0;
+  for (auto& in : plan.prog) n_like += in.op == FOP_LIKE && in.cmp != LIKE_ALL;
+  const uint64_t o_like = t.take((uint64_t)n_like * n_words * 8 + 16);
   // (the second upload, behind the wait: the gather's jobs and the char bases of the output batches)
   const uint64_t o_jobs = t.take((uint64_t)nc * sizeof(FilterGatherJob) + 16), o_obase = t.take((uint64_t)nc * nb_max * 8 + 16);
   if (!r->filt_tmp.ensure(t.off + kAlign)) {
@@ -112,7 +116,7 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
     }
   }
   for (auto& in : plan.prog) {  // (the plan was compiled against these columns' types; what the decode made of them must fit)
-    if (in.op > FOP_CMP_DEC128) continue;
+    if (!fop_reads_values(in.op)) continue;
     if (in.col < nc && r->cols[in.col].dict_out) {  // (string predicates evaluated on the entries: not yet)
       if (column_names && in.col < n_names) set_err(ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[in.col]);
       else set_err(ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", r->cols[in.col].column_id);
@@ -135,9 +139,15 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
     HIP_TRY(ctx, ctx->upload(X, host.data(), up_bytes, st));
     HIP_TRY(ctx, hipMemsetAsync(d_counters, 0, n_counters * 8, st));
     const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((n_words + 3) / 4, 16384);
+    if (n_like) {  // the matcher first: the evaluation reads its bits
+      hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_like), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
+                         reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W, reinterpret_cast<unsigned long long*>(X + o_like));
+      HIP_TRY(ctx, hipGetLastError());
+    }
     hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
                        reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W,
-                       reinterpret_cast<unsigned long long*>(X + o_keep), reinterpret_cast<uint32_t*>(X + o_cnt));
+                       reinterpret_cast<unsigned long long*>(X + o_keep), reinterpret_cast<uint32_t*>(X + o_cnt),
+                       reinterpret_cast<const unsigned long long*>(X + o_like));
     HIP_TRY(ctx, hipGetLastError());
     int rc = enc_scan(ctx, st, reinterpret_cast<const uint32_t*>(X + o_cnt), n_words, reinterpret_cast<uint64_t*>(X + o_sums),
                       reinterpret_cast<uint64_t*>(d_counters), reinterpret_cast<uint64_t*>(X + o_woff));

@@ -1,8 +1,9 @@
 // orcgpu_filter_plan.inc -- the row filter's plan compiler, host only and free of HIP (tests/hostcheck/filter_plan_check.cpp
 // compiles this very text under AddressSanitizer + UBSan): a predicate as the pre-order node list of include/orcgpu.h ->
 // the post-order program filter_eval_kernel runs (device/filter_program.h).  Names become column indices, the type table
-// of orcgpu_result_filter is applied, Decimal128 and TimestampNs literals are brought to the column's own scale / unit, and
-// the depth is bounded.
+// of orcgpu_result_filter is applied, Decimal128 and TimestampNs literals are brought to the column's own scale / unit, LIKE
+// patterns are cut into the parts filter_like_kernel matches (tests/hostcheck/filter_plan_like_check.cpp), and the depth is
+// bounded.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -10,8 +11,11 @@
 
 #include "device/filter_program.h"
 #include "orcgpu_decimal.inc"
+#include "orcgpu_like.inc"
 
 namespace orcgpu_host {
+
+static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
 
 struct FilterPlan {
   std::vector<FilterInsn> prog;
@@ -204,10 +208,93 @@ struct FilterCompiler {
         out.prog.push_back(in);
         return ORCGPU_OK;
       }
+      case ORCGPU_PRED_LIKE: {
+        uint32_t col = 0;
+        const int rc = column(n, col);
+        if (rc) return rc;
+        return like(n, col);
+      }
       default:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: unknown node op%s %lld", "", n.op);
     }
   }
+  // A LIKE leaf.  The pattern is cut at its unescaped `%` into parts of literal bytes and `_` marks; since a `_` takes exactly the
+  // code point that stands there, a part matched from a given start has one length and the kernel never backtracks: the first part
+  // sits at the value's start unless the pattern begins with `%`, the last one at its end unless it ends with `%`, the ones
+  // between are found leftmost-first.  No wildcard: the string comparison EQ; only `%`: every valid row.
+  int like(const orcgpu_predicate_node& n, uint32_t col) {
+    const int kind = kinds[col];
+    if ((kind != ORCGPU_T_STRING && kind != ORCGPU_T_VARCHAR && kind != ORCGPU_T_CHAR) || n.value_type != ORCGPU_PV_UTF8)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "row filter: LIKE takes a String / Varchar / Char column and a Utf8 pattern: column '%s' with value type %lld does not fit", n.column, n.value_type);
+    if (n.i < 0 || n.i > 127) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the LIKE escape for column '%s' is %lld (0: none, else 1 .. 127)", n.column, n.i);
+    if (n.value_is_null) {
+      emit(FOP_UNKNOWN);
+      return ORCGPU_OK;
+    }
+    if (n.s_len && !n.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the LIKE pattern for column '%s' has a length and no bytes", n.column);
+    if (n.s_len > 2ull * kLikeMaxBytes)  // (even with every byte escaped)
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the LIKE pattern for column '%s' is longer than %lld bytes", n.column, kLikeMaxBytes);
+    LikePattern pat;
+    if (!like_unescape(n.s, (size_t)n.s_len, (int)n.i, pat))
+      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the LIKE pattern for column '%s' ends in its escape byte", n.column);
+    const size_t ne = pat.kinds.size();
+    if (ne > kLikeMaxBytes)
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the LIKE pattern for column '%s' is longer than %lld bytes", n.column, kLikeMaxBytes);
+    FilterInsn in{};
+    in.col = col;
+    if (pat.wildcard_free()) {
+      in.op = FOP_CMP_STRING;
+      in.cmp = ORCGPU_PRED_EQ;
+      in.lit_off = out.lits.size();
+      in.lit_len = (uint32_t)ne;
+      out.lits.insert(out.lits.end(), pat.bytes.begin(), pat.bytes.end());
+      out.prog.push_back(in);
+      return ORCGPU_OK;
+    }
+    std::vector<uint32_t> part_first, part_len;
+    std::vector<uint8_t> bytes, ones;
+    bool any_one = false;
+    for (size_t k = 0; k < ne;) {
+      if (pat.kinds[k] == LIKE_EL_ANY) {
+        k++;
+        continue;
+      }
+      part_first.push_back((uint32_t)bytes.size());
+      for (; k < ne && pat.kinds[k] != LIKE_EL_ANY; k++) {
+        bytes.push_back(pat.bytes[k]);
+        ones.push_back(pat.kinds[k] == LIKE_EL_ONE);
+        any_one |= pat.kinds[k] == LIKE_EL_ONE;
+      }
+      part_len.push_back((uint32_t)bytes.size() - part_first.back());
+    }
+    const uint32_t np = (uint32_t)part_first.size();
+    if (np > kLikeMaxParts)
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the LIKE pattern for column '%s' has more than %lld parts between its %% signs", n.column, kLikeMaxParts);
+    const uint32_t flags = (pat.kinds[0] != LIKE_EL_ANY ? LIKE_ANCHOR_START : 0) | (pat.kinds[ne - 1] != LIKE_EL_ANY ? LIKE_ANCHOR_END : 0);
+    uint32_t shape = LIKE_GENERAL;
+    if (!np) shape = LIKE_ALL;
+    else if (np == 1 && !any_one) shape = flags == LIKE_ANCHOR_START ? LIKE_PREFIX : flags == LIKE_ANCHOR_END ? LIKE_SUFFIX : flags == 0 ? LIKE_CONTAINS : LIKE_GENERAL;
+    in.op = FOP_LIKE;
+    in.cmp = shape;
+    if (shape != LIKE_ALL) {
+      in.i = n_like++;  // its plane of match bits
+      while (out.lits.size() & 3) out.lits.push_back(0);
+      in.lit_off = out.lits.size();
+      std::vector<uint32_t> words = {shape, flags, np, (uint32_t)bytes.size()};
+      for (uint32_t p = 0; p < np; p++) {
+        words.push_back(part_first[p]);
+        words.push_back(part_len[p]);
+      }
+      for (uint32_t w : words)
+        for (int b = 0; b < 4; b++) out.lits.push_back((uint8_t)(w >> (8 * b)));
+      out.lits.insert(out.lits.end(), bytes.begin(), bytes.end());
+      out.lits.insert(out.lits.end(), ones.begin(), ones.end());
+      in.lit_len = (uint32_t)(out.lits.size() - in.lit_off);
+    }
+    out.prog.push_back(in);
+    return ORCGPU_OK;
+  }
+  long long n_like = 0;  // LIKE leaves with a mask plane so far
 };
 
 // ORCGPU_OK, or the status a reader with this filter ends with (out.err says why).  names[k] / kinds[k]: column k.

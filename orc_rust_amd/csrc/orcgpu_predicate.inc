@@ -2,6 +2,7 @@
 // filters (bloom_filter.rs), evaluate_predicate (row_group_filter.rs:50-620), RowSelection::from_row_group_filter
 // (row_selection.rs:348-392).  The reader (orcgpu_reader.inc) turns the outcome into the row groups it reads.
 #include "orcgpu_decimal.inc"
+#include "orcgpu_like.inc"
 namespace orcgpu_host {
 
 // ColumnStatistics of one row group (statistics.rs:115-200): TryFrom picks the first typed message present
@@ -399,6 +400,35 @@ struct PredEval {
       result[g] = !st.present ? 1 : (is_null ? st.has_null : st.number_of_values > 0);
     }
   }
+  // A LIKE leaf (ORCGPU_PRED_LIKE; the reference has none) is a sound "might match" and never fails the evaluation -- a malformed
+  // pattern is the row filter's to report.  Not under a NOT, on String statistics: a pattern without a wildcard is EQ on its
+  // unescaped bytes, Bloom filter included; one with the literal prefix p in front of its first wildcard can only match values in
+  // [p, succ(p)), so the group is kept iff its upper bound >= p and its lower bound < succ(p) (truncated bounds are still bounds;
+  // p all 0xFF: the first test alone).  Everything else keeps every group.
+  void like(const PredNode& n, bool neg, std::vector<uint8_t>& result) {
+    if (neg || n.value_is_null || n.value_type != ORCGPU_PV_UTF8 || n.i < 0 || n.i > 127) return;
+    const ColumnGroups* c = nullptr;
+    for (size_t k = 0; k < names.size() && !c; k++)
+      if (names[k] == n.column) c = &cols[k];
+    LikePattern pat;
+    if (!c || !like_unescape(n.s.data(), n.s.size(), (int)n.i, pat)) return;
+    const bool exact = pat.wildcard_free();
+    const std::string p = pat.prefix();
+    if (!exact && p.empty()) return;
+    std::string succ;
+    const bool has_succ = like_prefix_succ(p, succ);
+    PredNode lit = n;  // (what the EQ rule and the Bloom filter are asked)
+    lit.s = p;
+    for (size_t g = 0; g < result.size() && g < c->stats.size(); g++) {
+      const GroupStats& st = c->stats[g];
+      const bool strings = st.present && st.kind == GroupStats::STRING;
+      if (st.present && !strings) continue;
+      if (exact) {
+        if (strings && !cmp_string(st.smin, st.smax, ORCGPU_PRED_EQ, p, st.exact_min, st.exact_max)) result[g] = 0;
+        else if (!bloom_match(c->blooms.empty() ? nullptr : &c->blooms[g], ORCGPU_PRED_EQ, lit)) result[g] = 0;
+      } else if (strings && (st.smax < p || (has_succ && !(st.smin < succ)))) result[g] = 0;
+    }
+  }
   // one subtree in pre-order; returns the index behind it.  `neg`: under a NOT (pushed down as the reference does)
   size_t eval(size_t at, bool neg, std::vector<uint8_t>& result) {
     if (at >= nodes.size() || failed) {
@@ -406,6 +436,10 @@ struct PredEval {
       return nodes.size();
     }
     const PredNode& n = nodes[at];
+    if (n.op == ORCGPU_PRED_LIKE) {
+      like(n, neg, result);
+      return at + 1;
+    }
     if (n.op <= ORCGPU_PRED_GE) {
       comparison(n, neg ? negate(n.op) : n.op, result);
       return at + 1;

@@ -839,7 +839,7 @@ int reader_compile_filter(orcgpu_reader* rd) {
   if (rc) return rc;
   // a comparison on a dictionary-output column would have to be evaluated on the entries: refused, by name, before anything is read
   for (auto& in : rd->filter_plan.prog) {
-    if (in.op > FOP_CMP_DEC128 || in.col >= names.size()) continue;
+    if (!fop_reads_values(in.op) || in.col >= names.size()) continue;
     size_t root = 0;
     for (size_t k = 0; k < rd->col_ids.size(); k++) {
       if (rd->col_parent[k]) continue;

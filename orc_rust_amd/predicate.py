@@ -6,6 +6,7 @@ import datetime
 import decimal
 
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL, AND, OR, NOT = range(11)
+LIKE = 16  # (11 .. 15 are unknown ops)
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
 _EPOCH = datetime.datetime(1970, 1, 1)
 
@@ -80,10 +81,12 @@ class PredicateValue:
 
 
 class Predicate:
-    """Predicate::{Comparison, IsNull, IsNotNull, And, Or, Not} with the reference's constructors (predicate.rs:98-180)."""
+    """Predicate::{Comparison, IsNull, IsNotNull, And, Or, Not} with the reference's constructors (predicate.rs:98-180), and
+    this library's own LIKE leaf (like / not_like / starts_with / ends_with / contains)."""
 
     def __init__(self, op, column=None, value=None, children=()):
         self.op, self.column, self.value, self.children = op, column, value, list(children)
+        self.escape = None  # LIKE: the escape character
 
     @classmethod
     def comparison(cls, column, op, value):
@@ -97,6 +100,46 @@ class Predicate:
     gte = classmethod(lambda cls, c, v: cls(GE, c, v))
     is_null = classmethod(lambda cls, c: cls(IS_NULL, c))
     is_not_null = classmethod(lambda cls, c: cls(IS_NOT_NULL, c))
+
+    @classmethod
+    def like(cls, column, pattern, escape=None):
+        """SQL LIKE on a String / Varchar / Char column (ORCGPU_PRED_LIKE, this library's own): `%` any run of bytes, `_` one code
+        point, `escape` (one ASCII character, or None) makes the pattern character behind it a literal.  pattern: str (encoded to
+        UTF-8), bytes, or None for the NULL pattern.  The whole value must match."""
+        if escape is not None and not (isinstance(escape, str) and len(escape) == 1 and 0 < ord(escape) < 128):
+            raise ValueError("LIKE escape: one ASCII character or None, got %r" % (escape,))
+        if pattern is not None and not isinstance(pattern, (str, bytes, bytearray)):
+            raise ValueError("LIKE pattern: a str, bytes or None, got %r" % (pattern,))
+        p = cls(LIKE, column, PredicateValue(PV_UTF8, pattern))
+        p.escape = escape
+        return p
+
+    @classmethod
+    def not_like(cls, column, pattern, escape=None):
+        return cls.not_(cls.like(column, pattern, escape))
+
+    @staticmethod
+    def _like_literal(text):
+        """text with `%`, `_` and the escape character itself escaped by a backslash"""
+        if isinstance(text, str):
+            return text.replace("\\", "\\\\").replace("%", "\\%").replace("_", "\\_")
+        return bytes(text).replace(b"\\", b"\\\\").replace(b"%", b"\\%").replace(b"_", b"\\_")
+
+    @classmethod
+    def starts_with(cls, column, text):
+        lit = cls._like_literal(text)
+        return cls.like(column, lit + ("%" if isinstance(lit, str) else b"%"), escape="\\")
+
+    @classmethod
+    def ends_with(cls, column, text):
+        lit = cls._like_literal(text)
+        return cls.like(column, ("%" if isinstance(lit, str) else b"%") + lit, escape="\\")
+
+    @classmethod
+    def contains(cls, column, text):
+        lit = cls._like_literal(text)
+        pc = "%" if isinstance(lit, str) else b"%"
+        return cls.like(column, pc + lit + pc, escape="\\")
 
     @classmethod
     def and_(cls, predicates):
@@ -140,6 +183,8 @@ class Predicate:
                         n.f = float(v.value)
                     else:
                         n.i = int(v.value)
+            if p.op == LIKE:
+                n.i = ord(p.escape) if p.escape else 0
             out.append(n)
             for c in p.children:
                 walk(c)
