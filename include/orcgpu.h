@@ -429,7 +429,14 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_IS_NULL = 6, ORCGPU_PRED_IS_NOT_NULL = 7, ORCGPU_PRED_AND = 8, ORCGPU_PRED_OR = 9, ORCGPU_PRED_NOT = 10,
        /* (11 .. 15: unknown ops) */
        ORCGPU_PRED_LIKE = 16 /* SQL LIKE, this library's own: a leaf with column, value_type = ORCGPU_PV_UTF8, s / s_len = the pattern,
-                                i = the escape byte (0: none, else 1 .. 127), value_is_null = the NULL pattern; see orcgpu_result_filter */ };
+                                i = the escape byte (0: none, else 1 .. 127), value_is_null = the NULL pattern; see orcgpu_result_filter */,
+       ORCGPU_PRED_IN = 17 /* SQL IN, this library's own: a leaf with column; n_children counts the ORCGPU_PRED_LITERAL nodes that
+                              follow it in pre-order, its list.  There is no NOT IN: put ORCGPU_PRED_NOT above the leaf */,
+       ORCGPU_PRED_LITERAL = 18 /* one value of an IN list: column = NULL, n_children = 0; value_type, value_is_null, i, f, s, s_len as
+                                   in a comparison node.  Anywhere but under an ORCGPU_PRED_IN it is ORCGPU_INVALID_ARGUMENT */ };
+/* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
+#define ORCGPU_IN_MAX_VALUES 65536
+#define ORCGPU_IN_MAX_BYTES (4u << 20)
 /* What a LIKE pattern may hold after unescaping: bytes (wildcards included) and non-empty parts between its `%` signs.  The
  * compiled pattern then fits the matcher kernel's LDS. */
 #define ORCGPU_LIKE_MAX_BYTES 1024
@@ -443,7 +450,7 @@ enum { ORCGPU_PV_BOOLEAN = 0, ORCGPU_PV_INT8 = 1, ORCGPU_PV_INT16 = 2, ORCGPU_PV
        ORCGPU_PV_FLOAT64 = 6, ORCGPU_PV_UTF8 = 7, ORCGPU_PV_DECIMAL128 = 8, ORCGPU_PV_TIMESTAMP_NS = 9 };
 typedef struct {
   int32_t op;            /* ORCGPU_PRED_*                                                                 */
-  uint32_t n_children;   /* AND / OR                                                                      */
+  uint32_t n_children;   /* AND / OR; IN: the literal nodes of its list                                    */
   const char* column;    /* comparisons and null tests: the name of a projected root column               */
   int32_t value_type;    /* comparisons: ORCGPU_PV_*                                                       */
   int32_t value_is_null; /* ... Some / None                                                                */
@@ -506,6 +513,22 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     held in the matcher kernel's LDS).  A column read as a dictionary column: ORCGPU_UNSUPPORTED, as for a comparison.  Each
  *     message names the column.  The pattern is matched by a kernel of its own (filter_like_kernel) in front of the evaluation,
  *     on the same stream: no further host wait.
+ *   - ORCGPU_PRED_IN: x IN (v1, ..., vk) is exactly OR(x = v1, ..., x = vk) under the rules above, and everything follows from that.
+ *     A null row is UNKNOWN.  The empty list is FALSE for every row, null rows included (an OR of no children).  A NULL literal in
+ *     the list (value_is_null) turns every non-match into UNKNOWN: NOT IN over a list with a NULL keeps nothing, a list of nothing
+ *     but NULLs is UNKNOWN everywhere.  Duplicates are harmless.  Every literal is checked against the column as the literal of an
+ *     EQ is, with the same statuses and messages; the literal kinds may be mixed within what the column takes.  Float columns
+ *     compare as double: a NaN literal equals no row, -0.0 and 0.0 are one key, a Float32 literal is rounded through float first.
+ *     Decimal128 and TimestampNs literals are brought to the column's scale / unit as for EQ; one that does not land on a value of
+ *     the scale / unit equals no row (FALSE on valid rows, no error).  A column read as a dictionary column, a nested column among
+ *     the columns and a Timestamp column decoded to Decimal128(38, 9): ORCGPU_UNSUPPORTED, as for a comparison.  More than
+ *     ORCGPU_IN_MAX_VALUES literal nodes or more than ORCGPU_IN_MAX_BYTES bytes of Utf8 literals in one list: ORCGPU_UNSUPPORTED
+ *     (the message names the column).  A literal node anywhere but under an IN, an IN child that is not a literal node, a literal
+ *     node with children and a node list that ends inside the list: ORCGPU_INVALID_ARGUMENT.  The list counts toward
+ *     ORCGPU_FILTER_MAX_DEPTH as the leaf alone.  One distinct key (and no NULL) is compiled to the comparison EQ.  Otherwise the
+ *     keys go into a hash set (open addressing, linear probing) that a kernel of its own (filter_in_kernel) probes per row in front
+ *     of the evaluation, on the same stream: from LDS when the table is at most 32 KiB, else where it lies in global memory; no
+ *     further host wait.  The cost per row does not grow with the list.
  *   - A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
  *   - A leaf naming a column that is not there, a leaf without a name, an unknown op, a node list that ends inside a node's
  *     children or goes on behind the root, and a predicate nested deeper than ORCGPU_FILTER_MAX_DEPTH levels (a leaf alone is

@@ -13,6 +13,9 @@
 //                         64 input rows like `keep`; the evaluation forms T = match & valid, F = ~match & valid from it.  The
 //                         compiled pattern (parts of literal bytes and `_` marks between the `%`) lies in LDS; no backtracking;
 //                         a lane per short value, the wavefront on 64 candidate starts at once for a long one.
+//   filter_in_kernel      likewise for IN leaves: per leaf a plane of "the row is valid and its key is in the list", from a hash
+//                         set the host has built (filter_program.h): staged in LDS up to 32 KiB, probed in global memory above;
+//                         a lane per value, so a row costs one probe however long the list is.
 //   (enc_scan)            exclusive scan of the popcounts: the output row of every word's first kept row.
 //   filter_place_kernel   every kept row writes its stripe row at its output row: src_rows[], the gather's index list.
 //   filter_count_kernel   per (output batch, column): null count and string bytes -- what the host needs to lay the output out
@@ -219,6 +222,145 @@ filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
   }
 }
 
+// ---- IN: the hash set of filter_program.h ----
+struct InTable {
+  uint32_t kind, n_slots, min_len, max_len, bytes;  // n_slots = 0: no usable table, nothing matches
+  const unsigned long long* occ;
+  const uint8_t* slots;
+  const uint8_t* base;  // strings: key offsets count from here, and stay below `bytes`
+};
+// The header, checked against the table's bytes: a table whose parts do not fit is treated as empty.
+__device__ __forceinline__ InTable in_table(const uint8_t* tab, uint32_t bytes) {
+  InTable t = {};
+  t.base = tab;
+  if (bytes < kInHeaderBytes) return t;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(tab);
+  t.kind = h[0];
+  t.n_slots = h[1];
+  t.min_len = h[3];
+  t.max_len = h[4];
+  t.bytes = bytes;
+  t.base = tab;
+  const uint64_t occ_bytes = ((uint64_t)t.n_slots + 63) / 64 * 8, slot_bytes = t.kind == IN_KEY_I64 ? 8 : 16;
+  if (t.kind > IN_KEY_STRING || t.n_slots < 2 || (t.n_slots & (t.n_slots - 1)) || kInHeaderBytes + occ_bytes + (uint64_t)t.n_slots * slot_bytes > bytes) t.n_slots = 0;
+  t.occ = reinterpret_cast<const unsigned long long*>(tab + kInHeaderBytes);
+  t.slots = tab + kInHeaderBytes + occ_bytes;
+  return t;
+}
+// Linear probing from the hash's own slot: at most n_slots steps, ended by the key or by a free slot.
+__device__ __forceinline__ bool in_probe_i64(const InTable& t, unsigned long long key) {
+  const uint32_t mask = t.n_slots - 1;
+  uint32_t s = in_hash_i64(key) & mask;
+  for (uint32_t step = 0; step < t.n_slots; step++, s = (s + 1) & mask) {
+    if (!((t.occ[s >> 6] >> (s & 63)) & 1)) return false;
+    if (reinterpret_cast<const unsigned long long*>(t.slots)[s] == key) return true;
+  }
+  return false;
+}
+__device__ __forceinline__ bool in_probe_dec128(const InTable& t, unsigned long long lo, unsigned long long hi) {
+  const uint32_t mask = t.n_slots - 1;
+  uint32_t s = in_hash_dec128(lo, hi) & mask;
+  for (uint32_t step = 0; step < t.n_slots; step++, s = (s + 1) & mask) {
+    if (!((t.occ[s >> 6] >> (s & 63)) & 1)) return false;
+    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(t.slots) + 2 * (uint64_t)s;
+    if (k[0] == lo && k[1] == hi) return true;
+  }
+  return false;
+}
+// p[0, len): every byte load of the value is bounded by its length, every one of a key by the table's bytes
+__device__ __forceinline__ bool in_probe_string(const InTable& t, const uint8_t* p, uint32_t len) {
+  const uint32_t mask = t.n_slots - 1, h = in_hash_bytes(p, len);
+  uint32_t s = h & mask;
+  for (uint32_t step = 0; step < t.n_slots; step++, s = (s + 1) & mask) {
+    if (!((t.occ[s >> 6] >> (s & 63)) & 1)) return false;
+    const uint32_t* k = reinterpret_cast<const uint32_t*>(t.slots) + 4 * (uint64_t)s;
+    if (k[0] != h || k[1] != len) continue;
+    const uint32_t off = k[2];
+    if (off > t.bytes || len > t.bytes - off) continue;
+    const uint8_t* q = t.base + off;
+    uint32_t x = 0;
+    while (x < len && p[x] == q[x]) x++;
+    if (x == len) return true;
+  }
+  return false;
+}
+
+// One plane of an IN leaf, probed in the table `tab` (LDS or global memory: the caller's two instantiations)
+__device__ __forceinline__ void filter_in_plane(const uint8_t* tab, uint32_t tab_bytes, const FilterCol& c, const SelBatch* segs, const unsigned long long* seg_first,
+                                                uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* plane) {
+  const InTable t = in_table(tab, tab_bytes);
+  // (the key kind the table was built for must be the one the column is decoded to: the host has checked it; a table that does
+  // not fit its column matches nothing)
+  const bool fits = t.n_slots && (c.kind == FKIND_STRING ? t.kind == IN_KEY_STRING : c.kind == FKIND_DEC128 ? t.kind == IN_KEY_DEC128
+                                                                                    : (c.kind == FKIND_INT || c.kind == FKIND_FLOAT) && t.kind == IN_KEY_I64);
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t n_words = (n_in + 63) / 64;
+  for (uint64_t w = (uint64_t)blockIdx.x * 4 + wave; w < n_words; w += (uint64_t)gridDim.x * 4) {
+    const uint64_t j = w * 64 + lane;
+    const bool live = j < n_in;
+    const uint64_t row = live ? filter_src_row(segs, seg_first, n_segs, j) : 0;
+    const uint64_t u = row / B;
+    const uint32_t l = (uint32_t)(row % B);
+    bool m = false;
+    if (fits && live && filter_valid(c, u, l, W)) {
+      if (c.kind == FKIND_INT) {
+        long long v;
+        if (c.width == 1) v = reinterpret_cast<const int8_t*>(c.values)[row];
+        else if (c.width == 2) v = reinterpret_cast<const int16_t*>(c.values)[row];
+        else if (c.width == 4) v = reinterpret_cast<const int32_t*>(c.values)[row];
+        else v = reinterpret_cast<const long long*>(c.values)[row];
+        m = in_probe_i64(t, (unsigned long long)v);
+      } else if (c.kind == FKIND_FLOAT) {
+        const double v = c.width == 4 ? (double)reinterpret_cast<const float*>(c.values)[row] : reinterpret_cast<const double*>(c.values)[row];
+        m = v == v && in_probe_i64(t, in_float_key(v));  // (a NaN row equals no key)
+      } else if (c.kind == FKIND_DEC128) {
+        const uint4 q = reinterpret_cast<const uint4*>(c.values)[row];
+        m = in_probe_dec128(t, ((unsigned long long)q.y << 32) | q.x, ((unsigned long long)q.w << 32) | q.z);
+      } else {
+        const int32_t* o = c.offsets + u * (B + 1) + l;
+        const uint32_t a = (uint32_t)o[0], len = (uint32_t)o[1] - a;
+        // (a length no key has: a non-match from the offsets alone, no byte is loaded)
+        if (len >= t.min_len && len <= t.max_len) m = in_probe_string(t, c.chars + c.char_base[u] + a, len);
+      }
+    }
+    const unsigned long long M = __ballot(m);
+    if (lane == 0) plane[w] = M;
+  }
+}
+
+// The IN leaves' set membership, in front of filter_eval_kernel on its stream, with the grid of filter_like_kernel.  blockIdx.y = a
+// mask plane (the IN and the LIKE leaves of a program number their planes together; a block whose plane is not an IN leaf's
+// leaves at once); a wavefront trip is one 64-bit word of the plane, laid out like `keep`: bit = the row is valid and its key is
+// in the set (null rows and rows past n_in: 0).  A table of up to kInLdsBytes is staged in LDS once per workgroup, a larger one is
+// probed where it lies: 65536 int64 keys are 1 MiB of slots, which an XCD's L2 holds.  One lane per value, strings included.
+extern "C" __global__ void __launch_bounds__(256)
+filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                 const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* masks) {
+  __shared__ unsigned long long tab_s[kInLdsBytes / 8];
+  __shared__ uint32_t insn_s;
+  if (threadIdx.x == 0) {
+    uint32_t at = n_insn;
+    for (uint32_t k = 0; k < n_insn; k++)
+      if (prog[k].op == FOP_IN && !(prog[k].cmp & IN_NO_TABLE) && prog[k].i == (long long)blockIdx.y) at = k;
+    insn_s = at;
+  }
+  __syncthreads();
+  if (insn_s >= n_insn) return;
+  const FilterInsn in = prog[insn_s];
+  const FilterCol c = cols[in.col];
+  unsigned long long* plane = masks + (uint64_t)blockIdx.y * ((n_in + 63) / 64);
+  // (lit_off and lit_len are multiples of 8 and the pool starts 256-byte aligned: whole 8-byte words)
+  const unsigned long long* g = reinterpret_cast<const unsigned long long*>(lits + in.lit_off);
+  const uint32_t bytes = in.lit_len & ~7u;
+  if (bytes >= kInHeaderBytes && bytes <= kInLdsBytes) {
+    for (uint32_t x = threadIdx.x; x < bytes / 8; x += 256) tab_s[x] = g[x];
+    __syncthreads();
+    filter_in_plane(reinterpret_cast<const uint8_t*>(tab_s), bytes, c, segs, seg_first, n_segs, n_in, B, W, plane);
+  } else {
+    filter_in_plane(reinterpret_cast<const uint8_t*>(g), bytes < kInHeaderBytes ? 0 : bytes, c, segs, seg_first, n_segs, n_in, B, W, plane);
+  }
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
                    const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* keep,
@@ -311,6 +453,20 @@ filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
         const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : like_masks[(uint64_t)in.i * n_words + w];
         T = match & valid_m;
         F = ~match & valid_m;
+      } else if (in.op == FOP_IN) {
+        // the trip's membership bits are there already (filter_in_kernel); a Boolean column and a list no key of which can equal a
+        // row have no plane.  With a NULL literal in the list a row that matches no key is UNKNOWN, not FALSE.
+        const FilterCol c = cols[in.col];
+        const bool valid = live && filter_valid(c, u, l, W);
+        const unsigned long long valid_m = __ballot(valid);
+        unsigned long long match = 0;
+        if (!(in.cmp & IN_NO_TABLE)) match = like_masks[(uint64_t)in.i * n_words + w];
+        else if (in.cmp & (IN_BOOL_FALSE | IN_BOOL_TRUE)) {
+          const unsigned long long bits = __ballot(valid && ((reinterpret_cast<const unsigned long long*>(c.values)[u * W + (l >> 6)] >> (l & 63)) & 1));
+          match = (in.cmp & IN_BOOL_TRUE ? bits : 0ull) | (in.cmp & IN_BOOL_FALSE ? ~bits : 0ull);
+        }
+        T = match & valid_m;
+        F = in.cmp & IN_HAS_NULL ? 0ull : ~match & valid_m;
       } else if (in.op == FOP_TRUE) {
         T = live_m;
       } else if (in.op == FOP_FALSE) {

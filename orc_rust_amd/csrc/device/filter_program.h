@@ -17,17 +17,20 @@ enum {
   FOP_AND = 10,        // pops two, pushes one
   FOP_OR = 11,
   FOP_NOT = 12,
-  FOP_LIKE = 13        // String / Varchar / Char against a compiled LIKE pattern: a leaf that reads its column's values, through the
+  FOP_LIKE = 13,       // String / Varchar / Char against a compiled LIKE pattern: a leaf that reads its column's values, through the
                        // match bits filter_like_kernel leaves (cmp: LIKE_*, the pattern's shape; i: which of the program's mask planes)
+  FOP_IN = 14          // x IN (list): a leaf that reads its column's values, through the match bits filter_in_kernel leaves (cmp: IN_*
+                       // flags; i: its mask plane, numbered with the LIKE planes; lit_off / lit_len: its hash set in the literal pool;
+                       // lo: the FKIND_* its column must be decoded to)
 };
 // does this instruction read the values of column `col` (not only its validity)?
-inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op == FOP_LIKE; }
+inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op == FOP_LIKE || op == FOP_IN; }
 // FKIND_INT holds Timestamp columns decoded to int64 (seconds .. nanoseconds) as well: the host brings the literal to the unit
 enum { FKIND_INT = 0, FKIND_FLOAT = 1, FKIND_BOOL = 2, FKIND_STRING = 3, FKIND_OTHER = 4 /* fixed width, null tests only */, FKIND_DEC128 = 5 };
 
 struct FilterInsn {
   uint32_t op;       // FOP_*
-  uint32_t cmp;      // ORCGPU_PRED_EQ .. _GE; FOP_LIKE: LIKE_*
+  uint32_t cmp;      // ORCGPU_PRED_EQ .. _GE; FOP_LIKE: LIKE_*; FOP_IN: IN_* flags
   uint32_t col;      // index into the FilterCol table
   uint32_t lit_len;  // strings: bytes of the literal (FOP_LIKE: of the compiled pattern)
   long long i;       // integer / Boolean literal; Decimal128: the literal's high word (signed); FOP_LIKE: its mask plane
@@ -52,5 +55,60 @@ enum { LIKE_ANCHOR_START = 1, LIKE_ANCHOR_END = 2 };
 constexpr uint32_t kLikeMaxBytes = 1024, kLikeMaxParts = 64;
 constexpr uint32_t kLikeHeaderWords = 4;
 constexpr uint32_t kLikeBlobMax = (kLikeHeaderWords + 2 * kLikeMaxParts) * 4 + 2 * kLikeMaxBytes;
+
+// ---- the hash set of an IN leaf, as it lies in the literal pool at lit_off (8-byte aligned, lit_len bytes, a multiple of 8) ----
+//   header, 8 x uint32: key kind (IN_KEY_*), n_slots (a power of two, at least twice the keys), n_keys (distinct), the shortest and
+//     the longest key in bytes (strings), flags (IN_*), 0, 0
+//   occupancy, ceil(n_slots / 64) x uint64: bit s = slot s holds a key -- so every int64 is a legal key
+//   slots -- IN_KEY_I64: n_slots x uint64, the key (integers and Timestamps as int64; floats: the bits of the double, with
+//     -0.0 stored as 0.0 and no NaN); IN_KEY_DEC128: n_slots x {uint64 low, uint64 high}; IN_KEY_STRING: n_slots x {uint32 hash,
+//     uint32 length, uint32 offset of the key's bytes from the table's start, uint32 0}, the bytes of all keys behind the slots
+// Open addressing, linear probing: a key sits in the first free slot at or behind hash & (n_slots - 1), wrapping round.  A probe
+// ends at the key, at a free slot, or after n_slots steps: a damaged table cannot spin.  The hash functions are the ones below,
+// for the host that builds and the kernel that probes.
+enum { IN_KEY_I64 = 0, IN_KEY_DEC128 = 1, IN_KEY_STRING = 2 };
+enum {
+  IN_HAS_NULL = 1,    // the list holds a NULL literal: a row that matches no key is UNKNOWN, not FALSE
+  IN_NO_TABLE = 2,    // no key can equal a row, or a Boolean column: no hash set, no mask plane, nothing for filter_in_kernel
+  IN_BOOL_FALSE = 4,  // Boolean column (with IN_NO_TABLE): false is in the list
+  IN_BOOL_TRUE = 8    // ... true is
+};
+constexpr uint32_t kInHeaderBytes = 32;
+constexpr uint32_t kInLdsBytes = 32768;  // a table of up to this many bytes is staged in LDS, a larger one is probed in global memory
+#if defined(__HIPCC__)
+#define FILTER_HD __host__ __device__
+#else
+#define FILTER_HD
+#endif
+FILTER_HD inline unsigned long long in_mix64(unsigned long long k) {  // (the finaliser of MurmurHash3)
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+FILTER_HD inline uint32_t in_hash_i64(unsigned long long key) { return (uint32_t)in_mix64(key); }
+FILTER_HD inline uint32_t in_hash_dec128(unsigned long long lo, unsigned long long hi) { return (uint32_t)in_mix64(lo ^ in_mix64(hi)); }
+FILTER_HD inline uint32_t in_hash_bytes(const uint8_t* p, uint32_t n) {  // FNV-1a, then the 32-bit finaliser of MurmurHash3
+  uint32_t h = 2166136261u;
+  for (uint32_t k = 0; k < n; k++) h = (h ^ p[k]) * 16777619u;
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+// a float column's key: the double's bits, -0.0 as 0.0 (the caller has left NaN out: it equals nothing)
+FILTER_HD inline unsigned long long in_float_key(double v) {
+  if (v == 0.0) v = 0.0;
+  union {
+    double d;
+    unsigned long long u;
+  } x;
+  x.d = v;
+  return x.u;
+}
 
 constexpr uint32_t kFilterStack = 64;  // = ORCGPU_FILTER_MAX_DEPTH: a predicate of depth d needs at most d slots of the evaluation stack

@@ -67,10 +67,15 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   const uint64_t o_sums = t.take(((n_words + 2047) / 2048) * 8 + 16);
   const uint64_t n_counters = 1 + 2ull * nc * nb_max;  // the kept row count, then null counts and string bytes [column][batch]
   const uint64_t o_counters = t.take(n_counters * 8 + 16), o_rows = t.take(n_in * 4 + 16);
-  // (the LIKE leaves' planes of match bits, laid out like `keep`: part of this workspace, which only ever grows)
-  uint32_t n_like = 0;
-  for (auto& in : plan.prog) n_like += in.op == FOP_LIKE && in.cmp != LIKE_ALL;
-  const uint64_t o_like = t.take((uint64_t)n_like * n_words * 8 + 16);
+  // (the LIKE and IN leaves' planes of match bits, numbered together and laid out like `keep`: part of this workspace, which
+  // only ever grows)
+  uint32_t n_like = 0, n_set = 0;
+  for (auto& in : plan.prog) {
+    n_like += in.op == FOP_LIKE && in.cmp != LIKE_ALL;
+    n_set += in.op == FOP_IN && !(in.cmp & IN_NO_TABLE);
+  }
+  const uint32_t n_planes = n_like + n_set;
+  const uint64_t o_like = t.take((uint64_t)n_planes * n_words * 8 + 16);
   // (the second upload, behind the wait: the gather's jobs and the char bases of the output batches)
   const uint64_t o_jobs = t.take((uint64_t)nc * sizeof(FilterGatherJob) + 16), o_obase = t.take((uint64_t)nc * nb_max * 8 + 16);
   if (!r->filt_tmp.ensure(t.off + kAlign)) {
@@ -122,7 +127,7 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
       else set_err(ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", r->cols[in.col].column_id);
       return ORCGPU_UNSUPPORTED;
     }
-    const uint32_t want = in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : in.op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
+    const uint32_t want = in.op == FOP_IN ? (uint32_t)in.lo : in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : in.op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
     if (in.col >= nc || fcols[in.col].kind != want) {
       set_err(ctx, "row filter: column %u is not decoded to the type its comparison needs", in.col < nc ? r->cols[in.col].column_id : in.col);
       return ORCGPU_MISMATCHED_SCHEMA;
@@ -140,7 +145,12 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
     HIP_TRY(ctx, hipMemsetAsync(d_counters, 0, n_counters * 8, st));
     const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((n_words + 3) / 4, 16384);
     if (n_like) {  // the matcher first: the evaluation reads its bits
-      hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_like), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
+      hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_planes), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
+                         reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W, reinterpret_cast<unsigned long long*>(X + o_like));
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_set) {  // ... and the set membership of the IN leaves (a block of either kernel whose plane is the other's leaves at once)
+      hipLaunchKernelGGL(filter_in_kernel, dim3(eval_blocks, n_planes), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
                          reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W, reinterpret_cast<unsigned long long*>(X + o_like));
       HIP_TRY(ctx, hipGetLastError());
     }

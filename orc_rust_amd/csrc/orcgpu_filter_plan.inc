@@ -2,8 +2,8 @@
 // compiles this very text under AddressSanitizer + UBSan): a predicate as the pre-order node list of include/orcgpu.h ->
 // the post-order program filter_eval_kernel runs (device/filter_program.h).  Names become column indices, the type table
 // of orcgpu_result_filter is applied, Decimal128 and TimestampNs literals are brought to the column's own scale / unit, LIKE
-// patterns are cut into the parts filter_like_kernel matches (tests/hostcheck/filter_plan_like_check.cpp), and the depth is
-// bounded.
+// patterns are cut into the parts filter_like_kernel matches (tests/hostcheck/filter_plan_like_check.cpp), IN lists become the
+// hash sets filter_in_kernel probes (orcgpu_in.inc, tests/hostcheck/filter_plan_in_check.cpp), and the depth is bounded.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -11,10 +11,12 @@
 
 #include "device/filter_program.h"
 #include "orcgpu_decimal.inc"
+#include "orcgpu_in.inc"
 #include "orcgpu_like.inc"
 
 namespace orcgpu_host {
 
+static_assert(ORCGPU_PRED_IN == 17 && ORCGPU_PRED_LITERAL == 18 && ORCGPU_IN_MAX_VALUES == 65536, "the IN leaf of include/orcgpu.h");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
 
 struct FilterPlan {
@@ -58,12 +60,12 @@ struct FilterCompiler {
   // Decimal (|v| < 10^38 < 2^127) equals a clamp, so EQ is never TRUE and the order comparisons are right as they stand.
   // d < 0: q = floor(literal / 10^-d); with a remainder no row equals the literal: EQ / NE are asked of the upper clamp (still
   // UNKNOWN on a null row), LT / LE become LE q, GT / GE become GT q.
-  int decimal(const orcgpu_predicate_node& n, uint32_t col, FilterInsn& in) {
+  int decimal(const orcgpu_predicate_node& n, const char* column, uint32_t col, FilterInsn& in) {
     i128 lit = 0;
     if (!dec_literal(n.s, n.s_len, n.i, lit))
-      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the Decimal128 literal for column '%s' is malformed (16 bytes, a scale of 0 .. 38, a magnitude below 10^38)", n.column);
+      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the Decimal128 literal for column '%s' is malformed (16 bytes, a scale of 0 .. 38, a magnitude below 10^38)", column);
     const int col_scale = params ? params[col] : 0;
-    if (col_scale < 0 || col_scale > kDecMaxDigits) return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' has the scale %lld", n.column, col_scale);
+    if (col_scale < 0 || col_scale > kDecMaxDigits) return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' has the scale %lld", column, col_scale);
     const int d = col_scale - (int)n.i;
     i128 L = 0;
     if (d >= 0) {
@@ -83,11 +85,11 @@ struct FilterCompiler {
   // A TimestampNs literal -> (op', literal') in the unit the column is decoded to: q = floor(ns / unit), as above.  The literal is
   // in the finest unit, so it is only ever divided and nothing can leave int64.  Every int64 is a value a row may hold, hence the
   // constant cases are asked of INT64_MIN: LT is TRUE for no valid row, GE for every one, both UNKNOWN on a null row.
-  int timestamp(const orcgpu_predicate_node& n, uint32_t col, FilterInsn& in) {
+  int timestamp(const orcgpu_predicate_node& n, const char* column, uint32_t col, FilterInsn& in) {
     static const int64_t per_unit[4] = {1000000000, 1000000, 1000, 1};  // seconds, milli-, micro-, nanoseconds
     const int unit = params ? params[col] : 3;
     if (unit < 0 || unit > 3)
-      return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is decoded to Decimal128(38, 9), not to an int64 unit: a comparison on it is not supported", n.column);
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is decoded to Decimal128(38, 9), not to an int64 unit: a comparison on it is not supported", column);
     const int64_t p = per_unit[unit];
     int64_t q = n.i / p, r = n.i % p;
     if (r < 0) {  // (C++ truncates toward zero; instants before 1970 need the floor)
@@ -101,6 +103,55 @@ struct FilterCompiler {
       } else in.cmp = in.cmp == ORCGPU_PRED_LT || in.cmp == ORCGPU_PRED_LE ? ORCGPU_PRED_LE : ORCGPU_PRED_GT;
     }
     in.i = q;
+    return ORCGPU_OK;
+  }
+  // The type table of orcgpu_result_filter: may the literal of node `n` be compared with column `col` (named `column`)?  Sets the
+  // instruction's class and, for the plain kinds, its literal.  A comparison and every literal of an IN list go through here.
+  int literal(const orcgpu_predicate_node& n, const char* column, uint32_t col, FilterInsn& in) {
+    const int kind = kinds[col], vt = n.value_type;
+    const bool int_lit = vt == ORCGPU_PV_INT8 || vt == ORCGPU_PV_INT16 || vt == ORCGPU_PV_INT32 || vt == ORCGPU_PV_INT64;
+    bool ok = false;
+    switch (kind) {
+      case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG:
+        ok = int_lit;
+        in.op = FOP_CMP_INT;
+        in.i = n.i;
+        break;
+      case ORCGPU_T_DATE:
+        ok = vt == ORCGPU_PV_INT32 || vt == ORCGPU_PV_INT64;
+        in.op = FOP_CMP_INT;
+        in.i = n.i;
+        break;
+      case ORCGPU_T_FLOAT: case ORCGPU_T_DOUBLE:
+        ok = vt == ORCGPU_PV_FLOAT32 || vt == ORCGPU_PV_FLOAT64;
+        in.op = FOP_CMP_FLOAT;
+        in.f = vt == ORCGPU_PV_FLOAT32 ? (double)(float)n.f : n.f;
+        break;
+      case ORCGPU_T_BOOLEAN:
+        ok = vt == ORCGPU_PV_BOOLEAN;
+        in.op = FOP_CMP_BOOL;
+        in.i = n.i != 0;
+        break;
+      case ORCGPU_T_STRING: case ORCGPU_T_VARCHAR: case ORCGPU_T_CHAR: case ORCGPU_T_BINARY:
+        ok = vt == ORCGPU_PV_UTF8;
+        in.op = FOP_CMP_STRING;
+        break;
+      case ORCGPU_T_DECIMAL:
+        if (vt != ORCGPU_PV_DECIMAL128)
+          return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' is compared with Decimal128 literals only (value type %lld is not supported)", column, vt);
+        ok = true;
+        in.op = FOP_CMP_DEC128;
+        break;
+      case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT:
+        if (vt != ORCGPU_PV_TIMESTAMP_NS)
+          return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is compared with TimestampNs literals only (value type %lld is not supported)", column, vt);
+        ok = true;
+        in.op = FOP_CMP_INT;
+        break;
+      default:
+        return fail(ORCGPU_UNSUPPORTED, "row filter: column '%s' of ORC type kind %lld cannot be compared", column, kind);
+    }
+    if (!ok) return fail(ORCGPU_MISMATCHED_SCHEMA, "row filter: column '%s' cannot be compared with a literal of value type %lld", column, vt);
     return ORCGPU_OK;
   }
   // the node at `at` and everything below it; `at` then stands behind them
@@ -142,61 +193,19 @@ struct FilterCompiler {
         uint32_t col = 0;
         const int rc = column(n, col);
         if (rc) return rc;
-        const int kind = kinds[col], vt = n.value_type;
-        const bool int_lit = vt == ORCGPU_PV_INT8 || vt == ORCGPU_PV_INT16 || vt == ORCGPU_PV_INT32 || vt == ORCGPU_PV_INT64;
+        const int kind = kinds[col];
         FilterInsn in{};
         in.cmp = (uint32_t)n.op;
         in.col = col;
-        bool ok = false;
-        switch (kind) {
-          case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG:
-            ok = int_lit;
-            in.op = FOP_CMP_INT;
-            in.i = n.i;
-            break;
-          case ORCGPU_T_DATE:
-            ok = vt == ORCGPU_PV_INT32 || vt == ORCGPU_PV_INT64;
-            in.op = FOP_CMP_INT;
-            in.i = n.i;
-            break;
-          case ORCGPU_T_FLOAT: case ORCGPU_T_DOUBLE:
-            ok = vt == ORCGPU_PV_FLOAT32 || vt == ORCGPU_PV_FLOAT64;
-            in.op = FOP_CMP_FLOAT;
-            in.f = vt == ORCGPU_PV_FLOAT32 ? (double)(float)n.f : n.f;
-            break;
-          case ORCGPU_T_BOOLEAN:
-            ok = vt == ORCGPU_PV_BOOLEAN;
-            in.op = FOP_CMP_BOOL;
-            in.i = n.i != 0;
-            break;
-          case ORCGPU_T_STRING: case ORCGPU_T_VARCHAR: case ORCGPU_T_CHAR: case ORCGPU_T_BINARY:
-            ok = vt == ORCGPU_PV_UTF8;
-            in.op = FOP_CMP_STRING;
-            break;
-          case ORCGPU_T_DECIMAL:
-            if (vt != ORCGPU_PV_DECIMAL128)
-              return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' is compared with Decimal128 literals only (value type %lld is not supported)", n.column, vt);
-            ok = true;
-            in.op = FOP_CMP_DEC128;
-            break;
-          case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT:
-            if (vt != ORCGPU_PV_TIMESTAMP_NS)
-              return fail(ORCGPU_UNSUPPORTED, "row filter: the Timestamp column '%s' is compared with TimestampNs literals only (value type %lld is not supported)", n.column, vt);
-            ok = true;
-            in.op = FOP_CMP_INT;
-            break;
-          default:
-            return fail(ORCGPU_UNSUPPORTED, "row filter: column '%s' of ORC type kind %lld cannot be compared", n.column, kind);
-        }
-        if (!ok) return fail(ORCGPU_MISMATCHED_SCHEMA, "row filter: column '%s' cannot be compared with a literal of value type %lld", n.column, vt);
+        if (const int lrc = literal(n, n.column, col, in)) return lrc;
         if (n.value_is_null) {
           emit(FOP_UNKNOWN);
           return ORCGPU_OK;
         }
         if (kind == ORCGPU_T_DECIMAL) {
-          if (const int drc = decimal(n, col, in)) return drc;
+          if (const int drc = decimal(n, n.column, col, in)) return drc;
         } else if (kind == ORCGPU_T_TIMESTAMP || kind == ORCGPU_T_TIMESTAMP_INSTANT) {
-          if (const int trc = timestamp(n, col, in)) return trc;
+          if (const int trc = timestamp(n, n.column, col, in)) return trc;
         }
         if (in.op == FOP_CMP_STRING) {
           if (n.s_len && !n.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", n.column);
@@ -214,6 +223,25 @@ struct FilterCompiler {
         if (rc) return rc;
         return like(n, col);
       }
+      case ORCGPU_PRED_IN: {
+        // (the shape of the list before anything else: its literal nodes follow the leaf, and `at` must end behind them)
+        if ((uint64_t)at + n.n_children > n_nodes)
+          return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the node list ends inside an IN list%s (%lld nodes)", "", n_nodes);
+        for (uint32_t k = 0; k < n.n_children; k++) {
+          const orcgpu_predicate_node& l = nodes[at + k];
+          if (l.op != ORCGPU_PRED_LITERAL)
+            return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an IN list holds literal nodes only%s (node op %lld)", "", l.op);
+          if (l.n_children) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node of an IN list has children%s (%lld)", "", l.n_children);
+        }
+        uint32_t col = 0;
+        const int rc = column(n, col);
+        if (rc) return rc;
+        const int irc = in_list(n, nodes + at, col);
+        at += n.n_children;
+        return irc;
+      }
+      case ORCGPU_PRED_LITERAL:
+        return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
       default:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: unknown node op%s %lld", "", n.op);
     }
@@ -277,7 +305,7 @@ struct FilterCompiler {
     in.op = FOP_LIKE;
     in.cmp = shape;
     if (shape != LIKE_ALL) {
-      in.i = n_like++;  // its plane of match bits
+      in.i = n_planes++;  // its plane of match bits
       while (out.lits.size() & 3) out.lits.push_back(0);
       in.lit_off = out.lits.size();
       std::vector<uint32_t> words = {shape, flags, np, (uint32_t)bytes.size()};
@@ -294,7 +322,101 @@ struct FilterCompiler {
     out.prog.push_back(in);
     return ORCGPU_OK;
   }
-  long long n_like = 0;  // LIKE leaves with a mask plane so far
+  // An IN leaf: x IN (v1 .. vk) is OR(x = v1, ..., x = vk).  Every literal passes the type table of EQ and is brought to the
+  // column's key by the code EQ uses; a literal that can equal no row (NaN, a Decimal off the column's scale, a Timestamp between
+  // two values of its unit) is FALSE on valid rows like the empty rest of the OR, so it is left out.  Then by shape: no literal:
+  // FALSE; only NULLs, or no usable key beside a NULL: UNKNOWN; one key and no NULL: the EQ instruction itself; a Boolean column
+  // and a list without a usable key: FOP_IN without a table; everything else: FOP_IN with a hash set and a mask plane.
+  int in_list(const orcgpu_predicate_node& n, const orcgpu_predicate_node* list, uint32_t col) {
+    const uint32_t k = n.n_children;
+    if (k > ORCGPU_IN_MAX_VALUES)
+      return fail(ORCGPU_UNSUPPORTED, "row filter: the IN list for column '%s' holds more than %lld values", n.column, ORCGPU_IN_MAX_VALUES);
+    if (!k) {
+      emit(FOP_FALSE);
+      return ORCGPU_OK;
+    }
+    const int kind = kinds[col];
+    const bool is_ts = kind == ORCGPU_T_TIMESTAMP || kind == ORCGPU_T_TIMESTAMP_INSTANT;
+    InKeys keys;
+    uint32_t fop = 0;
+    uint64_t bytes = 0;
+    bool has_false = false, has_true = false;
+    for (uint32_t x = 0; x < k; x++) {
+      const orcgpu_predicate_node& l = list[x];
+      FilterInsn eq{};
+      eq.cmp = ORCGPU_PRED_EQ;
+      eq.col = col;
+      if (const int lrc = literal(l, n.column, col, eq)) return lrc;
+      fop = eq.op;
+      if (l.value_is_null) {
+        keys.has_null = true;
+        continue;
+      }
+      if (eq.op == FOP_CMP_INT) {
+        if (is_ts) {
+          if (const int trc = timestamp(l, n.column, col, eq)) return trc;
+          if (eq.cmp != ORCGPU_PRED_EQ) continue;  // between two values of the unit
+        }
+        keys.k64.push_back((uint64_t)eq.i);
+      } else if (eq.op == FOP_CMP_FLOAT) {
+        if (eq.f != eq.f) continue;  // NaN
+        keys.k64.push_back(in_float_key(eq.f));
+      } else if (eq.op == FOP_CMP_BOOL) {
+        (eq.i ? has_true : has_false) = true;
+      } else if (eq.op == FOP_CMP_DEC128) {
+        if (const int drc = decimal(l, n.column, col, eq)) return drc;
+        const i128 v = (i128)(((unsigned __int128)(uint64_t)eq.i << 64) | (unsigned __int128)eq.lo), lim = dec_pow10(kDecMaxDigits);
+        if (v <= -lim || v >= lim) continue;  // off the column's scale, or beyond every Decimal
+        keys.add_dec128(eq.lo, eq.i);
+      } else {
+        if (l.s_len && !l.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", n.column);
+        if (l.s_len > 0x7fffffffull) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' is longer than 2^31 - 1 bytes", n.column);
+        bytes += l.s_len;
+        if (bytes > ORCGPU_IN_MAX_BYTES)
+          return fail(ORCGPU_UNSUPPORTED, "row filter: the IN list for column '%s' holds more than %lld bytes of literals", n.column, ORCGPU_IN_MAX_BYTES);
+        keys.kstr.emplace_back(l.s ? l.s : "", (size_t)l.s_len);
+      }
+    }
+    keys.kind = fop == FOP_CMP_DEC128 ? IN_KEY_DEC128 : fop == FOP_CMP_STRING ? IN_KEY_STRING : IN_KEY_I64;
+    keys.dedup();
+    const size_t nk = fop == FOP_CMP_BOOL ? (size_t)has_false + has_true : keys.size();
+    if (!nk && keys.has_null) {
+      emit(FOP_UNKNOWN);
+      return ORCGPU_OK;
+    }
+    FilterInsn in{};
+    in.col = col;
+    if (nk == 1 && !keys.has_null) {  // the comparison itself: no plane, no further kernel
+      in.op = fop;
+      in.cmp = ORCGPU_PRED_EQ;
+      if (fop == FOP_CMP_BOOL) in.i = has_true;
+      else if (fop == FOP_CMP_INT) in.i = (long long)keys.k64[0];
+      else if (fop == FOP_CMP_FLOAT) memcpy(&in.f, &keys.k64[0], 8);
+      else if (fop == FOP_CMP_DEC128) {
+        in.i = InKeys::dec_high(keys.k128[0]);
+        in.lo = keys.k128[0].second;
+      } else {
+        in.lit_off = out.lits.size();
+        in.lit_len = (uint32_t)keys.kstr[0].size();
+        out.lits.insert(out.lits.end(), keys.kstr[0].begin(), keys.kstr[0].end());
+      }
+      out.prog.push_back(in);
+      return ORCGPU_OK;
+    }
+    in.op = FOP_IN;
+    in.cmp = keys.has_null ? IN_HAS_NULL : 0;
+    in.lo = fop == FOP_CMP_INT ? FKIND_INT : fop == FOP_CMP_FLOAT ? FKIND_FLOAT : fop == FOP_CMP_BOOL ? FKIND_BOOL : fop == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
+    if (!nk || fop == FOP_CMP_BOOL) {
+      in.cmp |= IN_NO_TABLE | (has_false ? IN_BOOL_FALSE : 0) | (has_true ? IN_BOOL_TRUE : 0);
+      in.i = -1;
+    } else {
+      in.i = n_planes++;
+      in.lit_off = in_build_table(keys, in.cmp, out.lits, in.lit_len);
+    }
+    out.prog.push_back(in);
+    return ORCGPU_OK;
+  }
+  long long n_planes = 0;  // LIKE and IN leaves with a mask plane so far: the planes are numbered together
 };
 
 // ORCGPU_OK, or the status a reader with this filter ends with (out.err says why).  names[k] / kinds[k]: column k.

@@ -429,6 +429,141 @@ struct PredEval {
       } else if (strings && (st.smax < p || (has_succ && !(st.smin < succ)))) result[g] = 0;
     }
   }
+  // An IN leaf (ORCGPU_PRED_IN; the reference has none) keeps the groups the OR of its EQ leaves keeps, by the rules of
+  // comparison() per literal: statistics, then the Bloom filter; a literal of the wrong type and a group without typed statistics
+  // fail the evaluation as they do for EQ.  One difference: Double statistics whose minimum or maximum is a NaN bound nothing, and
+  // the group is kept.  Under a NOT every group is kept (sound; NE's rule buys nothing for a list).  The
+  // literals are sorted once per leaf and the ones inside a group's [min, max] are found by binary search; only those are put to
+  // the Bloom filter, so 65536 literals do not cost 65536 tests per group.
+  void in_list(size_t at, bool neg, std::vector<uint8_t>& result) {
+    const PredNode& n = nodes[at];
+    const size_t k = n.n_children;
+    for (size_t x = 0; x < k; x++)
+      if (nodes[at + 1 + x].op != ORCGPU_PRED_LITERAL) {
+        failed = true;
+        return;
+      }
+    if (neg) return;
+    if (!k) {  // an OR of no children: no group can hold a row
+      std::fill(result.begin(), result.end(), 0);
+      return;
+    }
+    const ColumnGroups* c = column(n.column);
+    if (!c) return;
+    // the literals by kind, each kind in the order its statistics compare in; .second = the literal's node
+    std::vector<std::pair<int64_t, size_t>> ints;
+    std::vector<std::pair<double, size_t>> floats;
+    std::vector<std::pair<std::string, size_t>> strs;
+    struct Dec {
+      i128 v;
+      int scale;
+      size_t node;
+    };
+    std::vector<Dec> decs;
+    size_t n_i8_16 = 0, n_bool = 0, n_ts = 0, n_nan = 0, n_bad_dec = 0;
+    bool has_true = false, has_false = false;
+    size_t node_true = 0, node_false = 0;
+    for (size_t x = 0; x < k; x++) {
+      const PredNode& l = nodes[at + 1 + x];
+      const int vt = l.value_type;
+      n_ts += vt == ORCGPU_PV_TIMESTAMP_NS;  // (the NULL one as well: Timestamp statistics take it as it is)
+      if (l.value_is_null) continue;
+      if (vt >= ORCGPU_PV_INT8 && vt <= ORCGPU_PV_INT64) {
+        ints.emplace_back(l.i, at + 1 + x);
+        n_i8_16 += vt == ORCGPU_PV_INT8 || vt == ORCGPU_PV_INT16;
+      } else if (vt == ORCGPU_PV_FLOAT32 || vt == ORCGPU_PV_FLOAT64) {
+        const double d = vt == ORCGPU_PV_FLOAT32 ? (double)(float)l.f : l.f;
+        if (d == d) floats.emplace_back(d, at + 1 + x);
+        else n_nan++;  // (inside no [min - eps, max + eps])
+      } else if (vt == ORCGPU_PV_UTF8) strs.emplace_back(l.s, at + 1 + x);
+      else if (vt == ORCGPU_PV_BOOLEAN) {
+        n_bool++;
+        if (l.i) has_true = true, node_true = at + 1 + x;
+        else has_false = true, node_false = at + 1 + x;
+      } else if (vt == ORCGPU_PV_DECIMAL128) {
+        Dec d{0, (int)l.i, at + 1 + x};
+        if (dec_literal(l.s.data(), l.s.size(), l.i, d.v)) decs.push_back(d);
+        else n_bad_dec++;
+      }
+    }
+    const size_t n_float = floats.size() + n_nan, n_dec = decs.size() + n_bad_dec;
+    std::sort(ints.begin(), ints.end());
+    std::sort(floats.begin(), floats.end());
+    std::sort(strs.begin(), strs.end());
+    std::sort(decs.begin(), decs.end(), [](const Dec& a, const Dec& b) { return dec_cmp(a.v, a.scale, b.v, b.scale) < 0; });
+    std::vector<uint8_t> any(result.size(), 0);
+    for (size_t g = 0; g < result.size() && g < c->stats.size(); g++) {
+      const GroupStats& st = c->stats[g];
+      const GroupBloom* bloom = c->blooms.empty() ? nullptr : &c->blooms[g];
+      auto ask = [&](size_t node) { return bloom_match(bloom, ORCGPU_PRED_EQ, nodes[node]); };
+      bool keep = false;
+      if (!st.present) {  // no statistics: every literal is inside, the Bloom filter alone can say no
+        for (size_t x = 0; x < k && !keep; x++) keep = ask(at + 1 + x);
+        any[g] = keep;
+        continue;
+      }
+      switch (st.kind) {
+        case GroupStats::NONE:
+          failed = true;
+          return;
+        case GroupStats::INTEGER: case GroupStats::DATE: case GroupStats::TIMESTAMP: {
+          if (st.kind == GroupStats::TIMESTAMP) {
+            // (a TimestampNs literal prunes nothing and fails nothing; any other literal must be an Int64)
+            if (ints.size() + n_ts != k || n_i8_16) return (void)(failed = true);
+            for (auto& e : ints)
+              if (nodes[e.second].value_type != ORCGPU_PV_INT64) return (void)(failed = true);
+            if (n_ts) {
+              keep = true;
+              break;
+            }
+          } else if (ints.size() != k || (st.kind == GroupStats::DATE && n_i8_16)) return (void)(failed = true);
+          auto lo = std::lower_bound(ints.begin(), ints.end(), std::make_pair(st.imin, (size_t)0));
+          for (; lo != ints.end() && lo->first <= st.imax && !keep; ++lo) keep = ask(lo->second);
+          break;
+        }
+        case GroupStats::DOUBLE: {
+          if (n_float != k) return (void)(failed = true);
+          const double eps = 1e-9;
+          if (st.dmin != st.dmin || st.dmax != st.dmax) {
+            // (a NaN in the group has poisoned the writer's minimum / maximum: they bound nothing, so every literal is inside.
+            // EQ's own rule, the reference's, finds nothing inside such a pair; a list is not made unsound for its sake)
+            for (size_t x = 0; x < floats.size() && !keep; x++) keep = ask(floats[x].second);
+            break;
+          }
+          auto lo = std::lower_bound(floats.begin(), floats.end(), std::make_pair(st.dmin - eps, (size_t)0));
+          for (; lo != floats.end() && lo->first <= st.dmax + eps && !keep; ++lo) keep = ask(lo->second);
+          break;
+        }
+        case GroupStats::STRING: case GroupStats::DECIMAL: {
+          const bool is_dec = st.kind == GroupStats::DECIMAL;
+          if (strs.size() + (is_dec ? n_dec : 0) != k || n_bad_dec) return (void)(failed = true);
+          // (the strings from the lower bound on, each by EQ's own rule: exact and truncated bounds differ at the ends only)
+          auto lo = std::lower_bound(strs.begin(), strs.end(), st.smin, [](const std::pair<std::string, size_t>& e, const std::string& v) { return e.first < v; });
+          for (; lo != strs.end() && !(st.smax < lo->first) && !keep; ++lo)
+            keep = cmp_string(st.smin, st.smax, ORCGPU_PRED_EQ, lo->first, is_dec || st.exact_min, is_dec || st.exact_max) && ask(lo->second);
+          if (is_dec && !decs.empty()) {
+            i128 mn, mx;
+            int mn_scale, mx_scale;
+            if (!dec_parse(st.smin, mn, mn_scale) || !dec_parse(st.smax, mx, mx_scale)) return (void)(failed = true);
+            auto dl = std::lower_bound(decs.begin(), decs.end(), 0, [&](const Dec& e, int) { return dec_cmp(e.v, e.scale, mn, mn_scale) < 0; });
+            for (; dl != decs.end() && dec_cmp(dl->v, dl->scale, mx, mx_scale) <= 0 && !keep; ++dl) keep = ask(dl->node);
+          }
+          break;
+        }
+        case GroupStats::BUCKET: {
+          if (n_bool != k) return (void)(failed = true);
+          const uint64_t t = st.true_count, fcount = st.number_of_values - t;
+          keep = (has_true && t > 0 && ask(node_true)) || (has_false && fcount > 0 && ask(node_false));
+          break;
+        }
+        default:  // Binary, Collection: the statistics say nothing, whatever the literal
+          for (size_t x = 0; x < k && !keep; x++) keep = ask(at + 1 + x);
+          break;
+      }
+      any[g] = keep;
+    }
+    for (size_t g = 0; g < result.size(); g++) result[g] = g < c->stats.size() ? any[g] : result[g];
+  }
   // one subtree in pre-order; returns the index behind it.  `neg`: under a NOT (pushed down as the reference does)
   size_t eval(size_t at, bool neg, std::vector<uint8_t>& result) {
     if (at >= nodes.size() || failed) {
@@ -436,6 +571,14 @@ struct PredEval {
       return nodes.size();
     }
     const PredNode& n = nodes[at];
+    if (n.op == ORCGPU_PRED_IN) {
+      if (at + 1 + (size_t)n.n_children > nodes.size()) {
+        failed = true;
+        return nodes.size();
+      }
+      in_list(at, neg, result);
+      return at + 1 + n.n_children;
+    }
     if (n.op == ORCGPU_PRED_LIKE) {
       like(n, neg, result);
       return at + 1;

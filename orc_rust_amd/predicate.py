@@ -7,6 +7,7 @@ import decimal
 
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL, AND, OR, NOT = range(11)
 LIKE = 16  # (11 .. 15 are unknown ops)
+IN, LITERAL = 17, 18  # an IN leaf, and one value of its list
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
 _EPOCH = datetime.datetime(1970, 1, 1)
 
@@ -82,7 +83,7 @@ class PredicateValue:
 
 class Predicate:
     """Predicate::{Comparison, IsNull, IsNotNull, And, Or, Not} with the reference's constructors (predicate.rs:98-180), and
-    this library's own LIKE leaf (like / not_like / starts_with / ends_with / contains)."""
+    this library's own LIKE leaf (like / not_like / starts_with / ends_with / contains) and IN leaf (in_list / not_in)."""
 
     def __init__(self, op, column=None, value=None, children=()):
         self.op, self.column, self.value, self.children = op, column, value, list(children)
@@ -140,6 +141,31 @@ class Predicate:
         lit = cls._like_literal(text)
         pc = "%" if isinstance(lit, str) else b"%"
         return cls.like(column, pc + lit + pc, escape="\\")
+
+    @classmethod
+    def in_list(cls, column, values):
+        """SQL IN (ORCGPU_PRED_IN, this library's own): column IN (values), exactly the OR of column = v over the values under
+        three-valued logic -- the empty list is FALSE, a NULL among the values makes every non-match UNKNOWN.  values: an iterable
+        of PredicateValue of the kinds the column takes (at most 65536 of them)."""
+        if isinstance(values, (PredicateValue, str, bytes)):
+            raise TypeError("IN list: an iterable of PredicateValue, got %r" % (values,))
+        try:
+            values = list(values)
+        except TypeError:
+            raise TypeError("IN list: an iterable of PredicateValue, got %r" % (values,)) from None
+        for v in values:
+            if not isinstance(v, PredicateValue):
+                raise TypeError("IN list: every value is a PredicateValue, got %r" % (v,))
+        return cls(IN, column, children=[cls(LITERAL, value=v) for v in values])
+
+    @classmethod
+    def not_in(cls, column, values):
+        return cls.not_(cls.in_list(column, values))
+
+    @classmethod
+    def between(cls, column, lo, hi):
+        """lo <= column <= hi: and_([gte(column, lo), lte(column, hi)])"""
+        return cls.and_([cls.gte(column, lo), cls.lte(column, hi)])
 
     @classmethod
     def and_(cls, predicates):
