@@ -27,7 +27,8 @@
 // The input rows are the result's rows as its batches hand them out: all rows of the stripe (n_segs = 0), or the row ranges
 // of a row selection (SelBatch segments).  Leaves and the gather read the stripe-wide buffers of the decode the way
 // select_build_kernel does: uniform batches of `B` rows, `W` validity words per batch, string offsets that restart per
-// batch plus the batch's char base.  Output rows [k * B, (k + 1) * B) form output batch k.
+// batch plus the batch's char base.  Output rows [k * B, (k + 1) * B) form output batch k.  All of that is written down once, in
+// the row-access helpers in front of the kernels (filter_row .. filter_value_str): a kernel addresses a row through them only.
 #pragma once
 #include <stdint.h>
 
@@ -66,12 +67,84 @@ __device__ __forceinline__ uint64_t filter_src_row(const SelBatch* segs, const u
   return segs[lo].start + (j - seg_first[lo]);
 }
 
-__device__ __forceinline__ bool filter_valid(const FilterCol& c, uint64_t u, uint32_t l, uint32_t W) {
-  return !c.validity || ((c.validity[u * W + (l >> 6)] >> (l & 63)) & 1);
+// ---- row access: how every kernel below finds a row and loads what a column holds for it ----
+// A row of the stripe as the decode laid it out: uniform batch u, row l of it
+struct FilterRow {
+  bool live;  // false: an input row past n_in (row = u = l = 0 then: loads stay in bounds, their results are masked out)
+  uint64_t row, u;
+  uint32_t l;
+};
+__device__ __forceinline__ FilterRow filter_row_of(uint64_t row, uint32_t B, bool live = true) {
+  return {live, row, row / B, (uint32_t)(row % B)};
 }
-__device__ __forceinline__ uint32_t filter_str_len(const FilterCol& c, uint64_t u, uint32_t l, uint32_t B) {
-  const int32_t* o = c.offsets + u * (B + 1) + l;
-  return (uint32_t)o[1] - (uint32_t)o[0];
+__device__ __forceinline__ FilterRow filter_row(const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B,
+                                                uint64_t j) {
+  return filter_row_of(j < n_in ? filter_src_row(segs, seg_first, n_segs, j) : 0, B, j < n_in);
+}
+// The 64-bit words of a mask over the input rows (`keep`, a plane), dealt to the wavefronts of a grid of 256-thread blocks:
+//   for (uint64_t w = ws.first; w < ws.n; w += ws.stride) { input row j = w * 64 + lane ... }
+struct FilterWords {
+  uint64_t first, stride, n;
+};
+__device__ __forceinline__ FilterWords filter_words(uint64_t n_in) {
+  return {(uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (uint64_t)gridDim.x * 4, (n_in + 63) / 64};
+}
+
+// bit l of batch u in bit words laid out per uniform batch (validity, Boolean values)
+__device__ __forceinline__ bool filter_bit(const unsigned long long* w, uint64_t u, uint32_t l, uint32_t W) { return (w[u * W + (l >> 6)] >> (l & 63)) & 1; }
+__device__ __forceinline__ bool filter_valid(const FilterCol& c, uint64_t u, uint32_t l, uint32_t W) {
+  return !c.validity || filter_bit(c.validity, u, l, W);
+}
+__device__ __forceinline__ bool filter_load_bit(const FilterCol& c, uint64_t u, uint32_t l, uint32_t W) {
+  return filter_bit(reinterpret_cast<const unsigned long long*>(c.values), u, l, W);
+}
+__device__ __forceinline__ long long filter_load_i64(const FilterCol& c, uint64_t row) {
+  if (c.width == 1) return reinterpret_cast<const int8_t*>(c.values)[row];
+  if (c.width == 2) return reinterpret_cast<const int16_t*>(c.values)[row];
+  if (c.width == 4) return reinterpret_cast<const int32_t*>(c.values)[row];
+  return reinterpret_cast<const long long*>(c.values)[row];
+}
+__device__ __forceinline__ double filter_load_f64(const FilterCol& c, uint64_t row) {
+  return c.width == 4 ? (double)reinterpret_cast<const float*>(c.values)[row] : reinterpret_cast<const double*>(c.values)[row];
+}
+// one 16-byte load (row * 16 off a 256-byte aligned arena), little-endian halves
+__device__ __forceinline__ void filter_load_dec128(const FilterCol& c, uint64_t row, unsigned long long* lo, unsigned long long* hi) {
+  const uint4 q = reinterpret_cast<const uint4*>(c.values)[row];
+  *lo = ((unsigned long long)q.y << 32) | q.x;
+  *hi = ((unsigned long long)q.w << 32) | q.z;
+}
+// A string value by its offsets pair alone -- o[0], o[1] of filter_str_offsets --: where it starts among its batch's bytes, and
+// its length
+struct FilterSpan {
+  uint32_t start, len;
+};
+__device__ __forceinline__ const int32_t* filter_str_offsets(const FilterCol& c, uint64_t u, uint32_t l, uint32_t B) {
+  return c.offsets + u * (B + 1) + l;
+}
+__device__ __forceinline__ FilterSpan filter_str_span(const FilterCol& c, uint64_t u, uint32_t l, uint32_t B) {
+  const int32_t* o = filter_str_offsets(c, u, l, B);
+  const uint32_t a = (uint32_t)o[0];
+  return {a, (uint32_t)o[1] - a};
+}
+__device__ __forceinline__ uint32_t filter_str_len(const FilterCol& c, uint64_t u, uint32_t l, uint32_t B) { return filter_str_span(c, u, l, B).len; }
+// A string value: its bytes p[0, len).  The chars buffer promises nothing behind its last value: whoever loads p[x] keeps x < len.
+// From a span already loaded (whoever decides by the length alone loads no char base for the values it passes over), or from the row.
+struct FilterStr {
+  const uint8_t* p;
+  uint32_t len;
+};
+__device__ __forceinline__ FilterStr filter_value_str(const FilterCol& c, uint64_t u, FilterSpan s) { return {c.chars + c.char_base[u] + s.start, s.len}; }
+__device__ __forceinline__ FilterStr filter_value_str(const FilterCol& c, uint64_t u, uint32_t l, uint32_t B) {
+  return filter_value_str(c, u, filter_str_span(c, u, l, B));
+}
+// Leaf blockIdx.y of a plane kernel's leaf list: its instruction.  false -- the whole block leaves -- for what only a damaged
+// upload holds: an index past the program, an instruction of another op, a plane past the workspace's.
+__device__ __forceinline__ bool filter_leaf(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, uint32_t op, uint32_t n_planes,
+                                            FilterInsn* in) {
+  const uint32_t k = leaves[blockIdx.y];
+  if (k >= n_insn) return false;
+  *in = prog[k];
+  return in->op == op && (unsigned long long)in->i < n_planes;
 }
 
 // ---- LIKE: the compiled pattern of filter_program.h, staged in LDS ----
@@ -158,25 +231,17 @@ __device__ __forceinline__ bool like_match(const uint8_t* p, uint32_t len, const
   return true;
 }
 
-// The LIKE leaves' matcher, in front of filter_eval_kernel on its stream.  blockIdx.y = a mask plane, i.e. one LIKE leaf of the
-// program (FilterInsn::i); a wavefront trip is one 64-bit word of the plane, laid out like `keep`: bit = the row's value matches
-// (null rows and rows past n_in: 0).  The compiled pattern is staged in LDS once per workgroup.  Values of up to
-// kFilterShortString bytes are matched by their own lane, longer ones one after the other by the whole wavefront.  Every load of
-// a value byte is bounded by the value's length: the chars buffer promises nothing behind its last value.
+// The LIKE leaves' matcher, in front of filter_eval_kernel on its stream.  blockIdx.y = a LIKE leaf with a plane: instruction
+// leaves[blockIdx.y] of the program, which names its plane (FilterInsn::i); a wavefront trip is one 64-bit word of the plane, laid
+// out like `keep`: bit = the row's value matches (null rows and rows past n_in: 0).  The compiled pattern is staged in LDS once per
+// workgroup.  Values of up to kFilterShortString bytes are matched by their own lane, longer ones one after the other by the whole
+// wavefront.  Every load of a value byte is bounded by the value's length.
 extern "C" __global__ void __launch_bounds__(256)
-filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
-                   const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* masks) {
+filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                   const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes, uint32_t n_planes) {
   __shared__ uint32_t pat_s[kLikeBlobMax / 4];
-  __shared__ uint32_t insn_s;
-  if (threadIdx.x == 0) {
-    uint32_t at = n_insn;
-    for (uint32_t k = 0; k < n_insn; k++)
-      if (prog[k].op == FOP_LIKE && prog[k].cmp != LIKE_ALL && prog[k].i == (long long)blockIdx.y) at = k;
-    insn_s = at;
-  }
-  __syncthreads();
-  if (insn_s >= n_insn) return;
-  const FilterInsn in = prog[insn_s];
+  FilterInsn in;
+  if (!filter_leaf(prog, n_insn, leaves, FOP_LIKE, n_planes, &in) || in.cmp == LIKE_ALL) return;
   const uint32_t blob = in.lit_len < kLikeBlobMax ? in.lit_len : kLikeBlobMax;
   for (uint32_t x = threadIdx.x; x < blob; x += 256) reinterpret_cast<uint8_t*>(pat_s)[x] = lits[in.lit_off + x];
   __syncthreads();
@@ -190,32 +255,22 @@ filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
   P.ones = P.bytes + P.n_elems;
   const bool lit = P.shape != LIKE_GENERAL;  // one part of literal bytes: the prefix, suffix and contains shapes skip the `_` tests
   const FilterCol c = cols[in.col];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t n_words = (n_in + 63) / 64;
-  unsigned long long* plane = masks + (uint64_t)blockIdx.y * n_words;
-  for (uint64_t w = (uint64_t)blockIdx.x * 4 + wave; w < n_words; w += (uint64_t)gridDim.x * 4) {
-    const uint64_t j = w * 64 + lane;
-    const bool live = j < n_in;
-    const uint64_t row = live ? filter_src_row(segs, seg_first, n_segs, j) : 0;
-    const uint64_t u = row / B;
-    const uint32_t l = (uint32_t)(row % B);
-    const bool valid = live && filter_valid(c, u, l, W);
-    uint32_t len = 0;
-    unsigned long long at = 0;
-    if (valid) {
-      const int32_t* o = c.offsets + u * (B + 1) + l;
-      const uint32_t a = (uint32_t)o[0];
-      len = (uint32_t)o[1] - a;
-      at = c.char_base[u] + a;
-    }
-    const bool is_long = valid && len > kFilterShortString;
+  const uint32_t lane = threadIdx.x & 63;
+  const FilterWords ws = filter_words(n_in);
+  unsigned long long* plane = planes + (uint64_t)in.i * ws.n;
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
+    const bool valid = r.live && filter_valid(c, r.u, r.l, W);
+    FilterStr v = {c.chars, 0};
+    if (valid) v = filter_value_str(c, r.u, r.l, B);
+    const bool is_long = valid && v.len > kFilterShortString;
     bool m = false;
-    if (valid && !is_long) m = lit ? like_match<false, true>(c.chars + at, len, P, lane) : like_match<false, false>(c.chars + at, len, P, lane);
+    if (valid && !is_long) m = lit ? like_match<false, true>(v.p, v.len, P, lane) : like_match<false, false>(v.p, v.len, P, lane);
     unsigned long long M = __ballot(m);
     for (unsigned long long todo = __ballot(is_long); todo; todo &= todo - 1) {
       const int src = __builtin_ctzll(todo);
-      const uint8_t* p = c.chars + (unsigned long long)__shfl((long long)at, src);
-      const uint32_t n = (uint32_t)__shfl((int)len, src);
+      const uint8_t* p = c.chars + __shfl((long long)(v.p - c.chars), src);
+      const uint32_t n = (uint32_t)__shfl((int)v.len, src);
       if (lit ? like_match<true, true>(p, n, P, lane) : like_match<true, false>(p, n, P, lane)) M |= 1ull << src;
     }
     if (lane == 0) plane[w] = M;
@@ -293,34 +348,25 @@ __device__ __forceinline__ void filter_in_plane(const uint8_t* tab, uint32_t tab
   // not fit its column matches nothing)
   const bool fits = t.n_slots && (c.kind == FKIND_STRING ? t.kind == IN_KEY_STRING : c.kind == FKIND_DEC128 ? t.kind == IN_KEY_DEC128
                                                                                     : (c.kind == FKIND_INT || c.kind == FKIND_FLOAT) && t.kind == IN_KEY_I64);
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t n_words = (n_in + 63) / 64;
-  for (uint64_t w = (uint64_t)blockIdx.x * 4 + wave; w < n_words; w += (uint64_t)gridDim.x * 4) {
-    const uint64_t j = w * 64 + lane;
-    const bool live = j < n_in;
-    const uint64_t row = live ? filter_src_row(segs, seg_first, n_segs, j) : 0;
-    const uint64_t u = row / B;
-    const uint32_t l = (uint32_t)(row % B);
+  const uint32_t lane = threadIdx.x & 63;
+  const FilterWords ws = filter_words(n_in);
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
     bool m = false;
-    if (fits && live && filter_valid(c, u, l, W)) {
+    if (fits && r.live && filter_valid(c, r.u, r.l, W)) {
       if (c.kind == FKIND_INT) {
-        long long v;
-        if (c.width == 1) v = reinterpret_cast<const int8_t*>(c.values)[row];
-        else if (c.width == 2) v = reinterpret_cast<const int16_t*>(c.values)[row];
-        else if (c.width == 4) v = reinterpret_cast<const int32_t*>(c.values)[row];
-        else v = reinterpret_cast<const long long*>(c.values)[row];
-        m = in_probe_i64(t, (unsigned long long)v);
+        m = in_probe_i64(t, (unsigned long long)filter_load_i64(c, r.row));
       } else if (c.kind == FKIND_FLOAT) {
-        const double v = c.width == 4 ? (double)reinterpret_cast<const float*>(c.values)[row] : reinterpret_cast<const double*>(c.values)[row];
+        const double v = filter_load_f64(c, r.row);
         m = v == v && in_probe_i64(t, in_float_key(v));  // (a NaN row equals no key)
       } else if (c.kind == FKIND_DEC128) {
-        const uint4 q = reinterpret_cast<const uint4*>(c.values)[row];
-        m = in_probe_dec128(t, ((unsigned long long)q.y << 32) | q.x, ((unsigned long long)q.w << 32) | q.z);
+        unsigned long long lo, hi;
+        filter_load_dec128(c, r.row, &lo, &hi);
+        m = in_probe_dec128(t, lo, hi);
       } else {
-        const int32_t* o = c.offsets + u * (B + 1) + l;
-        const uint32_t a = (uint32_t)o[0], len = (uint32_t)o[1] - a;
+        const FilterSpan s = filter_str_span(c, r.u, r.l, B);
         // (a length no key has: a non-match from the offsets alone, no byte is loaded)
-        if (len >= t.min_len && len <= t.max_len) m = in_probe_string(t, c.chars + c.char_base[u] + a, len);
+        if (s.len >= t.min_len && s.len <= t.max_len) m = in_probe_string(t, filter_value_str(c, r.u, s).p, s.len);
       }
     }
     const unsigned long long M = __ballot(m);
@@ -328,27 +374,19 @@ __device__ __forceinline__ void filter_in_plane(const uint8_t* tab, uint32_t tab
   }
 }
 
-// The IN leaves' set membership, in front of filter_eval_kernel on its stream, with the grid of filter_like_kernel.  blockIdx.y = a
-// mask plane (the IN and the LIKE leaves of a program number their planes together; a block whose plane is not an IN leaf's
-// leaves at once); a wavefront trip is one 64-bit word of the plane, laid out like `keep`: bit = the row is valid and its key is
-// in the set (null rows and rows past n_in: 0).  A table of up to kInLdsBytes is staged in LDS once per workgroup, a larger one is
-// probed where it lies: 65536 int64 keys are 1 MiB of slots, which an XCD's L2 holds.  One lane per value, strings included.
+// The IN leaves' set membership, in front of filter_eval_kernel on its stream.  blockIdx.y = an IN leaf with a table: instruction
+// leaves[blockIdx.y] of the program, which names its plane (the IN and the LIKE leaves of a program number their planes together);
+// a wavefront trip is one 64-bit word of the plane, laid out like `keep`: bit = the row is valid and its key is in the set (null
+// rows and rows past n_in: 0).  A table of up to kInLdsBytes is staged in LDS once per workgroup, a larger one is probed where it
+// lies: 65536 int64 keys are 1 MiB of slots, which an XCD's L2 holds.  One lane per value, strings included.
 extern "C" __global__ void __launch_bounds__(256)
-filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
-                 const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* masks) {
+filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                 const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes, uint32_t n_planes) {
   __shared__ unsigned long long tab_s[kInLdsBytes / 8];
-  __shared__ uint32_t insn_s;
-  if (threadIdx.x == 0) {
-    uint32_t at = n_insn;
-    for (uint32_t k = 0; k < n_insn; k++)
-      if (prog[k].op == FOP_IN && !(prog[k].cmp & IN_NO_TABLE) && prog[k].i == (long long)blockIdx.y) at = k;
-    insn_s = at;
-  }
-  __syncthreads();
-  if (insn_s >= n_insn) return;
-  const FilterInsn in = prog[insn_s];
+  FilterInsn in;
+  if (!filter_leaf(prog, n_insn, leaves, FOP_IN, n_planes, &in) || (in.cmp & IN_NO_TABLE)) return;
   const FilterCol c = cols[in.col];
-  unsigned long long* plane = masks + (uint64_t)blockIdx.y * ((n_in + 63) / 64);
+  unsigned long long* plane = planes + (uint64_t)in.i * ((n_in + 63) / 64);
   // (lit_off and lit_len are multiples of 8 and the pool starts 256-byte aligned: whole 8-byte words)
   const unsigned long long* g = reinterpret_cast<const unsigned long long*>(lits + in.lit_off);
   const uint32_t bytes = in.lit_len & ~7u;
@@ -364,75 +402,59 @@ filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, c
 extern "C" __global__ void __launch_bounds__(256)
 filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
                    const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* keep,
-                   uint32_t* cnt, const unsigned long long* like_masks) {
+                   uint32_t* cnt, const unsigned long long* planes) {
   __shared__ unsigned long long stk_t[4][kFilterStack], stk_f[4][kFilterStack];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t n_words = (n_in + 63) / 64;
-  for (uint64_t w = (uint64_t)blockIdx.x * 4 + wave; w < n_words; w += (uint64_t)gridDim.x * 4) {
-    const uint64_t j = w * 64 + lane;
-    const bool live = j < n_in;
-    const uint64_t row = live ? filter_src_row(segs, seg_first, n_segs, j) : 0;
-    const uint64_t u = row / B;
-    const uint32_t l = (uint32_t)(row % B);
-    const unsigned long long live_m = __ballot(live);
+  const FilterWords ws = filter_words(n_in);
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
+    const unsigned long long live_m = __ballot(r.live);
     uint32_t sp = 0;
     for (uint32_t k = 0; k < n_insn; k++) {
       const FilterInsn in = prog[k];
       unsigned long long T = 0, F = 0;
       if (in.op <= FOP_IS_NOT_NULL) {
         const FilterCol c = cols[in.col];
-        const bool valid = live && filter_valid(c, u, l, W);
+        const bool valid = r.live && filter_valid(c, r.u, r.l, W);
         bool t = false, f = false;
         if (in.op == FOP_IS_NULL) {
-          t = live && !valid;
+          t = r.live && !valid;
           f = valid;
         } else if (in.op == FOP_IS_NOT_NULL) {
           t = valid;
-          f = live && !valid;
+          f = r.live && !valid;
         } else if (valid) {
           bool lt = false, eq = false, gt = false;
-          if (in.op == FOP_CMP_INT) {
-            long long v;
-            if (c.width == 1) v = reinterpret_cast<const int8_t*>(c.values)[row];
-            else if (c.width == 2) v = reinterpret_cast<const int16_t*>(c.values)[row];
-            else if (c.width == 4) v = reinterpret_cast<const int32_t*>(c.values)[row];
-            else v = reinterpret_cast<const long long*>(c.values)[row];
+          if (in.op == FOP_CMP_INT || in.op == FOP_CMP_BOOL) {
+            const long long v = in.op == FOP_CMP_INT ? filter_load_i64(c, r.row) : (long long)filter_load_bit(c, r.u, r.l, W);
             lt = v < in.i;
             eq = v == in.i;
             gt = v > in.i;
           } else if (in.op == FOP_CMP_FLOAT) {
-            const double v = c.width == 4 ? (double)reinterpret_cast<const float*>(c.values)[row] : reinterpret_cast<const double*>(c.values)[row];
+            const double v = filter_load_f64(c, r.row);
             lt = v < in.f;
             eq = v == in.f;
             gt = v > in.f;
-          } else if (in.op == FOP_CMP_BOOL) {
-            const long long v = (long long)((reinterpret_cast<const unsigned long long*>(c.values)[u * W + (l >> 6)] >> (l & 63)) & 1);
-            lt = v < in.i;
-            eq = v == in.i;
-            gt = v > in.i;
-          } else if (in.op == FOP_CMP_DEC128) {
-            // one 16-byte load (row * 16 off a 256-byte aligned arena); the high words as signed, the low words as unsigned
-            const uint4 q = reinterpret_cast<const uint4*>(c.values)[row];
-            const long long vh = (long long)(((unsigned long long)q.w << 32) | q.z);
-            const unsigned long long vl = ((unsigned long long)q.y << 32) | q.x;
+          } else if (in.op == FOP_CMP_DEC128) {  // the high words as signed, the low words as unsigned
+            unsigned long long vl, hi;
+            filter_load_dec128(c, r.row, &vl, &hi);
+            const long long vh = (long long)hi;
             eq = vh == in.i && vl == in.lo;
             lt = vh < in.i || (vh == in.i && vl < in.lo);
             gt = !lt && !eq;
           } else {  // FOP_CMP_STRING
-            const int32_t* o = c.offsets + u * (B + 1) + l;
-            const uint32_t a = (uint32_t)o[0], len = (uint32_t)o[1] - a;
-            const uint8_t* p = c.chars + c.char_base[u] + a;
+            const FilterStr v = filter_value_str(c, r.u, r.l, B);
             const uint8_t* q = lits + in.lit_off;
-            const uint32_t m = len < in.lit_len ? len : in.lit_len;
+            const uint32_t m = v.len < in.lit_len ? v.len : in.lit_len;
             uint32_t x = 0;
-            while (x < m && p[x] == q[x]) x++;
+            while (x < m && v.p[x] == q[x]) x++;
             if (x < m) {
-              lt = p[x] < q[x];
+              lt = v.p[x] < q[x];
               gt = !lt;
             } else {
-              lt = len < in.lit_len;
-              eq = len == in.lit_len;
-              gt = len > in.lit_len;
+              lt = v.len < in.lit_len;
+              eq = v.len == in.lit_len;
+              gt = v.len > in.lit_len;
             }
           }
           switch (in.cmp) {
@@ -449,20 +471,20 @@ filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
         F = __ballot(f);
       } else if (in.op == FOP_LIKE) {
         // the trip's match bits are there already (filter_like_kernel); only `%`: every valid row, and no plane to load
-        const unsigned long long valid_m = __ballot(live && filter_valid(cols[in.col], u, l, W));
-        const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : like_masks[(uint64_t)in.i * n_words + w];
+        const unsigned long long valid_m = __ballot(r.live && filter_valid(cols[in.col], r.u, r.l, W));
+        const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : planes[(uint64_t)in.i * ws.n + w];
         T = match & valid_m;
         F = ~match & valid_m;
       } else if (in.op == FOP_IN) {
         // the trip's membership bits are there already (filter_in_kernel); a Boolean column and a list no key of which can equal a
         // row have no plane.  With a NULL literal in the list a row that matches no key is UNKNOWN, not FALSE.
         const FilterCol c = cols[in.col];
-        const bool valid = live && filter_valid(c, u, l, W);
+        const bool valid = r.live && filter_valid(c, r.u, r.l, W);
         const unsigned long long valid_m = __ballot(valid);
         unsigned long long match = 0;
-        if (!(in.cmp & IN_NO_TABLE)) match = like_masks[(uint64_t)in.i * n_words + w];
+        if (!(in.cmp & IN_NO_TABLE)) match = planes[(uint64_t)in.i * ws.n + w];
         else if (in.cmp & (IN_BOOL_FALSE | IN_BOOL_TRUE)) {
-          const unsigned long long bits = __ballot(valid && ((reinterpret_cast<const unsigned long long*>(c.values)[u * W + (l >> 6)] >> (l & 63)) & 1));
+          const unsigned long long bits = __ballot(valid && filter_load_bit(c, r.u, r.l, W));
           match = (in.cmp & IN_BOOL_TRUE ? bits : 0ull) | (in.cmp & IN_BOOL_FALSE ? ~bits : 0ull);
         }
         T = match & valid_m;
@@ -523,11 +545,9 @@ filter_count_kernel(const FilterCol* cols, const uint32_t* src_rows, const unsig
   const uint32_t len = (uint32_t)(kept - first < B ? kept - first : B);
   unsigned long long n_null = 0, n_bytes = 0;
   for (uint32_t i = threadIdx.x; i < len; i += 256) {
-    const uint64_t row = src_rows[first + i];
-    const uint64_t u = row / B;
-    const uint32_t l = (uint32_t)(row % B);
-    if (!filter_valid(c, u, l, W)) n_null++;
-    if (c.kind == FKIND_STRING) n_bytes += filter_str_len(c, u, l, B);
+    const FilterRow r = filter_row_of(src_rows[first + i], B);
+    if (!filter_valid(c, r.u, r.l, W)) n_null++;
+    if (c.kind == FKIND_STRING) n_bytes += filter_str_len(c, r.u, r.l, B);
   }
   for (int o = 32; o; o >>= 1) {
     n_null += (unsigned long long)__shfl_xor((long long)n_null, o);
@@ -583,18 +603,14 @@ filter_gather_kernel(const FilterGatherJob* jobs, const uint32_t* src_rows, uint
   if (j.out_validity || c.kind == FKIND_BOOL) {
     for (uint32_t i0 = 0; i0 < len; i0 += 256) {
       const uint32_t i = i0 + threadIdx.x;
-      const bool live = i < len;
-      const uint64_t row = live ? rows[i] : 0;
-      const uint64_t u = row / B;
-      const uint32_t l = (uint32_t)(row % B);
-      const unsigned long long lm = __ballot(live);
+      const FilterRow r = filter_row_of(i < len ? rows[i] : 0, B, i < len);
+      const unsigned long long lm = __ballot(r.live);
       if (j.out_validity) {
-        const unsigned long long vm = __ballot(live && filter_valid(c, u, l, W));
+        const unsigned long long vm = __ballot(r.live && filter_valid(c, r.u, r.l, W));
         if (lane == 0 && lm) j.out_validity[ob * W + (i >> 6)] = vm;
       }
       if (c.kind == FKIND_BOOL) {
-        const bool bit = live && ((reinterpret_cast<const unsigned long long*>(c.values)[u * W + (l >> 6)] >> (l & 63)) & 1);
-        const unsigned long long bm = __ballot(bit);
+        const unsigned long long bm = __ballot(r.live && filter_load_bit(c, r.u, r.l, W));
         if (lane == 0 && lm) reinterpret_cast<unsigned long long*>(j.out_values)[ob * W + (i >> 6)] = bm;
       }
     }
@@ -621,8 +637,8 @@ filter_gather_kernel(const FilterGatherJob* jobs, const uint32_t* src_rows, uint
     const uint32_t i = i0 + threadIdx.x;
     unsigned long long n = 0;
     if (i < len) {
-      const uint64_t row = rows[i];
-      n = filter_str_len(c, row / B, (uint32_t)(row % B), B);
+      const FilterRow r = filter_row_of(rows[i], B);
+      n = filter_str_len(c, r.u, r.l, B);
     }
     unsigned long long inc = n;
     for (int o = 1; o < 64; o <<= 1) {
@@ -641,24 +657,24 @@ filter_gather_kernel(const FilterGatherJob* jobs, const uint32_t* src_rows, uint
   if (threadIdx.x == 0) ooff[len] = (int32_t)(uint32_t)carry_s;
   // ---- ... and the bytes: a lane per short value, then a wavefront per long one ----
   uint8_t* dst0 = j.out_chars + j.out_char_base[ob];
+  // (both loops read the offsets pair themselves, not through filter_str_span: the length tests and the copy loop's own then
+  // compile to one branch per value, which matters to a block that walks a batch's rows one after the other)
   for (uint32_t i = threadIdx.x; i < len; i += 256) {
-    const uint64_t row = rows[i];
-    const uint64_t u = row / B;
-    const int32_t* o = c.offsets + u * (B + 1) + (uint32_t)(row % B);
+    const FilterRow r = filter_row_of(rows[i], B);
+    const int32_t* o = filter_str_offsets(c, r.u, r.l, B);
     const uint32_t a = (uint32_t)o[0], n = (uint32_t)o[1] - a;
     if (n == 0 || n > kFilterShortString) continue;
-    const uint8_t* p = c.chars + c.char_base[u] + a;
+    const FilterStr v = filter_value_str(c, r.u, FilterSpan{a, n});
     uint8_t* d = dst0 + (uint32_t)ooff[i];
-    for (uint32_t x = 0; x < n; x++) d[x] = p[x];
+    for (uint32_t x = 0; x < v.len; x++) d[x] = v.p[x];
   }
   for (uint32_t i = wave; i < len; i += 4) {
-    const uint64_t row = rows[i];
-    const uint64_t u = row / B;
-    const int32_t* o = c.offsets + u * (B + 1) + (uint32_t)(row % B);
+    const FilterRow r = filter_row_of(rows[i], B);
+    const int32_t* o = filter_str_offsets(c, r.u, r.l, B);
     const uint32_t a = (uint32_t)o[0], n = (uint32_t)o[1] - a;
     if (n <= kFilterShortString) continue;
-    const uint8_t* p = c.chars + c.char_base[u] + a;
+    const FilterStr v = filter_value_str(c, r.u, FilterSpan{a, n});
     uint8_t* d = dst0 + (uint32_t)ooff[i];
-    for (uint32_t x = lane; x < n; x += 64) d[x] = p[x];
+    for (uint32_t x = lane; x < n; x += 64) d[x] = v.p[x];
   }
 }

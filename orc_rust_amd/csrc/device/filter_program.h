@@ -28,6 +28,11 @@ inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op ==
 // FKIND_INT holds Timestamp columns decoded to int64 (seconds .. nanoseconds) as well: the host brings the literal to the unit
 enum { FKIND_INT = 0, FKIND_FLOAT = 1, FKIND_BOOL = 2, FKIND_STRING = 3, FKIND_OTHER = 4 /* fixed width, null tests only */, FKIND_DEC128 = 5 };
 
+// the FKIND_* the column of an instruction that reads values must be decoded to (lo: FilterInsn::lo, where FOP_IN keeps its own)
+inline uint32_t fop_value_kind(uint32_t op, unsigned long long lo = 0) {
+  return op == FOP_IN ? (uint32_t)lo : op == FOP_CMP_INT ? FKIND_INT : op == FOP_CMP_FLOAT ? FKIND_FLOAT : op == FOP_CMP_BOOL ? FKIND_BOOL : op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
+}
+
 struct FilterInsn {
   uint32_t op;       // FOP_*
   uint32_t cmp;      // ORCGPU_PRED_EQ .. _GE; FOP_LIKE: LIKE_*; FOP_IN: IN_* flags

@@ -1,20 +1,36 @@
 // orcgpu_filter.inc -- the row filter at the seam: orcgpu_result_filter and what the file reader calls per stripe.  The plan
-// compiler is orcgpu_filter_plan.inc (host only), the kernels device/filter_kernels.hip.
+// compiler is orcgpu_filter_plan.inc (host only), the call's arithmetic orcgpu_filter_host.inc (host only), the kernels
+// device/filter_kernels.hip; what is left here touches the device.
 //
 // One filtered result costs ONE host wait: behind evaluate -> scan -> place -> count the host fetches the kept row count with
-// the per-batch null counts and string byte totals (result_filter_plan, "the filter's one wait"); with them it lays the
+// the per-batch null counts and string byte totals (filter_run_front, "the filter's one wait"); with them it lays the
 // output arena out compactly -- so that a copy back moves the kept rows' bytes and no more -- and enqueues the gather, which
 // nobody waits for: orcgpu_result_fetch_async orders its copies behind the decode stream.
-#include "orcgpu_filter_plan.inc"
+#include "orcgpu_filter_host.inc"
 namespace {
+
+static_assert(kFilterAlign == kAlign && kFilterColBytes == sizeof(FilterCol) && kFilterJobBytes == sizeof(FilterGatherJob) && kFilterSegBytes == sizeof(SelBatch),
+              "orcgpu_filter_host.inc states the alignment and the sizes of the device's structs");
 
 int enc_scan(orcgpu_ctx* ctx, hipStream_t st, const uint32_t* d_in, uint64_t count, uint64_t* d_sums, uint64_t* d_total, uint64_t* d_out);
 
-int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept,
-                       const char* const* column_names = nullptr, uint32_t n_names = 0) {
-  if (rows_seen) *rows_seen = 0;
-  if (rows_kept) *rows_kept = 0;
-  if (r->status) return r->status;  // a failed decode is left as it is
+// One filter call: what its steps hand on
+struct FilterCall {
+  orcgpu_ctx* ctx;
+  orcgpu_result* r;
+  const orcgpu_host::FilterPlan& plan;
+  uint32_t nc = 0, B = 0, W = 0;
+  std::vector<SelBatch> segs;       // the input rows: those of a row selection's batches (none: the stripe's) ...
+  std::vector<uint64_t> seg_first;  // ... and the input row each starts at
+  uint64_t n_in = 0;
+  std::vector<FilterColDesc> descs;
+  std::vector<FilterCol> fcols;
+  uint8_t* X = nullptr;  // the workspace on the device
+  template <typename T>
+  T* at(uint64_t off) const { return reinterpret_cast<T*>(X + off); }
+};
+
+int filter_refuse(orcgpu_ctx* ctx, const orcgpu_result* r) {
   if (r->hold && orcgpu_hold::hold_exported(r->hold)) {
     set_err(ctx, "a result that exported device batches still view cannot be filtered");
     return ORCGPU_INVALID_ARGUMENT;
@@ -23,9 +39,7 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
     set_err(ctx, "a row filter has already been applied to this result");
     return ORCGPU_INVALID_ARGUMENT;
   }
-  const uint32_t nc = (uint32_t)r->cols.size();
-  for (uint32_t c = 0; c < nc; c++) {
-    const ColumnOut& co = r->cols[c];
+  for (const ColumnOut& co : r->cols) {
     if (co.is_struct || co.is_union || co.is_list || co.elem || co.parent >= 0 || !r->subs.empty()) {
       set_err(ctx, "row filter: column %u of the result is nested (Struct / List / Map / Union are not filtered)", co.column_id);
       return ORCGPU_UNSUPPORTED;
@@ -35,273 +49,224 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
       return ORCGPU_UNSUPPORTED;
     }
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return ORCGPU_OK;
+}
+
+void filter_segments(FilterCall& f) {
+  f.n_in = f.r->n_rows;
+  if (!f.r->selected) return;
+  f.n_in = 0;
+  for (auto& b : f.r->sel) {
+    f.seg_first.push_back(f.n_in);
+    f.segs.push_back(b);
+    f.n_in += b.len;
+  }
+}
+
+void filter_describe(FilterCall& f) {
+  for (const ColumnOut& co : f.r->cols)  // (in the order FilterColDesc declares them)
+    f.descs.push_back({co.orc_type, co.width, co.ts_unit, co.is_bool, co.is_string, co.has_present, co.dict_out, co.dict_decoded, co.dict_len, co.dict_bytes});
+}
+
+// The columns as the kernels see them, with pointers into the decode's arenas; the char bases of the string columns go into the
+// first upload (`host`)
+void filter_fill_cols(FilterCall& f, const FilterWorkspace& ws, uint32_t src_batches, uint8_t* host) {
+  f.fcols.resize(f.nc);
+  for (uint32_t c = 0; c < f.nc; c++) {
+    const ColumnOut& co = f.r->cols[c];
+    const uint8_t* A = f.r->arena[co.lane].p;
+    FilterCol& fc = f.fcols[c];
+    memset(&fc, 0, sizeof(fc));
+    fc.validity = co.has_present && f.r->n_rows ? reinterpret_cast<const unsigned long long*>(A + co.validity_off) : nullptr;
+    fc.width = co.width;
+    fc.kind = filter_col_kind(f.descs[c]);
+    if (co.is_string) {
+      fc.offsets = reinterpret_cast<const int32_t*>(A + co.offsets_off);
+      fc.chars = (co.values_in_chars ? f.r->chars[co.lane].p : A) + co.values_off;
+      fc.char_base = f.at<const unsigned long long>(ws.o_cbase[c]);
+      for (size_t k = 0; k < co.char_base.size() && k < src_batches; k++) reinterpret_cast<uint64_t*>(host + ws.o_cbase[c])[k] = co.char_base[k];
+    } else fc.values = A + co.values_off;
+  }
+}
+
+int filter_check(FilterCall& f, const char* const* column_names, uint32_t n_names) {
+  std::vector<uint32_t> kinds(f.nc);
+  for (uint32_t c = 0; c < f.nc; c++) kinds[c] = f.fcols[c].kind;
+  uint32_t col = 0;
+  const int rc = filter_check_kinds(f.plan, kinds.data(), f.descs.data(), f.nc, &col);
+  if (rc == ORCGPU_UNSUPPORTED) {
+    if (column_names && col < n_names) set_err(f.ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[col]);
+    else set_err(f.ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", f.r->cols[col].column_id);
+  } else if (rc) set_err(f.ctx, "row filter: column %u is not decoded to the type its comparison needs", col < f.nc ? f.r->cols[col].column_id : col);
+  return rc;
+}
+
+// The first upload, then plane kernels -> evaluate -> scan -> place -> count, and the filter's one wait: `back` gets the kept
+// row count, then null counts and string bytes per (column, output batch)
+int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host, std::vector<uint64_t>& back) {
+  orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
-  const uint32_t B = r->batch, W = r->words_per_batch;
-  // ---- the input rows: the stripe's, or those of a row selection's batches ----
-  std::vector<SelBatch> segs;
-  std::vector<uint64_t> seg_first;
-  uint64_t n_in = r->n_rows;
-  if (r->selected) {
-    n_in = 0;
-    for (auto& b : r->sel) {
-      seg_first.push_back(n_in);
-      segs.push_back(b);
-      n_in += b.len;
-    }
+  const orcgpu_host::FilterPlan& plan = f.plan;
+  const uint32_t n_segs = (uint32_t)f.segs.size(), n_insn = (uint32_t)plan.prog.size(), n_like = (uint32_t)plan.like_leaves.size(), n_set = (uint32_t)plan.in_leaves.size();
+  if (n_insn) memcpy(host.data() + ws.o_prog, plan.prog.data(), n_insn * sizeof(FilterInsn));
+  if (!plan.lits.empty()) memcpy(host.data() + ws.o_lits, plan.lits.data(), plan.lits.size());
+  if (n_like) memcpy(host.data() + ws.o_leaves, plan.like_leaves.data(), (size_t)n_like * 4);
+  if (n_set) memcpy(host.data() + ws.o_leaves + (size_t)n_like * 4, plan.in_leaves.data(), (size_t)n_set * 4);
+  if (n_segs) {
+    memcpy(host.data() + ws.o_segs, f.segs.data(), (size_t)n_segs * sizeof(SelBatch));
+    memcpy(host.data() + ws.o_first, f.seg_first.data(), (size_t)n_segs * 8);
   }
-  const uint32_t n_segs = (uint32_t)segs.size();
-  const uint64_t n_words = (n_in + 63) / 64, nb_max = (n_in + B - 1) / B;
-  if (rows_seen) *rows_seen = n_in;
-  // ---- temporaries: tables that go up in one copy, then what the kernels leave ----
-  Bump t;
-  const uint64_t o_prog = t.take(plan.prog.size() * sizeof(FilterInsn) + 16), o_lits = t.take(plan.lits.size() + 16);
-  const uint64_t o_cols = t.take((uint64_t)nc * sizeof(FilterCol) + 16), o_segs = t.take((uint64_t)n_segs * sizeof(SelBatch) + 16);
-  const uint64_t o_first = t.take((uint64_t)n_segs * 8 + 16);
-  std::vector<uint64_t> o_cbase(nc, 0);
-  const uint32_t src_batches = r->selected ? r->full_batches : r->n_batches;  // uniform batches of the decode
-  for (uint32_t c = 0; c < nc; c++)
-    if (r->cols[c].is_string) o_cbase[c] = t.take((uint64_t)src_batches * 8 + 16);
-  const uint64_t up_bytes = t.off;
-  const uint64_t o_keep = t.take(n_words * 8 + 16), o_cnt = t.take(n_words * 4 + 16), o_woff = t.take(n_words * 8 + 16);
-  const uint64_t o_sums = t.take(((n_words + 2047) / 2048) * 8 + 16);
-  const uint64_t n_counters = 1 + 2ull * nc * nb_max;  // the kept row count, then null counts and string bytes [column][batch]
-  const uint64_t o_counters = t.take(n_counters * 8 + 16), o_rows = t.take(n_in * 4 + 16);
-  // (the LIKE and IN leaves' planes of match bits, numbered together and laid out like `keep`: part of this workspace, which
-  // only ever grows)
-  uint32_t n_like = 0, n_set = 0;
-  for (auto& in : plan.prog) {
-    n_like += in.op == FOP_LIKE && in.cmp != LIKE_ALL;
-    n_set += in.op == FOP_IN && !(in.cmp & IN_NO_TABLE);
+  if (f.nc) memcpy(host.data() + ws.o_cols, f.fcols.data(), (size_t)f.nc * sizeof(FilterCol));
+  if (!f.n_in) return ORCGPU_OK;
+  const FilterInsn* d_prog = f.at<const FilterInsn>(ws.o_prog);
+  const uint8_t* d_lits = f.at<const uint8_t>(ws.o_lits);
+  const uint32_t* d_leaves = f.at<const uint32_t>(ws.o_leaves);
+  const FilterCol* d_cols = f.at<const FilterCol>(ws.o_cols);
+  const SelBatch* d_segs = f.at<const SelBatch>(ws.o_segs);
+  const unsigned long long* d_first = f.at<const unsigned long long>(ws.o_first);
+  unsigned long long *d_counters = f.at<unsigned long long>(ws.o_counters), *d_keep = f.at<unsigned long long>(ws.o_keep), *d_planes = f.at<unsigned long long>(ws.o_planes);
+  uint32_t* d_rows = f.at<uint32_t>(ws.o_rows);
+  const uint32_t nb_max = (uint32_t)ws.nb_max, n_planes = n_like + n_set;
+  HIP_TRY(ctx, ctx->upload(f.X, host.data(), ws.up_bytes, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_counters, 0, ws.n_counters * 8, st));
+  const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((ws.n_words + 3) / 4, 16384);
+  if (n_like) {  // the matcher first: the evaluation reads its bits
+    hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_like), dim3(256), 0, st, d_prog, n_insn, d_leaves, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W,
+                       d_planes, n_planes);
+    HIP_TRY(ctx, hipGetLastError());
   }
-  const uint32_t n_planes = n_like + n_set;
-  const uint64_t o_like = t.take((uint64_t)n_planes * n_words * 8 + 16);
-  // (the second upload, behind the wait: the gather's jobs and the char bases of the output batches)
-  const uint64_t o_jobs = t.take((uint64_t)nc * sizeof(FilterGatherJob) + 16), o_obase = t.take((uint64_t)nc * nb_max * 8 + 16);
-  if (!r->filt_tmp.ensure(t.off + kAlign)) {
-    set_err(ctx, "hipMalloc(%llu) for the row filter failed", (unsigned long long)t.off);
+  if (n_set) {  // ... and the set membership of the IN leaves
+    hipLaunchKernelGGL(filter_in_kernel, dim3(eval_blocks, n_set), dim3(256), 0, st, d_prog, n_insn, d_leaves + n_like, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W,
+                       d_planes, n_planes);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, d_prog, n_insn, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W, d_keep,
+                     f.at<uint32_t>(ws.o_cnt), d_planes);
+  HIP_TRY(ctx, hipGetLastError());
+  const int rc = enc_scan(ctx, st, f.at<const uint32_t>(ws.o_cnt), ws.n_words, f.at<uint64_t>(ws.o_sums), reinterpret_cast<uint64_t*>(d_counters), f.at<uint64_t>(ws.o_woff));
+  if (rc) return rc;
+  hipLaunchKernelGGL(filter_place_kernel, dim3((uint32_t)((f.n_in + 255) / 256)), dim3(256), 0, st, d_keep, f.at<const unsigned long long>(ws.o_woff), d_segs, d_first, n_segs,
+                     f.n_in, d_rows);
+  HIP_TRY(ctx, hipGetLastError());
+  for (uint32_t o = 0; o < f.nc; o += 65535u)
+    hipLaunchKernelGGL(filter_count_kernel, dim3(nb_max, std::min<uint32_t>(65535u, f.nc - o)), dim3(256), 0, st, d_cols + o, d_rows, d_counters, f.B, f.W, nb_max,
+                       d_counters + 1 + (uint64_t)o * nb_max, d_counters + 1 + ((uint64_t)f.nc + o) * nb_max);
+  HIP_TRY(ctx, hipGetLastError());
+  // ---- the filter's one wait: the kept row count, null counts and string bytes per output batch ----
+  HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_counters, ws.n_counters * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return ORCGPU_OK;
+}
+
+// The kept rows into the output arena as `out` places them: the dictionaries that go along, the second upload, the gather
+int filter_run_gather(FilterCall& f, const FilterWorkspace& ws, const FilterOutput& out, uint64_t kept) {
+  orcgpu_ctx* ctx = f.ctx;
+  orcgpu_result* r = f.r;
+  hipStream_t st = ctx->stream;
+  if (!r->filt_arena.ensure(out.arena_bytes + kAlign)) {
+    set_err(ctx, "hipMalloc(%llu) for the filtered rows failed", (unsigned long long)out.arena_bytes);
     return ORCGPU_HIP_ERROR;
   }
-  uint8_t* X = r->filt_tmp.p;
-  std::vector<uint8_t> host(up_bytes, 0);
-  if (!plan.prog.empty()) memcpy(host.data() + o_prog, plan.prog.data(), plan.prog.size() * sizeof(FilterInsn));
-  if (!plan.lits.empty()) memcpy(host.data() + o_lits, plan.lits.data(), plan.lits.size());
-  if (n_segs) {
-    memcpy(host.data() + o_segs, segs.data(), (size_t)n_segs * sizeof(SelBatch));
-    memcpy(host.data() + o_first, seg_first.data(), (size_t)n_segs * 8);
-  }
-  std::vector<FilterCol> fcols(nc);
-  for (uint32_t c = 0; c < nc; c++) {
+  uint8_t* O = r->filt_arena.p;
+  std::vector<uint8_t> up2(ws.up2_bytes, 0);
+  FilterGatherJob* jobs = reinterpret_cast<FilterGatherJob*>(up2.data());
+  for (uint32_t c = 0; c < f.nc; c++) {
+    FilterGatherJob& j = jobs[c];
+    const FilterPlace& p = out.place[c];
+    j.src = f.fcols[c];
+    j.out_validity = p.has_validity ? reinterpret_cast<unsigned long long*>(O + p.validity) : nullptr;
+    j.out_values = O + p.values;
+    j.out_chars = O + p.values;
+    j.out_offsets = reinterpret_cast<int32_t*>(O + p.offsets);
+    j.out_char_base = f.at<const unsigned long long>(ws.o_obase) + (uint64_t)c * ws.nb_max;
     const ColumnOut& co = r->cols[c];
+    if (!co.dict_out || !co.dict_decoded) continue;
     const uint8_t* A = r->arena[co.lane].p;
-    FilterCol& f = fcols[c];
-    memset(&f, 0, sizeof(f));
-    f.validity = co.has_present && r->n_rows ? reinterpret_cast<const unsigned long long*>(A + co.validity_off) : nullptr;
-    f.width = co.width;
-    if (co.is_bool) {
-      f.kind = FKIND_BOOL;
-      f.values = A + co.values_off;
-    } else if (co.is_string) {
-      f.kind = FKIND_STRING;
-      f.offsets = reinterpret_cast<const int32_t*>(A + co.offsets_off);
-      f.chars = (co.values_in_chars ? r->chars[co.lane].p : A) + co.values_off;
-      f.char_base = reinterpret_cast<const unsigned long long*>(X + o_cbase[c]);
-      for (size_t k = 0; k < co.char_base.size() && k < src_batches; k++) reinterpret_cast<uint64_t*>(host.data() + o_cbase[c])[k] = co.char_base[k];
-    } else {
-      const int ot = co.orc_type;
-      const bool is_int = ot == ORCGPU_T_BYTE || ot == ORCGPU_T_SHORT || ot == ORCGPU_T_INT || ot == ORCGPU_T_LONG || ot == ORCGPU_T_DATE;
-      const bool is_float = ot == ORCGPU_T_FLOAT || ot == ORCGPU_T_DOUBLE;
-      // (a value narrower or wider than the type's own -- with_schema -- is still compared as what it is: 1 / 2 / 4 / 8 bytes)
-      // (a Timestamp decoded to an int64 unit is compared as the integer it is; decoded to Decimal128(38, 9) it is not compared)
-      const bool is_ts = (ot == ORCGPU_T_TIMESTAMP || ot == ORCGPU_T_TIMESTAMP_INSTANT) && co.ts_unit <= 3 && co.width == 8;
-      const bool is_dec = ot == ORCGPU_T_DECIMAL && co.width == 16;
-      f.kind = (is_int && co.width <= 8) || is_ts ? FKIND_INT
-               : (is_float && (co.width == 4 || co.width == 8) ? FKIND_FLOAT : (is_dec ? FKIND_DEC128 : FKIND_OTHER));
-      f.values = A + co.values_off;
-    }
+    HIP_TRY(ctx, hipMemcpyAsync(O + p.dict_offsets, A + co.dict_offsets_off, (co.dict_len + 1) * 4, hipMemcpyDeviceToDevice, st));
+    if (co.dict_bytes) HIP_TRY(ctx, hipMemcpyAsync(O + p.dict_values, A + co.dict_values_off, co.dict_bytes, hipMemcpyDeviceToDevice, st));
   }
-  for (auto& in : plan.prog) {  // (the plan was compiled against these columns' types; what the decode made of them must fit)
-    if (!fop_reads_values(in.op)) continue;
-    if (in.col < nc && r->cols[in.col].dict_out) {  // (string predicates evaluated on the entries: not yet)
-      if (column_names && in.col < n_names) set_err(ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[in.col]);
-      else set_err(ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", r->cols[in.col].column_id);
-      return ORCGPU_UNSUPPORTED;
-    }
-    const uint32_t want = in.op == FOP_IN ? (uint32_t)in.lo : in.op == FOP_CMP_INT ? FKIND_INT : in.op == FOP_CMP_FLOAT ? FKIND_FLOAT : in.op == FOP_CMP_BOOL ? FKIND_BOOL : in.op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
-    if (in.col >= nc || fcols[in.col].kind != want) {
-      set_err(ctx, "row filter: column %u is not decoded to the type its comparison needs", in.col < nc ? r->cols[in.col].column_id : in.col);
-      return ORCGPU_MISMATCHED_SCHEMA;
-    }
-  }
-  if (nc) memcpy(host.data() + o_cols, fcols.data(), (size_t)nc * sizeof(FilterCol));
-  const FilterCol* d_cols = reinterpret_cast<const FilterCol*>(X + o_cols);
-  const SelBatch* d_segs = reinterpret_cast<const SelBatch*>(X + o_segs);
-  const unsigned long long* d_first = reinterpret_cast<const unsigned long long*>(X + o_first);
-  unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(X + o_counters);
-  uint32_t* d_rows = reinterpret_cast<uint32_t*>(X + o_rows);
-  std::vector<uint64_t> back(n_counters, 0);
-  if (n_in) {
-    HIP_TRY(ctx, ctx->upload(X, host.data(), up_bytes, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_counters, 0, n_counters * 8, st));
-    const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((n_words + 3) / 4, 16384);
-    if (n_like) {  // the matcher first: the evaluation reads its bits
-      hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_planes), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
-                         reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W, reinterpret_cast<unsigned long long*>(X + o_like));
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    if (n_set) {  // ... and the set membership of the IN leaves (a block of either kernel whose plane is the other's leaves at once)
-      hipLaunchKernelGGL(filter_in_kernel, dim3(eval_blocks, n_planes), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
-                         reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W, reinterpret_cast<unsigned long long*>(X + o_like));
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, reinterpret_cast<const FilterInsn*>(X + o_prog), (uint32_t)plan.prog.size(),
-                       reinterpret_cast<const uint8_t*>(X + o_lits), d_cols, d_segs, d_first, n_segs, n_in, B, W,
-                       reinterpret_cast<unsigned long long*>(X + o_keep), reinterpret_cast<uint32_t*>(X + o_cnt),
-                       reinterpret_cast<const unsigned long long*>(X + o_like));
-    HIP_TRY(ctx, hipGetLastError());
-    int rc = enc_scan(ctx, st, reinterpret_cast<const uint32_t*>(X + o_cnt), n_words, reinterpret_cast<uint64_t*>(X + o_sums),
-                      reinterpret_cast<uint64_t*>(d_counters), reinterpret_cast<uint64_t*>(X + o_woff));
-    if (rc) return rc;
-    hipLaunchKernelGGL(filter_place_kernel, dim3((uint32_t)((n_in + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(X + o_keep),
-                       reinterpret_cast<const unsigned long long*>(X + o_woff), d_segs, d_first, n_segs, n_in, d_rows);
-    HIP_TRY(ctx, hipGetLastError());
-    for (uint32_t o = 0; o < nc; o += 65535u)
-      hipLaunchKernelGGL(filter_count_kernel, dim3((uint32_t)nb_max, std::min<uint32_t>(65535u, nc - o)), dim3(256), 0, st, d_cols + o, d_rows,
-                         reinterpret_cast<const unsigned long long*>(d_counters), B, W, (uint32_t)nb_max, d_counters + 1 + (uint64_t)o * nb_max,
-                         d_counters + 1 + ((uint64_t)nc + o) * nb_max);
-    HIP_TRY(ctx, hipGetLastError());
-    // ---- the filter's one wait: the kept row count, null counts and string bytes per output batch ----
-    HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_counters, n_counters * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  const uint64_t kept = back[0];
-  if (kept > n_in) {
-    set_err(ctx, "row filter: %llu rows kept of %llu", (unsigned long long)kept, (unsigned long long)n_in);
-    return ORCGPU_UNEXPECTED;
-  }
-  const uint32_t nbo = (uint32_t)((kept + B - 1) / B);
-  auto nulls_of = [&](uint32_t c, uint32_t k) { return back[1 + (uint64_t)c * nb_max + k]; };
-  auto bytes_of = [&](uint32_t c, uint32_t k) { return back[1 + ((uint64_t)nc + c) * nb_max + k]; };
-  // ---- the output arena, compact: per column what a decode of `kept` rows would hold ----
-  Bump a;
-  std::vector<FilterGatherJob> jobs(nc);
-  std::vector<uint64_t> obase((size_t)nc * nb_max, 0);
-  struct Place {
-    uint64_t validity = 0, values = 0, offsets = 0, dict_offsets = 0, dict_values = 0;
-    bool has_validity = false;
-  };
-  std::vector<Place> place(nc);
-  int status = 0;
-  uint32_t err_batch = 0, err_col = 0;
-  for (uint32_t c = 0; c < nc; c++) {
-    const ColumnOut& co = r->cols[c];
-    Place& p = place[c];
-    uint64_t nulls = 0, bytes = 0;
-    for (uint32_t k = 0; k < nbo; k++) {
-      nulls += nulls_of(c, k);
-      obase[(size_t)c * nb_max + k] = bytes;
-      bytes += bytes_of(c, k);
-      // OffsetOverflow (string.rs:139-140: the offsets of a batch are i32), as the decoder's check of its uniform batches
-      if (co.is_string && bytes_of(c, k) > 0x7fffffffull && (!status || k < err_batch)) {
-        status = ORCGPU_OFFSET_OVERFLOW;
-        err_batch = k;
-        err_col = c;
-      }
-    }
-    p.has_validity = nulls != 0;
-    if (p.has_validity) p.validity = a.take((uint64_t)nbo * W * 8 + 16);
-    if (co.is_bool) p.values = a.take((uint64_t)nbo * W * 8 + 16);
-    else if (co.is_string) {
-      p.offsets = a.take((uint64_t)nbo * (B + 1) * 4 + 16);
-      p.values = a.take(bytes + 16);
-    } else p.values = a.take(kept * co.width + 16);
-    if (co.dict_out && co.dict_decoded) {  // the stripe's dictionary goes along untouched: this arena is all that is copied back
-      p.dict_offsets = a.take((co.dict_len + 1) * 4 + 16);
-      p.dict_values = a.take(co.dict_bytes + 16);
-    }
-  }
-  r->filt_used = kept ? a.off : 0;
-  if (kept) {
-    if (!r->filt_arena.ensure(a.off + kAlign)) {
-      set_err(ctx, "hipMalloc(%llu) for the filtered rows failed", (unsigned long long)a.off);
-      return ORCGPU_HIP_ERROR;
-    }
-    uint8_t* O = r->filt_arena.p;
-    for (uint32_t c = 0; c < nc; c++) {
-      FilterGatherJob& j = jobs[c];
-      memset(&j, 0, sizeof(j));
-      j.src = fcols[c];
-      const Place& p = place[c];
-      j.out_validity = p.has_validity ? reinterpret_cast<unsigned long long*>(O + p.validity) : nullptr;
-      j.out_values = O + p.values;
-      j.out_chars = O + p.values;
-      j.out_offsets = reinterpret_cast<int32_t*>(O + p.offsets);
-      j.out_char_base = reinterpret_cast<const unsigned long long*>(X + o_obase) + (uint64_t)c * nb_max;
-    }
-    for (uint32_t c = 0; c < nc; c++) {
-      const ColumnOut& co = r->cols[c];
-      if (!co.dict_out || !co.dict_decoded) continue;
-      const uint8_t* A = r->arena[co.lane].p;
-      HIP_TRY(ctx, hipMemcpyAsync(O + place[c].dict_offsets, A + co.dict_offsets_off, (co.dict_len + 1) * 4, hipMemcpyDeviceToDevice, st));
-      if (co.dict_bytes) HIP_TRY(ctx, hipMemcpyAsync(O + place[c].dict_values, A + co.dict_values_off, co.dict_bytes, hipMemcpyDeviceToDevice, st));
-    }
-    std::vector<uint8_t> up2(o_obase + obase.size() * 8 - o_jobs, 0);
-    memcpy(up2.data(), jobs.data(), (size_t)nc * sizeof(FilterGatherJob));
-    memcpy(up2.data() + (o_obase - o_jobs), obase.data(), obase.size() * 8);
-    HIP_TRY(ctx, ctx->upload(X + o_jobs, up2.data(), up2.size(), st));
-    for (uint32_t o = 0; o < nc; o += 65535u)
-      hipLaunchKernelGGL(filter_gather_kernel, dim3(nbo, std::min<uint32_t>(65535u, nc - o)), dim3(256), 0, st,
-                         reinterpret_cast<const FilterGatherJob*>(X + o_jobs) + o, d_rows, kept, B, W);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  // ---- the result now speaks in the kept rows: uniform batches in the filter's own arena ----
-  r->arrow_bytes = 0;
-  for (uint32_t c = 0; c < nc; c++) {
+  if (!out.obase.empty()) memcpy(up2.data() + (ws.o_obase - ws.o_jobs), out.obase.data(), out.obase.size() * 8);
+  HIP_TRY(ctx, ctx->upload(f.X + ws.o_jobs, up2.data(), up2.size(), st));
+  for (uint32_t o = 0; o < f.nc; o += 65535u)
+    hipLaunchKernelGGL(filter_gather_kernel, dim3(out.nbo, std::min<uint32_t>(65535u, f.nc - o)), dim3(256), 0, st, f.at<const FilterGatherJob>(ws.o_jobs) + o,
+                       f.at<const uint32_t>(ws.o_rows), kept, f.B, f.W);
+  HIP_TRY(ctx, hipGetLastError());
+  return ORCGPU_OK;
+}
+
+// The result now speaks in the kept rows: uniform batches in the filter's own arena
+void filter_adopt_output(orcgpu_result* r, FilterOutput& out, uint64_t kept) {
+  for (size_t c = 0; c < r->cols.size(); c++) {
     ColumnOut& co = r->cols[c];
-    const Place& p = place[c];
+    FilterPlace& p = out.place[c];
     co.lane = 0;
     co.values_in_chars = false;
     co.validity_off = p.validity;
     co.values_off = p.values;
     co.offsets_off = p.offsets;
     if (co.dict_out) {
-      if (!kept) {  // (no batch is left to refer to it)
-        co.dict_len = co.dict_bytes = 0;
-        co.dict_decoded = false;
-      }
-      co.dict_offsets_off = kept ? p.dict_offsets : 0;
-      co.dict_values_off = kept ? p.dict_values : 0;
-      if (co.dict_decoded) r->arrow_bytes += (co.dict_len + 1) * 4 + co.dict_bytes;
+      if (!p.dict_kept) co.dict_len = co.dict_bytes = 0, co.dict_decoded = false;  // (no batch is left to refer to it)
+      co.dict_offsets_off = p.dict_kept ? p.dict_offsets : 0;
+      co.dict_values_off = p.dict_kept ? p.dict_values : 0;
     }
-    co.null_counts.assign(nbo, 0);
-    co.char_base.assign(co.is_string ? nbo : 0, 0);
-    co.char_total.assign(co.is_string ? nbo : 0, 0);
+    co.null_counts = std::move(p.null_counts);
+    co.char_base = std::move(p.char_base);
+    co.char_total = std::move(p.char_total);
     co.sel_nulls.clear();
     co.sel_char_start.clear();
     co.sel_char_total.clear();
-    for (uint32_t k = 0; k < nbo; k++) {
-      const uint64_t rows = std::min<uint64_t>(B, kept - (uint64_t)k * B);
-      co.null_counts[k] = nulls_of(c, k);
-      if (co.is_string) {
-        co.char_base[k] = obase[(size_t)c * nb_max + k];
-        co.char_total[k] = bytes_of(c, k);
-      }
-      r->arrow_bytes += co.is_string ? co.char_total[k] + 4 * (rows + 1) : (co.is_bool ? (rows + 7) / 8 : rows * co.width);
-      if (co.null_counts[k]) r->arrow_bytes += (rows + 7) / 8;
-    }
   }
+  r->arrow_bytes = out.arrow_bytes;
   r->n_rows = kept;
-  r->n_batches = nbo;
+  r->n_batches = out.nbo;
   r->selected = false;
   r->sel.clear();
   r->filtered = true;
   r->mirror_valid = false;
   r->dev_ready_recorded = false;
-  if (status) {
-    r->status = status;
-    r->err_batch = err_batch;
-    r->err_col = err_col;
+  if (out.status) {
+    r->status = out.status;
+    r->err_batch = out.err_batch;
+    r->err_col = out.err_col;
   }
+}
+
+int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept,
+                       const char* const* column_names = nullptr, uint32_t n_names = 0) {
+  if (rows_seen) *rows_seen = 0;
+  if (rows_kept) *rows_kept = 0;
+  if (r->status) return r->status;  // a failed decode is left as it is
+  if (const int rc = filter_refuse(ctx, r)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  FilterCall f{ctx, r, plan};
+  f.nc = (uint32_t)r->cols.size();
+  f.B = r->batch;
+  f.W = r->words_per_batch;
+  filter_segments(f);
+  filter_describe(f);
+  if (rows_seen) *rows_seen = f.n_in;
+  const uint32_t src_batches = r->selected ? r->full_batches : r->n_batches;  // uniform batches of the decode
+  const FilterWorkspace ws(plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), src_batches, f.n_in, f.B);
+  if (!r->filt_tmp.ensure(ws.bytes + kAlign)) {
+    set_err(ctx, "hipMalloc(%llu) for the row filter failed", (unsigned long long)ws.bytes);
+    return ORCGPU_HIP_ERROR;
+  }
+  f.X = r->filt_tmp.p;
+  std::vector<uint8_t> host(ws.up_bytes, 0);
+  filter_fill_cols(f, ws, src_batches, host.data());
+  if (const int rc = filter_check(f, column_names, n_names)) return rc;
+  std::vector<uint64_t> back(ws.n_counters, 0);
+  if (const int rc = filter_run_front(f, ws, host, back)) return rc;
+  const uint64_t kept = back[0];
+  if (kept > f.n_in) {
+    set_err(ctx, "row filter: %llu rows kept of %llu", (unsigned long long)kept, (unsigned long long)f.n_in);
+    return ORCGPU_UNEXPECTED;
+  }
+  FilterOutput out = filter_place_output(f.descs.data(), back.data(), f.nc, ws.nb_max, kept, f.B, f.W);
+  r->filt_used = kept ? out.arena_bytes : 0;
+  if (kept)
+    if (const int rc = filter_run_gather(f, ws, out, kept)) return rc;
+  filter_adopt_output(r, out, kept);
   if (rows_kept) *rows_kept = kept;
   return ORCGPU_OK;
 }

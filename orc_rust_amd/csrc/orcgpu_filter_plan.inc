@@ -23,6 +23,9 @@ struct FilterPlan {
   std::vector<FilterInsn> prog;
   std::vector<uint8_t> lits;  // the string literals, one after the other
   uint32_t depth = 0;         // of the predicate (a leaf alone: 1)
+  // the leaves with a mask plane, as instruction indices in program order: the grids of filter_like_kernel and filter_in_kernel
+  std::vector<uint32_t> like_leaves, in_leaves;
+  size_t n_planes() const { return like_leaves.size() + in_leaves.size(); }  // (numbered together, in leaf order: FilterInsn::i)
   char err[256] = {0};
 };
 
@@ -54,6 +57,25 @@ struct FilterCompiler {
     in.cmp = cmp;
     in.col = col;
     out.prog.push_back(in);
+  }
+  // the bytes of a string literal: there when it has a length, and few enough for an int32 offset
+  int check_bytes(const char* s, uint64_t s_len, const char* column) {
+    if (s_len && !s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", column);
+    if (s_len > 0x7fffffffull) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' is longer than 2^31 - 1 bytes", column);
+    return ORCGPU_OK;
+  }
+  // ... checked and appended to the literal pool, as the literal of instruction `in`
+  int pool_bytes(const char* s, uint64_t s_len, const char* column, FilterInsn& in) {
+    if (const int rc = check_bytes(s, s_len, column)) return rc;
+    in.lit_off = out.lits.size();
+    in.lit_len = (uint32_t)s_len;
+    if (s_len) out.lits.insert(out.lits.end(), reinterpret_cast<const uint8_t*>(s), reinterpret_cast<const uint8_t*>(s) + s_len);
+    return ORCGPU_OK;
+  }
+  // the instruction about to be pushed takes the next mask plane and joins its kernel's leaf list
+  void take_plane(FilterInsn& in, std::vector<uint32_t>& leaves) {
+    in.i = (long long)out.n_planes();
+    leaves.push_back((uint32_t)out.prog.size());
   }
   // A Decimal128 literal -> (op', literal') at the column's own scale, so that the kernel compares unscaled values and never
   // rescales a row.  d = column scale - literal scale.  d >= 0: literal * 10^d, clamped to int128 where it leaves it -- no valid
@@ -207,13 +229,8 @@ struct FilterCompiler {
         } else if (kind == ORCGPU_T_TIMESTAMP || kind == ORCGPU_T_TIMESTAMP_INSTANT) {
           if (const int trc = timestamp(n, n.column, col, in)) return trc;
         }
-        if (in.op == FOP_CMP_STRING) {
-          if (n.s_len && !n.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", n.column);
-          if (n.s_len > 0x7fffffffull) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' is longer than 2^31 - 1 bytes", n.column);
-          in.lit_off = out.lits.size();
-          in.lit_len = (uint32_t)n.s_len;
-          if (n.s_len) out.lits.insert(out.lits.end(), reinterpret_cast<const uint8_t*>(n.s), reinterpret_cast<const uint8_t*>(n.s) + n.s_len);
-        }
+        if (in.op == FOP_CMP_STRING)
+          if (const int src = pool_bytes(n.s, n.s_len, n.column, in)) return src;
         out.prog.push_back(in);
         return ORCGPU_OK;
       }
@@ -273,9 +290,7 @@ struct FilterCompiler {
     if (pat.wildcard_free()) {
       in.op = FOP_CMP_STRING;
       in.cmp = ORCGPU_PRED_EQ;
-      in.lit_off = out.lits.size();
-      in.lit_len = (uint32_t)ne;
-      out.lits.insert(out.lits.end(), pat.bytes.begin(), pat.bytes.end());
+      if (const int src = pool_bytes(reinterpret_cast<const char*>(pat.bytes.data()), ne, n.column, in)) return src;
       out.prog.push_back(in);
       return ORCGPU_OK;
     }
@@ -305,7 +320,7 @@ struct FilterCompiler {
     in.op = FOP_LIKE;
     in.cmp = shape;
     if (shape != LIKE_ALL) {
-      in.i = n_planes++;  // its plane of match bits
+      take_plane(in, out.like_leaves);  // its plane of match bits
       while (out.lits.size() & 3) out.lits.push_back(0);
       in.lit_off = out.lits.size();
       std::vector<uint32_t> words = {shape, flags, np, (uint32_t)bytes.size()};
@@ -313,8 +328,8 @@ struct FilterCompiler {
         words.push_back(part_first[p]);
         words.push_back(part_len[p]);
       }
-      for (uint32_t w : words)
-        for (int b = 0; b < 4; b++) out.lits.push_back((uint8_t)(w >> (8 * b)));
+      out.lits.resize(in.lit_off + 4 * words.size());
+      for (size_t w = 0; w < words.size(); w++) put32(out.lits, in.lit_off + 4 * w, words[w]);
       out.lits.insert(out.lits.end(), bytes.begin(), bytes.end());
       out.lits.insert(out.lits.end(), ones.begin(), ones.end());
       in.lit_len = (uint32_t)(out.lits.size() - in.lit_off);
@@ -369,8 +384,7 @@ struct FilterCompiler {
         if (v <= -lim || v >= lim) continue;  // off the column's scale, or beyond every Decimal
         keys.add_dec128(eq.lo, eq.i);
       } else {
-        if (l.s_len && !l.s) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' has a length and no bytes", n.column);
-        if (l.s_len > 0x7fffffffull) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the literal for column '%s' is longer than 2^31 - 1 bytes", n.column);
+        if (const int src = check_bytes(l.s, l.s_len, n.column)) return src;
         bytes += l.s_len;
         if (bytes > ORCGPU_IN_MAX_BYTES)
           return fail(ORCGPU_UNSUPPORTED, "row filter: the IN list for column '%s' holds more than %lld bytes of literals", n.column, ORCGPU_IN_MAX_BYTES);
@@ -395,28 +409,23 @@ struct FilterCompiler {
       else if (fop == FOP_CMP_DEC128) {
         in.i = InKeys::dec_high(keys.k128[0]);
         in.lo = keys.k128[0].second;
-      } else {
-        in.lit_off = out.lits.size();
-        in.lit_len = (uint32_t)keys.kstr[0].size();
-        out.lits.insert(out.lits.end(), keys.kstr[0].begin(), keys.kstr[0].end());
-      }
+      } else if (const int src = pool_bytes(keys.kstr[0].data(), keys.kstr[0].size(), n.column, in)) return src;
       out.prog.push_back(in);
       return ORCGPU_OK;
     }
     in.op = FOP_IN;
     in.cmp = keys.has_null ? IN_HAS_NULL : 0;
-    in.lo = fop == FOP_CMP_INT ? FKIND_INT : fop == FOP_CMP_FLOAT ? FKIND_FLOAT : fop == FOP_CMP_BOOL ? FKIND_BOOL : fop == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
+    in.lo = fop_value_kind(fop);
     if (!nk || fop == FOP_CMP_BOOL) {
       in.cmp |= IN_NO_TABLE | (has_false ? IN_BOOL_FALSE : 0) | (has_true ? IN_BOOL_TRUE : 0);
       in.i = -1;
     } else {
-      in.i = n_planes++;
+      take_plane(in, out.in_leaves);
       in.lit_off = in_build_table(keys, in.cmp, out.lits, in.lit_len);
     }
     out.prog.push_back(in);
     return ORCGPU_OK;
   }
-  long long n_planes = 0;  // LIKE and IN leaves with a mask plane so far: the planes are numbered together
 };
 
 // ORCGPU_OK, or the status a reader with this filter ends with (out.err says why).  names[k] / kinds[k]: column k.
@@ -425,6 +434,8 @@ inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, 
                           FilterPlan& out, const int32_t* params = nullptr) {
   out.prog.clear();
   out.lits.clear();
+  out.like_leaves.clear();
+  out.in_leaves.clear();
   out.depth = 0;
   out.err[0] = 0;
   FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, params, out};

@@ -36,10 +36,11 @@ struct InKeys {
   size_t size() const { return kind == IN_KEY_I64 ? k64.size() : kind == IN_KEY_DEC128 ? k128.size() : kstr.size(); }
 };
 
-inline void in_put32(std::vector<uint8_t>& pool, size_t at, uint32_t v) {
+// little-endian words into the literal pool (the IN tables here, the LIKE patterns of orcgpu_filter_plan.inc)
+inline void put32(std::vector<uint8_t>& pool, size_t at, uint32_t v) {
   for (int b = 0; b < 4; b++) pool[at + b] = (uint8_t)(v >> (8 * b));
 }
-inline void in_put64(std::vector<uint8_t>& pool, size_t at, uint64_t v) {
+inline void put64(std::vector<uint8_t>& pool, size_t at, uint64_t v) {
   for (int b = 0; b < 8; b++) pool[at + b] = (uint8_t)(v >> (8 * b));
 }
 
@@ -65,7 +66,7 @@ inline uint64_t in_build_table(const InKeys& keys, uint32_t flags, std::vector<u
   total = (total + 7) & ~(size_t)7;
   pool.resize(base + total, 0);
   const uint32_t header[8] = {keys.kind, n_slots, n, min_len, max_len, flags, 0, 0};
-  for (int w = 0; w < 8; w++) in_put32(pool, base + 4 * w, header[w]);
+  for (int w = 0; w < 8; w++) put32(pool, base + 4 * w, header[w]);
   std::vector<uint64_t> occ(occ_words, 0);
   auto claim = [&](uint32_t hash) {  // the first free slot at or behind the hash's own
     uint32_t s = hash & (n_slots - 1);
@@ -74,27 +75,27 @@ inline uint64_t in_build_table(const InKeys& keys, uint32_t flags, std::vector<u
     return s;
   };
   if (keys.kind == IN_KEY_I64) {
-    for (uint64_t k : keys.k64) in_put64(pool, base + o_slots + 8 * (size_t)claim(in_hash_i64(k)), k);
+    for (uint64_t k : keys.k64) put64(pool, base + o_slots + 8 * (size_t)claim(in_hash_i64(k)), k);
   } else if (keys.kind == IN_KEY_DEC128) {
     for (auto& k : keys.k128) {
       const uint64_t hi = (uint64_t)InKeys::dec_high(k), lo = k.second;
       const size_t at = base + o_slots + 16 * (size_t)claim(in_hash_dec128(lo, hi));
-      in_put64(pool, at, lo);
-      in_put64(pool, at + 8, hi);
+      put64(pool, at, lo);
+      put64(pool, at + 8, hi);
     }
   } else {
     size_t off = o_bytes;
     for (const std::string& s : keys.kstr) {
       const uint32_t h = in_hash_bytes(reinterpret_cast<const uint8_t*>(s.data()), (uint32_t)s.size());
       const size_t at = base + o_slots + 16 * (size_t)claim(h);
-      in_put32(pool, at, h);
-      in_put32(pool, at + 4, (uint32_t)s.size());
-      in_put32(pool, at + 8, (uint32_t)off);
+      put32(pool, at, h);
+      put32(pool, at + 4, (uint32_t)s.size());
+      put32(pool, at + 8, (uint32_t)off);
       if (!s.empty()) memcpy(pool.data() + base + off, s.data(), s.size());
       off += s.size();
     }
   }
-  for (uint32_t w = 0; w < occ_words; w++) in_put64(pool, base + o_occ + 8 * (size_t)w, occ[w]);
+  for (uint32_t w = 0; w < occ_words; w++) put64(pool, base + o_occ + 8 * (size_t)w, occ[w]);
   len = (uint32_t)total;
   return base;
 }

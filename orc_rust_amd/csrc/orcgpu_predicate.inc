@@ -629,6 +629,25 @@ std::vector<PredNode> copy_predicate(const orcgpu_predicate_node* nodes, uint32_
   }
   return out;
 }
+// ... and back: the nodes as the C ABI spells them, viewing the strings of `nodes` (which must outlive the view)
+std::vector<orcgpu_predicate_node> view_predicate(const std::vector<PredNode>& nodes) {
+  std::vector<orcgpu_predicate_node> out(nodes.size());
+  for (size_t k = 0; k < nodes.size(); k++) {
+    const PredNode& p = nodes[k];
+    orcgpu_predicate_node& n = out[k];
+    memset(&n, 0, sizeof(n));
+    n.op = p.op;
+    n.n_children = p.n_children;
+    n.column = p.has_column ? p.column.c_str() : nullptr;
+    n.value_type = p.value_type;
+    n.value_is_null = p.value_is_null ? 1 : 0;
+    n.i = p.i;
+    n.f = p.f;
+    n.s = p.s.data();
+    n.s_len = p.s.size();
+  }
+  return out;
+}
 
 // evaluate_predicate: false = the evaluation is an Err (the reader then selects every row of the stripe)
 bool predicate_row_groups(const std::vector<PredNode>& nodes, const std::vector<std::string>& names, const std::vector<ColumnGroups>& cols,

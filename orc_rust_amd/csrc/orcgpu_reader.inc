@@ -819,21 +819,7 @@ int reader_compile_filter(orcgpu_reader* rd) {
     c.arrow_target = rd->has_schema ? rd->col_target[k] : rd->ts_arrow_target;
     params.push_back(t.kind == ORCGPU_T_DECIMAL ? (int32_t)t.scale : ts_unit_of(c));
   }
-  std::vector<orcgpu_predicate_node> nodes(rd->filter_nodes.size());
-  for (size_t k = 0; k < nodes.size(); k++) {
-    const PredNode& p = rd->filter_nodes[k];
-    orcgpu_predicate_node& n = nodes[k];
-    memset(&n, 0, sizeof(n));
-    n.op = p.op;
-    n.n_children = p.n_children;
-    n.column = p.has_column ? p.column.c_str() : nullptr;
-    n.value_type = p.value_type;
-    n.value_is_null = p.value_is_null ? 1 : 0;
-    n.i = p.i;
-    n.f = p.f;
-    n.s = p.s.data();
-    n.s_len = p.s.size();
-  }
+  const std::vector<orcgpu_predicate_node> nodes = view_predicate(rd->filter_nodes);
   const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan, params.data());
   if (rc) set_err(rd->ctx, "%s", rd->filter_plan.err);
   if (rc) return rc;

@@ -13,6 +13,7 @@
 // ... and for the node lists built in here:
 //   bad <name> <status> <1 when the message names the column>
 //   planes <op, i and cmp of every instruction of a program with two IN leaves and a LIKE leaf>
+//   leaves like <instruction indices of that program's LIKE leaves with a plane> in <... of its IN leaves with a table>
 //   depth <status of an IN leaf at the deepest level allowed> <status one level deeper>
 // Exit code 0 whenever the compiler RETURNED; a sanitizer report aborts with its own exit code.
 #include <cstdint>
@@ -207,6 +208,10 @@ int main(int argc, char** argv) {
     if (filter_compile(nodes.data(), (uint32_t)nodes.size(), kNames, kKinds, kColumns, plan, kParams)) abort();
     printf("planes");
     for (const FilterInsn& in : plan.prog) printf(" %u:%lld:%u", in.op, in.i, in.cmp);
+    printf("\nleaves like");
+    for (uint32_t k : plan.like_leaves) printf(" %u", k);
+    printf(" in");
+    for (uint32_t k : plan.in_leaves) printf(" %u", k);
     printf("\n");
     for (const FilterInsn& in : plan.prog)
       if (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE) && ((in.lit_off & 7) || in.lit_off + in.lit_len > plan.lits.size())) abort();

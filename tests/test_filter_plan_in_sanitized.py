@@ -221,5 +221,9 @@ def test_malformed_node_lists_and_a_program_of_several_leaves(lines):
     # IN (1, 2) -> plane 0; IN (5) -> EQ; LIKE -> plane 1; the Boolean list -> no plane; IN ('xy', 'z') -> plane 2; IN () -> FALSE
     assert planes == [(FOP_IN, 0, 0), (FOP_CMP_INT, 5, EQ), (FOP_OR, 0, 0), (FOP_LIKE, 1, 1), (FOP_OR, 0, 0),
                       (FOP_IN, -1, IN_NO_TABLE | IN_BOOL_FALSE | IN_BOOL_TRUE), (FOP_OR, 0, 0), (FOP_IN, 2, 0), (FOP_OR, 0, 0), (FOP_FALSE, 0, 0), (FOP_OR, 0, 0)]
+    # the leaf lists the two plane kernels are launched over: the instruction indices of planes 0 and 2 (IN) and of plane 1 (LIKE)
+    leaves = [ln for ln in lines if ln[0] == "leaves"][0]
+    at = {i: k for k, (op, i, _) in enumerate(planes) if op in (FOP_IN, FOP_LIKE) and i >= 0}
+    assert leaves[1] == "like" and leaves[3] == "in" and [int(x) for x in leaves[2:3]] == [at[1]] == [3] and [int(x) for x in leaves[4:]] == [at[0], at[2]] == [0, 7]
     depth = [ln for ln in lines if ln[0] == "depth"][0]
     assert [int(x) for x in depth[1:]] == [OK, INVALID]
