@@ -555,6 +555,69 @@ int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_predica
 int orcgpu_reader_set_row_filter(orcgpu_reader* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes);
 /* Rows the row filter has seen (decoded rows, those of the row selection when there is one) and kept so far. */
 int orcgpu_reader_filter_rows(const orcgpu_reader* r, uint64_t* rows_seen, uint64_t* rows_kept);
+/* ---- aggregates over the kept rows: COUNT, SUM, MIN, MAX and SUM(a * b), reduced on the device ------------------------------
+ * A row filter hands the kept rows out; a query like TPC-H Q6 wants one number of them.  An aggregate list is reduced where the
+ * decoded rows lie (device/agg_kernels.hip), from the keep mask the filter's evaluation leaves: nothing is scanned, placed,
+ * gathered or copied back but one record per aggregate.  The reference has no aggregation; the semantics are fixed here.
+ *   - A KEPT row is one the row selection selects (if there is one) and for which the row filter's root is TRUE (if there is
+ *     one, under the rules above).  With neither, every row is kept.
+ *   - Null values are skipped; SUM_PRODUCT skips a row when either operand is null.  SUM, MIN, MAX and SUM_PRODUCT over no value
+ *     are NULL (is_null = 1); the counts are 0.
+ *   - COUNT_ROWS (no column): the kept rows.  COUNT: the kept rows whose value is not null; any root column, dictionary columns
+ *     included (String and Binary columns take COUNT only).  Both are ORCGPU_AGG_KIND_U64.
+ *   - SUM takes Byte .. Long, Float, Double and Decimal.  SUM_PRODUCT takes two Byte .. Long columns, two Float / Double columns
+ *     or two Decimal columns (a column with itself is fine).
+ *       Integers: SUM is exact as a signed 128-bit integer; SUM_PRODUCT multiplies exactly in 128 bits and accumulates in 192
+ *       bits.  ORCGPU_AGG_KIND_I128 in w[0..1]; overflow = 1 when the final value does not fit 128 bits.  The accumulators are wide
+ *       enough for every partial sum, so the result does not depend on the order of summation.
+ *       Decimal: the unscaled values are accumulated in 192 bits at the column's scale; SUM_PRODUCT at the scale s1 + s2 (more
+ *       than 38: ORCGPU_UNSUPPORTED, the message names the columns).  ORCGPU_AGG_KIND_DEC128 in w[0..1] with scale_or_unit = the
+ *       scale; overflow = 1 when the final |sum| >= 10^38, and -- SUM_PRODUCT, sticky -- when an operand of a row does not fit a
+ *       signed 64-bit word (Decimal(18, s) and narrower always fit).  The value of a result with overflow = 1 is unspecified.
+ *       Float / Double: accumulated as double (a Float32 widened first, a product rounded once); NaN and inf - inf give NaN as
+ *       IEEE says.  ORCGPU_AGG_KIND_F64 in f.  The sum is DETERMINISTIC: the same result, selection, filter and batch size give the
+ *       same bits on every run (a reduction of fixed shape, no floating-point atomics) -- but not the bits of another order.
+ *   - MIN, MAX take Byte .. Long, Date (days), Boolean (0 / 1) and Timestamp / Timestamp-instant decoded to an int64 unit:
+ *     ORCGPU_AGG_KIND_I64 in w[0], scale_or_unit = a Timestamp's unit (0 s, 1 ms, 2 us, 3 ns), else -1; Decimal: ORCGPU_AGG_KIND_DEC128
+ *     at the column's scale; Float / Double: ORCGPU_AGG_KIND_F64, NaN values skipped unless every kept non-null value is NaN, in
+ *     which case the result is NaN; -0.0 and 0.0 compare equal, either may come back.
+ *   - Any other (op, column kind) pair, and a SUM_PRODUCT of mixed kinds: ORCGPU_MISMATCHED_SCHEMA.  SUM, MIN, MAX or SUM_PRODUCT on
+ *     a column read as a dictionary column, or on a Timestamp decoded to Decimal128(38, 9): ORCGPU_UNSUPPORTED.  A nested column in
+ *     the result: ORCGPU_UNSUPPORTED.  A column that is not a projected root column, no spec or more than ORCGPU_AGG_MAX of them, an
+ *     unknown op: ORCGPU_INVALID_ARGUMENT.  Every message names the column. */
+#define ORCGPU_AGG_MAX 64
+enum { ORCGPU_AGG_OP_COUNT_ROWS = 0, ORCGPU_AGG_OP_COUNT = 1, ORCGPU_AGG_OP_SUM = 2, ORCGPU_AGG_OP_MIN = 3, ORCGPU_AGG_OP_MAX = 4, ORCGPU_AGG_OP_SUM_PRODUCT = 5 };
+enum { ORCGPU_AGG_KIND_U64 = 0, ORCGPU_AGG_KIND_I128 = 1, ORCGPU_AGG_KIND_DEC128 = 2, ORCGPU_AGG_KIND_F64 = 3, ORCGPU_AGG_KIND_I64 = 4 };
+typedef struct {
+  uint32_t op;          /* ORCGPU_AGG_OP_* */
+  const char* column;   /* NULL for COUNT_ROWS */
+  const char* column2;  /* SUM_PRODUCT: the second operand */
+} orcgpu_agg_spec;
+typedef struct {
+  uint32_t kind;        /* ORCGPU_AGG_KIND_* */
+  uint32_t is_null, overflow;
+  int32_t scale_or_unit;
+  uint64_t w[3];        /* little-endian words, two's complement: the count, the integer, the unscaled value */
+  double f;
+} orcgpu_agg_value;
+/* Aggregates the rows of a decoded result -- uniform, selected, or the kept rows a row filter left in it -- that the predicate
+ * keeps (n_nodes = 0: no filter).  column_names[i] names the result's column i for the leaves and the specs; out gets n_specs
+ * values.  The result is read and left as it was: the call may be repeated, and a filter applied afterwards gives what it gives
+ * without it.  A result whose status is not OK is refused with that status.  One host wait per call. */
+int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                            const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs, uint32_t n_specs,
+                            orcgpu_agg_value* out);
+/* A builder setter (before the first call; the specs and their strings are copied): the reader aggregates instead of handing
+ * out batches.  orcgpu_reader_aggregate then drains it -- every stripe it would read, under everything the builder set:
+ * projection, byte range, shard, timestamp precision, row selection, predicate and pruning, row filter, read-ahead -- and per
+ * stripe the aggregation takes the place of the filter's compaction and of the copy back: orcgpu_reader_d2h_bytes stays 0, one
+ * host wait per stripe.  The stripes' records are merged on the host in stripe order (integer and Decimal words added with
+ * carry, doubles added in stripe order, flags OR-ed).  orcgpu_reader_filter_rows reports seen and kept rows as under the filter.
+ * The projection must hold the aggregated and the filter's columns; whatever else it holds is decoded as always.  On such a
+ * reader orcgpu_reader_next_batch[_device] return ORCGPU_INVALID_ARGUMENT and leave it usable; orcgpu_reader_aggregate without
+ * aggregates set is ORCGPU_INVALID_ARGUMENT, a second call ORCGPU_END_OF_FILE. */
+int orcgpu_reader_set_aggregates(orcgpu_reader* r, const orcgpu_agg_spec* specs, uint32_t n_specs);
+int orcgpu_reader_aggregate(orcgpu_reader* r, orcgpu_agg_value* out);
 /* Read-ahead: how many decoded stripes the reader may be ahead of the caller (default 2 -- every result set in flight costs a pinned host copy of a stripe --, at most 8; 0 = none: every stripe is
  * read, staged, decoded and copied back inside the orcgpu_reader_next_batch call that needs it).  With read-ahead two threads
  * of the reader work beside the caller: one reads and stages the stripes to come, one decodes the stripes staged so far

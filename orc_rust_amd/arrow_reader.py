@@ -144,6 +144,23 @@ class ArrowReaderBuilder:
         self._device_output = bool(on)
         return self
 
+    def aggregate(self, specs, raw=False):
+        """COUNT, SUM, MIN, MAX and SUM(a * b) over the rows the builder's selection and row filter keep, reduced on the GPU
+        (orcgpu_reader_set_aggregates / orcgpu_reader_aggregate): specs is a list of orc_rust_amd.aggregate.Agg, the result a list
+        of int (counts, integer results; a Timestamp's with `.units`), decimal.Decimal, float, or None for NULL.  Builds the reader
+        and drains it: every stripe is decoded and aggregated where it lies, no batch is copied back.  The projection must hold the
+        aggregated and the filter's columns.  OverflowError, naming the spec, when a result leaves its range."""
+        return self.aggregating_reader(specs).aggregate(raw=raw)
+
+    def aggregating_reader(self, specs):
+        """The same in two steps: the ArrowReader whose aggregate() drains it (and whose filter_rows() / d2h_bytes() report on it)."""
+        from . import aggregate as A
+        arr, keep = A.spec_array(specs)
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregates(self._h, arr, len(arr)))
+        r = self.build()
+        r._agg_specs = A.check_specs(specs)
+        return r
+
     def total_row_count(self):
         return self._ctx.L.orcgpu_reader_total_rows(self._h)
 
@@ -185,6 +202,17 @@ class ArrowReader:
         n = C.c_uint64(0)
         self._ctx._check(self._ctx.L.orcgpu_reader_d2h_bytes(self._h, C.byref(n)))
         return n.value
+
+    def aggregate(self, raw=False):
+        """Drains a reader built by ArrowReaderBuilder.aggregating_reader (orcgpu_reader_aggregate): the list of Python values."""
+        from . import aggregate as A
+        specs = getattr(self, "_agg_specs", None)
+        out = (A.AggValue * max(1, len(specs or ())))()
+        rc = self._ctx.L.orcgpu_reader_aggregate(self._h, out)
+        if rc == 110:  # ORCGPU_END_OF_FILE: the reader has been drained before
+            raise StopIteration
+        self._ctx._check(rc)
+        return list(out)[:len(specs)] if raw else A.values_of(out, specs)
 
     def reads_ahead(self):
         """Whether the reader's read-ahead threads are at work on its context right now (orcgpu_reader_reads_ahead)"""

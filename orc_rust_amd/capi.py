@@ -26,6 +26,7 @@ EXPORTS = [
     "orcgpu_reader_set_row_group_pruning", "orcgpu_reader_row_groups", "orcgpu_index_entry", "orcgpu_reader_set_predicate",
     "orcgpu_predicate_row_groups",
     "orcgpu_result_filter", "orcgpu_reader_set_row_filter", "orcgpu_reader_filter_rows",
+    "orcgpu_result_aggregate", "orcgpu_reader_set_aggregates", "orcgpu_reader_aggregate",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
@@ -210,6 +211,11 @@ def load():
                                        C.POINTER(C.c_uint64)]
     L.orcgpu_reader_set_row_filter.argtypes = [C.c_void_p, C.POINTER(PredicateNode), C.c_uint32]
     L.orcgpu_reader_filter_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    from .aggregate import AggSpec, AggValue
+    L.orcgpu_result_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                          C.POINTER(AggSpec), C.c_uint32, C.POINTER(AggValue)]
+    L.orcgpu_reader_set_aggregates.argtypes = [C.c_void_p, C.POINTER(AggSpec), C.c_uint32]
+    L.orcgpu_reader_aggregate.argtypes = [C.c_void_p, C.POINTER(AggValue)]
     L.orcgpu_reader_set_row_group_pruning.argtypes = [C.c_void_p, C.c_int]
     L.orcgpu_reader_row_groups.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.orcgpu_index_entry.argtypes = [C.POINTER(Column), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.c_int32, C.POINTER(StreamEntry)]
@@ -434,6 +440,21 @@ class Context:
         kept = C.c_uint64(0)
         self._check(self.L.orcgpu_result_filter(self.h, result.h, nodes, len(nodes), names, len(column_names), C.byref(kept)))
         return kept.value
+
+    def result_aggregate(self, result, specs, column_names, predicate=None, raw=False):
+        """orcgpu_result_aggregate: the aggregates `specs` (a list of orc_rust_amd.aggregate.Agg) over the rows of a decoded,
+        selected or filtered Result that `predicate` keeps (None: all of them); column_names[i] names the result's column i.  The
+        result is left as it was.  Returns the Python values (aggregate.value_of); raw=True: the orcgpu_agg_value records."""
+        from . import aggregate as A
+        arr, keep = A.spec_array(specs)
+        nodes, n_nodes = None, 0
+        if predicate is not None:
+            nodes, keep_p = predicate.flatten()
+            n_nodes = len(nodes)
+        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
+        out = (A.AggValue * len(arr))()
+        self._check(self.L.orcgpu_result_aggregate(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, len(arr), out))
+        return list(out) if raw else A.values_of(out, specs)
 
     def timing(self):
         a, b, c = C.c_float(), C.c_float(), C.c_uint32()

@@ -1,0 +1,225 @@
+// agg_kernels.hip -- COUNT, SUM, MIN, MAX and the one product SUM(a * b) over the KEPT rows of a decoded stripe, reduced where the
+// rows lie: nothing is scanned, placed, gathered or copied back but one record per aggregate.
+//
+// The reference has no aggregation; the semantics are those of include/orcgpu.h (orcgpu_result_aggregate).  The kept rows are
+// the bits of the keep mask filter_eval_kernel leaves (filter_kernels.hip), or -- without a filter -- every input row.
+//
+//   agg_partial_kernel   grid (agg_blocks(n_in), instructions).  A wavefront takes one 64-row word of the keep mask per trip and
+//                        passes over the words that are 0; a lane loads its row through the row-access layer (filter_access.h) and
+//                        adds it to an accumulator of its own.  Behind the last trip the wavefront folds its 64 accumulators with
+//                        shuffles in a fixed tree, the block its four wavefronts through LDS in wavefront order: ONE record per
+//                        (block, instruction).
+//   agg_final_kernel     one block per instruction: thread t folds records t, t + 256, ... in index order, then the same tree.
+//
+// Integer and Decimal sums travel as three 64-bit words with explicit carries -- wide enough for every partial sum, so the
+// order of summation cannot show.  Float sums take whatever the fixed shape gives: the grid is a function of the input row
+// count alone (agg_program.h), there is no atomic anywhere, and so the same call gives the same bits.
+#pragma once
+#include <stdint.h>
+
+#include "agg_program.h"
+#include "filter_access.h"
+#include "filter_program.h"
+
+struct AggAcc {
+  unsigned long long w0, w1, w2;
+  double f;
+  unsigned long long count;
+  uint32_t flags;
+};
+
+// a += b over signed 192-bit integers in two's complement
+__device__ __forceinline__ void agg_add192(AggAcc& a, unsigned long long b0, unsigned long long b1, unsigned long long b2) {
+  const unsigned long long r0 = a.w0 + b0;
+  const unsigned long long c0 = r0 < b0;
+  const unsigned long long t1 = a.w1 + b1;
+  const unsigned long long c1 = t1 < b1;
+  const unsigned long long r1 = t1 + c0;
+  const unsigned long long c2 = r1 < c0;
+  a.w0 = r0;
+  a.w1 = r1;
+  a.w2 = a.w2 + b2 + c1 + c2;
+}
+__device__ __forceinline__ void agg_add_i64(AggAcc& a, long long v) {
+  const unsigned long long s = (unsigned long long)(v >> 63);
+  agg_add192(a, (unsigned long long)v, s, s);
+}
+__device__ __forceinline__ void agg_add_i128(AggAcc& a, unsigned long long lo, unsigned long long hi) {
+  agg_add192(a, lo, hi, (unsigned long long)((long long)hi >> 63));
+}
+__device__ __forceinline__ bool agg_less_i128(unsigned long long alo, unsigned long long ahi, unsigned long long blo, unsigned long long bhi) {
+  return (long long)ahi < (long long)bhi || (ahi == bhi && alo < blo);
+}
+
+// a <- a (+) b: what two accumulators of one instruction fold to.  `a` stands in front of `b` in the fixed order.
+__device__ __forceinline__ void agg_fold(uint32_t kind, bool is_max, AggAcc& a, const AggAcc& b) {
+  a.flags |= b.flags;
+  if (kind == AK_SUM_F64 || kind == AK_SP_F64) {
+    a.f += b.f;
+  } else if (kind < AK_MINMAX_INT) {
+    agg_add192(a, b.w0, b.w1, b.w2);
+  } else if (b.count) {
+    bool take = !a.count;
+    if (!take) {
+      if (kind == AK_MINMAX_INT) take = is_max ? (long long)b.w0 > (long long)a.w0 : (long long)b.w0 < (long long)a.w0;
+      else if (kind == AK_MINMAX_DEC) take = is_max ? agg_less_i128(a.w0, a.w1, b.w0, b.w1) : agg_less_i128(b.w0, b.w1, a.w0, a.w1);
+      else take = is_max ? b.f > a.f : b.f < a.f;
+    }
+    if (take) {
+      a.w0 = b.w0;
+      a.w1 = b.w1;
+      a.f = b.f;
+    }
+  }
+  a.count += b.count;
+}
+
+__device__ __forceinline__ unsigned long long agg_shfl_down(unsigned long long v, int o) { return (unsigned long long)__shfl_down((long long)v, o); }
+// The wavefront's 64 accumulators -> lane 0's, in the tree ((0 + 32) + (16 + 48)) + ... of shuffles down by 32, 16, .. 1
+__device__ __forceinline__ void agg_wave_fold(uint32_t kind, bool is_max, AggAcc& a) {
+  for (int o = 32; o; o >>= 1) {
+    AggAcc b;
+    b.w0 = agg_shfl_down(a.w0, o);
+    b.w1 = agg_shfl_down(a.w1, o);
+    b.w2 = agg_shfl_down(a.w2, o);
+    b.f = __shfl_down(a.f, o);
+    b.count = agg_shfl_down(a.count, o);
+    b.flags = (uint32_t)__shfl_down((int)a.flags, o);
+    agg_fold(kind, is_max, a, b);
+  }
+}
+// ... and the block's four wavefronts -> thread 0's, through LDS in wavefront order
+__device__ __forceinline__ void agg_block_fold(uint32_t kind, bool is_max, AggAcc& a, AggAcc* lds) {
+  agg_wave_fold(kind, is_max, a);
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = a;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (uint32_t x = 1; x < 4; x++) agg_fold(kind, is_max, a, lds[x]);
+}
+__device__ __forceinline__ void agg_store(AggPartial* out, const AggAcc& a) {
+  out->w[0] = a.w0;
+  out->w[1] = a.w1;
+  out->w[2] = a.w2;
+  out->f = a.f;
+  out->count = a.count;
+  out->flags = a.flags;
+  out->pad = 0;
+}
+
+// One value into a lane's accumulator: MIN / MAX of what is there and (w0, w1 | f)
+__device__ __forceinline__ void agg_minmax(uint32_t kind, bool is_max, AggAcc& a, unsigned long long w0, unsigned long long w1, double f) {
+  AggAcc b = {w0, w1, 0, f, 1, 0};
+  agg_fold(kind, is_max, a, b);
+}
+
+// keep: the mask filter_eval_kernel left, one word per 64 input rows (null: no filter, every input row is kept).
+// partials: [instruction][block].  A lane whose row is not kept loads nothing; a kept row is an input row below n_in, and the
+// row-access layer turns it into a row of the stripe: every load lies where the decode wrote.
+extern "C" __global__ void __launch_bounds__(256)
+agg_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
+                   uint32_t B, uint32_t W, const unsigned long long* keep, AggPartial* partials) {
+  __shared__ AggAcc fold_s[4];
+  const AggInsn in = insns[blockIdx.y];
+  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const bool is_max = in.is_max != 0;
+  const FilterCol c = cols[in.col], c2 = cols[in.col2];
+  const uint32_t lane = threadIdx.x & 63;
+  const FilterWords ws = filter_words(n_in);
+  AggAcc a = {0, 0, 0, 0.0, 0, 0};
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const uint64_t left = n_in - w * 64;  // (w < ws.n: at least 1)
+    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    if (!m) continue;
+    if (kind == AK_COUNT_ROWS) {  // (the word's popcount, once: lane 0's share)
+      if (lane == 0) a.w0 += (unsigned long long)__builtin_popcountll(m);
+      continue;
+    }
+    if (!((m >> lane) & 1)) continue;
+    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
+    if (!r.live || !filter_valid(c, r.u, r.l, W)) continue;
+    switch (kind) {
+      case AK_COUNT: a.w0++; break;
+      case AK_SUM_INT:
+        agg_add_i64(a, filter_load_i64(c, r.row));
+        a.count++;
+        break;
+      case AK_SUM_DEC: {
+        unsigned long long lo, hi;
+        filter_load_dec128(c, r.row, &lo, &hi);
+        agg_add_i128(a, lo, hi);
+        a.count++;
+        break;
+      }
+      case AK_SUM_F64:
+        a.f += filter_load_f64(c, r.row);
+        a.count++;
+        break;
+      case AK_SP_INT:
+      case AK_SP_DEC: {
+        if (!filter_valid(c2, r.u, r.l, W)) break;
+        long long x, y;
+        if (kind == AK_SP_INT) {
+          x = filter_load_i64(c, r.row);
+          y = filter_load_i64(c2, r.row);
+        } else {
+          unsigned long long xl, xh, yl, yh;
+          filter_load_dec128(c, r.row, &xl, &xh);
+          filter_load_dec128(c2, r.row, &yl, &yh);
+          if (xh != (unsigned long long)((long long)xl >> 63) || yh != (unsigned long long)((long long)yl >> 63)) {
+            a.flags |= AGG_OVERFLOW;  // an operand that does not fit a signed 64-bit word: sticky, the row is left out
+            a.count++;
+            break;
+          }
+          x = (long long)xl;
+          y = (long long)yl;
+        }
+        const __int128 p = (__int128)x * (__int128)y;
+        agg_add_i128(a, (unsigned long long)p, (unsigned long long)(p >> 64));
+        a.count++;
+        break;
+      }
+      case AK_SP_F64:
+        if (!filter_valid(c2, r.u, r.l, W)) break;
+        a.f += filter_load_f64(c, r.row) * filter_load_f64(c2, r.row);
+        a.count++;
+        break;
+      case AK_MINMAX_INT: {
+        const long long v = in.fkind == FKIND_BOOL ? (long long)filter_load_bit(c, r.u, r.l, W) : filter_load_i64(c, r.row);
+        agg_minmax(kind, is_max, a, (unsigned long long)v, 0, 0.0);
+        break;
+      }
+      case AK_MINMAX_DEC: {
+        unsigned long long lo, hi;
+        filter_load_dec128(c, r.row, &lo, &hi);
+        agg_minmax(kind, is_max, a, lo, hi, 0.0);
+        break;
+      }
+      default: {  // AK_MINMAX_F64
+        const double v = filter_load_f64(c, r.row);
+        if (v != v) a.flags |= AGG_SAW_NAN;
+        else agg_minmax(kind, is_max, a, 0, 0, v);
+        break;
+      }
+    }
+  }
+  agg_block_fold(kind, is_max, a, fold_s);
+  if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
+}
+
+// blockIdx.x = instruction: its n_blocks records -> out[instruction]
+extern "C" __global__ void __launch_bounds__(256)
+agg_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_t n_blocks, AggPartial* out) {
+  __shared__ AggAcc fold_s[4];
+  const AggInsn in = insns[blockIdx.x];
+  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const bool is_max = in.is_max != 0;
+  const AggPartial* p = partials + (uint64_t)blockIdx.x * n_blocks;
+  AggAcc a = {0, 0, 0, 0.0, 0, 0};
+  for (uint32_t k = threadIdx.x; k < n_blocks; k += 256) {
+    const AggAcc b = {p[k].w[0], p[k].w[1], p[k].w[2], p[k].f, p[k].count, p[k].flags};
+    agg_fold(kind, is_max, a, b);
+  }
+  agg_block_fold(kind, is_max, a, fold_s);
+  if (threadIdx.x == 0) agg_store(out + blockIdx.x, a);
+}

@@ -43,6 +43,7 @@
 #include "device/decompress_kernels.hip"
 #include "device/select_kernels.hip"
 #include "device/filter_kernels.hip"
+#include "device/agg_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -495,6 +496,8 @@ struct orcgpu_result {
   bool filtered = false;
   DevBuf filt_arena, filt_tmp;  // the kept rows; the filter's tables, keep mask and row list
   size_t filt_used = 0;
+  std::vector<AggPartial> agg_records;  // an aggregating file reader: the stripe's record per aggregate, then its kept row count
+  uint64_t agg_seen = 0;                // ... and the rows the aggregation saw
   std::vector<ColumnOut> cols;
   std::vector<std::string> field_names;  // per column: the name of a Struct's field (set by the file reader; empty: "f<position>")
   // Elements of the List / Map columns: one result each over a "stripe" whose rows are the column's elements (all of the
@@ -1209,6 +1212,7 @@ struct SummaryLayout {
 #include "orcgpu_export_device.inc"
 #include "orcgpu_select.inc"
 #include "orcgpu_filter.inc"
+#include "orcgpu_agg.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"

@@ -1,0 +1,244 @@
+// orcgpu_agg_plan.inc -- the aggregation's plan compiler and its arithmetic on the host, free of HIP
+// (tests/hostcheck/agg_plan_check.cpp compiles this very text under AddressSanitizer + UBSan): a list of orcgpu_agg_spec against
+// the columns of a result -> the instructions agg_partial_kernel runs (device/agg_program.h), with every refusal of
+// orcgpu_result_aggregate (include/orcgpu.h) decided here; the merge of two partial records, which is what the kernels do and what
+// the file reader does with its stripes' records; and the last step, a record -> the orcgpu_agg_value handed out, with the range
+// checks.  Included behind orcgpu_filter_host.inc, whose FilterColDesc and filter_col_kind say what a decoded column is.
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "device/agg_program.h"
+
+namespace orcgpu_host {
+
+static_assert(sizeof(AggInsn) == 32 && sizeof(AggPartial) == 48, "agg_program.h: the records the kernels read and write");
+
+// What the plan reads of a column of the result
+struct AggCol {
+  FilterColDesc d;
+  uint32_t scale = 0;   // Decimal
+  bool nested = false;  // Struct / List / Map / Union, or a column below one
+};
+
+struct AggPlan {
+  std::vector<AggInsn> insns;
+  char err[256] = {0};
+};
+
+enum { ACLASS_INT, ACLASS_DATE, ACLASS_BOOL, ACLASS_FLOAT, ACLASS_DEC, ACLASS_TS, ACLASS_OTHER };
+inline int agg_class(int32_t t) {
+  switch (t) {
+    case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG: return ACLASS_INT;
+    case ORCGPU_T_DATE: return ACLASS_DATE;
+    case ORCGPU_T_BOOLEAN: return ACLASS_BOOL;
+    case ORCGPU_T_FLOAT: case ORCGPU_T_DOUBLE: return ACLASS_FLOAT;
+    case ORCGPU_T_DECIMAL: return ACLASS_DEC;
+    case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT: return ACLASS_TS;
+    default: return ACLASS_OTHER;
+  }
+}
+inline const char* agg_op_name(uint32_t op) {
+  static const char* const n[] = {"COUNT_ROWS", "COUNT", "SUM", "MIN", "MAX", "SUM_PRODUCT"};
+  return op <= ORCGPU_AGG_OP_SUM_PRODUCT ? n[op] : "?";
+}
+
+struct AggCompiler {
+  const char* const* names;
+  const AggCol* cols;
+  uint32_t n_columns;
+  AggPlan& out;
+
+  int fail(int rc, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {
+    snprintf(out.err, sizeof(out.err), fmt, a, b, c);
+    return rc;
+  }
+  int column(const char* name, uint32_t op, uint32_t& col) {
+    if (!name) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: %s without a column name", agg_op_name(op));
+    for (uint32_t k = 0; k < n_columns; k++)
+      if (names[k] && strcmp(names[k], name) == 0) {
+        col = k;
+        return ORCGPU_OK;
+      }
+    return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: column '%s' of %s is not a projected root column", name, agg_op_name(op));
+  }
+  // the class of a column an op other than COUNT reads the values of, or its refusal
+  int value_class(uint32_t op, uint32_t col, int& cls) {
+    const AggCol& c = cols[col];
+    const char* name = names[col];
+    if (c.d.dict_out) return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is read as a dictionary column: %s on its keys is not supported", name, agg_op_name(op));
+    cls = agg_class(c.d.orc_type);
+    if (cls == ACLASS_TS && (c.d.ts_unit > 3 || c.d.width != 8))
+      return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is a Timestamp decoded to Decimal128(38, 9): %s is not supported on it", name, agg_op_name(op));
+    const bool sum = op == ORCGPU_AGG_OP_SUM || op == ORCGPU_AGG_OP_SUM_PRODUCT;
+    if (cls == ACLASS_OTHER || (sum && cls != ACLASS_INT && cls != ACLASS_FLOAT && cls != ACLASS_DEC))
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s does not take column '%s'", agg_op_name(op), name);
+    // ... and what the decode made of it must be what the kernel loads
+    const uint32_t want = cls == ACLASS_BOOL ? FKIND_BOOL : cls == ACLASS_FLOAT ? FKIND_FLOAT : cls == ACLASS_DEC ? FKIND_DEC128 : FKIND_INT;
+    if (filter_col_kind(c.d) != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type %s needs", name, agg_op_name(op));
+    return ORCGPU_OK;
+  }
+  int compile(const orcgpu_agg_spec* specs, uint32_t n_specs) {
+    if (!specs || !n_specs) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: no aggregates given");
+    if (n_specs > ORCGPU_AGG_MAX) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: more than ORCGPU_AGG_MAX (64) aggregates");
+    for (uint32_t k = 0; k < n_columns; k++)
+      if (cols[k].nested)
+        return fail(ORCGPU_UNSUPPORTED, "aggregate: the result holds the nested column '%s' (Struct / List / Map / Union are not aggregated)", names[k] ? names[k] : "");
+    for (uint32_t s = 0; s < n_specs; s++) {
+      const orcgpu_agg_spec& sp = specs[s];
+      AggInsn in{};
+      in.op = sp.op;
+      if (sp.op > ORCGPU_AGG_OP_SUM_PRODUCT) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: unknown op in the list%s", "");
+      if (sp.op == ORCGPU_AGG_OP_COUNT_ROWS) {
+        in.kind = AK_COUNT_ROWS;
+        out.insns.push_back(in);
+        continue;
+      }
+      if (const int rc = column(sp.column, sp.op, in.col)) return rc;
+      in.col2 = in.col;
+      in.fkind = filter_col_kind(cols[in.col].d);
+      if (sp.op == ORCGPU_AGG_OP_COUNT) {
+        in.kind = AK_COUNT;
+        out.insns.push_back(in);
+        continue;
+      }
+      int cls = 0;
+      if (const int rc = value_class(sp.op, in.col, cls)) return rc;
+      if (sp.op == ORCGPU_AGG_OP_SUM) {
+        in.kind = cls == ACLASS_INT ? AK_SUM_INT : cls == ACLASS_FLOAT ? AK_SUM_F64 : AK_SUM_DEC;
+        in.scale = cls == ACLASS_DEC ? (int32_t)cols[in.col].scale : 0;
+      } else if (sp.op == ORCGPU_AGG_OP_SUM_PRODUCT) {
+        if (const int rc = column(sp.column2, sp.op, in.col2)) return rc;
+        int cls2 = 0;
+        if (const int rc = value_class(sp.op, in.col2, cls2)) return rc;
+        if (cls != cls2) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: SUM_PRODUCT of columns '%s' and '%s' of different kinds", names[in.col], names[in.col2]);
+        in.kind = cls == ACLASS_INT ? AK_SP_INT : cls == ACLASS_FLOAT ? AK_SP_F64 : AK_SP_DEC;
+        if (cls == ACLASS_DEC) {
+          in.scale = (int32_t)(cols[in.col].scale + cols[in.col2].scale);
+          if (in.scale > 38)
+            return fail(ORCGPU_UNSUPPORTED, "aggregate: the scales of columns '%s' and '%s' add to more than 38: their SUM_PRODUCT is not supported", names[in.col], names[in.col2]);
+        }
+      } else {  // MIN, MAX
+        in.is_max = sp.op == ORCGPU_AGG_OP_MAX;
+        in.kind = cls == ACLASS_FLOAT ? AK_MINMAX_F64 : cls == ACLASS_DEC ? AK_MINMAX_DEC : AK_MINMAX_INT;
+        in.scale = cls == ACLASS_DEC ? (int32_t)cols[in.col].scale : cls == ACLASS_TS ? cols[in.col].d.ts_unit : -1;
+      }
+      out.insns.push_back(in);
+    }
+    return ORCGPU_OK;
+  }
+};
+
+inline int agg_compile(const orcgpu_agg_spec* specs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out) {
+  out.insns.clear();
+  out.err[0] = 0;
+  AggCompiler c{names, cols, n_columns, out};
+  return c.compile(specs, n_specs);
+}
+
+// ---- the arithmetic: signed 192-bit integers as three little-endian words ----
+inline void agg_add192(unsigned long long* a, const unsigned long long* b) {
+  unsigned long long carry = 0;
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long t = a[k] + b[k];
+    const unsigned long long c1 = t < b[k];
+    a[k] = t + carry;
+    carry = c1 | (unsigned long long)(a[k] < carry);
+  }
+}
+inline bool agg_less_i128(const unsigned long long* a, const unsigned long long* b) {
+  return (long long)a[1] < (long long)b[1] || (a[1] == b[1] && a[0] < b[0]);
+}
+// does the value fit a signed 128-bit integer?
+inline bool agg_fits_i128(const unsigned long long* w) { return w[2] == (unsigned long long)((long long)w[1] >> 63); }
+// |value| < 10^38, what a Decimal128 may hold
+inline bool agg_fits_decimal(const unsigned long long* w) {
+  unsigned long long m[3] = {w[0], w[1], w[2]};
+  if ((long long)m[2] < 0) {  // -v = ~v + 1
+    unsigned long long one[3] = {1, 0, 0};
+    for (auto& x : m) x = ~x;
+    agg_add192(m, one);
+  }
+  const unsigned long long hi = 0x4b3b4ca85a86c47aull, lo = 0x098a224000000000ull;  // 10^38
+  return m[2] == 0 && (m[1] < hi || (m[1] == hi && m[0] < lo));
+}
+
+// into <- into (+) from: what agg_fold (device/agg_kernels.hip) does, on the host -- the reader's stripes in stripe order
+inline void agg_merge(const AggInsn& in, AggPartial& into, const AggPartial& from) {
+  into.flags |= from.flags;
+  if (in.kind == AK_SUM_F64 || in.kind == AK_SP_F64) {
+    into.f += from.f;
+  } else if (in.kind < AK_MINMAX_INT) {
+    agg_add192(into.w, from.w);
+  } else if (from.count) {
+    bool take = !into.count;
+    if (!take) {
+      if (in.kind == AK_MINMAX_INT) take = in.is_max ? (long long)from.w[0] > (long long)into.w[0] : (long long)from.w[0] < (long long)into.w[0];
+      else if (in.kind == AK_MINMAX_DEC) take = in.is_max ? agg_less_i128(into.w, from.w) : agg_less_i128(from.w, into.w);
+      else take = in.is_max ? from.f > into.f : from.f < into.f;
+    }
+    if (take) {
+      into.w[0] = from.w[0];
+      into.w[1] = from.w[1];
+      into.f = from.f;
+    }
+  }
+  into.count += from.count;
+}
+
+// The record of an instruction -> what the caller gets
+inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value* v) {
+  memset(v, 0, sizeof(*v));
+  const bool sticky = (p.flags & AGG_OVERFLOW) != 0;
+  switch (in.kind) {
+    case AK_COUNT_ROWS:
+    case AK_COUNT:
+      v->kind = ORCGPU_AGG_KIND_U64;
+      v->w[0] = p.w[0];
+      return;
+    case AK_SUM_INT:
+    case AK_SP_INT:
+      v->kind = ORCGPU_AGG_KIND_I128;
+      v->is_null = p.count == 0;
+      v->overflow = !agg_fits_i128(p.w) || sticky;
+      break;
+    case AK_SUM_DEC:
+    case AK_SP_DEC:
+      v->kind = ORCGPU_AGG_KIND_DEC128;
+      v->scale_or_unit = in.scale;
+      v->is_null = p.count == 0;
+      v->overflow = !agg_fits_decimal(p.w) || sticky;
+      break;
+    case AK_SUM_F64:
+    case AK_SP_F64:
+      v->kind = ORCGPU_AGG_KIND_F64;
+      v->is_null = p.count == 0;
+      v->f = p.f;
+      return;
+    case AK_MINMAX_INT:
+      v->kind = ORCGPU_AGG_KIND_I64;
+      v->scale_or_unit = in.scale;
+      v->is_null = p.count == 0;
+      v->w[0] = p.count ? p.w[0] : 0;
+      return;
+    case AK_MINMAX_DEC:
+      v->kind = ORCGPU_AGG_KIND_DEC128;
+      v->scale_or_unit = in.scale;
+      v->is_null = p.count == 0;
+      if (p.count) {
+        v->w[0] = p.w[0];
+        v->w[1] = p.w[1];
+        v->w[2] = (unsigned long long)((long long)p.w[1] >> 63);
+      }
+      return;
+    default:  // AK_MINMAX_F64: NaN only when every value was one
+      v->kind = ORCGPU_AGG_KIND_F64;
+      v->is_null = p.count == 0 && !(p.flags & AGG_SAW_NAN);
+      v->f = p.count ? p.f : ((p.flags & AGG_SAW_NAN) ? __builtin_nan("") : 0.0);
+      return;
+  }
+  if (!v->is_null)
+    for (int k = 0; k < 3; k++) v->w[k] = p.w[k];
+}
+
+}  // namespace orcgpu_host

@@ -63,9 +63,11 @@ void filter_segments(FilterCall& f) {
   }
 }
 
+FilterColDesc filter_desc_of(const ColumnOut& co) {  // (in the order FilterColDesc declares them)
+  return {co.orc_type, co.width, co.ts_unit, co.is_bool, co.is_string, co.has_present, co.dict_out, co.dict_decoded, co.dict_len, co.dict_bytes};
+}
 void filter_describe(FilterCall& f) {
-  for (const ColumnOut& co : f.r->cols)  // (in the order FilterColDesc declares them)
-    f.descs.push_back({co.orc_type, co.width, co.ts_unit, co.is_bool, co.is_string, co.has_present, co.dict_out, co.dict_decoded, co.dict_len, co.dict_bytes});
+  for (const ColumnOut& co : f.r->cols) f.descs.push_back(filter_desc_of(co));
 }
 
 // The columns as the kernels see them, with pointers into the decode's arenas; the char bases of the string columns go into the
@@ -74,10 +76,15 @@ void filter_fill_cols(FilterCall& f, const FilterWorkspace& ws, uint32_t src_bat
   f.fcols.resize(f.nc);
   for (uint32_t c = 0; c < f.nc; c++) {
     const ColumnOut& co = f.r->cols[c];
-    const uint8_t* A = f.r->arena[co.lane].p;
+    const uint8_t* A = f.r->filtered ? f.r->filt_arena.p : f.r->arena[co.lane].p;  // (a filtered result, aggregated: the kept rows' arena)
     FilterCol& fc = f.fcols[c];
     memset(&fc, 0, sizeof(fc));
-    fc.validity = co.has_present && f.r->n_rows ? reinterpret_cast<const unsigned long long*>(A + co.validity_off) : nullptr;
+    bool has_validity = co.has_present && f.r->n_rows;
+    if (f.r->filtered) {  // (the kept rows carry a validity buffer only when one of them is null)
+      has_validity = false;
+      for (const uint64_t n : co.null_counts) has_validity = has_validity || n;
+    }
+    fc.validity = has_validity ? reinterpret_cast<const unsigned long long*>(A + co.validity_off) : nullptr;
     fc.width = co.width;
     fc.kind = filter_col_kind(f.descs[c]);
     if (co.is_string) {
@@ -101,9 +108,8 @@ int filter_check(FilterCall& f, const char* const* column_names, uint32_t n_name
   return rc;
 }
 
-// The first upload, then plane kernels -> evaluate -> scan -> place -> count, and the filter's one wait: `back` gets the kept
-// row count, then null counts and string bytes per (column, output batch)
-int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host, std::vector<uint64_t>& back) {
+// The first upload: the program, its literals and leaf lists, the segments and the columns (nothing goes up for no input row)
+int filter_upload(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host) {
   orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
   const orcgpu_host::FilterPlan& plan = f.plan;
@@ -118,17 +124,26 @@ int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8
   }
   if (f.nc) memcpy(host.data() + ws.o_cols, f.fcols.data(), (size_t)f.nc * sizeof(FilterCol));
   if (!f.n_in) return ORCGPU_OK;
+  HIP_TRY(ctx, ctx->upload(f.X, host.data(), ws.up_bytes, st));
+  HIP_TRY(ctx, hipMemsetAsync(f.at<unsigned long long>(ws.o_counters), 0, ws.n_counters * 8, st));
+  return ORCGPU_OK;
+}
+
+// Plane kernels -> evaluate: the keep mask (one word per 64 input rows) and its popcounts, and nothing after them -- what the
+// filter compacts from and the aggregation reduces from
+int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
+  orcgpu_ctx* ctx = f.ctx;
+  hipStream_t st = ctx->stream;
+  const orcgpu_host::FilterPlan& plan = f.plan;
+  const uint32_t n_segs = (uint32_t)f.segs.size(), n_insn = (uint32_t)plan.prog.size(), n_like = (uint32_t)plan.like_leaves.size(), n_set = (uint32_t)plan.in_leaves.size();
   const FilterInsn* d_prog = f.at<const FilterInsn>(ws.o_prog);
   const uint8_t* d_lits = f.at<const uint8_t>(ws.o_lits);
   const uint32_t* d_leaves = f.at<const uint32_t>(ws.o_leaves);
   const FilterCol* d_cols = f.at<const FilterCol>(ws.o_cols);
   const SelBatch* d_segs = f.at<const SelBatch>(ws.o_segs);
   const unsigned long long* d_first = f.at<const unsigned long long>(ws.o_first);
-  unsigned long long *d_counters = f.at<unsigned long long>(ws.o_counters), *d_keep = f.at<unsigned long long>(ws.o_keep), *d_planes = f.at<unsigned long long>(ws.o_planes);
-  uint32_t* d_rows = f.at<uint32_t>(ws.o_rows);
-  const uint32_t nb_max = (uint32_t)ws.nb_max, n_planes = n_like + n_set;
-  HIP_TRY(ctx, ctx->upload(f.X, host.data(), ws.up_bytes, st));
-  HIP_TRY(ctx, hipMemsetAsync(d_counters, 0, ws.n_counters * 8, st));
+  unsigned long long *d_keep = f.at<unsigned long long>(ws.o_keep), *d_planes = f.at<unsigned long long>(ws.o_planes);
+  const uint32_t n_planes = n_like + n_set;
   const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((ws.n_words + 3) / 4, 16384);
   if (n_like) {  // the matcher first: the evaluation reads its bits
     hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_like), dim3(256), 0, st, d_prog, n_insn, d_leaves, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W,
@@ -143,6 +158,23 @@ int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8
   hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, d_prog, n_insn, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W, d_keep,
                      f.at<uint32_t>(ws.o_cnt), d_planes);
   HIP_TRY(ctx, hipGetLastError());
+  return ORCGPU_OK;
+}
+
+// The first upload, then plane kernels -> evaluate -> scan -> place -> count, and the filter's one wait: `back` gets the kept
+// row count, then null counts and string bytes per (column, output batch)
+int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host, std::vector<uint64_t>& back) {
+  orcgpu_ctx* ctx = f.ctx;
+  hipStream_t st = ctx->stream;
+  if (const int rc = filter_upload(f, ws, host)) return rc;
+  if (!f.n_in) return ORCGPU_OK;
+  if (const int rc = filter_run_eval(f, ws)) return rc;
+  const uint32_t n_segs = (uint32_t)f.segs.size(), nb_max = (uint32_t)ws.nb_max;
+  const FilterCol* d_cols = f.at<const FilterCol>(ws.o_cols);
+  const SelBatch* d_segs = f.at<const SelBatch>(ws.o_segs);
+  const unsigned long long* d_first = f.at<const unsigned long long>(ws.o_first);
+  unsigned long long *d_counters = f.at<unsigned long long>(ws.o_counters), *d_keep = f.at<unsigned long long>(ws.o_keep);
+  uint32_t* d_rows = f.at<uint32_t>(ws.o_rows);
   const int rc = enc_scan(ctx, st, f.at<const uint32_t>(ws.o_cnt), ws.n_words, f.at<uint64_t>(ws.o_sums), reinterpret_cast<uint64_t*>(d_counters), f.at<uint64_t>(ws.o_woff));
   if (rc) return rc;
   hipLaunchKernelGGL(filter_place_kernel, dim3((uint32_t)((f.n_in + 255) / 256)), dim3(256), 0, st, d_keep, f.at<const unsigned long long>(ws.o_woff), d_segs, d_first, n_segs,

@@ -322,6 +322,16 @@ struct orcgpu_reader {
   std::vector<orcgpu_host::PredNode> filter_nodes;
   orcgpu_host::FilterPlan filter_plan;
   std::atomic<uint64_t> filter_seen{0}, filter_kept{0};
+  // ---- aggregates (orcgpu_reader_set_aggregates): the specs as given (their strings copied), and -- from orcgpu_reader_aggregate
+  // on -- their instructions; every decoded stripe is aggregated where the filter and the copy back would stand ----
+  bool has_aggs = false, aggs_done = false;
+  struct AggSpec {
+    uint32_t op = 0;
+    bool has_column = false, has_column2 = false;
+    std::string column, column2;
+  };
+  std::vector<AggSpec> agg_specs;
+  orcgpu_host::AggPlan agg_plan;
   // ---- device output (orcgpu_reader_set_device_output): the batches are views of the results' HBM, handed out by
   // orcgpu_reader_next_batch_device; no copy back is started.  A result the caller is done with goes to `home` instead of `spare`
   // -- at once, or when the last exported batch or tensor that views it is released (device_hold.h) ----
@@ -838,12 +848,80 @@ int reader_compile_filter(orcgpu_reader* rd) {
   return ORCGPU_OK;
 }
 
+std::vector<orcgpu_agg_spec> reader_view_aggs(const orcgpu_reader* rd) {
+  std::vector<orcgpu_agg_spec> out(rd->agg_specs.size());
+  for (size_t k = 0; k < out.size(); k++) {
+    const orcgpu_reader::AggSpec& s = rd->agg_specs[k];
+    out[k] = {s.op, s.has_column ? s.column.c_str() : nullptr, s.has_column2 ? s.column2.c_str() : nullptr};
+  }
+  return out;
+}
+
+// The aggregate list against the projected root columns as the file's metadata and the builder describe them -> its instructions,
+// once, before anything is read: every refusal arrives here.  (What a stripe's decode made of the columns is checked again, per
+// stripe, by the plan the kernels run: reader_aggregate_result.)
+int reader_compile_aggs(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<AggCol> cols;
+  for (size_t k = 0, root = 0; k < rd->col_ids.size(); k++) {
+    if (rd->col_parent[k]) continue;
+    const OrcType& t = rd->md.types[rd->col_ids[k]];
+    names.push_back(rd->col_names[root++].c_str());
+    orcgpu_column c{};
+    c.arrow_target = rd->has_schema ? rd->col_target[k] : rd->ts_arrow_target;
+    AggCol a;
+    a.d.orc_type = t.kind;
+    a.d.ts_unit = ts_unit_of(c);
+    a.d.is_bool = t.kind == ORCGPU_T_BOOLEAN;
+    a.d.dict_out = rd->col_dict[k] != 0;
+    a.d.is_string = !a.d.dict_out && (t.kind == ORCGPU_T_STRING || t.kind == ORCGPU_T_VARCHAR || t.kind == ORCGPU_T_CHAR || t.kind == ORCGPU_T_BINARY);
+    const bool is_ts = t.kind == ORCGPU_T_TIMESTAMP || t.kind == ORCGPU_T_TIMESTAMP_INSTANT;
+    a.d.width = t.kind == ORCGPU_T_BYTE ? 1 : t.kind == ORCGPU_T_SHORT ? 2 : (t.kind == ORCGPU_T_INT || t.kind == ORCGPU_T_FLOAT || t.kind == ORCGPU_T_DATE || a.d.dict_out) ? 4
+                : (t.kind == ORCGPU_T_DECIMAL || (is_ts && a.d.ts_unit > 3)) ? 16 : (a.d.is_bool || a.d.is_string) ? 0 : 8;
+    a.scale = t.scale;
+    a.nested = t.kind == ORCGPU_T_STRUCT || t.kind == ORCGPU_T_LIST || t.kind == ORCGPU_T_MAP || t.kind == ORCGPU_T_UNION;
+    cols.push_back(a);
+  }
+  const std::vector<orcgpu_agg_spec> specs = reader_view_aggs(rd);
+  const int rc = agg_compile(specs.data(), (uint32_t)specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
+  if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
+  return rc;
+}
+
+// The aggregation of one decoded (and selected) stripe, where reader_filter_result and the copy back stand otherwise: its
+// records stay with the result until orcgpu_reader_aggregate merges them, in stripe order.  A stripe whose decode failed ends the call.
+int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
+  if (res->status) {
+    set_err(rd->ctx, "stripe decode failed in batch %u, column %u", res->err_batch, res->err_col);
+    return res->status;
+  }
+  std::vector<const char*> names;
+  for (auto& n : rd->col_names) names.push_back(n.c_str());
+  if (names.size() != res->cols.size()) {  // (a flat projection: one result column per root column; anything else the plan has refused)
+    set_err(rd->ctx, "aggregate: the result holds %zu columns for %zu projected root columns", res->cols.size(), names.size());
+    return ORCGPU_UNSUPPORTED;
+  }
+  const std::vector<orcgpu_agg_spec> specs = reader_view_aggs(rd);
+  AggPlan plan;
+  if (const int rc = result_compile_aggs(rd->ctx, res, specs.data(), (uint32_t)specs.size(), names.data(), plan)) return rc;
+  for (size_t k = 0; k < plan.insns.size(); k++)
+    if (plan.insns[k].kind != rd->agg_plan.insns[k].kind || plan.insns[k].scale != rd->agg_plan.insns[k].scale) {
+      set_err(rd->ctx, "aggregate: column '%s' is not decoded to the type its aggregate was planned for", names[plan.insns[k].col]);
+      return ORCGPU_MISMATCHED_SCHEMA;
+    }
+  const int rc = result_aggregate_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, res->agg_records, &res->agg_seen, names.data(), (uint32_t)names.size());
+  if (rc) return rc;
+  rd->filter_seen += res->agg_seen;
+  rd->filter_kept += res->agg_records.back().w[0];
+  return ORCGPU_OK;
+}
+
 // A result the caller is done with, to decode a later stripe into (rd->m is held by a reader that reads ahead)
 orcgpu_result* reader_take_spare(orcgpu_reader* rd) {
   // (a result that comes home was viewed by batches and tensors whose consumers released them on the HOST: work they enqueued on
   // streams of their own may not have run yet, and nothing orders the decode stream behind it -- so decode_staged_once waits for
   // the device before it writes into a result that has been exported)
-  if (rd->device_output) return static_cast<orcgpu_result*>(orcgpu_hold::home_take(*rd->home));
+  if (rd->device_output && !rd->has_aggs) return static_cast<orcgpu_result*>(orcgpu_hold::home_take(*rd->home));
   if (rd->spare.empty()) return nullptr;
   orcgpu_result* r = rd->spare.back();
   rd->spare.pop_back();
@@ -889,9 +967,10 @@ int reader_advance_stripe(orcgpu_reader* rd) {
     for (size_t k = 0; k < got.size(); k++) {
       if (!rc) res[k]->field_names = rd->col_field;
       if (!rc && got[k]->has_sel) rc = result_select_batches(ctx, res[k], got[k]->sel);  // (the stripe's share of the selection)
-      if (!rc && rd->has_filter) rc = reader_filter_result(rd, res[k]);
+      if (!rc && rd->has_aggs) rc = reader_aggregate_result(rd, res[k]);  // (in place of the filter's compaction and of any copy back)
+      else if (!rc && rd->has_filter) rc = reader_filter_result(rd, res[k]);
       orcgpu_staged_free(got[k]);
-      if (!rc) rc = reader_result_decoded(rd, res[k], false);  // (the host path copies back when the first batch is asked for)
+      if (!rc && !rd->has_aggs) rc = reader_result_decoded(rd, res[k], false);  // (the host path copies back when the first batch is asked for)
     }
     if (host_prof)
       fprintf(stderr, "[orcgpu] reader: metadata %.2f ms, staging %zu pieces (%.1f MB) %.2f ms, decode %.2f ms, selection %.2f ms\n", t1 - t0,
@@ -995,9 +1074,10 @@ void reader_decoder(orcgpu_reader* rd) {
     for (size_t k = 0; k < group.size(); k++) {
       if (!rc) results[k]->field_names = rd->col_field;
       if (!rc && group[k]->has_sel) rc = result_select_batches(ctx, results[k], group[k]->sel);  // (the stripe's share of the selection)
-      if (!rc && rd->has_filter) rc = reader_filter_result(rd, results[k]);  // (before the copy back is started: only the kept rows cross the link)
+      if (!rc && rd->has_aggs) rc = reader_aggregate_result(rd, results[k]);  // (in place of the filter's compaction and of the copy back)
+      else if (!rc && rd->has_filter) rc = reader_filter_result(rd, results[k]);  // (before the copy back is started: only the kept rows cross the link)
       orcgpu_staged_free(group[k]);
-      if (!rc) rc = reader_result_decoded(rd, results[k], true);
+      if (!rc && !rd->has_aggs) rc = reader_result_decoded(rd, results[k], true);
     }
     if (rc) {
       err = ctx->err;
@@ -1295,8 +1375,27 @@ int orcgpu_index_entry(const orcgpu_column* column, int has_present, int compres
 // ArrowReader::next (arrow_reader.rs:333-346): 0 = a batch was exported, ORCGPU_END_OF_FILE = no more batches, else an error code
 // (the end has a code of its own: the status of a failing batch may be any OrcError, ORCGPU_IO_ERROR = 1 included)
 // (out_array: the host path; out_device: the device path -- the reader is in one mode or the other, and the wrong call changes nothing)
+static int reader_next_stripe(orcgpu_reader* rd);
+// The row filter's program, compiled at the first call that reads; a refusal is final and ends the reader
+static int reader_ready_filter(orcgpu_reader* rd) {
+  if (rd->filter_failed) return ORCGPU_END_OF_FILE;  // (the filter was refused by the call before: the iterator has ended)
+  if (rd->has_filter && !rd->filter_ready) {
+    const int rc = orcgpu_host::reader_compile_filter(rd);
+    if (rc) {
+      rd->filter_failed = true;
+      rd->next_stripe = rd->stripe_order.size();
+      return rc;
+    }
+    rd->filter_ready = true;
+  }
+  return ORCGPU_OK;
+}
 static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowDeviceArray* out_device, struct ArrowSchema* out_schema) {
   if (!rd || (!out_array && !out_device) || !out_schema) return ORCGPU_INVALID_ARGUMENT;
+  if (rd->has_aggs) {
+    set_err(rd->ctx, "this reader aggregates (orcgpu_reader_set_aggregates): call orcgpu_reader_aggregate, it hands out no batches");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (rd->device_output != (out_device != nullptr)) {
     set_err(rd->ctx, rd->device_output ? "this reader hands out device batches (orcgpu_reader_set_device_output): call orcgpu_reader_next_batch_device"
                                        : "orcgpu_reader_next_batch_device needs orcgpu_reader_set_device_output before the first batch");
@@ -1320,16 +1419,8 @@ static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct A
     }
   }
   if (rd->device_refused) return refuse_nested(rd->ctx, rd->device_refused_name, rd->device_refused_kind);
-  if (rd->filter_failed) return ORCGPU_END_OF_FILE;  // (the filter was refused by the call before: the iterator has ended)
-  if (rd->has_filter && !rd->filter_ready) {
-    rc = orcgpu_host::reader_compile_filter(rd);
-    if (rc) {
-      rd->filter_failed = true;
-      rd->next_stripe = rd->stripe_order.size();
-      return rc;
-    }
-    rd->filter_ready = true;
-  }
+  rc = reader_ready_filter(rd);
+  if (rc) return rc;
   for (;;) {
     if (rd->current) {
       uint32_t eb = 0, ec = 0;
@@ -1352,47 +1443,52 @@ static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct A
         }
         return rc;
       }
-      {
-        // done with this stripe: a later one is decoded into its buffers (by the worker, or by this thread when there is none)
-        std::lock_guard<std::mutex> g(rd->m);
-        orcgpu_host::reader_give_spare(rd, rd->current);
-      }
-      rd->current = nullptr;
     }
-    if (!rd->prefetch) {
-      rc = orcgpu_host::reader_advance_stripe(rd);  // (ORCGPU_END_OF_FILE: every stripe has been handed out)
-      if (rc) return rc;
-      continue;
-    }
-    if (!rd->worker_started) {
-      if (rd->stripe_order.empty()) return ORCGPU_END_OF_FILE;
-      // the stripe footers are decompressed by the GPU kernels on the decode stream: all of them now, before the two threads
-      // share the context (from here on the stager only copies, the decoder only decodes)
-      orcgpu_host::reader_read_metadata_ahead(rd);
-      rc = 0;  // (a footer that cannot be read is reported when its stripe's turn comes)
-      // (a footer that cannot be read: the stripes before it are still handed out, the error arrives in its place)
-      rd->worker_started = true;
-      rd->stager = std::thread(orcgpu_host::reader_stager, rd);
-      rd->decoder = std::thread(orcgpu_host::reader_decoder, rd);
-    }
-    orcgpu_reader::Ready item;
-    {
-      std::unique_lock<std::mutex> g(rd->m);
-      rd->cv_ready.wait(g, [rd] { return !rd->ready.empty() || rd->worker_done; });
-      if (rd->ready.empty()) return ORCGPU_END_OF_FILE;  // every stripe has been handed out
-      item = std::move(rd->ready.front());
-      rd->ready.pop_front();
-    }
-    rd->cv_room.notify_all();
-    if (item.rc) {
-      orcgpu_host::reader_stop_worker(rd);
-      rd->ctx->err = item.err;
-      return item.rc;
-    }
-    rd->current = item.res;
-    rd->next_batch = 0;
-    rd->current_counted = false;
+    rc = reader_next_stripe(rd);  // (ORCGPU_END_OF_FILE: every stripe has been handed out)
+    if (rc) return rc;
   }
+}
+
+// The next decoded stripe becomes rd->current; the one before goes back, for a later stripe to be decoded into its buffers (by the
+// worker, or by this thread when there is none).  ORCGPU_END_OF_FILE: there is no further stripe.
+static int reader_next_stripe(orcgpu_reader* rd) {
+  if (rd->current) {
+    {
+      std::lock_guard<std::mutex> g(rd->m);
+      orcgpu_host::reader_give_spare(rd, rd->current);
+    }
+    rd->current = nullptr;
+  }
+  if (!rd->prefetch) return orcgpu_host::reader_advance_stripe(rd);
+  if (!rd->worker_started) {
+    if (rd->stripe_order.empty()) return ORCGPU_END_OF_FILE;
+    // the stripe footers are decompressed by the GPU kernels on the decode stream: all of them now, before the two threads
+    // share the context (from here on the stager only copies, the decoder only decodes)
+    orcgpu_host::reader_read_metadata_ahead(rd);
+    // (a footer that cannot be read is reported when its stripe's turn comes)
+    // (a footer that cannot be read: the stripes before it are still handed out, the error arrives in its place)
+    rd->worker_started = true;
+    rd->stager = std::thread(orcgpu_host::reader_stager, rd);
+    rd->decoder = std::thread(orcgpu_host::reader_decoder, rd);
+  }
+  orcgpu_reader::Ready item;
+  {
+    std::unique_lock<std::mutex> g(rd->m);
+    rd->cv_ready.wait(g, [rd] { return !rd->ready.empty() || rd->worker_done; });
+    if (rd->ready.empty()) return ORCGPU_END_OF_FILE;  // every stripe has been handed out
+    item = std::move(rd->ready.front());
+    rd->ready.pop_front();
+  }
+  rd->cv_room.notify_all();
+  if (item.rc) {
+    orcgpu_host::reader_stop_worker(rd);
+    rd->ctx->err = item.err;
+    return item.rc;
+  }
+  rd->current = item.res;
+  rd->next_batch = 0;
+  rd->current_counted = false;
+  return ORCGPU_OK;
 }
 
 int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowSchema* out_schema) {
@@ -1402,6 +1498,56 @@ int orcgpu_reader_next_batch(orcgpu_reader* rd, struct ArrowArray* out_array, st
 int orcgpu_reader_next_batch_device(orcgpu_reader* rd, struct ArrowDeviceArray* out_array, struct ArrowSchema* out_schema) {
   if (!out_array) return ORCGPU_INVALID_ARGUMENT;
   return reader_next(rd, nullptr, out_array, out_schema);
+}
+int orcgpu_reader_set_aggregates(orcgpu_reader* rd, const orcgpu_agg_spec* specs, uint32_t n_specs) {
+  if (!rd || rd->built || !specs || !n_specs || n_specs > ORCGPU_AGG_MAX) return ORCGPU_INVALID_ARGUMENT;
+  rd->agg_specs.assign(n_specs, {});
+  for (uint32_t k = 0; k < n_specs; k++) {
+    orcgpu_reader::AggSpec& s = rd->agg_specs[k];
+    s.op = specs[k].op;
+    s.has_column = specs[k].column != nullptr;
+    s.has_column2 = specs[k].column2 != nullptr;
+    if (s.has_column) s.column = specs[k].column;
+    if (s.has_column2) s.column2 = specs[k].column2;
+  }
+  rd->has_aggs = true;
+  return ORCGPU_OK;
+}
+// Drains the reader: every stripe's records, merged in stripe order, then the values
+int orcgpu_reader_aggregate(orcgpu_reader* rd, orcgpu_agg_value* out) {
+  if (!rd || !out) return ORCGPU_INVALID_ARGUMENT;
+  if (!rd->has_aggs) {
+    set_err(rd->ctx, "orcgpu_reader_aggregate needs orcgpu_reader_set_aggregates before the first call");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (rd->aggs_done) return ORCGPU_END_OF_FILE;
+  int rc = orcgpu_host::reader_build(rd);
+  if (rc) return rc;
+  rd->aggs_done = true;  // (whatever comes of it: an error ends the reader as it ends an iterator)
+  rc = orcgpu_host::reader_compile_aggs(rd);
+  if (!rc) rc = reader_ready_filter(rd);
+  if (rc) {
+    rd->next_stripe = rd->stripe_order.size();
+    return rc;
+  }
+  const std::vector<AggInsn>& insns = rd->agg_plan.insns;
+  std::vector<AggPartial> total(insns.size(), AggPartial{});
+  while (!(rc = reader_next_stripe(rd))) {
+    const std::vector<AggPartial>& part = rd->current->agg_records;
+    if (part.size() != insns.size() + 1) {
+      set_err(rd->ctx, "aggregate: a stripe came without its records");
+      rc = ORCGPU_UNEXPECTED;
+      break;
+    }
+    for (size_t k = 0; k < insns.size(); k++) orcgpu_host::agg_merge(insns[k], total[k], part[k]);
+  }
+  if (rc != ORCGPU_END_OF_FILE) {
+    orcgpu_host::reader_stop_worker(rd);
+    rd->next_stripe = rd->stripe_order.size();
+    return rc;
+  }
+  for (size_t k = 0; k < insns.size(); k++) orcgpu_host::agg_finish(insns[k], total[k], &out[k]);
+  return ORCGPU_OK;
 }
 int orcgpu_reader_set_device_output(orcgpu_reader* rd, int on) {
   if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
