@@ -1214,6 +1214,7 @@ struct SummaryLayout {
 #include "orcgpu_filter.inc"
 #include "orcgpu_agg.inc"
 #include "orcgpu_reader.inc"
+#include "orcgpu_reader_api.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"
 #include "orcgpu_writer_host.inc"

@@ -7,9 +7,10 @@
 //   Stripe::new / StreamMap          src/stripe.rs:127-182, :311-336
 //   RowIndex                         src/row_index.rs:204-330
 //
-// Included by orcgpu_reader.inc (the product: liborcgpu.so) AND by tests/hostcheck/hostcheck.cpp, which compiles exactly this
+// Included by orcgpu_reader_meta.inc and orcgpu_reader_plan.inc (the product: liborcgpu.so) AND by tests/hostcheck/hostcheck.cpp, which compiles exactly this
 // text with g++ -fsanitize=address,undefined and feeds it the fixture files and their mutations on the CPU
 // (tests/test_host_sanitized.py) -- everything here parses UNTRUSTED bytes.
+#pragma once
 #include <algorithm>
 #include <cstdarg>
 #include <cstdint>
@@ -89,7 +90,7 @@ namespace orcgpu_host {
 
 // what went wrong, for the caller to pass on (the product: orcgpu_last_error)
 struct MetaErr {
-  char msg[256] = {0};
+  char msg[512] = {0};  // (as long as the context keeps: orcgpu_last_error)
   void set(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
     va_list ap;
     va_start(ap, fmt);

@@ -1,6 +1,7 @@
 // orcgpu_selection.inc -- RowSelection stepping, PURE C++ (no HIP): the stepping of NaiveStripeDecoder::next_with_row_selection
 // (array_decoder/mod.rs:302-365), RowSelection's normalisation, split_off and intersection (row_selection.rs:278-314, :466-482).
 // Included by orcgpu_select.inc (the product) and by tests/hostcheck/hostcheck.cpp (the sanitizer build of the host layer).
+#pragma once
 namespace {
 
 struct RowSel {
