@@ -618,6 +618,67 @@ int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgp
  * aggregates set is ORCGPU_INVALID_ARGUMENT, a second call ORCGPU_END_OF_FILE. */
 int orcgpu_reader_set_aggregates(orcgpu_reader* r, const orcgpu_agg_spec* specs, uint32_t n_specs);
 int orcgpu_reader_aggregate(orcgpu_reader* r, orcgpu_agg_value* out);
+/* ---- GROUP BY for the aggregates: one record per (aggregate, group), the keys hashed on the device ---------------------------
+ * TPC-H Q1 is SELECT l_returnflag, l_linestatus, sum(...), count(*) ... GROUP BY l_returnflag, l_linestatus.  The aggregate list
+ * above is reduced per GROUP of kept rows (device/agg_group_kernels.hip); what comes back is the groups' keys and one value per
+ * (group, aggregate), and nothing else.  The reference has no aggregation; the semantics are fixed here.  A first step on purpose:
+ * low-cardinality grouping, at most ORCGPU_GROUP_MAX groups in one result (one stripe) -- flags, statuses, dates, small codes.
+ *   - Kept rows and aggregates are what they are above: every op, column kind, refusal and overflow rule, applied per group.
+ *     COUNT_ROWS of a group is its kept rows and never 0: a group exists only if a kept row has its key.
+ *   - KEYS: 1 .. ORCGPU_GROUP_MAX_KEYS key columns, named like the aggregates' columns: projected root columns.  A column may be
+ *     a key and an aggregated column.  Byte .. Long, Date (days) and Timestamp / Timestamp-instant decoded to an int64 unit are
+ *     ORCGPU_GROUP_KEY_I64 (w[0], sign-extended into w[1]); Boolean is ORCGPU_GROUP_KEY_BOOL (w[0] = 0 / 1); Decimal is
+ *     ORCGPU_GROUP_KEY_DEC128, compared as the unscaled 128-bit value (one column has one scale); String / Varchar / Char are
+ *     ORCGPU_GROUP_KEY_STRING (the name ORCGPU_GROUP_KEY_BYTES is the limit below), compared as the exported bytes (a Char value includes its padding), len bytes in `bytes`.
+ *     scale_or_unit: the Decimal scale, a Timestamp's unit (0 s .. 3 ns), else -1.
+ *   - Refused, the message naming the column: a Float / Double or Binary key ORCGPU_MISMATCHED_SCHEMA; a key column read as a
+ *     dictionary column, a Timestamp key decoded to Decimal128(38, 9), a nested column in the result ORCGPU_UNSUPPORTED; an unknown
+ *     column, a key listed twice, no key, more than ORCGPU_GROUP_MAX_KEYS keys ORCGPU_INVALID_ARGUMENT.
+ *   - A NULL key value is a key value of its own, as in SQL: the rows whose key is NULL in that column and equal in the others
+ *     form one group, reported with is_null = 1 (and everything else of that key 0).
+ *   - Data-dependent limits, found on the device and reported after the call's one wait as ORCGPU_UNSUPPORTED, nothing returned:
+ *     more than ORCGPU_GROUP_MAX groups in one result (the message gives the limit); a String key value of more than
+ *     ORCGPU_GROUP_KEY_BYTES bytes among the kept rows (the message names the column).  For the reader also a total of more than
+ *     ORCGPU_GROUP_MAX_TOTAL groups over all stripes.
+ *   - ORDER: groups come back in order of first appearance -- by the smallest kept input row of the group within a result, by
+ *     stripe order across stripes.  The whole answer is the same on every run of the same call: groups, order, integer and Decimal
+ *     values (exact), MIN / MAX, and Float / Double sums bit for bit (a reduction of fixed shape; no floating-point atomic; which
+ *     thread wins a race for a slot of the hash table shows in no output).
+ *   - No kept row: zero groups, not one group of NULLs. */
+#define ORCGPU_GROUP_MAX_KEYS 4
+#define ORCGPU_GROUP_MAX 256
+#define ORCGPU_GROUP_MAX_TOTAL 65536
+#define ORCGPU_GROUP_KEY_BYTES 64
+enum { ORCGPU_GROUP_KEY_I64 = 0, ORCGPU_GROUP_KEY_DEC128 = 1, ORCGPU_GROUP_KEY_BOOL = 2, ORCGPU_GROUP_KEY_STRING = 3 };
+typedef struct {
+  uint32_t kind;        /* ORCGPU_GROUP_KEY_I64 / _DEC128 / _BOOL / _BYTES_KIND */
+  uint32_t is_null;
+  int32_t scale_or_unit;
+  uint32_t len;         /* bytes of a String key */
+  uint64_t w[2];        /* little-endian words, two's complement */
+  uint8_t bytes[ORCGPU_GROUP_KEY_BYTES];
+} orcgpu_group_key;
+typedef struct orcgpu_groups orcgpu_groups;
+/* orcgpu_result_aggregate with a GROUP BY: the rows of `r` the predicate keeps, grouped by key_columns, every group reduced by
+ * specs.  *out is a handle to free with orcgpu_groups_free (NULL on failure).  The result is read and left as it was; one host
+ * wait per call, which fetches the group count, the flags, the key records and the value records. */
+int orcgpu_result_aggregate_groups(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                   const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                   const orcgpu_agg_spec* specs, uint32_t n_specs, orcgpu_groups** out);
+/* A builder setter beside orcgpu_reader_set_aggregates (before the first call; the names are copied): the reader's aggregates
+ * are grouped.  orcgpu_reader_aggregate_groups drains it as orcgpu_reader_aggregate does: per stripe the grouped aggregation stands
+ * where the ungrouped one stands, orcgpu_reader_d2h_bytes stays 0, orcgpu_reader_filter_rows reports as under the filter; the
+ * stripes' groups are merged on the host by key in first-appearance order.  orcgpu_reader_aggregate on a reader with a group-by
+ * set, and orcgpu_reader_aggregate_groups on one without, are ORCGPU_INVALID_ARGUMENT and leave the reader usable; a group-by
+ * without aggregates is ORCGPU_INVALID_ARGUMENT at the drain; a second drain is ORCGPU_END_OF_FILE.
+ * ORCGPU_GROUP_HASH_BITS=N (1 .. 32, read per call) keeps N bits of the key tuples' hash, for tests of long probe sequences: the
+ * answer is the same. */
+int orcgpu_reader_set_group_by(orcgpu_reader* r, const char* const* key_columns, uint32_t n_keys);
+int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
+uint32_t orcgpu_groups_count(const orcgpu_groups* g);
+int orcgpu_groups_key(const orcgpu_groups* g, uint32_t group, uint32_t key, orcgpu_group_key* out);
+int orcgpu_groups_value(const orcgpu_groups* g, uint32_t group, uint32_t spec, orcgpu_agg_value* out);
+void orcgpu_groups_free(orcgpu_groups* g);
 /* Read-ahead: how many decoded stripes the reader may be ahead of the caller (default 2 -- every result set in flight costs a pinned host copy of a stripe --, at most 8; 0 = none: every stripe is
  * read, staged, decoded and copied back inside the orcgpu_reader_next_batch call that needs it).  With read-ahead two threads
  * of the reader work beside the caller: one reads and stages the stripes to come, one decodes the stripes staged so far

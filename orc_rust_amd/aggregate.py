@@ -12,6 +12,8 @@ import decimal
 COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT = range(6)  # ORCGPU_AGG_OP_*
 KIND_U64, KIND_I128, KIND_DEC128, KIND_F64, KIND_I64 = range(5)  # ORCGPU_AGG_KIND_*
 AGG_MAX = 64  # ORCGPU_AGG_MAX
+GROUP_KEY_I64, GROUP_KEY_DEC128, GROUP_KEY_BOOL, GROUP_KEY_STRING = range(4)  # ORCGPU_GROUP_KEY_*
+GROUP_MAX_KEYS, GROUP_MAX, GROUP_MAX_TOTAL, GROUP_KEY_BYTES = 4, 256, 65536, 64  # ORCGPU_GROUP_*
 _NAMES = ("count_rows", "count", "sum", "min", "max", "sum_product")
 TS_UNITS = ("s", "ms", "us", "ns")
 
@@ -23,6 +25,11 @@ class AggSpec(C.Structure):
 class AggValue(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("is_null", C.c_uint32), ("overflow", C.c_uint32), ("scale_or_unit", C.c_int32), ("w", C.c_uint64 * 3),
                 ("f", C.c_double)]
+
+
+class GroupKey(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("is_null", C.c_uint32), ("scale_or_unit", C.c_int32), ("len", C.c_uint32), ("w", C.c_uint64 * 2),
+                ("bytes", C.c_uint8 * GROUP_KEY_BYTES)]
 
 
 def _column(what, name):
@@ -86,6 +93,30 @@ def check_specs(specs):
     return list(specs)
 
 
+def check_group_by(group_by):
+    """The group_by argument of aggregate(), checked before anything reaches the GPU: a list or tuple of 1 .. 4 distinct non-empty
+    str.  Returns it as a list."""
+    if not isinstance(group_by, (list, tuple)):
+        raise TypeError("aggregate: group_by is a list or tuple of column names, not %s" % type(group_by).__name__)
+    seen = set()
+    for name in group_by:
+        _column("aggregate: group_by", name)
+        if name in seen:
+            raise ValueError("aggregate: group_by lists column %r twice" % name)
+        seen.add(name)
+    if not group_by:
+        raise ValueError("aggregate: an empty group_by")
+    if len(group_by) > GROUP_MAX_KEYS:
+        raise ValueError("aggregate: %d group_by columns, at most %d" % (len(group_by), GROUP_MAX_KEYS))
+    return list(group_by)
+
+
+def key_array(group_by):
+    """[str] -> ctypes array of char*"""
+    names = check_group_by(group_by)
+    return (C.c_char_p * len(names))(*[n.encode() for n in names])
+
+
 def spec_array(specs):
     """[Agg] -> (ctypes array of orcgpu_agg_spec, what keeps its strings alive)"""
     specs = check_specs(specs)
@@ -130,3 +161,57 @@ def value_of(v, spec):
 
 def values_of(arr, specs):
     return [value_of(v, s) for v, s in zip(arr, specs)]
+
+
+def key_of(k):
+    """orcgpu_group_key -> int / bool / decimal.Decimal / TimestampValue / str / None; a String key whose bytes are not valid
+    UTF-8 comes back as bytes."""
+    if k.is_null:
+        return None
+    if k.kind == GROUP_KEY_BOOL:
+        return bool(k.w[0])
+    if k.kind == GROUP_KEY_DEC128:
+        with decimal.localcontext() as c:
+            c.prec = 60
+            return decimal.Decimal(_signed(k.w[:2], 128)).scaleb(-k.scale_or_unit)
+    if k.kind == GROUP_KEY_STRING:
+        raw = bytes(k.bytes[:min(k.len, GROUP_KEY_BYTES)])
+        try:
+            return raw.decode("utf-8")
+        except UnicodeDecodeError:
+            return raw
+    x = _signed(k.w[:1], 64)
+    if 0 <= k.scale_or_unit < len(TS_UNITS):
+        x = TimestampValue(x)
+        x.units = TS_UNITS[k.scale_or_unit]
+    return x
+
+
+def groups_of(L, handle, n_keys, specs, raw=False):
+    """An orcgpu_groups handle -> [(keys tuple, values list)] in first-appearance order; the handle is freed.  raw=True: the values
+    are the orcgpu_agg_value records.  OverflowError names the spec and the group's keys."""
+    try:
+        out = []
+        for g in range(L.orcgpu_groups_count(handle)):
+            keys = []
+            for k in range(n_keys):
+                rec = GroupKey()
+                if L.orcgpu_groups_key(handle, g, k, C.byref(rec)):
+                    raise RuntimeError("orcgpu_groups_key(%d, %d)" % (g, k))
+                keys.append(key_of(rec))
+            vals = []
+            for i, s in enumerate(specs):
+                v = AggValue()
+                if L.orcgpu_groups_value(handle, g, i, C.byref(v)):
+                    raise RuntimeError("orcgpu_groups_value(%d, %d)" % (g, i))
+                if raw:
+                    vals.append(v)
+                    continue
+                try:
+                    vals.append(value_of(v, s))
+                except OverflowError:
+                    raise OverflowError("aggregate: %r left the range of its result in the group %r" % (s, tuple(keys))) from None
+            out.append((tuple(keys), vals))
+        return out
+    finally:
+        L.orcgpu_groups_free(handle)

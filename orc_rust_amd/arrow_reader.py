@@ -144,21 +144,30 @@ class ArrowReaderBuilder:
         self._device_output = bool(on)
         return self
 
-    def aggregate(self, specs, raw=False):
+    def aggregate(self, specs, raw=False, group_by=None):
         """COUNT, SUM, MIN, MAX and SUM(a * b) over the rows the builder's selection and row filter keep, reduced on the GPU
         (orcgpu_reader_set_aggregates / orcgpu_reader_aggregate): specs is a list of orc_rust_amd.aggregate.Agg, the result a list
         of int (counts, integer results; a Timestamp's with `.units`), decimal.Decimal, float, or None for NULL.  Builds the reader
         and drains it: every stripe is decoded and aggregated where it lies, no batch is copied back.  The projection must hold the
-        aggregated and the filter's columns.  OverflowError, naming the spec, when a result leaves its range."""
-        return self.aggregating_reader(specs).aggregate(raw=raw)
+        aggregated and the filter's columns.  OverflowError, naming the spec, when a result leaves its range.
 
-    def aggregating_reader(self, specs):
+        group_by: a list or tuple of 1 .. 4 distinct column names (orcgpu_reader_set_group_by / orcgpu_reader_aggregate_groups): the
+        result is a list of (keys tuple, values list), one per group of kept rows, in order of first appearance; at most 256
+        groups a stripe.  A key is an int, bool, decimal.Decimal, str (bytes when not UTF-8) or None for the NULL key.  The
+        projection must hold the key columns too.  OverflowError names the spec and the group's keys."""
+        return self.aggregating_reader(specs, group_by=group_by).aggregate(raw=raw)
+
+    def aggregating_reader(self, specs, group_by=None):
         """The same in two steps: the ArrowReader whose aggregate() drains it (and whose filter_rows() / d2h_bytes() report on it)."""
         from . import aggregate as A
         arr, keep = A.spec_array(specs)
+        keys = A.key_array(group_by) if group_by is not None else None
         self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregates(self._h, arr, len(arr)))
+        if keys is not None:
+            self._ctx._check(self._ctx.L.orcgpu_reader_set_group_by(self._h, keys, len(keys)))
         r = self.build()
         r._agg_specs = A.check_specs(specs)
+        r._group_by = A.check_group_by(group_by) if group_by is not None else None
         return r
 
     def total_row_count(self):
@@ -207,6 +216,13 @@ class ArrowReader:
         """Drains a reader built by ArrowReaderBuilder.aggregating_reader (orcgpu_reader_aggregate): the list of Python values."""
         from . import aggregate as A
         specs = getattr(self, "_agg_specs", None)
+        if getattr(self, "_group_by", None) is not None:
+            handle = C.c_void_p()
+            rc = self._ctx.L.orcgpu_reader_aggregate_groups(self._h, C.byref(handle))
+            if rc == 110:
+                raise StopIteration
+            self._ctx._check(rc)
+            return A.groups_of(self._ctx.L, handle, len(self._group_by), specs, raw=raw)
         out = (A.AggValue * max(1, len(specs or ())))()
         rc = self._ctx.L.orcgpu_reader_aggregate(self._h, out)
         if rc == 110:  # ORCGPU_END_OF_FILE: the reader has been drained before

@@ -27,6 +27,8 @@ EXPORTS = [
     "orcgpu_predicate_row_groups",
     "orcgpu_result_filter", "orcgpu_reader_set_row_filter", "orcgpu_reader_filter_rows",
     "orcgpu_result_aggregate", "orcgpu_reader_set_aggregates", "orcgpu_reader_aggregate",
+    "orcgpu_result_aggregate_groups", "orcgpu_reader_set_group_by", "orcgpu_reader_aggregate_groups", "orcgpu_groups_count", "orcgpu_groups_key",
+    "orcgpu_groups_value", "orcgpu_groups_free",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
@@ -216,6 +218,17 @@ def load():
                                           C.POINTER(AggSpec), C.c_uint32, C.POINTER(AggValue)]
     L.orcgpu_reader_set_aggregates.argtypes = [C.c_void_p, C.POINTER(AggSpec), C.c_uint32]
     L.orcgpu_reader_aggregate.argtypes = [C.c_void_p, C.POINTER(AggValue)]
+    from .aggregate import GroupKey
+    L.orcgpu_result_aggregate_groups.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                 C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_set_group_by.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
+    L.orcgpu_reader_aggregate_groups.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.orcgpu_groups_count.restype = C.c_uint32
+    L.orcgpu_groups_count.argtypes = [C.c_void_p]
+    L.orcgpu_groups_key.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GroupKey)]
+    L.orcgpu_groups_value.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(AggValue)]
+    L.orcgpu_groups_free.restype = None
+    L.orcgpu_groups_free.argtypes = [C.c_void_p]
     L.orcgpu_reader_set_row_group_pruning.argtypes = [C.c_void_p, C.c_int]
     L.orcgpu_reader_row_groups.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.orcgpu_index_entry.argtypes = [C.POINTER(Column), C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.c_int32, C.POINTER(StreamEntry)]
@@ -455,6 +468,21 @@ class Context:
         out = (A.AggValue * len(arr))()
         self._check(self.L.orcgpu_result_aggregate(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, len(arr), out))
         return list(out) if raw else A.values_of(out, specs)
+
+    def result_aggregate_groups(self, result, specs, group_by, column_names, predicate=None, raw=False):
+        """orcgpu_result_aggregate_groups: result_aggregate per group of the key columns `group_by` (1 .. 4 column names).  Returns
+        [(keys tuple, values list)] in first-appearance order (aggregate.key_of / value_of); raw=True: the values as records."""
+        from . import aggregate as A
+        arr, keep = A.spec_array(specs)
+        keys = A.key_array(group_by)
+        nodes, n_nodes = None, 0
+        if predicate is not None:
+            nodes, keep_p = predicate.flatten()
+            n_nodes = len(nodes)
+        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
+        out = C.c_void_p()
+        self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, len(arr), C.byref(out)))
+        return A.groups_of(self.L, out, len(keys), A.check_specs(specs), raw=raw)
 
     def timing(self):
         a, b, c = C.c_float(), C.c_float(), C.c_uint32()

@@ -1,0 +1,318 @@
+// agg_group_kernels.hip -- GROUP BY for the aggregates of agg_kernels.hip: the kept rows of a decoded stripe reduced to one
+// record per (aggregate, group), for at most kGroupMax (256) groups a stripe.  Nothing is sorted, gathered or copied back but the
+// groups' keys and records.  The semantics are those of include/orcgpu.h (orcgpu_result_aggregate_groups).
+//
+//   group_assign_kernel       over the words of the keep mask, like agg_partial_kernel.  A kept row hashes its key tuple (per key
+//                             the validity bit and the int64 / 128-bit value / string bytes) and probes an open-addressing table
+//                             of kGroupSlots slots in global memory, linear probing.  A free slot is claimed with a 64-bit
+//                             atomicCAS that stores the claiming input row + 1; a claimed one is compared by loading its claimer's
+//                             keys through the row-access layer (filter_access.h): there is no second copy of the keys.  The row's
+//                             slot goes to a uint32 plane, one entry per input row, and the slot's smallest row is kept with an
+//                             atomicMax on ~row -- once per (wavefront, slot) and only while it still raises the value.  More
+//                             than kGroupMax claims set GROUP_TOO_MANY; later rows stop inserting.
+//   group_number_kernel       one block of kGroupSlots threads: ranks the claimed slots by their first row -> the dense group
+//                             number of every slot and n_groups, and a GroupKeyRecord per (group, key) from the first row.  Which
+//                             row won which slot cannot show: numbers, keys and order come from the first rows alone.
+//   agg_group_partial_kernel  grid (agg_group_blocks(n_in), instructions).  Every wavefront owns a table of kGroupMax AggAcc in
+//                             LDS.  Per 64-row word a lane loads its row as agg_partial_kernel does (agg_row) into an accumulator
+//                             of one row; the wavefront folds the lanes of one group into acc[group] in a fixed order (below).
+//                             Behind the last trip thread t folds acc[t] of the four wavefronts in wavefront order and stores the
+//                             record (instruction, block, group t).
+//   agg_group_final_kernel    one block per (group, instruction): the blocks' records in index order, agg_final_kernel's tree.
+//
+// The fold of a word into LDS, by the number of distinct groups d among its kept lanes -- a function of the data alone, so the same
+// call takes the same path and a Float sum keeps its bits:
+//   d <= kGroupTreeMax (4)    per distinct group, lowest lane first, a masked agg_wave_fold (the lanes of other groups hold the
+//                             empty accumulator) and lane 0 folds the result into acc[group]: 6 shuffle steps a group, whatever the
+//                             multiplicity.  The Q1 kind: a handful of flags.
+//   else                      rounds: a lane's rank among the lanes of its group (popcount of the ballot below it) picks the round
+//                             in which it folds its row into acc[group]; the lanes of a round hold different groups, so different
+//                             addresses.  As many rounds as the largest multiplicity, at most 64 / d rounded up when spread evenly.
+// The threshold is reasoned, not tuned: a tree step moves six 64-bit values by shuffle, a round is one 48-byte LDS read-modify-write,
+// and for d groups spread evenly the two cost 6 d steps against 64 / d rounds.
+//
+// LDS: 4 x 256 x 48 B = 48 KiB a block (three blocks a CU of 160 KiB).  acc[group] is 48 bytes wide, 12 banks: lanes of one round
+// on groups 16 apart (b64 accesses, 64 banks) share banks -- up to 4-way, on the rounds path and in the last fold only.
+// No floating-point atomic anywhere; the integer atomics (CAS, Max, Add, Or) decide slots and flags, never a value handed out.
+//
+// Resource usage of the two wide kernels (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): in front of each.
+#pragma once
+#include <stdint.h>
+
+#include "agg_group_program.h"
+#include "agg_kernels.hip"
+
+constexpr uint32_t kGroupTreeMax = 4;
+
+// ---- a row's key tuple: its hash, and whether two rows hold the same ----
+__device__ __forceinline__ unsigned long long group_key_hash(const FilterCol& c, uint32_t fkind, const FilterRow& r, uint32_t B, uint32_t W) {
+  if (!filter_valid(c, r.u, r.l, W)) return 0x9e3779b97f4a7c15ull;  // NULL: a key value of its own
+  switch (fkind) {
+    case FKIND_BOOL: return 2 + (unsigned long long)filter_load_bit(c, r.u, r.l, W);
+    case FKIND_DEC128: {
+      unsigned long long lo, hi;
+      filter_load_dec128(c, r.row, &lo, &hi);
+      return 4 + (unsigned long long)in_hash_dec128(lo, hi);
+    }
+    case FKIND_STRING: {
+      const FilterStr s = filter_value_str(c, r.u, r.l, B);
+      return 4 + (unsigned long long)in_hash_bytes(s.p, s.len);
+    }
+    default: return 4 + in_mix64((unsigned long long)filter_load_i64(c, r.row));
+  }
+}
+__device__ __forceinline__ uint32_t group_row_hash(const GroupKeys& keys, const FilterCol* cols, const FilterRow& r, uint32_t B, uint32_t W) {
+  unsigned long long h = 0;
+  for (uint32_t k = 0; k < keys.n; k++) h = in_mix64(h + group_key_hash(cols[keys.col[k]], keys.fkind[k], r, B, W) + k);
+  return (uint32_t)h & keys.hash_mask;
+}
+__device__ __forceinline__ bool group_key_equal(const FilterCol& c, uint32_t fkind, const FilterRow& a, const FilterRow& b, uint32_t B, uint32_t W) {
+  const bool va = filter_valid(c, a.u, a.l, W), vb = filter_valid(c, b.u, b.l, W);
+  if (!va || !vb) return va == vb;
+  switch (fkind) {
+    case FKIND_BOOL: return filter_load_bit(c, a.u, a.l, W) == filter_load_bit(c, b.u, b.l, W);
+    case FKIND_DEC128: {
+      unsigned long long alo, ahi, blo, bhi;
+      filter_load_dec128(c, a.row, &alo, &ahi);
+      filter_load_dec128(c, b.row, &blo, &bhi);
+      return alo == blo && ahi == bhi;
+    }
+    case FKIND_STRING: {
+      const FilterStr x = filter_value_str(c, a.u, a.l, B), y = filter_value_str(c, b.u, b.l, B);
+      if (x.len != y.len) return false;
+      for (uint32_t k = 0; k < x.len; k++)
+        if (x.p[k] != y.p[k]) return false;
+      return true;
+    }
+    default: return filter_load_i64(c, a.row) == filter_load_i64(c, b.row);
+  }
+}
+__device__ __forceinline__ bool group_rows_equal(const GroupKeys& keys, const FilterCol* cols, const FilterRow& a, const FilterRow& b, uint32_t B, uint32_t W) {
+  for (uint32_t k = 0; k < keys.n; k++)
+    if (!group_key_equal(cols[keys.col[k]], keys.fkind[k], a, b, B, W)) return false;
+  return true;
+}
+
+// table (kGroupSlots slots) and ctl are zeroed by the call before this kernel; plane gets one entry per input row of the words
+// that hold a kept row: the row's slot, or kGroupNoSlot for a row that is not kept or stopped inserting.  Every index into the
+// table is masked to kGroupSlots; a claimer read from a slot is an input row some thread put there, so below n_in.
+// Resource usage (gfx950): 62 VGPRs, 105 SGPRs, no scratch, no spill, no LDS; occupancy 7 waves / SIMD.
+extern "C" __global__ void __launch_bounds__(256)
+group_assign_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B,
+                    uint32_t W, const unsigned long long* keep, GroupSlot* table, GroupControl* ctl, uint32_t* plane) {
+  const uint32_t lane = threadIdx.x & 63;
+  const FilterWords ws = filter_words(n_in);
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const uint64_t left = n_in - w * 64;
+    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    if (!m) continue;
+    const uint64_t j = w * 64 + lane;
+    const bool kept = ((m >> lane) & 1) && j < n_in;
+    uint32_t slot = kGroupNoSlot;
+    if (kept) {
+      const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, j);
+      const uint32_t h = group_row_hash(keys, cols, r, B, W);
+      for (uint32_t step = 0; step < kGroupSlots; step++) {
+        const uint32_t s = (h + step) & (kGroupSlots - 1);
+        unsigned long long cur = __atomic_load_n(&table[s].claim, __ATOMIC_RELAXED);
+        if (!cur) {
+          if (__atomic_load_n(&ctl->flags, __ATOMIC_RELAXED) & GROUP_TOO_MANY) break;  // (the answer is refused: nothing more goes in)
+          cur = atomicCAS(&table[s].claim, 0ull, (unsigned long long)(j + 1));
+          if (!cur) {
+            if (atomicAdd(&ctl->claimed, 1u) >= kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
+            slot = s;
+            break;
+          }
+        }
+        const uint64_t rep = cur - 1;
+        if (rep == j || (rep < n_in && group_rows_equal(keys, cols, r, filter_row(segs, seg_first, n_segs, n_in, B, rep), B, W))) {
+          slot = s;
+          break;
+        }
+      }
+      if (slot == kGroupNoSlot) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);  // (stopped, or the table is full: more than kGroupMax claims)
+    }
+    plane[j] = slot;  // (the plane holds 64 entries for every word of the mask)
+    // the slot's first row: the lowest lane of every slot in this word speaks for the others, and only while it lowers the row
+    unsigned long long todo = __ballot(slot != kGroupNoSlot);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t ls = (uint32_t)__shfl((int)slot, leader);
+      const unsigned long long same = __ballot(slot == ls);
+      if ((int)lane == leader && __atomic_load_n(&table[ls].first_inv, __ATOMIC_RELAXED) < ~j) atomicMax(&table[ls].first_inv, ~j);
+      todo &= ~same;
+    }
+  }
+}
+
+// <<<1, kGroupSlots>>>: thread s is slot s.  slot_group[s] = the slot's dense group number (kGroupNoSlot: free, or past kGroupMax);
+// key_recs: [group][key].  Nothing is numbered for a table that holds more than kGroupMax groups.
+extern "C" __global__ void __launch_bounds__(1024)
+group_number_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B,
+                    uint32_t W, const GroupSlot* table, GroupControl* ctl, uint32_t* slot_group, GroupKeyRecord* key_recs) {
+  __shared__ unsigned long long first_s[kGroupSlots];
+  __shared__ uint32_t n_s;
+  const uint32_t s = threadIdx.x;
+  if (s == 0) n_s = 0;
+  const bool used = table[s].claim != 0;
+  const unsigned long long first = used ? ~table[s].first_inv : ~0ull;
+  first_s[s] = first;
+  __syncthreads();
+  uint32_t rank = 0;
+  if (used) {
+    for (uint32_t t = 0; t < kGroupSlots; t++) rank += first_s[t] < first;
+    atomicAdd(&n_s, 1u);
+  }
+  __syncthreads();
+  const uint32_t n_groups = n_s;
+  const bool fits = n_groups <= kGroupMax && !(ctl->flags & GROUP_TOO_MANY);
+  if (s == 0) {
+    ctl->n_groups = n_groups;
+    if (n_groups > kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
+  }
+  const bool mine = used && fits && rank < kGroupMax && first < n_in;
+  slot_group[s] = mine ? rank : kGroupNoSlot;
+  if (!mine) return;
+  const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, first);
+  for (uint32_t k = 0; k < keys.n; k++) {
+    const FilterCol c = cols[keys.col[k]];
+    GroupKeyRecord* out = key_recs + (uint64_t)rank * keys.n + k;
+    out->is_null = 0;
+    out->len = 0;
+    out->w[0] = out->w[1] = 0;
+    for (uint32_t x = 0; x < kGroupKeyBytes; x++) out->bytes[x] = 0;
+    if (!filter_valid(c, r.u, r.l, W)) {
+      out->is_null = 1;
+      continue;
+    }
+    if (keys.fkind[k] == FKIND_BOOL) {
+      out->w[0] = filter_load_bit(c, r.u, r.l, W);
+    } else if (keys.fkind[k] == FKIND_DEC128) {
+      unsigned long long lo, hi;
+      filter_load_dec128(c, r.row, &lo, &hi);
+      out->w[0] = lo;
+      out->w[1] = hi;
+    } else if (keys.fkind[k] == FKIND_STRING) {
+      const FilterStr v = filter_value_str(c, r.u, r.l, B);
+      out->len = v.len;
+      if (v.len > kGroupKeyBytes) atomicOr(&ctl->flags, (uint32_t)GROUP_KEY_TOO_LONG << k);
+      for (uint32_t x = 0; x < v.len && x < kGroupKeyBytes; x++) out->bytes[x] = v.p[x];
+    } else {
+      const long long v = filter_load_i64(c, r.row);
+      out->w[0] = (unsigned long long)v;
+      out->w[1] = (unsigned long long)(v >> 63);
+    }
+  }
+}
+
+// partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's
+// entries are trusted no further than a slot index below kGroupSlots, the numbers of slot_group no further than a group below
+// kGroupMax: whatever a refused table left in them, every LDS and global address stays in bounds.
+// Resource usage (gfx950): 78 VGPRs, 104 SGPRs, no scratch, no spill, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
+                         uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                         AggPartial* partials) {
+  __shared__ AggAcc acc_s[4][kGroupMax];
+  if (ctl->flags & GROUP_TOO_MANY) return;  // (uniform: the whole grid leaves)
+  const uint32_t n_groups = ctl->n_groups < kGroupMax ? ctl->n_groups : kGroupMax;
+  const AggInsn in = insns[blockIdx.y];
+  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const bool is_max = in.is_max != 0;
+  const FilterCol c = cols[in.col], c2 = cols[in.col2];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const AggAcc zero = {0, 0, 0, 0.0, 0, 0};
+  AggAcc* const acc = acc_s[wave];
+  for (uint32_t g = lane; g < kGroupMax; g += 64) acc[g] = zero;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  const FilterWords ws = filter_words(n_in);
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const uint64_t left = n_in - w * 64;
+    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    if (!m) continue;
+    const uint64_t j = w * 64 + lane;
+    uint32_t g = kGroupNoSlot;
+    AggAcc v = zero;
+    if (((m >> lane) & 1) && j < n_in) {
+      const uint32_t slot = plane[j];
+      g = slot < kGroupSlots ? slot_group[slot] : kGroupNoSlot;
+      if (g >= n_groups) g = kGroupNoSlot;
+    }
+    const bool kept = g != kGroupNoSlot;
+    if (kept) {
+      if (kind == AK_COUNT_ROWS) v.w0 = 1;
+      else agg_row(kind, is_max, in, c, c2, filter_row(segs, seg_first, n_segs, n_in, B, j), W, v);
+    }
+    // the distinct groups of the word, and a lane's peers: the lanes that hold its group
+    unsigned long long todo = __ballot(kept), peers = 0;
+    uint32_t d = 0;
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t lg = (uint32_t)__shfl((int)g, leader);
+      const unsigned long long same = __ballot(kept && g == lg);
+      if (kept && g == lg) peers = same;
+      todo &= ~same;
+      d++;
+    }
+    if (!d) continue;
+    if (d <= kGroupTreeMax) {
+      todo = __ballot(kept);
+      while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t lg = (uint32_t)__shfl((int)g, leader);
+        const bool in_it = kept && g == lg;
+        AggAcc t = in_it ? v : zero;
+        agg_wave_fold(kind, is_max, t);
+        if (lane == 0) {
+          AggAcc a = acc[lg];
+          agg_fold(kind, is_max, a, t);
+          acc[lg] = a;
+        }
+        todo &= ~__ballot(in_it);
+      }
+    } else {
+      const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+      uint32_t rounds = kept ? (uint32_t)__popcll(peers) : 0;
+      for (int o = 32; o; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)rounds, o);
+        rounds = other > rounds ? other : rounds;
+      }
+      for (uint32_t round = 0; round < rounds; round++) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // (a round reads what the round before wrote, from another lane)
+        if (kept && rank == round) {
+          AggAcc a = acc[g];
+          agg_fold(kind, is_max, a, v);
+          acc[g] = a;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  }
+  __syncthreads();
+  const uint32_t t = threadIdx.x;
+  if (t < n_groups) {
+    AggAcc a = acc_s[0][t];
+    for (uint32_t x = 1; x < 4; x++) agg_fold(kind, is_max, a, acc_s[x][t]);
+    agg_store(partials + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * kGroupMax + t, a);
+  }
+}
+
+// grid (kGroupMax, instructions): block (g, k) folds the n_blocks records of group g under instruction k -> out[k][g]; the blocks
+// of groups that do not exist leave at once
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_t n_blocks, const GroupControl* ctl, AggPartial* out) {
+  __shared__ AggAcc fold_s[4];
+  if ((ctl->flags & GROUP_TOO_MANY) || blockIdx.x >= ctl->n_groups) return;
+  const AggInsn in = insns[blockIdx.y];
+  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const bool is_max = in.is_max != 0;
+  const AggPartial* p = partials + (uint64_t)blockIdx.y * n_blocks * kGroupMax + blockIdx.x;
+  AggAcc a = {0, 0, 0, 0.0, 0, 0};
+  for (uint32_t k = threadIdx.x; k < n_blocks; k += 256) {
+    const AggPartial& q = p[(uint64_t)k * kGroupMax];
+    const AggAcc b = {q.w[0], q.w[1], q.w[2], q.f, q.count, q.flags};
+    agg_fold(kind, is_max, a, b);
+  }
+  agg_block_fold(kind, is_max, a, fold_s);
+  if (threadIdx.x == 0) agg_store(out + (uint64_t)blockIdx.y * kGroupMax + blockIdx.x, a);
+}

@@ -113,6 +113,77 @@ __device__ __forceinline__ void agg_minmax(uint32_t kind, bool is_max, AggAcc& a
   agg_fold(kind, is_max, a, b);
 }
 
+// One kept row into an accumulator of instruction `in` (any kind but AK_COUNT_ROWS, which reads no row): what agg_partial_kernel
+// and agg_group_partial_kernel (agg_group_kernels.hip) do per lane.  A null value adds nothing.
+__device__ __forceinline__ void agg_row(uint32_t kind, bool is_max, const AggInsn& in, const FilterCol& c, const FilterCol& c2, const FilterRow& r, uint32_t W,
+                                        AggAcc& a) {
+  if (!r.live || !filter_valid(c, r.u, r.l, W)) return;
+  switch (kind) {
+    case AK_COUNT: a.w0++; break;
+    case AK_SUM_INT:
+      agg_add_i64(a, filter_load_i64(c, r.row));
+      a.count++;
+      break;
+    case AK_SUM_DEC: {
+      unsigned long long lo, hi;
+      filter_load_dec128(c, r.row, &lo, &hi);
+      agg_add_i128(a, lo, hi);
+      a.count++;
+      break;
+    }
+    case AK_SUM_F64:
+      a.f += filter_load_f64(c, r.row);
+      a.count++;
+      break;
+    case AK_SP_INT:
+    case AK_SP_DEC: {
+      if (!filter_valid(c2, r.u, r.l, W)) break;
+      long long x, y;
+      if (kind == AK_SP_INT) {
+        x = filter_load_i64(c, r.row);
+        y = filter_load_i64(c2, r.row);
+      } else {
+        unsigned long long xl, xh, yl, yh;
+        filter_load_dec128(c, r.row, &xl, &xh);
+        filter_load_dec128(c2, r.row, &yl, &yh);
+        if (xh != (unsigned long long)((long long)xl >> 63) || yh != (unsigned long long)((long long)yl >> 63)) {
+          a.flags |= AGG_OVERFLOW;  // an operand that does not fit a signed 64-bit word: sticky, the row is left out
+          a.count++;
+          break;
+        }
+        x = (long long)xl;
+        y = (long long)yl;
+      }
+      const __int128 p = (__int128)x * (__int128)y;
+      agg_add_i128(a, (unsigned long long)p, (unsigned long long)(p >> 64));
+      a.count++;
+      break;
+    }
+    case AK_SP_F64:
+      if (!filter_valid(c2, r.u, r.l, W)) break;
+      a.f += filter_load_f64(c, r.row) * filter_load_f64(c2, r.row);
+      a.count++;
+      break;
+    case AK_MINMAX_INT: {
+      const long long v = in.fkind == FKIND_BOOL ? (long long)filter_load_bit(c, r.u, r.l, W) : filter_load_i64(c, r.row);
+      agg_minmax(kind, is_max, a, (unsigned long long)v, 0, 0.0);
+      break;
+    }
+    case AK_MINMAX_DEC: {
+      unsigned long long lo, hi;
+      filter_load_dec128(c, r.row, &lo, &hi);
+      agg_minmax(kind, is_max, a, lo, hi, 0.0);
+      break;
+    }
+    default: {  // AK_MINMAX_F64
+      const double v = filter_load_f64(c, r.row);
+      if (v != v) a.flags |= AGG_SAW_NAN;
+      else agg_minmax(kind, is_max, a, 0, 0, v);
+      break;
+    }
+  }
+}
+
 // keep: the mask filter_eval_kernel left, one word per 64 input rows (null: no filter, every input row is kept).
 // partials: [instruction][block].  A lane whose row is not kept loads nothing; a kept row is an input row below n_in, and the
 // row-access layer turns it into a row of the stripe: every load lies where the decode wrote.
@@ -137,71 +208,7 @@ agg_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* 
     }
     if (!((m >> lane) & 1)) continue;
     const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
-    if (!r.live || !filter_valid(c, r.u, r.l, W)) continue;
-    switch (kind) {
-      case AK_COUNT: a.w0++; break;
-      case AK_SUM_INT:
-        agg_add_i64(a, filter_load_i64(c, r.row));
-        a.count++;
-        break;
-      case AK_SUM_DEC: {
-        unsigned long long lo, hi;
-        filter_load_dec128(c, r.row, &lo, &hi);
-        agg_add_i128(a, lo, hi);
-        a.count++;
-        break;
-      }
-      case AK_SUM_F64:
-        a.f += filter_load_f64(c, r.row);
-        a.count++;
-        break;
-      case AK_SP_INT:
-      case AK_SP_DEC: {
-        if (!filter_valid(c2, r.u, r.l, W)) break;
-        long long x, y;
-        if (kind == AK_SP_INT) {
-          x = filter_load_i64(c, r.row);
-          y = filter_load_i64(c2, r.row);
-        } else {
-          unsigned long long xl, xh, yl, yh;
-          filter_load_dec128(c, r.row, &xl, &xh);
-          filter_load_dec128(c2, r.row, &yl, &yh);
-          if (xh != (unsigned long long)((long long)xl >> 63) || yh != (unsigned long long)((long long)yl >> 63)) {
-            a.flags |= AGG_OVERFLOW;  // an operand that does not fit a signed 64-bit word: sticky, the row is left out
-            a.count++;
-            break;
-          }
-          x = (long long)xl;
-          y = (long long)yl;
-        }
-        const __int128 p = (__int128)x * (__int128)y;
-        agg_add_i128(a, (unsigned long long)p, (unsigned long long)(p >> 64));
-        a.count++;
-        break;
-      }
-      case AK_SP_F64:
-        if (!filter_valid(c2, r.u, r.l, W)) break;
-        a.f += filter_load_f64(c, r.row) * filter_load_f64(c2, r.row);
-        a.count++;
-        break;
-      case AK_MINMAX_INT: {
-        const long long v = in.fkind == FKIND_BOOL ? (long long)filter_load_bit(c, r.u, r.l, W) : filter_load_i64(c, r.row);
-        agg_minmax(kind, is_max, a, (unsigned long long)v, 0, 0.0);
-        break;
-      }
-      case AK_MINMAX_DEC: {
-        unsigned long long lo, hi;
-        filter_load_dec128(c, r.row, &lo, &hi);
-        agg_minmax(kind, is_max, a, lo, hi, 0.0);
-        break;
-      }
-      default: {  // AK_MINMAX_F64
-        const double v = filter_load_f64(c, r.row);
-        if (v != v) a.flags |= AGG_SAW_NAN;
-        else agg_minmax(kind, is_max, a, 0, 0, v);
-        break;
-      }
-    }
+    agg_row(kind, is_max, in, c, c2, r, W, a);
   }
   agg_block_fold(kind, is_max, a, fold_s);
   if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);

@@ -44,6 +44,7 @@
 #include "device/select_kernels.hip"
 #include "device/filter_kernels.hip"
 #include "device/agg_kernels.hip"
+#include "device/agg_group_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -498,6 +499,8 @@ struct orcgpu_result {
   size_t filt_used = 0;
   std::vector<AggPartial> agg_records;  // an aggregating file reader: the stripe's record per aggregate, then its kept row count
   uint64_t agg_seen = 0;                // ... and the rows the aggregation saw
+  std::vector<GroupKeyRecord> grp_keys;  // ... with a GROUP BY: the stripe's groups in first-appearance order, keys [group][key]
+  std::vector<AggPartial> grp_vals;      // ... and records [group][aggregate, then the group's kept row count]
   std::vector<ColumnOut> cols;
   std::vector<std::string> field_names;  // per column: the name of a Struct's field (set by the file reader; empty: "f<position>")
   // Elements of the List / Map columns: one result each over a "stripe" whose rows are the column's elements (all of the

@@ -45,6 +45,9 @@ struct orcgpu_reader {
     std::string column, column2;
   };
   std::vector<AggSpec> agg_specs;
+  // GROUP BY (orcgpu_reader_set_group_by): the key columns as given
+  bool has_group = false;
+  std::vector<std::string> group_keys;
   // device output (orcgpu_reader_set_device_output): the batches are views of the results' HBM, handed out by
   // orcgpu_reader_next_batch_device; no copy back is started.  A result the caller is done with goes to `home` instead of `spare`
   // -- at once, or when the last exported batch or tensor that views it is released (device_hold.h)
@@ -72,6 +75,7 @@ struct orcgpu_reader {
   // copy back would stand
   bool aggs_done = false;
   orcgpu_host::AggPlan agg_plan;
+  orcgpu_host::GroupPlan group_plan;
   uint64_t d2h_bytes = 0;                     // column-buffer bytes copied to the host so far (orcgpu_reader_d2h_bytes)
   bool current_counted = false;               // ... those of `current` are in it
   bool device_checked = false, device_refused = false;  // the projection has been looked at for nested columns; it has one
@@ -328,9 +332,7 @@ std::vector<orcgpu_agg_spec> reader_view_aggs(const orcgpu_reader* rd) {
 // The aggregate list against the projected root columns as the file's metadata and the builder describe them -> its instructions,
 // once, before anything is read: every refusal arrives here.  (What a stripe's decode made of the columns is checked again, per
 // stripe, by the plan the kernels run: reader_aggregate_result.)
-int reader_compile_aggs(orcgpu_reader* rd) {
-  std::vector<const char*> names;
-  std::vector<AggCol> cols;
+void reader_describe_roots(orcgpu_reader* rd, std::vector<const char*>& names, std::vector<AggCol>& cols) {
   for (size_t k : rd->proj.roots()) {
     const ProjCol& pc = rd->proj.cols[k];
     const OrcType& t = rd->md.types[pc.id];
@@ -350,9 +352,24 @@ int reader_compile_aggs(orcgpu_reader* rd) {
     a.nested = is_nested_kind(t.kind);
     cols.push_back(a);
   }
+}
+int reader_compile_aggs(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<AggCol> cols;
+  reader_describe_roots(rd, names, cols);
   const std::vector<orcgpu_agg_spec> specs = reader_view_aggs(rd);
   const int rc = agg_compile(specs.data(), (uint32_t)specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
   if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
+  return rc;
+}
+// ... and the key list of a GROUP BY, against the same description
+int reader_compile_group(orcgpu_reader* rd) {
+  std::vector<const char*> names, keys;
+  std::vector<AggCol> cols;
+  reader_describe_roots(rd, names, cols);
+  for (auto& k : rd->group_keys) keys.push_back(k.c_str());
+  const int rc = group_compile(keys.data(), (uint32_t)keys.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->group_plan);
+  if (rc) set_err(rd->ctx, "%s", rd->group_plan.err);
   return rc;
 }
 
@@ -377,6 +394,26 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
       set_err(rd->ctx, "aggregate: column '%s' is not decoded to the type its aggregate was planned for", names[plan.insns[k].col]);
       return ORCGPU_MISMATCHED_SCHEMA;
     }
+  if (rd->has_group) {  // the grouped reduction in the same place: the stripe's groups stay with the result
+    std::vector<const char*> keys;
+    for (auto& k : rd->group_keys) keys.push_back(k.c_str());
+    GroupPlan gplan;
+    if (const int rc = result_compile_group(rd->ctx, res, keys.data(), (uint32_t)keys.size(), names.data(), gplan)) return rc;
+    for (size_t k = 0; k < gplan.keys.size(); k++)
+      if (gplan.keys[k].kind != rd->group_plan.keys[k].kind || gplan.keys[k].scale_or_unit != rd->group_plan.keys[k].scale_or_unit) {
+        set_err(rd->ctx, "group by: key column '%s' is not decoded to the type its key was planned for", names[gplan.keys[k].col]);
+        return ORCGPU_MISMATCHED_SCHEMA;
+      }
+    GroupSet set;
+    uint64_t kept = 0;
+    const int rc = result_aggregate_groups_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, gplan, set, &res->agg_seen, &kept, names.data(), (uint32_t)names.size());
+    if (rc) return rc;
+    res->grp_keys = std::move(set.keys);
+    res->grp_vals = std::move(set.vals);
+    rd->filter_seen += res->agg_seen;
+    rd->filter_kept += kept;
+    return ORCGPU_OK;
+  }
   const int rc = result_aggregate_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, res->agg_records, &res->agg_seen, names.data(), (uint32_t)names.size());
   if (rc) return rc;
   rd->filter_seen += res->agg_seen;

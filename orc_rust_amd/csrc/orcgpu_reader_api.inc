@@ -340,6 +340,10 @@ int orcgpu_reader_aggregate(orcgpu_reader* rd, orcgpu_agg_value* out) {
     set_err(rd->ctx, "orcgpu_reader_aggregate needs orcgpu_reader_set_aggregates before the first call");
     return ORCGPU_INVALID_ARGUMENT;
   }
+  if (rd->has_group) {
+    set_err(rd->ctx, "this reader groups its aggregates (orcgpu_reader_set_group_by): call orcgpu_reader_aggregate_groups");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (rd->aggs_done) return ORCGPU_END_OF_FILE;
   int rc = orcgpu_host::reader_build(rd);
   if (rc) return rc;
@@ -367,6 +371,68 @@ int orcgpu_reader_aggregate(orcgpu_reader* rd, orcgpu_agg_value* out) {
     return rc;
   }
   for (size_t k = 0; k < insns.size(); k++) orcgpu_host::agg_finish(insns[k], total[k], &out[k]);
+  return ORCGPU_OK;
+}
+int orcgpu_reader_set_group_by(orcgpu_reader* rd, const char* const* key_columns, uint32_t n_keys) {
+  if (!rd || rd->built || !key_columns || !n_keys || n_keys > ORCGPU_GROUP_MAX_KEYS) return ORCGPU_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_keys; k++)
+    if (!key_columns[k]) return ORCGPU_INVALID_ARGUMENT;
+  rd->group_keys.assign(key_columns, key_columns + n_keys);
+  rd->has_group = true;
+  return ORCGPU_OK;
+}
+// Drains the reader: every stripe's groups, merged by key in stripe order, then the keys and the values
+int orcgpu_reader_aggregate_groups(orcgpu_reader* rd, orcgpu_groups** out) {
+  if (out) *out = nullptr;
+  if (!rd || !out) return ORCGPU_INVALID_ARGUMENT;
+  if (!rd->has_group) {
+    set_err(rd->ctx, "orcgpu_reader_aggregate_groups needs orcgpu_reader_set_group_by before the first call");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (rd->aggs_done) return ORCGPU_END_OF_FILE;
+  int rc = orcgpu_host::reader_build(rd);
+  if (rc) return rc;
+  rd->aggs_done = true;  // (whatever comes of it: an error ends the reader as it ends an iterator)
+  if (!rd->has_aggs) {
+    set_err(rd->ctx, "group by: orcgpu_reader_set_group_by without orcgpu_reader_set_aggregates");
+    rc = ORCGPU_INVALID_ARGUMENT;
+  }
+  if (!rc) rc = orcgpu_host::reader_compile_group(rd);
+  if (!rc) rc = orcgpu_host::reader_compile_aggs(rd);
+  if (!rc) rc = reader_ready_filter(rd);
+  if (rc) {
+    rd->next_stripe = rd->stripe_order.size();
+    return rc;
+  }
+  std::vector<AggInsn> insns = rd->agg_plan.insns;
+  const uint32_t n_specs = (uint32_t)insns.size();
+  insns.push_back(AggInsn{});  // (the group's kept row count: AK_COUNT_ROWS)
+  const size_t nk = rd->group_plan.keys.size(), ni = insns.size();
+  orcgpu_host::GroupSet total;
+  total.n_keys = (uint32_t)nk;
+  total.n_insn = (uint32_t)ni;
+  while (!(rc = reader_next_stripe(rd))) {
+    const orcgpu_result* res = rd->current;
+    if (res->grp_keys.size() % nk || res->grp_vals.size() != res->grp_keys.size() / nk * ni) {
+      set_err(rd->ctx, "group by: a stripe came without its groups");
+      rc = ORCGPU_UNEXPECTED;
+      break;
+    }
+    char err[256];
+    rc = orcgpu_host::group_merge(rd->group_plan, insns, total, res->grp_keys.data(), res->grp_vals.data(), (uint32_t)(res->grp_keys.size() / nk), err, sizeof(err));
+    if (rc) {
+      set_err(rd->ctx, "%s", err);
+      break;
+    }
+  }
+  if (rc != ORCGPU_END_OF_FILE) {
+    orcgpu_host::reader_stop_worker(rd);
+    rd->next_stripe = rd->stripe_order.size();
+    return rc;
+  }
+  orcgpu_groups* g = new orcgpu_groups;
+  orcgpu_host::group_finish(rd->group_plan, insns, n_specs, total, *g);
+  *out = g;
   return ORCGPU_OK;
 }
 int orcgpu_reader_set_device_output(orcgpu_reader* rd, int on) {
