@@ -675,6 +675,75 @@ int orcgpu_result_aggregate_groups(orcgpu_ctx* ctx, const orcgpu_result* r, cons
  * answer is the same. */
 int orcgpu_reader_set_group_by(orcgpu_reader* r, const char* const* key_columns, uint32_t n_keys);
 int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
+/* ---- SUM and AVG over arithmetic expressions, evaluated per kept row on the device --------------------------------------------
+ * TPC-H Q1's select list holds sum(l_extendedprice * (1 - l_discount)), sum(l_extendedprice * (1 - l_discount) * (1 + l_tax)) and
+ * three averages.  One aggregate argument may be an arithmetic EXPRESSION over columns and literals, evaluated exactly, per kept
+ * row, in kernels beside those that reduce the plain aggregates (device/agg_expr_eval.h, device/agg_kernels.hip).  The reference has
+ * no aggregation; the semantics are fixed here.
+ *   - NODES, in pre-order like orcgpu_predicate_node: ORCGPU_AGG_EXPR_COLUMN (`column`: a projected root column),
+ *     ORCGPU_AGG_EXPR_LITERAL (value_type ORCGPU_PV_INT64: i; ORCGPU_PV_FLOAT64: f; ORCGPU_PV_DECIMAL128: s / s_len / i under the
+ *     rules of that value type in predicates), ORCGPU_AGG_EXPR_ADD / _SUB / _MUL (exactly two children) and ORCGPU_AGG_EXPR_NEG (one).
+ *     No division, no functions.
+ *   - CLASSES, decided bottom-up when the list is compiled:
+ *       INT    Byte .. Long columns and INT64 literals.  Every intermediate value is a signed 128-bit integer.  ORCGPU_AGG_KIND_I128.
+ *       DEC    at least one Decimal column or DECIMAL128 literal; Byte .. Long columns and INT64 literals beside them count as
+ *              Decimals of scale 0.  a * b has the scale s_a + s_b; a + b and a - b the scale max(s_a, s_b), the operand of lower
+ *              scale multiplied by the power of ten, exactly; NEG keeps the scale.  A node whose scale passes 38:
+ *              ORCGPU_UNSUPPORTED, the message names the expression's first column.  Every intermediate value is the unscaled
+ *              signed 128-bit integer.  ORCGPU_AGG_KIND_DEC128 at the root's scale; overflow = 1 when the final |sum| >= 10^38.
+ *       FLOAT  Float / Double columns (a Float widened first) and FLOAT64 literals; INT64 literals too when (double)i is exact,
+ *              else ORCGPU_INVALID_ARGUMENT.  Every operation is ONE IEEE double operation rounded once: nothing is contracted into
+ *              a fused multiply-add.  ORCGPU_AGG_KIND_F64, deterministic as SUM is: the same bits on every run of the same call.
+ *   - REFUSED when the list is compiled.  ORCGPU_MISMATCHED_SCHEMA, the message naming the column: a Float / Double column or a
+ *     FLOAT64 literal together with an integer or Decimal column; a FLOAT64 literal in an INT / DEC expression (a DECIMAL128
+ *     literal in a FLOAT one); a column of any other kind (Date, Boolean, Timestamp, String, ...).  ORCGPU_UNSUPPORTED: a column read
+ *     as a dictionary column, a Timestamp decoded to Decimal128 (as for SUM); an expression that needs more than
+ *     ORCGPU_AGG_EXPR_MAX_DEPTH operand slots when the child that needs more slots is evaluated first (of the trees of
+ *     ORCGPU_AGG_EXPR_MAX_NODES nodes only the perfectly balanced one of 16 leaves does; operand order never changes a result).
+ *     ORCGPU_INVALID_ARGUMENT: an unknown or unprojected column; a malformed tree (a wrong child count -- n_children is not
+ *     carried: an operator simply takes the nodes behind it --, nodes left over, an unknown node op, a literal of another value
+ *     type, a bad Decimal literal); an expression without any column; more than ORCGPU_AGG_EXPR_MAX_NODES nodes.
+ *   - NULLS: a row in which any column of the expression is NULL contributes nothing: the expression is NULL and SUM skips it.
+ *   - OVERFLOW: an INT / DEC operation whose exact result does not fit a signed 128-bit integer -- the multiplication by a power of
+ *     ten that aligns two scales included -- sets the sticky overflow flag of the aggregate; that row's value is left out, the row
+ *     still counts.  Nothing wraps silently.  The sum itself is 192 bits wide, as for SUM.
+ *   - OPS: ORCGPU_AGG_OP_SUM_EXPR the sum of the expression over the kept rows where it is not NULL, NULL over no such row;
+ *     ORCGPU_AGG_OP_AVG the average of a plain column (the columns SUM takes); ORCGPU_AGG_OP_AVG_EXPR the average of an expression.
+ *     A *_EXPR op without an expression -- through an entry point without `exprs` too -- is ORCGPU_INVALID_ARGUMENT.
+ *   - AVG is the exact sum divided by the number of values, finished on the host.  FLOAT: sum / (double)count.  INT:
+ *     ORCGPU_AGG_KIND_F64, the double nearest to the exact rational sum / count, ties to even; a sum that does not fit 128 bits is
+ *     overflow = 1.  DEC at scale s: ORCGPU_AGG_KIND_DEC128 at scale min(s + 4, 38), the exact quotient rounded half away from zero
+ *     (Hive's and Spark's rule); overflow = 1 when the sum overflowed or |result| >= 10^38.  Over no value: NULL.
+ * The three entry points below are the ones above with a second array parallel to `specs`: exprs[k] is the expression of specs[k],
+ * {NULL, 0} for an op that takes none (exprs = NULL: no spec has one -- this is what the entry points above call).  Everything said
+ * of the aggregates holds per expression aggregate: row selection, filter, pruning, grouping, the merge across stripes, no byte
+ * copied back, one wait per stripe.  orcgpu_reader_set_aggregate_exprs copies nodes, names and literal bytes;
+ * orcgpu_reader_aggregate[_groups] drain as before. */
+#define ORCGPU_AGG_EXPR_MAX_NODES 32
+#define ORCGPU_AGG_EXPR_MAX_DEPTH 4
+enum { ORCGPU_AGG_OP_SUM_EXPR = 6, ORCGPU_AGG_OP_AVG = 7, ORCGPU_AGG_OP_AVG_EXPR = 8 };
+enum { ORCGPU_AGG_EXPR_COLUMN = 0, ORCGPU_AGG_EXPR_LITERAL = 1, ORCGPU_AGG_EXPR_ADD = 2, ORCGPU_AGG_EXPR_SUB = 3, ORCGPU_AGG_EXPR_MUL = 4,
+       ORCGPU_AGG_EXPR_NEG = 5 };
+typedef struct {
+  uint32_t op;           /* ORCGPU_AGG_EXPR_*                                   */
+  const char* column;    /* COLUMN: the name of a projected root column        */
+  int32_t value_type;    /* LITERAL: ORCGPU_PV_INT64 / _FLOAT64 / _DECIMAL128  */
+  int64_t i;
+  double f;
+  const char* s;
+  uint64_t s_len;
+} orcgpu_agg_expr_node;  /* pre-order, like orcgpu_predicate_node */
+typedef struct {
+  const orcgpu_agg_expr_node* nodes;
+  uint32_t n_nodes;
+} orcgpu_agg_expr;
+int orcgpu_result_aggregate_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                  const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs,
+                                  const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_agg_value* out);
+int orcgpu_result_aggregate_groups_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                         const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                         const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_groups** out);
+int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs);
 uint32_t orcgpu_groups_count(const orcgpu_groups* g);
 int orcgpu_groups_key(const orcgpu_groups* g, uint32_t group, uint32_t key, orcgpu_group_key* out);
 int orcgpu_groups_value(const orcgpu_groups* g, uint32_t group, uint32_t spec, orcgpu_agg_value* out);

@@ -5,21 +5,43 @@ orcgpu_reader_aggregate): the specs a caller writes, their C form, and the Pytho
     total, = ArrowReaderBuilder.try_new("lineitem.orc").with_projection([...]).with_row_filter(q6).aggregate(
         [Agg.sum_product("l_extendedprice", "l_discount")])          # a decimal.Decimal
 
+An aggregate's argument may be an arithmetic expression over columns and literals, evaluated exactly per kept row on the GPU
+(orcgpu_result_aggregate_exprs): `col(name)` and `lit(v)` build an Expr, `+ - *` and unary `-` combine them, plain Python numbers
+on either side are wrapped.  TPC-H Q1 whole:
+
+    from orc_rust_amd.aggregate import Agg, col
+    price, disc, tax = col("l_extendedprice"), col("l_discount"), col("l_tax")
+    q1 = builder.aggregate([Agg.sum("l_quantity"), Agg.sum("l_extendedprice"), Agg.sum(price * (1 - disc)), Agg.sum(price * (1 - disc) * (1 + tax)),
+                            Agg.avg("l_quantity"), Agg.avg("l_extendedprice"), Agg.avg("l_discount"), Agg.count_rows()],
+                           group_by=["l_returnflag", "l_linestatus"])
+
 Pure plumbing: nothing is computed here, and every argument is checked before anything reaches the GPU."""
 import ctypes as C
 import decimal
 
-COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT = range(6)  # ORCGPU_AGG_OP_*
+COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG, AVG_EXPR = range(9)  # ORCGPU_AGG_OP_*
+EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(6)  # ORCGPU_AGG_EXPR_*
+PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
+EXPR_MAX_NODES, EXPR_MAX_DEPTH = 32, 4  # ORCGPU_AGG_EXPR_MAX_*
 KIND_U64, KIND_I128, KIND_DEC128, KIND_F64, KIND_I64 = range(5)  # ORCGPU_AGG_KIND_*
 AGG_MAX = 64  # ORCGPU_AGG_MAX
 GROUP_KEY_I64, GROUP_KEY_DEC128, GROUP_KEY_BOOL, GROUP_KEY_STRING = range(4)  # ORCGPU_GROUP_KEY_*
 GROUP_MAX_KEYS, GROUP_MAX, GROUP_MAX_TOTAL, GROUP_KEY_BYTES = 4, 256, 65536, 64  # ORCGPU_GROUP_*
-_NAMES = ("count_rows", "count", "sum", "min", "max", "sum_product")
+_NAMES = ("count_rows", "count", "sum", "min", "max", "sum_product", "sum", "avg", "avg")
 TS_UNITS = ("s", "ms", "us", "ns")
 
 
 class AggSpec(C.Structure):
     _fields_ = [("op", C.c_uint32), ("column", C.c_char_p), ("column2", C.c_char_p)]
+
+
+class AggExprNode(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("column", C.c_char_p), ("value_type", C.c_int32), ("i", C.c_int64), ("f", C.c_double), ("s", C.c_char_p),
+                ("s_len", C.c_uint64)]
+
+
+class AggExpr(C.Structure):
+    _fields_ = [("nodes", C.POINTER(AggExprNode)), ("n_nodes", C.c_uint32)]
 
 
 class AggValue(C.Structure):
@@ -40,11 +62,120 @@ def _column(what, name):
     return name
 
 
-class Agg:
-    """One aggregate: Agg.count_rows(), .count(c), .sum(c), .min(c), .max(c), .sum_product(a, b)."""
+class Expr:
+    """An arithmetic expression over columns and literals: built by col() and lit(), combined with + - * and unary -."""
 
-    def __init__(self, op, column=None, column2=None):
-        self.op, self.column, self.column2 = op, column, column2
+    def __init__(self, op, children=(), column=None, value_type=None, value=None):
+        self.op, self.children, self.column, self.value_type, self.value = op, tuple(children), column, value_type, value
+
+    @staticmethod
+    def _wrap(x):
+        return x if isinstance(x, Expr) else lit(x)
+
+    def __add__(self, other):
+        return Expr(EXPR_ADD, (self, Expr._wrap(other)))
+
+    def __radd__(self, other):
+        return Expr(EXPR_ADD, (Expr._wrap(other), self))
+
+    def __sub__(self, other):
+        return Expr(EXPR_SUB, (self, Expr._wrap(other)))
+
+    def __rsub__(self, other):
+        return Expr(EXPR_SUB, (Expr._wrap(other), self))
+
+    def __mul__(self, other):
+        return Expr(EXPR_MUL, (self, Expr._wrap(other)))
+
+    def __rmul__(self, other):
+        return Expr(EXPR_MUL, (Expr._wrap(other), self))
+
+    def __neg__(self):
+        return Expr(EXPR_NEG, (self,))
+
+    def __repr__(self):
+        if self.op == EXPR_COLUMN:
+            return "col(%r)" % self.column
+        if self.op == EXPR_LITERAL:
+            if self.value_type == PV_DECIMAL128:
+                return "lit(Decimal('%s'))" % decimal.Decimal(self.value[0]).scaleb(-self.value[1], _WIDE)
+            return "lit(%r)" % (self.value,)
+        if self.op == EXPR_NEG:
+            return "(-%r)" % (self.children[0],)
+        return "(%r %s %r)" % (self.children[0], {EXPR_ADD: "+", EXPR_SUB: "-", EXPR_MUL: "*"}[self.op], self.children[1])
+
+    def node_count(self):
+        return 1 + sum(c.node_count() for c in self.children)
+
+    def flatten(self):
+        """-> (ctypes array of AggExprNode in pre-order, objects to keep alive): what Predicate.flatten does for a predicate."""
+        out, keep = [], []
+
+        def walk(e):
+            n = AggExprNode()
+            n.op = e.op
+            if e.op == EXPR_COLUMN:
+                keep.append(e.column.encode())
+                n.column = keep[-1]
+            elif e.op == EXPR_LITERAL:
+                n.value_type = e.value_type
+                if e.value_type == PV_DECIMAL128:
+                    unscaled, scale = e.value
+                    keep.append(int(unscaled).to_bytes(16, "little", signed=True))
+                    n.s, n.s_len, n.i = keep[-1], 16, int(scale)
+                elif e.value_type == PV_FLOAT64:
+                    n.f = e.value
+                else:
+                    n.i = e.value
+            out.append(n)
+            for c in e.children:
+                walk(c)
+
+        walk(self)
+        return (AggExprNode * len(out))(*out), keep
+
+
+_WIDE = decimal.Context(prec=80)
+
+
+def col(name):
+    """A projected root column as an expression."""
+    return Expr(EXPR_COLUMN, column=_column("col", name))
+
+
+def lit(v):
+    """A literal as an expression: an int (int64), a decimal.Decimal (a Decimal128 literal: at most 38 digits, scale 0 .. 38; a
+    positive exponent is written out at scale 0) or a float.  bool is a TypeError; a NaN / Infinity Decimal, a magnitude of 10^38 or
+    more unscaled, a scale past 38 and an int outside int64 are a ValueError."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, decimal.Decimal)):
+        raise TypeError("lit: an int, a decimal.Decimal or a float, not %s" % type(v).__name__)
+    if isinstance(v, int):
+        if not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("lit: the int %d is outside int64" % v)
+        return Expr(EXPR_LITERAL, value_type=PV_INT64, value=v)
+    if isinstance(v, float):
+        return Expr(EXPR_LITERAL, value_type=PV_FLOAT64, value=v)
+    if not v.is_finite():
+        raise ValueError("lit: the Decimal %r is not a finite number" % (v,))
+    sign, digits, exponent = v.as_tuple()
+    unscaled = int("".join(map(str, digits)) or "0")
+    if exponent > 0:
+        if unscaled and len(digits) + exponent > 38:
+            raise ValueError("lit: the Decimal %r has a magnitude of 10^38 or more" % (v,))
+        unscaled, exponent = unscaled * 10 ** exponent, 0
+    if sign:
+        unscaled = -unscaled
+    if -exponent > 38 or abs(unscaled) >= 10 ** 38:
+        raise ValueError("lit: the Decimal %r needs a scale of 0 .. 38 and an unscaled magnitude below 10^38" % (v,))
+    return Expr(EXPR_LITERAL, value_type=PV_DECIMAL128, value=(unscaled, -exponent))
+
+
+class Agg:
+    """One aggregate: Agg.count_rows(), .count(c), .sum(c), .avg(c), .min(c), .max(c), .sum_product(a, b); sum and avg take a column
+    name or an Expr."""
+
+    def __init__(self, op, column=None, column2=None, expr=None):
+        self.op, self.column, self.column2, self.expr = op, column, column2, expr
 
     @classmethod
     def count_rows(cls):
@@ -56,7 +187,15 @@ class Agg:
 
     @classmethod
     def sum(cls, column):
+        if isinstance(column, Expr):
+            return cls(SUM_EXPR, expr=column)
         return cls(SUM, _column("Agg.sum", column))
+
+    @classmethod
+    def avg(cls, column):
+        if isinstance(column, Expr):
+            return cls(AVG_EXPR, expr=column)
+        return cls(AVG, _column("Agg.avg", column))
 
     @classmethod
     def min(cls, column):
@@ -71,7 +210,7 @@ class Agg:
         return cls(SUM_PRODUCT, _column("Agg.sum_product", column), _column("Agg.sum_product", column2))
 
     def __repr__(self):
-        return "Agg.%s(%s)" % (_NAMES[self.op], ", ".join(repr(c) for c in (self.column, self.column2) if c is not None))
+        return "Agg.%s(%s)" % (_NAMES[self.op], ", ".join(repr(c) for c in (self.column, self.column2, self.expr) if c is not None))
 
 
 class TimestampValue(int):
@@ -128,6 +267,24 @@ def spec_array(specs):
             if name is not None:
                 keep.append(name.encode())
                 setattr(arr[i], field, keep[-1])
+    return arr, keep
+
+
+def expr_array(specs):
+    """[Agg] -> (ctypes array of orcgpu_agg_expr parallel to spec_array's, what keeps its nodes alive), or (None, []) when no
+    spec holds an Expr: the bindings then call the entry points without expressions."""
+    specs = check_specs(specs)
+    if not any(s.expr is not None for s in specs):
+        return None, []
+    arr = (AggExpr * len(specs))()
+    keep = []
+    for i, s in enumerate(specs):
+        if s.expr is None:
+            continue
+        nodes, alive = s.expr.flatten()
+        keep.append((nodes, alive))
+        arr[i].nodes = nodes
+        arr[i].n_nodes = len(nodes)
     return arr, keep
 
 

@@ -29,6 +29,7 @@ EXPORTS = [
     "orcgpu_result_aggregate", "orcgpu_reader_set_aggregates", "orcgpu_reader_aggregate",
     "orcgpu_result_aggregate_groups", "orcgpu_reader_set_group_by", "orcgpu_reader_aggregate_groups", "orcgpu_groups_count", "orcgpu_groups_key",
     "orcgpu_groups_value", "orcgpu_groups_free",
+    "orcgpu_result_aggregate_exprs", "orcgpu_result_aggregate_groups_exprs", "orcgpu_reader_set_aggregate_exprs",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
@@ -218,7 +219,12 @@ def load():
                                           C.POINTER(AggSpec), C.c_uint32, C.POINTER(AggValue)]
     L.orcgpu_reader_set_aggregates.argtypes = [C.c_void_p, C.POINTER(AggSpec), C.c_uint32]
     L.orcgpu_reader_aggregate.argtypes = [C.c_void_p, C.POINTER(AggValue)]
-    from .aggregate import GroupKey
+    from .aggregate import AggExpr, GroupKey
+    L.orcgpu_result_aggregate_exprs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32, C.POINTER(AggValue)]
+    L.orcgpu_result_aggregate_groups_exprs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                       C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_set_aggregate_exprs.argtypes = [C.c_void_p, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32]
     L.orcgpu_result_aggregate_groups.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                                  C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.c_uint32, C.POINTER(C.c_void_p)]
     L.orcgpu_reader_set_group_by.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
@@ -460,13 +466,17 @@ class Context:
         result is left as it was.  Returns the Python values (aggregate.value_of); raw=True: the orcgpu_agg_value records."""
         from . import aggregate as A
         arr, keep = A.spec_array(specs)
+        exprs, keep_e = A.expr_array(specs)
         nodes, n_nodes = None, 0
         if predicate is not None:
             nodes, keep_p = predicate.flatten()
             n_nodes = len(nodes)
         names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
         out = (A.AggValue * len(arr))()
-        self._check(self.L.orcgpu_result_aggregate(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, len(arr), out))
+        if exprs is None:
+            self._check(self.L.orcgpu_result_aggregate(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, len(arr), out))
+        else:
+            self._check(self.L.orcgpu_result_aggregate_exprs(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, exprs, len(arr), out))
         return list(out) if raw else A.values_of(out, specs)
 
     def result_aggregate_groups(self, result, specs, group_by, column_names, predicate=None, raw=False):
@@ -481,7 +491,12 @@ class Context:
             n_nodes = len(nodes)
         names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
         out = C.c_void_p()
-        self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, len(arr), C.byref(out)))
+        exprs, keep_e = A.expr_array(specs)
+        if exprs is None:
+            self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, len(arr), C.byref(out)))
+        else:
+            self._check(self.L.orcgpu_result_aggregate_groups_exprs(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, exprs, len(arr),
+                                                                    C.byref(out)))
         return A.groups_of(self.L, out, len(keys), A.check_specs(specs), raw=raw)
 
     def timing(self):

@@ -1,0 +1,274 @@
+// agg_expr_eval.h -- the arithmetic of an aggregate's expression (include/orcgpu.h: ORCGPU_AGG_OP_SUM_EXPR / _AVG_EXPR), ONE text
+// for the kernels (agg_kernels.hip), the host's plan compiler, which folds literals with it (orcgpu_agg_expr.inc), and the CPU
+// check that runs it against Python ints (tests/hostcheck/agg_expr_check.cpp): checked signed 128-bit add / subtract / multiply /
+// negate, the powers of ten, the interpreter of a program of AggExprOp (agg_program.h) over four operand slots, and -- host only --
+// AVG's division.  Plain C++ behind AGG_HD; nothing wraps silently: an operation whose exact result does not fit a signed
+// 128-bit integer reports it, and the caller sets AGG_OVERFLOW.
+#pragma once
+#include <stdint.h>
+
+#include "agg_program.h"
+
+#if defined(__HIPCC__)
+#define AGG_HD __host__ __device__ __forceinline__
+#else
+#define AGG_HD inline
+#endif
+
+typedef __int128 agg_i128;
+typedef unsigned __int128 agg_u128;
+
+AGG_HD agg_i128 agg_i128_of(unsigned long long lo, unsigned long long hi) { return (agg_i128)(((agg_u128)hi << 64) | lo); }
+AGG_HD agg_i128 agg_i128_min() { return (agg_i128)((agg_u128)1 << 127); }
+
+// r = a + b; false when the exact sum does not fit (r is then the wrapped value, not to be used)
+AGG_HD bool agg_add_checked(agg_i128 a, agg_i128 b, agg_i128* r) {
+  const agg_u128 s = (agg_u128)a + (agg_u128)b;
+  *r = (agg_i128)s;
+  return (agg_i128)(((agg_u128)a ^ s) & ((agg_u128)b ^ s)) >= 0;
+}
+AGG_HD bool agg_sub_checked(agg_i128 a, agg_i128 b, agg_i128* r) {
+  const agg_u128 s = (agg_u128)a - (agg_u128)b;
+  *r = (agg_i128)s;
+  return (agg_i128)(((agg_u128)a ^ (agg_u128)b) & ((agg_u128)a ^ s)) >= 0;
+}
+AGG_HD bool agg_neg_checked(agg_i128 a, agg_i128* r) {
+  *r = (agg_i128)((agg_u128)0 - (agg_u128)a);
+  return a != agg_i128_min();
+}
+// r = a * b from the magnitudes' four 64 x 64 -> 128 partial products: the 256-bit product fits when its high half is zero and
+// its low half is at most 2^127, 2^127 itself for a negative result only
+AGG_HD bool agg_mul_checked(agg_i128 a, agg_i128 b, agg_i128* r) {
+  const bool neg = (a < 0) != (b < 0);
+  const agg_u128 ma = a < 0 ? (agg_u128)0 - (agg_u128)a : (agg_u128)a, mb = b < 0 ? (agg_u128)0 - (agg_u128)b : (agg_u128)b;
+  const unsigned long long a0 = (unsigned long long)ma, a1 = (unsigned long long)(ma >> 64), b0 = (unsigned long long)mb, b1 = (unsigned long long)(mb >> 64);
+  const agg_u128 p00 = (agg_u128)a0 * b0, p01 = (agg_u128)a0 * b1, p10 = (agg_u128)a1 * b0, p11 = (agg_u128)a1 * b1;
+  // bits 64 .. 191: the cross products and the high word of p00; what passes bit 127 is the high half's
+  const agg_u128 mid = (p00 >> 64) + (unsigned long long)p01 + (unsigned long long)p10;
+  const bool high = p11 != 0 || (p01 >> 64) != 0 || (p10 >> 64) != 0 || (mid >> 64) != 0;
+  const agg_u128 low = (mid << 64) | (unsigned long long)p00;
+  const agg_u128 top = (agg_u128)1 << 127;
+  *r = (agg_i128)(neg ? (agg_u128)0 - low : low);
+  return !high && (low < top || (neg && low == top));
+}
+// 10^k, k = 0 .. 38 (what a Decimal128's 38 digits take)
+AGG_HD agg_i128 agg_pow10(uint32_t k) {
+  agg_i128 v = 1;
+  for (uint32_t x = 0; x < k && x < 38; x++) v *= 10;
+  return v;
+}
+
+// (contraction is switched off for the evaluator by name: the rounded-operation intrinsics alone are plain + and * in some
+// toolchains, and "one IEEE operation" must not rest on where the optimiser happens to see a multiply and an add)
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+AGG_HD double agg_f64_add(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __dadd_rn(a, b);
+#else
+  volatile double r = a + b;  // (one rounding: nothing to contract with)
+  return r;
+#endif
+}
+AGG_HD double agg_f64_mul(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __dmul_rn(a, b);  // never contracted into an FMA with the addition behind it
+#else
+  volatile double r = a * b;
+  return r;
+#endif
+}
+AGG_HD double agg_f64_of_bits(unsigned long long u) {
+  union {
+    unsigned long long u;
+    double d;
+  } x;
+  x.u = u;
+  return x.d;
+}
+AGG_HD unsigned long long agg_bits_of_f64(double d) {
+  union {
+    unsigned long long u;
+    double d;
+  } x;
+  x.d = d;
+  return x.u;
+}
+
+// The four operand slots as named values, moved on push and pop: s0 is the top.  (An indexed private array would live in scratch
+// memory on the GPU.)
+template <typename T>
+struct AggSlots {
+  T s0, s1, s2, s3;
+  AGG_HD void push(T v) {
+    s3 = s2;
+    s2 = s1;
+    s1 = s0;
+    s0 = v;
+  }
+  // the two top slots -> one: what stood below them moves up
+  AGG_HD void merge(T v) {
+    s0 = v;
+    s1 = s2;
+    s2 = s3;
+  }
+};
+
+enum { AGG_ROW_NULL = 0, AGG_ROW_VALUE = 1, AGG_ROW_OVERFLOW = 2 };
+
+// A program of the INT / DEC class on one row.  Row: `bool valid(uint32_t col)`, `agg_i128 load_int(uint32_t col)` (an int64
+// column) and `agg_i128 load_dec(uint32_t col)`.  AGG_ROW_NULL: a gating column is NULL, the row contributes nothing;
+// AGG_ROW_OVERFLOW: an operation left 128 bits, the row counts and its value is left out; AGG_ROW_VALUE: *out.
+// The host's compiler guarantees what is not checked again here: at most four slots in use, operands where an op takes them.
+template <typename Row>
+AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+  AggSlots<agg_i128> s = {0, 0, 0, 0};
+  bool ok = true;
+  for (uint32_t k = 0; k < n; k++) {
+    const AggExprOp op = prog[k];
+    agg_i128 r = 0;
+    switch (op.op) {
+      case AX_GATE:
+        if (!row.valid(op.col)) return AGG_ROW_NULL;
+        break;
+      case AX_PUSH_INT: s.push(row.load_int(op.col)); break;
+      case AX_PUSH_DEC: s.push(row.load_dec(op.col)); break;
+      case AX_PUSH_LIT: s.push(agg_i128_of(op.lo, op.hi)); break;
+      case AX_ADD:
+        ok &= agg_add_checked(s.s1, s.s0, &r);
+        s.merge(r);
+        break;
+      case AX_SUB:
+        ok &= agg_sub_checked(s.s1, s.s0, &r);
+        s.merge(r);
+        break;
+      case AX_RSUB:
+        ok &= agg_sub_checked(s.s0, s.s1, &r);
+        s.merge(r);
+        break;
+      case AX_MUL:
+        ok &= agg_mul_checked(s.s1, s.s0, &r);
+        s.merge(r);
+        break;
+      case AX_NEG:
+        ok &= agg_neg_checked(s.s0, &r);
+        s.s0 = r;
+        break;
+      case AX_SCALE10:
+        ok &= agg_mul_checked(s.s0, agg_i128_of(op.lo, op.hi), &r);
+        s.s0 = r;
+        break;
+      default: break;
+    }
+  }
+  *out = s.s0;
+  return ok ? AGG_ROW_VALUE : AGG_ROW_OVERFLOW;
+}
+
+// ... of the FLOAT class.  Row: `valid` and `double load_f64(uint32_t col)`.  Every operation is one IEEE double operation.
+template <typename Row>
+AGG_HD int agg_expr_eval_f64(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+  AggSlots<double> s = {0.0, 0.0, 0.0, 0.0};
+  for (uint32_t k = 0; k < n; k++) {
+    const AggExprOp op = prog[k];
+    switch (op.op) {
+      case AX_GATE:
+        if (!row.valid(op.col)) return AGG_ROW_NULL;
+        break;
+      case AX_PUSH_F64: s.push(row.load_f64(op.col)); break;
+      case AX_PUSH_LIT: s.push(agg_f64_of_bits(op.lo)); break;
+      case AX_ADD: s.merge(agg_f64_add(s.s1, s.s0)); break;
+      case AX_SUB: s.merge(agg_f64_add(s.s1, -s.s0)); break;
+      case AX_RSUB: s.merge(agg_f64_add(s.s0, -s.s1)); break;
+      case AX_MUL: s.merge(agg_f64_mul(s.s1, s.s0)); break;
+      case AX_NEG: s.s0 = -s.s0; break;
+      default: break;
+    }
+  }
+  *out = s.s0;
+  return AGG_ROW_VALUE;
+}
+#if defined(__clang__)
+#pragma clang fp contract(fast)  // (what hipcc builds the rest of the library with)
+#endif
+
+// ---- AVG's division: host functions (the device hands over the exact sum and the count) ----
+
+// |w| of a signed 192-bit integer (three little-endian words); returns whether it was negative
+inline bool agg_abs192(const unsigned long long* w, unsigned long long* m) {
+  const bool neg = (long long)w[2] < 0;
+  unsigned long long carry = neg ? 1 : 0;
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long x = neg ? ~w[k] : w[k];
+    m[k] = x + carry;
+    carry = carry && m[k] == 0;
+  }
+  return neg;
+}
+// m <- m * f (f below 2^64); false when it leaves 192 bits
+inline bool agg_mul192_u64(unsigned long long* m, unsigned long long f) {
+  unsigned long long carry = 0;
+  for (int k = 0; k < 3; k++) {
+    const agg_u128 p = (agg_u128)m[k] * f + carry;
+    m[k] = (unsigned long long)p;
+    carry = (unsigned long long)(p >> 64);
+  }
+  return carry == 0;
+}
+// m <- m / d, returns the remainder (d != 0): long division, a 128-by-64 step per word
+inline unsigned long long agg_div192_u64(unsigned long long* m, unsigned long long d) {
+  unsigned long long rem = 0;
+  for (int k = 2; k >= 0; k--) {
+    const agg_u128 cur = ((agg_u128)rem << 64) | m[k];
+    m[k] = (unsigned long long)(cur / d);
+    rem = (unsigned long long)(cur % d);
+  }
+  return rem;
+}
+// The average of a Decimal sum `w` (|sum| < 10^38) at scale s over `count` values, at scale min(s + 4, 38): the exact quotient
+// rounded half away from zero, as Hive and Spark do.  out: the signed 192-bit result (the caller checks |result| < 10^38).
+inline void agg_avg_decimal(const unsigned long long* w, unsigned long long count, uint32_t scale, uint32_t* out_scale, unsigned long long* out) {
+  const uint32_t rs = scale + 4 < 38 ? scale + 4 : 38;
+  *out_scale = rs;
+  unsigned long long m[3];
+  const bool neg = agg_abs192(w, m);
+  agg_mul192_u64(m, (unsigned long long)agg_pow10(rs - scale));  // (below 10^42: it fits)
+  const unsigned long long rem = agg_div192_u64(m, count);
+  if (rem >= count - rem) {  // 2 rem >= count: half or more, away from zero
+    for (int k = 0; k < 3; k++)
+      if (++m[k]) break;
+  }
+  unsigned long long carry = neg ? 1 : 0;
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long x = neg ? ~m[k] : m[k];
+    out[k] = x + carry;
+    carry = carry && out[k] == 0;
+  }
+}
+inline int agg_bits128(agg_u128 v) {
+  int n = 0;
+  while (v) {
+    n++;
+    v >>= 1;
+  }
+  return n;
+}
+// The double nearest to the exact rational sum / count, ties to even (Python's int / int): sum a signed 128-bit integer
+inline double agg_avg_int(agg_i128 sum, unsigned long long count) {
+  if (sum == 0) return 0.0;
+  const bool neg = sum < 0;
+  const agg_u128 n = neg ? (agg_u128)0 - (agg_u128)sum : (agg_u128)sum;
+  // a quotient of at least 55 bits, and whether anything is left behind it
+  const int want = 56 + agg_bits128(count) - agg_bits128(n), sh = want > 0 ? want : 0;  // (n << sh: at most 120 bits when sh > 0)
+  const agg_u128 num = n << sh;
+  const agg_u128 q = num / count;
+  const bool sticky = num % count != 0;
+  const int bq = agg_bits128(q);
+  const int drop = bq - 53;  // (bq >= 56: with sh > 0 by the choice of sh, with sh = 0 because bits(n) >= 56 + bits(count))
+  unsigned long long mant = (unsigned long long)(q >> drop);
+  const agg_u128 rest = q & (((agg_u128)1 << drop) - 1), half = (agg_u128)1 << (drop - 1);
+  if (rest > half || (rest == half && (sticky || (mant & 1)))) mant++;
+  const double r = __builtin_ldexp((double)mant, drop - sh);
+  return neg ? -r : r;
+}

@@ -208,18 +208,23 @@ group_number_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs,
 // partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's
 // entries are trusted no further than a slot index below kGroupSlots, the numbers of slot_group no further than a group below
 // kGroupMax: whatever a refused table left in them, every LDS and global address stays in bounds.
-// Resource usage (gfx950): 78 VGPRs, 104 SGPRs, no scratch, no spill, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.
-extern "C" __global__ void __launch_bounds__(256)
-agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
-                         uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
-                         AggPartial* partials) {
-  __shared__ AggAcc acc_s[4][kGroupMax];
+// Resource usage (gfx950): agg_group_partial_kernel 68 VGPRs, 102 SGPRs; agg_group_expr_partial_kernel 72 VGPRs, 102 SGPRs; both no scratch, no
+// spill, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.
+// (The body of two kernels: EXPR = false is agg_group_partial_kernel, which takes the plain kinds and leaves the AK_EXPR_* rows of
+// grid.y at once; EXPR = true is agg_group_expr_partial_kernel, the other way round, launched only when the list holds such an
+// instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.)
+template <bool EXPR>
+__device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs,
+                                                       const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W,
+                                                       const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                                                       AggPartial* partials, AggAcc (*acc_s)[kGroupMax]) {
   if (ctl->flags & GROUP_TOO_MANY) return;  // (uniform: the whole grid leaves)
   const uint32_t n_groups = ctl->n_groups < kGroupMax ? ctl->n_groups : kGroupMax;
   const AggInsn in = insns[blockIdx.y];
-  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  if (agg_is_expr(in.kind) != EXPR) return;  // (uniform over the block)
+  const uint32_t kind = EXPR ? in.kind : in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
   const bool is_max = in.is_max != 0;
-  const FilterCol c = cols[in.col], c2 = cols[in.col2];
+  const FilterCol c = cols[EXPR ? 0 : in.col], c2 = cols[EXPR ? 0 : in.col2];  // (EXPR: col / col2 are no column indexes; unused)
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const AggAcc zero = {0, 0, 0, 0.0, 0, 0};
   AggAcc* const acc = acc_s[wave];
@@ -240,7 +245,8 @@ agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelB
     }
     const bool kept = g != kGroupNoSlot;
     if (kept) {
-      if (kind == AK_COUNT_ROWS) v.w0 = 1;
+      if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(segs, seg_first, n_segs, n_in, B, j), W, v);
+      else if (kind == AK_COUNT_ROWS) v.w0 = 1;
       else agg_row(kind, is_max, in, c, c2, filter_row(segs, seg_first, n_segs, n_in, B, j), W, v);
     }
     // the distinct groups of the word, and a lane's peers: the lanes that hold its group
@@ -296,6 +302,20 @@ agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelB
     agg_store(partials + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * kGroupMax + t, a);
   }
 }
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
+                         uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                         AggPartial* partials) {
+  __shared__ AggAcc acc_s[4][kGroupMax];
+  agg_group_partial_body<false>(insns, nullptr, cols, segs, seg_first, n_segs, n_in, B, W, keep, plane, slot_group, ctl, partials, acc_s);
+}
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first,
+                              uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane,
+                              const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials) {
+  __shared__ AggAcc acc_s[4][kGroupMax];
+  agg_group_partial_body<true>(insns, ops, cols, segs, seg_first, n_segs, n_in, B, W, keep, plane, slot_group, ctl, partials, acc_s);
+}
 
 // grid (kGroupMax, instructions): block (g, k) folds the n_blocks records of group g under instruction k -> out[k][g]; the blocks
 // of groups that do not exist leave at once
@@ -304,7 +324,7 @@ agg_group_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_
   __shared__ AggAcc fold_s[4];
   if ((ctl->flags & GROUP_TOO_MANY) || blockIdx.x >= ctl->n_groups) return;
   const AggInsn in = insns[blockIdx.y];
-  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const uint32_t kind = in.kind < AK_ALL_N ? in.kind : AK_COUNT_ROWS;
   const bool is_max = in.is_max != 0;
   const AggPartial* p = partials + (uint64_t)blockIdx.y * n_blocks * kGroupMax + blockIdx.x;
   AggAcc a = {0, 0, 0, 0.0, 0, 0};

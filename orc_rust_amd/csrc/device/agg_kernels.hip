@@ -10,6 +10,10 @@
 //                        shuffles in a fixed tree, the block its four wavefronts through LDS in wavefront order: ONE record per
 //                        (block, instruction).
 //   agg_final_kernel     one block per instruction: thread t folds records t, t + 256, ... in index order, then the same tree.
+//   agg_expr_partial_kernel  agg_partial_kernel for the instructions that sum an arithmetic expression (AK_EXPR_*): the same grid,
+//                        the same records, the same folds; a lane runs the instruction's program (agg_expr_eval.h) on its row.
+//                        A kernel of its own, launched only when the list holds such an instruction, so that the interpreter's
+//                        registers are not the plain kinds'; each of the two kernels leaves the other's rows of grid.y at once.
 //
 // Integer and Decimal sums travel as three 64-bit words with explicit carries -- wide enough for every partial sum, so the
 // order of summation cannot show.  Float sums take whatever the fixed shape gives: the grid is a function of the input row
@@ -17,6 +21,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "agg_expr_eval.h"
 #include "agg_program.h"
 #include "filter_access.h"
 #include "filter_program.h"
@@ -54,9 +59,9 @@ __device__ __forceinline__ bool agg_less_i128(unsigned long long alo, unsigned l
 // a <- a (+) b: what two accumulators of one instruction fold to.  `a` stands in front of `b` in the fixed order.
 __device__ __forceinline__ void agg_fold(uint32_t kind, bool is_max, AggAcc& a, const AggAcc& b) {
   a.flags |= b.flags;
-  if (kind == AK_SUM_F64 || kind == AK_SP_F64) {
+  if (agg_is_float_sum(kind)) {
     a.f += b.f;
-  } else if (kind < AK_MINMAX_INT) {
+  } else if (agg_is_wide_sum(kind)) {
     agg_add192(a, b.w0, b.w1, b.w2);
   } else if (b.count) {
     bool take = !a.count;
@@ -184,6 +189,43 @@ __device__ __forceinline__ void agg_row(uint32_t kind, bool is_max, const AggIns
   }
 }
 
+// A row as the expression evaluator reads it: the columns through the row-access layer.  `col` comes from the program, which the
+// host checked against the column table; it is uniform over the wavefront, so a column's description is read by scalar loads.
+struct AggExprRow {
+  const FilterCol* cols;
+  FilterRow r;
+  uint32_t W;
+  __device__ __forceinline__ bool valid(uint32_t col) const { return filter_valid(cols[col], r.u, r.l, W); }
+  __device__ __forceinline__ agg_i128 load_int(uint32_t col) const { return (agg_i128)filter_load_i64(cols[col], r.row); }
+  __device__ __forceinline__ agg_i128 load_dec(uint32_t col) const {
+    unsigned long long lo, hi;
+    filter_load_dec128(cols[col], r.row, &lo, &hi);
+    return agg_i128_of(lo, hi);
+  }
+  __device__ __forceinline__ double load_f64(uint32_t col) const { return filter_load_f64(cols[col], r.row); }
+};
+
+#pragma clang fp contract(off)  // (the sum's addition is an operation of its own, never fused with the expression's last multiply)
+// One kept row into an accumulator of an AK_EXPR_* instruction whose program is prog[0 .. n): a row with a NULL operand adds
+// nothing; a row whose value left 128 bits counts, sets the sticky flag and adds nothing
+__device__ __forceinline__ void agg_expr_row(uint32_t kind, const AggExprOp* prog, uint32_t n, const FilterCol* cols, const FilterRow& r, uint32_t W, AggAcc& a) {
+  if (!r.live) return;
+  const AggExprRow row = {cols, r, W};
+  if (kind == AK_EXPR_F64) {
+    double v;
+    if (agg_expr_eval_f64(prog, n, row, &v) == AGG_ROW_NULL) return;
+    a.f += v;
+  } else {
+    agg_i128 v;
+    const int rc = agg_expr_eval_i128(prog, n, row, &v);
+    if (rc == AGG_ROW_NULL) return;
+    if (rc == AGG_ROW_OVERFLOW) a.flags |= AGG_OVERFLOW;
+    else agg_add_i128(a, (unsigned long long)v, (unsigned long long)((agg_u128)v >> 64));
+  }
+  a.count++;
+}
+#pragma clang fp contract(fast)  // (what the rest of the library is built with)
+
 // keep: the mask filter_eval_kernel left, one word per 64 input rows (null: no filter, every input row is kept).
 // partials: [instruction][block].  A lane whose row is not kept loads nothing; a kept row is an input row below n_in, and the
 // row-access layer turns it into a row of the stripe: every load lies where the decode wrote.
@@ -192,6 +234,7 @@ agg_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* 
                    uint32_t B, uint32_t W, const unsigned long long* keep, AggPartial* partials) {
   __shared__ AggAcc fold_s[4];
   const AggInsn in = insns[blockIdx.y];
+  if (agg_is_expr(in.kind)) return;  // (agg_expr_partial_kernel's: col / col2 are no column indexes)
   const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
   const bool is_max = in.is_max != 0;
   const FilterCol c = cols[in.col], c2 = cols[in.col2];
@@ -214,12 +257,36 @@ agg_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* 
   if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
 }
 
+// agg_partial_kernel for the AK_EXPR_* instructions of the list (the others' blocks leave at once): ops is the op table the
+// instructions' programs lie in.  Same grid, same records [instruction][block].
+extern "C" __global__ void __launch_bounds__(256)
+agg_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs,
+                        uint64_t n_in, uint32_t B, uint32_t W, const unsigned long long* keep, AggPartial* partials) {
+  __shared__ AggAcc fold_s[4];
+  const AggInsn in = insns[blockIdx.y];
+  if (!agg_is_expr(in.kind)) return;
+  const uint32_t kind = in.kind;
+  const AggExprOp* prog = ops + in.col;
+  const uint32_t lane = threadIdx.x & 63;
+  const FilterWords ws = filter_words(n_in);
+  AggAcc a = {0, 0, 0, 0.0, 0, 0};
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const uint64_t left = n_in - w * 64;  // (w < ws.n: at least 1)
+    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    if (!((m >> lane) & 1)) continue;
+    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
+    agg_expr_row(kind, prog, in.col2, cols, r, W, a);
+  }
+  agg_block_fold(kind, false, a, fold_s);
+  if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
+}
+
 // blockIdx.x = instruction: its n_blocks records -> out[instruction]
 extern "C" __global__ void __launch_bounds__(256)
 agg_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_t n_blocks, AggPartial* out) {
   __shared__ AggAcc fold_s[4];
   const AggInsn in = insns[blockIdx.x];
-  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const uint32_t kind = in.kind < AK_ALL_N ? in.kind : AK_COUNT_ROWS;
   const bool is_max = in.is_max != 0;
   const AggPartial* p = partials + (uint64_t)blockIdx.x * n_blocks;
   AggAcc a = {0, 0, 0, 0.0, 0, 0};

@@ -16,15 +16,49 @@ enum {
   AK_MINMAX_INT = 8,   // int64 (integers, Date, Timestamp in its unit; FKIND_BOOL: the bit as 0 / 1)
   AK_MINMAX_DEC = 9,   // Decimal128, signed 128-bit order
   AK_MINMAX_F64 = 10,  // doubles; NaN values are left out and noted (AGG_SAW_NAN)
-  AK_N = 11
+  AK_N = 11,           // the kinds agg_partial_kernel / agg_group_partial_kernel reduce
+  // SUM / AVG of an arithmetic expression: a program of AggExprOp per kept row (agg_expr_eval.h), reduced by kernels of their own
+  // (agg_expr_partial_kernel / agg_group_expr_partial_kernel), so that the kinds above keep their registers.  col / col2 are the
+  // program's offset and length in the op table uploaded beside the instructions, not column indexes.
+  AK_EXPR_INT = 11,    // every value a signed 128-bit integer, the sum in 192 bits
+  AK_EXPR_DEC = 12,    // ... the unscaled value of a Decimal at the root's scale
+  AK_EXPR_F64 = 13,    // doubles, every operation rounded once
+  AK_ALL_N = 14
 };
 enum { AGG_OVERFLOW = 1, AGG_SAW_NAN = 2 };
+constexpr bool agg_is_expr(uint32_t kind) { return kind >= AK_EXPR_INT && kind < AK_ALL_N; }
+// which of the two folds a kind takes: a float sum, a 192-bit sum (the counts are sums), or MIN / MAX
+constexpr bool agg_is_float_sum(uint32_t kind) { return kind == AK_SUM_F64 || kind == AK_SP_F64 || kind == AK_EXPR_F64; }
+constexpr bool agg_is_wide_sum(uint32_t kind) { return kind < AK_MINMAX_INT || kind == AK_EXPR_INT || kind == AK_EXPR_DEC; }
+
+// One step of an expression's post-order program over at most kAggExprSlots operand slots.  A program begins with one AX_GATE per
+// distinct column: a row in which one of them is NULL contributes nothing.
+enum {
+  AX_GATE = 0,       // col: the row counts only when this column's value is not NULL
+  AX_PUSH_INT = 1,   // col (FKIND_INT): its int64, sign-extended
+  AX_PUSH_DEC = 2,   // col (FKIND_DEC128): its unscaled 128-bit value
+  AX_PUSH_F64 = 3,   // col (FKIND_FLOAT): its double, a Float32 widened first
+  AX_PUSH_LIT = 4,   // lo / hi: a 128-bit integer, or in lo the bits of a double
+  AX_ADD = 5,        // the two top slots a (below) and b (top) -> a + b
+  AX_SUB = 6,        //                                          -> a - b
+  AX_RSUB = 7,       //                                          -> b - a (the right child was evaluated first)
+  AX_MUL = 8,        //                                          -> a * b
+  AX_NEG = 9,        // the top slot -> its negation
+  AX_SCALE10 = 10,   // the top slot -> itself times lo / hi = 10^k (k in `col`), exactly
+  AX_N = 11
+};
+constexpr uint32_t kAggExprSlots = 4, kAggExprMaxNodes = 32;
+struct AggExprOp {
+  uint32_t op;   // AX_*
+  uint32_t col;  // index into the FilterCol table; AX_SCALE10: k
+  unsigned long long lo, hi;
+};
 
 struct AggInsn {
   uint32_t kind;     // AK_*
   uint32_t is_max;   // AK_MINMAX_*: 1 = MAX
-  uint32_t col;      // index into the FilterCol table
-  uint32_t col2;     // AK_SP_*: the second operand
+  uint32_t col;      // index into the FilterCol table (AK_EXPR_*: the program's first op in the op table)
+  uint32_t col2;     // AK_SP_*: the second operand (AK_EXPR_*: the program's length)
   uint32_t fkind;    // FKIND_* of `col` as the decode left it
   uint32_t op;       // ORCGPU_AGG_* as given
   int32_t scale;     // Decimal results: the scale; Timestamp MIN / MAX: the unit

@@ -6,6 +6,10 @@
 // after it) -> agg_partial_kernel -> agg_final_kernel -> the wait, which fetches one record per aggregate and the kept row count.
 // Without a filter nothing is evaluated: the partial kernel takes every input row as kept.  The result is read, never changed.
 //
+// Instructions that sum an arithmetic expression (AK_EXPR_*) bring their programs in an op table uploaded beside the instructions;
+// agg_expr_partial_kernel / agg_group_expr_partial_kernel reduce them behind the plain partial kernel, into the same records, and
+// are launched only when the list holds such an instruction.
+//
 // With a GROUP BY (orcgpu_result_aggregate_groups; orcgpu_group_plan.inc, device/agg_group_kernels.hip) the same front, then: zero
 // the table -> group_assign_kernel -> group_number_kernel -> agg_group_partial_kernel -> agg_group_final_kernel -> the one wait,
 // which fetches the group count and the flags, the key records and the value records in one copy.
@@ -16,13 +20,14 @@ namespace {
 // Where the aggregation's own tables lie: behind the filter's workspace, in the same allocation
 struct AggWorkspace {
   uint32_t n_insn = 0, blocks = 0;  // instructions (the aggregates, then the kept row count); agg_partial_kernel's blocks along x
-  uint64_t o_insn = 0, o_part = 0, o_out = 0, bytes = 0;
-  AggWorkspace(uint64_t filter_bytes, uint32_t n_specs, uint64_t n_in) {
+  uint64_t o_insn = 0, o_ops = 0, o_part = 0, o_out = 0, bytes = 0;
+  AggWorkspace(uint64_t filter_bytes, uint32_t n_specs, uint64_t n_in, size_t n_ops) {
     FilterBump t;
     t.off = filter_bytes;
     n_insn = n_specs + 1;
     blocks = agg_blocks(n_in);
     o_insn = t.take((uint64_t)n_insn * sizeof(AggInsn) + 16);
+    o_ops = t.take((uint64_t)n_ops * sizeof(AggExprOp) + 16);
     o_part = t.take((uint64_t)n_insn * blocks * sizeof(AggPartial) + 16);
     o_out = t.take((uint64_t)n_insn * sizeof(AggPartial) + 16);
     bytes = t.off;
@@ -33,14 +38,15 @@ struct AggWorkspace {
 // on the stream before every call; [o_back, o_back + back_bytes) is what the one wait fetches: control, key records, value records
 struct GroupWorkspace {
   uint32_t n_insn = 0, n_keys = 0, blocks = 0;
-  uint64_t o_insn = 0, o_table = 0, zero_bytes = 0, o_plane = 0, o_slot_group = 0, o_part = 0, o_back = 0, back_keys = 0, back_vals = 0, back_bytes = 0, first = 0, bytes = 0;
-  GroupWorkspace(uint64_t filter_bytes, uint32_t n_specs, uint32_t n_keys_, uint64_t n_in) {
+  uint64_t o_insn = 0, o_ops = 0, o_table = 0, zero_bytes = 0, o_plane = 0, o_slot_group = 0, o_part = 0, o_back = 0, back_keys = 0, back_vals = 0, back_bytes = 0, first = 0, bytes = 0;
+  GroupWorkspace(uint64_t filter_bytes, uint32_t n_specs, uint32_t n_keys_, uint64_t n_in, size_t n_ops) {
     FilterBump t;
     t.off = filter_bytes;
     n_insn = n_specs + 1;
     n_keys = n_keys_;
     blocks = agg_group_blocks(n_in);
     first = o_insn = t.take((uint64_t)n_insn * sizeof(AggInsn) + 16);
+    o_ops = t.take((uint64_t)n_ops * sizeof(AggExprOp) + 16);
     o_table = t.take((uint64_t)kGroupSlots * sizeof(GroupSlot));
     zero_bytes = (uint64_t)kGroupSlots * sizeof(GroupSlot);
     o_plane = t.take((n_in + 63) / 64 * 64 * 4 + 16);
@@ -54,6 +60,22 @@ struct GroupWorkspace {
   }
 };
 
+// Do the instructions read what is there?  A column index below nc; a program inside the op table whose every op names a column
+// below nc.  (The plan was compiled against these columns: anything else is a caller's mix-up.)
+bool agg_plan_in_bounds(const std::vector<AggInsn>& insns, const std::vector<AggExprOp>& ops, uint32_t nc) {
+  for (const AggInsn& in : insns) {
+    if (in.kind == AK_COUNT_ROWS) continue;
+    if (!agg_is_expr(in.kind)) {
+      if (in.kind >= AK_N || in.col >= nc || in.col2 >= nc) return false;
+      continue;
+    }
+    if (in.col > ops.size() || in.col2 > ops.size() - in.col || !in.col2) return false;
+    for (uint32_t k = in.col; k < in.col + in.col2; k++)
+      if (ops[k].op >= AX_N || (ops[k].op <= AX_PUSH_F64 && ops[k].col >= nc)) return false;
+  }
+  return true;
+}
+
 void agg_describe(const orcgpu_result* r, const std::vector<FilterColDesc>& descs, std::vector<orcgpu_host::AggCol>& cols) {
   cols.resize(r->cols.size());
   for (size_t c = 0; c < r->cols.size(); c++) {
@@ -65,7 +87,8 @@ void agg_describe(const orcgpu_result* r, const std::vector<FilterColDesc>& desc
 }
 
 // Partial -> final -> the one wait: records[k] for instruction k
-int agg_run(FilterCall& f, const FilterWorkspace& ws, const AggWorkspace& aw, const std::vector<AggInsn>& insns, bool has_filter, AggPartial* records) {
+int agg_run(FilterCall& f, const FilterWorkspace& ws, const AggWorkspace& aw, const std::vector<AggInsn>& insns, const std::vector<AggExprOp>& ops, bool has_filter,
+            AggPartial* records) {
   orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
   const AggInsn* d_insn = f.at<const AggInsn>(aw.o_insn);
@@ -75,6 +98,13 @@ int agg_run(FilterCall& f, const FilterWorkspace& ws, const AggWorkspace& aw, co
                      f.at<const unsigned long long>(ws.o_first), (uint32_t)f.segs.size(), f.n_in, f.B, f.W,
                      has_filter ? f.at<const unsigned long long>(ws.o_keep) : nullptr, d_part);
   HIP_TRY(ctx, hipGetLastError());
+  if (!ops.empty()) {  // the expression instructions' rows of the same records
+    HIP_TRY(ctx, ctx->upload(f.X + aw.o_ops, ops.data(), ops.size() * sizeof(AggExprOp), st));
+    hipLaunchKernelGGL(agg_expr_partial_kernel, dim3(aw.blocks, aw.n_insn), dim3(256), 0, st, d_insn, f.at<const AggExprOp>(aw.o_ops), f.at<const FilterCol>(ws.o_cols),
+                       f.at<const SelBatch>(ws.o_segs), f.at<const unsigned long long>(ws.o_first), (uint32_t)f.segs.size(), f.n_in, f.B, f.W,
+                       has_filter ? f.at<const unsigned long long>(ws.o_keep) : nullptr, d_part);
+    HIP_TRY(ctx, hipGetLastError());
+  }
   hipLaunchKernelGGL(agg_final_kernel, dim3(aw.n_insn), dim3(256), 0, st, d_insn, d_part, aw.blocks, d_out);
   HIP_TRY(ctx, hipGetLastError());
   // ---- the aggregation's one wait: a record per aggregate, and the kept row count ----
@@ -102,7 +132,7 @@ int result_aggregate_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
   if (rows_seen) *rows_seen = f.n_in;
   const uint32_t src_batches = r->selected ? r->full_batches : r->n_batches;
   const FilterWorkspace ws(f.plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), src_batches, f.n_in, f.B);
-  const AggWorkspace aw(ws.bytes, (uint32_t)aplan.insns.size(), f.n_in);
+  const AggWorkspace aw(ws.bytes, (uint32_t)aplan.insns.size(), f.n_in, aplan.ops.size());
   if (!r->filt_tmp.ensure(aw.bytes + kAlign)) {
     set_err(ctx, "hipMalloc(%llu) for the aggregation failed", (unsigned long long)aw.bytes);
     return ORCGPU_HIP_ERROR;
@@ -113,8 +143,7 @@ int result_aggregate_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
   if (fplan)
     if (const int rc = filter_check(f, column_names, n_names)) return rc;
   std::vector<AggInsn> insns = aplan.insns;
-  for (const AggInsn& in : insns)  // (the plan was compiled against these columns: an index past them is a caller's mix-up)
-    if (in.kind != AK_COUNT_ROWS && (in.col >= f.nc || in.col2 >= f.nc)) return ORCGPU_UNEXPECTED;
+  if (!agg_plan_in_bounds(insns, aplan.ops, f.nc)) return ORCGPU_UNEXPECTED;
   AggInsn kept{};
   kept.kind = AK_COUNT_ROWS;
   insns.push_back(kept);
@@ -122,7 +151,7 @@ int result_aggregate_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
   if (const int rc = filter_upload(f, ws, host)) return rc;
   if (fplan)
     if (const int rc = filter_run_eval(f, ws)) return rc;
-  if (const int rc = agg_run(f, ws, aw, insns, fplan != nullptr, records.data())) return rc;
+  if (const int rc = agg_run(f, ws, aw, insns, aplan.ops, fplan != nullptr, records.data())) return rc;
   if (records.back().w[0] > f.n_in) {
     set_err(ctx, "aggregate: %llu rows kept of %llu", (unsigned long long)records.back().w[0], (unsigned long long)f.n_in);
     return ORCGPU_UNEXPECTED;
@@ -131,21 +160,21 @@ int result_aggregate_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
 }
 
 // The plan of an aggregate list against a decoded result's columns
-int result_compile_aggs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_agg_spec* specs, uint32_t n_specs, const char* const* column_names,
-                        orcgpu_host::AggPlan& plan) {
+int result_compile_aggs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs,
+                        const char* const* column_names, orcgpu_host::AggPlan& plan) {
   std::vector<FilterColDesc> descs;
   for (const ColumnOut& co : r->cols) descs.push_back(filter_desc_of(co));
   std::vector<orcgpu_host::AggCol> cols;
   agg_describe(r, descs, cols);
-  const int rc = orcgpu_host::agg_compile(specs, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan);
+  const int rc = orcgpu_host::agg_compile(specs, exprs, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan);
   if (rc) set_err(ctx, "%s", plan.err);
   return rc;
 }
 
 // The grouped reduction behind the evaluation and its one wait: `set` gets the result's groups in first-appearance order, with
 // the instructions' records and behind them the group's kept row count
-int group_run(FilterCall& f, const FilterWorkspace& ws, const GroupWorkspace& gw, const orcgpu_host::GroupPlan& gplan, const std::vector<AggInsn>& insns, bool has_filter,
-              const char* const* column_names, orcgpu_host::GroupSet& set) {
+int group_run(FilterCall& f, const FilterWorkspace& ws, const GroupWorkspace& gw, const orcgpu_host::GroupPlan& gplan, const std::vector<AggInsn>& insns,
+              const std::vector<AggExprOp>& ops, bool has_filter, const char* const* column_names, orcgpu_host::GroupSet& set) {
   orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
   GroupKeys keys{};
@@ -181,6 +210,12 @@ int group_run(FilterCall& f, const FilterWorkspace& ws, const GroupWorkspace& gw
   hipLaunchKernelGGL(agg_group_partial_kernel, dim3(gw.blocks, gw.n_insn), dim3(256), 0, st, d_insn, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W, d_keep, d_plane,
                      d_slot_group, d_ctl, d_part);
   HIP_TRY(ctx, hipGetLastError());
+  if (!ops.empty()) {  // the expression instructions' rows of the same records
+    HIP_TRY(ctx, ctx->upload(f.X + gw.o_ops, ops.data(), ops.size() * sizeof(AggExprOp), st));
+    hipLaunchKernelGGL(agg_group_expr_partial_kernel, dim3(gw.blocks, gw.n_insn), dim3(256), 0, st, d_insn, f.at<const AggExprOp>(gw.o_ops), d_cols, d_segs, d_first, n_segs,
+                       f.n_in, f.B, f.W, d_keep, d_plane, d_slot_group, d_ctl, d_part);
+    HIP_TRY(ctx, hipGetLastError());
+  }
   hipLaunchKernelGGL(agg_group_final_kernel, dim3(kGroupMax, gw.n_insn), dim3(256), 0, st, d_insn, d_part, gw.blocks, d_ctl, d_out);
   HIP_TRY(ctx, hipGetLastError());
   // ---- the grouped aggregation's one wait: the group count and the flags, the key records, the value records ----
@@ -229,7 +264,7 @@ int result_aggregate_groups_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const
   if (rows_seen) *rows_seen = f.n_in;
   const uint32_t src_batches = r->selected ? r->full_batches : r->n_batches;
   const FilterWorkspace ws(f.plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), src_batches, f.n_in, f.B);
-  const GroupWorkspace gw(ws.bytes, (uint32_t)aplan.insns.size(), (uint32_t)gplan.keys.size(), f.n_in);
+  const GroupWorkspace gw(ws.bytes, (uint32_t)aplan.insns.size(), (uint32_t)gplan.keys.size(), f.n_in, aplan.ops.size());
   if (!r->filt_tmp.ensure(gw.bytes + kAlign)) {
     set_err(ctx, "hipMalloc(%llu) for the grouped aggregation failed", (unsigned long long)gw.bytes);
     return ORCGPU_HIP_ERROR;
@@ -240,8 +275,7 @@ int result_aggregate_groups_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const
   if (fplan)
     if (const int rc = filter_check(f, column_names, n_names)) return rc;
   std::vector<AggInsn> insns = aplan.insns;
-  for (const AggInsn& in : insns)  // (the plans were compiled against these columns: an index past them is a caller's mix-up)
-    if (in.kind != AK_COUNT_ROWS && (in.col >= f.nc || in.col2 >= f.nc)) return ORCGPU_UNEXPECTED;
+  if (!agg_plan_in_bounds(insns, aplan.ops, f.nc)) return ORCGPU_UNEXPECTED;
   for (const orcgpu_host::GroupKey& k : gplan.keys)
     if (k.col >= f.nc || k.col >= n_names || f.fcols[k.col].kind != k.fkind) return ORCGPU_UNEXPECTED;
   AggInsn kept{};
@@ -251,7 +285,7 @@ int result_aggregate_groups_plan(orcgpu_ctx* ctx, const orcgpu_result* r_, const
   if (const int rc = filter_upload(f, ws, host)) return rc;
   if (fplan)
     if (const int rc = filter_run_eval(f, ws)) return rc;
-  if (const int rc = group_run(f, ws, gw, gplan, insns, fplan != nullptr, column_names, set)) return rc;
+  if (const int rc = group_run(f, ws, gw, gplan, insns, aplan.ops, fplan != nullptr, column_names, set)) return rc;
   uint64_t total = 0;
   for (uint32_t g = 0; g < set.n_groups(); g++) total += set.vals[(size_t)g * set.n_insn + set.n_insn - 1].w[0];
   if (total > f.n_in) {
@@ -279,6 +313,11 @@ int result_compile_group(orcgpu_ctx* ctx, const orcgpu_result* r, const char* co
 extern "C" int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
                                        const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs, uint32_t n_specs,
                                        orcgpu_agg_value* out) {
+  return orcgpu_result_aggregate_exprs(ctx, r, nodes, n_nodes, column_names, n_columns, specs, nullptr, n_specs, out);
+}
+extern "C" int orcgpu_result_aggregate_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                             const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs,
+                                             const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_agg_value* out) {
   if (!ctx || !r || (n_nodes && !nodes) || (n_columns && !column_names) || !out) return ORCGPU_INVALID_ARGUMENT;
   if (r->status) return r->status;
   if (n_columns != r->cols.size()) {
@@ -286,7 +325,7 @@ extern "C" int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, 
     return ORCGPU_INVALID_ARGUMENT;
   }
   orcgpu_host::AggPlan aplan;
-  if (const int rc = result_compile_aggs(ctx, r, specs, n_specs, column_names, aplan)) return rc;
+  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, n_specs, column_names, aplan)) return rc;
   orcgpu_host::FilterPlan fplan;
   if (n_nodes) {
     std::vector<int32_t> kinds(n_columns), params(n_columns, 0);
@@ -310,6 +349,11 @@ extern "C" int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, 
 extern "C" int orcgpu_result_aggregate_groups(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
                                               const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
                                               const orcgpu_agg_spec* specs, uint32_t n_specs, orcgpu_groups** out) {
+  return orcgpu_result_aggregate_groups_exprs(ctx, r, nodes, n_nodes, column_names, n_columns, key_columns, n_keys, specs, nullptr, n_specs, out);
+}
+extern "C" int orcgpu_result_aggregate_groups_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                                    const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                                    const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_groups** out) {
   if (out) *out = nullptr;
   if (!ctx || !r || (n_nodes && !nodes) || (n_columns && !column_names) || !out) return ORCGPU_INVALID_ARGUMENT;
   if (r->status) return r->status;
@@ -320,7 +364,7 @@ extern "C" int orcgpu_result_aggregate_groups(orcgpu_ctx* ctx, const orcgpu_resu
   orcgpu_host::GroupPlan gplan;
   if (const int rc = result_compile_group(ctx, r, key_columns, n_keys, column_names, gplan)) return rc;
   orcgpu_host::AggPlan aplan;
-  if (const int rc = result_compile_aggs(ctx, r, specs, n_specs, column_names, aplan)) return rc;
+  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, n_specs, column_names, aplan)) return rc;
   orcgpu_host::FilterPlan fplan;
   if (n_nodes) {
     std::vector<int32_t> kinds(n_columns), params(n_columns, 0);

@@ -1,0 +1,306 @@
+// orcgpu_agg_expr.inc -- an aggregate's arithmetic expression (include/orcgpu.h: orcgpu_agg_expr) -> the post-order program the
+// kernels interpret per kept row (device/agg_program.h: AggExprOp; device/agg_expr_eval.h), free of HIP
+// (tests/hostcheck/agg_expr_check.cpp compiles this very text under AddressSanitizer + UBSan).  The pre-order nodes are parsed into
+// a tree; the tree is typed (INT / DEC / FLOAT), the Decimal scale rule applied -- the operand of lower scale of a + b is wrapped
+// into a multiplication by a power of ten --, subtrees of literals alone folded with the evaluator's own checked arithmetic, the
+// nodes labelled with the operand slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Every refusal
+// of the expression aggregates is decided here.  Included from orcgpu_agg_plan.inc, between its column description and its compiler.
+#include "device/agg_expr_eval.h"
+
+namespace orcgpu_host {
+
+static_assert(sizeof(AggExprOp) == 24, "agg_program.h: the record the kernels read");
+static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
+
+enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
+
+struct AggExprCompiler {
+  const char* const* names;
+  const AggCol* cols;
+  uint32_t n_columns;
+  const char* op_name;
+  char* err;
+  size_t err_len;
+
+  struct Node {
+    uint32_t op = 0;        // ORCGPU_AGG_EXPR_*, or kScale: this library's own "times 10^k"
+    int a = -1, b = -1;     // children
+    uint32_t col = 0;       // COLUMN
+    int32_t value_type = 0; // LITERAL
+    agg_i128 iv = 0;        // LITERAL of the INT / DEC class; kScale: 10^k
+    double fv = 0.0;        // LITERAL of the FLOAT class
+    int scale = 0;          // DEC
+    uint32_t k = 0;         // kScale
+    uint32_t label = 1;     // operand slots the subtree needs
+  };
+  static constexpr uint32_t kScale = 100;
+  std::vector<Node> t;
+  const orcgpu_agg_expr_node* src = nullptr;
+  uint32_t n_src = 0, at = 0;
+  const char* first_column = "";
+  int cls = XCLASS_INT;
+
+  int fail(int rc, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {
+    snprintf(err, err_len, fmt, a, b, c);
+    return rc;
+  }
+
+  // pre-order -> tree; `node` gets the subtree's root
+  int parse(int& node) {
+    if (at >= n_src) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s ends before an operator has its operands", op_name);
+    const orcgpu_agg_expr_node& s = src[at++];
+    Node n;
+    n.op = s.op;
+    const int me = (int)t.size();
+    t.push_back(n);
+    if (s.op == ORCGPU_AGG_EXPR_COLUMN) {
+      if (!s.column) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a column node of the expression of %s without a name", op_name);
+      uint32_t col = n_columns;
+      for (uint32_t k = 0; k < n_columns && col == n_columns; k++)
+        if (names[k] && strcmp(names[k], s.column) == 0) col = k;
+      if (col == n_columns) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: column '%s' in the expression of %s is not a projected root column", s.column, op_name);
+      t[me].col = col;
+      if (!*first_column) first_column = names[col];
+    } else if (s.op == ORCGPU_AGG_EXPR_LITERAL) {
+      t[me].value_type = s.value_type;
+      if (s.value_type == ORCGPU_PV_INT64) {
+        t[me].iv = s.i;
+      } else if (s.value_type == ORCGPU_PV_FLOAT64) {
+        t[me].fv = s.f;
+      } else if (s.value_type == ORCGPU_PV_DECIMAL128) {
+        i128 v = 0;
+        if (!dec_literal(s.s, s.s_len, s.i, v)) return -1;  // (named below, once the first column is known)
+        t[me].iv = v;
+        t[me].scale = (int)s.i;
+      } else {
+        return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a literal of the expression of %s is not an INT64, FLOAT64 or DECIMAL128 value", op_name);
+      }
+    } else if (s.op == ORCGPU_AGG_EXPR_ADD || s.op == ORCGPU_AGG_EXPR_SUB || s.op == ORCGPU_AGG_EXPR_MUL || s.op == ORCGPU_AGG_EXPR_NEG) {
+      int a = -1, b = -1;
+      if (const int rc = parse(a)) return rc;
+      if (s.op != ORCGPU_AGG_EXPR_NEG)
+        if (const int rc = parse(b)) return rc;
+      t[me].a = a;
+      t[me].b = b;
+    } else {
+      return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an unknown node in the expression of %s", op_name);
+    }
+    node = me;
+    return ORCGPU_OK;
+  }
+
+  // the class of the expression off its leaves, or the refusal
+  int classify() {
+    const char *float_col = nullptr, *exact_col = nullptr;
+    bool f64_lit = false, dec_lit = false, dec_col = false;
+    for (const Node& n : t) {
+      if (n.op == ORCGPU_AGG_EXPR_LITERAL) {
+        f64_lit |= n.value_type == ORCGPU_PV_FLOAT64;
+        dec_lit |= n.value_type == ORCGPU_PV_DECIMAL128;
+      }
+      if (n.op != ORCGPU_AGG_EXPR_COLUMN) continue;
+      const AggCol& c = cols[n.col];
+      const char* name = names[n.col];
+      if (c.d.dict_out) return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is read as a dictionary column: %s on its keys is not supported", name, op_name);
+      const int k = agg_class(c.d.orc_type);
+      if (k == ACLASS_TS && (c.d.ts_unit > 3 || c.d.width != 8))
+        return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is a Timestamp decoded to Decimal128(38, 9): %s is not supported on it", name, op_name);
+      if (k != ACLASS_INT && k != ACLASS_FLOAT && k != ACLASS_DEC) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s does not take column '%s'", op_name, name);
+      const uint32_t want = k == ACLASS_FLOAT ? FKIND_FLOAT : k == ACLASS_DEC ? FKIND_DEC128 : FKIND_INT;
+      if (filter_col_kind(c.d) != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type the expression of %s needs", name, op_name);
+      if (k == ACLASS_FLOAT && !float_col) float_col = name;
+      if (k != ACLASS_FLOAT && !exact_col) exact_col = name;
+      dec_col |= k == ACLASS_DEC;
+    }
+    if (!float_col && !exact_col) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s holds no column", op_name);
+    if (float_col && exact_col)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s mixes the Float / Double column '%s' with the integer or Decimal column '%s'", op_name, float_col, exact_col);
+    if (f64_lit && exact_col)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside the integer or Decimal column '%s'", op_name, exact_col);
+    if (dec_lit && float_col)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s'", op_name, float_col);
+    cls = float_col ? XCLASS_FLOAT : (dec_col || dec_lit) ? XCLASS_DEC : XCLASS_INT;
+    if (cls == XCLASS_FLOAT)
+      for (Node& n : t)
+        if (n.op == ORCGPU_AGG_EXPR_LITERAL && n.value_type == ORCGPU_PV_INT64) {
+          const long long i = (long long)n.iv;
+          const double d = (double)i;
+          if (!(d >= -9223372036854775808.0 && d < 9223372036854775808.0 && (long long)d == i))
+            return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an INT64 literal beside column '%s' in the expression of %s is not exact as a double", float_col, op_name);
+          n.fv = d;
+        }
+    return ORCGPU_OK;
+  }
+
+  bool is_lit(int n) const { return t[n].op == ORCGPU_AGG_EXPR_LITERAL; }
+
+  // x <- x * 10^k: folded into a literal when the product fits, else a node of its own (the rows then report the overflow)
+  int scaled(int x, uint32_t k) {
+    if (!k) return x;
+    const agg_i128 f = agg_pow10(k);
+    agg_i128 r = 0;
+    if (is_lit(x) && agg_mul_checked(t[x].iv, f, &r)) {
+      t[x].iv = r;
+      t[x].scale += (int)k;
+      return x;
+    }
+    Node n;
+    n.op = kScale;
+    n.a = x;
+    n.k = k;
+    n.iv = f;
+    n.scale = t[x].scale + (int)k;
+    n.label = t[x].label;  // (unary: the slots its operand needs)
+    t.push_back(n);
+    return (int)t.size() - 1;
+  }
+
+  // bottom-up: the scales (DEC), the folding of literal-only subtrees, the labels.  Returns the node that stands for `n` now.
+  int type_node(int n, int& out) {
+    out = n;
+    if (t[n].a < 0) return ORCGPU_OK;  // a leaf: label 1, its own scale
+    int a = t[n].a, b = t[n].b;
+    if (const int rc = type_node(a, a)) return rc;
+    if (b >= 0)
+      if (const int rc = type_node(b, b)) return rc;
+    const uint32_t op = t[n].op;
+    if (cls == XCLASS_DEC) {
+      if (op == ORCGPU_AGG_EXPR_MUL) {
+        t[n].scale = t[a].scale + t[b].scale;
+      } else if (op == ORCGPU_AGG_EXPR_NEG) {
+        t[n].scale = t[a].scale;
+      } else {
+        const int s = t[a].scale > t[b].scale ? t[a].scale : t[b].scale;
+        if (s <= 38) {
+          a = scaled(a, (uint32_t)(s - t[a].scale));
+          b = scaled(b, (uint32_t)(s - t[b].scale));
+        }
+        t[n].scale = s;
+      }
+      if (t[n].scale > 38)
+        return fail(ORCGPU_UNSUPPORTED, "aggregate: a node of the expression of %s over column '%s' has a scale of more than 38: it is not supported", op_name, first_column);
+    }
+    t[n].a = a;
+    t[n].b = b;
+    if (is_lit(a) && (b < 0 || is_lit(b))) {  // literals alone: folded when the exact result fits
+      bool ok = true;
+      Node lit;
+      lit.op = ORCGPU_AGG_EXPR_LITERAL;
+      lit.scale = t[n].scale;
+      if (cls == XCLASS_FLOAT) {
+        lit.value_type = ORCGPU_PV_FLOAT64;
+        const double x = t[a].fv, y = b >= 0 ? t[b].fv : 0.0;
+        lit.fv = op == ORCGPU_AGG_EXPR_ADD ? agg_f64_add(x, y) : op == ORCGPU_AGG_EXPR_SUB ? agg_f64_add(x, -y) : op == ORCGPU_AGG_EXPR_MUL ? agg_f64_mul(x, y) : -x;
+      } else {
+        lit.value_type = ORCGPU_PV_INT64;
+        const agg_i128 x = t[a].iv, y = b >= 0 ? t[b].iv : 0;
+        ok = op == ORCGPU_AGG_EXPR_ADD ? agg_add_checked(x, y, &lit.iv) : op == ORCGPU_AGG_EXPR_SUB ? agg_sub_checked(x, y, &lit.iv)
+           : op == ORCGPU_AGG_EXPR_MUL ? agg_mul_checked(x, y, &lit.iv) : agg_neg_checked(x, &lit.iv);
+      }
+      if (ok) {
+        t[n] = lit;
+        return ORCGPU_OK;
+      }
+    }
+    const uint32_t la = t[a].label, lb = b >= 0 ? t[b].label : 0;
+    t[n].label = b < 0 ? la : la == lb ? la + 1 : la > lb ? la : lb;
+    return ORCGPU_OK;
+  }
+
+  void emit(int n, std::vector<AggExprOp>& ops) {
+    const Node& x = t[n];
+    AggExprOp o{};
+    if (x.op == ORCGPU_AGG_EXPR_COLUMN) {
+      const int k = agg_class(cols[x.col].d.orc_type);
+      o.op = k == ACLASS_FLOAT ? AX_PUSH_F64 : k == ACLASS_DEC ? AX_PUSH_DEC : AX_PUSH_INT;
+      o.col = x.col;
+    } else if (x.op == ORCGPU_AGG_EXPR_LITERAL) {
+      o.op = AX_PUSH_LIT;
+      if (cls == XCLASS_FLOAT) {
+        o.lo = agg_bits_of_f64(x.fv);
+      } else {
+        o.lo = (unsigned long long)x.iv;
+        o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
+      }
+    } else if (x.op == kScale) {
+      emit(x.a, ops);
+      o.op = AX_SCALE10;
+      o.col = x.k;
+      o.lo = (unsigned long long)x.iv;
+      o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
+    } else if (x.op == ORCGPU_AGG_EXPR_NEG) {
+      emit(x.a, ops);
+      o.op = AX_NEG;
+    } else {
+      const bool right_first = t[x.b].label > t[x.a].label;
+      emit(right_first ? x.b : x.a, ops);
+      emit(right_first ? x.a : x.b, ops);
+      o.op = x.op == ORCGPU_AGG_EXPR_ADD ? AX_ADD : x.op == ORCGPU_AGG_EXPR_MUL ? AX_MUL : right_first ? AX_RSUB : AX_SUB;
+    }
+    ops.push_back(o);
+  }
+
+  // The program of `e` goes behind `ops`; kind / scale: the AK_EXPR_* kind and the root's scale (DEC)
+  int compile(const orcgpu_agg_expr* e, std::vector<AggExprOp>& ops, uint32_t& kind, int32_t& scale) {
+    if (!e || !e->nodes || !e->n_nodes) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: %s without an expression", op_name);
+    if (e->n_nodes > ORCGPU_AGG_EXPR_MAX_NODES) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s has more than ORCGPU_AGG_EXPR_MAX_NODES (32) nodes", op_name);
+    src = e->nodes;
+    n_src = e->n_nodes;
+    at = 0;
+    t.clear();
+    int root = -1;
+    bool bad_decimal = false;
+    {
+      const int rc = parse(root);
+      if (rc == -1) bad_decimal = true;
+      else if (rc) return rc;
+    }
+    if (bad_decimal) {  // (the column to name may stand behind the literal)
+      for (uint32_t k = 0; k < n_src && !*first_column; k++)
+        if (src[k].op == ORCGPU_AGG_EXPR_COLUMN && src[k].column) first_column = src[k].column;
+      return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a DECIMAL128 literal of the expression of %s over column '%s' is not 16 bytes of |value| < 10^38 at a scale of 0 .. 38", op_name, first_column);
+    }
+    if (at != n_src) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s has nodes left over behind its tree", op_name);
+    if (const int rc = classify()) return rc;
+    if (cls == XCLASS_DEC)
+      for (Node& n : t)
+        if (n.op == ORCGPU_AGG_EXPR_COLUMN) n.scale = agg_class(cols[n.col].d.orc_type) == ACLASS_DEC ? (int)cols[n.col].scale : 0;
+    if (const int rc = type_node(root, root)) return rc;
+    if (t[root].label > kAggExprSlots)
+      return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
+    // the gates: every distinct column, in order of appearance
+    std::vector<uint32_t> seen;
+    for (uint32_t k = 0; k < n_src; k++) {
+      if (src[k].op != ORCGPU_AGG_EXPR_COLUMN) continue;
+      uint32_t col = 0;
+      while (!names[col] || strcmp(names[col], src[k].column) != 0) col++;  // (parse found it)
+      bool dup = false;
+      for (uint32_t s : seen) dup |= s == col;
+      if (dup) continue;
+      seen.push_back(col);
+      AggExprOp g{};
+      g.op = AX_GATE;
+      g.col = col;
+      ops.push_back(g);
+    }
+    const size_t first_op = ops.size();
+    emit(root, ops);
+    // (the labels promise it; the program itself is what the kernels run, so it is counted once more before it is accepted)
+    uint32_t depth = 0, most = 0;
+    for (size_t k = first_op; k < ops.size(); k++) {
+      const uint32_t o = ops[k].op;
+      if (o >= AX_PUSH_INT && o <= AX_PUSH_LIT) depth++;
+      else if (o >= AX_ADD && o <= AX_MUL) depth--;
+      most = depth > most ? depth : most;
+    }
+    if (most > kAggExprSlots || depth != 1) {
+      ops.resize(first_op);
+      return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
+    }
+    kind = cls == XCLASS_FLOAT ? AK_EXPR_F64 : cls == XCLASS_DEC ? AK_EXPR_DEC : AK_EXPR_INT;
+    scale = cls == XCLASS_DEC ? t[root].scale : 0;
+    return ORCGPU_OK;
+  }
+};
+
+}  // namespace orcgpu_host

@@ -23,6 +23,7 @@ struct AggCol {
 
 struct AggPlan {
   std::vector<AggInsn> insns;
+  std::vector<AggExprOp> ops;  // the programs of the AK_EXPR_* instructions, one behind the other (insn.col: first op, insn.col2: ops)
   char err[256] = {0};
 };
 
@@ -39,9 +40,14 @@ inline int agg_class(int32_t t) {
   }
 }
 inline const char* agg_op_name(uint32_t op) {
-  static const char* const n[] = {"COUNT_ROWS", "COUNT", "SUM", "MIN", "MAX", "SUM_PRODUCT"};
-  return op <= ORCGPU_AGG_OP_SUM_PRODUCT ? n[op] : "?";
+  static const char* const n[] = {"COUNT_ROWS", "COUNT", "SUM", "MIN", "MAX", "SUM_PRODUCT", "SUM_EXPR", "AVG", "AVG_EXPR"};
+  return op <= ORCGPU_AGG_OP_AVG_EXPR ? n[op] : "?";
 }
+inline bool agg_op_is_avg(uint32_t op) { return op == ORCGPU_AGG_OP_AVG || op == ORCGPU_AGG_OP_AVG_EXPR; }
+
+}  // namespace orcgpu_host
+#include "orcgpu_agg_expr.inc"
+namespace orcgpu_host {
 
 struct AggCompiler {
   const char* const* names;
@@ -70,7 +76,7 @@ struct AggCompiler {
     cls = agg_class(c.d.orc_type);
     if (cls == ACLASS_TS && (c.d.ts_unit > 3 || c.d.width != 8))
       return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is a Timestamp decoded to Decimal128(38, 9): %s is not supported on it", name, agg_op_name(op));
-    const bool sum = op == ORCGPU_AGG_OP_SUM || op == ORCGPU_AGG_OP_SUM_PRODUCT;
+    const bool sum = op == ORCGPU_AGG_OP_SUM || op == ORCGPU_AGG_OP_SUM_PRODUCT || op == ORCGPU_AGG_OP_AVG;
     if (cls == ACLASS_OTHER || (sum && cls != ACLASS_INT && cls != ACLASS_FLOAT && cls != ACLASS_DEC))
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s does not take column '%s'", agg_op_name(op), name);
     // ... and what the decode made of it must be what the kernel loads
@@ -78,7 +84,8 @@ struct AggCompiler {
     if (filter_col_kind(c.d) != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type %s needs", name, agg_op_name(op));
     return ORCGPU_OK;
   }
-  int compile(const orcgpu_agg_spec* specs, uint32_t n_specs) {
+  // exprs: parallel to specs, or null when no spec has an expression
+  int compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs) {
     if (!specs || !n_specs) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: no aggregates given");
     if (n_specs > ORCGPU_AGG_MAX) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: more than ORCGPU_AGG_MAX (64) aggregates");
     for (uint32_t k = 0; k < n_columns; k++)
@@ -88,7 +95,16 @@ struct AggCompiler {
       const orcgpu_agg_spec& sp = specs[s];
       AggInsn in{};
       in.op = sp.op;
-      if (sp.op > ORCGPU_AGG_OP_SUM_PRODUCT) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: unknown op in the list%s", "");
+      if (sp.op > ORCGPU_AGG_OP_AVG_EXPR) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: unknown op in the list%s", "");
+      if (sp.op == ORCGPU_AGG_OP_SUM_EXPR || sp.op == ORCGPU_AGG_OP_AVG_EXPR) {
+        AggExprCompiler x{names, cols, n_columns, agg_op_name(sp.op), out.err, sizeof(out.err)};
+        const size_t first = out.ops.size();
+        if (const int rc = x.compile(exprs ? &exprs[s] : nullptr, out.ops, in.kind, in.scale)) return rc;
+        in.col = (uint32_t)first;
+        in.col2 = (uint32_t)(out.ops.size() - first);
+        out.insns.push_back(in);
+        continue;
+      }
       if (sp.op == ORCGPU_AGG_OP_COUNT_ROWS) {
         in.kind = AK_COUNT_ROWS;
         out.insns.push_back(in);
@@ -104,7 +120,7 @@ struct AggCompiler {
       }
       int cls = 0;
       if (const int rc = value_class(sp.op, in.col, cls)) return rc;
-      if (sp.op == ORCGPU_AGG_OP_SUM) {
+      if (sp.op == ORCGPU_AGG_OP_SUM || sp.op == ORCGPU_AGG_OP_AVG) {
         in.kind = cls == ACLASS_INT ? AK_SUM_INT : cls == ACLASS_FLOAT ? AK_SUM_F64 : AK_SUM_DEC;
         in.scale = cls == ACLASS_DEC ? (int32_t)cols[in.col].scale : 0;
       } else if (sp.op == ORCGPU_AGG_OP_SUM_PRODUCT) {
@@ -129,11 +145,16 @@ struct AggCompiler {
   }
 };
 
-inline int agg_compile(const orcgpu_agg_spec* specs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out) {
+inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns,
+                       AggPlan& out) {
   out.insns.clear();
+  out.ops.clear();
   out.err[0] = 0;
   AggCompiler c{names, cols, n_columns, out};
-  return c.compile(specs, n_specs);
+  return c.compile(specs, exprs, n_specs);
+}
+inline int agg_compile(const orcgpu_agg_spec* specs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out) {
+  return agg_compile(specs, nullptr, n_specs, names, cols, n_columns, out);
 }
 
 // ---- the arithmetic: signed 192-bit integers as three little-endian words ----
@@ -166,9 +187,9 @@ inline bool agg_fits_decimal(const unsigned long long* w) {
 // into <- into (+) from: what agg_fold (device/agg_kernels.hip) does, on the host -- the reader's stripes in stripe order
 inline void agg_merge(const AggInsn& in, AggPartial& into, const AggPartial& from) {
   into.flags |= from.flags;
-  if (in.kind == AK_SUM_F64 || in.kind == AK_SP_F64) {
+  if (agg_is_float_sum(in.kind)) {
     into.f += from.f;
-  } else if (in.kind < AK_MINMAX_INT) {
+  } else if (agg_is_wide_sum(in.kind)) {
     agg_add192(into.w, from.w);
   } else if (from.count) {
     bool take = !into.count;
@@ -190,6 +211,29 @@ inline void agg_merge(const AggInsn& in, AggPartial& into, const AggPartial& fro
 inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value* v) {
   memset(v, 0, sizeof(*v));
   const bool sticky = (p.flags & AGG_OVERFLOW) != 0;
+  if (agg_op_is_avg(in.op)) {  // the exact sum over the count of values, finished here
+    v->is_null = p.count == 0;
+    if (agg_is_float_sum(in.kind)) {
+      v->kind = ORCGPU_AGG_KIND_F64;
+      v->f = p.count ? p.f / (double)p.count : 0.0;
+    } else if (in.kind == AK_SUM_DEC || in.kind == AK_EXPR_DEC) {
+      v->kind = ORCGPU_AGG_KIND_DEC128;
+      v->scale_or_unit = in.scale + 4 < 38 ? in.scale + 4 : 38;
+      v->overflow = !agg_fits_decimal(p.w) || sticky;
+      if (p.count && !v->overflow) {
+        uint32_t scale = 0;
+        unsigned long long q[3];
+        agg_avg_decimal(p.w, p.count, (uint32_t)in.scale, &scale, q);
+        v->overflow = !agg_fits_decimal(q);
+        for (int k = 0; k < 3; k++) v->w[k] = q[k];
+      }
+    } else {  // AK_SUM_INT, AK_EXPR_INT
+      v->kind = ORCGPU_AGG_KIND_F64;
+      v->overflow = !agg_fits_i128(p.w) || sticky;
+      if (p.count && !v->overflow) v->f = agg_avg_int(agg_i128_of(p.w[0], p.w[1]), p.count);
+    }
+    return;
+  }
   switch (in.kind) {
     case AK_COUNT_ROWS:
     case AK_COUNT:
@@ -198,12 +242,14 @@ inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value*
       return;
     case AK_SUM_INT:
     case AK_SP_INT:
+    case AK_EXPR_INT:
       v->kind = ORCGPU_AGG_KIND_I128;
       v->is_null = p.count == 0;
       v->overflow = !agg_fits_i128(p.w) || sticky;
       break;
     case AK_SUM_DEC:
     case AK_SP_DEC:
+    case AK_EXPR_DEC:
       v->kind = ORCGPU_AGG_KIND_DEC128;
       v->scale_or_unit = in.scale;
       v->is_null = p.count == 0;
@@ -211,6 +257,7 @@ inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value*
       break;
     case AK_SUM_F64:
     case AK_SP_F64:
+    case AK_EXPR_F64:
       v->kind = ORCGPU_AGG_KIND_F64;
       v->is_null = p.count == 0;
       v->f = p.f;

@@ -43,6 +43,13 @@ struct orcgpu_reader {
     uint32_t op = 0;
     bool has_column = false, has_column2 = false;
     std::string column, column2;
+    // the spec's expression (orcgpu_reader_set_aggregate_exprs), nodes in pre-order with their names and literal bytes copied
+    struct ExprNode {
+      orcgpu_agg_expr_node n{};
+      bool has_column = false, has_s = false;
+      std::string column, s;
+    };
+    std::vector<ExprNode> expr;
   };
   std::vector<AggSpec> agg_specs;
   // GROUP BY (orcgpu_reader_set_group_by): the key columns as given
@@ -320,13 +327,28 @@ int reader_compile_filter(orcgpu_reader* rd) {
   return ORCGPU_OK;
 }
 
-std::vector<orcgpu_agg_spec> reader_view_aggs(const orcgpu_reader* rd) {
-  std::vector<orcgpu_agg_spec> out(rd->agg_specs.size());
-  for (size_t k = 0; k < out.size(); k++) {
+// The reader's copies as the C arrays the plan compiler takes: specs and, parallel to them, exprs (whose nodes live in `nodes`)
+struct ReaderAggView {
+  std::vector<orcgpu_agg_spec> specs;
+  std::vector<orcgpu_agg_expr> exprs;
+  std::vector<std::vector<orcgpu_agg_expr_node>> nodes;
+};
+void reader_view_aggs(const orcgpu_reader* rd, ReaderAggView& v) {
+  const size_t n = rd->agg_specs.size();
+  v.specs.resize(n);
+  v.exprs.assign(n, orcgpu_agg_expr{nullptr, 0});
+  v.nodes.assign(n, {});
+  for (size_t k = 0; k < n; k++) {
     const orcgpu_reader::AggSpec& s = rd->agg_specs[k];
-    out[k] = {s.op, s.has_column ? s.column.c_str() : nullptr, s.has_column2 ? s.column2.c_str() : nullptr};
+    v.specs[k] = {s.op, s.has_column ? s.column.c_str() : nullptr, s.has_column2 ? s.column2.c_str() : nullptr};
+    for (const auto& e : s.expr) {
+      orcgpu_agg_expr_node x = e.n;
+      x.column = e.has_column ? e.column.c_str() : nullptr;
+      x.s = e.has_s ? e.s.data() : nullptr;
+      v.nodes[k].push_back(x);
+    }
+    if (!v.nodes[k].empty()) v.exprs[k] = {v.nodes[k].data(), (uint32_t)v.nodes[k].size()};
   }
-  return out;
 }
 
 // The aggregate list against the projected root columns as the file's metadata and the builder describe them -> its instructions,
@@ -357,8 +379,9 @@ int reader_compile_aggs(orcgpu_reader* rd) {
   std::vector<const char*> names;
   std::vector<AggCol> cols;
   reader_describe_roots(rd, names, cols);
-  const std::vector<orcgpu_agg_spec> specs = reader_view_aggs(rd);
-  const int rc = agg_compile(specs.data(), (uint32_t)specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
+  ReaderAggView v;
+  reader_view_aggs(rd, v);
+  const int rc = agg_compile(v.specs.data(), v.exprs.data(), (uint32_t)v.specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
   if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
   return rc;
 }
@@ -386,12 +409,16 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
     set_err(rd->ctx, "aggregate: the result holds %zu columns for %zu projected root columns", res->cols.size(), names.size());
     return ORCGPU_UNSUPPORTED;
   }
-  const std::vector<orcgpu_agg_spec> specs = reader_view_aggs(rd);
+  ReaderAggView v;
+  reader_view_aggs(rd, v);
   AggPlan plan;
-  if (const int rc = result_compile_aggs(rd->ctx, res, specs.data(), (uint32_t)specs.size(), names.data(), plan)) return rc;
+  if (const int rc = result_compile_aggs(rd->ctx, res, v.specs.data(), v.exprs.data(), (uint32_t)v.specs.size(), names.data(), plan)) return rc;
   for (size_t k = 0; k < plan.insns.size(); k++)
     if (plan.insns[k].kind != rd->agg_plan.insns[k].kind || plan.insns[k].scale != rd->agg_plan.insns[k].scale) {
-      set_err(rd->ctx, "aggregate: column '%s' is not decoded to the type its aggregate was planned for", names[plan.insns[k].col]);
+      if (agg_is_expr(plan.insns[k].kind) || agg_is_expr(rd->agg_plan.insns[k].kind))  // (col is no column index then)
+        set_err(rd->ctx, "aggregate: the columns of the expression of aggregate %zu are not decoded to the types it was planned for", k);
+      else
+        set_err(rd->ctx, "aggregate: column '%s' is not decoded to the type its aggregate was planned for", names[plan.insns[k].col]);
       return ORCGPU_MISMATCHED_SCHEMA;
     }
   if (rd->has_group) {  // the grouped reduction in the same place: the stripe's groups stay with the result

@@ -320,7 +320,13 @@ int orcgpu_reader_next_batch_device(orcgpu_reader* rd, struct ArrowDeviceArray* 
   return reader_next(rd, nullptr, out_array, out_schema);
 }
 int orcgpu_reader_set_aggregates(orcgpu_reader* rd, const orcgpu_agg_spec* specs, uint32_t n_specs) {
+  return orcgpu_reader_set_aggregate_exprs(rd, specs, nullptr, n_specs);
+}
+int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* rd, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs) {
   if (!rd || rd->built || !specs || !n_specs || n_specs > ORCGPU_AGG_MAX) return ORCGPU_INVALID_ARGUMENT;
+  if (exprs)
+    for (uint32_t k = 0; k < n_specs; k++)
+      if (exprs[k].n_nodes && !exprs[k].nodes) return ORCGPU_INVALID_ARGUMENT;
   rd->agg_specs.assign(n_specs, {});
   for (uint32_t k = 0; k < n_specs; k++) {
     orcgpu_reader::AggSpec& s = rd->agg_specs[k];
@@ -329,6 +335,19 @@ int orcgpu_reader_set_aggregates(orcgpu_reader* rd, const orcgpu_agg_spec* specs
     s.has_column2 = specs[k].column2 != nullptr;
     if (s.has_column) s.column = specs[k].column;
     if (s.has_column2) s.column2 = specs[k].column2;
+    // (one node past the limit is kept, so that the plan compiler refuses the expression with its message; what a literal's bytes
+    // mean is the compiler's to say too: 16 for a Decimal)
+    for (uint32_t x = 0; exprs && x < exprs[k].n_nodes && x <= ORCGPU_AGG_EXPR_MAX_NODES; x++) {
+      const orcgpu_agg_expr_node& n = exprs[k].nodes[x];
+      orcgpu_reader::AggSpec::ExprNode e;
+      e.n = n;
+      e.has_column = n.column != nullptr;
+      if (e.has_column) e.column = n.column;
+      e.has_s = n.s != nullptr && n.s_len <= 64;
+      if (e.has_s) e.s.assign(n.s, n.s_len);
+      else e.n.s_len = 0;  // (no bytes are kept: no length either)
+      s.expr.push_back(std::move(e));
+    }
   }
   rd->has_aggs = true;
   return ORCGPU_OK;
