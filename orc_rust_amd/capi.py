@@ -460,43 +460,41 @@ class Context:
         self._check(self.L.orcgpu_result_filter(self.h, result.h, nodes, len(nodes), names, len(column_names), C.byref(kept)))
         return kept.value
 
+    @staticmethod
+    def _aggregate_args(specs, column_names, predicate):
+        """What both result_aggregate* calls marshal alike: (the predicate's and the names' arguments, the specs' -- with the
+        expressions or None in the middle --, what has to stay alive over the call)"""
+        from . import aggregate as A
+        arr, keep = A.spec_array(specs)
+        exprs, keep_e = A.expr_array(specs)
+        nodes, keep_p = predicate.flatten() if predicate is not None else (None, None)
+        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
+        return (nodes, len(nodes) if nodes is not None else 0, names, len(column_names)), (arr, exprs, len(arr)), (keep, keep_e, keep_p)
+
     def result_aggregate(self, result, specs, column_names, predicate=None, raw=False):
         """orcgpu_result_aggregate: the aggregates `specs` (a list of orc_rust_amd.aggregate.Agg) over the rows of a decoded,
         selected or filtered Result that `predicate` keeps (None: all of them); column_names[i] names the result's column i.  The
         result is left as it was.  Returns the Python values (aggregate.value_of); raw=True: the orcgpu_agg_value records."""
         from . import aggregate as A
-        arr, keep = A.spec_array(specs)
-        exprs, keep_e = A.expr_array(specs)
-        nodes, n_nodes = None, 0
-        if predicate is not None:
-            nodes, keep_p = predicate.flatten()
-            n_nodes = len(nodes)
-        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
-        out = (A.AggValue * len(arr))()
+        rows, (arr, exprs, n), keep = self._aggregate_args(specs, column_names, predicate)
+        out = (A.AggValue * n)()
         if exprs is None:
-            self._check(self.L.orcgpu_result_aggregate(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, len(arr), out))
+            self._check(self.L.orcgpu_result_aggregate(self.h, result.h, *rows, arr, n, out))
         else:
-            self._check(self.L.orcgpu_result_aggregate_exprs(self.h, result.h, nodes, n_nodes, names, len(column_names), arr, exprs, len(arr), out))
+            self._check(self.L.orcgpu_result_aggregate_exprs(self.h, result.h, *rows, arr, exprs, n, out))
         return list(out) if raw else A.values_of(out, specs)
 
     def result_aggregate_groups(self, result, specs, group_by, column_names, predicate=None, raw=False):
         """orcgpu_result_aggregate_groups: result_aggregate per group of the key columns `group_by` (1 .. 4 column names).  Returns
         [(keys tuple, values list)] in first-appearance order (aggregate.key_of / value_of); raw=True: the values as records."""
         from . import aggregate as A
-        arr, keep = A.spec_array(specs)
+        rows, (arr, exprs, n), keep = self._aggregate_args(specs, column_names, predicate)
         keys = A.key_array(group_by)
-        nodes, n_nodes = None, 0
-        if predicate is not None:
-            nodes, keep_p = predicate.flatten()
-            n_nodes = len(nodes)
-        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
         out = C.c_void_p()
-        exprs, keep_e = A.expr_array(specs)
         if exprs is None:
-            self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, len(arr), C.byref(out)))
+            self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, *rows, keys, len(keys), arr, n, C.byref(out)))
         else:
-            self._check(self.L.orcgpu_result_aggregate_groups_exprs(self.h, result.h, nodes, n_nodes, names, len(column_names), keys, len(keys), arr, exprs, len(arr),
-                                                                    C.byref(out)))
+            self._check(self.L.orcgpu_result_aggregate_groups_exprs(self.h, result.h, *rows, keys, len(keys), arr, exprs, n, C.byref(out)))
         return A.groups_of(self.L, out, len(keys), A.check_specs(specs), raw=raw)
 
     def timing(self):

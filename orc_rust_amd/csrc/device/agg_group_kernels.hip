@@ -98,19 +98,20 @@ __device__ __forceinline__ bool group_rows_equal(const GroupKeys& keys, const Fi
 // table is masked to kGroupSlots; a claimer read from a slot is an input row some thread put there, so below n_in.
 // Resource usage (gfx950): 62 VGPRs, 105 SGPRs, no scratch, no spill, no LDS; occupancy 7 waves / SIMD.
 extern "C" __global__ void __launch_bounds__(256)
-group_assign_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B,
-                    uint32_t W, const unsigned long long* keep, GroupSlot* table, GroupControl* ctl, uint32_t* plane) {
+group_assign_kernel(GroupKeys keys, KeptRows rows, GroupSlot* table, GroupControl* ctl, uint32_t* plane) {
   const uint32_t lane = threadIdx.x & 63;
+  const FilterCol* const cols = rows.cols;
+  const uint64_t n_in = rows.n_in;
+  const uint32_t B = rows.B, W = rows.W;
   const FilterWords ws = filter_words(n_in);
   for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
-    const uint64_t left = n_in - w * 64;
-    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    const unsigned long long m = agg_keep_word(rows, w);
     if (!m) continue;
     const uint64_t j = w * 64 + lane;
     const bool kept = ((m >> lane) & 1) && j < n_in;
     uint32_t slot = kGroupNoSlot;
     if (kept) {
-      const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, j);
+      const FilterRow r = filter_row(rows, j);
       const uint32_t h = group_row_hash(keys, cols, r, B, W);
       for (uint32_t step = 0; step < kGroupSlots; step++) {
         const uint32_t s = (h + step) & (kGroupSlots - 1);
@@ -125,7 +126,7 @@ group_assign_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs,
           }
         }
         const uint64_t rep = cur - 1;
-        if (rep == j || (rep < n_in && group_rows_equal(keys, cols, r, filter_row(segs, seg_first, n_segs, n_in, B, rep), B, W))) {
+        if (rep == j || (rep < n_in && group_rows_equal(keys, cols, r, filter_row(rows, rep), B, W))) {
           slot = s;
           break;
         }
@@ -148,8 +149,7 @@ group_assign_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs,
 // <<<1, kGroupSlots>>>: thread s is slot s.  slot_group[s] = the slot's dense group number (kGroupNoSlot: free, or past kGroupMax);
 // key_recs: [group][key].  Nothing is numbered for a table that holds more than kGroupMax groups.
 extern "C" __global__ void __launch_bounds__(1024)
-group_number_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B,
-                    uint32_t W, const GroupSlot* table, GroupControl* ctl, uint32_t* slot_group, GroupKeyRecord* key_recs) {
+group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, GroupControl* ctl, uint32_t* slot_group, GroupKeyRecord* key_recs) {
   __shared__ unsigned long long first_s[kGroupSlots];
   __shared__ uint32_t n_s;
   const uint32_t s = threadIdx.x;
@@ -170,12 +170,13 @@ group_number_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs,
     ctl->n_groups = n_groups;
     if (n_groups > kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
   }
-  const bool mine = used && fits && rank < kGroupMax && first < n_in;
+  const bool mine = used && fits && rank < kGroupMax && first < rows.n_in;
   slot_group[s] = mine ? rank : kGroupNoSlot;
   if (!mine) return;
-  const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, first);
+  const uint32_t B = rows.B, W = rows.W;
+  const FilterRow r = filter_row(rows, first);
   for (uint32_t k = 0; k < keys.n; k++) {
-    const FilterCol c = cols[keys.col[k]];
+    const FilterCol c = rows.cols[keys.col[k]];
     GroupKeyRecord* out = key_recs + (uint64_t)rank * keys.n + k;
     out->is_null = 0;
     out->len = 0;
@@ -214,10 +215,11 @@ group_number_kernel(GroupKeys keys, const FilterCol* cols, const SelBatch* segs,
 // grid.y at once; EXPR = true is agg_group_expr_partial_kernel, the other way round, launched only when the list holds such an
 // instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.)
 template <bool EXPR>
-__device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs,
-                                                       const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W,
-                                                       const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
-                                                       AggPartial* partials, AggAcc (*acc_s)[kGroupMax]) {
+__device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* plane,
+                                                       const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials, AggAcc (*acc_s)[kGroupMax]) {
+  const FilterCol* const cols = rows.cols;
+  const uint64_t n_in = rows.n_in;
+  const uint32_t W = rows.W;
   if (ctl->flags & GROUP_TOO_MANY) return;  // (uniform: the whole grid leaves)
   const uint32_t n_groups = ctl->n_groups < kGroupMax ? ctl->n_groups : kGroupMax;
   const AggInsn in = insns[blockIdx.y];
@@ -232,8 +234,7 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   const FilterWords ws = filter_words(n_in);
   for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
-    const uint64_t left = n_in - w * 64;
-    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    const unsigned long long m = agg_keep_word(rows, w);
     if (!m) continue;
     const uint64_t j = w * 64 + lane;
     uint32_t g = kGroupNoSlot;
@@ -245,9 +246,9 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
     }
     const bool kept = g != kGroupNoSlot;
     if (kept) {
-      if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(segs, seg_first, n_segs, n_in, B, j), W, v);
+      if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
       else if (kind == AK_COUNT_ROWS) v.w0 = 1;
-      else agg_row(kind, is_max, in, c, c2, filter_row(segs, seg_first, n_segs, n_in, B, j), W, v);
+      else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, v);
     }
     // the distinct groups of the word, and a lane's peers: the lanes that hold its group
     unsigned long long todo = __ballot(kept), peers = 0;
@@ -303,18 +304,15 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
   }
 }
 extern "C" __global__ void __launch_bounds__(256)
-agg_group_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
-                         uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
-                         AggPartial* partials) {
+agg_group_partial_kernel(const AggInsn* insns, KeptRows rows, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials) {
   __shared__ AggAcc acc_s[4][kGroupMax];
-  agg_group_partial_body<false>(insns, nullptr, cols, segs, seg_first, n_segs, n_in, B, W, keep, plane, slot_group, ctl, partials, acc_s);
+  agg_group_partial_body<false>(insns, nullptr, rows, plane, slot_group, ctl, partials, acc_s);
 }
 extern "C" __global__ void __launch_bounds__(256)
-agg_group_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first,
-                              uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, const unsigned long long* keep, const uint32_t* plane,
-                              const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials) {
+agg_group_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                              AggPartial* partials) {
   __shared__ AggAcc acc_s[4][kGroupMax];
-  agg_group_partial_body<true>(insns, ops, cols, segs, seg_first, n_segs, n_in, B, W, keep, plane, slot_group, ctl, partials, acc_s);
+  agg_group_partial_body<true>(insns, ops, rows, plane, slot_group, ctl, partials, acc_s);
 }
 
 // grid (kGroupMax, instructions): block (g, k) folds the n_blocks records of group g under instruction k -> out[k][g]; the blocks
@@ -325,14 +323,6 @@ agg_group_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_
   if ((ctl->flags & GROUP_TOO_MANY) || blockIdx.x >= ctl->n_groups) return;
   const AggInsn in = insns[blockIdx.y];
   const uint32_t kind = in.kind < AK_ALL_N ? in.kind : AK_COUNT_ROWS;
-  const bool is_max = in.is_max != 0;
-  const AggPartial* p = partials + (uint64_t)blockIdx.y * n_blocks * kGroupMax + blockIdx.x;
-  AggAcc a = {0, 0, 0, 0.0, 0, 0};
-  for (uint32_t k = threadIdx.x; k < n_blocks; k += 256) {
-    const AggPartial& q = p[(uint64_t)k * kGroupMax];
-    const AggAcc b = {q.w[0], q.w[1], q.w[2], q.f, q.count, q.flags};
-    agg_fold(kind, is_max, a, b);
-  }
-  agg_block_fold(kind, is_max, a, fold_s);
+  const AggAcc a = agg_fold_records(kind, in.is_max != 0, partials + (uint64_t)blockIdx.y * n_blocks * kGroupMax + blockIdx.x, kGroupMax, n_blocks, fold_s);
   if (threadIdx.x == 0) agg_store(out + (uint64_t)blockIdx.y * kGroupMax + blockIdx.x, a);
 }

@@ -14,6 +14,7 @@
 //                        the same records, the same folds; a lane runs the instruction's program (agg_expr_eval.h) on its row.
 //                        A kernel of its own, launched only when the list holds such an instruction, so that the interpreter's
 //                        registers are not the plain kinds'; each of the two kernels leaves the other's rows of grid.y at once.
+//                        The two are one body, agg_partial_body<EXPR>; the rows they walk arrive as one argument (KeptRows).
 //
 // Integer and Decimal sums travel as three 64-bit words with explicit carries -- wide enough for every partial sum, so the
 // order of summation cannot show.  Float sums take whatever the fixed shape gives: the grid is a function of the input row
@@ -226,59 +227,62 @@ __device__ __forceinline__ void agg_expr_row(uint32_t kind, const AggExprOp* pro
 }
 #pragma clang fp contract(fast)  // (what the rest of the library is built with)
 
-// keep: the mask filter_eval_kernel left, one word per 64 input rows (null: no filter, every input row is kept).
+// Word w of the keep mask (w below the word count): without a filter every input row is kept, the last word up to n_in
+__device__ __forceinline__ unsigned long long agg_keep_word(const KeptRows& rows, uint64_t w) {
+  const uint64_t left = rows.n_in - w * 64;  // (at least 1)
+  return rows.keep ? rows.keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+}
+
 // partials: [instruction][block].  A lane whose row is not kept loads nothing; a kept row is an input row below n_in, and the
 // row-access layer turns it into a row of the stripe: every load lies where the decode wrote.
-extern "C" __global__ void __launch_bounds__(256)
-agg_partial_kernel(const AggInsn* insns, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in,
-                   uint32_t B, uint32_t W, const unsigned long long* keep, AggPartial* partials) {
-  __shared__ AggAcc fold_s[4];
+// (The body of two kernels: EXPR = false is agg_partial_kernel, which takes the plain kinds and leaves the AK_EXPR_* rows of grid.y
+// at once -- their col / col2 are no column indexes; EXPR = true is agg_expr_partial_kernel, the other way round.  ops: the op
+// table the instructions' programs lie in, EXPR only.)
+template <bool EXPR>
+__device__ __forceinline__ void agg_partial_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, AggPartial* partials, AggAcc* fold_s) {
   const AggInsn in = insns[blockIdx.y];
-  if (agg_is_expr(in.kind)) return;  // (agg_expr_partial_kernel's: col / col2 are no column indexes)
-  const uint32_t kind = in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
-  const bool is_max = in.is_max != 0;
-  const FilterCol c = cols[in.col], c2 = cols[in.col2];
+  if (agg_is_expr(in.kind) != EXPR) return;  // (uniform over the block)
+  const uint32_t kind = EXPR ? in.kind : in.kind < AK_N ? in.kind : AK_COUNT_ROWS;
+  const bool is_max = !EXPR && in.is_max != 0;
+  const FilterCol c = rows.cols[EXPR ? 0 : in.col], c2 = rows.cols[EXPR ? 0 : in.col2];  // (EXPR: unused)
   const uint32_t lane = threadIdx.x & 63;
-  const FilterWords ws = filter_words(n_in);
+  const FilterWords ws = filter_words(rows.n_in);
   AggAcc a = {0, 0, 0, 0.0, 0, 0};
   for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
-    const uint64_t left = n_in - w * 64;  // (w < ws.n: at least 1)
-    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+    const unsigned long long m = agg_keep_word(rows, w);
     if (!m) continue;
-    if (kind == AK_COUNT_ROWS) {  // (the word's popcount, once: lane 0's share)
+    if (!EXPR && kind == AK_COUNT_ROWS) {  // (the word's popcount, once: lane 0's share)
       if (lane == 0) a.w0 += (unsigned long long)__builtin_popcountll(m);
       continue;
     }
     if (!((m >> lane) & 1)) continue;
-    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
-    agg_row(kind, is_max, in, c, c2, r, W, a);
+    const FilterRow r = filter_row(rows, w * 64 + lane);
+    if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, rows.cols, r, rows.W, a);
+    else agg_row(kind, is_max, in, c, c2, r, rows.W, a);
   }
   agg_block_fold(kind, is_max, a, fold_s);
   if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
 }
-
-// agg_partial_kernel for the AK_EXPR_* instructions of the list (the others' blocks leave at once): ops is the op table the
-// instructions' programs lie in.  Same grid, same records [instruction][block].
-extern "C" __global__ void __launch_bounds__(256)
-agg_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, const FilterCol* cols, const SelBatch* segs, const unsigned long long* seg_first, uint32_t n_segs,
-                        uint64_t n_in, uint32_t B, uint32_t W, const unsigned long long* keep, AggPartial* partials) {
+extern "C" __global__ void __launch_bounds__(256) agg_partial_kernel(const AggInsn* insns, KeptRows rows, AggPartial* partials) {
   __shared__ AggAcc fold_s[4];
-  const AggInsn in = insns[blockIdx.y];
-  if (!agg_is_expr(in.kind)) return;
-  const uint32_t kind = in.kind;
-  const AggExprOp* prog = ops + in.col;
-  const uint32_t lane = threadIdx.x & 63;
-  const FilterWords ws = filter_words(n_in);
+  agg_partial_body<false>(insns, nullptr, rows, partials, fold_s);
+}
+extern "C" __global__ void __launch_bounds__(256) agg_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, AggPartial* partials) {
+  __shared__ AggAcc fold_s[4];
+  agg_partial_body<true>(insns, ops, rows, partials, fold_s);
+}
+
+// What a final kernel's block makes of n_blocks records that lie `stride` records apart: thread t folds records t, t + 256, ... in
+// index order, then the block's tree -- that order is the contract.  Thread 0 holds the result.
+__device__ __forceinline__ AggAcc agg_fold_records(uint32_t kind, bool is_max, const AggPartial* p, uint64_t stride, uint32_t n_blocks, AggAcc* fold_s) {
   AggAcc a = {0, 0, 0, 0.0, 0, 0};
-  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
-    const uint64_t left = n_in - w * 64;  // (w < ws.n: at least 1)
-    const unsigned long long m = keep ? keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
-    if (!((m >> lane) & 1)) continue;
-    const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
-    agg_expr_row(kind, prog, in.col2, cols, r, W, a);
+  for (uint32_t k = threadIdx.x; k < n_blocks; k += 256) {
+    const AggPartial& q = p[k * stride];
+    const AggAcc b = {q.w[0], q.w[1], q.w[2], q.f, q.count, q.flags};
+    agg_fold(kind, is_max, a, b);
   }
-  agg_block_fold(kind, false, a, fold_s);
-  if (threadIdx.x == 0) agg_store(partials + (uint64_t)blockIdx.y * gridDim.x + blockIdx.x, a);
+  agg_block_fold(kind, is_max, a, fold_s);
+  return a;
 }
 
 // blockIdx.x = instruction: its n_blocks records -> out[instruction]
@@ -287,13 +291,6 @@ agg_final_kernel(const AggInsn* insns, const AggPartial* partials, uint32_t n_bl
   __shared__ AggAcc fold_s[4];
   const AggInsn in = insns[blockIdx.x];
   const uint32_t kind = in.kind < AK_ALL_N ? in.kind : AK_COUNT_ROWS;
-  const bool is_max = in.is_max != 0;
-  const AggPartial* p = partials + (uint64_t)blockIdx.x * n_blocks;
-  AggAcc a = {0, 0, 0, 0.0, 0, 0};
-  for (uint32_t k = threadIdx.x; k < n_blocks; k += 256) {
-    const AggAcc b = {p[k].w[0], p[k].w[1], p[k].w[2], p[k].f, p[k].count, p[k].flags};
-    agg_fold(kind, is_max, a, b);
-  }
-  agg_block_fold(kind, is_max, a, fold_s);
+  const AggAcc a = agg_fold_records(kind, in.is_max != 0, partials + (uint64_t)blockIdx.x * n_blocks, 1, n_blocks, fold_s);
   if (threadIdx.x == 0) agg_store(out + blockIdx.x, a);
 }

@@ -5,6 +5,7 @@
 // of a row selection (SelBatch segments).  The stripe-wide buffers of the decode are read the way select_build_kernel does:
 // uniform batches of `B` rows, `W` validity words per batch, string offsets that restart per batch plus the batch's char base.
 // All of that is written down once, here (filter_row .. filter_value_str): a kernel addresses a row through these helpers only.
+// The aggregation's kernels take what filter_row needs, with the columns and the keep mask, as one argument: KeptRows.
 #pragma once
 #include <stdint.h>
 
@@ -51,6 +52,22 @@ struct FilterWords {
 };
 __device__ __forceinline__ FilterWords filter_words(uint64_t n_in) {
   return {(uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), (uint64_t)gridDim.x * 4, (n_in + 63) / 64};
+}
+
+// The rows a kernel walks, as ONE kernel argument passed by value (the aggregation's kernels; the host builds it once per call):
+// the columns, the input rows' segments, and the keep mask filter_eval_kernel left -- one word per 64 input rows; null: no filter,
+// every input row is kept
+struct KeptRows {
+  const FilterCol* cols;
+  const SelBatch* segs;
+  const unsigned long long* seg_first;
+  uint32_t n_segs;
+  uint64_t n_in;
+  uint32_t B, W;
+  const unsigned long long* keep;
+};
+__device__ __forceinline__ FilterRow filter_row(const KeptRows& rows, uint64_t j) {
+  return filter_row(rows.segs, rows.seg_first, rows.n_segs, rows.n_in, rows.B, j);
 }
 
 // bit l of batch u in bit words laid out per uniform batch (validity, Boolean values)

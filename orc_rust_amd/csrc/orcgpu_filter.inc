@@ -6,6 +6,10 @@
 // the per-batch null counts and string byte totals (filter_run_front, "the filter's one wait"); with them it lays the
 // output arena out compactly -- so that a copy back moves the kept rows' bytes and no more -- and enqueues the gather, which
 // nobody waits for: orcgpu_result_fetch_async orders its copies behind the decode stream.
+//
+// The aggregation's calls (orcgpu_agg.inc) open the way the filter's does and evaluate with its kernels: the opening
+// (filter_open, filter_workspace, filter_reserve), the predicate's compile against a result (result_compile_filter) and the
+// kernel argument for the rows (filter_kept_rows) stand here once, for the three of them.
 #include "orcgpu_filter_host.inc"
 namespace {
 
@@ -14,18 +18,23 @@ static_assert(kFilterAlign == kAlign && kFilterColBytes == sizeof(FilterCol) && 
 
 int enc_scan(orcgpu_ctx* ctx, hipStream_t st, const uint32_t* d_in, uint64_t count, uint64_t* d_sums, uint64_t* d_total, uint64_t* d_out);
 
-// One filter call: what its steps hand on
+// One call on a decoded result -- the row filter's, or an aggregation's (orcgpu_agg.inc), which borrows the front of the filter's
+// pipeline up to the evaluation: what its steps hand on
 struct FilterCall {
   orcgpu_ctx* ctx;
   orcgpu_result* r;
   const orcgpu_host::FilterPlan& plan;
-  uint32_t nc = 0, B = 0, W = 0;
+  const char* const* column_names;  // the result's columns, for the messages (null: none)
+  uint32_t n_names;
+  bool has_filter = true;  // false: an aggregation without a predicate -- `plan` is the empty one, nothing is evaluated
+  uint32_t nc = 0, B = 0, W = 0, src_batches = 0;  // (src_batches: uniform batches of the decode)
   std::vector<SelBatch> segs;       // the input rows: those of a row selection's batches (none: the stripe's) ...
   std::vector<uint64_t> seg_first;  // ... and the input row each starts at
   uint64_t n_in = 0;
   std::vector<FilterColDesc> descs;
   std::vector<FilterCol> fcols;
-  uint8_t* X = nullptr;  // the workspace on the device
+  uint8_t* X = nullptr;       // the workspace on the device
+  std::vector<uint8_t> host;  // the first upload
   template <typename T>
   T* at(uint64_t off) const { return reinterpret_cast<T*>(X + off); }
 };
@@ -71,8 +80,9 @@ void filter_describe(FilterCall& f) {
 }
 
 // The columns as the kernels see them, with pointers into the decode's arenas; the char bases of the string columns go into the
-// first upload (`host`)
-void filter_fill_cols(FilterCall& f, const FilterWorkspace& ws, uint32_t src_batches, uint8_t* host) {
+// first upload
+void filter_fill_cols(FilterCall& f, const FilterWorkspace& ws) {
+  uint8_t* const host = f.host.data();
   f.fcols.resize(f.nc);
   for (uint32_t c = 0; c < f.nc; c++) {
     const ColumnOut& co = f.r->cols[c];
@@ -91,12 +101,14 @@ void filter_fill_cols(FilterCall& f, const FilterWorkspace& ws, uint32_t src_bat
       fc.offsets = reinterpret_cast<const int32_t*>(A + co.offsets_off);
       fc.chars = (co.values_in_chars ? f.r->chars[co.lane].p : A) + co.values_off;
       fc.char_base = f.at<const unsigned long long>(ws.o_cbase[c]);
-      for (size_t k = 0; k < co.char_base.size() && k < src_batches; k++) reinterpret_cast<uint64_t*>(host + ws.o_cbase[c])[k] = co.char_base[k];
+      for (size_t k = 0; k < co.char_base.size() && k < f.src_batches; k++) reinterpret_cast<uint64_t*>(host + ws.o_cbase[c])[k] = co.char_base[k];
     } else fc.values = A + co.values_off;
   }
 }
 
-int filter_check(FilterCall& f, const char* const* column_names, uint32_t n_names) {
+int filter_check(FilterCall& f) {
+  const char* const* column_names = f.column_names;
+  const uint32_t n_names = f.n_names;
   std::vector<uint32_t> kinds(f.nc);
   for (uint32_t c = 0; c < f.nc; c++) kinds[c] = f.fcols[c].kind;
   uint32_t col = 0;
@@ -109,8 +121,9 @@ int filter_check(FilterCall& f, const char* const* column_names, uint32_t n_name
 }
 
 // The first upload: the program, its literals and leaf lists, the segments and the columns (nothing goes up for no input row)
-int filter_upload(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host) {
+int filter_upload(FilterCall& f, const FilterWorkspace& ws) {
   orcgpu_ctx* ctx = f.ctx;
+  std::vector<uint8_t>& host = f.host;
   hipStream_t st = ctx->stream;
   const orcgpu_host::FilterPlan& plan = f.plan;
   const uint32_t n_segs = (uint32_t)f.segs.size(), n_insn = (uint32_t)plan.prog.size(), n_like = (uint32_t)plan.like_leaves.size(), n_set = (uint32_t)plan.in_leaves.size();
@@ -163,10 +176,10 @@ int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
 
 // The first upload, then plane kernels -> evaluate -> scan -> place -> count, and the filter's one wait: `back` gets the kept
 // row count, then null counts and string bytes per (column, output batch)
-int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint8_t>& host, std::vector<uint64_t>& back) {
+int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint64_t>& back) {
   orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
-  if (const int rc = filter_upload(f, ws, host)) return rc;
+  if (const int rc = filter_upload(f, ws)) return rc;
   if (!f.n_in) return ORCGPU_OK;
   if (const int rc = filter_run_eval(f, ws)) return rc;
   const uint32_t n_segs = (uint32_t)f.segs.size(), nb_max = (uint32_t)ws.nb_max;
@@ -263,32 +276,69 @@ void filter_adopt_output(orcgpu_result* r, FilterOutput& out, uint64_t kept) {
   }
 }
 
+// The opening of a call on a decoded result, in two steps; between them a caller lays its own tables out behind ws.bytes.
+// filter_open: the device, the input rows and what the columns are (*rows_seen: the input rows)
+int filter_open(FilterCall& f, uint64_t* rows_seen) {
+  HIP_TRY(f.ctx, hipSetDevice(f.ctx->device));
+  f.nc = (uint32_t)f.r->cols.size();
+  f.B = f.r->batch;
+  f.W = f.r->words_per_batch;
+  filter_segments(f);
+  filter_describe(f);
+  f.src_batches = f.r->selected ? f.r->full_batches : f.r->n_batches;
+  if (rows_seen) *rows_seen = f.n_in;
+  return ORCGPU_OK;
+}
+FilterWorkspace filter_workspace(const FilterCall& f) {
+  return FilterWorkspace(f.plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), f.src_batches, f.n_in, f.B);
+}
+// filter_reserve: `bytes` of workspace on the device (ws.bytes and what the caller laid behind it; `what` names the caller in
+// the message), the columns into the first upload, and the plan against what the columns were decoded to
+int filter_reserve(FilterCall& f, const FilterWorkspace& ws, uint64_t bytes, const char* what) {
+  if (!f.r->filt_tmp.ensure(bytes + kAlign)) {
+    set_err(f.ctx, "hipMalloc(%llu) for %s failed", (unsigned long long)bytes, what);
+    return ORCGPU_HIP_ERROR;
+  }
+  f.X = f.r->filt_tmp.p;
+  f.host.assign(ws.up_bytes, 0);
+  filter_fill_cols(f, ws);
+  return f.has_filter ? filter_check(f) : ORCGPU_OK;
+}
+
+// The rows an aggregation's kernels walk: the kernel argument, once per call
+KeptRows filter_kept_rows(const FilterCall& f, const FilterWorkspace& ws) {
+  return {f.at<const FilterCol>(ws.o_cols), f.at<const SelBatch>(ws.o_segs), f.at<const unsigned long long>(ws.o_first), (uint32_t)f.segs.size(), f.n_in, f.B, f.W,
+          f.has_filter ? f.at<const unsigned long long>(ws.o_keep) : nullptr};
+}
+
+// The predicate's plan against a decoded result's columns (column_names: one per column of the result)
+int result_compile_filter(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes, const char* const* column_names,
+                          orcgpu_host::FilterPlan& plan) {
+  const uint32_t n_columns = (uint32_t)r->cols.size();
+  std::vector<int32_t> kinds(n_columns), params(n_columns, 0);
+  for (uint32_t c = 0; c < n_columns; c++) {
+    const ColumnOut& co = r->cols[c];
+    kinds[c] = co.orc_type;
+    params[c] = co.orc_type == ORCGPU_T_DECIMAL ? (int32_t)co.scale : co.ts_unit;  // what Decimal128 / TimestampNs literals are brought to
+  }
+  const int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan, params.data());
+  if (rc) set_err(ctx, "%s", plan.err);
+  return rc;
+}
+
+// Open, front, place, gather, adopt
 int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept,
                        const char* const* column_names = nullptr, uint32_t n_names = 0) {
   if (rows_seen) *rows_seen = 0;
   if (rows_kept) *rows_kept = 0;
   if (r->status) return r->status;  // a failed decode is left as it is
   if (const int rc = filter_refuse(ctx, r)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  FilterCall f{ctx, r, plan};
-  f.nc = (uint32_t)r->cols.size();
-  f.B = r->batch;
-  f.W = r->words_per_batch;
-  filter_segments(f);
-  filter_describe(f);
-  if (rows_seen) *rows_seen = f.n_in;
-  const uint32_t src_batches = r->selected ? r->full_batches : r->n_batches;  // uniform batches of the decode
-  const FilterWorkspace ws(plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), src_batches, f.n_in, f.B);
-  if (!r->filt_tmp.ensure(ws.bytes + kAlign)) {
-    set_err(ctx, "hipMalloc(%llu) for the row filter failed", (unsigned long long)ws.bytes);
-    return ORCGPU_HIP_ERROR;
-  }
-  f.X = r->filt_tmp.p;
-  std::vector<uint8_t> host(ws.up_bytes, 0);
-  filter_fill_cols(f, ws, src_batches, host.data());
-  if (const int rc = filter_check(f, column_names, n_names)) return rc;
+  FilterCall f{ctx, r, plan, column_names, n_names};
+  if (const int rc = filter_open(f, rows_seen)) return rc;
+  const FilterWorkspace ws = filter_workspace(f);
+  if (const int rc = filter_reserve(f, ws, ws.bytes, "the row filter")) return rc;
   std::vector<uint64_t> back(ws.n_counters, 0);
-  if (const int rc = filter_run_front(f, ws, host, back)) return rc;
+  if (const int rc = filter_run_front(f, ws, back)) return rc;
   const uint64_t kept = back[0];
   if (kept > f.n_in) {
     set_err(ctx, "row filter: %llu rows kept of %llu", (unsigned long long)kept, (unsigned long long)f.n_in);
@@ -314,17 +364,7 @@ extern "C" int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orc
     set_err(ctx, "row filter: %u column names for a result of %zu columns", n_columns, r->cols.size());
     return ORCGPU_INVALID_ARGUMENT;
   }
-  std::vector<int32_t> kinds(n_columns), params(n_columns, 0);
-  for (uint32_t c = 0; c < n_columns; c++) {
-    const ColumnOut& co = r->cols[c];
-    kinds[c] = co.orc_type;
-    params[c] = co.orc_type == ORCGPU_T_DECIMAL ? (int32_t)co.scale : co.ts_unit;  // what Decimal128 / TimestampNs literals are brought to
-  }
   orcgpu_host::FilterPlan plan;
-  int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan, params.data());
-  if (rc) {
-    set_err(ctx, "%s", plan.err);
-    return rc;
-  }
+  if (const int rc = result_compile_filter(ctx, r, nodes, n_nodes, column_names, plan)) return rc;
   return result_filter_plan(ctx, r, plan, nullptr, rows_kept, column_names, n_columns);
 }

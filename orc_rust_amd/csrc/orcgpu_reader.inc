@@ -385,12 +385,18 @@ int reader_compile_aggs(orcgpu_reader* rd) {
   if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
   return rc;
 }
+// The reader's own strings as the C array the plan compilers and the calls take
+static std::vector<const char*> reader_c_strings(const std::vector<std::string>& strings) {
+  std::vector<const char*> out;
+  for (auto& s : strings) out.push_back(s.c_str());
+  return out;
+}
 // ... and the key list of a GROUP BY, against the same description
 int reader_compile_group(orcgpu_reader* rd) {
-  std::vector<const char*> names, keys;
+  std::vector<const char*> names;
+  const std::vector<const char*> keys = reader_c_strings(rd->group_keys);
   std::vector<AggCol> cols;
   reader_describe_roots(rd, names, cols);
-  for (auto& k : rd->group_keys) keys.push_back(k.c_str());
   const int rc = group_compile(keys.data(), (uint32_t)keys.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->group_plan);
   if (rc) set_err(rd->ctx, "%s", rd->group_plan.err);
   return rc;
@@ -403,8 +409,7 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
     set_err(rd->ctx, "stripe decode failed in batch %u, column %u", res->err_batch, res->err_col);
     return res->status;
   }
-  std::vector<const char*> names;
-  for (auto& n : rd->proj.names) names.push_back(n.c_str());
+  const std::vector<const char*> names = reader_c_strings(rd->proj.names), keys = reader_c_strings(rd->group_keys);
   if (names.size() != res->cols.size()) {  // (a flat projection: one result column per root column; anything else the plan has refused)
     set_err(rd->ctx, "aggregate: the result holds %zu columns for %zu projected root columns", res->cols.size(), names.size());
     return ORCGPU_UNSUPPORTED;
@@ -421,30 +426,24 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
         set_err(rd->ctx, "aggregate: column '%s' is not decoded to the type its aggregate was planned for", names[plan.insns[k].col]);
       return ORCGPU_MISMATCHED_SCHEMA;
     }
+  GroupPlan gplan;
   if (rd->has_group) {  // the grouped reduction in the same place: the stripe's groups stay with the result
-    std::vector<const char*> keys;
-    for (auto& k : rd->group_keys) keys.push_back(k.c_str());
-    GroupPlan gplan;
     if (const int rc = result_compile_group(rd->ctx, res, keys.data(), (uint32_t)keys.size(), names.data(), gplan)) return rc;
     for (size_t k = 0; k < gplan.keys.size(); k++)
       if (gplan.keys[k].kind != rd->group_plan.keys[k].kind || gplan.keys[k].scale_or_unit != rd->group_plan.keys[k].scale_or_unit) {
         set_err(rd->ctx, "group by: key column '%s' is not decoded to the type its key was planned for", names[gplan.keys[k].col]);
         return ORCGPU_MISMATCHED_SCHEMA;
       }
-    GroupSet set;
-    uint64_t kept = 0;
-    const int rc = result_aggregate_groups_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, gplan, set, &res->agg_seen, &kept, names.data(), (uint32_t)names.size());
-    if (rc) return rc;
-    res->grp_keys = std::move(set.keys);
-    res->grp_vals = std::move(set.vals);
-    rd->filter_seen += res->agg_seen;
-    rd->filter_kept += kept;
-    return ORCGPU_OK;
   }
-  const int rc = result_aggregate_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, res->agg_records, &res->agg_seen, names.data(), (uint32_t)names.size());
+  GroupSet set;
+  uint64_t kept = 0;
+  const int rc = result_aggregate_call(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, rd->has_group ? &gplan : nullptr, set, &res->agg_seen, &kept,
+                                       names.data(), (uint32_t)names.size());
   if (rc) return rc;
+  if (rd->has_group) res->grp_keys = std::move(set.keys), res->grp_vals = std::move(set.vals);
+  else res->agg_records = std::move(set.vals);
   rd->filter_seen += res->agg_seen;
-  rd->filter_kept += res->agg_records.back().w[0];
+  rd->filter_kept += kept;
   return ORCGPU_OK;
 }
 

@@ -352,6 +352,28 @@ int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* rd, const orcgpu_agg_spec* 
   rd->has_aggs = true;
   return ORCGPU_OK;
 }
+// What the two drains share.  reader_drain_begin: a reader is drained once, and built first; from then on whatever comes of it ends
+// the reader as an error ends an iterator.  reader_drain: rc is what the compile steps gave; then the filter, then every stripe in
+// stripe order handed to merge_stripe (rd->current: its status ends the loop).  ORCGPU_OK: every stripe has been merged.
+static int reader_drain_begin(orcgpu_reader* rd) {
+  if (rd->aggs_done) return ORCGPU_END_OF_FILE;
+  const int rc = orcgpu_host::reader_build(rd);
+  if (!rc) rd->aggs_done = true;
+  return rc;
+}
+static int reader_drain(orcgpu_reader* rd, int rc, const std::function<int()>& merge_stripe) {
+  if (!rc) rc = reader_ready_filter(rd);
+  if (rc) {
+    rd->next_stripe = rd->stripe_order.size();
+    return rc;
+  }
+  while (!(rc = reader_next_stripe(rd)))
+    if ((rc = merge_stripe())) break;
+  if (rc == ORCGPU_END_OF_FILE) return ORCGPU_OK;
+  orcgpu_host::reader_stop_worker(rd);
+  rd->next_stripe = rd->stripe_order.size();
+  return rc;
+}
 // Drains the reader: every stripe's records, merged in stripe order, then the values
 int orcgpu_reader_aggregate(orcgpu_reader* rd, orcgpu_agg_value* out) {
   if (!rd || !out) return ORCGPU_INVALID_ARGUMENT;
@@ -363,32 +385,20 @@ int orcgpu_reader_aggregate(orcgpu_reader* rd, orcgpu_agg_value* out) {
     set_err(rd->ctx, "this reader groups its aggregates (orcgpu_reader_set_group_by): call orcgpu_reader_aggregate_groups");
     return ORCGPU_INVALID_ARGUMENT;
   }
-  if (rd->aggs_done) return ORCGPU_END_OF_FILE;
-  int rc = orcgpu_host::reader_build(rd);
-  if (rc) return rc;
-  rd->aggs_done = true;  // (whatever comes of it: an error ends the reader as it ends an iterator)
-  rc = orcgpu_host::reader_compile_aggs(rd);
-  if (!rc) rc = reader_ready_filter(rd);
-  if (rc) {
-    rd->next_stripe = rd->stripe_order.size();
-    return rc;
-  }
+  if (const int rc = reader_drain_begin(rd)) return rc;
+  int rc = orcgpu_host::reader_compile_aggs(rd);
   const std::vector<AggInsn>& insns = rd->agg_plan.insns;
   std::vector<AggPartial> total(insns.size(), AggPartial{});
-  while (!(rc = reader_next_stripe(rd))) {
+  rc = reader_drain(rd, rc, [&]() -> int {
     const std::vector<AggPartial>& part = rd->current->agg_records;
     if (part.size() != insns.size() + 1) {
       set_err(rd->ctx, "aggregate: a stripe came without its records");
-      rc = ORCGPU_UNEXPECTED;
-      break;
+      return ORCGPU_UNEXPECTED;
     }
     for (size_t k = 0; k < insns.size(); k++) orcgpu_host::agg_merge(insns[k], total[k], part[k]);
-  }
-  if (rc != ORCGPU_END_OF_FILE) {
-    orcgpu_host::reader_stop_worker(rd);
-    rd->next_stripe = rd->stripe_order.size();
-    return rc;
-  }
+    return ORCGPU_OK;
+  });
+  if (rc) return rc;
   for (size_t k = 0; k < insns.size(); k++) orcgpu_host::agg_finish(insns[k], total[k], &out[k]);
   return ORCGPU_OK;
 }
@@ -408,21 +418,14 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* rd, orcgpu_groups** out) {
     set_err(rd->ctx, "orcgpu_reader_aggregate_groups needs orcgpu_reader_set_group_by before the first call");
     return ORCGPU_INVALID_ARGUMENT;
   }
-  if (rd->aggs_done) return ORCGPU_END_OF_FILE;
-  int rc = orcgpu_host::reader_build(rd);
-  if (rc) return rc;
-  rd->aggs_done = true;  // (whatever comes of it: an error ends the reader as it ends an iterator)
+  if (const int rc = reader_drain_begin(rd)) return rc;
+  int rc = ORCGPU_OK;
   if (!rd->has_aggs) {
     set_err(rd->ctx, "group by: orcgpu_reader_set_group_by without orcgpu_reader_set_aggregates");
     rc = ORCGPU_INVALID_ARGUMENT;
   }
   if (!rc) rc = orcgpu_host::reader_compile_group(rd);
   if (!rc) rc = orcgpu_host::reader_compile_aggs(rd);
-  if (!rc) rc = reader_ready_filter(rd);
-  if (rc) {
-    rd->next_stripe = rd->stripe_order.size();
-    return rc;
-  }
   std::vector<AggInsn> insns = rd->agg_plan.insns;
   const uint32_t n_specs = (uint32_t)insns.size();
   insns.push_back(AggInsn{});  // (the group's kept row count: AK_COUNT_ROWS)
@@ -430,25 +433,18 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* rd, orcgpu_groups** out) {
   orcgpu_host::GroupSet total;
   total.n_keys = (uint32_t)nk;
   total.n_insn = (uint32_t)ni;
-  while (!(rc = reader_next_stripe(rd))) {
+  rc = reader_drain(rd, rc, [&]() -> int {
     const orcgpu_result* res = rd->current;
     if (res->grp_keys.size() % nk || res->grp_vals.size() != res->grp_keys.size() / nk * ni) {
       set_err(rd->ctx, "group by: a stripe came without its groups");
-      rc = ORCGPU_UNEXPECTED;
-      break;
+      return ORCGPU_UNEXPECTED;
     }
     char err[256];
-    rc = orcgpu_host::group_merge(rd->group_plan, insns, total, res->grp_keys.data(), res->grp_vals.data(), (uint32_t)(res->grp_keys.size() / nk), err, sizeof(err));
-    if (rc) {
-      set_err(rd->ctx, "%s", err);
-      break;
-    }
-  }
-  if (rc != ORCGPU_END_OF_FILE) {
-    orcgpu_host::reader_stop_worker(rd);
-    rd->next_stripe = rd->stripe_order.size();
-    return rc;
-  }
+    const int mrc = orcgpu_host::group_merge(rd->group_plan, insns, total, res->grp_keys.data(), res->grp_vals.data(), (uint32_t)(res->grp_keys.size() / nk), err, sizeof(err));
+    if (mrc) set_err(rd->ctx, "%s", err);
+    return mrc;
+  });
+  if (rc) return rc;
   orcgpu_groups* g = new orcgpu_groups;
   orcgpu_host::group_finish(rd->group_plan, insns, n_specs, total, *g);
   *out = g;
