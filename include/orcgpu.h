@@ -621,8 +621,9 @@ int orcgpu_reader_aggregate(orcgpu_reader* r, orcgpu_agg_value* out);
 /* ---- GROUP BY for the aggregates: one record per (aggregate, group), the keys hashed on the device ---------------------------
  * TPC-H Q1 is SELECT l_returnflag, l_linestatus, sum(...), count(*) ... GROUP BY l_returnflag, l_linestatus.  The aggregate list
  * above is reduced per GROUP of kept rows (device/agg_group_kernels.hip); what comes back is the groups' keys and one value per
- * (group, aggregate), and nothing else.  The reference has no aggregation; the semantics are fixed here.  A first step on purpose:
- * low-cardinality grouping, at most ORCGPU_GROUP_MAX groups in one result (one stripe) -- flags, statuses, dates, small codes.
+ * (group, aggregate), and nothing else.  The reference has no aggregation; the semantics are fixed here.  By default
+ * low-cardinality grouping, at most ORCGPU_GROUP_MAX groups in one result (one stripe) -- flags, statuses, dates, small codes;
+ * a higher limit is opt-in (LIMITS below).
  *   - Kept rows and aggregates are what they are above: every op, column kind, refusal and overflow rule, applied per group.
  *     COUNT_ROWS of a group is its kept rows and never 0: a group exists only if a kept row has its key.
  *   - KEYS: 1 .. ORCGPU_GROUP_MAX_KEYS key columns, named like the aggregates' columns: projected root columns.  A column may be
@@ -644,10 +645,29 @@ int orcgpu_reader_aggregate(orcgpu_reader* r, orcgpu_agg_value* out);
  *     stripe order across stripes.  The whole answer is the same on every run of the same call: groups, order, integer and Decimal
  *     values (exact), MIN / MAX, and Float / Double sums bit for bit (a reduction of fixed shape; no floating-point atomic; which
  *     thread wins a race for a slot of the hash table shows in no output).
- *   - No kept row: zero groups, not one group of NULLs. */
+ *   - No kept row: zero groups, not one group of NULLs.
+ *   - LIMITS.  ORCGPU_GROUP_MAX and ORCGPU_GROUP_MAX_TOTAL are the defaults.  orcgpu_reader_set_group_limits and
+ *     orcgpu_result_aggregate_groups_limit (below) raise them, up to ORCGPU_GROUP_LIMIT_MAX groups in one result and
+ *     ORCGPU_GROUP_TOTAL_LIMIT_MAX over a reader's stripes -- GROUP BY l_suppkey, l_partkey, l_orderkey.  Everything above holds per
+ *     group with only the numbers changed: the data-dependent refusals are "more than max_groups groups in one result" and "more
+ *     than max_total groups over the stripes", ORCGPU_UNSUPPORTED, the message giving the limit that was set.
+ *     WHICH PATH RUNS is decided by the limit alone, on the host, never by the data: max_groups <= ORCGPU_GROUP_MAX runs the
+ *     reduction described above (accumulators per group in LDS); a higher limit runs, for the whole call and however few groups
+ *     the rows hold, the wide path (device/agg_group_wide_kernels.hip): the kept rows are sorted stably by their group's number of
+ *     first appearance (an LSD radix sort, 8 bits a pass, as many passes as the limit needs) and every group is reduced as one
+ *     segment, its rows in ascending input-row order, in a tree whose shape depends on the group's kept-row count alone.  Its cost
+ *     follows the rows, not the limit; its device workspace holds records for min(max_groups, input rows) groups.  Integers,
+ *     Decimals, MIN / MAX, groups and order are the same on both paths; a Float / Double sum may differ in its last bits between
+ *     the two, because the order of summation differs.  Each path is deterministic for itself: on the wide path the whole answer,
+ *     Float sums bit for bit, is a function of the kept rows in input order and of max_groups only.
+ *     HOST WAITS: the narrow path one per call, as above.  The wide path TWO: the first fetches the group count and the flags
+ *     (16 bytes), and -- the flags checked -- the second exactly n_groups key records and n_groups x aggregates value records.
+ *     Nothing copied back is sized by the limit. */
 #define ORCGPU_GROUP_MAX_KEYS 4
 #define ORCGPU_GROUP_MAX 256
 #define ORCGPU_GROUP_MAX_TOTAL 65536
+#define ORCGPU_GROUP_LIMIT_MAX 1048576
+#define ORCGPU_GROUP_TOTAL_LIMIT_MAX 16777216
 #define ORCGPU_GROUP_KEY_BYTES 64
 enum { ORCGPU_GROUP_KEY_I64 = 0, ORCGPU_GROUP_KEY_DEC128 = 1, ORCGPU_GROUP_KEY_BOOL = 2, ORCGPU_GROUP_KEY_STRING = 3 };
 typedef struct {
@@ -744,6 +764,17 @@ int orcgpu_result_aggregate_groups_exprs(orcgpu_ctx* ctx, const orcgpu_result* r
                                          const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
                                          const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_groups** out);
 int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs);
+/* The limits of a GROUP BY (LIMITS above).  orcgpu_result_aggregate_groups_limit is orcgpu_result_aggregate_groups_exprs with the
+ * limit of groups in the result: 0 = ORCGPU_GROUP_MAX, a value above ORCGPU_GROUP_LIMIT_MAX ORCGPU_INVALID_ARGUMENT; the entries
+ * without a limit are this one called with 0.  orcgpu_reader_set_group_limits is legal where orcgpu_reader_set_group_by is (before
+ * the first call, in either order with it): max_groups per stripe and max_total over the stripes, 0 = leave the default (256 /
+ * 65536); a value above its maximum, and max_total < max_groups after the defaults are applied, are ORCGPU_INVALID_ARGUMENT and
+ * change nothing.  A limit above ORCGPU_GROUP_MAX costs two host waits a stripe instead of one. */
+int orcgpu_result_aggregate_groups_limit(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                         const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                         const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, uint32_t max_groups,
+                                         orcgpu_groups** out);
+int orcgpu_reader_set_group_limits(orcgpu_reader* r, uint32_t max_groups, uint32_t max_total);
 uint32_t orcgpu_groups_count(const orcgpu_groups* g);
 int orcgpu_groups_key(const orcgpu_groups* g, uint32_t group, uint32_t key, orcgpu_group_key* out);
 int orcgpu_groups_value(const orcgpu_groups* g, uint32_t group, uint32_t spec, orcgpu_agg_value* out);

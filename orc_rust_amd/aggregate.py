@@ -27,6 +27,7 @@ KIND_U64, KIND_I128, KIND_DEC128, KIND_F64, KIND_I64 = range(5)  # ORCGPU_AGG_KI
 AGG_MAX = 64  # ORCGPU_AGG_MAX
 GROUP_KEY_I64, GROUP_KEY_DEC128, GROUP_KEY_BOOL, GROUP_KEY_STRING = range(4)  # ORCGPU_GROUP_KEY_*
 GROUP_MAX_KEYS, GROUP_MAX, GROUP_MAX_TOTAL, GROUP_KEY_BYTES = 4, 256, 65536, 64  # ORCGPU_GROUP_*
+GROUP_LIMIT_MAX, GROUP_TOTAL_LIMIT_MAX = 1 << 20, 1 << 24  # ORCGPU_GROUP_LIMIT_MAX, ORCGPU_GROUP_TOTAL_LIMIT_MAX
 _NAMES = ("count_rows", "count", "sum", "min", "max", "sum_product", "sum", "avg", "avg")
 TS_UNITS = ("s", "ms", "us", "ns")
 
@@ -248,6 +249,26 @@ def check_group_by(group_by):
     if len(group_by) > GROUP_MAX_KEYS:
         raise ValueError("aggregate: %d group_by columns, at most %d" % (len(group_by), GROUP_MAX_KEYS))
     return list(group_by)
+
+
+def check_group_limits(max_groups, max_total_groups, group_by):
+    """The max_groups / max_total_groups arguments of aggregate(), checked before anything reaches the GPU: each None (the
+    default: 256 / 65536) or an int -- not a bool -- of 1 .. 2^20 / 1 .. 2^24, the total not below the limit of one stripe, and
+    neither without a group_by.  Returns them as the C calls take them: 0 for None."""
+    for what, v, top in (("max_groups", max_groups, GROUP_LIMIT_MAX), ("max_total_groups", max_total_groups, GROUP_TOTAL_LIMIT_MAX)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("aggregate: %s is an int, not %s (%r)" % (what, type(v).__name__, v))
+        if not 1 <= v <= top:
+            raise ValueError("aggregate: %s is %d, not in 1 .. %d" % (what, v, top))
+        if group_by is None:
+            raise ValueError("aggregate: %s = %d without a group_by" % (what, v))
+    groups = GROUP_MAX if max_groups is None else max_groups
+    total = GROUP_MAX_TOTAL if max_total_groups is None else max_total_groups
+    if total < groups:
+        raise ValueError("aggregate: max_total_groups is %d, below max_groups = %d" % (total, groups))
+    return max_groups or 0, max_total_groups or 0
 
 
 def key_array(group_by):

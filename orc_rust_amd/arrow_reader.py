@@ -144,7 +144,7 @@ class ArrowReaderBuilder:
         self._device_output = bool(on)
         return self
 
-    def aggregate(self, specs, raw=False, group_by=None):
+    def aggregate(self, specs, raw=False, group_by=None, max_groups=None, max_total_groups=None):
         """COUNT, SUM, AVG, MIN, MAX, SUM(a * b) and SUM / AVG of an arithmetic expression (aggregate.col / aggregate.lit) over the rows the builder's selection and row filter keep, reduced on the GPU
         (orcgpu_reader_set_aggregates / orcgpu_reader_aggregate): specs is a list of orc_rust_amd.aggregate.Agg, the result a list
         of int (counts, integer results; a Timestamp's with `.units`), decimal.Decimal, float, or None for NULL.  Builds the reader
@@ -154,12 +154,18 @@ class ArrowReaderBuilder:
         group_by: a list or tuple of 1 .. 4 distinct column names (orcgpu_reader_set_group_by / orcgpu_reader_aggregate_groups): the
         result is a list of (keys tuple, values list), one per group of kept rows, in order of first appearance; at most 256
         groups a stripe.  A key is an int, bool, decimal.Decimal, str (bytes when not UTF-8) or None for the NULL key.  The
-        projection must hold the key columns too.  OverflowError names the spec and the group's keys."""
-        return self.aggregating_reader(specs, group_by=group_by).aggregate(raw=raw)
+        projection must hold the key columns too.  OverflowError names the spec and the group's keys.
 
-    def aggregating_reader(self, specs, group_by=None):
+        max_groups (1 .. 2^20) and max_total_groups (1 .. 2^24, not below max_groups) raise the limits of groups in one stripe and
+        over the file from 256 and 65536 (orcgpu_reader_set_group_limits); they need group_by.  A max_groups above 256 runs the
+        wide path -- a sort of the kept rows by group and a segmented reduction -- for every stripe, however few groups it holds:
+        GROUP BY l_suppkey, l_partkey.  A Float sum may differ in its last bits from the default path's."""
+        return self.aggregating_reader(specs, group_by=group_by, max_groups=max_groups, max_total_groups=max_total_groups).aggregate(raw=raw)
+
+    def aggregating_reader(self, specs, group_by=None, max_groups=None, max_total_groups=None):
         """The same in two steps: the ArrowReader whose aggregate() drains it (and whose filter_rows() / d2h_bytes() report on it)."""
         from . import aggregate as A
+        max_groups, max_total_groups = A.check_group_limits(max_groups, max_total_groups, group_by)
         arr, keep = A.spec_array(specs)
         keys = A.key_array(group_by) if group_by is not None else None
         exprs, keep_e = A.expr_array(specs)
@@ -169,6 +175,8 @@ class ArrowReaderBuilder:
             self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregate_exprs(self._h, arr, exprs, len(arr)))
         if keys is not None:
             self._ctx._check(self._ctx.L.orcgpu_reader_set_group_by(self._h, keys, len(keys)))
+        if max_groups or max_total_groups:
+            self._ctx._check(self._ctx.L.orcgpu_reader_set_group_limits(self._h, max_groups, max_total_groups))
         r = self.build()
         r._agg_specs = A.check_specs(specs)
         r._group_by = A.check_group_by(group_by) if group_by is not None else None

@@ -30,6 +30,7 @@ EXPORTS = [
     "orcgpu_result_aggregate_groups", "orcgpu_reader_set_group_by", "orcgpu_reader_aggregate_groups", "orcgpu_groups_count", "orcgpu_groups_key",
     "orcgpu_groups_value", "orcgpu_groups_free",
     "orcgpu_result_aggregate_exprs", "orcgpu_result_aggregate_groups_exprs", "orcgpu_reader_set_aggregate_exprs",
+    "orcgpu_result_aggregate_groups_limit", "orcgpu_reader_set_group_limits",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
@@ -228,6 +229,10 @@ def load():
     L.orcgpu_result_aggregate_groups.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                                  C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.c_uint32, C.POINTER(C.c_void_p)]
     L.orcgpu_reader_set_group_by.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
+    L.orcgpu_result_aggregate_groups_limit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                       C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32, C.c_uint32,
+                                                       C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_set_group_limits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     L.orcgpu_reader_aggregate_groups.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.orcgpu_groups_count.restype = C.c_uint32
     L.orcgpu_groups_count.argtypes = [C.c_void_p]
@@ -484,14 +489,19 @@ class Context:
             self._check(self.L.orcgpu_result_aggregate_exprs(self.h, result.h, *rows, arr, exprs, n, out))
         return list(out) if raw else A.values_of(out, specs)
 
-    def result_aggregate_groups(self, result, specs, group_by, column_names, predicate=None, raw=False):
+    def result_aggregate_groups(self, result, specs, group_by, column_names, predicate=None, raw=False, max_groups=None):
         """orcgpu_result_aggregate_groups: result_aggregate per group of the key columns `group_by` (1 .. 4 column names).  Returns
-        [(keys tuple, values list)] in first-appearance order (aggregate.key_of / value_of); raw=True: the values as records."""
+        [(keys tuple, values list)] in first-appearance order (aggregate.key_of / value_of); raw=True: the values as records.
+        max_groups: the limit of groups in the result, 1 .. 2^20 (orcgpu_result_aggregate_groups_limit; None: 256); above 256 the
+        wide path runs."""
         from . import aggregate as A
+        max_groups, _ = A.check_group_limits(max_groups, None if max_groups is None else A.GROUP_TOTAL_LIMIT_MAX, group_by)  # (one result: no total)
         rows, (arr, exprs, n), keep = self._aggregate_args(specs, column_names, predicate)
         keys = A.key_array(group_by)
         out = C.c_void_p()
-        if exprs is None:
+        if max_groups:
+            self._check(self.L.orcgpu_result_aggregate_groups_limit(self.h, result.h, *rows, keys, len(keys), arr, exprs, n, max_groups, C.byref(out)))
+        elif exprs is None:
             self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, *rows, keys, len(keys), arr, n, C.byref(out)))
         else:
             self._check(self.L.orcgpu_result_aggregate_groups_exprs(self.h, result.h, *rows, keys, len(keys), arr, exprs, n, C.byref(out)))

@@ -96,9 +96,10 @@ __device__ __forceinline__ bool group_rows_equal(const GroupKeys& keys, const Fi
 // table (kGroupSlots slots) and ctl are zeroed by the call before this kernel; plane gets one entry per input row of the words
 // that hold a kept row: the row's slot, or kGroupNoSlot for a row that is not kept or stopped inserting.  Every index into the
 // table is masked to kGroupSlots; a claimer read from a slot is an input row some thread put there, so below n_in.
-// Resource usage (gfx950): 62 VGPRs, 105 SGPRs, no scratch, no spill, no LDS; occupancy 7 waves / SIMD.
-extern "C" __global__ void __launch_bounds__(256)
-group_assign_kernel(GroupKeys keys, KeptRows rows, GroupSlot* table, GroupControl* ctl, uint32_t* plane) {
+// (The body of two kernels: group_assign_kernel gives it the constants kGroupSlots and kGroupMax, group_wide_assign_kernel of
+// agg_group_wide_kernels.hip a table of `slots` slots -- a power of two -- and the limit `max_groups` that was set.)
+__device__ __forceinline__ void group_assign_body(const GroupKeys& keys, const KeptRows& rows, GroupSlot* table, const uint32_t slots, const uint32_t max_groups,
+                                                  GroupControl* ctl, uint32_t* plane) {
   const uint32_t lane = threadIdx.x & 63;
   const FilterCol* const cols = rows.cols;
   const uint64_t n_in = rows.n_in;
@@ -113,14 +114,14 @@ group_assign_kernel(GroupKeys keys, KeptRows rows, GroupSlot* table, GroupContro
     if (kept) {
       const FilterRow r = filter_row(rows, j);
       const uint32_t h = group_row_hash(keys, cols, r, B, W);
-      for (uint32_t step = 0; step < kGroupSlots; step++) {
-        const uint32_t s = (h + step) & (kGroupSlots - 1);
+      for (uint32_t step = 0; step < slots; step++) {
+        const uint32_t s = (h + step) & (slots - 1);
         unsigned long long cur = __atomic_load_n(&table[s].claim, __ATOMIC_RELAXED);
         if (!cur) {
           if (__atomic_load_n(&ctl->flags, __ATOMIC_RELAXED) & GROUP_TOO_MANY) break;  // (the answer is refused: nothing more goes in)
           cur = atomicCAS(&table[s].claim, 0ull, (unsigned long long)(j + 1));
           if (!cur) {
-            if (atomicAdd(&ctl->claimed, 1u) >= kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
+            if (atomicAdd(&ctl->claimed, 1u) >= max_groups) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
             slot = s;
             break;
           }
@@ -145,34 +146,15 @@ group_assign_kernel(GroupKeys keys, KeptRows rows, GroupSlot* table, GroupContro
     }
   }
 }
+// Resource usage (gfx950): 62 VGPRs, 105 SGPRs, no scratch, no spill, no LDS; occupancy 7 waves / SIMD.
+extern "C" __global__ void __launch_bounds__(256)
+group_assign_kernel(GroupKeys keys, KeptRows rows, GroupSlot* table, GroupControl* ctl, uint32_t* plane) {
+  group_assign_body(keys, rows, table, kGroupSlots, kGroupMax, ctl, plane);
+}
 
-// <<<1, kGroupSlots>>>: thread s is slot s.  slot_group[s] = the slot's dense group number (kGroupNoSlot: free, or past kGroupMax);
-// key_recs: [group][key].  Nothing is numbered for a table that holds more than kGroupMax groups.
-extern "C" __global__ void __launch_bounds__(1024)
-group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, GroupControl* ctl, uint32_t* slot_group, GroupKeyRecord* key_recs) {
-  __shared__ unsigned long long first_s[kGroupSlots];
-  __shared__ uint32_t n_s;
-  const uint32_t s = threadIdx.x;
-  if (s == 0) n_s = 0;
-  const bool used = table[s].claim != 0;
-  const unsigned long long first = used ? ~table[s].first_inv : ~0ull;
-  first_s[s] = first;
-  __syncthreads();
-  uint32_t rank = 0;
-  if (used) {
-    for (uint32_t t = 0; t < kGroupSlots; t++) rank += first_s[t] < first;
-    atomicAdd(&n_s, 1u);
-  }
-  __syncthreads();
-  const uint32_t n_groups = n_s;
-  const bool fits = n_groups <= kGroupMax && !(ctl->flags & GROUP_TOO_MANY);
-  if (s == 0) {
-    ctl->n_groups = n_groups;
-    if (n_groups > kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
-  }
-  const bool mine = used && fits && rank < kGroupMax && first < rows.n_in;
-  slot_group[s] = mine ? rank : kGroupNoSlot;
-  if (!mine) return;
+// The GroupKeyRecord of every key column of group `rank`, from the group's first row `first` (an input row below n_in) ->
+// key_recs[rank][key]; a String key of more than kGroupKeyBytes bytes sets the key's flag
+__device__ __forceinline__ void group_store_keys(const GroupKeys& keys, const KeptRows& rows, uint64_t first, uint32_t rank, GroupControl* ctl, GroupKeyRecord* key_recs) {
   const uint32_t B = rows.B, W = rows.W;
   const FilterRow r = filter_row(rows, first);
   for (uint32_t k = 0; k < keys.n; k++) {
@@ -204,6 +186,35 @@ group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, Group
       out->w[1] = (unsigned long long)(v >> 63);
     }
   }
+}
+
+// <<<1, kGroupSlots>>>: thread s is slot s.  slot_group[s] = the slot's dense group number (kGroupNoSlot: free, or past kGroupMax);
+// key_recs: [group][key].  Nothing is numbered for a table that holds more than kGroupMax groups.
+extern "C" __global__ void __launch_bounds__(1024)
+group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, GroupControl* ctl, uint32_t* slot_group, GroupKeyRecord* key_recs) {
+  __shared__ unsigned long long first_s[kGroupSlots];
+  __shared__ uint32_t n_s;
+  const uint32_t s = threadIdx.x;
+  if (s == 0) n_s = 0;
+  const bool used = table[s].claim != 0;
+  const unsigned long long first = used ? ~table[s].first_inv : ~0ull;
+  first_s[s] = first;
+  __syncthreads();
+  uint32_t rank = 0;
+  if (used) {
+    for (uint32_t t = 0; t < kGroupSlots; t++) rank += first_s[t] < first;
+    atomicAdd(&n_s, 1u);
+  }
+  __syncthreads();
+  const uint32_t n_groups = n_s;
+  const bool fits = n_groups <= kGroupMax && !(ctl->flags & GROUP_TOO_MANY);
+  if (s == 0) {
+    ctl->n_groups = n_groups;
+    if (n_groups > kGroupMax) atomicOr(&ctl->flags, (uint32_t)GROUP_TOO_MANY);
+  }
+  const bool mine = used && fits && rank < kGroupMax && first < rows.n_in;
+  slot_group[s] = mine ? rank : kGroupNoSlot;
+  if (mine) group_store_keys(keys, rows, first, rank, ctl, key_recs);
 }
 
 // partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's

@@ -10,6 +10,10 @@ constexpr uint32_t kGroupMax = 256;         // ORCGPU_GROUP_MAX: groups of one r
 constexpr uint32_t kGroupKeyBytes = 64;     // ORCGPU_GROUP_KEY_BYTES: a String key value's bytes
 constexpr uint32_t kGroupSlots = 1024;      // the open-addressing table group_assign_kernel probes: four slots a group at the limit
 constexpr uint32_t kGroupNoSlot = 0xffffffffu;
+// The wide path (agg_group_wide_kernels.hip), taken when the limit of groups in one result is set above kGroupMax
+constexpr uint32_t kGroupLimitMax = 1u << 20;   // ORCGPU_GROUP_LIMIT_MAX: the highest limit of groups in one result
+constexpr uint32_t kGroupWideTile = 2048;       // input rows, and sorted pairs, a block of the wide kernels takes: 4 wavefronts x 8 words
+constexpr uint32_t kGroupRadixBits = 8;         // bits of the group number a pass of the sort takes
 
 // The key columns, by value into every kernel.  hash_mask: the bits of a key tuple's hash that are kept (ORCGPU_GROUP_HASH_BITS)
 struct GroupKeys {
@@ -32,7 +36,7 @@ struct GroupControl {
   uint32_t flags;     // GROUP_*
   uint32_t n_groups;  // group_number_kernel: occupied slots (may pass kGroupMax: GROUP_TOO_MANY is set then)
   uint32_t claimed;   // group_assign_kernel: slots claimed so far
-  uint32_t pad;
+  uint32_t kept;      // the wide path only: the kept rows, which are the pairs its sort moves (else 0)
 };
 
 // The key of a group in one key column, from the group's first row: w = the int64 (sign-extended into w[1]), the Boolean as 0 / 1

@@ -45,6 +45,7 @@
 #include "device/filter_kernels.hip"
 #include "device/agg_kernels.hip"
 #include "device/agg_group_kernels.hip"
+#include "device/agg_group_wide_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"

@@ -9,6 +9,10 @@
 //   agg_run      agg_partial_kernel -> agg_final_kernel -> the wait, which fetches one record per instruction;
 //   group_run    zero the table -> group_assign_kernel -> group_number_kernel -> agg_group_partial_kernel -> agg_group_final_kernel
 //                -> the wait, which fetches the group count and the flags, the key records and the value records in one copy.
+//   group_run_wide   (a GroupPlan whose max_groups is above kGroupMax: device/agg_group_wide_kernels.hip, its head comment has the
+//                pipeline) zero the table -> assign -> count / scan / number -> the sort's passes -> segments -> the reduction ->
+//                the FIRST wait, which fetches the control -> the flags check -> the SECOND, which fetches n_groups key and value
+//                records.  Two waits, and nothing copied back that the limit sizes.
 // The result is read, never changed.  The instructions are the plan's and, behind them, the kept row count (AK_COUNT_ROWS).
 //
 // Instructions that sum an arithmetic expression (AK_EXPR_*) bring their programs in an op table uploaded beside the instructions
@@ -25,6 +29,7 @@ namespace {
 struct AggWorkspace {
   uint32_t n_insn = 0, n_keys = 0, blocks = 0;  // instructions (the aggregates, then the kept row count); the partial kernel's blocks along x
   uint64_t o_insn = 0, o_ops = 0, o_table = 0, zero_bytes = 0, o_plane = 0, o_slot_group = 0, o_part = 0, o_back = 0, back_keys = 0, back_vals = 0, back_bytes = 0, bytes = 0;
+  orcgpu_host::GroupWideLayout wide;  // the wide path's tables instead (group_wide_layout), behind the instructions and the op table
   AggWorkspace(uint64_t filter_bytes, uint32_t n_specs, const orcgpu_host::GroupPlan* gplan, uint64_t n_in, size_t n_ops) {
     FilterBump t;
     t.off = filter_bytes;
@@ -32,6 +37,13 @@ struct AggWorkspace {
     blocks = gplan ? agg_group_blocks(n_in) : agg_blocks(n_in);
     o_insn = t.take((uint64_t)n_insn * sizeof(AggInsn) + 16);
     o_ops = t.take((uint64_t)n_ops * sizeof(AggExprOp) + 16);
+    if (gplan && orcgpu_host::group_is_wide(gplan->max_groups)) {
+      n_keys = (uint32_t)gplan->keys.size();
+      blocks = agg_blocks(n_in);
+      wide = orcgpu_host::group_wide_layout(t.off, gplan->max_groups, n_in, n_insn, n_keys);
+      bytes = wide.bytes;
+      return;
+    }
     if (gplan) {
       n_keys = (uint32_t)gplan->keys.size();
       zero_bytes = (uint64_t)kGroupSlots * sizeof(GroupSlot);
@@ -135,12 +147,8 @@ int agg_run(const FilterCall& f, const AggWorkspace& aw, const KeptRows& rows, c
   return ORCGPU_OK;
 }
 
-// The grouped reduction behind the evaluation and its one wait: `set` gets the result's groups in first-appearance order, with
-// the instructions' records and behind them the group's kept row count
-int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows, const orcgpu_host::GroupPlan& gplan, const std::vector<AggInsn>& insns,
-              const std::vector<AggExprOp>& ops, orcgpu_host::GroupSet& set) {
-  orcgpu_ctx* ctx = f.ctx;
-  hipStream_t st = ctx->stream;
+// The key list as the kernels take it; ORCGPU_GROUP_HASH_BITS is read per call
+GroupKeys group_keys_of(const orcgpu_host::GroupPlan& gplan) {
   GroupKeys keys{};
   keys.n = (uint32_t)gplan.keys.size();
   keys.hash_mask = orcgpu_host::group_hash_mask(getenv("ORCGPU_GROUP_HASH_BITS"));
@@ -148,15 +156,27 @@ int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows,
     keys.col[k] = gplan.keys[k].col;
     keys.fkind[k] = gplan.keys[k].fkind;
   }
+  return keys;
+}
+// ORCGPU_POISON, the debugging aid of the decode, over the aggregation's tables of either path: nothing may depend on what the
+// workspace held before.  (A failure to fill is not the call's failure.)
+void group_poison(const FilterCall& f, const AggWorkspace& gw) {
+  static const char* poison = getenv("ORCGPU_POISON");
+  if (poison && *poison) (void)hipMemsetAsync(f.X + gw.o_insn, (int)strtol(poison, nullptr, 0) & 0xFF, gw.bytes - gw.o_insn, f.ctx->stream);
+}
+
+// The grouped reduction behind the evaluation and its one wait: `set` gets the result's groups in first-appearance order, with
+// the instructions' records and behind them the group's kept row count
+int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows, const orcgpu_host::GroupPlan& gplan, const std::vector<AggInsn>& insns,
+              const std::vector<AggExprOp>& ops, orcgpu_host::GroupSet& set) {
+  orcgpu_ctx* ctx = f.ctx;
+  hipStream_t st = ctx->stream;
+  const GroupKeys keys = group_keys_of(gplan);
   GroupSlot* d_table = f.at<GroupSlot>(gw.o_table);
   GroupControl* d_ctl = f.at<GroupControl>(gw.o_back);
   uint32_t *d_plane = f.at<uint32_t>(gw.o_plane), *d_slot_group = f.at<uint32_t>(gw.o_slot_group);
   AggPartial *d_part = f.at<AggPartial>(gw.o_part), *d_out = f.at<AggPartial>(gw.o_back + gw.back_vals);
-  {
-    // (the debugging aid of the decode: nothing here may depend on what the workspace held before)
-    static const char* poison = getenv("ORCGPU_POISON");
-    if (poison && *poison) HIP_TRY(ctx, hipMemsetAsync(f.X + gw.o_insn, (int)strtol(poison, nullptr, 0) & 0xFF, gw.bytes - gw.o_insn, st));
-  }
+  group_poison(f, gw);
   if (const int rc = agg_upload(f, gw, insns, ops)) return rc;
   HIP_TRY(ctx, hipMemsetAsync(d_table, 0, gw.zero_bytes, st));
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, gw.back_bytes, st));
@@ -187,6 +207,94 @@ int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows,
   const AggPartial* vals = reinterpret_cast<const AggPartial*>(back.data() + gw.back_vals);  // [instruction][kGroupMax]
   for (uint32_t g = 0; g < n; g++)
     for (uint32_t k = 0; k < ni; k++) set.vals[(size_t)g * ni + k] = vals[(size_t)k * kGroupMax + g];
+  return ORCGPU_OK;
+}
+
+// group_run where the plan's limit is above kGroupMax: the same answer by the wide path, for whatever the rows hold
+int group_run_wide(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows, const orcgpu_host::GroupPlan& gplan, const std::vector<AggInsn>& insns,
+                   const std::vector<AggExprOp>& ops, orcgpu_host::GroupSet& set) {
+  orcgpu_ctx* ctx = f.ctx;
+  hipStream_t st = ctx->stream;
+  const orcgpu_host::GroupWideLayout& w = gw.wide;
+  if (f.n_in >= 0xffffffffull - 64) {  // (a pair of the sort holds its input row in 32 bits)
+    set_err(ctx, "group by: a result of %llu input rows is more than a limit above ORCGPU_GROUP_MAX takes", (unsigned long long)f.n_in);
+    return ORCGPU_UNSUPPORTED;
+  }
+  const GroupKeys keys = group_keys_of(gplan);
+  const uint64_t n_in = f.n_in;
+  GroupSlot* d_table = f.at<GroupSlot>(w.o_table);
+  GroupControl* d_ctl = f.at<GroupControl>(w.o_ctl);
+  uint32_t *d_plane = f.at<uint32_t>(w.o_plane), *d_slot_group = f.at<uint32_t>(w.o_slot_group), *d_first = f.at<uint32_t>(w.o_blk_first),
+           *d_kept = f.at<uint32_t>(w.o_blk_kept), *d_hist = f.at<uint32_t>(w.o_hist), *d_seg = f.at<uint32_t>(w.o_seg);
+  uint32_t *d_keys[2] = {f.at<uint32_t>(w.o_keys[0]), f.at<uint32_t>(w.o_keys[1])}, *d_rows[2] = {f.at<uint32_t>(w.o_rows[0]), f.at<uint32_t>(w.o_rows[1])};
+  GroupKeyRecord* d_key_recs = f.at<GroupKeyRecord>(w.o_key_recs);
+  AggPartial* d_vals = f.at<AggPartial>(w.o_vals);
+  group_poison(f, gw);
+  if (const int rc = agg_upload(f, gw, insns, ops)) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(d_table, 0, w.table_bytes, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, sizeof(GroupControl), st));
+  hipLaunchKernelGGL(group_wide_assign_kernel, dim3(gw.blocks), dim3(256), 0, st, keys, rows, d_table, w.slots, gplan.max_groups, d_ctl, d_plane);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(group_wide_count_kernel, dim3(w.tiles), dim3(256), 0, st, rows, (const GroupSlot*)d_table, w.slots, (const uint32_t*)d_plane, d_first, d_kept);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(group_wide_scan_kernel, dim3(1), dim3(1024), 0, st, d_first, w.tiles, &d_ctl->n_groups, gplan.max_groups, &d_ctl->flags);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(group_wide_scan_kernel, dim3(1), dim3(1024), 0, st, d_kept, w.tiles, &d_ctl->kept, 0u, &d_ctl->flags);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(group_wide_number_kernel, dim3(w.tiles), dim3(256), 0, st, keys, rows, (const GroupSlot*)d_table, w.slots, w.cap, (const uint32_t*)d_plane,
+                     (const uint32_t*)d_first, (const uint32_t*)d_kept, d_ctl, d_slot_group, d_key_recs, d_rows[0]);
+  HIP_TRY(ctx, hipGetLastError());
+  const uint32_t flat = (uint32_t)std::min<uint64_t>((n_in + 255) / 256, 4096);  // the grid of the kernels that stride over the pairs
+  hipLaunchKernelGGL(group_wide_keys_kernel, dim3(flat), dim3(256), 0, st, (const uint32_t*)d_plane, (const uint32_t*)d_slot_group, w.slots, w.cap, n_in,
+                     (const GroupControl*)d_ctl, (const uint32_t*)d_rows[0], d_keys[0]);
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t at = 0;  // which of the two buffers holds the pairs
+  for (uint32_t pass = 0; pass < w.passes; pass++, at ^= 1) {
+    const uint32_t shift = pass * kGroupRadixBits;
+    hipLaunchKernelGGL(group_wide_hist_kernel, dim3(w.tiles), dim3(256), 0, st, (const uint32_t*)d_keys[at], shift, n_in, (const GroupControl*)d_ctl, d_hist);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(group_wide_scan_kernel, dim3(1), dim3(1024), 0, st, d_hist, w.tiles * 256u, (uint32_t*)nullptr, 0u, &d_ctl->flags);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(group_wide_scatter_kernel, dim3(w.tiles), dim3(256), 0, st, (const uint32_t*)d_keys[at], (const uint32_t*)d_rows[at], d_keys[at ^ 1],
+                       d_rows[at ^ 1], shift, n_in, (const GroupControl*)d_ctl, (const uint32_t*)d_hist);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(group_wide_segments_kernel, dim3(flat), dim3(256), 0, st, (const uint32_t*)d_keys[at], w.cap, n_in, (const GroupControl*)d_ctl, d_seg);
+  HIP_TRY(ctx, hipGetLastError());
+  {
+    // one wavefront a group, four a block: as many blocks as the records have room for groups, up to a grid that fills the device
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)w.cap + 3) / 4, 8192);
+    const AggInsn* d_insn = f.at<const AggInsn>(gw.o_insn);
+    hipLaunchKernelGGL(agg_group_wide_kernel, dim3(blocks, gw.n_insn), dim3(256), 0, st, d_insn, rows, (const uint32_t*)d_rows[at], (const uint32_t*)d_seg,
+                       (const GroupControl*)d_ctl, w.cap, d_vals);
+    HIP_TRY(ctx, hipGetLastError());
+    if (!ops.empty()) {
+      hipLaunchKernelGGL(agg_group_wide_expr_kernel, dim3(blocks, gw.n_insn), dim3(256), 0, st, d_insn, f.at<const AggExprOp>(gw.o_ops), rows, (const uint32_t*)d_rows[at],
+                         (const uint32_t*)d_seg, (const GroupControl*)d_ctl, w.cap, d_vals);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+  }
+  // ---- the first wait: the group count and the flags ----
+  GroupControl ctl;
+  HIP_TRY(ctx, hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  char err[256];
+  if (const int rc = orcgpu_host::group_check_flags(gplan, ctl.flags, ctl.n_groups, f.column_names, err, sizeof(err))) {
+    set_err(ctx, "%s", err);
+    return rc;
+  }
+  if (ctl.n_groups > w.cap) {  // (more groups than input rows: nothing is sized by such a count)
+    set_err(ctx, "group by: %u groups of %llu input rows", ctl.n_groups, (unsigned long long)n_in);
+    return ORCGPU_UNEXPECTED;
+  }
+  // ---- the second: exactly n_groups key records and n_groups x instructions value records ----
+  const uint32_t n = ctl.n_groups, nk = keys.n, ni = gw.n_insn;
+  set.keys.resize((size_t)n * nk);
+  set.vals.resize((size_t)n * ni);
+  if (!n) return ORCGPU_OK;
+  HIP_TRY(ctx, hipMemcpyAsync(set.keys.data(), d_key_recs, (size_t)n * nk * sizeof(GroupKeyRecord), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(set.vals.data(), d_vals, (size_t)n * ni * sizeof(AggPartial), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
   return ORCGPU_OK;
 }
 
@@ -222,7 +330,7 @@ int result_aggregate_call(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
   if (f.has_filter)
     if (const int rc = filter_run_eval(f, ws)) return rc;
   const KeptRows rows = filter_kept_rows(f, ws);
-  if (const int rc = gplan ? group_run(f, aw, rows, *gplan, insns, aplan.ops, set) : agg_run(f, aw, rows, insns, aplan.ops, set.vals.data())) return rc;
+  if (const int rc = gplan ? (orcgpu_host::group_is_wide(gplan->max_groups) ? group_run_wide : group_run)(f, aw, rows, *gplan, insns, aplan.ops, set) : agg_run(f, aw, rows, insns, aplan.ops, set.vals.data())) return rc;
   uint64_t total = 0;  // the last record of every group: its kept rows
   for (size_t k = set.n_insn - 1; k < set.vals.size(); k += set.n_insn) total += set.vals[k].w[0];
   if (total > f.n_in) {
@@ -270,15 +378,29 @@ extern "C" int orcgpu_result_aggregate_exprs(orcgpu_ctx* ctx, const orcgpu_resul
 extern "C" int orcgpu_result_aggregate_groups(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
                                               const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
                                               const orcgpu_agg_spec* specs, uint32_t n_specs, orcgpu_groups** out) {
-  return orcgpu_result_aggregate_groups_exprs(ctx, r, nodes, n_nodes, column_names, n_columns, key_columns, n_keys, specs, nullptr, n_specs, out);
+  return orcgpu_result_aggregate_groups_limit(ctx, r, nodes, n_nodes, column_names, n_columns, key_columns, n_keys, specs, nullptr, n_specs, 0, out);
 }
 extern "C" int orcgpu_result_aggregate_groups_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
                                                     const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
                                                     const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_groups** out) {
+  return orcgpu_result_aggregate_groups_limit(ctx, r, nodes, n_nodes, column_names, n_columns, key_columns, n_keys, specs, exprs, n_specs, 0, out);
+}
+extern "C" int orcgpu_result_aggregate_groups_limit(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                                    const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                                    const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, uint32_t max_groups,
+                                                    orcgpu_groups** out) {
   if (out) *out = nullptr;
   if (const int rc = result_aggregate_args(ctx, r, nodes, n_nodes, column_names, n_columns, out, "group by")) return rc;
   orcgpu_host::GroupPlan gplan;
   if (const int rc = result_compile_group(ctx, r, key_columns, n_keys, column_names, gplan)) return rc;
+  {
+    char err[256];
+    uint32_t total = 0;  // (one result: the total over stripes is not this call's; the highest keeps it out of the way)
+    if (const int rc = orcgpu_host::group_limits(max_groups, ORCGPU_GROUP_TOTAL_LIMIT_MAX, &gplan.max_groups, &total, err, sizeof(err))) {
+      set_err(ctx, "%s", err);
+      return rc;
+    }
+  }
   orcgpu_host::AggPlan aplan;
   if (const int rc = result_compile_aggs(ctx, r, specs, exprs, n_specs, column_names, aplan)) return rc;
   orcgpu_host::FilterPlan fplan;

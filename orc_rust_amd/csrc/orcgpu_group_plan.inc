@@ -2,7 +2,8 @@
 // this very text under AddressSanitizer + UBSan): the key list against the columns of a result -> what the kernels of
 // device/agg_group_kernels.hip hash and compare, with every refusal of orcgpu_result_aggregate_groups (include/orcgpu.h) decided
 // here; the merge of the stripes' groups by key tuple, in first-appearance order, with agg_merge per instruction; the cap on the
-// total; and the last step, the records -> the orcgpu_group_key and orcgpu_agg_value handed out.  Included behind
+// total; the limits of a GROUP BY and, for the wide path of device/agg_group_wide_kernels.hip, its table's slots, its sort's passes
+// and its workspace layout (tests/hostcheck/group_wide_check.cpp compiles those likewise); and the last step, the records -> the orcgpu_group_key and orcgpu_agg_value handed out.  Included behind
 // orcgpu_agg_plan.inc, whose AggCol says what a column is.
 #include <cstdlib>
 #include <string>
@@ -31,8 +32,83 @@ struct GroupKey {
 };
 struct GroupPlan {
   std::vector<GroupKey> keys;
+  uint32_t max_groups = ORCGPU_GROUP_MAX;       // the limits: groups of one result (above kGroupMax: the wide path) ...
+  uint32_t max_total = ORCGPU_GROUP_MAX_TOTAL;  // ... and over a reader's stripes (group_limits)
   char err[256] = {0};
 };
+
+// ---- the limits, and what the wide path (device/agg_group_wide_kernels.hip) is sized by: plain arithmetic ----
+static_assert(kGroupLimitMax == ORCGPU_GROUP_LIMIT_MAX && kGroupLimitMax <= ORCGPU_GROUP_TOTAL_LIMIT_MAX, "the limits of include/orcgpu.h");
+
+// The limits as given (0: the default) -> max_groups / max_total; ORCGPU_INVALID_ARGUMENT with a message for a value above its
+// maximum, and for a total below the limit of one result
+inline int group_limits(uint32_t max_groups, uint32_t max_total, uint32_t* out_groups, uint32_t* out_total, char* err, size_t err_len) {
+  const uint32_t g = max_groups ? max_groups : ORCGPU_GROUP_MAX, t = max_total ? max_total : ORCGPU_GROUP_MAX_TOTAL;
+  if (g > ORCGPU_GROUP_LIMIT_MAX) {
+    snprintf(err, err_len, "group by: a limit of %u groups in one result is above ORCGPU_GROUP_LIMIT_MAX (%u)", g, (unsigned)ORCGPU_GROUP_LIMIT_MAX);
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (t > ORCGPU_GROUP_TOTAL_LIMIT_MAX) {
+    snprintf(err, err_len, "group by: a limit of %u groups over the stripes is above ORCGPU_GROUP_TOTAL_LIMIT_MAX (%u)", t, (unsigned)ORCGPU_GROUP_TOTAL_LIMIT_MAX);
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (t < g) {
+    snprintf(err, err_len, "group by: a limit of %u groups over the stripes is below the limit of %u groups in one result", t, g);
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  *out_groups = g;
+  *out_total = t;
+  return ORCGPU_OK;
+}
+// Which path a call takes: the limit alone decides, never the data
+inline bool group_is_wide(uint32_t max_groups) { return max_groups > kGroupMax; }
+// The slots of the wide path's table: the power of two >= 4 x the limit (the narrow path's 1024 at 256)
+inline uint32_t group_wide_slots(uint32_t max_groups) {
+  uint32_t s = 4;
+  while (s < 4ull * max_groups) s <<= 1;
+  return s;
+}
+// The passes of its sort: kGroupRadixBits bits of the group number each, as many as the numbers below the limit hold
+inline uint32_t group_wide_passes(uint32_t max_groups) {
+  uint32_t bits = 0;
+  while ((1ull << bits) < max_groups) bits++;
+  const uint32_t p = (bits + kGroupRadixBits - 1) / kGroupRadixBits;
+  return p ? p : 1;
+}
+// Where its tables lie behind `base` (every offset aligned to kFilterAlign, in this order, none overlapping; bytes: the end).
+// tiles: the blocks of the kernels that take a tile each; cap: the groups the records have room for -- a result holds no more
+// groups than the limit allows, nor than it has input rows.  [o_ctl, + sizeof(GroupControl)) is what the first wait fetches;
+// the second fetches n_groups records from o_key_recs ([group][key]) and from o_vals ([group][instruction]).
+struct GroupWideLayout {
+  uint32_t slots = 0, passes = 0, tiles = 0, cap = 0;
+  uint64_t o_table = 0, table_bytes = 0, o_plane = 0, o_slot_group = 0, o_blk_first = 0, o_blk_kept = 0, o_keys[2] = {0, 0}, o_rows[2] = {0, 0}, o_hist = 0, o_seg = 0,
+           o_ctl = 0, o_key_recs = 0, o_vals = 0, bytes = 0;
+};
+inline GroupWideLayout group_wide_layout(uint64_t base, uint32_t max_groups, uint64_t n_in, uint32_t n_insn, uint32_t n_keys) {
+  GroupWideLayout w;
+  FilterBump t;
+  t.off = base;
+  const uint64_t padded = (n_in + 63) / 64 * 64, tiles = (n_in + kGroupWideTile - 1) / kGroupWideTile;
+  w.slots = group_wide_slots(max_groups);
+  w.passes = group_wide_passes(max_groups);
+  w.tiles = (uint32_t)(tiles ? tiles : 1);
+  w.cap = (uint32_t)(n_in < max_groups ? n_in : max_groups);
+  w.table_bytes = (uint64_t)w.slots * sizeof(GroupSlot);
+  w.o_table = t.take(w.table_bytes);
+  w.o_plane = t.take(padded * 4);
+  w.o_slot_group = t.take((uint64_t)w.slots * 4);
+  w.o_blk_first = t.take((uint64_t)w.tiles * 4);
+  w.o_blk_kept = t.take((uint64_t)w.tiles * 4);
+  for (int k = 0; k < 2; k++) w.o_keys[k] = t.take(padded * 4);
+  for (int k = 0; k < 2; k++) w.o_rows[k] = t.take(padded * 4);
+  w.o_hist = t.take((uint64_t)w.tiles * 256 * 4);
+  w.o_seg = t.take((uint64_t)w.cap * 4);
+  w.o_ctl = t.take(sizeof(GroupControl));
+  w.o_key_recs = t.take((uint64_t)w.cap * n_keys * sizeof(GroupKeyRecord));
+  w.o_vals = t.take((uint64_t)w.cap * n_insn * sizeof(AggPartial));
+  w.bytes = t.take(0);
+  return w;
+}
 
 // The key compiler: names / cols are the result's columns, as for agg_compile
 inline int group_compile(const char* const* key_columns, uint32_t n_keys, const char* const* names, const AggCol* cols, uint32_t n_columns, GroupPlan& out) {
@@ -121,19 +197,24 @@ inline std::string group_tuple(const GroupPlan& plan, const GroupKeyRecord* rec)
 
 // total <- total merged with the groups of a later stripe (its keys [group][key], vals [group][instruction], n groups): a key seen
 // before folds into its group with agg_merge, a new one goes behind the groups so far.  ORCGPU_UNSUPPORTED when the total
-// passes ORCGPU_GROUP_MAX_TOTAL; `total` is then no longer of use.
+// passes the plan's max_total (ORCGPU_GROUP_MAX_TOTAL unless it was set); `total` is then no longer of use.  Linear in the
+// groups offered: the index grows by doubling, so that a stripe of a million groups rehashes it once at the most.
 inline int group_merge(const GroupPlan& plan, const std::vector<AggInsn>& insns, GroupSet& total, const GroupKeyRecord* keys, const AggPartial* vals, uint32_t n,
                        char* err, size_t err_len) {
   const uint32_t nk = (uint32_t)plan.keys.size(), ni = (uint32_t)insns.size();
   total.n_keys = nk;
   total.n_insn = ni;
+  {
+    const size_t have = total.index.size(), want = have + n < plan.max_total ? have + n : (size_t)plan.max_total + 1;
+    if ((double)want > (double)total.index.bucket_count() * total.index.max_load_factor()) total.index.reserve(want > 2 * have ? want : 2 * have);
+  }
   for (uint32_t g = 0; g < n; g++) {
     const std::string tuple = group_tuple(plan, keys + (size_t)g * nk);
     auto it = total.index.find(tuple);
     if (it == total.index.end()) {
       const uint32_t at = total.n_groups();
-      if (at >= ORCGPU_GROUP_MAX_TOTAL) {
-        snprintf(err, err_len, "group by: more than ORCGPU_GROUP_MAX_TOTAL (%d) groups over the stripes", ORCGPU_GROUP_MAX_TOTAL);
+      if (at >= plan.max_total) {
+        snprintf(err, err_len, "group by: more than %u groups over the stripes (the limit set; ORCGPU_GROUP_MAX_TOTAL by default)", plan.max_total);
         return ORCGPU_UNSUPPORTED;
       }
       total.index.emplace(tuple, at);
@@ -179,8 +260,8 @@ inline void group_finish(const GroupPlan& plan, const std::vector<AggInsn>& insn
 
 // What the device's flags say of a result, or ORCGPU_OK: names are the result's columns
 inline int group_check_flags(const GroupPlan& plan, uint32_t flags, uint32_t n_groups, const char* const* names, char* err, size_t err_len) {
-  if ((flags & GROUP_TOO_MANY) || n_groups > kGroupMax) {
-    snprintf(err, err_len, "group by: more than ORCGPU_GROUP_MAX (%u) groups in one stripe", kGroupMax);
+  if ((flags & GROUP_TOO_MANY) || n_groups > plan.max_groups) {
+    snprintf(err, err_len, "group by: more than %u groups in one stripe (the limit set; ORCGPU_GROUP_MAX by default)", plan.max_groups);
     return ORCGPU_UNSUPPORTED;
   }
   for (size_t k = 0; k < plan.keys.size(); k++)

@@ -55,6 +55,7 @@ struct orcgpu_reader {
   // GROUP BY (orcgpu_reader_set_group_by): the key columns as given
   bool has_group = false;
   std::vector<std::string> group_keys;
+  uint32_t group_max = ORCGPU_GROUP_MAX, group_max_total = ORCGPU_GROUP_MAX_TOTAL;  // its limits (orcgpu_reader_set_group_limits)
   // device output (orcgpu_reader_set_device_output): the batches are views of the results' HBM, handed out by
   // orcgpu_reader_next_batch_device; no copy back is started.  A result the caller is done with goes to `home` instead of `spare`
   // -- at once, or when the last exported batch or tensor that views it is released (device_hold.h)
@@ -398,6 +399,8 @@ int reader_compile_group(orcgpu_reader* rd) {
   std::vector<AggCol> cols;
   reader_describe_roots(rd, names, cols);
   const int rc = group_compile(keys.data(), (uint32_t)keys.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->group_plan);
+  rd->group_plan.max_groups = rd->group_max;  // (what the merge refuses the total against, and the flags check the stripe)
+  rd->group_plan.max_total = rd->group_max_total;
   if (rc) set_err(rd->ctx, "%s", rd->group_plan.err);
   return rc;
 }
@@ -429,6 +432,8 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
   GroupPlan gplan;
   if (rd->has_group) {  // the grouped reduction in the same place: the stripe's groups stay with the result
     if (const int rc = result_compile_group(rd->ctx, res, keys.data(), (uint32_t)keys.size(), names.data(), gplan)) return rc;
+    gplan.max_groups = rd->group_max;  // (the limit picks the stripe's path: above ORCGPU_GROUP_MAX the wide one)
+    gplan.max_total = rd->group_max_total;
     for (size_t k = 0; k < gplan.keys.size(); k++)
       if (gplan.keys[k].kind != rd->group_plan.keys[k].kind || gplan.keys[k].scale_or_unit != rd->group_plan.keys[k].scale_or_unit) {
         set_err(rd->ctx, "group by: key column '%s' is not decoded to the type its key was planned for", names[gplan.keys[k].col]);

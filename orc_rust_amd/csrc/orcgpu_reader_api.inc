@@ -410,6 +410,13 @@ int orcgpu_reader_set_group_by(orcgpu_reader* rd, const char* const* key_columns
   rd->has_group = true;
   return ORCGPU_OK;
 }
+int orcgpu_reader_set_group_limits(orcgpu_reader* rd, uint32_t max_groups, uint32_t max_total) {
+  if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
+  char err[256];
+  const int rc = orcgpu_host::group_limits(max_groups, max_total, &rd->group_max, &rd->group_max_total, err, sizeof(err));  // (0: the default)
+  if (rc) set_err(rd->ctx, "%s", err);
+  return rc;
+}
 // Drains the reader: every stripe's groups, merged by key in stripe order, then the keys and the values
 int orcgpu_reader_aggregate_groups(orcgpu_reader* rd, orcgpu_groups** out) {
   if (out) *out = nullptr;
