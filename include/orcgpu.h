@@ -625,7 +625,8 @@ int orcgpu_reader_aggregate(orcgpu_reader* r, orcgpu_agg_value* out);
  * low-cardinality grouping, at most ORCGPU_GROUP_MAX groups in one result (one stripe) -- flags, statuses, dates, small codes;
  * a higher limit is opt-in (LIMITS below).
  *   - Kept rows and aggregates are what they are above: every op, column kind, refusal and overflow rule, applied per group.
- *     COUNT_ROWS of a group is its kept rows and never 0: a group exists only if a kept row has its key.
+ *     COUNT_ROWS of a group is its kept rows and never 0: a group exists only if a kept row has its key.  (An unconditioned
+ *     COUNT_ROWS: under a condition of its own -- FILTER (WHERE ...) below -- it may be 0.)
  *   - KEYS: 1 .. ORCGPU_GROUP_MAX_KEYS key columns, named like the aggregates' columns: projected root columns.  A column may be
  *     a key and an aggregated column.  Byte .. Long, Date (days) and Timestamp / Timestamp-instant decoded to an int64 unit are
  *     ORCGPU_GROUP_KEY_I64 (w[0], sign-extended into w[1]); Boolean is ORCGPU_GROUP_KEY_BOOL (w[0] = 0 / 1); Decimal is
@@ -775,6 +776,53 @@ int orcgpu_result_aggregate_groups_limit(orcgpu_ctx* ctx, const orcgpu_result* r
                                          const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, uint32_t max_groups,
                                          orcgpu_groups** out);
 int orcgpu_reader_set_group_limits(orcgpu_reader* r, uint32_t max_groups, uint32_t max_total);
+/* ---- FILTER (WHERE ...) per aggregate: several aggregates in one pass, each over its own subset of the kept rows ------------------
+ * TPC-H Q14 is sum(case when p_type like 'PROMO%' then l_extendedprice * (1 - l_discount) else 0 end) beside the same sum over
+ * every row; Q12 counts two priority classes side by side; every pivot is this shape.  In SQL: agg(x) FILTER (WHERE p), or
+ * agg(CASE WHEN p THEN x END).  An aggregate may carry a CONDITION, evaluated per row on the device (agg_cond_eval_kernel in
+ * device/agg_kernels.hip, with the row filter's own per-word evaluation) in front of the kernels that reduce.  The reference has no
+ * aggregation; the semantics are fixed here.
+ *   - A condition is a predicate in exactly the row filter's language (orcgpu_result_filter above): the same nodes in pre-order,
+ *     the same literal rules, the same three-valued logic, ORCGPU_FILTER_MAX_DEPTH per condition, and the same refusals with the
+ *     same statuses and messages (they begin "row filter:").  Its leaves name projected root columns.
+ *   - THE RULE: a conditioned aggregate is the same aggregate computed as if its argument were NULL in every kept row for which
+ *     the condition is not TRUE -- FALSE and UNKNOWN alike.  Everything else follows: COUNT_ROWS with a condition counts the kept
+ *     rows where it is TRUE, COUNT(c) those of them where c is not null; SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG and AVG_EXPR
+ *     skip the other rows exactly as they skip NULL values -- NULL over no passing value, AVG divides by the passing values, the
+ *     sticky overflow flag is set by passing rows only.
+ *   - The KEPT rows are what they were: row selection and row filter.  Conditions change neither them nor
+ *     orcgpu_reader_filter_rows, prune no row groups and change no stripe planning.  A GROUP exists iff a kept row has its key,
+ *     whatever the conditions say, and the order stays first appearance among the kept rows; a group in which no row passes an
+ *     aggregate's condition reports that aggregate as NULL, or 0 for the counts.  So "COUNT_ROWS of a group is never 0" (GROUP BY
+ *     above) holds for an unconditioned COUNT_ROWS only.
+ *   - DETERMINISM: a row that does not pass adds nothing to a Float / Double sum -- it is left out, it does not add +0.0 -- and the
+ *     shape of every reduction stays the function it was: the ungrouped grid of the input row count, the wide path's fold of the
+ *     group's kept-row count c and of every row's lane, a row that does not pass being a lane step that adds nothing.  The same
+ *     call gives the same bits.  Ungrouped, aggregate(a FILTER (WHERE p)) under the row filter f is, bit for bit, aggregate(a)
+ *     under f AND p.
+ *   - LIMITS: conditions that are node for node the same (op, children, column, literal kind and bytes) share one evaluation; at
+ *     most ORCGPU_AGG_MAX distinct conditions a list.  The device workspace holds one mask plane (one bit per input row) per
+ *     distinct condition; what cannot be had is the aggregation's out-of-memory status.  No further host wait.
+ *   - Not there: CASE with a non-NULL ELSE inside an arithmetic expression; conditions as pruning predicates.
+ * The entry points below are the ones above with a third array parallel to `specs`: filters[k] is the condition of specs[k],
+ * {NULL, 0} for none -- n_nodes = 0 is "none" at every entry point, whatever `nodes` holds; a count without nodes is
+ * ORCGPU_INVALID_ARGUMENT -- (filters = NULL: no spec has one -- this is what every entry point above calls; exprs may be NULL likewise).
+ * orcgpu_result_aggregate_groups_filters takes max_groups as orcgpu_result_aggregate_groups_limit does (0: ORCGPU_GROUP_MAX).
+ * orcgpu_reader_set_aggregate_filters is legal after orcgpu_reader_set_aggregates[_exprs] and before the first call; it copies
+ * nodes, names and literal bytes; n_specs must be the list's, else ORCGPU_INVALID_ARGUMENT and nothing changes; a later
+ * orcgpu_reader_set_aggregates[_exprs] drops the conditions with the list they belonged to. */
+typedef struct {
+  const orcgpu_predicate_node* nodes;  /* pre-order, as for orcgpu_result_filter */
+  uint32_t n_nodes;
+} orcgpu_agg_filter;
+int orcgpu_result_aggregate_filters(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                    const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs,
+                                    const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters, uint32_t n_specs, orcgpu_agg_value* out);
+int orcgpu_result_aggregate_groups_filters(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                           const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                           const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters,
+                                           uint32_t n_specs, uint32_t max_groups, orcgpu_groups** out);
+int orcgpu_reader_set_aggregate_filters(orcgpu_reader* r, const orcgpu_agg_filter* filters, uint32_t n_specs);
 uint32_t orcgpu_groups_count(const orcgpu_groups* g);
 int orcgpu_groups_key(const orcgpu_groups* g, uint32_t group, uint32_t key, orcgpu_group_key* out);
 int orcgpu_groups_value(const orcgpu_groups* g, uint32_t group, uint32_t spec, orcgpu_agg_value* out);

@@ -19,6 +19,8 @@ Pure plumbing: nothing is computed here, and every argument is checked before an
 import ctypes as C
 import decimal
 
+from .predicate import Predicate, PredicateNode
+
 COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG, AVG_EXPR = range(9)  # ORCGPU_AGG_OP_*
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(6)  # ORCGPU_AGG_EXPR_*
 PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
@@ -43,6 +45,10 @@ class AggExprNode(C.Structure):
 
 class AggExpr(C.Structure):
     _fields_ = [("nodes", C.POINTER(AggExprNode)), ("n_nodes", C.c_uint32)]
+
+
+class AggFilter(C.Structure):
+    _fields_ = [("nodes", C.POINTER(PredicateNode)), ("n_nodes", C.c_uint32)]
 
 
 class AggValue(C.Structure):
@@ -173,10 +179,20 @@ def lit(v):
 
 class Agg:
     """One aggregate: Agg.count_rows(), .count(c), .sum(c), .avg(c), .min(c), .max(c), .sum_product(a, b); sum and avg take a column
-    name or an Expr."""
+    name or an Expr.  .where(predicate) conditions any of them: agg(x) FILTER (WHERE predicate)."""
 
-    def __init__(self, op, column=None, column2=None, expr=None):
-        self.op, self.column, self.column2, self.expr = op, column, column2, expr
+    def __init__(self, op, column=None, column2=None, expr=None, filter=None):
+        self.op, self.column, self.column2, self.expr, self.filter = op, column, column2, expr, filter
+
+    def where(self, predicate):
+        """A new Agg over the kept rows for which `predicate` (a orc_rust_amd.predicate.Predicate over projected root columns, in
+        the row filter's language) is TRUE: SQL's agg(x) FILTER (WHERE predicate), i.e. agg(CASE WHEN predicate THEN x END).  One
+        condition an aggregate: combine several with Predicate.and_ first."""
+        if not isinstance(predicate, Predicate):
+            raise TypeError("Agg.where: a Predicate, not %s" % type(predicate).__name__)
+        if self.filter is not None:
+            raise ValueError("Agg.where: %r has a condition already; combine the two with Predicate.and_([...])" % (self,))
+        return Agg(self.op, self.column, self.column2, self.expr, predicate)
 
     @classmethod
     def count_rows(cls):
@@ -211,7 +227,8 @@ class Agg:
         return cls(SUM_PRODUCT, _column("Agg.sum_product", column), _column("Agg.sum_product", column2))
 
     def __repr__(self):
-        return "Agg.%s(%s)" % (_NAMES[self.op], ", ".join(repr(c) for c in (self.column, self.column2, self.expr) if c is not None))
+        text = "Agg.%s(%s)" % (_NAMES[self.op], ", ".join(repr(c) for c in (self.column, self.column2, self.expr) if c is not None))
+        return text if self.filter is None else "%s.where(%r)" % (text, self.filter)
 
 
 class TimestampValue(int):
@@ -303,6 +320,24 @@ def expr_array(specs):
         if s.expr is None:
             continue
         nodes, alive = s.expr.flatten()
+        keep.append((nodes, alive))
+        arr[i].nodes = nodes
+        arr[i].n_nodes = len(nodes)
+    return arr, keep
+
+
+def filter_array(specs):
+    """[Agg] -> (ctypes array of orcgpu_agg_filter parallel to spec_array's, what keeps its nodes alive), or (None, []) when no
+    spec has a condition: the bindings then call the entry points without conditions."""
+    specs = check_specs(specs)
+    if not any(s.filter is not None for s in specs):
+        return None, []
+    arr = (AggFilter * len(specs))()
+    keep = []
+    for i, s in enumerate(specs):
+        if s.filter is None:
+            continue
+        nodes, alive = s.filter.flatten()
         keep.append((nodes, alive))
         arr[i].nodes = nodes
         arr[i].n_nodes = len(nodes)

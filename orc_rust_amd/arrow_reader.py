@@ -145,7 +145,7 @@ class ArrowReaderBuilder:
         return self
 
     def aggregate(self, specs, raw=False, group_by=None, max_groups=None, max_total_groups=None):
-        """COUNT, SUM, AVG, MIN, MAX, SUM(a * b) and SUM / AVG of an arithmetic expression (aggregate.col / aggregate.lit) over the rows the builder's selection and row filter keep, reduced on the GPU
+        """COUNT, SUM, AVG, MIN, MAX, SUM(a * b) and SUM / AVG of an arithmetic expression (aggregate.col / aggregate.lit) over the rows the builder's selection and row filter keep -- each aggregate over its own subset of them when it carries a condition (Agg.where) --, reduced on the GPU
         (orcgpu_reader_set_aggregates / orcgpu_reader_aggregate): specs is a list of orc_rust_amd.aggregate.Agg, the result a list
         of int (counts, integer results; a Timestamp's with `.units`), decimal.Decimal, float, or None for NULL.  Builds the reader
         and drains it: every stripe is decoded and aggregated where it lies, no batch is copied back.  The projection must hold the
@@ -173,6 +173,9 @@ class ArrowReaderBuilder:
             self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregates(self._h, arr, len(arr)))
         else:
             self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregate_exprs(self._h, arr, exprs, len(arr)))
+        filters, keep_f = A.filter_array(specs)
+        if filters is not None:
+            self._ctx._check(self._ctx.L.orcgpu_reader_set_aggregate_filters(self._h, filters, len(arr)))
         if keys is not None:
             self._ctx._check(self._ctx.L.orcgpu_reader_set_group_by(self._h, keys, len(keys)))
         if max_groups or max_total_groups:

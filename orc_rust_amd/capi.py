@@ -31,6 +31,7 @@ EXPORTS = [
     "orcgpu_groups_value", "orcgpu_groups_free",
     "orcgpu_result_aggregate_exprs", "orcgpu_result_aggregate_groups_exprs", "orcgpu_reader_set_aggregate_exprs",
     "orcgpu_result_aggregate_groups_limit", "orcgpu_reader_set_group_limits",
+    "orcgpu_result_aggregate_filters", "orcgpu_result_aggregate_groups_filters", "orcgpu_reader_set_aggregate_filters",
     "orcgpu_reader_total_rows", "orcgpu_reader_stripe_count", "orcgpu_reader_column_count", "orcgpu_reader_column_name",
     "orcgpu_reader_next_batch",
     "orcgpu_result_dictionary_view", "orcgpu_result_copy_dictionary", "orcgpu_reader_set_dictionary_columns",
@@ -233,6 +234,13 @@ def load():
                                                        C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32, C.c_uint32,
                                                        C.POINTER(C.c_void_p)]
     L.orcgpu_reader_set_group_limits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    from .aggregate import AggFilter
+    L.orcgpu_result_aggregate_filters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                  C.POINTER(AggSpec), C.POINTER(AggExpr), C.POINTER(AggFilter), C.c_uint32, C.POINTER(AggValue)]
+    L.orcgpu_result_aggregate_groups_filters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                                         C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.POINTER(AggExpr), C.POINTER(AggFilter),
+                                                         C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_set_aggregate_filters.argtypes = [C.c_void_p, C.POINTER(AggFilter), C.c_uint32]
     L.orcgpu_reader_aggregate_groups.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.orcgpu_groups_count.restype = C.c_uint32
     L.orcgpu_groups_count.argtypes = [C.c_void_p]
@@ -468,22 +476,25 @@ class Context:
     @staticmethod
     def _aggregate_args(specs, column_names, predicate):
         """What both result_aggregate* calls marshal alike: (the predicate's and the names' arguments, the specs' -- with the
-        expressions or None in the middle --, what has to stay alive over the call)"""
+        expressions or None and the conditions or None in the middle --, what has to stay alive over the call)"""
         from . import aggregate as A
         arr, keep = A.spec_array(specs)
         exprs, keep_e = A.expr_array(specs)
+        filters, keep_f = A.filter_array(specs)
         nodes, keep_p = predicate.flatten() if predicate is not None else (None, None)
         names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
-        return (nodes, len(nodes) if nodes is not None else 0, names, len(column_names)), (arr, exprs, len(arr)), (keep, keep_e, keep_p)
+        return (nodes, len(nodes) if nodes is not None else 0, names, len(column_names)), (arr, exprs, filters, len(arr)), (keep, keep_e, keep_f, keep_p)
 
     def result_aggregate(self, result, specs, column_names, predicate=None, raw=False):
         """orcgpu_result_aggregate: the aggregates `specs` (a list of orc_rust_amd.aggregate.Agg) over the rows of a decoded,
         selected or filtered Result that `predicate` keeps (None: all of them); column_names[i] names the result's column i.  The
         result is left as it was.  Returns the Python values (aggregate.value_of); raw=True: the orcgpu_agg_value records."""
         from . import aggregate as A
-        rows, (arr, exprs, n), keep = self._aggregate_args(specs, column_names, predicate)
+        rows, (arr, exprs, filters, n), keep = self._aggregate_args(specs, column_names, predicate)
         out = (A.AggValue * n)()
-        if exprs is None:
+        if filters is not None:
+            self._check(self.L.orcgpu_result_aggregate_filters(self.h, result.h, *rows, arr, exprs, filters, n, out))
+        elif exprs is None:
             self._check(self.L.orcgpu_result_aggregate(self.h, result.h, *rows, arr, n, out))
         else:
             self._check(self.L.orcgpu_result_aggregate_exprs(self.h, result.h, *rows, arr, exprs, n, out))
@@ -496,10 +507,12 @@ class Context:
         wide path runs."""
         from . import aggregate as A
         max_groups, _ = A.check_group_limits(max_groups, None if max_groups is None else A.GROUP_TOTAL_LIMIT_MAX, group_by)  # (one result: no total)
-        rows, (arr, exprs, n), keep = self._aggregate_args(specs, column_names, predicate)
+        rows, (arr, exprs, filters, n), keep = self._aggregate_args(specs, column_names, predicate)
         keys = A.key_array(group_by)
         out = C.c_void_p()
-        if max_groups:
+        if filters is not None:
+            self._check(self.L.orcgpu_result_aggregate_groups_filters(self.h, result.h, *rows, keys, len(keys), arr, exprs, filters, n, max_groups, C.byref(out)))
+        elif max_groups:
             self._check(self.L.orcgpu_result_aggregate_groups_limit(self.h, result.h, *rows, keys, len(keys), arr, exprs, n, max_groups, C.byref(out)))
         elif exprs is None:
             self._check(self.L.orcgpu_result_aggregate_groups(self.h, result.h, *rows, keys, len(keys), arr, n, C.byref(out)))

@@ -220,8 +220,11 @@ group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, Group
 // partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's
 // entries are trusted no further than a slot index below kGroupSlots, the numbers of slot_group no further than a group below
 // kGroupMax: whatever a refused table left in them, every LDS and global address stays in bounds.
-// Resource usage (gfx950): agg_group_partial_kernel 68 VGPRs, 102 SGPRs; agg_group_expr_partial_kernel 72 VGPRs, 102 SGPRs; both no scratch, no
-// spill, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.
+// Resource usage (gfx950): agg_group_partial_kernel 70 VGPRs, 106 SGPRs; agg_group_expr_partial_kernel 74 VGPRs, 106 SGPRs; both no scratch, no
+// spill of either register kind, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.  (The condition's word is ONE scalar load
+// a trip, cond[w]: a lane's bit of its own word, loaded per lane, cost two and four scalar registers spilled to VGPR lanes.)
+// A kept row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane that holds the empty contribution: it
+// keeps its group, its rank and its place in the tree or the rounds, so the condition never changes which shape runs.
 // (The body of two kernels: EXPR = false is agg_group_partial_kernel, which takes the plain kinds and leaves the AK_EXPR_* rows of
 // grid.y at once; EXPR = true is agg_group_expr_partial_kernel, the other way round, launched only when the list holds such an
 // instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.)
@@ -240,6 +243,8 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
   const FilterCol c = cols[EXPR ? 0 : in.col], c2 = cols[EXPR ? 0 : in.col2];  // (EXPR: col / col2 are no column indexes; unused)
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const AggAcc zero = {0, 0, 0, 0.0, 0, 0};
+  bool blocked;
+  const unsigned long long* const cond = agg_cond_plane(rows, in.cond, &blocked);
   AggAcc* const acc = acc_s[wave];
   for (uint32_t g = lane; g < kGroupMax; g += 64) acc[g] = zero;
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -256,7 +261,9 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
       if (g >= n_groups) g = kGroupNoSlot;
     }
     const bool kept = g != kGroupNoSlot;
-    if (kept) {
+    // (a row its instruction's condition does not pass keeps the empty contribution and its place in the fold below)
+    const unsigned long long pass_m = blocked ? 0ull : cond ? cond[w] : ~0ull;  // (the word's rows that pass: one scalar load a word)
+    if (kept && ((pass_m >> lane) & 1)) {
       if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
       else if (kind == AK_COUNT_ROWS) v.w0 = 1;
       else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, v);

@@ -294,8 +294,11 @@ group_wide_segments_kernel(const uint32_t* keys, uint32_t cap, uint64_t n_in, co
 }
 
 // out: [group][instruction], n_insn = gridDim.y records a group.  The fold rule of the head comment.
-// Resource usage (gfx950): agg_group_wide_kernel 48 VGPRs, 94 SGPRs; agg_group_wide_expr_kernel 72 VGPRs, 94 SGPRs; both no scratch,
-// no spill, no LDS: occupancy 8 and 7 waves / SIMD, by registers alone.
+// Resource usage (gfx950): agg_group_wide_kernel 46 VGPRs, 102 SGPRs; agg_group_wide_expr_kernel 72 VGPRs, 102 SGPRs; both no scratch,
+// no spill, no LDS: occupancy 7 waves / SIMD, by registers alone -- the plain kernel by its scalar registers: the condition's plane
+// (a pointer and the count of planes beside the rows) took it from 94 past the 100 that eight waves allow.
+// A row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane step that adds nothing: start, end, c and
+// every row's lane stay those of the fold rule.  COUNT_ROWS under a condition counts the passing rows, lane by lane.
 // (The body of two kernels, as agg_group_partial_body is: EXPR = false takes the plain kinds, EXPR = true the AK_EXPR_* rows of grid.y.)
 template <bool EXPR>
 __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* order_rows, const uint32_t* seg,
@@ -311,16 +314,23 @@ __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const 
   const bool is_max = in.is_max != 0;
   const FilterCol c = cols[EXPR ? 0 : in.col], c2 = cols[EXPR ? 0 : in.col2];  // (EXPR: col / col2 are no column indexes; unused)
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool blocked;
+  const unsigned long long* const cond = agg_cond_plane(rows, in.cond, &blocked);
+  if (blocked) return;  // (uniform over the block; the host has refused such a plan before any launch)
   for (uint64_t g = (uint64_t)blockIdx.x * 4 + wave; g < n_groups; g += (uint64_t)gridDim.x * 4) {
     const uint32_t start = seg[g], end = g + 1 < n_groups ? seg[g + 1] : n;
     AggAcc a = {0, 0, 0, 0.0, 0, 0};
     if (start <= end && end <= n) {  // (what the sort leaves; anything else folds to the empty record)
-      if (!EXPR && kind == AK_COUNT_ROWS) {
+      if (!EXPR && kind == AK_COUNT_ROWS && !cond) {
         if (lane == 0) a.w0 = end - start;
       } else {
         for (uint32_t p = start + lane; p < end; p += 64) {
           const uint32_t j = order_rows[p];
-          if (j >= n_in) continue;
+          if (j >= n_in || !agg_row_passes(cond, j)) continue;  // (a row that does not pass: a lane step that adds nothing)
+          if (!EXPR && kind == AK_COUNT_ROWS) {
+            a.w0++;
+            continue;
+          }
           if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, a);
           else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, a);
         }

@@ -16,6 +16,11 @@
 //                        registers are not the plain kinds'; each of the two kernels leaves the other's rows of grid.y at once.
 //                        The two are one body, agg_partial_body<EXPR>; the rows they walk arrive as one argument (KeptRows).
 //
+//   agg_cond_eval_kernel     in front of all of them when an aggregate carries a condition (AggInsn::cond, agg(x) FILTER (WHERE ...)):
+//                        one mask plane per distinct condition, laid out like the keep mask, = the rows that are kept AND for which
+//                        the condition is TRUE, evaluated by the row filter's own per-word evaluation (filter_eval_word).  A
+//                        conditioned instruction reduces its plane where the others reduce the keep mask.
+//
 // Integer and Decimal sums travel as three 64-bit words with explicit carries -- wide enough for every partial sum, so the
 // order of summation cannot show.  Float sums take whatever the fixed shape gives: the grid is a function of the input row
 // count alone (agg_program.h), there is no atomic anywhere, and so the same call gives the same bits.
@@ -25,6 +30,7 @@
 #include "agg_expr_eval.h"
 #include "agg_program.h"
 #include "filter_access.h"
+#include "filter_kernels.hip"
 #include "filter_program.h"
 
 struct AggAcc {
@@ -233,6 +239,42 @@ __device__ __forceinline__ unsigned long long agg_keep_word(const KeptRows& rows
   return rows.keep ? rows.keep[w] : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
 }
 
+// The plane of an instruction's condition (cond = k + 1: plane k, which agg_cond_eval_kernel left as "kept, and the condition is
+// TRUE"), found once per kernel: null without a condition.  *blocked: a plane past those of the call -- the host refuses such a
+// plan before any launch (agg_plan_in_bounds); here no row passes and nothing is loaded.
+__device__ __forceinline__ const unsigned long long* agg_cond_plane(const KeptRows& rows, uint32_t cond, bool* blocked) {
+  *blocked = cond > rows.n_cond;
+  return cond && !*blocked ? rows.cond + (uint64_t)(cond - 1) * ((rows.n_in + 63) / 64) : nullptr;
+}
+// Does the kept input row j (below n_in) pass?  What the grouped kernels ask per row
+__device__ __forceinline__ bool agg_row_passes(const unsigned long long* plane, uint64_t j) { return !plane || ((plane[j >> 6] >> (j & 63)) & 1); }
+
+// The planes of an aggregate list's distinct conditions, in front of the partial kernels on their stream.  grid (blocks over the
+// words as filter_eval_kernel's, conditions): blockIdx.y = condition k, whose program is prog[spans[k].first, + spans[k].n) of the
+// call's predicate program (the row filter's instructions, then the conditions'; a span that leaves it evaluates to no row).
+// out[k][w] = TRUE-word of condition k & keep word: EVERY word of every plane is written on every call, a word whose keep word
+// is 0 as 0 without a row being loaded.  The LIKE / IN leaves of the conditions find their match bits in leaf_planes, where
+// filter_like_kernel / filter_in_kernel left them.
+extern "C" __global__ void __launch_bounds__(256)
+agg_cond_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const AggCondSpan* spans, const uint8_t* lits, KeptRows rows, const unsigned long long* leaf_planes,
+                     unsigned long long* out) {
+  __shared__ unsigned long long stk_t[4][kFilterStack], stk_f[4][kFilterStack];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  AggCondSpan span = spans[blockIdx.y];
+  if (span.first > n_insn || span.n > n_insn - span.first) span.n = 0;
+  const FilterWords ws = filter_words(rows.n_in);
+  unsigned long long* plane = out + (uint64_t)blockIdx.y * ws.n;
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const unsigned long long m = agg_keep_word(rows, w);
+    unsigned long long pass = 0;
+    if (m && span.n) {  // (uniform over the wavefront)
+      const FilterRow r = filter_row(rows, w * 64 + lane);
+      pass = filter_eval_word(prog + span.first, span.n, lits, rows.cols, r, __ballot(r.live), rows.B, rows.W, leaf_planes, ws.n, w, stk_t[wave], stk_f[wave]) & m;
+    }
+    if (lane == 0) plane[w] = pass;
+  }
+}
+
 // partials: [instruction][block].  A lane whose row is not kept loads nothing; a kept row is an input row below n_in, and the
 // row-access layer turns it into a row of the stripe: every load lies where the decode wrote.
 // (The body of two kernels: EXPR = false is agg_partial_kernel, which takes the plain kinds and leaves the AK_EXPR_* rows of grid.y
@@ -247,9 +289,11 @@ __device__ __forceinline__ void agg_partial_body(const AggInsn* insns, const Agg
   const FilterCol c = rows.cols[EXPR ? 0 : in.col], c2 = rows.cols[EXPR ? 0 : in.col2];  // (EXPR: unused)
   const uint32_t lane = threadIdx.x & 63;
   const FilterWords ws = filter_words(rows.n_in);
+  bool blocked;
+  const unsigned long long* const plane = agg_cond_plane(rows, in.cond, &blocked);
   AggAcc a = {0, 0, 0, 0.0, 0, 0};
-  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
-    const unsigned long long m = agg_keep_word(rows, w);
+  for (uint64_t w = blocked ? ws.n : ws.first; w < ws.n; w += ws.stride) {
+    const unsigned long long m = plane ? plane[w] : agg_keep_word(rows, w);  // (a row its condition does not pass is a row that is not kept)
     if (!m) continue;
     if (!EXPR && kind == AK_COUNT_ROWS) {  // (the word's popcount, once: lane 0's share)
       if (lane == 0) a.w0 += (unsigned long long)__builtin_popcountll(m);

@@ -62,7 +62,12 @@ struct AggInsn {
   uint32_t fkind;    // FKIND_* of `col` as the decode left it
   uint32_t op;       // ORCGPU_AGG_* as given
   int32_t scale;     // Decimal results: the scale; Timestamp MIN / MAX: the unit
-  uint32_t pad;
+  uint32_t cond;     // 0: every kept row; k + 1: the kept rows of condition plane k (KeptRows::cond) -- agg(x) FILTER (WHERE ...)
+};
+// Where the program of one distinct condition lies in the call's predicate program (FilterInsn, filter_program.h): what
+// agg_cond_eval_kernel evaluates into plane blockIdx.y
+struct AggCondSpan {
+  uint32_t first, n;
 };
 
 // A partial result, and the final one: `count` values went into it (0: NULL for everything but the counts, which live in w[0]).

@@ -56,7 +56,8 @@ __device__ __forceinline__ FilterWords filter_words(uint64_t n_in) {
 
 // The rows a kernel walks, as ONE kernel argument passed by value (the aggregation's kernels; the host builds it once per call):
 // the columns, the input rows' segments, and the keep mask filter_eval_kernel left -- one word per 64 input rows; null: no filter,
-// every input row is kept
+// every input row is kept.  Behind it the planes of the aggregates' conditions (agg_cond_eval_kernel): n_cond of them, each laid
+// out like `keep`, plane k at cond + k * ceil(n_in / 64) -- bit = the row is kept and condition k is TRUE for it; none: null, 0
 struct KeptRows {
   const FilterCol* cols;
   const SelBatch* segs;
@@ -65,6 +66,8 @@ struct KeptRows {
   uint64_t n_in;
   uint32_t B, W;
   const unsigned long long* keep;
+  const unsigned long long* cond;
+  uint32_t n_cond;
 };
 __device__ __forceinline__ FilterRow filter_row(const KeptRows& rows, uint64_t j) {
   return filter_row(rows.segs, rows.seg_first, rows.n_segs, rows.n_in, rows.B, j);

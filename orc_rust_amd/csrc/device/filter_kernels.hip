@@ -9,6 +9,8 @@
 //                         a per-wavefront stack with wave-uniform code.  Writes keep = T_root & live and its popcount.
 //                         A Decimal leaf compares the row's 16 bytes with a literal the host has brought to the column's scale,
 //                         a Timestamp leaf is the integer leaf on a literal in the column's unit: no row is ever rescaled.
+//                         The evaluation of one word is filter_eval_word, which the aggregates' conditions run too
+//                         (agg_cond_eval_kernel, agg_kernels.hip).
 //   filter_like_kernel    runs in front of it when the program holds LIKE leaves: per leaf a plane of match bits, one word per
 //                         64 input rows like `keep`; the evaluation forms T = match & valid, F = ~match & valid from it.  The
 //                         compiled pattern (parts of literal bytes and `_` marks between the `%`) lies in LDS; no backtracking;
@@ -309,6 +311,121 @@ filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves
   }
 }
 
+// One 64-row word of a predicate: the program prog[0, n_insn) over the trip's rows -- lane l holds input row w * 64 + l as `r`,
+// live_m = the ballot of r.live --, evaluated as the head comment says: a leaf yields two ballot words, inner nodes combine words on
+// the wavefront's own stack (stk_t / stk_f: kFilterStack words each, in LDS).  Returns the rows where the root is TRUE, live rows
+// only.  planes: the LIKE / IN leaves' match bits, n_words words a plane.  What filter_eval_kernel runs for the row filter and
+// agg_cond_eval_kernel (agg_kernels.hip) for an aggregate's condition.
+__device__ __forceinline__ unsigned long long filter_eval_word(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const FilterRow& r,
+                                                               unsigned long long live_m, uint32_t B, uint32_t W, const unsigned long long* planes, uint64_t n_words,
+                                                               uint64_t w, unsigned long long* stk_t, unsigned long long* stk_f) {
+  uint32_t sp = 0;
+  for (uint32_t k = 0; k < n_insn; k++) {
+    const FilterInsn in = prog[k];
+    unsigned long long T = 0, F = 0;
+    if (in.op <= FOP_IS_NOT_NULL) {
+      const FilterCol c = cols[in.col];
+      const bool valid = r.live && filter_valid(c, r.u, r.l, W);
+      bool t = false, f = false;
+      if (in.op == FOP_IS_NULL) {
+        t = r.live && !valid;
+        f = valid;
+      } else if (in.op == FOP_IS_NOT_NULL) {
+        t = valid;
+        f = r.live && !valid;
+      } else if (valid) {
+        bool lt = false, eq = false, gt = false;
+        if (in.op == FOP_CMP_INT || in.op == FOP_CMP_BOOL) {
+          const long long v = in.op == FOP_CMP_INT ? filter_load_i64(c, r.row) : (long long)filter_load_bit(c, r.u, r.l, W);
+          lt = v < in.i;
+          eq = v == in.i;
+          gt = v > in.i;
+        } else if (in.op == FOP_CMP_FLOAT) {
+          const double v = filter_load_f64(c, r.row);
+          lt = v < in.f;
+          eq = v == in.f;
+          gt = v > in.f;
+        } else if (in.op == FOP_CMP_DEC128) {  // the high words as signed, the low words as unsigned
+          unsigned long long vl, hi;
+          filter_load_dec128(c, r.row, &vl, &hi);
+          const long long vh = (long long)hi;
+          eq = vh == in.i && vl == in.lo;
+          lt = vh < in.i || (vh == in.i && vl < in.lo);
+          gt = !lt && !eq;
+        } else {  // FOP_CMP_STRING
+          const FilterStr v = filter_value_str(c, r.u, r.l, B);
+          const uint8_t* q = lits + in.lit_off;
+          const uint32_t m = v.len < in.lit_len ? v.len : in.lit_len;
+          uint32_t x = 0;
+          while (x < m && v.p[x] == q[x]) x++;
+          if (x < m) {
+            lt = v.p[x] < q[x];
+            gt = !lt;
+          } else {
+            lt = v.len < in.lit_len;
+            eq = v.len == in.lit_len;
+            gt = v.len > in.lit_len;
+          }
+        }
+        switch (in.cmp) {
+          case 0: t = eq; break;         // EQ
+          case 1: t = !eq; break;        // NE (true with a NaN on either side)
+          case 2: t = lt; break;         // LT
+          case 3: t = lt || eq; break;   // LE
+          case 4: t = gt; break;         // GT
+          default: t = gt || eq; break;  // GE
+        }
+        f = !t;
+      }
+      T = __ballot(t);
+      F = __ballot(f);
+    } else if (in.op == FOP_LIKE) {
+      // the trip's match bits are there already (filter_like_kernel); only `%`: every valid row, and no plane to load
+      const unsigned long long valid_m = __ballot(r.live && filter_valid(cols[in.col], r.u, r.l, W));
+      const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : planes[(uint64_t)in.i * n_words + w];
+      T = match & valid_m;
+      F = ~match & valid_m;
+    } else if (in.op == FOP_IN) {
+      // the trip's membership bits are there already (filter_in_kernel); a Boolean column and a list no key of which can equal a
+      // row have no plane.  With a NULL literal in the list a row that matches no key is UNKNOWN, not FALSE.
+      const FilterCol c = cols[in.col];
+      const bool valid = r.live && filter_valid(c, r.u, r.l, W);
+      const unsigned long long valid_m = __ballot(valid);
+      unsigned long long match = 0;
+      if (!(in.cmp & IN_NO_TABLE)) match = planes[(uint64_t)in.i * n_words + w];
+      else if (in.cmp & (IN_BOOL_FALSE | IN_BOOL_TRUE)) {
+        const unsigned long long bits = __ballot(valid && filter_load_bit(c, r.u, r.l, W));
+        match = (in.cmp & IN_BOOL_TRUE ? bits : 0ull) | (in.cmp & IN_BOOL_FALSE ? ~bits : 0ull);
+      }
+      T = match & valid_m;
+      F = in.cmp & IN_HAS_NULL ? 0ull : ~match & valid_m;
+    } else if (in.op == FOP_TRUE) {
+      T = live_m;
+    } else if (in.op == FOP_FALSE) {
+      F = live_m;
+    } else if (in.op == FOP_NOT) {
+      sp--;
+      T = stk_f[sp];
+      F = stk_t[sp];
+    } else if (in.op == FOP_AND || in.op == FOP_OR) {
+      sp -= 2;
+      const unsigned long long t1 = stk_t[sp], f1 = stk_f[sp], t2 = stk_t[sp + 1], f2 = stk_f[sp + 1];
+      if (in.op == FOP_AND) {
+        T = t1 & t2;
+        F = f1 | f2;
+      } else {
+        T = t1 | t2;
+        F = f1 & f2;
+      }
+    }  // (FOP_UNKNOWN: neither)
+    // (every lane holds the same words and writes them to the same slot: the wavefront's stack needs no barrier)
+    stk_t[sp] = T;
+    stk_f[sp] = F;
+    sp++;
+  }
+  return (sp ? stk_t[0] : 0ull) & live_m;
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
                    const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* keep,
@@ -318,112 +435,7 @@ filter_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const uint8_t* lits,
   const FilterWords ws = filter_words(n_in);
   for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
     const FilterRow r = filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane);
-    const unsigned long long live_m = __ballot(r.live);
-    uint32_t sp = 0;
-    for (uint32_t k = 0; k < n_insn; k++) {
-      const FilterInsn in = prog[k];
-      unsigned long long T = 0, F = 0;
-      if (in.op <= FOP_IS_NOT_NULL) {
-        const FilterCol c = cols[in.col];
-        const bool valid = r.live && filter_valid(c, r.u, r.l, W);
-        bool t = false, f = false;
-        if (in.op == FOP_IS_NULL) {
-          t = r.live && !valid;
-          f = valid;
-        } else if (in.op == FOP_IS_NOT_NULL) {
-          t = valid;
-          f = r.live && !valid;
-        } else if (valid) {
-          bool lt = false, eq = false, gt = false;
-          if (in.op == FOP_CMP_INT || in.op == FOP_CMP_BOOL) {
-            const long long v = in.op == FOP_CMP_INT ? filter_load_i64(c, r.row) : (long long)filter_load_bit(c, r.u, r.l, W);
-            lt = v < in.i;
-            eq = v == in.i;
-            gt = v > in.i;
-          } else if (in.op == FOP_CMP_FLOAT) {
-            const double v = filter_load_f64(c, r.row);
-            lt = v < in.f;
-            eq = v == in.f;
-            gt = v > in.f;
-          } else if (in.op == FOP_CMP_DEC128) {  // the high words as signed, the low words as unsigned
-            unsigned long long vl, hi;
-            filter_load_dec128(c, r.row, &vl, &hi);
-            const long long vh = (long long)hi;
-            eq = vh == in.i && vl == in.lo;
-            lt = vh < in.i || (vh == in.i && vl < in.lo);
-            gt = !lt && !eq;
-          } else {  // FOP_CMP_STRING
-            const FilterStr v = filter_value_str(c, r.u, r.l, B);
-            const uint8_t* q = lits + in.lit_off;
-            const uint32_t m = v.len < in.lit_len ? v.len : in.lit_len;
-            uint32_t x = 0;
-            while (x < m && v.p[x] == q[x]) x++;
-            if (x < m) {
-              lt = v.p[x] < q[x];
-              gt = !lt;
-            } else {
-              lt = v.len < in.lit_len;
-              eq = v.len == in.lit_len;
-              gt = v.len > in.lit_len;
-            }
-          }
-          switch (in.cmp) {
-            case 0: t = eq; break;         // EQ
-            case 1: t = !eq; break;        // NE (true with a NaN on either side)
-            case 2: t = lt; break;         // LT
-            case 3: t = lt || eq; break;   // LE
-            case 4: t = gt; break;         // GT
-            default: t = gt || eq; break;  // GE
-          }
-          f = !t;
-        }
-        T = __ballot(t);
-        F = __ballot(f);
-      } else if (in.op == FOP_LIKE) {
-        // the trip's match bits are there already (filter_like_kernel); only `%`: every valid row, and no plane to load
-        const unsigned long long valid_m = __ballot(r.live && filter_valid(cols[in.col], r.u, r.l, W));
-        const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : planes[(uint64_t)in.i * ws.n + w];
-        T = match & valid_m;
-        F = ~match & valid_m;
-      } else if (in.op == FOP_IN) {
-        // the trip's membership bits are there already (filter_in_kernel); a Boolean column and a list no key of which can equal a
-        // row have no plane.  With a NULL literal in the list a row that matches no key is UNKNOWN, not FALSE.
-        const FilterCol c = cols[in.col];
-        const bool valid = r.live && filter_valid(c, r.u, r.l, W);
-        const unsigned long long valid_m = __ballot(valid);
-        unsigned long long match = 0;
-        if (!(in.cmp & IN_NO_TABLE)) match = planes[(uint64_t)in.i * ws.n + w];
-        else if (in.cmp & (IN_BOOL_FALSE | IN_BOOL_TRUE)) {
-          const unsigned long long bits = __ballot(valid && filter_load_bit(c, r.u, r.l, W));
-          match = (in.cmp & IN_BOOL_TRUE ? bits : 0ull) | (in.cmp & IN_BOOL_FALSE ? ~bits : 0ull);
-        }
-        T = match & valid_m;
-        F = in.cmp & IN_HAS_NULL ? 0ull : ~match & valid_m;
-      } else if (in.op == FOP_TRUE) {
-        T = live_m;
-      } else if (in.op == FOP_FALSE) {
-        F = live_m;
-      } else if (in.op == FOP_NOT) {
-        sp--;
-        T = stk_f[wave][sp];
-        F = stk_t[wave][sp];
-      } else if (in.op == FOP_AND || in.op == FOP_OR) {
-        sp -= 2;
-        const unsigned long long t1 = stk_t[wave][sp], f1 = stk_f[wave][sp], t2 = stk_t[wave][sp + 1], f2 = stk_f[wave][sp + 1];
-        if (in.op == FOP_AND) {
-          T = t1 & t2;
-          F = f1 | f2;
-        } else {
-          T = t1 | t2;
-          F = f1 & f2;
-        }
-      }  // (FOP_UNKNOWN: neither)
-      // (every lane holds the same words and writes them to the same slot: the wavefront's stack needs no barrier)
-      stk_t[wave][sp] = T;
-      stk_f[wave][sp] = F;
-      sp++;
-    }
-    const unsigned long long root = (sp ? stk_t[wave][0] : 0ull) & live_m;
+    const unsigned long long root = filter_eval_word(prog, n_insn, lits, cols, r, __ballot(r.live), B, W, planes, ws.n, w, stk_t[wave], stk_f[wave]);
     if (lane == 0) {
       keep[w] = root;
       cnt[w] = (uint32_t)__builtin_popcountll(root);

@@ -19,6 +19,11 @@
 // (agg_upload); agg_expr_partial_kernel / agg_group_expr_partial_kernel reduce them behind the plain partial kernel, into the same
 // records, and are launched only when the list holds such an instruction (agg_launch_partials).  The six kernels that walk rows
 // take them as one argument, KeptRows (filter_kept_rows).
+//
+// Aggregates with a condition (FILTER (WHERE ...): AggPlan::conds) bring their programs behind the row filter's in ONE predicate
+// program (filter_plan_append), so that the filter's workspace, upload, kind check and plane kernels serve them as they are;
+// agg_cond_eval_kernel then leaves one mask plane per distinct condition behind the keep mask and in front of the partial
+// kernels, on the call's stream (agg_run_conds).  No further wait.
 #include "orcgpu_agg_plan.inc"
 #include "orcgpu_group_plan.inc"
 namespace {
@@ -28,15 +33,22 @@ namespace {
 // records [instruction][kGroupMax], and [o_table, o_table + zero_bytes) is zeroed on the stream before every call
 struct AggWorkspace {
   uint32_t n_insn = 0, n_keys = 0, blocks = 0;  // instructions (the aggregates, then the kept row count); the partial kernel's blocks along x
+  uint32_t n_conds = 0;  // distinct conditions: their spans in the predicate program, and a plane of ceil(n_in / 64) words each
+  uint64_t o_spans = 0, o_cond = 0;
   uint64_t o_insn = 0, o_ops = 0, o_table = 0, zero_bytes = 0, o_plane = 0, o_slot_group = 0, o_part = 0, o_back = 0, back_keys = 0, back_vals = 0, back_bytes = 0, bytes = 0;
   orcgpu_host::GroupWideLayout wide;  // the wide path's tables instead (group_wide_layout), behind the instructions and the op table
-  AggWorkspace(uint64_t filter_bytes, uint32_t n_specs, const orcgpu_host::GroupPlan* gplan, uint64_t n_in, size_t n_ops) {
+  AggWorkspace(uint64_t filter_bytes, uint32_t n_specs, const orcgpu_host::GroupPlan* gplan, uint64_t n_in, size_t n_ops, size_t n_conds_ = 0) {
     FilterBump t;
     t.off = filter_bytes;
     n_insn = n_specs + 1;
+    n_conds = (uint32_t)n_conds_;
     blocks = gplan ? agg_group_blocks(n_in) : agg_blocks(n_in);
     o_insn = t.take((uint64_t)n_insn * sizeof(AggInsn) + 16);
     o_ops = t.take((uint64_t)n_ops * sizeof(AggExprOp) + 16);
+    if (n_conds) {
+      o_spans = t.take((uint64_t)n_conds * sizeof(AggCondSpan) + 16);
+      o_cond = t.take((uint64_t)n_conds * ((n_in + 63) / 64) * 8 + 16);
+    }
     if (gplan && orcgpu_host::group_is_wide(gplan->max_groups)) {
       n_keys = (uint32_t)gplan->keys.size();
       blocks = agg_blocks(n_in);
@@ -61,22 +73,8 @@ struct AggWorkspace {
   }
 };
 
-// Do the instructions read what is there?  A column index below nc; a program inside the op table whose every op names a column
-// below nc.  (The plan was compiled against these columns: anything else is a caller's mix-up.)
-bool agg_plan_in_bounds(const std::vector<AggInsn>& insns, const std::vector<AggExprOp>& ops, uint32_t nc) {
-  for (const AggInsn& in : insns) {
-    if (in.kind == AK_COUNT_ROWS) continue;
-    if (!agg_is_expr(in.kind)) {
-      if (in.kind >= AK_N || in.col >= nc || in.col2 >= nc) return false;
-      continue;
-    }
-    if (in.col > ops.size() || in.col2 > ops.size() - in.col || !in.col2) return false;
-    for (uint32_t k = in.col; k < in.col + in.col2; k++)
-      if (ops[k].op >= AX_N || (ops[k].op <= AX_PUSH_F64 && ops[k].col >= nc)) return false;
-  }
-  return true;
-}
-// ... and the keys: a column of the result, by name too, decoded to the kind the key was planned for
+// Do the keys read what is there (the instructions: agg_plan_in_bounds, orcgpu_agg_plan.inc)?  A column of the result, by name
+// too, decoded to the kind the key was planned for
 bool group_plan_in_bounds(const orcgpu_host::GroupPlan& gplan, const FilterCall& f) {
   for (const orcgpu_host::GroupKey& k : gplan.keys)
     if (k.col >= f.nc || k.col >= f.n_names || f.fcols[k.col].kind != k.fkind) return false;
@@ -95,10 +93,10 @@ std::vector<orcgpu_host::AggCol> result_agg_cols(const orcgpu_result* r) {
   return cols;
 }
 // The plan of an aggregate list against a decoded result's columns
-int result_compile_aggs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs,
-                        const char* const* column_names, orcgpu_host::AggPlan& plan) {
+int result_compile_aggs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters,
+                        uint32_t n_specs, const char* const* column_names, orcgpu_host::AggPlan& plan) {
   const std::vector<orcgpu_host::AggCol> cols = result_agg_cols(r);
-  const int rc = orcgpu_host::agg_compile(specs, exprs, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan);
+  const int rc = orcgpu_host::agg_compile(specs, exprs, filters, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan);
   if (rc) set_err(ctx, "%s", plan.err);
   return rc;
 }
@@ -147,6 +145,21 @@ int agg_run(const FilterCall& f, const AggWorkspace& aw, const KeptRows& rows, c
   return ORCGPU_OK;
 }
 
+// The planes of the list's distinct conditions, behind the keep mask and in front of the partial kernels: the spans go up (where
+// each condition's program lies in the call's predicate program, `first` instructions in), agg_cond_eval_kernel writes every word
+// of every plane
+int agg_run_conds(const FilterCall& f, const FilterWorkspace& ws, const AggWorkspace& aw, const orcgpu_host::AggPlan& aplan, uint32_t first, const KeptRows& rows) {
+  std::vector<AggCondSpan> spans = aplan.cond_spans;
+  for (AggCondSpan& sp : spans) sp.first += first;
+  HIP_TRY(f.ctx, f.ctx->upload(f.X + aw.o_spans, spans.data(), spans.size() * sizeof(AggCondSpan), f.ctx->stream));
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((ws.n_words + 3) / 4, 16384);
+  hipLaunchKernelGGL(agg_cond_eval_kernel, dim3(blocks, aw.n_conds), dim3(256), 0, f.ctx->stream, f.at<const FilterInsn>(ws.o_prog), (uint32_t)f.plan.prog.size(),
+                     f.at<const AggCondSpan>(aw.o_spans), f.at<const uint8_t>(ws.o_lits), rows, f.at<const unsigned long long>(ws.o_planes),
+                     f.at<unsigned long long>(aw.o_cond));
+  HIP_TRY(f.ctx, hipGetLastError());
+  return ORCGPU_OK;
+}
+
 // The key list as the kernels take it; ORCGPU_GROUP_HASH_BITS is read per call
 GroupKeys group_keys_of(const orcgpu_host::GroupPlan& gplan) {
   GroupKeys keys{};
@@ -158,9 +171,9 @@ GroupKeys group_keys_of(const orcgpu_host::GroupPlan& gplan) {
   }
   return keys;
 }
-// ORCGPU_POISON, the debugging aid of the decode, over the aggregation's tables of either path: nothing may depend on what the
-// workspace held before.  (A failure to fill is not the call's failure.)
-void group_poison(const FilterCall& f, const AggWorkspace& gw) {
+// ORCGPU_POISON, the debugging aid of the decode, over the aggregation's tables of every path, in front of everything the call
+// enqueues: nothing may depend on what the workspace held before.  (A failure to fill is not the call's failure.)
+void agg_poison(const FilterCall& f, const AggWorkspace& gw) {
   static const char* poison = getenv("ORCGPU_POISON");
   if (poison && *poison) (void)hipMemsetAsync(f.X + gw.o_insn, (int)strtol(poison, nullptr, 0) & 0xFF, gw.bytes - gw.o_insn, f.ctx->stream);
 }
@@ -176,7 +189,6 @@ int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows,
   GroupControl* d_ctl = f.at<GroupControl>(gw.o_back);
   uint32_t *d_plane = f.at<uint32_t>(gw.o_plane), *d_slot_group = f.at<uint32_t>(gw.o_slot_group);
   AggPartial *d_part = f.at<AggPartial>(gw.o_part), *d_out = f.at<AggPartial>(gw.o_back + gw.back_vals);
-  group_poison(f, gw);
   if (const int rc = agg_upload(f, gw, insns, ops)) return rc;
   HIP_TRY(ctx, hipMemsetAsync(d_table, 0, gw.zero_bytes, st));
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, gw.back_bytes, st));
@@ -229,7 +241,6 @@ int group_run_wide(const FilterCall& f, const AggWorkspace& gw, const KeptRows& 
   uint32_t *d_keys[2] = {f.at<uint32_t>(w.o_keys[0]), f.at<uint32_t>(w.o_keys[1])}, *d_rows[2] = {f.at<uint32_t>(w.o_rows[0]), f.at<uint32_t>(w.o_rows[1])};
   GroupKeyRecord* d_key_recs = f.at<GroupKeyRecord>(w.o_key_recs);
   AggPartial* d_vals = f.at<AggPartial>(w.o_vals);
-  group_poison(f, gw);
   if (const int rc = agg_upload(f, gw, insns, ops)) return rc;
   HIP_TRY(ctx, hipMemsetAsync(d_table, 0, w.table_bytes, st));
   HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, sizeof(GroupControl), st));
@@ -314,22 +325,39 @@ int result_aggregate_call(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu
   if (rows_seen) *rows_seen = 0;
   if (rows_kept) *rows_kept = 0;
   if (r->status) return r->status;
-  FilterCall f{ctx, r, fplan ? *fplan : no_filter, column_names, n_names, fplan != nullptr};
+  // the call's predicate program: the row filter's, and behind it the programs of the aggregates' conditions
+  const size_t n_conds = aplan.cond_spans.size();
+  const orcgpu_host::FilterPlan* const row_plan = fplan ? fplan : &no_filter;
+  orcgpu_host::FilterPlan both;
+  uint32_t cond_first = 0;
+  if (n_conds) {
+    if (fplan) both = *fplan;
+    cond_first = orcgpu_host::filter_plan_append(both, aplan.conds);
+  }
+  const orcgpu_host::FilterPlan* const program = n_conds ? &both : row_plan;
+  FilterCall f{ctx, r, *program, column_names, n_names, fplan != nullptr, fplan ? (uint32_t)fplan->prog.size() : 0u};
   if (const int rc = filter_open(f, rows_seen)) return rc;
   const FilterWorkspace ws = filter_workspace(f);
-  const AggWorkspace aw(ws.bytes, (uint32_t)aplan.insns.size(), gplan, f.n_in, aplan.ops.size());
+  const AggWorkspace aw(ws.bytes, (uint32_t)aplan.insns.size(), gplan, f.n_in, aplan.ops.size(), n_conds);
   if (const int rc = filter_reserve(f, ws, aw.bytes, gplan ? "the grouped aggregation" : "the aggregation")) return rc;
   std::vector<AggInsn> insns = aplan.insns;
-  if (!agg_plan_in_bounds(insns, aplan.ops, f.nc)) return ORCGPU_UNEXPECTED;
+  if (!orcgpu_host::agg_plan_in_bounds(insns, aplan.ops, f.nc, (uint32_t)n_conds) || !orcgpu_host::agg_conds_in_bounds(aplan.cond_spans, cond_first, f.plan.prog.size()))
+    return ORCGPU_UNEXPECTED;
   if (gplan && !group_plan_in_bounds(*gplan, f)) return ORCGPU_UNEXPECTED;
   AggInsn kept{};
   kept.kind = AK_COUNT_ROWS;
   insns.push_back(kept);
   if (!f.n_in) return ORCGPU_OK;  // (no input row: every record is the empty one; no group)
+  agg_poison(f, aw);
   if (const int rc = filter_upload(f, ws)) return rc;
-  if (f.has_filter)
+  if (f.has_filter || n_conds)
     if (const int rc = filter_run_eval(f, ws)) return rc;
-  const KeptRows rows = filter_kept_rows(f, ws);
+  KeptRows rows = filter_kept_rows(f, ws);
+  if (n_conds) {
+    if (const int rc = agg_run_conds(f, ws, aw, aplan, cond_first, rows)) return rc;
+    rows.cond = f.at<const unsigned long long>(aw.o_cond);
+    rows.n_cond = aw.n_conds;
+  }
   if (const int rc = gplan ? (orcgpu_host::group_is_wide(gplan->max_groups) ? group_run_wide : group_run)(f, aw, rows, *gplan, insns, aplan.ops, set) : agg_run(f, aw, rows, insns, aplan.ops, set.vals.data())) return rc;
   uint64_t total = 0;  // the last record of every group: its kept rows
   for (size_t k = set.n_insn - 1; k < set.vals.size(); k += set.n_insn) total += set.vals[k].w[0];
@@ -363,9 +391,14 @@ extern "C" int orcgpu_result_aggregate(orcgpu_ctx* ctx, const orcgpu_result* r, 
 extern "C" int orcgpu_result_aggregate_exprs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
                                              const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs,
                                              const orcgpu_agg_expr* exprs, uint32_t n_specs, orcgpu_agg_value* out) {
+  return orcgpu_result_aggregate_filters(ctx, r, nodes, n_nodes, column_names, n_columns, specs, exprs, nullptr, n_specs, out);
+}
+extern "C" int orcgpu_result_aggregate_filters(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                               const char* const* column_names, uint32_t n_columns, const orcgpu_agg_spec* specs,
+                                               const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters, uint32_t n_specs, orcgpu_agg_value* out) {
   if (const int rc = result_aggregate_args(ctx, r, nodes, n_nodes, column_names, n_columns, out, "aggregate")) return rc;
   orcgpu_host::AggPlan aplan;
-  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, n_specs, column_names, aplan)) return rc;
+  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, filters, n_specs, column_names, aplan)) return rc;
   orcgpu_host::FilterPlan fplan;
   if (n_nodes)
     if (const int rc = result_compile_filter(ctx, r, nodes, n_nodes, column_names, fplan)) return rc;
@@ -389,6 +422,12 @@ extern "C" int orcgpu_result_aggregate_groups_limit(orcgpu_ctx* ctx, const orcgp
                                                     const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
                                                     const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, uint32_t max_groups,
                                                     orcgpu_groups** out) {
+  return orcgpu_result_aggregate_groups_filters(ctx, r, nodes, n_nodes, column_names, n_columns, key_columns, n_keys, specs, exprs, nullptr, n_specs, max_groups, out);
+}
+extern "C" int orcgpu_result_aggregate_groups_filters(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                                                      const char* const* column_names, uint32_t n_columns, const char* const* key_columns, uint32_t n_keys,
+                                                      const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters,
+                                                      uint32_t n_specs, uint32_t max_groups, orcgpu_groups** out) {
   if (out) *out = nullptr;
   if (const int rc = result_aggregate_args(ctx, r, nodes, n_nodes, column_names, n_columns, out, "group by")) return rc;
   orcgpu_host::GroupPlan gplan;
@@ -402,7 +441,7 @@ extern "C" int orcgpu_result_aggregate_groups_limit(orcgpu_ctx* ctx, const orcgp
     }
   }
   orcgpu_host::AggPlan aplan;
-  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, n_specs, column_names, aplan)) return rc;
+  if (const int rc = result_compile_aggs(ctx, r, specs, exprs, filters, n_specs, column_names, aplan)) return rc;
   orcgpu_host::FilterPlan fplan;
   if (n_nodes)
     if (const int rc = result_compile_filter(ctx, r, nodes, n_nodes, column_names, fplan)) return rc;

@@ -4,6 +4,9 @@
 // orcgpu_result_aggregate (include/orcgpu.h) decided here; the merge of two partial records, which is what the kernels do and what
 // the file reader does with its stripes' records; and the last step, a record -> the orcgpu_agg_value handed out, with the range
 // checks.  Included behind orcgpu_filter_host.inc, whose FilterColDesc and filter_col_kind say what a decoded column is.
+// An aggregate's condition (orcgpu_agg_filter: agg(x) FILTER (WHERE ...)) is a predicate in the row filter's language and is
+// compiled by the row filter's compiler (orcgpu_filter_plan.inc) against the same columns: agg_compile_conds, tested by
+// tests/hostcheck/agg_filter_plan_check.cpp.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -24,6 +27,10 @@ struct AggCol {
 struct AggPlan {
   std::vector<AggInsn> insns;
   std::vector<AggExprOp> ops;  // the programs of the AK_EXPR_* instructions, one behind the other (insn.col: first op, insn.col2: ops)
+  // the DISTINCT conditions of the list: their programs one behind the other in one plan (filter_plan_append), and where each
+  // lies; insn.cond = k + 1 names cond_spans[k], whose plane agg_cond_eval_kernel fills
+  FilterPlan conds;
+  std::vector<AggCondSpan> cond_spans;
   char err[256] = {0};
 };
 
@@ -145,13 +152,112 @@ struct AggCompiler {
   }
 };
 
-inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns,
-                       AggPlan& out) {
+// Are two conditions the same, node for node: op, children, column, literal kind and bytes?
+inline bool agg_cond_nodes_equal(const orcgpu_agg_filter& a, const orcgpu_agg_filter& b) {
+  if (a.n_nodes != b.n_nodes) return false;
+  for (uint32_t k = 0; k < a.n_nodes; k++) {
+    const orcgpu_predicate_node &x = a.nodes[k], &y = b.nodes[k];
+    if (x.op != y.op || x.n_children != y.n_children || x.value_type != y.value_type || (x.value_is_null != 0) != (y.value_is_null != 0) || x.i != y.i ||
+        memcmp(&x.f, &y.f, sizeof(double)) != 0 || x.s_len != y.s_len || !x.column != !y.column || !x.s != !y.s)
+      return false;
+    if (x.column && strcmp(x.column, y.column) != 0) return false;
+    if (x.s && x.s_len && memcmp(x.s, y.s, (size_t)x.s_len) != 0) return false;
+  }
+  return true;
+}
+
+// The conditions of a list, filters[0 .. n) parallel to its specs ({NULL, 0}: the spec has none) -> out.conds / out.cond_spans and
+// cond_of[s] = 0 or k + 1 for spec s (n_nodes = 0: none).  Every condition is compiled by filter_compile against the columns the aggregates were
+// compiled against -- the row filter's nodes, literal rules, depth limit, statuses and messages --; conditions that are node for
+// node the same share one program and one plane; more than ORCGPU_AGG_MAX distinct ones are ORCGPU_INVALID_ARGUMENT.  A condition
+// that reads the values of a column read as a dictionary column is ORCGPU_UNSUPPORTED, as under the row filter.
+inline int agg_compile_conds(const orcgpu_agg_filter* filters, uint32_t n, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out,
+                             std::vector<uint32_t>& cond_of) {
+  out.conds = FilterPlan{};
+  out.cond_spans.clear();
+  cond_of.assign(n, 0);
+  if (!filters) return ORCGPU_OK;
+  std::vector<int32_t> kinds(n_columns), params(n_columns);
+  for (uint32_t c = 0; c < n_columns; c++) {
+    kinds[c] = cols[c].d.orc_type;
+    params[c] = kinds[c] == ORCGPU_T_DECIMAL ? (int32_t)cols[c].scale : cols[c].d.ts_unit;
+  }
+  std::vector<uint32_t> first_spec;  // per distinct condition: the spec that brought it
+  for (uint32_t s = 0; s < n; s++) {
+    const orcgpu_agg_filter& f = filters[s];
+    if (!f.n_nodes) continue;  // (no condition, whatever `nodes` holds: what orcgpu_reader_set_aggregate_filters takes it for too)
+    if (!f.nodes) {
+      snprintf(out.err, sizeof(out.err), "aggregate: the condition of aggregate %u has a node count and no nodes", s);
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+    uint32_t k = 0;
+    while (k < first_spec.size() && !agg_cond_nodes_equal(filters[first_spec[k]], f)) k++;
+    if (k == first_spec.size()) {
+      if (k == ORCGPU_AGG_MAX) {
+        snprintf(out.err, sizeof(out.err), "aggregate: more than ORCGPU_AGG_MAX (64) distinct conditions");
+        return ORCGPU_INVALID_ARGUMENT;
+      }
+      FilterPlan one;
+      if (const int rc = filter_compile(f.nodes, f.n_nodes, names, kinds.data(), n_columns, one, params.data())) {
+        memcpy(out.err, one.err, sizeof(out.err));
+        return rc;
+      }
+      for (const FilterInsn& in : one.prog)
+        if (fop_reads_values(in.op) && in.col < n_columns && cols[in.col].d.dict_out) {
+          filter_dict_refusal(out.err, sizeof(out.err), names[in.col] ? names[in.col] : "", in.col);
+          return ORCGPU_UNSUPPORTED;
+        }
+      const uint32_t first = filter_plan_append(out.conds, one);
+      out.cond_spans.push_back(AggCondSpan{first, (uint32_t)one.prog.size()});
+      first_spec.push_back(s);
+    }
+    cond_of[s] = k + 1;
+  }
+  return ORCGPU_OK;
+}
+
+// filters: parallel to specs like exprs, or null when no spec has a condition
+inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters, uint32_t n_specs, const char* const* names,
+                       const AggCol* cols, uint32_t n_columns, AggPlan& out) {
   out.insns.clear();
   out.ops.clear();
+  out.conds = FilterPlan{};
+  out.cond_spans.clear();
   out.err[0] = 0;
   AggCompiler c{names, cols, n_columns, out};
-  return c.compile(specs, exprs, n_specs);
+  if (const int rc = c.compile(specs, exprs, n_specs)) return rc;
+  std::vector<uint32_t> cond_of;  // (one instruction per spec: an AVG is its sum, finished over the count)
+  if (const int rc = agg_compile_conds(filters, n_specs, names, cols, n_columns, out, cond_of)) return rc;
+  for (uint32_t s = 0; s < n_specs; s++) out.insns[s].cond = cond_of[s];
+  return ORCGPU_OK;
+}
+inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns,
+                       AggPlan& out) {
+  return agg_compile(specs, exprs, nullptr, n_specs, names, cols, n_columns, out);
+}
+
+// Do the instructions read what is there?  A column index below nc; a program inside the op table whose every op names a column
+// below nc; a condition among the n_conds planes of the call.  (The plan was compiled against these columns: anything else is a
+// caller's mix-up, ORCGPU_UNEXPECTED before any launch.)
+inline bool agg_plan_in_bounds(const std::vector<AggInsn>& insns, const std::vector<AggExprOp>& ops, uint32_t nc, uint32_t n_conds = 0) {
+  for (const AggInsn& in : insns) {
+    if (in.cond > n_conds) return false;
+    if (in.kind == AK_COUNT_ROWS) continue;
+    if (!agg_is_expr(in.kind)) {
+      if (in.kind >= AK_N || in.col >= nc || in.col2 >= nc) return false;
+      continue;
+    }
+    if (in.col > ops.size() || in.col2 > ops.size() - in.col || !in.col2) return false;
+    for (uint32_t k = in.col; k < in.col + in.col2; k++)
+      if (ops[k].op >= AX_N || (ops[k].op <= AX_PUSH_F64 && ops[k].col >= nc)) return false;
+  }
+  return true;
+}
+// ... and the conditions' programs: inside the n_insn instructions of the call's predicate program, from `first` on
+inline bool agg_conds_in_bounds(const std::vector<AggCondSpan>& spans, uint32_t first, size_t n_insn) {
+  for (const AggCondSpan& sp : spans)
+    if (!sp.n || (uint64_t)first + sp.first + sp.n > n_insn) return false;
+  return true;
 }
 inline int agg_compile(const orcgpu_agg_spec* specs, uint32_t n_specs, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out) {
   return agg_compile(specs, nullptr, n_specs, names, cols, n_columns, out);

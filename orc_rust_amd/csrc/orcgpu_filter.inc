@@ -26,7 +26,10 @@ struct FilterCall {
   const orcgpu_host::FilterPlan& plan;
   const char* const* column_names;  // the result's columns, for the messages (null: none)
   uint32_t n_names;
-  bool has_filter = true;  // false: an aggregation without a predicate -- `plan` is the empty one, nothing is evaluated
+  bool has_filter = true;  // false: an aggregation without a predicate -- `plan` holds no row filter, no keep mask is evaluated
+  // the row filter's instructions in front of plan.prog (~0: all of it).  An aggregation whose aggregates carry conditions lays
+  // their programs behind them (filter_plan_append): the plane kernels serve the whole program, filter_eval_kernel runs this front
+  uint32_t n_row_insn = ~0u;
   uint32_t nc = 0, B = 0, W = 0, src_batches = 0;  // (src_batches: uniform batches of the decode)
   std::vector<SelBatch> segs;       // the input rows: those of a row selection's batches (none: the stripe's) ...
   std::vector<uint64_t> seg_first;  // ... and the input row each starts at
@@ -114,8 +117,9 @@ int filter_check(FilterCall& f) {
   uint32_t col = 0;
   const int rc = filter_check_kinds(f.plan, kinds.data(), f.descs.data(), f.nc, &col);
   if (rc == ORCGPU_UNSUPPORTED) {
-    if (column_names && col < n_names) set_err(f.ctx, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", column_names[col]);
-    else set_err(f.ctx, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", f.r->cols[col].column_id);
+    char err[256];
+    filter_dict_refusal(err, sizeof(err), column_names && col < n_names ? column_names[col] : nullptr, f.r->cols[col].column_id);
+    set_err(f.ctx, "%s", err);
   } else if (rc) set_err(f.ctx, "row filter: column %u is not decoded to the type its comparison needs", col < f.nc ? f.r->cols[col].column_id : col);
   return rc;
 }
@@ -143,7 +147,8 @@ int filter_upload(FilterCall& f, const FilterWorkspace& ws) {
 }
 
 // Plane kernels -> evaluate: the keep mask (one word per 64 input rows) and its popcounts, and nothing after them -- what the
-// filter compacts from and the aggregation reduces from
+// filter compacts from and the aggregation reduces from.  (No row filter -- an aggregation with conditions only: the plane kernels
+// alone.)
 int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
   orcgpu_ctx* ctx = f.ctx;
   hipStream_t st = ctx->stream;
@@ -168,8 +173,9 @@ int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
                        d_planes, n_planes);
     HIP_TRY(ctx, hipGetLastError());
   }
-  hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, d_prog, n_insn, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W, d_keep,
-                     f.at<uint32_t>(ws.o_cnt), d_planes);
+  if (!f.has_filter) return ORCGPU_OK;
+  hipLaunchKernelGGL(filter_eval_kernel, dim3(eval_blocks), dim3(256), 0, st, d_prog, std::min(n_insn, f.n_row_insn), d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B,
+                     f.W, d_keep, f.at<uint32_t>(ws.o_cnt), d_planes);
   HIP_TRY(ctx, hipGetLastError());
   return ORCGPU_OK;
 }
@@ -302,7 +308,7 @@ int filter_reserve(FilterCall& f, const FilterWorkspace& ws, uint64_t bytes, con
   f.X = f.r->filt_tmp.p;
   f.host.assign(ws.up_bytes, 0);
   filter_fill_cols(f, ws);
-  return f.has_filter ? filter_check(f) : ORCGPU_OK;
+  return f.plan.prog.empty() ? ORCGPU_OK : filter_check(f);
 }
 
 // The rows an aggregation's kernels walk: the kernel argument, once per call

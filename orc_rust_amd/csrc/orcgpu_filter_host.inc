@@ -52,6 +52,14 @@ inline uint32_t filter_col_kind(const FilterColDesc& d) {
   return (is_int && d.width <= 8) || is_ts ? FKIND_INT : (is_float && (d.width == 4 || d.width == 8) ? FKIND_FLOAT : (is_dec ? FKIND_DEC128 : FKIND_OTHER));
 }
 
+// The one text of the dictionary-column refusal, for whoever finds it: the call's check against a decoded result (filter_check,
+// orcgpu_filter.inc) and the plan compiler of the aggregates' conditions (agg_compile_conds, orcgpu_agg_plan.inc).  name: the
+// column's, or null where only its id is known.
+inline void filter_dict_refusal(char* out, size_t n, const char* name, uint32_t column_id) {
+  if (name) snprintf(out, n, "row filter: column '%s' is read as a dictionary column: a comparison on its keys is not supported", name);
+  else snprintf(out, n, "row filter: column %u is read as a dictionary column: a comparison on its keys is not supported", column_id);
+}
+
 // The plan was compiled against the columns' types; what the decode made of them must fit.  ORCGPU_OK, or for the first
 // instruction that does not fit: ORCGPU_UNSUPPORTED (it reads the values of a dictionary-output column: string predicates evaluated
 // on the entries are not there yet) or ORCGPU_MISMATCHED_SCHEMA (no such column, or not decoded to the kind it compares), with

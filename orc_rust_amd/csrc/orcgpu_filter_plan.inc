@@ -452,4 +452,26 @@ inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, 
   return ORCGPU_OK;
 }
 
+// `from`, a plan compiled on its own against the same columns, behind `into`: its instructions behind into's, its literals behind
+// into's from an 8-byte boundary (what the IN tables and the LIKE patterns are aligned to), its mask planes numbered behind
+// into's, its leaves in into's leaf lists -- so that one literal pool, one launch of filter_like_kernel and one of filter_in_kernel
+// serve both.  Returns the index of its first instruction.  This is how the conditions of an aggregate list (orcgpu_agg_plan.inc)
+// share a program with each other and, at the call, with the row filter.
+inline uint32_t filter_plan_append(FilterPlan& into, const FilterPlan& from) {
+  const uint32_t first = (uint32_t)into.prog.size();
+  const long long planes = (long long)into.n_planes();
+  while (into.lits.size() & 7) into.lits.push_back(0);
+  const unsigned long long lit0 = into.lits.size();
+  into.lits.insert(into.lits.end(), from.lits.begin(), from.lits.end());
+  for (FilterInsn in : from.prog) {
+    if (in.op == FOP_CMP_STRING || in.op == FOP_LIKE || in.op == FOP_IN) in.lit_off += lit0;
+    if ((in.op == FOP_LIKE && in.cmp != LIKE_ALL) || (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE))) in.i += planes;
+    into.prog.push_back(in);
+  }
+  for (const uint32_t k : from.like_leaves) into.like_leaves.push_back(first + k);
+  for (const uint32_t k : from.in_leaves) into.in_leaves.push_back(first + k);
+  if (from.depth > into.depth) into.depth = from.depth;
+  return first;
+}
+
 }  // namespace orcgpu_host

@@ -50,6 +50,8 @@ struct orcgpu_reader {
       std::string column, s;
     };
     std::vector<ExprNode> expr;
+    // the spec's condition (orcgpu_reader_set_aggregate_filters): its nodes with their names and literal bytes copied; none: empty
+    std::vector<orcgpu_host::PredNode> filter;
   };
   std::vector<AggSpec> agg_specs;
   // GROUP BY (orcgpu_reader_set_group_by): the key columns as given
@@ -333,12 +335,16 @@ struct ReaderAggView {
   std::vector<orcgpu_agg_spec> specs;
   std::vector<orcgpu_agg_expr> exprs;
   std::vector<std::vector<orcgpu_agg_expr_node>> nodes;
+  std::vector<orcgpu_agg_filter> filters;  // parallel too: the specs' conditions, whose nodes live in `filter_nodes`
+  std::vector<std::vector<orcgpu_predicate_node>> filter_nodes;
 };
 void reader_view_aggs(const orcgpu_reader* rd, ReaderAggView& v) {
   const size_t n = rd->agg_specs.size();
   v.specs.resize(n);
   v.exprs.assign(n, orcgpu_agg_expr{nullptr, 0});
   v.nodes.assign(n, {});
+  v.filters.assign(n, orcgpu_agg_filter{nullptr, 0});
+  v.filter_nodes.assign(n, {});
   for (size_t k = 0; k < n; k++) {
     const orcgpu_reader::AggSpec& s = rd->agg_specs[k];
     v.specs[k] = {s.op, s.has_column ? s.column.c_str() : nullptr, s.has_column2 ? s.column2.c_str() : nullptr};
@@ -349,6 +355,10 @@ void reader_view_aggs(const orcgpu_reader* rd, ReaderAggView& v) {
       v.nodes[k].push_back(x);
     }
     if (!v.nodes[k].empty()) v.exprs[k] = {v.nodes[k].data(), (uint32_t)v.nodes[k].size()};
+    if (!s.filter.empty()) {
+      v.filter_nodes[k] = view_predicate(s.filter);
+      v.filters[k] = {v.filter_nodes[k].data(), (uint32_t)v.filter_nodes[k].size()};
+    }
   }
 }
 
@@ -382,7 +392,7 @@ int reader_compile_aggs(orcgpu_reader* rd) {
   reader_describe_roots(rd, names, cols);
   ReaderAggView v;
   reader_view_aggs(rd, v);
-  const int rc = agg_compile(v.specs.data(), v.exprs.data(), (uint32_t)v.specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
+  const int rc = agg_compile(v.specs.data(), v.exprs.data(), v.filters.data(), (uint32_t)v.specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
   if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
   return rc;
 }
@@ -420,7 +430,7 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
   ReaderAggView v;
   reader_view_aggs(rd, v);
   AggPlan plan;
-  if (const int rc = result_compile_aggs(rd->ctx, res, v.specs.data(), v.exprs.data(), (uint32_t)v.specs.size(), names.data(), plan)) return rc;
+  if (const int rc = result_compile_aggs(rd->ctx, res, v.specs.data(), v.exprs.data(), v.filters.data(), (uint32_t)v.specs.size(), names.data(), plan)) return rc;
   for (size_t k = 0; k < plan.insns.size(); k++)
     if (plan.insns[k].kind != rd->agg_plan.insns[k].kind || plan.insns[k].scale != rd->agg_plan.insns[k].scale) {
       if (agg_is_expr(plan.insns[k].kind) || agg_is_expr(rd->agg_plan.insns[k].kind))  // (col is no column index then)

@@ -352,6 +352,16 @@ int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* rd, const orcgpu_agg_spec* 
   rd->has_aggs = true;
   return ORCGPU_OK;
 }
+int orcgpu_reader_set_aggregate_filters(orcgpu_reader* rd, const orcgpu_agg_filter* filters, uint32_t n_specs) {
+  if (!rd || rd->built || !rd->has_aggs || n_specs != rd->agg_specs.size()) return ORCGPU_INVALID_ARGUMENT;
+  for (uint32_t k = 0; filters && k < n_specs; k++)
+    if (filters[k].n_nodes && !filters[k].nodes) return ORCGPU_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_specs; k++) {
+    rd->agg_specs[k].filter.clear();
+    if (filters && filters[k].n_nodes) rd->agg_specs[k].filter = orcgpu_host::copy_predicate(filters[k].nodes, filters[k].n_nodes);
+  }
+  return ORCGPU_OK;
+}
 // What the two drains share.  reader_drain_begin: a reader is drained once, and built first; from then on whatever comes of it ends
 // the reader as an error ends an iterator.  reader_drain: rc is what the compile steps gave; then the filter, then every stripe in
 // stripe order handed to merge_stripe (rd->current: its status ends the loop).  ORCGPU_OK: every stripe has been merged.

@@ -12,6 +12,11 @@ PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UT
 _EPOCH = datetime.datetime(1970, 1, 1)
 
 
+_PV_NAMES = ("Boolean", "Int8", "Int16", "Int32", "Int64", "Float32", "Float64", "Utf8", "Decimal128", "TimestampNs")
+_OP_NAMES = {EQ: "eq", NE: "ne", LT: "lt", LE: "lte", GT: "gt", GE: "gte", IS_NULL: "is_null", IS_NOT_NULL: "is_not_null", AND: "and_", OR: "or_", NOT: "not_",
+             LIKE: "like", IN: "in_list"}
+
+
 class PredicateNode(C.Structure):
     _fields_ = [("op", C.c_int32), ("n_children", C.c_uint32), ("column", C.c_char_p), ("value_type", C.c_int32), ("value_is_null", C.c_int32),
                 ("i", C.c_int64), ("f", C.c_double), ("s", C.c_char_p), ("s_len", C.c_uint64)]
@@ -29,6 +34,9 @@ class PredicateValue:
 
     def __init__(self, kind, value):
         self.kind, self.value = kind, value
+
+    def __repr__(self):
+        return "%s(%r)" % (_PV_NAMES[self.kind], self.value)
 
     Boolean = classmethod(lambda cls, v: cls(PV_BOOLEAN, v))
     Int8 = classmethod(lambda cls, v: cls(PV_INT8, v))
@@ -178,6 +186,20 @@ class Predicate:
     @classmethod
     def not_(cls, predicate):
         return cls(NOT, children=[predicate])
+
+    def __repr__(self):
+        name = _OP_NAMES.get(self.op, "op%d" % self.op)
+        if self.op in (AND, OR):
+            return "%s(%r)" % (name, self.children)
+        if self.op == NOT:
+            return "not_(%r)" % (self.children[0],)
+        if self.op in (IS_NULL, IS_NOT_NULL):
+            return "%s(%r)" % (name, self.column)
+        if self.op == IN:
+            return "in_list(%r, %r)" % (self.column, [c.value for c in self.children])
+        if self.op == LIKE:
+            return "like(%r, %r%s)" % (self.column, self.value.value, "" if self.escape is None else ", escape=%r" % self.escape)
+        return "%s(%r, %r)" % (name, self.column, self.value)
 
     def flatten(self):
         """-> (ctypes array of PredicateNode in pre-order, objects to keep alive)."""
