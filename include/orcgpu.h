@@ -827,6 +827,62 @@ uint32_t orcgpu_groups_count(const orcgpu_groups* g);
 int orcgpu_groups_key(const orcgpu_groups* g, uint32_t group, uint32_t key, orcgpu_group_key* out);
 int orcgpu_groups_value(const orcgpu_groups* g, uint32_t group, uint32_t spec, orcgpu_agg_value* out);
 void orcgpu_groups_free(orcgpu_groups* g);
+/* ---- Top-k: ORDER BY ... LIMIT k, the top rows selected on the device -------------------------------------------------------------
+ * SELECT ... WHERE ... ORDER BY x [DESC] LIMIT k: the ten largest orders, the hundred latest events.  The aggregates return one
+ * record, the row filter every kept row; this returns the k first kept rows under a sort order, chosen and ordered where the rows
+ * lie (device/top_k_kernels.hip: a radix select over the key bytes, then a stable radix sort of at most k rows), so that only they
+ * cross the link.  The reference has no ORDER BY and no LIMIT; the semantics are fixed here.
+ *   - The KEPT rows are what they are for the row filter and the aggregates: those the row selection selects (if there is one) for
+ *     which the row filter's root is TRUE (if there is one); with neither, every row.
+ *   - SORT KEYS: 1 .. ORCGPU_TOP_K_MAX_KEYS, the first the most significant; each names a projected root column.  Byte .. Long,
+ *     Date (days) and a Timestamp / Timestamp-instant decoded to an int64 unit compare as signed 64-bit integers; Boolean false <
+ *     true; Decimal as the unscaled signed 128-bit value (one column has one scale); Float / Double as double, a Float widened
+ *     first, in the total order -inf < finite < +inf < NaN, every NaN equal to every other, -0.0 equal to 0.0.
+ *   - PER-KEY FLAGS: `descending` reverses the order of that key's non-null values only; `nulls_first` places its NULLs before
+ *     all of its non-null values, whatever `descending` says -- the default is after them.
+ *   - THE ANSWER: the kept rows sorted STABLY by the keys -- rows equal in every key keep ascending input-row order, which across
+ *     stripes is stripe order, then row --, the first k of them.  Ties included it is a function of the kept rows in input order,
+ *     the keys and k: the same on every run, whichever thread wins whichever race (no atomic decides a value, a place or an order).
+ *   - k: 1 .. ORCGPU_TOP_K_MAX.  Fewer than k kept rows: all of them.  No kept row: no batch.
+ *   - Every column of the projection comes along: Strings, Binary, Decimal, Timestamps and dictionary-output columns travel as
+ *     payload exactly as the row filter's gather moves them.
+ *   - REFUSED, each message beginning "top-k:" and naming the column.  ORCGPU_UNSUPPORTED: a String / Varchar / Char / Binary key; a
+ *     key column read as a dictionary column; a Timestamp key decoded to Decimal128(38, 9); a nested column in the result, as for
+ *     the filter.  ORCGPU_INVALID_ARGUMENT: an unknown or unprojected column; a key listed twice; no key or more than
+ *     ORCGPU_TOP_K_MAX_KEYS; k = 0 or k > ORCGPU_TOP_K_MAX.
+ *   - COST: one host wait per call, as for the filter; beside the filter's counters it fetches the select's state and at most k
+ *     key records (9 bytes a key, 17 for a Decimal key, rounded up to 8).  The launch sequence is a function of the key kinds and
+ *     k alone.  The device workspace holds three planes of one bit per input row, a second row list and the records, behind the
+ *     filter's own.
+ *   - Not there: String keys (the next step); keys that are expressions; a running cut-off handed from stripe to stripe; OFFSET;
+ *     ORDER BY over GROUP BY results.
+ * orcgpu_result_top_k is orcgpu_result_filter with ORDER BY keys LIMIT k; n_nodes = 0 is "no predicate".  Afterwards the result's
+ * batches are the answer's rows IN SORTED ORDER, packed into batches of batch_size rows, and everything that speaks of a filtered
+ * result speaks of them (_rows, _batches, _batch_view, _copy_batch, _fetch[_async], _export_batch[_device]); a copy back moves
+ * those rows only.  A result whose status is not OK is left alone and that status returned.  *rows_kept: the rows the predicate
+ * kept; *rows_out: min(k, kept).
+ * orcgpu_reader_set_top_k is a builder setter (before the first call; names are copied).  Per stripe the top-k stands where the
+ * filter's compaction stands -- after the row selection and the row filter if set, with and without read-ahead and device output --:
+ * a stripe hands out its own at most k best rows, sorted, in batches of batch_size rows; a stripe without kept rows yields no
+ * batch.  orcgpu_reader_filter_rows reports seen and predicate-kept rows, not k.  Together with aggregates it is
+ * ORCGPU_INVALID_ARGUMENT at whichever setter comes second, and nothing changes.
+ * orcgpu_reader_top_k_order is legal once next_batch[_device] has returned ORCGPU_END_OF_FILE; before that, and on a reader without
+ * top-k, it is ORCGPU_INVALID_ARGUMENT.  positions[i] is the index of the i-th row of the GLOBAL answer in the concatenation of all
+ * rows the reader handed out, in hand-out order; *n = min(k, total kept rows); cap < *n is ORCGPU_INVALID_ARGUMENT with *n set.
+ * (The reader keeps one key record per handed-out row, fetched in the stripe's one wait, and merges them k-way on the host: ties
+ * by stripe order, then position.) */
+#define ORCGPU_TOP_K_MAX_KEYS 4
+#define ORCGPU_TOP_K_MAX 65536
+typedef struct {
+  const char* column;
+  uint32_t descending;   /* 0: ascending */
+  uint32_t nulls_first;  /* 0: NULLs behind every value of this key */
+} orcgpu_sort_key;
+int orcgpu_result_top_k(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                        const char* const* column_names, uint32_t n_columns, const orcgpu_sort_key* keys, uint32_t n_keys, uint32_t k,
+                        uint64_t* rows_kept, uint64_t* rows_out);
+int orcgpu_reader_set_top_k(orcgpu_reader* r, const orcgpu_sort_key* keys, uint32_t n_keys, uint32_t k);
+int orcgpu_reader_top_k_order(orcgpu_reader* r, uint64_t* positions, uint64_t cap, uint64_t* n);
 /* Read-ahead: how many decoded stripes the reader may be ahead of the caller (default 2 -- every result set in flight costs a pinned host copy of a stripe --, at most 8; 0 = none: every stripe is
  * read, staged, decoded and copied back inside the orcgpu_reader_next_batch call that needs it).  With read-ahead two threads
  * of the reader work beside the caller: one reads and stages the stripes to come, one decodes the stripes staged so far

@@ -31,6 +31,14 @@ def check_dictionary_columns(names):
     return list(names)
 
 
+def concat_batches(batches):
+    """The batches of one reader as one pyarrow.Table.  (A batch's schema says "not null" of a column without a NULL in that batch,
+    so the batches' schemas differ and Table.from_batches refuses them: the table is built column by column, every field nullable.)"""
+    import pyarrow as pa
+    names = batches[0].schema.names
+    return pa.Table.from_arrays([pa.chunked_array([b.column(i) for b in batches]) for i in range(len(names))], names=names)
+
+
 class ArrowReaderBuilder:
     def __init__(self, ctx, handle, keep=None):
         self._ctx, self._h, self._keep = ctx, handle, keep
@@ -185,6 +193,27 @@ class ArrowReaderBuilder:
         r._group_by = A.check_group_by(group_by) if group_by is not None else None
         return r
 
+    def with_top_k(self, by, k):
+        """ORDER BY by LIMIT k (orcgpu_reader_set_top_k): `by` is a list of orc_rust_amd.top_k.SortKey (a bare column name and a
+        (name, "asc" | "desc") tuple are accepted for one).  The reader then iterates every stripe's own at most k best kept rows,
+        sorted, selected on the GPU behind the row selection and the row filter; ArrowReader.top_k_order() merges them once the
+        reader is drained.  Not together with aggregates."""
+        from . import top_k as T
+        keys, keep = T.key_array(by)
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_top_k(self._h, keys, len(keys), T.check_k(k)))
+        return self
+
+    def top_k(self, by, k):
+        """The same, drained: one pyarrow.Table of the answer in order -- the stripes' candidates concatenated, then one `take` by
+        ArrowReader.top_k_order().  Host output."""
+        import pyarrow as pa
+        reader = self.with_top_k(by, k).build()
+        batches = list(reader)
+        order = reader.top_k_order()
+        if not batches:  # (no kept row: no batch, so no schema -- the projected names over null columns)
+            return pa.schema([(n, pa.null()) for n in reader.column_names()]).empty_table()
+        return concat_batches(batches).take(pa.array(order, type=pa.uint64()))
+
     def total_row_count(self):
         return self._ctx.L.orcgpu_reader_total_rows(self._h)
 
@@ -226,6 +255,17 @@ class ArrowReader:
         n = C.c_uint64(0)
         self._ctx._check(self._ctx.L.orcgpu_reader_d2h_bytes(self._h, C.byref(n)))
         return n.value
+
+    def top_k_order(self):
+        """Once the reader is drained: where the rows of the global answer of with_top_k stand in the concatenation of all rows it
+        handed out, in order (orcgpu_reader_top_k_order) -- a list of ints, min(k, kept rows) long."""
+        n = C.c_uint64(0)
+        rc = self._ctx.L.orcgpu_reader_top_k_order(self._h, None, 0, C.byref(n))
+        if rc and not n.value:
+            self._ctx._check(rc)
+        out = (C.c_uint64 * max(1, n.value))()
+        self._ctx._check(self._ctx.L.orcgpu_reader_top_k_order(self._h, out, n.value, C.byref(n)))
+        return list(out)[:n.value]
 
     def aggregate(self, raw=False):
         """Drains a reader built by ArrowReaderBuilder.aggregating_reader (orcgpu_reader_aggregate): the list of Python values."""

@@ -42,6 +42,7 @@ EXPORTS = [
     "orcgpu_writer_set_compression", "orcgpu_compress_stream", "orcgpu_writer_set_row_index",
     "orcgpu_writer_set_dictionary", "orcgpu_writer_dictionary_counts",
     "orcgpu_writer_set_bloom_filter",
+    "orcgpu_result_top_k", "orcgpu_reader_set_top_k", "orcgpu_reader_top_k_order",
 ]
 
 
@@ -215,6 +216,11 @@ def load():
     L.orcgpu_result_filter.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                        C.POINTER(C.c_uint64)]
     L.orcgpu_reader_set_row_filter.argtypes = [C.c_void_p, C.POINTER(PredicateNode), C.c_uint32]
+    from .top_k import SortKeyStruct
+    L.orcgpu_result_top_k.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
+                                      C.POINTER(SortKeyStruct), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.orcgpu_reader_set_top_k.argtypes = [C.c_void_p, C.POINTER(SortKeyStruct), C.c_uint32, C.c_uint32]
+    L.orcgpu_reader_top_k_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
     L.orcgpu_reader_filter_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     from .aggregate import AggSpec, AggValue
     L.orcgpu_result_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
@@ -472,6 +478,19 @@ class Context:
         kept = C.c_uint64(0)
         self._check(self.L.orcgpu_result_filter(self.h, result.h, nodes, len(nodes), names, len(column_names), C.byref(kept)))
         return kept.value
+
+    def result_top_k(self, result, by, k, column_names, predicate=None):
+        """orcgpu_result_top_k: the result's batches become the first k of its kept rows (predicate None: all rows) under the sort
+        keys `by` (orc_rust_amd.top_k), in sorted order.  Returns (rows the predicate kept, rows handed out)."""
+        from . import top_k as T
+        keys, keep = T.key_array(by)
+        k = T.check_k(k)
+        nodes, keep_p = predicate.flatten() if predicate is not None else (None, None)
+        names = (C.c_char_p * max(1, len(column_names)))(*[n.encode() for n in column_names])
+        kept, out = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.orcgpu_result_top_k(self.h, result.h, nodes, len(nodes) if nodes is not None else 0, names, len(column_names), keys, len(keys), k,
+                                               C.byref(kept), C.byref(out)))
+        return kept.value, out.value
 
     @staticmethod
     def _aggregate_args(specs, column_names, predicate):

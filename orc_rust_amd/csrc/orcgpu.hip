@@ -46,6 +46,7 @@
 #include "device/agg_kernels.hip"
 #include "device/agg_group_kernels.hip"
 #include "device/agg_group_wide_kernels.hip"
+#include "device/top_k_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -502,6 +503,7 @@ struct orcgpu_result {
   uint64_t agg_seen = 0;                // ... and the rows the aggregation saw
   std::vector<GroupKeyRecord> grp_keys;  // ... with a GROUP BY: the stripe's groups in first-appearance order, keys [group][key]
   std::vector<AggPartial> grp_vals;      // ... and records [group][aggregate, then the group's kept row count]
+  std::vector<uint8_t> top_k_records;    // a top-k file reader: the key record of every row the stripe hands out, in their order
   std::vector<ColumnOut> cols;
   std::vector<std::string> field_names;  // per column: the name of a Struct's field (set by the file reader; empty: "f<position>")
   // Elements of the List / Map columns: one result each over a "stripe" whose rows are the column's elements (all of the
@@ -1217,6 +1219,7 @@ struct SummaryLayout {
 #include "orcgpu_select.inc"
 #include "orcgpu_filter.inc"
 #include "orcgpu_agg.inc"
+#include "orcgpu_top_k.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_reader_api.inc"
 #include "orcgpu_encode.inc"

@@ -295,8 +295,8 @@ int filter_open(FilterCall& f, uint64_t* rows_seen) {
   if (rows_seen) *rows_seen = f.n_in;
   return ORCGPU_OK;
 }
-FilterWorkspace filter_workspace(const FilterCall& f) {
-  return FilterWorkspace(f.plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), f.src_batches, f.n_in, f.B);
+FilterWorkspace filter_workspace(const FilterCall& f, uint64_t out_rows_max = ~0ull) {
+  return FilterWorkspace(f.plan, f.descs.data(), f.nc, (uint32_t)f.segs.size(), f.src_batches, f.n_in, f.B, out_rows_max);
 }
 // filter_reserve: `bytes` of workspace on the device (ws.bytes and what the caller laid behind it; `what` names the caller in
 // the message), the columns into the first upload, and the plan against what the columns were decoded to

@@ -85,10 +85,12 @@ struct FilterWorkspace {
   uint64_t o_jobs = 0, o_obase = 0, up2_bytes = 0;
   uint64_t bytes = 0;
 
-  FilterWorkspace(const orcgpu_host::FilterPlan& plan, const FilterColDesc* descs, uint32_t nc, uint32_t n_segs, uint32_t src_batches, uint64_t n_in, uint32_t B) {
+  // (out_rows_max: a caller that hands out fewer rows than it takes in -- the top-k -- sizes the output batches by them)
+  FilterWorkspace(const orcgpu_host::FilterPlan& plan, const FilterColDesc* descs, uint32_t nc, uint32_t n_segs, uint32_t src_batches, uint64_t n_in, uint32_t B,
+                  uint64_t out_rows_max = ~0ull) {
     FilterBump t;
     n_words = (n_in + 63) / 64;
-    nb_max = (n_in + B - 1) / B;
+    nb_max = (std::min(n_in, out_rows_max) + B - 1) / B;
     o_prog = t.take(plan.prog.size() * sizeof(FilterInsn) + 16);
     o_lits = t.take(plan.lits.size() + 16);
     o_leaves = t.take(plan.n_planes() * 4 + 16);

@@ -58,6 +58,14 @@ struct orcgpu_reader {
   bool has_group = false;
   std::vector<std::string> group_keys;
   uint32_t group_max = ORCGPU_GROUP_MAX, group_max_total = ORCGPU_GROUP_MAX_TOTAL;  // its limits (orcgpu_reader_set_group_limits)
+  // ORDER BY ... LIMIT k (orcgpu_reader_set_top_k): the keys as given (their names copied)
+  bool has_top_k = false;
+  struct SortKey {
+    std::string column;
+    uint32_t descending = 0, nulls_first = 0;
+  };
+  std::vector<SortKey> top_k_keys;
+  uint32_t top_k_k = 0;
   // device output (orcgpu_reader_set_device_output): the batches are views of the results' HBM, handed out by
   // orcgpu_reader_next_batch_device; no copy back is started.  A result the caller is done with goes to `home` instead of `spare`
   // -- at once, or when the last exported batch or tensor that views it is released (device_hold.h)
@@ -86,6 +94,11 @@ struct orcgpu_reader {
   bool aggs_done = false;
   orcgpu_host::AggPlan agg_plan;
   orcgpu_host::GroupPlan group_plan;
+  // the top-k's keys against the projected root columns, from the first next_batch on; the key records of the rows handed out so
+  // far, stripe by stripe in hand-out order (orcgpu_reader_top_k_order merges them once the file has ended)
+  bool top_k_ready = false, top_k_eof = false;
+  orcgpu_host::TopKPlan top_k_plan;
+  std::vector<orcgpu_host::TopKStripe> top_k_stripes;
   uint64_t d2h_bytes = 0;                     // column-buffer bytes copied to the host so far (orcgpu_reader_d2h_bytes)
   bool current_counted = false;               // ... those of `current` are in it
   bool device_checked = false, device_refused = false;  // the projection has been looked at for nested columns; it has one
@@ -462,6 +475,49 @@ int reader_aggregate_result(orcgpu_reader* rd, orcgpu_result* res) {
   return ORCGPU_OK;
 }
 
+// The reader's sort keys as the C array the plan compiler takes
+std::vector<orcgpu_sort_key> reader_view_sort_keys(const orcgpu_reader* rd) {
+  std::vector<orcgpu_sort_key> keys;
+  for (auto& k : rd->top_k_keys) keys.push_back({k.column.c_str(), k.descending, k.nulls_first});
+  return keys;
+}
+// The sort keys against the projected root columns as the file's metadata and the builder describe them, once, before anything is
+// read: every refusal arrives here.  (What a stripe's decode made of the columns is checked again per stripe: reader_top_k_result.)
+int reader_compile_top_k(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<AggCol> cols;
+  reader_describe_roots(rd, names, cols);
+  const std::vector<orcgpu_sort_key> keys = reader_view_sort_keys(rd);
+  const int rc = top_k_compile(keys.data(), (uint32_t)keys.size(), rd->top_k_k, names.data(), cols.data(), (uint32_t)cols.size(), rd->top_k_plan);
+  if (rc) set_err(rd->ctx, "%s", rd->top_k_plan.err);
+  return rc;
+}
+// The top-k of one decoded (and selected) stripe, where reader_filter_result stands otherwise: behind the row filter's evaluation
+// if there is one, its at most k best rows become the result's batches and their key records stay with the result until it is
+// handed out.  A stripe whose decode failed is left as it is: its error arrives with its failing batch.
+int reader_top_k_result(orcgpu_reader* rd, orcgpu_result* res) {
+  res->top_k_records.clear();
+  if (res->status) return ORCGPU_OK;
+  std::vector<const char*> names;
+  for (size_t k : rd->proj.roots()) names.push_back(rd->proj.names[rd->proj.cols[k].root].c_str());
+  if (names.size() != res->cols.size()) {
+    set_err(rd->ctx, "top-k: the result holds %zu columns for %zu projected root columns", res->cols.size(), names.size());
+    return ORCGPU_UNEXPECTED;
+  }
+  const std::vector<orcgpu_sort_key> keys = reader_view_sort_keys(rd);
+  TopKPlan plan;
+  if (const int rc = result_compile_top_k(rd->ctx, res, keys.data(), (uint32_t)keys.size(), rd->top_k_k, names.data(), plan)) return rc;
+  if (plan.keys.len != rd->top_k_plan.keys.len || memcmp(&plan.keys, &rd->top_k_plan.keys, sizeof(plan.keys)) != 0) {
+    set_err(rd->ctx, "top-k: the key columns are not decoded to the types the keys were planned for");
+    return ORCGPU_MISMATCHED_SCHEMA;
+  }
+  uint64_t seen = 0, kept = 0;
+  const int rc = result_top_k_plan(rd->ctx, res, rd->has_filter ? &rd->filter_plan : nullptr, plan, &seen, &kept, nullptr, &res->top_k_records, names.data(), (uint32_t)names.size());
+  rd->filter_seen += seen;
+  rd->filter_kept += kept;
+  return rc;
+}
+
 // A result the caller is done with, to decode a later stripe into (rd->m is held by a reader that reads ahead)
 orcgpu_result* reader_take_spare(orcgpu_reader* rd) {
   // (a result that comes home was viewed by batches and tensors whose consumers released them on the HOST: work they enqueued on
@@ -496,6 +552,7 @@ int reader_finish_decoded(orcgpu_reader* rd, orcgpu_staged* staged, orcgpu_resul
   }
   if (!rc && staged->has_sel) rc = result_select_batches(rd->ctx, res, staged->sel);
   if (!rc && rd->has_aggs) rc = reader_aggregate_result(rd, res);
+  else if (!rc && rd->has_top_k) rc = reader_top_k_result(rd, res);
   else if (!rc && rd->has_filter) rc = reader_filter_result(rd, res);
   orcgpu_staged_free(staged);
   if (!rc && !rd->has_aggs) rc = reader_result_decoded(rd, res, start_copy);
@@ -507,6 +564,12 @@ void reader_make_current(orcgpu_reader* rd, orcgpu_result* res) {
   rd->current = res;
   rd->next_batch = 0;
   rd->current_counted = false;
+  if (rd->has_top_k && !res->status) {  // (hand-out order: the records of its rows go behind those of the stripes before)
+    TopKStripe s;
+    s.n = res->n_rows;
+    s.recs.swap(res->top_k_records);
+    rd->top_k_stripes.push_back(std::move(s));
+  }
 }
 
 // prefetch = 0: both steps in the caller's thread (the pieces of a stripe in one decode call).  ORCGPU_END_OF_FILE = the file has no more rows to give

@@ -213,6 +213,15 @@ static int reader_ready_filter(orcgpu_reader* rd) {
     }
     rd->filter_ready = true;
   }
+  if (rd->has_top_k && !rd->top_k_ready) {  // (the sort keys likewise: refused before anything of the file is read)
+    const int rc = orcgpu_host::reader_compile_top_k(rd);
+    if (rc) {
+      rd->filter_failed = true;
+      rd->next_stripe = rd->stripe_order.size();
+      return rc;
+    }
+    rd->top_k_ready = true;
+  }
   return ORCGPU_OK;
 }
 static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct ArrowDeviceArray* out_device, struct ArrowSchema* out_schema) {
@@ -268,6 +277,7 @@ static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct A
       }
     }
     rc = reader_next_stripe(rd);  // (ORCGPU_END_OF_FILE: every stripe has been handed out)
+    if (rc == ORCGPU_END_OF_FILE) rd->top_k_eof = true;
     if (rc) return rc;
   }
 }
@@ -319,11 +329,54 @@ int orcgpu_reader_next_batch_device(orcgpu_reader* rd, struct ArrowDeviceArray* 
   if (!out_array) return ORCGPU_INVALID_ARGUMENT;
   return reader_next(rd, nullptr, out_array, out_schema);
 }
+int orcgpu_reader_set_top_k(orcgpu_reader* rd, const orcgpu_sort_key* keys, uint32_t n_keys, uint32_t k) {
+  if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
+  if (rd->has_aggs) {
+    set_err(rd->ctx, "top-k: this reader aggregates (orcgpu_reader_set_aggregates): it hands out no rows to select from");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  // what needs no column is refused here, the rest with the first batch: the columns are known once the reader is built
+  orcgpu_host::TopKPlan plan;
+  const int rc = orcgpu_host::top_k_compile(keys, n_keys, k, nullptr, nullptr, 0, plan);
+  if (rc && (!keys || !n_keys || n_keys > ORCGPU_TOP_K_MAX_KEYS || !k || k > ORCGPU_TOP_K_MAX)) {
+    set_err(rd->ctx, "%s", plan.err);
+    return rc;
+  }
+  for (uint32_t q = 0; q < n_keys; q++)
+    if (!keys[q].column) {
+      set_err(rd->ctx, "top-k: a sort key without a column name");
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+  rd->top_k_keys.clear();
+  for (uint32_t q = 0; q < n_keys; q++) rd->top_k_keys.push_back({keys[q].column, keys[q].descending ? 1u : 0u, keys[q].nulls_first ? 1u : 0u});
+  rd->top_k_k = k;
+  rd->has_top_k = true;
+  return ORCGPU_OK;
+}
+int orcgpu_reader_top_k_order(orcgpu_reader* rd, uint64_t* positions, uint64_t cap, uint64_t* n) {
+  if (!rd || !n) return ORCGPU_INVALID_ARGUMENT;
+  *n = 0;
+  if (!rd->has_top_k) {
+    set_err(rd->ctx, "top-k: orcgpu_reader_top_k_order needs orcgpu_reader_set_top_k before the first call");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  if (!rd->top_k_eof || !rd->top_k_ready) {
+    set_err(rd->ctx, "top-k: orcgpu_reader_top_k_order is legal once next_batch has returned ORCGPU_END_OF_FILE");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  const int rc = orcgpu_host::top_k_merge(rd->top_k_stripes, rd->top_k_plan.keys.len, rd->top_k_k, positions, cap, n);
+  if (rc) set_err(rd->ctx, "top-k: room for %llu positions, the answer holds %llu", (unsigned long long)cap, (unsigned long long)*n);
+  return rc;
+}
 int orcgpu_reader_set_aggregates(orcgpu_reader* rd, const orcgpu_agg_spec* specs, uint32_t n_specs) {
   return orcgpu_reader_set_aggregate_exprs(rd, specs, nullptr, n_specs);
 }
 int orcgpu_reader_set_aggregate_exprs(orcgpu_reader* rd, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, uint32_t n_specs) {
   if (!rd || rd->built || !specs || !n_specs || n_specs > ORCGPU_AGG_MAX) return ORCGPU_INVALID_ARGUMENT;
+  if (rd->has_top_k) {
+    set_err(rd->ctx, "aggregate: this reader selects the top k rows (orcgpu_reader_set_top_k): it does not aggregate as well");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (exprs)
     for (uint32_t k = 0; k < n_specs; k++)
       if (exprs[k].n_nodes && !exprs[k].nodes) return ORCGPU_INVALID_ARGUMENT;
