@@ -433,7 +433,15 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_IN = 17 /* SQL IN, this library's own: a leaf with column; n_children counts the ORCGPU_PRED_LITERAL nodes that
                               follow it in pre-order, its list.  There is no NOT IN: put ORCGPU_PRED_NOT above the leaf */,
        ORCGPU_PRED_LITERAL = 18 /* one value of an IN list: column = NULL, n_children = 0; value_type, value_is_null, i, f, s, s_len as
-                                   in a comparison node.  Anywhere but under an ORCGPU_PRED_IN it is ORCGPU_INVALID_ARGUMENT */ };
+                                   in a comparison node.  Anywhere but under an ORCGPU_PRED_IN it is ORCGPU_INVALID_ARGUMENT */,
+       ORCGPU_PRED_CMP_EXPR = 19 /* lhs OP rhs over two arithmetic expressions, this library's own: a leaf with column = NULL,
+                                    i = ORCGPU_PRED_EQ .. _GE and n_children = 2; the two expression subtrees follow it in pre-order,
+                                    the left side first.  See orcgpu_result_filter */,
+       /* the nodes of such a subtree: the language of orcgpu_agg_expr_node, with every field where that struct has it */
+       ORCGPU_PRED_EXPR_COLUMN = 20 /* `column`: a projected root column; no children */,
+       ORCGPU_PRED_EXPR_LITERAL = 21 /* value_type ORCGPU_PV_INT64: i; _FLOAT64: f; _DECIMAL128: s / s_len / i; no children */,
+       ORCGPU_PRED_EXPR_ADD = 22, ORCGPU_PRED_EXPR_SUB = 23, ORCGPU_PRED_EXPR_MUL = 24 /* exactly two children */,
+       ORCGPU_PRED_EXPR_NEG = 25 /* exactly one child */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
 #define ORCGPU_IN_MAX_BYTES (4u << 20)
@@ -529,6 +537,32 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     keys go into a hash set (open addressing, linear probing) that a kernel of its own (filter_in_kernel) probes per row in front
  *     of the evaluation, on the same stream: from LDS when the table is at most 32 KiB, else where it lies in global memory; no
  *     further host wait.  The cost per row does not grow with the list.
+ *   - ORCGPU_PRED_CMP_EXPR: lhs OP rhs.  Each side is an arithmetic expression in the language of the expression aggregates
+ *     (orcgpu_result_aggregate_exprs: columns, literals, + - *, unary -), OP one of EQ .. GE, evaluated exactly, per row.
+ *     CLASSES, decided over BOTH sides together: INT (Byte .. Long columns and INT64 literals; a Date column takes part as int64
+ *     days -- in this leaf only, SUM over a Date column is refused as before), DEC (at least one Decimal column or DECIMAL128
+ *     literal on either side; integers beside them are Decimals of scale 0; the scale rule is that of the expression aggregates,
+ *     a node past scale 38 is ORCGPU_UNSUPPORTED) and FLOAT (Float / Double columns and FLOAT64 literals, every operation one IEEE
+ *     double operation).  Float and exact operands do not mix: ORCGPU_MISMATCHED_SCHEMA, naming the column.  A Boolean, String /
+ *     Varchar / Char / Binary or Timestamp column, a nested one and one read as a dictionary column: ORCGPU_UNSUPPORTED, naming it.
+ *     THE COMPARISON: INT compares as int128.  FLOAT compares as a Float leaf does (a NaN on either side makes all but NE false,
+ *     -0.0 == 0.0).  DEC compares in exact rational order: the side of the smaller scale is multiplied by 10^d, d the difference
+ *     of the two sides' scales; where that product leaves 128 bits the order is still exact -- a positive side that overflows is
+ *     greater than any int128, a negative one smaller.  No row is UNKNOWN because of this final rescale.
+ *     UNKNOWN on a row where a column of either side is NULL, and on a row where an operation INSIDE a side leaves 128 bits: the
+ *     value does not exist, as for a NULL; nothing wraps.  The row filter counts the latter (row, leaf) evaluations:
+ *     orcgpu_reader_filter_overflow_rows (0 unless something overflowed; the count travels in the filter's one host wait).  As an
+ *     aggregate's condition and as the filter of a top-k the rule holds and the count is not surfaced.
+ *     SIMPLE FORMS: a side of literals alone is folded.  A bare column against a side that folds to a literal the column's own
+ *     comparison takes (an integer or Date column and a literal within int64; a Float / Double column; a Decimal column and a
+ *     literal of |value| < 10^38) compiles to that comparison, the operator mirrored when the column stands on the right -- and
+ *     orcgpu_predicate_row_groups prunes it as that comparison when the literal side is ONE literal node; two literal sides
+ *     compile to TRUE / FALSE.  Every other expression leaf is a sound "might match" for row-group pruning: it keeps every group
+ *     and never fails the evaluation.  LIMITS: each side at most ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH
+ *     operand slots (the balanced 16-leaf tree is refused); the leaf counts toward ORCGPU_FILTER_MAX_DEPTH as a leaf alone.  An
+ *     expression node anywhere but under an ORCGPU_PRED_CMP_EXPR, a wrong child count, a node list that ends inside a subtree,
+ *     a comparison op outside 0 .. 5: ORCGPU_INVALID_ARGUMENT.  Both sides are evaluated by a kernel of its own
+ *     (filter_expr_kernel) in front of the evaluation, on the same stream, into two planes (TRUE, FALSE): no further host wait.
  *   - A Struct, List, Map or Union column among the columns: ORCGPU_UNSUPPORTED.
  *   - A leaf naming a column that is not there, a leaf without a name, an unknown op, a node list that ends inside a node's
  *     children or goes on behind the root, and a predicate nested deeper than ORCGPU_FILTER_MAX_DEPTH levels (a leaf alone is
@@ -555,6 +589,10 @@ int orcgpu_result_filter(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_predica
 int orcgpu_reader_set_row_filter(orcgpu_reader* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes);
 /* Rows the row filter has seen (decoded rows, those of the row selection when there is one) and kept so far. */
 int orcgpu_reader_filter_rows(const orcgpu_reader* r, uint64_t* rows_seen, uint64_t* rows_kept);
+/* (row, expression leaf) evaluations of the row filter so far in which an operation inside a side of an ORCGPU_PRED_CMP_EXPR left
+ * 128 bits: the leaf was UNKNOWN there.  0 unless something overflowed.  Aggregates' conditions and the top-k's filter do not
+ * count. */
+int orcgpu_reader_filter_overflow_rows(const orcgpu_reader* r, uint64_t* rows);
 /* ---- aggregates over the kept rows: COUNT, SUM, MIN, MAX and SUM(a * b), reduced on the device ------------------------------
  * A row filter hands the kept rows out; a query like TPC-H Q6 wants one number of them.  An aggregate list is reduced where the
  * decoded rows lie (device/agg_kernels.hip), from the keep mask the filter's evaluation leaves: nothing is scanned, placed,

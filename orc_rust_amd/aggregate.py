@@ -100,6 +100,26 @@ class Expr:
     def __neg__(self):
         return Expr(EXPR_NEG, (self,))
 
+    # A comparison of two expressions is a row filter's leaf (Predicate.compare).  `==` and `!=` stay what they are -- identity,
+    # with the hash that goes with it: .eq(x) / .ne(x) build those two.
+    def __lt__(self, other):
+        return Predicate.compare(self, "<", other)
+
+    def __le__(self, other):
+        return Predicate.compare(self, "<=", other)
+
+    def __gt__(self, other):
+        return Predicate.compare(self, ">", other)
+
+    def __ge__(self, other):
+        return Predicate.compare(self, ">=", other)
+
+    def eq(self, other):
+        return Predicate.compare(self, "=", other)
+
+    def ne(self, other):
+        return Predicate.compare(self, "!=", other)
+
     def __repr__(self):
         if self.op == EXPR_COLUMN:
             return "col(%r)" % self.column

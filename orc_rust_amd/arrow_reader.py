@@ -250,6 +250,13 @@ class ArrowReader:
         self._ctx._check(self._ctx.L.orcgpu_reader_filter_rows(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def filter_overflow_rows(self):
+        """(row, expression leaf) evaluations of the row filter so far in which an operation inside a side of a Predicate.compare
+        leaf left 128 bits -- the leaf was UNKNOWN there: orcgpu_reader_filter_overflow_rows.  0 unless something overflowed."""
+        n = C.c_uint64(0)
+        self._ctx._check(self._ctx.L.orcgpu_reader_filter_overflow_rows(self._h, C.byref(n)))
+        return n.value
+
     def d2h_bytes(self):
         """Column-buffer bytes this reader has copied to the host so far (orcgpu_reader_d2h_bytes); 0 with device output."""
         n = C.c_uint64(0)

@@ -43,6 +43,7 @@ EXPORTS = [
     "orcgpu_writer_set_dictionary", "orcgpu_writer_dictionary_counts",
     "orcgpu_writer_set_bloom_filter",
     "orcgpu_result_top_k", "orcgpu_reader_set_top_k", "orcgpu_reader_top_k_order",
+    "orcgpu_reader_filter_overflow_rows",
 ]
 
 
@@ -222,6 +223,7 @@ def load():
     L.orcgpu_reader_set_top_k.argtypes = [C.c_void_p, C.POINTER(SortKeyStruct), C.c_uint32, C.c_uint32]
     L.orcgpu_reader_top_k_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]
     L.orcgpu_reader_filter_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.orcgpu_reader_filter_overflow_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     from .aggregate import AggSpec, AggValue
     L.orcgpu_result_aggregate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                           C.POINTER(AggSpec), C.c_uint32, C.POINTER(AggValue)]

@@ -18,6 +18,10 @@
 //   filter_in_kernel      likewise for IN leaves: per leaf a plane of "the row is valid and its key is in the list", from a hash
 //                         set the host has built (filter_program.h): staged in LDS up to 32 KiB, probed in global memory above;
 //                         a lane per value, so a row costs one probe however long the list is.
+//   filter_expr_kernel    likewise for expression leaves (lhs OP rhs): per leaf TWO planes, the rows where the comparison is TRUE
+//                         and the rows where it is FALSE (neither: UNKNOWN -- a NULL column on either side, or an operation inside
+//                         a side that left 128 bits, which it counts).  A lane per row interprets both sides' op tables
+//                         (agg_expr_eval.h, the expression aggregates' evaluator) and compares (filter_expr_eval.h).
 //   (enc_scan)            exclusive scan of the popcounts: the output row of every word's first kept row.
 //   filter_place_kernel   every kept row writes its stripe row at its output row: src_rows[], the gather's index list.
 //   filter_count_kernel   per (output batch, column): null count and string bytes -- what the host needs to lay the output out
@@ -37,6 +41,7 @@
 
 #include "filter_program.h"
 #include "filter_access.h"
+#include "filter_expr_eval.h"
 
 struct FilterGatherJob {
   FilterCol src;
@@ -311,6 +316,77 @@ filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves
   }
 }
 
+// ---- expression leaves: both sides by the expression aggregates' evaluator, then the comparison of filter_expr_eval.h ----
+// What agg_expr_eval_* reads of a row
+struct FilterExprRow {
+  const FilterCol* cols;
+  FilterRow r;
+  uint32_t W;
+  __device__ __forceinline__ bool valid(uint32_t col) const { return filter_valid(cols[col], r.u, r.l, W); }
+  __device__ __forceinline__ agg_i128 load_int(uint32_t col) const { return (agg_i128)filter_load_i64(cols[col], r.row); }
+  __device__ __forceinline__ agg_i128 load_dec(uint32_t col) const {
+    unsigned long long lo, hi;
+    filter_load_dec128(cols[col], r.row, &lo, &hi);
+    return agg_i128_of(lo, hi);
+  }
+  __device__ __forceinline__ double load_f64(uint32_t col) const { return filter_load_f64(cols[col], r.row); }
+};
+
+// The expression leaves' two sides, in front of filter_eval_kernel on its stream.  blockIdx.y = an expression leaf: instruction
+// leaves[blockIdx.y] of the program, which names its T plane (FilterInsn::i; i + 1: its F plane, numbered with the LIKE and IN
+// planes); a wavefront trip is one 64-bit word of each, laid out like `keep`: T bit = the comparison is TRUE for the row, F bit =
+// it is FALSE; neither (UNKNOWN): a column of either side is NULL, or an operation inside a side left 128 bits -- the latter rows
+// are counted, one add per block into *overflow.  Rows past n_in: neither.  Both op tables lie in the literal pool and are read
+// at wave-uniform addresses; the operand slots are named values (AggSlots): no indexed private array, no scratch.
+extern "C" __global__ void __launch_bounds__(256)
+filter_expr_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                   const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes, uint32_t n_planes,
+                   unsigned long long* overflow) {
+  __shared__ uint32_t over_s[4];
+  FilterInsn in;
+  FilterExprBlob e;
+  if (!filter_leaf(prog, n_insn, leaves, FOP_CMP_EXPR, n_planes, &in) || (unsigned long long)in.i + 1 >= n_planes || in.cmp > 5) return;
+  if (!filter_expr_blob(lits + in.lit_off, in.lit_len, &e)) return;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const FilterWords ws = filter_words(n_in);
+  unsigned long long* plane_t = planes + (uint64_t)in.i * ws.n;
+  unsigned long long* plane_f = plane_t + ws.n;
+  uint32_t n_over = 0;  // (wave-uniform: popcounts of ballots)
+  for (uint64_t w = ws.first; w < ws.n; w += ws.stride) {
+    const FilterExprRow row = {cols, filter_row(segs, seg_first, n_segs, n_in, B, w * 64 + lane), W};
+    bool t = false, known = false, over = false;
+    if (row.r.live) {
+      int sl, sr;
+      if (e.cls == FXC_FLOAT) {
+        double a = 0.0, b = 0.0;
+        sl = agg_expr_eval_f64(e.lhs, e.n_lhs, row, &a);
+        sr = agg_expr_eval_f64(e.rhs, e.n_rhs, row, &b);
+        known = sl == AGG_ROW_VALUE && sr == AGG_ROW_VALUE;
+        t = known && filter_expr_compare_f64(in.cmp, a, b);
+      } else {
+        agg_i128 a = 0, b = 0;
+        sl = agg_expr_eval_i128(e.lhs, e.n_lhs, row, &a);
+        sr = agg_expr_eval_i128(e.rhs, e.n_rhs, row, &b);
+        known = sl == AGG_ROW_VALUE && sr == AGG_ROW_VALUE;
+        over = sl != AGG_ROW_NULL && sr != AGG_ROW_NULL && !known;  // (a NULL column comes first: the row is not counted)
+        t = known && filter_expr_compare_i128(in.cmp, a, b, e.d, e.p10);
+      }
+    }
+    const unsigned long long T = __ballot(t), F = __ballot(known && !t);
+    n_over += (uint32_t)__builtin_popcountll(__ballot(over));
+    if (lane == 0) {
+      plane_t[w] = T;
+      plane_f[w] = F;
+    }
+  }
+  if (lane == 0) over_s[wave] = n_over;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long n = (unsigned long long)over_s[0] + over_s[1] + over_s[2] + over_s[3];
+    if (n) atomicAdd(overflow, n);
+  }
+}
+
 // One 64-row word of a predicate: the program prog[0, n_insn) over the trip's rows -- lane l holds input row w * 64 + l as `r`,
 // live_m = the ballot of r.live --, evaluated as the head comment says: a leaf yields two ballot words, inner nodes combine words on
 // the wavefront's own stack (stk_t / stk_f: kFilterStack words each, in LDS).  Returns the rows where the root is TRUE, live rows
@@ -399,6 +475,10 @@ __device__ __forceinline__ unsigned long long filter_eval_word(const FilterInsn*
       }
       T = match & valid_m;
       F = in.cmp & IN_HAS_NULL ? 0ull : ~match & valid_m;
+    } else if (in.op == FOP_CMP_EXPR) {
+      // both answers are there already (filter_expr_kernel): the T plane and the F plane behind it; neither bit: UNKNOWN
+      T = planes[(uint64_t)in.i * n_words + w] & live_m;
+      F = planes[((uint64_t)in.i + 1) * n_words + w] & live_m;
     } else if (in.op == FOP_TRUE) {
       T = live_m;
     } else if (in.op == FOP_FALSE) {

@@ -19,9 +19,12 @@ enum {
   FOP_NOT = 12,
   FOP_LIKE = 13,       // String / Varchar / Char against a compiled LIKE pattern: a leaf that reads its column's values, through the
                        // match bits filter_like_kernel leaves (cmp: LIKE_*, the pattern's shape; i: which of the program's mask planes)
-  FOP_IN = 14          // x IN (list): a leaf that reads its column's values, through the match bits filter_in_kernel leaves (cmp: IN_*
+  FOP_IN = 14,         // x IN (list): a leaf that reads its column's values, through the match bits filter_in_kernel leaves (cmp: IN_*
                        // flags; i: its mask plane, numbered with the LIKE planes; lit_off / lit_len: its hash set in the literal pool;
                        // lo: the FKIND_* its column must be decoded to)
+  FOP_CMP_EXPR = 15    // lhs OP rhs over two arithmetic expressions: a leaf that reads the values of every column either side names,
+                       // through the TWO planes filter_expr_kernel leaves (cmp: ORCGPU_PRED_EQ .. _GE; i: its T plane, i + 1 its F plane,
+                       // numbered with the LIKE / IN planes; lit_off / lit_len: the two op tables in the literal pool, see below; col: unused)
 };
 // does this instruction read the values of column `col` (not only its validity)?
 inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op == FOP_LIKE || op == FOP_IN; }
@@ -115,5 +118,15 @@ FILTER_HD inline unsigned long long in_float_key(double v) {
   x.d = v;
   return x.u;
 }
+
+// ---- an expression leaf, as it lies in the literal pool at lit_off (8-byte aligned, lit_len bytes) ----
+//   header, 4 x uint32: the class (FXC_*), the ops of the left side's program, the ops of the right side's, and d = the right
+//     side's scale minus the left side's as an int32 (FXC_DEC: |d| <= 38; the side of the smaller scale is multiplied by 10^|d|
+//     before the two are compared; else 0)
+//   2 x uint64: 10^|d|, low and high word
+//   the left side's program, then the right side's: AggExprOp records (agg_program.h, 24 bytes each), each program with its
+//     AX_GATE ops in front
+enum { FXC_INT = 0, FXC_DEC = 1, FXC_FLOAT = 2 };
+constexpr uint32_t kExprHeaderBytes = 32, kExprOpBytes = 24;
 
 constexpr uint32_t kFilterStack = 64;  // = ORCGPU_FILTER_MAX_DEPTH: a predicate of depth d needs at most d slots of the evaluation stack

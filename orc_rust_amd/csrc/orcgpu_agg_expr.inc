@@ -4,10 +4,45 @@
 // a tree; the tree is typed (INT / DEC / FLOAT), the Decimal scale rule applied -- the operand of lower scale of a + b is wrapped
 // into a multiplication by a power of ten --, subtrees of literals alone folded with the evaluator's own checked arithmetic, the
 // nodes labelled with the operand slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Every refusal
-// of the expression aggregates is decided here.  Included from orcgpu_agg_plan.inc, between its column description and its compiler.
+// of the expression aggregates is decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
+//
+// The row filter's expression leaf (ORCGPU_PRED_CMP_EXPR: lhs OP rhs) has its two sides compiled here too (compile_pair, called by
+// orcgpu_filter_plan.inc): one parse, one typing, one scale rule, one folding and one labelling for both users.  What differs is
+// said by `predicate`: the class is decided over both sides together, a Date column takes part as int64 days, a side may hold no
+// column at all, and the columns an expression cannot take are ORCGPU_UNSUPPORTED.  The file is self-contained: it describes a
+// column by what the typing needs (AggExprCol), not by what the aggregates know of it.
+#pragma once
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
 #include "device/agg_expr_eval.h"
+#include "device/filter_program.h"
+#include "orcgpu_decimal.inc"
 
 namespace orcgpu_host {
+
+enum { ACLASS_INT, ACLASS_DATE, ACLASS_BOOL, ACLASS_FLOAT, ACLASS_DEC, ACLASS_TS, ACLASS_OTHER };
+inline int agg_class(int32_t t) {
+  switch (t) {
+    case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG: return ACLASS_INT;
+    case ORCGPU_T_DATE: return ACLASS_DATE;
+    case ORCGPU_T_BOOLEAN: return ACLASS_BOOL;
+    case ORCGPU_T_FLOAT: case ORCGPU_T_DOUBLE: return ACLASS_FLOAT;
+    case ORCGPU_T_DECIMAL: return ACLASS_DEC;
+    case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT: return ACLASS_TS;
+    default: return ACLASS_OTHER;
+  }
+}
+
+// What the typing reads of a column
+struct AggExprCol {
+  int32_t orc_type = 0;
+  uint32_t scale = 0;            // Decimal
+  uint32_t fkind = FKIND_OTHER;  // FKIND_*: what the decode makes of its values
+  bool dict_out = false;         // read as a dictionary column
+  bool ts_wide = false;          // a Timestamp decoded to Decimal128(38, 9)
+};
 
 static_assert(sizeof(AggExprOp) == 24, "agg_program.h: the record the kernels read");
 static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
@@ -16,11 +51,12 @@ enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
 
 struct AggExprCompiler {
   const char* const* names;
-  const AggCol* cols;
+  const AggExprCol* cols;
   uint32_t n_columns;
   const char* op_name;
   char* err;
   size_t err_len;
+  bool predicate = false;  // the two sides of a row filter's expression leaf (the head comment)
 
   struct Node {
     uint32_t op = 0;        // ORCGPU_AGG_EXPR_*, or kScale: this library's own "times 10^k"
@@ -89,7 +125,13 @@ struct AggExprCompiler {
     return ORCGPU_OK;
   }
 
-  // the class of the expression off its leaves, or the refusal
+  // the class a column takes part as: a Date column is int64 days under a predicate, and nothing an expression takes elsewhere
+  int col_class(uint32_t col) const {
+    const int k = agg_class(cols[col].orc_type);
+    return predicate && k == ACLASS_DATE ? ACLASS_INT : k;
+  }
+
+  // the class of the expression off its leaves (all of `t`: both sides of a predicate's leaf), or the refusal
   int classify() {
     const char *float_col = nullptr, *exact_col = nullptr;
     bool f64_lit = false, dec_lit = false, dec_col = false;
@@ -99,34 +141,38 @@ struct AggExprCompiler {
         dec_lit |= n.value_type == ORCGPU_PV_DECIMAL128;
       }
       if (n.op != ORCGPU_AGG_EXPR_COLUMN) continue;
-      const AggCol& c = cols[n.col];
+      const AggExprCol& c = cols[n.col];
       const char* name = names[n.col];
-      if (c.d.dict_out) return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is read as a dictionary column: %s on its keys is not supported", name, op_name);
-      const int k = agg_class(c.d.orc_type);
-      if (k == ACLASS_TS && (c.d.ts_unit > 3 || c.d.width != 8))
+      if (c.dict_out) return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is read as a dictionary column: %s on its keys is not supported", name, op_name);
+      const int k = col_class(n.col);
+      if (predicate && k != ACLASS_INT && k != ACLASS_FLOAT && k != ACLASS_DEC)
+        return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' cannot stand in the expression of %s: Boolean, String / Varchar / Char / Binary, Timestamp and nested columns are not supported there", name, op_name);
+      if (k == ACLASS_TS && c.ts_wide)
         return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is a Timestamp decoded to Decimal128(38, 9): %s is not supported on it", name, op_name);
       if (k != ACLASS_INT && k != ACLASS_FLOAT && k != ACLASS_DEC) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s does not take column '%s'", op_name, name);
       const uint32_t want = k == ACLASS_FLOAT ? FKIND_FLOAT : k == ACLASS_DEC ? FKIND_DEC128 : FKIND_INT;
-      if (filter_col_kind(c.d) != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type the expression of %s needs", name, op_name);
+      if (c.fkind != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type the expression of %s needs", name, op_name);
       if (k == ACLASS_FLOAT && !float_col) float_col = name;
       if (k != ACLASS_FLOAT && !exact_col) exact_col = name;
       dec_col |= k == ACLASS_DEC;
     }
-    if (!float_col && !exact_col) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s holds no column", op_name);
+    if (!float_col && !exact_col && !predicate) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s holds no column", op_name);
+    if (!float_col && !exact_col && f64_lit && dec_lit)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside a DECIMAL128 literal", op_name);
     if (float_col && exact_col)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s mixes the Float / Double column '%s' with the integer or Decimal column '%s'", op_name, float_col, exact_col);
     if (f64_lit && exact_col)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside the integer or Decimal column '%s'", op_name, exact_col);
     if (dec_lit && float_col)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s'", op_name, float_col);
-    cls = float_col ? XCLASS_FLOAT : (dec_col || dec_lit) ? XCLASS_DEC : XCLASS_INT;
+    cls = float_col || (!exact_col && f64_lit) ? XCLASS_FLOAT : (dec_col || dec_lit) ? XCLASS_DEC : XCLASS_INT;
     if (cls == XCLASS_FLOAT)
       for (Node& n : t)
         if (n.op == ORCGPU_AGG_EXPR_LITERAL && n.value_type == ORCGPU_PV_INT64) {
           const long long i = (long long)n.iv;
           const double d = (double)i;
           if (!(d >= -9223372036854775808.0 && d < 9223372036854775808.0 && (long long)d == i))
-            return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an INT64 literal beside column '%s' in the expression of %s is not exact as a double", float_col, op_name);
+            return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an INT64 literal beside column '%s' in the expression of %s is not exact as a double", float_col ? float_col : "", op_name);
           n.fv = d;
         }
     return ORCGPU_OK;
@@ -211,7 +257,7 @@ struct AggExprCompiler {
     const Node& x = t[n];
     AggExprOp o{};
     if (x.op == ORCGPU_AGG_EXPR_COLUMN) {
-      const int k = agg_class(cols[x.col].d.orc_type);
+      const int k = col_class(x.col);
       o.op = k == ACLASS_FLOAT ? AX_PUSH_F64 : k == ACLASS_DEC ? AX_PUSH_DEC : AX_PUSH_INT;
       o.col = x.col;
     } else if (x.op == ORCGPU_AGG_EXPR_LITERAL) {
@@ -240,15 +286,13 @@ struct AggExprCompiler {
     ops.push_back(o);
   }
 
-  // The program of `e` goes behind `ops`; kind / scale: the AK_EXPR_* kind and the root's scale (DEC)
-  int compile(const orcgpu_agg_expr* e, std::vector<AggExprOp>& ops, uint32_t& kind, int32_t& scale) {
+  // pre-order nodes -> a tree behind what `t` holds; root: its root
+  int parse_expr(const orcgpu_agg_expr* e, int& root) {
     if (!e || !e->nodes || !e->n_nodes) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: %s without an expression", op_name);
     if (e->n_nodes > ORCGPU_AGG_EXPR_MAX_NODES) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s has more than ORCGPU_AGG_EXPR_MAX_NODES (32) nodes", op_name);
     src = e->nodes;
     n_src = e->n_nodes;
     at = 0;
-    t.clear();
-    int root = -1;
     bool bad_decimal = false;
     {
       const int rc = parse(root);
@@ -261,10 +305,21 @@ struct AggExprCompiler {
       return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a DECIMAL128 literal of the expression of %s over column '%s' is not 16 bytes of |value| < 10^38 at a scale of 0 .. 38", op_name, first_column);
     }
     if (at != n_src) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s has nodes left over behind its tree", op_name);
+    return ORCGPU_OK;
+  }
+  // the class of everything parsed, and the columns' scales
+  int type_leaves() {
     if (const int rc = classify()) return rc;
     if (cls == XCLASS_DEC)
       for (Node& n : t)
-        if (n.op == ORCGPU_AGG_EXPR_COLUMN) n.scale = agg_class(cols[n.col].d.orc_type) == ACLASS_DEC ? (int)cols[n.col].scale : 0;
+        if (n.op == ORCGPU_AGG_EXPR_COLUMN) n.scale = agg_class(cols[n.col].orc_type) == ACLASS_DEC ? (int)cols[n.col].scale : 0;
+    return ORCGPU_OK;
+  }
+  // The tree at `root`, parsed from e and typed at its leaves -> its program behind `ops`: scales, folding, labels, the gates,
+  // the ops.  root: the node that stands for it afterwards
+  int finish(const orcgpu_agg_expr* e, int& root, std::vector<AggExprOp>& ops) {
+    src = e->nodes;
+    n_src = e->n_nodes;
     if (const int rc = type_node(root, root)) return rc;
     if (t[root].label > kAggExprSlots)
       return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
@@ -297,8 +352,53 @@ struct AggExprCompiler {
       ops.resize(first_op);
       return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
     }
+    return ORCGPU_OK;
+  }
+
+  // The program of `e` goes behind `ops`; kind / scale: the AK_EXPR_* kind and the root's scale (DEC)
+  int compile(const orcgpu_agg_expr* e, std::vector<AggExprOp>& ops, uint32_t& kind, int32_t& scale) {
+    t.clear();
+    int root = -1;
+    if (const int rc = parse_expr(e, root)) return rc;
+    if (const int rc = type_leaves()) return rc;
+    if (const int rc = finish(e, root, ops)) return rc;
     kind = cls == XCLASS_FLOAT ? AK_EXPR_F64 : cls == XCLASS_DEC ? AK_EXPR_DEC : AK_EXPR_INT;
     scale = cls == XCLASS_DEC ? t[root].scale : 0;
+    return ORCGPU_OK;
+  }
+
+  // One side of a predicate's leaf, compiled: its program, and what its root has become -- a literal (the side held literals
+  // alone, or folded to one), a bare column, or neither
+  struct Side {
+    std::vector<AggExprOp> ops;
+    int scale = 0;  // DEC
+    bool is_lit = false, is_col = false;
+    agg_i128 iv = 0;  // is_lit, INT / DEC
+    double fv = 0.0;  // is_lit, FLOAT
+    uint32_t col = 0;  // is_col
+  };
+  // lhs OP rhs: both sides parsed, typed TOGETHER (`cls` is the leaf's), then each finished on its own
+  int compile_pair(const orcgpu_agg_expr* lhs, const orcgpu_agg_expr* rhs, Side& l, Side& r) {
+    t.clear();
+    int rl = -1, rr = -1;
+    if (const int rc = parse_expr(lhs, rl)) return rc;
+    if (const int rc = parse_expr(rhs, rr)) return rc;
+    if (const int rc = type_leaves()) return rc;
+    const orcgpu_agg_expr* es[2] = {lhs, rhs};
+    int roots[2] = {rl, rr};
+    Side* sides[2] = {&l, &r};
+    for (int k = 0; k < 2; k++) {
+      Side& s = *sides[k];
+      s = Side{};
+      if (const int rc = finish(es[k], roots[k], s.ops)) return rc;
+      const Node& n = t[roots[k]];
+      s.scale = cls == XCLASS_DEC ? n.scale : 0;
+      s.is_lit = n.op == ORCGPU_AGG_EXPR_LITERAL;
+      s.is_col = n.op == ORCGPU_AGG_EXPR_COLUMN;
+      s.iv = n.iv;
+      s.fv = n.fv;
+      s.col = n.col;
+    }
     return ORCGPU_OK;
   }
 };

@@ -34,17 +34,16 @@ struct AggPlan {
   char err[256] = {0};
 };
 
-enum { ACLASS_INT, ACLASS_DATE, ACLASS_BOOL, ACLASS_FLOAT, ACLASS_DEC, ACLASS_TS, ACLASS_OTHER };
-inline int agg_class(int32_t t) {
-  switch (t) {
-    case ORCGPU_T_BYTE: case ORCGPU_T_SHORT: case ORCGPU_T_INT: case ORCGPU_T_LONG: return ACLASS_INT;
-    case ORCGPU_T_DATE: return ACLASS_DATE;
-    case ORCGPU_T_BOOLEAN: return ACLASS_BOOL;
-    case ORCGPU_T_FLOAT: case ORCGPU_T_DOUBLE: return ACLASS_FLOAT;
-    case ORCGPU_T_DECIMAL: return ACLASS_DEC;
-    case ORCGPU_T_TIMESTAMP: case ORCGPU_T_TIMESTAMP_INSTANT: return ACLASS_TS;
-    default: return ACLASS_OTHER;
-  }
+// (ACLASS_* / agg_class: orcgpu_agg_expr.inc, which the row filter's plan compiler has included already)
+// a column as the expression compiler reads it
+inline AggExprCol agg_expr_col(const AggCol& c) {
+  AggExprCol x;
+  x.orc_type = c.d.orc_type;
+  x.scale = c.scale;
+  x.fkind = filter_col_kind(c.d);
+  x.dict_out = c.d.dict_out;
+  x.ts_wide = agg_class(c.d.orc_type) == ACLASS_TS && (c.d.ts_unit > 3 || c.d.width != 8);
+  return x;
 }
 inline const char* agg_op_name(uint32_t op) {
   static const char* const n[] = {"COUNT_ROWS", "COUNT", "SUM", "MIN", "MAX", "SUM_PRODUCT", "SUM_EXPR", "AVG", "AVG_EXPR"};
@@ -104,7 +103,9 @@ struct AggCompiler {
       in.op = sp.op;
       if (sp.op > ORCGPU_AGG_OP_AVG_EXPR) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: unknown op in the list%s", "");
       if (sp.op == ORCGPU_AGG_OP_SUM_EXPR || sp.op == ORCGPU_AGG_OP_AVG_EXPR) {
-        AggExprCompiler x{names, cols, n_columns, agg_op_name(sp.op), out.err, sizeof(out.err)};
+        std::vector<AggExprCol> xcols(n_columns);
+        for (uint32_t k = 0; k < n_columns; k++) xcols[k] = agg_expr_col(cols[k]);
+        AggExprCompiler x{names, xcols.data(), n_columns, agg_op_name(sp.op), out.err, sizeof(out.err)};
         const size_t first = out.ops.size();
         if (const int rc = x.compile(exprs ? &exprs[s] : nullptr, out.ops, in.kind, in.scale)) return rc;
         in.col = (uint32_t)first;
@@ -202,11 +203,20 @@ inline int agg_compile_conds(const orcgpu_agg_filter* filters, uint32_t n, const
         memcpy(out.err, one.err, sizeof(out.err));
         return rc;
       }
-      for (const FilterInsn& in : one.prog)
+      for (const FilterInsn& in : one.prog) {
         if (fop_reads_values(in.op) && in.col < n_columns && cols[in.col].d.dict_out) {
           filter_dict_refusal(out.err, sizeof(out.err), names[in.col] ? names[in.col] : "", in.col);
           return ORCGPU_UNSUPPORTED;
         }
+        if (in.op != FOP_CMP_EXPR) continue;
+        std::vector<FilterExprRead> reads;  // (an expression leaf reads the values of several columns)
+        filter_expr_reads(one, in, reads);
+        for (const FilterExprRead& rd : reads)
+          if (rd.col < n_columns && cols[rd.col].d.dict_out) {
+            filter_dict_refusal(out.err, sizeof(out.err), names[rd.col] ? names[rd.col] : "", rd.col);
+            return ORCGPU_UNSUPPORTED;
+          }
+      }
       const uint32_t first = filter_plan_append(out.conds, one);
       out.cond_spans.push_back(AggCondSpan{first, (uint32_t)one.prog.size()});
       first_spec.push_back(s);

@@ -131,10 +131,12 @@ int filter_upload(FilterCall& f, const FilterWorkspace& ws) {
   hipStream_t st = ctx->stream;
   const orcgpu_host::FilterPlan& plan = f.plan;
   const uint32_t n_segs = (uint32_t)f.segs.size(), n_insn = (uint32_t)plan.prog.size(), n_like = (uint32_t)plan.like_leaves.size(), n_set = (uint32_t)plan.in_leaves.size();
+  const uint32_t n_expr = (uint32_t)plan.expr_leaves.size();
   if (n_insn) memcpy(host.data() + ws.o_prog, plan.prog.data(), n_insn * sizeof(FilterInsn));
   if (!plan.lits.empty()) memcpy(host.data() + ws.o_lits, plan.lits.data(), plan.lits.size());
   if (n_like) memcpy(host.data() + ws.o_leaves, plan.like_leaves.data(), (size_t)n_like * 4);
   if (n_set) memcpy(host.data() + ws.o_leaves + (size_t)n_like * 4, plan.in_leaves.data(), (size_t)n_set * 4);
+  if (n_expr) memcpy(host.data() + ws.o_leaves + ((size_t)n_like + n_set) * 4, plan.expr_leaves.data(), (size_t)n_expr * 4);
   if (n_segs) {
     memcpy(host.data() + ws.o_segs, f.segs.data(), (size_t)n_segs * sizeof(SelBatch));
     memcpy(host.data() + ws.o_first, f.seg_first.data(), (size_t)n_segs * 8);
@@ -142,7 +144,7 @@ int filter_upload(FilterCall& f, const FilterWorkspace& ws) {
   if (f.nc) memcpy(host.data() + ws.o_cols, f.fcols.data(), (size_t)f.nc * sizeof(FilterCol));
   if (!f.n_in) return ORCGPU_OK;
   HIP_TRY(ctx, ctx->upload(f.X, host.data(), ws.up_bytes, st));
-  HIP_TRY(ctx, hipMemsetAsync(f.at<unsigned long long>(ws.o_counters), 0, ws.n_counters * 8, st));
+  HIP_TRY(ctx, hipMemsetAsync(f.at<unsigned long long>(ws.o_counters), 0, (ws.n_counters + 1) * 8, st));  // (+ 1: the overflow count)
   return ORCGPU_OK;
 }
 
@@ -161,7 +163,7 @@ int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
   const SelBatch* d_segs = f.at<const SelBatch>(ws.o_segs);
   const unsigned long long* d_first = f.at<const unsigned long long>(ws.o_first);
   unsigned long long *d_keep = f.at<unsigned long long>(ws.o_keep), *d_planes = f.at<unsigned long long>(ws.o_planes);
-  const uint32_t n_planes = n_like + n_set;
+  const uint32_t n_expr = (uint32_t)plan.expr_leaves.size(), n_planes = (uint32_t)plan.n_planes();
   const uint32_t eval_blocks = (uint32_t)std::min<uint64_t>((ws.n_words + 3) / 4, 16384);
   if (n_like) {  // the matcher first: the evaluation reads its bits
     hipLaunchKernelGGL(filter_like_kernel, dim3(eval_blocks, n_like), dim3(256), 0, st, d_prog, n_insn, d_leaves, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W,
@@ -171,6 +173,11 @@ int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
   if (n_set) {  // ... and the set membership of the IN leaves
     hipLaunchKernelGGL(filter_in_kernel, dim3(eval_blocks, n_set), dim3(256), 0, st, d_prog, n_insn, d_leaves + n_like, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in, f.B, f.W,
                        d_planes, n_planes);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (n_expr) {  // ... and the two sides of the expression leaves, compared: a T and an F plane each
+    hipLaunchKernelGGL(filter_expr_kernel, dim3(eval_blocks, n_expr), dim3(256), 0, st, d_prog, n_insn, d_leaves + n_like + n_set, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in,
+                       f.B, f.W, d_planes, n_planes, f.at<unsigned long long>(ws.o_overflow));
     HIP_TRY(ctx, hipGetLastError());
   }
   if (!f.has_filter) return ORCGPU_OK;
@@ -204,7 +211,7 @@ int filter_run_front(FilterCall& f, const FilterWorkspace& ws, std::vector<uint6
                        d_counters + 1 + (uint64_t)o * nb_max, d_counters + 1 + ((uint64_t)f.nc + o) * nb_max);
   HIP_TRY(ctx, hipGetLastError());
   // ---- the filter's one wait: the kept row count, null counts and string bytes per output batch ----
-  HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_counters, ws.n_counters * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_counters, (ws.n_counters + 1) * 8, hipMemcpyDeviceToHost, st));  // (the overflow count behind them)
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return ORCGPU_OK;
 }
@@ -334,8 +341,9 @@ int result_compile_filter(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_
 
 // Open, front, place, gather, adopt
 int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::FilterPlan& plan, uint64_t* rows_seen, uint64_t* rows_kept,
-                       const char* const* column_names = nullptr, uint32_t n_names = 0) {
+                       const char* const* column_names = nullptr, uint32_t n_names = 0, uint64_t* overflow_rows = nullptr) {
   if (rows_seen) *rows_seen = 0;
+  if (overflow_rows) *overflow_rows = 0;
   if (rows_kept) *rows_kept = 0;
   if (r->status) return r->status;  // a failed decode is left as it is
   if (const int rc = filter_refuse(ctx, r)) return rc;
@@ -343,9 +351,10 @@ int result_filter_plan(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_host::Fil
   if (const int rc = filter_open(f, rows_seen)) return rc;
   const FilterWorkspace ws = filter_workspace(f);
   if (const int rc = filter_reserve(f, ws, ws.bytes, "the row filter")) return rc;
-  std::vector<uint64_t> back(ws.n_counters, 0);
+  std::vector<uint64_t> back(ws.n_counters + 1, 0);
   if (const int rc = filter_run_front(f, ws, back)) return rc;
   const uint64_t kept = back[0];
+  if (overflow_rows) *overflow_rows = back[ws.n_counters];
   if (kept > f.n_in) {
     set_err(ctx, "row filter: %llu rows kept of %llu", (unsigned long long)kept, (unsigned long long)f.n_in);
     return ORCGPU_UNEXPECTED;

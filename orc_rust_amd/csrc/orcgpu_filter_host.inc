@@ -66,6 +66,19 @@ inline void filter_dict_refusal(char* out, size_t n, const char* name, uint32_t 
 // the instruction's column in *col.
 inline int filter_check_kinds(const orcgpu_host::FilterPlan& plan, const uint32_t* kinds, const FilterColDesc* descs, uint32_t nc, uint32_t* col) {
   for (auto& in : plan.prog) {
+    if (in.op == FOP_CMP_EXPR) {  // every column either side names: there, and -- where its values are read -- decoded to what the op loads
+      std::vector<orcgpu_host::FilterExprRead> reads;
+      orcgpu_host::filter_expr_reads(plan, in, reads);
+      if (reads.empty()) return ORCGPU_MISMATCHED_SCHEMA;  // (a leaf without its op tables)
+      for (const auto& rd : reads) {
+        *col = rd.col;
+        if (rd.col >= nc) return ORCGPU_MISMATCHED_SCHEMA;
+        if (rd.kind == orcgpu_host::kFilterExprAnyKind) continue;
+        if (descs[rd.col].dict_out) return ORCGPU_UNSUPPORTED;
+        if (kinds[rd.col] != rd.kind) return ORCGPU_MISMATCHED_SCHEMA;
+      }
+      continue;
+    }
     if (!fop_reads_values(in.op)) continue;
     *col = in.col;
     if (in.col < nc && descs[in.col].dict_out) return ORCGPU_UNSUPPORTED;
@@ -78,10 +91,13 @@ inline int filter_check_kinds(const orcgpu_host::FilterPlan& plan, const uint32_
 // leave, and the second upload behind the wait [o_jobs, o_jobs + up2_bytes): the gather's jobs and the output batches' char bases.
 struct FilterWorkspace {
   uint64_t n_words = 0, nb_max = 0;  // 64-bit words of a mask over the input rows; output batches at most
-  uint64_t o_prog = 0, o_lits = 0, o_leaves = 0, o_cols = 0, o_segs = 0, o_first = 0, up_bytes = 0;  // (o_leaves: the LIKE leaves, then the IN leaves)
+  uint64_t o_prog = 0, o_lits = 0, o_leaves = 0, o_cols = 0, o_segs = 0, o_first = 0, up_bytes = 0;  // (o_leaves: the LIKE leaves, the IN leaves, the expression leaves)
   std::vector<uint64_t> o_cbase;  // per string column: the char bases of the decode's uniform batches
   uint64_t o_keep = 0, o_cnt = 0, o_woff = 0, o_sums = 0, o_counters = 0, o_rows = 0, o_planes = 0;
   uint64_t n_counters = 0;  // the kept row count, then null counts and string bytes [column][batch]
+  // ... and ONE word behind them (in the 16 bytes every part is given beyond its size), zeroed and fetched with them: the (row, leaf)
+  // evaluations of the expression leaves in which an operation left 128 bits (filter_expr_kernel)
+  uint64_t o_overflow = 0;
   uint64_t o_jobs = 0, o_obase = 0, up2_bytes = 0;
   uint64_t bytes = 0;
 
@@ -93,7 +109,7 @@ struct FilterWorkspace {
     nb_max = (std::min(n_in, out_rows_max) + B - 1) / B;
     o_prog = t.take(plan.prog.size() * sizeof(FilterInsn) + 16);
     o_lits = t.take(plan.lits.size() + 16);
-    o_leaves = t.take(plan.n_planes() * 4 + 16);
+    o_leaves = t.take(plan.n_planes() * 4 + 16);  // (an expression leaf has two planes and one entry)
     o_cols = t.take((uint64_t)nc * kFilterColBytes + 16);
     o_segs = t.take((uint64_t)n_segs * kFilterSegBytes + 16);
     o_first = t.take((uint64_t)n_segs * 8 + 16);
@@ -107,6 +123,7 @@ struct FilterWorkspace {
     o_sums = t.take(((n_words + 2047) / 2048) * 8 + 16);
     n_counters = 1 + 2ull * nc * nb_max;
     o_counters = t.take(n_counters * 8 + 16);
+    o_overflow = o_counters + n_counters * 8;
     o_rows = t.take(n_in * 4 + 16);
     // (the LIKE and IN leaves' planes of match bits, numbered together and laid out like `keep`)
     o_planes = t.take((uint64_t)plan.n_planes() * n_words * 8 + 16);

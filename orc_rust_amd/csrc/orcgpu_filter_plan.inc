@@ -3,13 +3,17 @@
 // the post-order program filter_eval_kernel runs (device/filter_program.h).  Names become column indices, the type table
 // of orcgpu_result_filter is applied, Decimal128 and TimestampNs literals are brought to the column's own scale / unit, LIKE
 // patterns are cut into the parts filter_like_kernel matches (tests/hostcheck/filter_plan_like_check.cpp), IN lists become the
-// hash sets filter_in_kernel probes (orcgpu_in.inc, tests/hostcheck/filter_plan_in_check.cpp), and the depth is bounded.
+// hash sets filter_in_kernel probes (orcgpu_in.inc, tests/hostcheck/filter_plan_in_check.cpp), the two sides of an expression leaf
+// (lhs OP rhs) become the op tables filter_expr_kernel interprets -- compiled by the expression aggregates' compiler,
+// orcgpu_agg_expr.inc (tests/hostcheck/filter_plan_expr_check.cpp) --, and the depth is bounded.
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "device/filter_expr_eval.h"
 #include "device/filter_program.h"
+#include "orcgpu_agg_expr.inc"
 #include "orcgpu_decimal.inc"
 #include "orcgpu_in.inc"
 #include "orcgpu_like.inc"
@@ -17,6 +21,12 @@
 namespace orcgpu_host {
 
 static_assert(ORCGPU_PRED_IN == 17 && ORCGPU_PRED_LITERAL == 18 && ORCGPU_IN_MAX_VALUES == 65536, "the IN leaf of include/orcgpu.h");
+static_assert(ORCGPU_PRED_CMP_EXPR == 19 && ORCGPU_PRED_EXPR_COLUMN == 20 && ORCGPU_PRED_EXPR_NEG == 25 &&
+                  ORCGPU_PRED_EXPR_LITERAL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_LITERAL && ORCGPU_PRED_EXPR_ADD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_ADD &&
+                  ORCGPU_PRED_EXPR_SUB - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_SUB && ORCGPU_PRED_EXPR_MUL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MUL &&
+                  ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG,
+              "the expression leaf of include/orcgpu.h: its nodes are the expression aggregates', 20 further on");
+static_assert((int)FXC_INT == (int)XCLASS_INT && (int)FXC_DEC == (int)XCLASS_DEC && (int)FXC_FLOAT == (int)XCLASS_FLOAT && sizeof(AggExprOp) == kExprOpBytes, "filter_program.h: an expression leaf's blob");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
 
 struct FilterPlan {
@@ -24,8 +34,10 @@ struct FilterPlan {
   std::vector<uint8_t> lits;  // the string literals, one after the other
   uint32_t depth = 0;         // of the predicate (a leaf alone: 1)
   // the leaves with a mask plane, as instruction indices in program order: the grids of filter_like_kernel and filter_in_kernel
-  std::vector<uint32_t> like_leaves, in_leaves;
-  size_t n_planes() const { return like_leaves.size() + in_leaves.size(); }  // (numbered together, in leaf order: FilterInsn::i)
+  // ... and of filter_expr_kernel.  A LIKE and an IN leaf own one plane, an expression leaf TWO (T, then F; neither bit: UNKNOWN)
+  std::vector<uint32_t> like_leaves, in_leaves, expr_leaves;
+  size_t n_planes() const { return like_leaves.size() + in_leaves.size() + 2 * expr_leaves.size(); }  // (numbered together, in leaf order: FilterInsn::i)
+  size_t n_leaves() const { return like_leaves.size() + in_leaves.size() + expr_leaves.size(); }
   char err[256] = {0};
 };
 
@@ -86,9 +98,13 @@ struct FilterCompiler {
     i128 lit = 0;
     if (!dec_literal(n.s, n.s_len, n.i, lit))
       return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the Decimal128 literal for column '%s' is malformed (16 bytes, a scale of 0 .. 38, a magnitude below 10^38)", column);
+    return decimal_value(lit, (int)n.i, column, col, in);
+  }
+  // ... the literal as a value: |lit| < 10^38 at lit_scale 0 .. 38
+  int decimal_value(i128 lit, int lit_scale, const char* column, uint32_t col, FilterInsn& in) {
     const int col_scale = params ? params[col] : 0;
     if (col_scale < 0 || col_scale > kDecMaxDigits) return fail(ORCGPU_UNSUPPORTED, "row filter: the Decimal column '%s' has the scale %lld", column, col_scale);
-    const int d = col_scale - (int)n.i;
+    const int d = col_scale - lit_scale;
     i128 L = 0;
     if (d >= 0) {
       if (!dec_scale_up(lit, d, L)) L = lit < 0 ? dec_i128_min() : dec_i128_max();
@@ -257,11 +273,131 @@ struct FilterCompiler {
         at += n.n_children;
         return irc;
       }
+      case ORCGPU_PRED_CMP_EXPR:
+        return cmp_expr(n, at);
+      case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: case ORCGPU_PRED_EXPR_NEG:
+        return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
       default:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: unknown node op%s %lld", "", n.op);
     }
+  }
+  // One side of an expression leaf: the subtree at `at` as the expression aggregates' nodes; `at` then stands behind it
+  int expr_side(uint32_t& at, std::vector<orcgpu_agg_expr_node>& side) {
+    if (at >= n_nodes) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the node list ends inside an expression%s (%lld nodes)", "", n_nodes);
+    const orcgpu_predicate_node& n = nodes[at++];
+    uint32_t kids = 0;
+    switch (n.op) {
+      case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: kids = 0; break;
+      case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: kids = 2; break;
+      case ORCGPU_PRED_EXPR_NEG: kids = 1; break;
+      default: return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds expression nodes only%s (node op %lld)", "", n.op);
+    }
+    if (n.n_children != kids) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node with the wrong number of children%s (%lld)", "", n.n_children);
+    if (n.op == ORCGPU_PRED_EXPR_LITERAL && n.value_is_null)
+      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds no NULL literal%s (node %lld)", "", (long long)at - 1);
+    if (side.size() > ORCGPU_AGG_EXPR_MAX_NODES) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a side of an expression comparison has more than ORCGPU_AGG_EXPR_MAX_NODES (%s%lld) nodes", "", ORCGPU_AGG_EXPR_MAX_NODES);
+    orcgpu_agg_expr_node x{};
+    x.op = (uint32_t)(n.op - ORCGPU_PRED_EXPR_COLUMN);
+    x.column = n.column;
+    x.value_type = n.value_type;
+    x.i = n.i;
+    x.f = n.f;
+    x.s = n.s;
+    x.s_len = n.s_len;
+    side.push_back(x);
+    for (uint32_t k = 0; k < kids; k++)
+      if (const int rc = expr_side(at, side)) return rc;
+    return ORCGPU_OK;
+  }
+  static uint32_t mirrored(uint32_t cmp) {  // a OP b == b OP' a
+    return cmp == ORCGPU_PRED_LT ? ORCGPU_PRED_GT : cmp == ORCGPU_PRED_GT ? ORCGPU_PRED_LT : cmp == ORCGPU_PRED_LE ? ORCGPU_PRED_GE : cmp == ORCGPU_PRED_GE ? ORCGPU_PRED_LE : cmp;
+  }
+  // An expression leaf, lhs OP rhs (include/orcgpu.h).  Both sides are compiled by the expression aggregates' compiler, typed
+  // together; then by shape: two literals: TRUE / FALSE; a bare column against a literal its own comparison takes: that comparison,
+  // mirrored when the column is on the right; everything else: FOP_CMP_EXPR with the two op tables in the literal pool and two
+  // mask planes.
+  int cmp_expr(const orcgpu_predicate_node& n, uint32_t& at) {
+    if (n.n_children != 2) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression comparison has two sides%s (%lld children)", "", n.n_children);
+    if (n.i < ORCGPU_PRED_EQ || n.i > ORCGPU_PRED_GE) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the operator of an expression comparison is %s%lld (ORCGPU_PRED_EQ .. _GE: 0 .. 5)", "", n.i);
+    std::vector<orcgpu_agg_expr_node> ln, rn;
+    if (const int rc = expr_side(at, ln)) return rc;
+    if (const int rc = expr_side(at, rn)) return rc;
+    std::vector<AggExprCol> xcols(n_columns);
+    for (uint32_t k = 0; k < n_columns; k++) {
+      AggExprCol& c = xcols[k];
+      c.orc_type = kinds[k];
+      const int cls = agg_class(kinds[k]);
+      c.scale = cls == ACLASS_DEC && params && params[k] > 0 ? (uint32_t)params[k] : 0;
+      // (what the decode made of the column is checked against the compiled leaf per call: filter_check_kinds)
+      c.fkind = cls == ACLASS_FLOAT ? FKIND_FLOAT : cls == ACLASS_DEC ? FKIND_DEC128 : (cls == ACLASS_INT || cls == ACLASS_DATE) ? FKIND_INT : FKIND_OTHER;
+    }
+    AggExprCompiler x{names, xcols.data(), n_columns, "a comparison", out.err, sizeof(out.err)};
+    x.predicate = true;
+    const orcgpu_agg_expr le{ln.data(), (uint32_t)ln.size()}, re{rn.data(), (uint32_t)rn.size()};
+    AggExprCompiler::Side l, r;
+    if (const int rc = x.compile_pair(&le, &re, l, r)) {
+      // (the compiler's messages speak for the aggregates: here it is the row filter that refuses)
+      std::string msg = out.err;
+      if (msg.compare(0, 10, "aggregate:") == 0) msg = "row filter:" + msg.substr(10);
+      snprintf(out.err, sizeof(out.err), "%s", msg.c_str());
+      return rc;
+    }
+    const uint32_t cmp = (uint32_t)n.i;
+    const int32_t d = x.cls == XCLASS_DEC ? r.scale - l.scale : 0;  // (both 0 .. 38)
+    const agg_i128 p10 = agg_pow10((uint32_t)(d < 0 ? -d : d));
+    if (l.is_lit && r.is_lit) {
+      const bool t = x.cls == XCLASS_FLOAT ? filter_expr_compare_f64(cmp, l.fv, r.fv) : filter_expr_compare_i128(cmp, l.iv, r.iv, d, p10);
+      emit(t ? FOP_TRUE : FOP_FALSE);
+      return ORCGPU_OK;
+    }
+    if ((l.is_col && r.is_lit) || (l.is_lit && r.is_col)) {
+      const AggExprCompiler::Side &c = l.is_col ? l : r, &v = l.is_col ? r : l;
+      const int kind = agg_class(kinds[c.col]);
+      FilterInsn in{};
+      in.cmp = l.is_col ? cmp : mirrored(cmp);
+      in.col = c.col;
+      if (x.cls == XCLASS_FLOAT) {
+        in.op = FOP_CMP_FLOAT;
+        in.f = v.fv;
+        out.prog.push_back(in);
+        return ORCGPU_OK;
+      }
+      if (x.cls == XCLASS_INT && v.iv >= (agg_i128)INT64_MIN && v.iv <= (agg_i128)INT64_MAX) {
+        in.op = FOP_CMP_INT;
+        in.i = (long long)v.iv;
+        out.prog.push_back(in);
+        return ORCGPU_OK;
+      }
+      const agg_i128 lim = dec_pow10(kDecMaxDigits);
+      if (x.cls == XCLASS_DEC && kind == ACLASS_DEC && v.iv > -lim && v.iv < lim && v.scale >= 0 && v.scale <= kDecMaxDigits) {
+        in.op = FOP_CMP_DEC128;
+        if (const int rc = decimal_value(v.iv, v.scale, names[c.col], c.col, in)) return rc;
+        out.prog.push_back(in);
+        return ORCGPU_OK;
+      }
+    }
+    FilterInsn in{};
+    in.op = FOP_CMP_EXPR;
+    in.cmp = cmp;
+    in.i = (long long)out.n_planes();  // its T plane; i + 1: its F plane
+    out.expr_leaves.push_back((uint32_t)out.prog.size());
+    while (out.lits.size() & 7) out.lits.push_back(0);
+    in.lit_off = out.lits.size();
+    const size_t n_ops = l.ops.size() + r.ops.size();
+    out.lits.resize(in.lit_off + kExprHeaderBytes + n_ops * sizeof(AggExprOp));
+    put32(out.lits, in.lit_off, (uint32_t)x.cls);
+    put32(out.lits, in.lit_off + 4, (uint32_t)l.ops.size());
+    put32(out.lits, in.lit_off + 8, (uint32_t)r.ops.size());
+    put32(out.lits, in.lit_off + 12, (uint32_t)d);
+    const unsigned long long pw[2] = {(unsigned long long)p10, (unsigned long long)((agg_u128)p10 >> 64)};
+    memcpy(out.lits.data() + in.lit_off + 16, pw, 16);
+    memcpy(out.lits.data() + in.lit_off + kExprHeaderBytes, l.ops.data(), l.ops.size() * sizeof(AggExprOp));
+    memcpy(out.lits.data() + in.lit_off + kExprHeaderBytes + l.ops.size() * sizeof(AggExprOp), r.ops.data(), r.ops.size() * sizeof(AggExprOp));
+    in.lit_len = (uint32_t)(out.lits.size() - in.lit_off);
+    out.prog.push_back(in);
+    return ORCGPU_OK;
   }
   // A LIKE leaf.  The pattern is cut at its unescaped `%` into parts of literal bytes and `_` marks; since a `_` takes exactly the
   // code point that stands there, a part matched from a given start has one length and the kernel never backtracks: the first part
@@ -436,6 +572,7 @@ inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, 
   out.lits.clear();
   out.like_leaves.clear();
   out.in_leaves.clear();
+  out.expr_leaves.clear();
   out.depth = 0;
   out.err[0] = 0;
   FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, params, out};
@@ -452,6 +589,26 @@ inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, 
   return ORCGPU_OK;
 }
 
+// The columns whose VALUES an expression leaf reads (its gates read validity alone), each with the FKIND_* it must be decoded to:
+// what fop_reads_values / fop_value_kind say of the other leaves, for a leaf that names several columns.  A gate's column is
+// listed too, with kind FKIND_OTHER + 1 ("any"): it must exist.
+struct FilterExprRead {
+  uint32_t col, kind;
+};
+constexpr uint32_t kFilterExprAnyKind = FKIND_DEC128 + 1;
+inline void filter_expr_reads(const FilterPlan& plan, const FilterInsn& in, std::vector<FilterExprRead>& out) {
+  FilterExprBlob b;
+  if (in.op != FOP_CMP_EXPR || in.lit_off > plan.lits.size() || in.lit_len > plan.lits.size() - in.lit_off || !filter_expr_blob(plan.lits.data() + in.lit_off, in.lit_len, &b)) return;
+  for (uint32_t k = 0; k < b.n_lhs + b.n_rhs; k++) {
+    AggExprOp op;
+    memcpy(&op, plan.lits.data() + in.lit_off + kExprHeaderBytes + (size_t)k * sizeof(AggExprOp), sizeof(op));
+    if (op.op == AX_GATE) out.push_back({op.col, kFilterExprAnyKind});
+    else if (op.op == AX_PUSH_INT) out.push_back({op.col, FKIND_INT});
+    else if (op.op == AX_PUSH_DEC) out.push_back({op.col, FKIND_DEC128});
+    else if (op.op == AX_PUSH_F64) out.push_back({op.col, FKIND_FLOAT});
+  }
+}
+
 // `from`, a plan compiled on its own against the same columns, behind `into`: its instructions behind into's, its literals behind
 // into's from an 8-byte boundary (what the IN tables and the LIKE patterns are aligned to), its mask planes numbered behind
 // into's, its leaves in into's leaf lists -- so that one literal pool, one launch of filter_like_kernel and one of filter_in_kernel
@@ -464,12 +621,13 @@ inline uint32_t filter_plan_append(FilterPlan& into, const FilterPlan& from) {
   const unsigned long long lit0 = into.lits.size();
   into.lits.insert(into.lits.end(), from.lits.begin(), from.lits.end());
   for (FilterInsn in : from.prog) {
-    if (in.op == FOP_CMP_STRING || in.op == FOP_LIKE || in.op == FOP_IN) in.lit_off += lit0;
-    if ((in.op == FOP_LIKE && in.cmp != LIKE_ALL) || (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE))) in.i += planes;
+    if (in.op == FOP_CMP_STRING || in.op == FOP_LIKE || in.op == FOP_IN || in.op == FOP_CMP_EXPR) in.lit_off += lit0;
+    if ((in.op == FOP_LIKE && in.cmp != LIKE_ALL) || (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE)) || in.op == FOP_CMP_EXPR) in.i += planes;
     into.prog.push_back(in);
   }
   for (const uint32_t k : from.like_leaves) into.like_leaves.push_back(first + k);
   for (const uint32_t k : from.in_leaves) into.in_leaves.push_back(first + k);
+  for (const uint32_t k : from.expr_leaves) into.expr_leaves.push_back(first + k);
   if (from.depth > into.depth) into.depth = from.depth;
   return first;
 }

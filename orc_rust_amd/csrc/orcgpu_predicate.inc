@@ -564,6 +564,46 @@ struct PredEval {
     }
     for (size_t g = 0; g < result.size(); g++) result[g] = g < c->stats.size() ? any[g] : result[g];
   }
+  // the index behind the expression subtree at `at` (ORCGPU_PRED_EXPR_* nodes with their own child counts), or 0 for what is none
+  size_t expr_end(size_t at) const {
+    if (at >= nodes.size()) return 0;
+    const PredNode& n = nodes[at];
+    const uint32_t kids = n.op == ORCGPU_PRED_EXPR_COLUMN || n.op == ORCGPU_PRED_EXPR_LITERAL ? 0 : n.op == ORCGPU_PRED_EXPR_NEG ? 1
+                        : n.op == ORCGPU_PRED_EXPR_ADD || n.op == ORCGPU_PRED_EXPR_SUB || n.op == ORCGPU_PRED_EXPR_MUL ? 2 : ~0u;
+    if (kids == ~0u || n.n_children != kids) return 0;
+    size_t next = at + 1;
+    for (uint32_t k = 0; k < kids; k++)
+      if (!(next = expr_end(next))) return 0;
+    return next;
+  }
+  // An expression leaf (ORCGPU_PRED_CMP_EXPR; the reference has none) is a sound "might match" and never fails the evaluation:
+  // what it cannot take is the row filter's to report.  One form prunes: a bare column against ONE literal node is the comparison
+  // it equals, the operator mirrored when the column stands on the right, by the rules of comparison() -- where those rules would
+  // fail the evaluation (an INT64 literal beside Decimal statistics, a column without an index) every group is kept instead.
+  // Returns the index behind the leaf; a malformed one fails the evaluation like any malformed node list.
+  size_t cmp_expr(size_t at, bool neg, std::vector<uint8_t>& result) {
+    const PredNode& n = nodes[at];
+    const size_t l = at + 1, r = n.n_children == 2 ? expr_end(l) : 0, end = r ? expr_end(r) : 0;
+    if (!end || n.i < ORCGPU_PRED_EQ || n.i > ORCGPU_PRED_GE) {
+      failed = true;
+      return nodes.size();
+    }
+    const bool col_left = nodes[l].op == ORCGPU_PRED_EXPR_COLUMN && nodes[r].op == ORCGPU_PRED_EXPR_LITERAL;
+    const bool col_right = nodes[l].op == ORCGPU_PRED_EXPR_LITERAL && nodes[r].op == ORCGPU_PRED_EXPR_COLUMN;
+    if ((!col_left && !col_right) || failed) return end;
+    int op = (int)n.i;
+    if (col_right) op = op == ORCGPU_PRED_LT ? ORCGPU_PRED_GT : op == ORCGPU_PRED_GT ? ORCGPU_PRED_LT : op == ORCGPU_PRED_LE ? ORCGPU_PRED_GE : op == ORCGPU_PRED_GE ? ORCGPU_PRED_LE : op;
+    PredNode leaf = nodes[col_left ? r : l];  // the literal, as the comparison node it stands for
+    leaf.op = op;
+    leaf.n_children = 0;
+    leaf.column = nodes[col_left ? l : r].column;
+    leaf.has_column = true;
+    std::vector<uint8_t> t = result;
+    comparison(leaf, neg ? negate(op) : op, t);
+    if (failed) failed = false;  // (kept whole)
+    else result = t;
+    return end;
+  }
   // one subtree in pre-order; returns the index behind it.  `neg`: under a NOT (pushed down as the reference does)
   size_t eval(size_t at, bool neg, std::vector<uint8_t>& result) {
     if (at >= nodes.size() || failed) {
@@ -583,6 +623,7 @@ struct PredEval {
       like(n, neg, result);
       return at + 1;
     }
+    if (n.op == ORCGPU_PRED_CMP_EXPR) return cmp_expr(at, neg, result);
     if (n.op <= ORCGPU_PRED_GE) {
       comparison(n, neg ? negate(n.op) : n.op, result);
       return at + 1;

@@ -88,7 +88,7 @@ struct orcgpu_reader {
   // the row filter's program, from the first next_batch on
   bool filter_ready = false, filter_failed = false;
   orcgpu_host::FilterPlan filter_plan;
-  std::atomic<uint64_t> filter_seen{0}, filter_kept{0};
+  std::atomic<uint64_t> filter_seen{0}, filter_kept{0}, filter_overflow{0};
   // the aggregates' instructions, from orcgpu_reader_aggregate on; every decoded stripe is aggregated where the filter and the
   // copy back would stand
   bool aggs_done = false;
@@ -305,10 +305,11 @@ void reader_read_metadata_ahead(orcgpu_reader* rd) {
 // its failing batch.
 int reader_filter_result(orcgpu_reader* rd, orcgpu_result* res) {
   if (res->status) return ORCGPU_OK;
-  uint64_t seen = 0, kept = 0;
-  const int rc = result_filter_plan(rd->ctx, res, rd->filter_plan, &seen, &kept);
+  uint64_t seen = 0, kept = 0, overflow = 0;
+  const int rc = result_filter_plan(rd->ctx, res, rd->filter_plan, &seen, &kept, nullptr, 0, &overflow);
   rd->filter_seen += seen;
   rd->filter_kept += kept;
+  rd->filter_overflow += overflow;
   return rc;
 }
 
@@ -334,9 +335,16 @@ int reader_compile_filter(orcgpu_reader* rd) {
   // a comparison on a dictionary-output column would have to be evaluated on the entries: refused, by name, before anything is read
   const std::vector<size_t> roots = rd->proj.roots();
   for (auto& in : rd->filter_plan.prog) {
-    if (!fop_reads_values(in.op) || in.col >= names.size()) continue;
-    if (rd->proj.cols[roots[in.col]].dict) {
-      set_err(rd->ctx, "row filter: column '%s' is read as a dictionary column (orcgpu_reader_set_dictionary_columns): a comparison on it is not supported", names[in.col]);
+    std::vector<uint32_t> read;  // the columns whose values the leaf reads: its own, or every one an expression leaf names
+    if (in.op == FOP_CMP_EXPR) {
+      std::vector<FilterExprRead> reads;
+      filter_expr_reads(rd->filter_plan, in, reads);
+      for (const FilterExprRead& x : reads)
+        if (x.kind != kFilterExprAnyKind) read.push_back(x.col);
+    } else if (fop_reads_values(in.op)) read.push_back(in.col);
+    for (const uint32_t col : read) {
+      if (col >= names.size() || !rd->proj.cols[roots[col]].dict) continue;
+      set_err(rd->ctx, "row filter: column '%s' is read as a dictionary column (orcgpu_reader_set_dictionary_columns): a comparison on it is not supported", names[col]);
       return ORCGPU_UNSUPPORTED;
     }
   }

@@ -59,6 +59,11 @@ int orcgpu_reader_filter_rows(const orcgpu_reader* rd, uint64_t* rows_seen, uint
   if (rows_kept) *rows_kept = rd->filter_kept.load();
   return ORCGPU_OK;
 }
+int orcgpu_reader_filter_overflow_rows(const orcgpu_reader* rd, uint64_t* rows) {
+  if (!rd || !rows) return ORCGPU_INVALID_ARGUMENT;
+  *rows = rd->filter_overflow.load();
+  return ORCGPU_OK;
+}
 int orcgpu_reader_set_row_group_pruning(orcgpu_reader* rd, int on) {
   if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
   rd->prune = on != 0;

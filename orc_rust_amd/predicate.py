@@ -8,6 +8,10 @@ import decimal
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL, AND, OR, NOT = range(11)
 LIKE = 16  # (11 .. 15 are unknown ops)
 IN, LITERAL = 17, 18  # an IN leaf, and one value of its list
+CMP_EXPR = 19  # lhs OP rhs over two arithmetic expressions; its subtrees are made of the nodes below
+EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(20, 26)  # ORCGPU_PRED_EXPR_*: aggregate.EXPR_* + 20
+_CMP_OPS = {"=": EQ, "!=": NE, "<": LT, "<=": LE, ">": GT, ">=": GE}
+_CMP_SIGNS = {v: k for k, v in _CMP_OPS.items()}
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
 _EPOCH = datetime.datetime(1970, 1, 1)
 
@@ -91,11 +95,34 @@ class PredicateValue:
 
 class Predicate:
     """Predicate::{Comparison, IsNull, IsNotNull, And, Or, Not} with the reference's constructors (predicate.rs:98-180), and
-    this library's own LIKE leaf (like / not_like / starts_with / ends_with / contains) and IN leaf (in_list / not_in)."""
+    this library's own LIKE leaf (like / not_like / starts_with / ends_with / contains), IN leaf (in_list / not_in) and
+    expression leaf (compare: lhs OP rhs over arithmetic expressions of columns and literals)."""
 
     def __init__(self, op, column=None, value=None, children=()):
         self.op, self.column, self.value, self.children = op, column, value, list(children)
         self.escape = None  # LIKE: the escape character
+        self.cmp, self.exprs = None, ()  # CMP_EXPR: EQ .. GE, and the two sides (aggregate.Expr)
+
+    @classmethod
+    def compare(cls, lhs, op, rhs):
+        """lhs OP rhs (ORCGPU_PRED_CMP_EXPR, this library's own): each side an aggregate.Expr -- col(name), lit(v), + - * and
+        unary - -- or a plain int / float / decimal.Decimal, which lit() wraps; op one of "=", "!=", "<", "<=", ">", ">=".
+        Evaluated exactly, per row, on the GPU: UNKNOWN where a column of either side is NULL or an operation inside a side leaves
+        128 bits.  `col("a") < col("b")`, `.eq(x)` and `.ne(x)` on an Expr build the same."""
+        from .aggregate import Expr, lit  # (aggregate.py imports this module)
+        if not isinstance(op, str) or op not in _CMP_OPS:
+            raise ValueError("Predicate.compare: the operator is one of %s, got %r" % (", ".join(sorted(_CMP_OPS)), op))
+        sides = []
+        for x in (lhs, rhs):
+            if not isinstance(x, Expr):
+                try:
+                    x = lit(x)
+                except TypeError:
+                    raise TypeError("Predicate.compare: a side is an Expr, an int, a float or a decimal.Decimal, not %s" % type(x).__name__) from None
+            sides.append(x)
+        p = cls(CMP_EXPR)
+        p.cmp, p.exprs = _CMP_OPS[op], tuple(sides)
+        return p
 
     @classmethod
     def comparison(cls, column, op, value):
@@ -197,6 +224,8 @@ class Predicate:
             return "%s(%r)" % (name, self.column)
         if self.op == IN:
             return "in_list(%r, %r)" % (self.column, [c.value for c in self.children])
+        if self.op == CMP_EXPR:
+            return "(%r %s %r)" % (self.exprs[0], _CMP_SIGNS[self.cmp], self.exprs[1])
         if self.op == LIKE:
             return "like(%r, %r%s)" % (self.column, self.value.value, "" if self.escape is None else ", escape=%r" % self.escape)
         return "%s(%r, %r)" % (name, self.column, self.value)
@@ -205,10 +234,37 @@ class Predicate:
         """-> (ctypes array of PredicateNode in pre-order, objects to keep alive)."""
         out, keep = [], []
 
+        def walk_expr(e):  # aggregate.Expr -> ORCGPU_PRED_EXPR_* nodes, filled as Expr.flatten fills an AggExprNode
+            n = PredicateNode()
+            n.op = e.op + EXPR_COLUMN
+            n.n_children = len(e.children)
+            if e.op + EXPR_COLUMN == EXPR_COLUMN:
+                keep.append(e.column.encode())
+                n.column = keep[-1]
+            elif e.op + EXPR_COLUMN == EXPR_LITERAL:
+                n.value_type = e.value_type
+                if e.value_type == PV_DECIMAL128:
+                    unscaled, scale = e.value
+                    keep.append(int(unscaled).to_bytes(16, "little", signed=True))
+                    n.s, n.s_len, n.i = keep[-1], 16, int(scale)
+                elif e.value_type == PV_FLOAT64:
+                    n.f = e.value
+                else:
+                    n.i = e.value
+            out.append(n)
+            for c in e.children:
+                walk_expr(c)
+
         def walk(p):
             n = PredicateNode()
             n.op = p.op
             n.n_children = len(p.children)
+            if p.op == CMP_EXPR:
+                n.n_children, n.i = 2, p.cmp
+                out.append(n)
+                for e in p.exprs:
+                    walk_expr(e)
+                return
             if p.column is not None:
                 b = p.column.encode()
                 keep.append(b)
