@@ -663,10 +663,12 @@ __device__ __forceinline__ void dict_offsets_body(const int64_t* dlens, const ui
   __shared__ uint64_t wsum[4];
   __shared__ uint64_t carry_s;
   __shared__ int bad_s;
+  __shared__ unsigned long long neg_s;  // sum of the negative lengths, which the offsets take as 0
   uint64_t n = scalars[dict_n_idx];
   if (threadIdx.x == 0) {
     carry_s = 0;
     bad_s = 0;
+    neg_s = 0;
   }
   __syncthreads();
   for (uint64_t s = 0; s < n; s += 256) {
@@ -674,6 +676,7 @@ __device__ __forceinline__ void dict_offsets_body(const int64_t* dlens, const ui
     int64_t l = i < n ? dlens[i] : 0;
     if (l < 0) {
       atomicOr(&bad_s, 1);
+      atomicAdd(&neg_s, (unsigned long long)l);
       l = 0;
     }
     uint64_t v = (uint64_t)l;
@@ -696,8 +699,12 @@ __device__ __forceinline__ void dict_offsets_body(const int64_t* dlens, const ui
     uint64_t total = carry_s;
     dict_off[n] = (int32_t)(total > 0x7fffffffull ? 0x7fffffff : total);
     // construction errors fail the whole stripe decoder (new_string_decoder `?`, string.rs:70-72): index 0
-    const bool failed = total > 0x7fffffffull || bad_s || total > scalars[data_len_idx];
-    if (total > 0x7fffffffull) report_err64(err, 0, ORC_E_OFFSET_OVERFLOW);
+    // the reference's order (next_byte_batch, as for a direct column's batch): the i64 sum of the lengths as they are, negative
+    // ones included and wrapping, above i32::MAX is OffsetOverflow; only then does a negative length surface as an Arrow error;
+    // a sum that wrapped below zero asks for more bytes than the stream has
+    const long long signed_total = (long long)(total + neg_s);
+    const bool failed = signed_total > 0x7fffffffll || bad_s || total > scalars[data_len_idx];
+    if (signed_total > 0x7fffffffll) report_err64(err, 0, ORC_E_OFFSET_OVERFLOW);
     else if (bad_s) report_err64(err, 0, ORC_E_ARROW);
     else if (total > scalars[data_len_idx]) report_err64(err, 0, ORC_E_ARROW | ORC_E_EOF);  // offsets past the values buffer (try_new)
     // what the UTF-8 checks look at: nothing when the dictionary failed already (they come last in try_new)
