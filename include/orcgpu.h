@@ -441,7 +441,10 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_EXPR_COLUMN = 20 /* `column`: a projected root column; no children */,
        ORCGPU_PRED_EXPR_LITERAL = 21 /* value_type ORCGPU_PV_INT64: i; _FLOAT64: f; _DECIMAL128: s / s_len / i; no children */,
        ORCGPU_PRED_EXPR_ADD = 22, ORCGPU_PRED_EXPR_SUB = 23, ORCGPU_PRED_EXPR_MUL = 24 /* exactly two children */,
-       ORCGPU_PRED_EXPR_NEG = 25 /* exactly one child */ };
+       ORCGPU_PRED_EXPR_NEG = 25 /* exactly one child */,
+       ORCGPU_PRED_IN_SET = 26 /* x IN SET s, this library's own: a leaf with column and i = orcgpu_key_set_id of a sealed key set of
+                                  the same context; no children.  There is no NOT IN SET: put ORCGPU_PRED_NOT above the leaf.  See
+                                  "key sets" below */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
 #define ORCGPU_IN_MAX_BYTES (4u << 20)
@@ -921,6 +924,58 @@ int orcgpu_result_top_k(orcgpu_ctx* ctx, orcgpu_result* r, const orcgpu_predicat
                         uint64_t* rows_kept, uint64_t* rows_out);
 int orcgpu_reader_set_top_k(orcgpu_reader* r, const orcgpu_sort_key* keys, uint32_t n_keys, uint32_t k);
 int orcgpu_reader_top_k_order(orcgpu_reader* r, uint64_t* positions, uint64_t cap, uint64_t* n);
+
+/* ---- key sets: a semi-join filter against a key set built on the GPU (this library's own) ------------------------------------------
+ * `A.key IN (SELECT B.key FROM B WHERE ...)`: the rows of A whose key appears among the kept rows of B.  The BUILD side collects
+ * the distinct non-NULL keys of one column over the kept rows of one or more reads into a hash set that stays in HBM, and whether
+ * any kept row's key was NULL; the PROBE side names the sealed set in a predicate leaf, ORCGPU_PRED_IN_SET.  No key crosses the link.
+ *
+ *   - orcgpu_key_set_create: capacity is fixed here.  max_keys: 1 .. ORCGPU_KEY_SET_MAX_KEYS (else ORCGPU_INVALID_ARGUMENT); the
+ *     table holds the power of two >= 2 x max_keys slots of 8 bytes, at least 64.  Memory that cannot be had: ORCGPU_HIP_ERROR, as
+ *     for every buffer of the library.  ORCGPU_KEY_SET_HASH_BITS = N (1 .. 32) in the environment, read by this call, makes the
+ *     build and every probe of the set use N bits of a key's hash: long probe chains, the same membership (a testing aid).
+ *   - orcgpu_reader_collect_keys drains the reader the way orcgpu_reader_aggregate does: every stripe is decoded, the row selection
+ *     and the row filter are applied as a keep mask only, and the kept rows' keys are inserted where they lie -- no compaction, no
+ *     gather, no copy back: no batch is produced, orcgpu_reader_d2h_bytes stays 0, and the insert adds no host wait per stripe.
+ *     `column`: a projected root column.  Several readers may collect into one set before it is sealed (a build side split over
+ *     files).  A reader with aggregates or a top-k, and one that has handed out a batch: ORCGPU_INVALID_ARGUMENT.  A sharded reader
+ *     collects its shard's keys only.  orcgpu_result_collect_keys is the same for one hand-decoded result (nodes: the row filter,
+ *     n_nodes = 0: none; column_names: one per column of the result), as orcgpu_result_aggregate is to the reader call.
+ *   - Key columns, on both sides: Byte, Short, Int, Long and Date, all taken as int64, as an integer comparison takes them.
+ *     ORCGPU_UNSUPPORTED, the message naming the column: a Timestamp column (the units and zones of two files need not agree), a
+ *     Decimal, Float / Double, Boolean, String / Varchar / Char / Binary column, one read as a dictionary column, a nested one.
+ *     ORCGPU_INVALID_ARGUMENT: an unknown or unprojected column; a sealed (or failed) set passed to collect; an unsealed or failed
+ *     set, or one of another context, named by a predicate.
+ *   - orcgpu_key_set_seal is the build's ONE host wait.  info: the distinct keys, whether a kept row's key was NULL, and the input
+ *     rows the collects went through (behind the row selection, in front of the row filter).  More than max_keys distinct keys
+ *     arrived: ORCGPU_UNSUPPORTED, the message gives the limit, and the set is unusable from then on (collect and predicates refuse
+ *     it; free it).  After a seal the set is read-only; sealing it again returns the same info.
+ *   - orcgpu_key_set_id: unique among all sets of the process, hence within the context; 0 for NULL.
+ *   - orcgpu_key_set_free: the handle goes now; the set's memory goes when the last reader, result call or plan whose compiled
+ *     filter names it is gone -- a reader that filters by a set may be read to its end after the set has been freed.  Free every
+ *     set before orcgpu_close.
+ *
+ * SEMANTICS, in one rule: `x IN SET s` is exactly ORCGPU_PRED_IN over the values the build side's kept rows held, NULLs included.
+ * So a NULL row is UNKNOWN; an empty set is FALSE everywhere (UNKNOWN everywhere when all it saw was NULLs); has_null turns every
+ * non-match into UNKNOWN, so NOT over such a leaf keeps nothing -- which is what SQL's `IN (subquery)` requires.  The leaf lives
+ * in the filter's language: it serves the row filter, an aggregate's FILTER (WHERE ...) and the top-k's filter alike, beside every
+ * other leaf.  As a pruning predicate (orcgpu_reader_set_predicate) it is a sound "might match": it keeps every row group and never
+ * fails the evaluation.  A program without such a leaf launches exactly what it launched before there were key sets. */
+#define ORCGPU_KEY_SET_MAX_KEYS (1u << 26)
+typedef struct orcgpu_key_set orcgpu_key_set;
+typedef struct {
+  uint64_t n_keys;    /* distinct non-NULL keys                                        */
+  uint64_t rows_seen; /* input rows of the collects                                    */
+  int32_t has_null;   /* a kept row's key was NULL                                     */
+  int32_t pad;
+} orcgpu_key_set_info;
+int orcgpu_key_set_create(orcgpu_ctx* ctx, uint64_t max_keys, orcgpu_key_set** set);
+int orcgpu_reader_collect_keys(orcgpu_reader* r, const char* column, orcgpu_key_set* set);
+int orcgpu_result_collect_keys(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                               const char* const* column_names, uint32_t n_columns, const char* column, orcgpu_key_set* set);
+int orcgpu_key_set_seal(orcgpu_key_set* set, orcgpu_key_set_info* info);
+uint64_t orcgpu_key_set_id(const orcgpu_key_set* set);
+void orcgpu_key_set_free(orcgpu_key_set* set);
 /* Read-ahead: how many decoded stripes the reader may be ahead of the caller (default 2 -- every result set in flight costs a pinned host copy of a stripe --, at most 8; 0 = none: every stripe is
  * read, staged, decoded and copied back inside the orcgpu_reader_next_batch call that needs it).  With read-ahead two threads
  * of the reader work beside the caller: one reads and stages the stripes to come, one decodes the stripes staged so far

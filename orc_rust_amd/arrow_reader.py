@@ -193,6 +193,29 @@ class ArrowReaderBuilder:
         r._group_by = A.check_group_by(group_by) if group_by is not None else None
         return r
 
+    def collect_keys(self, column, max_keys=1 << 20, into=None):
+        """The build side of a semi-join (orcgpu_reader_collect_keys): builds the reader and drains it -- every stripe is decoded,
+        the builder's row selection and row filter are applied as a keep mask, and the kept rows' distinct non-NULL keys of `column`
+        (a projected Byte, Short, Int, Long or Date column) go into a hash set that stays on the GPU; no batch is copied back.
+        Returns the orc_rust_amd.KeySet, sealed, for Predicate.in_set; max_keys (1 .. 2^26) fixes its capacity, and more distinct
+        keys than that fail the seal.  into: a KeySet that is still open (KeySet(ctx, max_keys)) -- the keys are added to it and it
+        is left open, so that several files can build one set; seal() it afterwards."""
+        from .key_set import KeySet, check_collect_args
+        check_collect_args(column, max_keys, into)
+        ks = into if into is not None else KeySet(self._ctx, max_keys)
+        reader = self.build()
+        try:
+            reader.collect_keys(column, ks)
+            if into is None:
+                ks.seal()
+        except Exception:
+            if into is None:
+                ks.close()
+            raise
+        finally:
+            reader.close()
+        return ks
+
     def with_top_k(self, by, k):
         """ORDER BY by LIMIT k (orcgpu_reader_set_top_k): `by` is a list of orc_rust_amd.top_k.SortKey (a bare column name and a
         (name, "asc" | "desc") tuple are accepted for one).  The reader then iterates every stripe's own at most k best kept rows,
@@ -291,6 +314,14 @@ class ArrowReader:
             raise StopIteration
         self._ctx._check(rc)
         return list(out)[:len(specs)] if raw else A.values_of(out, specs)
+
+    def collect_keys(self, column, key_set):
+        """Drains this reader into an open KeySet (orcgpu_reader_collect_keys): what ArrowReaderBuilder.collect_keys does, for a
+        caller that wants the reader's filter_rows() / d2h_bytes() afterwards.  The set is left open."""
+        from .key_set import check_collect_args
+        check_collect_args(column, key_set.max_keys if hasattr(key_set, "max_keys") else 1, key_set)
+        self._ctx._check(self._ctx.L.orcgpu_reader_collect_keys(self._h, column.encode(), key_set._h))
+        return key_set
 
     def reads_ahead(self):
         """Whether the reader's read-ahead threads are at work on its context right now (orcgpu_reader_reads_ahead)"""

@@ -44,6 +44,8 @@ EXPORTS = [
     "orcgpu_writer_set_bloom_filter",
     "orcgpu_result_top_k", "orcgpu_reader_set_top_k", "orcgpu_reader_top_k_order",
     "orcgpu_reader_filter_overflow_rows",
+    "orcgpu_key_set_create", "orcgpu_reader_collect_keys", "orcgpu_result_collect_keys", "orcgpu_key_set_seal", "orcgpu_key_set_id",
+    "orcgpu_key_set_free",
 ]
 
 
@@ -141,6 +143,10 @@ ENC_ON_DEVICE = 1
 ARROW = {"bool": 10, "int8": 11, "int16": 12, "int32": 13, "int64": 14, "float32": 15, "float64": 16, "utf8": 17, "binary": 18,
          "large_utf8": 25, "large_binary": 26}
 ARROW_DICTIONARY_UTF8 = 27  # include/orcgpu.h: ORCGPU_ARROW_DICTIONARY_UTF8 (orcgpu_column.arrow_target: int32 keys + one dictionary per stripe)
+
+
+class KeySetInfo(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("rows_seen", C.c_uint64), ("has_null", C.c_int32), ("pad", C.c_int32)]
 
 
 class BatchView(C.Structure):
@@ -319,6 +325,14 @@ def load():
     L.orcgpu_writer_set_bloom_filter.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_double]
     L.orcgpu_compress_stream.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64)]
+    L.orcgpu_key_set_create.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_collect_keys.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+    L.orcgpu_result_collect_keys.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_void_p]
+    L.orcgpu_key_set_seal.argtypes = [C.c_void_p, C.POINTER(KeySetInfo)]
+    L.orcgpu_key_set_id.restype = C.c_uint64
+    L.orcgpu_key_set_id.argtypes = [C.c_void_p]
+    L.orcgpu_key_set_free.restype = None
+    L.orcgpu_key_set_free.argtypes = [C.c_void_p]
     _lib = L
     return L
 

@@ -17,7 +17,8 @@
 //                         a lane per short value, the wavefront on 64 candidate starts at once for a long one.
 //   filter_in_kernel      likewise for IN leaves: per leaf a plane of "the row is valid and its key is in the list", from a hash
 //                         set the host has built (filter_program.h): staged in LDS up to 32 KiB, probed in global memory above;
-//                         a lane per value, so a row costs one probe however long the list is.
+//                         a lane per value, so a row costs one probe however long the list is.  A set leaf (FOP_IN_SET) is the
+//                         same leaf against a table key_set_seal_kernel left in that layout (key_set_kernels.hip).
 //   filter_expr_kernel    likewise for expression leaves (lhs OP rhs): per leaf TWO planes, the rows where the comparison is TRUE
 //                         and the rows where it is FALSE (neither: UNKNOWN -- a NULL column on either side, or an operation inside
 //                         a side that left 128 bits, which it counts).  A lane per row interprets both sides' op tables
@@ -56,12 +57,13 @@ constexpr uint32_t kFilterShortString = 32;    // values up to this many bytes a
 
 // Leaf blockIdx.y of a plane kernel's leaf list: its instruction.  false -- the whole block leaves -- for what only a damaged
 // upload holds: an index past the program, an instruction of another op, a plane past the workspace's.
+// (op_too: a second op the list may hold -- filter_in_kernel's list holds FOP_IN and FOP_IN_SET leaves)
 __device__ __forceinline__ bool filter_leaf(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, uint32_t op, uint32_t n_planes,
-                                            FilterInsn* in) {
+                                            FilterInsn* in, uint32_t op_too = ~0u) {
   const uint32_t k = leaves[blockIdx.y];
   if (k >= n_insn) return false;
   *in = prog[k];
-  return in->op == op && (unsigned long long)in->i < n_planes;
+  return (in->op == op || in->op == op_too) && (unsigned long long)in->i < n_planes;
 }
 
 // ---- LIKE: the compiled pattern of filter_program.h, staged in LDS ----
@@ -195,40 +197,7 @@ filter_like_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leav
 }
 
 // ---- IN: the hash set of filter_program.h ----
-struct InTable {
-  uint32_t kind, n_slots, min_len, max_len, bytes;  // n_slots = 0: no usable table, nothing matches
-  const unsigned long long* occ;
-  const uint8_t* slots;
-  const uint8_t* base;  // strings: key offsets count from here, and stay below `bytes`
-};
-// The header, checked against the table's bytes: a table whose parts do not fit is treated as empty.
-__device__ __forceinline__ InTable in_table(const uint8_t* tab, uint32_t bytes) {
-  InTable t = {};
-  t.base = tab;
-  if (bytes < kInHeaderBytes) return t;
-  const uint32_t* h = reinterpret_cast<const uint32_t*>(tab);
-  t.kind = h[0];
-  t.n_slots = h[1];
-  t.min_len = h[3];
-  t.max_len = h[4];
-  t.bytes = bytes;
-  t.base = tab;
-  const uint64_t occ_bytes = ((uint64_t)t.n_slots + 63) / 64 * 8, slot_bytes = t.kind == IN_KEY_I64 ? 8 : 16;
-  if (t.kind > IN_KEY_STRING || t.n_slots < 2 || (t.n_slots & (t.n_slots - 1)) || kInHeaderBytes + occ_bytes + (uint64_t)t.n_slots * slot_bytes > bytes) t.n_slots = 0;
-  t.occ = reinterpret_cast<const unsigned long long*>(tab + kInHeaderBytes);
-  t.slots = tab + kInHeaderBytes + occ_bytes;
-  return t;
-}
-// Linear probing from the hash's own slot: at most n_slots steps, ended by the key or by a free slot.
-__device__ __forceinline__ bool in_probe_i64(const InTable& t, unsigned long long key) {
-  const uint32_t mask = t.n_slots - 1;
-  uint32_t s = in_hash_i64(key) & mask;
-  for (uint32_t step = 0; step < t.n_slots; step++, s = (s + 1) & mask) {
-    if (!((t.occ[s >> 6] >> (s & 63)) & 1)) return false;
-    if (reinterpret_cast<const unsigned long long*>(t.slots)[s] == key) return true;
-  }
-  return false;
-}
+// (InTable, in_table and in_probe_i64: filter_program.h, where the host can call them too)
 __device__ __forceinline__ bool in_probe_dec128(const InTable& t, unsigned long long lo, unsigned long long hi) {
   const uint32_t mask = t.n_slots - 1;
   uint32_t s = in_hash_dec128(lo, hi) & mask;
@@ -301,11 +270,13 @@ filter_in_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves
                  const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes, uint32_t n_planes) {
   __shared__ unsigned long long tab_s[kInLdsBytes / 8];
   FilterInsn in;
-  if (!filter_leaf(prog, n_insn, leaves, FOP_IN, n_planes, &in) || (in.cmp & IN_NO_TABLE)) return;
+  if (!filter_leaf(prog, n_insn, leaves, FOP_IN, n_planes, &in, FOP_IN_SET) || (in.cmp & IN_NO_TABLE)) return;
   const FilterCol c = cols[in.col];
   unsigned long long* plane = planes + (uint64_t)in.i * ((n_in + 63) / 64);
-  // (lit_off and lit_len are multiples of 8 and the pool starts 256-byte aligned: whole 8-byte words)
-  const unsigned long long* g = reinterpret_cast<const unsigned long long*>(lits + in.lit_off);
+  // (lit_off and lit_len are multiples of 8 and the pool starts 256-byte aligned: whole 8-byte words.  A key set's sealed table
+  // lies in an allocation of its own, 256-byte aligned: lit_off is its address, as the host compiled it from a live, sealed set)
+  const unsigned long long* g = in.op == FOP_IN_SET ? reinterpret_cast<const unsigned long long*>((uintptr_t)in.lit_off)
+                                                    : reinterpret_cast<const unsigned long long*>(lits + in.lit_off);
   const uint32_t bytes = in.lit_len & ~7u;
   if (bytes >= kInHeaderBytes && bytes <= kInLdsBytes) {
     for (uint32_t x = threadIdx.x; x < bytes / 8; x += 256) tab_s[x] = g[x];
@@ -461,7 +432,7 @@ __device__ __forceinline__ unsigned long long filter_eval_word(const FilterInsn*
       const unsigned long long match = in.cmp == LIKE_ALL ? ~0ull : planes[(uint64_t)in.i * n_words + w];
       T = match & valid_m;
       F = ~match & valid_m;
-    } else if (in.op == FOP_IN) {
+    } else if (in.op == FOP_IN || in.op == FOP_IN_SET) {
       // the trip's membership bits are there already (filter_in_kernel); a Boolean column and a list no key of which can equal a
       // row have no plane.  With a NULL literal in the list a row that matches no key is UNKNOWN, not FALSE.
       const FilterCol c = cols[in.col];

@@ -22,18 +22,22 @@ enum {
   FOP_IN = 14,         // x IN (list): a leaf that reads its column's values, through the match bits filter_in_kernel leaves (cmp: IN_*
                        // flags; i: its mask plane, numbered with the LIKE planes; lit_off / lit_len: its hash set in the literal pool;
                        // lo: the FKIND_* its column must be decoded to)
-  FOP_CMP_EXPR = 15    // lhs OP rhs over two arithmetic expressions: a leaf that reads the values of every column either side names,
+  FOP_CMP_EXPR = 15,   // lhs OP rhs over two arithmetic expressions: a leaf that reads the values of every column either side names,
                        // through the TWO planes filter_expr_kernel leaves (cmp: ORCGPU_PRED_EQ .. _GE; i: its T plane, i + 1 its F plane,
                        // numbered with the LIKE / IN planes; lit_off / lit_len: the two op tables in the literal pool, see below; col: unused)
+  FOP_IN_SET = 16      // x IN SET s: FOP_IN against the sealed table of a device-resident key set (key_set_kernels.hip), which lies
+                       // in the layout below, kind IN_KEY_I64.  lit_off is the table's DEVICE ADDRESS, not an offset into the literal
+                       // pool; lit_len its bytes; cmp: IN_HAS_NULL or 0; i: its mask plane, numbered with the LIKE / IN planes; lo:
+                       // FKIND_INT.  filter_in_kernel probes it, filter_eval_kernel reads the plane as it reads FOP_IN's
 };
 // does this instruction read the values of column `col` (not only its validity)?
-inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op == FOP_LIKE || op == FOP_IN; }
+inline bool fop_reads_values(uint32_t op) { return op <= FOP_CMP_DEC128 || op == FOP_LIKE || op == FOP_IN || op == FOP_IN_SET; }
 // FKIND_INT holds Timestamp columns decoded to int64 (seconds .. nanoseconds) as well: the host brings the literal to the unit
 enum { FKIND_INT = 0, FKIND_FLOAT = 1, FKIND_BOOL = 2, FKIND_STRING = 3, FKIND_OTHER = 4 /* fixed width, null tests only */, FKIND_DEC128 = 5 };
 
 // the FKIND_* the column of an instruction that reads values must be decoded to (lo: FilterInsn::lo, where FOP_IN keeps its own)
 inline uint32_t fop_value_kind(uint32_t op, unsigned long long lo = 0) {
-  return op == FOP_IN ? (uint32_t)lo : op == FOP_CMP_INT ? FKIND_INT : op == FOP_CMP_FLOAT ? FKIND_FLOAT : op == FOP_CMP_BOOL ? FKIND_BOOL : op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
+  return op == FOP_IN || op == FOP_IN_SET ? (uint32_t)lo : op == FOP_CMP_INT ? FKIND_INT : op == FOP_CMP_FLOAT ? FKIND_FLOAT : op == FOP_CMP_BOOL ? FKIND_BOOL : op == FOP_CMP_DEC128 ? FKIND_DEC128 : FKIND_STRING;
 }
 
 struct FilterInsn {
@@ -66,7 +70,8 @@ constexpr uint32_t kLikeBlobMax = (kLikeHeaderWords + 2 * kLikeMaxParts) * 4 + 2
 
 // ---- the hash set of an IN leaf, as it lies in the literal pool at lit_off (8-byte aligned, lit_len bytes, a multiple of 8) ----
 //   header, 8 x uint32: key kind (IN_KEY_*), n_slots (a power of two, at least twice the keys), n_keys (distinct), the shortest and
-//     the longest key in bytes (strings), flags (IN_*), 0, 0
+//     the longest key in bytes (strings), flags (IN_*), the hash bits that are DROPPED (0: none -- every IN list; a key set built
+//     under ORCGPU_KEY_SET_HASH_BITS: the complement of its hash mask), 0
 //   occupancy, ceil(n_slots / 64) x uint64: bit s = slot s holds a key -- so every int64 is a legal key
 //   slots -- IN_KEY_I64: n_slots x uint64, the key (integers and Timestamps as int64; floats: the bits of the double, with
 //     -0.0 stored as 0.0 and no NaN); IN_KEY_DEC128: n_slots x {uint64 low, uint64 high}; IN_KEY_STRING: n_slots x {uint32 hash,
@@ -117,6 +122,49 @@ FILTER_HD inline unsigned long long in_float_key(double v) {
   } x;
   x.d = v;
   return x.u;
+}
+
+// Where a key's chain starts.  hash_mask: what of the hash counts -- all of it for an IN list, so that this is hash & mask; fewer
+// bits (a key set built under ORCGPU_KEY_SET_HASH_BITS) start every chain in the table's LAST slots, so that long chains wrap round
+// its end.
+FILTER_HD inline uint32_t in_first_slot(uint32_t hash, uint32_t hash_mask, uint32_t mask) { return ((hash & hash_mask) + ~hash_mask) & mask; }
+
+// The table as a probe sees it, and the int64 probe: for filter_in_kernel, and for the host that checks a table it has laid out
+struct InTable {
+  uint32_t kind, n_slots, min_len, max_len, bytes;  // n_slots = 0: no usable table, nothing matches
+  uint32_t hash_mask;                               // what of a key's hash counts (all of it, but for a key set built under fewer bits)
+  const unsigned long long* occ;
+  const uint8_t* slots;
+  const uint8_t* base;  // strings: key offsets count from here, and stay below `bytes`
+};
+// The header, checked against the table's bytes: a table whose parts do not fit is treated as empty.
+FILTER_HD inline InTable in_table(const uint8_t* tab, uint32_t bytes) {
+  InTable t = {};
+  t.base = tab;
+  if (bytes < kInHeaderBytes) return t;
+  const uint32_t* h = reinterpret_cast<const uint32_t*>(tab);
+  t.kind = h[0];
+  t.n_slots = h[1];
+  t.min_len = h[3];
+  t.max_len = h[4];
+  t.hash_mask = ~h[6];
+  t.bytes = bytes;
+  t.base = tab;
+  const uint64_t occ_bytes = ((uint64_t)t.n_slots + 63) / 64 * 8, slot_bytes = t.kind == IN_KEY_I64 ? 8 : 16;
+  if (t.kind > IN_KEY_STRING || t.n_slots < 2 || (t.n_slots & (t.n_slots - 1)) || kInHeaderBytes + occ_bytes + (uint64_t)t.n_slots * slot_bytes > bytes) t.n_slots = 0;
+  t.occ = reinterpret_cast<const unsigned long long*>(tab + kInHeaderBytes);
+  t.slots = tab + kInHeaderBytes + occ_bytes;
+  return t;
+}
+// Linear probing from the hash's own slot: at most n_slots steps, ended by the key or by a free slot.
+FILTER_HD inline bool in_probe_i64(const InTable& t, unsigned long long key) {
+  const uint32_t mask = t.n_slots - 1;
+  uint32_t s = in_first_slot(in_hash_i64(key), t.hash_mask, mask);
+  for (uint32_t step = 0; step < t.n_slots; step++, s = (s + 1) & mask) {
+    if (!((t.occ[s >> 6] >> (s & 63)) & 1)) return false;
+    if (reinterpret_cast<const unsigned long long*>(t.slots)[s] == key) return true;
+  }
+  return false;
 }
 
 // ---- an expression leaf, as it lies in the literal pool at lit_off (8-byte aligned, lit_len bytes) ----

@@ -47,6 +47,7 @@
 #include "device/agg_group_kernels.hip"
 #include "device/agg_group_wide_kernels.hip"
 #include "device/top_k_kernels.hip"
+#include "device/key_set_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -273,6 +274,9 @@ int call_z_lanes = -1;  // a call split over column lanes: its Zstandard path de
   // threads at once -- the read-ahead reader stages stripe k + 1 while stripe k is decoded; what the two share is guarded here:
   std::mutex pool_m;   // arena_pool (taken from by staging, given back to by orcgpu_staged_free)
   std::mutex err_m;    // `err`
+  // the key sets created on this context and not yet freed, by id (orcgpu_key_set_call.inc): what a predicate's set leaf may name
+  std::mutex key_sets_m;
+  std::map<uint64_t, struct orcgpu_key_set*> key_sets;
   struct CopyPool* copiers = nullptr;
   // writer time zones seen so far (lane 0 only): host table + its copy in HBM ({at[n] i64}{offs[n] i32})
   struct Zone {
@@ -1217,11 +1221,14 @@ struct SummaryLayout {
 #include "orcgpu_export.inc"
 #include "orcgpu_export_device.inc"
 #include "orcgpu_select.inc"
+#include "orcgpu_key_set.inc"
+orcgpu_host::KeySetRefs ctx_key_set_refs(orcgpu_ctx* ctx);  // (orcgpu_key_set_call.inc)
 #include "orcgpu_filter.inc"
 #include "orcgpu_agg.inc"
 #include "orcgpu_top_k.inc"
 #include "orcgpu_reader.inc"
 #include "orcgpu_reader_api.inc"
+#include "orcgpu_key_set_call.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"
 #include "orcgpu_writer_host.inc"

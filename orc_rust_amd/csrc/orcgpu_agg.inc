@@ -96,7 +96,8 @@ std::vector<orcgpu_host::AggCol> result_agg_cols(const orcgpu_result* r) {
 int result_compile_aggs(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters,
                         uint32_t n_specs, const char* const* column_names, orcgpu_host::AggPlan& plan) {
   const std::vector<orcgpu_host::AggCol> cols = result_agg_cols(r);
-  const int rc = orcgpu_host::agg_compile(specs, exprs, filters, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan);
+  const orcgpu_host::KeySetRefs sets = ctx_key_set_refs(ctx);  // (what a condition's set leaf may name)
+  const int rc = orcgpu_host::agg_compile(specs, exprs, filters, n_specs, column_names, cols.data(), (uint32_t)cols.size(), plan, &sets);
   if (rc) set_err(ctx, "%s", plan.err);
   return rc;
 }

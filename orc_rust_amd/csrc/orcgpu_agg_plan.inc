@@ -173,7 +173,7 @@ inline bool agg_cond_nodes_equal(const orcgpu_agg_filter& a, const orcgpu_agg_fi
 // node the same share one program and one plane; more than ORCGPU_AGG_MAX distinct ones are ORCGPU_INVALID_ARGUMENT.  A condition
 // that reads the values of a column read as a dictionary column is ORCGPU_UNSUPPORTED, as under the row filter.
 inline int agg_compile_conds(const orcgpu_agg_filter* filters, uint32_t n, const char* const* names, const AggCol* cols, uint32_t n_columns, AggPlan& out,
-                             std::vector<uint32_t>& cond_of) {
+                             std::vector<uint32_t>& cond_of, const KeySetRefs* sets = nullptr) {
   out.conds = FilterPlan{};
   out.cond_spans.clear();
   cond_of.assign(n, 0);
@@ -199,7 +199,7 @@ inline int agg_compile_conds(const orcgpu_agg_filter* filters, uint32_t n, const
         return ORCGPU_INVALID_ARGUMENT;
       }
       FilterPlan one;
-      if (const int rc = filter_compile(f.nodes, f.n_nodes, names, kinds.data(), n_columns, one, params.data())) {
+      if (const int rc = filter_compile(f.nodes, f.n_nodes, names, kinds.data(), n_columns, one, params.data(), sets)) {
         memcpy(out.err, one.err, sizeof(out.err));
         return rc;
       }
@@ -228,7 +228,7 @@ inline int agg_compile_conds(const orcgpu_agg_filter* filters, uint32_t n, const
 
 // filters: parallel to specs like exprs, or null when no spec has a condition
 inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* exprs, const orcgpu_agg_filter* filters, uint32_t n_specs, const char* const* names,
-                       const AggCol* cols, uint32_t n_columns, AggPlan& out) {
+                       const AggCol* cols, uint32_t n_columns, AggPlan& out, const KeySetRefs* sets = nullptr) {
   out.insns.clear();
   out.ops.clear();
   out.conds = FilterPlan{};
@@ -237,7 +237,7 @@ inline int agg_compile(const orcgpu_agg_spec* specs, const orcgpu_agg_expr* expr
   AggCompiler c{names, cols, n_columns, out};
   if (const int rc = c.compile(specs, exprs, n_specs)) return rc;
   std::vector<uint32_t> cond_of;  // (one instruction per spec: an AVG is its sum, finished over the count)
-  if (const int rc = agg_compile_conds(filters, n_specs, names, cols, n_columns, out, cond_of)) return rc;
+  if (const int rc = agg_compile_conds(filters, n_specs, names, cols, n_columns, out, cond_of, sets)) return rc;
   for (uint32_t s = 0; s < n_specs; s++) out.insns[s].cond = cond_of[s];
   return ORCGPU_OK;
 }

@@ -334,7 +334,8 @@ int result_compile_filter(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_
     kinds[c] = co.orc_type;
     params[c] = co.orc_type == ORCGPU_T_DECIMAL ? (int32_t)co.scale : co.ts_unit;  // what Decimal128 / TimestampNs literals are brought to
   }
-  const int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan, params.data());
+  const orcgpu_host::KeySetRefs sets = ctx_key_set_refs(ctx);  // (what a set leaf may name)
+  const int rc = orcgpu_host::filter_compile(nodes, n_nodes, column_names, kinds.data(), n_columns, plan, params.data(), &sets);
   if (rc) set_err(ctx, "%s", plan.err);
   return rc;
 }

@@ -5,9 +5,11 @@
 // patterns are cut into the parts filter_like_kernel matches (tests/hostcheck/filter_plan_like_check.cpp), IN lists become the
 // hash sets filter_in_kernel probes (orcgpu_in.inc, tests/hostcheck/filter_plan_in_check.cpp), the two sides of an expression leaf
 // (lhs OP rhs) become the op tables filter_expr_kernel interprets -- compiled by the expression aggregates' compiler,
-// orcgpu_agg_expr.inc (tests/hostcheck/filter_plan_expr_check.cpp) --, and the depth is bounded.
+// orcgpu_agg_expr.inc (tests/hostcheck/filter_plan_expr_check.cpp) --, a set leaf (x IN SET s) becomes FOP_IN_SET with the address
+// of the sealed table of the key set it names (orcgpu_key_set.inc, tests/hostcheck/key_set_check.cpp), and the depth is bounded.
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -16,6 +18,7 @@
 #include "orcgpu_agg_expr.inc"
 #include "orcgpu_decimal.inc"
 #include "orcgpu_in.inc"
+#include "orcgpu_key_set.inc"
 #include "orcgpu_like.inc"
 
 namespace orcgpu_host {
@@ -38,6 +41,8 @@ struct FilterPlan {
   std::vector<uint32_t> like_leaves, in_leaves, expr_leaves;
   size_t n_planes() const { return like_leaves.size() + in_leaves.size() + 2 * expr_leaves.size(); }  // (numbered together, in leaf order: FilterInsn::i)
   size_t n_leaves() const { return like_leaves.size() + in_leaves.size() + expr_leaves.size(); }
+  // the memory of the key sets whose tables FOP_IN_SET instructions name by address: whoever keeps the plan keeps them alive
+  std::vector<std::shared_ptr<void>> holds;
   char err[256] = {0};
 };
 
@@ -49,6 +54,7 @@ struct FilterCompiler {
   uint32_t n_columns;
   const int32_t* params;  // per column -- Decimal: its scale; Timestamp: the unit it is decoded to (0 s, 1 ms, 2 us, 3 ns, 4 Decimal128(38, 9))
   FilterPlan& out;
+  const KeySetRefs* sets = nullptr;  // the key sets of the context the plan is compiled for (none: every set leaf is refused)
 
   int fail(int rc, const char* fmt, const char* a = "", long long b = 0) {
     snprintf(out.err, sizeof(out.err), fmt, a, b);
@@ -275,6 +281,12 @@ struct FilterCompiler {
       }
       case ORCGPU_PRED_CMP_EXPR:
         return cmp_expr(n, at);
+      case ORCGPU_PRED_IN_SET: {
+        uint32_t col = 0;
+        const int rc = column(n, col);
+        if (rc) return rc;
+        return in_set(n, col);
+      }
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: case ORCGPU_PRED_EXPR_NEG:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
@@ -473,6 +485,36 @@ struct FilterCompiler {
     out.prog.push_back(in);
     return ORCGPU_OK;
   }
+  // A set leaf: x IN SET s is x IN (the keys the set's build side held, NULLs included), so by the IN list's shapes: an empty set
+  // without a NULL: FALSE; an empty one with: UNKNOWN; everything else: FOP_IN_SET -- FOP_IN whose table is the set's own, sealed on
+  // the device and named by address, with a mask plane among the IN leaves' (filter_in_kernel's grid takes both).  The keys never
+  // come to the host, so one key is not turned into an EQ.
+  int in_set(const orcgpu_predicate_node& n, uint32_t col) {
+    if (n.n_children) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the set leaf for column '%s' has children (%lld)", n.column, n.n_children);
+    if (const int rc = key_set_column_check(kinds[col], false, false, n.column, "row filter", out.err, sizeof(out.err))) return rc;
+    const KeySetRef* set = nullptr;
+    for (size_t k = 0; sets && k < sets->size(); k++)
+      if ((*sets)[k].id == (uint64_t)n.i) set = &(*sets)[k];
+    if (!set) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the key set named for column '%s' (id %lld) is not a set of this context", n.column, n.i);
+    if (set->state == KEY_SET_BUILDING) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the key set named for column '%s' (id %lld) is not sealed", n.column, n.i);
+    if (set->state != KEY_SET_SEALED)
+      return fail(ORCGPU_INVALID_ARGUMENT, "row filter: the key set named for column '%s' took more than its limit of %lld keys and is unusable", n.column, set->max_keys);
+    if (!set->n_keys) {
+      emit(set->has_null ? FOP_UNKNOWN : FOP_FALSE);
+      return ORCGPU_OK;
+    }
+    FilterInsn in{};
+    in.op = FOP_IN_SET;
+    in.col = col;
+    in.cmp = set->has_null ? IN_HAS_NULL : 0;
+    in.lo = FKIND_INT;
+    take_plane(in, out.in_leaves);
+    in.lit_off = set->table;
+    in.lit_len = set->bytes;
+    out.holds.push_back(set->hold);
+    out.prog.push_back(in);
+    return ORCGPU_OK;
+  }
   // An IN leaf: x IN (v1 .. vk) is OR(x = v1, ..., x = vk).  Every literal passes the type table of EQ and is brought to the
   // column's key by the code EQ uses; a literal that can equal no row (NaN, a Decimal off the column's scale, a Timestamp between
   // two values of its unit) is FALSE on valid rows like the empty rest of the OR, so it is left out.  Then by shape: no literal:
@@ -567,15 +609,16 @@ struct FilterCompiler {
 // ORCGPU_OK, or the status a reader with this filter ends with (out.err says why).  names[k] / kinds[k]: column k.
 // params[k]: a Decimal column's scale, the unit a Timestamp column is decoded to (FilterCompiler::params); none: scale 0, nanoseconds.
 inline int filter_compile(const orcgpu_predicate_node* nodes, uint32_t n_nodes, const char* const* names, const int32_t* kinds, uint32_t n_columns,
-                          FilterPlan& out, const int32_t* params = nullptr) {
+                          FilterPlan& out, const int32_t* params = nullptr, const KeySetRefs* sets = nullptr) {
   out.prog.clear();
   out.lits.clear();
   out.like_leaves.clear();
   out.in_leaves.clear();
   out.expr_leaves.clear();
+  out.holds.clear();
   out.depth = 0;
   out.err[0] = 0;
-  FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, params, out};
+  FilterCompiler fc{nodes, n_nodes, names, kinds, n_columns, params, out, sets};
   if (!nodes || !n_nodes) return fc.fail(ORCGPU_INVALID_ARGUMENT, "row filter: no predicate%s", "");
   for (uint32_t k = 0; k < n_columns; k++) {
     const int t = kinds[k];
@@ -622,12 +665,14 @@ inline uint32_t filter_plan_append(FilterPlan& into, const FilterPlan& from) {
   into.lits.insert(into.lits.end(), from.lits.begin(), from.lits.end());
   for (FilterInsn in : from.prog) {
     if (in.op == FOP_CMP_STRING || in.op == FOP_LIKE || in.op == FOP_IN || in.op == FOP_CMP_EXPR) in.lit_off += lit0;
-    if ((in.op == FOP_LIKE && in.cmp != LIKE_ALL) || (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE)) || in.op == FOP_CMP_EXPR) in.i += planes;
+    // (a set leaf names its table by address: nothing of it lies in the pool)
+    if ((in.op == FOP_LIKE && in.cmp != LIKE_ALL) || (in.op == FOP_IN && !(in.cmp & IN_NO_TABLE)) || in.op == FOP_IN_SET || in.op == FOP_CMP_EXPR) in.i += planes;
     into.prog.push_back(in);
   }
   for (const uint32_t k : from.like_leaves) into.like_leaves.push_back(first + k);
   for (const uint32_t k : from.in_leaves) into.in_leaves.push_back(first + k);
   for (const uint32_t k : from.expr_leaves) into.expr_leaves.push_back(first + k);
+  into.holds.insert(into.holds.end(), from.holds.begin(), from.holds.end());
   if (from.depth > into.depth) into.depth = from.depth;
   return first;
 }

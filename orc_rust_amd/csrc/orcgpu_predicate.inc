@@ -624,6 +624,9 @@ struct PredEval {
       return at + 1;
     }
     if (n.op == ORCGPU_PRED_CMP_EXPR) return cmp_expr(at, neg, result);
+    // A set leaf (ORCGPU_PRED_IN_SET) is a sound "might match": the set's keys live on the device, so every group is kept, under
+    // a NOT too, and the evaluation never fails on it -- what the leaf cannot take is the row filter's to report.
+    if (n.op == ORCGPU_PRED_IN_SET) return at + 1;
     if (n.op <= ORCGPU_PRED_GE) {
       comparison(n, neg ? negate(n.op) : n.op, result);
       return at + 1;

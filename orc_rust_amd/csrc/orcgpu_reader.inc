@@ -99,6 +99,11 @@ struct orcgpu_reader {
   bool top_k_ready = false, top_k_eof = false;
   orcgpu_host::TopKPlan top_k_plan;
   std::vector<orcgpu_host::TopKStripe> top_k_stripes;
+  // orcgpu_reader_collect_keys: every decoded stripe gives the kept rows' keys of one column to a key set, where the aggregation
+  // would stand; like it, the reader then hands out no batch and copies nothing back
+  bool has_collect = false;
+  struct orcgpu_key_set* collect_set = nullptr;
+  uint32_t collect_col = 0;
   uint64_t d2h_bytes = 0;                     // column-buffer bytes copied to the host so far (orcgpu_reader_d2h_bytes)
   bool current_counted = false;               // ... those of `current` are in it
   bool device_checked = false, device_refused = false;  // the projection has been looked at for nested columns; it has one
@@ -329,7 +334,8 @@ int reader_compile_filter(orcgpu_reader* rd) {
     params.push_back(t.kind == ORCGPU_T_DECIMAL ? (int32_t)t.scale : ts_unit_of(c));
   }
   const std::vector<orcgpu_predicate_node> nodes = view_predicate(rd->filter_nodes);
-  const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan, params.data());
+  const KeySetRefs sets = ctx_key_set_refs(rd->ctx);  // (what a set leaf may name; the plan holds the memory of the ones it does)
+  const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan, params.data(), &sets);
   if (rc) set_err(rd->ctx, "%s", rd->filter_plan.err);
   if (rc) return rc;
   // a comparison on a dictionary-output column would have to be evaluated on the entries: refused, by name, before anything is read
@@ -413,7 +419,8 @@ int reader_compile_aggs(orcgpu_reader* rd) {
   reader_describe_roots(rd, names, cols);
   ReaderAggView v;
   reader_view_aggs(rd, v);
-  const int rc = agg_compile(v.specs.data(), v.exprs.data(), v.filters.data(), (uint32_t)v.specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan);
+  const KeySetRefs sets = ctx_key_set_refs(rd->ctx);
+  const int rc = agg_compile(v.specs.data(), v.exprs.data(), v.filters.data(), (uint32_t)v.specs.size(), names.data(), cols.data(), (uint32_t)cols.size(), rd->agg_plan, &sets);
   if (rc) set_err(rd->ctx, "%s", rd->agg_plan.err);
   return rc;
 }
@@ -526,12 +533,14 @@ int reader_top_k_result(orcgpu_reader* rd, orcgpu_result* res) {
   return rc;
 }
 
+int reader_collect_result(orcgpu_reader* rd, orcgpu_result* res);  // (orcgpu_key_set_call.inc)
+
 // A result the caller is done with, to decode a later stripe into (rd->m is held by a reader that reads ahead)
 orcgpu_result* reader_take_spare(orcgpu_reader* rd) {
   // (a result that comes home was viewed by batches and tensors whose consumers released them on the HOST: work they enqueued on
   // streams of their own may not have run yet, and nothing orders the decode stream behind it -- so decode_staged_once waits for
   // the device before it writes into a result that has been exported)
-  if (rd->device_output && !rd->has_aggs) return static_cast<orcgpu_result*>(orcgpu_hold::home_take(*rd->home));
+  if (rd->device_output && !rd->has_aggs && !rd->has_collect) return static_cast<orcgpu_result*>(orcgpu_hold::home_take(*rd->home));
   if (rd->spare.empty()) return nullptr;
   orcgpu_result* r = rd->spare.back();
   rd->spare.pop_back();
@@ -560,10 +569,11 @@ int reader_finish_decoded(orcgpu_reader* rd, orcgpu_staged* staged, orcgpu_resul
   }
   if (!rc && staged->has_sel) rc = result_select_batches(rd->ctx, res, staged->sel);
   if (!rc && rd->has_aggs) rc = reader_aggregate_result(rd, res);
+  else if (!rc && rd->has_collect) rc = reader_collect_result(rd, res);
   else if (!rc && rd->has_top_k) rc = reader_top_k_result(rd, res);
   else if (!rc && rd->has_filter) rc = reader_filter_result(rd, res);
   orcgpu_staged_free(staged);
-  if (!rc && !rd->has_aggs) rc = reader_result_decoded(rd, res, start_copy);
+  if (!rc && !rd->has_aggs && !rd->has_collect) rc = reader_result_decoded(rd, res, start_copy);
   return rc;
 }
 

@@ -235,6 +235,10 @@ static int reader_next(orcgpu_reader* rd, struct ArrowArray* out_array, struct A
     set_err(rd->ctx, "this reader aggregates (orcgpu_reader_set_aggregates): call orcgpu_reader_aggregate, it hands out no batches");
     return ORCGPU_INVALID_ARGUMENT;
   }
+  if (rd->has_collect) {
+    set_err(rd->ctx, "this reader collected keys (orcgpu_reader_collect_keys): it hands out no batches");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
   if (rd->device_output != (out_device != nullptr)) {
     set_err(rd->ctx, rd->device_output ? "this reader hands out device batches (orcgpu_reader_set_device_output): call orcgpu_reader_next_batch_device"
                                        : "orcgpu_reader_next_batch_device needs orcgpu_reader_set_device_output before the first batch");

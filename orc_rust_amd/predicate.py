@@ -8,6 +8,7 @@ import decimal
 EQ, NE, LT, LE, GT, GE, IS_NULL, IS_NOT_NULL, AND, OR, NOT = range(11)
 LIKE = 16  # (11 .. 15 are unknown ops)
 IN, LITERAL = 17, 18  # an IN leaf, and one value of its list
+IN_SET = 26  # x IN SET s: a leaf whose i names a sealed key_set.KeySet
 CMP_EXPR = 19  # lhs OP rhs over two arithmetic expressions; its subtrees are made of the nodes below
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(20, 26)  # ORCGPU_PRED_EXPR_*: aggregate.EXPR_* + 20
 _CMP_OPS = {"=": EQ, "!=": NE, "<": LT, "<=": LE, ">": GT, ">=": GE}
@@ -18,7 +19,7 @@ _EPOCH = datetime.datetime(1970, 1, 1)
 
 _PV_NAMES = ("Boolean", "Int8", "Int16", "Int32", "Int64", "Float32", "Float64", "Utf8", "Decimal128", "TimestampNs")
 _OP_NAMES = {EQ: "eq", NE: "ne", LT: "lt", LE: "lte", GT: "gt", GE: "gte", IS_NULL: "is_null", IS_NOT_NULL: "is_not_null", AND: "and_", OR: "or_", NOT: "not_",
-             LIKE: "like", IN: "in_list"}
+             LIKE: "like", IN: "in_list", IN_SET: "in_set"}
 
 
 class PredicateNode(C.Structure):
@@ -198,6 +199,25 @@ class Predicate:
         return cls.not_(cls.in_list(column, values))
 
     @classmethod
+    def in_set(cls, column, key_set):
+        """A semi-join (ORCGPU_PRED_IN_SET, this library's own): column IN SET key_set, where key_set is a sealed
+        orc_rust_amd.KeySet -- the distinct keys an ArrowReaderBuilder.collect_keys left on the GPU.  Exactly in_list over the values
+        the build side's kept rows held, NULLs included: a NULL row is UNKNOWN, the empty set FALSE, and a NULL on the build side
+        makes every non-match UNKNOWN.  The column is a Byte, Short, Int, Long or Date column."""
+        from .key_set import KeySet
+        if not isinstance(column, str):
+            raise TypeError("in_set: the column is a str, not %s" % type(column).__name__)
+        if not isinstance(key_set, KeySet):
+            raise TypeError("in_set: the set is a KeySet (ArrowReaderBuilder.collect_keys), not %s" % type(key_set).__name__)
+        p = cls(IN_SET, column)
+        p.key_set = key_set  # (kept alive with the predicate)
+        return p
+
+    @classmethod
+    def not_in_set(cls, column, key_set):
+        return cls.not_(cls.in_set(column, key_set))
+
+    @classmethod
     def between(cls, column, lo, hi):
         """lo <= column <= hi: and_([gte(column, lo), lte(column, hi)])"""
         return cls.and_([cls.gte(column, lo), cls.lte(column, hi)])
@@ -224,6 +244,8 @@ class Predicate:
             return "%s(%r)" % (name, self.column)
         if self.op == IN:
             return "in_list(%r, %r)" % (self.column, [c.value for c in self.children])
+        if self.op == IN_SET:
+            return "in_set(%r, %r)" % (self.column, self.key_set)
         if self.op == CMP_EXPR:
             return "(%r %s %r)" % (self.exprs[0], _CMP_SIGNS[self.cmp], self.exprs[1])
         if self.op == LIKE:
@@ -289,6 +311,9 @@ class Predicate:
                         n.i = int(v.value)
             if p.op == LIKE:
                 n.i = ord(p.escape) if p.escape else 0
+            if p.op == IN_SET:
+                n.i = p.key_set.id()
+                keep.append(p.key_set)
             out.append(n)
             for c in p.children:
                 walk(c)
