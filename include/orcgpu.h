@@ -991,6 +991,43 @@ const char* orcgpu_reader_column_name(orcgpu_reader* r, uint32_t i);
  * anything else = the OrcError status of the failing batch (the iterator then ends). */
 int orcgpu_reader_next_batch(orcgpu_reader* r, struct ArrowArray* out_array, struct ArrowSchema* out_schema);
 
+/* ---- Computed columns: arithmetic expressions materialised on the device, once per stripe (this library's own) --------------------
+ * A reader may be given 1 .. ORCGPU_COMPUTED_MAX computed columns, each {name, expression}, in order.  The expression is an
+ * orcgpu_agg_expr over the nodes of the expression aggregates and of the row filter's comparison: column, literal, + - *, unary -.
+ *   - OPERANDS are projected flat root columns of the file.  Another computed column as an operand is ORCGPU_UNSUPPORTED.  At most
+ *     ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH operand slots.
+ *   - TYPING is the expression compiler's, in the mode one side of ORCGPU_PRED_CMP_EXPR takes: a Date takes part as int64 days; the
+ *     class is decided over the whole expression.  Integer class: Int64.  Decimal class: Decimal128(38, s), s by the scale rule of
+ *     the expression aggregates.  Float class: Float64, one IEEE operation at a time, never contracted.  The compiler's refusals
+ *     keep their messages and name the computed column: Boolean, String / Varchar / Char / Binary, Timestamp, dictionary-output and
+ *     nested operands, a node scale above 38, an expression without any column.
+ *   - NULL: a row's value is NULL where any column operand is NULL.  It is NULL, and COUNTED, where an operation inside the
+ *     expression leaves 128 bits, where an Int64 result does not fit int64, and where a Decimal result has a magnitude of 10^38 or
+ *     more: never a wrapped value.  orcgpu_reader_computed_overflow_rows gives the count so far: of the selected rows -- all rows
+ *     without a row selection --, before the row filter.
+ *   - NAMES are non-empty and distinct, and none equals a root column name of the file, projected or not
+ *     (ORCGPU_INVALID_ARGUMENT, naming it).  A nested column in the projection beside computed columns is ORCGPU_UNSUPPORTED, by
+ *     name.  These refusals, and the expressions', arrive with the first batch (or the aggregate / collect call): the projection is
+ *     known once the reader is built.  Setting them after the first batch is ORCGPU_INVALID_ARGUMENT.
+ *   - PLACE: the computed columns follow the projected ones, in the order given, as nullable fields -- in the exported schema, in
+ *     every batch, and among the names the row filter, the aggregates (arguments, Agg.where, operands of their expressions), GROUP BY
+ *     keys (Int64, Decimal), top-k keys and orcgpu_reader_collect_keys (Int64) resolve against.  They come back through the host
+ *     path, the device path, a row selection and the row filter's gather like any fixed-width column of the file.
+ *   - As a pruning predicate a leaf on a computed column keeps every stripe and row group: the statistics know nothing of it.
+ * The columns are evaluated inside the decode call, behind the last kernel that writes an operand and in front of the call's
+ * closing copy, which brings their per-batch null counts and the overflow count back with everything else: no wait is added.  A
+ * decode call with computed columns runs on one column lane (the operands must be complete on the stream that evaluates).  The
+ * reader's row selection on a stripe is fixed before its decode call, so the count can be of the selected rows there.
+ * orcgpu_result_compute_columns does the same on a hand-decoded result, before any orcgpu_result_select / _filter on it:
+ * column_names names the result's columns (one per column; they are the operands and the names a computed column may not take),
+ * the computed columns are appended behind them -- every later result call then takes n more column names --, *overflow_rows gets
+ * the count over all rows.  One host wait of its own.  A result whose decode failed is left alone: its status is returned. */
+#define ORCGPU_COMPUTED_MAX 8
+int orcgpu_reader_set_computed_columns(orcgpu_reader* r, const char* const* names, const orcgpu_agg_expr* exprs, uint32_t n);
+int orcgpu_result_compute_columns(orcgpu_ctx* ctx, orcgpu_result* result, const char* const* names, const orcgpu_agg_expr* exprs, uint32_t n,
+                                  const char* const* column_names, uint64_t* overflow_rows);
+int orcgpu_reader_computed_overflow_rows(const orcgpu_reader* r, uint64_t* rows);
+
 /* ---- device-resident batches (Arrow C Device Data Interface, DLPack) --------------------------------------------------------------
  * A decoded result lives in HBM; the entry points above copy it to pinned host memory before a consumer sees a byte.  These
  * hand the device buffers out instead, for consumers on the same GPU (a torch model, this library's own writer with

@@ -31,6 +31,43 @@ def check_dictionary_columns(names):
     return list(names)
 
 
+COMPUTED_MAX = 8  # ORCGPU_COMPUTED_MAX
+
+
+def check_computed_columns(columns):
+    """The argument of with_computed_columns, checked before anything reaches the GPU: a dict {name: Expr} or a list / tuple of
+    (name, Expr) pairs, 1 .. 8 of them; every name a non-empty str, none twice; every expression an orc_rust_amd.aggregate.Expr
+    (col, lit and + - * on them) of at most 32 nodes.  Returns the pairs as a list."""
+    from .aggregate import EXPR_MAX_NODES, Expr
+    if isinstance(columns, dict):
+        pairs = list(columns.items())
+    elif isinstance(columns, (list, tuple)):
+        pairs = list(columns)
+        for p in pairs:
+            if not isinstance(p, (list, tuple)) or len(p) != 2:
+                raise TypeError("with_computed_columns: every entry is a (name, Expr) pair, not %r" % (p,))
+    else:
+        raise TypeError("with_computed_columns: a dict {name: Expr} or a list of (name, Expr) pairs, not %s" % type(columns).__name__)
+    seen = set()
+    for name, expr in pairs:
+        if not isinstance(name, str):
+            raise TypeError("with_computed_columns: a column name must be a str, not %s" % type(name).__name__)
+        if not name:
+            raise ValueError("with_computed_columns: an empty column name")
+        if name in seen:
+            raise ValueError("with_computed_columns: the name %r is given twice" % name)
+        seen.add(name)
+        if not isinstance(expr, Expr):
+            raise TypeError("with_computed_columns: the expression of %r is an aggregate.Expr (col, lit and + - * on them), not %s" % (name, type(expr).__name__))
+        if expr.node_count() > EXPR_MAX_NODES:
+            raise ValueError("with_computed_columns: the expression of %r has %d nodes, at most %d" % (name, expr.node_count(), EXPR_MAX_NODES))
+    if not pairs:
+        raise ValueError("with_computed_columns: no computed column given")
+    if len(pairs) > COMPUTED_MAX:
+        raise ValueError("with_computed_columns: %d computed columns, at most %d" % (len(pairs), COMPUTED_MAX))
+    return [(n, e) for n, e in pairs]
+
+
 def concat_batches(batches):
     """The batches of one reader as one pyarrow.Table.  (A batch's schema says "not null" of a column without a NULL in that batch,
     so the batches' schemas differ and Table.from_batches refuses them: the table is built column by column, every field nullable.)"""
@@ -107,6 +144,25 @@ class ArrowReaderBuilder:
         names = check_dictionary_columns(names)
         arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
         self._ctx._check(self._ctx.L.orcgpu_reader_set_dictionary_columns(self._h, arr, len(names)))
+        return self
+
+    def with_computed_columns(self, columns):
+        """Computed columns (orcgpu_reader_set_computed_columns): `columns` is a dict {name: Expr} or a list of (name, Expr), Expr
+        from orc_rust_amd.aggregate (col, lit, + - *, unary -) over projected flat root columns.  Each is evaluated once per stripe
+        on the GPU into an Int64, Decimal128(38, s) or Float64 column that follows the projected ones, nullable, and that the row
+        filter, the aggregates, GROUP BY, top-k and collect_keys see by name.  NULL where an operand is NULL; NULL and counted
+        (ArrowReader.computed_overflow_rows) where the exact value does not fit."""
+        from .aggregate import AggExpr
+        pairs = check_computed_columns(columns)
+        names = (C.c_char_p * len(pairs))(*[n.encode() for n, _ in pairs])
+        exprs = (AggExpr * len(pairs))()
+        keep = []
+        for i, (_, e) in enumerate(pairs):
+            nodes, alive = e.flatten()
+            keep.append((nodes, alive))
+            exprs[i].nodes = nodes
+            exprs[i].n_nodes = len(nodes)
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_computed_columns(self._h, names, exprs, len(pairs)))
         return self
 
     def with_row_selection(self, selectors):
@@ -278,6 +334,13 @@ class ArrowReader:
         leaf left 128 bits -- the leaf was UNKNOWN there: orcgpu_reader_filter_overflow_rows.  0 unless something overflowed."""
         n = C.c_uint64(0)
         self._ctx._check(self._ctx.L.orcgpu_reader_filter_overflow_rows(self._h, C.byref(n)))
+        return n.value
+
+    def computed_overflow_rows(self):
+        """Rows decoded so far in which a computed column's value did not fit -- an operation left 128 bits, an Int64 result left
+        int64, a Decimal result reached 10^38 -- and is NULL: orcgpu_reader_computed_overflow_rows.  0 unless something overflowed."""
+        n = C.c_uint64(0)
+        self._ctx._check(self._ctx.L.orcgpu_reader_computed_overflow_rows(self._h, C.byref(n)))
         return n.value
 
     def d2h_bytes(self):

@@ -46,6 +46,7 @@ EXPORTS = [
     "orcgpu_reader_filter_overflow_rows",
     "orcgpu_key_set_create", "orcgpu_reader_collect_keys", "orcgpu_result_collect_keys", "orcgpu_key_set_seal", "orcgpu_key_set_id",
     "orcgpu_key_set_free",
+    "orcgpu_reader_set_computed_columns", "orcgpu_reader_computed_overflow_rows", "orcgpu_result_compute_columns",
 ]
 
 
@@ -241,6 +242,9 @@ def load():
     L.orcgpu_result_aggregate_groups_exprs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                                        C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32, C.POINTER(C.c_void_p)]
     L.orcgpu_reader_set_aggregate_exprs.argtypes = [C.c_void_p, C.POINTER(AggSpec), C.POINTER(AggExpr), C.c_uint32]
+    L.orcgpu_reader_set_computed_columns.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(AggExpr), C.c_uint32]
+    L.orcgpu_reader_computed_overflow_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.orcgpu_result_compute_columns.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(AggExpr), C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
     L.orcgpu_result_aggregate_groups.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32,
                                                  C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(AggSpec), C.c_uint32, C.POINTER(C.c_void_p)]
     L.orcgpu_reader_set_group_by.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32]
@@ -494,6 +498,25 @@ class Context:
         kept = C.c_uint64(0)
         self._check(self.L.orcgpu_result_filter(self.h, result.h, nodes, len(nodes), names, len(column_names), C.byref(kept)))
         return kept.value
+
+    def result_compute_columns(self, result, columns, column_names):
+        """orcgpu_result_compute_columns: the computed columns (a dict or a list of (name, aggregate.Expr)) appended behind the
+        columns of a decoded result, which column_names names; before any select / filter on it.  Returns the overflow count."""
+        from .aggregate import AggExpr
+        from .arrow_reader import check_computed_columns
+        pairs = check_computed_columns(columns)
+        names = (C.c_char_p * len(pairs))(*[n.encode() for n, _ in pairs])
+        exprs = (AggExpr * len(pairs))()
+        keep = []
+        for i, (_, e) in enumerate(pairs):
+            nodes, alive = e.flatten()
+            keep.append((nodes, alive))
+            exprs[i].nodes = nodes
+            exprs[i].n_nodes = len(nodes)
+        cn = (C.c_char_p * len(column_names))(*[n.encode() for n in column_names])
+        over = C.c_uint64(0)
+        self._check(self.L.orcgpu_result_compute_columns(self.h, result.h, names, exprs, len(pairs), cn, C.byref(over)))
+        return over.value
 
     def result_top_k(self, result, by, k, column_names, predicate=None):
         """orcgpu_result_top_k: the result's batches become the first k of its kept rows (predicate None: all rows) under the sort

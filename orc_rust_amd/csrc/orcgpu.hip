@@ -48,6 +48,7 @@
 #include "device/agg_group_wide_kernels.hip"
 #include "device/top_k_kernels.hip"
 #include "device/key_set_kernels.hip"
+#include "device/compute_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -124,6 +125,7 @@ struct StagedStream {
 }  // namespace
 
 #include "orcgpu_decode_host.inc"
+#include "orcgpu_computed_plan.inc"
 static_assert(kJobBlockBytes == RLE_BLK && kJobTileBlocks == RLE_TILE && kJobCodecByte == CODEC_BYTE, "orcgpu_decode_host.inc states the device's constants");
 
 constexpr int kMaxLanes = 4;
@@ -335,6 +337,8 @@ struct orcgpu_staged {
   bool has_sel = false;
   std::vector<SelBatch> sel;
   bool piece = false;  // some row groups of a stripe (what a selection leaves of it), not the stripe
+  // computed columns (orcgpu_computed.inc): the reader's plan; the decode call appends them to the result's columns.  None: null
+  std::shared_ptr<const orcgpu_host::ComputedPlan> computed;
   const StagedStream* find(uint32_t col, int kind) const {
     for (auto& s : streams)
       if (s.column_id == col && s.kind == kind) return &s;
@@ -361,6 +365,7 @@ struct ColumnOut {
   int32_t ts_unit = 3;
   uint32_t precision = 0, scale = 0;
   bool has_present = false;
+  bool computed = false;     // a computed column (orcgpu_computed.inc): no column of the file; its field is nullable whatever the batch holds
   uint64_t values_off = 0, values_bytes = 0;      // in the result arena (or the chars arena)
   int lane = 0;                                   // which lane's arenas hold the column
   bool values_in_chars = false;                   // dictionary strings: values live in orcgpu_result::chars
@@ -508,6 +513,7 @@ struct orcgpu_result {
   std::vector<GroupKeyRecord> grp_keys;  // ... with a GROUP BY: the stripe's groups in first-appearance order, keys [group][key]
   std::vector<AggPartial> grp_vals;      // ... and records [group][aggregate, then the group's kept row count]
   std::vector<uint8_t> top_k_records;    // a top-k file reader: the key record of every row the stripe hands out, in their order
+  uint64_t computed_overflow = 0;        // computed columns: the rows of this decode whose value overflowed (NULL and counted)
   std::vector<ColumnOut> cols;
   std::vector<std::string> field_names;  // per column: the name of a Struct's field (set by the file reader; empty: "f<position>")
   // Elements of the List / Map columns: one result each over a "stripe" whose rows are the column's elements (all of the

@@ -7,6 +7,11 @@ struct LaneClock {
   double t0 = 0, cols = 0, dp = 0, plan = 0, launch = 0, first = 0, walk = 0, pres = 0, exp = 0, fin = 0, dict = 0, enq = 0, sync = 0;
 };
 
+// The tables of compute_columns_kernel as one upload (orcgpu_computed.inc): the columns, the jobs, the programs, the selection's batches
+struct ComputedTable {
+  uint64_t o_cols = 0, o_jobs = 0, o_ops = 0, o_segs = 0, bytes = 0;
+};
+
 // What the steps of decode_lane share: one lane's share of a decode call, from its plan to the pointers its launches take.
 struct LaneRun {
   orcgpu_ctx* ctx;
@@ -39,6 +44,14 @@ struct LaneRun {
   uint32_t* d_tsum = nullptr;
   int njobs = 0;
   LaneClock ht;
+  // computed columns (orcgpu_computed.inc): per stripe that carries them, where their counts lie in the summary and the kernel's
+  // tables in the workspace
+  struct ComputedPlace {
+    uint32_t stripe = 0, first_col = 0, nullcount_off = 0;
+    uint64_t table_off = 0;
+    ComputedTable tab;
+  };
+  std::vector<ComputedPlace> computed;
 
   uint8_t* arena(const orcgpu_result* r) const { return r->arena[ctx->lane_id].p; }
   // a column's validity words and their ranks (null: no validity)
@@ -52,6 +65,7 @@ struct LaneRun {
 }  // namespace
 
 #include "orcgpu_ext.inc"
+#include "orcgpu_computed.inc"
 
 namespace {
 
@@ -420,6 +434,7 @@ int plan_columns(LaneRun& R) {
         return rc;
       }
     }
+    if (int rc = computed_plan_stripe(R, si)) return rc;
   }
   R.ht.cols = host_us_now();
   return ORCGPU_OK;
@@ -946,6 +961,8 @@ int launch_dictionaries_and_post(LaneRun& R) {
   R.ht.dict = host_us_now();
   rc = launch_post_ext(R);
   if (rc) return rc;
+  rc = computed_launch(R);  // (computed columns: behind the last kernel that writes a column, their counts into the summary)
+  if (rc) return rc;
   HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)(R.SL.bytes / 8), false, 256, R.st, (const unsigned long long*)R.dsum, (unsigned long long*)R.hs,
                       (uint64_t)(R.SL.bytes / 8)));
   HIP_TRY(ctx, hipEventRecord(ctx->ev[3], R.st));
@@ -1264,6 +1281,7 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   debug_report(R);
   if ((rc = grow_failed_slots(R))) return rc;
   for (auto& cp : R.P.cols) resolve_column(R, cp);
+  computed_resolve(R);
   note_host_parts(R);
   return ORCGPU_OK;
 }
@@ -1320,6 +1338,7 @@ static int reset_results(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_
     }
     for (auto* sub : r->subs) orcgpu_result_free(sub);
     r->subs.clear();
+    computed_append_columns(s, r);
     r->status = 0;
     r->err_batch = r->err_col = 0;
     if (r->mirror) r->mirror->wait();  // (a copy of the previous contents still on its way to the host reads these buffers)
@@ -1359,6 +1378,8 @@ static int choose_lanes(orcgpu_staged* const* stripes, uint32_t n, std::vector<s
       }
     if (staged >= (64ull << 20) && mx_all >= 16384) want_lanes = 2;
   }
+  for (uint32_t si = 0; si < n; si++)
+    if (stripes[si]->computed) want_lanes = 1;  // (computed columns: the operands complete on the stream that evaluates)
   int n_lanes = (int)std::min<size_t>((size_t)want_lanes, max_cols);
   if (n_lanes <= 1) return n_lanes;
   // the weight of a root column = staged bytes of the streams of its columns over all stripes of the call; one pass per stripe,

@@ -494,8 +494,8 @@ static int export_batch_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, uint32_
     ks.format = ksp->strings[0].c_str();
     ks.name = ksp->strings[1].c_str();
     // a root column is nullable when the batch has nulls (RecordBatch::try_from_iter, mod.rs:552-562); the fields of a Struct
-    // and the elements of Lists come from the schema, where every field is nullable
-    ks.flags = (v.null_count || co.parent >= 0 || sliced) ? 2 /* ARROW_FLAG_NULLABLE */ : 0;
+    // and the elements of Lists come from the schema, where every field is nullable; so is a computed column, whatever the batch holds
+    ks.flags = (v.null_count || co.parent >= 0 || sliced || co.computed) ? 2 /* ARROW_FLAG_NULLABLE */ : 0;
     ks.n_children = (int64_t)ksp->kids.size();
     ks.children = ksp->kids.empty() ? nullptr : ksp->kids.data();
     ks.dictionary = ksp->dict_store.empty() ? nullptr : &ksp->dict_store[0];

@@ -221,7 +221,7 @@ static int export_batch_device_named(orcgpu_ctx* ctx, const orcgpu_result* rc_, 
     memset(&ks, 0, sizeof(ks));
     ks.format = ksp->strings[0].c_str();
     ks.name = ksp->strings[1].c_str();
-    ks.flags = v.null_count ? 2 /* ARROW_FLAG_NULLABLE */ : 0;
+    ks.flags = (v.null_count || co.computed) ? 2 /* ARROW_FLAG_NULLABLE; a computed column: always */ : 0;
     if (co.dict_out) {
       SchemaPriv* dsp = new SchemaPriv();
       dsp->strings.reserve(2);

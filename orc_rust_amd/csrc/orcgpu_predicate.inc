@@ -264,6 +264,15 @@ struct PredEval {
   const std::vector<ColumnGroups>& cols;
   size_t n_groups;
   bool failed = false;  // the reference's `?`: the whole evaluation is an Err
+  // columns the statistics know nothing of (the reader's computed columns): a leaf on one is a sound "might match", under a NOT
+  // too, and never fails the evaluation -- what it cannot take is the row filter's to report
+  const std::vector<std::string>* opaque = nullptr;
+  bool is_opaque(const PredNode& n) const {
+    if (!opaque || !n.has_column) return false;
+    for (const std::string& o : *opaque)
+      if (o == n.column) return true;
+    return false;
+  }
 
   static int negate(int op) {  // ComparisonOp::negate
     switch (op) {
@@ -611,6 +620,8 @@ struct PredEval {
       return nodes.size();
     }
     const PredNode& n = nodes[at];
+    if (is_opaque(n) && (n.op <= ORCGPU_PRED_GE || n.op == ORCGPU_PRED_IS_NULL || n.op == ORCGPU_PRED_IS_NOT_NULL || n.op == ORCGPU_PRED_LIKE)) return at + 1;
+    if (is_opaque(n) && n.op == ORCGPU_PRED_IN && at + 1 + (size_t)n.n_children <= nodes.size()) return at + 1 + n.n_children;
     if (n.op == ORCGPU_PRED_IN) {
       if (at + 1 + (size_t)n.n_children > nodes.size()) {
         failed = true;
@@ -695,9 +706,10 @@ std::vector<orcgpu_predicate_node> view_predicate(const std::vector<PredNode>& n
 
 // evaluate_predicate: false = the evaluation is an Err (the reader then selects every row of the stripe)
 bool predicate_row_groups(const std::vector<PredNode>& nodes, const std::vector<std::string>& names, const std::vector<ColumnGroups>& cols,
-                          size_t n_groups, std::vector<uint8_t>& keep) {
+                          size_t n_groups, std::vector<uint8_t>& keep, const std::vector<std::string>* opaque = nullptr) {
   keep.assign(n_groups, 1);
   PredEval ev{nodes, names, cols, n_groups};
+  ev.opaque = opaque;
   const size_t end = ev.eval(0, false, keep);
   return !ev.failed && end == nodes.size();
 }

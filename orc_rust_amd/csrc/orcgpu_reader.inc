@@ -104,6 +104,18 @@ struct orcgpu_reader {
   bool has_collect = false;
   struct orcgpu_key_set* collect_set = nullptr;
   uint32_t collect_col = 0;
+  // computed columns (orcgpu_reader_set_computed_columns): the columns as given (their names and nodes copied); from reader_build
+  // on their plan, which every staged stripe carries into its decode call, and their names behind the roots' in proj.names
+  bool has_computed = false;
+  struct ComputedSpec {
+    std::string name;
+    std::vector<AggSpec::ExprNode> expr;
+  };
+  std::vector<ComputedSpec> computed_specs;
+  std::shared_ptr<orcgpu_host::ComputedPlan> computed_plan;
+  int computed_rc = 0;                        // their refusal, final: every later call that builds the reader gets it again
+  std::string computed_err;
+  std::atomic<uint64_t> computed_overflow{0}; // rows decoded so far whose computed value overflowed (orcgpu_reader_computed_overflow_rows)
   uint64_t d2h_bytes = 0;                     // column-buffer bytes copied to the host so far (orcgpu_reader_d2h_bytes)
   bool current_counted = false;               // ... those of `current` are in it
   bool device_checked = false, device_refused = false;  // the projection has been looked at for nested columns; it has one
@@ -144,8 +156,10 @@ void ctx_err_put(orcgpu_ctx* c, const std::string& text) {
   c->err = text;
 }
 
+int reader_compile_computed(orcgpu_reader* rd);
 int reader_build(orcgpu_reader* rd) {
-  if (rd->built) return ORCGPU_OK;
+  if (rd->built && rd->computed_rc) set_err(rd->ctx, "%s", rd->computed_err.c_str());
+  if (rd->built) return rd->computed_rc;
   rd->built = true;
   rd->stripe_order.clear();
   for (size_t i = 0; i < rd->md.stripes.size(); i++) {
@@ -155,6 +169,14 @@ int reader_build(orcgpu_reader* rd) {
   MetaErr e;
   const int rc = build_projection(rd->md, rd->opt, rd->proj, e);
   if (rc && e.msg[0]) set_err(rd->ctx, "%s", e.msg);
+  if (!rc && rd->has_computed) {  // (a refusal ends the reader: nothing of the file is read)
+    rd->computed_rc = reader_compile_computed(rd);
+    if (rd->computed_rc) {
+      rd->computed_err = ctx_err_text(rd->ctx);
+      rd->next_stripe = rd->stripe_order.size();
+    }
+    return rd->computed_rc;
+  }
   return rc;
 }
 
@@ -186,7 +208,9 @@ int reader_stage_rows(orcgpu_reader* rd, const StripeFooter& sf, const std::vect
   d.streams = streams.data();
   d.n_columns = (uint32_t)cols.size();
   d.columns = cols.data();
-  return orcgpu_stage_stripe(ctx, &d, staged_out);  // (the caller's buffers may go as soon as it returns)
+  const int rc = orcgpu_stage_stripe(ctx, &d, staged_out);  // (the caller's buffers may go as soon as it returns)
+  if (!rc && rd->computed_plan) (*staged_out)->computed = rd->computed_plan;  // (the decode call appends the computed columns)
+  return rc;
 }
 
 // The footer of stripe number `at` of the reader's stripes: the one read ahead, or read now into `local`
@@ -213,7 +237,10 @@ bool reader_predicate_groups(orcgpu_reader* rd, StripeFooter& sf, uint64_t n_row
       }
   const uint64_t stride = rd->md.row_index_stride;
   const uint64_t ng = stride ? (n_rows + stride - 1) / stride : 0;
-  return predicate_row_groups(rd->predicate, names, cols, (size_t)ng, keep);
+  std::vector<std::string> computed;  // (the statistics know nothing of them: a leaf on one keeps every row group)
+  if (rd->computed_plan)
+    for (const ComputedColumn& c : rd->computed_plan->cols) computed.push_back(c.name);
+  return predicate_row_groups(rd->predicate, names, cols, (size_t)ng, keep, rd->computed_plan ? &computed : nullptr);
 }
 
 // The next stripe of the file -> staged rows: the whole stripe, or -- under a row selection, when its ROW_INDEX streams allow
@@ -333,6 +360,12 @@ int reader_compile_filter(orcgpu_reader* rd) {
     c.arrow_target = rd->opt.has_schema ? pc.target : rd->opt.ts_arrow_target;
     params.push_back(t.kind == ORCGPU_T_DECIMAL ? (int32_t)t.scale : ts_unit_of(c));
   }
+  if (rd->computed_plan)  // the computed columns behind the roots: Long, Decimal(38, s) or Double
+    for (const ComputedColumn& c : rd->computed_plan->cols) {
+      names.push_back(c.name.c_str());
+      kinds.push_back(computed_orc_type(c));
+      params.push_back(c.cls == XCLASS_DEC ? c.scale : 3);
+    }
   const std::vector<orcgpu_predicate_node> nodes = view_predicate(rd->filter_nodes);
   const KeySetRefs sets = ctx_key_set_refs(rd->ctx);  // (what a set leaf may name; the plan holds the memory of the ones it does)
   const int rc = filter_compile(nodes.data(), (uint32_t)nodes.size(), names.data(), kinds.data(), (uint32_t)names.size(), rd->filter_plan, params.data(), &sets);
@@ -349,7 +382,7 @@ int reader_compile_filter(orcgpu_reader* rd) {
         if (x.kind != kFilterExprAnyKind) read.push_back(x.col);
     } else if (fop_reads_values(in.op)) read.push_back(in.col);
     for (const uint32_t col : read) {
-      if (col >= names.size() || !rd->proj.cols[roots[col]].dict) continue;
+      if (col >= roots.size() || !rd->proj.cols[roots[col]].dict) continue;  // (past the roots: a computed column)
       set_err(rd->ctx, "row filter: column '%s' is read as a dictionary column (orcgpu_reader_set_dictionary_columns): a comparison on it is not supported", names[col]);
       return ORCGPU_UNSUPPORTED;
     }
@@ -392,7 +425,7 @@ void reader_view_aggs(const orcgpu_reader* rd, ReaderAggView& v) {
 // The aggregate list against the projected root columns as the file's metadata and the builder describe them -> its instructions,
 // once, before anything is read: every refusal arrives here.  (What a stripe's decode made of the columns is checked again, per
 // stripe, by the plan the kernels run: reader_aggregate_result.)
-void reader_describe_roots(orcgpu_reader* rd, std::vector<const char*>& names, std::vector<AggCol>& cols) {
+void reader_describe_file_roots(orcgpu_reader* rd, std::vector<const char*>& names, std::vector<AggCol>& cols) {
   for (size_t k : rd->proj.roots()) {
     const ProjCol& pc = rd->proj.cols[k];
     const OrcType& t = rd->md.types[pc.id];
@@ -412,6 +445,61 @@ void reader_describe_roots(orcgpu_reader* rd, std::vector<const char*>& names, s
     a.nested = is_nested_kind(t.kind);
     cols.push_back(a);
   }
+}
+// ... and behind them the computed columns, as what the decode call makes of them: Long, Decimal(38, s) or Double
+void reader_describe_roots(orcgpu_reader* rd, std::vector<const char*>& names, std::vector<AggCol>& cols) {
+  reader_describe_file_roots(rd, names, cols);
+  if (!rd->computed_plan) return;
+  for (const ComputedColumn& c : rd->computed_plan->cols) {
+    names.push_back(c.name.c_str());
+    AggCol a;
+    a.d.orc_type = computed_orc_type(c);
+    a.d.width = computed_width(c);
+    a.d.ts_unit = 3;
+    a.d.has_present = true;
+    a.scale = c.cls == XCLASS_DEC ? (uint32_t)c.scale : 0;
+    cols.push_back(a);
+  }
+}
+// The computed columns against the file's root columns and the projected ones, once, when the reader is built: every refusal
+// arrives here.  Then their names stand behind the roots' wherever the reader's names are read (proj.names)
+int reader_compile_computed(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<AggCol> cols;
+  reader_describe_file_roots(rd, names, cols);
+  std::vector<AggExprCol> xcols;
+  std::vector<uint8_t> nested;
+  for (const AggCol& c : cols) {
+    xcols.push_back(agg_expr_col(c));
+    nested.push_back(c.nested ? 1 : 0);
+  }
+  std::vector<const char*> file_roots;
+  if (!rd->md.types.empty())
+    for (auto& n : rd->md.types[0].field_names) file_roots.push_back(n.c_str());
+  std::vector<const char*> cnames;
+  std::vector<orcgpu_agg_expr> exprs;
+  std::vector<std::vector<orcgpu_agg_expr_node>> nodes(rd->computed_specs.size());
+  for (size_t k = 0; k < rd->computed_specs.size(); k++) {
+    const orcgpu_reader::ComputedSpec& s = rd->computed_specs[k];
+    cnames.push_back(s.name.c_str());
+    for (const auto& e : s.expr) {
+      orcgpu_agg_expr_node x = e.n;
+      x.column = e.has_column ? e.column.c_str() : nullptr;
+      x.s = e.has_s ? e.s.data() : nullptr;
+      nodes[k].push_back(x);
+    }
+    exprs.push_back({nodes[k].data(), (uint32_t)nodes[k].size()});
+  }
+  auto plan = std::make_shared<ComputedPlan>();
+  const int rc = computed_compile(cnames.data(), exprs.data(), (uint32_t)cnames.size(), file_roots.data(), (uint32_t)file_roots.size(), names.data(), xcols.data(),
+                                  nested.data(), (uint32_t)names.size(), *plan);
+  if (rc) {
+    set_err(rd->ctx, "%s", plan->err);
+    return rc;
+  }
+  for (const ComputedColumn& c : plan->cols) rd->proj.names.push_back(c.name);
+  rd->computed_plan = std::move(plan);
+  return ORCGPU_OK;
 }
 int reader_compile_aggs(orcgpu_reader* rd) {
   std::vector<const char*> names;
@@ -515,6 +603,8 @@ int reader_top_k_result(orcgpu_reader* rd, orcgpu_result* res) {
   if (res->status) return ORCGPU_OK;
   std::vector<const char*> names;
   for (size_t k : rd->proj.roots()) names.push_back(rd->proj.names[rd->proj.cols[k].root].c_str());
+  if (rd->computed_plan)
+    for (const ComputedColumn& c : rd->computed_plan->cols) names.push_back(c.name.c_str());
   if (names.size() != res->cols.size()) {
     set_err(rd->ctx, "top-k: the result holds %zu columns for %zu projected root columns", res->cols.size(), names.size());
     return ORCGPU_UNEXPECTED;
@@ -567,6 +657,7 @@ int reader_finish_decoded(orcgpu_reader* rd, orcgpu_staged* staged, orcgpu_resul
     res->field_names.clear();
     for (auto& c : rd->proj.cols) res->field_names.push_back(c.field);
   }
+  if (!rc) rd->computed_overflow += res->computed_overflow;  // (0 without computed columns)
   if (!rc && staged->has_sel) rc = result_select_batches(rd->ctx, res, staged->sel);
   if (!rc && rd->has_aggs) rc = reader_aggregate_result(rd, res);
   else if (!rc && rd->has_collect) rc = reader_collect_result(rd, res);

@@ -64,6 +64,48 @@ int orcgpu_reader_filter_overflow_rows(const orcgpu_reader* rd, uint64_t* rows) 
   *rows = rd->filter_overflow.load();
   return ORCGPU_OK;
 }
+int orcgpu_reader_set_computed_columns(orcgpu_reader* rd, const char* const* names, const orcgpu_agg_expr* exprs, uint32_t n) {
+  if (!rd) return ORCGPU_INVALID_ARGUMENT;
+  if (rd->built) {
+    set_err(rd->ctx, "computed columns: set after the reader has been built (its first batch, column count or drain)");
+    return ORCGPU_INVALID_ARGUMENT;
+  }
+  // what needs no column of the file is refused here, the rest when the reader is built: the projection is known then
+  char err[256] = "";
+  if (const int rc = orcgpu_host::computed_check_names(names, n, nullptr, 0, err, sizeof(err))) {
+    set_err(rd->ctx, "%s", err);
+    return rc;
+  }
+  for (uint32_t k = 0; k < n; k++)
+    if (!exprs || (exprs[k].n_nodes && !exprs[k].nodes)) {
+      set_err(rd->ctx, "computed columns: an expression without its nodes");
+      return ORCGPU_INVALID_ARGUMENT;
+    }
+  rd->computed_specs.assign(n, {});
+  for (uint32_t k = 0; k < n; k++) {
+    orcgpu_reader::ComputedSpec& s = rd->computed_specs[k];
+    s.name = names[k];
+    // (one node past the limit is kept, so that the plan compiler refuses the expression with its message)
+    for (uint32_t x = 0; x < exprs[k].n_nodes && x <= ORCGPU_AGG_EXPR_MAX_NODES; x++) {
+      const orcgpu_agg_expr_node& nd = exprs[k].nodes[x];
+      orcgpu_reader::AggSpec::ExprNode e;
+      e.n = nd;
+      e.has_column = nd.column != nullptr;
+      if (e.has_column) e.column = nd.column;
+      e.has_s = nd.s != nullptr && nd.s_len <= 64;
+      if (e.has_s) e.s.assign(nd.s, nd.s_len);
+      else e.n.s_len = 0;
+      s.expr.push_back(std::move(e));
+    }
+  }
+  rd->has_computed = true;
+  return ORCGPU_OK;
+}
+int orcgpu_reader_computed_overflow_rows(const orcgpu_reader* rd, uint64_t* rows) {
+  if (!rd || !rows) return ORCGPU_INVALID_ARGUMENT;
+  *rows = rd->computed_overflow.load();
+  return ORCGPU_OK;
+}
 int orcgpu_reader_set_row_group_pruning(orcgpu_reader* rd, int on) {
   if (!rd || rd->built) return ORCGPU_INVALID_ARGUMENT;
   rd->prune = on != 0;
