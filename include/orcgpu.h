@@ -1028,6 +1028,95 @@ int orcgpu_result_compute_columns(orcgpu_ctx* ctx, orcgpu_result* result, const 
                                   const char* const* column_names, uint64_t* overflow_rows);
 int orcgpu_reader_computed_overflow_rows(const orcgpu_reader* r, uint64_t* rows);
 
+/* ---- Key maps and lookup columns: a many-to-one equi-join, build-side columns fetched by key on the device (this library's own) ----
+ * `SELECT A.*, B.v FROM A LEFT JOIN B ON A.fk = B.key` where B.key is unique -- a foreign key against a unique key, what a star
+ * schema needs.  The BUILD side keeps chosen columns beside its keys in HBM (a key map); the PROBE side gets them as ordinary
+ * columns (lookup columns), filled by a kernel inside the decode call.  No key and no value crosses the link.
+ *
+ * A KEY MAP IS A KEY SET THAT ALSO HOLDS VALUES: per distinct non-NULL key of the build side's kept rows one row of
+ * 1 .. ORCGPU_KEY_MAP_MAX_VALUES value columns.  Everything said of a key set above holds for a map: the key kinds (Byte / Short /
+ * Int / Long / Date, as int64), the kept rows (behind the row selection and the row filter), max_keys and its refusal at the seal,
+ * rows_seen, has_null, several readers collecting into one map, the key whose value is the build's free-slot sentinel,
+ * ORCGPU_KEY_SET_HASH_BITS and ORCGPU_POISON.
+ *   - A SEALED MAP MAY BE NAMED BY ORCGPU_PRED_IN_SET exactly as a set is (i = orcgpu_key_map_id): an inner join is the lookup plus
+ *     that leaf; one table serves both.
+ *   - KEYS MUST BE UNIQUE.  A second kept row with a key already in the map -- in the same stripe, another stripe or another reader
+ *     -- sets a sticky flag; orcgpu_key_map_seal then fails with ORCGPU_UNSUPPORTED, the message says "duplicate key", and the map
+ *     is unusable (collect, lookup columns and predicates refuse it; free it).  Which of the two rows came first may depend on the
+ *     run; whether the flag is set may not: it is set exactly when some insert found its own key already present -- for the
+ *     sentinel's value, when the atomic OR of its flag returned "already set".  A NULL build key holds no values and never matches.
+ *   - VALUE COLUMNS.  Byte .. Long and Date become Int64 (a Date is int64 days, as in the row filter's expressions and the computed
+ *     columns); Decimal(p, s) becomes Decimal128(p, s) with the column's own precision and scale; Float / Double become Float64.  A
+ *     NULL value is stored as NULL.  ORCGPU_UNSUPPORTED, the message naming the column: Boolean, String / Varchar / Char / Binary,
+ *     Timestamp, a column read as a dictionary column, a nested column.  ORCGPU_INVALID_ARGUMENT: an unknown or unprojected column,
+ *     a value name listed twice, zero values or more than 8.  A later collect into the same open map whose value count, kinds,
+ *     precision or scale differ from the first collect's is ORCGPU_MISMATCHED_SCHEMA.
+ *   - THE BUILD SIDE NAMES COLUMNS AS EVERY STAGE DOES: the key and the value columns may be computed columns or lookup columns of
+ *     the BUILD reader -- they are ordinary columns by then.  So a snowflake chain is written: customer -> nation is looked up
+ *     while orders -> customer is built.
+ *   - orcgpu_reader_collect_map drains the reader as orcgpu_reader_collect_keys does (no batch, no copy back, no host wait per
+ *     stripe); orcgpu_result_collect_map is the same for one hand-decoded result.  orcgpu_key_map_seal is the build's ONE host wait;
+ *     info: the set's n_keys / has_null / rows_seen, n_values and per value its kind (ORCGPU_KEY_MAP_*), precision and scale.
+ *     Sealing again returns the same info.  orcgpu_key_map_free: the handle goes now, the memory when the last reader or plan that
+ *     probes it is gone -- freeing the handle under a live reader is safe.
+ *   - MEMORY: the set's table (the power of two >= 2 x max_keys slots of 8 bytes, occupancy, 256 control bytes) and, allocated by
+ *     the first collect, per value a plane of (slots + 1) x 8 or 16 bytes and (slots + 1) validity bytes.
+ *
+ * LOOKUP COLUMNS on the probe side: 1 .. ORCGPU_LOOKUP_MAX per reader, each {name, probe key column, map, value index}, over at
+ * most 4 distinct (map, key column) pairs.
+ *   - A row's lookup value is the map's value for the row's key.  It is NULL where the key is NULL, where the map has no such key,
+ *     and where the stored value is NULL: LEFT JOIN.
+ *   - The probe key is a projected flat root column of the key kinds above (anything else: ORCGPU_UNSUPPORTED by name; unknown or
+ *     unprojected: ORCGPU_INVALID_ARGUMENT).  A computed or lookup column as probe key is ORCGPU_UNSUPPORTED.
+ *   - Names obey the computed columns' rules (non-empty, distinct, no root column name of the file) and differ from the computed
+ *     columns' names: ORCGPU_INVALID_ARGUMENT, naming it.
+ *   - PLACE: lookup columns follow the file's projected columns and PRECEDE the computed ones, as nullable fields of type Int64,
+ *     Decimal128(p, s) or Float64 -- in the schema and in every batch, host and device output alike, and among the names the row
+ *     filter, aggregate arguments and conditions, GROUP BY keys (Int64, Decimal; Float64 stays refused), top-k keys,
+ *     orcgpu_reader_collect_keys and orcgpu_reader_collect_map resolve against.
+ *   - As a pruning predicate a leaf on a lookup column keeps every row group.
+ *   - A computed column whose expression names a lookup column is ORCGPU_UNSUPPORTED in this version; the message says so.
+ *   - ORCGPU_INVALID_ARGUMENT: an unsealed or failed map, one of another context, a value index past the map's values, a fifth pair,
+ *     setting them after the reader has been built.  ORCGPU_UNSUPPORTED: a nested column in the projection.  Refusals that need the
+ *     file's columns arrive with the first batch (or the aggregate / collect call), as the computed columns' do.
+ * The columns are filled inside the decode call by one launch per (map, key column) pair -- ONE probe per row serves all of the
+ * pair's values --, behind the last kernel that writes a column and in front of the computed columns' kernel and the call's closing
+ * copy, which brings their per-batch null counts back: no host wait is added.  Such a decode call runs on one column lane.  A
+ * reader without lookup columns launches, allocates and exports exactly what it did before.
+ * orcgpu_result_lookup_columns does the same on a hand-decoded result, before any orcgpu_result_select / _filter /
+ * _compute_columns on it: column_names names the result's columns, the lookup columns are appended behind them -- every later
+ * result call then takes n more column names.  One host wait of its own.  A result whose decode failed is left alone. */
+#define ORCGPU_KEY_MAP_MAX_VALUES 8
+#define ORCGPU_LOOKUP_MAX 8
+enum { ORCGPU_KEY_MAP_INT64 = 0, ORCGPU_KEY_MAP_DECIMAL128 = 1, ORCGPU_KEY_MAP_FLOAT64 = 2 };
+typedef struct orcgpu_key_map orcgpu_key_map;
+typedef struct {
+  uint64_t n_keys;    /* distinct non-NULL keys                                        */
+  uint64_t rows_seen; /* input rows of the collects                                    */
+  int32_t has_null;   /* a kept row's key was NULL                                     */
+  uint32_t n_values;  /* value columns (0: nothing was collected)                      */
+  uint32_t kind[ORCGPU_KEY_MAP_MAX_VALUES];      /* ORCGPU_KEY_MAP_*                   */
+  uint32_t precision[ORCGPU_KEY_MAP_MAX_VALUES]; /* Decimal128                         */
+  uint32_t scale[ORCGPU_KEY_MAP_MAX_VALUES];
+} orcgpu_key_map_info;
+typedef struct {
+  const char* name;            /* the lookup column                                    */
+  const char* key_column;      /* the probe key: a projected flat root column          */
+  const orcgpu_key_map* map;   /* sealed, of the reader's context                      */
+  uint32_t value;              /* which of the map's value columns                     */
+  uint32_t pad;
+} orcgpu_lookup_spec;
+int orcgpu_key_map_create(orcgpu_ctx* ctx, uint64_t max_keys, orcgpu_key_map** map);
+int orcgpu_reader_collect_map(orcgpu_reader* r, const char* key_column, const char* const* value_columns, uint32_t n_values, orcgpu_key_map* map);
+int orcgpu_result_collect_map(orcgpu_ctx* ctx, const orcgpu_result* r, const orcgpu_predicate_node* nodes, uint32_t n_nodes,
+                              const char* const* column_names, uint32_t n_columns, const char* key_column, const char* const* value_columns,
+                              uint32_t n_values, orcgpu_key_map* map);
+int orcgpu_key_map_seal(orcgpu_key_map* map, orcgpu_key_map_info* info);
+uint64_t orcgpu_key_map_id(const orcgpu_key_map* map);
+void orcgpu_key_map_free(orcgpu_key_map* map);
+int orcgpu_reader_set_lookup_columns(orcgpu_reader* r, const orcgpu_lookup_spec* specs, uint32_t n);
+int orcgpu_result_lookup_columns(orcgpu_ctx* ctx, orcgpu_result* result, const orcgpu_lookup_spec* specs, uint32_t n, const char* const* column_names);
+
 /* ---- device-resident batches (Arrow C Device Data Interface, DLPack) --------------------------------------------------------------
  * A decoded result lives in HBM; the entry points above copy it to pinned host memory before a consumer sees a byte.  These
  * hand the device buffers out instead, for consumers on the same GPU (a torch model, this library's own writer with

@@ -7,5 +7,6 @@ from .arrow_reader import ArrowReader, ArrowReaderBuilder  # noqa: F401
 from .arrow_writer import ArrowWriter, ArrowWriterBuilder  # noqa: F401
 from .device_batch import DeviceColumn, DeviceRecordBatch  # noqa: F401
 from .key_set import KeySet  # noqa: F401
+from .key_map import KeyMap  # noqa: F401
 
-__all__ = ["capi", "ArrowReader", "ArrowReaderBuilder", "ArrowWriter", "ArrowWriterBuilder", "DeviceColumn", "DeviceRecordBatch", "KeySet"]
+__all__ = ["capi", "ArrowReader", "ArrowReaderBuilder", "ArrowWriter", "ArrowWriterBuilder", "DeviceColumn", "DeviceRecordBatch", "KeySet", "KeyMap"]

@@ -165,6 +165,23 @@ class ArrowReaderBuilder:
         self._ctx._check(self._ctx.L.orcgpu_reader_set_computed_columns(self._h, names, exprs, len(pairs)))
         return self
 
+    def with_lookup_columns(self, key_map, key, columns):
+        """Lookup columns (orcgpu_reader_set_lookup_columns): `key_map` is a sealed orc_rust_amd.KeyMap on this reader's context,
+        `key` the probe key (a projected Byte, Short, Int, Long or Date column of this file), `columns` a dict {output name: build
+        value name}.  Each output column holds, per row, the map's value for the row's key -- NULL where the key is NULL, where the
+        map has no such key and where the stored value is NULL (LEFT JOIN) --, follows the projected columns (in front of the
+        computed ones), and is seen by name by the row filter, the aggregates, GROUP BY, top-k, collect_keys and collect_map.  One
+        call per (map, key); up to 8 columns over up to 4 such pairs."""
+        from .key_map import check_lookup_args, lookup_spec_array
+        so_far = getattr(self, "_lookups", [])
+        entries = so_far + check_lookup_args(key_map, key, columns, so_far=so_far)
+        if key_map.ctx is not self._ctx:
+            raise ValueError("with_lookup_columns: the map lives on another context: open the reader with ctx=key_map.ctx")
+        arr, keep = lookup_spec_array(entries)
+        self._ctx._check(self._ctx.L.orcgpu_reader_set_lookup_columns(self._h, arr, len(arr)))
+        self._lookups = entries
+        return self
+
     def with_row_selection(self, selectors):
         """RowSelection over the file's rows (arrow_reader.rs:113): selectors = [(row_count, skip)], i.e.
         RowSelector::select(n) = (n, False), RowSelector::skip(n) = (n, True)."""
@@ -272,6 +289,29 @@ class ArrowReaderBuilder:
             reader.close()
         return ks
 
+    def collect_map(self, key, values, max_keys=1 << 20, into=None):
+        """The build side of a many-to-one join (orcgpu_reader_collect_map): builds the reader and drains it as collect_keys does;
+        the kept rows' non-NULL keys of `key` go into a hash table on the GPU and, beside each, the row's values of the columns
+        `values` (1 .. 8 projected Byte .. Long, Date, Decimal, Float or Double columns -- computed and lookup columns of this
+        reader among them).  The keys must be unique: a key that comes twice fails the seal ("duplicate key").  Returns the
+        orc_rust_amd.KeyMap, sealed, for with_lookup_columns and Predicate.in_set.  into: a KeyMap that is still open -- it is left
+        open, so that several files can build one map; seal() it afterwards."""
+        from .key_map import KeyMap, check_collect_map_args
+        values = check_collect_map_args(key, values, max_keys, into)
+        km = into if into is not None else KeyMap(self._ctx, max_keys)
+        reader = self.build()
+        try:
+            reader.collect_map(key, values, km)
+            if into is None:
+                km.seal()
+        except Exception:
+            if into is None:
+                km.close()
+            raise
+        finally:
+            reader.close()
+        return km
+
     def with_top_k(self, by, k):
         """ORDER BY by LIMIT k (orcgpu_reader_set_top_k): `by` is a list of orc_rust_amd.top_k.SortKey (a bare column name and a
         (name, "asc" | "desc") tuple are accepted for one).  The reader then iterates every stripe's own at most k best kept rows,
@@ -377,6 +417,16 @@ class ArrowReader:
             raise StopIteration
         self._ctx._check(rc)
         return list(out)[:len(specs)] if raw else A.values_of(out, specs)
+
+    def collect_map(self, key, values, key_map):
+        """Drains this reader into an open KeyMap (orcgpu_reader_collect_map): what ArrowReaderBuilder.collect_map does, for a
+        reader built by hand."""
+        from .key_map import check_collect_map_args
+        values = check_collect_map_args(key, values, key_map.max_keys if hasattr(key_map, "max_keys") else 1, key_map)
+        va = (C.c_char_p * len(values))(*[v.encode() for v in values])
+        self._ctx._check(self._ctx.L.orcgpu_reader_collect_map(self._h, key.encode(), va, len(values), key_map._h))
+        key_map.value_names = values
+        return key_map
 
     def collect_keys(self, column, key_set):
         """Drains this reader into an open KeySet (orcgpu_reader_collect_keys): what ArrowReaderBuilder.collect_keys does, for a

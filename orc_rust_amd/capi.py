@@ -47,6 +47,8 @@ EXPORTS = [
     "orcgpu_key_set_create", "orcgpu_reader_collect_keys", "orcgpu_result_collect_keys", "orcgpu_key_set_seal", "orcgpu_key_set_id",
     "orcgpu_key_set_free",
     "orcgpu_reader_set_computed_columns", "orcgpu_reader_computed_overflow_rows", "orcgpu_result_compute_columns",
+    "orcgpu_key_map_create", "orcgpu_reader_collect_map", "orcgpu_result_collect_map", "orcgpu_key_map_seal", "orcgpu_key_map_id",
+    "orcgpu_key_map_free", "orcgpu_reader_set_lookup_columns", "orcgpu_result_lookup_columns",
 ]
 
 
@@ -148,6 +150,15 @@ ARROW_DICTIONARY_UTF8 = 27  # include/orcgpu.h: ORCGPU_ARROW_DICTIONARY_UTF8 (or
 
 class KeySetInfo(C.Structure):
     _fields_ = [("n_keys", C.c_uint64), ("rows_seen", C.c_uint64), ("has_null", C.c_int32), ("pad", C.c_int32)]
+
+
+class KeyMapInfo(C.Structure):
+    _fields_ = [("n_keys", C.c_uint64), ("rows_seen", C.c_uint64), ("has_null", C.c_int32), ("n_values", C.c_uint32),
+                ("kind", C.c_uint32 * 8), ("precision", C.c_uint32 * 8), ("scale", C.c_uint32 * 8)]
+
+
+class LookupSpec(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("key_column", C.c_char_p), ("map", C.c_void_p), ("value", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class BatchView(C.Structure):
@@ -337,6 +348,17 @@ def load():
     L.orcgpu_key_set_id.argtypes = [C.c_void_p]
     L.orcgpu_key_set_free.restype = None
     L.orcgpu_key_set_free.argtypes = [C.c_void_p]
+    L.orcgpu_key_map_create.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.orcgpu_reader_collect_map.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p]
+    L.orcgpu_result_collect_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PredicateNode), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p,
+                                            C.POINTER(C.c_char_p), C.c_uint32, C.c_void_p]
+    L.orcgpu_key_map_seal.argtypes = [C.c_void_p, C.POINTER(KeyMapInfo)]
+    L.orcgpu_key_map_id.restype = C.c_uint64
+    L.orcgpu_key_map_id.argtypes = [C.c_void_p]
+    L.orcgpu_key_map_free.restype = None
+    L.orcgpu_key_map_free.argtypes = [C.c_void_p]
+    L.orcgpu_reader_set_lookup_columns.argtypes = [C.c_void_p, C.POINTER(LookupSpec), C.c_uint32]
+    L.orcgpu_result_lookup_columns.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LookupSpec), C.c_uint32, C.POINTER(C.c_char_p)]
     _lib = L
     return L
 
@@ -517,6 +539,27 @@ class Context:
         over = C.c_uint64(0)
         self._check(self.L.orcgpu_result_compute_columns(self.h, result.h, names, exprs, len(pairs), cn, C.byref(over)))
         return over.value
+
+    def result_lookup_columns(self, result, key_map, key, columns, column_names):
+        """orcgpu_result_lookup_columns: the lookup columns `columns` ({output name: build value name}) of the sealed KeyMap
+        `key_map`, probed with the result's column `key`, appended behind the columns of a decoded result, which column_names
+        names; before any select / filter / computed column on it."""
+        from .key_map import check_lookup_args, lookup_spec_array
+        arr, keep = lookup_spec_array(check_lookup_args(key_map, key, columns, ctx=self))
+        cn = (C.c_char_p * len(column_names))(*[n.encode() for n in column_names])
+        self._check(self.L.orcgpu_result_lookup_columns(self.h, result.h, arr, len(arr), cn))
+
+    def result_collect_map(self, result, key, values, key_map, column_names, predicate=None):
+        """orcgpu_result_collect_map: the kept rows of a decoded result (predicate None: all rows) give the keys of column `key`
+        and the values of columns `values` to the open KeyMap `key_map`."""
+        from .key_map import check_collect_map_args
+        values = check_collect_map_args(key, values, key_map.max_keys, key_map)
+        nodes, keep = predicate.flatten() if predicate is not None else (None, None)
+        cn = (C.c_char_p * len(column_names))(*[n.encode() for n in column_names])
+        va = (C.c_char_p * len(values))(*[v.encode() for v in values])
+        self._check(self.L.orcgpu_result_collect_map(self.h, result.h, nodes, len(nodes) if nodes is not None else 0, cn, len(column_names), key.encode(), va, len(values),
+                                                     key_map._h))
+        key_map.value_names = values
 
     def result_top_k(self, result, by, k, column_names, predicate=None):
         """orcgpu_result_top_k: the result's batches become the first k of its kept rows (predicate None: all rows) under the sort

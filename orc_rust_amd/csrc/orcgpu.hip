@@ -49,6 +49,7 @@
 #include "device/top_k_kernels.hip"
 #include "device/key_set_kernels.hip"
 #include "device/compute_kernels.hip"
+#include "device/key_map_kernels.hip"
 #include "device/rle_encode.hip"
 #include "device/lz_compress.hip"
 #include "device/writer_types.hip"
@@ -126,6 +127,7 @@ struct StagedStream {
 
 #include "orcgpu_decode_host.inc"
 #include "orcgpu_computed_plan.inc"
+#include "orcgpu_lookup_plan.inc"
 static_assert(kJobBlockBytes == RLE_BLK && kJobTileBlocks == RLE_TILE && kJobCodecByte == CODEC_BYTE, "orcgpu_decode_host.inc states the device's constants");
 
 constexpr int kMaxLanes = 4;
@@ -339,6 +341,8 @@ struct orcgpu_staged {
   bool piece = false;  // some row groups of a stripe (what a selection leaves of it), not the stripe
   // computed columns (orcgpu_computed.inc): the reader's plan; the decode call appends them to the result's columns.  None: null
   std::shared_ptr<const orcgpu_host::ComputedPlan> computed;
+  // lookup columns (orcgpu_lookup.inc): likewise; they stand in front of the computed ones.  None: null
+  std::shared_ptr<const orcgpu_host::LookupPlan> lookup;
   const StagedStream* find(uint32_t col, int kind) const {
     for (auto& s : streams)
       if (s.column_id == col && s.kind == kind) return &s;
@@ -1235,6 +1239,7 @@ orcgpu_host::KeySetRefs ctx_key_set_refs(orcgpu_ctx* ctx);  // (orcgpu_key_set_c
 #include "orcgpu_reader.inc"
 #include "orcgpu_reader_api.inc"
 #include "orcgpu_key_set_call.inc"
+#include "orcgpu_key_map.inc"
 #include "orcgpu_encode.inc"
 #include "orcgpu_compress.inc"
 #include "orcgpu_writer_host.inc"

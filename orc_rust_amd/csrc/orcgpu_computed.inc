@@ -133,7 +133,8 @@ int computed_plan_stripe(LaneRun& R, uint32_t si) {
   orcgpu_result* r = R.results[si];
   Plan& P = R.P;
   const orcgpu_host::ComputedPlan& plan = *s->computed;
-  const size_t n_file = s->cols.size(), n = plan.cols.size();
+  // (the columns in front of the computed ones: the file's, then the lookup columns -- which no program reads)
+  const size_t n_file = s->cols.size() + (s->lookup ? s->lookup->cols.size() : 0), n = plan.cols.size();
   if (R.mask || r->cols.size() != n_file + n) {
     set_err(R.ctx, "computed columns: the decode call is not laid out for them");
     return ORCGPU_UNEXPECTED;

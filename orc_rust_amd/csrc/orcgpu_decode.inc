@@ -52,6 +52,12 @@ struct LaneRun {
     ComputedTable tab;
   };
   std::vector<ComputedPlace> computed;
+  // lookup columns (orcgpu_lookup.inc): per stripe that carries them, where their counts lie in the summary and the jobs in the workspace
+  struct LookupPlace {
+    uint32_t stripe = 0, first_col = 0, n_cols = 0, nullcount_off = 0;
+    uint64_t table_off = 0;
+  };
+  std::vector<LookupPlace> lookup;
 
   uint8_t* arena(const orcgpu_result* r) const { return r->arena[ctx->lane_id].p; }
   // a column's validity words and their ranks (null: no validity)
@@ -65,6 +71,7 @@ struct LaneRun {
 }  // namespace
 
 #include "orcgpu_ext.inc"
+#include "orcgpu_lookup.inc"
 #include "orcgpu_computed.inc"
 
 namespace {
@@ -434,6 +441,7 @@ int plan_columns(LaneRun& R) {
         return rc;
       }
     }
+    if (int rc = lookup_plan_stripe(R, si)) return rc;
     if (int rc = computed_plan_stripe(R, si)) return rc;
   }
   R.ht.cols = host_us_now();
@@ -961,6 +969,8 @@ int launch_dictionaries_and_post(LaneRun& R) {
   R.ht.dict = host_us_now();
   rc = launch_post_ext(R);
   if (rc) return rc;
+  rc = lookup_launch(R);  // (lookup columns: behind the last kernel that writes a column, in front of the computed columns)
+  if (rc) return rc;
   rc = computed_launch(R);  // (computed columns: behind the last kernel that writes a column, their counts into the summary)
   if (rc) return rc;
   HIP_TRY(ctx, launch(summary_to_host_kernel, (uint64_t)(R.SL.bytes / 8), false, 256, R.st, (const unsigned long long*)R.dsum, (unsigned long long*)R.hs,
@@ -1281,6 +1291,7 @@ static int decode_lane(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_t 
   debug_report(R);
   if ((rc = grow_failed_slots(R))) return rc;
   for (auto& cp : R.P.cols) resolve_column(R, cp);
+  lookup_resolve(R);
   computed_resolve(R);
   note_host_parts(R);
   return ORCGPU_OK;
@@ -1338,6 +1349,7 @@ static int reset_results(orcgpu_ctx* ctx, orcgpu_staged* const* stripes, uint32_
     }
     for (auto* sub : r->subs) orcgpu_result_free(sub);
     r->subs.clear();
+    lookup_append_columns(s, r);
     computed_append_columns(s, r);
     r->status = 0;
     r->err_batch = r->err_col = 0;
@@ -1379,7 +1391,7 @@ static int choose_lanes(orcgpu_staged* const* stripes, uint32_t n, std::vector<s
     if (staged >= (64ull << 20) && mx_all >= 16384) want_lanes = 2;
   }
   for (uint32_t si = 0; si < n; si++)
-    if (stripes[si]->computed) want_lanes = 1;  // (computed columns: the operands complete on the stream that evaluates)
+    if (stripes[si]->computed || stripes[si]->lookup) want_lanes = 1;  // (computed columns: the operands complete on the stream that evaluates)
   int n_lanes = (int)std::min<size_t>((size_t)want_lanes, max_cols);
   if (n_lanes <= 1) return n_lanes;
   // the weight of a root column = staged bytes of the streams of its columns over all stripes of the call; one pass per stripe,

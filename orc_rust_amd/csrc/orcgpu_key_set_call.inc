@@ -13,7 +13,11 @@
 namespace {
 struct KeySetMem {
   DevBuf buf;
-  ~KeySetMem() { buf.release(); }
+  DevBuf values;  // a key map's value planes (orcgpu_key_map.inc); a set: none
+  ~KeySetMem() {
+    buf.release();
+    values.release();
+  }
 };
 }  // namespace
 
@@ -25,6 +29,7 @@ struct orcgpu_key_set {
   std::shared_ptr<KeySetMem> mem;
   int state = orcgpu_host::KEY_SET_BUILDING;
   orcgpu_key_set_info info{};
+  uint32_t sealed_flags = 0;  // the control words' flags as the seal fetched them (a key map reads its duplicate flag here)
 };
 
 orcgpu_host::KeySetRefs ctx_key_set_refs(orcgpu_ctx* ctx) {
@@ -106,7 +111,9 @@ int key_set_collect_call(orcgpu_ctx* ctx, const orcgpu_result* r_, const orcgpu_
 namespace orcgpu_host {
 // The collect of one decoded (and selected) stripe of a reader, where the aggregation stands otherwise: nothing stays with the
 // result.  A stripe whose decode failed ends the call.
+int reader_collect_map_result(orcgpu_reader* rd, orcgpu_result* res);  // (orcgpu_key_map.inc)
 int reader_collect_result(orcgpu_reader* rd, orcgpu_result* res) {
+  if (rd->collect_map) return reader_collect_map_result(rd, res);
   if (res->status) {
     set_err(rd->ctx, "stripe decode failed in batch %u, column %u", res->err_batch, res->err_col);
     return res->status;
@@ -194,6 +201,7 @@ int orcgpu_key_set_seal(orcgpu_key_set* set, orcgpu_key_set_info* info) {
       std::lock_guard<std::mutex> g(ctx->key_sets_m);  // (ctx_key_set_refs reads these)
       set->info.n_keys = over ? 0 : ctl.n_keys;
       set->info.has_null = !over && (ctl.flags & KEY_SET_HAS_NULL) ? 1 : 0;
+      set->sealed_flags = ctl.flags;
       set->state = over ? orcgpu_host::KEY_SET_FAILED : orcgpu_host::KEY_SET_SEALED;
     }
   }

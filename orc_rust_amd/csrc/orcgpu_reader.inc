@@ -104,6 +104,20 @@ struct orcgpu_reader {
   bool has_collect = false;
   struct orcgpu_key_set* collect_set = nullptr;
   uint32_t collect_col = 0;
+  // orcgpu_reader_collect_map: the same drain into a key map (collect_set is its set then), with the value columns beside the key
+  struct orcgpu_key_map* collect_map = nullptr;
+  std::vector<uint32_t> collect_values;
+  // lookup columns (orcgpu_reader_set_lookup_columns): the columns as given -- names copied, of each map what a probe needs and a
+  // share of its memory, so that the handle may be freed --; from reader_build on their plan, which every staged stripe carries
+  // into its decode call, and their names behind the roots' and in front of the computed columns' in proj.names
+  bool has_lookup = false;
+  struct LookupSpecCopy {
+    std::string name, key_column;
+    std::shared_ptr<orcgpu_host::LookupMapRef> map;
+    uint32_t value = 0;
+  };
+  std::vector<LookupSpecCopy> lookup_specs;
+  std::shared_ptr<orcgpu_host::LookupPlan> lookup_plan;
   // computed columns (orcgpu_reader_set_computed_columns): the columns as given (their names and nodes copied); from reader_build
   // on their plan, which every staged stripe carries into its decode call, and their names behind the roots' in proj.names
   bool has_computed = false;
@@ -157,6 +171,7 @@ void ctx_err_put(orcgpu_ctx* c, const std::string& text) {
 }
 
 int reader_compile_computed(orcgpu_reader* rd);
+int reader_compile_lookup(orcgpu_reader* rd);
 int reader_build(orcgpu_reader* rd) {
   if (rd->built && rd->computed_rc) set_err(rd->ctx, "%s", rd->computed_err.c_str());
   if (rd->built) return rd->computed_rc;
@@ -169,8 +184,10 @@ int reader_build(orcgpu_reader* rd) {
   MetaErr e;
   const int rc = build_projection(rd->md, rd->opt, rd->proj, e);
   if (rc && e.msg[0]) set_err(rd->ctx, "%s", e.msg);
-  if (!rc && rd->has_computed) {  // (a refusal ends the reader: nothing of the file is read)
-    rd->computed_rc = reader_compile_computed(rd);
+  if (!rc && (rd->has_computed || rd->has_lookup)) {  // (a refusal ends the reader: nothing of the file is read)
+    // the lookup columns first: their names stand in front of the computed columns'.  (computed_rc / _err keep either's refusal)
+    rd->computed_rc = rd->has_lookup ? reader_compile_lookup(rd) : ORCGPU_OK;
+    if (!rd->computed_rc && rd->has_computed) rd->computed_rc = reader_compile_computed(rd);
     if (rd->computed_rc) {
       rd->computed_err = ctx_err_text(rd->ctx);
       rd->next_stripe = rd->stripe_order.size();
@@ -209,7 +226,8 @@ int reader_stage_rows(orcgpu_reader* rd, const StripeFooter& sf, const std::vect
   d.n_columns = (uint32_t)cols.size();
   d.columns = cols.data();
   const int rc = orcgpu_stage_stripe(ctx, &d, staged_out);  // (the caller's buffers may go as soon as it returns)
-  if (!rc && rd->computed_plan) (*staged_out)->computed = rd->computed_plan;  // (the decode call appends the computed columns)
+  if (!rc && rd->lookup_plan) (*staged_out)->lookup = rd->lookup_plan;        // (the decode call appends the lookup columns ...)
+  if (!rc && rd->computed_plan) (*staged_out)->computed = rd->computed_plan;  // (... and the computed columns behind them)
   return rc;
 }
 
@@ -238,9 +256,11 @@ bool reader_predicate_groups(orcgpu_reader* rd, StripeFooter& sf, uint64_t n_row
   const uint64_t stride = rd->md.row_index_stride;
   const uint64_t ng = stride ? (n_rows + stride - 1) / stride : 0;
   std::vector<std::string> computed;  // (the statistics know nothing of them: a leaf on one keeps every row group)
+  if (rd->lookup_plan)
+    for (const LookupColumn& c : rd->lookup_plan->cols) computed.push_back(c.name);
   if (rd->computed_plan)
     for (const ComputedColumn& c : rd->computed_plan->cols) computed.push_back(c.name);
-  return predicate_row_groups(rd->predicate, names, cols, (size_t)ng, keep, rd->computed_plan ? &computed : nullptr);
+  return predicate_row_groups(rd->predicate, names, cols, (size_t)ng, keep, computed.empty() ? nullptr : &computed);
 }
 
 // The next stripe of the file -> staged rows: the whole stripe, or -- under a row selection, when its ROW_INDEX streams allow
@@ -360,7 +380,13 @@ int reader_compile_filter(orcgpu_reader* rd) {
     c.arrow_target = rd->opt.has_schema ? pc.target : rd->opt.ts_arrow_target;
     params.push_back(t.kind == ORCGPU_T_DECIMAL ? (int32_t)t.scale : ts_unit_of(c));
   }
-  if (rd->computed_plan)  // the computed columns behind the roots: Long, Decimal(38, s) or Double
+  if (rd->lookup_plan)  // the lookup columns behind the roots: Long, Decimal(p, s) or Double
+    for (const LookupColumn& c : rd->lookup_plan->cols) {
+      names.push_back(c.name.c_str());
+      kinds.push_back(lookup_orc_type(c.v));
+      params.push_back(c.v.kind == KMV_DEC128 ? (int32_t)c.v.scale : 3);
+    }
+  if (rd->computed_plan)  // the computed columns behind them: Long, Decimal(38, s) or Double
     for (const ComputedColumn& c : rd->computed_plan->cols) {
       names.push_back(c.name.c_str());
       kinds.push_back(computed_orc_type(c));
@@ -449,6 +475,17 @@ void reader_describe_file_roots(orcgpu_reader* rd, std::vector<const char*>& nam
 // ... and behind them the computed columns, as what the decode call makes of them: Long, Decimal(38, s) or Double
 void reader_describe_roots(orcgpu_reader* rd, std::vector<const char*>& names, std::vector<AggCol>& cols) {
   reader_describe_file_roots(rd, names, cols);
+  if (rd->lookup_plan)
+    for (const LookupColumn& c : rd->lookup_plan->cols) {
+      names.push_back(c.name.c_str());
+      AggCol a;
+      a.d.orc_type = lookup_orc_type(c.v);
+      a.d.width = key_map_value_width(c.v.kind);
+      a.d.ts_unit = 3;
+      a.d.has_present = true;
+      a.scale = c.v.kind == KMV_DEC128 ? c.v.scale : 0;
+      cols.push_back(a);
+    }
   if (!rd->computed_plan) return;
   for (const ComputedColumn& c : rd->computed_plan->cols) {
     names.push_back(c.name.c_str());
@@ -490,6 +527,16 @@ int reader_compile_computed(orcgpu_reader* rd) {
     }
     exprs.push_back({nodes[k].data(), (uint32_t)nodes[k].size()});
   }
+  if (rd->lookup_plan)  // (an operand that is a lookup column is refused by name, before the compiler would call it unknown)
+    for (size_t k = 0; k < nodes.size(); k++)
+      for (const orcgpu_agg_expr_node& x : nodes[k]) {
+        char err[320];
+        if (x.op != ORCGPU_AGG_EXPR_COLUMN || !x.column) continue;
+        if (const int rc = lookup_refuse_computed_operand(*rd->lookup_plan, cnames[k], x.column, err, sizeof(err))) {
+          set_err(rd->ctx, "%s", err);
+          return rc;
+        }
+      }
   auto plan = std::make_shared<ComputedPlan>();
   const int rc = computed_compile(cnames.data(), exprs.data(), (uint32_t)cnames.size(), file_roots.data(), (uint32_t)file_roots.size(), names.data(), xcols.data(),
                                   nested.data(), (uint32_t)names.size(), *plan);
@@ -499,6 +546,44 @@ int reader_compile_computed(orcgpu_reader* rd) {
   }
   for (const ComputedColumn& c : plan->cols) rd->proj.names.push_back(c.name);
   rd->computed_plan = std::move(plan);
+  return ORCGPU_OK;
+}
+// The lookup columns against the file's root columns, the projected ones and the computed columns' names, once, when the reader is
+// built and in front of the computed columns: every refusal arrives here.  Then their names stand behind the roots' in proj.names
+int reader_compile_lookup(orcgpu_reader* rd) {
+  std::vector<const char*> names;
+  std::vector<AggCol> cols;
+  reader_describe_file_roots(rd, names, cols);
+  std::vector<LookupProjCol> pcols;
+  for (const AggCol& c : cols) {
+    LookupProjCol p;
+    p.orc_type = c.d.orc_type;
+    p.dict_read = c.d.dict_out;
+    p.nested = c.nested;
+    pcols.push_back(p);
+  }
+  std::vector<const char*> file_roots, computed;
+  if (!rd->md.types.empty())
+    for (auto& n : rd->md.types[0].field_names) file_roots.push_back(n.c_str());
+  for (const orcgpu_reader::ComputedSpec& s : rd->computed_specs) computed.push_back(s.name.c_str());
+  std::vector<LookupSpec> specs;
+  for (const orcgpu_reader::LookupSpecCopy& s : rd->lookup_specs) {
+    LookupSpec x;
+    x.name = s.name.c_str();
+    x.key_column = s.key_column.c_str();
+    x.map = s.map.get();
+    x.value = s.value;
+    specs.push_back(x);
+  }
+  auto plan = std::make_shared<LookupPlan>();
+  const int rc = lookup_compile(specs.data(), (uint32_t)specs.size(), file_roots.data(), (uint32_t)file_roots.size(), computed.data(), (uint32_t)computed.size(), names.data(),
+                                pcols.data(), (uint32_t)names.size(), *plan);
+  if (rc) {
+    set_err(rd->ctx, "%s", plan->err);
+    return rc;
+  }
+  for (const LookupColumn& c : plan->cols) rd->proj.names.push_back(c.name);
+  rd->lookup_plan = std::move(plan);
   return ORCGPU_OK;
 }
 int reader_compile_aggs(orcgpu_reader* rd) {
@@ -603,6 +688,8 @@ int reader_top_k_result(orcgpu_reader* rd, orcgpu_result* res) {
   if (res->status) return ORCGPU_OK;
   std::vector<const char*> names;
   for (size_t k : rd->proj.roots()) names.push_back(rd->proj.names[rd->proj.cols[k].root].c_str());
+  if (rd->lookup_plan)
+    for (const LookupColumn& c : rd->lookup_plan->cols) names.push_back(c.name.c_str());
   if (rd->computed_plan)
     for (const ComputedColumn& c : rd->computed_plan->cols) names.push_back(c.name.c_str());
   if (names.size() != res->cols.size()) {

@@ -34,6 +34,8 @@ def check_collect_args(column, max_keys, into):
     check_max_keys(max_keys)
     if into is not None and not isinstance(into, KeySet):
         raise TypeError("collect_keys: into is a KeySet, not %s" % type(into).__name__)
+    if into is not None and type(into) is not KeySet and hasattr(into, "value_names"):
+        raise TypeError("collect_keys: into is a KeyMap: a map takes its keys with their values (collect_map)")
     if into is not None and into.sealed:
         raise ValueError("collect_keys: into is sealed: it takes no further keys")
 
