@@ -444,7 +444,9 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_EXPR_NEG = 25 /* exactly one child */,
        ORCGPU_PRED_IN_SET = 26 /* x IN SET s, this library's own: a leaf with column and i = orcgpu_key_set_id of a sealed key set of
                                   the same context; no children.  There is no NOT IN SET: put ORCGPU_PRED_NOT above the leaf.  See
-                                  "key sets" below */ };
+                                  "key sets" below */,
+       ORCGPU_PRED_EXPR_DATE_PART = 36 /* an expression node like 20 .. 25 (ORCGPU_AGG_EXPR_DATE_PART + 20): exactly one child,
+                                          i = ORCGPU_DATE_PART_*.  A leaf that holds one keeps every row group when pruning */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
 #define ORCGPU_IN_MAX_BYTES (4u << 20)
@@ -561,7 +563,8 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     literal of |value| < 10^38) compiles to that comparison, the operator mirrored when the column stands on the right -- and
  *     orcgpu_predicate_row_groups prunes it as that comparison when the literal side is ONE literal node; two literal sides
  *     compile to TRUE / FALSE.  Every other expression leaf is a sound "might match" for row-group pruning: it keeps every group
- *     and never fails the evaluation.  LIMITS: each side at most ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH
+ *     and never fails the evaluation; a leaf that holds a date part (ORCGPU_PRED_EXPR_DATE_PART: the expression aggregates' DATE
+ *     PARTS, with the overflow of an operand outside int32 UNKNOWN and counted like any other) is always such a leaf.  LIMITS: each side at most ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH
  *     operand slots (the balanced 16-leaf tree is refused); the leaf counts toward ORCGPU_FILTER_MAX_DEPTH as a leaf alone.  An
  *     expression node anywhere but under an ORCGPU_PRED_CMP_EXPR, a wrong child count, a node list that ends inside a subtree,
  *     a comparison op outside 0 .. 5: ORCGPU_INVALID_ARGUMENT.  Both sides are evaluated by a kernel of its own
@@ -745,7 +748,7 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *   - NODES, in pre-order like orcgpu_predicate_node: ORCGPU_AGG_EXPR_COLUMN (`column`: a projected root column),
  *     ORCGPU_AGG_EXPR_LITERAL (value_type ORCGPU_PV_INT64: i; ORCGPU_PV_FLOAT64: f; ORCGPU_PV_DECIMAL128: s / s_len / i under the
  *     rules of that value type in predicates), ORCGPU_AGG_EXPR_ADD / _SUB / _MUL (exactly two children) and ORCGPU_AGG_EXPR_NEG (one).
- *     No division, no functions.
+ *     ORCGPU_AGG_EXPR_DATE_PART (one child, the part in `i`) is the one function: DATE PARTS below.  No division.
  *   - CLASSES, decided bottom-up when the list is compiled:
  *       INT    Byte .. Long columns and INT64 literals.  Every intermediate value is a signed 128-bit integer.  ORCGPU_AGG_KIND_I128.
  *       DEC    at least one Decimal column or DECIMAL128 literal; Byte .. Long columns and INT64 literals beside them count as
@@ -769,6 +772,27 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *   - OVERFLOW: an INT / DEC operation whose exact result does not fit a signed 128-bit integer -- the multiplication by a power of
  *     ten that aligns two scales included -- sets the sticky overflow flag of the aggregate; that row's value is left out, the row
  *     still counts.  Nothing wraps silently.  The sum itself is 192 bits wide, as for SUM.
+ *   - DATE PARTS: ORCGPU_AGG_EXPR_DATE_PART takes ONE operand expression and, in `i`, a part: ORCGPU_DATE_PART_YEAR, _QUARTER
+ *     (1 .. 4), _MONTH (1 .. 12), _DAY (1 .. 31), _DAY_OF_WEEK (ISO: Monday = 1 .. Sunday = 7), _DAY_OF_YEAR (1 .. 366) -- SQL's
+ *     extract(part from date).  The operand's value is an exact integer number of days since 1970-01-01; the calendar is the
+ *     proleptic Gregorian one with astronomical year numbering (year 0 exists, the years before it are negative), as numpy's
+ *     datetime64 and Arrow's date32 kernels count.  In every stage that speaks this language -- the aggregates here, the row
+ *     filter's ORCGPU_PRED_CMP_EXPR (there the node is ORCGPU_PRED_EXPR_DATE_PART), the computed columns:
+ *       OPERAND  every leaf below the node is a Byte / Short / Int / Long / Date column or an INT64 literal, combined with + - *,
+ *                unary - and further date parts.  Below the node a Date column takes part as int64 days in EVERY mode -- outside
+ *                it nothing changes: SUM(date + 1) stays ORCGPU_MISMATCHED_SCHEMA.  A Decimal or Float / Double column, or a
+ *                DECIMAL128 / FLOAT64 literal, below the node is ORCGPU_MISMATCHED_SCHEMA, the message naming the function
+ *                (`year()`, ...) and the column; every other column keeps the refusal it has without the node.
+ *       RESULT   an integer: of the INT class, or of scale 0 inside a DEC expression (year(d) * 100 + month(d), year(d) * price).
+ *                A FLOAT expression does not take the node: ORCGPU_MISMATCHED_SCHEMA.
+ *       RANGE    the operand must lie in int32, what a Date column holds (years -5877641 .. 5881580).  Outside it the row
+ *                OVERFLOWS exactly as an operation that leaves 128 bits does (below; UNKNOWN and counted in the row filter, NULL and
+ *                counted in a computed column): never a wrapped or clamped value.
+ *       NULL     where any column of the operand is NULL, like every other node.  A date part of literals alone is folded when the
+ *                list is compiled, unless it overflows: then it is left to the rows.
+ *       LIMITS   the node counts against ORCGPU_AGG_EXPR_MAX_NODES and needs the operand slots of its operand.  A part outside
+ *                0 .. 5 and a node without its operand are ORCGPU_INVALID_ARGUMENT.
+ *     Row-group pruning does not look through the node: a filter leaf that holds one keeps every row group.
  *   - OPS: ORCGPU_AGG_OP_SUM_EXPR the sum of the expression over the kept rows where it is not NULL, NULL over no such row;
  *     ORCGPU_AGG_OP_AVG the average of a plain column (the columns SUM takes); ORCGPU_AGG_OP_AVG_EXPR the average of an expression.
  *     A *_EXPR op without an expression -- through an entry point without `exprs` too -- is ORCGPU_INVALID_ARGUMENT.
@@ -785,7 +809,11 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
 #define ORCGPU_AGG_EXPR_MAX_DEPTH 4
 enum { ORCGPU_AGG_OP_SUM_EXPR = 6, ORCGPU_AGG_OP_AVG = 7, ORCGPU_AGG_OP_AVG_EXPR = 8 };
 enum { ORCGPU_AGG_EXPR_COLUMN = 0, ORCGPU_AGG_EXPR_LITERAL = 1, ORCGPU_AGG_EXPR_ADD = 2, ORCGPU_AGG_EXPR_SUB = 3, ORCGPU_AGG_EXPR_MUL = 4,
-       ORCGPU_AGG_EXPR_NEG = 5 };
+       ORCGPU_AGG_EXPR_NEG = 5,
+       /* (6 .. 15: unknown nodes) */
+       ORCGPU_AGG_EXPR_DATE_PART = 16 /* one child; i = ORCGPU_DATE_PART_*: see DATE PARTS above */ };
+enum { ORCGPU_DATE_PART_YEAR = 0, ORCGPU_DATE_PART_QUARTER = 1, ORCGPU_DATE_PART_MONTH = 2, ORCGPU_DATE_PART_DAY = 3,
+       ORCGPU_DATE_PART_DAY_OF_WEEK = 4, ORCGPU_DATE_PART_DAY_OF_YEAR = 5 };
 typedef struct {
   uint32_t op;           /* ORCGPU_AGG_EXPR_*                                   */
   const char* column;    /* COLUMN: the name of a projected root column        */
@@ -993,7 +1021,8 @@ int orcgpu_reader_next_batch(orcgpu_reader* r, struct ArrowArray* out_array, str
 
 /* ---- Computed columns: arithmetic expressions materialised on the device, once per stripe (this library's own) --------------------
  * A reader may be given 1 .. ORCGPU_COMPUTED_MAX computed columns, each {name, expression}, in order.  The expression is an
- * orcgpu_agg_expr over the nodes of the expression aggregates and of the row filter's comparison: column, literal, + - *, unary -.
+ * orcgpu_agg_expr over the nodes of the expression aggregates and of the row filter's comparison: column, literal, + - *, unary -,
+ * and the date part (ORCGPU_AGG_EXPR_DATE_PART: year(d), month(d), ...; an operand outside int32 is NULL and counted, below).
  *   - OPERANDS are projected flat root columns of the file.  Another computed column as an operand is ORCGPU_UNSUPPORTED.  At most
  *     ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH operand slots.
  *   - TYPING is the expression compiler's, in the mode one side of ORCGPU_PRED_CMP_EXPR takes: a Date takes part as int64 days; the

@@ -7,7 +7,8 @@ orcgpu_reader_aggregate): the specs a caller writes, their C form, and the Pytho
 
 An aggregate's argument may be an arithmetic expression over columns and literals, evaluated exactly per kept row on the GPU
 (orcgpu_result_aggregate_exprs): `col(name)` and `lit(v)` build an Expr, `+ - *` and unary `-` combine them, plain Python numbers
-on either side are wrapped.  TPC-H Q1 whole:
+on either side are wrapped; `year(e)`, `quarter(e)`, `month(e)`, `day(e)`, `day_of_week(e)`, `day_of_year(e)` and `extract(part, e)`
+take a calendar field of a Date (or of any integer expression of days since 1970-01-01).  TPC-H Q1 whole:
 
     from orc_rust_amd.aggregate import Agg, col
     price, disc, tax = col("l_extendedprice"), col("l_discount"), col("l_tax")
@@ -23,6 +24,8 @@ from .predicate import Predicate, PredicateNode
 
 COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG, AVG_EXPR = range(9)  # ORCGPU_AGG_OP_*
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(6)  # ORCGPU_AGG_EXPR_*
+EXPR_DATE_PART = 16  # ORCGPU_AGG_EXPR_DATE_PART (6 .. 15 are unknown nodes): one child, the part in the node's `i`
+DATE_PARTS = ("year", "quarter", "month", "day", "day_of_week", "day_of_year")  # ORCGPU_DATE_PART_*, by number
 PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
 EXPR_MAX_NODES, EXPR_MAX_DEPTH = 32, 4  # ORCGPU_AGG_EXPR_MAX_*
 KIND_U64, KIND_I128, KIND_DEC128, KIND_F64, KIND_I64 = range(5)  # ORCGPU_AGG_KIND_*
@@ -72,8 +75,9 @@ def _column(what, name):
 class Expr:
     """An arithmetic expression over columns and literals: built by col() and lit(), combined with + - * and unary -."""
 
-    def __init__(self, op, children=(), column=None, value_type=None, value=None):
+    def __init__(self, op, children=(), column=None, value_type=None, value=None, part=None):
         self.op, self.children, self.column, self.value_type, self.value = op, tuple(children), column, value_type, value
+        self.part = part  # EXPR_DATE_PART: the index into DATE_PARTS
 
     @staticmethod
     def _wrap(x):
@@ -129,6 +133,8 @@ class Expr:
             return "lit(%r)" % (self.value,)
         if self.op == EXPR_NEG:
             return "(-%r)" % (self.children[0],)
+        if self.op == EXPR_DATE_PART:
+            return "%s(%r)" % (DATE_PARTS[self.part], self.children[0])
         return "(%r %s %r)" % (self.children[0], {EXPR_ADD: "+", EXPR_SUB: "-", EXPR_MUL: "*"}[self.op], self.children[1])
 
     def node_count(self):
@@ -154,6 +160,8 @@ class Expr:
                     n.f = e.value
                 else:
                     n.i = e.value
+            elif e.op == EXPR_DATE_PART:
+                n.i = e.part
             out.append(n)
             for c in e.children:
                 walk(c)
@@ -195,6 +203,47 @@ def lit(v):
     if -exponent > 38 or abs(unscaled) >= 10 ** 38:
         raise ValueError("lit: the Decimal %r needs a scale of 0 .. 38 and an unscaled magnitude below 10^38" % (v,))
     return Expr(EXPR_LITERAL, value_type=PV_DECIMAL128, value=(unscaled, -exponent))
+
+
+def extract(part, e):
+    """SQL's extract(part from e) (ORCGPU_AGG_EXPR_DATE_PART): a calendar field of a Date.  part: one of DATE_PARTS -- "year",
+    "quarter" (1 .. 4), "month" (1 .. 12), "day" (1 .. 31), "day_of_week" (ISO: Monday = 1 .. Sunday = 7), "day_of_year" (1 .. 366).
+    e: a column name, or an Expr over Byte / Short / Int / Long / Date columns and ints whose value is a number of days since
+    1970-01-01 (`col("d") + 30`).  Proleptic Gregorian, year 0 exists.  The result is an integer; days outside int32 overflow the
+    row.  year(e), quarter(e), month(e), day(e), day_of_week(e) and day_of_year(e) are extract with the part named."""
+    if not isinstance(part, str):
+        raise TypeError("extract: the part is a str (one of %s), not %s" % (", ".join(DATE_PARTS), type(part).__name__))
+    if part not in DATE_PARTS:
+        raise ValueError("extract: the part is one of %s, got %r" % (", ".join(DATE_PARTS), part))
+    if isinstance(e, str):
+        e = col(e)
+    if not isinstance(e, Expr):
+        raise TypeError("%s: an Expr or a column name, not %s" % (part, type(e).__name__))
+    return Expr(EXPR_DATE_PART, (e,), part=DATE_PARTS.index(part))
+
+
+def year(e):
+    return extract("year", e)
+
+
+def quarter(e):
+    return extract("quarter", e)
+
+
+def month(e):
+    return extract("month", e)
+
+
+def day(e):
+    return extract("day", e)
+
+
+def day_of_week(e):
+    return extract("day_of_week", e)
+
+
+def day_of_year(e):
+    return extract("day_of_year", e)
 
 
 class Agg:

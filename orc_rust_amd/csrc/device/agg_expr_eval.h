@@ -58,6 +58,53 @@ AGG_HD agg_i128 agg_pow10(uint32_t k) {
   return v;
 }
 
+// A calendar field (AX_PART_*) of the day `days` after 1970-01-01, proleptic Gregorian with astronomical year numbering (year 0
+// exists, the years before it are negative), for every int32: civil-from-days by the 400-year era.  32-bit unsigned arithmetic
+// throughout, so that every division is by a constant and becomes a multiply-high; no table, no loop over years.
+// FLOOR, not C's truncation, for the days before the era's origin: the day number is first moved to where nothing is negative.
+// n = days + 2^31 counts from day -2^31; that day lies kDateEra0 whole eras and kDateDay0 days after a 1 March of a year divisible
+// by 400 (0000-03-01 is day -719468, and -2^31 + 719468 = -14695 * 146097 + 131235).  n / 146097 and n % 146097 are taken of the
+// unsigned n, the kDateDay0 days are added to the remainder -- one conditional carry into the era -- and the era number is made
+// signed again at the end, in the year alone.
+constexpr uint32_t kDateEraDays = 146097, kDateDay0 = 131235;
+constexpr int32_t kDateEra0 = -14695;
+static_assert((long long)kDateEra0 * kDateEraDays + kDateDay0 == -2147483648LL + 719468, "day -2^31 in eras and days since 0000-03-01");
+AGG_HD int32_t agg_date_part(int32_t days, uint32_t part) {
+  const uint32_t n = (uint32_t)days ^ 0x80000000u;  // days + 2^31, 0 .. 2^32 - 1
+  if (part == AX_PART_DAY_OF_WEEK) {  // ISO, Monday = 1: 1970-01-01 is a Thursday, and 2^31 = 2 (mod 7), so n = days + 2 (mod 7)
+    const uint32_t w = n % 7u + 1u;   // days + 3 (mod 7), 1 .. 7: 0 = Monday
+    return (int32_t)((w >= 7u ? w - 7u : w) + 1u);
+  }
+  uint32_t era = n / kDateEraDays, doe = n - era * kDateEraDays + kDateDay0;  // doe: the day of the era, 0 .. 146096 after the carry
+  if (doe >= kDateEraDays) {
+    doe -= kDateEraDays;
+    era++;
+  }
+  // the era's four centuries of 36524 days (the last one a day longer), a century's 25 groups of four years of 1461 days (the last
+  // one of a short century a day shorter), a group's four years of 365 days (the last one a day longer): a quotient of 4 is the
+  // last day of the longer last part
+  uint32_t cent = doe / 36524u;
+  cent -= cent >> 2;
+  const uint32_t doc = doe - cent * 36524u;  // 0 .. 36524
+  const uint32_t quad = doc / 1461u;         // 0 .. 24
+  const uint32_t doq = doc - quad * 1461u;   // 0 .. 1460
+  uint32_t yoq = doq / 365u;
+  yoq -= yoq >> 2;
+  const uint32_t doy = doq - yoq * 365u;  // the day of the year that begins on 1 March, 0 .. 365
+  const uint32_t mp = (5u * doy + 2u) / 153u;  // its month, 0 = March .. 11 = February
+  const uint32_t month = mp < 10u ? mp + 3u : mp - 9u;
+  if (part == AX_PART_MONTH) return (int32_t)month;
+  if (part == AX_PART_QUARTER) return (int32_t)((month + 2u) / 3u);
+  if (part == AX_PART_DAY) return (int32_t)(doy - (153u * mp + 2u) / 5u + 1u);
+  if (part == AX_PART_DAY_OF_YEAR) {
+    // January and February close the March year: day 306 is 1 January.  From March on, the civil year is the March year, a leap
+    // year when it is the first of its group of four -- but not the first of a century, unless of the era
+    const uint32_t leap = (yoq == 0u && (quad != 0u || cent == 0u)) ? 1u : 0u;
+    return (int32_t)(mp < 10u ? doy + 60u + leap : doy - 305u);
+  }
+  return (kDateEra0 + (int32_t)era) * 400 + (int32_t)(cent * 100u + quad * 4u + yoq) + (month <= 2u ? 1 : 0);  // AX_PART_YEAR
+}
+
 // (contraction is switched off for the evaluator by name: the rounded-operation intrinsics alone are plain + and * in some
 // toolchains, and "one IEEE operation" must not rest on where the optimiser happens to see a multiply and an add)
 #if defined(__clang__)
@@ -159,6 +206,14 @@ AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row,
         ok &= agg_mul_checked(s.s0, agg_i128_of(op.lo, op.hi), &r);
         s.s0 = r;
         break;
+      case AX_DATE_PART: {
+        // the days must be what a Date holds, int32; one outside overflows like an operation that leaves 128 bits.  The calendar
+        // works on the 32-bit word alone: the 128-bit slots are not live across it
+        const long long d = (long long)s.s0;
+        ok &= s.s0 == (agg_i128)(int32_t)d;
+        s.s0 = (agg_i128)agg_date_part((int32_t)d, op.col);
+        break;
+      }
       default: break;
     }
   }

@@ -220,7 +220,7 @@ group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, Group
 // partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's
 // entries are trusted no further than a slot index below kGroupSlots, the numbers of slot_group no further than a group below
 // kGroupMax: whatever a refused table left in them, every LDS and global address stays in bounds.
-// Resource usage (gfx950): agg_group_partial_kernel 70 VGPRs, 106 SGPRs; agg_group_expr_partial_kernel 74 VGPRs, 106 SGPRs; both no scratch, no
+// Resource usage (gfx950): agg_group_partial_kernel 70 VGPRs, 106 SGPRs; agg_group_expr_partial_kernel 75 VGPRs, 106 SGPRs; both no scratch, no
 // spill of either register kind, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.  (The condition's word is ONE scalar load
 // a trip, cond[w]: a lane's bit of its own word, loaded per lane, cost two and four scalar registers spilled to VGPR lanes.)
 // A kept row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane that holds the empty contribution: it

@@ -294,9 +294,10 @@ group_wide_segments_kernel(const uint32_t* keys, uint32_t cap, uint64_t n_in, co
 }
 
 // out: [group][instruction], n_insn = gridDim.y records a group.  The fold rule of the head comment.
-// Resource usage (gfx950): agg_group_wide_kernel 46 VGPRs, 102 SGPRs; agg_group_wide_expr_kernel 72 VGPRs, 102 SGPRs; both no scratch,
-// no spill, no LDS: occupancy 7 waves / SIMD, by registers alone -- the plain kernel by its scalar registers: the condition's plane
-// (a pointer and the count of planes beside the rows) took it from 94 past the 100 that eight waves allow.
+// Resource usage (gfx950): agg_group_wide_kernel 46 VGPRs, 102 SGPRs; agg_group_wide_expr_kernel 76 VGPRs, 106 SGPRs; both no scratch,
+// no spill, no LDS: occupancy 7 waves / SIMD for the plain kernel, by its scalar registers -- the condition's plane (a pointer and
+// the count of planes beside the rows) took it from 94 past the 100 that eight waves allow -- and 6 for the
+// expression kernel, by its vector registers: seven waves allow 72.
 // A row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane step that adds nothing: start, end, c and
 // every row's lane stay those of the fold rule.  COUNT_ROWS under a condition counts the passing rows, lane by lane.
 // (The body of two kernels, as agg_group_partial_body is: EXPR = false takes the plain kinds, EXPR = true the AK_EXPR_* rows of grid.y.)

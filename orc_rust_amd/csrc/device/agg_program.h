@@ -45,12 +45,15 @@ enum {
   AX_MUL = 8,        //                                          -> a * b
   AX_NEG = 9,        // the top slot -> its negation
   AX_SCALE10 = 10,   // the top slot -> itself times lo / hi = 10^k (k in `col`), exactly
-  AX_N = 11
+  AX_DATE_PART = 11, // the top slot, days since 1970-01-01 -> a calendar field of that day (`col`: AX_PART_*); outside int32: overflow
+  AX_N = 12
 };
+// The calendar fields of AX_DATE_PART (include/orcgpu.h: ORCGPU_DATE_PART_*), proleptic Gregorian, astronomical year numbering
+enum { AX_PART_YEAR = 0, AX_PART_QUARTER = 1, AX_PART_MONTH = 2, AX_PART_DAY = 3, AX_PART_DAY_OF_WEEK = 4, AX_PART_DAY_OF_YEAR = 5, AX_PART_N = 6 };
 constexpr uint32_t kAggExprSlots = 4, kAggExprMaxNodes = 32;
 struct AggExprOp {
   uint32_t op;   // AX_*
-  uint32_t col;  // index into the FilterCol table; AX_SCALE10: k
+  uint32_t col;  // index into the FilterCol table; AX_SCALE10: k; AX_DATE_PART: AX_PART_*
   unsigned long long lo, hi;
 };
 

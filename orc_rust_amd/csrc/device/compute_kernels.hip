@@ -66,7 +66,7 @@ struct ComputeExprRow {
   __device__ __forceinline__ double load_f64(uint32_t col) const { return filter_load_f64(cols[col], r.row); }
 };
 
-// gfx950: VGPRs 54, SGPRs 72, LDS 0, scratch 0 (none expected, none used), occupancy 8 waves / SIMD
+// gfx950: VGPRs 56, SGPRs 90, LDS 0, scratch 0 (none expected, none used), occupancy 8 waves / SIMD
 __global__ __launch_bounds__(256) void compute_columns_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
                                                               uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
   const ComputeJob job = jobs[blockIdx.y];

@@ -2,9 +2,10 @@
 // kernels interpret per kept row (device/agg_program.h: AggExprOp; device/agg_expr_eval.h), free of HIP
 // (tests/hostcheck/agg_expr_check.cpp compiles this very text under AddressSanitizer + UBSan).  The pre-order nodes are parsed into
 // a tree; the tree is typed (INT / DEC / FLOAT), the Decimal scale rule applied -- the operand of lower scale of a + b is wrapped
-// into a multiplication by a power of ten --, subtrees of literals alone folded with the evaluator's own checked arithmetic, the
-// nodes labelled with the operand slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Every refusal
-// of the expression aggregates is decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
+// into a multiplication by a power of ten --, a date part (year(d), ...) typed as an integer over an operand of days, subtrees of
+// literals alone folded with the evaluator's own checked arithmetic and calendar function, the nodes labelled with the operand
+// slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Every refusal of the expression aggregates is
+// decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
 //
 // The row filter's expression leaf (ORCGPU_PRED_CMP_EXPR: lhs OP rhs) has its two sides compiled here too (compile_pair, called by
 // orcgpu_filter_plan.inc): one parse, one typing, one scale rule, one folding and one labelling for both users.  What differs is
@@ -45,6 +46,8 @@ struct AggExprCol {
 };
 
 static_assert(sizeof(AggExprOp) == 24, "agg_program.h: the record the kernels read");
+static_assert((int)AX_PART_YEAR == (int)ORCGPU_DATE_PART_YEAR && (int)AX_PART_DAY_OF_YEAR == (int)ORCGPU_DATE_PART_DAY_OF_YEAR && (int)AX_PART_N == (int)ORCGPU_DATE_PART_DAY_OF_YEAR + 1,
+              "the parts of include/orcgpu.h are the interpreter's");
 static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
 
 enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
@@ -67,6 +70,8 @@ struct AggExprCompiler {
     double fv = 0.0;        // LITERAL of the FLOAT class
     int scale = 0;          // DEC
     uint32_t k = 0;         // kScale
+    uint32_t part = 0;      // DATE_PART: ORCGPU_DATE_PART_*
+    bool in_date = false;   // a leaf that stands below a DATE_PART: its value is a number of days
     uint32_t label = 1;     // operand slots the subtree needs
   };
   static constexpr uint32_t kScale = 100;
@@ -75,9 +80,16 @@ struct AggExprCompiler {
   uint32_t n_src = 0, at = 0;
   const char* first_column = "";
   int cls = XCLASS_INT;
+  uint32_t date_depth = 0;      // parse: the DATE_PART nodes above the node at hand
+  uint32_t date_part_of = 0;    // ... and the part of the innermost one, for the messages
 
-  int fail(int rc, const char* fmt, const char* a = "", const char* b = "", const char* c = "") {
-    snprintf(err, err_len, fmt, a, b, c);
+  static const char* part_name(uint32_t part) {
+    static const char* const n[] = {"year()", "quarter()", "month()", "day()", "day_of_week()", "day_of_year()"};
+    return part < AX_PART_N ? n[part] : "?";
+  }
+
+  int fail(int rc, const char* fmt, const char* a = "", const char* b = "", const char* c = "", const char* d = "") {
+    snprintf(err, err_len, fmt, a, b, c, d);
     return rc;
   }
 
@@ -87,6 +99,8 @@ struct AggExprCompiler {
     const orcgpu_agg_expr_node& s = src[at++];
     Node n;
     n.op = s.op;
+    n.in_date = date_depth != 0;
+    n.part = date_part_of;  // (a leaf: the function it stands below)
     const int me = (int)t.size();
     t.push_back(n);
     if (s.op == ORCGPU_AGG_EXPR_COLUMN) {
@@ -118,6 +132,19 @@ struct AggExprCompiler {
         if (const int rc = parse(b)) return rc;
       t[me].a = a;
       t[me].b = b;
+    } else if (s.op == ORCGPU_AGG_EXPR_DATE_PART) {
+      if (s.i < ORCGPU_DATE_PART_YEAR || s.i > ORCGPU_DATE_PART_DAY_OF_YEAR)
+        return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a date part node of the expression of %s names no part (ORCGPU_DATE_PART_YEAR .. _DAY_OF_YEAR: 0 .. 5)", op_name);
+      const uint32_t outer = date_part_of;
+      date_depth++;
+      date_part_of = (uint32_t)s.i;
+      int a = -1;
+      const int rc = parse(a);
+      date_depth--;
+      date_part_of = outer;
+      if (rc) return rc;
+      t[me].a = a;
+      t[me].part = (uint32_t)s.i;
     } else {
       return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an unknown node in the expression of %s", op_name);
     }
@@ -125,18 +152,25 @@ struct AggExprCompiler {
     return ORCGPU_OK;
   }
 
-  // the class a column takes part as: a Date column is int64 days under a predicate, and nothing an expression takes elsewhere
-  int col_class(uint32_t col) const {
+  // the class a column takes part as: a Date column is int64 days under a predicate and below a date part, and nothing an
+  // expression takes elsewhere
+  int col_class(uint32_t col, bool in_date = false) const {
     const int k = agg_class(cols[col].orc_type);
-    return predicate && k == ACLASS_DATE ? ACLASS_INT : k;
+    return (predicate || in_date) && k == ACLASS_DATE ? ACLASS_INT : k;
   }
 
   // the class of the expression off its leaves (all of `t`: both sides of a predicate's leaf), or the refusal
   int classify() {
     const char *float_col = nullptr, *exact_col = nullptr;
     bool f64_lit = false, dec_lit = false, dec_col = false;
+    const char* date_fn = nullptr;  // the first date part of the expression
     for (const Node& n : t) {
+      if (n.op == ORCGPU_AGG_EXPR_DATE_PART && !date_fn) date_fn = part_name(n.part);
       if (n.op == ORCGPU_AGG_EXPR_LITERAL) {
+        // the operand of a date part is a number of days: an exact integer
+        if (n.in_date && n.value_type != ORCGPU_PV_INT64)
+          return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s takes days, an integer: a %s literal stands below it", part_name(n.part), op_name,
+                      n.value_type == ORCGPU_PV_FLOAT64 ? "FLOAT64" : "DECIMAL128");
         f64_lit |= n.value_type == ORCGPU_PV_FLOAT64;
         dec_lit |= n.value_type == ORCGPU_PV_DECIMAL128;
       }
@@ -144,7 +178,7 @@ struct AggExprCompiler {
       const AggExprCol& c = cols[n.col];
       const char* name = names[n.col];
       if (c.dict_out) return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' is read as a dictionary column: %s on its keys is not supported", name, op_name);
-      const int k = col_class(n.col);
+      const int k = col_class(n.col, n.in_date);
       if (predicate && k != ACLASS_INT && k != ACLASS_FLOAT && k != ACLASS_DEC)
         return fail(ORCGPU_UNSUPPORTED, "aggregate: column '%s' cannot stand in the expression of %s: Boolean, String / Varchar / Char / Binary, Timestamp and nested columns are not supported there", name, op_name);
       if (k == ACLASS_TS && c.ts_wide)
@@ -152,6 +186,9 @@ struct AggExprCompiler {
       if (k != ACLASS_INT && k != ACLASS_FLOAT && k != ACLASS_DEC) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s does not take column '%s'", op_name, name);
       const uint32_t want = k == ACLASS_FLOAT ? FKIND_FLOAT : k == ACLASS_DEC ? FKIND_DEC128 : FKIND_INT;
       if (c.fkind != want) return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: column '%s' is not decoded to the type the expression of %s needs", name, op_name);
+      if (n.in_date && k != ACLASS_INT)
+        return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s takes days, a Byte / Short / Int / Long / Date column: not the %s column '%s'", part_name(n.part), op_name,
+                    k == ACLASS_FLOAT ? "Float / Double" : "Decimal", name);
       if (k == ACLASS_FLOAT && !float_col) float_col = name;
       if (k != ACLASS_FLOAT && !exact_col) exact_col = name;
       dec_col |= k == ACLASS_DEC;
@@ -166,6 +203,9 @@ struct AggExprCompiler {
     if (dec_lit && float_col)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s'", op_name, float_col);
     cls = float_col || (!exact_col && f64_lit) ? XCLASS_FLOAT : (dec_col || dec_lit) ? XCLASS_DEC : XCLASS_INT;
+    // (reached with a date part of literals alone: one over a column has met the mixing rule above)
+    if (cls == XCLASS_FLOAT && date_fn)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the Float / Double expression of %s holds %s, an integer", op_name, date_fn);
     if (cls == XCLASS_FLOAT)
       for (Node& n : t)
         if (n.op == ORCGPU_AGG_EXPR_LITERAL && n.value_type == ORCGPU_PV_INT64) {
@@ -213,6 +253,8 @@ struct AggExprCompiler {
     if (cls == XCLASS_DEC) {
       if (op == ORCGPU_AGG_EXPR_MUL) {
         t[n].scale = t[a].scale + t[b].scale;
+      } else if (op == ORCGPU_AGG_EXPR_DATE_PART) {
+        t[n].scale = 0;  // (an integer, over an operand of integers: scale 0 below it too)
       } else if (op == ORCGPU_AGG_EXPR_NEG) {
         t[n].scale = t[a].scale;
       } else {
@@ -228,6 +270,18 @@ struct AggExprCompiler {
     }
     t[n].a = a;
     t[n].b = b;
+    if (op == ORCGPU_AGG_EXPR_DATE_PART) {  // of a literal: folded with the evaluator's own function unless it overflows -- then the rows report it
+      if (is_lit(a) && t[a].iv == (agg_i128)(int32_t)(long long)t[a].iv) {
+        Node lit;
+        lit.op = ORCGPU_AGG_EXPR_LITERAL;
+        lit.value_type = ORCGPU_PV_INT64;
+        lit.iv = agg_date_part((int32_t)(long long)t[a].iv, t[n].part);
+        t[n] = lit;
+        return ORCGPU_OK;
+      }
+      t[n].label = t[a].label;  // (unary: the slots its operand needs)
+      return ORCGPU_OK;
+    }
     if (is_lit(a) && (b < 0 || is_lit(b))) {  // literals alone: folded when the exact result fits
       bool ok = true;
       Node lit;
@@ -257,7 +311,7 @@ struct AggExprCompiler {
     const Node& x = t[n];
     AggExprOp o{};
     if (x.op == ORCGPU_AGG_EXPR_COLUMN) {
-      const int k = col_class(x.col);
+      const int k = col_class(x.col, x.in_date);
       o.op = k == ACLASS_FLOAT ? AX_PUSH_F64 : k == ACLASS_DEC ? AX_PUSH_DEC : AX_PUSH_INT;
       o.col = x.col;
     } else if (x.op == ORCGPU_AGG_EXPR_LITERAL) {
@@ -277,6 +331,10 @@ struct AggExprCompiler {
     } else if (x.op == ORCGPU_AGG_EXPR_NEG) {
       emit(x.a, ops);
       o.op = AX_NEG;
+    } else if (x.op == ORCGPU_AGG_EXPR_DATE_PART) {
+      emit(x.a, ops);
+      o.op = AX_DATE_PART;
+      o.col = x.part;
     } else {
       const bool right_first = t[x.b].label > t[x.a].label;
       emit(right_first ? x.b : x.a, ops);
@@ -345,7 +403,7 @@ struct AggExprCompiler {
     for (size_t k = first_op; k < ops.size(); k++) {
       const uint32_t o = ops[k].op;
       if (o >= AX_PUSH_INT && o <= AX_PUSH_LIT) depth++;
-      else if (o >= AX_ADD && o <= AX_MUL) depth--;
+      else if (o >= AX_ADD && o <= AX_MUL) depth--;  // (AX_NEG, AX_SCALE10, AX_DATE_PART: unary, the depth stays)
       most = depth > most ? depth : most;
     }
     if (most > kAggExprSlots || depth != 1) {

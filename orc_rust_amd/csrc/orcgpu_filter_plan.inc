@@ -27,7 +27,7 @@ static_assert(ORCGPU_PRED_IN == 17 && ORCGPU_PRED_LITERAL == 18 && ORCGPU_IN_MAX
 static_assert(ORCGPU_PRED_CMP_EXPR == 19 && ORCGPU_PRED_EXPR_COLUMN == 20 && ORCGPU_PRED_EXPR_NEG == 25 &&
                   ORCGPU_PRED_EXPR_LITERAL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_LITERAL && ORCGPU_PRED_EXPR_ADD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_ADD &&
                   ORCGPU_PRED_EXPR_SUB - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_SUB && ORCGPU_PRED_EXPR_MUL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MUL &&
-                  ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG,
+                  ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG && ORCGPU_PRED_EXPR_DATE_PART - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DATE_PART,
               "the expression leaf of include/orcgpu.h: its nodes are the expression aggregates', 20 further on");
 static_assert((int)FXC_INT == (int)XCLASS_INT && (int)FXC_DEC == (int)XCLASS_DEC && (int)FXC_FLOAT == (int)XCLASS_FLOAT && sizeof(AggExprOp) == kExprOpBytes, "filter_program.h: an expression leaf's blob");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
@@ -288,6 +288,7 @@ struct FilterCompiler {
         return in_set(n, col);
       }
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: case ORCGPU_PRED_EXPR_NEG:
+      case ORCGPU_PRED_EXPR_DATE_PART:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
@@ -303,7 +304,7 @@ struct FilterCompiler {
     switch (n.op) {
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: kids = 0; break;
       case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: kids = 2; break;
-      case ORCGPU_PRED_EXPR_NEG: kids = 1; break;
+      case ORCGPU_PRED_EXPR_NEG: case ORCGPU_PRED_EXPR_DATE_PART: kids = 1; break;  // (the part travels in `i`, below)
       default: return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds expression nodes only%s (node op %lld)", "", n.op);
     }
     if (n.n_children != kids) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node with the wrong number of children%s (%lld)", "", n.n_children);

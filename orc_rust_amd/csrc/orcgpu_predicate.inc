@@ -577,7 +577,7 @@ struct PredEval {
   size_t expr_end(size_t at) const {
     if (at >= nodes.size()) return 0;
     const PredNode& n = nodes[at];
-    const uint32_t kids = n.op == ORCGPU_PRED_EXPR_COLUMN || n.op == ORCGPU_PRED_EXPR_LITERAL ? 0 : n.op == ORCGPU_PRED_EXPR_NEG ? 1
+    const uint32_t kids = n.op == ORCGPU_PRED_EXPR_COLUMN || n.op == ORCGPU_PRED_EXPR_LITERAL ? 0 : n.op == ORCGPU_PRED_EXPR_NEG || n.op == ORCGPU_PRED_EXPR_DATE_PART ? 1
                         : n.op == ORCGPU_PRED_EXPR_ADD || n.op == ORCGPU_PRED_EXPR_SUB || n.op == ORCGPU_PRED_EXPR_MUL ? 2 : ~0u;
     if (kids == ~0u || n.n_children != kids) return 0;
     size_t next = at + 1;
