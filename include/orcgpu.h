@@ -446,7 +446,11 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
                                   the same context; no children.  There is no NOT IN SET: put ORCGPU_PRED_NOT above the leaf.  See
                                   "key sets" below */,
        ORCGPU_PRED_EXPR_DATE_PART = 36 /* an expression node like 20 .. 25 (ORCGPU_AGG_EXPR_DATE_PART + 20): exactly one child,
-                                          i = ORCGPU_DATE_PART_*.  A leaf that holds one keeps every row group when pruning */ };
+                                          i = ORCGPU_DATE_PART_*.  A leaf that holds one keeps every row group when pruning */,
+       ORCGPU_PRED_EXPR_DIV = 37, ORCGPU_PRED_EXPR_FLOOR_DIV = 38, ORCGPU_PRED_EXPR_MOD = 39
+                                       /* a / b, a // b, a % b: expression nodes like 20 .. 25 (ORCGPU_AGG_EXPR_DIV .. _MOD + 20), exactly
+                                          two children; DIV: i = the result scale 0 .. 38, or -1 (the expression aggregates' DIVISION).
+                                          A leaf that holds one keeps every row group when pruning */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
 #define ORCGPU_IN_MAX_BYTES (4u << 20)
@@ -564,7 +568,9 @@ int orcgpu_reader_set_predicate(orcgpu_reader* r, const orcgpu_predicate_node* n
  *     orcgpu_predicate_row_groups prunes it as that comparison when the literal side is ONE literal node; two literal sides
  *     compile to TRUE / FALSE.  Every other expression leaf is a sound "might match" for row-group pruning: it keeps every group
  *     and never fails the evaluation; a leaf that holds a date part (ORCGPU_PRED_EXPR_DATE_PART: the expression aggregates' DATE
- *     PARTS, with the overflow of an operand outside int32 UNKNOWN and counted like any other) is always such a leaf.  LIMITS: each side at most ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH
+ *     PARTS, with the overflow of an operand outside int32 UNKNOWN and counted like any other) is always such a leaf, and so is one
+ *     that holds a division (ORCGPU_PRED_EXPR_DIV / _FLOOR_DIV / _MOD: the expression aggregates' DIVISION; a zero divisor is an
+ *     overflow, so the row is UNKNOWN and counted).  LIMITS: each side at most ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH
  *     operand slots (the balanced 16-leaf tree is refused); the leaf counts toward ORCGPU_FILTER_MAX_DEPTH as a leaf alone.  An
  *     expression node anywhere but under an ORCGPU_PRED_CMP_EXPR, a wrong child count, a node list that ends inside a subtree,
  *     a comparison op outside 0 .. 5: ORCGPU_INVALID_ARGUMENT.  Both sides are evaluated by a kernel of its own
@@ -748,7 +754,8 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *   - NODES, in pre-order like orcgpu_predicate_node: ORCGPU_AGG_EXPR_COLUMN (`column`: a projected root column),
  *     ORCGPU_AGG_EXPR_LITERAL (value_type ORCGPU_PV_INT64: i; ORCGPU_PV_FLOAT64: f; ORCGPU_PV_DECIMAL128: s / s_len / i under the
  *     rules of that value type in predicates), ORCGPU_AGG_EXPR_ADD / _SUB / _MUL (exactly two children) and ORCGPU_AGG_EXPR_NEG (one).
- *     ORCGPU_AGG_EXPR_DATE_PART (one child, the part in `i`) is the one function: DATE PARTS below.  No division.
+ *     ORCGPU_AGG_EXPR_DATE_PART (one child, the part in `i`) is the one function: DATE PARTS below.
+ *     ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD (exactly two children; DIV: a result scale in `i`): DIVISION below.
  *   - CLASSES, decided bottom-up when the list is compiled:
  *       INT    Byte .. Long columns and INT64 literals.  Every intermediate value is a signed 128-bit integer.  ORCGPU_AGG_KIND_I128.
  *       DEC    at least one Decimal column or DECIMAL128 literal; Byte .. Long columns and INT64 literals beside them count as
@@ -793,6 +800,32 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *       LIMITS   the node counts against ORCGPU_AGG_EXPR_MAX_NODES and needs the operand slots of its operand.  A part outside
  *                0 .. 5 and a node without its operand are ORCGPU_INVALID_ARGUMENT.
  *     Row-group pruning does not look through the node: a filter leaf that holds one keeps every row group.
+ *   - DIVISION: three binary nodes, a / b (ORCGPU_AGG_EXPR_DIV), a // b (_FLOOR_DIV) and a % b (_MOD), in every stage that speaks
+ *     this language -- the aggregates here, the row filter's ORCGPU_PRED_CMP_EXPR (there the nodes are ORCGPU_PRED_EXPR_DIV /
+ *     _FLOOR_DIV / _MOD), the computed columns:
+ *       a / b, FLOAT   one IEEE double division, correctly rounded: x / 0 is +-Infinity and 0 / 0 NaN.  Never an overflow.  `i` is
+ *                not read beyond its range check.
+ *       a / b, EXACT   an expression of integer or Decimal leaves that holds a `/` ANYWHERE is of the DEC class, with no Decimal leaf
+ *                at all too: long / 2 is a Decimal.  With the operands' scales sa and sb, the result's scale s is the node's `i`:
+ *                0 .. 38 the caller's choice, -1 the default rule s = min(38, max(6, sa + 4)); any other `i` is
+ *                ORCGPU_INVALID_ARGUMENT.  Let k = s - sa + sb: k < 0 or k > 38 is ORCGPU_UNSUPPORTED, the message naming the three
+ *                scales.  The value is the exact quotient at scale s, rounded half away from zero as AVG's is: over the unscaled
+ *                integers Q = round(A * 10^k / B).  The row OVERFLOWS when B = 0, when A * 10^k leaves a signed 128-bit integer, or
+ *                when the quotient does (-2^127 / -1).  A 256-bit numerator, which would keep the rows whose quotient fits although
+ *                A * 10^k does not, is not built: those rows overflow.
+ *       a // b, a % b  Python's and numpy's rule: the quotient is floored and the remainder has the divisor's sign, so that
+ *                a == (a // b) * b + a % b.  Both operands are integers: of the INT class, or subtrees of scale 0 inside a DEC
+ *                expression (year(d) % 100 beside a price); the result is an integer, of scale 0.  An operand of a non-zero scale is
+ *                ORCGPU_MISMATCHED_SCHEMA, the message naming the operator and the expression's first column; either operator in a
+ *                FLOAT expression is the same status.  The row OVERFLOWS when b = 0, and for // at -2^127 // -1.  An INT
+ *                expression that holds only these two stays of the INT class.
+ *       OVERFLOW is what it is everywhere in this language: AGG_OVERFLOW's sticky flag in an aggregate, UNKNOWN and counted in the
+ *                row filter, NULL and counted in a computed column.  A result is never wrapped, clamped or silently NULL.
+ *       NULL     where any column of either operand is NULL.  A division of literals alone is folded when the list is compiled,
+ *                unless it overflows: then it is left to the rows.
+ *       LIMITS   each node counts against ORCGPU_AGG_EXPR_MAX_NODES and needs operand slots like + - *.  The operand of a date part
+ *                is an integer: a quotient of a non-zero scale below one is ORCGPU_MISMATCHED_SCHEMA.
+ *     Row-group pruning does not look through a division: a filter leaf that holds one keeps every row group.
  *   - OPS: ORCGPU_AGG_OP_SUM_EXPR the sum of the expression over the kept rows where it is not NULL, NULL over no such row;
  *     ORCGPU_AGG_OP_AVG the average of a plain column (the columns SUM takes); ORCGPU_AGG_OP_AVG_EXPR the average of an expression.
  *     A *_EXPR op without an expression -- through an entry point without `exprs` too -- is ORCGPU_INVALID_ARGUMENT.
@@ -811,7 +844,9 @@ enum { ORCGPU_AGG_OP_SUM_EXPR = 6, ORCGPU_AGG_OP_AVG = 7, ORCGPU_AGG_OP_AVG_EXPR
 enum { ORCGPU_AGG_EXPR_COLUMN = 0, ORCGPU_AGG_EXPR_LITERAL = 1, ORCGPU_AGG_EXPR_ADD = 2, ORCGPU_AGG_EXPR_SUB = 3, ORCGPU_AGG_EXPR_MUL = 4,
        ORCGPU_AGG_EXPR_NEG = 5,
        /* (6 .. 15: unknown nodes) */
-       ORCGPU_AGG_EXPR_DATE_PART = 16 /* one child; i = ORCGPU_DATE_PART_*: see DATE PARTS above */ };
+       ORCGPU_AGG_EXPR_DATE_PART = 16 /* one child; i = ORCGPU_DATE_PART_*: see DATE PARTS above */,
+       ORCGPU_AGG_EXPR_DIV = 17 /* a / b; i = the result scale 0 .. 38 of an exact division, -1: the default rule */,
+       ORCGPU_AGG_EXPR_FLOOR_DIV = 18 /* a // b */, ORCGPU_AGG_EXPR_MOD = 19 /* a % b: two children each; see DIVISION above */ };
 enum { ORCGPU_DATE_PART_YEAR = 0, ORCGPU_DATE_PART_QUARTER = 1, ORCGPU_DATE_PART_MONTH = 2, ORCGPU_DATE_PART_DAY = 3,
        ORCGPU_DATE_PART_DAY_OF_WEEK = 4, ORCGPU_DATE_PART_DAY_OF_YEAR = 5 };
 typedef struct {
@@ -1022,7 +1057,8 @@ int orcgpu_reader_next_batch(orcgpu_reader* r, struct ArrowArray* out_array, str
 /* ---- Computed columns: arithmetic expressions materialised on the device, once per stripe (this library's own) --------------------
  * A reader may be given 1 .. ORCGPU_COMPUTED_MAX computed columns, each {name, expression}, in order.  The expression is an
  * orcgpu_agg_expr over the nodes of the expression aggregates and of the row filter's comparison: column, literal, + - *, unary -,
- * and the date part (ORCGPU_AGG_EXPR_DATE_PART: year(d), month(d), ...; an operand outside int32 is NULL and counted, below).
+ * the date part (ORCGPU_AGG_EXPR_DATE_PART: year(d), month(d), ...; an operand outside int32 is NULL and counted, below) and the
+ * divisions (ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD; a zero divisor is NULL and counted; int / int is a Decimal128(38, 6) column).
  *   - OPERANDS are projected flat root columns of the file.  Another computed column as an operand is ORCGPU_UNSUPPORTED.  At most
  *     ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH operand slots.
  *   - TYPING is the expression compiler's, in the mode one side of ORCGPU_PRED_CMP_EXPR takes: a Date takes part as int64 days; the

@@ -7,7 +7,8 @@ orcgpu_reader_aggregate): the specs a caller writes, their C form, and the Pytho
 
 An aggregate's argument may be an arithmetic expression over columns and literals, evaluated exactly per kept row on the GPU
 (orcgpu_result_aggregate_exprs): `col(name)` and `lit(v)` build an Expr, `+ - *` and unary `-` combine them, plain Python numbers
-on either side are wrapped; `year(e)`, `quarter(e)`, `month(e)`, `day(e)`, `day_of_week(e)`, `day_of_year(e)` and `extract(part, e)`
+on either side are wrapped; `/` (and `divide(a, b, scale=n)` to choose a Decimal quotient's scale), `//` and `%` divide -- exactly,
+a zero divisor an overflow of the row, `//` and `%` on integers with Python's floor rule; `year(e)`, `quarter(e)`, `month(e)`, `day(e)`, `day_of_week(e)`, `day_of_year(e)` and `extract(part, e)`
 take a calendar field of a Date (or of any integer expression of days since 1970-01-01).  TPC-H Q1 whole:
 
     from orc_rust_amd.aggregate import Agg, col
@@ -25,6 +26,7 @@ from .predicate import Predicate, PredicateNode
 COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG, AVG_EXPR = range(9)  # ORCGPU_AGG_OP_*
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(6)  # ORCGPU_AGG_EXPR_*
 EXPR_DATE_PART = 16  # ORCGPU_AGG_EXPR_DATE_PART (6 .. 15 are unknown nodes): one child, the part in the node's `i`
+EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 17, 18, 19  # ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD: two children; DIV: the result scale, or -1, in `i`
 DATE_PARTS = ("year", "quarter", "month", "day", "day_of_week", "day_of_year")  # ORCGPU_DATE_PART_*, by number
 PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
 EXPR_MAX_NODES, EXPR_MAX_DEPTH = 32, 4  # ORCGPU_AGG_EXPR_MAX_*
@@ -73,11 +75,12 @@ def _column(what, name):
 
 
 class Expr:
-    """An arithmetic expression over columns and literals: built by col() and lit(), combined with + - * and unary -."""
+    """An arithmetic expression over columns and literals: built by col() and lit(), combined with + - * / // % and unary -."""
 
-    def __init__(self, op, children=(), column=None, value_type=None, value=None, part=None):
+    def __init__(self, op, children=(), column=None, value_type=None, value=None, part=None, scale=None):
         self.op, self.children, self.column, self.value_type, self.value = op, tuple(children), column, value_type, value
         self.part = part  # EXPR_DATE_PART: the index into DATE_PARTS
+        self.scale = scale  # EXPR_DIV: the scale of an exact quotient the caller chose (divide), None: the default rule
 
     @staticmethod
     def _wrap(x):
@@ -100,6 +103,24 @@ class Expr:
 
     def __rmul__(self, other):
         return Expr(EXPR_MUL, (Expr._wrap(other), self))
+
+    def __truediv__(self, other):
+        return Expr(EXPR_DIV, (self, Expr._wrap(other)))
+
+    def __rtruediv__(self, other):
+        return Expr(EXPR_DIV, (Expr._wrap(other), self))
+
+    def __floordiv__(self, other):
+        return Expr(EXPR_FLOOR_DIV, (self, Expr._wrap(other)))
+
+    def __rfloordiv__(self, other):
+        return Expr(EXPR_FLOOR_DIV, (Expr._wrap(other), self))
+
+    def __mod__(self, other):
+        return Expr(EXPR_MOD, (self, Expr._wrap(other)))
+
+    def __rmod__(self, other):
+        return Expr(EXPR_MOD, (Expr._wrap(other), self))
 
     def __neg__(self):
         return Expr(EXPR_NEG, (self,))
@@ -135,7 +156,10 @@ class Expr:
             return "(-%r)" % (self.children[0],)
         if self.op == EXPR_DATE_PART:
             return "%s(%r)" % (DATE_PARTS[self.part], self.children[0])
-        return "(%r %s %r)" % (self.children[0], {EXPR_ADD: "+", EXPR_SUB: "-", EXPR_MUL: "*"}[self.op], self.children[1])
+        if self.op == EXPR_DIV and self.scale is not None:
+            return "divide(%r, %r, scale=%d)" % (self.children[0], self.children[1], self.scale)
+        signs = {EXPR_ADD: "+", EXPR_SUB: "-", EXPR_MUL: "*", EXPR_DIV: "/", EXPR_FLOOR_DIV: "//", EXPR_MOD: "%"}
+        return "(%r %s %r)" % (self.children[0], signs[self.op], self.children[1])
 
     def node_count(self):
         return 1 + sum(c.node_count() for c in self.children)
@@ -162,6 +186,8 @@ class Expr:
                     n.i = e.value
             elif e.op == EXPR_DATE_PART:
                 n.i = e.part
+            elif e.op == EXPR_DIV:
+                n.i = -1 if e.scale is None else e.scale
             out.append(n)
             for c in e.children:
                 walk(c)
@@ -203,6 +229,29 @@ def lit(v):
     if -exponent > 38 or abs(unscaled) >= 10 ** 38:
         raise ValueError("lit: the Decimal %r needs a scale of 0 .. 38 and an unscaled magnitude below 10^38" % (v,))
     return Expr(EXPR_LITERAL, value_type=PV_DECIMAL128, value=(unscaled, -exponent))
+
+
+def divide(a, b, scale=None):
+    """a / b (ORCGPU_AGG_EXPR_DIV) with the scale of an exact quotient chosen: a and b are an Expr, a column name or a number.
+    Over integer and Decimal operands the result is a Decimal at `scale` (0 .. 38), the exact quotient rounded half away from zero;
+    scale=None is what `a / b` gives: min(38, max(6, sa + 4)) for a dividend of scale sa.  Over doubles it is one IEEE division and
+    the scale is not read.  A zero divisor, and a dividend that leaves 128 bits once it is taken times the power of ten the scale
+    asks for, overflow the row."""
+    if scale is not None:
+        if isinstance(scale, bool) or not isinstance(scale, int):
+            raise TypeError("divide: the scale is an int 0 .. 38 or None, not %s" % type(scale).__name__)
+        if not 0 <= scale <= 38:
+            raise ValueError("divide: the scale is 0 .. 38, got %d" % scale)
+    ops = []
+    for x in (a, b):
+        if isinstance(x, str):
+            x = col(x)
+        elif not isinstance(x, Expr):
+            if isinstance(x, bool) or not isinstance(x, (int, float, decimal.Decimal)):
+                raise TypeError("divide: an Expr, a column name or a number, not %s" % type(x).__name__)
+            x = lit(x)
+        ops.append(x)
+    return Expr(EXPR_DIV, ops, scale=scale)
 
 
 def extract(part, e):

@@ -37,7 +37,7 @@ COMPUTED_MAX = 8  # ORCGPU_COMPUTED_MAX
 def check_computed_columns(columns):
     """The argument of with_computed_columns, checked before anything reaches the GPU: a dict {name: Expr} or a list / tuple of
     (name, Expr) pairs, 1 .. 8 of them; every name a non-empty str, none twice; every expression an orc_rust_amd.aggregate.Expr
-    (col, lit, + - * and year() .. extract() on them) of at most 32 nodes.  Returns the pairs as a list."""
+    (col, lit, + - * / // %, divide() and year() .. extract() on them) of at most 32 nodes.  Returns the pairs as a list."""
     from .aggregate import EXPR_MAX_NODES, Expr
     if isinstance(columns, dict):
         pairs = list(columns.items())

@@ -3,7 +3,8 @@
 // check that runs it against Python ints (tests/hostcheck/agg_expr_check.cpp): checked signed 128-bit add / subtract / multiply /
 // negate, the powers of ten, the interpreter of a program of AggExprOp (agg_program.h) over four operand slots, and -- host only --
 // AVG's division.  Plain C++ behind AGG_HD; nothing wraps silently: an operation whose exact result does not fit a signed
-// 128-bit integer reports it, and the caller sets AGG_OVERFLOW.
+// 128-bit integer reports it, and the caller sets AGG_OVERFLOW.  Division (/, //, %) is here too: a signed 128-by-128-bit divide
+// by magnitudes with explicit paths, never the compiler's expansion of `__int128 /`; a zero divisor overflows the row.
 #pragma once
 #include <stdint.h>
 
@@ -56,6 +57,100 @@ AGG_HD agg_i128 agg_pow10(uint32_t k) {
   agg_i128 v = 1;
   for (uint32_t x = 0; x < k && x < 38; x++) v *= 10;
   return v;
+}
+
+// ---- division (include/orcgpu.h: DIVISION): by magnitudes, with explicit paths.  gfx950 divides nothing wider than 32 bits in one
+// instruction; a 64-bit unsigned `/` is the widest the compiler is asked to expand here, and `__int128 /` is never written.
+
+// (u1 : u0) / v for u1 < v, so that the quotient fits 64 bits; *rem gets the remainder.  Knuth's algorithm D in two digits of 32
+// bits: v normalised, each quotient digit estimated from the divisor's top digit and corrected at most twice.
+AGG_HD unsigned long long agg_div128_u64(unsigned long long u1, unsigned long long u0, unsigned long long v, unsigned long long* rem) {
+  const unsigned long long b = 1ull << 32;
+  const int s = __builtin_clzll(v);  // (v != 0: u1 < v)
+  v <<= s;
+  const unsigned long long vn1 = v >> 32, vn0 = v & 0xffffffffull;
+  const unsigned long long un32 = s ? (u1 << s) | (u0 >> (64 - s)) : u1, un10 = u0 << s;
+  const unsigned long long un1 = un10 >> 32, un0 = un10 & 0xffffffffull;
+  unsigned long long q1 = un32 / vn1, rhat = un32 - q1 * vn1;
+  for (int k = 0; k < 2 && rhat < b && (q1 >= b || q1 * vn0 > (rhat << 32 | un1)); k++) {
+    q1--;
+    rhat += vn1;
+  }
+  const unsigned long long un21 = (un32 << 32 | un1) - q1 * v;  // (modulo 2^64: the true value is below v)
+  unsigned long long q0 = un21 / vn1;
+  rhat = un21 - q0 * vn1;
+  for (int k = 0; k < 2 && rhat < b && (q0 >= b || q0 * vn0 > (rhat << 32 | un0)); k++) {
+    q0--;
+    rhat += vn1;
+  }
+  *rem = ((un21 << 32 | un0) - q0 * v) >> s;
+  return (q1 << 32) + q0;
+}
+
+// n / d of unsigned 128-bit magnitudes, d != 0; *rem gets the remainder.  Three paths, chosen per lane:
+//   both below 2^64 (almost every real row)   one 64-bit unsigned divide
+//   d below 2^64, n not                       long division, a 128-by-64 step per word of n
+//   d of 2^64 or more                         the quotient is below 2^64: estimated from the divisor's top 64 normalised bits over
+//                                             n / 2 (at most one too large once shifted back, so one is taken off), corrected once
+AGG_HD agg_u128 agg_udivmod128(agg_u128 n, agg_u128 d, agg_u128* rem) {
+  const unsigned long long n0 = (unsigned long long)n, n1 = (unsigned long long)(n >> 64), d0 = (unsigned long long)d, d1 = (unsigned long long)(d >> 64);
+  if (d1 == 0) {
+    if (n1 == 0) {
+      const unsigned long long q = n0 / d0;
+      *rem = n0 - q * d0;
+      return q;
+    }
+    const unsigned long long q1 = n1 / d0;
+    unsigned long long r = n1 - q1 * d0;
+    const unsigned long long q0 = agg_div128_u64(r, n0, d0, &r);
+    *rem = r;
+    return ((agg_u128)q1 << 64) | q0;
+  }
+  const int s = __builtin_clzll(d1);
+  const unsigned long long v1 = (unsigned long long)((d << s) >> 64);  // bit 63 is set
+  unsigned long long r = 0;
+  unsigned long long q = agg_div128_u64(n1 >> 1, (n1 << 63) | (n0 >> 1), v1, &r) >> (63 - s);  // (n1 / 2 < 2^63 <= v1)
+  if (q) q--;
+  agg_u128 left = n - ((agg_u128)q * d0 + ((agg_u128)(q * d1) << 64));  // q * d <= n: nothing leaves 128 bits
+  if (left >= d) {
+    q++;
+    left -= d;
+  }
+  *rem = left;
+  return q;
+}
+
+enum { AGG_DIV_ROUND = 0, AGG_DIV_FLOOR = 1, AGG_DIV_MOD = 2 };
+static_assert(AX_FLOOR_DIV - AX_DIV == AGG_DIV_FLOOR && AX_MOD - AX_DIV == AGG_DIV_MOD, "the interpreter takes the mode off the op");
+// The three divisions of two signed 128-bit integers: AGG_DIV_ROUND the exact quotient rounded half away from zero (a Decimal
+// division, its dividend already times 10^k), AGG_DIV_FLOOR the floored quotient and AGG_DIV_MOD the remainder that goes with it
+// (the divisor's sign, as Python and numpy have them: a == (a // b) * b + a % b).  The magnitudes are divided, then the rounding or
+// the floor adjustment applied, then the sign.  false, and *r = 0: b is zero, or the quotient is 2^127 (-2^127 by -1).
+AGG_HD bool agg_div_checked(agg_i128 a, agg_i128 b, uint32_t mode, agg_i128* r) {
+  *r = 0;
+  if (b == 0) return false;
+  const bool neg = (a < 0) != (b < 0);
+  const agg_u128 ma = a < 0 ? (agg_u128)0 - (agg_u128)a : (agg_u128)a, mb = b < 0 ? (agg_u128)0 - (agg_u128)b : (agg_u128)b;
+  agg_u128 rem = 0;
+  agg_u128 q = agg_udivmod128(ma, mb, &rem);
+  if (mode == AGG_DIV_MOD) {
+    const agg_u128 m = neg && rem != 0 ? mb - rem : rem;  // below |b|: it fits
+    *r = (agg_i128)(b < 0 ? (agg_u128)0 - m : m);
+    return true;
+  }
+  // half or more away from zero (rem < mb: no carry in mb - rem; a quotient that is bumped is below 2^127); the floor of a
+  // negative inexact quotient is one further from zero
+  if (mode == AGG_DIV_ROUND ? rem >= mb - rem : neg && rem != 0) q++;
+  const agg_u128 top = (agg_u128)1 << 127;
+  if (q > top || (q == top && !neg)) return false;
+  *r = (agg_i128)(neg ? (agg_u128)0 - q : q);
+  return true;
+}
+// a / b of Decimals: round(a * 10^k / b) with `pow` = 10^k.  false: b is zero, a * 10^k leaves 128 bits, or the quotient does.
+AGG_HD bool agg_div_scaled_checked(agg_i128 a, agg_i128 pow, agg_i128 b, agg_i128* r) {
+  agg_i128 n = 0;
+  *r = 0;
+  return agg_mul_checked(a, pow, &n) && agg_div_checked(n, b, AGG_DIV_ROUND, r);
 }
 
 // A calendar field (AX_PART_*) of the day `days` after 1970-01-01, proleptic Gregorian with astronomical year numbering (year 0
@@ -126,6 +221,14 @@ AGG_HD double agg_f64_mul(double a, double b) {
   return r;
 #endif
 }
+AGG_HD double agg_f64_div(double a, double b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ddiv_rn(a, b);  // correctly rounded; x / 0 is an infinity and 0 / 0 NaN, as IEEE says
+#else
+  volatile double r = a / b;
+  return r;
+#endif
+}
 AGG_HD double agg_f64_of_bits(unsigned long long u) {
   union {
     unsigned long long u;
@@ -160,6 +263,11 @@ struct AggSlots {
     s1 = s2;
     s2 = s3;
   }
+  AGG_HD void swap() {
+    const T v = s0;
+    s0 = s1;
+    s1 = v;
+  }
 };
 
 enum { AGG_ROW_NULL = 0, AGG_ROW_VALUE = 1, AGG_ROW_OVERFLOW = 2 };
@@ -168,8 +276,11 @@ enum { AGG_ROW_NULL = 0, AGG_ROW_VALUE = 1, AGG_ROW_OVERFLOW = 2 };
 // column) and `agg_i128 load_dec(uint32_t col)`.  AGG_ROW_NULL: a gating column is NULL, the row contributes nothing;
 // AGG_ROW_OVERFLOW: an operation left 128 bits, the row counts and its value is left out; AGG_ROW_VALUE: *out.
 // The host's compiler guarantees what is not checked again here: at most four slots in use, operands where an op takes them.
-template <typename Row>
-AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+// DIV: the divide is compiled in.  The kernels have an instantiation without it, with the registers they had before there was a
+// division, which the host launches for the programs that hold none (agg_ops_hold_division); a division that reaches it all the
+// same overflows the row -- never a silent value.
+template <bool DIV, typename Row>
+AGG_HD int agg_expr_eval_i128_as(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
   AggSlots<agg_i128> s = {0, 0, 0, 0};
   bool ok = true;
   for (uint32_t k = 0; k < n; k++) {
@@ -214,6 +325,23 @@ AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row,
         s.s0 = (agg_i128)agg_date_part((int32_t)d, op.col);
         break;
       }
+      case AX_DIV:
+      case AX_FLOOR_DIV:
+      case AX_MOD: {
+        if constexpr (!DIV) {
+          ok = false;
+          s.merge(0);
+          break;
+        }
+        // ONE divide for the three.  The dividend of a Decimal division is first taken times 10^k; where that product leaves 128
+        // bits the row overflows, whatever the divide makes of the wrapped value
+        agg_i128 a = s.s1;
+        if (op.op == AX_DIV && op.col != 0) ok &= agg_mul_checked(a, agg_i128_of(op.lo, op.hi), &a);
+        ok &= agg_div_checked(a, s.s0, op.op - AX_DIV, &r);
+        s.merge(r);
+        break;
+      }
+      case AX_SWAP: s.swap(); break;
       default: break;
     }
   }
@@ -221,9 +349,15 @@ AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row,
   return ok ? AGG_ROW_VALUE : AGG_ROW_OVERFLOW;
 }
 
-// ... of the FLOAT class.  Row: `valid` and `double load_f64(uint32_t col)`.  Every operation is one IEEE double operation.
 template <typename Row>
-AGG_HD int agg_expr_eval_f64(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+  return agg_expr_eval_i128_as<true>(prog, n, row, out);
+}
+
+// ... of the FLOAT class.  Row: `valid` and `double load_f64(uint32_t col)`.  Every operation is one IEEE double operation.
+// (DIV as above; without it a division gives NaN.)
+template <bool DIV, typename Row>
+AGG_HD int agg_expr_eval_f64_as(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
   AggSlots<double> s = {0.0, 0.0, 0.0, 0.0};
   for (uint32_t k = 0; k < n; k++) {
     const AggExprOp op = prog[k];
@@ -238,11 +372,17 @@ AGG_HD int agg_expr_eval_f64(const AggExprOp* prog, uint32_t n, const Row& row, 
       case AX_RSUB: s.merge(agg_f64_add(s.s0, -s.s1)); break;
       case AX_MUL: s.merge(agg_f64_mul(s.s1, s.s0)); break;
       case AX_NEG: s.s0 = -s.s0; break;
+      case AX_DIV: s.merge(DIV ? agg_f64_div(s.s1, s.s0) : agg_f64_of_bits(0x7ff8000000000000ull)); break;
+      case AX_SWAP: s.swap(); break;
       default: break;
     }
   }
   *out = s.s0;
   return AGG_ROW_VALUE;
+}
+template <typename Row>
+AGG_HD int agg_expr_eval_f64(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+  return agg_expr_eval_f64_as<true>(prog, n, row, out);
 }
 #if defined(__clang__)
 #pragma clang fp contract(fast)  // (what hipcc builds the rest of the library with)

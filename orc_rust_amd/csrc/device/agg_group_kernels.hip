@@ -220,15 +220,17 @@ group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, Group
 // partials: [instruction][block][group], kGroupMax groups a block of which the first ctl->n_groups are written.  The plane's
 // entries are trusted no further than a slot index below kGroupSlots, the numbers of slot_group no further than a group below
 // kGroupMax: whatever a refused table left in them, every LDS and global address stays in bounds.
-// Resource usage (gfx950): agg_group_partial_kernel 70 VGPRs, 106 SGPRs; agg_group_expr_partial_kernel 75 VGPRs, 106 SGPRs; both no scratch, no
+// Resource usage (gfx950): agg_group_partial_kernel 70 VGPRs, 106 SGPRs; agg_group_expr_partial_kernel 75 VGPRs, 106 SGPRs
+// (agg_group_expr_div_partial_kernel, with the divide: 85 VGPRs); all no scratch, no
 // spill of either register kind, 49152 bytes of LDS: three blocks a CU by LDS, 3 waves / SIMD.  (The condition's word is ONE scalar load
 // a trip, cond[w]: a lane's bit of its own word, loaded per lane, cost two and four scalar registers spilled to VGPR lanes.)
 // A kept row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane that holds the empty contribution: it
 // keeps its group, its rank and its place in the tree or the rounds, so the condition never changes which shape runs.
 // (The body of two kernels: EXPR = false is agg_group_partial_kernel, which takes the plain kinds and leaves the AK_EXPR_* rows of
 // grid.y at once; EXPR = true is agg_group_expr_partial_kernel, the other way round, launched only when the list holds such an
-// instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.)
-template <bool EXPR>
+// instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.  DIV: the
+// interpreter with the divide, agg_group_expr_div_partial_kernel, launched in its place when a program holds a division.)
+template <bool EXPR, bool DIV = false>
 __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* plane,
                                                        const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials, AggAcc (*acc_s)[kGroupMax]) {
   const FilterCol* const cols = rows.cols;
@@ -264,7 +266,7 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
     // (a row its instruction's condition does not pass keeps the empty contribution and its place in the fold below)
     const unsigned long long pass_m = blocked ? 0ull : cond ? cond[w] : ~0ull;  // (the word's rows that pass: one scalar load a word)
     if (kept && ((pass_m >> lane) & 1)) {
-      if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
+      if constexpr (EXPR) agg_expr_row<DIV>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
       else if (kind == AK_COUNT_ROWS) v.w0 = 1;
       else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, v);
     }
@@ -331,6 +333,12 @@ agg_group_expr_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRo
                               AggPartial* partials) {
   __shared__ AggAcc acc_s[4][kGroupMax];
   agg_group_partial_body<true>(insns, ops, rows, plane, slot_group, ctl, partials, acc_s);
+}
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_expr_div_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                                  AggPartial* partials) {
+  __shared__ AggAcc acc_s[4][kGroupMax];
+  agg_group_partial_body<true, true>(insns, ops, rows, plane, slot_group, ctl, partials, acc_s);
 }
 
 // grid (kGroupMax, instructions): block (g, k) folds the n_blocks records of group g under instruction k -> out[k][g]; the blocks

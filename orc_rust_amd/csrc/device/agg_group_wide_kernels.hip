@@ -297,11 +297,13 @@ group_wide_segments_kernel(const uint32_t* keys, uint32_t cap, uint64_t n_in, co
 // Resource usage (gfx950): agg_group_wide_kernel 46 VGPRs, 102 SGPRs; agg_group_wide_expr_kernel 76 VGPRs, 106 SGPRs; both no scratch,
 // no spill, no LDS: occupancy 7 waves / SIMD for the plain kernel, by its scalar registers -- the condition's plane (a pointer and
 // the count of planes beside the rows) took it from 94 past the 100 that eight waves allow -- and 6 for the
-// expression kernel, by its vector registers: seven waves allow 72.
+// expression kernel, by its vector registers: seven waves allow 72.  agg_group_wide_expr_div_kernel, the
+// expression kernel with the divide, which only a list that holds a division runs: 82 VGPRs, 106 SGPRs, no scratch, 5 waves (6o).
 // A row whose instruction has a condition (AggInsn::cond) and does not pass it is a lane step that adds nothing: start, end, c and
 // every row's lane stay those of the fold rule.  COUNT_ROWS under a condition counts the passing rows, lane by lane.
-// (The body of two kernels, as agg_group_partial_body is: EXPR = false takes the plain kinds, EXPR = true the AK_EXPR_* rows of grid.y.)
-template <bool EXPR>
+// (The body of two kernels, as agg_group_partial_body is: EXPR = false takes the plain kinds, EXPR = true the AK_EXPR_* rows of grid.y;
+// DIV: the interpreter with the divide, agg_group_wide_expr_div_kernel, launched in its place when a program holds a division.)
+template <bool EXPR, bool DIV = false>
 __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* order_rows, const uint32_t* seg,
                                                     const GroupControl* ctl, uint32_t cap, AggPartial* out) {
   const FilterCol* const cols = rows.cols;
@@ -332,7 +334,7 @@ __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const 
             a.w0++;
             continue;
           }
-          if constexpr (EXPR) agg_expr_row(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, a);
+          if constexpr (EXPR) agg_expr_row<DIV>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, a);
           else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, a);
         }
         agg_wave_fold(kind, is_max, a);
@@ -349,4 +351,9 @@ extern "C" __global__ void __launch_bounds__(256)
 agg_group_wide_expr_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* order_rows, const uint32_t* seg, const GroupControl* ctl,
                            uint32_t cap, AggPartial* out) {
   agg_group_wide_body<true>(insns, ops, rows, order_rows, seg, ctl, cap, out);
+}
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_wide_expr_div_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* order_rows, const uint32_t* seg, const GroupControl* ctl,
+                               uint32_t cap, AggPartial* out) {
+  agg_group_wide_body<true, true>(insns, ops, rows, order_rows, seg, ctl, cap, out);
 }

@@ -1,6 +1,7 @@
 // agg_program.h -- an aggregate list as the host compiles it (orcgpu_agg_plan.inc) and agg_partial_kernel / agg_final_kernel run
 // it (agg_kernels.hip), and the record both kernels and the host's merge speak in.  Plain C++: no HIP in here.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 // What an instruction accumulates, and from what the column holds (the FKIND_* of filter_program.h say how a value is loaded)
@@ -46,16 +47,30 @@ enum {
   AX_NEG = 9,        // the top slot -> its negation
   AX_SCALE10 = 10,   // the top slot -> itself times lo / hi = 10^k (k in `col`), exactly
   AX_DATE_PART = 11, // the top slot, days since 1970-01-01 -> a calendar field of that day (`col`: AX_PART_*); outside int32: overflow
-  AX_N = 12
+  // Division (include/orcgpu.h: DIVISION).  Each takes the two top slots a (below) and b (top), like AX_SUB; none commutes, and there
+  // are no reversed forms: where the right child was evaluated first, the compiler puts ONE AX_SWAP in front of the op.
+  AX_DIV = 12,       // -> a / b.  INT / DEC: round(a * 10^k / b), half away from zero (k in `col`, 10^k in lo / hi); FLOAT: one IEEE division
+  AX_FLOOR_DIV = 13, // -> floor(a / b), integers (INT / DEC alone)
+  AX_MOD = 14,       // -> a - floor(a / b) * b: the remainder with the divisor's sign (INT / DEC alone)
+  AX_SWAP = 15,      // the two top slots change places
+  AX_N = 16
 };
 // The calendar fields of AX_DATE_PART (include/orcgpu.h: ORCGPU_DATE_PART_*), proleptic Gregorian, astronomical year numbering
 enum { AX_PART_YEAR = 0, AX_PART_QUARTER = 1, AX_PART_MONTH = 2, AX_PART_DAY = 3, AX_PART_DAY_OF_WEEK = 4, AX_PART_DAY_OF_YEAR = 5, AX_PART_N = 6 };
 constexpr uint32_t kAggExprSlots = 4, kAggExprMaxNodes = 32;
 struct AggExprOp {
   uint32_t op;   // AX_*
-  uint32_t col;  // index into the FilterCol table; AX_SCALE10: k; AX_DATE_PART: AX_PART_*
+  uint32_t col;  // index into the FilterCol table; AX_SCALE10, AX_DIV: k; AX_DATE_PART: AX_PART_*
   unsigned long long lo, hi;
 };
+
+// Does a table of programs hold a division?  The host asks before a launch: the kernels that interpret programs come in two
+// instantiations, and the one without the divide keeps the registers -- and the occupancy -- it had before there was one.
+inline bool agg_ops_hold_division(const AggExprOp* ops, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (ops[k].op >= AX_DIV && ops[k].op <= AX_MOD) return true;
+  return false;
+}
 
 struct AggInsn {
   uint32_t kind;     // AK_*

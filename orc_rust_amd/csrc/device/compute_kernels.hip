@@ -66,9 +66,13 @@ struct ComputeExprRow {
   __device__ __forceinline__ double load_f64(uint32_t col) const { return filter_load_f64(cols[col], r.row); }
 };
 
-// gfx950: VGPRs 56, SGPRs 90, LDS 0, scratch 0 (none expected, none used), occupancy 8 waves / SIMD
-__global__ __launch_bounds__(256) void compute_columns_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
-                                                              uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
+// gfx950: compute_columns_kernel VGPRs 55, SGPRs 90; compute_columns_div_kernel VGPRs 63, SGPRs 96; both LDS 0, scratch 0 (none
+// expected, none used), occupancy 8 waves / SIMD
+// (The body of two kernels: DIV = false is compute_columns_kernel; DIV = true, the interpreter with the divide, is
+// compute_columns_div_kernel, launched in its place when a program of the plan holds a division.)
+template <bool DIV>
+__device__ __forceinline__ void compute_columns_body(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches, uint32_t B, uint32_t W,
+                                                     const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
   const ComputeJob job = jobs[blockIdx.y];
   const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= (uint64_t)n_batches * W) return;  // (the whole wavefront: the ballot below is taken by the wavefronts that stay)
@@ -89,9 +93,9 @@ __global__ __launch_bounds__(256) void compute_columns_kernel(const ComputeJob* 
   if (live && sane) {
     const ComputeExprRow x{cols, filter_row_of(row, B), W};
     if (job.kind == CK_F64) {
-      state = agg_expr_eval_f64(job.prog, job.n_ops, x, &fv);
+      state = agg_expr_eval_f64_as<DIV>(job.prog, job.n_ops, x, &fv);
     } else {
-      state = agg_expr_eval_i128(job.prog, job.n_ops, x, &iv);
+      state = agg_expr_eval_i128_as<DIV>(job.prog, job.n_ops, x, &iv);
       if (state == AGG_ROW_VALUE) {
         if (job.kind == CK_INT64) {
           if (iv != (agg_i128)(long long)iv) state = AGG_ROW_OVERFLOW;
@@ -139,4 +143,12 @@ __global__ __launch_bounds__(256) void compute_columns_kernel(const ComputeJob* 
     if (nulls) atomicAdd(job.null_counts + u, (unsigned long long)nulls);
     if (m_over) atomicAdd(job.overflow_rows, (unsigned long long)__popcll(m_over));
   }
+}
+__global__ __launch_bounds__(256) void compute_columns_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
+                                                              uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
+  compute_columns_body<false>(jobs, cols, n_cols, n_rows, n_batches, B, W, segs, n_segs, count_all);
+}
+__global__ __launch_bounds__(256) void compute_columns_div_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
+                                                                  uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
+  compute_columns_body<true>(jobs, cols, n_cols, n_rows, n_batches, B, W, segs, n_segs, count_all);
 }

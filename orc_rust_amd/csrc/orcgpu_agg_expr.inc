@@ -4,7 +4,10 @@
 // a tree; the tree is typed (INT / DEC / FLOAT), the Decimal scale rule applied -- the operand of lower scale of a + b is wrapped
 // into a multiplication by a power of ten --, a date part (year(d), ...) typed as an integer over an operand of days, subtrees of
 // literals alone folded with the evaluator's own checked arithmetic and calendar function, the nodes labelled with the operand
-// slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Every refusal of the expression aggregates is
+// slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Division (a / b, a // b, a % b; include/
+// orcgpu.h: DIVISION): a `/` anywhere makes an exact expression a Decimal one, its node's scale and the power of ten of its dividend
+// are decided with the scales; `//` and `%` take integers -- scale 0 -- and no doubles; where the right child of one of the three goes
+// first, ONE AX_SWAP stands in front of the op (there are no reversed forms).  Every refusal of the expression aggregates is
 // decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
 //
 // The row filter's expression leaf (ORCGPU_PRED_CMP_EXPR: lhs OP rhs) has its two sides compiled here too (compile_pair, called by
@@ -48,6 +51,7 @@ struct AggExprCol {
 static_assert(sizeof(AggExprOp) == 24, "agg_program.h: the record the kernels read");
 static_assert((int)AX_PART_YEAR == (int)ORCGPU_DATE_PART_YEAR && (int)AX_PART_DAY_OF_YEAR == (int)ORCGPU_DATE_PART_DAY_OF_YEAR && (int)AX_PART_N == (int)ORCGPU_DATE_PART_DAY_OF_YEAR + 1,
               "the parts of include/orcgpu.h are the interpreter's");
+static_assert(ORCGPU_AGG_EXPR_DIV == 17 && ORCGPU_AGG_EXPR_FLOOR_DIV == 18 && ORCGPU_AGG_EXPR_MOD == 19, "the division nodes of include/orcgpu.h");
 static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
 
 enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
@@ -71,6 +75,7 @@ struct AggExprCompiler {
     int scale = 0;          // DEC
     uint32_t k = 0;         // kScale
     uint32_t part = 0;      // DATE_PART: ORCGPU_DATE_PART_*
+    int want_scale = -1;    // DIV: the result scale the caller chose (the node's `i`), -1: the default rule
     bool in_date = false;   // a leaf that stands below a DATE_PART: its value is a number of days
     uint32_t label = 1;     // operand slots the subtree needs
   };
@@ -83,6 +88,8 @@ struct AggExprCompiler {
   uint32_t date_depth = 0;      // parse: the DATE_PART nodes above the node at hand
   uint32_t date_part_of = 0;    // ... and the part of the innermost one, for the messages
 
+  static bool is_division(uint32_t op) { return op == ORCGPU_AGG_EXPR_DIV || op == ORCGPU_AGG_EXPR_FLOOR_DIV || op == ORCGPU_AGG_EXPR_MOD; }
+  static const char* division_name(uint32_t op) { return op == ORCGPU_AGG_EXPR_DIV ? "/" : op == ORCGPU_AGG_EXPR_FLOOR_DIV ? "//" : "%"; }
   static const char* part_name(uint32_t part) {
     static const char* const n[] = {"year()", "quarter()", "month()", "day()", "day_of_week()", "day_of_year()"};
     return part < AX_PART_N ? n[part] : "?";
@@ -125,7 +132,12 @@ struct AggExprCompiler {
       } else {
         return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a literal of the expression of %s is not an INT64, FLOAT64 or DECIMAL128 value", op_name);
       }
-    } else if (s.op == ORCGPU_AGG_EXPR_ADD || s.op == ORCGPU_AGG_EXPR_SUB || s.op == ORCGPU_AGG_EXPR_MUL || s.op == ORCGPU_AGG_EXPR_NEG) {
+    } else if (s.op == ORCGPU_AGG_EXPR_ADD || s.op == ORCGPU_AGG_EXPR_SUB || s.op == ORCGPU_AGG_EXPR_MUL || s.op == ORCGPU_AGG_EXPR_NEG || is_division(s.op)) {
+      if (s.op == ORCGPU_AGG_EXPR_DIV) {
+        if (s.i < -1 || s.i > 38)
+          return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a division node of the expression of %s names no result scale (i: 0 .. 38, or -1 for the default rule)", op_name);
+        t[me].want_scale = (int)s.i;
+      }
       int a = -1, b = -1;
       if (const int rc = parse(a)) return rc;
       if (s.op != ORCGPU_AGG_EXPR_NEG)
@@ -164,8 +176,12 @@ struct AggExprCompiler {
     const char *float_col = nullptr, *exact_col = nullptr;
     bool f64_lit = false, dec_lit = false, dec_col = false;
     const char* date_fn = nullptr;  // the first date part of the expression
+    const char* int_div = nullptr;  // the first // or % of the expression
+    bool has_div = false;           // a / anywhere: an exact expression is a Decimal one
     for (const Node& n : t) {
       if (n.op == ORCGPU_AGG_EXPR_DATE_PART && !date_fn) date_fn = part_name(n.part);
+      if ((n.op == ORCGPU_AGG_EXPR_FLOOR_DIV || n.op == ORCGPU_AGG_EXPR_MOD) && !int_div) int_div = division_name(n.op);
+      has_div |= n.op == ORCGPU_AGG_EXPR_DIV;
       if (n.op == ORCGPU_AGG_EXPR_LITERAL) {
         // the operand of a date part is a number of days: an exact integer
         if (n.in_date && n.value_type != ORCGPU_PV_INT64)
@@ -202,10 +218,12 @@ struct AggExprCompiler {
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside the integer or Decimal column '%s'", op_name, exact_col);
     if (dec_lit && float_col)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s'", op_name, float_col);
-    cls = float_col || (!exact_col && f64_lit) ? XCLASS_FLOAT : (dec_col || dec_lit) ? XCLASS_DEC : XCLASS_INT;
+    cls = float_col || (!exact_col && f64_lit) ? XCLASS_FLOAT : (dec_col || dec_lit || has_div) ? XCLASS_DEC : XCLASS_INT;
     // (reached with a date part of literals alone: one over a column has met the mixing rule above)
     if (cls == XCLASS_FLOAT && date_fn)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the Float / Double expression of %s holds %s, an integer", op_name, date_fn);
+    if (cls == XCLASS_FLOAT && int_div)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the Float / Double expression of %s over column '%s' holds %s, which takes integers", op_name, float_col ? float_col : "", int_div);
     if (cls == XCLASS_FLOAT)
       for (Node& n : t)
         if (n.op == ORCGPU_AGG_EXPR_LITERAL && n.value_type == ORCGPU_PV_INT64) {
@@ -254,7 +272,27 @@ struct AggExprCompiler {
       if (op == ORCGPU_AGG_EXPR_MUL) {
         t[n].scale = t[a].scale + t[b].scale;
       } else if (op == ORCGPU_AGG_EXPR_DATE_PART) {
-        t[n].scale = 0;  // (an integer, over an operand of integers: scale 0 below it too)
+        // an integer, over an operand of integers: scale 0 below it too -- but for a division that left another scale there
+        if (t[a].scale != 0)
+          return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s over column '%s' takes days, an integer: its operand is a quotient of a non-zero scale", part_name(t[n].part), op_name, first_column);
+        t[n].scale = 0;
+      } else if (op == ORCGPU_AGG_EXPR_DIV) {
+        // Q = round(A * 10^k / B) at scale s: the caller's, or min(38, max(6, sa + 4))
+        const int sa = t[a].scale, sb = t[b].scale;
+        const int s = t[n].want_scale >= 0 ? t[n].want_scale : sa + 4 > 38 ? 38 : sa + 4 < 6 ? 6 : sa + 4;
+        const int k = s - sa + sb;
+        if (k < 0 || k > 38) {
+          snprintf(err, err_len, "aggregate: a division in the expression of %s over column '%s': dividend scale %d, divisor scale %d, result scale %d need the dividend times 10^%d, "
+                   "outside 10^0 .. 10^38: not supported", op_name, first_column, sa, sb, s, k);
+          return ORCGPU_UNSUPPORTED;
+        }
+        t[n].scale = s;
+        t[n].k = (uint32_t)k;
+        t[n].iv = agg_pow10((uint32_t)k);
+      } else if (op == ORCGPU_AGG_EXPR_FLOOR_DIV || op == ORCGPU_AGG_EXPR_MOD) {
+        if (t[a].scale != 0 || t[b].scale != 0)
+          return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s over column '%s' takes integers: an operand has a non-zero scale", division_name(op), op_name, first_column);
+        t[n].scale = 0;
       } else if (op == ORCGPU_AGG_EXPR_NEG) {
         t[n].scale = t[a].scale;
       } else {
@@ -290,12 +328,15 @@ struct AggExprCompiler {
       if (cls == XCLASS_FLOAT) {
         lit.value_type = ORCGPU_PV_FLOAT64;
         const double x = t[a].fv, y = b >= 0 ? t[b].fv : 0.0;
-        lit.fv = op == ORCGPU_AGG_EXPR_ADD ? agg_f64_add(x, y) : op == ORCGPU_AGG_EXPR_SUB ? agg_f64_add(x, -y) : op == ORCGPU_AGG_EXPR_MUL ? agg_f64_mul(x, y) : -x;
+        lit.fv = op == ORCGPU_AGG_EXPR_ADD ? agg_f64_add(x, y) : op == ORCGPU_AGG_EXPR_SUB ? agg_f64_add(x, -y) : op == ORCGPU_AGG_EXPR_MUL ? agg_f64_mul(x, y)
+               : op == ORCGPU_AGG_EXPR_DIV ? agg_f64_div(x, y) : -x;
       } else {
         lit.value_type = ORCGPU_PV_INT64;
         const agg_i128 x = t[a].iv, y = b >= 0 ? t[b].iv : 0;
         ok = op == ORCGPU_AGG_EXPR_ADD ? agg_add_checked(x, y, &lit.iv) : op == ORCGPU_AGG_EXPR_SUB ? agg_sub_checked(x, y, &lit.iv)
-           : op == ORCGPU_AGG_EXPR_MUL ? agg_mul_checked(x, y, &lit.iv) : agg_neg_checked(x, &lit.iv);
+           : op == ORCGPU_AGG_EXPR_MUL ? agg_mul_checked(x, y, &lit.iv) : op == ORCGPU_AGG_EXPR_DIV ? agg_div_scaled_checked(x, t[n].iv, y, &lit.iv)
+           : op == ORCGPU_AGG_EXPR_FLOOR_DIV ? agg_div_checked(x, y, AGG_DIV_FLOOR, &lit.iv) : op == ORCGPU_AGG_EXPR_MOD ? agg_div_checked(x, y, AGG_DIV_MOD, &lit.iv)
+           : agg_neg_checked(x, &lit.iv);
       }
       if (ok) {
         t[n] = lit;
@@ -339,7 +380,21 @@ struct AggExprCompiler {
       const bool right_first = t[x.b].label > t[x.a].label;
       emit(right_first ? x.b : x.a, ops);
       emit(right_first ? x.a : x.b, ops);
-      o.op = x.op == ORCGPU_AGG_EXPR_ADD ? AX_ADD : x.op == ORCGPU_AGG_EXPR_MUL ? AX_MUL : right_first ? AX_RSUB : AX_SUB;
+      if (is_division(x.op)) {
+        if (right_first) {  // a back below b
+          AggExprOp w{};
+          w.op = AX_SWAP;
+          ops.push_back(w);
+        }
+        o.op = x.op == ORCGPU_AGG_EXPR_DIV ? AX_DIV : x.op == ORCGPU_AGG_EXPR_FLOOR_DIV ? AX_FLOOR_DIV : AX_MOD;
+        if (x.op == ORCGPU_AGG_EXPR_DIV && cls != XCLASS_FLOAT) {
+          o.col = x.k;
+          o.lo = (unsigned long long)x.iv;
+          o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
+        }
+      } else {
+        o.op = x.op == ORCGPU_AGG_EXPR_ADD ? AX_ADD : x.op == ORCGPU_AGG_EXPR_MUL ? AX_MUL : right_first ? AX_RSUB : AX_SUB;
+      }
     }
     ops.push_back(o);
   }
@@ -403,7 +458,8 @@ struct AggExprCompiler {
     for (size_t k = first_op; k < ops.size(); k++) {
       const uint32_t o = ops[k].op;
       if (o >= AX_PUSH_INT && o <= AX_PUSH_LIT) depth++;
-      else if (o >= AX_ADD && o <= AX_MUL) depth--;  // (AX_NEG, AX_SCALE10, AX_DATE_PART: unary, the depth stays)
+      else if ((o >= AX_ADD && o <= AX_MUL) || (o >= AX_DIV && o <= AX_MOD)) depth--;  // (AX_NEG, AX_SCALE10, AX_DATE_PART: unary, the depth stays)
+      else if (o == AX_SWAP && depth < 2) most = kAggExprSlots + 1;                     // (... and AX_SWAP changes two operands that must be there)
       most = depth > most ? depth : most;
     }
     if (most > kAggExprSlots || depth != 1) {

@@ -27,7 +27,9 @@ static_assert(ORCGPU_PRED_IN == 17 && ORCGPU_PRED_LITERAL == 18 && ORCGPU_IN_MAX
 static_assert(ORCGPU_PRED_CMP_EXPR == 19 && ORCGPU_PRED_EXPR_COLUMN == 20 && ORCGPU_PRED_EXPR_NEG == 25 &&
                   ORCGPU_PRED_EXPR_LITERAL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_LITERAL && ORCGPU_PRED_EXPR_ADD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_ADD &&
                   ORCGPU_PRED_EXPR_SUB - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_SUB && ORCGPU_PRED_EXPR_MUL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MUL &&
-                  ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG && ORCGPU_PRED_EXPR_DATE_PART - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DATE_PART,
+                  ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG && ORCGPU_PRED_EXPR_DATE_PART - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DATE_PART &&
+                  ORCGPU_PRED_EXPR_DIV - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DIV && ORCGPU_PRED_EXPR_FLOOR_DIV - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_FLOOR_DIV &&
+                  ORCGPU_PRED_EXPR_MOD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MOD,
               "the expression leaf of include/orcgpu.h: its nodes are the expression aggregates', 20 further on");
 static_assert((int)FXC_INT == (int)XCLASS_INT && (int)FXC_DEC == (int)XCLASS_DEC && (int)FXC_FLOAT == (int)XCLASS_FLOAT && sizeof(AggExprOp) == kExprOpBytes, "filter_program.h: an expression leaf's blob");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
@@ -288,7 +290,7 @@ struct FilterCompiler {
         return in_set(n, col);
       }
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: case ORCGPU_PRED_EXPR_NEG:
-      case ORCGPU_PRED_EXPR_DATE_PART:
+      case ORCGPU_PRED_EXPR_DATE_PART: case ORCGPU_PRED_EXPR_DIV: case ORCGPU_PRED_EXPR_FLOOR_DIV: case ORCGPU_PRED_EXPR_MOD:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
@@ -304,6 +306,7 @@ struct FilterCompiler {
     switch (n.op) {
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: kids = 0; break;
       case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: kids = 2; break;
+      case ORCGPU_PRED_EXPR_DIV: case ORCGPU_PRED_EXPR_FLOOR_DIV: case ORCGPU_PRED_EXPR_MOD: kids = 2; break;  // (a division's scale travels in `i`, below)
       case ORCGPU_PRED_EXPR_NEG: case ORCGPU_PRED_EXPR_DATE_PART: kids = 1; break;  // (the part travels in `i`, below)
       default: return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds expression nodes only%s (node op %lld)", "", n.op);
     }
@@ -651,6 +654,22 @@ inline void filter_expr_reads(const FilterPlan& plan, const FilterInsn& in, std:
     else if (op.op == AX_PUSH_DEC) out.push_back({op.col, FKIND_DEC128});
     else if (op.op == AX_PUSH_F64) out.push_back({op.col, FKIND_FLOAT});
   }
+}
+
+// Does an expression leaf of the plan hold a division?  (The call then launches filter_expr_div_kernel in place of filter_expr_kernel.)
+inline bool filter_plan_holds_division(const FilterPlan& plan) {
+  for (const uint32_t leaf : plan.expr_leaves) {
+    if (leaf >= plan.prog.size()) continue;
+    const FilterInsn& in = plan.prog[leaf];
+    FilterExprBlob b;
+    if (in.op != FOP_CMP_EXPR || in.lit_off > plan.lits.size() || in.lit_len > plan.lits.size() - in.lit_off || !filter_expr_blob(plan.lits.data() + in.lit_off, in.lit_len, &b)) continue;
+    for (uint32_t k = 0; k < b.n_lhs + b.n_rhs; k++) {
+      AggExprOp op;
+      memcpy(&op, plan.lits.data() + in.lit_off + kExprHeaderBytes + (size_t)k * sizeof(AggExprOp), sizeof(op));
+      if (agg_ops_hold_division(&op, 1)) return true;
+    }
+  }
+  return false;
 }
 
 // `from`, a plan compiled on its own against the same columns, behind `into`: its instructions behind into's, its literals behind

@@ -578,7 +578,8 @@ struct PredEval {
     if (at >= nodes.size()) return 0;
     const PredNode& n = nodes[at];
     const uint32_t kids = n.op == ORCGPU_PRED_EXPR_COLUMN || n.op == ORCGPU_PRED_EXPR_LITERAL ? 0 : n.op == ORCGPU_PRED_EXPR_NEG || n.op == ORCGPU_PRED_EXPR_DATE_PART ? 1
-                        : n.op == ORCGPU_PRED_EXPR_ADD || n.op == ORCGPU_PRED_EXPR_SUB || n.op == ORCGPU_PRED_EXPR_MUL ? 2 : ~0u;
+                        : n.op == ORCGPU_PRED_EXPR_ADD || n.op == ORCGPU_PRED_EXPR_SUB || n.op == ORCGPU_PRED_EXPR_MUL ? 2
+                        : n.op == ORCGPU_PRED_EXPR_DIV || n.op == ORCGPU_PRED_EXPR_FLOOR_DIV || n.op == ORCGPU_PRED_EXPR_MOD ? 2 : ~0u;  // (never pruned through: a leaf that holds one has no bare column beside one literal)
     if (kids == ~0u || n.n_children != kids) return 0;
     size_t next = at + 1;
     for (uint32_t k = 0; k < kids; k++)

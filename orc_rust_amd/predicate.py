@@ -12,6 +12,7 @@ IN_SET = 26  # x IN SET s: a leaf whose i names a sealed key_set.KeySet
 CMP_EXPR = 19  # lhs OP rhs over two arithmetic expressions; its subtrees are made of the nodes below
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(20, 26)  # ORCGPU_PRED_EXPR_*: aggregate.EXPR_* + 20
 EXPR_DATE_PART = 36  # ... aggregate.EXPR_DATE_PART + 20: one child, the part in `i`
+EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 37, 38, 39  # ... aggregate.EXPR_DIV .. EXPR_MOD + 20: two children; DIV: the result scale, or -1, in `i`
 _CMP_OPS = {"=": EQ, "!=": NE, "<": LT, "<=": LE, ">": GT, ">=": GE}
 _CMP_SIGNS = {v: k for k, v in _CMP_OPS.items()}
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
@@ -276,6 +277,8 @@ class Predicate:
                     n.i = e.value
             elif e.op + EXPR_COLUMN == EXPR_DATE_PART:
                 n.i = e.part
+            elif e.op + EXPR_COLUMN == EXPR_DIV:
+                n.i = -1 if e.scale is None else e.scale
             out.append(n)
             for c in e.children:
                 walk_expr(c)
