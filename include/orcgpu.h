@@ -450,6 +450,12 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_EXPR_DIV = 37, ORCGPU_PRED_EXPR_FLOOR_DIV = 38, ORCGPU_PRED_EXPR_MOD = 39
                                        /* a / b, a // b, a % b: expression nodes like 20 .. 25 (ORCGPU_AGG_EXPR_DIV .. _MOD + 20), exactly
                                           two children; DIV: i = the result scale 0 .. 38, or -1 (the expression aggregates' DIVISION).
+                                          A leaf that holds one keeps every row group when pruning */,
+       /* (40: an unknown op) */
+       ORCGPU_PRED_EXPR_IF = 41, ORCGPU_PRED_EXPR_COALESCE = 42, ORCGPU_PRED_EXPR_ABS = 43, ORCGPU_PRED_EXPR_NULL = 44,
+       ORCGPU_PRED_EXPR_CMP = 45, ORCGPU_PRED_EXPR_IS_NULL = 46, ORCGPU_PRED_EXPR_AND = 47, ORCGPU_PRED_EXPR_OR = 48,
+       ORCGPU_PRED_EXPR_NOT = 49      /* the conditional nodes of an expression (ORCGPU_AGG_EXPR_IF .. _NOT + 20; the expression
+                                          aggregates' CONDITIONALS): 3, 2, 1, 0, 2, 1, 2, 2, 1 children; CMP: i = ORCGPU_PRED_EQ .. _GE.
                                           A leaf that holds one keeps every row group when pruning */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
@@ -756,6 +762,7 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *     rules of that value type in predicates), ORCGPU_AGG_EXPR_ADD / _SUB / _MUL (exactly two children) and ORCGPU_AGG_EXPR_NEG (one).
  *     ORCGPU_AGG_EXPR_DATE_PART (one child, the part in `i`) is the one function: DATE PARTS below.
  *     ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD (exactly two children; DIV: a result scale in `i`): DIVISION below.
+ *     ORCGPU_AGG_EXPR_IF / _COALESCE / _ABS / _NULL and the condition nodes _CMP / _IS_NULL / _AND / _OR / _NOT: CONDITIONALS below.
  *   - CLASSES, decided bottom-up when the list is compiled:
  *       INT    Byte .. Long columns and INT64 literals.  Every intermediate value is a signed 128-bit integer.  ORCGPU_AGG_KIND_I128.
  *       DEC    at least one Decimal column or DECIMAL128 literal; Byte .. Long columns and INT64 literals beside them count as
@@ -826,6 +833,46 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *       LIMITS   each node counts against ORCGPU_AGG_EXPR_MAX_NODES and needs operand slots like + - *.  The operand of a date part
  *                is an integer: a quotient of a non-zero scale below one is ORCGPU_MISMATCHED_SCHEMA.
  *     Row-group pruning does not look through a division: a filter leaf that holds one keeps every row group.
+ *   - CONDITIONALS: nine nodes, in every stage that speaks this language (in the row filter's ORCGPU_PRED_CMP_EXPR they are
+ *     ORCGPU_PRED_EXPR_IF .. _NOT, 20 further on).  Four produce a NUMBER:
+ *       IF(cond, a, b)  three children.  a where cond is TRUE, b where it is FALSE or UNKNOWN (SQL's CASE WHEN cond THEN a ELSE b END;
+ *                nest it for more branches).
+ *       COALESCE(a, b)  two children.  a unless a is NULL, then b.
+ *       ABS(a)   one child.  -2^127 overflows; on doubles the sign bit is cleared (abs(-0.0) = 0.0, a NaN keeps its payload).
+ *       NULL     no children.  It takes the class and scale of the sibling it meets as a value operand of IF or COALESCE; anywhere
+ *                else, and beside another NULL, it is ORCGPU_INVALID_ARGUMENT.
+ *     and five produce a CONDITION -- TRUE, FALSE or UNKNOWN --, legal only as the first child of IF or below AND / OR / NOT:
+ *       CMP(a, b)  `i` holds ORCGPU_PRED_EQ .. _GE (anything else: ORCGPU_INVALID_ARGUMENT).  UNKNOWN where either side is NULL.
+ *                Integers and Decimals compare exactly, the side of the smaller scale first brought to the larger as + brings it
+ *                (times a power of ten, which can overflow that side).  Doubles compare by IEEE's rules: with a NaN every
+ *                comparison is FALSE but !=.
+ *       IS_NULL(a)  TRUE or FALSE, never UNKNOWN.
+ *       AND, OR, NOT  Kleene's.
+ *     A condition where a number is wanted, or a number where a condition is wanted -- the root of an expression is a number --, is
+ *     ORCGPU_INVALID_ARGUMENT, the message naming the node.
+ *       CLASSES  the two value operands of IF and of COALESCE, and the two sides of CMP, are of one class: an integer beside a
+ *                Decimal is promoted as + promotes it, a Float / Double beside an integer or Decimal is refused as + refuses it
+ *                (ORCGPU_MISMATCHED_SCHEMA).  The result has the larger of the two scales; the other operand is taken times the power
+ *                of ten, which can overflow THAT operand only.
+ *       NULL AND OVERFLOW ARE PER OPERAND, not per row.  Every operand has a value, "is NULL" and "overflowed".  Arithmetic (+ - * /
+ *                // %, unary -, ABS, a date part, the scale alignment) gives NULL if an operand is NULL -- NULL comes first --,
+ *                otherwise overflow if an operand overflowed or the operation does.  CMP the same, with UNKNOWN for NULL.  IS_NULL of
+ *                an operand that overflowed overflows.  IF takes the three fields of the branch it chooses: the other branch may be
+ *                NULL, divide by zero or leave 128 bits, and nothing is seen of it; a condition that overflowed overflows the IF.
+ *                COALESCE takes a's fields unless a is NULL, then b's: it overflows if a overflowed.  AND and OR are decided by value:
+ *                a FALSE operand makes AND FALSE and a TRUE operand makes OR TRUE whatever the other operand is or did, on either
+ *                side; otherwise overflow comes before UNKNOWN.  So IF(b != 0, a / b, 0) and IF(b != 0 AND a / b > 2, ..) count no
+ *                overflow where b = 0.  NOT keeps UNKNOWN and overflow.  Both branches are evaluated on every row; the fields make
+ *                that invisible.
+ *       THE ROOT decides the row as it always did: overflow is AGG_OVERFLOW in an aggregate, UNKNOWN and counted in the row filter,
+ *                NULL and counted in a computed column; NULL is a row that contributes nothing, UNKNOWN, and a NULL that is not
+ *                counted.
+ *       LIMITS   every node counts against ORCGPU_AGG_EXPR_MAX_NODES.  Operand slots follow the Sethi-Ullman labelling extended to
+ *                the ternary node with its condition first: with the labels lc, la, lb of its children, IF needs
+ *                max(lc, 1 + (la == lb ? la + 1 : max(la, lb))); more than ORCGPU_AGG_EXPR_MAX_DEPTH is ORCGPU_UNSUPPORTED.
+ *                An ABS of a literal is folded; no other conditional node is.  An expression without any column stays
+ *                refused where it was.
+ *     Row-group pruning does not look through a conditional: a filter leaf that holds one keeps every row group.
  *   - OPS: ORCGPU_AGG_OP_SUM_EXPR the sum of the expression over the kept rows where it is not NULL, NULL over no such row;
  *     ORCGPU_AGG_OP_AVG the average of a plain column (the columns SUM takes); ORCGPU_AGG_OP_AVG_EXPR the average of an expression.
  *     A *_EXPR op without an expression -- through an entry point without `exprs` too -- is ORCGPU_INVALID_ARGUMENT.
@@ -846,7 +893,13 @@ enum { ORCGPU_AGG_EXPR_COLUMN = 0, ORCGPU_AGG_EXPR_LITERAL = 1, ORCGPU_AGG_EXPR_
        /* (6 .. 15: unknown nodes) */
        ORCGPU_AGG_EXPR_DATE_PART = 16 /* one child; i = ORCGPU_DATE_PART_*: see DATE PARTS above */,
        ORCGPU_AGG_EXPR_DIV = 17 /* a / b; i = the result scale 0 .. 38 of an exact division, -1: the default rule */,
-       ORCGPU_AGG_EXPR_FLOOR_DIV = 18 /* a // b */, ORCGPU_AGG_EXPR_MOD = 19 /* a % b: two children each; see DIVISION above */ };
+       ORCGPU_AGG_EXPR_FLOOR_DIV = 18 /* a // b */, ORCGPU_AGG_EXPR_MOD = 19 /* a % b: two children each; see DIVISION above */,
+       /* (20: an unknown node).  CONDITIONALS above -- value nodes: */
+       ORCGPU_AGG_EXPR_IF = 21 /* three children: a condition, then, otherwise */, ORCGPU_AGG_EXPR_COALESCE = 22 /* two children */,
+       ORCGPU_AGG_EXPR_ABS = 23 /* one child */, ORCGPU_AGG_EXPR_NULL = 24 /* no children: the NULL of its sibling's class and scale */,
+       /* ... and condition nodes, legal only as the first child of IF or below AND / OR / NOT: */
+       ORCGPU_AGG_EXPR_CMP = 25 /* two value children; i = ORCGPU_PRED_EQ .. _GE (0 .. 5) */, ORCGPU_AGG_EXPR_IS_NULL = 26 /* one value child */,
+       ORCGPU_AGG_EXPR_AND = 27, ORCGPU_AGG_EXPR_OR = 28 /* two condition children */, ORCGPU_AGG_EXPR_NOT = 29 /* one condition child */ };
 enum { ORCGPU_DATE_PART_YEAR = 0, ORCGPU_DATE_PART_QUARTER = 1, ORCGPU_DATE_PART_MONTH = 2, ORCGPU_DATE_PART_DAY = 3,
        ORCGPU_DATE_PART_DAY_OF_WEEK = 4, ORCGPU_DATE_PART_DAY_OF_YEAR = 5 };
 typedef struct {
@@ -1058,7 +1111,8 @@ int orcgpu_reader_next_batch(orcgpu_reader* r, struct ArrowArray* out_array, str
  * A reader may be given 1 .. ORCGPU_COMPUTED_MAX computed columns, each {name, expression}, in order.  The expression is an
  * orcgpu_agg_expr over the nodes of the expression aggregates and of the row filter's comparison: column, literal, + - *, unary -,
  * the date part (ORCGPU_AGG_EXPR_DATE_PART: year(d), month(d), ...; an operand outside int32 is NULL and counted, below) and the
- * divisions (ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD; a zero divisor is NULL and counted; int / int is a Decimal128(38, 6) column).
+ * divisions (ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD; a zero divisor is NULL and counted; int / int is a Decimal128(38, 6) column),
+ * and the conditionals (ORCGPU_AGG_EXPR_IF .. _NOT: CASE WHEN, COALESCE, ABS; a NULL result is NULL and not counted).
  *   - OPERANDS are projected flat root columns of the file.  Another computed column as an operand is ORCGPU_UNSUPPORTED.  At most
  *     ORCGPU_AGG_EXPR_MAX_NODES nodes and ORCGPU_AGG_EXPR_MAX_DEPTH operand slots.
  *   - TYPING is the expression compiler's, in the mode one side of ORCGPU_PRED_CMP_EXPR takes: a Date takes part as int64 days; the

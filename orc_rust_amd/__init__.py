@@ -8,7 +8,8 @@ from .arrow_writer import ArrowWriter, ArrowWriterBuilder  # noqa: F401
 from .device_batch import DeviceColumn, DeviceRecordBatch  # noqa: F401
 from .key_set import KeySet  # noqa: F401
 from .key_map import KeyMap  # noqa: F401
-from .aggregate import day, day_of_week, day_of_year, divide, extract, month, quarter, year  # noqa: F401
+from .aggregate import abs_, case, coalesce, day, day_of_week, day_of_year, divide, extract, month, nullif, quarter, when, year  # noqa: F401
 
 __all__ = ["capi", "ArrowReader", "ArrowReaderBuilder", "ArrowWriter", "ArrowWriterBuilder", "DeviceColumn", "DeviceRecordBatch", "KeySet", "KeyMap",
-           "year", "quarter", "month", "day", "day_of_week", "day_of_year", "extract", "divide"]
+           "year", "quarter", "month", "day", "day_of_week", "day_of_year", "extract", "divide",
+           "when", "case", "coalesce", "nullif", "abs_"]

@@ -9,7 +9,10 @@ An aggregate's argument may be an arithmetic expression over columns and literal
 (orcgpu_result_aggregate_exprs): `col(name)` and `lit(v)` build an Expr, `+ - *` and unary `-` combine them, plain Python numbers
 on either side are wrapped; `/` (and `divide(a, b, scale=n)` to choose a Decimal quotient's scale), `//` and `%` divide -- exactly,
 a zero divisor an overflow of the row, `//` and `%` on integers with Python's floor rule; `year(e)`, `quarter(e)`, `month(e)`, `day(e)`, `day_of_week(e)`, `day_of_year(e)` and `extract(part, e)`
-take a calendar field of a Date (or of any integer expression of days since 1970-01-01).  TPC-H Q1 whole:
+take a calendar field of a Date (or of any integer expression of days since 1970-01-01); `when(cond, a, b)`, `case([(c1, a), ...],
+otherwise)`, `coalesce(a, b, ...)`, `nullif(a, b)` and `abs(e)` choose per row -- SQL's CASE WHEN, COALESCE, NULLIF and ABS, with NULL
+and overflow tracked per operand, so that the branch not taken is never seen: `when(col("b").ne(0), col("a") / col("b"), 0)`.
+TPC-H Q1 whole:
 
     from orc_rust_amd.aggregate import Agg, col
     price, disc, tax = col("l_extendedprice"), col("l_discount"), col("l_tax")
@@ -21,12 +24,16 @@ Pure plumbing: nothing is computed here, and every argument is checked before an
 import ctypes as C
 import decimal
 
-from .predicate import Predicate, PredicateNode
+from .predicate import _CMP_SIGNS, Predicate, PredicateNode
 
 COUNT_ROWS, COUNT, SUM, MIN, MAX, SUM_PRODUCT, SUM_EXPR, AVG, AVG_EXPR = range(9)  # ORCGPU_AGG_OP_*
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(6)  # ORCGPU_AGG_EXPR_*
 EXPR_DATE_PART = 16  # ORCGPU_AGG_EXPR_DATE_PART (6 .. 15 are unknown nodes): one child, the part in the node's `i`
 EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 17, 18, 19  # ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD: two children; DIV: the result scale, or -1, in `i`
+# ORCGPU_AGG_EXPR_IF .. _NOT (20 is an unknown node): the conditionals.  IF (condition, then, otherwise), COALESCE (2), ABS (1) and NULL
+# (0 children) are numbers; CMP (2; the comparison EQ .. GE in `i`), IS_NULL (1), AND, OR (2) and NOT (1) are conditions
+EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_NULL, EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT = range(21, 30)
+_CONDITIONS = (EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT)
 DATE_PARTS = ("year", "quarter", "month", "day", "day_of_week", "day_of_year")  # ORCGPU_DATE_PART_*, by number
 PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
 EXPR_MAX_NODES, EXPR_MAX_DEPTH = 32, 4  # ORCGPU_AGG_EXPR_MAX_*
@@ -77,14 +84,18 @@ def _column(what, name):
 class Expr:
     """An arithmetic expression over columns and literals: built by col() and lit(), combined with + - * / // % and unary -."""
 
-    def __init__(self, op, children=(), column=None, value_type=None, value=None, part=None, scale=None):
+    def __init__(self, op, children=(), column=None, value_type=None, value=None, part=None, scale=None, cmp=None):
         self.op, self.children, self.column, self.value_type, self.value = op, tuple(children), column, value_type, value
         self.part = part  # EXPR_DATE_PART: the index into DATE_PARTS
         self.scale = scale  # EXPR_DIV: the scale of an exact quotient the caller chose (divide), None: the default rule
+        self.cmp = cmp  # EXPR_CMP: predicate.EQ .. GE
 
     @staticmethod
     def _wrap(x):
         return x if isinstance(x, Expr) else lit(x)
+
+    def __abs__(self):
+        return abs_(self)
 
     def __add__(self, other):
         return Expr(EXPR_ADD, (self, Expr._wrap(other)))
@@ -158,6 +169,17 @@ class Expr:
             return "%s(%r)" % (DATE_PARTS[self.part], self.children[0])
         if self.op == EXPR_DIV and self.scale is not None:
             return "divide(%r, %r, scale=%d)" % (self.children[0], self.children[1], self.scale)
+        if self.op == EXPR_NULL:
+            return "None"
+        if self.op in (EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_IS_NULL):
+            name = {EXPR_IF: "when", EXPR_COALESCE: "coalesce", EXPR_ABS: "abs", EXPR_IS_NULL: "is_null"}[self.op]
+            return "%s(%s)" % (name, ", ".join(repr(c) for c in self.children))
+        if self.op == EXPR_NOT:
+            return "(~%r)" % (self.children[0],)
+        if self.op == EXPR_CMP:
+            return "(%r %s %r)" % (self.children[0], _CMP_SIGNS[self.cmp], self.children[1])
+        if self.op in (EXPR_AND, EXPR_OR):
+            return "(%r %s %r)" % (self.children[0], "&" if self.op == EXPR_AND else "|", self.children[1])
         signs = {EXPR_ADD: "+", EXPR_SUB: "-", EXPR_MUL: "*", EXPR_DIV: "/", EXPR_FLOOR_DIV: "//", EXPR_MOD: "%"}
         return "(%r %s %r)" % (self.children[0], signs[self.op], self.children[1])
 
@@ -188,6 +210,8 @@ class Expr:
                 n.i = e.part
             elif e.op == EXPR_DIV:
                 n.i = -1 if e.scale is None else e.scale
+            elif e.op == EXPR_CMP:
+                n.i = e.cmp
             out.append(n)
             for c in e.children:
                 walk(c)
@@ -252,6 +276,105 @@ def divide(a, b, scale=None):
             x = lit(x)
         ops.append(x)
     return Expr(EXPR_DIV, ops, scale=scale)
+
+
+def _operand(what, x, null_ok=False):
+    """An operand of when / case / coalesce / nullif / abs_: an Expr that is a number, a column name, a number, or -- null_ok -- None."""
+    if x is None and null_ok:
+        return Expr(EXPR_NULL)
+    if isinstance(x, str):
+        return col(x)
+    if isinstance(x, Expr):
+        if x.op in _CONDITIONS:
+            raise TypeError("%s: %r is a condition, not a number" % (what, x))
+        return x
+    if isinstance(x, bool) or not isinstance(x, (int, float, decimal.Decimal)):
+        raise TypeError("%s: an Expr, a column name%s or a number, not %s" % (what, ", None" if null_ok else "", type(x).__name__))
+    return lit(x)
+
+
+def _condition(what, p):
+    """A Predicate as the condition nodes of an expression (ORCGPU_AGG_EXPR_CMP / _IS_NULL / _AND / _OR / _NOT).  What has no such
+    node -- LIKE, IN, in_set, a comparison with a string, Boolean, Timestamp or NULL value -- is a TypeError naming the leaf."""
+    from . import predicate as P
+    if not isinstance(p, Predicate):
+        raise TypeError("%s: the condition is a Predicate (col('a') < 5, Predicate.is_null('a'), ...), not %s" % (what, type(p).__name__))
+    if p.op == P.CMP_EXPR:
+        return Expr(EXPR_CMP, p.exprs, cmp=p.cmp)
+    if p.op in (P.IS_NULL, P.IS_NOT_NULL):
+        e = Expr(EXPR_IS_NULL, (col(p.column),))
+        return e if p.op == P.IS_NULL else Expr(EXPR_NOT, (e,))
+    if p.op == P.NOT:
+        if len(p.children) != 1:
+            raise ValueError("%s: %r has not one operand" % (what, p))
+        return Expr(EXPR_NOT, (_condition(what, p.children[0]),))
+    if p.op in (P.AND, P.OR):
+        if not p.children:
+            raise ValueError("%s: %r has no operand" % (what, p))
+        e = _condition(what, p.children[0])
+        for c in p.children[1:]:
+            e = Expr(EXPR_AND if p.op == P.AND else EXPR_OR, (e, _condition(what, c)))
+        return e
+    v = p.value
+    if P.EQ <= p.op <= P.GE and isinstance(v, P.PredicateValue) and v.value is not None and not isinstance(v.value, bool):
+        x = None
+        if v.kind in (P.PV_INT8, P.PV_INT16, P.PV_INT32, P.PV_INT64):
+            x = lit(int(v.value))
+        elif v.kind in (P.PV_FLOAT32, P.PV_FLOAT64):
+            x = lit(float(v.value))
+        elif v.kind == P.PV_DECIMAL128:
+            x = Expr(EXPR_LITERAL, value_type=PV_DECIMAL128, value=tuple(v.value))
+        if x is not None:
+            return Expr(EXPR_CMP, (col(p.column), x), cmp=p.op)
+    raise TypeError("%s: the leaf %r cannot stand in an expression's condition -- only comparisons of numbers, is_null / is_not_null and "
+                    "and_ / or_ / not_ over them can; condition an aggregate on it with Agg.where" % (what, p))
+
+
+def when(cond, then, otherwise=None):
+    """CASE WHEN cond THEN then ELSE otherwise END (ORCGPU_AGG_EXPR_IF): `then` where cond is TRUE, `otherwise` where it is FALSE
+    or UNKNOWN.  cond: a Predicate -- what `col('a') < 5`, Expr.eq / ne and Predicate.compare return, Predicate.is_null /
+    is_not_null, a plain numeric Predicate.comparison, and and_ / or_ / not_ over these.  then / otherwise: an Expr, a column name,
+    a number, or None for NULL (not both).  The branch that is not taken may be NULL, divide by zero or overflow: nothing is seen
+    of it.  Nest for more branches, or use case()."""
+    c = _condition("when", cond)
+    if then is None and otherwise is None:
+        raise ValueError("when: both branches are None")
+    return Expr(EXPR_IF, (c, _operand("when", then, True), _operand("when", otherwise, True)))
+
+
+def case(branches, otherwise=None):
+    """CASE WHEN c1 THEN a WHEN c2 THEN b ... ELSE otherwise END: branches is a non-empty list of (condition, value) pairs, nested
+    into when() from the right."""
+    if not isinstance(branches, (list, tuple)) or not branches:
+        raise ValueError("case: a non-empty list of (condition, value) pairs")
+    for b in branches:
+        if not isinstance(b, (list, tuple)) or len(b) != 2:
+            raise TypeError("case: every branch is a (condition, value) pair, not %r" % (b,))
+    e = otherwise
+    for cond, value in reversed(branches):
+        e = when(cond, value, e)
+    return e
+
+
+def coalesce(a, b, *more):
+    """COALESCE(a, b, ...) (ORCGPU_AGG_EXPR_COALESCE): the first operand that is not NULL; nested to the right."""
+    xs = [_operand("coalesce", x) for x in (a, b) + more]
+    e = xs[-1]
+    for x in reversed(xs[:-1]):
+        e = Expr(EXPR_COALESCE, (x, e))
+    return e
+
+
+def nullif(a, b):
+    """NULLIF(a, b): NULL where a = b, else a -- `x / nullif(y, 0)`.  It is when(a.eq(b), None, a), with no node of its own: a's
+    nodes are counted twice against the 32 of an expression."""
+    a = _operand("nullif", a)
+    return when(a.eq(_operand("nullif", b)), None, a)
+
+
+def abs_(e):
+    """|e| (ORCGPU_AGG_EXPR_ABS), also abs(expr): -2^127 overflows the row; a double has its sign bit cleared."""
+    return Expr(EXPR_ABS, (_operand("abs_", e),))
 
 
 def extract(part, e):

@@ -268,9 +268,193 @@ struct AggSlots {
     s0 = s1;
     s1 = v;
   }
+  // the three top slots -> one (AX_IF)
+  AGG_HD void merge3(T v) {
+    s0 = v;
+    s1 = s3;
+  }
+};
+
+// What the interpreter with the conditionals (include/orcgpu.h: CONDITIONALS) knows of each slot beside its value: whether it is
+// NULL and whether it overflowed, as two masks -- bit k is slot k, bit 0 the top -- moved as AggSlots moves the values.  Two words,
+// not an array: no scratch.  A slot never has both bits: where an operand is NULL the result is NULL, overflow or not.
+struct AggSlotBits {
+  uint32_t nul, ovf;
+  AGG_HD bool n(uint32_t k) const { return (nul >> k) & 1; }
+  AGG_HD bool o(uint32_t k) const { return (ovf >> k) & 1; }
+  AGG_HD void push(bool n_, bool o_) {
+    nul = ((nul << 1) | (n_ ? 1u : 0u)) & 15u;
+    ovf = ((ovf << 1) | (o_ ? 1u : 0u)) & 15u;
+  }
+  AGG_HD void set(bool n_, bool o_) {
+    nul = (nul & ~1u) | (n_ ? 1u : 0u);
+    ovf = (ovf & ~1u) | (o_ ? 1u : 0u);
+  }
+  AGG_HD void merge(bool n_, bool o_) {
+    nul = ((nul >> 2) << 1) | (n_ ? 1u : 0u);
+    ovf = ((ovf >> 2) << 1) | (o_ ? 1u : 0u);
+  }
+  AGG_HD void merge3(bool n_, bool o_) {
+    nul = ((nul >> 3) << 1) | (n_ ? 1u : 0u);
+    ovf = ((ovf >> 3) << 1) | (o_ ? 1u : 0u);
+  }
+  AGG_HD void swap() {
+    nul = (nul & ~3u) | ((nul & 1u) << 1) | ((nul >> 1) & 1u);
+    ovf = (ovf & ~3u) | ((ovf & 1u) << 1) | ((ovf >> 1) & 1u);
+  }
 };
 
 enum { AGG_ROW_NULL = 0, AGG_ROW_VALUE = 1, AGG_ROW_OVERFLOW = 2 };
+
+// Kleene's AND (is_or = false) / OR of two conditions, each a value (non-zero: TRUE), a NULL bit (UNKNOWN) and an overflow bit.  The
+// operand that decides -- a known FALSE under AND, a known TRUE under OR -- decides whatever the other one is: that is what makes
+// `b != 0 AND a / b > 2` a guard.  Otherwise overflow comes before UNKNOWN.
+AGG_HD void agg_kleene(bool is_or, bool va, bool na, bool oa, bool vb, bool nb, bool ob, bool* v, bool* n, bool* o) {
+  const bool decided = (!na && !oa && va == is_or) || (!nb && !ob && vb == is_or);
+  *o = !decided && (oa || ob);
+  *n = !decided && !*o && (na || nb);
+  *v = decided ? is_or : !is_or;  // (neither decides and both are known: TRUE AND TRUE, FALSE OR FALSE)
+}
+// a `cmp` b from "a < b" and "a == b" (for doubles: IEEE's, both false with a NaN -- then only != holds)
+AGG_HD bool agg_cmp_of(uint32_t cmp, bool lt, bool eq, bool gt) {
+  return cmp == 0 ? eq : cmp == 1 ? !eq : cmp == 2 ? lt : cmp == 3 ? (lt || eq) : cmp == 4 ? gt : (gt || eq);
+}
+
+// A program WITH conditionals (agg_program.h: AX_CMP .. AX_PUSH_NULL) of the INT / DEC class on one row: no gates; every slot has
+// its NULL and overflow bits, arithmetic hands them on (NULL first, then overflow), AX_IF and AX_COALESCE take the chosen slot's, and
+// only the root's decide the row -- an untaken branch neither gates the row nor counts as an overflow.  Both branches are
+// evaluated; there is no jump.
+template <bool DIV, typename Row>
+AGG_HD int agg_expr_eval_i128_cond(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+  AggSlots<agg_i128> s = {0, 0, 0, 0};
+  AggSlotBits m = {0, 0};
+  // (the mark in front of a program with conditionals -- agg_program.h: kAggCondMark -- is for the other interpreters: skipped)
+  for (uint32_t k = agg_cond_marked(prog, n) ? 1 : 0; k < n; k++) {
+    const AggExprOp op = prog[k];
+    agg_i128 r = 0;
+    bool ok = true;
+    switch (op.op) {
+      case AX_GATE:
+        if (!row.valid(op.col)) return AGG_ROW_NULL;
+        break;
+      case AX_PUSH_INT:
+      case AX_PUSH_DEC: {
+        const bool v = !op.lo || row.valid(op.col);
+        if (v) r = op.op == AX_PUSH_INT ? row.load_int(op.col) : row.load_dec(op.col);
+        s.push(r);
+        m.push(!v, false);
+        break;
+      }
+      case AX_PUSH_LIT:
+        s.push(agg_i128_of(op.lo, op.hi));
+        m.push(false, false);
+        break;
+      case AX_PUSH_NULL:
+        s.push(0);
+        m.push(true, false);
+        break;
+      case AX_ADD:
+      case AX_SUB:
+      case AX_RSUB:
+      case AX_MUL:
+      case AX_DIV:
+      case AX_FLOOR_DIV:
+      case AX_MOD: {
+        if (op.op == AX_ADD) {
+          ok = agg_add_checked(s.s1, s.s0, &r);
+        } else if (op.op == AX_SUB) {
+          ok = agg_sub_checked(s.s1, s.s0, &r);
+        } else if (op.op == AX_RSUB) {
+          ok = agg_sub_checked(s.s0, s.s1, &r);
+        } else if (op.op == AX_MUL) {
+          ok = agg_mul_checked(s.s1, s.s0, &r);
+        } else if constexpr (DIV) {
+          agg_i128 a = s.s1;
+          if (op.op == AX_DIV && op.col != 0) ok = agg_mul_checked(a, agg_i128_of(op.lo, op.hi), &a);
+          ok &= agg_div_checked(a, s.s0, op.op - AX_DIV, &r);
+        } else {
+          ok = false;
+        }
+        const bool nul = m.n(0) || m.n(1);
+        const bool ovf = !nul && (m.o(0) || m.o(1) || !ok);
+        s.merge(nul || ovf ? (agg_i128)0 : r);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_NEG:
+      case AX_SCALE10:
+      case AX_DATE_PART:
+      case AX_ABS: {
+        if (op.op == AX_NEG) {
+          ok = agg_neg_checked(s.s0, &r);
+        } else if (op.op == AX_SCALE10) {
+          ok = agg_mul_checked(s.s0, agg_i128_of(op.lo, op.hi), &r);
+        } else if (op.op == AX_ABS) {
+          r = s.s0;
+          if (r < 0) ok = agg_neg_checked(s.s0, &r);
+        } else {
+          const long long d = (long long)s.s0;
+          ok = s.s0 == (agg_i128)(int32_t)d;
+          r = (agg_i128)agg_date_part((int32_t)d, op.col);
+        }
+        const bool nul = m.n(0);
+        const bool ovf = !nul && (m.o(0) || !ok);
+        s.s0 = nul || ovf ? (agg_i128)0 : r;
+        m.set(nul, ovf);
+        break;
+      }
+      case AX_CMP: {
+        const bool nul = m.n(0) || m.n(1);
+        const bool ovf = !nul && (m.o(0) || m.o(1));
+        const bool t = !nul && !ovf && agg_cmp_of(op.col, s.s1 < s.s0, s.s1 == s.s0, s.s1 > s.s0);
+        s.merge(t ? 1 : 0);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_IS_NULL:
+        s.s0 = m.n(0) ? 1 : 0;
+        m.set(false, m.o(0));
+        break;
+      case AX_AND:
+      case AX_OR: {
+        bool v, nul, ovf;
+        agg_kleene(op.op == AX_OR, s.s1 != 0, m.n(1), m.o(1), s.s0 != 0, m.n(0), m.o(0), &v, &nul, &ovf);
+        s.merge(v && !nul && !ovf ? 1 : 0);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_NOT:
+        s.s0 = !m.n(0) && !m.o(0) && s.s0 == 0 ? 1 : 0;
+        break;
+      case AX_IF: {
+        // the condition in slot 2; then below otherwise, or -- col = 1 -- the other way round
+        const bool take = !m.n(2) && !m.o(2) && s.s2 != 0;
+        const uint32_t at = take != (op.col != 0) ? 1u : 0u;
+        const bool co = m.o(2);  // (an overflowed condition: which branch is not known, and that is an overflow)
+        const bool nul = !co && m.n(at), ovf = co || m.o(at);
+        r = nul || ovf ? (agg_i128)0 : (at ? s.s1 : s.s0);
+        s.merge3(r);
+        m.merge3(nul, ovf);
+        break;
+      }
+      case AX_COALESCE: {
+        const bool b = m.n(1);  // a is NULL: b, with what b carries
+        r = b ? s.s0 : s.s1;
+        const bool nul = b ? m.n(0) : false, ovf = b ? m.o(0) : m.o(1);
+        s.merge(r);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_SWAP:
+        s.swap();
+        m.swap();
+        break;
+      default: break;
+    }
+  }
+  *out = s.s0;
+  return m.n(0) ? AGG_ROW_NULL : m.o(0) ? AGG_ROW_OVERFLOW : AGG_ROW_VALUE;
+}
 
 // A program of the INT / DEC class on one row.  Row: `bool valid(uint32_t col)`, `agg_i128 load_int(uint32_t col)` (an int64
 // column) and `agg_i128 load_dec(uint32_t col)`.  AGG_ROW_NULL: a gating column is NULL, the row contributes nothing;
@@ -279,8 +463,14 @@ enum { AGG_ROW_NULL = 0, AGG_ROW_VALUE = 1, AGG_ROW_OVERFLOW = 2 };
 // DIV: the divide is compiled in.  The kernels have an instantiation without it, with the registers they had before there was a
 // division, which the host launches for the programs that hold none (agg_ops_hold_division); a division that reaches it all the
 // same overflows the row -- never a silent value.
-template <bool DIV, typename Row>
+// COND: the interpreter with the conditionals, above -- the third instantiation, with the divide too, launched for the programs
+// that hold a conditional op (agg_ops_hold_conditional).  The instantiations without it are, instruction for instruction, what they
+// were, and still never hand out a value for such a program: it begins with kAggCondMark, an AX_MOD on the empty, all-zero slots,
+// which here is a division the instantiation does not have (DIV = false) or a division by zero (DIV = true) -- `ok` is sticky, the row
+// overflows.  (A check of their own in these interpreters was tried in three forms; each cost registers: INTEGRATION.md 6p.)
+template <bool DIV, bool COND = false, typename Row>
 AGG_HD int agg_expr_eval_i128_as(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+  if constexpr (COND) return agg_expr_eval_i128_cond<DIV>(prog, n, row, out);
   AggSlots<agg_i128> s = {0, 0, 0, 0};
   bool ok = true;
   for (uint32_t k = 0; k < n; k++) {
@@ -356,8 +546,110 @@ AGG_HD int agg_expr_eval_i128(const AggExprOp* prog, uint32_t n, const Row& row,
 
 // ... of the FLOAT class.  Row: `valid` and `double load_f64(uint32_t col)`.  Every operation is one IEEE double operation.
 // (DIV as above; without it a division gives NaN.)
+// ... WITH conditionals (agg_expr_eval_i128_cond's counterpart).  No operation on doubles overflows, so a slot has its NULL bit
+// alone; a condition is 1.0 / 0.0.  A comparison is IEEE's: with a NaN all are false but !=.
 template <bool DIV, typename Row>
+AGG_HD int agg_expr_eval_f64_cond(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+  AggSlots<double> s = {0.0, 0.0, 0.0, 0.0};
+  AggSlotBits m = {0, 0};
+  // (the mark in front and, in this class, the two ops behind -- agg_program.h: kAggCondMark -- are for the other interpreters)
+  const bool marked = agg_cond_marked(prog, n);
+  if (marked) n = n >= 1 + kAggCondTailF64 ? n - kAggCondTailF64 : 1;
+  for (uint32_t k = marked ? 1 : 0; k < n; k++) {
+    const AggExprOp op = prog[k];
+    double r = 0.0;
+    switch (op.op) {
+      case AX_GATE:
+        if (!row.valid(op.col)) return AGG_ROW_NULL;
+        break;
+      case AX_PUSH_F64: {
+        const bool v = !op.lo || row.valid(op.col);
+        if (v) r = row.load_f64(op.col);
+        s.push(r);
+        m.push(!v, false);
+        break;
+      }
+      case AX_PUSH_LIT:
+        s.push(agg_f64_of_bits(op.lo));
+        m.push(false, false);
+        break;
+      case AX_PUSH_NULL:
+        s.push(0.0);
+        m.push(true, false);
+        break;
+      case AX_ADD:
+      case AX_SUB:
+      case AX_RSUB:
+      case AX_MUL:
+      case AX_DIV: {
+        r = op.op == AX_ADD ? agg_f64_add(s.s1, s.s0) : op.op == AX_SUB ? agg_f64_add(s.s1, -s.s0) : op.op == AX_RSUB ? agg_f64_add(s.s0, -s.s1)
+          : op.op == AX_MUL ? agg_f64_mul(s.s1, s.s0) : DIV ? agg_f64_div(s.s1, s.s0) : agg_f64_of_bits(0x7ff8000000000000ull);
+        const bool nul = m.n(0) || m.n(1);
+        s.merge(nul ? 0.0 : r);
+        m.merge(nul, false);
+        break;
+      }
+      case AX_NEG:
+        if (!m.n(0)) s.s0 = -s.s0;
+        break;
+      case AX_ABS:
+        if (!m.n(0)) s.s0 = agg_f64_of_bits(agg_bits_of_f64(s.s0) & 0x7fffffffffffffffull);
+        break;
+      case AX_CMP: {
+        const bool nul = m.n(0) || m.n(1);
+        const bool t = !nul && agg_cmp_of(op.col, s.s1 < s.s0, s.s1 == s.s0, s.s1 > s.s0);
+        s.merge(t ? 1.0 : 0.0);
+        m.merge(nul, false);
+        break;
+      }
+      case AX_IS_NULL:
+        s.s0 = m.n(0) ? 1.0 : 0.0;
+        m.set(false, false);
+        break;
+      case AX_AND:
+      case AX_OR: {
+        bool v, nul, ovf;
+        agg_kleene(op.op == AX_OR, s.s1 != 0.0, m.n(1), false, s.s0 != 0.0, m.n(0), false, &v, &nul, &ovf);
+        s.merge(v && !nul ? 1.0 : 0.0);
+        m.merge(nul, false);
+        break;
+      }
+      case AX_NOT:
+        s.s0 = !m.n(0) && s.s0 == 0.0 ? 1.0 : 0.0;
+        break;
+      case AX_IF: {
+        const bool take = !m.n(2) && s.s2 != 0.0;
+        const uint32_t at = take != (op.col != 0) ? 1u : 0u;
+        const bool nul = m.n(at);
+        r = nul ? 0.0 : (at ? s.s1 : s.s0);
+        s.merge3(r);
+        m.merge3(nul, false);
+        break;
+      }
+      case AX_COALESCE: {
+        const bool b = m.n(1);
+        r = b ? s.s0 : s.s1;
+        const bool nul = b && m.n(0);
+        s.merge(r);
+        m.merge(nul, false);
+        break;
+      }
+      case AX_SWAP:
+        s.swap();
+        m.swap();
+        break;
+      default: break;
+    }
+  }
+  *out = s.s0;
+  return m.n(0) ? AGG_ROW_NULL : AGG_ROW_VALUE;
+}
+
+// (COND as above.  Without it a program with conditionals gives NaN, as a division gives NaN without DIV: the mark is no op of this
+// class, but such a program of this class ENDS with `push NaN, add` -- kAggCondTailF64 --, which only these interpreters run.)
+template <bool DIV, bool COND = false, typename Row>
 AGG_HD int agg_expr_eval_f64_as(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+  if constexpr (COND) return agg_expr_eval_f64_cond<DIV>(prog, n, row, out);
   AggSlots<double> s = {0.0, 0.0, 0.0, 0.0};
   for (uint32_t k = 0; k < n; k++) {
     const AggExprOp op = prog[k];

@@ -53,15 +53,32 @@ enum {
   AX_FLOOR_DIV = 13, // -> floor(a / b), integers (INT / DEC alone)
   AX_MOD = 14,       // -> a - floor(a / b) * b: the remainder with the divisor's sign (INT / DEC alone)
   AX_SWAP = 15,      // the two top slots change places
-  AX_N = 16
+  // Conditionals (include/orcgpu.h: CONDITIONALS).  A program that holds one of these has NO gates: every slot carries, beside its
+  // value, a NULL bit and an overflow bit (agg_expr_eval.h: AggSlotBits), its column pushes are "nullable" (lo = 1: the slot's NULL
+  // bit is the row's validity), and only the root's bits decide the row.  A condition is a slot like any other: 1 TRUE, 0 FALSE,
+  // the NULL bit UNKNOWN.  Only the interpreter with the conditionals runs them: the host launches it for such a program, and the
+  // program is marked so that any other interpreter overflows the row (kAggCondMark, below).
+  AX_CMP = 16,       // the two top slots a (below) and b (top) -> a `col` b (`col`: 0 .. 5 for = != < <= > >=); UNKNOWN where either is NULL
+  AX_IS_NULL = 17,   // the top slot -> TRUE where it is NULL, else FALSE: never UNKNOWN
+  AX_AND = 18,       // the two top slots -> Kleene's AND; a FALSE operand decides, whatever the other one is or did
+  AX_OR = 19,        //                   -> Kleene's OR; a TRUE operand decides
+  AX_NOT = 20,       // the top slot -> Kleene's NOT
+  AX_IF = 21,        // the three top slots -> the `then` slot where the condition is TRUE, else the `otherwise` slot, with the chosen
+                     // slot's NULL and overflow bits.  The condition is always evaluated first and stands lowest; `col` = 0: then
+                     // below otherwise, 1: otherwise was evaluated first and stands below then.  (The slots by NUMBER, any of the
+                     // six orders, was tried: the select by a slot number put the slots into scratch memory.)
+  AX_COALESCE = 22,  // the two top slots a (below) and b (top) -> a unless a is NULL, then b
+  AX_ABS = 23,       // the top slot -> its magnitude; -2^127 overflows; a double: the sign bit cleared
+  AX_PUSH_NULL = 24, // a slot whose NULL bit is set
+  AX_N = 25
 };
 // The calendar fields of AX_DATE_PART (include/orcgpu.h: ORCGPU_DATE_PART_*), proleptic Gregorian, astronomical year numbering
 enum { AX_PART_YEAR = 0, AX_PART_QUARTER = 1, AX_PART_MONTH = 2, AX_PART_DAY = 3, AX_PART_DAY_OF_WEEK = 4, AX_PART_DAY_OF_YEAR = 5, AX_PART_N = 6 };
 constexpr uint32_t kAggExprSlots = 4, kAggExprMaxNodes = 32;
 struct AggExprOp {
   uint32_t op;   // AX_*
-  uint32_t col;  // index into the FilterCol table; AX_SCALE10, AX_DIV: k; AX_DATE_PART: AX_PART_*
-  unsigned long long lo, hi;
+  uint32_t col;  // index into the FilterCol table; AX_SCALE10, AX_DIV: k; AX_DATE_PART: AX_PART_*; AX_CMP: the comparison; AX_IF: the slots
+  unsigned long long lo, hi;  // (AX_PUSH_INT / _DEC / _F64: lo = 1 in a program with conditionals: the push is nullable)
 };
 
 // Does a table of programs hold a division?  The host asks before a launch: the kernels that interpret programs come in two
@@ -71,6 +88,24 @@ inline bool agg_ops_hold_division(const AggExprOp* ops, size_t n) {
     if (ops[k].op >= AX_DIV && ops[k].op <= AX_MOD) return true;
   return false;
 }
+
+// ... or a conditional?  (The same question for the third instantiation, the one with the divide AND the conditionals.)
+inline bool agg_ops_hold_conditional(const AggExprOp* ops, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (ops[k].op >= AX_CMP && ops[k].op < AX_N) return true;
+  return false;
+}
+// AX_IF's `col`: which branch was evaluated first
+constexpr uint32_t kAggIfThenFirst = 0, kAggIfElseFirst = 1;
+// What makes a program with conditionals safe in the hands of an interpreter WITHOUT them, at no cost to that interpreter: existing
+// ops.  Its first op is kAggCondMark, an AX_MOD, which no other program begins with (a binary op needs operands): over the empty,
+// all-zero slots it is a division by zero -- or a division the instantiation lacks --, `ok` is sticky and the row overflows.  The
+// double interpreter has no AX_MOD and no overflow; there the program ends with kAggCondTailF64 ops, `AX_PUSH_LIT NaN, AX_ADD`:
+// whatever the ops it knows left on top, the result is NaN, as a division's is without the divide.  The interpreter with the
+// conditionals skips the mark and the tail.
+constexpr uint32_t kAggCondMark = AX_MOD, kAggCondTailF64 = 2;
+constexpr unsigned long long kAggCondNaNBits = 0x7ff8000000000000ull;
+constexpr bool agg_cond_marked(const AggExprOp* prog, uint32_t n) { return n != 0 && prog[0].op == kAggCondMark; }
 
 struct AggInsn {
   uint32_t kind;     // AK_*

@@ -7,7 +7,11 @@
 // slots they need (Sethi-Ullman: the child that needs more goes first) and emitted.  Division (a / b, a // b, a % b; include/
 // orcgpu.h: DIVISION): a `/` anywhere makes an exact expression a Decimal one, its node's scale and the power of ten of its dividend
 // are decided with the scales; `//` and `%` take integers -- scale 0 -- and no doubles; where the right child of one of the three goes
-// first, ONE AX_SWAP stands in front of the op (there are no reversed forms).  Every refusal of the expression aggregates is
+// first, ONE AX_SWAP stands in front of the op (there are no reversed forms).  Conditionals (IF, COALESCE, ABS, NULL and the
+// conditions CMP, IS_NULL, AND, OR, NOT; include/orcgpu.h: CONDITIONALS): numbers and conditions are told apart after the parse, the
+// value operands of IF / COALESCE and the sides of CMP get the scale rule of +, the ternary node its own labelling, and a program
+// that holds one is emitted WITHOUT gates, its column pushes nullable, behind a mark that makes every interpreter without the
+// conditionals overflow the row (agg_program.h: kAggCondMark) -- a program that holds none is, op for op, what it was.  Every refusal of the expression aggregates is
 // decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
 //
 // The row filter's expression leaf (ORCGPU_PRED_CMP_EXPR: lhs OP rhs) has its two sides compiled here too (compile_pair, called by
@@ -52,6 +56,9 @@ static_assert(sizeof(AggExprOp) == 24, "agg_program.h: the record the kernels re
 static_assert((int)AX_PART_YEAR == (int)ORCGPU_DATE_PART_YEAR && (int)AX_PART_DAY_OF_YEAR == (int)ORCGPU_DATE_PART_DAY_OF_YEAR && (int)AX_PART_N == (int)ORCGPU_DATE_PART_DAY_OF_YEAR + 1,
               "the parts of include/orcgpu.h are the interpreter's");
 static_assert(ORCGPU_AGG_EXPR_DIV == 17 && ORCGPU_AGG_EXPR_FLOOR_DIV == 18 && ORCGPU_AGG_EXPR_MOD == 19, "the division nodes of include/orcgpu.h");
+static_assert(ORCGPU_AGG_EXPR_IF == 21 && ORCGPU_AGG_EXPR_COALESCE == 22 && ORCGPU_AGG_EXPR_ABS == 23 && ORCGPU_AGG_EXPR_NULL == 24 && ORCGPU_AGG_EXPR_CMP == 25 &&
+                  ORCGPU_AGG_EXPR_IS_NULL == 26 && ORCGPU_AGG_EXPR_AND == 27 && ORCGPU_AGG_EXPR_OR == 28 && ORCGPU_AGG_EXPR_NOT == 29,
+              "the conditional nodes of include/orcgpu.h: the value nodes, then the condition nodes, without a gap");
 static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
 
 enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
@@ -68,6 +75,8 @@ struct AggExprCompiler {
   struct Node {
     uint32_t op = 0;        // ORCGPU_AGG_EXPR_*, or kScale: this library's own "times 10^k"
     int a = -1, b = -1;     // children
+    int c = -1;             // IF: the third child (a: the condition, b: then, c: otherwise)
+    uint32_t cmp = 0;       // CMP: ORCGPU_PRED_EQ .. _GE
     uint32_t col = 0;       // COLUMN
     int32_t value_type = 0; // LITERAL
     agg_i128 iv = 0;        // LITERAL of the INT / DEC class; kScale: 10^k
@@ -90,6 +99,18 @@ struct AggExprCompiler {
 
   static bool is_division(uint32_t op) { return op == ORCGPU_AGG_EXPR_DIV || op == ORCGPU_AGG_EXPR_FLOOR_DIV || op == ORCGPU_AGG_EXPR_MOD; }
   static const char* division_name(uint32_t op) { return op == ORCGPU_AGG_EXPR_DIV ? "/" : op == ORCGPU_AGG_EXPR_FLOOR_DIV ? "//" : "%"; }
+  // the conditional nodes (include/orcgpu.h: CONDITIONALS): those that produce a condition, and all nine
+  static bool is_condition(uint32_t op) { return op >= ORCGPU_AGG_EXPR_CMP && op <= ORCGPU_AGG_EXPR_NOT; }
+  static bool is_conditional(uint32_t op) { return op >= ORCGPU_AGG_EXPR_IF && op <= ORCGPU_AGG_EXPR_NOT; }
+  static uint32_t conditional_children(uint32_t op) {
+    return op == ORCGPU_AGG_EXPR_IF ? 3 : op == ORCGPU_AGG_EXPR_NULL ? 0 : (op == ORCGPU_AGG_EXPR_ABS || op == ORCGPU_AGG_EXPR_IS_NULL || op == ORCGPU_AGG_EXPR_NOT) ? 1 : 2;
+  }
+  static const char* node_name(uint32_t op) {
+    static const char* const n[] = {"IF", "COALESCE", "ABS", "NULL", "CMP", "IS_NULL", "AND", "OR", "NOT"};
+    if (is_conditional(op)) return n[op - ORCGPU_AGG_EXPR_IF];
+    return op == ORCGPU_AGG_EXPR_COLUMN ? "a column" : op == ORCGPU_AGG_EXPR_LITERAL ? "a literal" : op == ORCGPU_AGG_EXPR_ADD ? "+" : op == ORCGPU_AGG_EXPR_SUB ? "-"
+         : op == ORCGPU_AGG_EXPR_MUL ? "*" : op == ORCGPU_AGG_EXPR_NEG ? "unary -" : op == ORCGPU_AGG_EXPR_DATE_PART ? "a date part" : is_division(op) ? division_name(op) : "?";
+  }
   static const char* part_name(uint32_t part) {
     static const char* const n[] = {"year()", "quarter()", "month()", "day()", "day_of_week()", "day_of_year()"};
     return part < AX_PART_N ? n[part] : "?";
@@ -157,6 +178,18 @@ struct AggExprCompiler {
       if (rc) return rc;
       t[me].a = a;
       t[me].part = (uint32_t)s.i;
+    } else if (is_conditional(s.op)) {
+      if (s.op == ORCGPU_AGG_EXPR_CMP) {
+        if (s.i < ORCGPU_PRED_EQ || s.i > ORCGPU_PRED_GE)
+          return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a CMP node of the expression of %s names no comparison (i: ORCGPU_PRED_EQ .. _GE, 0 .. 5)", op_name);
+        t[me].cmp = (uint32_t)s.i;
+      }
+      int kid[3] = {-1, -1, -1};
+      for (uint32_t k = 0; k < conditional_children(s.op); k++)
+        if (const int rc = parse(kid[k])) return rc;
+      t[me].a = kid[0];
+      t[me].b = kid[1];
+      t[me].c = kid[2];
     } else {
       return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an unknown node in the expression of %s", op_name);
     }
@@ -263,13 +296,37 @@ struct AggExprCompiler {
   int type_node(int n, int& out) {
     out = n;
     if (t[n].a < 0) return ORCGPU_OK;  // a leaf: label 1, its own scale
-    int a = t[n].a, b = t[n].b;
+    int a = t[n].a, b = t[n].b, c = t[n].c;
     if (const int rc = type_node(a, a)) return rc;
     if (b >= 0)
       if (const int rc = type_node(b, b)) return rc;
+    if (c >= 0)
+      if (const int rc = type_node(c, c)) return rc;
     const uint32_t op = t[n].op;
     if (cls == XCLASS_DEC) {
-      if (op == ORCGPU_AGG_EXPR_MUL) {
+      if (op == ORCGPU_AGG_EXPR_IF || op == ORCGPU_AGG_EXPR_COALESCE) {
+        // the two value operands at the larger of their scales; a NULL takes its sibling's
+        int &x = op == ORCGPU_AGG_EXPR_IF ? b : a, &y = op == ORCGPU_AGG_EXPR_IF ? c : b;
+        if (t[x].op == ORCGPU_AGG_EXPR_NULL) t[x].scale = t[y].scale;
+        if (t[y].op == ORCGPU_AGG_EXPR_NULL) t[y].scale = t[x].scale;
+        const int s = t[x].scale > t[y].scale ? t[x].scale : t[y].scale;
+        if (s <= 38) {
+          x = scaled(x, (uint32_t)(s - t[x].scale));
+          y = scaled(y, (uint32_t)(s - t[y].scale));
+        }
+        t[n].scale = s;
+      } else if (op == ORCGPU_AGG_EXPR_CMP) {
+        const int s = t[a].scale > t[b].scale ? t[a].scale : t[b].scale;
+        if (s > 38)
+          return fail(ORCGPU_UNSUPPORTED, "aggregate: a node of the expression of %s over column '%s' has a scale of more than 38: it is not supported", op_name, first_column);
+        a = scaled(a, (uint32_t)(s - t[a].scale));
+        b = scaled(b, (uint32_t)(s - t[b].scale));
+        t[n].scale = 0;
+      } else if (op == ORCGPU_AGG_EXPR_ABS) {
+        t[n].scale = t[a].scale;
+      } else if (is_condition(op)) {
+        t[n].scale = 0;
+      } else if (op == ORCGPU_AGG_EXPR_MUL) {
         t[n].scale = t[a].scale + t[b].scale;
       } else if (op == ORCGPU_AGG_EXPR_DATE_PART) {
         // an integer, over an operand of integers: scale 0 below it too -- but for a division that left another scale there
@@ -308,6 +365,29 @@ struct AggExprCompiler {
     }
     t[n].a = a;
     t[n].b = b;
+    t[n].c = c;
+    if (is_conditional(op)) {
+      if (op == ORCGPU_AGG_EXPR_ABS && is_lit(a)) {  // of a literal: folded with the evaluator's own function unless it overflows
+        Node lit = t[a];
+        bool ok = true;
+        if (cls == XCLASS_FLOAT) lit.fv = agg_f64_of_bits(agg_bits_of_f64(lit.fv) & 0x7fffffffffffffffull);
+        else if (lit.iv < 0) ok = agg_neg_checked(t[a].iv, &lit.iv);
+        if (ok) {
+          t[n] = lit;
+          return ORCGPU_OK;
+        }
+      }
+      // the slots: Sethi-Ullman, and for the ternary node its extension with the condition first -- its result waits in one slot
+      // while the two branches are evaluated as a binary node's operands are, the one that needs more first
+      const uint32_t la = t[a].label, lb = b >= 0 ? t[b].label : 0, lc = c >= 0 ? t[c].label : 0;
+      if (c >= 0) {
+        const uint32_t both = lb == lc ? lb + 1 : lb > lc ? lb : lc;
+        t[n].label = la > both + 1 ? la : both + 1;
+      } else {
+        t[n].label = b < 0 ? la : la == lb ? la + 1 : la > lb ? la : lb;
+      }
+      return ORCGPU_OK;
+    }
     if (op == ORCGPU_AGG_EXPR_DATE_PART) {  // of a literal: folded with the evaluator's own function unless it overflows -- then the rows report it
       if (is_lit(a) && t[a].iv == (agg_i128)(int32_t)(long long)t[a].iv) {
         Node lit;
@@ -355,6 +435,32 @@ struct AggExprCompiler {
       const int k = col_class(x.col, x.in_date);
       o.op = k == ACLASS_FLOAT ? AX_PUSH_F64 : k == ACLASS_DEC ? AX_PUSH_DEC : AX_PUSH_INT;
       o.col = x.col;
+      o.lo = cond_program ? 1 : 0;  // (nullable: no gate stands in front of a program with conditionals)
+    } else if (x.op == ORCGPU_AGG_EXPR_NULL) {
+      o.op = AX_PUSH_NULL;
+    } else if (x.op == ORCGPU_AGG_EXPR_ABS || x.op == ORCGPU_AGG_EXPR_IS_NULL || x.op == ORCGPU_AGG_EXPR_NOT) {
+      emit(x.a, ops);
+      o.op = x.op == ORCGPU_AGG_EXPR_ABS ? AX_ABS : x.op == ORCGPU_AGG_EXPR_IS_NULL ? AX_IS_NULL : AX_NOT;
+    } else if (x.op == ORCGPU_AGG_EXPR_IF) {
+      // the condition first: it ends in slot 2; then the branch that needs more slots
+      const bool else_first = t[x.c].label > t[x.b].label;
+      emit(x.a, ops);
+      emit(else_first ? x.c : x.b, ops);
+      emit(else_first ? x.b : x.c, ops);
+      o.op = AX_IF;
+      o.col = else_first ? kAggIfElseFirst : kAggIfThenFirst;
+    } else if (x.op == ORCGPU_AGG_EXPR_COALESCE || is_condition(x.op)) {  // (CMP, AND, OR: the unary conditions went above)
+      const bool right_first = t[x.b].label > t[x.a].label;
+      emit(right_first ? x.b : x.a, ops);
+      emit(right_first ? x.a : x.b, ops);
+      // AND and OR are symmetric; for the other two, a back below b
+      if (right_first && (x.op == ORCGPU_AGG_EXPR_COALESCE || x.op == ORCGPU_AGG_EXPR_CMP)) {
+        AggExprOp w{};
+        w.op = AX_SWAP;
+        ops.push_back(w);
+      }
+      o.op = x.op == ORCGPU_AGG_EXPR_COALESCE ? AX_COALESCE : x.op == ORCGPU_AGG_EXPR_CMP ? AX_CMP : x.op == ORCGPU_AGG_EXPR_AND ? AX_AND : AX_OR;
+      if (x.op == ORCGPU_AGG_EXPR_CMP) o.col = x.cmp;
     } else if (x.op == ORCGPU_AGG_EXPR_LITERAL) {
       o.op = AX_PUSH_LIT;
       if (cls == XCLASS_FLOAT) {
@@ -399,6 +505,12 @@ struct AggExprCompiler {
     ops.push_back(o);
   }
 
+  bool cond_program = false;  // finish / emit: the program at hand holds a conditional op
+  bool holds_conditional(int n) const {
+    if (n < 0) return false;
+    return is_conditional(t[n].op) || holds_conditional(t[n].a) || holds_conditional(t[n].b) || holds_conditional(t[n].c);
+  }
+
   // pre-order nodes -> a tree behind what `t` holds; root: its root
   int parse_expr(const orcgpu_agg_expr* e, int& root) {
     if (!e || !e->nodes || !e->n_nodes) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: %s without an expression", op_name);
@@ -418,6 +530,31 @@ struct AggExprCompiler {
       return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a DECIMAL128 literal of the expression of %s over column '%s' is not 16 bytes of |value| < 10^38 at a scale of 0 .. 38", op_name, first_column);
     }
     if (at != n_src) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s has nodes left over behind its tree", op_name);
+    return check_kinds(root, false, false);
+  }
+  // Numbers where numbers are wanted, conditions where conditions are: the root is a number, the first child of IF and the children
+  // of AND / OR / NOT are conditions, every other operand a number.  null_ok: a NULL node may stand here -- a value operand of IF or
+  // COALESCE whose sibling is not a NULL itself.
+  int check_kinds(int n, bool want_cond, bool null_ok) {
+    const uint32_t op = t[n].op;
+    if (is_condition(op) != want_cond)
+      return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: %s in the expression of %s over column '%s' stands where a %s is wanted", node_name(op), op_name, first_column,
+                  want_cond ? "condition is wanted: it is a number" : "number is wanted: it is a condition");
+    if (op == ORCGPU_AGG_EXPR_NULL && !null_ok)
+      return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: NULL in the expression of %s over column '%s' stands outside the value operands of IF and COALESCE, or beside another NULL", op_name, first_column);
+    const bool kids_cond = op == ORCGPU_AGG_EXPR_AND || op == ORCGPU_AGG_EXPR_OR || op == ORCGPU_AGG_EXPR_NOT;
+    const int kid[3] = {t[n].a, t[n].b, t[n].c};
+    for (int k = 0; k < 3; k++) {
+      if (kid[k] < 0) continue;
+      bool cond = kids_cond, nul = false;
+      if (op == ORCGPU_AGG_EXPR_IF) {
+        cond = k == 0;
+        nul = k != 0 && t[kid[k == 1 ? 2 : 1]].op != ORCGPU_AGG_EXPR_NULL;
+      } else if (op == ORCGPU_AGG_EXPR_COALESCE) {
+        nul = t[kid[1 - k]].op != ORCGPU_AGG_EXPR_NULL;
+      }
+      if (const int rc = check_kinds(kid[k], cond, nul)) return rc;
+    }
     return ORCGPU_OK;
   }
   // the class of everything parsed, and the columns' scales
@@ -436,9 +573,12 @@ struct AggExprCompiler {
     if (const int rc = type_node(root, root)) return rc;
     if (t[root].label > kAggExprSlots)
       return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
+    // A tree that still holds a conditional node has no gates: NULL is per operand there, the pushes are nullable and the root's
+    // bits decide the row.  Every other program is what it always was.
+    cond_program = holds_conditional(root);
     // the gates: every distinct column, in order of appearance
     std::vector<uint32_t> seen;
-    for (uint32_t k = 0; k < n_src; k++) {
+    for (uint32_t k = 0; k < n_src && !cond_program; k++) {
       if (src[k].op != ORCGPU_AGG_EXPR_COLUMN) continue;
       uint32_t col = 0;
       while (!names[col] || strcmp(names[col], src[k].column) != 0) col++;  // (parse found it)
@@ -452,14 +592,31 @@ struct AggExprCompiler {
       ops.push_back(g);
     }
     const size_t first_op = ops.size();
+    if (cond_program) {  // the mark: an interpreter without the conditionals overflows the row on it (agg_program.h: kAggCondMark)
+      AggExprOp mark{};
+      mark.op = kAggCondMark;
+      ops.push_back(mark);
+    }
     emit(root, ops);
+    const size_t end_op = ops.size();  // (what is counted below: not the mark, not the tail)
+    if (cond_program && cls == XCLASS_FLOAT) {  // ... and in the double class NaN is its result there: `push NaN, add` behind the program
+      AggExprOp nan{}, add{};
+      nan.op = AX_PUSH_LIT;
+      nan.lo = kAggCondNaNBits;
+      add.op = AX_ADD;
+      ops.push_back(nan);
+      ops.push_back(add);
+    }
     // (the labels promise it; the program itself is what the kernels run, so it is counted once more before it is accepted)
     uint32_t depth = 0, most = 0;
-    for (size_t k = first_op; k < ops.size(); k++) {
+    for (size_t k = first_op + (cond_program ? 1 : 0); k < end_op; k++) {
       const uint32_t o = ops[k].op;
-      if (o >= AX_PUSH_INT && o <= AX_PUSH_LIT) depth++;
+      if ((o >= AX_PUSH_INT && o <= AX_PUSH_LIT) || o == AX_PUSH_NULL) depth++;
       else if ((o >= AX_ADD && o <= AX_MUL) || (o >= AX_DIV && o <= AX_MOD)) depth--;  // (AX_NEG, AX_SCALE10, AX_DATE_PART: unary, the depth stays)
       else if (o == AX_SWAP && depth < 2) most = kAggExprSlots + 1;                     // (... and AX_SWAP changes two operands that must be there)
+      else if (o == AX_CMP || o == AX_AND || o == AX_OR || o == AX_COALESCE) depth--;   // (AX_IS_NULL, AX_NOT, AX_ABS: unary)
+      else if (o == AX_IF && (depth < 3 || ops[k].col > kAggIfElseFirst)) most = kAggExprSlots + 1;
+      else if (o == AX_IF) depth -= 2;
       most = depth > most ? depth : most;
     }
     if (most > kAggExprSlots || depth != 1) {

@@ -259,7 +259,8 @@ inline bool agg_plan_in_bounds(const std::vector<AggInsn>& insns, const std::vec
     }
     if (in.col > ops.size() || in.col2 > ops.size() - in.col || !in.col2) return false;
     for (uint32_t k = in.col; k < in.col + in.col2; k++)
-      if (ops[k].op >= AX_N || (ops[k].op <= AX_PUSH_F64 && ops[k].col >= nc) || (ops[k].op == AX_DATE_PART && ops[k].col >= AX_PART_N) || (ops[k].op == AX_DIV && ops[k].col > 38)) return false;
+      if (ops[k].op >= AX_N || (ops[k].op <= AX_PUSH_F64 && ops[k].col >= nc) || (ops[k].op == AX_DATE_PART && ops[k].col >= AX_PART_N) || (ops[k].op == AX_DIV && ops[k].col > 38) ||
+          (ops[k].op == AX_CMP && ops[k].col > 5) || (ops[k].op == AX_IF && ops[k].col > kAggIfElseFirst)) return false;
   }
   return true;
 }

@@ -98,8 +98,13 @@ inline int computed_compile(const char* const* names, const orcgpu_agg_expr* exp
     }
     c.cls = (uint32_t)x.cls;
     c.n_ops = (uint32_t)plan.ops.size() - c.first_op;
-    for (uint32_t o = c.first_op; o < plan.ops.size(); o++)
-      if (plan.ops[o].op == AX_GATE) c.reads.push_back(plan.ops[o].col);
+    // (a program with conditionals has no gates: its pushes name the columns; a program with gates pushes no other column)
+    for (uint32_t o = c.first_op; o < plan.ops.size(); o++) {
+      if (plan.ops[o].op > AX_PUSH_F64) continue;
+      bool dup = false;
+      for (const uint32_t seen : c.reads) dup |= seen == plan.ops[o].col;
+      if (!dup) c.reads.push_back(plan.ops[o].col);
+    }
     plan.cols.push_back(std::move(c));
   }
   return ORCGPU_OK;

@@ -29,7 +29,11 @@ static_assert(ORCGPU_PRED_CMP_EXPR == 19 && ORCGPU_PRED_EXPR_COLUMN == 20 && ORC
                   ORCGPU_PRED_EXPR_SUB - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_SUB && ORCGPU_PRED_EXPR_MUL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MUL &&
                   ORCGPU_PRED_EXPR_NEG - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NEG && ORCGPU_PRED_EXPR_DATE_PART - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DATE_PART &&
                   ORCGPU_PRED_EXPR_DIV - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_DIV && ORCGPU_PRED_EXPR_FLOOR_DIV - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_FLOOR_DIV &&
-                  ORCGPU_PRED_EXPR_MOD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MOD,
+                  ORCGPU_PRED_EXPR_MOD - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_MOD && ORCGPU_PRED_EXPR_IF - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_IF &&
+                  ORCGPU_PRED_EXPR_COALESCE - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_COALESCE && ORCGPU_PRED_EXPR_ABS - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_ABS &&
+                  ORCGPU_PRED_EXPR_NULL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NULL && ORCGPU_PRED_EXPR_CMP - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_CMP &&
+                  ORCGPU_PRED_EXPR_IS_NULL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_IS_NULL && ORCGPU_PRED_EXPR_AND - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_AND &&
+                  ORCGPU_PRED_EXPR_OR - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_OR && ORCGPU_PRED_EXPR_NOT - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NOT,
               "the expression leaf of include/orcgpu.h: its nodes are the expression aggregates', 20 further on");
 static_assert((int)FXC_INT == (int)XCLASS_INT && (int)FXC_DEC == (int)XCLASS_DEC && (int)FXC_FLOAT == (int)XCLASS_FLOAT && sizeof(AggExprOp) == kExprOpBytes, "filter_program.h: an expression leaf's blob");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
@@ -291,6 +295,8 @@ struct FilterCompiler {
       }
       case ORCGPU_PRED_EXPR_COLUMN: case ORCGPU_PRED_EXPR_LITERAL: case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: case ORCGPU_PRED_EXPR_NEG:
       case ORCGPU_PRED_EXPR_DATE_PART: case ORCGPU_PRED_EXPR_DIV: case ORCGPU_PRED_EXPR_FLOOR_DIV: case ORCGPU_PRED_EXPR_MOD:
+      case ORCGPU_PRED_EXPR_IF: case ORCGPU_PRED_EXPR_COALESCE: case ORCGPU_PRED_EXPR_ABS: case ORCGPU_PRED_EXPR_NULL: case ORCGPU_PRED_EXPR_CMP:
+      case ORCGPU_PRED_EXPR_IS_NULL: case ORCGPU_PRED_EXPR_AND: case ORCGPU_PRED_EXPR_OR: case ORCGPU_PRED_EXPR_NOT:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
@@ -308,6 +314,11 @@ struct FilterCompiler {
       case ORCGPU_PRED_EXPR_ADD: case ORCGPU_PRED_EXPR_SUB: case ORCGPU_PRED_EXPR_MUL: kids = 2; break;
       case ORCGPU_PRED_EXPR_DIV: case ORCGPU_PRED_EXPR_FLOOR_DIV: case ORCGPU_PRED_EXPR_MOD: kids = 2; break;  // (a division's scale travels in `i`, below)
       case ORCGPU_PRED_EXPR_NEG: case ORCGPU_PRED_EXPR_DATE_PART: kids = 1; break;  // (the part travels in `i`, below)
+      // the conditionals (the comparison of a CMP travels in `i`); numbers against conditions are the expression compiler's to check
+      case ORCGPU_PRED_EXPR_IF: kids = 3; break;
+      case ORCGPU_PRED_EXPR_COALESCE: case ORCGPU_PRED_EXPR_CMP: case ORCGPU_PRED_EXPR_AND: case ORCGPU_PRED_EXPR_OR: kids = 2; break;
+      case ORCGPU_PRED_EXPR_ABS: case ORCGPU_PRED_EXPR_IS_NULL: case ORCGPU_PRED_EXPR_NOT: kids = 1; break;
+      case ORCGPU_PRED_EXPR_NULL: kids = 0; break;
       default: return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds expression nodes only%s (node op %lld)", "", n.op);
     }
     if (n.n_children != kids) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node with the wrong number of children%s (%lld)", "", n.n_children);
@@ -656,8 +667,8 @@ inline void filter_expr_reads(const FilterPlan& plan, const FilterInsn& in, std:
   }
 }
 
-// Does an expression leaf of the plan hold a division?  (The call then launches filter_expr_div_kernel in place of filter_expr_kernel.)
-inline bool filter_plan_holds_division(const FilterPlan& plan) {
+// Does an expression leaf of the plan hold an op `holds` says yes to?
+inline bool filter_plan_holds(const FilterPlan& plan, bool (*holds)(const AggExprOp*, size_t)) {
   for (const uint32_t leaf : plan.expr_leaves) {
     if (leaf >= plan.prog.size()) continue;
     const FilterInsn& in = plan.prog[leaf];
@@ -666,11 +677,15 @@ inline bool filter_plan_holds_division(const FilterPlan& plan) {
     for (uint32_t k = 0; k < b.n_lhs + b.n_rhs; k++) {
       AggExprOp op;
       memcpy(&op, plan.lits.data() + in.lit_off + kExprHeaderBytes + (size_t)k * sizeof(AggExprOp), sizeof(op));
-      if (agg_ops_hold_division(&op, 1)) return true;
+      if (holds(&op, 1)) return true;
     }
   }
   return false;
 }
+// ... a division?  (The call then launches filter_expr_div_kernel in place of filter_expr_kernel.)
+inline bool filter_plan_holds_division(const FilterPlan& plan) { return filter_plan_holds(plan, agg_ops_hold_division); }
+// ... a conditional?  (filter_expr_cond_kernel, which has the divide too.)
+inline bool filter_plan_holds_conditional(const FilterPlan& plan) { return filter_plan_holds(plan, agg_ops_hold_conditional); }
 
 // `from`, a plan compiled on its own against the same columns, behind `into`: its instructions behind into's, its literals behind
 // into's from an 8-byte boundary (what the IN tables and the LIKE patterns are aligned to), its mask planes numbered behind

@@ -579,7 +579,11 @@ struct PredEval {
     const PredNode& n = nodes[at];
     const uint32_t kids = n.op == ORCGPU_PRED_EXPR_COLUMN || n.op == ORCGPU_PRED_EXPR_LITERAL ? 0 : n.op == ORCGPU_PRED_EXPR_NEG || n.op == ORCGPU_PRED_EXPR_DATE_PART ? 1
                         : n.op == ORCGPU_PRED_EXPR_ADD || n.op == ORCGPU_PRED_EXPR_SUB || n.op == ORCGPU_PRED_EXPR_MUL ? 2
-                        : n.op == ORCGPU_PRED_EXPR_DIV || n.op == ORCGPU_PRED_EXPR_FLOOR_DIV || n.op == ORCGPU_PRED_EXPR_MOD ? 2 : ~0u;  // (never pruned through: a leaf that holds one has no bare column beside one literal)
+                        : n.op == ORCGPU_PRED_EXPR_DIV || n.op == ORCGPU_PRED_EXPR_FLOOR_DIV || n.op == ORCGPU_PRED_EXPR_MOD ? 2  // (never pruned through: a leaf that holds one has no bare column beside one literal)
+                        // ... and the conditionals, never pruned through for the same reason
+                        : n.op == ORCGPU_PRED_EXPR_IF ? 3 : n.op == ORCGPU_PRED_EXPR_NULL ? 0
+                        : n.op == ORCGPU_PRED_EXPR_ABS || n.op == ORCGPU_PRED_EXPR_IS_NULL || n.op == ORCGPU_PRED_EXPR_NOT ? 1
+                        : n.op == ORCGPU_PRED_EXPR_COALESCE || n.op == ORCGPU_PRED_EXPR_CMP || n.op == ORCGPU_PRED_EXPR_AND || n.op == ORCGPU_PRED_EXPR_OR ? 2 : ~0u;
     if (kids == ~0u || n.n_children != kids) return 0;
     size_t next = at + 1;
     for (uint32_t k = 0; k < kids; k++)

@@ -13,6 +13,8 @@ CMP_EXPR = 19  # lhs OP rhs over two arithmetic expressions; its subtrees are ma
 EXPR_COLUMN, EXPR_LITERAL, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG = range(20, 26)  # ORCGPU_PRED_EXPR_*: aggregate.EXPR_* + 20
 EXPR_DATE_PART = 36  # ... aggregate.EXPR_DATE_PART + 20: one child, the part in `i`
 EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 37, 38, 39  # ... aggregate.EXPR_DIV .. EXPR_MOD + 20: two children; DIV: the result scale, or -1, in `i`
+# ... aggregate.EXPR_IF .. EXPR_NOT + 20: the conditionals (3, 2, 1, 0, 2, 1, 2, 2, 1 children; CMP: the comparison EQ .. GE in `i`)
+EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_NULL, EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT = range(41, 50)
 _CMP_OPS = {"=": EQ, "!=": NE, "<": LT, "<=": LE, ">": GT, ">=": GE}
 _CMP_SIGNS = {v: k for k, v in _CMP_OPS.items()}
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
@@ -236,6 +238,16 @@ class Predicate:
     def not_(cls, predicate):
         return cls(NOT, children=[predicate])
 
+    # p & q, p | q, ~p: and_([p, q]), or_([p, q]), not_(p)
+    def __and__(self, other):
+        return Predicate.and_([self, other]) if isinstance(other, Predicate) else NotImplemented
+
+    def __or__(self, other):
+        return Predicate.or_([self, other]) if isinstance(other, Predicate) else NotImplemented
+
+    def __invert__(self):
+        return Predicate.not_(self)
+
     def __repr__(self):
         name = _OP_NAMES.get(self.op, "op%d" % self.op)
         if self.op in (AND, OR):
@@ -279,6 +291,8 @@ class Predicate:
                 n.i = e.part
             elif e.op + EXPR_COLUMN == EXPR_DIV:
                 n.i = -1 if e.scale is None else e.scale
+            elif e.op + EXPR_COLUMN == EXPR_CMP:
+                n.i = e.cmp
             out.append(n)
             for c in e.children:
                 walk_expr(c)
