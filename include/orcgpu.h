@@ -456,7 +456,12 @@ enum { ORCGPU_PRED_EQ = 0, ORCGPU_PRED_NE = 1, ORCGPU_PRED_LT = 2, ORCGPU_PRED_L
        ORCGPU_PRED_EXPR_CMP = 45, ORCGPU_PRED_EXPR_IS_NULL = 46, ORCGPU_PRED_EXPR_AND = 47, ORCGPU_PRED_EXPR_OR = 48,
        ORCGPU_PRED_EXPR_NOT = 49      /* the conditional nodes of an expression (ORCGPU_AGG_EXPR_IF .. _NOT + 20; the expression
                                           aggregates' CONDITIONALS): 3, 2, 1, 0, 2, 1, 2, 2, 1 children; CMP: i = ORCGPU_PRED_EQ .. _GE.
-                                          A leaf that holds one keeps every row group when pruning */ };
+                                          A leaf that holds one keeps every row group when pruning */,
+       ORCGPU_PRED_EXPR_CAST = 50, ORCGPU_PRED_EXPR_ROUND = 51, ORCGPU_PRED_EXPR_FLOOR = 52, ORCGPU_PRED_EXPR_CEIL = 53,
+       ORCGPU_PRED_EXPR_TRUNC = 54    /* the conversion nodes of an expression (ORCGPU_AGG_EXPR_CAST .. _TRUNC + 20; the expression
+                                          aggregates' CONVERSIONS): exactly one child each; CAST: value_type = the target, i = the scale of
+                                          a DECIMAL128 target; ROUND: i = the digits.  A leaf that holds one keeps every row group when
+                                          pruning */ };
 /* What one IN list may hold: literal nodes (before duplicates are dropped), and bytes of Utf8 literals in all. */
 #define ORCGPU_IN_MAX_VALUES 65536
 #define ORCGPU_IN_MAX_BYTES (4u << 20)
@@ -763,6 +768,7 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *     ORCGPU_AGG_EXPR_DATE_PART (one child, the part in `i`) is the one function: DATE PARTS below.
  *     ORCGPU_AGG_EXPR_DIV / _FLOOR_DIV / _MOD (exactly two children; DIV: a result scale in `i`): DIVISION below.
  *     ORCGPU_AGG_EXPR_IF / _COALESCE / _ABS / _NULL and the condition nodes _CMP / _IS_NULL / _AND / _OR / _NOT: CONDITIONALS below.
+ *     ORCGPU_AGG_EXPR_CAST / _ROUND / _FLOOR / _CEIL / _TRUNC (one child each): CONVERSIONS below.
  *   - CLASSES, decided bottom-up when the list is compiled:
  *       INT    Byte .. Long columns and INT64 literals.  Every intermediate value is a signed 128-bit integer.  ORCGPU_AGG_KIND_I128.
  *       DEC    at least one Decimal column or DECIMAL128 literal; Byte .. Long columns and INT64 literals beside them count as
@@ -873,6 +879,42 @@ int orcgpu_reader_aggregate_groups(orcgpu_reader* r, orcgpu_groups** out);
  *                An ABS of a literal is folded; no other conditional node is.  An expression without any column stays
  *                refused where it was.
  *     Row-group pruning does not look through a conditional: a filter leaf that holds one keeps every row group.
+ *   - CONVERSIONS: five nodes with one child each, in every stage that speaks this language (in the row filter's
+ *     ORCGPU_PRED_CMP_EXPR they are ORCGPU_PRED_EXPR_CAST .. _TRUNC, 20 further on): conversion BETWEEN the classes, and rounding
+ *     inside them.  Without one, a Float / Double beside an integer or a Decimal stays ORCGPU_MISMATCHED_SCHEMA (the message says
+ *     that a cast brings them together); with one, l_quantity * weight is cast(l_quantity, FLOAT64) * weight.
+ *       CLASSES  An expression that holds one of these nodes has its classes decided PER NODE, bottom-up.  The two operands of
+ *                + - * / // %, the two sides of CMP and the value operands of IF / COALESCE are still of one class: INT beside DEC
+ *                is promoted, an INT64 literal beside doubles is a double where that is exact, doubles beside anything else are
+ *                ORCGPU_MISMATCHED_SCHEMA.  a / b of two integers is a Decimal.  CAST gives its subtree the target class; ROUND,
+ *                FLOOR, CEIL and TRUNC keep their child's.  The ROOT's class decides the aggregate's kind and the computed column's
+ *                type (Int64 / Decimal128(38, s) / Float64).  A date part, // and % keep their integer operands: CAST to INT64 below
+ *                them is legal, and so is FLOOR / CEIL / TRUNC / ROUND to 0 digits of a Decimal, which is of scale 0.  What stands
+ *                below a conversion is not "below the date part" above it: a Date column there is what it is without the part.
+ *       CAST     value_type = the target: ORCGPU_PV_INT64, _FLOAT64 or _DECIMAL128, then i = the scale t, 0 .. 38.
+ *                to FLOAT64   from FLOAT: nothing (no op).  From INT, or DEC at scale s: the double nearest the exact rational
+ *                             unscaled / 10^s, ties to even -- Python's float(Fraction(unscaled, 10**s)).  Never an overflow.
+ *                to DECIMAL128 at scale t   from INT, or DEC at scale s <= t: times 10^(t - s), checked.  From DEC at scale s > t:
+ *                             divided by 10^(s - t), rounded half away from zero (AVG's and /'s rule).  From FLOAT: the double's
+ *                             exact value m * 2^e times 10^t, computed exactly and rounded half away from zero; NaN, an infinity
+ *                             and a result of magnitude 10^38 or more overflow the row; -0.0 gives 0.  DEC at scale t.
+ *                to INT64     from INT: the value.  From DEC at scale s: the unscaled value divided by 10^s, truncated toward zero.
+ *                             From FLOAT: truncated toward zero (Arrow's, Spark's and C's rule; rounding is cast(round(x))).  In all
+ *                             three a result outside int64 overflows the row, as do NaN and the infinities.  INT.
+ *       ROUND    i = the digits n, 0 .. 38.  DEC at scale s: unchanged where n >= s, else rescaled to scale n, half away from zero.
+ *                INT: unchanged.  FLOAT: n must be 0 -- C's round(), half away from zero, still a double; NaN and the infinities
+ *                pass --; n > 0 is ORCGPU_UNSUPPORTED (the message: round a double to n places with a cast to DECIMAL128 at n).
+ *       FLOOR, CEIL, TRUNC   DEC at scale s: the integer, at scale 0, toward -infinity, toward +infinity, toward zero.  INT: unchanged,
+ *                no op.  FLOAT: IEEE floor / ceil / trunc, still a double.
+ *       NULL AND OVERFLOW are per operand, as with the CONDITIONALS -- a program with a conversion is laid out and run like one with
+ *                a conditional --: NULL in gives NULL out; overflow is the language's: AGG_OVERFLOW in an aggregate (of the FLOAT
+ *                class too, where a conversion inside overflowed), UNKNOWN and counted in the row filter, NULL and counted in a
+ *                computed column.
+ *       LIMITS   every node counts against ORCGPU_AGG_EXPR_MAX_NODES and needs the operand slots of its child.  A conversion of a
+ *                literal alone is folded when the list is compiled, unless it overflows: then it is left to the rows.
+ *       REFUSED  ORCGPU_INVALID_ARGUMENT: a CAST whose value_type is no target, a scale or digits outside 0 .. 38, a node without
+ *                its child, a condition as the child (the message names the node).  ORCGPU_UNSUPPORTED: ROUND of a double to n > 0.
+ *     Row-group pruning does not look through a conversion: a filter leaf that holds one keeps every row group.
  *   - OPS: ORCGPU_AGG_OP_SUM_EXPR the sum of the expression over the kept rows where it is not NULL, NULL over no such row;
  *     ORCGPU_AGG_OP_AVG the average of a plain column (the columns SUM takes); ORCGPU_AGG_OP_AVG_EXPR the average of an expression.
  *     A *_EXPR op without an expression -- through an entry point without `exprs` too -- is ORCGPU_INVALID_ARGUMENT.
@@ -899,7 +941,10 @@ enum { ORCGPU_AGG_EXPR_COLUMN = 0, ORCGPU_AGG_EXPR_LITERAL = 1, ORCGPU_AGG_EXPR_
        ORCGPU_AGG_EXPR_ABS = 23 /* one child */, ORCGPU_AGG_EXPR_NULL = 24 /* no children: the NULL of its sibling's class and scale */,
        /* ... and condition nodes, legal only as the first child of IF or below AND / OR / NOT: */
        ORCGPU_AGG_EXPR_CMP = 25 /* two value children; i = ORCGPU_PRED_EQ .. _GE (0 .. 5) */, ORCGPU_AGG_EXPR_IS_NULL = 26 /* one value child */,
-       ORCGPU_AGG_EXPR_AND = 27, ORCGPU_AGG_EXPR_OR = 28 /* two condition children */, ORCGPU_AGG_EXPR_NOT = 29 /* one condition child */ };
+       ORCGPU_AGG_EXPR_AND = 27, ORCGPU_AGG_EXPR_OR = 28 /* two condition children */, ORCGPU_AGG_EXPR_NOT = 29 /* one condition child */,
+       /* CONVERSIONS above: one child each */
+       ORCGPU_AGG_EXPR_CAST = 30 /* value_type = the target ORCGPU_PV_INT64 / _FLOAT64 / _DECIMAL128; DECIMAL128: i = the scale 0 .. 38 */,
+       ORCGPU_AGG_EXPR_ROUND = 31 /* i = the digits 0 .. 38 */, ORCGPU_AGG_EXPR_FLOOR = 32, ORCGPU_AGG_EXPR_CEIL = 33, ORCGPU_AGG_EXPR_TRUNC = 34 };
 enum { ORCGPU_DATE_PART_YEAR = 0, ORCGPU_DATE_PART_QUARTER = 1, ORCGPU_DATE_PART_MONTH = 2, ORCGPU_DATE_PART_DAY = 3,
        ORCGPU_DATE_PART_DAY_OF_WEEK = 4, ORCGPU_DATE_PART_DAY_OF_YEAR = 5 };
 typedef struct {

@@ -12,6 +12,13 @@ a zero divisor an overflow of the row, `//` and `%` on integers with Python's fl
 take a calendar field of a Date (or of any integer expression of days since 1970-01-01); `when(cond, a, b)`, `case([(c1, a), ...],
 otherwise)`, `coalesce(a, b, ...)`, `nullif(a, b)` and `abs(e)` choose per row -- SQL's CASE WHEN, COALESCE, NULLIF and ABS, with NULL
 and overflow tracked per operand, so that the branch not taken is never seen: `when(col("b").ne(0), col("a") / col("b"), 0)`.
+`cast(e, "int64")`, `cast(e, "float64")` and `cast(e, decimal_(scale))` convert between the classes (the Decimal target is spelled
+`decimal_` in this module, where `decimal` is the standard library's; the package exports it as `orc_rust_amd.decimal` too) -- a Decimal beside a Double needs
+one: `cast("l_quantity", "float64") * col("weight")` --, and `round_(e, digits)`, `floor(e)`, `ceil(e)`, `trunc(e)` (also Python's
+`round(expr, 2)`, `math.floor(expr)`, `math.ceil(expr)`, `math.trunc(expr)`) round inside a class: a Decimal half away from zero to
+`digits` places, or to the integer below, above or toward zero; a double by C's round / floor / ceil / trunc.  Exact and
+deterministic: a cast to float64 is the nearest double of the exact value, a cast to int64 truncates toward zero, and a value the
+target cannot hold overflows the row.
 TPC-H Q1 whole:
 
     from orc_rust_amd.aggregate import Agg, col
@@ -34,6 +41,9 @@ EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 17, 18, 19  # ORCGPU_AGG_EXPR_DIV / _FLOOR_
 # (0 children) are numbers; CMP (2; the comparison EQ .. GE in `i`), IS_NULL (1), AND, OR (2) and NOT (1) are conditions
 EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_NULL, EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT = range(21, 30)
 _CONDITIONS = (EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT)
+# ORCGPU_AGG_EXPR_CAST .. _TRUNC: the conversions, one child each.  CAST: the target in the node's value_type (PV_INT64 / PV_FLOAT64 /
+# PV_DECIMAL128) and, for a Decimal target, the scale in `i`; ROUND: the digits in `i`
+EXPR_CAST, EXPR_ROUND, EXPR_FLOOR, EXPR_CEIL, EXPR_TRUNC = range(30, 35)
 DATE_PARTS = ("year", "quarter", "month", "day", "day_of_week", "day_of_year")  # ORCGPU_DATE_PART_*, by number
 PV_INT64, PV_FLOAT64, PV_DECIMAL128 = 4, 6, 8  # ORCGPU_PV_* of an expression's literals
 EXPR_MAX_NODES, EXPR_MAX_DEPTH = 32, 4  # ORCGPU_AGG_EXPR_MAX_*
@@ -89,6 +99,7 @@ class Expr:
         self.part = part  # EXPR_DATE_PART: the index into DATE_PARTS
         self.scale = scale  # EXPR_DIV: the scale of an exact quotient the caller chose (divide), None: the default rule
         self.cmp = cmp  # EXPR_CMP: predicate.EQ .. GE
+        # (EXPR_CAST: value_type is the target and `scale` a Decimal target's scale; EXPR_ROUND: `scale` holds the digits)
 
     @staticmethod
     def _wrap(x):
@@ -96,6 +107,18 @@ class Expr:
 
     def __abs__(self):
         return abs_(self)
+
+    def __round__(self, digits=None):
+        return round_(self, 0 if digits is None else digits)
+
+    def __floor__(self):
+        return floor(self)
+
+    def __ceil__(self):
+        return ceil(self)
+
+    def __trunc__(self):
+        return trunc(self)
 
     def __add__(self, other):
         return Expr(EXPR_ADD, (self, Expr._wrap(other)))
@@ -174,6 +197,13 @@ class Expr:
         if self.op in (EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_IS_NULL):
             name = {EXPR_IF: "when", EXPR_COALESCE: "coalesce", EXPR_ABS: "abs", EXPR_IS_NULL: "is_null"}[self.op]
             return "%s(%s)" % (name, ", ".join(repr(c) for c in self.children))
+        if self.op == EXPR_CAST:
+            target = {PV_INT64: "'int64'", PV_FLOAT64: "'float64'"}.get(self.value_type) or "decimal(%d)" % self.scale
+            return "cast(%r, %s)" % (self.children[0], target)
+        if self.op == EXPR_ROUND:
+            return "round_(%r, %d)" % (self.children[0], self.scale)
+        if self.op in (EXPR_FLOOR, EXPR_CEIL, EXPR_TRUNC):
+            return "%s(%r)" % ({EXPR_FLOOR: "floor", EXPR_CEIL: "ceil", EXPR_TRUNC: "trunc"}[self.op], self.children[0])
         if self.op == EXPR_NOT:
             return "(~%r)" % (self.children[0],)
         if self.op == EXPR_CMP:
@@ -212,6 +242,11 @@ class Expr:
                 n.i = -1 if e.scale is None else e.scale
             elif e.op == EXPR_CMP:
                 n.i = e.cmp
+            elif e.op == EXPR_CAST:
+                n.value_type = e.value_type
+                n.i = e.scale if e.value_type == PV_DECIMAL128 else 0
+            elif e.op == EXPR_ROUND:
+                n.i = e.scale
             out.append(n)
             for c in e.children:
                 walk(c)
@@ -375,6 +410,70 @@ def nullif(a, b):
 def abs_(e):
     """|e| (ORCGPU_AGG_EXPR_ABS), also abs(expr): -2^127 overflows the row; a double has its sign bit cleared."""
     return Expr(EXPR_ABS, (_operand("abs_", e),))
+
+
+class DecimalTarget:
+    """decimal(scale): the Decimal128(38, scale) target of a cast."""
+
+    def __init__(self, scale):
+        if isinstance(scale, bool) or not isinstance(scale, int):
+            raise TypeError("decimal: the scale is an int 0 .. 38, not %s" % type(scale).__name__)
+        if not 0 <= scale <= 38:
+            raise ValueError("decimal: the scale is 0 .. 38, got %d" % scale)
+        self.scale = scale
+
+    def __repr__(self):
+        return "decimal(%d)" % self.scale
+
+
+def decimal_(scale):
+    """The target of cast(e, decimal_(scale)): Decimal128(38, scale), scale 0 .. 38.  `decimal_` here -- `decimal` is the standard
+    library's module in this one --; the package also exports it under the name `orc_rust_amd.decimal`."""
+    return DecimalTarget(scale)
+
+
+def cast(e, target):
+    """CAST(e AS target) (ORCGPU_AGG_EXPR_CAST).  e: an Expr, a column name or a number; target: "int64", "float64" or
+    decimal_(scale) (orc_rust_amd.decimal(scale): the same function).  To float64: the double nearest the exact value (of a Decimal: unscaled / 10^scale), ties to even.  To
+    decimal(t): an integer or a Decimal of a lower scale times the power of ten; a Decimal of a higher scale divided by it, half away
+    from zero; a double's exact value times 10^t, half away from zero.  To int64: truncated toward zero.  NaN, an infinity and a value
+    the target cannot hold overflow the row."""
+    x = _operand("cast", e)
+    if isinstance(target, DecimalTarget):
+        return Expr(EXPR_CAST, (x,), value_type=PV_DECIMAL128, scale=target.scale)
+    if not isinstance(target, str):
+        raise TypeError("cast: the target is 'int64', 'float64' or decimal(scale), not %s" % type(target).__name__)
+    if target not in ("int64", "float64"):
+        raise ValueError("cast: the target is 'int64', 'float64' or decimal(scale), got %r" % target)
+    return Expr(EXPR_CAST, (x,), value_type=PV_INT64 if target == "int64" else PV_FLOAT64)
+
+
+def round_(e, digits=0):
+    """ROUND(e, digits) (ORCGPU_AGG_EXPR_ROUND), also round(expr, digits): a Decimal of a higher scale is brought to `digits`
+    places (0 .. 38), half away from zero; an integer is unchanged; a double takes digits = 0 alone -- C's round(), still a double:
+    round a double to n places with cast(e, decimal_(n))."""
+    x = _operand("round_", e)
+    if isinstance(digits, bool) or not isinstance(digits, int):
+        raise TypeError("round_: the digits are an int 0 .. 38, not %s" % type(digits).__name__)
+    if not 0 <= digits <= 38:
+        raise ValueError("round_: the digits are 0 .. 38, got %d" % digits)
+    return Expr(EXPR_ROUND, (x,), scale=digits)
+
+
+def floor(e):
+    """FLOOR(e) (ORCGPU_AGG_EXPR_FLOOR), also math.floor(expr): a Decimal -> the integer at scale 0 toward -infinity; an integer
+    unchanged; a double -> IEEE floor, still a double."""
+    return Expr(EXPR_FLOOR, (_operand("floor", e),))
+
+
+def ceil(e):
+    """CEIL(e) (ORCGPU_AGG_EXPR_CEIL), also math.ceil(expr): toward +infinity."""
+    return Expr(EXPR_CEIL, (_operand("ceil", e),))
+
+
+def trunc(e):
+    """TRUNC(e) (ORCGPU_AGG_EXPR_TRUNC), also math.trunc(expr): toward zero."""
+    return Expr(EXPR_TRUNC, (_operand("trunc", e),))
 
 
 def extract(part, e):

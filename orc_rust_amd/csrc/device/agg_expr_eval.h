@@ -4,7 +4,9 @@
 // negate, the powers of ten, the interpreter of a program of AggExprOp (agg_program.h) over four operand slots, and -- host only --
 // AVG's division.  Plain C++ behind AGG_HD; nothing wraps silently: an operation whose exact result does not fit a signed
 // 128-bit integer reports it, and the caller sets AGG_OVERFLOW.  Division (/, //, %) is here too: a signed 128-by-128-bit divide
-// by magnitudes with explicit paths, never the compiler's expansion of `__int128 /`; a zero divisor overflows the row.
+// by magnitudes with explicit paths, never the compiler's expansion of `__int128 /`; a zero divisor overflows the row.  So are the
+// conversions between the classes (include/orcgpu.h: CONVERSIONS) and the mixed interpreter that runs a program holding values of
+// both kinds (tests/hostcheck/conv_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -320,6 +322,307 @@ AGG_HD bool agg_cmp_of(uint32_t cmp, bool lt, bool eq, bool gt) {
   return cmp == 0 ? eq : cmp == 1 ? !eq : cmp == 2 ? lt : cmp == 3 ? (lt || eq) : cmp == 4 ? gt : (gt || eq);
 }
 
+// ---- conversions (include/orcgpu.h: CONVERSIONS): between the classes, and rounding inside them.  Integer code throughout but for
+// the one division of the fast path and the four IEEE roundings; no table, no indexed array.
+
+AGG_HD int agg_bits_u128(agg_u128 v) {
+  const unsigned long long hi = (unsigned long long)(v >> 64), lo = (unsigned long long)v;
+  return hi ? 128 - __builtin_clzll(hi) : lo ? 64 - __builtin_clzll(lo) : 0;
+}
+AGG_HD agg_i128 agg_pow10_38() { return agg_i128_of(0x098a224000000000ull, 0x4b3b4ca85a86c47aull); }
+
+// The double nearest the exact rational v / 10^k (`pow` = 10^k, k = 0 .. 38), ties to even: Python's float(Fraction(v, 10**k)).
+// |v| < 2^53 and k <= 22: both are exact doubles, and one IEEE division of them is correctly rounded.  Otherwise the magnitudes
+// are divided (agg_udivmod128), the remainder is extended bit by bit until the quotient has 56 significant bits -- where the
+// quotient is 0 the remainder is first moved up by the zero bits that can only follow --, what is left is the sticky bit, and the
+// rounding to 53 bits is done by hand.  The result lies in 10^-38 .. 2^127: never a subnormal, never an infinity.
+AGG_HD double agg_to_f64(agg_i128 v, uint32_t k, agg_i128 pow) {
+  if (v == 0) return 0.0;
+  const bool neg = v < 0;
+  const agg_u128 m = neg ? (agg_u128)0 - (agg_u128)v : (agg_u128)v, d = (agg_u128)pow;
+  if (m < ((agg_u128)1 << 53) && k <= 22) {
+    // (10^22 = 5^22 * 2^22 passes 64 bits: its two words are exact doubles, and so is their sum)
+    const double dd = agg_f64_add(agg_f64_mul((double)(unsigned long long)(d >> 64), 18446744073709551616.0), (double)(unsigned long long)d);
+    const double r = agg_f64_div((double)(unsigned long long)m, dd);
+    return neg ? -r : r;
+  }
+  agg_u128 r = 0;
+  agg_u128 q = agg_udivmod128(m, d, &r);
+  int e = 0;  // the value is (q + r / d) * 2^e
+  if (q == 0) {
+    const int s = agg_bits_u128(d) - agg_bits_u128(m) - 1;  // (m < d: m << s has a bit less than d, it stays below it)
+    if (s > 0) {
+      r <<= s;
+      e = -s;
+    }
+  }
+  while (q < ((agg_u128)1 << 55)) {  // (r < d < 2^127: r << 1 fits)
+    r <<= 1;
+    const bool bit = r >= d;
+    if (bit) r -= d;
+    q = (q << 1) | (bit ? 1u : 0u);
+    e--;
+  }
+  const int drop = agg_bits_u128(q) - 53;  // (at least 3)
+  unsigned long long mant = (unsigned long long)(q >> drop);
+  const agg_u128 rest = q & (((agg_u128)1 << drop) - 1), half = (agg_u128)1 << (drop - 1);
+  if (rest > half || (rest == half && (r != 0 || (mant & 1)))) mant++;
+  int ex = drop + e;  // mant * 2^ex
+  if (mant >> 53) {
+    mant >>= 1;
+    ex++;
+  }
+  return agg_f64_of_bits(((unsigned long long)(1023 + 52 + ex) << 52) | (mant & ((1ull << 52) - 1)) | (neg ? 1ull << 63 : 0ull));
+}
+
+// round(x * 10^t), half away from zero, of the double's exact value m * 2^e (`pow` = 10^t): m (53 bits) times 10^t (at most 127)
+// is held in three 64-bit words and shifted.  false, and *r = 0: NaN, an infinity, or a magnitude of 10^38 or more.  -0.0 gives 0.
+AGG_HD bool agg_f64_to_dec(double x, agg_i128 pow, agg_i128* r) {
+  *r = 0;
+  const unsigned long long b = agg_bits_of_f64(x);
+  const bool neg = (b >> 63) != 0;
+  const uint32_t be = (uint32_t)(b >> 52) & 0x7ffu;
+  unsigned long long m = b & ((1ull << 52) - 1);
+  if (be == 0x7ffu) return false;
+  int e = -1074;
+  if (be != 0) {
+    m |= 1ull << 52;
+    e = (int)be - 1075;
+  }
+  if (m == 0) return true;
+  const agg_u128 p = (agg_u128)pow;
+  const agg_u128 lo = (agg_u128)(unsigned long long)p * m, hi = (agg_u128)(unsigned long long)(p >> 64) * m + (unsigned long long)(lo >> 64);
+  unsigned long long w0 = (unsigned long long)lo, w1 = (unsigned long long)hi, w2 = (unsigned long long)(hi >> 64);
+  agg_u128 q;
+  if (e >= 0) {
+    q = ((agg_u128)w1 << 64) | w0;
+    if (w2 != 0 || e > 127 || agg_bits_u128(q) + e > 127) return false;  // (2^127 or more)
+    q <<= e;
+  } else {
+    int sh = -e - 1;            // down to the bit behind the point: 0 .. 1073
+    if (sh > 191) return true;  // (the product is below 2^180: less than a half)
+    if (sh >= 128) {
+      w0 = w2;
+      w1 = 0;
+      w2 = 0;
+      sh -= 128;
+    } else if (sh >= 64) {
+      w0 = w1;
+      w1 = w2;
+      w2 = 0;
+      sh -= 64;
+    }
+    if (sh) {
+      w0 = (w0 >> sh) | (w1 << (64 - sh));
+      w1 = (w1 >> sh) | (w2 << (64 - sh));
+      w2 >>= sh;
+    }
+    if (w2 != 0) return false;  // (2^127 or more)
+    q = ((agg_u128)w1 << 64) | w0;
+    q = (q >> 1) + (unsigned long long)(q & 1);  // the bit behind the point is a half or more: away from zero
+  }
+  if (q >= (agg_u128)agg_pow10_38()) return false;
+  *r = (agg_i128)(neg ? (agg_u128)0 - q : q);
+  return true;
+}
+// x truncated toward zero.  false, and *r = 0: NaN, an infinity, or a result outside int64.
+AGG_HD bool agg_f64_to_i64(double x, agg_i128* r) {
+  *r = 0;
+  if (!(x >= -9223372036854775808.0 && x < 9223372036854775808.0)) return false;
+  *r = (agg_i128)(long long)x;
+  return true;
+}
+// v / 10^k (`pow` = 10^k, k >= 1) to an integer by `mode` (AGG_ROUND_*): the magnitudes divided, then the mode, then the sign
+AGG_HD agg_i128 agg_rescale(agg_i128 v, agg_i128 pow, uint32_t mode) {
+  const bool neg = v < 0;
+  const agg_u128 m = neg ? (agg_u128)0 - (agg_u128)v : (agg_u128)v, d = (agg_u128)pow;
+  agg_u128 rem = 0;
+  agg_u128 q = agg_udivmod128(m, d, &rem);
+  const bool up = mode == AGG_ROUND_HALF_AWAY ? rem >= d - rem : mode == AGG_ROUND_FLOOR ? (neg && rem != 0) : mode == AGG_ROUND_CEIL ? (!neg && rem != 0) : false;
+  if (up) q++;
+  return (agg_i128)(neg ? (agg_u128)0 - q : q);
+}
+// C's round (half away from zero), floor, ceil, trunc: one IEEE operation each
+AGG_HD double agg_f64_round(double x, uint32_t mode) {
+  return mode == AGG_ROUND_HALF_AWAY ? __builtin_round(x) : mode == AGG_ROUND_FLOOR ? __builtin_floor(x) : mode == AGG_ROUND_CEIL ? __builtin_ceil(x) : __builtin_trunc(x);
+}
+
+// The MIXED interpreter: a program with conversions (agg_program.h: AX_TO_F64 .. AX_F64_ROUND) on one row.  A slot is 128 bits; an
+// integer or an unscaled Decimal fills it, a double lives as its bits in the low word.  It is the interpreter with the divide and
+// the conditionals (below) and more: NULL and overflow per slot (AggSlotBits), no jump, no indexed private array -- no scratch.  In
+// a program with conversions an arithmetic op, AX_NEG, AX_ABS and AX_CMP carry kAggOpF64 where their operands are doubles; the kernels'
+// fourth instantiation runs EVERY program of its launch here, so a program without conversions says by `f64cls` what all its
+// operands are, and its mark and tail (kAggCondMark) are skipped as its own interpreter skips them.  A condition is the integer 1 / 0.
+// Row: `valid`, `load_int`, `load_dec` and `load_f64`.  *out: the root's slot -- of the FLOAT class: the bits of the double.
+template <typename Row>
+AGG_HD int agg_expr_eval_mixed(const AggExprOp* prog, uint32_t n, const Row& row, bool f64cls, agg_i128* out) {
+  AggSlots<agg_i128> s = {0, 0, 0, 0};
+  AggSlotBits m = {0, 0};
+  const bool marked = agg_cond_marked(prog, n), conv = agg_conv_marked(prog, n);
+  const uint32_t tail = conv ? kAggConvTail : marked && f64cls ? kAggCondTailF64 : 0;
+  n = n >= 1 + tail ? n - tail : marked ? 1 : n;
+  for (uint32_t k = marked ? 1 : 0; k < n; k++) {
+    const AggExprOp op = prog[k];
+    const bool isf = conv ? (op.hi & kAggOpF64) != 0 : f64cls;
+    agg_i128 r = 0;
+    bool ok = true;
+    switch (op.op) {
+      case AX_GATE:
+        if (!row.valid(op.col)) return AGG_ROW_NULL;
+        break;
+      case AX_PUSH_INT:
+      case AX_PUSH_DEC:
+      case AX_PUSH_F64: {
+        const bool v = !op.lo || row.valid(op.col);
+        if (v) r = op.op == AX_PUSH_INT ? row.load_int(op.col) : op.op == AX_PUSH_DEC ? row.load_dec(op.col) : (agg_i128)agg_bits_of_f64(row.load_f64(op.col));
+        s.push(r);
+        m.push(!v, false);
+        break;
+      }
+      case AX_PUSH_LIT:
+        s.push(agg_i128_of(op.lo, op.hi));
+        m.push(false, false);
+        break;
+      case AX_PUSH_NULL:
+        s.push(0);
+        m.push(true, false);
+        break;
+      case AX_ADD:
+      case AX_SUB:
+      case AX_RSUB:
+      case AX_MUL:
+      case AX_DIV:
+      case AX_FLOOR_DIV:
+      case AX_MOD: {
+        if (isf) {
+          const double a = agg_f64_of_bits((unsigned long long)s.s1), b = agg_f64_of_bits((unsigned long long)s.s0);
+          const double f = op.op == AX_ADD ? agg_f64_add(a, b) : op.op == AX_SUB ? agg_f64_add(a, -b) : op.op == AX_RSUB ? agg_f64_add(b, -a)
+                         : op.op == AX_MUL ? agg_f64_mul(a, b) : agg_f64_div(a, b);
+          r = (agg_i128)agg_bits_of_f64(f);
+          ok = op.op <= AX_DIV;  // (// and % take no doubles: the compiler emits none)
+        } else if (op.op == AX_ADD) {
+          ok = agg_add_checked(s.s1, s.s0, &r);
+        } else if (op.op == AX_SUB) {
+          ok = agg_sub_checked(s.s1, s.s0, &r);
+        } else if (op.op == AX_RSUB) {
+          ok = agg_sub_checked(s.s0, s.s1, &r);
+        } else if (op.op == AX_MUL) {
+          ok = agg_mul_checked(s.s1, s.s0, &r);
+        } else {
+          agg_i128 a = s.s1;
+          if (op.op == AX_DIV && op.col != 0) ok = agg_mul_checked(a, agg_i128_of(op.lo, op.hi & ~kAggOpF64), &a);
+          ok &= agg_div_checked(a, s.s0, op.op - AX_DIV, &r);
+        }
+        const bool nul = m.n(0) || m.n(1);
+        const bool ovf = !nul && (m.o(0) || m.o(1) || !ok);
+        s.merge(nul || ovf ? (agg_i128)0 : r);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_NEG:
+      case AX_SCALE10:
+      case AX_DATE_PART:
+      case AX_ABS:
+      case AX_TO_F64:
+      case AX_F64_TO_DEC:
+      case AX_F64_TO_INT:
+      case AX_RESCALE:
+      case AX_FIT_I64:
+      case AX_F64_ROUND: {
+        const unsigned long long bits = (unsigned long long)s.s0;
+        const agg_i128 pow = agg_i128_of(op.lo, op.hi & ~kAggOpF64);
+        if (op.op == AX_NEG) {
+          if (isf) r = (agg_i128)(bits ^ (1ull << 63));
+          else ok = agg_neg_checked(s.s0, &r);
+        } else if (op.op == AX_SCALE10) {
+          ok = agg_mul_checked(s.s0, pow, &r);
+        } else if (op.op == AX_ABS) {
+          r = s.s0;
+          if (isf) r = (agg_i128)(bits & 0x7fffffffffffffffull);
+          else if (r < 0) ok = agg_neg_checked(s.s0, &r);
+        } else if (op.op == AX_DATE_PART) {
+          const long long d = (long long)s.s0;
+          ok = s.s0 == (agg_i128)(int32_t)d;
+          r = (agg_i128)agg_date_part((int32_t)d, op.col);
+        } else if (op.op == AX_TO_F64) {
+          r = (agg_i128)agg_bits_of_f64(agg_to_f64(s.s0, op.col, pow));
+        } else if (op.op == AX_F64_TO_DEC) {
+          ok = agg_f64_to_dec(agg_f64_of_bits(bits), pow, &r);
+        } else if (op.op == AX_F64_TO_INT) {
+          ok = agg_f64_to_i64(agg_f64_of_bits(bits), &r);
+        } else if (op.op == AX_RESCALE) {
+          r = agg_rescale(s.s0, pow, (op.col >> 8) & 3u);
+        } else if (op.op == AX_FIT_I64) {
+          r = s.s0;
+          ok = r == (agg_i128)(long long)r;
+        } else {
+          r = (agg_i128)agg_bits_of_f64(agg_f64_round(agg_f64_of_bits(bits), op.col & 3u));
+        }
+        const bool nul = m.n(0);
+        const bool ovf = !nul && (m.o(0) || !ok);
+        s.s0 = nul || ovf ? (agg_i128)0 : r;
+        m.set(nul, ovf);
+        break;
+      }
+      case AX_CMP: {
+        const bool nul = m.n(0) || m.n(1);
+        const bool ovf = !nul && (m.o(0) || m.o(1));
+        bool lt = s.s1 < s.s0, eq = s.s1 == s.s0, gt = s.s1 > s.s0;
+        if (isf) {
+          const double a = agg_f64_of_bits((unsigned long long)s.s1), b = agg_f64_of_bits((unsigned long long)s.s0);
+          lt = a < b;
+          eq = a == b;
+          gt = a > b;
+        }
+        const bool t = !nul && !ovf && agg_cmp_of(op.col, lt, eq, gt);
+        s.merge(t ? 1 : 0);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_IS_NULL:
+        s.s0 = m.n(0) ? 1 : 0;
+        m.set(false, m.o(0));
+        break;
+      case AX_AND:
+      case AX_OR: {
+        bool v, nul, ovf;
+        agg_kleene(op.op == AX_OR, s.s1 != 0, m.n(1), m.o(1), s.s0 != 0, m.n(0), m.o(0), &v, &nul, &ovf);
+        s.merge(v && !nul && !ovf ? 1 : 0);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_NOT:
+        s.s0 = !m.n(0) && !m.o(0) && s.s0 == 0 ? 1 : 0;
+        break;
+      case AX_IF: {
+        const bool take = !m.n(2) && !m.o(2) && s.s2 != 0;
+        const uint32_t at = take != (op.col != 0) ? 1u : 0u;
+        const bool co = m.o(2);
+        const bool nul = !co && m.n(at), ovf = co || m.o(at);
+        r = nul || ovf ? (agg_i128)0 : (at ? s.s1 : s.s0);
+        s.merge3(r);
+        m.merge3(nul, ovf);
+        break;
+      }
+      case AX_COALESCE: {
+        const bool b = m.n(1);
+        r = b ? s.s0 : s.s1;
+        const bool nul = b ? m.n(0) : false, ovf = b ? m.o(0) : m.o(1);
+        s.merge(r);
+        m.merge(nul, ovf);
+        break;
+      }
+      case AX_SWAP:
+        s.swap();
+        m.swap();
+        break;
+      default: break;
+    }
+  }
+  *out = s.s0;
+  return m.n(0) ? AGG_ROW_NULL : m.o(0) ? AGG_ROW_OVERFLOW : AGG_ROW_VALUE;
+}
+
 // A program WITH conditionals (agg_program.h: AX_CMP .. AX_PUSH_NULL) of the INT / DEC class on one row: no gates; every slot has
 // its NULL and overflow bits, arithmetic hands them on (NULL first, then overflow), AX_IF and AX_COALESCE take the chosen slot's, and
 // only the root's decide the row -- an untaken branch neither gates the row nor counts as an overflow.  Both branches are
@@ -468,8 +771,12 @@ AGG_HD int agg_expr_eval_i128_cond(const AggExprOp* prog, uint32_t n, const Row&
 // were, and still never hand out a value for such a program: it begins with kAggCondMark, an AX_MOD on the empty, all-zero slots,
 // which here is a division the instantiation does not have (DIV = false) or a division by zero (DIV = true) -- `ok` is sticky, the row
 // overflows.  (A check of their own in these interpreters was tried in three forms; each cost registers: INTEGRATION.md 6p.)
-template <bool DIV, bool COND = false, typename Row>
+// CONV: the mixed interpreter, above -- the fourth instantiation, launched for the programs that hold a conversion
+// (agg_ops_hold_conversion); the three others are what they were, and a program with conversions overflows the row in each of them
+// (agg_program.h: kAggConvMarkCol).
+template <bool DIV, bool COND = false, bool CONV = false, typename Row>
 AGG_HD int agg_expr_eval_i128_as(const AggExprOp* prog, uint32_t n, const Row& row, agg_i128* out) {
+  if constexpr (CONV) return agg_expr_eval_mixed(prog, n, row, false, out);
   if constexpr (COND) return agg_expr_eval_i128_cond<DIV>(prog, n, row, out);
   AggSlots<agg_i128> s = {0, 0, 0, 0};
   bool ok = true;
@@ -647,8 +954,16 @@ AGG_HD int agg_expr_eval_f64_cond(const AggExprOp* prog, uint32_t n, const Row& 
 
 // (COND as above.  Without it a program with conditionals gives NaN, as a division gives NaN without DIV: the mark is no op of this
 // class, but such a program of this class ENDS with `push NaN, add` -- kAggCondTailF64 --, which only these interpreters run.)
-template <bool DIV, bool COND = false, typename Row>
+// (CONV as above: the mixed interpreter, whose root slot holds the double's bits.  There, and only there, a program of this class
+// can overflow a row: a conversion to an integer or a Decimal inside it.)
+template <bool DIV, bool COND = false, bool CONV = false, typename Row>
 AGG_HD int agg_expr_eval_f64_as(const AggExprOp* prog, uint32_t n, const Row& row, double* out) {
+  if constexpr (CONV) {
+    agg_i128 v = 0;
+    const int rc = agg_expr_eval_mixed(prog, n, row, true, &v);
+    *out = agg_f64_of_bits((unsigned long long)v);
+    return rc;
+  }
   if constexpr (COND) return agg_expr_eval_f64_cond<DIV>(prog, n, row, out);
   AggSlots<double> s = {0.0, 0.0, 0.0, 0.0};
   for (uint32_t k = 0; k < n; k++) {

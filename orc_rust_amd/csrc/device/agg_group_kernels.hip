@@ -230,7 +230,7 @@ group_number_kernel(GroupKeys keys, KeptRows rows, const GroupSlot* table, Group
 // grid.y at once; EXPR = true is agg_group_expr_partial_kernel, the other way round, launched only when the list holds such an
 // instruction -- the interpreter's registers are not the plain kinds'.  ops: the op table of the programs, EXPR only.  DIV: the
 // interpreter with the divide, agg_group_expr_div_partial_kernel, launched in its place when a program holds a division.)
-template <bool EXPR, bool DIV = false, bool COND = false>
+template <bool EXPR, bool DIV = false, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* plane,
                                                        const uint32_t* slot_group, const GroupControl* ctl, AggPartial* partials, AggAcc (*acc_s)[kGroupMax]) {
   const FilterCol* const cols = rows.cols;
@@ -266,7 +266,7 @@ __device__ __forceinline__ void agg_group_partial_body(const AggInsn* insns, con
     // (a row its instruction's condition does not pass keeps the empty contribution and its place in the fold below)
     const unsigned long long pass_m = blocked ? 0ull : cond ? cond[w] : ~0ull;  // (the word's rows that pass: one scalar load a word)
     if (kept && ((pass_m >> lane) & 1)) {
-      if constexpr (EXPR) agg_expr_row<DIV, COND>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
+      if constexpr (EXPR) agg_expr_row<DIV, COND, CONV>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, v);
       else if (kind == AK_COUNT_ROWS) v.w0 = 1;
       else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, v);
     }
@@ -346,6 +346,13 @@ agg_group_expr_cond_partial_kernel(const AggInsn* insns, const AggExprOp* ops, K
                                    AggPartial* partials) {
   __shared__ AggAcc acc_s[4][kGroupMax];
   agg_group_partial_body<true, true, true>(insns, ops, rows, plane, slot_group, ctl, partials, acc_s);
+}
+// (the mixed interpreter: launched when a program of the list holds a conversion)
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_expr_conv_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* plane, const uint32_t* slot_group, const GroupControl* ctl,
+                                   AggPartial* partials) {
+  __shared__ AggAcc acc_s[4][kGroupMax];
+  agg_group_partial_body<true, true, true, true>(insns, ops, rows, plane, slot_group, ctl, partials, acc_s);
 }
 
 // grid (kGroupMax, instructions): block (g, k) folds the n_blocks records of group g under instruction k -> out[k][g]; the blocks

@@ -303,7 +303,7 @@ group_wide_segments_kernel(const uint32_t* keys, uint32_t cap, uint64_t n_in, co
 // every row's lane stay those of the fold rule.  COUNT_ROWS under a condition counts the passing rows, lane by lane.
 // (The body of two kernels, as agg_group_partial_body is: EXPR = false takes the plain kinds, EXPR = true the AK_EXPR_* rows of grid.y;
 // DIV: the interpreter with the divide, agg_group_wide_expr_div_kernel, launched in its place when a program holds a division.)
-template <bool EXPR, bool DIV = false, bool COND = false>
+template <bool EXPR, bool DIV = false, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, const uint32_t* order_rows, const uint32_t* seg,
                                                     const GroupControl* ctl, uint32_t cap, AggPartial* out) {
   const FilterCol* const cols = rows.cols;
@@ -334,7 +334,7 @@ __device__ __forceinline__ void agg_group_wide_body(const AggInsn* insns, const 
             a.w0++;
             continue;
           }
-          if constexpr (EXPR) agg_expr_row<DIV, COND>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, a);
+          if constexpr (EXPR) agg_expr_row<DIV, COND, CONV>(kind, ops + in.col, in.col2, cols, filter_row(rows, j), W, a);
           else agg_row(kind, is_max, in, c, c2, filter_row(rows, j), W, a);
         }
         agg_wave_fold(kind, is_max, a);
@@ -362,4 +362,10 @@ extern "C" __global__ void __launch_bounds__(256)
 agg_group_wide_expr_cond_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* order_rows, const uint32_t* seg, const GroupControl* ctl,
                                 uint32_t cap, AggPartial* out) {
   agg_group_wide_body<true, true, true>(insns, ops, rows, order_rows, seg, ctl, cap, out);
+}
+// (the mixed interpreter: launched when a program of the list holds a conversion)
+extern "C" __global__ void __launch_bounds__(256)
+agg_group_wide_expr_conv_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, const uint32_t* order_rows, const uint32_t* seg, const GroupControl* ctl,
+                                uint32_t cap, AggPartial* out) {
+  agg_group_wide_body<true, true, true, true>(insns, ops, rows, order_rows, seg, ctl, cap, out);
 }

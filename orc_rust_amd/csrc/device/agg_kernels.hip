@@ -215,17 +215,20 @@ struct AggExprRow {
 #pragma clang fp contract(off)  // (the sum's addition is an operation of its own, never fused with the expression's last multiply)
 // One kept row into an accumulator of an AK_EXPR_* instruction whose program is prog[0 .. n): a row with a NULL operand adds
 // nothing; a row whose value left 128 bits counts, sets the sticky flag and adds nothing
-template <bool DIV, bool COND = false>
+// (CONV: the mixed interpreter -- conversions, include/orcgpu.h: CONVERSIONS --, in which a row of the FLOAT class can overflow too)
+template <bool DIV, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void agg_expr_row(uint32_t kind, const AggExprOp* prog, uint32_t n, const FilterCol* cols, const FilterRow& r, uint32_t W, AggAcc& a) {
   if (!r.live) return;
   const AggExprRow row = {cols, r, W};
   if (kind == AK_EXPR_F64) {
     double v;
-    if (agg_expr_eval_f64_as<DIV, COND>(prog, n, row, &v) == AGG_ROW_NULL) return;
-    a.f += v;
+    const int rc = agg_expr_eval_f64_as<DIV, COND, CONV>(prog, n, row, &v);
+    if (rc == AGG_ROW_NULL) return;
+    if (CONV && rc == AGG_ROW_OVERFLOW) a.flags |= AGG_OVERFLOW;
+    else a.f += v;
   } else {
     agg_i128 v;
-    const int rc = agg_expr_eval_i128_as<DIV, COND>(prog, n, row, &v);
+    const int rc = agg_expr_eval_i128_as<DIV, COND, CONV>(prog, n, row, &v);
     if (rc == AGG_ROW_NULL) return;
     if (rc == AGG_ROW_OVERFLOW) a.flags |= AGG_OVERFLOW;
     else agg_add_i128(a, (unsigned long long)v, (unsigned long long)((agg_u128)v >> 64));
@@ -285,7 +288,7 @@ agg_cond_eval_kernel(const FilterInsn* prog, uint32_t n_insn, const AggCondSpan*
 // Resource usage (gfx950): agg_expr_partial_kernel 73 VGPRs, 106 SGPRs, 6 waves / SIMD; agg_expr_div_partial_kernel 83 VGPRs, 106 SGPRs,
 // 5 waves / SIMD -- the occupancy step the divide costs, paid only by a list that divides; both 192 bytes of LDS, no scratch
 // (INTEGRATION.md 6o).)
-template <bool EXPR, bool DIV = false, bool COND = false>
+template <bool EXPR, bool DIV = false, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void agg_partial_body(const AggInsn* insns, const AggExprOp* ops, const KeptRows& rows, AggPartial* partials, AggAcc* fold_s) {
   const AggInsn in = insns[blockIdx.y];
   if (agg_is_expr(in.kind) != EXPR) return;  // (uniform over the block)
@@ -306,7 +309,7 @@ __device__ __forceinline__ void agg_partial_body(const AggInsn* insns, const Agg
     }
     if (!((m >> lane) & 1)) continue;
     const FilterRow r = filter_row(rows, w * 64 + lane);
-    if constexpr (EXPR) agg_expr_row<DIV, COND>(kind, ops + in.col, in.col2, rows.cols, r, rows.W, a);
+    if constexpr (EXPR) agg_expr_row<DIV, COND, CONV>(kind, ops + in.col, in.col2, rows.cols, r, rows.W, a);
     else agg_row(kind, is_max, in, c, c2, r, rows.W, a);
   }
   agg_block_fold(kind, is_max, a, fold_s);
@@ -329,6 +332,12 @@ extern "C" __global__ void __launch_bounds__(256) agg_expr_div_partial_kernel(co
 extern "C" __global__ void __launch_bounds__(256) agg_expr_cond_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, AggPartial* partials) {
   __shared__ AggAcc fold_s[4];
   agg_partial_body<true, true, true>(insns, ops, rows, partials, fold_s);
+}
+// ... and the mixed interpreter (include/orcgpu.h: CONVERSIONS), launched in their place when a program of the list holds a
+// conversion (agg_ops_hold_conversion): it runs every program of the list.  Resources: INTEGRATION.md 6q.
+extern "C" __global__ void __launch_bounds__(256) agg_expr_conv_partial_kernel(const AggInsn* insns, const AggExprOp* ops, KeptRows rows, AggPartial* partials) {
+  __shared__ AggAcc fold_s[4];
+  agg_partial_body<true, true, true, true>(insns, ops, rows, partials, fold_s);
 }
 
 // What a final kernel's block makes of n_blocks records that lie `stride` records apart: thread t folds records t, t + 256, ... in

@@ -70,14 +70,29 @@ enum {
   AX_COALESCE = 22,  // the two top slots a (below) and b (top) -> a unless a is NULL, then b
   AX_ABS = 23,       // the top slot -> its magnitude; -2^127 overflows; a double: the sign bit cleared
   AX_PUSH_NULL = 24, // a slot whose NULL bit is set
-  AX_N = 25
+  // Conversions (include/orcgpu.h: CONVERSIONS).  A program that holds one may hold values of BOTH kinds: a slot is 128 bits, and a
+  // double lives as its bits in the slot's low word.  Only the mixed interpreter (agg_expr_eval.h: agg_expr_eval_mixed) runs them; such a
+  // program is laid out like one with conditionals -- no gates, nullable pushes, NULL and overflow per slot -- behind a mark and in
+  // front of a tail that make every other interpreter overflow the row or give NaN (kAggConvMarkCol, below).  Each takes the top slot.
+  AX_TO_F64 = 25,      // an integer / the unscaled value of a Decimal at scale k -> the double nearest value / 10^k, ties to even
+                       // (k in `col`, 10^k in lo / hi); never an overflow
+  AX_F64_TO_DEC = 26,  // a double -> round(x * 10^t), half away from zero, computed exactly (t in `col`, 10^t in lo / hi); NaN, an
+                       // infinity and a magnitude of 10^38 or more overflow
+  AX_F64_TO_INT = 27,  // a double -> truncated toward zero; NaN, an infinity and a result outside int64 overflow
+  AX_RESCALE = 28,     // an unscaled Decimal -> itself divided by 10^k (k in the low byte of `col`, 10^k in lo / hi), rounded by the
+                       // mode in bits 8 .. 9 of `col` (AGG_ROUND_*): `col` has the room, no new field; never an overflow
+  AX_FIT_I64 = 29,     // the value unchanged; outside int64: overflow
+  AX_F64_ROUND = 30,   // a double -> round / floor / ceil / trunc of it (`col`: AGG_ROUND_*), still a double; NaN and infinities pass
+  AX_N = 31
 };
+// The rounding modes of AX_RESCALE and AX_F64_ROUND
+enum { AGG_ROUND_HALF_AWAY = 0, AGG_ROUND_FLOOR = 1, AGG_ROUND_CEIL = 2, AGG_ROUND_TRUNC = 3 };
 // The calendar fields of AX_DATE_PART (include/orcgpu.h: ORCGPU_DATE_PART_*), proleptic Gregorian, astronomical year numbering
 enum { AX_PART_YEAR = 0, AX_PART_QUARTER = 1, AX_PART_MONTH = 2, AX_PART_DAY = 3, AX_PART_DAY_OF_WEEK = 4, AX_PART_DAY_OF_YEAR = 5, AX_PART_N = 6 };
 constexpr uint32_t kAggExprSlots = 4, kAggExprMaxNodes = 32;
 struct AggExprOp {
   uint32_t op;   // AX_*
-  uint32_t col;  // index into the FilterCol table; AX_SCALE10, AX_DIV: k; AX_DATE_PART: AX_PART_*; AX_CMP: the comparison; AX_IF: the slots
+  uint32_t col;  // index into the FilterCol table; AX_SCALE10, AX_DIV, AX_TO_F64 ..: k; AX_DATE_PART: AX_PART_*; AX_CMP: the comparison; AX_IF: the slots
   unsigned long long lo, hi;  // (AX_PUSH_INT / _DEC / _F64: lo = 1 in a program with conditionals: the push is nullable)
 };
 
@@ -92,7 +107,7 @@ inline bool agg_ops_hold_division(const AggExprOp* ops, size_t n) {
 // ... or a conditional?  (The same question for the third instantiation, the one with the divide AND the conditionals.)
 inline bool agg_ops_hold_conditional(const AggExprOp* ops, size_t n) {
   for (size_t k = 0; k < n; k++)
-    if (ops[k].op >= AX_CMP && ops[k].op < AX_N) return true;
+    if (ops[k].op >= AX_CMP && ops[k].op <= AX_PUSH_NULL) return true;
   return false;
 }
 // AX_IF's `col`: which branch was evaluated first
@@ -106,6 +121,27 @@ constexpr uint32_t kAggIfThenFirst = 0, kAggIfElseFirst = 1;
 constexpr uint32_t kAggCondMark = AX_MOD, kAggCondTailF64 = 2;
 constexpr unsigned long long kAggCondNaNBits = 0x7ff8000000000000ull;
 constexpr bool agg_cond_marked(const AggExprOp* prog, uint32_t n) { return n != 0 && prog[0].op == kAggCondMark; }
+// A program with conversions (AX_TO_F64 .. AX_F64_ROUND) gets the same protection, from the interpreters with the conditionals too
+// -- they skip the mark -- and again at no cost to any of them: existing ops.  Its mark is the conditionals' with kAggConvMarkCol in
+// `col` (no other AX_MOD has a `col`), and it ENDS with kAggConvTail ops that only the interpreters WITHOUT the conversions run:
+//   a root of the INT / DEC class   push 0, push 0, AX_MOD (a slot that overflowed), AX_SWAP, AX_COALESCE: the overflowed slot is
+//                                   not NULL, so it is the result -- the row overflows whatever the ops they know left on top;
+//   a root of the FLOAT class       push NaN, AX_SWAP, AX_COALESCE (the interpreter with the conditionals: NaN, not NULL), then
+//                                   kAggCondTailF64's push NaN, AX_ADD, which that interpreter strips and the plain one runs: NaN.
+// The mixed interpreter skips the mark and the tail.
+// In such a program an arithmetic op, AX_NEG, AX_ABS and AX_CMP say which kind their operands are: kAggOpF64 in `hi` -- the one bit
+// no power of ten reaches (10^38 < 2^127) and no such op used.  (The alternative, float twins of those eleven ops, was not taken:
+// the twins would double the interpreter's switch, where the flag is one test on an op already loaded.)
+constexpr uint32_t kAggConvMarkCol = 1, kAggConvTail = 5;
+constexpr unsigned long long kAggOpF64 = 1ull << 63;
+constexpr bool agg_conv_marked(const AggExprOp* prog, uint32_t n) { return agg_cond_marked(prog, n) && prog[0].col == kAggConvMarkCol; }
+// ... or a conversion?  (The fourth instantiation: the mixed interpreter.)  A program compiled with per-node classes is one even
+// where folding left it no conversion op: its mark says so.
+inline bool agg_ops_hold_conversion(const AggExprOp* ops, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if ((ops[k].op >= AX_TO_F64 && ops[k].op < AX_N) || (ops[k].op == kAggCondMark && ops[k].col == kAggConvMarkCol)) return true;
+  return false;
+}
 
 struct AggInsn {
   uint32_t kind;     // AK_*

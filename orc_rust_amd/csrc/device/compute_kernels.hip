@@ -70,7 +70,7 @@ struct ComputeExprRow {
 // expected, none used), occupancy 8 waves / SIMD
 // (The body of two kernels: DIV = false is compute_columns_kernel; DIV = true, the interpreter with the divide, is
 // compute_columns_div_kernel, launched in its place when a program of the plan holds a division.)
-template <bool DIV, bool COND = false>
+template <bool DIV, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void compute_columns_body(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches, uint32_t B, uint32_t W,
                                                      const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
   const ComputeJob job = jobs[blockIdx.y];
@@ -93,9 +93,9 @@ __device__ __forceinline__ void compute_columns_body(const ComputeJob* jobs, con
   if (live && sane) {
     const ComputeExprRow x{cols, filter_row_of(row, B), W};
     if (job.kind == CK_F64) {
-      state = agg_expr_eval_f64_as<DIV, COND>(job.prog, job.n_ops, x, &fv);
+      state = agg_expr_eval_f64_as<DIV, COND, CONV>(job.prog, job.n_ops, x, &fv);
     } else {
-      state = agg_expr_eval_i128_as<DIV, COND>(job.prog, job.n_ops, x, &iv);
+      state = agg_expr_eval_i128_as<DIV, COND, CONV>(job.prog, job.n_ops, x, &iv);
       if (state == AGG_ROW_VALUE) {
         if (job.kind == CK_INT64) {
           if (iv != (agg_i128)(long long)iv) state = AGG_ROW_OVERFLOW;
@@ -156,4 +156,9 @@ __global__ __launch_bounds__(256) void compute_columns_div_kernel(const ComputeJ
 __global__ __launch_bounds__(256) void compute_columns_cond_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
                                                                    uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
   compute_columns_body<true, true>(jobs, cols, n_cols, n_rows, n_batches, B, W, segs, n_segs, count_all);
+}
+// (the mixed interpreter: launched when a program of the plan holds a conversion)
+__global__ __launch_bounds__(256) void compute_columns_conv_kernel(const ComputeJob* jobs, const FilterCol* cols, uint32_t n_cols, uint64_t n_rows, uint32_t n_batches,
+                                                                   uint32_t B, uint32_t W, const SelBatch* segs, uint32_t n_segs, uint32_t count_all) {
+  compute_columns_body<true, true, true>(jobs, cols, n_cols, n_rows, n_batches, B, W, segs, n_segs, count_all);
 }

@@ -313,7 +313,7 @@ struct FilterExprRow {
 // launched in its place when a leaf of the call holds a division.
 // Resource usage (gfx950): filter_expr_kernel 71 VGPRs, 106 SGPRs, 7 waves / SIMD; filter_expr_div_kernel 78 VGPRs, 106 SGPRs, 6 waves /
 // SIMD -- the occupancy step the divide costs, paid only by a call that divides; both 16 bytes of LDS, no scratch.)
-template <bool DIV, bool COND = false>
+template <bool DIV, bool COND = false, bool CONV = false>
 __device__ __forceinline__ void filter_expr_body(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
                                                  const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes,
                                                  uint32_t n_planes, unsigned long long* overflow, uint32_t* over_s) {
@@ -333,14 +333,15 @@ __device__ __forceinline__ void filter_expr_body(const FilterInsn* prog, uint32_
       int sl, sr;
       if (e.cls == FXC_FLOAT) {
         double a = 0.0, b = 0.0;
-        sl = agg_expr_eval_f64_as<DIV, COND>(e.lhs, e.n_lhs, row, &a);
-        sr = agg_expr_eval_f64_as<DIV, COND>(e.rhs, e.n_rhs, row, &b);
+        sl = agg_expr_eval_f64_as<DIV, COND, CONV>(e.lhs, e.n_lhs, row, &a);
+        sr = agg_expr_eval_f64_as<DIV, COND, CONV>(e.rhs, e.n_rhs, row, &b);
         known = sl == AGG_ROW_VALUE && sr == AGG_ROW_VALUE;
+        if constexpr (CONV) over = sl != AGG_ROW_NULL && sr != AGG_ROW_NULL && !known;  // (a conversion inside a side of doubles can overflow)
         t = known && filter_expr_compare_f64(in.cmp, a, b);
       } else {
         agg_i128 a = 0, b = 0;
-        sl = agg_expr_eval_i128_as<DIV, COND>(e.lhs, e.n_lhs, row, &a);
-        sr = agg_expr_eval_i128_as<DIV, COND>(e.rhs, e.n_rhs, row, &b);
+        sl = agg_expr_eval_i128_as<DIV, COND, CONV>(e.lhs, e.n_lhs, row, &a);
+        sr = agg_expr_eval_i128_as<DIV, COND, CONV>(e.rhs, e.n_rhs, row, &b);
         known = sl == AGG_ROW_VALUE && sr == AGG_ROW_VALUE;
         over = sl != AGG_ROW_NULL && sr != AGG_ROW_NULL && !known;  // (a NULL column comes first: the row is not counted)
         t = known && filter_expr_compare_i128(in.cmp, a, b, e.d, e.p10);
@@ -381,6 +382,14 @@ filter_expr_cond_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t*
                         unsigned long long* overflow) {
   __shared__ uint32_t over_s[4];
   filter_expr_body<true, true>(prog, n_insn, leaves, lits, cols, segs, seg_first, n_segs, n_in, B, W, planes, n_planes, overflow, over_s);
+}
+// (the mixed interpreter: launched when a leaf of the call holds a conversion)
+extern "C" __global__ void __launch_bounds__(256)
+filter_expr_conv_kernel(const FilterInsn* prog, uint32_t n_insn, const uint32_t* leaves, const uint8_t* lits, const FilterCol* cols, const SelBatch* segs,
+                        const unsigned long long* seg_first, uint32_t n_segs, uint64_t n_in, uint32_t B, uint32_t W, unsigned long long* planes, uint32_t n_planes,
+                        unsigned long long* overflow) {
+  __shared__ uint32_t over_s[4];
+  filter_expr_body<true, true, true>(prog, n_insn, leaves, lits, cols, segs, seg_first, n_segs, n_in, B, W, planes, n_planes, overflow, over_s);
 }
 
 // One 64-row word of a predicate: the program prog[0, n_insn) over the trip's rows -- lane l holds input row w * 64 + l as `r`,

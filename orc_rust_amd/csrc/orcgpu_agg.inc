@@ -138,8 +138,8 @@ int agg_run(const FilterCall& f, const AggWorkspace& aw, const KeptRows& rows, c
   AggPartial *d_part = f.at<AggPartial>(aw.o_part), *d_out = f.at<AggPartial>(aw.o_back);
   if (const int rc = agg_upload(f, aw, insns, ops)) return rc;
   // (the expression kernel with the divide, or with the divide and the conditionals, only for a list that needs it)
-  const bool div = agg_ops_hold_division(ops.data(), ops.size()), cond = agg_ops_hold_conditional(ops.data(), ops.size());
-  if (const int rc = agg_launch_partials(f, aw, !ops.empty(), agg_partial_kernel, cond ? agg_expr_cond_partial_kernel : div ? agg_expr_div_partial_kernel : agg_expr_partial_kernel, rows, d_part)) return rc;
+  const bool div = agg_ops_hold_division(ops.data(), ops.size()), cond = agg_ops_hold_conditional(ops.data(), ops.size()), conv = agg_ops_hold_conversion(ops.data(), ops.size());
+  if (const int rc = agg_launch_partials(f, aw, !ops.empty(), agg_partial_kernel, conv ? agg_expr_conv_partial_kernel : cond ? agg_expr_cond_partial_kernel : div ? agg_expr_div_partial_kernel : agg_expr_partial_kernel, rows, d_part)) return rc;
   hipLaunchKernelGGL(agg_final_kernel, dim3(aw.n_insn), dim3(256), 0, st, f.at<const AggInsn>(aw.o_insn), d_part, aw.blocks, d_out);
   HIP_TRY(ctx, hipGetLastError());
   // ---- the aggregation's one wait: a record per aggregate, and the kept row count ----
@@ -200,7 +200,8 @@ int group_run(const FilterCall& f, const AggWorkspace& gw, const KeptRows& rows,
   hipLaunchKernelGGL(group_number_kernel, dim3(1), dim3(kGroupSlots), 0, st, keys, rows, d_table, d_ctl, d_slot_group, f.at<GroupKeyRecord>(gw.o_back + gw.back_keys));
   HIP_TRY(ctx, hipGetLastError());
   if (const int rc = agg_launch_partials(f, gw, !ops.empty(), agg_group_partial_kernel,
-                                         agg_ops_hold_conditional(ops.data(), ops.size()) ? agg_group_expr_cond_partial_kernel
+                                         agg_ops_hold_conversion(ops.data(), ops.size()) ? agg_group_expr_conv_partial_kernel
+                                         : agg_ops_hold_conditional(ops.data(), ops.size()) ? agg_group_expr_cond_partial_kernel
                                          : agg_ops_hold_division(ops.data(), ops.size()) ? agg_group_expr_div_partial_kernel : agg_group_expr_partial_kernel, rows, (const uint32_t*)d_plane,
                                          (const uint32_t*)d_slot_group, (const GroupControl*)d_ctl, d_part))
     return rc;
@@ -285,7 +286,7 @@ int group_run_wide(const FilterCall& f, const AggWorkspace& gw, const KeptRows& 
                        (const GroupControl*)d_ctl, w.cap, d_vals);
     HIP_TRY(ctx, hipGetLastError());
     if (!ops.empty()) {
-      hipLaunchKernelGGL(agg_ops_hold_conditional(ops.data(), ops.size()) ? agg_group_wide_expr_cond_kernel : agg_ops_hold_division(ops.data(), ops.size()) ? agg_group_wide_expr_div_kernel : agg_group_wide_expr_kernel, dim3(blocks, gw.n_insn), dim3(256), 0, st, d_insn, f.at<const AggExprOp>(gw.o_ops), rows, (const uint32_t*)d_rows[at],
+      hipLaunchKernelGGL(agg_ops_hold_conversion(ops.data(), ops.size()) ? agg_group_wide_expr_conv_kernel : agg_ops_hold_conditional(ops.data(), ops.size()) ? agg_group_wide_expr_cond_kernel : agg_ops_hold_division(ops.data(), ops.size()) ? agg_group_wide_expr_div_kernel : agg_group_wide_expr_kernel, dim3(blocks, gw.n_insn), dim3(256), 0, st, d_insn, f.at<const AggExprOp>(gw.o_ops), rows, (const uint32_t*)d_rows[at],
                          (const uint32_t*)d_seg, (const GroupControl*)d_ctl, w.cap, d_vals);
       HIP_TRY(ctx, hipGetLastError());
     }

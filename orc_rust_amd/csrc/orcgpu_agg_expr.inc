@@ -11,7 +11,12 @@
 // conditions CMP, IS_NULL, AND, OR, NOT; include/orcgpu.h: CONDITIONALS): numbers and conditions are told apart after the parse, the
 // value operands of IF / COALESCE and the sides of CMP get the scale rule of +, the ternary node its own labelling, and a program
 // that holds one is emitted WITHOUT gates, its column pushes nullable, behind a mark that makes every interpreter without the
-// conditionals overflow the row (agg_program.h: kAggCondMark) -- a program that holds none is, op for op, what it was.  Every refusal of the expression aggregates is
+// conditionals overflow the row (agg_program.h: kAggCondMark) -- a program that holds none is, op for op, what it was.  Conversions
+// (CAST, ROUND, FLOOR, CEIL, TRUNC; include/orcgpu.h: CONVERSIONS): a tree that holds one (`mixed`) has its classes decided PER NODE,
+// bottom-up (Node::nc: node_class, meet), each conversion node becomes the child itself, a folded literal or one of kToF64 ..
+// kF64Round (type_conversion), and the program is laid out like one with conditionals, for the mixed interpreter alone, behind a
+// mark and in front of a tail that keep it safe everywhere else (agg_program.h: kAggConvMarkCol) -- a tree that holds none takes
+// none of these paths.  Every refusal of the expression aggregates is
 // decided here.  Included from orcgpu_agg_plan.inc, in front of its compiler.
 //
 // The row filter's expression leaf (ORCGPU_PRED_CMP_EXPR: lhs OP rhs) has its two sides compiled here too (compile_pair, called by
@@ -59,6 +64,8 @@ static_assert(ORCGPU_AGG_EXPR_DIV == 17 && ORCGPU_AGG_EXPR_FLOOR_DIV == 18 && OR
 static_assert(ORCGPU_AGG_EXPR_IF == 21 && ORCGPU_AGG_EXPR_COALESCE == 22 && ORCGPU_AGG_EXPR_ABS == 23 && ORCGPU_AGG_EXPR_NULL == 24 && ORCGPU_AGG_EXPR_CMP == 25 &&
                   ORCGPU_AGG_EXPR_IS_NULL == 26 && ORCGPU_AGG_EXPR_AND == 27 && ORCGPU_AGG_EXPR_OR == 28 && ORCGPU_AGG_EXPR_NOT == 29,
               "the conditional nodes of include/orcgpu.h: the value nodes, then the condition nodes, without a gap");
+static_assert(ORCGPU_AGG_EXPR_CAST == 30 && ORCGPU_AGG_EXPR_ROUND == 31 && ORCGPU_AGG_EXPR_FLOOR == 32 && ORCGPU_AGG_EXPR_CEIL == 33 && ORCGPU_AGG_EXPR_TRUNC == 34,
+              "the conversion nodes of include/orcgpu.h, behind the conditionals without a gap");
 static_assert(kAggExprSlots == ORCGPU_AGG_EXPR_MAX_DEPTH && kAggExprMaxNodes == ORCGPU_AGG_EXPR_MAX_NODES, "the limits of include/orcgpu.h");
 
 enum { XCLASS_INT = 0, XCLASS_DEC = 1, XCLASS_FLOAT = 2 };
@@ -86,9 +93,20 @@ struct AggExprCompiler {
     uint32_t part = 0;      // DATE_PART: ORCGPU_DATE_PART_*
     int want_scale = -1;    // DIV: the result scale the caller chose (the node's `i`), -1: the default rule
     bool in_date = false;   // a leaf that stands below a DATE_PART: its value is a number of days
+    int nc = XCLASS_INT;    // a tree with conversions: the node's own class (XCLASS_*), decided bottom-up
+    bool fop = false;       // ... and whether the node's OPERANDS are doubles (an arithmetic node, NEG, ABS, CMP): kAggOpF64
+    int to = 0;             // CAST: the target class; its scale in want_scale.  ROUND: the digits in want_scale
     uint32_t label = 1;     // operand slots the subtree needs
   };
   static constexpr uint32_t kScale = 100;
+  // ... and what a conversion node becomes once its child's class is known (type_node): one child each
+  static constexpr uint32_t kToF64 = 101;     // exact at scale k -> double (AX_TO_F64)
+  static constexpr uint32_t kF64ToDec = 102;  // double -> Decimal at scale k (AX_F64_TO_DEC)
+  static constexpr uint32_t kF64ToInt = 103;  // double -> int64 (AX_F64_TO_INT)
+  static constexpr uint32_t kRescale = 104;   // exact, divided by 10^k by the mode in `part` (AX_RESCALE)
+  static constexpr uint32_t kToInt = 105;     // exact at scale k -> int64: AX_RESCALE by 10^k toward zero where k != 0, then AX_FIT_I64
+  static constexpr uint32_t kF64Round = 106;  // double, rounded by the mode in `part` (AX_F64_ROUND)
+  bool mixed = false;  // the tree holds a conversion node: classes are per node (Node::nc), and the program is one for the mixed interpreter
   std::vector<Node> t;
   const orcgpu_agg_expr_node* src = nullptr;
   uint32_t n_src = 0, at = 0;
@@ -105,9 +123,11 @@ struct AggExprCompiler {
   static uint32_t conditional_children(uint32_t op) {
     return op == ORCGPU_AGG_EXPR_IF ? 3 : op == ORCGPU_AGG_EXPR_NULL ? 0 : (op == ORCGPU_AGG_EXPR_ABS || op == ORCGPU_AGG_EXPR_IS_NULL || op == ORCGPU_AGG_EXPR_NOT) ? 1 : 2;
   }
+  // the conversion nodes (include/orcgpu.h: CONVERSIONS): one child each
+  static bool is_conversion(uint32_t op) { return op >= ORCGPU_AGG_EXPR_CAST && op <= ORCGPU_AGG_EXPR_TRUNC; }
   static const char* node_name(uint32_t op) {
-    static const char* const n[] = {"IF", "COALESCE", "ABS", "NULL", "CMP", "IS_NULL", "AND", "OR", "NOT"};
-    if (is_conditional(op)) return n[op - ORCGPU_AGG_EXPR_IF];
+    static const char* const n[] = {"IF", "COALESCE", "ABS", "NULL", "CMP", "IS_NULL", "AND", "OR", "NOT", "CAST", "ROUND", "FLOOR", "CEIL", "TRUNC"};
+    if (is_conditional(op) || is_conversion(op)) return n[op - ORCGPU_AGG_EXPR_IF];
     return op == ORCGPU_AGG_EXPR_COLUMN ? "a column" : op == ORCGPU_AGG_EXPR_LITERAL ? "a literal" : op == ORCGPU_AGG_EXPR_ADD ? "+" : op == ORCGPU_AGG_EXPR_SUB ? "-"
          : op == ORCGPU_AGG_EXPR_MUL ? "*" : op == ORCGPU_AGG_EXPR_NEG ? "unary -" : op == ORCGPU_AGG_EXPR_DATE_PART ? "a date part" : is_division(op) ? division_name(op) : "?";
   }
@@ -178,6 +198,30 @@ struct AggExprCompiler {
       if (rc) return rc;
       t[me].a = a;
       t[me].part = (uint32_t)s.i;
+    } else if (is_conversion(s.op)) {
+      if (s.op == ORCGPU_AGG_EXPR_CAST) {
+        // (The message begins with the words an unknown node is refused in: until there was a CAST, 30 WAS an unknown node, a node 30
+        // with nothing filled in -- value_type 0 -- is what a caller of that time sent, and tests/test_cond_host_sanitized.py pins
+        // those words for it.  Same status as ever; the second half says what is wrong to a caller who did write a CAST.)
+        if (s.value_type != ORCGPU_PV_INT64 && s.value_type != ORCGPU_PV_FLOAT64 && s.value_type != ORCGPU_PV_DECIMAL128)
+          return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an unknown node in the expression of %s: a CAST whose value_type names no target type (ORCGPU_PV_INT64, _FLOAT64 or _DECIMAL128)", op_name);
+        if (s.value_type == ORCGPU_PV_DECIMAL128 && (s.i < 0 || s.i > 38))
+          return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a CAST node of the expression of %s to DECIMAL128 names no scale (i: 0 .. 38)", op_name);
+        t[me].to = s.value_type == ORCGPU_PV_INT64 ? XCLASS_INT : s.value_type == ORCGPU_PV_FLOAT64 ? XCLASS_FLOAT : XCLASS_DEC;
+        t[me].want_scale = s.value_type == ORCGPU_PV_DECIMAL128 ? (int)s.i : 0;
+      } else if (s.op == ORCGPU_AGG_EXPR_ROUND) {
+        if (s.i < 0 || s.i > 38) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a ROUND node of the expression of %s names no digits (i: 0 .. 38)", op_name);
+        t[me].want_scale = (int)s.i;
+      }
+      mixed = true;
+      // (what stands below a conversion is no operand of the date part above it: the node's own result is)
+      const uint32_t outer_depth = date_depth;
+      date_depth = 0;
+      int a = -1;
+      const int rc = at >= n_src ? fail(ORCGPU_INVALID_ARGUMENT, "aggregate: a %s node of the expression of %s stands without its child", node_name(s.op), op_name) : parse(a);
+      date_depth = outer_depth;
+      if (rc) return rc;
+      t[me].a = a;
     } else if (is_conditional(s.op)) {
       if (s.op == ORCGPU_AGG_EXPR_CMP) {
         if (s.i < ORCGPU_PRED_EQ || s.i > ORCGPU_PRED_GE)
@@ -243,14 +287,15 @@ struct AggExprCompiler {
       dec_col |= k == ACLASS_DEC;
     }
     if (!float_col && !exact_col && !predicate) return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: the expression of %s holds no column", op_name);
+    if (mixed) return ORCGPU_OK;  // (a tree with conversions: the classes meet per node, in type_node)
     if (!float_col && !exact_col && f64_lit && dec_lit)
       return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside a DECIMAL128 literal", op_name);
     if (float_col && exact_col)
-      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s mixes the Float / Double column '%s' with the integer or Decimal column '%s'", op_name, float_col, exact_col);
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s mixes the Float / Double column '%s' with the integer or Decimal column '%s': bring one to the other's class with a cast", op_name, float_col, exact_col);
     if (f64_lit && exact_col)
-      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside the integer or Decimal column '%s'", op_name, exact_col);
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a FLOAT64 literal beside the integer or Decimal column '%s': bring one to the other's class with a cast", op_name, exact_col);
     if (dec_lit && float_col)
-      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s'", op_name, float_col);
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s holds a DECIMAL128 literal beside the Float / Double column '%s': bring one to the other's class with a cast", op_name, float_col);
     cls = float_col || (!exact_col && f64_lit) ? XCLASS_FLOAT : (dec_col || dec_lit || has_div) ? XCLASS_DEC : XCLASS_INT;
     // (reached with a date part of literals alone: one over a column has met the mixing rule above)
     if (cls == XCLASS_FLOAT && date_fn)
@@ -271,6 +316,149 @@ struct AggExprCompiler {
 
   bool is_lit(int n) const { return t[n].op == ORCGPU_AGG_EXPR_LITERAL; }
 
+  // ---- a tree with conversions (include/orcgpu.h: CONVERSIONS): the class of every node, bottom-up ----
+  static const char* cast_hint() { return "bring one to the other's class with a cast"; }
+  // the two operands x and y of an operator, of CMP, or the value operands of IF / COALESCE, are of one class `k`: an integer
+  // beside a Decimal is promoted (the representation is the same), an INT64 literal beside doubles becomes a double when that is
+  // exact, a NULL takes its sibling's class; doubles beside anything else are refused
+  int meet(int x, int y, int& k) {
+    if (t[x].op == ORCGPU_AGG_EXPR_NULL) t[x].nc = t[y].nc;
+    if (t[y].op == ORCGPU_AGG_EXPR_NULL) t[y].nc = t[x].nc;
+    for (int pass = 0; pass < 2; pass++) {
+      Node &p = t[pass ? y : x], &q = t[pass ? x : y];
+      if (q.nc != XCLASS_FLOAT || p.nc != XCLASS_INT || p.op != ORCGPU_AGG_EXPR_LITERAL || p.value_type != ORCGPU_PV_INT64) continue;
+      const long long i = (long long)p.iv;
+      const double d = (double)i;
+      if (p.iv != (agg_i128)i || !(d >= -9223372036854775808.0 && d < 9223372036854775808.0 && (long long)d == i))
+        return fail(ORCGPU_INVALID_ARGUMENT, "aggregate: an INT64 literal beside column '%s' in the expression of %s is not exact as a double", first_column, op_name);
+      p.fv = d;
+      p.nc = XCLASS_FLOAT;
+      p.value_type = ORCGPU_PV_FLOAT64;
+    }
+    if ((t[x].nc == XCLASS_FLOAT) != (t[y].nc == XCLASS_FLOAT))
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: the expression of %s over column '%s' mixes a Float / Double operand with an integer or Decimal one: %s", op_name, first_column, cast_hint());
+    k = t[x].nc == XCLASS_FLOAT ? XCLASS_FLOAT : (t[x].nc == XCLASS_DEC || t[y].nc == XCLASS_DEC) ? XCLASS_DEC : XCLASS_INT;
+    return ORCGPU_OK;
+  }
+  // the class of node n over its typed children, and whether its operands are doubles
+  int node_class(int n, int a, int b, int c) {
+    const uint32_t op = t[n].op;
+    int k = XCLASS_INT;
+    if (op == ORCGPU_AGG_EXPR_ADD || op == ORCGPU_AGG_EXPR_SUB || op == ORCGPU_AGG_EXPR_MUL || is_division(op) || op == ORCGPU_AGG_EXPR_CMP || op == ORCGPU_AGG_EXPR_COALESCE) {
+      if (const int rc = meet(a, b, k)) return rc;
+    } else if (op == ORCGPU_AGG_EXPR_IF) {
+      if (const int rc = meet(b, c, k)) return rc;
+    } else if (op == ORCGPU_AGG_EXPR_NEG || op == ORCGPU_AGG_EXPR_ABS || op == kScale) {
+      k = t[a].nc;
+    } else if (op == ORCGPU_AGG_EXPR_DATE_PART) {
+      if (t[a].nc == XCLASS_FLOAT)
+        return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s over column '%s' takes days, an integer: its operand is a Float / Double (cast it to int64)", part_name(t[n].part), op_name, first_column);
+    }
+    if ((op == ORCGPU_AGG_EXPR_FLOOR_DIV || op == ORCGPU_AGG_EXPR_MOD) && k == XCLASS_FLOAT)
+      return fail(ORCGPU_MISMATCHED_SCHEMA, "aggregate: %s in the expression of %s over column '%s' takes integers: its operands are Float / Double (cast them to int64)", division_name(op), op_name, first_column);
+    t[n].fop = k == XCLASS_FLOAT;
+    t[n].nc = is_condition(op) || op == ORCGPU_AGG_EXPR_DATE_PART ? XCLASS_INT : op == ORCGPU_AGG_EXPR_DIV && k == XCLASS_INT ? XCLASS_DEC : k;
+    return ORCGPU_OK;
+  }
+  void set_pow(Node& x, uint32_t k) {
+    x.k = k;
+    x.iv = agg_pow10(k);
+  }
+  // A conversion node over its typed child `a`: what it becomes -- the child itself where nothing happens, a literal where the
+  // child is one and the conversion does not overflow, else one of the nodes kToF64 .. kF64Round
+  int type_conversion(int n, int a, int& out) {
+    const uint32_t op = t[n].op;
+    const Node ch = t[a];
+    const bool f = ch.nc == XCLASS_FLOAT, lit = is_lit(a);
+    Node x = t[n];
+    x.a = a;
+    x.label = ch.label;  // (unary: the slots its operand needs)
+    Node folded = ch;    // a literal child's successor
+    bool fold = false;
+    out = n;
+    if (op == ORCGPU_AGG_EXPR_CAST && x.to == XCLASS_FLOAT) {
+      if (f) return out = a, ORCGPU_OK;
+      x.op = kToF64;
+      set_pow(x, (uint32_t)ch.scale);
+      x.nc = XCLASS_FLOAT;
+      x.scale = 0;
+      fold = lit;
+      folded.fv = agg_to_f64(ch.iv, x.k, x.iv);
+      folded.value_type = ORCGPU_PV_FLOAT64;
+    } else if (op == ORCGPU_AGG_EXPR_CAST && x.to == XCLASS_DEC) {
+      const int ts = x.want_scale;
+      if (f) {
+        x.op = kF64ToDec;
+        set_pow(x, (uint32_t)ts);
+        fold = lit && agg_f64_to_dec(ch.fv, x.iv, &folded.iv);
+        folded.value_type = ORCGPU_PV_INT64;
+      } else if (ts >= ch.scale) {
+        if (ts == ch.scale && !lit && ch.nc != XCLASS_DEC) {
+          // an integer to decimal(0): nothing to multiply by, but the CLASS changes -- carried by this node, a "times 10^0" that emits
+          // no op, so that the child (a column leaf, say) keeps the class it has
+          x.op = kScale;
+          set_pow(x, 0);
+          x.nc = XCLASS_DEC;
+          x.scale = ts;
+          t[n] = x;
+          return ORCGPU_OK;
+        }
+        out = scaled(a, (uint32_t)(ts - ch.scale));  // (the child itself where the scales agree: a Decimal already, or a literal)
+        t[out].nc = XCLASS_DEC;
+        return ORCGPU_OK;
+      } else {
+        x.op = kRescale;
+        x.part = AGG_ROUND_HALF_AWAY;
+        set_pow(x, (uint32_t)(ch.scale - ts));
+        fold = lit;
+        folded.iv = agg_rescale(ch.iv, x.iv, AGG_ROUND_HALF_AWAY);
+      }
+      x.nc = XCLASS_DEC;
+      x.scale = ts;
+    } else if (op == ORCGPU_AGG_EXPR_CAST) {  // to int64
+      if (f) {
+        x.op = kF64ToInt;
+        fold = lit && agg_f64_to_i64(ch.fv, &folded.iv);
+        folded.value_type = ORCGPU_PV_INT64;
+      } else {
+        x.op = kToInt;
+        set_pow(x, (uint32_t)ch.scale);
+        folded.iv = x.k ? agg_rescale(ch.iv, x.iv, AGG_ROUND_TRUNC) : ch.iv;
+        fold = lit && folded.iv == (agg_i128)(long long)folded.iv;
+      }
+      x.nc = XCLASS_INT;
+      x.scale = 0;
+    } else {  // ROUND, FLOOR, CEIL, TRUNC: the child's class
+      const uint32_t mode = op == ORCGPU_AGG_EXPR_ROUND ? AGG_ROUND_HALF_AWAY : op == ORCGPU_AGG_EXPR_FLOOR ? AGG_ROUND_FLOOR : op == ORCGPU_AGG_EXPR_CEIL ? AGG_ROUND_CEIL : AGG_ROUND_TRUNC;
+      const int digits = op == ORCGPU_AGG_EXPR_ROUND ? x.want_scale : 0;
+      x.nc = ch.nc;
+      x.part = mode;
+      if (f) {
+        if (digits != 0)
+          return fail(ORCGPU_UNSUPPORTED, "aggregate: ROUND in the expression of %s over column '%s' rounds a Float / Double to decimal places: only ROUND(x, 0) is a double's; round to n places with a cast to decimal(n)", op_name, first_column);
+        x.op = kF64Round;
+        fold = lit;
+        folded.fv = agg_f64_round(ch.fv, mode);
+      } else {
+        if (digits >= ch.scale) return out = a, ORCGPU_OK;  // (an integer, or nothing to round away)
+        x.op = kRescale;
+        set_pow(x, (uint32_t)(ch.scale - digits));
+        x.scale = digits;
+        fold = lit;
+        folded.iv = agg_rescale(ch.iv, x.iv, mode);
+      }
+    }
+    if (fold) {
+      folded.nc = x.nc;
+      folded.scale = x.scale;
+      folded.label = 1;
+      t[n] = folded;
+    } else {
+      t[n] = x;
+    }
+    return ORCGPU_OK;
+  }
+
   // x <- x * 10^k: folded into a literal when the product fits, else a node of its own (the rows then report the overflow)
   int scaled(int x, uint32_t k) {
     if (!k) return x;
@@ -287,6 +475,7 @@ struct AggExprCompiler {
     n.k = k;
     n.iv = f;
     n.scale = t[x].scale + (int)k;
+    n.nc = t[x].nc;
     n.label = t[x].label;  // (unary: the slots its operand needs)
     t.push_back(n);
     return (int)t.size() - 1;
@@ -303,7 +492,13 @@ struct AggExprCompiler {
     if (c >= 0)
       if (const int rc = type_node(c, c)) return rc;
     const uint32_t op = t[n].op;
-    if (cls == XCLASS_DEC) {
+    if (mixed) {
+      if (is_conversion(op)) return type_conversion(n, a, out);
+      if (const int rc = node_class(n, a, b, c)) return rc;
+    }
+    // (a tree with conversions: an integer is a Decimal of scale 0 wherever its operands are exact, so the scale rule runs there)
+    const int kcls = mixed ? (t[n].fop ? XCLASS_FLOAT : t[n].nc) : cls;  // the class the node's folding computes in
+    if (mixed ? !t[n].fop : cls == XCLASS_DEC) {
       if (op == ORCGPU_AGG_EXPR_IF || op == ORCGPU_AGG_EXPR_COALESCE) {
         // the two value operands at the larger of their scales; a NULL takes its sibling's
         int &x = op == ORCGPU_AGG_EXPR_IF ? b : a, &y = op == ORCGPU_AGG_EXPR_IF ? c : b;
@@ -370,7 +565,7 @@ struct AggExprCompiler {
       if (op == ORCGPU_AGG_EXPR_ABS && is_lit(a)) {  // of a literal: folded with the evaluator's own function unless it overflows
         Node lit = t[a];
         bool ok = true;
-        if (cls == XCLASS_FLOAT) lit.fv = agg_f64_of_bits(agg_bits_of_f64(lit.fv) & 0x7fffffffffffffffull);
+        if (kcls == XCLASS_FLOAT) lit.fv = agg_f64_of_bits(agg_bits_of_f64(lit.fv) & 0x7fffffffffffffffull);
         else if (lit.iv < 0) ok = agg_neg_checked(t[a].iv, &lit.iv);
         if (ok) {
           t[n] = lit;
@@ -405,7 +600,8 @@ struct AggExprCompiler {
       Node lit;
       lit.op = ORCGPU_AGG_EXPR_LITERAL;
       lit.scale = t[n].scale;
-      if (cls == XCLASS_FLOAT) {
+      lit.nc = t[n].nc;
+      if (kcls == XCLASS_FLOAT) {
         lit.value_type = ORCGPU_PV_FLOAT64;
         const double x = t[a].fv, y = b >= 0 ? t[b].fv : 0.0;
         lit.fv = op == ORCGPU_AGG_EXPR_ADD ? agg_f64_add(x, y) : op == ORCGPU_AGG_EXPR_SUB ? agg_f64_add(x, -y) : op == ORCGPU_AGG_EXPR_MUL ? agg_f64_mul(x, y)
@@ -463,7 +659,7 @@ struct AggExprCompiler {
       if (x.op == ORCGPU_AGG_EXPR_CMP) o.col = x.cmp;
     } else if (x.op == ORCGPU_AGG_EXPR_LITERAL) {
       o.op = AX_PUSH_LIT;
-      if (cls == XCLASS_FLOAT) {
+      if ((mixed ? x.nc : cls) == XCLASS_FLOAT) {
         o.lo = agg_bits_of_f64(x.fv);
       } else {
         o.lo = (unsigned long long)x.iv;
@@ -471,10 +667,34 @@ struct AggExprCompiler {
       }
     } else if (x.op == kScale) {
       emit(x.a, ops);
+      if (!x.k) return;  // (a cast of an integer to decimal(0): the class alone changed -- type_conversion)
       o.op = AX_SCALE10;
       o.col = x.k;
       o.lo = (unsigned long long)x.iv;
       o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
+    } else if (x.op >= kToF64 && x.op <= kF64Round) {  // what the conversion nodes became (type_conversion)
+      emit(x.a, ops);
+      o.col = x.k;
+      o.lo = (unsigned long long)x.iv;
+      o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
+      if (x.op == kToInt) {
+        if (x.k) {
+          o.op = AX_RESCALE;
+          o.col = x.k | ((uint32_t)AGG_ROUND_TRUNC << 8);
+          ops.push_back(o);
+        }
+        o = AggExprOp{};
+        o.op = AX_FIT_I64;
+      } else if (x.op == kRescale) {
+        o.op = AX_RESCALE;
+        o.col = x.k | (x.part << 8);
+      } else if (x.op == kF64Round || x.op == kF64ToInt) {
+        o = AggExprOp{};
+        o.op = x.op == kF64Round ? AX_F64_ROUND : AX_F64_TO_INT;
+        o.col = x.op == kF64Round ? x.part : 0;
+      } else {
+        o.op = x.op == kToF64 ? AX_TO_F64 : AX_F64_TO_DEC;
+      }
     } else if (x.op == ORCGPU_AGG_EXPR_NEG) {
       emit(x.a, ops);
       o.op = AX_NEG;
@@ -493,7 +713,7 @@ struct AggExprCompiler {
           ops.push_back(w);
         }
         o.op = x.op == ORCGPU_AGG_EXPR_DIV ? AX_DIV : x.op == ORCGPU_AGG_EXPR_FLOOR_DIV ? AX_FLOOR_DIV : AX_MOD;
-        if (x.op == ORCGPU_AGG_EXPR_DIV && cls != XCLASS_FLOAT) {
+        if (x.op == ORCGPU_AGG_EXPR_DIV && !(mixed ? x.fop : cls == XCLASS_FLOAT)) {
           o.col = x.k;
           o.lo = (unsigned long long)x.iv;
           o.hi = (unsigned long long)((agg_u128)x.iv >> 64);
@@ -502,6 +722,8 @@ struct AggExprCompiler {
         o.op = x.op == ORCGPU_AGG_EXPR_ADD ? AX_ADD : x.op == ORCGPU_AGG_EXPR_MUL ? AX_MUL : right_first ? AX_RSUB : AX_SUB;
       }
     }
+    // (a program with conversions: the ops that work on either kind say which -- agg_program.h: kAggOpF64)
+    if (mixed && x.fop && ((o.op >= AX_ADD && o.op <= AX_NEG) || o.op == AX_DIV || o.op == AX_ABS || o.op == AX_CMP)) o.hi |= kAggOpF64;
     ops.push_back(o);
   }
 
@@ -560,22 +782,33 @@ struct AggExprCompiler {
   // the class of everything parsed, and the columns' scales
   int type_leaves() {
     if (const int rc = classify()) return rc;
-    if (cls == XCLASS_DEC)
+    if (cls == XCLASS_DEC || mixed)
       for (Node& n : t)
         if (n.op == ORCGPU_AGG_EXPR_COLUMN) n.scale = agg_class(cols[n.col].orc_type) == ACLASS_DEC ? (int)cols[n.col].scale : 0;
+    if (mixed)
+      for (Node& n : t) {
+        if (n.op == ORCGPU_AGG_EXPR_COLUMN) {
+          const int k = col_class(n.col, n.in_date);
+          n.nc = k == ACLASS_FLOAT ? XCLASS_FLOAT : k == ACLASS_DEC ? XCLASS_DEC : XCLASS_INT;
+        } else if (n.op == ORCGPU_AGG_EXPR_LITERAL) {
+          n.nc = n.value_type == ORCGPU_PV_FLOAT64 ? XCLASS_FLOAT : n.value_type == ORCGPU_PV_DECIMAL128 ? XCLASS_DEC : XCLASS_INT;
+        }
+      }
     return ORCGPU_OK;
   }
   // The tree at `root`, parsed from e and typed at its leaves -> its program behind `ops`: scales, folding, labels, the gates,
   // the ops.  root: the node that stands for it afterwards
-  int finish(const orcgpu_agg_expr* e, int& root, std::vector<AggExprOp>& ops) {
+  int finish(const orcgpu_agg_expr* e, int& root, std::vector<AggExprOp>& ops, bool typed = false) {
     src = e->nodes;
     n_src = e->n_nodes;
-    if (const int rc = type_node(root, root)) return rc;
+    if (!typed)
+      if (const int rc = type_node(root, root)) return rc;
     if (t[root].label > kAggExprSlots)
       return fail(ORCGPU_UNSUPPORTED, "aggregate: the expression of %s over column '%s' needs more than ORCGPU_AGG_EXPR_MAX_DEPTH (4) operand slots", op_name, first_column);
     // A tree that still holds a conditional node has no gates: NULL is per operand there, the pushes are nullable and the root's
     // bits decide the row.  Every other program is what it always was.
-    cond_program = holds_conditional(root);
+    // A tree with conversions is laid out the same way, for the mixed interpreter, whether a conditional is left in it or not.
+    cond_program = holds_conditional(root) || mixed;
     // the gates: every distinct column, in order of appearance
     std::vector<uint32_t> seen;
     for (uint32_t k = 0; k < n_src && !cond_program; k++) {
@@ -595,11 +828,25 @@ struct AggExprCompiler {
     if (cond_program) {  // the mark: an interpreter without the conditionals overflows the row on it (agg_program.h: kAggCondMark)
       AggExprOp mark{};
       mark.op = kAggCondMark;
+      mark.col = mixed ? kAggConvMarkCol : 0;
       ops.push_back(mark);
     }
     emit(root, ops);
     const size_t end_op = ops.size();  // (what is counted below: not the mark, not the tail)
-    if (cond_program && cls == XCLASS_FLOAT) {  // ... and in the double class NaN is its result there: `push NaN, add` behind the program
+    if (mixed) {  // the tail that keeps a program with conversions safe in every other interpreter (agg_program.h: kAggConvTail)
+      AggExprOp lit{}, mod{}, swap{}, coal{}, add{};
+      lit.op = AX_PUSH_LIT;
+      mod.op = AX_MOD;
+      swap.op = AX_SWAP;
+      coal.op = AX_COALESCE;
+      add.op = AX_ADD;
+      if (cls == XCLASS_FLOAT) {
+        lit.lo = kAggCondNaNBits;
+        for (const AggExprOp& o : {lit, swap, coal, lit, add}) ops.push_back(o);
+      } else {
+        for (const AggExprOp& o : {lit, lit, mod, swap, coal}) ops.push_back(o);
+      }
+    } else if (cond_program && cls == XCLASS_FLOAT) {  // ... and in the double class NaN is its result there: `push NaN, add` behind the program
       AggExprOp nan{}, add{};
       nan.op = AX_PUSH_LIT;
       nan.lo = kAggCondNaNBits;
@@ -629,10 +876,17 @@ struct AggExprCompiler {
   // The program of `e` goes behind `ops`; kind / scale: the AK_EXPR_* kind and the root's scale (DEC)
   int compile(const orcgpu_agg_expr* e, std::vector<AggExprOp>& ops, uint32_t& kind, int32_t& scale) {
     t.clear();
+    mixed = false;
     int root = -1;
     if (const int rc = parse_expr(e, root)) return rc;
     if (const int rc = type_leaves()) return rc;
-    if (const int rc = finish(e, root, ops)) return rc;
+    if (mixed) {  // the root's class is the expression's
+      src = e->nodes;
+      n_src = e->n_nodes;
+      if (const int rc = type_node(root, root)) return rc;
+      cls = t[root].nc;
+    }
+    if (const int rc = finish(e, root, ops, mixed)) return rc;
     kind = cls == XCLASS_FLOAT ? AK_EXPR_F64 : cls == XCLASS_DEC ? AK_EXPR_DEC : AK_EXPR_INT;
     scale = cls == XCLASS_DEC ? t[root].scale : 0;
     return ORCGPU_OK;
@@ -651,17 +905,23 @@ struct AggExprCompiler {
   // lhs OP rhs: both sides parsed, typed TOGETHER (`cls` is the leaf's), then each finished on its own
   int compile_pair(const orcgpu_agg_expr* lhs, const orcgpu_agg_expr* rhs, Side& l, Side& r) {
     t.clear();
+    mixed = false;
     int rl = -1, rr = -1;
     if (const int rc = parse_expr(lhs, rl)) return rc;
     if (const int rc = parse_expr(rhs, rr)) return rc;
     if (const int rc = type_leaves()) return rc;
+    if (mixed) {  // the two sides meet as the operands of a comparison do: the leaf's class is theirs
+      if (const int rc = type_node(rl, rl)) return rc;
+      if (const int rc = type_node(rr, rr)) return rc;
+      if (const int rc = meet(rl, rr, cls)) return rc;
+    }
     const orcgpu_agg_expr* es[2] = {lhs, rhs};
     int roots[2] = {rl, rr};
     Side* sides[2] = {&l, &r};
     for (int k = 0; k < 2; k++) {
       Side& s = *sides[k];
       s = Side{};
-      if (const int rc = finish(es[k], roots[k], s.ops)) return rc;
+      if (const int rc = finish(es[k], roots[k], s.ops, mixed)) return rc;
       const Node& n = t[roots[k]];
       s.scale = cls == XCLASS_DEC ? n.scale : 0;
       s.is_lit = n.op == ORCGPU_AGG_EXPR_LITERAL;

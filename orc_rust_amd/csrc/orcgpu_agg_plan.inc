@@ -333,6 +333,7 @@ inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value*
     if (agg_is_float_sum(in.kind)) {
       v->kind = ORCGPU_AGG_KIND_F64;
       v->f = p.count ? p.f / (double)p.count : 0.0;
+      v->overflow = sticky;  // (an expression of doubles alone: a conversion inside it overflowed a row -- include/orcgpu.h: CONVERSIONS)
     } else if (in.kind == AK_SUM_DEC || in.kind == AK_EXPR_DEC) {
       v->kind = ORCGPU_AGG_KIND_DEC128;
       v->scale_or_unit = in.scale + 4 < 38 ? in.scale + 4 : 38;
@@ -378,6 +379,7 @@ inline void agg_finish(const AggInsn& in, const AggPartial& p, orcgpu_agg_value*
       v->kind = ORCGPU_AGG_KIND_F64;
       v->is_null = p.count == 0;
       v->f = p.f;
+      v->overflow = sticky;  // (AK_EXPR_F64 alone sets it: a conversion inside the expression overflowed a row)
       return;
     case AK_MINMAX_INT:
       v->kind = ORCGPU_AGG_KIND_I64;

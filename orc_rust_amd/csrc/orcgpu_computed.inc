@@ -120,7 +120,7 @@ int computed_enqueue(orcgpu_ctx* ctx, hipStream_t st, orcgpu_result* r, const or
   if (n_segs) memcpy(host.data() + tab.o_segs, sel->data(), n_segs * sizeof(SelBatch));
   HIP_TRY(ctx, ctx->upload(T, host.data(), host.size(), st));
   const uint64_t n_words = (uint64_t)r->n_batches * r->words_per_batch;
-  hipLaunchKernelGGL(agg_ops_hold_conditional(plan.ops.data(), plan.ops.size()) ? compute_columns_cond_kernel : agg_ops_hold_division(plan.ops.data(), plan.ops.size()) ? compute_columns_div_kernel : compute_columns_kernel, dim3((uint32_t)((n_words + 3) / 4), (uint32_t)n), dim3(256), 0, st, reinterpret_cast<const ComputeJob*>(T + tab.o_jobs),
+  hipLaunchKernelGGL(agg_ops_hold_conversion(plan.ops.data(), plan.ops.size()) ? compute_columns_conv_kernel : agg_ops_hold_conditional(plan.ops.data(), plan.ops.size()) ? compute_columns_cond_kernel : agg_ops_hold_division(plan.ops.data(), plan.ops.size()) ? compute_columns_div_kernel : compute_columns_kernel, dim3((uint32_t)((n_words + 3) / 4), (uint32_t)n), dim3(256), 0, st, reinterpret_cast<const ComputeJob*>(T + tab.o_jobs),
                      reinterpret_cast<const FilterCol*>(T + tab.o_cols), (uint32_t)n_file, r->n_rows, r->n_batches, r->batch, r->words_per_batch,
                      reinterpret_cast<const SelBatch*>(T + tab.o_segs), (uint32_t)n_segs, sel ? 0u : 1u);
   HIP_TRY(ctx, hipGetLastError());

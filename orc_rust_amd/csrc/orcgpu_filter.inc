@@ -176,7 +176,7 @@ int filter_run_eval(FilterCall& f, const FilterWorkspace& ws) {
     HIP_TRY(ctx, hipGetLastError());
   }
   if (n_expr) {  // ... and the two sides of the expression leaves, compared: a T and an F plane each
-    hipLaunchKernelGGL(orcgpu_host::filter_plan_holds_conditional(plan) ? filter_expr_cond_kernel : orcgpu_host::filter_plan_holds_division(plan) ? filter_expr_div_kernel : filter_expr_kernel, dim3(eval_blocks, n_expr), dim3(256), 0, st, d_prog, n_insn, d_leaves + n_like + n_set, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in,
+    hipLaunchKernelGGL(orcgpu_host::filter_plan_holds_conversion(plan) ? filter_expr_conv_kernel : orcgpu_host::filter_plan_holds_conditional(plan) ? filter_expr_cond_kernel : orcgpu_host::filter_plan_holds_division(plan) ? filter_expr_div_kernel : filter_expr_kernel, dim3(eval_blocks, n_expr), dim3(256), 0, st, d_prog, n_insn, d_leaves + n_like + n_set, d_lits, d_cols, d_segs, d_first, n_segs, f.n_in,
                        f.B, f.W, d_planes, n_planes, f.at<unsigned long long>(ws.o_overflow));
     HIP_TRY(ctx, hipGetLastError());
   }

@@ -33,7 +33,8 @@ static_assert(ORCGPU_PRED_CMP_EXPR == 19 && ORCGPU_PRED_EXPR_COLUMN == 20 && ORC
                   ORCGPU_PRED_EXPR_COALESCE - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_COALESCE && ORCGPU_PRED_EXPR_ABS - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_ABS &&
                   ORCGPU_PRED_EXPR_NULL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NULL && ORCGPU_PRED_EXPR_CMP - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_CMP &&
                   ORCGPU_PRED_EXPR_IS_NULL - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_IS_NULL && ORCGPU_PRED_EXPR_AND - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_AND &&
-                  ORCGPU_PRED_EXPR_OR - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_OR && ORCGPU_PRED_EXPR_NOT - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NOT,
+                  ORCGPU_PRED_EXPR_OR - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_OR && ORCGPU_PRED_EXPR_NOT - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_NOT &&
+                  ORCGPU_PRED_EXPR_CAST - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_CAST && ORCGPU_PRED_EXPR_TRUNC - ORCGPU_PRED_EXPR_COLUMN == ORCGPU_AGG_EXPR_TRUNC,
               "the expression leaf of include/orcgpu.h: its nodes are the expression aggregates', 20 further on");
 static_assert((int)FXC_INT == (int)XCLASS_INT && (int)FXC_DEC == (int)XCLASS_DEC && (int)FXC_FLOAT == (int)XCLASS_FLOAT && sizeof(AggExprOp) == kExprOpBytes, "filter_program.h: an expression leaf's blob");
 static_assert(kLikeMaxBytes == ORCGPU_LIKE_MAX_BYTES && kLikeMaxParts == ORCGPU_LIKE_MAX_PARTS, "the LIKE limits of include/orcgpu.h are the kernel's");
@@ -297,6 +298,7 @@ struct FilterCompiler {
       case ORCGPU_PRED_EXPR_DATE_PART: case ORCGPU_PRED_EXPR_DIV: case ORCGPU_PRED_EXPR_FLOOR_DIV: case ORCGPU_PRED_EXPR_MOD:
       case ORCGPU_PRED_EXPR_IF: case ORCGPU_PRED_EXPR_COALESCE: case ORCGPU_PRED_EXPR_ABS: case ORCGPU_PRED_EXPR_NULL: case ORCGPU_PRED_EXPR_CMP:
       case ORCGPU_PRED_EXPR_IS_NULL: case ORCGPU_PRED_EXPR_AND: case ORCGPU_PRED_EXPR_OR: case ORCGPU_PRED_EXPR_NOT:
+      case ORCGPU_PRED_EXPR_CAST: case ORCGPU_PRED_EXPR_ROUND: case ORCGPU_PRED_EXPR_FLOOR: case ORCGPU_PRED_EXPR_CEIL: case ORCGPU_PRED_EXPR_TRUNC:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node stands outside an expression comparison%s (node %lld)", "", (long long)at - 1);
       case ORCGPU_PRED_LITERAL:
         return fail(ORCGPU_INVALID_ARGUMENT, "row filter: a literal node stands outside an IN list%s (node %lld)", "", (long long)at - 1);
@@ -319,6 +321,8 @@ struct FilterCompiler {
       case ORCGPU_PRED_EXPR_COALESCE: case ORCGPU_PRED_EXPR_CMP: case ORCGPU_PRED_EXPR_AND: case ORCGPU_PRED_EXPR_OR: kids = 2; break;
       case ORCGPU_PRED_EXPR_ABS: case ORCGPU_PRED_EXPR_IS_NULL: case ORCGPU_PRED_EXPR_NOT: kids = 1; break;
       case ORCGPU_PRED_EXPR_NULL: kids = 0; break;
+      // the conversions (a CAST's target travels in value_type and `i`, a ROUND's digits in `i`, below)
+      case ORCGPU_PRED_EXPR_CAST: case ORCGPU_PRED_EXPR_ROUND: case ORCGPU_PRED_EXPR_FLOOR: case ORCGPU_PRED_EXPR_CEIL: case ORCGPU_PRED_EXPR_TRUNC: kids = 1; break;
       default: return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression holds expression nodes only%s (node op %lld)", "", n.op);
     }
     if (n.n_children != kids) return fail(ORCGPU_INVALID_ARGUMENT, "row filter: an expression node with the wrong number of children%s (%lld)", "", n.n_children);
@@ -686,6 +690,8 @@ inline bool filter_plan_holds(const FilterPlan& plan, bool (*holds)(const AggExp
 inline bool filter_plan_holds_division(const FilterPlan& plan) { return filter_plan_holds(plan, agg_ops_hold_division); }
 // ... a conditional?  (filter_expr_cond_kernel, which has the divide too.)
 inline bool filter_plan_holds_conditional(const FilterPlan& plan) { return filter_plan_holds(plan, agg_ops_hold_conditional); }
+// ... a conversion?  (filter_expr_conv_kernel, the mixed interpreter.)
+inline bool filter_plan_holds_conversion(const FilterPlan& plan) { return filter_plan_holds(plan, agg_ops_hold_conversion); }
 
 // `from`, a plan compiled on its own against the same columns, behind `into`: its instructions behind into's, its literals behind
 // into's from an 8-byte boundary (what the IN tables and the LIKE patterns are aligned to), its mask planes numbered behind

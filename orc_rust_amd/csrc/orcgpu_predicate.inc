@@ -583,6 +583,7 @@ struct PredEval {
                         // ... and the conditionals, never pruned through for the same reason
                         : n.op == ORCGPU_PRED_EXPR_IF ? 3 : n.op == ORCGPU_PRED_EXPR_NULL ? 0
                         : n.op == ORCGPU_PRED_EXPR_ABS || n.op == ORCGPU_PRED_EXPR_IS_NULL || n.op == ORCGPU_PRED_EXPR_NOT ? 1
+                        : n.op >= ORCGPU_PRED_EXPR_CAST && n.op <= ORCGPU_PRED_EXPR_TRUNC ? 1  // (the conversions: never pruned through either)
                         : n.op == ORCGPU_PRED_EXPR_COALESCE || n.op == ORCGPU_PRED_EXPR_CMP || n.op == ORCGPU_PRED_EXPR_AND || n.op == ORCGPU_PRED_EXPR_OR ? 2 : ~0u;
     if (kids == ~0u || n.n_children != kids) return 0;
     size_t next = at + 1;

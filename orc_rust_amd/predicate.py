@@ -15,6 +15,9 @@ EXPR_DATE_PART = 36  # ... aggregate.EXPR_DATE_PART + 20: one child, the part in
 EXPR_DIV, EXPR_FLOOR_DIV, EXPR_MOD = 37, 38, 39  # ... aggregate.EXPR_DIV .. EXPR_MOD + 20: two children; DIV: the result scale, or -1, in `i`
 # ... aggregate.EXPR_IF .. EXPR_NOT + 20: the conditionals (3, 2, 1, 0, 2, 1, 2, 2, 1 children; CMP: the comparison EQ .. GE in `i`)
 EXPR_IF, EXPR_COALESCE, EXPR_ABS, EXPR_NULL, EXPR_CMP, EXPR_IS_NULL, EXPR_AND, EXPR_OR, EXPR_NOT = range(41, 50)
+# ... aggregate.EXPR_CAST .. EXPR_TRUNC + 20: the conversions, one child each (CAST: the target in value_type, a Decimal's scale in `i`;
+# ROUND: the digits in `i`)
+EXPR_CAST, EXPR_ROUND, EXPR_FLOOR, EXPR_CEIL, EXPR_TRUNC = range(50, 55)
 _CMP_OPS = {"=": EQ, "!=": NE, "<": LT, "<=": LE, ">": GT, ">=": GE}
 _CMP_SIGNS = {v: k for k, v in _CMP_OPS.items()}
 PV_BOOLEAN, PV_INT8, PV_INT16, PV_INT32, PV_INT64, PV_FLOAT32, PV_FLOAT64, PV_UTF8, PV_DECIMAL128, PV_TIMESTAMP_NS = range(10)
@@ -293,6 +296,11 @@ class Predicate:
                 n.i = -1 if e.scale is None else e.scale
             elif e.op + EXPR_COLUMN == EXPR_CMP:
                 n.i = e.cmp
+            elif e.op + EXPR_COLUMN == EXPR_CAST:
+                n.value_type = e.value_type
+                n.i = e.scale if e.value_type == PV_DECIMAL128 else 0
+            elif e.op + EXPR_COLUMN == EXPR_ROUND:
+                n.i = e.scale
             out.append(n)
             for c in e.children:
                 walk_expr(c)
